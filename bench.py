@@ -47,11 +47,10 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent
 sys.path.insert(0, str(ROOT))
-# The library overlaps up to eight trace launches on streams of its own; the HIP runtime maps streams onto FOUR hardware
-# queues unless told otherwise, and lanes that share a queue wait for each other (depth_for; an
-# integrator exports the same). It has to be in the environment before the runtime starts, i.e. before
-# torch is imported; a value the user exported is left alone.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+# The number of hardware queues the HIP runtime maps streams onto is the environment's (the library plans its frame pipeline
+# for what it finds, api.cpp depth_for); bench.py leaves it as the caller has it.
+HW_QUEUES_VAR = "GPU_MAX_HW_QUEUES"
+RUNTIME_DEFAULT_QUEUES = 4  # what the HIP runtime uses when the variable is not set
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s (spec)
 TRI_ALG_BYTES = 36     # the 9 fp32 SoA values Moller-Trumbore reads per triangle (triangle.rs:177-187)
@@ -72,19 +71,21 @@ INT_FULL_FRAC = 0.58  # of the binary's integer VALU instructions, those that is
 ISSUE_COST = {"valu_mean": 0.62 * 2.0 + 0.355 * 3.1 + 0.025 * 6.1, "salu": 2.0, "lds": 6.0, "vmem": 4.0}
 
 
-def pipeline_note(asked):
-    """What the library does with the frame pipeline (api.cpp depth_for / grid_for), for the JSON line."""
+def pipeline_note(asked, queues=None):
+    """What the library does with the frame pipeline (api.cpp depth_for / grid_for), for the JSON line. queues: the hardware
+    queues the library plans for (default: as the environment has them)."""
     if asked == 1:
         return "1 (no overlap between steps)"
-    try:
-        queues = int(os.environ.get("GPU_MAX_HW_QUEUES", "4"))
-    except ValueError:
-        queues = 4
+    if queues is None:
+        try:
+            queues = int(os.environ.get(HW_QUEUES_VAR) or RUNTIME_DEFAULT_QUEUES)
+        except ValueError:
+            queues = RUNTIME_DEFAULT_QUEUES
     depth = asked or (8 if queues >= 8 else 4)
     side = max(2, min(depth, queues))
     per_cu = -(-24 // side)
     return (f"{asked or f'auto: {depth}'} trace launches in flight, {min(depth, queues)} side by side on {per_cu}{' (4 for launches of 8 M work items or more)' if per_cu < 4 else ''} "
-            f"of a CU's 16 wave slots each while they overlap; GPU_MAX_HW_QUEUES={os.environ.get('GPU_MAX_HW_QUEUES')}")
+            f"of a CU's 16 wave slots each while they overlap; {HW_QUEUES_VAR}={os.environ.get(HW_QUEUES_VAR)}")
 
 
 def open_step_counters(dist, np, rank, world, guarded, timeout_s, failed=False):
@@ -237,7 +238,39 @@ def parse_args():
     ap.add_argument("--rehearse-single-gpu", action="store_true",
                     help="N > 1 ranks all on cuda:0 with a gloo gather through host memory: exercises the sharded "
                          "path on a one-GPU box; its numbers mean nothing")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the timed path computed in its last timed step (rank 0's fp32 radiance) as DIR/<name>.npy "
+                         "(at most 64 MB: a fixed, seeded sample of the pixels of a larger frame)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_outputs and args.emulate_all:
+        ap.error("--dump-outputs has no single timed path to dump with --emulate-all")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, np, radiance):
+    """Writes the last timed step's output under out_dir: radiance.npy (float32, the whole frame as the caller's buffer holds
+    it), or, when that would pass DUMP_LIMIT_BYTES, radiance_sample.npy (float32 rows of a fixed, seeded sample of the pixels)
+    with radiance_sample_index.npy (float64: each row's flat pixel index). Returns {name: shape}."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    radiance = np.ascontiguousarray(radiance, dtype=np.float32)
+    if radiance.nbytes <= DUMP_LIMIT_BYTES:
+        arrays = {"radiance": radiance}
+    else:
+        px = radiance.reshape(-1, 3)
+        k = DUMP_LIMIT_BYTES // (3 * 4 + 8)
+        idx = np.sort(np.random.default_rng(0).choice(px.shape[0], size=k, replace=False))
+        arrays = {"radiance_sample": px[idx], "radiance_sample_index": idx.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def launch_ranks(n):
@@ -597,6 +630,11 @@ def main():
         gather_mode[0] = "ipc" if gather_probe["ipc"] < gather_probe["rccl"] else "rccl"
     elapsed, enqueue_s, trace_ms, resolve_ms, n_launches, (mix_full, mix_half) = guarded(lambda: timed_leg(args.warmup, args.steps, True))
     helpers_timed = helpers_issued[0]
+    last_timed_output = None
+    if args.dump_outputs and rank == 0:  # (untimed: the fence at the end of the leg has run; the legs below overwrite `image`)
+        last_timed_output = image.cpu().numpy()
+        if emu:  # an emulated rank's share: its packed tiles lead the buffer, the rest was never written
+            last_timed_output = last_timed_output.reshape(-1)[:rbrt_amd.packed_pixels(W, H, args.emulate_rank, emu) * 3].reshape(-1, 3)
     scene.check()  # a NaN sphere discriminant (sphere.rs:33 panics) or corrupt path state fails the run loudly
     # per-rank split of a step (N > 1): spans on this rank's streams, means over the timed steps
     phases = None
@@ -945,6 +983,9 @@ def main():
             out["cpu_baseline"]["rmse"] = float(np.sqrt(np.mean((gpu.astype(np.float64) - cpu) ** 2)))
     if dbg is not None:
         out["debug_counters"] = dbg
+    if last_timed_output is not None:
+        out["dumped_outputs"] = {"dir": str(args.dump_outputs), "arrays": dump_outputs(args.dump_outputs, np_mod, last_timed_output),
+                                 "what": f"the fp32 radiance of timed step {args.steps} of {args.steps}"}
     print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()

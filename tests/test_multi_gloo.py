@@ -117,9 +117,9 @@ def test_pipeline_note_follows_the_hardware_queues(monkeypatch):
     import sys
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import bench
-    monkeypatch.setenv("GPU_MAX_HW_QUEUES", "8")
-    assert bench.pipeline_note(0).startswith("auto: 8 trace launches in flight, 8 side by side on 3 (4 for launches of 8 M")
-    monkeypatch.delenv("GPU_MAX_HW_QUEUES")
+    assert bench.pipeline_note(0, queues=8).startswith("auto: 8 trace launches in flight, 8 side by side on 3 (4 for launches of 8 M")
+    assert bench.pipeline_note(0, queues=2).startswith("auto: 4 trace launches in flight, 2 side by side on 12 of a CU")
+    monkeypatch.delenv(bench.HW_QUEUES_VAR, raising=False)
     assert bench.pipeline_note(0).startswith("auto: 4 trace launches in flight, 4 side by side on 6 of a CU")
     assert bench.pipeline_note(1) == "1 (no overlap between steps)"
 

@@ -2,7 +2,6 @@
 import os, sys, time, tempfile
 from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent; sys.path.insert(0, str(ROOT))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import rbrt_amd
 from rbrt_amd import abi, standin
 import ctypes as C

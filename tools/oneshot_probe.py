@@ -5,7 +5,6 @@ import os, sys, time
 from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT)); sys.path.insert(0, str(ROOT / "tests"))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import numpy as np
 import rbrt_amd
 import scenes

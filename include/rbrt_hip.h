@@ -49,7 +49,9 @@ extern "C" {
 #endif
 
 #define RBRT_ABI_VERSION 2 /* 2: rbrt_scene_t grew n_triangles / triangles / element_order (appended: the v1 prefix is unchanged);
-                              entry points added since (rbrt_hip_tile_xy / _tile_number) change no struct and no existing call */
+                              entry points added since (rbrt_hip_tile_xy / _tile_number) change no struct and no existing call;
+                              neither do RBRT_MAT_EMISSIVE and RBRT_FLAG_CONSTANT_BACKGROUND, added since (a library without
+                              them answers a kind-3 material with RBRT_ERR_INVALID_ARG) */
 
 typedef enum rbrt_status {
     RBRT_OK = 0,
@@ -62,17 +64,24 @@ typedef enum rbrt_status {
 } rbrt_status_t;
 
 /* Material = the closed set the reference's YAML factory can build
- * (blueprints.rs:50-74); replaces `Box<dyn RayScattering + Sync>` (materials.rs:4-12). */
+ * (blueprints.rs:50-74); replaces `Box<dyn RayScattering + Sync>` (materials.rs:4-12).
+ * Emissive (no counterpart in the reference, whose only light is the background): a surface that emits radiance
+ * `albedo` (linear, per channel, values above 1 allowed) from both sides and scatters nothing. Scene::hit treats it like
+ * any other object (it occludes); when it is a path's closest hit, colorize returns `albedo` at every remaining depth,
+ * depth 0 included, without drawing a random number, so a sample is a1 * (a2 * (... * (ak * L))) over the albedos of the
+ * scattering bounces before it. scene_create / render reject a non-finite or negative component with
+ * RBRT_ERR_INVALID_ARG. Every other kind value is rejected the same way. */
 typedef enum rbrt_material_kind {
     RBRT_MAT_LAMBERTIAN = 0, /* lambertian.rs:11-24: albedo            */
     RBRT_MAT_METAL = 1,      /* metal.rs:12-25     : albedo, param=roughness */
-    RBRT_MAT_DIELECTRIC = 2  /* dielectric.rs:11-59: param=ref_idx     */
+    RBRT_MAT_DIELECTRIC = 2, /* dielectric.rs:11-59: param=ref_idx     */
+    RBRT_MAT_EMISSIVE = 3    /* albedo = emitted radiance L, param unused */
 } rbrt_material_kind_t;
 
 typedef struct rbrt_material {
     int32_t kind;    /* rbrt_material_kind_t */
-    float albedo[3]; /* ignored for dielectric (attenuation is (1,1,1), dielectric.rs:18) */
-    float param;     /* metal: roughness; dielectric: ref_idx; lambertian: unused */
+    float albedo[3]; /* ignored for dielectric (attenuation is (1,1,1), dielectric.rs:18); emissive: the emitted radiance */
+    float param;     /* metal: roughness; dielectric: ref_idx; lambertian, emissive: unused */
 } rbrt_material_t;
 
 /* sphere.rs:6-10 */
@@ -172,6 +181,11 @@ typedef struct rbrt_render_opts {
 
 #define RBRT_FLAG_NONE 0u
 #define RBRT_FLAG_COLLECT_STATS 1u /* run the counting variant of the kernel (slower); see rbrt_hip_stats_t */
+/* A ray that hits nothing returns `bg` exactly, instead of the reference's sky gradient t*(1,1,1) + (1-t)*bg
+ * (lib.rs:68-71), which is white at the zenith whatever bg is. For dark scenes lit by RBRT_MAT_EMISSIVE objects.
+ * Honoured by rbrt_hip_render, _render_device and _render_pass; every pass of one rbrt_hip_render_pass series must use
+ * the same flag and bg, as it must use the same seed. */
+#define RBRT_FLAG_CONSTANT_BACKGROUND 2u
 
 #define RBRT_TILE 8u /* tile edge in pixels used for sharding and work ordering */
 /* How tiles are dealt to ranks. Tile NUMBER t (0 <= t < tiles_x * tiles_y) belongs to rank t % tile_world, and a rank's packed

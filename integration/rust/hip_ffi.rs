@@ -7,7 +7,9 @@
 use std::os::raw::{c_char, c_int};
 
 #[repr(C)] #[derive(Copy, Clone)]
-pub struct RbrtMaterial { pub kind: i32, pub albedo: [f32; 3], pub param: f32 }   // 0 lambertian, 1 metal, 2 dielectric
+pub struct RbrtMaterial { pub kind: i32, pub albedo: [f32; 3], pub param: f32 }   // 0 lambertian, 1 metal, 2 dielectric, 3 emissive
+pub const RBRT_MAT_EMISSIVE: i32 = 3;                  // albedo = emitted radiance (no counterpart in the reference)
+pub const RBRT_FLAG_CONSTANT_BACKGROUND: u32 = 2;      // RbrtRenderOpts::flags: rays that hit nothing return `bg`
 #[repr(C)] #[derive(Copy, Clone)]
 pub struct RbrtSphere { pub center: [f32; 3], pub radius: f32, pub mat: RbrtMaterial }
 #[repr(C)]

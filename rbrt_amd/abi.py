@@ -28,8 +28,10 @@ RBRT_ERR_NAN = -6
 MAT_LAMBERTIAN = 0
 MAT_METAL = 1
 MAT_DIELECTRIC = 2
+MAT_EMISSIVE = 3  # albedo = emitted radiance
 
 FLAG_COLLECT_STATS = 1
+FLAG_CONSTANT_BACKGROUND = 2  # rays that hit nothing return opts.bg instead of the sky gradient
 TILE = 8
 
 f32p = C.POINTER(C.c_float)

@@ -765,9 +765,15 @@ void adopt_refined(rbrt_hip_scene* s) {
     r->state.store(2, std::memory_order_release);
 }
 
-int check_material(const rbrt_material_t& m) {
-    if (m.kind < RBRT_MAT_LAMBERTIAN || m.kind > RBRT_MAT_DIELECTRIC)
+// `what`, `index`: the object the material belongs to, for the message.
+int check_material(const rbrt_material_t& m, const char* what, size_t index) {
+    if (m.kind < RBRT_MAT_LAMBERTIAN || m.kind > RBRT_MAT_EMISSIVE)
         return fail(RBRT_ERR_INVALID_ARG, "unknown material kind");
+    if (m.kind == RBRT_MAT_EMISSIVE)
+        for (int c = 0; c < 3; ++c)
+            if (!std::isfinite(m.albedo[c]) || m.albedo[c] < 0.0f)
+                return fail(RBRT_ERR_INVALID_ARG, std::string("emissive material of ") + what + " " + std::to_string(index) +
+                                                      ": the emitted radiance (albedo) must be finite and >= 0");
     return RBRT_OK;
 }
 
@@ -780,6 +786,7 @@ int fill_trace_params(const rbrt_hip_scene* s, const rbrt_camera_t* cam, const r
     P.eps_frac = 1.0f / o->min_dist;  // triangle.rs:146
     for (int k = 0; k < 3; ++k) P.bg[k] = o->bg[k];
     P.max_depth = o->max_depth;
+    P.constant_bg = (o->flags & RBRT_FLAG_CONSTANT_BACKGROUND) ? 1u : 0u;
     P.seed_key = host_splitmix64(o->seed);
     P.n_spheres = s->n_spheres;
     P.n_meshes = s->n_meshes;
@@ -923,9 +930,9 @@ int scene_create_impl(const rbrt_scene_t* scene, int device, rbrt_hip_scene_t** 
     if (uint64_t(scene->n_spheres) + scene->n_triangles + scene->n_meshes > uint64_t(kMaxObjects))
         return fail(RBRT_ERR_UNSUPPORTED, "more than 255 objects (spheres + triangles + meshes) in one scene");
     for (uint32_t i = 0; i < scene->n_spheres; ++i)
-        if (int rc = check_material(scene->spheres[i].mat)) return rc;
+        if (int rc = check_material(scene->spheres[i].mat, "sphere", i)) return rc;
     for (uint32_t i = 0; i < scene->n_triangles; ++i)
-        if (int rc = check_material(scene->triangles[i].mat)) return rc;
+        if (int rc = check_material(scene->triangles[i].mat, "triangle", i)) return rc;
     // Scene::elements order: the given one (every sphere and triangle exactly once), else spheres then triangles
     const uint32_t n_elem = scene->n_spheres + scene->n_triangles;
     std::vector<uint32_t> elems(n_elem);
@@ -942,7 +949,7 @@ int scene_create_impl(const rbrt_scene_t* scene, int device, rbrt_hip_scene_t** 
     }
     for (uint32_t i = 0; i < scene->n_meshes; ++i) {
         const rbrt_mesh_t& m = scene->meshes[i];
-        if (int rc = check_material(m.mat)) return rc;
+        if (int rc = check_material(m.mat, "mesh", i)) return rc;
         // The BVH is at most kMaxBvhDepth + 1 inner levels deep with <= kLeafMax triangles per leaf: 4 << 21 =
         // 8,388,608 triangles is what always fits, whatever their arrangement (bvh.cpp capacity()).
         if (m.n_total > (4u << (kMaxBvhDepth + 1)))
@@ -998,7 +1005,7 @@ int scene_create_impl(const rbrt_scene_t* scene, int device, rbrt_hip_scene_t** 
     auto put_mat = [&](size_t k, const rbrt_material_t& m) {
         for (int c = 0; c < 3; ++c) mats[k].albedo[c] = m.albedo[c];
         mats[k].param = m.param;
-        mats[k].kind = m.kind;
+        mats[k].kind = dev_material_kind(m.kind);
     };
     // A scene WITHOUT triangle elements is tested by the kernels' sphere-only loop, where element e IS device sphere e (no
     // element table is uploaded): the device array is therefore laid out in Scene::elements order, so that a permuted
@@ -2124,9 +2131,9 @@ int rbrt_hip_debug_scatter(const rbrt_material_t* mats, const float* in_dir, con
     if (!mats || !in_dir || !p || !normal || !rng_state) return fail(RBRT_ERR_INVALID_ARG, "debug_scatter: null argument");
     std::vector<DevMaterial> hm(n);
     for (size_t i = 0; i < n; ++i) {
-        if (int rc = check_material(mats[i])) return rc;
+        if (int rc = check_material(mats[i], "event", i)) return rc;
         for (int c = 0; c < 3; ++c) hm[i].albedo[c] = mats[i].albedo[c];
-        hm[i].param = mats[i].param, hm[i].kind = mats[i].kind;
+        hm[i].param = mats[i].param, hm[i].kind = dev_material_kind(mats[i].kind);
     }
     if (int rc = ensure_device(0)) return rc;
     DevMaterial* d_m = nullptr;

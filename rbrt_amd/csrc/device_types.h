@@ -95,8 +95,12 @@ struct DevTriangle {
 struct DevMaterial {
     float albedo[3];
     float param;
-    int32_t kind;
+    int32_t kind;  // rbrt_material_kind_t, except that an emitter is stored as kDevMatEmissive
 };
+// Device code of RBRT_MAT_EMISSIVE. The megakernel's classify() turns a hit into status ST_LAMB + kind, and ST_LAMB - 1 is
+// ST_TERM: an emitter's hit ends its path without a compare in the kernel (the TERM pass then starts the fold from L).
+constexpr int32_t kDevMatEmissive = -1;
+RBRT_HOST_DEVICE inline int32_t dev_material_kind(int32_t kind) { return kind == RBRT_MAT_EMISSIVE ? kDevMatEmissive : kind; }
 
 struct DevMesh {
     const BvhNode4* nodes;
@@ -130,6 +134,7 @@ struct TraceParams {
     float min_dist, max_dist, eps_frac;  // eps_frac = 1/min_dist (triangle.rs:146)
     float bg[3];
     uint32_t max_depth;
+    uint32_t constant_bg;  // RBRT_FLAG_CONSTANT_BACKGROUND: a ray that hits nothing returns bg (in the padding ahead of seed_key)
     uint64_t seed_key;  // splitmix64(seed)
     uint32_t n_spheres, n_meshes;
     uint32_t n_elem_tris;          // BasicTriangle elements (rbrt_scene_t::triangles)

@@ -602,8 +602,8 @@ __device__ __forceinline__ bool refract(V3 dir, V3 n, float ni_over_nt, V3& out)
     return false;
 }
 
-// RayScattering::scatter for the three materials. Returns the reference's bool; `records`
-// says whether the attenuation is anything other than the exact identity (1,1,1).
+// RayScattering::scatter for the three materials that scatter (not for an emitter: callers never pass one). Returns the
+// reference's bool; `records` says whether the attenuation is anything other than the exact identity (1,1,1).
 __device__ __forceinline__ bool scatter(const DevMaterial& m, V3 in_d, V3 p, V3 n, Rng& rng, V3& out_d) {
     if (m.kind == RBRT_MAT_LAMBERTIAN) {  // lambertian.rs:11-24
         V3 target = (p + normalize(n)) + random_point_in_unit_sphere(rng);
@@ -648,7 +648,9 @@ __device__ __forceinline__ V3 camera_ray_direction(V3 pos, V3 center, V3 right, 
 }
 
 // lib.rs:68-71: what a ray that hits nothing sees; the direction as it is (not re-normalised).
-__device__ __forceinline__ V3 background(float dy, const float* bg) {
+// `constant` (RBRT_FLAG_CONSTANT_BACKGROUND): bg itself.
+__device__ __forceinline__ V3 background(float dy, const float* bg, uint32_t constant) {
+    if (constant) return mk(bg);
     const float t = 0.5f * (dy + 1.0f);
     return t * mk(1.0f, 1.0f, 1.0f) + (1.0f - t) * mk(bg);
 }
@@ -791,7 +793,7 @@ __global__ __launch_bounds__(kSmallBlock) void sky_resolve_kernel(const TracePar
             Rng rng;
             rng.init(P.seed_key, row * R.width + col, P.sample_base + s);
             const V3 d = camera_ray_direction(pos, center, right, up, P.cam.mm_per_pix_hor, P.cam.mm_per_pix_vert, R.width, R.height, row, col, rng);
-            const V3 c = background(d.y, P.bg);
+            const V3 c = background(d.y, P.bg, P.constant_bg);
             ax = ax + c.x;
             ay = ay + c.y;
             az = az + c.z;
@@ -1296,7 +1298,8 @@ __global__ __launch_bounds__(kBlock) void scatter_debug_kernel(const DevMaterial
     if (i >= n) return;
     Rng rng = {rng_state[2 * i], rng_state[2 * i + 1]};
     V3 nd = mk(0.0f, 0.0f, 0.0f);
-    const bool ok = scatter(mats[i], mk(in_dir + 3 * i), mk(p + 3 * i), mk(normal + 3 * i), rng, nd);
+    // an emitter scatters nothing and draws nothing (the megakernel never shades one: classify() ends its path)
+    const bool ok = mats[i].kind != kDevMatEmissive && scatter(mats[i], mk(in_dir + 3 * i), mk(p + 3 * i), mk(normal + 3 * i), rng, nd);
     if (out_dir) out_dir[3 * i] = nd.x, out_dir[3 * i + 1] = nd.y, out_dir[3 * i + 2] = nd.z;
     if (out_ok) out_ok[i] = ok ? 1 : 0;
     if (out_rng_state) out_rng_state[2 * i] = rng.s0, out_rng_state[2 * i + 1] = rng.s1;

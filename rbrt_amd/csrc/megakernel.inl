@@ -89,7 +89,7 @@ static_assert(offsetof(DevMesh, tris) == 8 && offsetof(DevMesh, normals) == 16 &
               "LDS scene table layout");
 // path-generation parameters in LDS (behind the scene tables), as dword indices
 enum { G_POS = 0, G_RIGHT = 3, G_UP = 6, G_CENTER = 9, G_MMH = 12, G_MMV, G_W, G_H, G_BATCH, G_BATCH_MAGIC, G_TILES_X,
-       G_TILES_X_MAGIC, G_TILE_WORLD, G_TILE_RANK, G_N_LOCAL, G_REVERSED, G_SAMPLE_BASE, G_MAX_DEPTH, G_SEED_LO, G_SEED_HI, kGenDw };
+       G_TILES_X_MAGIC, G_TILE_WORLD, G_TILE_RANK, G_N_LOCAL, G_FLAGS, G_SAMPLE_BASE, G_MAX_DEPTH, G_SEED_LO, G_SEED_HI, kGenDw };
 struct SceneLds {
     const float* sph;      // [n_spheres][4]: centre xyz, radius
     const uint32_t* mat;   // [n_elem + n_meshes][5]: albedo xyz, param, kind (n_elem = spheres + BasicTriangle elements)
@@ -123,7 +123,9 @@ __device__ __forceinline__ uint32_t next_gated_mesh(const SceneLds& sc, uint32_t
     return m;
 }
 
-// What has to happen next to a path whose closest hit is known.
+// What has to happen next to a path whose closest hit is known. An emitter's device kind is kDevMatEmissive, which this
+// maps to ST_TERM: its path ends here, at any depth, without a scatter.
+static_assert(uint32_t(ST_LAMB + uint32_t(kDevMatEmissive)) == ST_TERM, "emitters classify as TERM");
 __device__ __forceinline__ uint32_t classify(const SceneLds& sc, int32_t obj, uint32_t depth) {
     if (obj < 0 || depth == 0) return ST_TERM;  // lib.rs:54,68
     return ST_LAMB + sc.mat[uint32_t(obj) * kMatDw + 4];
@@ -330,7 +332,8 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
             dst[G_BATCH] = P.batch, dst[G_BATCH_MAGIC] = P.batch_magic;
             dst[G_TILES_X] = P.tiles_x, dst[G_TILES_X_MAGIC] = P.tiles_x_magic;
             dst[G_TILE_WORLD] = P.tile_world, dst[G_TILE_RANK] = P.tile_rank;
-            dst[G_N_LOCAL] = n_work, dst[G_REVERSED] = P.tiles_reversed;
+            dst[G_N_LOCAL] = n_work, dst[G_FLAGS] = (P.tiles_reversed ? 1u : 0u) | (P.constant_bg ? 2u : 0u);  // (one word: a new one
+            // would take the header card's scene past 16 waves per CU, and reading the kernel argument cost 3 SGPR spills)
             dst[G_SAMPLE_BASE] = P.sample_base, dst[G_MAX_DEPTH] = P.max_depth;
             dst[G_SEED_LO] = uint32_t(P.seed_key), dst[G_SEED_HI] = uint32_t(P.seed_key >> 32);
         }
@@ -858,7 +861,11 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                 nrec = (meta >> 7) & 127u;
                 const int32_t obj = int32_t((meta >> 14) & 255u) - 1;
                 V3 color = mk(0.0f, 0.0f, 0.0f);  // hit with depth 0 or a failed scatter: lib.rs:63-66
-                if (obj < 0) color = background(__uint_as_float(POOL(F_DY, slot)), P.bg);  // lib.rs:68-71
+                if (obj < 0) {
+                    color = background(__uint_as_float(POOL(F_DY, slot)), P.bg, gp[G_FLAGS] & 2u);  // lib.rs:68-71
+                } else if (int32_t(sc.mat[uint32_t(obj) * kMatDw + 4]) == kDevMatEmissive) {
+                    color = mk(reinterpret_cast<const float*>(sc.mat + uint32_t(obj) * kMatDw));  // an emitter: its radiance L
+                }
                 if (nrec != 0) {  // lib.rs:62: attenuation * colorize(...), innermost bounce first
                     word = POOL(F_WORD, slot);
                     for (uint32_t k = nrec; k-- > 0;) {
@@ -925,7 +932,7 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                         const uint32_t batch = gp[G_BATCH];
                         const uint32_t tpos = div_magic(ts, batch, gp[G_BATCH_MAGIC]);
                         const uint32_t s = ts - tpos * batch;
-                        const uint32_t widx = gp[G_REVERSED] ? gp[G_N_LOCAL] - 1u - tpos : tpos;  // row-major, either way
+                        const uint32_t widx = (gp[G_FLAGS] & 1u) ? gp[G_N_LOCAL] - 1u - tpos : tpos;  // row-major, either way
                         item = s * npix + widx * 64u + pp;                       // < 2^32: the host sizes batches so
                         // the launch's tiles: all of the rank's, or those the tile pass left (TraceParams::tile_lists)
                         const uint32_t tile_local = P.tile_lists ? P.tile_lists[kTileListHeader + widx] : widx;

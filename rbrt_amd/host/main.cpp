@@ -2,9 +2,11 @@
 //   -t/--target_file dbg_out.png   --height 600   -w/--width 800
 //   -c/--config scenes/example_scene.yaml   -s/--samples 5   -h/--help   -V/--version
 // plus, not in the reference: --seed N (default 1), --gpus N (default 1), --gather host|rccl, --oversubscribe,
-// --pass-samples N, --checkpoint FILE, --checkpoint-every N, --report FILE (machine-readable timing of the run).
+// --pass-samples N, --checkpoint FILE, --checkpoint-every N, --report FILE (machine-readable timing of the run),
+// --background R,G,B (a constant background instead of the reference's sky gradient).
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -34,6 +36,8 @@ void usage() {
         "      --pass-samples <n>           samples per pass (a progress line, and a checkpoint, per pass) [default: automatic]\n"
         "      --checkpoint <file>          write the running per-pixel sums there after passes and resume from it\n"
         "      --checkpoint-every <n>       checkpoint after every n-th pass [default: 1]\n"
+        "      --background <r,g,b>         constant linear background radiance of rays that hit nothing, e.g. 0,0,0 for a scene\n"
+        "                                   lit by emissive objects only [default: the sky gradient]\n"
         "  -h, --help                       Print help\n"
         "  -V, --version                    Print version\n");
 }
@@ -64,6 +68,24 @@ bool parse_u32(const char* s, uint32_t& out) {
     return true;
 }
 
+// "R,G,B": three finite, non-negative floats
+bool parse_rgb(const char* s, float out[3]) {
+    const char* p = s;
+    for (int c = 0; c < 3; ++c) {
+        char* end = nullptr;
+        const float v = std::strtof(p, &end);
+        if (end == p || !std::isfinite(v) || v < 0.0f) return false;
+        out[c] = v;
+        if (c < 2) {
+            if (*end != ',') return false;
+            p = end + 1;
+        } else if (*end != '\0') {
+            return false;
+        }
+    }
+    return true;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -71,7 +93,8 @@ int main(int argc, char** argv) {
     uint32_t height = 600, width = 800, samples = 5, gpus = 1, pass_samples = 0, checkpoint_every = 1;
     std::string gather = "host", checkpoint, report_path;
     unsigned long long seed = 1;
-    bool oversubscribe = false;
+    bool oversubscribe = false, constant_background = false;
+    float background[3] = {0.0f, 0.0f, 0.0f};
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         std::string val;
@@ -131,6 +154,13 @@ int main(int argc, char** argv) {
             oversubscribe = true;
         } else if (a == "--report") {
             report_path = value();
+        } else if (a == "--background") {
+            const char* v = value();
+            if (!parse_rgb(v, background)) {
+                std::fprintf(stderr, "error: invalid value '%s' for '--background' (expected R,G,B: three non-negative numbers)\n", v);
+                return 2;
+            }
+            constant_background = true;
         } else if (a == "--seed") {
             seed = std::strtoull(value(), nullptr, 10);
         } else {
@@ -160,6 +190,8 @@ int main(int argc, char** argv) {
         cfg.checkpoint_path = checkpoint;
         cfg.checkpoint_every = int(checkpoint_every);
         cfg.gather = gather;
+        cfg.constant_background = constant_background;
+        for (int c = 0; c < 3; ++c) cfg.background[c] = background[c];
         rbrt::ImageBuffer img = rbrt::render_scene(cam, samples, scene, cfg);
         std::printf("Saving rendered image to %s\n", target.c_str());
         const auto t3 = clock::now();

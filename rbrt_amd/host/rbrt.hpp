@@ -76,6 +76,7 @@ struct Material {
     static Material lambertian(Vec3 albedo);
     static Material metal(Vec3 albedo, float roughness);
     static Material dielectric(float ref_idx);
+    static Material emissive(Vec3 radiance);  // RBRT_MAT_EMISSIVE: emits `radiance`, scatters nothing
 };
 // None when the type string matches none of metal / lambert / dielectric (the object is dropped).
 std::optional<Material> create_material_from_description(const std::string& mat_type, std::optional<Vec3> albedo,
@@ -214,6 +215,8 @@ struct RenderConfig {  // additions that the reference hard-codes or lacks
     std::string gather = "host";
     bool oversubscribe = false;       // rank r runs on device r % n_devices (rehearsal of N ranks on fewer GPUs; host gather only)
     RenderReport* report = nullptr;   // filled in when not null
+    bool constant_background = false; // RBRT_FLAG_CONSTANT_BACKGROUND: escaped rays return `background` (the CLI's --background)
+    float background[3] = {0.0f, 0.0f, 0.0f};
 };
 // rbrt_lib::render_scene (lib.rs:75-79): blocks until the image is complete. Runs on the GPU(s)
 // through the C ABI; there is no CPU path.

@@ -144,6 +144,10 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
     rbrt_render_opts_default(&opts);
     opts.spp = num_samples;
     opts.seed = cfg.seed;
+    if (cfg.constant_background) {
+        opts.flags |= RBRT_FLAG_CONSTANT_BACKGROUND;
+        for (int c = 0; c < 3; ++c) opts.bg[c] = cfg.background[c];
+    }
 
     ImageBuffer img;
     img.width = cam.img_width_pix;
@@ -190,6 +194,10 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
     want.width = img.width, want.height = img.height, want.spp = num_samples, want.world = uint32_t(world);
     want.seed = cfg.seed;
     want.fingerprint = cfg.checkpoint_path.empty() ? 0 : scene_fingerprint(c, view.scene);
+    if (want.fingerprint != 0 && cfg.constant_background) {  // (only then: a default run keeps its checkpoints' fingerprint)
+        want.fingerprint = fnv1a(&opts.flags, sizeof(opts.flags), want.fingerprint);
+        want.fingerprint = fnv1a(opts.bg, sizeof(opts.bg), want.fingerprint);
+    }
     uint32_t start_sample = 0;
     std::vector<std::vector<float>> resume_acc(world);
     if (!cfg.checkpoint_path.empty()) {

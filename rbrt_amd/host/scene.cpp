@@ -83,8 +83,15 @@ Material Material::dielectric(float ref_idx) {
     m.abi.param = ref_idx;
     return m;
 }
+Material Material::emissive(Vec3 radiance) {
+    Material m;
+    m.abi.kind = RBRT_MAT_EMISSIVE;
+    put3(m.abi.albedo, radiance);
+    return m;
+}
 
-// blueprints.rs:50-74: substring match on the lower-cased type, in the order metal, lambert, dielectric.
+// blueprints.rs:50-74: substring match on the lower-cased type, in the order metal, lambert, dielectric; then emissive (not in
+// the reference), last so that every name the reference accepts keeps its meaning ("emissive metal" is a metal).
 std::optional<Material> create_material_from_description(const std::string& mat_type, std::optional<Vec3> albedo,
                                                          std::optional<float> material_param) {
     std::string t = mat_type;
@@ -103,7 +110,11 @@ std::optional<Material> create_material_from_description(const std::string& mat_
             throw Error("you forgot to specify a refractory index vector (i.e. material_param: 1.8) dielectric");
         return Material::dielectric(*material_param);
     }
-    std::printf("Cannot figure out material_type from %s, material_type must be one of metal, lambertian or dielectric!\n",
+    if (t.find("emissive") != std::string::npos) {
+        if (!albedo) throw Error("you forgot to specify an albedo vector (the emitted radiance) for emissive");
+        return Material::emissive(*albedo);
+    }
+    std::printf("Cannot figure out material_type from %s, material_type must be one of metal, lambertian, dielectric or emissive!\n",
                 mat_type.c_str());
     return std::nullopt;
 }

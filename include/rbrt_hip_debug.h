@@ -8,21 +8,18 @@
  *
  * Lab knobs (environment, read by rbrt_hip_scene_create ONLY when RBRT_HIP_LAB=1; a value outside the stated range
  * makes scene_create fail with RBRT_ERR_INVALID_ARG instead of being clamped; none of them changes the image):
- *   RBRT_POOL=128|256            path slots per wave            RBRT_LDS_STACK=1..64       stack entries per lane in LDS
+ *   RBRT_LDS_STACK=1..64         stack entries per lane in LDS
  *   RBRT_Y_LOW / RBRT_Y_HIGH=1..64, RBRT_Y_HIGH_PARKED=1..256   refill water marks of the traversal lanes
  *   RBRT_LEAF_ROUND=1..64, RBRT_LEAF_LEAVES=1..128              when a leaf round runs
- *   RBRT_SHARE_IDLE=0..64, RBRT_SHARE_BELOW=<samples>           shared traversals in the drain
- *   RBRT_DRAIN_MODE=<bits 0,1,3>  RBRT_WORK_STRIPES, RBRT_WORK_STRIPES_OVERLAP=<chunks, power of two>
+ *   RBRT_SHARE_IDLE=0..64        idle lanes needed for a round of shared traversals in the drain (4; 0: none)
+ *   RBRT_WORK_STRIPES, RBRT_WORK_STRIPES_OVERLAP=<chunks, power of two>
  *   RBRT_SHADE_ROUNDS=1..64, RBRT_SHADE_CONT_MIN=1..64          register-resident shading rounds
- *   RBRT_WAVES_PER_CU=1..32      RBRT_PIPELINE=0..8             RBRT_LANE_PRIORITY=low|default|high
+ *   RBRT_WAVES_PER_CU=1..32      RBRT_PIPELINE=0..8
  *   RBRT_BVH_CT=<SAH traversal cost, 4.0>   RBRT_PLOC_RADIUS=1..256 (device builder's neighbour search)
  *   RBRT_BVH_DEVICE_MIN=<entries>, RBRT_BVH_DEVICE_ALGO=ploc|lbvh   RBRT_POISON_SAMPLES=1 (tests)
  *   RBRT_PRIMARY_CULL=0|1        the tile pass (1): tiles whose camera rays reach nothing bypass the trace kernel
- *   RBRT_TILE_ORDER=0|1|2        tiles handed out: as api.cpp decides (0), first-to-last (1), last-to-first (2)
- *   RBRT_TILE_CLASSES=0..4       overrides the rule by launch kind: work list ascending (0), or by tile class: heavy|light,
- *                                light/2|heavy|light/2, light|heavy, or (4) row-major order with its last light tiles moved to the end
- *   RBRT_TILE_ISOLATED_MODE=0..4 the list mode of a launch that has the GPU to itself (4); a launch of a stream uses 0
- *   RBRT_TILE_TAIL_DIV=1..1024   mode 4: the share of the work list (1/n, 8) that is handed out last, from light tiles
+ *   RBRT_TILE_TAIL_DIV=1..1024   a launch that has the GPU to itself: the share of the work list (1/n, 8) that is handed out
+ *                                last, from light tiles (api.cpp list_mode_for)
  *   RBRT_OVERLAP_WAVES_PER_CU=0..16  waves per CU of a launch of a stream (0: 24 / launches side by side, rounded up, and
  *                                4 instead of 3 for a launch of 8 M work items or more)
  *   RBRT_TRACE_LAUNCHES=1        one stderr line per trace launch, tile pass and helper launch (which lane, grid, table set)

@@ -23,13 +23,12 @@
 #include "../../include/rbrt_hip_debug.h"
 
 namespace rbrt {
-hipError_t launch_trace_megakernel(const TraceParams& P, uint32_t n_waves, uint32_t pool, bool stats, bool share,
-                                   hipStream_t stream);
-hipError_t launch_trace_helper(const TraceParams& P, uint32_t n_waves, uint32_t pool, bool share, hipStream_t stream);
-size_t megakernel_gseq_bytes(uint32_t n_waves, uint32_t pool);
+hipError_t launch_trace_megakernel(const TraceParams& P, uint32_t n_waves, bool stats, hipStream_t stream);
+hipError_t launch_trace_helper(const TraceParams& P, uint32_t n_waves, hipStream_t stream);
+size_t megakernel_gseq_bytes(uint32_t n_waves);
 size_t megakernel_gstack_bytes(uint32_t n_waves);
-size_t megakernel_lds_bytes(uint32_t pool, uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris);
-int megakernel_occupancy_per_cu(uint32_t pool, size_t lds_bytes);
+size_t megakernel_lds_bytes(uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris);
+int megakernel_occupancy_per_cu(size_t lds_bytes);
 hipError_t launch_primary_cull(const TraceParams& P, hipStream_t stream);
 hipError_t launch_sky_resolve(const TraceParams& P, const ResolveParams& R, hipStream_t stream);
 hipError_t launch_code_load(hipStream_t stream);
@@ -92,15 +91,13 @@ const char* lab_env(const char* name) {
     const char* lab = std::getenv("RBRT_HIP_LAB");
     return (lab && lab[0] == '1') ? std::getenv(name) : nullptr;
 }
-// dst = $name when set (lab mode); false + message when it is not an integer in [lo, hi] (or not in `allowed`, if given)
-bool lab_u32(const char* name, long long lo, long long hi, uint32_t& dst, std::string& err, std::initializer_list<long long> allowed = {}) {
+// dst = $name when set (lab mode); false + message when it is not an integer in [lo, hi]
+bool lab_u32(const char* name, long long lo, long long hi, uint32_t& dst, std::string& err) {
     const char* e = lab_env(name);
     if (!e) return true;
     char* end = nullptr;
     const long long v = std::strtoll(e, &end, 10);
-    bool ok = end != e && *end == '\0' && v >= lo && v <= hi;
-    if (ok && allowed.size() != 0) ok = std::find(allowed.begin(), allowed.end(), v) != allowed.end();
-    if (!ok) {
+    if (end == e || *end != '\0' || v < lo || v > hi) {
         err = std::string("lab knob ") + name + "=" + e + " is not valid (see include/rbrt_hip_debug.h)";
         return false;
     }
@@ -200,7 +197,6 @@ struct rbrt_hip_scene {
             TraceParams P;
             uint32_t grid = 0, helper_waves = 0, rounds = 0;
             uint64_t seq = 0;           // issue number: a later launch has more of its work left
-            bool share = false;
         } open;
     };
     std::vector<Lane> lanes;
@@ -244,27 +240,20 @@ struct rbrt_hip_scene {
     std::vector<Bound> h_bounds;
     uint32_t stack_need = 1;  // deepest BVH: 3 per level + 1
     uint32_t n_waves = 0;  // persistent megakernel grid: as many single-wave workgroups as fit the LDS
-    uint32_t pool = 128;          // path slots per wave (RBRT_POOL = 128 | 256)
     uint32_t stack_entries = kLdsStack;  // per-lane stack entries kept in LDS (RBRT_LDS_STACK)
     uint32_t y_low_water = 28;    // RBRT_Y_LOW
     uint32_t y_high_water = 28, y_high_min_parked = 16;  // RBRT_Y_HIGH, RBRT_Y_HIGH_PARKED
     uint32_t leaf_round = 6;      // RBRT_LEAF_ROUND
     uint32_t leaf_leaves = 16;    // RBRT_LEAF_LEAVES
     uint32_t share_idle = 4;      // RBRT_SHARE_IDLE (0: no shared traversals)
-    uint64_t share_below = ~0ull;  // RBRT_SHARE_BELOW: launches under this many samples use the sharing build (all)
-    uint32_t drain_mode = 1;      // RBRT_DRAIN_MODE
     uint32_t work_stripes = 16;   // RBRT_WORK_STRIPES: chunks (of 64 work items) per stripe for a launch that has the GPU to itself; 0 = contiguous shards
     // RBRT_WORK_STRIPES_OVERLAP: the same for a launch issued while another is running. Automatic (kStripesAuto): contiguous
     // shards for a big launch, stripes of 4 chunks for one below 20 M work items -- measured per step on one box, 4 against
     // 0: the frame of config 2 (39 M) +1.0 %, the 871k mesh +2.0 %, the rough mesh -0.8 %; a half (20 M) -0.8 %, a quarter
     // -2.7 %, an eighth -2.8 %, a 512x384 frame -2.5 %
     uint32_t work_stripes_overlap = kStripesAuto;
-    uint32_t tile_classes = 0;    // RBRT_TILE_CLASSES (order of the work list by tile class, tile_lists_kernel)
-    bool tile_classes_set = false;  // ... given: it overrides the rule of list_mode_for()
     bool trace_launches = false;    // RBRT_TRACE_LAUNCHES=1 (lab): one stderr line per trace launch and per tile pass
-    uint32_t isolated_list_mode = 4;  // RBRT_TILE_ISOLATED_MODE: the list mode of a launch that has the GPU to itself
     uint32_t tile_tail_div = 8;       // RBRT_TILE_TAIL_DIV (mode 4)
-    uint32_t tile_order = 0;      // RBRT_TILE_ORDER (0: empty_end_is_first decides; 1: first-to-last; 2: last-to-first)
     uint32_t primary_cull = 1;    // RBRT_PRIMARY_CULL (0: no tile pass, the trace kernel renders every tile)
     uint32_t shade_rounds = 1;    // RBRT_SHADE_ROUNDS (rounds while work items are left; unbounded afterwards)
     uint32_t shade_cont_min = 8;  // RBRT_SHADE_CONT_MIN
@@ -553,17 +542,16 @@ uint32_t grid_for(const rbrt_hip_scene* s, bool overlapped, uint32_t depth, bool
     return part < s->n_waves ? part : s->n_waves;
 }
 
-// In which order a launch's tiles are handed out (tile_lists_kernel's modes), by what KIND of launch it is -- a rule, not a
-// setting made on one frame (measured on five workloads, DESIGN.md section 6 "In which order the work list is handed out"):
-// a launch that has the GPU to itself (a blocking caller) ends with every wave finishing what it holds and nothing behind
-// it, so its HEAVY tiles -- a mesh box or more than one sphere in reach -- go out first and the launch drains on light
-// ones (mode 1: isolated launch of the 871k mesh 6.36 -> 5.00 ms, the rough stand-in 6.31 -> 6.11, an eighth 1.21 -> 1.11;
-// the example frame, whose row-major order happens to end on its thin horizon band, 4.04 -> 4.17); a launch issued into
-// a stream of launches keeps the image's row-major order (mode 0: within 1.5 % of the best order on all five, and the
-// best on three -- the next launch's bulk fills whatever the drain leaves).
-uint32_t list_mode_for(const rbrt_hip_scene* s, bool overlapped) {
-    if (s->tile_classes_set) return s->tile_classes;
-    return overlapped ? 0u : s->isolated_list_mode;
+// In which order a launch's tiles are handed out (tile_lists_kernel's list modes), by what KIND of launch it is -- a rule,
+// not a setting made on one frame. A launch issued into a stream of launches keeps the image's row-major order (mode 0):
+// the next launch's bulk fills whatever its drain leaves. A launch that has the GPU to itself (a blocking caller) has
+// nothing behind its drain (mode 4): row-major order as well, except that the last n_work / tile_tail_div LIGHT tiles of
+// it (no mesh box in reach, at most one sphere) are handed out at the very end, so the bulk keeps row-major order's mix
+// of work and the launch drains on light tiles whatever the image. Measured in round 4 on five workloads against the
+// orders by tile class ("Measured and dropped": row-major order within 1.5 % of the best for a
+// stream of launches, an isolated launch best with its heavy tiles early); mode 4's own A/B is not in the record.
+uint32_t list_mode_for(bool overlapped) {
+    return overlapped ? 0u : 4u;
 }
 
 // The lane streams of ONE-SHOT scenes (rbrt_hip_render: a scene made for one render and destroyed) are kept by the process and
@@ -614,7 +602,6 @@ int ensure_lanes(rbrt_hip_scene* s, uint32_t depth) {
         // then win the wave slots a finishing trace wave frees, ahead of the next trace launch's waves.
         int prio_low = 0, prio_high = 0;
         (void)hipDeviceGetStreamPriorityRange(&prio_low, &prio_high);  // (numerically: low >= high)
-        if (const char* pe = lab_env("RBRT_LANE_PRIORITY")) prio_low = !std::strcmp(pe, "default") ? 0 : !std::strcmp(pe, "high") ? prio_high : prio_low;
         hipError_t e = hipSuccess;
         if (s->one_shot) {
             R.stream_pool_key = s->device * 64 + (prio_low & 63);
@@ -677,7 +664,7 @@ int issue_helper(rbrt_hip_scene* s, rbrt_hip_scene::Lane& L, uint32_t waves, hip
     TraceParams P = L.open.P;
     P.wave_base = L.open.grid + L.open.helper_waves;
     P.helper_min_items = s->helpers_mode == 2u ? 0u : s->helper_min_items;  // (tests: every helper wave joins)
-    HIP_TRY(launch_trace_helper(P, waves, s->pool, L.open.share, carrier));
+    HIP_TRY(launch_trace_helper(P, waves, carrier));
     HIP_TRY(hipEventRecord(L.ev_helper, carrier));
     L.helper_pending = true;
     L.open.helper_waves += waves, L.open.rounds += 1u;
@@ -1158,33 +1145,28 @@ int scene_create_impl(const rbrt_scene_t* scene, int device, rbrt_hip_scene_t** 
         std::string err;
         uint32_t waves_per_cu = 0, poison = 0, stripes = s->work_stripes, stripes_overlap = s->work_stripes_overlap;
         const bool knobs_ok =
-            lab_u32("RBRT_POOL", 128, 256, s->pool, err, {128, 256}) && lab_u32("RBRT_LDS_STACK", 1, kStackMax, s->stack_entries, err) &&
+            lab_u32("RBRT_LDS_STACK", 1, kStackMax, s->stack_entries, err) &&
             lab_u32("RBRT_LEAF_ROUND", 1, 64, s->leaf_round, err) && lab_u32("RBRT_Y_HIGH", 1, 64, s->y_high_water, err) &&
             lab_u32("RBRT_Y_HIGH_PARKED", 1, 256, s->y_high_min_parked, err) && lab_u32("RBRT_Y_LOW", 1, 64, s->y_low_water, err) &&
             lab_u32("RBRT_WAVES_PER_CU", 1, 32, waves_per_cu, err) && lab_u32("RBRT_LEAF_LEAVES", 1, 128, s->leaf_leaves, err) &&
             lab_u32("RBRT_SHARE_IDLE", 0, 64, s->share_idle, err) && lab_u32("RBRT_WORK_STRIPES", 0, 65536, stripes, err) &&
-            lab_u32("RBRT_WORK_STRIPES_OVERLAP", 0, 65536, stripes_overlap, err) && lab_u32("RBRT_DRAIN_MODE", 0, 11, s->drain_mode, err) &&
+            lab_u32("RBRT_WORK_STRIPES_OVERLAP", 0, 65536, stripes_overlap, err) &&
             lab_u32("RBRT_SHADE_ROUNDS", 1, kMaxShadeRounds, s->shade_rounds, err) &&
             lab_u32("RBRT_SHADE_CONT_MIN", 1, 64, s->shade_cont_min, err) && lab_u32("RBRT_PIPELINE", 0, kMaxPipeline, s->pipeline, err) &&
             lab_u32("RBRT_POISON_SAMPLES", 0, 1, poison, err) && lab_u32("RBRT_PRIMARY_CULL", 0, 1, s->primary_cull, err) &&
-            lab_u32("RBRT_TILE_ORDER", 0, 2, s->tile_order, err) && lab_u32("RBRT_TILE_CLASSES", 0, 4, s->tile_classes, err) &&
-            lab_u32("RBRT_OVERLAP_WAVES_PER_CU", 0, 16, s->overlap_waves_per_cu, err) &&
-            lab_u32("RBRT_TILE_ISOLATED_MODE", 0, 4, s->isolated_list_mode, err) && lab_u32("RBRT_TILE_TAIL_DIV", 1, 1024, s->tile_tail_div, err) &&
+            lab_u32("RBRT_OVERLAP_WAVES_PER_CU", 0, 16, s->overlap_waves_per_cu, err) && lab_u32("RBRT_TILE_TAIL_DIV", 1, 1024, s->tile_tail_div, err) &&
             lab_u32("RBRT_HELPERS", 0, 2, s->helpers_mode, err) && lab_u32("RBRT_HELPER_MIN_ITEMS", 1, 1 << 24, s->helper_min_items, err) &&
             lab_u32("RBRT_HELPER_MIN_LAUNCH_MI", 0, 4096, s->helper_min_launch_mi, err) && lab_u32("RBRT_HELPER_MIN_FREE", 1, 16, s->helper_min_free_per_cu, err) &&
             lab_u32("RBRT_HELPER_ROUNDS", 1, 16, s->helper_rounds, err);
         if (!knobs_ok) return bail(fail(RBRT_ERR_INVALID_ARG, err));
-        s->tile_classes_set = lab_env("RBRT_TILE_CLASSES") != nullptr;
         s->trace_launches = lab_env("RBRT_TRACE_LAUNCHES") != nullptr;
         if ((stripes & (stripes - 1u)) != 0u || (stripes_overlap != kStripesAuto && (stripes_overlap & (stripes_overlap - 1u)) != 0u))  // the kernel shifts
             return bail(fail(RBRT_ERR_INVALID_ARG, "lab knob RBRT_WORK_STRIPES / RBRT_WORK_STRIPES_OVERLAP must be 0 or a power of two"));
         s->work_stripes = stripes, s->work_stripes_overlap = stripes_overlap;
-        s->drain_mode &= 11u;
         s->poison_samples = poison != 0;
-        if (const char* e = lab_env("RBRT_SHARE_BELOW")) s->share_below = std::strtoull(e, nullptr, 10);
         if (s->stack_entries > s->stack_need) s->stack_entries = s->stack_need;
         // resident waves per CU: LDS-limited (160 KiB per CU), at most 5 per SIMD (VGPR budget)
-        int per_cu = int((160u * 1024u) / megakernel_lds_bytes(s->pool, s->stack_entries, s->n_spheres, s->n_meshes, s->n_elem_tris));
+        int per_cu = int((160u * 1024u) / megakernel_lds_bytes(s->stack_entries, s->n_spheres, s->n_meshes, s->n_elem_tris));
         if (per_cu > 20) per_cu = 20;
         if (per_cu < 1) per_cu = 1;
         if (waves_per_cu != 0) per_cu = int(waves_per_cu), s->waves_fixed = true;
@@ -1429,8 +1411,7 @@ static int render_samples(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, const r
     P.tiles_x = tiles_x, P.tiles_y = tiles_y, P.n_tiles = n_tiles;
     P.tiles_x_magic = div_magic_of(tiles_x);
     P.tiles_reversed = empty_end_is_first(s, *cam, tiles_x, o->tile_rank, world, n_local) ? 1u : 0u;
-    if (s->tile_order != 0u) P.tiles_reversed = s->tile_order - 1u;  // (lab knob)
-    const uint32_t rowmajor_reversed = P.tiles_reversed;  // (a launch whose list is in class order resets it; the next batch may not)
+    const uint32_t rowmajor_reversed = P.tiles_reversed;  // (a launch whose list is in hand-out order resets it; the next batch may not)
     P.tile_rank = o->tile_rank, P.tile_world = world, P.n_local_tiles = n_local;
     P.stack_entries = s->stack_entries;
     P.y_low_water = s->y_low_water;
@@ -1439,7 +1420,6 @@ static int render_samples(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, const r
     P.leaf_round = s->leaf_round;
     P.leaf_leaves = s->leaf_leaves;
     P.share_idle = s->share_idle;
-    P.drain_mode = s->drain_mode;
     P.work_stripes = s->work_stripes;  // (per launch: set where the launch's size is known)
     P.shade_rounds = s->shade_rounds;
     P.shade_cont_min = s->shade_cont_min;
@@ -1474,7 +1454,7 @@ static int render_samples(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, const r
         if (!L.d_gseq) {  // the lane's per-wave scratch: scatter records beyond the four in LDS (written before they are read: no
                           // initial value), the overflow of the LDS stacks
             void* p = nullptr;
-            const size_t gseq_bytes = (megakernel_gseq_bytes(s->scratch_waves, s->pool) + kSlabAlign - 1) & ~(kSlabAlign - 1);
+            const size_t gseq_bytes = (megakernel_gseq_bytes(s->scratch_waves) + kSlabAlign - 1) & ~(kSlabAlign - 1);
             HIP_TRY(dev_alloc(s, gseq_bytes + megakernel_gstack_bytes(s->scratch_waves), &p));
             L.d_gseq = static_cast<uint32_t*>(p);
             L.d_gstack = reinterpret_cast<uint32_t*>(static_cast<char*>(p) + gseq_bytes);
@@ -1532,7 +1512,7 @@ static int render_samples(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, const r
         fill_trace_params(s, cam, o, T);
         T.tiles_x = tiles_x, T.tiles_y = tiles_y, T.n_tiles = n_tiles;
         T.tile_rank = o->tile_rank, T.tile_world = world, T.n_local_tiles = n_local;
-        T.tile_list_mode = list_mode_for(s, true);  // (what the launches of a stream use; an isolated launch makes its own list)
+        T.tile_list_mode = list_mode_for(true);  // (what the launches of a stream use; an isolated launch makes its own list)
         T.tile_tail_div = s->tile_tail_div;
         T.tiles_reversed = P.tiles_reversed;
         // (the one-wave form of the list kernel: `streams_now` means a launch of this scene is in flight or about to be, and a
@@ -1551,7 +1531,7 @@ static int render_samples(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, const r
             S.key_valid = true;
             // (the lane this call's first launch takes: if that launch finds the GPU idle it wants the isolated launch's list
             // as well -- made here too, it does not have to wait for the prep stream while the launches behind it pile up)
-            const uint32_t iso_mode = list_mode_for(s, false);
+            const uint32_t iso_mode = list_mode_for(false);
             if (li == s->next_lane % depth && iso_mode != T.tile_list_mode) {
                 rbrt_hip_scene::Lane::TileSet& S1 = L.tiles[1];
                 TraceParams T1 = T;
@@ -1579,7 +1559,7 @@ static int render_samples(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, const r
         if (!stats && depth > 1 && s->primary_cull != 0 && !s->streaming_hint && b == 0 && !busy_at_call) {
             rbrt_hip_scene::Lane::TileKey want;
             std::memset(&want, 0, sizeof(want));
-            want.cam = *cam, want.rank = o->tile_rank, want.world = world, want.list_mode = list_mode_for(s, false), want.min_dist = o->min_dist;
+            want.cam = *cam, want.rank = o->tile_rank, want.world = world, want.list_mode = list_mode_for(false), want.min_dist = o->min_dist;
             for (uint32_t li = 0; li < depth; ++li)
                 for (const auto& C : s->lanes[li].tiles)
                     if (C.key_valid && std::memcmp(&want, &C.key, sizeof(want)) == 0) lane_no = li;
@@ -1647,7 +1627,7 @@ static int render_samples(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, const r
         if (tile_pass) {
             rbrt_hip_scene::Lane::TileKey key;
             std::memset(&key, 0, sizeof(key));
-            const uint32_t list_mode = list_mode_for(s, overlapped && !stats);
+            const uint32_t list_mode = list_mode_for(overlapped && !stats);
             key.cam = *cam, key.rank = o->tile_rank, key.world = world, key.list_mode = list_mode, key.min_dist = o->min_dist;
             for (auto& C : L.tiles)
                 if (C.key_valid && std::memcmp(&key, &C.key, sizeof(key)) == 0) S = &C;
@@ -1689,11 +1669,10 @@ static int render_samples(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, const r
         if (S) HIP_TRY(hipStreamWaitEvent(ts, S->ev_lists, 0));  // (the set's tables: made on the prep stream, or at the first call on the caller's)
         const uint32_t grid = stats ? s->n_waves : grid_for(s, overlapped, depth, call_streams, company, P.n_items);
         (grid < s->n_waves ? s->n_half_grid : s->n_full_grid) += 1;
-        const bool share_build = s->share_idle != 0u && P.n_items < s->share_below;
         if (piped) HIP_TRY(hipEventRecord(L.ev_ready, ts));  // (behind everything the launch waits for: a helper launch waits for this)
-        HIP_TRY(launch_trace_megakernel(P, grid, s->pool, stats, share_build, ts));
-        if (piped && s->pool == 128u && s->helpers_mode != 0u) {
-            L.open.valid = true, L.open.P = P, L.open.grid = grid, L.open.helper_waves = 0u, L.open.rounds = 0u, L.open.share = share_build;
+        HIP_TRY(launch_trace_megakernel(P, grid, stats, ts));
+        if (piped && s->helpers_mode != 0u) {
+            L.open.valid = true, L.open.P = P, L.open.grid = grid, L.open.helper_waves = 0u, L.open.rounds = 0u;
             L.open.seq = ++s->open_seq;
             if (s->helpers_mode == 2u) {  // (tests: a helper with every overlapped launch, on a stream of its own)
                 if (!s->aux_stream) HIP_TRY(hipStreamCreateWithFlags(&s->aux_stream, hipStreamNonBlocking));
@@ -1859,9 +1838,9 @@ int rbrt_hip_scene_info(rbrt_hip_scene_t* s, rbrt_hip_scene_info_t* out) {
     out->bvh_stack_need = s->stack_need;
     out->n_nodes = s->total_nodes, out->n_triangles = s->total_tris;
     out->trace_waves = s->n_waves;
-    out->lds_bytes_per_wave = uint32_t(megakernel_lds_bytes(s->pool, s->stack_entries, s->n_spheres, s->n_meshes, s->n_elem_tris));
+    out->lds_bytes_per_wave = uint32_t(megakernel_lds_bytes(s->stack_entries, s->n_spheres, s->n_meshes, s->n_elem_tris));
     (void)hipSetDevice(s->device);
-    out->occupancy_api_waves_per_cu = uint32_t(megakernel_occupancy_per_cu(s->pool, out->lds_bytes_per_wave));
+    out->occupancy_api_waves_per_cu = uint32_t(megakernel_occupancy_per_cu(out->lds_bytes_per_wave));
     out->n_cus = s->n_cus;
     return RBRT_OK;
 }

@@ -29,20 +29,14 @@ constexpr int kBlock = 256;          // threads per workgroup of the test hooks'
 // not fit makes the dispatcher keep what frees up for it instead of handing it to the next trace launch's waves. Round 4's
 // kernel trace (profiles/r04_trace_frames.txt): the resolve -- 50 us of work -- took 3.0-3.4 ms in EVERY frame of a stream,
 // its lane waiting for it all the while. A one-wave workgroup runs in any slot a trace wave leaves.
-#ifndef RBRT_SMALL_BLOCK
-#define RBRT_SMALL_BLOCK 64
-#endif
-constexpr int kSmallBlock = RBRT_SMALL_BLOCK;
+constexpr int kSmallBlock = 64;
 constexpr int kMaxBvhDepth = 20;     // deepest 4-wide node (root = 0) the builder may create
 constexpr int kStackMax = 3 * (kMaxBvhDepth + 1) + 1;  // a visit defers at most 3 children per level
 constexpr int kMaxPathDepth = 64;    // opts.max_depth limit (reference: 50, lib.rs:99)
 constexpr int kMaxObjects = 255;     // spheres + meshes (object id is stored in one byte per bounce)
-#ifndef RBRT_LEAF_BITS
-#define RBRT_LEAF_BITS 2
-#endif
-constexpr int kLeafBits = RBRT_LEAF_BITS;  // width of the count field of a leaf link
+constexpr int kLeafBits = 2;              // width of the count field of a leaf link
 constexpr int kLeafMax = 1 << kLeafBits;   // triangles per leaf
-constexpr int kPoolMax = 256;        // largest path pool per wave the persistent megakernel is built for
+constexpr int kPool = 128;           // path slots per wave of the persistent megakernel (other sizes lost)
 constexpr uint32_t kWorkShards = 8;         // work-item counters (one per XCD)
 constexpr uint32_t kWorkCounterStride = 16;  // in u64: each counter on its own 128-B line
 constexpr uint32_t kMaxShadeRounds = 64;  // hard bound of register-resident shading rounds per pass
@@ -157,7 +151,7 @@ struct TraceParams {
     DevCounters* counters;
     // persistent megakernel only
     unsigned long long* work_counter;  // [kWorkShards * kWorkCounterStride] next unclaimed item per shard (zeroed before every launch)
-    uint32_t* gseq;                    // [n_waves][kPoolMax][kMaxPathDepth/4] scatter records beyond the 4 kept in LDS
+    uint32_t* gseq;                    // [n_waves][kPool][kMaxPathDepth/4] scatter records beyond the 4 kept in LDS
     uint32_t stack_entries;            // per-lane traversal stack entries kept in LDS (<= stack_need)
     uint32_t* gstack;                  // [n_waves][kStackMax][64] overflow of the LDS stacks
     uint32_t y_low_water;              // refill a traversal pass when fewer lanes than this are busy
@@ -166,7 +160,6 @@ struct TraceParams {
     uint32_t share_idle;               // shared traversals: idle lanes needed for a round of giving (0: never)
     uint32_t leaf_leaves;              // ... or once this many leaves are pending (a leaf round deals their triangles out to all lanes)
     uint32_t work_stripes;             // chunks per stripe when the work shards interleave over the item range (0: contiguous eighths)
-    uint32_t drain_mode;               // scheduling once the work items have run out (bits: megakernel.inl "drain")
     uint32_t shade_rounds;             // shading pass: rounds a sphere-only bounce chain may stay in registers
     uint32_t shade_cont_min;           // ... as long as at least this many lanes continue (ignored once the work has run out)
     // The tile pass (kernels.hip primary_cull_kernel + tile_lists_kernel, run before the trace launch; both null: off).

@@ -44,11 +44,8 @@ __device__ __forceinline__ float dot(V3 a, V3 b) { return (a.x * b.x + a.y * b.y
 // 13 instructions: v_sqrt / v_rcp plus correction steps, wrapped in range handling (input scaling for tiny
 // operands, v_div_scale / v_div_fixup, class checks for 0 and inf). For operands in the everyday range that
 // wrapping is the identity, and the correction steps -- reproduced below instruction for instruction -- give the same
-// bits. RBRT_FAST_IEEE: a wave takes the short forms when EVERY active lane's operands are in range (one compare or
-// two per call) and the compiler's forms otherwise. tests: test_short_ieee_forms_match_the_compilers (2^28 operands).
-#ifndef RBRT_FAST_IEEE
-#define RBRT_FAST_IEEE 1
-#endif
+// bits. A wave takes the short forms when EVERY active lane's operands are in range (one compare or two per call) and
+// the compiler's forms otherwise. tests: test_short_ieee_forms_match_the_compilers (2^28 operands).
 __device__ __forceinline__ float sqrt_core(float x) {  // x in [2^-80, 2^100]: hipcc's sqrt without its scaling / class steps
     const float r = __builtin_amdgcn_sqrtf(x);
     const float r_dn = __uint_as_float(__float_as_uint(r) - 1u), r_up = __uint_as_float(__float_as_uint(r) + 1u);
@@ -59,7 +56,7 @@ __device__ __forceinline__ float sqrt_core(float x) {  // x in [2^-80, 2^100]: h
 }
 __device__ __forceinline__ bool sqrt_in_range(float x) { return x > 0x1p-80f && x < 0x1p100f; }  // (false for NaN)
 __device__ __forceinline__ float ieee_sqrt(float x) {
-    if (RBRT_FAST_IEEE && __builtin_amdgcn_ballot_w64(!sqrt_in_range(x)) == 0ull) return sqrt_core(x);
+    if (__builtin_amdgcn_ballot_w64(!sqrt_in_range(x)) == 0ull) return sqrt_core(x);
     return __builtin_sqrtf(x);
 }
 __device__ __forceinline__ float length(V3 a) { return ieee_sqrt((a.x * a.x + a.y * a.y) + a.z * a.z); }
@@ -68,10 +65,6 @@ __device__ __attribute__((noinline)) V3 normalize_ieee(V3 a) {  // the compiler'
     return V3{a.x / len, a.y / len, a.z / len};
 }
 __device__ __forceinline__ V3 normalize(V3 a) {  // three divisions by the length, vec3.rs:119-126
-    if (!RBRT_FAST_IEEE) {
-        const float len = __builtin_sqrtf((a.x * a.x + a.y * a.y) + a.z * a.z);
-        return V3{a.x / len, a.y / len, a.z / len};
-    }
     const float s = (a.x * a.x + a.y * a.y) + a.z * a.z;
     const float mn = __builtin_fminf(__builtin_fminf(__builtin_fabsf(a.x), __builtin_fabsf(a.y)), __builtin_fabsf(a.z));
     // in range: no scaling in sqrt; len in [2^-40, 2^50]; every |component| >= 2^-100 (so v_div_scale leaves numerator
@@ -408,9 +401,6 @@ __device__ __forceinline__ void node4_visit(const BvhNode4* node, const RayCull&
 // compare-exchange that carries the link along is one compare and four selects: 25 for the five exchanges, against
 // 10 + 28, and five VCC hazards instead of twelve. Which child is walked first cannot change what is found (the tree only
 // culls; the result cell keeps the lexicographic (t, index) minimum), so equal keys may come out in either order.
-#ifndef RBRT_PAIR_SORT
-#define RBRT_PAIR_SORT 1
-#endif
 __device__ __forceinline__ void cswap_pair(uint32_t& ka, uint32_t& kb, int32_t& la, int32_t& lb) {
     const bool sw = kb < ka;
     const uint32_t k0 = sw ? kb : ka, k1 = sw ? ka : kb;
@@ -655,8 +645,7 @@ __device__ __forceinline__ V3 background(float dy, const float* bg, uint32_t con
     return t * mk(1.0f, 1.0f, 1.0f) + (1.0f - t) * mk(bg);
 }
 
-__host__ __device__ inline uint32_t megakernel_lds_dwords(uint32_t pool, uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes,
-                                                          uint32_t n_elem_tris);
+__host__ __device__ inline uint32_t megakernel_lds_dwords(uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris);
 #include "megakernel.inl"
 
 // lib.rs:116-122: (sqrt(c) * 256) as u8 — Rust's float->int cast saturates and maps NaN to 0.
@@ -1136,12 +1125,10 @@ __global__ __launch_bounds__(kListBlock) void tile_lists_kernel(const TraceParam
     uint32_t k = lo - r[0] - r[1];                                  // background-only tiles before it
     uint32_t* const work = P.tile_lists + kTileListHeader;
     uint32_t* const sky = work + n;
-    // where the classes go in the work list (tile_list_mode; 0: one class, ascending): 1 heavy | light, 2 light/2 | heavy |
-    // light/2, 3 light | heavy -- each class ascending in itself; 4: the image's row-major order in the direction it is handed
-    // out in (P.tiles_reversed: from the last tile down), except that the LAST n_work / tile_tail_div light tiles of that
-    // order are taken out of it and handed out at the very end: the bulk of the launch keeps row-major order's mix of
-    // traversal-heavy and shading-heavy work in every wave, and the launch drains on light tiles whatever the image
-    const uint32_t half = n_light / 2u;
+    // the work list (tile_list_mode; api.cpp list_mode_for): 0: ascending; 4: the image's row-major order in the direction it
+    // is handed out in (P.tiles_reversed: from the last tile down), except that the LAST n_work / tile_tail_div light tiles
+    // of that order are taken out of it and handed out at the very end: the bulk of the launch keeps row-major order's mix
+    // of traversal-heavy and shading-heavy work in every wave, and the launch drains on light tiles whatever the image
     uint32_t n_tail = n_work / (P.tile_tail_div != 0u ? P.tile_tail_div : 8u);
     n_tail = n_tail < n_light ? n_tail : n_light;
     const uint32_t n_front_light = n_light - n_tail;  // light tiles that stay in row-major order
@@ -1166,10 +1153,8 @@ __global__ __launch_bounds__(kListBlock) void tile_lists_kernel(const TraceParam
             if (c == 1u && l >= n_front_light) pos = (n_work - n_tail) + (l - n_front_light);
             else pos = h + (l < n_front_light ? l : n_front_light);
             ++r[c];
-        } else if (c == 0u) {
-            pos = (P.tile_list_mode == 2u ? half : P.tile_list_mode == 3u ? n_light : 0u) + r[0]++;
         } else {
-            pos = (P.tile_list_mode == 1u ? n_heavy : P.tile_list_mode == 2u && r[1] >= half ? n_heavy : 0u) + r[1]++;
+            pos = r[0]++;  // (mode 0 puts every tile in class 0)
         }
         work[pos] = tl;
       }
@@ -1308,28 +1293,26 @@ __global__ __launch_bounds__(kBlock) void scatter_debug_kernel(const DevMaterial
 // ---------------------------------------------------------------------------------------------
 // Launch wrappers (called from api.cpp, which is plain C++)
 // ---------------------------------------------------------------------------------------------
-size_t megakernel_gseq_bytes(uint32_t n_waves, uint32_t pool) { return size_t(n_waves) * pool * kSeqWords * sizeof(uint32_t); }
+size_t megakernel_gseq_bytes(uint32_t n_waves) { return size_t(n_waves) * kPool * kSeqWords * sizeof(uint32_t); }
 size_t megakernel_gstack_bytes(uint32_t n_waves) { return size_t(n_waves) * kStackMax * 64u * sizeof(uint32_t); }
 
-__host__ __device__ inline uint32_t megakernel_lds_dwords(uint32_t pool, uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes,
-                                                          uint32_t n_elem_tris) {
+__host__ __device__ inline uint32_t megakernel_lds_dwords(uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris) {
     const uint32_t n_elem = n_spheres + n_elem_tris;
     const uint32_t scene = n_spheres * kSphDw + (n_elem + n_meshes) * kMatDw + n_meshes * kMeshDw + kGenDw +
                            (n_elem_tris != 0u ? n_elem_tris * kTriDw + n_elem : 0u);  // triangle table + element order
-    const uint32_t pool_pad = (pool + 63u) & ~63u;  // status + list: one byte per (padded) slot each
-    uint32_t dw = uint32_t(kFields) * pool + kCellDw + kTqDw + kHelpDw + pool_pad / 2u + stack_entries * 64u + scene;
+    const uint32_t pool_pad = (uint32_t(kPool) + 63u) & ~63u;  // status + list: one byte per (padded) slot each
+    uint32_t dw = uint32_t(kFields * kPool) + kCellDw + kTqDw + kHelpDw + pool_pad / 2u + stack_entries * 64u + scene;
     if (RBRT_REGION_TIMERS) dw += uint32_t(kNumRegions);  // analysis build: a u32 cycle accumulator per region
     return dw;
 }
-size_t megakernel_lds_bytes(uint32_t pool, uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris) {
-    return size_t(megakernel_lds_dwords(pool, stack_entries, n_spheres, n_meshes, n_elem_tris)) * sizeof(uint32_t);
+size_t megakernel_lds_bytes(uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris) {
+    return size_t(megakernel_lds_dwords(stack_entries, n_spheres, n_meshes, n_elem_tris)) * sizeof(uint32_t);
 }
 
 // What the HIP runtime says fits: resident single-wave workgroups of the trace kernel per CU at this much LDS (0 on error).
-int megakernel_occupancy_per_cu(uint32_t pool, size_t lds_bytes) {
+int megakernel_occupancy_per_cu(size_t lds_bytes) {
     int n = 0;
-    hipError_t e = pool == 256 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, trace_megakernel<256, false, true>, 64, lds_bytes)
-                               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, trace_megakernel<128, false, true>, 64, lds_bytes);
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, trace_megakernel<false>, 64, lds_bytes);
     return e == hipSuccess ? n : 0;
 }
 
@@ -1337,39 +1320,20 @@ int megakernel_occupancy_per_cu(uint32_t pool, size_t lds_bytes) {
 // this stream) runs out, so any grid size is correct and no wave ever waits on another.
 // A helper launch (api.cpp "Elastic launches"): more waves for a launch that is already running -- the same parameters
 // (work counters, sample buffer, tables), scratch slots from P.wave_base on.
-hipError_t launch_trace_helper(const TraceParams& P, uint32_t n_waves, uint32_t pool, bool share, hipStream_t stream) {
+hipError_t launch_trace_helper(const TraceParams& P, uint32_t n_waves, hipStream_t stream) {
     if (P.n_items == 0 || n_waves == 0 || !P.helper_words) return hipSuccess;
-    const size_t lds = megakernel_lds_bytes(pool, P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris);
-    if (pool == 128 && share)
-        hipLaunchKernelGGL((trace_megakernel<128, false, true, true>), dim3(n_waves), dim3(64), lds, stream, P);
-    else if (pool == 128)
-        hipLaunchKernelGGL((trace_megakernel<128, false, false, true>), dim3(n_waves), dim3(64), lds, stream, P);
-    else
-        return hipErrorInvalidValue;  // (the lab's 256-slot pool has no helper build)
+    const size_t lds = megakernel_lds_bytes(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris);
+    hipLaunchKernelGGL((trace_megakernel<false, true>), dim3(n_waves), dim3(64), lds, stream, P);
     return hipGetLastError();
 }
 
-hipError_t launch_trace_megakernel(const TraceParams& P, uint32_t n_waves, uint32_t pool, bool stats, bool share,
-                                   hipStream_t stream) {
+hipError_t launch_trace_megakernel(const TraceParams& P, uint32_t n_waves, bool stats, hipStream_t stream) {
     if (P.n_items == 0 || n_waves == 0) return hipSuccess;
-    const size_t lds = megakernel_lds_bytes(pool, P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris);
-#define RBRT_LAUNCH_MK(POOLN, STATS, SHARE) \
-    hipLaunchKernelGGL((trace_megakernel<POOLN, STATS, SHARE>), dim3(n_waves), dim3(64), lds, stream, P)
-#define RBRT_LAUNCH_POOL(POOLN)                            \
-    do {                                                   \
-        if (stats && share) RBRT_LAUNCH_MK(POOLN, true, true);    \
-        else if (stats) RBRT_LAUNCH_MK(POOLN, true, false);       \
-        else if (share) RBRT_LAUNCH_MK(POOLN, false, true);       \
-        else RBRT_LAUNCH_MK(POOLN, false, false);                 \
-    } while (0)
-    if (pool == 128)
-        RBRT_LAUNCH_POOL(128);
-    else if (pool == 256)
-        RBRT_LAUNCH_POOL(256);
+    const size_t lds = megakernel_lds_bytes(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris);
+    if (stats)
+        hipLaunchKernelGGL((trace_megakernel<true>), dim3(n_waves), dim3(64), lds, stream, P);
     else
-        return hipErrorInvalidValue;
-#undef RBRT_LAUNCH_POOL
-#undef RBRT_LAUNCH_MK
+        hipLaunchKernelGGL((trace_megakernel<false>), dim3(n_waves), dim3(64), lds, stream, P);
     return hipGetLastError();
 }
 

@@ -1,6 +1,6 @@
 // megakernel.inl — the persistent path-tracing megakernel (included by kernels.hip).
 //
-// One wave64 per workgroup, a pool of POOLN path slots in LDS, and wavefront ballots to sort the
+// One wave64 per workgroup, a pool of kPool path slots in LDS, and wavefront ballots to sort the
 // paths into passes in which all 64 lanes run the same code.
 //
 // Why (measured, profiles/r01_v1_pmc_sq.json): with one thread per path only 15 % of the VALU lanes
@@ -36,15 +36,6 @@ enum { RBRT_REGIONS(RBRT_REGION_ENUM) kNumRegions };
 #define RBRT_MARK(name) asm volatile("; @@" #name ::: "memory")
 #else
 #define RBRT_MARK(name)
-#endif
-#ifndef RBRT_FAST_GATE
-#define RBRT_FAST_GATE 1  // mesh bbox gate through bbox_gate_fast (same decisions, no IEEE divisions on the common path)
-#endif
-#ifndef RBRT_PUSH_ORDER
-#define RBRT_PUSH_ORDER 0  // 0: children pushed far-to-near (sorted); 1: nearest next, the rest in slot order
-#endif
-#ifndef RBRT_SPHERE_BOUND
-#define RBRT_SPHERE_BOUND 1  // the triangle search of a ray that has hit a sphere starts at that hit's distance
 #endif
 #ifndef RBRT_MK_WAVES_PER_SIMD
 #define RBRT_MK_WAVES_PER_SIMD 4  // register budget: 512 / 4 = 128 VGPRs per lane
@@ -104,18 +95,17 @@ __device__ __forceinline__ const T* lds_ptr(const uint32_t* p) {  // a 64-bit de
 
 // First mesh with index >= m0 whose bbox gate (aabbox.rs:28-58) the ray passes, or n_meshes.
 // `closest`: the distance of the ray's closest hit so far (f32::MAX: none); a mesh whose box the ray enters only
-// beyond it (relaxed like the search bound of the refill) is passed over.
+// beyond it (relaxed like the search bound of the refill) is passed over. The gate is bbox_gate_fast: the same decisions as
+// bbox_gate, without IEEE divisions on the common path.
 template <bool STATS>
 __device__ __forceinline__ uint32_t next_gated_mesh(const SceneLds& sc, uint32_t n_meshes, uint32_t m0, V3 o, V3 d,
                                                     float closest, LocalCounters& lc) {
-    const float beyond = RBRT_SPHERE_BOUND
-                             ? closest * 1.001f + 0.001f * (1.0f + __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(o.x), __builtin_fabsf(o.y)),
-                                                                                  __builtin_fabsf(o.z)))
-                             : __builtin_inff();
+    const float beyond =
+        closest * 1.001f + 0.001f * (1.0f + __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(o.x), __builtin_fabsf(o.y)), __builtin_fabsf(o.z)));
     uint32_t m = m0;
     for (; m < n_meshes; ++m) {
         const float* md = reinterpret_cast<const float*>(sc.mesh + m * kMeshDw);
-        if (RBRT_FAST_GATE ? bbox_gate_fast(md + MD_BBOX_LO, md + MD_BBOX_HI, o, d, beyond) : bbox_gate(md + MD_BBOX_LO, md + MD_BBOX_HI, o, d)) {
+        if (bbox_gate_fast(md + MD_BBOX_LO, md + MD_BBOX_HI, o, d, beyond)) {
             if (STATS) ++lc.gate;
             break;
         }
@@ -221,20 +211,19 @@ struct WorkSource {
     }
 };
 
-// SHAREK: the build of the kernel that can share traversals between lanes in the drain (below). It is a separate
-// build because the second copy of the traversal loop costs the first one 3 % (register allocation at the
-// 128-VGPR limit): launches that are mostly bulk use the build without it.
-template <int POOLN, bool STATS, bool SHAREK, bool HELPER = false>
+// Three builds: the product, the counting build (STATS: diagnostics into DevCounters) and the helper build (HELPER: extra
+// waves for a launch that is already running, api.cpp "Elastic launches").
+template <bool STATS, bool HELPER = false>
 __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(const TraceParams P) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-    constexpr uint32_t kPoolPad = (uint32_t(POOLN) + 63u) & ~63u;  // census loops run in groups of 64 slots
+    constexpr uint32_t kPoolPad = (uint32_t(kPool) + 63u) & ~63u;  // census loops run in groups of 64 slots
     uint32_t* const pool = lds;
-    static_assert((kFields * POOLN) % 2 == 0, "the u64 cells must be 8-byte aligned");
+    static_assert((kFields * kPool) % 2 == 0, "the u64 cells must be 8-byte aligned");
     // Leaf rounds (below): cell[l] is the best (t, triangle index) found so far for the ray that lane l OWNS, merged
     // by whichever lanes tested its triangles; tq is the queue of (triangle, holder lane) pairs of the chunk being
     // tested; helpers[l] counts the lanes that are walking a part of lane l's tree for it (shared traversals).
-    unsigned long long* const cell = reinterpret_cast<unsigned long long*>(pool + kFields * POOLN);  // [64]
-    uint32_t* const tq = pool + kFields * POOLN + kCellDw;                                            // [64]
+    unsigned long long* const cell = reinterpret_cast<unsigned long long*>(pool + kFields * kPool);  // [64]
+    uint32_t* const tq = pool + kFields * kPool + kCellDw;                                            // [64]
     uint32_t* const helpers = tq + kTqDw;                                         // [64] bytes, four to a word
     uint8_t* const status = reinterpret_cast<uint8_t*>(helpers + kHelpDw);       // [kPoolPad] one byte per slot
     uint8_t* const list = status + kPoolPad;                                     // [kPoolPad] slot ids (< 256)
@@ -250,7 +239,7 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
     // (the accumulators sit at the very end of the workgroup's LDS: megakernel_lds_bytes adds room for them)
     // (u32: a wave spends at most a few million cycles in a region per launch; 76 bytes fit the slack of the product's
     // allocation granule, so this build keeps the product's 16 workgroups per CU)
-    uint32_t* const rt_acc = lds + (megakernel_lds_dwords(POOLN, P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris) - uint32_t(kNumRegions));
+    uint32_t* const rt_acc = lds + (megakernel_lds_dwords(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris) - uint32_t(kNumRegions));
     if (lane < uint32_t(kNumRegions)) rt_acc[lane] = 0u;
     unsigned long long rt_prev = __builtin_amdgcn_s_memtime();
     const unsigned long long rt_wall0 = __builtin_amdgcn_s_memrealtime();  // 100 MHz, the same clock on every CU
@@ -266,7 +255,7 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
 #endif
     // (a helper launch's waves take the scratch slots behind those of the launch they help)
     const uint32_t wave_slot = HELPER ? blockIdx.x + P.wave_base : blockIdx.x;
-    uint32_t* const gseq = P.gseq + size_t(wave_slot) * uint32_t(POOLN) * kSeqWords;
+    uint32_t* const gseq = P.gseq + size_t(wave_slot) * uint32_t(kPool) * kSeqWords;
     if (HELPER) {
         // registered BEFORE the first draw from the counters: a helper wave that holds work is counted in helper_words[0] by
         // the time the launch's last work item is handed out, and the resolve waits for that count to return to zero
@@ -291,9 +280,9 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
             }
         }
     }
-#define POOL(f, s) pool[(f) * POOLN + (s)]
+#define POOL(f, s) pool[(f) * kPool + (s)]
 
-    for (uint32_t s = lane; s < kPoolPad; s += 64) status[s] = s < uint32_t(POOLN) ? ST_EMPTY : ST_BUSY;  // pad slots never match
+    for (uint32_t s = lane; s < kPoolPad; s += 64) status[s] = s < uint32_t(kPool) ? ST_EMPTY : ST_BUSY;  // pad slots never match
     cell[lane] = kNoHitKey;
     if (lane < kHelpDw) helpers[lane] = 0u;
     // scene tables behind the stacks
@@ -427,7 +416,7 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                         closest = length(t_o - pc);
                     }
                 }
-                if (t_best > eps && t_best < 100000.0f && (!RBRT_SPHERE_BOUND || t_best_idx != 0xFFFFFFFFu)) {  // triangle.rs:405
+                if (t_best > eps && t_best < 100000.0f && t_best_idx != 0xFFFFFFFFu) {  // triangle.rs:405
                     const V3 p = t_o + t_best * t_d;
                     const float dist = length(t_o - p);
                     if (dist > P.min_dist && dist < P.max_dist) {
@@ -460,7 +449,7 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
         if (STATS) ++dg_census, dg_dr_rounds += more_work ? 0u : 1u;
 #if RBRT_REGION_TIMERS
         if (!more_work) {
-            if (rt_dr_rounds == 0) rt_dr_live = uint32_t(POOLN) - cnt[ST_EMPTY];  // paths in hand when the work ran out
+            if (rt_dr_rounds == 0) rt_dr_live = uint32_t(kPool) - cnt[ST_EMPTY];  // paths in hand when the work ran out
             ++rt_dr_rounds;
         }
 #endif
@@ -500,7 +489,6 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                                      __uint_as_float(md[MD_RADIUS]), P.eps_frac);
                     t_best = 1000000.0f;  // triangle.rs:398
                     t_best_idx = 0;
-#if RBRT_SPHERE_BOUND
                     // A ray that has hit a sphere (or an earlier mesh) already can only take a triangle that is CLOSER (scene.rs:37): the
                     // search starts at that distance instead of 1e6. The mesh's distance is length(o - (o + t d))
                     // with |d| = 1 to a few ulps, i.e. t up to rounding of the order 1e-7 (t + |o|); the bound is
@@ -518,7 +506,6 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                             if (bound < 100000.0f) t_best = bound, t_best_idx = 0xFFFFFFFFu;
                         }
                     }
-#endif
                     // (a degenerate ray -- NaN / inf / zero direction -- takes no mesh hit, like the reference's ordered
                     // compares give it none: its walk does not start, and the bound below eps fails the accept test)
                     const bool r_ok = ray_is_traversable(t_o, t_d);
@@ -549,11 +536,8 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
 
         // Traverse while the lanes are well filled; shade when they are not (that is what parks new
         // rays) or when shading work has piled up to a full wave.
-        // (once the work items have run out -- the drain -- there is nothing to keep lanes filled FOR: what counts
-        // is how few, and how full, the remaining rounds are. drain_mode bit 1: all traversals first.)
         const bool drain = !more_work;
-        const bool traverse = n_active != 0 && (best == 0 || (n_active >= P.y_low_water && best < 64u) ||
-                                                (drain && (P.drain_mode & 2u)));
+        const bool traverse = n_active != 0 && (best == 0 || (n_active >= P.y_low_water && best < 64u));
         if (traverse) {
             if (STATS) {
                 ++dg_pass[ST_TRAV];
@@ -566,14 +550,16 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
             // leave as soon as enough lanes are idle to make a refill / shading pass worthwhile; when no
             // other work exists, as soon as one lane has a result (it creates shading work)
             const uint32_t y_keep = cnt[ST_TRAV] >= P.y_high_min_parked ? P.y_high_water : P.y_low_water;
-            // (drain_mode bit 0: in the drain a burst runs until every lane has finished)
-            const uint32_t keep = (drain && (P.drain_mode & 1u)) ? 1u
+            // (once the work items have run out -- the drain -- there is nothing to keep lanes filled FOR: what counts is
+            // how few, and how full, the remaining rounds are, so a burst in the drain runs until every lane has finished)
+            const uint32_t keep = drain ? 1u
                                   : (best != 0 || cnt[ST_TRAV] != 0) ? (n_active < y_keep ? n_active : y_keep)
                                                                      : n_active;
             // (traversals are shared in the drain only: before it, a parked ray uses an idle lane better, and the
             // per-step bookkeeping of sharing costs more than the lanes it fills)
-            const bool share = SHAREK && P.share_idle != 0u && drain;
-            // (two copies of the loop: the bulk of a frame runs the one without any of the sharing code)
+            const bool share = P.share_idle != 0u && drain;
+            // (two copies of the loop: the bulk of a frame runs the one without any of the sharing code. One loop that
+            // tested `share` per step cost the bulk 3-5 %: register allocation at the 128-VGPR limit)
             auto burst = [&](auto share_tag) {
             constexpr bool SHARE = decltype(share_tag)::value;
         RBRT_MARK(burst_top);
@@ -723,17 +709,8 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                     }
                 }
         RBRT_MARK(walk);
-#ifdef RBRT_DUMMY_WALK  // calibration experiment: N extra full-rate VALU instructions per traversal step (the result is unused)
-                {
-                    float dummy = __uint_as_float(t_sp);
-#pragma unroll
-                    for (int i = 0; i < RBRT_DUMMY_WALK; ++i) asm volatile("v_add_f32 %0, %0, %0" : "+v"(dummy));
-                    asm volatile("" ::"v"(dummy));
-                }
-#endif
                 if (can_walk) {
                     uint32_t k[4];
-#if RBRT_PUSH_ORDER == 0 && RBRT_PAIR_SORT
                     int32_t sl[4];
                     node4_visit_sorted(t_nodes + t_cur, t_rc, eps, t_best, k, sl);
                     if (STATS) ++lc.nodes;
@@ -746,35 +723,6 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                     } else {
                         t_cur = t_sp != 0 ? pop() : kNoChild;
                     }
-#else
-                    f32x4 links;
-                    node4_visit<RBRT_PUSH_ORDER == 0>(t_nodes + t_cur, t_rc, eps, t_best, k, links);
-                    if (STATS) ++lc.nodes;
-                    if (STATS && t_cur == 0 && k[0] == kMissKey) ++dg_root_only;  // a traversal that ends at the root
-#if RBRT_PUSH_ORDER == 0
-                    if (k[0] != kMissKey) {  // farthest first, so that the nearest is popped first
-                        if (k[3] != kMissKey) push(link_of(links, k[3]));
-                        if (k[2] != kMissKey) push(link_of(links, k[2]));
-                        if (k[1] != kMissKey) push(link_of(links, k[1]));
-                        t_cur = link_of(links, k[0]);
-                    } else {
-                        t_cur = t_sp != 0 ? pop() : kNoChild;
-                    }
-#else
-                    // the nearest child next, the other hit children onto the stack in slot order (no sort, no
-                    // per-entry link selection); keys are distinct (the slot is in their low bits)
-                    const uint32_t kmin = min(min(k[0], k[1]), min(k[2], k[3]));
-                    if (kmin != kMissKey) {
-                        if (k[0] != kMissKey && k[0] != kmin) push(__float_as_int(links.x));
-                        if (k[1] != kMissKey && k[1] != kmin) push(__float_as_int(links.y));
-                        if (k[2] != kMissKey && k[2] != kmin) push(__float_as_int(links.z));
-                        if (k[3] != kMissKey && k[3] != kmin) push(__float_as_int(links.w));
-                        t_cur = link_of(links, kmin);
-                    } else {
-                        t_cur = t_sp != 0 ? pop() : kNoChild;
-                    }
-#endif
-#endif
                 }
                 if (t_active && t_cur == kNoChild && t_pend == kNoChild) {
                     if (!SHARE) {  // (no helpers exist outside shared bursts: the registers hold the result)
@@ -827,7 +775,7 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
             for (uint32_t g = 0; g < kPoolPad; g += 64) {
                 const bool m = status[g + lane] == ST_EMPTY;
                 const uint64_t mask = wballot(m);
-                if (m) list[c0 + c1 + lane_rank(mask)] = uint8_t(g + lane);  // c0 + c1 <= POOLN
+                if (m) list[c0 + c1 + lane_rank(mask)] = uint8_t(g + lane);  // c0 + c1 <= kPool
                 c1 += uint32_t(__popcll(mask));
             }
         }
@@ -915,9 +863,6 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                 uint32_t new_lo = 0, new_hi = 0;
                 if (avail < n_want) {
                     more_work = work.template next_chunk<HELPER>(P, lane, new_lo, new_hi);
-                    // drain_mode bit 3: a wave whose launch has run out of work items issues ahead of the bulk waves of
-                    // other launches on its SIMD: the drain is a chain of dependent rounds, the bulk fills the gaps
-                    if (!more_work && (P.drain_mode & 8u)) __builtin_amdgcn_s_setprio(2);
                     if (STATS && !more_work) dg_rt_workout = __builtin_amdgcn_s_memrealtime();
 #if RBRT_REGION_TIMERS
                     if (!more_work) rt_wall_workout = __builtin_amdgcn_s_memrealtime();

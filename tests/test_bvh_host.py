@@ -9,7 +9,7 @@ import scenes
 from rbrt_amd import abi
 
 NO_CHILD = -2 ** 31
-LEAF_BITS = 2  # device_types.h kLeafBits (RBRT_LEAF_BITS)
+LEAF_BITS = 2  # device_types.h kLeafBits
 LEAF_MAX = 1 << LEAF_BITS
 
 

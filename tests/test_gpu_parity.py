@@ -222,11 +222,11 @@ def test_pipelined_launches_match_unpipelined(hip, oracle, monkeypatch, depth):
 
 
 @pytest.mark.parametrize("env", [{"RBRT_SHARE_IDLE": "0"}, {"RBRT_SHARE_IDLE": "1"}, {"RBRT_SHARE_IDLE": "48"},
-                                 {"RBRT_SHARE_IDLE": "1", "RBRT_LDS_STACK": "1"}, {"RBRT_SHARE_BELOW": "0"}])
+                                 {"RBRT_SHARE_IDLE": "1", "RBRT_LDS_STACK": "1"}])
 def test_shared_traversals_do_not_change_the_image(hip, oracle, monkeypatch, env):
     """In the drain idle lanes take over stack entries of busy ones (megakernel.inl, "shared traversal"): whoever
-    walks which subtree, the image is the oracle's. Covers the build without sharing (RBRT_SHARE_BELOW=0), sharing
-    switched off and at its most eager, and given-away entries that live in the global overflow of the stack."""
+    walks which subtree, the image is the oracle's. Covers sharing switched off (RBRT_SHARE_IDLE=0) and at its most
+    eager, and given-away entries that live in the global overflow of the stack."""
     import torch
     cam = scenes.camera(oracle, 96, 64)
     sc = scenes.example_scene(oracle, 3000)
@@ -243,7 +243,7 @@ def test_shared_traversals_do_not_change_the_image(hip, oracle, monkeypatch, env
         assert_same_image(out.cpu().numpy(), exp, f"{env} (counting build)")
         given = hs.debug_counters()["shared_entries_given"]
         hs.check()
-    sharing = env.get("RBRT_SHARE_IDLE") != "0" and "RBRT_SHARE_BELOW" not in env
+    sharing = env.get("RBRT_SHARE_IDLE") != "0"
     assert (given > 0) == sharing, (env, given)
 
 

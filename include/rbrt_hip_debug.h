@@ -7,28 +7,32 @@
  * mesh gate) and so that bench.py can time the trace kernel with events on the stream it really runs on.
  *
  * Lab knobs (environment, read by rbrt_hip_scene_create ONLY when RBRT_HIP_LAB=1; a value outside the stated range
- * makes scene_create fail with RBRT_ERR_INVALID_ARG instead of being clamped; none of them changes the image):
+ * makes scene_create fail with RBRT_ERR_INVALID_ARG instead of being clamped; none of them changes the image; the BVH
+ * knobs are also read, with the same rules, by every call of the rbrt_hip_bvh_build_* entry points below):
  *   RBRT_LDS_STACK=1..64         stack entries per lane in LDS
  *   RBRT_Y_LOW / RBRT_Y_HIGH=1..64, RBRT_Y_HIGH_PARKED=1..256   refill water marks of the traversal lanes
  *   RBRT_LEAF_ROUND=1..64, RBRT_LEAF_LEAVES=1..128              when a leaf round runs
  *   RBRT_SHARE_IDLE=0..64        idle lanes needed for a round of shared traversals in the drain (4; 0: none)
- *   RBRT_WORK_STRIPES, RBRT_WORK_STRIPES_OVERLAP=<chunks, power of two>
+ *   RBRT_WORK_STRIPES, RBRT_WORK_STRIPES_OVERLAP=0..65536, 0 or a power of two   chunks per stripe (0: contiguous shards)
  *   RBRT_SHADE_ROUNDS=1..64, RBRT_SHADE_CONT_MIN=1..64          register-resident shading rounds
  *   RBRT_WAVES_PER_CU=1..32      RBRT_PIPELINE=0..8
- *   RBRT_BVH_CT=<SAH traversal cost, 4.0>   RBRT_PLOC_RADIUS=1..256 (device builder's neighbour search)
- *   RBRT_BVH_DEVICE_MIN=<entries>, RBRT_BVH_DEVICE_ALGO=ploc|lbvh   RBRT_POISON_SAMPLES=1 (tests)
+ *   RBRT_BVH_CT=(0, 1000]        SAH cost of a node visit, in triangle tests (4.0; a finite decimal number)
+ *   RBRT_PLOC_RADIUS=1..256      the device builder's neighbour search (16)
+ *   RBRT_BVH_DEVICE_MIN=0..1073741824   meshes of this many entries or more go to the device builder (instead of the cost rule)
+ *   RBRT_BVH_DEVICE_ALGO=ploc|lbvh      RBRT_POISON_SAMPLES=0|1 (tests)
  *   RBRT_PRIMARY_CULL=0|1        the tile pass (1): tiles whose camera rays reach nothing bypass the trace kernel
  *   RBRT_TILE_TAIL_DIV=1..1024   a launch that has the GPU to itself: the share of the work list (1/n, 8) that is handed out
  *                                last, from light tiles (api.cpp list_mode_for)
  *   RBRT_OVERLAP_WAVES_PER_CU=0..16  waves per CU of a launch of a stream (0: 24 / launches side by side, rounded up, and
  *                                4 instead of 3 for a launch of 8 M work items or more)
- *   RBRT_TRACE_LAUNCHES=1        one stderr line per trace launch, tile pass and helper launch (which lane, grid, table set)
+ *   RBRT_TRACE_LAUNCHES=0|1      one stderr line per trace launch, tile pass and helper launch (which lane, grid, table set)
  *   RBRT_HELPERS=0|1|2           helper launches (elastic launches): never, by the watcher (1), one with every overlapped launch (tests)
- *   RBRT_HELPER_MIN_ITEMS=<n>    a helper wave joins only while n work items per wave are left (4096); RBRT_HELPER_ROUNDS=1..16 (4)
- *   RBRT_HELPER_MIN_LAUNCH_MI=<n> launches of n Mi work items or more get helper launches (16: smaller ones came out 1 % slower)
- *   RBRT_HELPER_MIN_FREE=1..16    helper launches only while this many wave slots per CU are free (1)
- *   RBRT_BVH_SPATIAL=0..0.6      the host builder's budget of duplicated references (spatial splits), as a share of the triangles
- *   RBRT_TRACE_CREATE=1          one stderr line per rbrt_hip_scene_create: where its time went
+ *   RBRT_HELPER_MIN_ITEMS=1..16777216   a helper wave joins only while n work items per wave are left (4096)
+ *   RBRT_HELPER_ROUNDS=1..16     helper launches one launch can be given (4)
+ *   RBRT_HELPER_MIN_LAUNCH_MI=0..4096   launches of n Mi work items or more get helper launches (16: smaller ones came out 1 % slower)
+ *   RBRT_HELPER_MIN_FREE=1..16   helper launches only while this many wave slots per CU are free (1)
+ *   RBRT_BVH_SPATIAL=[0, 0.6]    the host builder's budget of duplicated references (spatial splits), as a share of the triangles
+ *   RBRT_TRACE_CREATE=0|1        one stderr line per rbrt_hip_scene_create: where its time went
  */
 #ifndef RBRT_HIP_DEBUG_H
 #define RBRT_HIP_DEBUG_H

@@ -104,6 +104,43 @@ bool lab_u32(const char* name, long long lo, long long hi, uint32_t& dst, std::s
     dst = uint32_t(v);
     return true;
 }
+// dst = $name when set (lab mode); false + message when the whole string is not a finite number in [lo, hi] ((lo, hi]
+// with lo_open)
+bool lab_f32(const char* name, float lo, bool lo_open, float hi, float& dst, std::string& err) {
+    const char* e = lab_env(name);
+    if (!e) return true;
+    char* end = nullptr;
+    const float v = std::strtof(e, &end);
+    if (end == e || *end != '\0' || !std::isfinite(v) || v < lo || (lo_open && v == lo) || v > hi) {
+        err = std::string("lab knob ") + name + "=" + e + " is not valid (see include/rbrt_hip_debug.h)";
+        return false;
+    }
+    dst = v;
+    return true;
+}
+
+// The BVH builders' lab knobs. Parsed on the caller's thread by rbrt_hip_scene_create and by each call of the debug builders,
+// and handed to the builders (a scene's background build too) instead of being read by them.
+struct BvhKnobs {
+    BvhBuildOptions host;                 // RBRT_BVH_CT -> cost_traverse, RBRT_BVH_SPATIAL -> spatial_budget
+    int device_algo = 0;                  // RBRT_BVH_DEVICE_ALGO: 0 ploc, 1 lbvh
+    uint32_t ploc_radius = kPlocRadius;   // RBRT_PLOC_RADIUS
+};
+bool lab_bvh_knobs(BvhKnobs& k, std::string& err) {
+    if (!lab_f32("RBRT_BVH_CT", 0.0f, true, 1000.0f, k.host.cost_traverse, err) ||
+        !lab_f32("RBRT_BVH_SPATIAL", 0.0f, false, kSpatialBudget, k.host.spatial_budget, err) ||  // (the record array is sized for kSpatialBudget)
+        !lab_u32("RBRT_PLOC_RADIUS", 1, 256, k.ploc_radius, err))
+        return false;
+    if (const char* a = lab_env("RBRT_BVH_DEVICE_ALGO")) {
+        if (!std::strcmp(a, "ploc") || !std::strcmp(a, "lbvh")) {
+            k.device_algo = a[0] == 'l' ? 1 : 0;
+        } else {
+            err = std::string("lab knob RBRT_BVH_DEVICE_ALGO=") + a + " is not valid (see include/rbrt_hip_debug.h)";
+            return false;
+        }
+    }
+    return true;
+}
 
 size_t workspace_cap_bytes() {
     size_t mb = 1024;
@@ -253,6 +290,7 @@ struct rbrt_hip_scene {
     // -2.7 %, an eighth -2.8 %, a 512x384 frame -2.5 %
     uint32_t work_stripes_overlap = kStripesAuto;
     bool trace_launches = false;    // RBRT_TRACE_LAUNCHES=1 (lab): one stderr line per trace launch and per tile pass
+    bool trace_create = false;      // RBRT_TRACE_CREATE=1 (lab): where scene_create's and scene_destroy's time went
     uint32_t tile_tail_div = 8;       // RBRT_TILE_TAIL_DIV (mode 4)
     uint32_t primary_cull = 1;    // RBRT_PRIMARY_CULL (0: no tile pass, the trace kernel renders every tile)
     uint32_t shade_rounds = 1;    // RBRT_SHADE_ROUNDS (rounds while work items are left; unbounded afterwards)
@@ -297,6 +335,7 @@ struct Refine {
     std::vector<uint32_t> tri_base, n_valid;
     std::vector<uint8_t> wanted;     // per mesh: 1 = device-built, to be rebuilt
     unsigned max_threads = 0;
+    BvhBuildOptions shape;           // the tree's shape, as scene_create parsed it (this thread reads no environment)
     // out
     std::vector<void*> allocs;
     BvhTri* d_tris_new = nullptr;
@@ -331,7 +370,7 @@ struct Refine {
         if (!hip(hipMemcpyAsync(h.data(), d_tris, tri_total * sizeof(BvhTri), hipMemcpyDeviceToHost, st), "read-back of the records")) return;
         if (!hip(hipStreamSynchronize(st), "read-back of the records")) return;
         std::vector<BvhBuildResult> built(meshes.size());
-        BvhBuildOptions opt;
+        BvhBuildOptions opt = shape;
         opt.max_threads = max_threads, opt.cancel = &cancel;
         for (size_t i = 0; i < meshes.size(); ++i) {
             if (!wanted[i]) continue;
@@ -425,7 +464,7 @@ int upload(rbrt_hip_scene* s, const std::vector<T>& host, T** out) {
 // links absolute, d_tris_out[0] being record tri_base of the scene's array), normals to d_normals (may be null).
 // r->ok says whether a tree was built; on error nothing is left allocated.
 hipError_t device_build_mesh(const rbrt_mesh_t& m, BvhTri* d_tris_out, uint32_t tri_base, Normal4* d_normals, DeviceBvhResult* r,
-                             double* upload_s = nullptr) {
+                             const BvhKnobs& knobs, double* upload_s = nullptr) {
     const double t_up0 = now_s();
     const float* src[12] = {m.v0x, m.v0y, m.v0z, m.e1x, m.e1y, m.e1z, m.e2x, m.e2y, m.e2z, m.nx, m.ny, m.nz};
     float* d_soa = nullptr;
@@ -440,9 +479,7 @@ hipError_t device_build_mesh(const rbrt_mesh_t& m, BvhTri* d_tris_out, uint32_t 
     if (e == hipSuccess) {
         const DeviceMeshSoa soa = {d_soa, d_soa + stride, d_soa + 2 * stride, d_soa + 3 * stride, d_soa + 4 * stride,
                                    d_soa + 5 * stride, d_soa + 6 * stride, d_soa + 7 * stride, d_soa + 8 * stride, d_pad};
-        int algo = 0;
-        if (const char* a = lab_env("RBRT_BVH_DEVICE_ALGO")) algo = !std::strcmp(a, "lbvh") ? 1 : 0;
-        e = build_bvh_device(soa, m.n_total, d_tris_out, tri_base, r, nullptr, algo);
+        e = build_bvh_device(soa, m.n_total, d_tris_out, tri_base, r, nullptr, knobs.device_algo, knobs.ploc_radius);
     }
     if (e == hipSuccess && r->ok && d_normals)
         e = device_normals(d_soa + 9 * stride, d_soa + 10 * stride, d_soa + 11 * stride, m.n_total, d_normals, nullptr);
@@ -1041,9 +1078,11 @@ int scene_create_impl(const rbrt_scene_t* scene, int device, rbrt_hip_scene_t** 
     if (const char* e = std::getenv("RBRT_BVH_REFINE")) refine_allowed = refine_allowed && e[0] != '0';
     uint32_t device_min_tris = 0;  // (lab: a threshold on the entry count instead of the cost rule)
     bool device_min_set = false;
+    BvhKnobs bvh_knobs;
     {
         std::string err;
-        if (!lab_u32("RBRT_BVH_DEVICE_MIN", 0, 1ll << 30, device_min_tris, err)) return bail(fail(RBRT_ERR_INVALID_ARG, err));
+        if (!lab_u32("RBRT_BVH_DEVICE_MIN", 0, 1ll << 30, device_min_tris, err) || !lab_bvh_knobs(bvh_knobs, err))
+            return bail(fail(RBRT_ERR_INVALID_ARG, err));
         device_min_set = lab_env("RBRT_BVH_DEVICE_MIN") != nullptr;
     }
     std::vector<uint8_t> device_built(scene->n_meshes, 0);
@@ -1066,7 +1105,7 @@ int scene_create_impl(const rbrt_scene_t* scene, int device, rbrt_hip_scene_t** 
             DeviceBvhResult r;
             const double tb0 = now_s();
             double up = 0.0;
-            const hipError_t e = device_build_mesh(m, s->d_tris + tri_base[i], tri_base[i], d_normals, &r, &up);
+            const hipError_t e = device_build_mesh(m, s->d_tris + tri_base[i], tri_base[i], d_normals, &r, bvh_knobs, &up);
             t_upload += up, t_build += now_s() - tb0 - up;
             if (e != hipSuccess)
                 return bail(fail(e == hipErrorOutOfMemory ? RBRT_ERR_OOM : RBRT_ERR_HIP, std::string("device BVH build: ") + hipGetErrorString(e)));
@@ -1086,7 +1125,7 @@ int scene_create_impl(const rbrt_scene_t* scene, int device, rbrt_hip_scene_t** 
         }
         if (!built) {
             const double tb0 = now_s();
-            BvhBuildResult bvh = build_bvh(m);
+            BvhBuildResult bvh = build_bvh(m, bvh_knobs.host);
             if (tri_base[i] != 0)
                 for (BvhNode4& nd : bvh.nodes)
                     for (int c = 0; c < 4; ++c)
@@ -1144,6 +1183,7 @@ int scene_create_impl(const rbrt_scene_t* scene, int device, rbrt_hip_scene_t** 
         int cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
         std::string err;
         uint32_t waves_per_cu = 0, poison = 0, stripes = s->work_stripes, stripes_overlap = s->work_stripes_overlap;
+        uint32_t trace_launches = 0, trace_create = 0;
         const bool knobs_ok =
             lab_u32("RBRT_LDS_STACK", 1, kStackMax, s->stack_entries, err) &&
             lab_u32("RBRT_LEAF_ROUND", 1, 64, s->leaf_round, err) && lab_u32("RBRT_Y_HIGH", 1, 64, s->y_high_water, err) &&
@@ -1157,9 +1197,10 @@ int scene_create_impl(const rbrt_scene_t* scene, int device, rbrt_hip_scene_t** 
             lab_u32("RBRT_OVERLAP_WAVES_PER_CU", 0, 16, s->overlap_waves_per_cu, err) && lab_u32("RBRT_TILE_TAIL_DIV", 1, 1024, s->tile_tail_div, err) &&
             lab_u32("RBRT_HELPERS", 0, 2, s->helpers_mode, err) && lab_u32("RBRT_HELPER_MIN_ITEMS", 1, 1 << 24, s->helper_min_items, err) &&
             lab_u32("RBRT_HELPER_MIN_LAUNCH_MI", 0, 4096, s->helper_min_launch_mi, err) && lab_u32("RBRT_HELPER_MIN_FREE", 1, 16, s->helper_min_free_per_cu, err) &&
-            lab_u32("RBRT_HELPER_ROUNDS", 1, 16, s->helper_rounds, err);
+            lab_u32("RBRT_HELPER_ROUNDS", 1, 16, s->helper_rounds, err) && lab_u32("RBRT_TRACE_LAUNCHES", 0, 1, trace_launches, err) &&
+            lab_u32("RBRT_TRACE_CREATE", 0, 1, trace_create, err);
         if (!knobs_ok) return bail(fail(RBRT_ERR_INVALID_ARG, err));
-        s->trace_launches = lab_env("RBRT_TRACE_LAUNCHES") != nullptr;
+        s->trace_launches = trace_launches != 0u, s->trace_create = trace_create != 0u;
         if ((stripes & (stripes - 1u)) != 0u || (stripes_overlap != kStripesAuto && (stripes_overlap & (stripes_overlap - 1u)) != 0u))  // the kernel shifts
             return bail(fail(RBRT_ERR_INVALID_ARG, "lab knob RBRT_WORK_STRIPES / RBRT_WORK_STRIPES_OVERLAP must be 0 or a power of two"));
         s->work_stripes = stripes, s->work_stripes_overlap = stripes_overlap;
@@ -1179,7 +1220,7 @@ int scene_create_impl(const rbrt_scene_t* scene, int device, rbrt_hip_scene_t** 
         // lanes up front: rbrt_hip_render_device then never allocates lanes (which synchronises the device); a one-shot
         // call makes the lanes its batches will use (rbrt_hip_render)
         const double t_lanes0 = now_s();
-        if (lab_env("RBRT_TRACE_CREATE"))
+        if (s->trace_create)
             std::fprintf(stderr, "[rbrt_hip] scene_create: device %.3f ms, record array %.3f, meshes %.3f (upload %.3f, build %.3f), tables + properties %.3f\n",
                          s->create_times.hip_init_s * 1e3, (t_meshes0 - t_create0 - s->create_times.hip_init_s) * 1e3, (t_meshes1 - t_meshes0) * 1e3,
                          t_upload * 1e3, t_build * 1e3, (t_lanes0 - t_meshes1) * 1e3);
@@ -1197,6 +1238,7 @@ int scene_create_impl(const rbrt_scene_t* scene, int device, rbrt_hip_scene_t** 
         r->meshes = meshes, r->tri_base = tri_base, r->n_valid = n_valid_of, r->wanted = device_built;
         const unsigned hc = std::thread::hardware_concurrency();
         r->max_threads = std::max(1u, hc / 2u);  // (the caller's thread goes on issuing launches)
+        r->shape = bvh_knobs.host;
         Refine* rp = r.get();
         try {
             r->th = std::thread([rp]() {
@@ -1241,7 +1283,7 @@ int rbrt_hip_scene_destroy(rbrt_hip_scene_t* s) {
         for (void* p : r->allocs) (void)hipFree(p);
         r->allocs.clear();
     }
-    const bool trace_destroy = lab_env("RBRT_TRACE_CREATE");
+    const bool trace_destroy = s->trace_create;
     const double td0 = now_s();
     (void)hipDeviceSynchronize();  // lane streams included
     const double td1 = now_s();
@@ -1669,6 +1711,8 @@ static int render_samples(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, const r
         if (S) HIP_TRY(hipStreamWaitEvent(ts, S->ev_lists, 0));  // (the set's tables: made on the prep stream, or at the first call on the caller's)
         const uint32_t grid = stats ? s->n_waves : grid_for(s, overlapped, depth, call_streams, company, P.n_items);
         (grid < s->n_waves ? s->n_half_grid : s->n_full_grid) += 1;
+        if (s->trace_launches)
+            std::fprintf(stderr, "[rbrt_hip] trace launch: grid %u waves on %u CUs (%u waves per CU)\n", grid, s->n_cus, s->n_waves / s->n_cus);
         if (piped) HIP_TRY(hipEventRecord(L.ev_ready, ts));  // (behind everything the launch waits for: a helper launch waits for this)
         HIP_TRY(launch_trace_megakernel(P, grid, stats, ts));
         if (piped && s->helpers_mode != 0u) {
@@ -1996,7 +2040,10 @@ int rbrt_hip_bvh_build_host(const rbrt_mesh_t* mesh, void** nodes_out, size_t* n
                             size_t* n_tris, uint32_t* max_depth, float* max_e12) {
     if (!mesh || !nodes_out || !n_nodes || !tris_out || !n_tris)
         return fail(RBRT_ERR_INVALID_ARG, "bvh_build_host: null argument");
-    BvhBuildResult r = build_bvh(*mesh);
+    BvhKnobs knobs;
+    std::string err;
+    if (!lab_bvh_knobs(knobs, err)) return fail(RBRT_ERR_INVALID_ARG, err);
+    BvhBuildResult r = build_bvh(*mesh, knobs.host);
     *n_nodes = r.nodes.size();
     *n_tris = r.tris.size();
     *nodes_out = std::malloc(std::max<size_t>(1, r.nodes.size() * sizeof(BvhNode4)));
@@ -2016,7 +2063,10 @@ int rbrt_hip_bvh_build_host_records(const void* records, size_t n, void** nodes_
                                     size_t* n_tris, uint32_t* max_depth, float* max_e12) {
     if ((!records && n) || !nodes_out || !n_nodes || !tris_out || !n_tris)
         return fail(RBRT_ERR_INVALID_ARG, "bvh_build_host_records: null argument");
-    BvhBuildResult r = build_bvh_from_records(static_cast<const BvhTri*>(records), n);
+    BvhKnobs knobs;
+    std::string err;
+    if (!lab_bvh_knobs(knobs, err)) return fail(RBRT_ERR_INVALID_ARG, err);
+    BvhBuildResult r = build_bvh_from_records(static_cast<const BvhTri*>(records), n, knobs.host);
     *n_nodes = r.nodes.size();
     *n_tris = r.tris.size();
     *nodes_out = std::malloc(std::max<size_t>(1, r.nodes.size() * sizeof(BvhNode4)));
@@ -2036,12 +2086,15 @@ int rbrt_hip_bvh_build_device(const rbrt_mesh_t* mesh, void** nodes_out, size_t*
     if (!mesh || !nodes_out || !n_nodes || !tris_out || !n_tris || !built)
         return fail(RBRT_ERR_INVALID_ARG, "bvh_build_device: null argument");
     *built = 0, *nodes_out = *tris_out = nullptr, *n_nodes = *n_tris = 0;
+    BvhKnobs knobs;
+    std::string err;
+    if (!lab_bvh_knobs(knobs, err)) return fail(RBRT_ERR_INVALID_ARG, err);
     if (int rc = ensure_device(0)) return rc;
     if (mesh->n_total < 8) return RBRT_OK;
     BvhTri* d_tris = nullptr;
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_tris), size_t(mesh->n_total) * sizeof(BvhTri)));
     DeviceBvhResult r;
-    hipError_t e = device_build_mesh(*mesh, d_tris, 0, nullptr, &r);
+    hipError_t e = device_build_mesh(*mesh, d_tris, 0, nullptr, &r, knobs);
     if (e == hipSuccess && r.ok) {
         *nodes_out = std::malloc(size_t(r.n_nodes) * sizeof(BvhNode4));
         *tris_out = std::malloc(std::max<size_t>(1, size_t(r.n_valid) * sizeof(BvhTri)));

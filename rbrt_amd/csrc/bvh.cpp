@@ -16,17 +16,7 @@ namespace rbrt {
 namespace {
 
 constexpr int kBins = 16;
-// SAH constants. On the GPU a node visit costs a dependent ~1 us fetch, a triangle test ~60 VALU
-// instructions, so leaves are allowed to fill up (<= kLeafMax) before another level is added.
-float cost_traverse() {
-    static const float v = [] {
-        const char* lab = std::getenv("RBRT_HIP_LAB");  // (a lab knob: include/rbrt_hip_debug.h)
-        const char* e = (lab && lab[0] == '1') ? std::getenv("RBRT_BVH_CT") : nullptr;
-        float x = e ? float(std::atof(e)) : 4.0f;
-        return x > 0.0f ? x : 4.0f;
-    }();
-    return v;
-}
+// SAH cost of a triangle test; a node visit costs BvhBuildOptions::cost_traverse of them (bvh.h).
 constexpr float kCostTri = 1.0f;
 // Binary inner nodes live at depths 0..kMaxInnerDepth; collapsing never deepens a path, so the
 // 4-wide tree is at most that deep too.
@@ -106,16 +96,6 @@ constexpr size_t kSlicedFrom = 32768;   // references from which a node of the T
 constexpr int kSpatialBins = 32;
 constexpr int kSpatialLostRun = 5;
 constexpr float kSpatialAlpha = 1e-4f;  // try a spatial split when the object split's children overlap by more than this share of the root's surface
-float spatial_budget_frac() {
-    static const float v = [] {
-        const char* lab = std::getenv("RBRT_HIP_LAB");  // (a lab knob: include/rbrt_hip_debug.h)
-        const char* e = (lab && lab[0] == '1') ? std::getenv("RBRT_BVH_SPATIAL") : nullptr;
-        const float x = e ? float(std::atof(e)) : kSpatialBudget;
-        return x >= 0.0f && x <= kSpatialBudget ? x : kSpatialBudget;  // (the record array is sized for kSpatialBudget)
-    }();
-    return v;
-}
-
 struct Builder {
     const rbrt_mesh_t* m = nullptr;  // the source: a mesh's SoA arrays ...
     const BvhTri* recs = nullptr;    // ... or n_recs triangle records in any order
@@ -500,7 +480,7 @@ struct Builder {
         }
         const float leaf_cost = kCostTri * float(count);
         float split_cost = std::numeric_limits<float>::infinity();
-        if (best_axis >= 0 && parent_area > 0.0f) split_cost = cost_traverse() + kCostTri * std::min(best_cost, sp_cost) / parent_area;
+        if (best_axis >= 0 && parent_area > 0.0f) split_cost = opt.cost_traverse + kCostTri * std::min(best_cost, sp_cost) / parent_area;
         if (count <= size_t(kLeafMax) && leaf_cost <= split_cost) return make_leaf(sk, refs, count, box, max_e12);
 
         std::vector<Prim> left, right;
@@ -640,7 +620,7 @@ struct Builder {
         if (const char* e = std::getenv("RBRT_BVH_THREADS")) n_threads = unsigned(std::max(1, std::atoi(e)));
         n_threads = std::min(n_threads, 16u);
         const size_t n_prims = prims.size();
-        const int64_t budget = int64_t(double(spatial_budget_frac()) * double(n_prims));
+        const int64_t budget = int64_t(double(opt.spatial_budget) * double(n_prims));
         {
             Box all;
             all.reset();

@@ -39,9 +39,16 @@ struct BvhBuildResult {
     bool cancelled = false;   // BvhBuildOptions::cancel was raised: the arrays are not a tree of the mesh
 };
 
+// SAH cost of a node visit, in triangle tests. On the GPU a node visit costs a dependent ~1 us fetch, a triangle test ~60
+// VALU instructions, so leaves are allowed to fill up (<= kLeafMax) before another level is added.
+constexpr float kCostTraverse = 4.0f;
+
 struct BvhBuildOptions {
     unsigned max_threads = 0;                    // 0: every hardware thread (at most 16; $RBRT_BVH_THREADS overrides)
     const std::atomic<bool>* cancel = nullptr;  // polled while building: a build nobody waits for any more ends early
+    // The tree's shape (lab knobs RBRT_BVH_CT and RBRT_BVH_SPATIAL, parsed by the caller: include/rbrt_hip_debug.h).
+    float cost_traverse = kCostTraverse;         // > 0
+    float spatial_budget = kSpatialBudget;       // duplicated references, as a share of the triangles: 0 .. kSpatialBudget
 };
 
 // Builds over the mesh's SoA arrays (host pointers).

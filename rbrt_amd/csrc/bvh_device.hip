@@ -237,7 +237,6 @@ __global__ __launch_bounds__(kTpb) void fit(const Work* w, Tree t, uint32_t* __r
 // neighbour within kPlocRadius positions whose union with it has the smallest surface, mutual choices merge, the
 // array is compacted (order kept) and the round repeats until one cluster is left. Unlike the radix tree, whose
 // splits are the Morton grid's, this looks at surfaces, and gives trees close to a top-down SAH build's.
-constexpr int kPlocRadius = 16;  // default search radius (RBRT_PLOC_RADIUS overrides: experiments)
 
 // The rounds of one batch are launched without the host in between: a round's cluster count is read from device memory
 // (`m_ptr`), the launches are sized by the count the host last saw (an upper bound: counts only fall).
@@ -472,7 +471,7 @@ hipError_t device_normals(const float* d_nx, const float* d_ny, const float* d_n
 
 // See bvh_device.h.
 hipError_t build_bvh_device(const DeviceMeshSoa& soa, uint32_t n_total, BvhTri* d_tris_out, uint32_t tri_base,
-                            DeviceBvhResult* res, hipStream_t stream, int algo) {
+                            DeviceBvhResult* res, hipStream_t stream, int algo, uint32_t ploc_radius) {
     res->ok = false;
     res->d_nodes = nullptr;
     const uint32_t n_tested = (n_total / 8u) * 8u;  // triangle.rs:166-167
@@ -569,9 +568,7 @@ hipError_t build_bvh_device(const DeviceMeshSoa& soa, uint32_t n_total, BvhTri* 
         hipLaunchKernelGGL(iota_kernel, dim3(blocks(n)), dim3(kTpb), 0, stream, cl[0], n);
         hipLaunchKernelGGL(ploc_seed, dim3(1), dim3(1), 0, stream, w, n);
         uint32_t* d_pm = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(w) + offsetof(Work, ploc_m));
-        uint32_t mcur = n, radius = uint32_t(kPlocRadius);
-        const char* lab = std::getenv("RBRT_HIP_LAB");  // (a lab knob: include/rbrt_hip_debug.h)
-        if (const char* e = (lab && lab[0] == '1') ? std::getenv("RBRT_PLOC_RADIUS") : nullptr) radius = uint32_t(std::min(256, std::max(1, std::atoi(e))));
+        uint32_t mcur = n, radius = ploc_radius;
         int cur = 0, rounds = 0;
         bool stalled = false;
         // (a round typically merges ~45 % of the clusters; with many ties in merged surface -- coincident or duplicate

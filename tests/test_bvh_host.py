@@ -48,16 +48,53 @@ def test_bvh4_invariants_with_spatial_splits(oracle):
     N, T, depth, me = build(md)
     assert len(T) > 6003  # some references are duplicated
     check_invariants(md, N, T, depth, me)
+    md = needle_soup(oracle)
+    N, T, depth, me = build(md)
+    assert len(T) > 2000 + 100  # the needles are cut many times
+    check_invariants(md, N, T, depth, me)
+
+
+def needle_soup(oracle):
+    """A cloud of small triangles with long needles through it (the needles are what spatial splits cut)."""
     rng = np.random.default_rng(11)
     a = rng.uniform(-1, 1, (120, 3))
     dirs = rng.normal(size=(120, 3))
     dirs /= np.linalg.norm(dirs, axis=1, keepdims=True)
     needles = np.stack([a, a + dirs * rng.uniform(0.5, 2.0, (120, 1)), a + dirs * 0.01 + rng.normal(size=(120, 3)) * 0.02], 1)
     soup = np.concatenate([scenes.random_soup(rng, 1880, extent=1.0, size=0.04), needles.astype(np.float32)])
-    md = oracle.mesh_prep(soup[rng.permutation(len(soup))])
+    return oracle.mesh_prep(soup[rng.permutation(len(soup))])
+
+
+@pytest.mark.parametrize("env", [{"RBRT_BVH_CT": "0.01"}, {"RBRT_BVH_CT": "1000"}, {"RBRT_BVH_SPATIAL": "0"},
+                                 {"RBRT_BVH_SPATIAL": "0.6"}], ids=lambda e: "-".join(f"{k}={v}" for k, v in e.items()))
+@pytest.mark.parametrize("mesh", ["rough", "needles"])
+def test_shape_knobs_keep_the_invariants_and_the_winner(oracle, monkeypatch, env, mesh):
+    """Lab knobs of the tree's shape (include/rbrt_hip_debug.h): a traversal cost at both ends of its range and no or the
+    full budget of spatial splits give other trees, with the same contract."""
+    md = scenes.standin_mesh(oracle, 3001, kind="rough", **scenes.EXAMPLE_MESH) if mesh == "rough" else needle_soup(oracle)
+    monkeypatch.setenv("RBRT_HIP_LAB", "1")
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
     N, T, depth, me = build(md)
-    assert len(T) > 2000 + 100  # the needles are cut many times
+    if env.get("RBRT_BVH_SPATIAL") == "0":
+        assert len(T) == len(np.unique(T[:, 9].view(np.uint32)))  # no duplicated reference
     check_invariants(md, N, T, depth, me)
+    check_walk_keeps_winner(oracle, md, N, T, *((600, 100) if mesh == "rough" else (1500, 30)))  # (the soup is sparse)
+
+
+def test_traversal_cost_is_read_by_every_build(oracle, monkeypatch):
+    """RBRT_BVH_CT is parsed per call (it was once cached by the first build of a process): builds of one mesh in one
+    process under two values give two trees, and the default value gives the default tree back."""
+    md = scenes.standin_mesh(oracle, 3001, **scenes.EXAMPLE_MESH)
+    monkeypatch.setenv("RBRT_HIP_LAB", "1")
+    monkeypatch.delenv("RBRT_BVH_CT", raising=False)
+    N0, T0, _, _ = build(md)
+    trees = {}
+    for ct in ("0.01", "1000", "4"):
+        monkeypatch.setenv("RBRT_BVH_CT", ct)
+        trees[ct] = build(md)
+    assert len(trees["0.01"][0]) > len(trees["1000"][0])  # a cheap node visit: more nodes
+    assert np.array_equal(trees["4"][0].view(np.uint32), N0.view(np.uint32)) and np.array_equal(trees["4"][1].view(np.uint32), T0.view(np.uint32))
 
 
 def check_invariants(md, N, T, depth, max_e12):
@@ -134,19 +171,22 @@ def test_bvh_culling_keeps_the_brute_force_winner(oracle, kind):
     N, T, _, _ = build(md)
     if kind == "rough":  # (the case spatial splits are for: some references must have been duplicated)
         assert len(T) > len(np.unique(T[:, 9].view(np.uint32)))
+    check_walk_keeps_winner(oracle, md, N, T)
+
+
+def check_walk_keeps_winner(oracle, md, N, T, n=1500, min_hits=300):
     child = N[:, 24:28].view(np.int32)
     idx = T[:, 9].view(np.uint32)
     rng = np.random.default_rng(3)
     c = ((md.bbox_lo + md.bbox_hi) / 2).astype(np.float64)
     R = float(np.linalg.norm(md.bbox_hi - md.bbox_lo) / 2)
-    n = 1500
     o = c + rng.normal(size=(n, 3)) * R * rng.choice([1.5, 4.0, 60.0], (n, 1))
     d = (c + rng.uniform(-1, 1, (n, 3)) * R * 0.9) - o
     d = d / np.linalg.norm(d, axis=1, keepdims=True) * rng.uniform(0.2, 3.0, (n, 1))
     rays = np.concatenate([o, d], 1).astype(np.float32)
     only_mesh = abi.SceneData(meshes=[md])
     t, obj, tri, _ = oracle.trace_rays(only_mesh, rays)
-    assert (obj >= 0).sum() > 300
+    assert (obj >= 0).sum() > min_hits
     eps, radius = 0.001, np.linalg.norm((md.bbox_hi - md.bbox_lo).astype(np.float64) / 2) * 1.0001
     for r in np.nonzero(obj >= 0)[0]:
         oo, dd = rays[r, :3].astype(np.float64), rays[r, 3:].astype(np.float64)

@@ -66,9 +66,22 @@ int rbrt_hip_selftest_gate(const float lo[3], const float hi[3], const float* ra
 
 /* Test hook: the image needs correctly rounded sqrt and / (vec3.rs:111-126); the kernels use short forms of them when
  * every lane's operands are in the everyday range (kernels.hip "IEEE square root and division, the short way"). Runs n
- * pseudo-random operands through the short forms and the compiler's: counts[0] / counts[1] = differing sqrt results /
- * normalize components (must be 0), counts[2] = lanes that really took the short path. */
+ * pseudo-random operands, three quarters of the waves drawn from the whole domain the gates admit, through the short forms
+ * and the compiler's: counts[0] / counts[1] = differing sqrt results / normalize components (must be 0), counts[2] = lanes
+ * whose sqrt and normalize both took the short path. */
 int rbrt_hip_selftest_ieee(uint64_t seed, size_t n, uint64_t counts[3]);
+
+/* Test hook: the kernels' ieee_sqrt of x[n] and normalize of v[m][3] (host arrays), element i in lane i % 64 of wave
+ * i / 64 (a short form runs only when every lane of the wave is inside its gate). out_sqrt[n], out_norm[m][3]: the
+ * results; out_sqrt_short[n] / out_norm_short[m]: 1 where the element's wave took the short form. */
+int rbrt_hip_debug_ieee(const float* x, size_t n, const float* v, size_t m, float* out_sqrt, uint8_t* out_sqrt_short,
+                        float* out_norm, uint8_t* out_norm_short);
+
+/* Test hook: the kernels' ieee_sqrt of every float whose bits are in [first_bits, first_bits + n) (positive normal floats
+ * only), 64 consecutive ones per wave, checked on the device: counts[0] = results that are not the correctly rounded
+ * square root (an exact integer test), counts[1] = results that differ from the compiler's sqrt, counts[2] = lanes that
+ * took the short form. */
+int rbrt_hip_selftest_sqrt_sweep(uint32_t first_bits, uint64_t n, uint64_t counts[3]);
 
 /* Diagnostic: pass statistics of the persistent megakernel from the last render with
  * RBRT_FLAG_COLLECT_STATS: out[0..5] passes per kind (empty, traverse, terminate, lambertian, metal,

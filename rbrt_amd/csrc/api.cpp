@@ -39,6 +39,9 @@ hipError_t launch_trace_rays(const TraceParams& P, const float* rays, size_t n, 
                              int32_t* out_tri, float* out_dist, hipStream_t stream);
 hipError_t launch_gate_selftest(const float* d_box, const float* d_rays, size_t n, uint8_t* d_fast, uint8_t* d_exact);
 hipError_t launch_ieee_selftest(uint64_t seed, size_t n, unsigned long long* d_counts);
+hipError_t launch_ieee_debug(const float* d_x, size_t n, const float* d_v, size_t m, float* d_sqrt, uint8_t* d_sqrt_short,
+                             float* d_norm, uint8_t* d_norm_short);
+hipError_t launch_sqrt_sweep(uint32_t first, uint64_t n, unsigned long long* d_counts);
 hipError_t launch_scatter_debug(const DevMaterial* d_mats, const float* d_in_dir, const float* d_p, const float* d_normal,
                                  const uint32_t* d_rng, size_t n, float* d_out_dir, uint8_t* d_out_ok, uint32_t* d_out_rng);
 uint64_t host_splitmix64(uint64_t x);
@@ -2152,6 +2155,55 @@ int rbrt_hip_selftest_ieee(uint64_t seed, size_t n, uint64_t counts[3]) {
     if (e == hipSuccess) e = hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost);
     (void)hipFree(d);
     if (e != hipSuccess) return fail(RBRT_ERR_HIP, std::string("selftest_ieee: ") + hipGetErrorString(e));
+    for (int k = 0; k < 3; ++k) counts[k] = h[k];
+    return RBRT_OK;
+}
+
+// Test hook: ieee_sqrt / normalize of the kernels on caller-supplied operands, with the path each element's wave took.
+int rbrt_hip_debug_ieee(const float* x, size_t n, const float* v, size_t m, float* out_sqrt, uint8_t* out_sqrt_short,
+                        float* out_norm, uint8_t* out_norm_short) {
+    if ((n && (!x || !out_sqrt || !out_sqrt_short)) || (m && (!v || !out_norm || !out_norm_short)))
+        return fail(RBRT_ERR_INVALID_ARG, "debug_ieee: null argument");
+    if (n >= (1ull << 32) * 256ull || m >= (1ull << 32) * 256ull) return fail(RBRT_ERR_INVALID_ARG, "debug_ieee: n or m too large");
+    if (n == 0 && m == 0) return RBRT_OK;
+    if (int rc = ensure_device(0)) return rc;
+    float *d_x = nullptr, *d_v = nullptr, *d_s = nullptr, *d_q = nullptr;
+    uint8_t *d_sf = nullptr, *d_qf = nullptr;
+    const size_t nx = std::max<size_t>(n, 1), nv = std::max<size_t>(m, 1);
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_x), nx * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_s), nx * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_sf), nx);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_v), nv * 3 * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_q), nv * 3 * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_qf), nv);
+    if (e == hipSuccess && n) e = hipMemcpy(d_x, x, n * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess && m) e = hipMemcpy(d_v, v, m * 3 * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = launch_ieee_debug(d_x, n, d_v, m, d_s, d_sf, d_q, d_qf);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess && n) e = hipMemcpy(out_sqrt, d_s, n * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && n) e = hipMemcpy(out_sqrt_short, d_sf, n, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && m) e = hipMemcpy(out_norm, d_q, m * 3 * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && m) e = hipMemcpy(out_norm_short, d_qf, m, hipMemcpyDeviceToHost);
+    (void)hipFree(d_x), (void)hipFree(d_s), (void)hipFree(d_sf), (void)hipFree(d_v), (void)hipFree(d_q), (void)hipFree(d_qf);
+    if (e != hipSuccess) return fail(RBRT_ERR_HIP, std::string("debug_ieee: ") + hipGetErrorString(e));
+    return RBRT_OK;
+}
+
+// Test hook: ieee_sqrt of every float with bits in [first_bits, first_bits + n), checked on the device.
+int rbrt_hip_selftest_sqrt_sweep(uint32_t first_bits, uint64_t n, uint64_t counts[3]) {
+    if (!counts) return fail(RBRT_ERR_INVALID_ARG, "selftest_sqrt_sweep: null argument");
+    if (first_bits < 0x00800000u || n > uint64_t(0x7F800000u - first_bits))
+        return fail(RBRT_ERR_INVALID_ARG, "selftest_sqrt_sweep: the range must hold positive normal floats only");
+    if (int rc = ensure_device(0)) return rc;
+    unsigned long long* d = nullptr;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), 3 * sizeof(unsigned long long)));
+    hipError_t e = hipMemset(d, 0, 3 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = launch_sqrt_sweep(first_bits, n, d);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    unsigned long long h[3] = {0, 0, 0};
+    if (e == hipSuccess) e = hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (e != hipSuccess) return fail(RBRT_ERR_HIP, std::string("selftest_sqrt_sweep: ") + hipGetErrorString(e));
     for (int k = 0; k < 3; ++k) counts[k] = h[k];
     return RBRT_OK;
 }

@@ -45,8 +45,9 @@ __device__ __forceinline__ float dot(V3 a, V3 b) { return (a.x * b.x + a.y * b.y
 // operands, v_div_scale / v_div_fixup, class checks for 0 and inf). For operands in the everyday range that
 // wrapping is the identity, and the correction steps -- reproduced below instruction for instruction -- give the same
 // bits. A wave takes the short forms when EVERY active lane's operands are in range (one compare or two per call) and
-// the compiler's forms otherwise. tests: test_short_ieee_forms_match_the_compilers (2^28 operands).
-__device__ __forceinline__ float sqrt_core(float x) {  // x in [2^-80, 2^100]: hipcc's sqrt without its scaling / class steps
+// the compiler's forms otherwise. tests: test_short_ieee_forms_match_the_compilers (2^28 operands), test_ieee_domain.py (every
+// float of sqrt_core's domain; normalize at the edges of its gate), test_ieee_model.py (the division in exact arithmetic).
+__device__ __forceinline__ float sqrt_core(float x) {  // x in (2^-80, 2^100): hipcc's sqrt without its scaling / class steps
     const float r = __builtin_amdgcn_sqrtf(x);
     const float r_dn = __uint_as_float(__float_as_uint(r) - 1u), r_up = __uint_as_float(__float_as_uint(r) + 1u);
     const float e_dn = __builtin_fmaf(-r_dn, r, x), e_up = __builtin_fmaf(-r_up, r, x);
@@ -55,22 +56,33 @@ __device__ __forceinline__ float sqrt_core(float x) {  // x in [2^-80, 2^100]: h
     return s;
 }
 __device__ __forceinline__ bool sqrt_in_range(float x) { return x > 0x1p-80f && x < 0x1p100f; }  // (false for NaN)
+// short_path: whether this lane's wave took sqrt_core (test hooks read it; the other overload drops it)
+__device__ __forceinline__ float ieee_sqrt(float x, bool& short_path) {
+    short_path = __builtin_amdgcn_ballot_w64(!sqrt_in_range(x)) == 0ull;
+    return short_path ? sqrt_core(x) : __builtin_sqrtf(x);
+}
 __device__ __forceinline__ float ieee_sqrt(float x) {
-    if (__builtin_amdgcn_ballot_w64(!sqrt_in_range(x)) == 0ull) return sqrt_core(x);
-    return __builtin_sqrtf(x);
+    bool short_path;
+    return ieee_sqrt(x, short_path);
 }
 __device__ __forceinline__ float length(V3 a) { return ieee_sqrt((a.x * a.x + a.y * a.y) + a.z * a.z); }
 __device__ __attribute__((noinline)) V3 normalize_ieee(V3 a) {  // the compiler's forms, out of line: the rare path
     const float len = __builtin_sqrtf((a.x * a.x + a.y * a.y) + a.z * a.z);
     return V3{a.x / len, a.y / len, a.z / len};
 }
-__device__ __forceinline__ V3 normalize(V3 a) {  // three divisions by the length, vec3.rs:119-126
+// normalize's gate: s = |a|^2 in (kNormSLo, kNormSHi) and every |component| > kNormMin. The upper bound is not
+// sqrt_in_range's 2^100: the short division rounds a subnormal quotient on its own, and gets about half of the quotients on
+// a subnormal midpoint wrong (x = (27 2^-104, 3 2^46, 27 2^-104): 5 2^-149 for 4 2^-149); the compiler's v_div_scale
+// scales those. len < 2^26 keeps every quotient of the short path normal. (tests: test_ieee_model.py, test_ieee_domain.py)
+constexpr float kNormSLo = 0x1p-80f, kNormSHi = 0x1p52f, kNormMin = 0x1p-100f;
+__device__ __forceinline__ V3 normalize(V3 a, bool& short_path) {  // three divisions by the length, vec3.rs:119-126
     const float s = (a.x * a.x + a.y * a.y) + a.z * a.z;
     const float mn = __builtin_fminf(__builtin_fminf(__builtin_fabsf(a.x), __builtin_fabsf(a.y)), __builtin_fabsf(a.z));
-    // in range: no scaling in sqrt; len in [2^-40, 2^50]; every |component| >= 2^-100 (so v_div_scale leaves numerator
-    // and denominator alone: exponent(num) > 23, |num/len| <= 1 is normal) and <= len; nothing is 0, inf or NaN
-    const bool ok = sqrt_in_range(s) && mn > 0x1p-100f;
-    if (__builtin_amdgcn_ballot_w64(!ok) != 0ull) return normalize_ieee(a);
+    // in range: no scaling in sqrt; len in [2^-40, 2^26); every |component| > 2^-100 and <= len, so |num/len| is in
+    // (2^-126, 1]: normal, and the residuals of the refinement are exact; nothing is 0, inf or NaN
+    const bool ok = s > kNormSLo && s < kNormSHi && mn > kNormMin;
+    short_path = __builtin_amdgcn_ballot_w64(!ok) == 0ull;
+    if (!short_path) return normalize_ieee(a);
     const float len = sqrt_core(s);
     // hipcc's fdiv, minus v_div_scale / v_div_fixup, the reciprocal refinement shared by the three numerators
     float rc = __builtin_amdgcn_rcpf(len);
@@ -88,6 +100,10 @@ __device__ __forceinline__ V3 normalize(V3 a) {  // three divisions by the lengt
         q.z = __builtin_fmaf(__builtin_fmaf(-len, v, a.z), rc, v);
     }
     return q;
+}
+__device__ __forceinline__ V3 normalize(V3 a) {
+    bool short_path;
+    return normalize(a, short_path);
 }
 __device__ __forceinline__ V3 cross(V3 a, V3 b) {
     return V3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
@@ -1223,26 +1239,36 @@ __global__ __launch_bounds__(kRaysBlock) void trace_rays_kernel(const TraceParam
 }
 
 // Test hook (rbrt_hip_selftest_ieee): the short IEEE forms (sqrt_core inside ieee_sqrt, normalize) against the
-// compiler's on pseudo-random operands. Waves 0,1,2 (mod 4) draw every lane's operands from the in-range domain, so
-// the short forms are what runs; waves 3 (mod 4) mix in zeros, denormals, huge, inf and NaN: the ballot sends those
-// waves through the compiler's forms, which must then be what comes out. counts[0] = mismatching sqrt results,
-// counts[1] = mismatching normalize components, counts[2] = lanes that took the short path (in-range waves).
+// compiler's on pseudo-random operands. Waves 0,1,2 (mod 4) draw every lane's operands from the whole domain the gates
+// admit, so the short forms are what runs: x in (2^-80, 2^100); the largest component of a in [2^-40, 2^(kNormTopExp+1))
+// (so |a|^2 is inside normalize's gate), the others from just above kNormMin up to its exponent (quotients down to the
+// smallest the gate lets through, exponent gaps far beyond 96). Waves 3 (mod 4) mix in zeros, denormals, huge, inf and
+// NaN: the ballot sends those waves through the compiler's forms, which must then be what comes out. counts[0] =
+// mismatching sqrt results, counts[1] = mismatching normalize components, counts[2] = lanes whose sqrt and normalize
+// both took the short path.
+constexpr int kNormTopExp = 24;
+static_assert(3.0f * float(1ull << (kNormTopExp + 1)) * float(1ull << (kNormTopExp + 1)) < kNormSHi,
+              "kNormTopExp: the in-range draws must stay inside normalize's gate");
 __global__ __launch_bounds__(kBlock) void ieee_selftest_kernel(uint64_t seed, size_t n, unsigned long long* counts) {
     const size_t i = size_t(blockIdx.x) * kBlock + threadIdx.x;
     if (i >= n) return;
     Rng rng;
     rng.init(seed, uint32_t(i >> 20), uint32_t(i));
     const uint32_t mode = uint32_t(i >> 6) & 3u;
-    auto draw = [&](int e_lo, int e_hi) {  // +-(1.m) * 2^e, e uniform in [e_lo, e_hi]
+    auto draw = [&](int e_lo, int e_hi) {  // +-(1.m) * 2^e, e uniform in [e_lo, e_hi]; never exactly +-2^e_lo
         const uint32_t r = rng.next_u32(), q = rng.next_u32();
         const int e = e_lo + int(q % uint32_t(e_hi - e_lo + 1));
-        return __uint_as_float((r & 0x807FFFFFu) | (uint32_t(e + 127) << 23));
+        const uint32_t m = (r & 0x007FFFFFu) == 0u && e == e_lo ? 1u : (r & 0x007FFFFFu);
+        return __uint_as_float((r & 0x80000000u) | m | (uint32_t(e + 127) << 23));
     };
     V3 a;
     float x;
     if (mode != 3u) {
-        a = mk(draw(-39, 49), draw(-39, 49), draw(-39, 49));
-        x = __builtin_fabsf(draw(-79, 99));
+        const uint32_t top = rng.next_u32() % 3u;
+        const int e_top = -40 + int(rng.next_u32() % uint32_t(kNormTopExp + 41));
+        const float big = draw(e_top, e_top);
+        a = mk(top == 0u ? big : draw(-100, e_top), top == 1u ? big : draw(-100, e_top), top == 2u ? big : draw(-100, e_top));
+        x = __builtin_fabsf(draw(-80, 99));
     } else {
         const uint32_t pick = rng.next_u32();
         a = mk(draw(-126, 127), draw(-126, 127), draw(-126, 127));
@@ -1254,13 +1280,66 @@ __global__ __launch_bounds__(kBlock) void ieee_selftest_kernel(uint64_t seed, si
         if ((pick & 48u) == 0u) x = __builtin_fabsf(specials[(pick >> 8) & 7u]);
     }
     auto same = [](float p, float q) { return __float_as_uint(p) == __float_as_uint(q) || (p != p && q != q); };
-    const float s_fast = ieee_sqrt(x), s_ref = __builtin_sqrtf(x);
-    const V3 n_fast = normalize(a), n_ref = normalize_ieee(a);
+    bool s_short, n_short;
+    const float s_fast = ieee_sqrt(x, s_short), s_ref = __builtin_sqrtf(x);
+    const V3 n_fast = normalize(a, n_short), n_ref = normalize_ieee(a);
     unsigned long long bad_s = same(s_fast, s_ref) ? 0ull : 1ull;
     unsigned long long bad_n = (same(n_fast.x, n_ref.x) ? 0ull : 1ull) + (same(n_fast.y, n_ref.y) ? 0ull : 1ull) + (same(n_fast.z, n_ref.z) ? 0ull : 1ull);
     if (bad_s) atomicAdd(&counts[0], bad_s);
     if (bad_n) atomicAdd(&counts[1], bad_n);
-    if (mode != 3u && threadIdx.x % 64 == 0) atomicAdd(&counts[2], 64ull);
+    const unsigned long long n_both = __popcll(__builtin_amdgcn_ballot_w64(s_short && n_short));
+    if (threadIdx.x % 64 == 0 && n_both) atomicAdd(&counts[2], n_both);
+}
+
+// Test hook (rbrt_hip_debug_ieee): ieee_sqrt and normalize on caller-supplied operands, element i in lane i % 64 of wave
+// i / 64, with whether that wave took the short path.
+__global__ __launch_bounds__(kBlock) void ieee_debug_kernel(const float* __restrict__ x, size_t n, const float* __restrict__ v, size_t m,
+                                                            float* out_sqrt, uint8_t* out_sqrt_short, float* out_norm, uint8_t* out_norm_short) {
+    const size_t i = size_t(blockIdx.x) * kBlock + threadIdx.x;
+    if (i < n) {
+        bool sh;
+        out_sqrt[i] = ieee_sqrt(x[i], sh);
+        out_sqrt_short[i] = sh ? 1 : 0;
+    }
+    if (i < m) {
+        bool sh;
+        const V3 q = normalize(mk(v + 3 * i), sh);
+        out_norm[3 * i] = q.x, out_norm[3 * i + 1] = q.y, out_norm[3 * i + 2] = q.z;
+        out_norm_short[i] = sh ? 1 : 0;
+    }
+}
+
+// Test hook (rbrt_hip_selftest_sqrt_sweep): ieee_sqrt of every float whose bits are in [first, first + n), each lane kSweepPerLane
+// of them, a wave 64 consecutive ones at a time. counts[0] = results that are not the correctly rounded square root by an
+// exact integer test (with x = mx 2^ex and r = mr 2^er, mx and mr integers: (2 mr - 1)^2 < 4 mx 2^(ex - 2 er) < (2 mr + 1)^2;
+// a square root is never a midpoint), counts[1] = results that differ from the compiler's sqrt, counts[2] = lanes that
+// took the short path. Positive normal x only.
+constexpr uint32_t kSweepPerLane = 32;
+__global__ __launch_bounds__(kBlock) void sqrt_sweep_kernel(uint32_t first, uint64_t n, unsigned long long* counts) {
+    const uint64_t lane = threadIdx.x % 64u, wave = (uint64_t(blockIdx.x) * kBlock + threadIdx.x) / 64u;
+    unsigned long long bad_exact = 0, bad_ref = 0, n_short = 0;
+    for (uint32_t j = 0; j < kSweepPerLane; ++j) {
+        const uint64_t k = (wave * kSweepPerLane + j) * 64u + lane;
+        if (k >= n) break;
+        const uint32_t xb = first + uint32_t(k);
+        const float x = __uint_as_float(xb);
+        bool sh;
+        const float r = ieee_sqrt(x, sh);
+        n_short += sh ? 1u : 0u;
+        const uint32_t rb = __float_as_uint(r);
+        bad_ref += rb != __float_as_uint(__builtin_sqrtf(x)) ? 1u : 0u;
+        const uint64_t mx = (xb & 0x007FFFFFu) | 0x00800000u, mr = (rb & 0x007FFFFFu) | 0x00800000u;
+        const int d = (int(xb >> 23) - 150) - 2 * (int(rb >> 23) - 150);  // ex - 2 er
+        bool ok = (rb >> 23) - 1u < 254u && d >= 0 && d <= 30;          // a positive normal r, and the scale the bounds need
+        if (ok) {
+            const uint64_t x4 = (mx << 2) << d;
+            ok = (2u * mr - 1u) * (2u * mr - 1u) < x4 && x4 < (2u * mr + 1u) * (2u * mr + 1u);
+        }
+        bad_exact += ok ? 0u : 1u;
+    }
+    if (bad_exact) atomicAdd(&counts[0], bad_exact);
+    if (bad_ref) atomicAdd(&counts[1], bad_ref);
+    if (n_short) atomicAdd(&counts[2], n_short);
 }
 
 // Test hook (rbrt_hip_selftest_gate): both forms of the mesh gate on arbitrary rays against one box.
@@ -1402,6 +1481,20 @@ hipError_t launch_gate_selftest(const float* d_box, const float* d_rays, size_t 
 hipError_t launch_ieee_selftest(uint64_t seed, size_t n, unsigned long long* d_counts) {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(ieee_selftest_kernel, dim3(uint32_t((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, nullptr, seed, n, d_counts);
+    return hipGetLastError();
+}
+hipError_t launch_ieee_debug(const float* d_x, size_t n, const float* d_v, size_t m, float* d_sqrt, uint8_t* d_sqrt_short,
+                             float* d_norm, uint8_t* d_norm_short) {
+    const size_t k = n > m ? n : m;
+    if (k == 0) return hipSuccess;
+    hipLaunchKernelGGL(ieee_debug_kernel, dim3(uint32_t((k + kBlock - 1) / kBlock)), dim3(kBlock), 0, nullptr, d_x, n, d_v, m, d_sqrt,
+                       d_sqrt_short, d_norm, d_norm_short);
+    return hipGetLastError();
+}
+hipError_t launch_sqrt_sweep(uint32_t first, uint64_t n, unsigned long long* d_counts) {
+    if (n == 0) return hipSuccess;
+    const uint64_t per_block = uint64_t(kBlock) * kSweepPerLane;
+    hipLaunchKernelGGL(sqrt_sweep_kernel, dim3(uint32_t((n + per_block - 1) / per_block)), dim3(kBlock), 0, nullptr, first, n, d_counts);
     return hipGetLastError();
 }
 hipError_t launch_scatter_debug(const DevMaterial* d_mats, const float* d_in_dir, const float* d_p, const float* d_normal,

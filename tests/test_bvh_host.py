@@ -174,16 +174,25 @@ def test_bvh_culling_keeps_the_brute_force_winner(oracle, kind):
     check_walk_keeps_winner(oracle, md, N, T)
 
 
-def check_walk_keeps_winner(oracle, md, N, T, n=1500, min_hits=300):
-    child = N[:, 24:28].view(np.int32)
-    idx = T[:, 9].view(np.uint32)
+def random_rays(md, n):
+    """n rays from near and far (1.5, 4 and 60 bounding radii) at random points of the mesh's box, unit and non-unit."""
     rng = np.random.default_rng(3)
     c = ((md.bbox_lo + md.bbox_hi) / 2).astype(np.float64)
     R = float(np.linalg.norm(md.bbox_hi - md.bbox_lo) / 2)
     o = c + rng.normal(size=(n, 3)) * R * rng.choice([1.5, 4.0, 60.0], (n, 1))
     d = (c + rng.uniform(-1, 1, (n, 3)) * R * 0.9) - o
     d = d / np.linalg.norm(d, axis=1, keepdims=True) * rng.uniform(0.2, 3.0, (n, 1))
-    rays = np.concatenate([o, d], 1).astype(np.float32)
+    return np.concatenate([o, d], 1).astype(np.float32)
+
+
+def check_walk_keeps_winner(oracle, md, N, T, n=1500, min_hits=300, rays=None):
+    """Walks the tree for every ray the scan says hits the mesh (rays: random_rays(md, n) unless given) and checks that the
+    winner's leaf is reached."""
+    child = N[:, 24:28].view(np.int32)
+    idx = T[:, 9].view(np.uint32)
+    c = ((md.bbox_lo + md.bbox_hi) / 2).astype(np.float64)
+    if rays is None:
+        rays = random_rays(md, n)
     only_mesh = abi.SceneData(meshes=[md])
     t, obj, tri, _ = oracle.trace_rays(only_mesh, rays)
     assert (obj >= 0).sum() > min_hits
@@ -253,3 +262,18 @@ def test_depth_budget_adversarial_and_oversize(oracle):
     h = C.c_void_p()
     assert abi.load_hip().rbrt_hip_scene_create(C.byref(sc), 0, C.byref(h)) == abi.RBRT_ERR_UNSUPPORTED
     assert b"8,388,608" in abi.load_hip().rbrt_hip_last_error()
+
+
+@pytest.mark.parametrize("family", ["far+1e+03", "far-3e+04", "far+1e+05", "slivers", "grid", "rough_spatial"])
+def test_culling_keeps_the_winner_on_adversarial_rays(oracle, monkeypatch, family):
+    """The pad under the rays it is tightest for (tests/cull_families.py): aimed at node faces, edges and corners and at
+    triangle edges, grazing, from 1.5 eps to 1e4 R away, over meshes far from the origin, slivers, and integer grids with
+    exact t ties between leaves."""
+    import cull_families
+    md, env = cull_families.families(oracle)[family]
+    monkeypatch.setenv("RBRT_HIP_LAB", "1")
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    N, T, depth, me = build(md)
+    check_invariants(md, N, T, depth, me)
+    check_walk_keeps_winner(oracle, md, N, T, rays=cull_families.rays(md, N, T, 1500, seed=len(family)), min_hits=100)

@@ -671,8 +671,9 @@ def test_cli_progress_checkpoint_and_resume(hip, oracle, tmp_path):
 def test_short_ieee_forms_match_the_compilers(hip):
     """The kernels take hipcc's correctly rounded sqrt and division without their range wrapping when a wave's
     operands are all in the everyday range, sharing the reciprocal refinement between the three divisions of a
-    normalize. 2^28 pseudo-random operands (three quarters in range, one quarter with zeros, denormals, huge values,
-    inf and NaN mixed in): not one bit of difference from the compiler's forms."""
+    normalize. 2^28 pseudo-random operands (three quarters drawn over the whole domain the gates admit, one quarter with
+    zeros, denormals, huge values, inf and NaN mixed in): not one bit of difference from the compiler's forms, and exactly
+    the in-range waves' lanes report that both short forms ran (tests/test_ieee_domain.py covers the domain's edges)."""
     import ctypes as C
     counts = (C.c_uint64 * 3)()
     total_fast = 0
@@ -680,7 +681,7 @@ def test_short_ieee_forms_match_the_compilers(hip):
         abi.check(abi.load_hip().rbrt_hip_selftest_ieee(seed, 1 << 27, counts))
         assert counts[0] == 0 and counts[1] == 0, list(counts)
         total_fast += counts[2]
-    assert total_fast == 2 * 3 * (1 << 27) // 4  # the in-range waves really ran the short forms' domain
+    assert total_fast == 2 * 3 * (1 << 27) // 4  # the in-range waves, and only they, ran the short forms
 
 
 @pytest.mark.parametrize("seed", range(int(__import__("os").environ.get("RBRT_FUZZ_SCENES", "16"))))

@@ -22,7 +22,12 @@ last place per step): render_scene takes the camera per call (lib.rs:75-79), and
 camera over and over (a stream of frames of a fixed view, where that pass is paid once) and is reported beside it as
 `ms_per_step_same_camera`; it is not `value`.
 
-Rank 0 prints ONE JSON line with, besides the contract's fields:
+A plain run does only what the headline needs: set-up, the timed leg (warm-up + K steps), --dump-outputs if asked, the
+result line. Everything else below (the counting pass and the roofline, the same-camera, isolated, single-frame and one-shot
+legs, the final frame's hash and the CPU baseline) runs with --full, and only there; a plain line has them as null or leaves
+them out, and says "full": false.
+
+With --full, rank 0 prints ONE JSON line with, besides the contract's fields:
   roofline     — the trace kernel's ALGORITHMIC bytes / the duration of an ISOLATED launch (a short second leg with
                  the frame pipeline off, so that a launch's HIP-event span is the cost of its own work and
                  kernel_ms <= that leg's ms per step) vs 8 TB/s HBM; beside it the figures that describe the
@@ -175,6 +180,11 @@ def setup_ipc_gather(torch, dist, np, rank, world, dev, mine, nbuf, guarded, tim
     return st
 
 
+# the options of the --full legs and what they are when not given (parse_args)
+FULL_LEG_DEFAULTS = {"cpu_col_stride": -1, "cpu_threads": 0, "isolated_steps": 8, "single_frames": 5, "one_shot": 5,
+                     "same_camera_steps": -1, "cpu_budget_s": 120.0, "check": False}
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -205,22 +215,33 @@ def parse_args():
                          "VISIBLE: the deep-BVH stress test (GPU-built tree, LDS stack overflow figures in roofline.lds_stack)")
     ap.add_argument("--mesh-scale", type=float, default=None, help="overrides the scene file's mesh scale")
     ap.add_argument("--mesh-translation", default=None, help="x,y,z: overrides the scene file's mesh translation")
-    ap.add_argument("--cpu-col-stride", type=int, default=-1,
-                    help="the CPU baseline renders every n-th image column (0 = skip the CPU baseline; 1 = the whole "
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, everything else the benchmark measures and checks: the counting pass and the "
+                         "roofline, the same-camera, isolated, single-frame and one-shot legs, the hash of a final frame of the "
+                         "configuration's camera, the CPU baseline. Without it a run does only what `value` and ms_per_step need")
+    # The options of the --full legs. Unset (None) they take the defaults in FULL_LEG_DEFAULTS; without --full only their
+    # `0 = skip` is accepted, so that a leg asked for by number is never left out quietly.
+    ap.add_argument("--cpu-col-stride", type=int, default=None,
+                    help="--full: the CPU baseline renders every n-th image column (0 = skip the CPU baseline; 1 = the whole "
                          "frame; default: the largest power-of-two fraction of the columns estimated to fit --cpu-budget-s)")
-    ap.add_argument("--cpu-threads", type=int, default=0, help="CPU baseline threads (0 = every core this process may use)")
-    ap.add_argument("--isolated-steps", type=int, default=8,
-                    help="steps of the second, unpipelined leg that times isolated trace launches for the roofline (N = 1 only; 0 = skip)")
-    ap.add_argument("--single-frames", type=int, default=5, help="blocking frames incl. D2H timed for single_frame (N = 1 only; 0 = skip)")
-    ap.add_argument("--one-shot", type=int, default=5,
-                    help="calls of the one-shot rbrt_hip_render (host arrays in, host RGB8 out: create + BVH build + render + copy + "
-                         "destroy, what the reference's one render_scene call costs end to end) timed for one_shot (N = 1 only; 0 = skip)")
-    ap.add_argument("--same-camera-steps", type=int, default=-1,
-                    help="steps of the leg that renders ONE camera over and over (the tile pass cached); -1 = as many as --steps, 0 = skip")
-    ap.add_argument("--cpu-budget-s", type=float, default=120.0,
-                    help="the CPU baseline renders the largest power-of-two fraction of the image's columns estimated to fit this many seconds")
+    ap.add_argument("--cpu-threads", type=int, default=None, help="--full: CPU baseline threads (0 = every core this process may use)")
+    ap.add_argument("--isolated-steps", type=int, default=None,
+                    help="--full: steps of the second, unpipelined leg that times isolated trace launches for the roofline "
+                         "(N = 1 only; default 8; 0 = skip)")
+    ap.add_argument("--single-frames", type=int, default=None,
+                    help="--full: blocking frames incl. D2H timed for single_frame (N = 1 only; default 5; 0 = skip)")
+    ap.add_argument("--one-shot", type=int, default=None,
+                    help="--full: calls of the one-shot rbrt_hip_render (host arrays in, host RGB8 out: create + BVH build + render + "
+                         "copy + destroy, what the reference's one render_scene call costs end to end) timed for one_shot (N = 1 only; "
+                         "default 5; 0 = skip)")
+    ap.add_argument("--same-camera-steps", type=int, default=None,
+                    help="--full: steps of the leg that renders ONE camera over and over (the tile pass cached); -1 = as many as "
+                         "--steps (default), 0 = skip")
+    ap.add_argument("--cpu-budget-s", type=float, default=None,
+                    help="--full: the CPU baseline renders the largest power-of-two fraction of the image's columns estimated to "
+                         "fit this many seconds (default 120)")
     ap.add_argument("--init-timeout-s", type=float, default=180.0, help="N > 1: limit for the process group's rendezvous and for every collective")
-    ap.add_argument("--check", action="store_true", help="also compare the sampled columns with the GPU image")
+    ap.add_argument("--check", action="store_true", help="--full: also compare the sampled columns with the GPU image")
     ap.add_argument("--emulate-rank-of", type=int, default=0, metavar="WORLD",
                     help="single process: time only rank 0's share of a WORLD-GPU run (its tiles, no gather); a "
                          "scaling estimate for one-GPU boxes, not a benchmark result")
@@ -248,6 +269,13 @@ def parse_args():
         ap.error("--warmup must not be negative")
     if args.dump_outputs and args.emulate_all:
         ap.error("--dump-outputs has no single timed path to dump with --emulate-all")
+    if not args.full:
+        asked = [f"--{k.replace('_', '-')}" for k in FULL_LEG_DEFAULTS if getattr(args, k) not in (None, 0)]
+        if asked:
+            ap.error(f"{', '.join(asked)}: only a --full run makes what {'these ask' if len(asked) > 1 else 'it asks'} for")
+    for k, v in FULL_LEG_DEFAULTS.items():
+        if getattr(args, k) is None:
+            setattr(args, k, v)
     return args
 
 
@@ -522,18 +550,20 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # ---- counting pass (untimed): the work counters behind the algorithmic-bytes figure ----------
-    stats_opts = abi.default_opts(spp=spp, seed=args.seed, tile_rank=args.emulate_rank if emu else rank, tile_world=emu if emu else world,
-                                  flags=abi.FLAG_COLLECT_STATS)
-    n_out = rbrt_amd.packed_pixels(W, H, rank, world) * 3 if world > 1 else W * H * 3
-    scratch = torch.empty(n_out, dtype=torch.float32, device=dev)
-    scene.render_device(cam, stats_opts, scratch.data_ptr(), None, stream)
-    torch.cuda.synchronize()
-    st = scene.stats()
-    dbg_all = scene.debug_counters()
-    sinfo = scene.info()
-    dbg = dbg_all if os.environ.get("RBRT_BENCH_DEBUG") else None
-    del scratch
+    # ---- counting pass (untimed, --full): the work counters behind the algorithmic-bytes figure ----------
+    dbg = None
+    if args.full:
+        stats_opts = abi.default_opts(spp=spp, seed=args.seed, tile_rank=args.emulate_rank if emu else rank, tile_world=emu if emu else world,
+                                      flags=abi.FLAG_COLLECT_STATS)
+        n_out = rbrt_amd.packed_pixels(W, H, rank, world) * 3 if world > 1 else W * H * 3
+        scratch = torch.empty(n_out, dtype=torch.float32, device=dev)
+        scene.render_device(cam, stats_opts, scratch.data_ptr(), None, stream)
+        torch.cuda.synchronize()
+        st = scene.stats()
+        dbg_all = scene.debug_counters()
+        sinfo = scene.info()
+        dbg = dbg_all if os.environ.get("RBRT_BENCH_DEBUG") else None
+        del scratch
 
     def max_over_ranks(x):
         if world == 1:
@@ -653,7 +683,7 @@ def main():
     # ---- the same camera over and over (a stream of frames of one view: the tile pass is paid once) ----
     same = None
     n_same = args.steps if args.same_camera_steps < 0 else args.same_camera_steps
-    if n_same > 0:
+    if args.full and n_same > 0:
         s_el, _, s_tr, _, s_nl, s_mix = guarded(lambda: timed_leg(args.warmup, n_same, False))
         same = {"steps": n_same, "ms_per_step": s_el / n_same * 1e3, "kernel_ms_pipelined": s_tr / max(1, s_nl),
                 "launch_mix": {"full_grid": s_mix[0], "half_grid": s_mix[1]}}
@@ -662,7 +692,7 @@ def main():
     # with its neighbours (it is a latency, and can exceed ms_per_step); the roofline's denominator is the
     # duration of a launch that has the GPU to itself, measured here with HIP events on the launch's own stream.
     iso = None
-    if world == 1 and not emu and args.isolated_steps > 0 and args.pipeline != 1:
+    if args.full and world == 1 and not emu and args.isolated_steps > 0 and args.pipeline != 1:
         scene.set_pipeline(1)
         step()
         fence()
@@ -682,7 +712,7 @@ def main():
     # rendered with the quantisation done on the device and 2.4 MB go over PCIe; and, as in rounds 1-2, the fp32 radiance
     # (9.4 MB), which the reference never exposes.
     single = None
-    if world == 1 and not emu and args.single_frames > 0:
+    if args.full and world == 1 and not emu and args.single_frames > 0:
         host_img = torch.empty((H, W, 3), dtype=torch.float32).pin_memory()
         host_rgb = torch.empty((H, W, 3), dtype=torch.uint8).pin_memory()
         rgb8 = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
@@ -716,7 +746,7 @@ def main():
     # scene arrays to the host's RGB8 image -- scene upload, BVH build, lanes, tile pass, render, quantisation, copy,
     # release -- of a camera the library has not seen. Nothing of it is in `value`.
     one_shot = None
-    if world == 1 and not emu and args.one_shot > 0:
+    if args.full and world == 1 and not emu and args.one_shot > 0:
         torch.cuda.synchronize()
         rad1, _ = rbrt_amd.render_scene(cam, spp, host_scene, seed=args.seed)  # (untimed: the configuration's camera, for the hash)
         first = rbrt_amd.last_render_times()
@@ -748,8 +778,9 @@ def main():
                             "call, whose parts the *_ms fields are; the HIP runtime is up already (first_call_ms: this process's first such call, with the radiance copied too)"}
         del rad1
 
-    # the frame whose hash is reported: the configuration's own camera, rendered last (untimed)
-    guarded(lambda: (step(False, final=True), fence()))
+    # the frame whose hash is reported (--full): the configuration's own camera, rendered last (untimed)
+    if args.full:
+        guarded(lambda: (step(False, final=True), fence()))
     if world > 1 and ipc["ok"]:  # rank 0 lets go of the peers' buffers before the peers (who end here) free them
         import gc
         for key in ("peer_mine", "peer_rendered", "consumed_by_rank0"):
@@ -762,125 +793,128 @@ def main():
             dist.destroy_process_group()
         return
 
-    import hashlib
-    image_sha = hashlib.sha256(image.cpu().numpy().tobytes()).hexdigest()[:16]
-    if os.environ.get("RBRT_PRIMARY_CULL") == "0" and os.environ.get("RBRT_HIP_LAB") == "1":
-        tile_pass = "off (lab knob RBRT_PRIMARY_CULL=0)"
-    else:
-        table = scene.primary_cull(cam)  # (debug hook: the table the library computes for this camera)
-        tile_pass = {"tiles": int(table.size), "background_only_tiles": int((table >> 31).sum()),
-                     "finished_by": "sky_resolve_kernel (streaming), the rest by trace_megakernel + resolve_kernel",
-                     # every timed step renders a camera the library has not seen: primary_cull_kernel + tile_lists_kernel
-                     # run inside the timed region, every step (ms_per_step_same_camera: the leg where they are cached)
-                     "in_timed_region": True, "cameras_in_timed_region": args.steps}
     samples_per_step = W * H * spp
     if emu:
         samples_per_step = rbrt_amd.packed_pixels(W, H, 0, emu) * spp
     value = samples_per_step * args.steps / elapsed / 1e6
-    # dominant kernel = trace_kernel; algorithmic bytes of ONE launch on this rank (DESIGN.md "Measurement")
-    local_pixels = (rbrt_amd.packed_pixels(W, H, rank, world) if world > 1 else W * H)
-    alg_bytes = (st["nodes_visited"] * st["node_bytes"] + st["tris_tested"] * TRI_ALG_BYTES +
-                 st["mesh_hits"] * NORMAL_ALG_BYTES + local_pixels * PIXEL_ALG_BYTES)
-    pipelined_kernel_ms = trace_ms / max(1, n_launches)
-    launches_per_step = max(1, round(n_launches / max(1, args.steps)))  # > 1 when a frame needs several sample batches
-    alg_bytes = alg_bytes // launches_per_step                          # the counters cover the whole frame
-    if iso is not None:
-        kernel_ms, kernel_ms_from = iso["kernel_ms"], "isolated launches (second leg, pipeline 1)"
-    else:
-        kernel_ms = pipelined_kernel_ms
-        kernel_ms_from = ("the timed region (pipeline 1: launches do not overlap)" if args.pipeline == 1 else
-                          "the timed region, launches OVERLAP: a latency, not the cost of the work")
-    achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9 if kernel_ms > 0 else 0.0
-    roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
-                "numerator": "ALGORITHMIC bytes (SURVEY 8(d)): 128 B x BVH nodes visited + 36 B x triangles tested + 12 B x "
-                             "mesh hits + 12 B x pixels; mostly L1/L2 hits, not DRAM traffic",
-                "kernel": "trace_megakernel", "kernel_ms": round(kernel_ms, 4), "kernel_ms_from": kernel_ms_from,
-                "kernel_ms_pipelined": round(pipelined_kernel_ms, 4), "launches_timed": n_launches,
-                "algorithmic_bytes_per_launch": alg_bytes,
-                "counters": {k: st[k] for k in ("rays", "mesh_gate_pass", "nodes_visited", "tris_tested", "mesh_hits")},
-                "per_sample": {"rays": round(st["rays"] / max(1, st["samples"]), 3), "nodes_visited": round(st["nodes_visited"] / max(1, st["samples"]), 3),
-                               "tris_tested": round(st["tris_tested"] / max(1, st["samples"]), 3),
-                               "nodes_per_traversal": round(st["nodes_visited"] / max(1, st["mesh_gate_pass"]), 2)},
-                # the per-lane traversal stack: kLdsStack entries in LDS, deeper ones exactly in a per-wave global scratch
-                "lds_stack": {"entries_in_lds": int(os.environ.get("RBRT_LDS_STACK", "8")) if os.environ.get("RBRT_HIP_LAB") == "1" else 8,
-                              "tree_stack_need": sinfo.get("bvh_stack_need"),
-                              "pushes_beyond_lds": dbg_all["stack_pushes_beyond_lds"],
-                              "pushes_beyond_lds_per_traversal": round(dbg_all["stack_pushes_beyond_lds"] / max(1, st["mesh_gate_pass"]), 5),
-                              "deepest_stack": dbg_all["stack_deepest"],
-                              "bvh_builder": ("host" if not create_times["meshes_device_built"] else
-                                              f"device first ({create_times['bvh_build_s'] * 1e3:.1f} ms), the host builder's tree adopted from a "
-                                              f"background thread after {refine_s * 1e3:.0f} ms" if refine_state == 1 else "device"),
-                              "bvh_nodes": sinfo.get("n_nodes")}}
-    if iso is not None:
-        roofline["isolated_leg"] = {k: (round(v, 4) if isinstance(v, float) else v) for k, v in iso.items()}
-    # The two figures that describe the kernel as it really runs come from rocprofv3 PMC passes (their own runs of
-    # this same command, tools/profile.sh; committed under profiles/): a bench run cannot read counters itself. A
-    # summary is used only if it was measured on the kernel sources this run uses (rbrt_amd/srchash.py); otherwise the
-    # counter-derived figures are left out and the line says so.
-    if world == 1 and not emu:
-        from rbrt_amd.srchash import kernel_source_sha256
-        src_hash = kernel_source_sha256()
-        roofline["kernel_source_sha256_16"] = src_hash
-        cands = sorted((ROOT / "profiles").glob("r*_pmc_summary.json"), reverse=True)
-        rec, prof = None, None
-        for cand in cands:
-            try:
-                r = json.loads(cand.read_text())
-            except Exception:
-                continue
-            if (r.get("workload") == f"{W}x{H}x{spp}" and r.get("triangles") == args.triangles and args.mesh == "smooth" and
-                    r.get("kernel_source_sha256_16") == src_hash):
-                rec, prof = r, cand
-                break
-        if rec is None:
-            roofline["counters_stale"] = True
-            roofline["counters_note"] = ("no profiles/r*_pmc_summary.json was measured on these kernel sources "
-                                         f"(sha {src_hash}) and workload: traffic / measured_hbm / valu_issue omitted; run tools/profile.sh")
+    # ---- what --full reports besides: the final frame's hash, the tile pass's table, the roofline (None in a plain run) ----
+    image_sha = tile_pass = roofline = None
+    if args.full:
+        import hashlib
+        image_sha = hashlib.sha256(image.cpu().numpy().tobytes()).hexdigest()[:16]
+        if os.environ.get("RBRT_PRIMARY_CULL") == "0" and os.environ.get("RBRT_HIP_LAB") == "1":
+            tile_pass = "off (lab knob RBRT_PRIMARY_CULL=0)"
         else:
-            src = f"profiles/{prof.name}"
-            roofline["counters_stale"] = False
-            roofline["traffic"] = rec.get("hbm_bytes_per_launch")
-            roofline["traffic_source"] = f"{src} (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE, separate passes)"
-            if rec.get("hbm_bytes_per_launch") and kernel_ms > 0:
-                gbs = rec["hbm_bytes_per_launch"] / (kernel_ms * 1e-3) / 1e9
-                roofline["measured_hbm"] = {"bytes_per_launch": rec["hbm_bytes_per_launch"], "GBps": round(gbs, 1),
-                                            "frac": round(gbs / HBM_PEAK_GBS, 4)}
-            if rec.get("sq_insts_valu") and kernel_ms > 0:
-                # SIMD cycles per wave64 VALU instruction: measured, tools/ubench/valu_rate.hip -> profiles/r03_valu_rate.txt
-                # (plain f32 / integer VALU at four or more resident waves per SIMD; one wave alone issues one per
-                # VALU_CYCLES_ONE_WAVE cycles -- the figure rounds 1 and 2 priced the kernel with, which is a LATENCY).
-                bound_ms = rec["sq_insts_valu"] * VALU_CYCLES_PER_INST / 1024.0 / CLOCK_GHZ / 1e9 * 1e3
-                roofline["valu_issue"] = {"sq_insts_valu": rec["sq_insts_valu"], "cycles_per_inst": VALU_CYCLES_PER_INST,
-                                          "cycles_per_inst_source": "profiles/r03_valu_rate.txt (tools/ubench/valu_rate.hip)",
-                                          "simds": 1024, "clock_ghz": CLOCK_GHZ, "bound_ms": round(bound_ms, 3),
-                                          "frac": round(bound_ms / kernel_ms, 4),
-                                          "one_wave_cycles_per_inst": VALU_CYCLES_ONE_WAVE,
-                                          "valu_lane_utilisation": rec.get("valu_lane_utilisation"), "source": src}
-                if rec.get("sq_insts_salu") and rec.get("sq_insts_lds") is not None:
-                    valu_mean, mix_from = ISSUE_COST["valu_mean"], "static mix of the binary (tools/static_cost.py): 62 % full-rate, 35.5 % other, 2.5 % transcendental"
-                    vm = rec.get("valu_mix")
-                    if vm and rec["sq_insts_valu"]:
-                        # the EXECUTED mix (rocprofv3 SQ_INSTS_VALU_* in the same summary): f32 add / mul / fma issue at the full
-                        # rate, transcendentals at 6.1 cycles, the integer classes at the full rate for INT_FULL_FRAC of them (the
-                        # share of add / xor / and / or / shift among the binary's integer instructions), everything else 3.1
-                        full = vm.get("add_f32", 0) + vm.get("mul_f32", 0) + vm.get("fma_f32", 0) + INT_FULL_FRAC * vm.get("int32", 0)
-                        trans = vm.get("trans_f32", 0)
-                        other = rec["sq_insts_valu"] - full - trans
-                        valu_mean = (full * 2.0 + other * 3.1 + trans * 6.1) / rec["sq_insts_valu"]
-                        mix_from = (f"executed mix (SQ_INSTS_VALU_*): {full / rec['sq_insts_valu']:.3f} full-rate, {other / rec['sq_insts_valu']:.3f} other, "
-                                    f"{trans / rec['sq_insts_valu']:.3f} transcendental")
-                    cyc = (rec["sq_insts_valu"] * valu_mean + rec["sq_insts_salu"] * ISSUE_COST["salu"] +
-                           rec.get("sq_insts_lds", 0) * ISSUE_COST["lds"] + rec.get("sq_insts_vmem_rd", 0) * ISSUE_COST["vmem"])
-                    mix_ms = cyc / 1024.0 / CLOCK_GHZ / 1e9 * 1e3
-                    roofline["issue_mix"] = {"bound_ms": round(mix_ms, 3), "frac": round(mix_ms / kernel_ms, 4),
-                                             "cycles_per_class": {**{k: round(v, 3) for k, v in ISSUE_COST.items()}, "valu_mean": round(valu_mean, 3)},
-                                             "valu_mix_from": mix_from,
-                                             "insts": {"valu": rec["sq_insts_valu"], "salu": rec["sq_insts_salu"], "lds": rec.get("sq_insts_lds"),
-                                                       "vmem_rd": rec.get("sq_insts_vmem_rd")},
-                                             "what": "SIMD issue cycles of ALL instruction classes at their measured costs (profiles/r03_valu_rate.txt) "
-                                                     "/ 1024 SIMDs / 2.4 GHz: the bound that binds (the tree is served from L1/L2); a model "
-                                                     "good to about one digit -- read it as ~0.8, not as three figures"}
+            table = scene.primary_cull(cam)  # (debug hook: the table the library computes for this camera)
+            tile_pass = {"tiles": int(table.size), "background_only_tiles": int((table >> 31).sum()),
+                         "finished_by": "sky_resolve_kernel (streaming), the rest by trace_megakernel + resolve_kernel",
+                         # every timed step renders a camera the library has not seen: primary_cull_kernel + tile_lists_kernel
+                         # run inside the timed region, every step (ms_per_step_same_camera: the leg where they are cached)
+                         "in_timed_region": True, "cameras_in_timed_region": args.steps}
+        # dominant kernel = trace_kernel; algorithmic bytes of ONE launch on this rank (DESIGN.md "Measurement")
+        local_pixels = (rbrt_amd.packed_pixels(W, H, rank, world) if world > 1 else W * H)
+        alg_bytes = (st["nodes_visited"] * st["node_bytes"] + st["tris_tested"] * TRI_ALG_BYTES +
+                     st["mesh_hits"] * NORMAL_ALG_BYTES + local_pixels * PIXEL_ALG_BYTES)
+        pipelined_kernel_ms = trace_ms / max(1, n_launches)
+        launches_per_step = max(1, round(n_launches / max(1, args.steps)))  # > 1 when a frame needs several sample batches
+        alg_bytes = alg_bytes // launches_per_step                          # the counters cover the whole frame
+        if iso is not None:
+            kernel_ms, kernel_ms_from = iso["kernel_ms"], "isolated launches (second leg, pipeline 1)"
+        else:
+            kernel_ms = pipelined_kernel_ms
+            kernel_ms_from = ("the timed region (pipeline 1: launches do not overlap)" if args.pipeline == 1 else
+                              "the timed region, launches OVERLAP: a latency, not the cost of the work")
+        achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9 if kernel_ms > 0 else 0.0
+        roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
+                    "numerator": "ALGORITHMIC bytes (SURVEY 8(d)): 128 B x BVH nodes visited + 36 B x triangles tested + 12 B x "
+                                 "mesh hits + 12 B x pixels; mostly L1/L2 hits, not DRAM traffic",
+                    "kernel": "trace_megakernel", "kernel_ms": round(kernel_ms, 4), "kernel_ms_from": kernel_ms_from,
+                    "kernel_ms_pipelined": round(pipelined_kernel_ms, 4), "launches_timed": n_launches,
+                    "algorithmic_bytes_per_launch": alg_bytes,
+                    "counters": {k: st[k] for k in ("rays", "mesh_gate_pass", "nodes_visited", "tris_tested", "mesh_hits")},
+                    "per_sample": {"rays": round(st["rays"] / max(1, st["samples"]), 3), "nodes_visited": round(st["nodes_visited"] / max(1, st["samples"]), 3),
+                                   "tris_tested": round(st["tris_tested"] / max(1, st["samples"]), 3),
+                                   "nodes_per_traversal": round(st["nodes_visited"] / max(1, st["mesh_gate_pass"]), 2)},
+                    # the per-lane traversal stack: kLdsStack entries in LDS, deeper ones exactly in a per-wave global scratch
+                    "lds_stack": {"entries_in_lds": int(os.environ.get("RBRT_LDS_STACK", "8")) if os.environ.get("RBRT_HIP_LAB") == "1" else 8,
+                                  "tree_stack_need": sinfo.get("bvh_stack_need"),
+                                  "pushes_beyond_lds": dbg_all["stack_pushes_beyond_lds"],
+                                  "pushes_beyond_lds_per_traversal": round(dbg_all["stack_pushes_beyond_lds"] / max(1, st["mesh_gate_pass"]), 5),
+                                  "deepest_stack": dbg_all["stack_deepest"],
+                                  "bvh_builder": ("host" if not create_times["meshes_device_built"] else
+                                                  f"device first ({create_times['bvh_build_s'] * 1e3:.1f} ms), the host builder's tree adopted from a "
+                                                  f"background thread after {refine_s * 1e3:.0f} ms" if refine_state == 1 else "device"),
+                                  "bvh_nodes": sinfo.get("n_nodes")}}
+        if iso is not None:
+            roofline["isolated_leg"] = {k: (round(v, 4) if isinstance(v, float) else v) for k, v in iso.items()}
+        # The two figures that describe the kernel as it really runs come from rocprofv3 PMC passes (their own runs of
+        # this same command, tools/profile.sh; committed under profiles/): a bench run cannot read counters itself. A
+        # summary is used only if it was measured on the kernel sources this run uses (rbrt_amd/srchash.py); otherwise the
+        # counter-derived figures are left out and the line says so.
+        if world == 1 and not emu:
+            from rbrt_amd.srchash import kernel_source_sha256
+            src_hash = kernel_source_sha256()
+            roofline["kernel_source_sha256_16"] = src_hash
+            cands = sorted((ROOT / "profiles").glob("r*_pmc_summary.json"), reverse=True)
+            rec, prof = None, None
+            for cand in cands:
+                try:
+                    r = json.loads(cand.read_text())
+                except Exception:
+                    continue
+                if (r.get("workload") == f"{W}x{H}x{spp}" and r.get("triangles") == args.triangles and args.mesh == "smooth" and
+                        r.get("kernel_source_sha256_16") == src_hash):
+                    rec, prof = r, cand
+                    break
+            if rec is None:
+                roofline["counters_stale"] = True
+                roofline["counters_note"] = ("no profiles/r*_pmc_summary.json was measured on these kernel sources "
+                                             f"(sha {src_hash}) and workload: traffic / measured_hbm / valu_issue omitted; run tools/profile.sh")
+            else:
+                src = f"profiles/{prof.name}"
+                roofline["counters_stale"] = False
+                roofline["traffic"] = rec.get("hbm_bytes_per_launch")
+                roofline["traffic_source"] = f"{src} (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE, separate passes)"
+                if rec.get("hbm_bytes_per_launch") and kernel_ms > 0:
+                    gbs = rec["hbm_bytes_per_launch"] / (kernel_ms * 1e-3) / 1e9
+                    roofline["measured_hbm"] = {"bytes_per_launch": rec["hbm_bytes_per_launch"], "GBps": round(gbs, 1),
+                                                "frac": round(gbs / HBM_PEAK_GBS, 4)}
+                if rec.get("sq_insts_valu") and kernel_ms > 0:
+                    # SIMD cycles per wave64 VALU instruction: measured, tools/ubench/valu_rate.hip -> profiles/r03_valu_rate.txt
+                    # (plain f32 / integer VALU at four or more resident waves per SIMD; one wave alone issues one per
+                    # VALU_CYCLES_ONE_WAVE cycles -- the figure rounds 1 and 2 priced the kernel with, which is a LATENCY).
+                    bound_ms = rec["sq_insts_valu"] * VALU_CYCLES_PER_INST / 1024.0 / CLOCK_GHZ / 1e9 * 1e3
+                    roofline["valu_issue"] = {"sq_insts_valu": rec["sq_insts_valu"], "cycles_per_inst": VALU_CYCLES_PER_INST,
+                                              "cycles_per_inst_source": "profiles/r03_valu_rate.txt (tools/ubench/valu_rate.hip)",
+                                              "simds": 1024, "clock_ghz": CLOCK_GHZ, "bound_ms": round(bound_ms, 3),
+                                              "frac": round(bound_ms / kernel_ms, 4),
+                                              "one_wave_cycles_per_inst": VALU_CYCLES_ONE_WAVE,
+                                              "valu_lane_utilisation": rec.get("valu_lane_utilisation"), "source": src}
+                    if rec.get("sq_insts_salu") and rec.get("sq_insts_lds") is not None:
+                        valu_mean, mix_from = ISSUE_COST["valu_mean"], "static mix of the binary (tools/static_cost.py): 62 % full-rate, 35.5 % other, 2.5 % transcendental"
+                        vm = rec.get("valu_mix")
+                        if vm and rec["sq_insts_valu"]:
+                            # the EXECUTED mix (rocprofv3 SQ_INSTS_VALU_* in the same summary): f32 add / mul / fma issue at the full
+                            # rate, transcendentals at 6.1 cycles, the integer classes at the full rate for INT_FULL_FRAC of them (the
+                            # share of add / xor / and / or / shift among the binary's integer instructions), everything else 3.1
+                            full = vm.get("add_f32", 0) + vm.get("mul_f32", 0) + vm.get("fma_f32", 0) + INT_FULL_FRAC * vm.get("int32", 0)
+                            trans = vm.get("trans_f32", 0)
+                            other = rec["sq_insts_valu"] - full - trans
+                            valu_mean = (full * 2.0 + other * 3.1 + trans * 6.1) / rec["sq_insts_valu"]
+                            mix_from = (f"executed mix (SQ_INSTS_VALU_*): {full / rec['sq_insts_valu']:.3f} full-rate, {other / rec['sq_insts_valu']:.3f} other, "
+                                        f"{trans / rec['sq_insts_valu']:.3f} transcendental")
+                        cyc = (rec["sq_insts_valu"] * valu_mean + rec["sq_insts_salu"] * ISSUE_COST["salu"] +
+                               rec.get("sq_insts_lds", 0) * ISSUE_COST["lds"] + rec.get("sq_insts_vmem_rd", 0) * ISSUE_COST["vmem"])
+                        mix_ms = cyc / 1024.0 / CLOCK_GHZ / 1e9 * 1e3
+                        roofline["issue_mix"] = {"bound_ms": round(mix_ms, 3), "frac": round(mix_ms / kernel_ms, 4),
+                                                 "cycles_per_class": {**{k: round(v, 3) for k, v in ISSUE_COST.items()}, "valu_mean": round(valu_mean, 3)},
+                                                 "valu_mix_from": mix_from,
+                                                 "insts": {"valu": rec["sq_insts_valu"], "salu": rec["sq_insts_salu"], "lds": rec.get("sq_insts_lds"),
+                                                           "vmem_rd": rec.get("sq_insts_vmem_rd")},
+                                                 "what": "SIMD issue cycles of ALL instruction classes at their measured costs (profiles/r03_valu_rate.txt) "
+                                                         "/ 1024 SIMDs / 2.4 GHz: the bound that binds (the tree is served from L1/L2); a model "
+                                                         "good to about one digit -- read it as ~0.8, not as three figures"}
 
     out = {
         "metric": "Mray-samples/sec (WxHxspp/s) on bunny scene; achieved HBM GB/s vs peak",
@@ -889,7 +923,7 @@ def main():
         "ms_per_step_new_camera": round(elapsed / args.steps * 1e3, 4),  # (= ms_per_step: every timed step has a new camera)
         "ms_per_step_same_camera": round(same["ms_per_step"], 4) if same else None,
         "higher_is_better": True,
-        "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": args.full,
         "config": {"workload": f"example_scene.yaml, {args.triangles}-triangle "
                                f"{'bunny.obj' if real_asset else 'stand-in mesh' if args.mesh == 'smooth' else 'ROUGH stand-in mesh'}"
                                f"{'' if args.mesh_scale is None else f' at scale {args.mesh_scale:g} (translation {args.mesh_translation})'}, "
@@ -946,7 +980,7 @@ def main():
 
     # ---- CPU baseline (rank 0, N = 1 only): bounded sample of the same workload ---------------------
     cpu_note = ""
-    if world == 1 and args.cpu_col_stride != 0:
+    if args.full and world == 1 and args.cpu_col_stride != 0:
         from oracle import pyoracle  # the checker, used here only as the timed CPU baseline
         n_threads = args.cpu_threads or len(os.sched_getaffinity(0))  # every core this process may use
         if args.cpu_col_stride < 0:

@@ -1,5 +1,6 @@
 """bench.py --dump-outputs (no GPU): what is written for a frame within the size limit and for one beyond it, and the
-arguments it is refused with."""
+arguments it is refused with; on the GPU, that a plain run and a --full one time and dump the same frames."""
+import json
 import os
 import subprocess
 import sys
@@ -41,3 +42,41 @@ def test_a_larger_frame_is_sampled_the_same_way_every_time(tmp_path, monkeypatch
 def test_bench_refuses_arguments_it_cannot_honour(argv):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *argv], capture_output=True, text=True, timeout=120)
     assert r.returncode == 2 and "error:" in r.stderr
+
+
+@pytest.mark.parametrize("argv", [["--one-shot", "3"], ["--check"], ["--same-camera-steps", "-1"], ["--cpu-col-stride", "4", "--isolated-steps", "2"]])
+def test_a_plain_run_refuses_the_options_of_the_full_legs(argv):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *argv], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "only a --full run" in r.stderr, r.stderr[-1000:]
+    for opt in argv:
+        if opt.startswith("--"):
+            assert opt in r.stderr
+
+
+SMALL = ["--steps", "3", "--warmup", "1", "--width", "256", "--height", "192", "--spp", "6", "--triangles", "3003"]
+
+
+def _run(argv):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *argv], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-3000:]
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+def test_a_plain_run_times_and_dumps_what_a_full_run_does(tmp_path):
+    """A plain run leaves out every leg but the timed one; what it times and dumps is the --full run's frame, bit for bit."""
+    plain = _run([*SMALL, "--dump-outputs", str(tmp_path / "plain")])
+    full = _run([*SMALL, "--full", "--cpu-col-stride", "16", "--cpu-threads", "4", "--dump-outputs", str(tmp_path / "full")])
+    assert plain["full"] is False and full["full"] is True
+    for j in (plain, full):
+        assert j["steps"] == 3 and j["warmup"] == 1 and j["value"] > 0.0 and j["ms_per_step"] > 0.0
+        assert j["dumped_outputs"]["arrays"] == {"radiance": [192, 256, 3]}
+    assert plain["roofline"] is None and plain["config"]["image_sha256_16"] is None and plain["ms_per_step_same_camera"] is None
+    assert not {"same_camera_leg", "single_frame", "one_shot", "cpu_baseline"} & set(plain)
+    assert full["roofline"]["kernel_ms"] > 0.0 and full["roofline"]["isolated_leg"]["steps"] == 8
+    assert full["same_camera_leg"]["steps"] == 3 and full["single_frame"]["frames"] == 5 and full["one_shot"]["calls"] == 5
+    assert full["cpu_baseline"]["value"] > 0.0 and len(full["config"]["image_sha256_16"]) == 16
+    a, b = np.load(tmp_path / "plain" / "radiance.npy"), np.load(tmp_path / "full" / "radiance.npy")
+    assert np.array_equal(a.view(np.uint32), b.view(np.uint32))

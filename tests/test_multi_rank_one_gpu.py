@@ -128,7 +128,7 @@ def _free_port():
 
 def _bench(extra, launcher=(), env=None, expect_failure=False):
     cmd = [sys.executable, *launcher, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "1", "--width", "256", "--height", "192", "--spp", "6",
-           "--triangles", "3003", "--cpu-col-stride", "0", "--isolated-steps", "0", "--single-frames", "0", "--vary-seed", "1", *extra]
+           "--triangles", "3003", "--full", "--cpu-col-stride", "0", "--isolated-steps", "0", "--single-frames", "0", "--vary-seed", "1", *extra]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=str(ROOT), env=dict(os.environ, **(env or {})))
     if expect_failure:
         assert r.returncode != 0, r.stdout[-1500:]

@@ -30,7 +30,7 @@ def main():
                 for kv in v.split():
                     k, val = kv.split("=", 1)
                     env[k] = val
-            cmd = [sys.executable, str(ROOT / "bench.py"), "--steps", str(args.steps), "--warmup", "2",
+            cmd = [sys.executable, str(ROOT / "bench.py"), "--full", "--steps", str(args.steps), "--warmup", "2",
                    "--cpu-col-stride", "0", "--single-frames", "0", "--isolated-steps", str(args.isolated_steps)] + args.extra.split()
             p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
             if p.returncode != 0:

@@ -21,8 +21,8 @@ if [ -n "$KEXPR" ]; then
 else
   step pytest 1000 python3 -m pytest tests -m gpu -q --timeout 600
 fi
-step bench 400 python3 bench.py --steps 20 --warmup 3 --check
+step bench 400 python3 bench.py --full --steps 20 --warmup 3 --check
 cp "$OUT/bench.log" "$OUT/bench.json" 2>/dev/null
-RBRT_BENCH_DEBUG=1 step bench_dbg 300 python3 bench.py --steps 3 --warmup 1 --cpu-col-stride 0 --isolated-steps 0 --single-frames 0
+RBRT_BENCH_DEBUG=1 step bench_dbg 300 python3 bench.py --full --steps 3 --warmup 1 --cpu-col-stride 0 --isolated-steps 0 --single-frames 0
 step bench_r8 300 python3 bench.py --steps 40 --warmup 5 --cpu-col-stride 0 --emulate-rank-of 8
 echo "session done"

@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/pmc_$TAG
 rm -rf "$OUT" && mkdir -p "$OUT"
 for kv in "$@"; do export "$kv"; done
-B="python3 bench.py --steps 3 --warmup 1 --pipeline 1 --cpu-col-stride 0 --single-frames 0"
+B="python3 bench.py --full --steps 3 --warmup 1 --pipeline 1 --cpu-col-stride 0 --single-frames 0"
 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_SALU SQ_INSTS_LDS \
     --output-format csv -d "$OUT/sq" -- $B > "$OUT/b1.json" 2> "$OUT/b1.err" || tail -3 "$OUT/b1.err"
 rocprofv3 --kernel-trace --pmc TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum SQ_INSTS_VMEM_RD SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS \

@@ -3,7 +3,7 @@
 # 64-KB instruction cache two CUs share?
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/pmc_icache; rm -rf $OUT; mkdir -p $OUT
-rocprofv3 --kernel-trace --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQ_IFETCH SQ_WAIT_INST_ANY SQ_WAVE_CYCLES --output-format csv -d $OUT/p -- python3 bench.py --steps 2 --warmup 0 --pipeline 1 --cpu-col-stride 0 --single-frames 0 --one-shot 0 > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
+rocprofv3 --kernel-trace --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQ_IFETCH SQ_WAIT_INST_ANY SQ_WAVE_CYCLES --output-format csv -d $OUT/p -- python3 bench.py --full --steps 2 --warmup 0 --pipeline 1 --cpu-col-stride 0 --single-frames 0 --one-shot 0 > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
 python3 - <<'PY'
 import csv, glob, collections
 f = glob.glob("gpurun_out/pmc_icache/p/**/*counter_collection.csv", recursive=True)[0]

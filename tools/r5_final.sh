@@ -20,12 +20,12 @@ RBRT_HIP_LAB=1 RBRT_HELPERS=2 RBRT_POISON_SAMPLES=1 step forced_helpers 1000 pyt
 RBRT_FUZZ_CAMERAS=500 RBRT_FUZZ_SCENES=150 step fuzz500 1100 python3 -m pytest tests/test_primary_cull.py tests/test_gpu_parity.py -m gpu -q --timeout 1000 -k "fuzz or random"
 fi
 if want bench; then
-for i in 1 2 3; do step driver_$i 500 python3 bench.py --gpus 1 --steps 20 --warmup 5 --cpu-col-stride 0; done
-B="python3 bench.py --steps 100 --warmup 5 --cpu-col-stride 0 --single-frames 3 --one-shot 3"
+for i in 1 2 3; do step driver_$i 500 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --cpu-col-stride 0; done
+B="python3 bench.py --full --steps 100 --warmup 5 --cpu-col-stride 0 --single-frames 3 --one-shot 3"
 for cfg in 2 2r 4 4v; do step cfg_$cfg 400 $B --config $cfg; done
 fi
 if want ends; then
-E="python3 bench.py --warmup 5 --cpu-col-stride 0 --single-frames 0 --one-shot 0 --isolated-steps 0 --same-camera-steps 0 --steps 20"
+E="python3 bench.py --full --warmup 5 --cpu-col-stride 0 --single-frames 0 --one-shot 0 --isolated-steps 0 --same-camera-steps 0 --steps 20"
 for pass in 1 2 3; do
   step frame_on_$pass 300 $E; RBRT_HIP_LAB=1 RBRT_HELPERS=0 step frame_off_$pass 300 $E
   step eighth_on_$pass 300 $E --emulate-rank-of 8; RBRT_HIP_LAB=1 RBRT_HELPERS=0 step eighth_off_$pass 300 $E --emulate-rank-of 8

@@ -51,7 +51,9 @@ extern "C" {
 #define RBRT_ABI_VERSION 2 /* 2: rbrt_scene_t grew n_triangles / triangles / element_order (appended: the v1 prefix is unchanged);
                               entry points added since (rbrt_hip_tile_xy / _tile_number) change no struct and no existing call;
                               neither do RBRT_MAT_EMISSIVE and RBRT_FLAG_CONSTANT_BACKGROUND, added since (a library without
-                              them answers a kind-3 material with RBRT_ERR_INVALID_ARG) */
+                              them answers a kind-3 material with RBRT_ERR_INVALID_ARG), nor RBRT_FLAG_THIN_LENS with its
+                              rbrt_camera_lens_t (rbrt_camera_t stays as it is: the lens wraps it) and
+                              rbrt_hip_supported_flags */
 
 typedef enum rbrt_status {
     RBRT_OK = 0,
@@ -186,6 +188,31 @@ typedef struct rbrt_render_opts {
  * Honoured by rbrt_hip_render, _render_device and _render_pass; every pass of one rbrt_hip_render_pass series must use
  * the same flag and bg, as it must use the same seed. */
 #define RBRT_FLAG_CONSTANT_BACKGROUND 2u
+/* A thin lens (no counterpart in the reference, whose cam.rs:64-82 starts every ray at the position): camera rays start on
+ * an elliptic disc around the position and all rays through one point of the image plane meet on the focus surface,
+ * which gives defocus blur. With the flag, the `cam` argument of rbrt_hip_render, _render_device and _render_pass must
+ * point at the `cam` member of an rbrt_camera_lens_t (below); without it nothing past rbrt_camera_t is ever read.
+ * Every pass of one rbrt_hip_render_pass series must use the same flag and lens, as it must use the same seed.
+ * A library that does not list the bit in rbrt_hip_supported_flags() ignores it: ask before relying on it. */
+#define RBRT_FLAG_THIN_LENS 4u
+
+/* The lens of a RBRT_FLAG_THIN_LENS render. The random stream of a sample, after the column and row jitter draws that
+ * place the pinhole target T on the image plane (cam.rs:70-75), draws lens points in float32, unfused, in this order:
+ *     repeat  lx = 2 u - 1; ly = 2 u - 1      (u: the next draws of the sample's stream, x first)
+ *     until   lx lx + ly ly < 1               ((lx lx) + (ly ly), strict)
+ *     o = position + (lx lens_u + ly lens_v)  (per component (lx u_c) + (ly v_c), then the sum)
+ *     F = position + focus_scale (T - position)
+ *     d = normalize(F - o)                    (three divisions by the length)
+ * and the bounce draws follow. An all-zero lens still draws. rbrt_hip_render, _render_device and _render_pass reject a
+ * non-finite lens_u or lens_v, a focus_scale that is not finite and > 0, or a non-zero `reserved` with
+ * RBRT_ERR_INVALID_ARG before the device is touched. */
+typedef struct rbrt_camera_lens {
+    rbrt_camera_t cam;  /* first member: &lens.cam is what every render entry point receives */
+    float lens_u[3];    /* lens half-axes in scene units (the aperture radius already applied) */
+    float lens_v[3];
+    float focus_scale;  /* focus surface = the image plane scaled about cam.position by this factor */
+    uint32_t reserved;  /* 0 */
+} rbrt_camera_lens_t;
 
 #define RBRT_TILE 8u /* tile edge in pixels used for sharding and work ordering */
 /* How tiles are dealt to ranks. Tile NUMBER t (0 <= t < tiles_x * tiles_y) belongs to rank t % tile_world, and a rank's packed
@@ -318,6 +345,9 @@ void rbrt_render_opts_default(rbrt_render_opts_t* opts); /* spp = 5 (src/main.rs
 int rbrt_hip_device_count(void);                         /* >= 0, or negative status */
 const char* rbrt_hip_last_error(void);
 int rbrt_hip_abi_version(void);
+/* Mask of the RBRT_FLAG_* bits this library honours (bits it does not know are ignored, not rejected): a host tests
+ * RBRT_FLAG_THIN_LENS here before it renders with a lens. */
+uint32_t rbrt_hip_supported_flags(void);
 #ifdef __cplusplus
 }
 #endif

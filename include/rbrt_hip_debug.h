@@ -130,6 +130,9 @@ int rbrt_hip_debug_scatter(const rbrt_material_t* mats, const float* in_dir, con
  * out of reach, and every mesh: by its box, or by the boxes at the top of its tree). A set bit is a promise; tests check
  * it against the oracle's rays. Host array. */
 int rbrt_hip_debug_primary_cull(rbrt_hip_scene_t* scene, const rbrt_camera_t* cam, uint32_t* out_words, size_t n_words);
+/* The same table for the camera rays of a RBRT_FLAG_THIN_LENS render with `lens` (kernels.hip primary_cull_kernel, "Lens
+ * rays"). The lens is validated like the render entry points' (RBRT_ERR_INVALID_ARG). */
+int rbrt_hip_debug_primary_cull_lens(rbrt_hip_scene_t* scene, const rbrt_camera_lens_t* lens, uint32_t* out_words, size_t n_words);
 
 /* Kernel timing with HIP events recorded on the launch stream around every trace-kernel launch
  * (and the resolve kernel after it). set_timing(scene, 1) starts / restarts the accumulation;

@@ -36,6 +36,14 @@ pub struct RbrtCamera {
     pub position: [f32; 3], pub right: [f32; 3], pub up: [f32; 3], pub img_center_point: [f32; 3],
     pub mm_per_pix_hor: f32, pub mm_per_pix_vert: f32, pub img_width_pix: u32, pub img_height_pix: u32,
 }
+pub const RBRT_FLAG_THIN_LENS: u32 = 4;                // RbrtRenderOpts::flags: `cam` points at RbrtCameraLens::cam (defocus)
+#[repr(C)]
+pub struct RbrtCameraLens {                            // rbrt_camera_lens_t; pass &lens.cam with RBRT_FLAG_THIN_LENS
+    pub cam: RbrtCamera,
+    pub lens_u: [f32; 3], pub lens_v: [f32; 3],        // lens half-axes in scene units (radius applied)
+    pub focus_scale: f32,                              // focus surface = image plane scaled about cam.position by this
+    pub reserved: u32,                                 // 0
+}
 #[repr(C)]
 pub struct RbrtRenderOpts {
     pub spp: u32, pub max_depth: u32, pub min_dist: f32, pub max_dist: f32, pub bg: [f32; 3],
@@ -49,4 +57,5 @@ extern "C" {
                            out_radiance: *mut f32, out_rgb8: *mut u8) -> c_int;
     pub fn rbrt_hip_last_error() -> *const c_char;
     pub fn rbrt_hip_device_count() -> c_int;
+    pub fn rbrt_hip_supported_flags() -> u32;           // test RBRT_FLAG_THIN_LENS here before relying on it
 }

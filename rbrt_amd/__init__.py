@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import abi
-from .abi import (Camera, Material, RenderOpts, RbrtError, SceneData, MeshData, default_opts, load_hip,  # noqa: F401
+from .abi import (Camera, CameraLens, Material, RenderOpts, RbrtError, SceneData, MeshData, default_opts, load_hip,  # noqa: F401
                   material, MAT_DIELECTRIC, MAT_LAMBERTIAN, MAT_METAL)
 
 __all__ = ["render_scene", "HipScene", "abi", "device_count"]
@@ -23,20 +23,33 @@ def device_count() -> int:
     return int(load_hip().rbrt_hip_device_count())
 
 
+def _cam_arg(cam: abi.Camera, lens, opts: abi.RenderOpts):
+    """(camera pointer, object to keep alive) for a render call. `lens`: None (pinhole), an abi.CameraLens or a tuple
+    (lens_u, lens_v, focus_scale); with a lens the call gets `cam` inside an rbrt_camera_lens_t and RBRT_FLAG_THIN_LENS."""
+    if lens is None:
+        return C.byref(cam), cam
+    if isinstance(lens, abi.CameraLens):
+        lens = (tuple(lens.lens_u), tuple(lens.lens_v), lens.focus_scale)
+    L = abi.camera_lens(cam, *lens)
+    opts.flags |= abi.FLAG_THIN_LENS
+    return C.byref(L.cam), L
+
+
 def render_scene(cam: abi.Camera, num_samples: int, scene: abi.SceneData, seed: int = 1, want_radiance: bool = True,
-                 **opt_overrides):
+                 lens=None, **opt_overrides):
     """One-shot render through rbrt_hip_render (host buffers in and out).
 
     Same contract as the reference's render_scene (lib.rs:75-79) plus the pre-gamma radiance:
     returns (radiance float32[H,W,3], rgb8 uint8[H,W,3]); want_radiance=False: (None, rgb8), exactly what the
-    reference returns.
+    reference returns. `lens`: a thin lens (see _cam_arg), None for the reference's pinhole camera.
     """
     lib = load_hip()
     opts = default_opts(spp=num_samples, seed=seed, **opt_overrides)
+    cam_p, _keep = _cam_arg(cam, lens, opts)
     H, W = cam.img_height_pix, cam.img_width_pix
     rad = np.zeros((H, W, 3), np.float32) if want_radiance else None
     rgb = np.empty((H, W, 3), np.uint8) if not want_radiance else np.zeros((H, W, 3), np.uint8)
-    rc = lib.rbrt_hip_render(C.byref(cam), scene.ptr(), C.byref(opts), rad.ctypes.data_as(abi.f32p) if want_radiance else None,
+    rc = lib.rbrt_hip_render(cam_p, scene.ptr(), C.byref(opts), rad.ctypes.data_as(abi.f32p) if want_radiance else None,
                              rgb.ctypes.data_as(abi.u8p))
     abi.check(rc)
     return rad, rgb
@@ -77,15 +90,20 @@ class HipScene:
         self.close()
 
     def render_device(self, cam: abi.Camera, opts: abi.RenderOpts, d_radiance: int | None, d_rgb8: int | None = None,
-                      stream: int | None = None):
-        """Asynchronous render into device pointers (ints, e.g. torch.Tensor.data_ptr())."""
-        abi.check(self._lib.rbrt_hip_render_device(self._h, C.byref(cam), C.byref(opts), C.c_void_p(stream or 0),
+                      stream: int | None = None, lens=None):
+        """Asynchronous render into device pointers (ints, e.g. torch.Tensor.data_ptr()). `lens`: see _cam_arg (opts is
+        not changed: the flag goes on a copy)."""
+        opts = _opts_copy(opts)
+        cam_p, _keep = _cam_arg(cam, lens, opts)
+        abi.check(self._lib.rbrt_hip_render_device(self._h, cam_p, C.byref(opts), C.c_void_p(stream or 0),
                                                    C.c_void_p(d_radiance or 0), C.c_void_p(d_rgb8 or 0)))
 
     def render_pass(self, cam: abi.Camera, opts: abi.RenderOpts, sample_begin: int, sample_end: int, d_accum: int,
-                    d_radiance: int | None = None, d_rgb8: int | None = None, stream: int | None = None):
+                    d_radiance: int | None = None, d_rgb8: int | None = None, stream: int | None = None, lens=None):
         """Samples [sample_begin, sample_end) of opts.spp, accumulated into d_accum (rbrt_hip_render_pass)."""
-        abi.check(self._lib.rbrt_hip_render_pass(self._h, C.byref(cam), C.byref(opts), C.c_void_p(stream or 0), sample_begin,
+        opts = _opts_copy(opts)
+        cam_p, _keep = _cam_arg(cam, lens, opts)
+        abi.check(self._lib.rbrt_hip_render_pass(self._h, cam_p, C.byref(opts), C.c_void_p(stream or 0), sample_begin,
                                                  sample_end, C.c_void_p(d_accum), C.c_void_p(d_radiance or 0),
                                                  C.c_void_p(d_rgb8 or 0)))
 
@@ -192,6 +210,18 @@ class HipScene:
         abi.check(self._lib.rbrt_hip_debug_primary_cull(self._h, C.byref(cam), out.ctypes.data_as(C.POINTER(C.c_uint32)), out.size))
         return out.reshape(ty, tx)
 
+    def primary_cull_lens(self, cam, lens):
+        """The same table for the lens rays of `cam` with `lens` (rbrt_hip_debug_primary_cull_lens; test hook)."""
+        if not isinstance(lens, abi.CameraLens):
+            lens = abi.camera_lens(cam, *lens)
+        else:
+            lens = abi.camera_lens(cam, tuple(lens.lens_u), tuple(lens.lens_v), lens.focus_scale)
+        tx, ty = (cam.img_width_pix + 7) // 8, (cam.img_height_pix + 7) // 8
+        out = np.zeros(tx * ty, np.uint32)
+        abi.check(self._lib.rbrt_hip_debug_primary_cull_lens(self._h, C.byref(lens), out.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                             out.size))
+        return out.reshape(ty, tx)
+
     def trace_rays(self, rays, min_dist=0.001, max_dist=2000.0):
         rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
         n = rays.shape[0]
@@ -203,6 +233,17 @@ class HipScene:
                                                 t.ctypes.data_as(abi.f32p), obj.ctypes.data_as(abi.i32p),
                                                 tri.ctypes.data_as(abi.i32p), dist.ctypes.data_as(abi.f32p)))
         return t, obj, tri, dist
+
+
+def _opts_copy(opts: abi.RenderOpts) -> abi.RenderOpts:
+    o = abi.RenderOpts()
+    C.memmove(C.byref(o), C.byref(opts), C.sizeof(o))
+    return o
+
+
+def supported_flags() -> int:
+    """The RBRT_FLAG_* bits the library honours (rbrt_hip_supported_flags)."""
+    return int(load_hip().rbrt_hip_supported_flags())
 
 
 def debug_scatter(kind, albedo, param, in_dir, point, normal, rng_state):

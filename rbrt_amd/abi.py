@@ -32,6 +32,7 @@ MAT_EMISSIVE = 3  # albedo = emitted radiance
 
 FLAG_COLLECT_STATS = 1
 FLAG_CONSTANT_BACKGROUND = 2  # rays that hit nothing return opts.bg instead of the sky gradient
+FLAG_THIN_LENS = 4  # the camera argument is the `cam` member of a CameraLens: defocus blur (rbrt_camera_lens_t)
 TILE = 8
 
 f32p = C.POINTER(C.c_float)
@@ -89,6 +90,29 @@ class Camera(C.Structure):
         ("img_width_pix", C.c_uint32),
         ("img_height_pix", C.c_uint32),
     ]
+
+
+class CameraLens(C.Structure):
+    """rbrt_camera_lens_t: a Camera and the thin lens around its position (RBRT_FLAG_THIN_LENS). The render calls receive
+    C.byref(lens.cam), which points into this struct."""
+    _fields_ = [
+        ("cam", Camera),
+        ("lens_u", C.c_float * 3),  # lens half-axes in scene units (radius applied)
+        ("lens_v", C.c_float * 3),
+        ("focus_scale", C.c_float),  # focus surface = the image plane scaled about cam.position by this factor
+        ("reserved", C.c_uint32),
+    ]
+
+
+def camera_lens(cam: Camera, lens_u, lens_v, focus_scale: float) -> CameraLens:
+    """A CameraLens holding a copy of `cam`."""
+    L = CameraLens()
+    C.memmove(C.byref(L.cam), C.byref(cam), C.sizeof(Camera))
+    L.lens_u = _f3(lens_u)
+    L.lens_v = _f3(lens_v)
+    L.focus_scale = float(focus_scale)
+    L.reserved = 0
+    return L
 
 
 class RenderOpts(C.Structure):
@@ -162,6 +186,7 @@ HIP_SYMBOLS = {
     "rbrt_hip_abi_version": (C.c_int, []),
     "rbrt_hip_scene_set_pipeline": (C.c_int, [C.c_void_p, C.c_uint32]),
     "rbrt_hip_scene_info": (C.c_int, [C.c_void_p, C.POINTER(SceneInfo)]),
+    "rbrt_hip_supported_flags": (C.c_uint32, []),
 }
 # ... and include/rbrt_hip_debug.h (test hooks and diagnostics, same library)
 DEBUG_SYMBOLS = {
@@ -188,6 +213,7 @@ DEBUG_SYMBOLS = {
     "rbrt_hip_debug_scatter": (C.c_int, [C.POINTER(Material), f32p, f32p, f32p, C.POINTER(C.c_uint32), C.c_size_t, f32p, u8p,
                                         C.POINTER(C.c_uint32)]),
     "rbrt_hip_debug_primary_cull": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(C.c_uint32), C.c_size_t]),
+    "rbrt_hip_debug_primary_cull_lens": (C.c_int, [C.c_void_p, C.POINTER(CameraLens), C.POINTER(C.c_uint32), C.c_size_t]),
     "rbrt_hip_scene_helper_launches": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "rbrt_hip_scene_create_times": (C.c_int, [C.c_void_p, C.POINTER(CallTimes)]),
     "rbrt_hip_last_render_times": (C.c_int, [C.POINTER(CallTimes)]),
@@ -355,6 +381,8 @@ def load_host() -> C.CDLL:
     lib.rbrt_host_scene_load.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
     lib.rbrt_host_scene_camera.restype = C.POINTER(Camera)
     lib.rbrt_host_scene_camera.argtypes = [C.c_void_p]
+    lib.rbrt_host_scene_lens.restype = C.POINTER(CameraLens)
+    lib.rbrt_host_scene_lens.argtypes = [C.c_void_p]
     lib.rbrt_host_scene_scene.restype = C.POINTER(Scene)
     lib.rbrt_host_scene_scene.argtypes = [C.c_void_p]
     lib.rbrt_host_scene_free.restype = None
@@ -381,6 +409,12 @@ class HostScene:
             raise RuntimeError("rbrt_host_scene_load: " + self._lib.rbrt_host_last_error().decode(errors="replace"))
         self.camera = Camera()
         C.memmove(C.byref(self.camera), self._lib.rbrt_host_scene_camera(self._h), C.sizeof(Camera))
+        # the camera's thin lens (camera_aperture_mm > 0 in the YAML), else None
+        lp = self._lib.rbrt_host_scene_lens(self._h)
+        self.lens = None
+        if lp:
+            self.lens = CameraLens()
+            C.memmove(C.byref(self.lens), lp, C.sizeof(CameraLens))
         self.struct = self._lib.rbrt_host_scene_scene(self._h).contents
 
     def ptr(self):

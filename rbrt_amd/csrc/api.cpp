@@ -27,7 +27,7 @@ hipError_t launch_trace_megakernel(const TraceParams& P, uint32_t n_waves, bool 
 hipError_t launch_trace_helper(const TraceParams& P, uint32_t n_waves, hipStream_t stream);
 size_t megakernel_gseq_bytes(uint32_t n_waves);
 size_t megakernel_gstack_bytes(uint32_t n_waves);
-size_t megakernel_lds_bytes(uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris);
+size_t megakernel_lds_bytes(uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris, uint32_t thin_lens);
 int megakernel_occupancy_per_cu(size_t lds_bytes);
 hipError_t launch_primary_cull(const TraceParams& P, hipStream_t stream);
 hipError_t launch_sky_resolve(const TraceParams& P, const ResolveParams& R, hipStream_t stream);
@@ -208,6 +208,8 @@ struct rbrt_hip_scene {
             uint32_t rank, world;
             uint32_t list_mode;  // the order of the work list (tile_lists_kernel): by the kind of launch, list_mode_for()
             float min_dist;      // the tree boxes of the pass are grown by a pad that holds 1 / min_dist (TraceParams::eps_frac)
+            uint32_t thin_lens;  // RBRT_FLAG_THIN_LENS and its lens (all zero for a pinhole camera)
+            float lens_u[3], lens_v[3], focus_scale;
         };
         struct TileSet {
             uint32_t* d_cull = nullptr;    // [n_tiles]
@@ -804,6 +806,28 @@ int check_material(const rbrt_material_t& m, const char* what, size_t index) {
     return RBRT_OK;
 }
 
+// RBRT_FLAG_THIN_LENS: the rbrt_camera_lens_t that `cam` is the first member of must hold a finite lens, a finite
+// focus_scale > 0 and reserved == 0. Non-zero (after fail()) when it does not.
+static int lens_invalid(const rbrt_camera_t* cam, const rbrt_render_opts_t* o) {
+    if (!cam || !o || !(o->flags & RBRT_FLAG_THIN_LENS)) return RBRT_OK;
+    const rbrt_camera_lens_t* lens = reinterpret_cast<const rbrt_camera_lens_t*>(cam);
+    for (int c = 0; c < 3; ++c)
+        if (!std::isfinite(lens->lens_u[c]) || !std::isfinite(lens->lens_v[c]))
+            return fail(RBRT_ERR_INVALID_ARG, "thin lens: lens_u and lens_v must be finite");
+    if (!std::isfinite(lens->focus_scale) || !(lens->focus_scale > 0.0f))
+        return fail(RBRT_ERR_INVALID_ARG, "thin lens: focus_scale must be finite and > 0");
+    if (lens->reserved != 0u) return fail(RBRT_ERR_INVALID_ARG, "thin lens: reserved must be 0");
+    return RBRT_OK;
+}
+
+// The lens part of a tile-table key (the tables of a lens camera are not those of the pinhole camera it wraps).
+template <class Key>
+static void key_lens(Key& k, const TraceParams& P) {
+    k.thin_lens = P.thin_lens;
+    for (int c = 0; c < 3; ++c) k.lens_u[c] = P.lens_u[c], k.lens_v[c] = P.lens_v[c];
+    k.focus_scale = P.focus_scale;
+}
+
 int fill_trace_params(const rbrt_hip_scene* s, const rbrt_camera_t* cam, const rbrt_render_opts_t* o,
                       TraceParams& P) {
     std::memset(&P, 0, sizeof(P));
@@ -814,6 +838,12 @@ int fill_trace_params(const rbrt_hip_scene* s, const rbrt_camera_t* cam, const r
     for (int k = 0; k < 3; ++k) P.bg[k] = o->bg[k];
     P.max_depth = o->max_depth;
     P.constant_bg = (o->flags & RBRT_FLAG_CONSTANT_BACKGROUND) ? 1u : 0u;
+    if (cam && (o->flags & RBRT_FLAG_THIN_LENS)) {  // (validated by lens_invalid: the words past the camera are a lens)
+        const rbrt_camera_lens_t* lens = reinterpret_cast<const rbrt_camera_lens_t*>(cam);
+        P.thin_lens = 1u;
+        for (int c = 0; c < 3; ++c) P.lens_u[c] = lens->lens_u[c], P.lens_v[c] = lens->lens_v[c];
+        P.focus_scale = lens->focus_scale;
+    }
     P.seed_key = host_splitmix64(o->seed);
     P.n_spheres = s->n_spheres;
     P.n_meshes = s->n_meshes;
@@ -897,6 +927,7 @@ int scene_create_impl(const rbrt_scene_t* scene, int device, rbrt_hip_scene_t** 
 extern "C" {
 
 int rbrt_hip_abi_version(void) { return RBRT_ABI_VERSION; }
+uint32_t rbrt_hip_supported_flags(void) { return RBRT_FLAG_COLLECT_STATS | RBRT_FLAG_CONSTANT_BACKGROUND | RBRT_FLAG_THIN_LENS; }
 
 const char* rbrt_hip_last_error(void) { return g_last_error.c_str(); }
 
@@ -1209,8 +1240,9 @@ int scene_create_impl(const rbrt_scene_t* scene, int device, rbrt_hip_scene_t** 
         s->work_stripes = stripes, s->work_stripes_overlap = stripes_overlap;
         s->poison_samples = poison != 0;
         if (s->stack_entries > s->stack_need) s->stack_entries = s->stack_need;
-        // resident waves per CU: LDS-limited (160 KiB per CU), at most 5 per SIMD (VGPR budget)
-        int per_cu = int((160u * 1024u) / megakernel_lds_bytes(s->stack_entries, s->n_spheres, s->n_meshes, s->n_elem_tris));
+        // resident waves per CU: LDS-limited (160 KiB per CU), at most 5 per SIMD (VGPR budget). (A thin-lens launch stages 32
+        // bytes more; where that costs it a wave per CU the waves of the grid beyond the resident ones start as others end.)
+        int per_cu = int((160u * 1024u) / megakernel_lds_bytes(s->stack_entries, s->n_spheres, s->n_meshes, s->n_elem_tris, 0u));
         if (per_cu > 20) per_cu = 20;
         if (per_cu < 1) per_cu = 1;
         if (waves_per_cu != 0) per_cu = int(waves_per_cu), s->waves_fixed = true;
@@ -1392,6 +1424,7 @@ static int render_samples(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, const r
         return fail(RBRT_ERR_UNSUPPORTED, "image has 2^32 or more pixels");
     const uint32_t world = o->tile_world ? o->tile_world : 1;
     if (o->tile_rank >= world) return fail(RBRT_ERR_INVALID_ARG, "tile_rank >= tile_world");
+    if (int rc = lens_invalid(cam, o)) return rc;
     HIP_TRY(hipSetDevice(s->device));
     std::lock_guard<std::mutex> watcher_lock(s->mu);  // (the watcher of elastic launches looks at the lanes between calls, not during one)
     adopt_refined(s);  // (the background thread's trees, once they are on the device: this call's launches use them)
@@ -1573,6 +1606,7 @@ static int render_samples(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, const r
             HIP_TRY(hipEventRecord(S.ev_lists, stream));
             std::memset(&S.key, 0, sizeof(S.key));
             S.key.cam = *cam, S.key.rank = o->tile_rank, S.key.world = world, S.key.list_mode = T.tile_list_mode, S.key.min_dist = o->min_dist;
+            key_lens(S.key, T);
             S.key_valid = true;
             // (the lane this call's first launch takes: if that launch finds the GPU idle it wants the isolated launch's list
             // as well -- made here too, it does not have to wait for the prep stream while the launches behind it pile up)
@@ -1605,6 +1639,7 @@ static int render_samples(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, const r
             rbrt_hip_scene::Lane::TileKey want;
             std::memset(&want, 0, sizeof(want));
             want.cam = *cam, want.rank = o->tile_rank, want.world = world, want.list_mode = list_mode_for(false), want.min_dist = o->min_dist;
+            key_lens(want, P);
             for (uint32_t li = 0; li < depth; ++li)
                 for (const auto& C : s->lanes[li].tiles)
                     if (C.key_valid && std::memcmp(&want, &C.key, sizeof(want)) == 0) lane_no = li;
@@ -1674,6 +1709,7 @@ static int render_samples(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, const r
             std::memset(&key, 0, sizeof(key));
             const uint32_t list_mode = list_mode_for(overlapped && !stats);
             key.cam = *cam, key.rank = o->tile_rank, key.world = world, key.list_mode = list_mode, key.min_dist = o->min_dist;
+            key_lens(key, P);
             for (auto& C : L.tiles)
                 if (C.key_valid && std::memcmp(&key, &C.key, sizeof(key)) == 0) S = &C;
             if (!S) {
@@ -1885,7 +1921,7 @@ int rbrt_hip_scene_info(rbrt_hip_scene_t* s, rbrt_hip_scene_info_t* out) {
     out->bvh_stack_need = s->stack_need;
     out->n_nodes = s->total_nodes, out->n_triangles = s->total_tris;
     out->trace_waves = s->n_waves;
-    out->lds_bytes_per_wave = uint32_t(megakernel_lds_bytes(s->stack_entries, s->n_spheres, s->n_meshes, s->n_elem_tris));
+    out->lds_bytes_per_wave = uint32_t(megakernel_lds_bytes(s->stack_entries, s->n_spheres, s->n_meshes, s->n_elem_tris, 0u));
     (void)hipSetDevice(s->device);
     out->occupancy_api_waves_per_cu = uint32_t(megakernel_occupancy_per_cu(out->lds_bytes_per_wave));
     out->n_cus = s->n_cus;
@@ -1919,6 +1955,7 @@ int rbrt_hip_unpack_tiles(int device, void* stream, const float* d_gathered, uin
 int rbrt_hip_render(const rbrt_camera_t* cam, const rbrt_scene_t* scene, const rbrt_render_opts_t* opts,
                     float* out_radiance, uint8_t* out_rgb8) {
     if (!cam || !scene || !opts) return fail(RBRT_ERR_INVALID_ARG, "render: null argument");
+    if (int rc = lens_invalid(cam, opts)) return rc;
     const double t_call0 = now_s();
     rbrt_hip_call_times_t& times = g_last_render_times;
     std::memset(&times, 0, sizeof(times));
@@ -2252,7 +2289,14 @@ int rbrt_hip_debug_scatter(const rbrt_material_t* mats, const float* in_dir, con
     return RBRT_OK;
 }
 
+static int debug_primary_cull(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, uint32_t flags, uint32_t* out_words, size_t n_words);
 int rbrt_hip_debug_primary_cull(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, uint32_t* out_words, size_t n_words) {
+    return debug_primary_cull(s, cam, RBRT_FLAG_NONE, out_words, n_words);
+}
+int rbrt_hip_debug_primary_cull_lens(rbrt_hip_scene_t* s, const rbrt_camera_lens_t* lens, uint32_t* out_words, size_t n_words) {
+    return debug_primary_cull(s, lens ? &lens->cam : nullptr, RBRT_FLAG_THIN_LENS, out_words, n_words);
+}
+static int debug_primary_cull(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, uint32_t flags, uint32_t* out_words, size_t n_words) {
     if (!s || !cam || !out_words) return fail(RBRT_ERR_INVALID_ARG, "debug_primary_cull: null argument");
     const uint32_t tiles_x = (cam->img_width_pix + RBRT_TILE - 1) / RBRT_TILE, tiles_y = (cam->img_height_pix + RBRT_TILE - 1) / RBRT_TILE;
     if (uint64_t(tiles_x) * tiles_y != n_words || n_words == 0 || n_words > 0xFFFFFFFFull)
@@ -2260,6 +2304,8 @@ int rbrt_hip_debug_primary_cull(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, u
     HIP_TRY(hipSetDevice(s->device));
     rbrt_render_opts_t o;
     rbrt_render_opts_default(&o);
+    o.flags = flags;
+    if (int rc = lens_invalid(cam, &o)) return rc;
     TraceParams P;
     fill_trace_params(s, cam, &o, P);
     P.tiles_x = tiles_x, P.tiles_y = tiles_y, P.n_tiles = uint32_t(n_words);

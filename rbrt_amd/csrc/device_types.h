@@ -181,6 +181,9 @@ struct TraceParams {
     uint32_t helper_seq;
     uint32_t wave_base;  // helper launches: first per-wave scratch slot (gseq / gstack) of this launch's waves; 0 for the launch itself
     uint32_t helper_min_items;  // helper launches: a helper wave joins only while at least this many work items per wave (the launch's and all its helpers') are left
+    // RBRT_FLAG_THIN_LENS: thin_lens = 1 and the rbrt_camera_lens_t words past the camera; 0 (pinhole): the lens is never read
+    uint32_t thin_lens;
+    float lens_u[3], lens_v[3], focus_scale;
 };
 
 struct ResolveParams {

@@ -640,18 +640,44 @@ __device__ __forceinline__ bool scatter(const DevMaterial& m, V3 in_d, V3 p, V3 
     }
 }
 
-// cam.rs:64-82: direction of the camera ray of sample (pixel, stream state); the column jitter is drawn first.
-__device__ __forceinline__ V3 camera_ray_direction(V3 pos, V3 center, V3 right, V3 up, float mm_hor, float mm_vert, uint32_t img_w,
-                                                   uint32_t img_h, uint32_t row, uint32_t col, Rng& rng) {
+// cam.rs:64-82: the point of the image plane the camera ray of sample (pixel, stream state) passes through; the column
+// jitter is drawn first.
+__device__ __forceinline__ V3 camera_target(V3 center, V3 right, V3 up, float mm_hor, float mm_vert, uint32_t img_w, uint32_t img_h,
+                                            uint32_t row, uint32_t col, Rng& rng) {
     const float col_off = float(col) - float(img_w / 2);
     const float row_off = float(row) - float(img_h / 2);
     const float u0 = rng.next_f32();
     const float col_mm = ((col_off + u0) - 0.5f) * mm_hor;
     const float u1 = rng.next_f32();
     const float row_mm = ((row_off + u1) - 0.5f) * mm_vert;
-    const V3 target = (center + (0.001f * col_mm) * right) - (0.001f * row_mm) * up;
-    return normalize(target - pos);
+    return (center + (0.001f * col_mm) * right) - (0.001f * row_mm) * up;
 }
+// ... and the direction of the (pinhole) camera ray through it.
+__device__ __forceinline__ V3 camera_ray_direction(V3 pos, V3 center, V3 right, V3 up, float mm_hor, float mm_vert, uint32_t img_w,
+                                                   uint32_t img_h, uint32_t row, uint32_t col, Rng& rng) {
+    return normalize(camera_target(center, right, up, mm_hor, mm_vert, img_w, img_h, row, col, rng) - pos);
+}
+// RBRT_FLAG_THIN_LENS (rbrt_hip.h rbrt_camera_lens_t): after the jitter draws that placed `target`, a
+// point of the unit disc by rejection from [-1, 1)^2 (no sin / cos: a restatement reproduces it bit for bit), the origin
+// on the lens and the direction to the focus surface's image of the target. `lens`: lens_u, lens_v, focus_scale.
+// In: o = position, f = the target; out: o = the origin on the lens, f = the focus point F (the ray's direction is then
+// normalize(f - o), as the pinhole's is normalize(target - position)).
+__device__ __forceinline__ void lens_point(V3& o, V3& f, const float* lens, Rng& rng) {
+    // (a wave-uniform loop: a lane whose point is accepted keeps it and its stream, by selects, while the others draw on)
+    float lx = 0.0f, ly = 0.0f;
+    bool pending = true;
+    do {
+        Rng t = rng;
+        const float x = 2.0f * t.next_f32() - 1.0f;
+        const float y = 2.0f * t.next_f32() - 1.0f;
+        if (pending) rng = t, lx = x, ly = y;
+        pending = pending && !(x * x + y * y < 1.0f);
+    } while (__builtin_amdgcn_ballot_w64(pending) != 0ull);
+    const V3 pos = o;
+    o = pos + (lx * mk(lens) + ly * mk(lens + 3));
+    f = pos + lens[6] * (f - pos);
+}
+constexpr uint32_t kLensDw = 8;  // lens words staged in the megakernel's LDS for a lens launch: lens_u, lens_v, focus_scale, pad
 
 // lib.rs:68-71: what a ray that hits nothing sees; the direction as it is (not re-normalised).
 // `constant` (RBRT_FLAG_CONSTANT_BACKGROUND): bg itself.
@@ -661,7 +687,8 @@ __device__ __forceinline__ V3 background(float dy, const float* bg, uint32_t con
     return t * mk(1.0f, 1.0f, 1.0f) + (1.0f - t) * mk(bg);
 }
 
-__host__ __device__ inline uint32_t megakernel_lds_dwords(uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris);
+__host__ __device__ inline uint32_t megakernel_lds_dwords(uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris,
+                                                          uint32_t thin_lens);
 #include "megakernel.inl"
 
 // lib.rs:116-122: (sqrt(c) * 256) as u8 — Rust's float->int cast saturates and maps NaN to 0.
@@ -797,7 +824,12 @@ __global__ __launch_bounds__(kSmallBlock) void sky_resolve_kernel(const TracePar
         for (uint32_t s = 0; s < R.batch; ++s) {
             Rng rng;
             rng.init(P.seed_key, row * R.width + col, P.sample_base + s);
-            const V3 d = camera_ray_direction(pos, center, right, up, P.cam.mm_per_pix_hor, P.cam.mm_per_pix_vert, R.width, R.height, row, col, rng);
+            V3 o = pos, f = camera_target(center, right, up, P.cam.mm_per_pix_hor, P.cam.mm_per_pix_vert, R.width, R.height, row, col, rng);
+            if (P.thin_lens) {
+                const float lens[7] = {P.lens_u[0], P.lens_u[1], P.lens_u[2], P.lens_v[0], P.lens_v[1], P.lens_v[2], P.focus_scale};
+                lens_point(o, f, lens, rng);
+            }
+            const V3 d = normalize(f - o);
             const V3 c = background(d.y, P.bg, P.constant_bg);
             ax = ax + c.x;
             ay = ay + c.y;
@@ -857,6 +889,24 @@ __global__ __launch_bounds__(kSmallBlock) void sky_resolve_kernel(const TracePar
 // every comparison false: nothing is culled. Non-finite or non-positive radii and non-finite boxes (a mesh without
 // triangles has lo = +inf) are never culled: the reference's NaN panic (sphere.rs:33), reported through
 // nan_discriminants, must still be reached. BasicTriangle elements are never culled (the YAML cannot describe them).
+//
+// Lens rays (RBRT_FLAG_THIN_LENS). A lens ray starts at o = position + lx lens_u + ly lens_v with lx^2 + ly^2 < 1 and
+// heads for F = position + focus_scale (T - position), T the pinhole target of its sample. By Cauchy-Schwarz |o - position|
+// <= sqrt(|lens_u|^2 + |lens_v|^2); with the float error of o (two roundings of the offset, one of the sum: 16 u of
+// |position| + |lens_u| + |lens_v| covers them) that is `lens_a` = a. F - position is parallel to T - position and at least
+// focus_scale * plane_dist long, so F - o, which differs from it by at most a, makes an angle of at most
+// beta = asin(a / (focus_scale * plane_dist)) with the pinhole direction of T (the code takes tan beta, which is larger):
+// every lens direction lies within beta of a pinhole direction of its tile. So a point of a lens line at parameter t, forward or backward, is within a + |t| sin beta
+// of a line through the position whose direction is in the tile's cone. The rules grow by that much: sphere radii by a
+// (R_out + a, R_in - a: a ray from o misses / cuts the ball as a ray from the position misses / cuts the ball moved by
+// position - o), the cone rho and the deep-cut caps by beta, the slabs' reach and box_unreachable's by a + beta (l + r + a)
+// resp. a + beta (far + a) (the parameter of a point of the object is at most its distance from the origin), and the
+// float-error slacks that depend on the origin's distance from the object (the sphere test's, the box test's, the tree pad)
+// take the distance plus a. F itself is float: on top of the error of T - position, focus_scale multiplies it and the
+// product, the sum and F - o add roundings of at most |position| + 2 focus_scale |T - position|_max + a; that error over
+// |F - o| >= focus_scale plane_dist - a replaces the pinhole's `angle`. With a >= focus_scale plane_dist (the lens may
+// reach the focus surface), or a NaN anywhere, the angle is NaN and nothing is culled. For a pinhole a = beta = 0 and
+// every rule is the one above, bit for bit.
 // ---------------------------------------------------------------------------------------------
 struct D3 {
     double x, y, z;
@@ -940,16 +990,36 @@ __global__ __launch_bounds__(kCullBlock, 4) void primary_cull_kernel(const Trace
     const double mmh = double(c.mm_per_pix_hor), mmv = double(c.mm_per_pix_vert);
     const double cm0 = (double(c0) - double(W / 2u) - 0.5 - pad) * mmh, cm1 = (double(c1) - double(W / 2u) + 0.5 + pad) * mmh;
     const double rm0 = (double(r0) - double(H / 2u) - 0.5 - pad) * mmv, rm1 = (double(r1) - double(H / 2u) + 0.5 + pad) * mmv;
+    // the float ray against the exact line: absolute error of (target - position), as an angle
+    const double cm_abs = fabs(cm0) > fabs(cm1) ? fabs(cm0) : fabs(cm1), rm_abs = fabs(rm0) > fabs(rm1) ? fabs(rm0) : fabs(rm1);
+    const double err = 8.0 * (1.0 / 8388608.0) * (dlen(ctr) + dlen(pos) + 0.001 * cm_abs * dlen(right) + 0.001 * rm_abs * dlen(up));
+    const double plane_dist = fabs(ddot(a, unit_or_nan(dcross(right, up))));  // no target is closer to the position
+    double angle = 2.0 * err / plane_dist + 1e-6;                                // (NaN or inf for a degenerate camera)
+    // Lens rays (header, "Lens rays"): lens_a bounds |o - position|, lens_beta the angle between a lens ray's exact direction
+    // and the pinhole direction of its target, `angle` becomes the float error of the lens ray's direction. 0 for a pinhole.
+    double lens_a = 0.0, lens_beta = 0.0;
+    if (P.thin_lens) {
+        const D3 lu = d3(P.lens_u), lv = d3(P.lens_v);
+        const double fs = double(P.focus_scale), nu = dlen(lu), nv = dlen(lv);
+        const double u16 = 16.0 * (1.0 / 16777216.0);
+        double tmax = 0.0;  // the farthest target: a corner (|T - position| is convex)
+        for (uint32_t k = 0; k < 4u; ++k) {
+            const double t = dlen(a + (0.001 * (k & 1u ? cm1 : cm0)) * right - (0.001 * (k & 2u ? rm1 : rm0)) * up);
+            tmax = t > tmax || !(t == t) ? t : tmax;
+        }
+        lens_a = sqrt(nu * nu + nv * nv) + u16 * (dlen(pos) + nu + nv);
+        const double f_min = fs * plane_dist;  // |F - position| >= focus_scale * plane_dist
+        const double err_f = fs * err + u16 * (dlen(pos) + 2.0 * fs * tmax + lens_a);
+        angle = 2.0 * err_f / (f_min - lens_a) + 1e-6;
+        const double sb = lens_a / f_min;      // sin beta
+        lens_beta = sb / sqrt(1.0 - sb * sb);  // tan beta >= beta (no asin: its code cost the pass VGPR spills)
+        if (!(sb < 1.0) || !(lens_beta == lens_beta)) angle = __builtin_nan("");  // (nothing is culled)
+    }
     CullSlab cols, rows;
     cols.n_lo = unit_or_nan(dcross(a + (0.001 * cm0) * right, up));
     cols.n_hi = unit_or_nan(dcross(a + (0.001 * cm1) * right, up));
     rows.n_lo = unit_or_nan(dcross(a - (0.001 * rm0) * up, right));
     rows.n_hi = unit_or_nan(dcross(a - (0.001 * rm1) * up, right));
-    // the float ray against the exact line: absolute error of (target - position), as an angle
-    const double cm_abs = fabs(cm0) > fabs(cm1) ? fabs(cm0) : fabs(cm1), rm_abs = fabs(rm0) > fabs(rm1) ? fabs(rm0) : fabs(rm1);
-    const double err = 8.0 * (1.0 / 8388608.0) * (dlen(ctr) + dlen(pos) + 0.001 * cm_abs * dlen(right) + 0.001 * rm_abs * dlen(up));
-    const double plane_dist = fabs(ddot(a, unit_or_nan(dcross(right, up))));  // no target is closer to the position
-    const double angle = 2.0 * err / plane_dist + 1e-6;                          // (NaN or inf for a degenerate camera)
     CullCone cone;
     cone.mid = unit_or_nan(a + (0.0005 * (cm0 + cm1)) * right - (0.0005 * (rm0 + rm1)) * up);
     double rho = 0.0;
@@ -959,10 +1029,11 @@ __global__ __launch_bounds__(kCullBlock, 4) void primary_cull_kernel(const Trace
         const double t = angle_between(cone.mid, u);
         rho = t > rho || !(t == t) ? t : rho;  // (a NaN sticks)
     }
-    rho += angle;
+    const double w_dir = angle + lens_beta;  // a ray's direction: within this of the exact pinhole lines of the tile
+    rho += w_dir;
     if (!(rho < 1.5)) rho = __builtin_nan("");  // (a tile a quarter turn wide: no rule applies)
     cone.cos_rho = cos(rho), cone.sin_rho = sin(rho);
-    cone.cos_w = cos(angle), cone.sin_w = sin(angle);
+    cone.cos_w = cos(w_dir), cone.sin_w = sin(w_dir);
 
     const uint32_t n_elem = P.n_spheres + P.n_elem_tris;
     uint32_t word = 0;
@@ -976,11 +1047,13 @@ __global__ __launch_bounds__(kCullBlock, 4) void primary_cull_kernel(const Trace
             const double r = double(sp.radius), l = dlen(q);
             if (r > 0.0 && r < 1e30 && l < 1e30) {  // (false for NaN)
                 // (the second term is the analysed one, 15x the bound in the header; the others are loose change on top)
-                const double slack = 1e-5 * r + 1e-5 * (l * l + r * r) / r + 1e-6 * l;
-                const double reach = r + slack + angle * (l + r);
+                const double lo = l + lens_a;  // (the distance of a ray's origin from the centre)
+                const double slack = 1e-5 * r + 1e-5 * (lo * lo + r * r) / r + 1e-6 * lo;
+                const double reach = r + slack + lens_a + w_dir * (l + r + lens_a);
+                const double r_out = r + slack + lens_a, r_in = r - slack - lens_a;
                 const D3 qhat = (1.0 / l) * q;
                 out = cols.outside(q, reach) || rows.outside(q, reach) ||
-                      (cone.misses(qhat, l, r + slack, 1.0) && (cone.misses(qhat, l, r + slack, -1.0) || cone.backward_deep(qhat, l, r - slack)));
+                      (cone.misses(qhat, l, r_out, 1.0) && (cone.misses(qhat, l, r_out, -1.0) || cone.backward_deep(qhat, l, r_in)));
             }
         }
         if (out) word |= 1u << e;
@@ -990,8 +1063,8 @@ __global__ __launch_bounds__(kCullBlock, 4) void primary_cull_kernel(const Trace
     const auto box_unreachable = [&](D3 lo, D3 hi, double slack, double far) -> bool {
         const D3 q = 0.5 * (lo + hi) - pos;
         const double l = dlen(q);
-        if (cone.misses((1.0 / l) * q, l, 0.5 * dlen(hi - lo) * 1.001 + slack, 1.0)) return true;
-        const double reach = slack + angle * far;
+        if (cone.misses((1.0 / l) * q, l, 0.5 * dlen(hi - lo) * 1.001 + slack + lens_a, 1.0)) return true;
+        const double reach = slack + lens_a + w_dir * (far + lens_a);
         for (uint32_t slab = 0; slab < 2u; ++slab) {
             const CullSlab& sl = slab ? rows : cols;
             bool pos_side = true, neg_side = true;
@@ -1025,7 +1098,7 @@ __global__ __launch_bounds__(kCullBlock, 4) void primary_cull_kernel(const Trace
         // skip a NaN, and an axis whose line runs outside its slab gives t_min = +inf or t_max = -inf: a miss, as in
         // geometry.) The slack is 16 u far, three times that bound; the angle between the float ray and the exact
         // line of its pixel is added on top by box_unreachable (angle * far). Round 3 had a chosen 1e-4 far here.
-        const double slack = 16.0 * (1.0 / 16777216.0) * far;
+        const double slack = 16.0 * (1.0 / 16777216.0) * (far + lens_a);
         const bool out = finite && box_unreachable(d3(md.bbox_lo), d3(md.bbox_hi), slack, far);
         if (out) word |= 1u << (24u + m);
         // A ray may pass the mesh's box and still have no triangle to hit: the tile is free of the mesh as well when
@@ -1039,7 +1112,7 @@ __global__ __launch_bounds__(kCullBlock, 4) void primary_cull_kernel(const Trace
         // of whose rays enters a grown box of some level takes no triangle below it.
         const D3 mc = d3(md.center) - pos;
         const double o_inf = fmax(fmax(fabs(pos.x), fabs(pos.y)), fabs(pos.z));
-        const double pad_base = 64.0 * (1.0 / 16777216.0) * (dlen(mc) + double(md.radius) + o_inf);
+        const double pad_base = 64.0 * (1.0 / 16777216.0) * (dlen(mc) + double(md.radius) + o_inf + lens_a);
         bool mesh_free = out;
         if (!out && all && finite && md.n_nodes != 0u) {  // (only where the answer matters: nothing else is in reach so far)
             constexpr uint32_t kCullLevels = 6;
@@ -1375,17 +1448,19 @@ __global__ __launch_bounds__(kBlock) void scatter_debug_kernel(const DevMaterial
 size_t megakernel_gseq_bytes(uint32_t n_waves) { return size_t(n_waves) * kPool * kSeqWords * sizeof(uint32_t); }
 size_t megakernel_gstack_bytes(uint32_t n_waves) { return size_t(n_waves) * kStackMax * 64u * sizeof(uint32_t); }
 
-__host__ __device__ inline uint32_t megakernel_lds_dwords(uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris) {
+__host__ __device__ inline uint32_t megakernel_lds_dwords(uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris,
+                                                          uint32_t thin_lens) {
     const uint32_t n_elem = n_spheres + n_elem_tris;
     const uint32_t scene = n_spheres * kSphDw + (n_elem + n_meshes) * kMatDw + n_meshes * kMeshDw + kGenDw +
+                           (thin_lens ? kLensDw : 0u) +                                // a lens launch's lens (nothing for a pinhole)
                            (n_elem_tris != 0u ? n_elem_tris * kTriDw + n_elem : 0u);  // triangle table + element order
     const uint32_t pool_pad = (uint32_t(kPool) + 63u) & ~63u;  // status + list: one byte per (padded) slot each
     uint32_t dw = uint32_t(kFields * kPool) + kCellDw + kTqDw + kHelpDw + pool_pad / 2u + stack_entries * 64u + scene;
     if (RBRT_REGION_TIMERS) dw += uint32_t(kNumRegions);  // analysis build: a u32 cycle accumulator per region
     return dw;
 }
-size_t megakernel_lds_bytes(uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris) {
-    return size_t(megakernel_lds_dwords(stack_entries, n_spheres, n_meshes, n_elem_tris)) * sizeof(uint32_t);
+size_t megakernel_lds_bytes(uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris, uint32_t thin_lens) {
+    return size_t(megakernel_lds_dwords(stack_entries, n_spheres, n_meshes, n_elem_tris, thin_lens)) * sizeof(uint32_t);
 }
 
 // What the HIP runtime says fits: resident single-wave workgroups of the trace kernel per CU at this much LDS (0 on error).
@@ -1401,14 +1476,14 @@ int megakernel_occupancy_per_cu(size_t lds_bytes) {
 // (work counters, sample buffer, tables), scratch slots from P.wave_base on.
 hipError_t launch_trace_helper(const TraceParams& P, uint32_t n_waves, hipStream_t stream) {
     if (P.n_items == 0 || n_waves == 0 || !P.helper_words) return hipSuccess;
-    const size_t lds = megakernel_lds_bytes(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris);
+    const size_t lds = megakernel_lds_bytes(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris, P.thin_lens);
     hipLaunchKernelGGL((trace_megakernel<false, true>), dim3(n_waves), dim3(64), lds, stream, P);
     return hipGetLastError();
 }
 
 hipError_t launch_trace_megakernel(const TraceParams& P, uint32_t n_waves, bool stats, hipStream_t stream) {
     if (P.n_items == 0 || n_waves == 0) return hipSuccess;
-    const size_t lds = megakernel_lds_bytes(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris);
+    const size_t lds = megakernel_lds_bytes(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris, P.thin_lens);
     if (stats)
         hipLaunchKernelGGL((trace_megakernel<true>), dim3(n_waves), dim3(64), lds, stream, P);
     else

@@ -239,7 +239,7 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
     // (the accumulators sit at the very end of the workgroup's LDS: megakernel_lds_bytes adds room for them)
     // (u32: a wave spends at most a few million cycles in a region per launch; 76 bytes fit the slack of the product's
     // allocation granule, so this build keeps the product's 16 workgroups per CU)
-    uint32_t* const rt_acc = lds + (megakernel_lds_dwords(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris) - uint32_t(kNumRegions));
+    uint32_t* const rt_acc = lds + (megakernel_lds_dwords(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris, P.thin_lens) - uint32_t(kNumRegions));
     if (lane < uint32_t(kNumRegions)) rt_acc[lane] = 0u;
     unsigned long long rt_prev = __builtin_amdgcn_s_memtime();
     const unsigned long long rt_wall0 = __builtin_amdgcn_s_memrealtime();  // 100 MHz, the same clock on every CU
@@ -321,17 +321,27 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
             dst[G_BATCH] = P.batch, dst[G_BATCH_MAGIC] = P.batch_magic;
             dst[G_TILES_X] = P.tiles_x, dst[G_TILES_X_MAGIC] = P.tiles_x_magic;
             dst[G_TILE_WORLD] = P.tile_world, dst[G_TILE_RANK] = P.tile_rank;
-            dst[G_N_LOCAL] = n_work, dst[G_FLAGS] = (P.tiles_reversed ? 1u : 0u) | (P.constant_bg ? 2u : 0u);  // (one word: a new one
-            // would take the header card's scene past 16 waves per CU, and reading the kernel argument cost 3 SGPR spills)
+            dst[G_N_LOCAL] = n_work, dst[G_FLAGS] = (P.tiles_reversed ? 1u : 0u) | (P.constant_bg ? 2u : 0u) | (P.thin_lens ? 4u : 0u);
+            // (one word: a new one would take the header card's scene past 16 waves per CU, and reading the kernel argument cost
+            // 3 SGPR spills. A lens launch's lens words sit behind everything else, at the dword offset from here that bits
+            // 8 and up of the flags word carry: a pinhole launch's LDS -- and with it every current scene's occupancy -- and its
+            // layout are what they were.)
+            if (P.thin_lens) {
+                const uint32_t at = kGenDw + (P.n_elem_tris != 0u ? P.n_elem_tris * kTriDw + n_elem : 0u);  // behind everything else
+                for (int c = 0; c < 3; ++c) gf[at + c] = P.lens_u[c], gf[at + 3 + c] = P.lens_v[c];
+                gf[at + 6] = P.focus_scale, dst[at + 7] = 0u;
+                dst[G_FLAGS] |= at << 8;
+            }
             dst[G_SAMPLE_BASE] = P.sample_base, dst[G_MAX_DEPTH] = P.max_depth;
             dst[G_SEED_LO] = uint32_t(P.seed_key), dst[G_SEED_HI] = uint32_t(P.seed_key >> 32);
         }
     }
     const uint32_t* const gp = sc_base + P.n_spheres * kSphDw + n_obj * kMatDw + P.n_meshes * kMeshDw;
     const float* const gpf = reinterpret_cast<const float*>(gp);
+    const uint32_t* const gtri = gp + kGenDw;
     const SceneLds sc = {reinterpret_cast<const float*>(sc_base), sc_base + P.n_spheres * kSphDw,
-                         sc_base + P.n_spheres * kSphDw + n_obj * kMatDw, reinterpret_cast<const float*>(gp + kGenDw),
-                         gp + kGenDw + P.n_elem_tris * kTriDw};
+                         sc_base + P.n_spheres * kSphDw + n_obj * kMatDw, reinterpret_cast<const float*>(gtri),
+                         gtri + P.n_elem_tris * kTriDw};
     // work items are reserved from the global counter in chunks, the next chunk asynchronously
     WorkSource work;
     work.init(n_items);
@@ -891,8 +901,12 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                         if (row < img_h && col < img_w) {
                             rng.init((uint64_t(gp[G_SEED_HI]) << 32) | gp[G_SEED_LO], row * img_w + col, gp[G_SAMPLE_BASE] + s);
                             o = mk(gpf + G_POS);
-                            d = camera_ray_direction(o, mk(gpf + G_CENTER), mk(gpf + G_RIGHT), mk(gpf + G_UP), gpf[G_MMH], gpf[G_MMV], img_w,
-                                                     img_h, row, col, rng);
+                            V3 f = camera_target(mk(gpf + G_CENTER), mk(gpf + G_RIGHT), mk(gpf + G_UP), gpf[G_MMH], gpf[G_MMV], img_w,
+                                                 img_h, row, col, rng);
+                            const uint32_t gen_flags = uint32_t(__builtin_amdgcn_readfirstlane(int(gp[G_FLAGS])));
+                            if (gen_flags & 4u)  // RBRT_FLAG_THIN_LENS (the same for every lane): the lens words at dword gen_flags >> 8
+                                lens_point(o, f, gpf + (gen_flags >> 8), rng);
+                            d = normalize(f - o);
                             depth = gp[G_MAX_DEPTH];
                             nrec = 0;
                             word = 0;

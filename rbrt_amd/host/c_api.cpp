@@ -13,6 +13,7 @@ struct rbrt_host_scene {
     rbrt::Scene scene;
     rbrt::Scene::AbiView view;
     rbrt_camera_t cam_abi;
+    rbrt_camera_lens_t lens_abi;
 };
 
 extern "C" {
@@ -24,12 +25,11 @@ int rbrt_host_scene_load(const char* yaml_path, uint32_t height, uint32_t width,
     try {
         rbrt::SceneBlueprint bp = rbrt::load_blueprints_from_yaml_file(yaml_path);
         auto* h = new rbrt_host_scene();
-        h->cam = rbrt::Camera::create(bp.camera_blueprint.camera_position, bp.camera_blueprint.camera_look_at,
-                                      bp.camera_blueprint.camera_up, height, width,
-                                      bp.camera_blueprint.camera_focal_length_mm);
+        h->cam = rbrt::camera_from_blueprint(bp.camera_blueprint, height, width);
         h->scene = rbrt::create_scene_from_scene_blueprint(bp);
         h->view = h->scene.to_abi();
         h->cam_abi = h->cam.to_abi();
+        h->lens_abi = h->cam.to_abi_lens();
         *out = h;
         return 0;
     } catch (const std::exception& e) {
@@ -38,6 +38,8 @@ int rbrt_host_scene_load(const char* yaml_path, uint32_t height, uint32_t width,
     }
 }
 const rbrt_camera_t* rbrt_host_scene_camera(const rbrt_host_scene* h) { return &h->cam_abi; }
+// The camera with its thin lens (camera_aperture_mm > 0), or NULL for a pinhole camera.
+const rbrt_camera_lens_t* rbrt_host_scene_lens(const rbrt_host_scene* h) { return h->cam.thin_lens ? &h->lens_abi : nullptr; }
 const rbrt_scene_t* rbrt_host_scene_scene(const rbrt_host_scene* h) { return &h->view.scene; }
 void rbrt_host_scene_free(rbrt_host_scene* h) { delete h; }
 

@@ -3,13 +3,15 @@
 //   -c/--config scenes/example_scene.yaml   -s/--samples 5   -h/--help   -V/--version
 // plus, not in the reference: --seed N (default 1), --gpus N (default 1), --gather host|rccl, --oversubscribe,
 // --pass-samples N, --checkpoint FILE, --checkpoint-every N, --report FILE (machine-readable timing of the run),
-// --background R,G,B (a constant background instead of the reference's sky gradient).
+// --background R,G,B (a constant background instead of the reference's sky gradient), --aperture MM and
+// --focus-distance D (a thin lens: they override the YAML's camera_aperture_mm / camera_focus_distance).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <optional>
 #include <string>
 
 #include "rbrt.hpp"
@@ -38,6 +40,10 @@ void usage() {
         "      --checkpoint-every <n>       checkpoint after every n-th pass [default: 1]\n"
         "      --background <r,g,b>         constant linear background radiance of rays that hit nothing, e.g. 0,0,0 for a scene\n"
         "                                   lit by emissive objects only [default: the sky gradient]\n"
+        "      --aperture <mm>              lens diameter in mm, overrides the YAML's camera_aperture_mm; 0 = pinhole\n"
+        "                                   [default: the YAML's, else 0]\n"
+        "      --focus-distance <d>         distance from the camera position to the plane in focus, along the view\n"
+        "                                   direction, in scene units; overrides the YAML's camera_focus_distance\n"
         "  -h, --help                       Print help\n"
         "  -V, --version                    Print version\n");
 }
@@ -69,6 +75,14 @@ bool parse_u32(const char* s, uint32_t& out) {
 }
 
 // "R,G,B": three finite, non-negative floats
+bool parse_f32(const char* s, float& out) {
+    char* end = nullptr;
+    const float v = std::strtof(s, &end);
+    if (end == s || *end != '\0') return false;
+    out = v;
+    return true;
+}
+
 bool parse_rgb(const char* s, float out[3]) {
     const char* p = s;
     for (int c = 0; c < 3; ++c) {
@@ -95,6 +109,7 @@ int main(int argc, char** argv) {
     unsigned long long seed = 1;
     bool oversubscribe = false, constant_background = false;
     float background[3] = {0.0f, 0.0f, 0.0f};
+    std::optional<float> aperture, focus_distance;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         std::string val;
@@ -161,6 +176,14 @@ int main(int argc, char** argv) {
                 return 2;
             }
             constant_background = true;
+        } else if (a == "--aperture" || a == "--focus-distance") {
+            const char* v = value();
+            float f = 0.0f;
+            if (!parse_f32(v, f)) {
+                std::fprintf(stderr, "error: invalid value '%s' for '%s' (expected a number)\n", v, a.c_str());
+                return 2;
+            }
+            (a == "--aperture" ? aperture : focus_distance) = f;
         } else if (a == "--seed") {
             seed = std::strtoull(value(), nullptr, 10);
         } else {
@@ -174,9 +197,9 @@ int main(int argc, char** argv) {
     try {
         const auto t0 = clock::now();
         rbrt::SceneBlueprint bp = rbrt::load_blueprints_from_yaml_file(config);
-        rbrt::Camera cam = rbrt::Camera::create(bp.camera_blueprint.camera_position, bp.camera_blueprint.camera_look_at,
-                                                bp.camera_blueprint.camera_up, height, width,
-                                                bp.camera_blueprint.camera_focal_length_mm);
+        if (aperture) bp.camera_blueprint.camera_aperture_mm = aperture;
+        if (focus_distance) bp.camera_blueprint.camera_focus_distance = focus_distance;
+        rbrt::Camera cam = rbrt::camera_from_blueprint(bp.camera_blueprint, height, width);  // (checks the lens again)
         const auto t1 = clock::now();
         rbrt::Scene scene = rbrt::create_scene_from_scene_blueprint(bp);  // .obj parse, transform, SoA conversion (mesh.rs:41-181)
         const auto t2 = clock::now();

@@ -64,10 +64,19 @@ struct Camera {
     float img_width_mm, img_height_mm, focal_len_mm;
     Vec3 position, look_at, up, right, img_center_point;
     float mm_per_pix_hor, mm_per_pix_vert;
+    // A thin lens (RBRT_FLAG_THIN_LENS; the reference's camera is a pinhole): set_lens fills these, thin_lens stays false
+    // for an aperture of 0.
+    bool thin_lens = false;
+    Vec3 lens_u, lens_v;
+    float focus_scale = 0.0f;
     // Camera::new(position, look_at, up, img_height_pix, img_width_pix, focal_len_mm)
     static Camera create(Vec3 position, Vec3 look_at, Vec3 up, uint32_t img_height_pix, uint32_t img_width_pix,
                          float focal_len_mm);
+    // aperture_mm: the lens diameter (0: pinhole); focus_distance: scene units from the position to the focus plane along
+    // look_at. Throws Error for a negative or non-finite value, or a positive aperture without a focus distance (<= 0).
+    void set_lens(float aperture_mm, float focus_distance);
     rbrt_camera_t to_abi() const;
+    rbrt_camera_lens_t to_abi_lens() const;  // cam = to_abi(); the lens words are zero for a pinhole
 };
 
 // ---- materials (blueprints.rs:50-74) -------------------------------------------------------------
@@ -101,7 +110,11 @@ struct SphereBlueprint {
 struct CameraBluePrint {
     Vec3 camera_up, camera_look_at, camera_position;
     float camera_focal_length_mm = 0;
+    std::optional<float> camera_aperture_mm;     // lens diameter in mm; absent or 0: pinhole
+    std::optional<float> camera_focus_distance;  // scene units from the position to the focus plane, along look_at
 };
+// Camera::create from a blueprint, with its lens (Camera::set_lens) when the blueprint has an aperture.
+Camera camera_from_blueprint(const CameraBluePrint& bp, uint32_t img_height_pix, uint32_t img_width_pix);
 struct SceneBlueprint {
     CameraBluePrint camera_blueprint;
     std::vector<TriangleMeshBlueprint> mesh_blueprints;

@@ -138,7 +138,9 @@ double seconds_since(std::chrono::steady_clock::time_point t0) {
 
 ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& scene, const RenderConfig& cfg) {
     if (!cfg.quiet) std::printf("Starting rendering...\n");
-    const rbrt_camera_t c = cam.to_abi();
+    // (every rank's calls get &c, the camera inside its lens: with RBRT_FLAG_THIN_LENS the library reads the lens past it)
+    const rbrt_camera_lens_t lens = cam.to_abi_lens();
+    const rbrt_camera_t& c = lens.cam;
     const Scene::AbiView view = scene.to_abi();
     rbrt_render_opts_t opts;
     rbrt_render_opts_default(&opts);
@@ -197,6 +199,17 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
     if (want.fingerprint != 0 && cfg.constant_background) {  // (only then: a default run keeps its checkpoints' fingerprint)
         want.fingerprint = fnv1a(&opts.flags, sizeof(opts.flags), want.fingerprint);
         want.fingerprint = fnv1a(opts.bg, sizeof(opts.bg), want.fingerprint);
+    }
+    if (cam.thin_lens) {  // (likewise: a pinhole run's checkpoints keep their fingerprint)
+        if (!(rbrt_hip_supported_flags() & RBRT_FLAG_THIN_LENS)) throw Error("the HIP library does not support a thin lens");
+        opts.flags |= RBRT_FLAG_THIN_LENS;
+        if (want.fingerprint != 0) {
+            const uint32_t bit = RBRT_FLAG_THIN_LENS;
+            want.fingerprint = fnv1a(&bit, sizeof(bit), want.fingerprint);
+            want.fingerprint = fnv1a(lens.lens_u, sizeof(lens.lens_u), want.fingerprint);
+            want.fingerprint = fnv1a(lens.lens_v, sizeof(lens.lens_v), want.fingerprint);
+            want.fingerprint = fnv1a(&lens.focus_scale, sizeof(lens.focus_scale), want.fingerprint);
+        }
     }
     uint32_t start_sample = 0;
     std::vector<std::vector<float>> resume_acc(world);

@@ -48,7 +48,47 @@ Camera Camera::create(Vec3 position, Vec3 look_at, Vec3 up, uint32_t img_height_
     return c;
 }
 
+// The thin lens, in float, unfused, in this order:
+//   r = aperture_mm / 2000;  lens_u = r right;  lens_v = r normalize(right x normalize(look_at));
+//   focus_scale = focus_distance / (focal_len_mm / 1000)
+// The image plane lies focal_len_mm / 1000 from the position along look_at, so scaling it about the position by
+// focus_scale puts the focus plane focus_distance from the position.
+void Camera::set_lens(float aperture_mm, float focus_distance) {
+    if (!std::isfinite(aperture_mm) || aperture_mm < 0.0f)
+        throw Error("camera_aperture_mm must be a finite number >= 0 (the lens diameter in mm; 0 = pinhole)");
+    thin_lens = false, lens_u = Vec3(), lens_v = Vec3(), focus_scale = 0.0f;
+    if (aperture_mm == 0.0f) return;
+    if (!std::isfinite(focus_distance) || !(focus_distance > 0.0f))
+        throw Error("a camera with camera_aperture_mm > 0 needs camera_focus_distance, a finite distance > 0 from the position "
+                    "to the plane in focus");
+    const float r = aperture_mm / 2000.0f;
+    lens_u = r * right;
+    lens_v = r * right.cross_product(look_at.normalize()).normalize();
+    focus_scale = focus_distance / (focal_len_mm / 1000.0f);
+    if (!std::isfinite(focus_scale) || !(focus_scale > 0.0f))
+        throw Error("camera_focus_distance / camera_focal_length_mm gives no finite focus scale > 0");
+    thin_lens = true;
+}
+
+Camera camera_from_blueprint(const CameraBluePrint& bp, uint32_t img_height_pix, uint32_t img_width_pix) {
+    Camera c = Camera::create(bp.camera_position, bp.camera_look_at, bp.camera_up, img_height_pix, img_width_pix,
+                              bp.camera_focal_length_mm);
+    if (bp.camera_aperture_mm) c.set_lens(*bp.camera_aperture_mm, bp.camera_focus_distance ? *bp.camera_focus_distance : 0.0f);
+    return c;
+}
+
 static void put3(float* dst, Vec3 v) { dst[0] = v.x, dst[1] = v.y, dst[2] = v.z; }
+
+rbrt_camera_lens_t Camera::to_abi_lens() const {
+    rbrt_camera_lens_t l{};
+    l.cam = to_abi();
+    if (thin_lens) {
+        put3(l.lens_u, lens_u);
+        put3(l.lens_v, lens_v);
+        l.focus_scale = focus_scale;
+    }
+    return l;
+}
 
 rbrt_camera_t Camera::to_abi() const {
     rbrt_camera_t a{};
@@ -187,6 +227,18 @@ SceneBlueprint load_blueprints_from_yaml_text(const std::string& text) {
     bp.camera_blueprint.camera_position = as_vec3(need(cam, "camera_position", "camera_blueprint"), "camera_position");
     bp.camera_blueprint.camera_focal_length_mm =
         as_f32(need(cam, "camera_focal_length_mm", "camera_blueprint"), "camera_focal_length_mm");
+    bp.camera_blueprint.camera_aperture_mm = opt_f32(cam, "camera_aperture_mm", "camera_aperture_mm");
+    bp.camera_blueprint.camera_focus_distance = opt_f32(cam, "camera_focus_distance", "camera_focus_distance");
+    {  // (checked here, so that a bad lens is a load error; the CLI's --aperture / --focus-distance are checked again)
+        const CameraBluePrint& cb = bp.camera_blueprint;
+        const float ap = cb.camera_aperture_mm ? *cb.camera_aperture_mm : 0.0f;
+        if (!std::isfinite(ap) || ap < 0.0f)
+            throw Error("camera_aperture_mm must be a finite number >= 0 (the lens diameter in mm; 0 = pinhole)");
+        if (cb.camera_focus_distance && !(std::isfinite(*cb.camera_focus_distance) && *cb.camera_focus_distance > 0.0f))
+            throw Error("camera_focus_distance must be a finite distance > 0");
+        if (ap > 0.0f && !cb.camera_focus_distance)
+            throw Error("camera_aperture_mm > 0 needs camera_focus_distance (the distance from the position to the plane in focus)");
+    }
     for (const Node& m : as_list(need(root, "mesh_blueprints", "scene"), "mesh_blueprints")) {
         TriangleMeshBlueprint b;
         b.obj_filepath = as_string(need(m, "obj_filepath", "mesh blueprint"), "obj_filepath");

@@ -53,7 +53,8 @@ extern "C" {
                               neither do RBRT_MAT_EMISSIVE and RBRT_FLAG_CONSTANT_BACKGROUND, added since (a library without
                               them answers a kind-3 material with RBRT_ERR_INVALID_ARG), nor RBRT_FLAG_THIN_LENS with its
                               rbrt_camera_lens_t (rbrt_camera_t stays as it is: the lens wraps it) and
-                              rbrt_hip_supported_flags */
+                              rbrt_hip_supported_flags, nor the smooth shading of meshes (rbrt_scene_shading_t and the
+                              two *_shaded entry points: rbrt_mesh_t and rbrt_scene_t stay as they are) */
 
 typedef enum rbrt_status {
     RBRT_OK = 0,
@@ -146,6 +147,35 @@ typedef struct rbrt_scene {
      * Object ids (rbrt_hip_trace_rays) follow this order: element k has id k, mesh m has id n_spheres + n_triangles + m. */
     const uint32_t* element_order;
 } rbrt_scene_t;
+
+/* Smooth shading of meshes (no counterpart in the reference, which shades every mesh hit with the stored face normal,
+ * mesh.rs:253-257). A mesh can carry three corner normals per SoA entry: n0, n1, n2, at vertices[0], v0 + e1 and v0 + e2.
+ * When the closest hit of a ray (o, d) -- the ray as it was traced for that segment -- is entry i of such a mesh,
+ * scatter uses the shading normal n_s in place of the stored face normal, in float32, unfused, in this order:
+ *     h = d x e2;  a = e1 . h;  f = 1 / a;  s = o - v0;  u = f (s . h)
+ *     q = s x e1;  v = f (d . q)                  (x and . in the reference's order: dot = (x + y) + z)
+ *     w = (1 - u) - v
+ *     m_c = ((w n0_c) + (u n1_c)) + (v n2_c)      per component c
+ *     n_s = normalize(m)                          (three divisions by the length)
+ *     if m's length is 0 or n_s is not finite: n_s = the stored face normal of entry i
+ * u and v are exactly those of the Moller-Trumbore test that made entry i the closest hit (triangle.rs:189-255). There is
+ * no clamping, and n_s is not flipped towards the ray. Lambertian, metal and dielectric then run unchanged, with n_s
+ * where they read the normal. Nothing else changes: spheres, BasicTriangles and meshes without normals, the random
+ * stream and its draw order, emitters, what is hit (the BVH and the tile pass), the counters. A scene where no mesh
+ * carries normals renders exactly as it does through rbrt_hip_scene_create / rbrt_hip_render. */
+typedef struct rbrt_mesh_normals {
+    /* corner normals of every SoA entry, n_total each (padding entries included); all nine NULL = the mesh is flat.
+     * They need not have unit length. */
+    const float *n0x, *n0y, *n0z;
+    const float *n1x, *n1y, *n1z;
+    const float *n2x, *n2y, *n2z;
+} rbrt_mesh_normals_t;
+
+typedef struct rbrt_scene_shading {
+    uint32_t n_meshes;                  /* == scene->n_meshes */
+    uint32_t reserved;                  /* 0 */
+    const rbrt_mesh_normals_t* meshes;  /* [n_meshes], the scene's mesh order; NULL = every mesh flat */
+} rbrt_scene_shading_t;
 
 /* The 8 of Camera's 14 fields (cam.rs:4-19) that get_ray_through_pixel (cam.rs:64-82) reads. */
 typedef struct rbrt_camera {
@@ -247,11 +277,20 @@ typedef struct rbrt_hip_scene rbrt_hip_scene_t; /* opaque: device-resident scene
  * H*W*3 elements; either may be NULL. */
 int rbrt_hip_render(const rbrt_camera_t* cam, const rbrt_scene_t* scene,
                     const rbrt_render_opts_t* opts, float* out_radiance, uint8_t* out_rgb8);
+/* The same with smooth meshes (rbrt_hip_scene_create_shaded's checks); shading = NULL is rbrt_hip_render. */
+int rbrt_hip_render_shaded(const rbrt_camera_t* cam, const rbrt_scene_t* scene, const rbrt_scene_shading_t* shading,
+                           const rbrt_render_opts_t* opts, float* out_radiance, uint8_t* out_rgb8);
 
 /* ---- resident scene: upload + BVH build once, render many times --------------------------- */
 
 int rbrt_hip_scene_create(const rbrt_scene_t* scene, int device, rbrt_hip_scene_t** out);
 int rbrt_hip_scene_destroy(rbrt_hip_scene_t* scene);
+/* rbrt_hip_scene_create with the corner normals of smooth meshes (rbrt_scene_shading_t above). shading = NULL behaves
+ * exactly like rbrt_hip_scene_create. RBRT_ERR_INVALID_ARG, before the device is touched: shading->n_meshes !=
+ * scene->n_meshes, reserved != 0, some but not all of a mesh's nine pointers NULL, or a non-finite component (padding
+ * entries included). rbrt_hip_render_device and rbrt_hip_render_pass need nothing more on a handle made this way. */
+int rbrt_hip_scene_create_shaded(const rbrt_scene_t* scene, const rbrt_scene_shading_t* shading, int device,
+                                 rbrt_hip_scene_t** out);
 
 /* Number of pixels this rank owns for a W x H image under (tile_rank, tile_world), counting
  * the padded pixels of partial edge tiles (each tile contributes RBRT_TILE*RBRT_TILE slots). */

@@ -134,6 +134,13 @@ int rbrt_hip_debug_primary_cull(rbrt_hip_scene_t* scene, const rbrt_camera_t* ca
  * rays"). The lens is validated like the render entry points' (RBRT_ERR_INVALID_ARG). */
 int rbrt_hip_debug_primary_cull_lens(rbrt_hip_scene_t* scene, const rbrt_camera_lens_t* lens, uint32_t* out_words, size_t n_words);
 
+/* Test hook for smooth shading (rbrt_hip.h rbrt_scene_shading_t): for each of n rays (ox, oy, oz, dx, dy, dz; host array),
+ * the normal the scatter of the megakernel would use at its closest hit (rbrt_hip_trace_rays' hit), computed by the same
+ * device function: a sphere's unnormalised p - center, a BasicTriangle's or a flat mesh's stored normal, a smooth mesh's
+ * n_s. out_normal: host float[n][3], NaN for a miss. */
+int rbrt_hip_debug_shading_normals(rbrt_hip_scene_t* scene, const float* rays, size_t n, float min_dist, float max_dist,
+                                   float* out_normal);
+
 /* Kernel timing with HIP events recorded on the launch stream around every trace-kernel launch
  * (and the resolve kernel after it). set_timing(scene, 1) starts / restarts the accumulation;
  * kernel_ms sums the durations of all launches since then (it synchronises on the last event) and

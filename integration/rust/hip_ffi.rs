@@ -44,6 +44,18 @@ pub struct RbrtCameraLens {                            // rbrt_camera_lens_t; pa
     pub focus_scale: f32,                              // focus surface = image plane scaled about cam.position by this
     pub reserved: u32,                                 // 0
 }
+#[repr(C)] #[derive(Copy, Clone)]
+pub struct RbrtMeshNormals {                           // rbrt_mesh_normals_t: corner normals of every SoA entry (n_total each)
+    pub n0x: *const f32, pub n0y: *const f32, pub n0z: *const f32,      // at vertices[0]
+    pub n1x: *const f32, pub n1y: *const f32, pub n1z: *const f32,      // at v0 + e1
+    pub n2x: *const f32, pub n2y: *const f32, pub n2z: *const f32,      // at v0 + e2; all nine null = a flat mesh
+}
+#[repr(C)]
+pub struct RbrtSceneShading {                          // rbrt_scene_shading_t: smooth shading of meshes
+    pub n_meshes: u32,                                 // == RbrtScene::n_meshes
+    pub reserved: u32,                                 // 0
+    pub meshes: *const RbrtMeshNormals,                // one per mesh, or null = every mesh flat
+}
 #[repr(C)]
 pub struct RbrtRenderOpts {
     pub spp: u32, pub max_depth: u32, pub min_dist: f32, pub max_dist: f32, pub bg: [f32; 3],
@@ -55,6 +67,8 @@ extern "C" {
     pub fn rbrt_render_opts_default(opts: *mut RbrtRenderOpts);
     pub fn rbrt_hip_render(cam: *const RbrtCamera, scene: *const RbrtScene, opts: *const RbrtRenderOpts,
                            out_radiance: *mut f32, out_rgb8: *mut u8) -> c_int;
+    pub fn rbrt_hip_render_shaded(cam: *const RbrtCamera, scene: *const RbrtScene, shading: *const RbrtSceneShading,
+                                  opts: *const RbrtRenderOpts, out_radiance: *mut f32, out_rgb8: *mut u8) -> c_int;
     pub fn rbrt_hip_last_error() -> *const c_char;
     pub fn rbrt_hip_device_count() -> c_int;
     pub fn rbrt_hip_supported_flags() -> u32;           // test RBRT_FLAG_THIN_LENS here before relying on it

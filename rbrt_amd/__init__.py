@@ -41,7 +41,9 @@ def render_scene(cam: abi.Camera, num_samples: int, scene: abi.SceneData, seed: 
 
     Same contract as the reference's render_scene (lib.rs:75-79) plus the pre-gamma radiance:
     returns (radiance float32[H,W,3], rgb8 uint8[H,W,3]); want_radiance=False: (None, rgb8), exactly what the
-    reference returns. `lens`: a thin lens (see _cam_arg), None for the reference's pinhole camera.
+    reference returns. `lens`: a thin lens (see _cam_arg), None for the reference's pinhole camera. A scene with smooth
+    meshes (MeshData normals=, YAML `shading: smooth`) goes through rbrt_hip_render_shaded, every other one through
+    rbrt_hip_render.
     """
     lib = load_hip()
     opts = default_opts(spp=num_samples, seed=seed, **opt_overrides)
@@ -49,10 +51,20 @@ def render_scene(cam: abi.Camera, num_samples: int, scene: abi.SceneData, seed: 
     H, W = cam.img_height_pix, cam.img_width_pix
     rad = np.zeros((H, W, 3), np.float32) if want_radiance else None
     rgb = np.empty((H, W, 3), np.uint8) if not want_radiance else np.zeros((H, W, 3), np.uint8)
-    rc = lib.rbrt_hip_render(cam_p, scene.ptr(), C.byref(opts), rad.ctypes.data_as(abi.f32p) if want_radiance else None,
-                             rgb.ctypes.data_as(abi.u8p))
+    out = (rad.ctypes.data_as(abi.f32p) if want_radiance else None, rgb.ctypes.data_as(abi.u8p))
+    shading = _shading_ptr(scene)
+    if shading is None:
+        rc = lib.rbrt_hip_render(cam_p, scene.ptr(), C.byref(opts), *out)
+    else:
+        rc = lib.rbrt_hip_render_shaded(cam_p, scene.ptr(), shading, C.byref(opts), *out)
     abi.check(rc)
     return rad, rgb
+
+
+def _shading_ptr(scene):
+    """The scene's rbrt_scene_shading_t*, None when no mesh carries corner normals."""
+    f = getattr(scene, "shading_ptr", None)
+    return f() if f is not None else None
 
 
 def last_render_times() -> dict:
@@ -70,7 +82,11 @@ class HipScene:
         self._h = C.c_void_p()
         self.device = device
         self.scene = scene  # keep host arrays alive
-        abi.check(self._lib.rbrt_hip_scene_create(scene.ptr(), device, C.byref(self._h)))
+        shading = _shading_ptr(scene)
+        if shading is None:
+            abi.check(self._lib.rbrt_hip_scene_create(scene.ptr(), device, C.byref(self._h)))
+        else:
+            abi.check(self._lib.rbrt_hip_scene_create_shaded(scene.ptr(), shading, device, C.byref(self._h)))
 
     def close(self):
         if self._h:
@@ -221,6 +237,15 @@ class HipScene:
         abi.check(self._lib.rbrt_hip_debug_primary_cull_lens(self._h, C.byref(lens), out.ctypes.data_as(C.POINTER(C.c_uint32)),
                                                              out.size))
         return out.reshape(ty, tx)
+
+    def shading_normals(self, rays, min_dist=0.001, max_dist=2000.0):
+        """The normal the scatter pass would use at each ray's closest hit, NaN for a miss (rbrt_hip_debug_shading_normals;
+        test hook): float32 (n, 3)."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        out = np.zeros((rays.shape[0], 3), np.float32)
+        abi.check(self._lib.rbrt_hip_debug_shading_normals(self._h, rays.ctypes.data_as(abi.f32p), rays.shape[0], min_dist,
+                                                           max_dist, out.ctypes.data_as(abi.f32p)))
+        return out
 
     def trace_rays(self, rays, min_dist=0.001, max_dist=2000.0):
         rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)

@@ -79,6 +79,19 @@ class Scene(C.Structure):
     ]
 
 
+NORMAL_FIELDS = ("n0x", "n0y", "n0z", "n1x", "n1y", "n1z", "n2x", "n2y", "n2z")
+
+
+class MeshNormals(C.Structure):
+    """rbrt_mesh_normals_t: the corner normals of a smooth mesh's SoA entries (all NULL: flat)."""
+    _fields_ = [(k, f32p) for k in NORMAL_FIELDS]
+
+
+class SceneShading(C.Structure):
+    """rbrt_scene_shading_t: one MeshNormals per mesh of the scene."""
+    _fields_ = [("n_meshes", C.c_uint32), ("reserved", C.c_uint32), ("meshes", C.POINTER(MeshNormals))]
+
+
 class Camera(C.Structure):
     _fields_ = [
         ("position", C.c_float * 3),
@@ -187,6 +200,9 @@ HIP_SYMBOLS = {
     "rbrt_hip_scene_set_pipeline": (C.c_int, [C.c_void_p, C.c_uint32]),
     "rbrt_hip_scene_info": (C.c_int, [C.c_void_p, C.POINTER(SceneInfo)]),
     "rbrt_hip_supported_flags": (C.c_uint32, []),
+    "rbrt_hip_scene_create_shaded": (C.c_int, [C.POINTER(Scene), C.POINTER(SceneShading), C.c_int, C.POINTER(C.c_void_p)]),
+    "rbrt_hip_render_shaded": (C.c_int, [C.POINTER(Camera), C.POINTER(Scene), C.POINTER(SceneShading), C.POINTER(RenderOpts),
+                                         f32p, u8p]),
 }
 # ... and include/rbrt_hip_debug.h (test hooks and diagnostics, same library)
 DEBUG_SYMBOLS = {
@@ -218,6 +234,7 @@ DEBUG_SYMBOLS = {
     "rbrt_hip_scene_create_times": (C.c_int, [C.c_void_p, C.POINTER(CallTimes)]),
     "rbrt_hip_last_render_times": (C.c_int, [C.POINTER(CallTimes)]),
     "rbrt_hip_scene_refine_wait": (C.c_int, [C.c_void_p, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    "rbrt_hip_debug_shading_normals": (C.c_int, [C.c_void_p, f32p, C.c_size_t, C.c_float, C.c_float, f32p]),
 }
 
 
@@ -321,9 +338,20 @@ class SceneData:
         self._order = None if self.element_order is None else (C.c_uint32 * len(self.element_order))(*self.element_order)
         self.struct = Scene(len(self.spheres), self._sph, len(self.meshes), self._msh, len(self.triangles), self._tri,
                             self._order if self._order is not None else C.POINTER(C.c_uint32)())
+        # smooth shading: an rbrt_scene_shading_t only when some mesh has corner normals
+        self._nrm = (MeshNormals * max(1, len(self.meshes)))()
+        for i, md in enumerate(self.meshes):
+            if md.normals is not None:
+                self._nrm[i] = md.normals_struct
+        self.shading = (SceneShading(len(self.meshes), 0, self._nrm)
+                        if any(md.normals is not None for md in self.meshes) else None)
 
     def ptr(self):
         return C.byref(self.struct)
+
+    def shading_ptr(self):
+        """The rbrt_scene_shading_t* of the *_shaded entry points, or None when every mesh is flat."""
+        return None if self.shading is None else C.byref(self.shading)
 
 
 class MeshData:
@@ -331,7 +359,8 @@ class MeshData:
 
     FIELDS = ("v0x", "v0y", "v0z", "e1x", "e1y", "e1z", "e2x", "e2y", "e2z", "nx", "ny", "nz")
 
-    def __init__(self, arrays: dict, is_padding: np.ndarray, n_real: int, bbox_lo, bbox_hi, mat: Material):
+    def __init__(self, arrays: dict, is_padding: np.ndarray, n_real: int, bbox_lo, bbox_hi, mat: Material, normals=None):
+        """normals: None (flat) or a dict of the nine corner normal arrays n0x .. n2z (n_total each): a smooth mesh."""
         self.arrays = {k: np.ascontiguousarray(arrays[k], dtype=np.float32) for k in self.FIELDS}
         self.is_padding = np.ascontiguousarray(is_padding, dtype=np.uint8)
         n_total = len(self.is_padding)
@@ -348,6 +377,17 @@ class MeshData:
         self.struct.bbox_lo = _f3(bbox_lo)
         self.struct.bbox_hi = _f3(bbox_hi)
         self.struct.mat = mat
+        self.normals = None
+        self.normals_struct = MeshNormals()
+        if normals is not None:
+            self.normals = {k: np.ascontiguousarray(normals[k], dtype=np.float32) for k in NORMAL_FIELDS}
+            for k in NORMAL_FIELDS:
+                assert len(self.normals[k]) == n_total, k
+                setattr(self.normals_struct, k, fptr(self.normals[k]))
+
+    def with_normals(self, normals):
+        """A copy of this mesh with corner normals (None: flat), sharing nothing mutable with it."""
+        return MeshData(self.arrays, self.is_padding, self.n_real, self.bbox_lo, self.bbox_hi, self.struct.mat, normals)
 
 
 def default_opts(spp: int = 5, seed: int = 1, **kw) -> RenderOpts:
@@ -385,6 +425,8 @@ def load_host() -> C.CDLL:
     lib.rbrt_host_scene_lens.argtypes = [C.c_void_p]
     lib.rbrt_host_scene_scene.restype = C.POINTER(Scene)
     lib.rbrt_host_scene_scene.argtypes = [C.c_void_p]
+    lib.rbrt_host_scene_shading.restype = C.POINTER(SceneShading)
+    lib.rbrt_host_scene_shading.argtypes = [C.c_void_p]
     lib.rbrt_host_scene_free.restype = None
     lib.rbrt_host_scene_free.argtypes = [C.c_void_p]
     lib.rbrt_host_save_image.restype = C.c_int
@@ -416,9 +458,14 @@ class HostScene:
             self.lens = CameraLens()
             C.memmove(C.byref(self.lens), lp, C.sizeof(CameraLens))
         self.struct = self._lib.rbrt_host_scene_scene(self._h).contents
+        sp = self._lib.rbrt_host_scene_shading(self._h)  # NULL unless some mesh is smooth
+        self.shading = sp.contents if sp else None
 
     def ptr(self):
         return C.byref(self.struct)
+
+    def shading_ptr(self):
+        return None if self.shading is None else C.byref(self.shading)
 
     def mesh_arrays(self, i: int) -> dict:
         m = self.struct.meshes[i]
@@ -427,6 +474,9 @@ class HostScene:
         out["bbox_lo"] = np.array(list(m.bbox_lo), np.float32)
         out["bbox_hi"] = np.array(list(m.bbox_hi), np.float32)
         out["n_real"] = m.n_real
+        if self.shading is not None and self.shading.meshes[i].n0x:  # a smooth mesh: its corner normals
+            mn = self.shading.meshes[i]
+            out.update({k: np.ctypeslib.as_array(getattr(mn, k), (m.n_total,)).copy() for k in NORMAL_FIELDS})
         return out
 
     def close(self):

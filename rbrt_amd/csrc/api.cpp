@@ -37,6 +37,7 @@ hipError_t launch_unpack(const float* gathered, uint32_t width, uint32_t height,
                          size_t rank_stride_pixels, float* out_radiance, uint8_t* out_rgb8, hipStream_t stream);
 hipError_t launch_trace_rays(const TraceParams& P, const float* rays, size_t n, float* out_t, int32_t* out_obj,
                              int32_t* out_tri, float* out_dist, hipStream_t stream);
+hipError_t launch_shading_normals(const TraceParams& P, const float* rays, size_t n, float* out_normal, hipStream_t stream);
 hipError_t launch_gate_selftest(const float* d_box, const float* d_rays, size_t n, uint8_t* d_fast, uint8_t* d_exact);
 hipError_t launch_ieee_selftest(uint64_t seed, size_t n, unsigned long long* d_counts);
 hipError_t launch_ieee_debug(const float* d_x, size_t n, const float* d_v, size_t m, float* d_sqrt, uint8_t* d_sqrt_short,
@@ -920,7 +921,8 @@ bool device_builder_is_cheaper(uint32_t n_total, const CreateHint& hint) {
     return n_total >= 8u && device_s < host_s;
 }
 
-int scene_create_impl(const rbrt_scene_t* scene, int device, rbrt_hip_scene_t** out, const CreateHint& hint);
+int scene_create_impl(const rbrt_scene_t* scene, const rbrt_scene_shading_t* shading, int device, rbrt_hip_scene_t** out,
+                      const CreateHint& hint);
 
 }  // namespace
 
@@ -972,14 +974,65 @@ uint32_t rbrt_hip_tile_number(uint32_t tile_row, uint32_t tile_col, uint32_t til
 }
 
 int rbrt_hip_scene_create(const rbrt_scene_t* scene, int device, rbrt_hip_scene_t** out) {
-    return scene_create_impl(scene, device, out, CreateHint());
+    return scene_create_impl(scene, nullptr, device, out, CreateHint());
+}
+
+int rbrt_hip_scene_create_shaded(const rbrt_scene_t* scene, const rbrt_scene_shading_t* shading, int device, rbrt_hip_scene_t** out) {
+    return scene_create_impl(scene, shading, device, out, CreateHint());
 }
 
 }  // extern "C"
 
 namespace {
 
-int scene_create_impl(const rbrt_scene_t* scene, int device, rbrt_hip_scene_t** out, const CreateHint& hint) {
+// The corner normals of smooth meshes (rbrt_hip.h rbrt_scene_shading_t): all nine arrays or none, every value finite.
+int check_shading(const rbrt_scene_t& scene, const rbrt_scene_shading_t* sh) {
+    if (!sh) return RBRT_OK;
+    if (sh->n_meshes != scene.n_meshes) return fail(RBRT_ERR_INVALID_ARG, "shading: n_meshes differs from the scene's");
+    if (sh->reserved != 0) return fail(RBRT_ERR_INVALID_ARG, "shading: reserved must be 0");
+    if (!sh->meshes) return RBRT_OK;
+    for (uint32_t i = 0; i < sh->n_meshes; ++i) {
+        const rbrt_mesh_normals_t& mn = sh->meshes[i];
+        const float* a[9] = {mn.n0x, mn.n0y, mn.n0z, mn.n1x, mn.n1y, mn.n1z, mn.n2x, mn.n2y, mn.n2z};
+        int n_null = 0;
+        for (const float* p : a) n_null += p == nullptr;
+        if (n_null == 9) continue;
+        if (n_null != 0) return fail(RBRT_ERR_INVALID_ARG, "shading: mesh " + std::to_string(i) + " has some corner normal arrays NULL, but not all nine");
+        for (const float* p : a)
+            for (uint32_t k = 0; k < scene.meshes[i].n_total; ++k)
+                if (!std::isfinite(p[k]))
+                    return fail(RBRT_ERR_INVALID_ARG, "shading: mesh " + std::to_string(i) + " has a non-finite corner normal at entry " + std::to_string(k));
+    }
+    return RBRT_OK;
+}
+
+bool mesh_is_smooth(const rbrt_scene_shading_t* sh, uint32_t i) { return sh && sh->meshes && sh->meshes[i].n0x; }
+
+// The normals allocation of a smooth mesh (device_types.h Normal4, SmoothRec): n_total Normal4s whose w holds the bits of
+// n_total, then n_total records of the entries' geometry and corner normals, all bitwise the caller's values.
+std::vector<Normal4> smooth_normals_blob(const rbrt_mesh_t& m, const rbrt_mesh_normals_t& mn) {
+    const uint32_t n = m.n_total;
+    const size_t per = sizeof(SmoothRec) / sizeof(Normal4);
+    std::vector<Normal4> blob(size_t(n) * (1 + per));
+    float w;
+    std::memcpy(&w, &n, sizeof(w));
+    for (uint32_t k = 0; k < n; ++k) blob[k] = Normal4{m.nx[k], m.ny[k], m.nz[k], w};
+    SmoothRec* rec = reinterpret_cast<SmoothRec*>(blob.data() + n);
+    for (uint32_t k = 0; k < n; ++k) {
+        SmoothRec& r = rec[k];
+        r.v0[0] = m.v0x[k], r.v0[1] = m.v0y[k], r.v0[2] = m.v0z[k];
+        r.e1[0] = m.e1x[k], r.e1[1] = m.e1y[k], r.e1[2] = m.e1z[k];
+        r.e2[0] = m.e2x[k], r.e2[1] = m.e2y[k], r.e2[2] = m.e2z[k];
+        r.n0[0] = mn.n0x[k], r.n0[1] = mn.n0y[k], r.n0[2] = mn.n0z[k];
+        r.n1[0] = mn.n1x[k], r.n1[1] = mn.n1y[k], r.n1[2] = mn.n1z[k];
+        r.n2[0] = mn.n2x[k], r.n2[1] = mn.n2y[k], r.n2[2] = mn.n2z[k];
+        r.pad[0] = r.pad[1] = 0.0f;
+    }
+    return blob;
+}
+
+int scene_create_impl(const rbrt_scene_t* scene, const rbrt_scene_shading_t* shading, int device, rbrt_hip_scene_t** out,
+                      const CreateHint& hint) {
     if (!scene || !out) return fail(RBRT_ERR_INVALID_ARG, "scene_create: null argument");
     *out = nullptr;
     if (scene->n_spheres && !scene->spheres) return fail(RBRT_ERR_INVALID_ARG, "spheres is null");
@@ -1016,6 +1069,7 @@ int scene_create_impl(const rbrt_scene_t* scene, int device, rbrt_hip_scene_t** 
                           !m.e2z || !m.nx || !m.ny || !m.nz || !m.is_padding))
             return fail(RBRT_ERR_INVALID_ARG, "mesh array pointer is null");
     }
+    if (int rc = check_shading(*scene, shading)) return rc;
     const double t_create0 = now_s();
     if (int rc = ensure_device(device)) return rc;
 
@@ -1127,9 +1181,11 @@ int scene_create_impl(const rbrt_scene_t* scene, int device, rbrt_hip_scene_t** 
         put_mat(n_elem + i, m.mat);
         DevMesh& dm = meshes[i];
         Normal4* d_normals = nullptr;
+        const bool smooth = mesh_is_smooth(shading, i) && m.n_total != 0;
         {
             void* p = nullptr;
-            HIP_TRY_BAIL(dev_alloc(s, std::max<size_t>(size_t(m.n_total) * sizeof(Normal4), 16), &p));
+            const size_t per_entry = sizeof(Normal4) + (smooth ? sizeof(SmoothRec) : 0);
+            HIP_TRY_BAIL(dev_alloc(s, std::max<size_t>(size_t(m.n_total) * per_entry, 16), &p));
             d_normals = static_cast<Normal4*>(p);
         }
         bool built = false;
@@ -1167,8 +1223,13 @@ int scene_create_impl(const rbrt_scene_t* scene, int device, rbrt_hip_scene_t** 
                             const uint32_t leaf = uint32_t(~nd.child[c]);
                             nd.child[c] = ~int32_t((((leaf >> kLeafBits) + tri_base[i]) << kLeafBits) | (leaf & uint32_t(kLeafMax - 1)));
                         }
-            std::vector<Normal4> normals(m.n_total);
-            for (uint32_t k = 0; k < m.n_total; ++k) normals[k] = Normal4{m.nx[k], m.ny[k], m.nz[k], 0.0f};
+            std::vector<Normal4> normals;
+            if (smooth) {
+                normals = smooth_normals_blob(m, shading->meshes[i]);
+            } else {
+                normals.resize(m.n_total);
+                for (uint32_t k = 0; k < m.n_total; ++k) normals[k] = Normal4{m.nx[k], m.ny[k], m.nz[k], 0.0f};
+            }
             const double tb1 = now_s();
             BvhNode4* d_nodes = nullptr;
             if (int rc = upload(s, bvh.nodes, &d_nodes)) return bail(rc);
@@ -1184,6 +1245,12 @@ int scene_create_impl(const rbrt_scene_t* scene, int device, rbrt_hip_scene_t** 
             s->stack_need = std::max(s->stack_need, bvh.stack_need);
             s->total_nodes += bvh.nodes.size();
             s->total_tris += bvh.tris.size();
+        }
+        if (built && smooth) {  // (the device builder wrote the flat Normal4s and has synchronised: the smooth ones replace them)
+            const double tu0 = now_s();
+            const std::vector<Normal4> blob = smooth_normals_blob(m, shading->meshes[i]);
+            HIP_TRY_BAIL(hipMemcpy(d_normals, blob.data(), blob.size() * sizeof(Normal4), hipMemcpyHostToDevice));
+            t_upload += now_s() - tu0;
         }
         dm.tris = s->d_tris, dm.normals = d_normals;
         float diag2 = 0.0f;
@@ -1954,6 +2021,11 @@ int rbrt_hip_unpack_tiles(int device, void* stream, const float* d_gathered, uin
 
 int rbrt_hip_render(const rbrt_camera_t* cam, const rbrt_scene_t* scene, const rbrt_render_opts_t* opts,
                     float* out_radiance, uint8_t* out_rgb8) {
+    return rbrt_hip_render_shaded(cam, scene, nullptr, opts, out_radiance, out_rgb8);
+}
+
+int rbrt_hip_render_shaded(const rbrt_camera_t* cam, const rbrt_scene_t* scene, const rbrt_scene_shading_t* shading,
+                           const rbrt_render_opts_t* opts, float* out_radiance, uint8_t* out_rgb8) {
     if (!cam || !scene || !opts) return fail(RBRT_ERR_INVALID_ARG, "render: null argument");
     if (int rc = lens_invalid(cam, opts)) return rc;
     const double t_call0 = now_s();
@@ -1969,7 +2041,7 @@ int rbrt_hip_render(const rbrt_camera_t* cam, const rbrt_scene_t* scene, const r
         const uint32_t w1 = opts->tile_world ? opts->tile_world : 1;
         hint.render_s_est = double(cam->img_width_pix) * cam->img_height_pix * opts->spp / w1 / 10.0e9;
     }
-    if (int rc = scene_create_impl(scene, 0, &s, hint)) return rc;
+    if (int rc = scene_create_impl(scene, shading, 0, &s, hint)) return rc;
     times = s->create_times;
     if (s->pipeline == 0) s->pipeline = 3;  // (the batches of this one render overlap on three lanes)
     const double t_render0 = now_s();
@@ -2321,6 +2393,29 @@ static int debug_primary_cull(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, uin
     // (the table is indexed by tile NUMBER, rbrt_hip.h "How tiles are dealt to ranks"; the hook hands it over in image order)
     for (uint32_t ty = 0; ty < tiles_y; ++ty)
         for (uint32_t tx = 0; tx < tiles_x; ++tx) out_words[size_t(ty) * tiles_x + tx] = by_number[tile_number(ty, tx, tiles_x)];
+    return RBRT_OK;
+}
+
+int rbrt_hip_debug_shading_normals(rbrt_hip_scene_t* s, const float* rays, size_t n, float min_dist, float max_dist, float* out_normal) {
+    if (!s || (n && (!rays || !out_normal))) return fail(RBRT_ERR_INVALID_ARG, "debug_shading_normals: null argument");
+    if (n == 0) return RBRT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    rbrt_render_opts_t o;
+    rbrt_render_opts_default(&o);
+    o.min_dist = min_dist;
+    o.max_dist = max_dist;
+    TraceParams P;
+    fill_trace_params(s, nullptr, &o, P);
+    float *d_rays = nullptr, *d_out = nullptr;
+    auto cleanup = [&]() { (void)hipFree(d_rays), (void)hipFree(d_out); };
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_rays), n * 6 * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_out), n * 3 * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(d_rays, rays, n * 6 * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = launch_shading_normals(P, d_rays, n, d_out, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out_normal, d_out, n * 3 * sizeof(float), hipMemcpyDeviceToHost);
+    cleanup();
+    if (e != hipSuccess) return fail(RBRT_ERR_HIP, std::string("debug_shading_normals: ") + hipGetErrorString(e));
     return RBRT_OK;
 }
 

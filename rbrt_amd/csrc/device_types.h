@@ -72,9 +72,20 @@ struct alignas(16) BvhTri {
 };
 static_assert(sizeof(BvhTri) == 48, "tri must be 48 B");
 
+// The stored face normal of a mesh entry. w is 0 for a flat mesh. For a smooth mesh (rbrt_scene_shading_t) w holds the bits
+// of n_total: the entry's smooth record (SmoothRec) is record [reference index] of the array that starts n_total Normal4s
+// past the mesh's first Normal4, in the same allocation. The scatter pass loads the Normal4 anyway, so a flat hit pays one
+// compare; the LDS layout of a launch does not depend on the shading.
 struct alignas(16) Normal4 {
     float x, y, z, w;
 };
+// One smooth mesh entry: its geometry, bitwise the SoA arrays' (for the barycentrics), and its three corner normals.
+struct alignas(16) SmoothRec {
+    float v0[3], e1[3], e2[3];
+    float n0[3], n1[3], n2[3];
+    float pad[2];
+};
+static_assert(sizeof(SmoothRec) == 80 && sizeof(SmoothRec) % sizeof(Normal4) == 0, "smooth record must be 80 B");
 
 struct DevSphere {
     float center[3];
@@ -99,7 +110,7 @@ RBRT_HOST_DEVICE inline int32_t dev_material_kind(int32_t kind) { return kind ==
 struct DevMesh {
     const BvhNode4* nodes;
     const BvhTri* tris;      // the SCENE's triangle array (all meshes; this mesh's leaves point into its own part)
-    const Normal4* normals;  // [reference index] -> (nx, ny, nz, 0)
+    const Normal4* normals;  // [reference index] -> (nx, ny, nz, 0), or (nx, ny, nz, bits of n_total) and the smooth records
     float bbox_lo[3];
     float bbox_hi[3];
     float center[3];  // of the bbox

@@ -560,6 +560,33 @@ __device__ __forceinline__ void scene_hit(const TraceParams& P, V3 o, V3 d, uint
 }
 
 // ---------------------------------------------------------------------------------------------
+// Shading normal of a mesh hit (rbrt_hip.h rbrt_scene_shading_t): the stored face normal of entry `tri`, or, on a smooth
+// mesh, the corner normals interpolated with the barycentrics of the Moller-Trumbore test that made it the closest hit
+// (tri_test's u and v, operation for operation). Called by the megakernel's scatter pass and the debug hook alike.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ V3 smooth_normal(const SmoothRec* rec, V3 o, V3 d, V3 face) {
+    const V3 v0 = mk(rec->v0), e1 = mk(rec->e1), e2 = mk(rec->e2);
+    const V3 h = cross(d, e2);
+    const float f = 1.0f / dot(e1, h);
+    const V3 s = o - v0;
+    const float u = f * dot(s, h);
+    const V3 q = cross(s, e1);
+    const float v = f * dot(d, q);
+    const float w = (1.0f - u) - v;
+    const V3 m = (w * mk(rec->n0) + u * mk(rec->n1)) + v * mk(rec->n2);
+    const V3 n = normalize(m);  // (a zero m gives 0 / 0: not finite)
+    const bool ok = __builtin_isfinite(n.x) && __builtin_isfinite(n.y) && __builtin_isfinite(n.z);
+    return ok ? n : face;
+}
+__device__ __forceinline__ V3 mesh_shading_normal(const Normal4* normals, uint32_t tri, V3 o, V3 d) {
+    const Normal4 nn = normals[tri];
+    const V3 face = mk(nn.x, nn.y, nn.z);  // mesh.rs:253-257
+    const uint32_t n_total = __float_as_uint(nn.w);
+    if (n_total == 0u) return face;
+    return smooth_normal(reinterpret_cast<const SmoothRec*>(normals + n_total) + tri, o, d, face);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Materials
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ V3 random_point_in_unit_sphere(Rng& rng) {  // materials.rs:14-30
@@ -1311,6 +1338,32 @@ __global__ __launch_bounds__(kRaysBlock) void trace_rays_kernel(const TraceParam
     if (out_dist) out_dist[i] = hit ? h.dist : nanv;
 }
 
+// The normal the scatter pass would use at the closest hit of arbitrary rays (test hook behind rbrt_hip_debug_shading_normals).
+__global__ __launch_bounds__(kRaysBlock) void shading_normals_kernel(const TraceParams P, const float* __restrict__ rays, size_t n,
+                                                                 float* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    uint32_t* stack = lds + threadIdx.x;
+    const size_t i = size_t(blockIdx.x) * kRaysBlock + threadIdx.x;
+    if (i >= n) return;
+    const V3 o = mk(rays + 6 * i), d = mk(rays + 6 * i + 3);
+    HitRec h;
+    LocalCounters lc = {0, 0, 0, 0, 0};
+    scene_hit<false>(P, o, d, stack, uint32_t(kRaysBlock), h, lc);
+    const float nanv = __int_as_float(0x7fc00000);
+    V3 nrm = mk(nanv, nanv, nanv);
+    const uint32_t n_elem = P.n_spheres + P.n_elem_tris;
+    if (h.obj >= 0 && uint32_t(h.obj) < n_elem) {
+        const uint32_t desc = P.elems != nullptr ? P.elems[h.obj] : uint32_t(h.obj);
+        if (desc >> 31) nrm = mk(P.elem_tris[desc & 0x7FFFFFFFu].normal);  // triangle.rs:432
+        else nrm = (o + h.t * d) - mk(P.spheres[desc].center);             // sphere.rs:56, unnormalised
+    } else if (h.obj >= 0) {
+        nrm = mesh_shading_normal(P.meshes[uint32_t(h.obj) - n_elem].normals, h.tri, o, d);
+    }
+    out[3 * i + 0] = nrm.x;
+    out[3 * i + 1] = nrm.y;
+    out[3 * i + 2] = nrm.z;
+}
+
 // Test hook (rbrt_hip_selftest_ieee): the short IEEE forms (sqrt_core inside ieee_sqrt, normalize) against the
 // compiler's on pseudo-random operands. Waves 0,1,2 (mod 4) draw every lane's operands from the whole domain the gates
 // admit, so the short forms are what runs: x in (2^-80, 2^100); the largest component of a in [2^-40, 2^(kNormTopExp+1))
@@ -1543,6 +1596,13 @@ hipError_t launch_trace_rays(const TraceParams& P, const float* rays, size_t n, 
     hipLaunchKernelGGL(trace_rays_kernel, dim3(uint32_t((n + kRaysBlock - 1) / kRaysBlock)), dim3(kRaysBlock),
                        size_t(kStackMax) * kRaysBlock * sizeof(uint32_t), stream, P, rays, n, out_t, out_obj,
                        out_tri, out_dist);
+    return hipGetLastError();
+}
+
+hipError_t launch_shading_normals(const TraceParams& P, const float* rays, size_t n, float* out_normal, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(shading_normals_kernel, dim3(uint32_t((n + kRaysBlock - 1) / kRaysBlock)), dim3(kRaysBlock),
+                       size_t(kStackMax) * kRaysBlock * sizeof(uint32_t), stream, P, rays, n, out_normal);
     return hipGetLastError();
 }
 

@@ -961,10 +961,8 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                     const uint32_t desc = P.n_elem_tris != 0u ? sc.elem[uint32_t(s_obj)] : uint32_t(s_obj);
                     if (desc >> 31) n = mk(sc.tri + (desc & 0x7FFFFFFFu) * kTriDw + 9);  // triangle.rs:432: the stored normal
                     else n = p - mk(sc.sph + desc * kSphDw);                            // sphere.rs:56, unnormalised
-                } else {
-                    const Normal4 nn =
-                        lds_ptr<Normal4>(sc.mesh + (uint32_t(s_obj) - n_elem) * kMeshDw + MD_NORMALS)[s_tri];
-                    n = mk(nn.x, nn.y, nn.z);  // mesh.rs:253-257
+                } else {  // the stored face normal (mesh.rs:253-257), or a smooth mesh's shading normal
+                    n = mesh_shading_normal(lds_ptr<Normal4>(sc.mesh + (uint32_t(s_obj) - n_elem) * kMeshDw + MD_NORMALS), s_tri, o, d);
                 }
                 DevMaterial m;
                 {

@@ -41,6 +41,8 @@ const rbrt_camera_t* rbrt_host_scene_camera(const rbrt_host_scene* h) { return &
 // The camera with its thin lens (camera_aperture_mm > 0), or NULL for a pinhole camera.
 const rbrt_camera_lens_t* rbrt_host_scene_lens(const rbrt_host_scene* h) { return h->cam.thin_lens ? &h->lens_abi : nullptr; }
 const rbrt_scene_t* rbrt_host_scene_scene(const rbrt_host_scene* h) { return &h->view.scene; }
+// The corner normals of the smooth meshes (YAML `shading: smooth`), or NULL when every mesh is flat.
+const rbrt_scene_shading_t* rbrt_host_scene_shading(const rbrt_host_scene* h) { return h->view.shading_ptr(); }
 void rbrt_host_scene_free(rbrt_host_scene* h) { delete h; }
 
 int rbrt_host_write_png(const char* path, const uint8_t* rgb, uint32_t width, uint32_t height) {

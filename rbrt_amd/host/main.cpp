@@ -4,7 +4,8 @@
 // plus, not in the reference: --seed N (default 1), --gpus N (default 1), --gather host|rccl, --oversubscribe,
 // --pass-samples N, --checkpoint FILE, --checkpoint-every N, --report FILE (machine-readable timing of the run),
 // --background R,G,B (a constant background instead of the reference's sky gradient), --aperture MM and
-// --focus-distance D (a thin lens: they override the YAML's camera_aperture_mm / camera_focus_distance).
+// --focus-distance D (a thin lens: they override the YAML's camera_aperture_mm / camera_focus_distance), --shading flat|smooth
+// (overrides every mesh blueprint's `shading`).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -44,6 +45,8 @@ void usage() {
         "                                   [default: the YAML's, else 0]\n"
         "      --focus-distance <d>         distance from the camera position to the plane in focus, along the view\n"
         "                                   direction, in scene units; overrides the YAML's camera_focus_distance\n"
+        "      --shading <how>              flat (face normals) or smooth (corner normals: the .obj's vn, else area-weighted\n"
+        "                                   vertex normals) for every mesh; overrides the YAML's `shading` [default: the YAML's]\n"
         "  -h, --help                       Print help\n"
         "  -V, --version                    Print version\n");
 }
@@ -110,6 +113,7 @@ int main(int argc, char** argv) {
     bool oversubscribe = false, constant_background = false;
     float background[3] = {0.0f, 0.0f, 0.0f};
     std::optional<float> aperture, focus_distance;
+    std::optional<bool> smooth;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         std::string val;
@@ -184,6 +188,13 @@ int main(int argc, char** argv) {
                 return 2;
             }
             (a == "--aperture" ? aperture : focus_distance) = f;
+        } else if (a == "--shading") {
+            const std::string v = value();
+            if (v != "flat" && v != "smooth") {
+                std::fprintf(stderr, "error: invalid value '%s' for '--shading' [possible values: flat, smooth]\n", v.c_str());
+                return 2;
+            }
+            smooth = v == "smooth";
         } else if (a == "--seed") {
             seed = std::strtoull(value(), nullptr, 10);
         } else {
@@ -199,6 +210,8 @@ int main(int argc, char** argv) {
         rbrt::SceneBlueprint bp = rbrt::load_blueprints_from_yaml_file(config);
         if (aperture) bp.camera_blueprint.camera_aperture_mm = aperture;
         if (focus_distance) bp.camera_blueprint.camera_focus_distance = focus_distance;
+        if (smooth)
+            for (rbrt::TriangleMeshBlueprint& mb : bp.mesh_blueprints) mb.smooth = *smooth;
         rbrt::Camera cam = rbrt::camera_from_blueprint(bp.camera_blueprint, height, width);  // (checks the lens again)
         const auto t1 = clock::now();
         rbrt::Scene scene = rbrt::create_scene_from_scene_blueprint(bp);  // .obj parse, transform, SoA conversion (mesh.rs:41-181)

@@ -99,6 +99,7 @@ struct TriangleMeshBlueprint {
     std::string material_type;
     std::optional<Vec3> albedo;
     std::optional<float> material_param;
+    bool smooth = false;  // `shading: smooth` (not in the reference): shade with corner normals, rbrt_scene_shading_t
 };
 struct SphereBlueprint {
     float radius = 0;
@@ -147,11 +148,19 @@ struct TriangleMesh {
     Vec3 bbox_lower, bbox_upper;
     Material material;
     uint32_t num_triangles = 0;  // before padding
-    // TriangleMesh::new(filepath, translation, rotation, scale, material), mesh.rs:41-74
+    // Smooth shading (not in the reference): corner_normals[k][c] = component c of corner k's normal of every SoA entry
+    // (padding entries copy entry 0's, as the other arrays do); all empty = a flat mesh.
+    std::vector<float> corner_normals[3][3];
+    bool smooth() const { return !corner_normals[0][0].empty(); }
+    // TriangleMesh::new(filepath, translation, rotation, scale, material), mesh.rs:41-74; smooth: with corner normals
+    // (load_mesh_from_file)
     static TriangleMesh create(const std::string& filepath, Vec3 translation, Vec3 rotation, float scale,
-                               Material material);
-    static TriangleMesh from_triangles(std::vector<std::array<Vec3, 3>> pre_vertices, Material material);
+                               Material material, bool smooth = false);
+    // pre_normals: null (flat) or the three corner normals of every triangle
+    static TriangleMesh from_triangles(std::vector<std::array<Vec3, 3>> pre_vertices, Material material,
+                                       const std::vector<std::array<Vec3, 3>>* pre_normals = nullptr);
     rbrt_mesh_t to_abi() const;
+    rbrt_mesh_normals_t to_abi_normals() const;  // all nine NULL for a flat mesh
 };
 constexpr uint32_t kNumVectorLanes = 8;  // mesh.rs:28-30: the AVX layout is the one restated
 
@@ -159,6 +168,14 @@ constexpr uint32_t kNumVectorLanes = 8;  // mesh.rs:28-30: the AVX layout is the
 // per-face vertex triples in file order, then scale -> rotate -> translate (mesh.rs:102-112).
 std::vector<std::array<Vec3, 3>> load_mesh_vertices_from_file(const std::string& filepath, Vec3 translation,
                                                               Vec3 rotation, float scale);
+// The same triangles (and the same stdout line) and, with smooth, every corner's normal, per model (tobj's): the file's
+// `vn` transformed as rotate_point(sign(scale) n) when every corner of the model names one, else the area-weighted vertex
+// normals of the transformed triangles (scene.cpp smooth_model_normals).
+struct ObjMesh {
+    std::vector<std::array<Vec3, 3>> triangles;
+    std::vector<std::array<Vec3, 3>> corner_normals;  // empty unless smooth
+};
+ObjMesh load_mesh_from_file(const std::string& filepath, Vec3 translation, Vec3 rotation, float scale, bool smooth);
 Vec3 get_triangle_normal(const std::array<Vec3, 3>& corners);                             // triangle.rs:30-34
 void compute_min_max_3d(const std::vector<std::array<Vec3, 3>>& tris, Vec3& lo, Vec3& hi);  // aabbox.rs:62-88
 
@@ -177,6 +194,11 @@ struct Scene {
         std::vector<rbrt_triangle_t> triangles;
         std::vector<rbrt_mesh_t> meshes;
         rbrt_scene_t scene{};
+        std::vector<rbrt_mesh_normals_t> normals;  // [mesh]
+        rbrt_scene_shading_t shading{};
+        bool any_smooth = false;
+        // what rbrt_hip_scene_create_shaded gets: NULL when no mesh is smooth
+        const rbrt_scene_shading_t* shading_ptr() const { return any_smooth ? &shading : nullptr; }
     };
     AbiView to_abi() const;
 };

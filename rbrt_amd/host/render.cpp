@@ -81,6 +81,20 @@ uint64_t scene_fingerprint(const rbrt_camera_t& cam, const rbrt_scene_t& sc) {
     return h;
 }
 
+// ... and the corner normals of smooth meshes, only when there are any (a flat scene's checkpoints keep their fingerprint).
+uint64_t shading_fingerprint(const rbrt_scene_t& sc, const rbrt_scene_shading_t* sh, uint64_t h) {
+    if (!sh || !sh->meshes) return h;
+    for (uint32_t i = 0; i < sh->n_meshes; ++i) {
+        const rbrt_mesh_normals_t& mn = sh->meshes[i];
+        const uint32_t smooth = mn.n0x != nullptr;
+        h = fnv1a(&smooth, sizeof(smooth), h);
+        if (!smooth) continue;
+        const float* arrs[9] = {mn.n0x, mn.n0y, mn.n0z, mn.n1x, mn.n1y, mn.n1z, mn.n2x, mn.n2y, mn.n2z};
+        for (const float* a : arrs) h = fnv1a(a, size_t(sc.meshes[i].n_total) * sizeof(float), h);
+    }
+    return h;
+}
+
 struct CheckpointHeader {
     char magic[8];  // "RBRTCKP1"
     uint32_t width, height, spp, world;
@@ -195,7 +209,7 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
     std::memcpy(want.magic, "RBRTCKP1", 8);
     want.width = img.width, want.height = img.height, want.spp = num_samples, want.world = uint32_t(world);
     want.seed = cfg.seed;
-    want.fingerprint = cfg.checkpoint_path.empty() ? 0 : scene_fingerprint(c, view.scene);
+    want.fingerprint = cfg.checkpoint_path.empty() ? 0 : shading_fingerprint(view.scene, view.shading_ptr(), scene_fingerprint(c, view.scene));
     if (want.fingerprint != 0 && cfg.constant_background) {  // (only then: a default run keeps its checkpoints' fingerprint)
         want.fingerprint = fnv1a(&opts.flags, sizeof(opts.flags), want.fingerprint);
         want.fingerprint = fnv1a(opts.bg, sizeof(opts.bg), want.fingerprint);
@@ -310,7 +324,7 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
         const int dev = device_of(rank);
         const size_t npix = world > 1 ? rbrt_hip_packed_pixels(img.width, img.height, o.tile_rank, o.tile_world)
                                       : size_t(img.width) * img.height;
-        if (rbrt_hip_scene_create(&view.scene, dev, &hs) != RBRT_OK) fail(rbrt_hip_last_error());
+        if (rbrt_hip_scene_create_shaded(&view.scene, view.shading_ptr(), dev, &hs) != RBRT_OK) fail(rbrt_hip_last_error());
         std::memset(&t_create[rank], 0, sizeof(t_create[rank]));
         if (hs) (void)rbrt_hip_scene_create_times(hs, &t_create[rank]);
         // (every pass is followed by a synchronisation here: only the sample batches INSIDE a pass overlap, on three lanes;

@@ -248,6 +248,11 @@ SceneBlueprint load_blueprints_from_yaml_text(const std::string& text) {
         b.material_type = as_string(need(m, "material_type", "mesh blueprint"), "material_type");
         b.albedo = opt_vec3(m, "albedo", "albedo");
         b.material_param = opt_f32(m, "material_param", "material_param");
+        if (const Node* sh = m.find("shading"); sh && !sh->is_null()) {  // (not in the reference; absent = flat)
+            const std::string v = as_string(*sh, "shading");
+            if (v != "flat" && v != "smooth") throw Error("shading: expected `flat` or `smooth`, got `" + v + "`");
+            b.smooth = v == "smooth";
+        }
         bp.mesh_blueprints.push_back(b);
     }
     for (const Node& s : as_list(need(root, "sphere_blueprints", "scene"), "sphere_blueprints")) {
@@ -282,27 +287,77 @@ namespace {
 // polygon's indices simply continue the list, and that is reproduced).
 struct ObjModel {
     std::vector<uint32_t> indices;
+    std::vector<int64_t> normal_indices;  // per index: the corner's `vn` (0-based), or -1 when it names none (or a bad one)
 };
 
-bool parse_index(const char*& p, long n_vertices, uint32_t& out) {
+// 1-based, negative = relative to the end; -1 when out of range
+long obj_index(long v, long n) {
+    const long idx = v > 0 ? v - 1 : n + v;
+    return (v == 0 || idx < 0 || idx >= n) ? -1 : idx;
+}
+
+// One face corner: v, v/vt, v//vn or v/vt/vn. Only the position decides whether the face is read (what the loader has
+// always accepted, it still accepts); a missing or bad vn leaves normal_out = -1.
+bool parse_index(const char*& p, long n_vertices, long n_normals, uint32_t& out, int64_t& normal_out) {
     char* end = nullptr;
     long v = std::strtol(p, &end, 10);
     if (end == p) return false;
     p = end;
-    while (*p && *p != ' ' && *p != '\t') ++p;  // skip /vt/vn
-    long idx = v > 0 ? v - 1 : n_vertices + v;    // 1-based, negative = relative to the end
-    if (v == 0 || idx < 0 || idx >= n_vertices) return false;
+    normal_out = -1;
+    if (*p == '/') {
+        const char* q = p + 1;
+        while (*q && *q != '/' && *q != ' ' && *q != '\t' && *q != '\r') ++q;  // vt (unused)
+        if (*q == '/') {
+            ++q;
+            char* e2 = nullptr;
+            const long vn = std::strtol(q, &e2, 10);
+            if (e2 != q && (*e2 == '\0' || *e2 == ' ' || *e2 == '\t' || *e2 == '\r')) normal_out = obj_index(vn, n_normals);
+        }
+    }
+    while (*p && *p != ' ' && *p != '\t') ++p;  // the rest of the token
+    const long idx = obj_index(v, n_vertices);
+    if (idx < 0) return false;
     out = uint32_t(idx);
     return true;
+}
+
+// Area-weighted vertex normals of one model's transformed triangles: per position index, the unnormalised cross(e1, e2)
+// of every triangle corner that uses it, summed in float in face order (corners 0, 1, 2), then normalised. A corner whose
+// sum does not normalise to a finite vector (a zero sum) gets its face normal, and a corner of a degenerate triangle whose
+// face normal is not finite either gets (0, 0, 0), which the library answers with the stored face normal.
+void smooth_model_normals(const std::vector<uint32_t>& idx, const std::array<Vec3, 3>* tris, size_t n_faces,
+                          std::vector<Vec3>& acc, std::vector<std::array<Vec3, 3>>& out) {
+    for (size_t f = 0; f < n_faces; ++f) {
+        const Vec3 c = (tris[f][1] - tris[f][0]).cross_product(tris[f][2] - tris[f][0]);
+        for (int k = 0; k < 3; ++k) acc[idx[3 * f + k]] = acc[idx[3 * f + k]] + c;
+    }
+    auto finite = [](Vec3 v) { return std::isfinite(v.x) && std::isfinite(v.y) && std::isfinite(v.z); };
+    for (size_t f = 0; f < n_faces; ++f) {
+        std::array<Vec3, 3> cn;
+        const Vec3 face = get_triangle_normal(tris[f]);
+        for (int k = 0; k < 3; ++k) {
+            const Vec3 n = acc[idx[3 * f + k]].normalize();
+            cn[k] = finite(n) ? n : finite(face) ? face : Vec3();
+        }
+        out.push_back(cn);
+    }
+    for (size_t f = 0; f < n_faces; ++f)
+        for (int k = 0; k < 3; ++k) acc[idx[3 * f + k]] = Vec3();
 }
 
 }  // namespace
 
 std::vector<std::array<Vec3, 3>> load_mesh_vertices_from_file(const std::string& filepath, Vec3 translation,
                                                               Vec3 rotation, float scale) {
+    return load_mesh_from_file(filepath, translation, rotation, scale, false).triangles;
+}
+
+ObjMesh load_mesh_from_file(const std::string& filepath, Vec3 translation, Vec3 rotation, float scale, bool smooth) {
     std::ifstream f(filepath, std::ios::binary);
     if (!f) throw Error("assertion failed: loaded_mesh.is_ok() (cannot open " + filepath + ")");
     std::vector<float> positions;
+    std::vector<float> normals;        // vn x y z
+    std::vector<uint8_t> normal_ok;    // ... read as three finite numbers
     std::vector<ObjModel> models(1);
     std::string line;
     size_t line_no = 0;
@@ -320,15 +375,30 @@ std::vector<std::array<Vec3, 3>> load_mesh_vertices_from_file(const std::string&
                 p = end;
             }
             positions.insert(positions.end(), v, v + 3);
+        } else if (p[0] == 'v' && p[1] == 'n' && (p[2] == ' ' || p[2] == '\t')) {
+            p += 3;
+            float v[3];
+            bool ok = true;
+            for (int k = 0; k < 3; ++k) {
+                char* end = nullptr;
+                v[k] = std::strtof(p, &end);
+                ok = ok && end != p && std::isfinite(v[k]);
+                p = end;
+            }
+            normals.insert(normals.end(), v, v + 3);
+            normal_ok.push_back(ok ? 1 : 0);
         } else if (p[0] == 'f' && (p[1] == ' ' || p[1] == '\t')) {
             p += 2;
-            const long nv = long(positions.size() / 3);
+            const long nv = long(positions.size() / 3), nn = long(normal_ok.size());
             for (;;) {
                 while (*p == ' ' || *p == '\t' || *p == '\r') ++p;
                 if (!*p) break;
                 uint32_t idx;
-                if (!parse_index(p, nv, idx)) throw Error(filepath + ":" + std::to_string(line_no) + ": bad face index");
+                int64_t nidx;
+                if (!parse_index(p, nv, nn, idx, nidx)) throw Error(filepath + ":" + std::to_string(line_no) + ": bad face index");
+                if (nidx >= 0 && !normal_ok[size_t(nidx)]) nidx = -1;
                 models.back().indices.push_back(idx);
+                models.back().normal_indices.push_back(nidx);
             }
         } else if ((p[0] == 'o' || p[0] == 'g') && (p[1] == ' ' || p[1] == '\t' || p[1] == '\0' || p[1] == '\r')) {
             if (!models.back().indices.empty()) models.emplace_back();
@@ -337,8 +407,12 @@ std::vector<std::array<Vec3, 3>> load_mesh_vertices_from_file(const std::string&
         }
     }
     std::vector<std::array<Vec3, 3>> model_vertices;
+    std::vector<std::array<Vec3, 3>> corner_normals;
+    std::vector<Vec3> acc(smooth ? positions.size() / 3 : 0);
+    const float sign = scale > 0.0f ? 1.0f : scale < 0.0f ? -1.0f : 0.0f;  // the normal transform of a uniform scale
     for (const ObjModel& m : models) {
-        for (size_t fidx = 0; fidx < m.indices.size() / 3; ++fidx) {
+        const size_t first = model_vertices.size(), n_faces = m.indices.size() / 3;
+        for (size_t fidx = 0; fidx < n_faces; ++fidx) {
             std::array<Vec3, 3> tri;
             for (int k = 0; k < 3; ++k) {
                 const uint32_t i = m.indices[3 * fidx + k];
@@ -347,9 +421,24 @@ std::vector<std::array<Vec3, 3>> load_mesh_vertices_from_file(const std::string&
             }
             model_vertices.push_back(tri);
         }
+        if (!smooth || n_faces == 0) continue;
+        bool file_normals = true;
+        for (size_t k = 0; k < 3 * n_faces; ++k) file_normals = file_normals && m.normal_indices[k] >= 0;
+        if (file_normals) {
+            for (size_t fidx = 0; fidx < n_faces; ++fidx) {
+                std::array<Vec3, 3> cn;
+                for (int k = 0; k < 3; ++k) {
+                    const size_t i = size_t(m.normal_indices[3 * fidx + k]);
+                    cn[k] = (sign * Vec3(normals[3 * i], normals[3 * i + 1], normals[3 * i + 2])).rotate_point(rotation);
+                }
+                corner_normals.push_back(cn);
+            }
+        } else {
+            smooth_model_normals(m.indices, model_vertices.data() + first, n_faces, acc, corner_normals);
+        }
     }
     std::printf("Successfully loaded %zu triangles from file %s!\n", model_vertices.size(), filepath.c_str());
-    return model_vertices;
+    return ObjMesh{std::move(model_vertices), std::move(corner_normals)};
 }
 
 Vec3 get_triangle_normal(const std::array<Vec3, 3>& c) {
@@ -374,7 +463,10 @@ void compute_min_max_3d(const std::vector<std::array<Vec3, 3>>& tris, Vec3& lo, 
 
 // mesh.rs:41-74 + convert_to_soa_mesh (mesh.rs:123-181) including its padding rule: N % lanes copies
 // of triangle 0 are appended (not lanes - N % lanes); the kernel side then drops the incomplete chunk.
-TriangleMesh TriangleMesh::from_triangles(std::vector<std::array<Vec3, 3>> pre_vertices, Material material) {
+TriangleMesh TriangleMesh::from_triangles(std::vector<std::array<Vec3, 3>> pre_vertices, Material material,
+                                          const std::vector<std::array<Vec3, 3>>* pre_corner_normals) {
+    if (pre_corner_normals && pre_corner_normals->size() != pre_vertices.size())
+        throw Error("TriangleMesh::from_triangles: one set of corner normals per triangle");
     TriangleMesh m;
     m.material = material;
     m.num_triangles = uint32_t(pre_vertices.size());
@@ -416,6 +508,16 @@ TriangleMesh TriangleMesh::from_triangles(std::vector<std::array<Vec3, 3>> pre_v
         m.normals[1].push_back(nn.y);
         m.normals[2].push_back(nn.z);
     }
+    if (pre_corner_normals && n != 0) {
+        for (size_t i = 0; i < n + n_pad; ++i) {
+            const std::array<Vec3, 3>& cn = (*pre_corner_normals)[i < n ? i : 0];  // (padding: entry 0's)
+            for (int k = 0; k < 3; ++k) {
+                m.corner_normals[k][0].push_back(cn[k].x);
+                m.corner_normals[k][1].push_back(cn[k].y);
+                m.corner_normals[k][2].push_back(cn[k].z);
+            }
+        }
+    }
     return m;
 }
 
@@ -425,12 +527,12 @@ LoadTimes& load_times() {
 }
 
 TriangleMesh TriangleMesh::create(const std::string& filepath, Vec3 translation, Vec3 rotation, float scale,
-                                  Material material) {
+                                  Material material, bool smooth) {
     const auto now = [] { return std::chrono::steady_clock::now(); };
     const auto t0 = now();
-    auto tris = load_mesh_vertices_from_file(filepath, translation, rotation, scale);
+    ObjMesh obj = load_mesh_from_file(filepath, translation, rotation, scale, smooth);
     const auto t1 = now();
-    TriangleMesh m = from_triangles(std::move(tris), material);
+    TriangleMesh m = from_triangles(std::move(obj.triangles), material, smooth ? &obj.corner_normals : nullptr);
     load_times().obj_load_s += std::chrono::duration<double>(t1 - t0).count();
     load_times().soa_prep_s += std::chrono::duration<double>(now() - t1).count();
     return m;
@@ -451,6 +553,15 @@ rbrt_mesh_t TriangleMesh::to_abi() const {
     return a;
 }
 
+rbrt_mesh_normals_t TriangleMesh::to_abi_normals() const {
+    rbrt_mesh_normals_t a{};
+    if (!smooth()) return a;
+    a.n0x = corner_normals[0][0].data(), a.n0y = corner_normals[0][1].data(), a.n0z = corner_normals[0][2].data();
+    a.n1x = corner_normals[1][0].data(), a.n1y = corner_normals[1][1].data(), a.n1z = corner_normals[1][2].data();
+    a.n2x = corner_normals[2][0].data(), a.n2y = corner_normals[2][1].data(), a.n2z = corner_normals[2][2].data();
+    return a;
+}
+
 Scene::AbiView Scene::to_abi() const {
     AbiView v;
     for (const Sphere& s : elements) {
@@ -466,7 +577,13 @@ Scene::AbiView Scene::to_abi() const {
         a.mat = t.material.abi;
         v.triangles.push_back(a);
     }
-    for (const TriangleMesh& m : triangle_meshes) v.meshes.push_back(m.to_abi());
+    for (const TriangleMesh& m : triangle_meshes) {
+        v.meshes.push_back(m.to_abi());
+        v.normals.push_back(m.to_abi_normals());
+        v.any_smooth = v.any_smooth || m.smooth();
+    }
+    v.shading.n_meshes = uint32_t(v.meshes.size());
+    v.shading.meshes = v.normals.data();
     v.scene.n_spheres = uint32_t(v.spheres.size());
     v.scene.spheres = v.spheres.data();
     v.scene.n_triangles = uint32_t(v.triangles.size());
@@ -492,7 +609,7 @@ Scene create_scene_from_scene_blueprint(const SceneBlueprint& bp) {
             continue;
         }
         scene.triangle_meshes.push_back(
-            TriangleMesh::create(mb.obj_filepath, mb.translation, mb.rotation_rad, mb.scale, *mat));
+            TriangleMesh::create(mb.obj_filepath, mb.translation, mb.rotation_rad, mb.scale, *mat, mb.smooth));
     }
     for (const SphereBlueprint& sb : bp.sphere_blueprints) {
         auto mat = create_material_from_description(sb.material_type, sb.albedo, sb.material_param);

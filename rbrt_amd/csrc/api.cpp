@@ -821,14 +821,6 @@ static int lens_invalid(const rbrt_camera_t* cam, const rbrt_render_opts_t* o) {
     return RBRT_OK;
 }
 
-// The lens part of a tile-table key (the tables of a lens camera are not those of the pinhole camera it wraps).
-template <class Key>
-static void key_lens(Key& k, const TraceParams& P) {
-    k.thin_lens = P.thin_lens;
-    for (int c = 0; c < 3; ++c) k.lens_u[c] = P.lens_u[c], k.lens_v[c] = P.lens_v[c];
-    k.focus_scale = P.focus_scale;
-}
-
 int fill_trace_params(const rbrt_hip_scene* s, const rbrt_camera_t* cam, const rbrt_render_opts_t* o,
                       TraceParams& P) {
     std::memset(&P, 0, sizeof(P));
@@ -1475,63 +1467,61 @@ int rbrt_hip_scene_kernel_ms(rbrt_hip_scene_t* s, float* trace_ms, float* resolv
     return RBRT_OK;
 }
 
-// Samples [s_begin, s_end) of a render of o->spp samples per pixel. `acc` holds (and receives) the per-pixel running
-// sums in sample order -- lib.rs:95-100's `color +=` -- packed like the radiance output; it is read unless
-// s_begin == 0 and written unless s_end == o->spp, in which case the mean (lib.rs:101) and the quantisation go out.
-static int render_samples(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, const rbrt_render_opts_t* o, void* stream_v,
-                   uint32_t s_begin, uint32_t s_end, float* acc, float* d_radiance, uint8_t* d_rgb8) {
-    if (!s || !cam || !o) return fail(RBRT_ERR_INVALID_ARG, "render: null argument");
-    if (o->spp == 0) return fail(RBRT_ERR_INVALID_ARG, "spp must be >= 1");
-    if (s_begin >= s_end || s_end > o->spp) return fail(RBRT_ERR_INVALID_ARG, "sample range must satisfy begin < end <= spp");
-    if (o->max_depth > uint32_t(kMaxPathDepth))
-        return fail(RBRT_ERR_UNSUPPORTED, "max_depth above the kernel limit of 64");
-    if (cam->img_width_pix == 0 || cam->img_height_pix == 0)
-        return fail(RBRT_ERR_INVALID_ARG, "image has zero pixels");
-    if (uint64_t(cam->img_width_pix) * cam->img_height_pix >= (1ull << 32))
-        return fail(RBRT_ERR_UNSUPPORTED, "image has 2^32 or more pixels");
-    const uint32_t world = o->tile_world ? o->tile_world : 1;
-    if (o->tile_rank >= world) return fail(RBRT_ERR_INVALID_ARG, "tile_rank >= tile_world");
-    if (int rc = lens_invalid(cam, o)) return rc;
-    HIP_TRY(hipSetDevice(s->device));
-    std::lock_guard<std::mutex> watcher_lock(s->mu);  // (the watcher of elastic launches looks at the lanes between calls, not during one)
-    adopt_refined(s);  // (the background thread's trees, once they are on the device: this call's launches use them)
-    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+// ---- A render call, step by step (render_samples) --------------------------------------------------------------------
+namespace {
 
-    const uint32_t W = cam->img_width_pix, H = cam->img_height_pix;
-    const uint32_t tiles_x = (W + RBRT_TILE - 1) / RBRT_TILE, tiles_y = (H + RBRT_TILE - 1) / RBRT_TILE;
-    const uint32_t n_tiles = tiles_x * tiles_y;
-    const uint32_t n_local = local_tiles_of(n_tiles, o->tile_rank, world);
-    const size_t npix = size_t(n_local) * 64u;
-    if (npix == 0) return RBRT_OK;
+// What a render call of samples [s_begin, s_end) on the caller's stream does, decided before anything is issued (plan_call).
+struct CallPlan {
+    hipStream_t stream = nullptr;
+    uint32_t s_begin = 0, s_end = 0, world = 1, tiles_x = 0, tiles_y = 0, n_tiles = 0, n_local = 0, depth = 1;  // depth: lanes in turn
+    size_t npix = 0, per_sample = 0, batch = 0, need = 0, n_batches = 0;  // batch: samples per launch, need: their buffer
+    bool stats = false, busy_at_call = false, streams_now = false, tile_pass = false, timing = false;
+};
 
+// The call's tiles, its sample batches and the lanes they take turns on. False: the rank has no tiles, nothing to do.
+bool plan_call(const rbrt_hip_scene* s, const rbrt_camera_t* cam, const rbrt_render_opts_t* o, CallPlan& c) {
+    c.world = o->tile_world ? o->tile_world : 1;
+    c.tiles_x = (cam->img_width_pix + RBRT_TILE - 1) / RBRT_TILE, c.tiles_y = (cam->img_height_pix + RBRT_TILE - 1) / RBRT_TILE;
+    c.n_tiles = c.tiles_x * c.tiles_y, c.n_local = local_tiles_of(c.n_tiles, o->tile_rank, c.world);
+    c.npix = size_t(c.n_local) * 64u;
+    if (c.npix == 0) return false;
     // workspace: as many samples per batch as fit the cap (at least one)
-    const size_t per_sample = npix * 3u * sizeof(float);
-    size_t batch = workspace_cap_bytes() / per_sample;
-    if (batch * npix > 0xFFF00000ull) batch = 0xFFF00000ull / npix;  // work items are 32-bit in the kernel
-    if (batch < 1) batch = 1;
-    if (batch > s_end - s_begin) batch = s_end - s_begin;
-    const size_t need = batch * per_sample;
+    c.per_sample = c.npix * 3u * sizeof(float);
+    c.batch = workspace_cap_bytes() / c.per_sample;
+    if (c.batch * c.npix > 0xFFF00000ull) c.batch = 0xFFF00000ull / c.npix;  // work items are 32-bit in the kernel
+    if (c.batch < 1) c.batch = 1;
+    if (c.batch > c.s_end - c.s_begin) c.batch = c.s_end - c.s_begin;
+    c.need = c.batch * c.per_sample, c.n_batches = (size_t(c.s_end - c.s_begin) + c.batch - 1) / c.batch;
     // The pipeline is for STREAMS of launches. A call that finds the GPU idle and is not one of a stream -- the CLI's one
     // render, a blocking caller -- uses the lanes there are (four from scene_create: four more cost 20 ms to make, more than
     // thirteen batches of a 1920x1080x512 render gain from them), and only the lanes it launches on get their buffers: the first frame of a scene took 12.9 ms with three lanes' buffers to make
     // and 39.9 with eight lanes', against 5.0 with one (4.2 from the second frame on). The first call of a stream that is
     // issued into a busy GPU makes the rest, during the stream's first frames.
-    const bool stats_call = (o->flags & RBRT_FLAG_COLLECT_STATS) != 0;
-    const uint32_t depth_full = depth_for(s, need);
-    const bool busy_at_call = other_launch_in_flight(s, nullptr);  // (asked once: every answer is up to eight hipEventQuery calls)
-    const bool streams_now = !stats_call && depth_full > 1 && (s->streaming_hint || busy_at_call);
-    const uint32_t depth = streams_now ? depth_full : std::min<uint32_t>(depth_full, uint32_t(std::max<size_t>(s->lanes.size(), 1)));
-    if (int rc = ensure_lanes(s, depth)) return rc;
-    const auto sync_lanes = [&]() -> int {  // everything in flight on the caller's stream and on the lanes
-        HIP_TRY(hipStreamSynchronize(stream));
-        for (auto& L : s->lanes) HIP_TRY(hipStreamSynchronize(L.stream));  // (helper launches are carried by lane streams)
-        if (s->aux_stream) HIP_TRY(hipStreamSynchronize(s->aux_stream));
-        return RBRT_OK;
-    };
+    c.stats = (o->flags & RBRT_FLAG_COLLECT_STATS) != 0;  // (counting launches: alone on lane 0)
+    const uint32_t depth_full = depth_for(s, c.need);
+    c.busy_at_call = other_launch_in_flight(s, nullptr);  // (asked once: every answer is up to eight hipEventQuery calls)
+    c.streams_now = !c.stats && depth_full > 1 && (s->streaming_hint || c.busy_at_call);
+    c.depth = c.streams_now ? depth_full : std::min<uint32_t>(depth_full, uint32_t(std::max<size_t>(s->lanes.size(), 1)));
+    c.tile_pass = s->primary_cull != 0;
+    return true;
+}
+
+// Waits for everything in flight on the caller's stream and on the lanes.
+int sync_lanes(rbrt_hip_scene* s, hipStream_t stream) {
+    HIP_TRY(hipStreamSynchronize(stream));
+    for (auto& L : s->lanes) HIP_TRY(hipStreamSynchronize(L.stream));  // (helper launches are carried by lane streams)
+    if (s->aux_stream) HIP_TRY(hipStreamSynchronize(s->aux_stream));
+    return RBRT_OK;
+}
+
+// The call's running sums, statistics counters and timing events. `acc`: the caller's running sums (render_pass), or null.
+int prepare_call(rbrt_hip_scene* s, CallPlan& c, const float* acc) {
+    const hipStream_t stream = c.stream;
+    const size_t per_sample = c.per_sample;
     // (running sums between the batches of one call: a call of one batch has none)
-    if (!acc && batch < s_end - s_begin && per_sample > s->acc_bytes) {
+    if (!acc && c.batch < c.s_end - c.s_begin && per_sample > s->acc_bytes) {
         if (s->d_acc) {
-            if (int rc = sync_lanes()) return rc;
+            if (int rc = sync_lanes(s, stream)) return rc;
             HIP_TRY(hipFree(s->d_acc));
             s->d_acc = nullptr, s->acc_bytes = 0;
         }
@@ -1539,192 +1529,184 @@ static int render_samples(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, const r
         HIP_TRY(hipMalloc(&p, per_sample));
         s->d_acc = static_cast<float*>(p), s->acc_bytes = per_sample;
     }
-
-    const bool stats = (o->flags & RBRT_FLAG_COLLECT_STATS) != 0;
-    if (stats) {
+    if (c.stats) {
         HIP_TRY(hipMemsetAsync(s->d_counters, 0, sizeof(DevCounters), stream));
-        {   // the two atomicMin slots start at all-ones
-            const unsigned long long ones = ~0ull;
-            HIP_TRY(hipMemcpyAsync(&s->d_counters->diag[24], &ones, sizeof(ones), hipMemcpyHostToDevice, stream));
-            HIP_TRY(hipMemcpyAsync(&s->d_counters->diag[28], &ones, sizeof(ones), hipMemcpyHostToDevice, stream));
-        }
+        const unsigned long long ones = ~0ull;  // the two atomicMin slots start at all-ones
+        HIP_TRY(hipMemcpyAsync(&s->d_counters->diag[24], &ones, sizeof(ones), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(&s->d_counters->diag[28], &ones, sizeof(ones), hipMemcpyHostToDevice, stream));
         s->stats_pending = true;
     }
+    s->last_batch = uint32_t(c.batch), s->last_n_batches = uint32_t(c.n_batches);
+    if (s->timing && s->events_used + 3 * c.n_batches > kMaxTimedLaunches * 3) s->timing_overflow = true;
+    c.timing = s->timing && !s->timing_overflow;
+    while (c.timing && s->events.size() < s->events_used + 3 * c.n_batches) {
+        hipEvent_t e;
+        HIP_TRY(hipEventCreate(&e));
+        s->events.push_back(e);
+    }
+    return RBRT_OK;
+}
 
+// The trace parameters every launch and tile pass of the call starts from: scene, camera and options (fill_trace_params),
+// the tile partition and the scene's scheduling knobs. Each launch adds its batch, lane and tile tables (issue_batches).
+TraceParams call_params(const rbrt_hip_scene* s, const rbrt_camera_t* cam, const rbrt_render_opts_t* o, const CallPlan& c) {
     TraceParams P;
     fill_trace_params(s, cam, o, P);
-    P.tiles_x = tiles_x, P.tiles_y = tiles_y, P.n_tiles = n_tiles;
-    P.tiles_x_magic = div_magic_of(tiles_x);
-    P.tiles_reversed = empty_end_is_first(s, *cam, tiles_x, o->tile_rank, world, n_local) ? 1u : 0u;
-    const uint32_t rowmajor_reversed = P.tiles_reversed;  // (a launch whose list is in hand-out order resets it; the next batch may not)
-    P.tile_rank = o->tile_rank, P.tile_world = world, P.n_local_tiles = n_local;
-    P.stack_entries = s->stack_entries;
-    P.y_low_water = s->y_low_water;
+    P.tiles_x = c.tiles_x, P.tiles_y = c.tiles_y, P.n_tiles = c.n_tiles, P.tiles_x_magic = div_magic_of(c.tiles_x);
+    P.tiles_reversed = empty_end_is_first(s, *cam, c.tiles_x, o->tile_rank, c.world, c.n_local) ? 1u : 0u;
+    P.tile_rank = o->tile_rank, P.tile_world = c.world, P.n_local_tiles = c.n_local, P.tile_tail_div = s->tile_tail_div;
+    P.stack_entries = s->stack_entries, P.share_idle = s->share_idle;
+    P.y_low_water = s->y_low_water, P.y_high_min_parked = s->y_high_min_parked;
     P.y_high_water = s->y_high_water < s->y_low_water ? s->y_low_water : s->y_high_water;
-    P.y_high_min_parked = s->y_high_min_parked;
-    P.leaf_round = s->leaf_round;
-    P.leaf_leaves = s->leaf_leaves;
-    P.share_idle = s->share_idle;
+    P.leaf_round = s->leaf_round, P.leaf_leaves = s->leaf_leaves;
     P.work_stripes = s->work_stripes;  // (per launch: set where the launch's size is known)
-    P.shade_rounds = s->shade_rounds;
-    P.shade_cont_min = s->shade_cont_min;
-    P.tile_tail_div = s->tile_tail_div;
+    P.shade_rounds = s->shade_rounds, P.shade_cont_min = s->shade_cont_min;
+    return P;
+}
 
-    ResolveParams R;
-    std::memset(&R, 0, sizeof(R));
-    R.width = W, R.height = H, R.tiles_x = tiles_x, R.n_tiles = n_tiles;
-    R.tile_rank = o->tile_rank, R.tile_world = world, R.n_local_tiles = n_local;
-    R.inv_spp = 1.0f / float(o->spp);  // lib.rs:101
-    R.acc = acc ? acc : s->d_acc;
-    R.out_radiance = d_radiance;
-    R.out_rgb8 = d_rgb8;
-
-    const size_t n_batches = (size_t(s_end - s_begin) + batch - 1) / batch;
-    s->last_batch = uint32_t(batch), s->last_n_batches = uint32_t(n_batches);
-    if (s->timing && s->events_used + 3 * n_batches > kMaxTimedLaunches * 3) s->timing_overflow = true;
-    const bool timing = s->timing && !s->timing_overflow;
-    if (timing) {
-        while (s->events.size() < s->events_used + 3 * n_batches) {
-            hipEvent_t e;
-            HIP_TRY(hipEventCreate(&e));
-            s->events.push_back(e);
-        }
+// The lane's per-wave scratch, sample buffer and tile tables, grown to what the call needs.
+int size_lane(rbrt_hip_scene* s, const CallPlan& c, uint32_t li) {
+    rbrt_hip_scene::Lane& L = s->lanes[li];
+    const size_t need = c.need, n_tiles = c.n_tiles, lists_need = size_t(kTileListHeader) + 2u * size_t(c.n_local);
+    if (!L.d_gseq) {  // the lane's per-wave scratch: scatter records beyond the four in LDS (written before they are read: no
+                      // initial value), the overflow of the LDS stacks
+        void* p = nullptr;
+        const size_t gseq_bytes = (megakernel_gseq_bytes(s->scratch_waves) + kSlabAlign - 1) & ~(kSlabAlign - 1);
+        HIP_TRY(dev_alloc(s, gseq_bytes + megakernel_gstack_bytes(s->scratch_waves), &p));
+        L.d_gseq = static_cast<uint32_t*>(p);
+        L.d_gstack = reinterpret_cast<uint32_t*>(static_cast<char*>(p) + gseq_bytes);
     }
-    // For a stream every lane's buffers are sized here, at the first call that needs them, not when a lane first comes up in
-    // the rotation (a hipMalloc in the middle of a stream of frames); otherwise a lane's are sized when a batch goes to it.
-    const bool tile_pass = s->primary_cull != 0;
-    const size_t lists_need = size_t(kTileListHeader) + 2u * size_t(n_local);
-    const auto size_lane = [&](uint32_t li) -> int {
+    for (auto& B : L.bufs) {
+        if (need <= B.sample_buf_bytes) continue;
+        if (B.d_sample_buf) {
+            if (int rc = sync_lanes(s, c.stream)) return rc;
+            HIP_TRY(hipFree(B.d_sample_buf));
+            B.d_sample_buf = nullptr, B.sample_buf_bytes = 0;
+        }
+        void* p = nullptr;
+        HIP_TRY(hipMalloc(&p, need));
+        B.d_sample_buf = static_cast<float*>(p), B.sample_buf_bytes = need;
+    }
+    if (c.tile_pass && (n_tiles > L.tile_cull_words || lists_need > L.tile_lists_words)) {
+        if (L.tiles[0].d_cull || L.tiles[0].d_lists) {
+            if (int rc = sync_lanes(s, c.stream)) return rc;
+            if (s->prep_stream) HIP_TRY(hipStreamSynchronize(s->prep_stream));
+        }
+        for (auto& T : L.tiles) {
+            // (a set that has grown leaves its old arrays in the slab: a few hundred KB per frame size, until destroy)
+            T.d_cull = T.d_lists = nullptr;
+            T.key_valid = false, T.free_recorded = false;
+            void* p = nullptr;
+            HIP_TRY(dev_alloc(s, size_t(n_tiles) * sizeof(uint32_t), &p));
+            T.d_cull = static_cast<uint32_t*>(p);
+            HIP_TRY(dev_alloc(s, lists_need * sizeof(uint32_t), &p));
+            T.d_lists = static_cast<uint32_t*>(p);
+            if (!T.ev_lists) HIP_TRY(hipEventCreateWithFlags(&T.ev_lists, hipEventDisableTiming));
+            if (!T.ev_free) HIP_TRY(hipEventCreateWithFlags(&T.ev_free, hipEventDisableTiming));
+        }
+        L.tile_cull_words = n_tiles, L.tile_lists_words = lists_need;
+    }
+    return RBRT_OK;
+}
+
+int ensure_prep_stream(rbrt_hip_scene* s) {
+    if (s->prep_stream) return RBRT_OK;
+    int prio_low = 0, prio_high = 0;
+    (void)hipDeviceGetStreamPriorityRange(&prio_low, &prio_high);  // (numerically: low >= high)
+    HIP_TRY(hipStreamCreateWithPriority(&s->prep_stream, hipStreamNonBlocking, prio_high));
+    return RBRT_OK;
+}
+
+// What a set of tile tables is made for: P's camera, lens (the tables of a lens camera are not those of the pinhole camera
+// it wraps), partition and min_dist, and the order of its work list. Keys are compared with memcmp: hence the memset.
+rbrt_hip_scene::Lane::TileKey tile_key(const TraceParams& P, uint32_t list_mode) {
+    rbrt_hip_scene::Lane::TileKey k;
+    std::memset(&k, 0, sizeof(k));
+    k.cam = P.cam, k.rank = P.tile_rank, k.world = P.tile_world, k.list_mode = list_mode, k.min_dist = P.min_dist;
+    k.thin_lens = P.thin_lens, k.focus_scale = P.focus_scale;
+    for (int c = 0; c < 3; ++c) k.lens_u[c] = P.lens_u[c], k.lens_v[c] = P.lens_v[c];
+    return k;
+}
+
+// The lane's set of tile tables made for `k` (the second one if both were), or null.
+rbrt_hip_scene::Lane::TileSet* find_tile_set(rbrt_hip_scene::Lane& L, const rbrt_hip_scene::Lane::TileKey& k) {
+    rbrt_hip_scene::Lane::TileSet* S = nullptr;
+    for (auto& C : L.tiles)
+        if (C.key_valid && std::memcmp(&k, &C.key, sizeof(k)) == 0) S = &C;
+    return S;
+}
+
+// The tile pass into set S on stream `cs`, behind the set's last readers and behind the pass that wrote it last (whatever
+// stream that ran on): base's camera and partition, the work list of `list_mode` in base's tile direction (mode 4 builds
+// its list in the direction row-major order is handed out in). `wide`: the list kernel as four waves instead of one.
+int fill_tile_set(rbrt_hip_scene::Lane::TileSet* S, const TraceParams& base, uint32_t list_mode, bool wide, hipStream_t cs) {
+    if (S->free_recorded) HIP_TRY(hipStreamWaitEvent(cs, S->ev_free, 0));
+    if (S->key_valid) HIP_TRY(hipStreamWaitEvent(cs, S->ev_lists, 0));
+    TraceParams P = base;
+    P.tile_cull = S->d_cull, P.tile_lists = S->d_lists, P.tile_list_mode = list_mode, P.tile_lists_wide = wide ? 1u : 0u;
+    HIP_TRY(launch_primary_cull(P, cs));
+    HIP_TRY(hipEventRecord(S->ev_lists, cs));
+    S->key = tile_key(P, list_mode), S->key_valid = true;
+    return RBRT_OK;
+}
+
+// The tile pass of a lane that has never had one runs now, for this camera, on the caller's stream (the lanes' buffers
+// were made just before; in the middle of a stream of frames a first pass would have to find room beside resident waves).
+// (Neither set of such a lane holds a key, so neither has been read: fill_tile_set issues no wait.)
+int warm_tile_tables(rbrt_hip_scene* s, const CallPlan& c, const TraceParams& P) {
+    // (mode: what the launches of a stream use; an isolated launch makes its own list)
+    const uint32_t mode = list_mode_for(true), iso_mode = list_mode_for(false);
+    for (uint32_t li = 0; li < c.depth; ++li) {
         rbrt_hip_scene::Lane& L = s->lanes[li];
-        if (!L.d_gseq) {  // the lane's per-wave scratch: scatter records beyond the four in LDS (written before they are read: no
-                          // initial value), the overflow of the LDS stacks
-            void* p = nullptr;
-            const size_t gseq_bytes = (megakernel_gseq_bytes(s->scratch_waves) + kSlabAlign - 1) & ~(kSlabAlign - 1);
-            HIP_TRY(dev_alloc(s, gseq_bytes + megakernel_gstack_bytes(s->scratch_waves), &p));
-            L.d_gseq = static_cast<uint32_t*>(p);
-            L.d_gstack = reinterpret_cast<uint32_t*>(static_cast<char*>(p) + gseq_bytes);
-        }
-        for (auto& B : L.bufs) {
-            if (need <= B.sample_buf_bytes) continue;
-            if (B.d_sample_buf) {
-                if (int rc = sync_lanes()) return rc;
-                HIP_TRY(hipFree(B.d_sample_buf));
-                B.d_sample_buf = nullptr, B.sample_buf_bytes = 0;
-            }
-            void* p = nullptr;
-            HIP_TRY(hipMalloc(&p, need));
-            B.d_sample_buf = static_cast<float*>(p), B.sample_buf_bytes = need;
-        }
-        if (tile_pass && (n_tiles > L.tile_cull_words || lists_need > L.tile_lists_words)) {
-            if (L.tiles[0].d_cull || L.tiles[0].d_lists) {
-                if (int rc = sync_lanes()) return rc;
-                if (s->prep_stream) HIP_TRY(hipStreamSynchronize(s->prep_stream));
-            }
-            for (auto& T : L.tiles) {
-                // (a set that has grown leaves its old arrays in the slab: a few hundred KB per frame size, until destroy)
-                T.d_cull = T.d_lists = nullptr;
-                T.key_valid = false, T.free_recorded = false;
-                void* p = nullptr;
-                HIP_TRY(dev_alloc(s, size_t(n_tiles) * sizeof(uint32_t), &p));
-                T.d_cull = static_cast<uint32_t*>(p);
-                HIP_TRY(dev_alloc(s, lists_need * sizeof(uint32_t), &p));
-                T.d_lists = static_cast<uint32_t*>(p);
-                if (!T.ev_lists) HIP_TRY(hipEventCreateWithFlags(&T.ev_lists, hipEventDisableTiming));
-                if (!T.ev_free) HIP_TRY(hipEventCreateWithFlags(&T.ev_free, hipEventDisableTiming));
-            }
-            L.tile_cull_words = n_tiles, L.tile_lists_words = lists_need;
-        }
-        return RBRT_OK;
-    };
-    if (streams_now)
-        for (uint32_t li = 0; li < depth; ++li)
-            if (int rc = size_lane(li)) return rc;
-    const auto ensure_prep_stream = [&]() -> int {
-        if (s->prep_stream) return RBRT_OK;
-        int prio_low = 0, prio_high = 0;
-        (void)hipDeviceGetStreamPriorityRange(&prio_low, &prio_high);  // (numerically: low >= high)
-        HIP_TRY(hipStreamCreateWithPriority(&s->prep_stream, hipStreamNonBlocking, prio_high));
-        return RBRT_OK;
-    };
-    // (a one-shot scene's launch has the GPU to itself and runs its tile pass on its own stream: it makes the prep stream
-    // only if a second batch ever overlaps the first -- creating and destroying one costs the call 0.3 ms)
-    if (tile_pass && !s->one_shot)
-        if (int rc = ensure_prep_stream()) return rc;
-    // The tile pass of a lane that has never had one runs now, for this camera, on the caller's stream (the lanes' buffers
-    // were made just above; in the middle of a stream of frames a first pass would have to find room beside resident waves).
-    if (tile_pass && streams_now) {
-        TraceParams T;
-        fill_trace_params(s, cam, o, T);
-        T.tiles_x = tiles_x, T.tiles_y = tiles_y, T.n_tiles = n_tiles;
-        T.tile_rank = o->tile_rank, T.tile_world = world, T.n_local_tiles = n_local;
-        T.tile_list_mode = list_mode_for(true);  // (what the launches of a stream use; an isolated launch makes its own list)
-        T.tile_tail_div = s->tile_tail_div;
-        T.tiles_reversed = P.tiles_reversed;
+        if (L.tiles[0].key_valid || L.tiles[1].key_valid) continue;
         // (the one-wave form of the list kernel: `streams_now` means a launch of this scene is in flight or about to be, and a
         // 256-thread workgroup waits for four free wave slots on one CU beside resident trace waves -- up to 10 ms for 21 us
         // of work, profiles/r04_default_kernel_stats.csv -- with the resolve chain of the caller's stream queued behind it)
-        T.tile_lists_wide = 0u;
-        for (uint32_t li = 0; li < depth; ++li) {
-            rbrt_hip_scene::Lane& L = s->lanes[li];
-            if (L.tiles[0].key_valid || L.tiles[1].key_valid) continue;
-            rbrt_hip_scene::Lane::TileSet& S = L.tiles[0];
-            T.tile_cull = S.d_cull, T.tile_lists = S.d_lists;
-            HIP_TRY(launch_primary_cull(T, stream));
-            HIP_TRY(hipEventRecord(S.ev_lists, stream));
-            std::memset(&S.key, 0, sizeof(S.key));
-            S.key.cam = *cam, S.key.rank = o->tile_rank, S.key.world = world, S.key.list_mode = T.tile_list_mode, S.key.min_dist = o->min_dist;
-            key_lens(S.key, T);
-            S.key_valid = true;
-            // (the lane this call's first launch takes: if that launch finds the GPU idle it wants the isolated launch's list
-            // as well -- made here too, it does not have to wait for the prep stream while the launches behind it pile up)
-            const uint32_t iso_mode = list_mode_for(false);
-            if (li == s->next_lane % depth && iso_mode != T.tile_list_mode) {
-                rbrt_hip_scene::Lane::TileSet& S1 = L.tiles[1];
-                TraceParams T1 = T;
-                T1.tile_list_mode = iso_mode;
-                T1.tile_cull = S1.d_cull, T1.tile_lists = S1.d_lists;
-                HIP_TRY(launch_primary_cull(T1, stream));
-                HIP_TRY(hipEventRecord(S1.ev_lists, stream));
-                S1.key = S.key, S1.key.list_mode = iso_mode;
-                S1.key_valid = true;
-            }
-        }
+        if (int rc = fill_tile_set(&L.tiles[0], P, mode, false, c.stream)) return rc;
+        // (the lane this call's first launch takes: if that launch finds the GPU idle it wants the isolated launch's list
+        // as well -- made here too, it does not have to wait for the prep stream while the launches behind it pile up)
+        if (li == s->next_lane % c.depth && iso_mode != mode)
+            if (int rc = fill_tile_set(&L.tiles[1], P, iso_mode, false, c.stream)) return rc;
     }
+    return RBRT_OK;
+}
+
+// One trace launch per sample batch, each on a lane with the tile tables of its camera, and behind each on the caller's
+// stream its resolve and the pixels of the background-only tiles. P_call: call_params; R: the call's resolve parameters.
+int issue_batches(rbrt_hip_scene* s, const CallPlan& c, const rbrt_render_opts_t* o, const TraceParams& P_call, ResolveParams R) {
+    const hipStream_t stream = c.stream;
+    const bool stats = c.stats, piped = c.depth > 1 && !stats;
     const size_t ev0 = s->events_used;
     bool call_streams = false;  // this call was made while an earlier one's launch was still running (decided at its first batch)
     uint32_t prev_lane = ~0u;
-    for (size_t b = 0; b < n_batches; ++b) {
-        const uint32_t base = s_begin + uint32_t(b * batch);
-        const uint32_t nb = uint32_t(std::min<size_t>(batch, s_end - base));
+    for (size_t b = 0; b < c.n_batches; ++b) {
+        const uint32_t base = c.s_begin + uint32_t(b * c.batch);
+        const uint32_t nb = uint32_t(std::min<size_t>(c.batch, c.s_end - base));
+        TraceParams P = P_call;
         // counting launches run alone on lane 0: their counters are reset and read on the caller's stream
         // (the lanes take turns; but a launch that finds nothing of this scene in flight and is not one of a stream -- a
         // blocking caller's -- goes to a lane that already has the tile tables of its camera, if there is one: with eight
         // lanes taking turns a caller who renders one view again and again would otherwise pay the tile pass eight times)
-        uint32_t lane_no = stats ? 0u : s->next_lane % depth;
+        uint32_t lane_no = stats ? 0u : s->next_lane % c.depth;
         // (a call's later batches find its earlier ones in flight)
-        if (!stats && depth > 1 && s->primary_cull != 0 && !s->streaming_hint && b == 0 && !busy_at_call) {
-            rbrt_hip_scene::Lane::TileKey want;
-            std::memset(&want, 0, sizeof(want));
-            want.cam = *cam, want.rank = o->tile_rank, want.world = world, want.list_mode = list_mode_for(false), want.min_dist = o->min_dist;
-            key_lens(want, P);
-            for (uint32_t li = 0; li < depth; ++li)
-                for (const auto& C : s->lanes[li].tiles)
-                    if (C.key_valid && std::memcmp(&want, &C.key, sizeof(want)) == 0) lane_no = li;
+        if (!stats && c.depth > 1 && c.tile_pass && !s->streaming_hint && b == 0 && !c.busy_at_call) {
+            const auto want = tile_key(P, list_mode_for(false));
+            for (uint32_t li = 0; li < c.depth; ++li)
+                if (find_tile_set(s->lanes[li], want)) lane_no = li;
         } else if (!stats) {
             ++s->next_lane;
-            if (b != 0 && depth > 1 && lane_no == prev_lane) lane_no = s->next_lane++ % depth;  // (beside the batch before, not behind it)
+            if (b != 0 && c.depth > 1 && lane_no == prev_lane) lane_no = s->next_lane++ % c.depth;  // (beside the batch before, not behind it)
         }
         prev_lane = lane_no;
-        if (int rc = size_lane(lane_no)) return rc;  // (nothing to do for a lane of a stream)
+        if (int rc = size_lane(s, c, lane_no)) return rc;  // (nothing to do for a lane of a stream)
         rbrt_hip_scene::Lane& L = s->lanes[lane_no];
-        const bool piped = depth > 1 && !stats;
         hipStream_t ts = piped ? L.stream : stream;  // the trace launch's stream
         rbrt_hip_scene::Lane::Buf& B = L.bufs[0];
         if (piped) {
             // the lane's sample buffer and counters are free once the resolve of its previous launch has run
             if (B.in_use) HIP_TRY(hipStreamWaitEvent(L.stream, B.ev_resolved, 0));
-        } else if (depth > 1) {
-            if (int rc = sync_lanes()) return rc;  // a counting launch: nothing else in flight
+        } else if (c.depth > 1) {
+            if (int rc = sync_lanes(s, stream)) return rc;  // a counting launch: nothing else in flight
         }
         L.open.valid = false;  // (the launch the watcher knew on this lane is being followed by another: no stream has ended)
         if (L.helper_pending) {
@@ -1741,10 +1723,7 @@ static int render_samples(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, const r
             HIP_TRY(hipMemcpyAsync(B.d_work_counter, s->h_zeros, counter_bytes, hipMemcpyHostToDevice, ts));
             L.helper_pending = false;
         }
-        P.sample_base = base;
-        P.batch = nb;
-        P.batch_magic = div_magic_of(nb);
-        P.n_items = uint64_t(npix) * nb;
+        P.sample_base = base, P.batch = nb, P.batch_magic = div_magic_of(nb), P.n_items = uint64_t(c.npix) * nb;
         // (a caller that streams launches keeps doing so: the first launch after a pause -- the GPU is idle, but the
         // launch before it was issued into a busy one -- is still issued as one of a stream)
         const bool busy = piped && other_launch_in_flight(s, &L);
@@ -1754,49 +1733,28 @@ static int render_samples(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, const r
         // behind it -- a blocking 1920x1080x512 eighth, two batches: 14.7 ms; both on the full grid 14.8; the FIRST on the
         // full grid and the second on 12 of 16 slots 15.8; the second on the stream's 3: 38.6)
         if (b == 0) call_streams = busy || (piped && s->streaming_hint);
-        const uint32_t to_come = uint32_t(n_batches - 1 - b);
+        const uint32_t to_come = uint32_t(c.n_batches - 1 - b);
         const bool overlapped = call_streams || (piped && to_come != 0u);
-        // (a blocking call's batch shares the GPU with the batches behind it: the last one ends alone and takes the full
-        // grid, the one before it shares with one, ...; a stream's launch takes the steady state's share: grid_for)
-        const uint32_t company = to_come;
         if (b == 0) s->streaming_hint = busy;
         P.work_stripes = !overlapped ? s->work_stripes
                          : s->work_stripes_overlap != kStripesAuto ? s->work_stripes_overlap
                          : 0u;  // (contiguous shards; with half grids three deep small launches preferred stripes of 4, round 3)
-        P.sample_buf = B.d_sample_buf;
-        P.work_counter = B.d_work_counter;
-        P.gseq = L.d_gseq;
-        P.gstack = L.d_gstack;
+        P.sample_buf = B.d_sample_buf, P.work_counter = B.d_work_counter, P.gseq = L.d_gseq, P.gstack = L.d_gstack;
         P.helper_words = L.d_helper_words, P.helper_seq = ++L.seq, P.wave_base = 0u;
         // which of the lane's two sets of tile tables this launch reads: the one made for this camera and partition, else
         // the one used longer ago, filled now
         rbrt_hip_scene::Lane::TileSet* S = nullptr;
-        if (tile_pass) {
-            rbrt_hip_scene::Lane::TileKey key;
-            std::memset(&key, 0, sizeof(key));
+        if (c.tile_pass) {
             const uint32_t list_mode = list_mode_for(overlapped && !stats);
-            key.cam = *cam, key.rank = o->tile_rank, key.world = world, key.list_mode = list_mode, key.min_dist = o->min_dist;
-            key_lens(key, P);
-            for (auto& C : L.tiles)
-                if (C.key_valid && std::memcmp(&key, &C.key, sizeof(key)) == 0) S = &C;
+            S = find_tile_set(L, tile_key(P, list_mode));
             if (!S) {
                 S = L.tiles[0].last_used <= L.tiles[1].last_used ? &L.tiles[0] : &L.tiles[1];
-                // behind the set's last readers and behind the pass that wrote it last (whatever stream that ran on), on the
-                // prep stream: beside the launches in flight, ahead of this one
+                // on the prep stream: beside the launches in flight, ahead of this one
                 // (a launch that has the GPU to itself has nothing to run beside: its pass goes on its own stream, one
                 // cross-stream hop less in front of a blocking frame)
                 if (overlapped)
-                    if (int rc = ensure_prep_stream()) return rc;
-                hipStream_t cs = overlapped ? s->prep_stream : ts;
-                if (S->free_recorded) HIP_TRY(hipStreamWaitEvent(cs, S->ev_free, 0));
-                if (S->key_valid) HIP_TRY(hipStreamWaitEvent(cs, S->ev_lists, 0));
-                P.tile_cull = S->d_cull, P.tile_lists = S->d_lists;
-                P.tile_list_mode = list_mode;
-                P.tiles_reversed = rowmajor_reversed;  // (mode 4 builds its list in the direction row-major order is handed out in)
-                P.tile_lists_wide = overlapped ? 0u : 1u;
-                HIP_TRY(launch_primary_cull(P, cs));
-                HIP_TRY(hipEventRecord(S->ev_lists, cs));
-                S->key = key, S->key_valid = true;
+                    if (int rc = ensure_prep_stream(s)) return rc;
+                if (int rc = fill_tile_set(S, P, list_mode, !overlapped, overlapped ? s->prep_stream : ts)) return rc;
                 if (s->trace_launches) std::fprintf(stderr, "[rbrt_hip] tile pass on the prep stream: lane %u set %d list_mode %u\n",
                                                     unsigned(&L - s->lanes.data()), int(S - L.tiles), list_mode);
             }
@@ -1804,41 +1762,33 @@ static int render_samples(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, const r
             if (s->trace_launches)
                 std::fprintf(stderr, "[rbrt_hip] t %.3f ms launch %llu lane %u %s grid list_mode %u set %d\n", now_s() * 1e3, (unsigned long long)s->launch_no,
                              unsigned(&L - s->lanes.data()), overlapped ? "half" : "full", S->key.list_mode, int(S - L.tiles));
+            P.tile_cull = S->d_cull, P.tile_lists = S->d_lists, P.tile_list_mode = S->key.list_mode;
+            if (S->key.list_mode != 0u) P.tiles_reversed = 0u;  // (the list is in hand-out order already)
         }
-        P.tile_cull = S ? S->d_cull : nullptr;
-        P.tile_lists = S ? S->d_lists : nullptr;
-        P.tile_list_mode = S ? S->key.list_mode : 0u;
-        if (S && S->key.list_mode != 0u) P.tiles_reversed = 0u;  // (the list is in hand-out order already)
-        else if (S) P.tiles_reversed = rowmajor_reversed;
         // (B.d_work_counter is zero: from its allocation, afterwards from the resolve kernel of the launch that used the set last)
         // RBRT_POISON_SAMPLES=1 (tests): a (pixel, sample) the kernel fails to write shows up as NaN in the image
         if (s->poison_samples) HIP_TRY(hipMemsetAsync(B.d_sample_buf, 0xFF, B.sample_buf_bytes, ts));
-        if (timing) HIP_TRY(hipEventRecord(s->events[ev0 + 3 * b], ts));  // after the memset nodes
+        if (c.timing) HIP_TRY(hipEventRecord(s->events[ev0 + 3 * b], ts));  // after the memset nodes
         if (S) HIP_TRY(hipStreamWaitEvent(ts, S->ev_lists, 0));  // (the set's tables: made on the prep stream, or at the first call on the caller's)
-        const uint32_t grid = stats ? s->n_waves : grid_for(s, overlapped, depth, call_streams, company, P.n_items);
+        // (a blocking call's batch shares the GPU with the batches behind it, `to_come`: the last one ends alone and takes the
+        // full grid, the one before it shares with one, ...; a stream's launch takes the steady state's share: grid_for)
+        const uint32_t grid = stats ? s->n_waves : grid_for(s, overlapped, c.depth, call_streams, to_come, P.n_items);
         (grid < s->n_waves ? s->n_half_grid : s->n_full_grid) += 1;
         if (s->trace_launches)
             std::fprintf(stderr, "[rbrt_hip] trace launch: grid %u waves on %u CUs (%u waves per CU)\n", grid, s->n_cus, s->n_waves / s->n_cus);
         if (piped) HIP_TRY(hipEventRecord(L.ev_ready, ts));  // (behind everything the launch waits for: a helper launch waits for this)
         HIP_TRY(launch_trace_megakernel(P, grid, stats, ts));
         if (piped && s->helpers_mode != 0u) {
-            L.open.valid = true, L.open.P = P, L.open.grid = grid, L.open.helper_waves = 0u, L.open.rounds = 0u;
-            L.open.seq = ++s->open_seq;
+            L.open.valid = true, L.open.P = P, L.open.grid = grid, L.open.helper_waves = 0u, L.open.rounds = 0u, L.open.seq = ++s->open_seq;
             if (s->helpers_mode == 2u) {  // (tests: a helper with every overlapped launch, on a stream of its own)
                 if (!s->aux_stream) HIP_TRY(hipStreamCreateWithFlags(&s->aux_stream, hipStreamNonBlocking));
                 if (int rc = issue_helper(s, L, s->n_cus, s->aux_stream)) return rc;
             }
         }
-        if (timing) HIP_TRY(hipEventRecord(s->events[ev0 + 3 * b + 1], ts));
-        R.sample_buf = B.d_sample_buf;
-        R.work_counter = B.d_work_counter;
-        R.batch = nb;
-        R.first_batch = base == 0;
-        R.last_batch = base + nb == o->spp;
-        R.tile_lists = P.tile_lists;
-        R.counters = stats ? s->d_counters : nullptr;
+        if (c.timing) HIP_TRY(hipEventRecord(s->events[ev0 + 3 * b + 1], ts));
+        R.sample_buf = B.d_sample_buf, R.work_counter = B.d_work_counter, R.tile_lists = P.tile_lists;
+        R.batch = nb, R.first_batch = base == 0, R.last_batch = base + nb == o->spp;
         R.helper_words = P.helper_words, R.helper_seq = P.helper_seq;
-        R.error_flag = &s->d_counters->diag[57];
         if (piped) {
             HIP_TRY(hipEventRecord(L.ev_traced, ts));
             L.in_use = true;
@@ -1849,24 +1799,73 @@ static int render_samples(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, const r
         // like every write to its buffers. BEHIND the resolve although it needs only the lists: issued beside its own
         // trace launch it waited for wave slots that persistent trace waves hold until their launch ends (1.2 ms on
         // average for 0.05 ms of work, with the resolve queued behind it); now it runs in the slots that launch just freed.
-        if (tile_pass) HIP_TRY(launch_sky_resolve(P, R, stream));
+        if (c.tile_pass) HIP_TRY(launch_sky_resolve(P, R, stream));
         if (S) {  // the set's last readers have been issued: a later pass into it waits for them
             HIP_TRY(hipEventRecord(S->ev_free, stream));
             S->free_recorded = true;
         }
-        if (depth > 1) {  // (also after a counting launch: it used lane 0's buffers on the caller's stream)
+        if (c.depth > 1) {  // (also after a counting launch: it used lane 0's buffers on the caller's stream)
             HIP_TRY(hipEventRecord(B.ev_resolved, stream));
             B.in_use = true;
         }
-        if (timing) {
+        if (c.timing) {
             HIP_TRY(hipEventRecord(s->events[ev0 + 3 * b + 2], stream));
             s->events_used = ev0 + 3 * (b + 1);
         }
     }
+    return RBRT_OK;
+}
+
+}  // namespace
+
+// Samples [s_begin, s_end) of a render of o->spp samples per pixel. `acc` holds (and receives) the per-pixel running
+// sums in sample order -- lib.rs:95-100's `color +=` -- packed like the radiance output; it is read unless
+// s_begin == 0 and written unless s_end == o->spp, in which case the mean (lib.rs:101) and the quantisation go out.
+static int render_samples(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, const rbrt_render_opts_t* o, void* stream_v,
+                   uint32_t s_begin, uint32_t s_end, float* acc, float* d_radiance, uint8_t* d_rgb8) {
+    if (!s || !cam || !o) return fail(RBRT_ERR_INVALID_ARG, "render: null argument");
+    if (o->spp == 0) return fail(RBRT_ERR_INVALID_ARG, "spp must be >= 1");
+    if (s_begin >= s_end || s_end > o->spp) return fail(RBRT_ERR_INVALID_ARG, "sample range must satisfy begin < end <= spp");
+    if (o->max_depth > uint32_t(kMaxPathDepth))
+        return fail(RBRT_ERR_UNSUPPORTED, "max_depth above the kernel limit of 64");
+    if (cam->img_width_pix == 0 || cam->img_height_pix == 0)
+        return fail(RBRT_ERR_INVALID_ARG, "image has zero pixels");
+    if (uint64_t(cam->img_width_pix) * cam->img_height_pix >= (1ull << 32))
+        return fail(RBRT_ERR_UNSUPPORTED, "image has 2^32 or more pixels");
+    if (o->tile_rank >= (o->tile_world ? o->tile_world : 1)) return fail(RBRT_ERR_INVALID_ARG, "tile_rank >= tile_world");
+    if (int rc = lens_invalid(cam, o)) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    std::lock_guard<std::mutex> watcher_lock(s->mu);  // (the watcher of elastic launches looks at the lanes between calls, not during one)
+    adopt_refined(s);  // (the background thread's trees, once they are on the device: this call's launches use them)
+    CallPlan c{static_cast<hipStream_t>(stream_v), s_begin, s_end};
+    if (!plan_call(s, cam, o, c)) return RBRT_OK;
+    if (int rc = ensure_lanes(s, c.depth)) return rc;
+    if (int rc = prepare_call(s, c, acc)) return rc;
+    const TraceParams P = call_params(s, cam, o, c);
+    ResolveParams R;
+    std::memset(&R, 0, sizeof(R));
+    R.width = cam->img_width_pix, R.height = cam->img_height_pix, R.tiles_x = c.tiles_x, R.n_tiles = c.n_tiles;
+    R.tile_rank = o->tile_rank, R.tile_world = c.world, R.n_local_tiles = c.n_local;
+    R.inv_spp = 1.0f / float(o->spp);  // lib.rs:101
+    R.acc = acc ? acc : s->d_acc, R.out_radiance = d_radiance, R.out_rgb8 = d_rgb8;
+    R.counters = c.stats ? s->d_counters : nullptr, R.error_flag = &s->d_counters->diag[57];
+    // For a stream every lane's buffers are sized here, at the first call that needs them, not when a lane first comes up in
+    // the rotation (a hipMalloc in the middle of a stream of frames); otherwise a lane's are sized when a batch goes to it.
+    if (c.streams_now)
+        for (uint32_t li = 0; li < c.depth; ++li)
+            if (int rc = size_lane(s, c, li)) return rc;
+    // (a one-shot scene's launch has the GPU to itself and runs its tile pass on its own stream: it makes the prep stream
+    // only if a second batch ever overlaps the first -- creating and destroying one costs the call 0.3 ms)
+    if (c.tile_pass && !s->one_shot)
+        if (int rc = ensure_prep_stream(s)) return rc;
+    if (c.tile_pass && c.streams_now)
+        if (int rc = warm_tile_tables(s, c, P)) return rc;
+    if (int rc = issue_batches(s, c, o, P, R)) return rc;
+
     // the watcher of elastic launches: started by the first call of a stream, woken when there is a launch to look after
     s->last_call_s = now_s();
-    if (s->helpers_mode == 1u && depth > 1 && !stats) {
-        if (!s->watcher.joinable() && streams_now) {
+    if (s->helpers_mode == 1u && c.depth > 1 && !c.stats) {
+        if (!s->watcher.joinable() && c.streams_now) {
             try {
                 s->watcher = std::thread([s]() {
                     try {

@@ -1,8 +1,17 @@
 // rbrt_oracle.cpp — TEST INFRASTRUCTURE, NOT PRODUCT CODE.
 //
-// CPU restatement of the reference's AVX render path (baurst/rbrt, Rust), used only as
-// the parity checker by tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg.
+// CPU restatement of the reference's AVX render path (baurst/rbrt, Rust) plus the product's
+// documented extensions (include/rbrt_hip.h), used only as the parity checker by tests/,
+// __graft_entry__.smoke() and bench.py's cpu_baseline leg.
 // Nothing under rbrt_amd/ may link, load or call this file.
+//
+// Two entry points render. rbrt_oracle_render_window is the reference's path alone: it refuses
+// (returns RBRT_ORACLE_REFUSED) any flag but COLLECT_STATS and any material kind outside 0-2, rather
+// than render what it would get wrong. rbrt_oracle_render_ext adds the extensions: emitters
+// (RBRT_MAT_EMISSIVE), RBRT_FLAG_CONSTANT_BACKGROUND, RBRT_FLAG_THIN_LENS (rbrt_camera_lens_t) and
+// the smooth shading of meshes (rbrt_scene_shading_t). The extensions have no counterpart in the
+// reference: they are pinned by the numpy restatements of their contracts (tests/np_lens.py,
+// tests/np_smooth.py, tests/np_full.py), not by the reference's KATs.
 //
 // The reference itself cannot be built here (Rust; no cargo/rustc in the image), so this is a
 // "port"-kind oracle. It is pinned by every known-answer test the reference's own unit tests
@@ -110,6 +119,8 @@ struct Hit {
     V3 point, normal;
     const rbrt_material_t* mat;
     float dist;
+    int32_t mesh = -1;  // a mesh's closest hit: the mesh index and its entry (the smooth shading normal needs both)
+    int32_t tri = -1;
 };
 
 // materials.rs:14-30 — draws x, y, z in that order; accept when length <= 1.0
@@ -453,43 +464,14 @@ inline bool scene_hit(const rbrt_scene_t& sc, const Ray& ray, float min_dist, fl
             if (h.dist < closest) {
                 closest = h.dist;
                 best = h;
+                best.mesh = int32_t(i);
+                best.tri = int32_t(idx);
                 any = true;
                 if (ids) *ids = HitIds{t, int32_t(n_elem + i), int32_t(idx)};
             }
         }
     }
     return any;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Camera + integrator  (cam.rs:64-82, lib.rs:43-73)
-// ---------------------------------------------------------------------------------------------
-inline Ray get_ray_through_pixel(const rbrt_camera_t& cam, uint32_t row, uint32_t col, Rng& rng) {
-    float col_off = float(col) - float(cam.img_width_pix / 2);
-    float row_off = float(row) - float(cam.img_height_pix / 2);
-    float u0 = rng.next_f32();
-    float col_mm = (col_off + u0 - 0.5f) * cam.mm_per_pix_hor;
-    float u1 = rng.next_f32();
-    float row_mm = (row_off + u1 - 0.5f) * cam.mm_per_pix_vert;
-    V3 target = v3(cam.img_center_point) + 0.001f * col_mm * v3(cam.right) - 0.001f * row_mm * v3(cam.up);
-    V3 pos = v3(cam.position);
-    return Ray{pos, normalize(target - pos)};
-}
-
-V3 colorize(const Ray& ray, const rbrt_scene_t& sc, const rbrt_render_opts_t& o, V3 bg, uint32_t depth,
-            Rng& rng, uint64_t* rays) {
-    Hit h;
-    if (rays) ++*rays;
-    if (scene_hit(sc, ray, o.min_dist, o.max_dist, h)) {
-        Ray scattered{v3(0, 0, 0), v3(0, 0, 0)};
-        V3 att = v3(0, 0, 0);
-        if (depth > 0 && scatter(*h.mat, ray, h, att, scattered, rng)) {
-            return att * colorize(scattered, sc, o, bg, depth - 1, rng, rays);
-        }
-        return v3(0, 0, 0);
-    }
-    float t = 0.5f * (ray.direction.y + 1.0f);
-    return t * v3(1.0f, 1.0f, 1.0f) + (1.0f - t) * bg;
 }
 
 // lib.rs:116-122: Rust `as u8` saturates, NaN -> 0.
@@ -501,22 +483,126 @@ inline uint8_t quantise(float c) {
     return uint8_t(v);
 }
 
-}  // namespace
+// ---------------------------------------------------------------------------------------------
+// Smooth shading of meshes (extension: include/rbrt_hip.h rbrt_scene_shading_t, tests/np_smooth.py)
+// ---------------------------------------------------------------------------------------------
+inline bool mesh_is_smooth(const rbrt_scene_shading_t* sh, int32_t mesh) {
+    return sh && sh->meshes && mesh >= 0 && sh->meshes[mesh].n0x;
+}
 
-// =============================================================================================
-// C entry points (ctypes from tests/, bench.py cpu_baseline, __graft_entry__.smoke)
-// =============================================================================================
-extern "C" {
+// The normal scatter uses at a closest hit of entry i of mesh m for the ray (o, d): u, v by the Moller-Trumbore
+// expressions of that entry (the scalar forms are the AVX forms lane for lane: same products, same sums, no contraction),
+// m = ((w n0) + (u n1)) + (v n2), normalize; the stored face normal when that is not finite.
+inline V3 smooth_normal(const rbrt_mesh_t& m, const rbrt_mesh_normals_t& n, size_t i, const Ray& ray) {
+    const V3 face = v3(m.nx[i], m.ny[i], m.nz[i]);
+    const V3 v0 = v3(m.v0x[i], m.v0y[i], m.v0z[i]);
+    const V3 e1 = v3(m.e1x[i], m.e1y[i], m.e1z[i]), e2 = v3(m.e2x[i], m.e2y[i], m.e2z[i]);
+    const V3 h = cross(ray.direction, e2);
+    const float a = dot(e1, h);
+    const float f = 1.0f / a;
+    const V3 s = ray.origin - v0;
+    const float u = f * dot(s, h);
+    const V3 q = cross(s, e1);
+    const float v = f * dot(ray.direction, q);
+    const float w = (1.0f - u) - v;
+    const V3 nm = v3(((w * n.n0x[i]) + (u * n.n1x[i])) + (v * n.n2x[i]),
+                     ((w * n.n0y[i]) + (u * n.n1y[i])) + (v * n.n2y[i]),
+                     ((w * n.n0z[i]) + (u * n.n1z[i])) + (v * n.n2z[i]));
+    const V3 ns = normalize(nm);
+    const bool ok = std::isfinite(ns.x) && std::isfinite(ns.y) && std::isfinite(ns.z);
+    return ok ? ns : face;
+}
 
-// lib.rs:75-124 restricted to columns [c0,c1) x rows [r0,r1) (full image: 0,W,0,H). Pixels outside
-// the window are left untouched; col_stride > 1 renders only every col_stride-th column of the window
-// (an unbiased sample of the image's workload for the CPU-baseline timing). Threads pull columns from a shared counter (rayon's par_iter over
-// columns, lib.rs:84-86); per-pixel arithmetic is sequential so the result is thread-count independent.
-// Returns the number of Scene::hit calls made (for the CPU-baseline report).
-uint64_t rbrt_oracle_render_window(const rbrt_camera_t* cam, const rbrt_scene_t* scene,
-                                   const rbrt_render_opts_t* opts, uint32_t c0, uint32_t c1,
-                                   uint32_t r0, uint32_t r1, uint32_t col_stride, int n_threads,
-                                   float* out_radiance, uint8_t* out_rgb8) {
+// scene_hit with the shading normal of a smooth mesh's closest hit in place of its face normal.
+inline bool scene_hit_shaded(const rbrt_scene_t& sc, const rbrt_scene_shading_t* sh, const Ray& ray, float min_dist,
+                             float max_dist, Hit& best) {
+    if (!scene_hit(sc, ray, min_dist, max_dist, best)) return false;
+    if (mesh_is_smooth(sh, best.mesh))
+        best.normal = smooth_normal(sc.meshes[best.mesh], sh->meshes[best.mesh], size_t(best.tri), ray);
+    return true;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Camera + integrator  (cam.rs:64-82, lib.rs:43-73)
+// ---------------------------------------------------------------------------------------------
+// cam.rs:64-82 up to the point T of the image plane
+inline V3 pixel_target(const rbrt_camera_t& cam, uint32_t row, uint32_t col, Rng& rng) {
+    float col_off = float(col) - float(cam.img_width_pix / 2);
+    float row_off = float(row) - float(cam.img_height_pix / 2);
+    float u0 = rng.next_f32();
+    float col_mm = (col_off + u0 - 0.5f) * cam.mm_per_pix_hor;
+    float u1 = rng.next_f32();
+    float row_mm = (row_off + u1 - 0.5f) * cam.mm_per_pix_vert;
+    return v3(cam.img_center_point) + 0.001f * col_mm * v3(cam.right) - 0.001f * row_mm * v3(cam.up);
+}
+
+inline Ray get_ray_through_pixel(const rbrt_camera_t& cam, uint32_t row, uint32_t col, Rng& rng) {
+    V3 target = pixel_target(cam, row, col, rng);
+    V3 pos = v3(cam.position);
+    return Ray{pos, normalize(target - pos)};
+}
+
+// Extension: the thin lens (include/rbrt_hip.h rbrt_camera_lens_t, tests/np_lens.py camera_ray_lens).
+inline Ray get_lens_ray_through_pixel(const rbrt_camera_lens_t& L, uint32_t row, uint32_t col, Rng& rng) {
+    const V3 target = pixel_target(L.cam, row, col, rng);
+    float lx, ly;
+    do {
+        lx = 2.0f * rng.next_f32() - 1.0f;
+        ly = 2.0f * rng.next_f32() - 1.0f;
+    } while (!((lx * lx) + (ly * ly) < 1.0f));
+    const V3 pos = v3(L.cam.position);
+    const V3 o = pos + ((lx * v3(L.lens_u)) + (ly * v3(L.lens_v)));
+    const V3 focus = pos + L.focus_scale * (target - pos);
+    return Ray{o, normalize(focus - o)};
+}
+
+// lib.rs:43-73, and the extensions: an emitter's closest hit returns its radiance at any depth (before the depth check,
+// no scatter, no draw); under RBRT_FLAG_CONSTANT_BACKGROUND an escaped ray returns bg; a smooth mesh scatters about its
+// shading normal. Without emitters, flags and shading this is the reference's colorize, operation for operation.
+V3 colorize(const Ray& ray, const rbrt_scene_t& sc, const rbrt_scene_shading_t* sh, const rbrt_render_opts_t& o, V3 bg,
+            uint32_t depth, Rng& rng, uint64_t* rays) {
+    Hit h;
+    if (rays) ++*rays;
+    if (scene_hit_shaded(sc, sh, ray, o.min_dist, o.max_dist, h)) {
+        if (h.mat->kind == RBRT_MAT_EMISSIVE) return v3(h.mat->albedo);
+        Ray scattered{v3(0, 0, 0), v3(0, 0, 0)};
+        V3 att = v3(0, 0, 0);
+        if (depth > 0 && scatter(*h.mat, ray, h, att, scattered, rng)) {
+            return att * colorize(scattered, sc, sh, o, bg, depth - 1, rng, rays);
+        }
+        return v3(0, 0, 0);
+    }
+    if (o.flags & RBRT_FLAG_CONSTANT_BACKGROUND) return bg;
+    float t = 0.5f * (ray.direction.y + 1.0f);
+    return t * v3(1.0f, 1.0f, 1.0f) + (1.0f - t) * bg;
+}
+
+// Whether every material kind of the scene lies in 0..max_kind.
+inline bool kinds_within(const rbrt_scene_t& sc, int32_t max_kind) {
+    auto ok = [&](const rbrt_material_t& m) { return m.kind >= 0 && m.kind <= max_kind; };
+    for (uint32_t i = 0; i < sc.n_spheres; ++i)
+        if (!ok(sc.spheres[i].mat)) return false;
+    for (uint32_t i = 0; i < sc.n_triangles; ++i)
+        if (!ok(sc.triangles[i].mat)) return false;
+    for (uint32_t i = 0; i < sc.n_meshes; ++i)
+        if (!ok(sc.meshes[i].mat)) return false;
+    return true;
+}
+
+thread_local char g_error[256] = "";
+
+inline bool refuse(const char* msg) {
+    std::snprintf(g_error, sizeof(g_error), "%s", msg);
+    return false;
+}
+
+// lib.rs:75-124 restricted to a window; `lens` non-null: the thin lens camera. Threads pull columns from a shared counter
+// (rayon's par_iter over columns, lib.rs:84-86); per-pixel arithmetic is sequential so the result is thread-count
+// independent. Returns the number of Scene::hit calls made.
+uint64_t render_window(const rbrt_camera_t* cam, const rbrt_camera_lens_t* lens, const rbrt_scene_t* scene,
+                       const rbrt_scene_shading_t* sh, const rbrt_render_opts_t* opts, uint32_t c0, uint32_t c1,
+                       uint32_t r0, uint32_t r1, uint32_t col_stride, int n_threads, float* out_radiance,
+                       uint8_t* out_rgb8) {
     const uint32_t W = cam->img_width_pix, H = cam->img_height_pix;
     if (c1 > W) c1 = W;
     if (r1 > H) r1 = H;
@@ -535,8 +621,8 @@ uint64_t rbrt_oracle_render_window(const rbrt_camera_t* cam, const rbrt_scene_t*
                 V3 color = v3(0, 0, 0);
                 for (uint32_t s = 0; s < opts->spp; ++s) {
                     Rng rng(opts->seed, row * W + col, s);
-                    Ray ray = get_ray_through_pixel(*cam, row, col, rng);
-                    color = color + colorize(ray, *scene, *opts, bg, opts->max_depth, rng, &rays);
+                    Ray ray = lens ? get_lens_ray_through_pixel(*lens, row, col, rng) : get_ray_through_pixel(*cam, row, col, rng);
+                    color = color + colorize(ray, *scene, sh, *opts, bg, opts->max_depth, rng, &rays);
                 }
                 color = color * (1.0f / float(opts->spp));
                 size_t o = (size_t(row) * W + col) * 3;
@@ -560,6 +646,66 @@ uint64_t rbrt_oracle_render_window(const rbrt_camera_t* cam, const rbrt_scene_t*
     for (auto& t : th) t.join();
     return total_rays.load();
 }
+
+}  // namespace
+
+// =============================================================================================
+// C entry points (ctypes from tests/, bench.py cpu_baseline, __graft_entry__.smoke)
+// =============================================================================================
+extern "C" {
+
+// lib.rs:75-124 restricted to columns [c0,c1) x rows [r0,r1) (full image: 0,W,0,H). Pixels outside
+// the window are left untouched; col_stride > 1 renders only every col_stride-th column of the window
+// (an unbiased sample of the image's workload for the CPU-baseline timing). Threads pull columns from a shared counter (rayon's par_iter over
+// columns, lib.rs:84-86); per-pixel arithmetic is sequential so the result is thread-count independent.
+// Returns the number of Scene::hit calls made (for the CPU-baseline report). The reference's path only: a flag other than
+// RBRT_FLAG_COLLECT_STATS (which does not change the image) or a material kind outside 0-2 is refused with
+// RBRT_ORACLE_REFUSED (rbrt_oracle_last_error says why), nothing rendered; rbrt_oracle_render_ext renders those.
+#define RBRT_ORACLE_REFUSED (~uint64_t(0))
+uint64_t rbrt_oracle_render_window(const rbrt_camera_t* cam, const rbrt_scene_t* scene,
+                                   const rbrt_render_opts_t* opts, uint32_t c0, uint32_t c1,
+                                   uint32_t r0, uint32_t r1, uint32_t col_stride, int n_threads,
+                                   float* out_radiance, uint8_t* out_rgb8) {
+    if (opts->flags & ~uint32_t(RBRT_FLAG_COLLECT_STATS)) {
+        refuse("rbrt_oracle_render_window: flags other than RBRT_FLAG_COLLECT_STATS need rbrt_oracle_render_ext");
+        return RBRT_ORACLE_REFUSED;
+    }
+    if (!kinds_within(*scene, RBRT_MAT_DIELECTRIC)) {
+        refuse("rbrt_oracle_render_window: a material kind outside 0-2 (emissive?) needs rbrt_oracle_render_ext");
+        return RBRT_ORACLE_REFUSED;
+    }
+    return render_window(cam, nullptr, scene, nullptr, opts, c0, c1, r0, r1, col_stride, n_threads, out_radiance, out_rgb8);
+}
+
+// The reference's path and the product's documented extensions (include/rbrt_hip.h): emitters, the constant background,
+// the thin lens (with RBRT_FLAG_THIN_LENS `cam` is the `cam` member of an rbrt_camera_lens_t) and smooth shading
+// (`shading` may be NULL). Returns 0, or -1 for what the product also refuses (rbrt_oracle_last_error says why); *rays:
+// the number of Scene::hit calls.
+int rbrt_oracle_render_ext(const rbrt_camera_t* cam, const rbrt_scene_t* scene, const rbrt_scene_shading_t* shading,
+                           const rbrt_render_opts_t* opts, uint32_t c0, uint32_t c1, uint32_t r0, uint32_t r1,
+                           uint32_t col_stride, int n_threads, float* out_radiance, uint8_t* out_rgb8, uint64_t* rays) {
+    const uint32_t known = RBRT_FLAG_COLLECT_STATS | RBRT_FLAG_CONSTANT_BACKGROUND | RBRT_FLAG_THIN_LENS;
+    if (!cam || !scene || !opts) return refuse("rbrt_oracle_render_ext: null argument"), -1;
+    if (opts->flags & ~known) return refuse("rbrt_oracle_render_ext: unknown flag bits"), -1;
+    if (!kinds_within(*scene, RBRT_MAT_EMISSIVE)) return refuse("rbrt_oracle_render_ext: a material kind outside 0-3"), -1;
+    if (shading && (shading->n_meshes != scene->n_meshes || shading->reserved != 0))
+        return refuse("rbrt_oracle_render_ext: shading->n_meshes != scene->n_meshes or reserved != 0"), -1;
+    const rbrt_camera_lens_t* lens = nullptr;
+    if (opts->flags & RBRT_FLAG_THIN_LENS) {
+        lens = reinterpret_cast<const rbrt_camera_lens_t*>(cam);  // cam is the first member
+        if (!(std::isfinite(lens->focus_scale) && lens->focus_scale > 0.0f) || lens->reserved != 0)
+            return refuse("rbrt_oracle_render_ext: focus_scale not finite and > 0, or reserved != 0"), -1;
+        for (int c = 0; c < 3; ++c)
+            if (!std::isfinite(lens->lens_u[c]) || !std::isfinite(lens->lens_v[c]))
+                return refuse("rbrt_oracle_render_ext: a non-finite lens axis"), -1;
+    }
+    const uint64_t n = render_window(cam, lens, scene, shading, opts, c0, c1, r0, r1, col_stride, n_threads, out_radiance,
+                                     out_rgb8);
+    if (rays) *rays = n;
+    return 0;
+}
+
+const char* rbrt_oracle_last_error(void) { return g_error; }
 
 uint64_t rbrt_oracle_render(const rbrt_camera_t* cam, const rbrt_scene_t* scene,
                             const rbrt_render_opts_t* opts, int n_threads, float* out_radiance,
@@ -591,6 +737,34 @@ void rbrt_oracle_trace_rays(const rbrt_scene_t* scene, const float* rays, size_t
                 if (out_obj) out_obj[i] = ok ? ids.obj : -1;
                 if (out_tri) out_tri[i] = ok ? ids.tri : -1;
                 if (out_dist) out_dist[i] = ok ? h.dist : std::numeric_limits<float>::quiet_NaN();
+            }
+        }
+    };
+    std::vector<std::thread> th;
+    for (int i = 1; i < n_threads; ++i) th.emplace_back(worker);
+    worker();
+    for (auto& t : th) t.join();
+}
+
+// The normal scatter would use at each ray's closest hit (what rbrt_hip_debug_shading_normals returns): a sphere's
+// unnormalised p - center, a BasicTriangle's or a flat mesh's stored normal, a smooth mesh's shading normal; NaN for a
+// miss. out_normal: float[n][3]. `shading` may be NULL.
+void rbrt_oracle_shading_normals(const rbrt_scene_t* scene, const rbrt_scene_shading_t* shading, const float* rays,
+                                 size_t n, float min_dist, float max_dist, int n_threads, float* out_normal) {
+    if (n_threads <= 0) n_threads = int(std::thread::hardware_concurrency());
+    if (n_threads <= 0) n_threads = 1;
+    std::atomic<size_t> next{0};
+    auto worker = [&]() {
+        for (;;) {
+            size_t b = next.fetch_add(256);
+            if (b >= n) break;
+            size_t e = b + 256 < n ? b + 256 : n;
+            for (size_t i = b; i < e; ++i) {
+                Ray r{v3(rays + 6 * i), v3(rays + 6 * i + 3)};
+                Hit h;
+                const float nan = std::numeric_limits<float>::quiet_NaN();
+                const V3 nrm = scene_hit_shaded(*scene, shading, r, min_dist, max_dist, h) ? h.normal : v3(nan, nan, nan);
+                out_normal[3 * i] = nrm.x, out_normal[3 * i + 1] = nrm.y, out_normal[3 * i + 2] = nrm.z;
             }
         }
     };

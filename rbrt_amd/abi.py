@@ -435,8 +435,26 @@ def load_host() -> C.CDLL:
     lib.rbrt_host_write_png.argtypes = [C.c_char_p, u8p, C.c_uint32, C.c_uint32]
     lib.rbrt_host_camera_new.restype = None
     lib.rbrt_host_camera_new.argtypes = [f32p, f32p, f32p, C.c_uint32, C.c_uint32, C.c_float, C.POINTER(Camera)]
+    lib.rbrt_host_yaml_dump.restype = C.c_int
+    lib.rbrt_host_yaml_dump.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p)]
+    lib.rbrt_host_free.restype = None
+    lib.rbrt_host_free.argtypes = [C.c_void_p]
     _host = lib
     return lib
+
+
+def yaml_dump(text) -> str:
+    """Test hook: the tree the C++ host's YAML reader builds from `text` (str or bytes), as JSON (rbrt_host_yaml_dump in
+    host/c_api.cpp describes the format). Raises RuntimeError with the reader's message when it refuses the text."""
+    lib = load_host()
+    raw = text.encode() if isinstance(text, str) else bytes(text)
+    out = C.c_void_p()
+    if lib.rbrt_host_yaml_dump(raw, len(raw), C.byref(out)) != 0:
+        raise RuntimeError(lib.rbrt_host_last_error().decode(errors="replace"))
+    try:
+        return C.string_at(out).decode(errors="replace")
+    finally:
+        lib.rbrt_host_free(out)
 
 
 class HostScene:

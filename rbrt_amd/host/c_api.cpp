@@ -1,12 +1,64 @@
 // c_api.cpp — C entry points of the host library for non-C++ callers (Python ctypes in tests/bench).
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 
 #include "rbrt.hpp"
+#include "yaml_lite.hpp"
 
 namespace {
 thread_local std::string g_err;
+
+void json_string(std::string& out, const std::string& s) {
+    out += '"';
+    for (unsigned char c : s) {
+        if (c == '"' || c == '\\') {
+            out += '\\';
+            out += char(c);
+        } else if (c < 0x20 || c == 0x7f) {
+            char buf[8];
+            std::snprintf(buf, sizeof buf, "\\u%04x", unsigned(c));
+            out += buf;
+        } else {
+            out += char(c);  // (UTF-8 passes through)
+        }
+    }
+    out += '"';
 }
+
+void json_node(std::string& out, const yaml_lite::Node& n) {
+    using yaml_lite::Node;
+    switch (n.kind) {
+        case Node::Null: out += "null"; break;
+        case Node::Scalar:
+            out += "{\"s\": ";
+            json_string(out, n.scalar);
+            out += n.quoted ? ", \"q\": true}" : ", \"q\": false}";
+            break;
+        case Node::List:
+            out += "{\"list\": [";
+            for (size_t i = 0; i < n.list.size(); ++i) {
+                if (i) out += ", ";
+                json_node(out, n.list[i]);
+            }
+            out += "]}";
+            break;
+        case Node::Map:
+            out += "{\"map\": [";
+            for (size_t i = 0; i < n.map.size(); ++i) {
+                if (i) out += ", ";
+                out += '[';
+                json_string(out, n.map[i].first);
+                out += ", ";
+                json_node(out, n.map[i].second);
+                out += ']';
+            }
+            out += "]}";
+            break;
+    }
+}
+}  // namespace
 
 struct rbrt_host_scene {
     rbrt::Camera cam;
@@ -68,6 +120,27 @@ int rbrt_host_save_image(const char* path, const uint8_t* rgb, uint32_t width, u
         return -1;
     }
 }
+
+// TEST HOOK ONLY (tests/test_yaml_differential.py): the tree yaml_lite::parse builds from `text`, as JSON in a string the
+// caller releases with rbrt_host_free. null: a null node; {"s": text, "q": quoted}: a scalar; {"list": [..]}: a sequence;
+// {"map": [[key, value], ..]}: a mapping as pairs in file order. Nonzero when the reader refuses the text; the message is in
+// rbrt_host_last_error.
+int rbrt_host_yaml_dump(const char* text, size_t len, char** json_out) {
+    try {
+        const yaml_lite::Node root = yaml_lite::parse(std::string(text, len));
+        std::string out;
+        json_node(out, root);
+        char* p = static_cast<char*>(std::malloc(out.size() + 1));
+        if (!p) throw std::runtime_error("out of memory");
+        std::memcpy(p, out.c_str(), out.size() + 1);
+        *json_out = p;
+        return 0;
+    } catch (const std::exception& e) {
+        g_err = e.what();
+        return -1;
+    }
+}
+void rbrt_host_free(void* p) { std::free(p); }
 
 // Camera::new alone (cam.rs:22-62), for parity tests against the oracle's restatement.
 void rbrt_host_camera_new(const float position[3], const float look_at[3], const float up[3], uint32_t height,

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <array>
 #include <cctype>
+#include <charconv>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -171,17 +172,76 @@ const Node& need(const Node& m, const char* key, const char* where) {
     return *n;
 }
 
+// Decimal text to a float or double, correctly rounded, whatever LC_NUMERIC the host process has set (strtod and strtof
+// obey it): std::from_chars. The text is a number already checked by its caller; false when it is not read to its end.
+template <class T>
+bool parse_decimal(const char* b, const char* e, T& out) {
+    if (b != e && *b == '+') ++b;
+    const std::from_chars_result r = std::from_chars(b, e, out, std::chars_format::general);
+    if (r.ec == std::errc::result_out_of_range && r.ptr == e) {
+        // strtod's answers: +-inf past the largest, +-0 below the smallest. Which of the two: the decimal exponent of the
+        // first significant digit, d.ddd x 10^(exp10 + lead - 1), is far from 0 on either side.
+        const bool neg = *b == '-';
+        const char* ex = std::find_if(b, e, [](char c) { return c == 'e' || c == 'E'; });
+        const char* dot = std::find(b, ex, '.');
+        const char* p = b + (neg ? 1 : 0);
+        while (p != ex && (*p == '0' || *p == '.')) ++p;
+        long exp10 = ex != e ? std::strtol(std::string(ex + 1, e).c_str(), nullptr, 10) : 0;
+        exp10 = std::max(-1000000L, std::min(1000000L, exp10));
+        const long lead = p < dot ? long(dot - p) : -long(p - dot);
+        out = exp10 + lead > 0 ? std::numeric_limits<T>::infinity() : T(0);
+        if (neg) out = -out;
+        return true;
+    }
+    return r.ec == std::errc() && r.ptr == e;
+}
+
+// A number of the YAML 1.2 core schema: [-+]? ( . digits | digits ( . digits* )? ) ( [eE] [-+]? digits )?, 0x / 0o integers,
+// [-+]? .inf | .Inf | .INF and .nan | .NaN | .NAN; one `_` between two digits is dropped (YAML 1.1's digit grouping, which
+// this reader has always taken). Everything else that strtod would take is refused: hex floats, `inf`, `nan`, `1e_5`.
 // serde_yaml hands a YAML float to an f32 field as f64 -> `as f32` (two roundings); mirrored here.
 float as_f32(const Node& n, const char* what) {
     if (n.kind != Node::Scalar || n.quoted || n.scalar.empty()) throw Error(std::string(what) + ": expected a number");
-    std::string s = n.scalar;
-    if (s == ".inf" || s == ".Inf" || s == ".INF" || s == "+.inf") return std::numeric_limits<float>::infinity();
-    if (s == "-.inf" || s == "-.Inf" || s == "-.INF") return -std::numeric_limits<float>::infinity();
-    if (s == ".nan" || s == ".NaN" || s == ".NAN") return std::numeric_limits<float>::quiet_NaN();
-    s.erase(std::remove(s.begin(), s.end(), '_'), s.end());
-    char* end = nullptr;
-    double d = std::strtod(s.c_str(), &end);
-    if (end == s.c_str() || *end != '\0') throw Error(std::string(what) + ": invalid number `" + n.scalar + "`");
+    const std::string& t = n.scalar;
+    auto invalid = [&]() -> Error { return Error(std::string(what) + ": invalid number `" + t + "`"); };
+    {
+        const std::string u = (t[0] == '+' || t[0] == '-') ? t.substr(1) : t;
+        if (u == ".inf" || u == ".Inf" || u == ".INF")
+            return t[0] == '-' ? -std::numeric_limits<float>::infinity() : std::numeric_limits<float>::infinity();
+    }
+    if (t == ".nan" || t == ".NaN" || t == ".NAN") return std::numeric_limits<float>::quiet_NaN();
+    auto digit = [](char c) { return c >= '0' && c <= '9'; };
+    if (t.size() > 2 && t[0] == '0' && (t[1] == 'x' || t[1] == 'o')) {  // core-schema hexadecimal and octal integers
+        unsigned long long v = 0;
+        const std::from_chars_result r = std::from_chars(t.data() + 2, t.data() + t.size(), v, t[1] == 'x' ? 16 : 8);
+        if (r.ec != std::errc() || r.ptr != t.data() + t.size()) throw invalid();
+        return float(double(v));
+    }
+    std::string s;
+    for (size_t i = 0; i < t.size(); ++i) {
+        if (t[i] == '_') {
+            if (i == 0 || i + 1 == t.size() || !digit(t[i - 1]) || !digit(t[i + 1])) throw invalid();
+            continue;
+        }
+        s += t[i];
+    }
+    size_t i = (s[0] == '+' || s[0] == '-') ? 1 : 0, int_digits = 0, frac_digits = 0;
+    while (i < s.size() && digit(s[i])) ++i, ++int_digits;
+    if (i < s.size() && s[i] == '.') {
+        ++i;
+        while (i < s.size() && digit(s[i])) ++i, ++frac_digits;
+    }
+    if (int_digits + frac_digits == 0) throw invalid();
+    if (i < s.size() && (s[i] == 'e' || s[i] == 'E')) {
+        ++i;
+        if (i < s.size() && (s[i] == '+' || s[i] == '-')) ++i;
+        size_t exp_digits = 0;
+        while (i < s.size() && digit(s[i])) ++i, ++exp_digits;
+        if (exp_digits == 0) throw invalid();
+    }
+    if (i != s.size()) throw invalid();
+    double d = 0.0;
+    if (!parse_decimal(s.data(), s.data() + s.size(), d)) throw invalid();
     return float(d);
 }
 
@@ -296,29 +356,47 @@ long obj_index(long v, long n) {
     return (v == 0 || idx < 0 || idx >= n) ? -1 : idx;
 }
 
-// One face corner: v, v/vt, v//vn or v/vt/vn. Only the position decides whether the face is read (what the loader has
-// always accepted, it still accepts); a missing or bad vn leaves normal_out = -1.
+// One face corner: v, v/vt, v//vn or v/vt/vn, each part an integer or empty, the token read to its end (`1abc` is not `1`).
+// Only the position decides whether the face is read (what the loader has always accepted, it still accepts); a missing
+// or bad vn leaves normal_out = -1.
 bool parse_index(const char*& p, long n_vertices, long n_normals, uint32_t& out, int64_t& normal_out) {
-    char* end = nullptr;
-    long v = std::strtol(p, &end, 10);
-    if (end == p) return false;
-    p = end;
-    normal_out = -1;
-    if (*p == '/') {
-        const char* q = p + 1;
-        while (*q && *q != '/' && *q != ' ' && *q != '\t' && *q != '\r') ++q;  // vt (unused)
-        if (*q == '/') {
-            ++q;
-            char* e2 = nullptr;
-            const long vn = std::strtol(q, &e2, 10);
-            if (e2 != q && (*e2 == '\0' || *e2 == ' ' || *e2 == '\t' || *e2 == '\r')) normal_out = obj_index(vn, n_normals);
+    const char* e = p;
+    while (*e && *e != ' ' && *e != '\t' && *e != '\r') ++e;
+    long part[3] = {0, 0, 0};
+    bool have[3] = {false, false, false};
+    int k = 0;
+    for (const char* q = p;; ++k) {
+        if (k == 3) return false;
+        const char* stop = std::find(q, e, '/');
+        if (stop != q) {
+            const char* digits = (*q == '+' || *q == '-') ? q + 1 : q;  // (from_chars takes no '+')
+            const std::from_chars_result r = std::from_chars(*q == '+' ? q + 1 : q, stop, part[k], 10);
+            if (digits == stop || *digits < '0' || *digits > '9' || r.ec != std::errc() || r.ptr != stop) return false;
+            have[k] = true;
         }
+        if (stop == e) break;
+        q = stop + 1;
     }
-    while (*p && *p != ' ' && *p != '\t') ++p;  // the rest of the token
-    const long idx = obj_index(v, n_vertices);
+    p = e;
+    if (!have[0]) return false;
+    normal_out = have[2] ? obj_index(part[2], n_normals) : -1;
+    const long idx = obj_index(part[0], n_vertices);
     if (idx < 0) return false;
     out = uint32_t(idx);
     return true;
+}
+
+// One number of a `v` or `vn` line: the blank-delimited token, read to its end the way Rust's str::parse::<f32> reads it
+// (correctly rounded, `inf` / `nan` / `infinity` in any case, no hex), independent of LC_NUMERIC. False: no such token.
+bool parse_obj_float(const char*& p, float& out) {
+    while (*p == ' ' || *p == '\t') ++p;
+    const char* e = p;
+    while (*e && *e != ' ' && *e != '\t' && *e != '\r') ++e;
+    if (e == p) return false;
+    const char* b = p;
+    p = e;
+    if ((*b == '+' || *b == '-') && e - b > 1 && (b[1] == '+' || b[1] == '-')) return false;
+    return parse_decimal(b, e, out);
 }
 
 // Area-weighted vertex normals of one model's transformed triangles: per position index, the unnormalised cross(e1, e2)
@@ -367,24 +445,15 @@ ObjMesh load_mesh_from_file(const std::string& filepath, Vec3 translation, Vec3 
         while (*p == ' ' || *p == '\t') ++p;
         if (p[0] == 'v' && (p[1] == ' ' || p[1] == '\t')) {
             p += 2;
-            float v[3];
-            for (int k = 0; k < 3; ++k) {
-                char* end = nullptr;
-                v[k] = std::strtof(p, &end);  // Rust's str::parse::<f32>: correctly rounded
-                if (end == p) throw Error(filepath + ":" + std::to_string(line_no) + ": bad vertex");
-                p = end;
-            }
+            float v[3] = {0.0f, 0.0f, 0.0f};
+            for (int k = 0; k < 3; ++k)
+                if (!parse_obj_float(p, v[k])) throw Error(filepath + ":" + std::to_string(line_no) + ": bad vertex");
             positions.insert(positions.end(), v, v + 3);
         } else if (p[0] == 'v' && p[1] == 'n' && (p[2] == ' ' || p[2] == '\t')) {
             p += 3;
-            float v[3];
+            float v[3] = {0.0f, 0.0f, 0.0f};
             bool ok = true;
-            for (int k = 0; k < 3; ++k) {
-                char* end = nullptr;
-                v[k] = std::strtof(p, &end);
-                ok = ok && end != p && std::isfinite(v[k]);
-                p = end;
-            }
+            for (int k = 0; k < 3; ++k) ok = ok && parse_obj_float(p, v[k]) && std::isfinite(v[k]);
             normals.insert(normals.end(), v, v + 3);
             normal_ok.push_back(ok ? 1 : 0);
         } else if (p[0] == 'f' && (p[1] == ' ' || p[1] == '\t')) {

@@ -18,6 +18,7 @@
 #include <cstring>
 #include "../../rbrt_amd/csrc/bvh.h"
 #include "../../rbrt_amd/host/rbrt.hpp"
+#include "../../rbrt_amd/host/yaml_lite.hpp"
 
 static int g_failed = 0;
 #define CHECK(cond)                                                        \
@@ -49,6 +50,39 @@ static void write_obj(const std::string& path, int n_tris, unsigned seed) {
         else
             o << "f " << -(3 * (n_tris - i)) << " " << -(3 * (n_tris - i)) + 1 << " " << -(3 * (n_tris - i)) + 2 << "\n";
     }
+}
+
+// One JSON string starting behind its opening quote; leaves `i` behind the closing one. (tests/golden/yaml_corpus.json is
+// written with ensure_ascii: everything outside ASCII is a \u escape, surrogate pairs included.)
+static std::string json_string(const std::string& j, size_t& i) {
+    std::string out;
+    auto utf8 = [&](uint32_t cp) {
+        if (cp < 0x80) out += char(cp);
+        else if (cp < 0x800) out += char(0xC0 | (cp >> 6)), out += char(0x80 | (cp & 0x3F));
+        else if (cp < 0x10000) out += char(0xE0 | (cp >> 12)), out += char(0x80 | ((cp >> 6) & 0x3F)), out += char(0x80 | (cp & 0x3F));
+        else out += char(0xF0 | (cp >> 18)), out += char(0x80 | ((cp >> 12) & 0x3F)), out += char(0x80 | ((cp >> 6) & 0x3F)), out += char(0x80 | (cp & 0x3F));
+    };
+    while (i < j.size() && j[i] != '"') {
+        if (j[i] != '\\') {
+            out += j[i++];
+            continue;
+        }
+        const char e = j[i + 1];
+        i += 2;
+        if (e == 'u') {
+            uint32_t cp = uint32_t(std::stoul(j.substr(i, 4), nullptr, 16));
+            i += 4;
+            if (cp >= 0xD800 && cp < 0xDC00 && j.compare(i, 2, "\\u") == 0) {
+                cp = 0x10000 + ((cp - 0xD800) << 10) + (uint32_t(std::stoul(j.substr(i + 2, 4), nullptr, 16)) - 0xDC00);
+                i += 6;
+            }
+            utf8(cp);
+        } else {
+            out += e == 'n' ? '\n' : e == 't' ? '\t' : e == 'r' ? '\r' : e == 'b' ? '\b' : e == 'f' ? '\f' : e;
+        }
+    }
+    ++i;
+    return out;
 }
 
 template <class F>
@@ -137,6 +171,47 @@ int main(int argc, char** argv) {
         }
     }
     CHECK(rejected >= 20);
+    // ---- every text of the differential corpus (tests/test_yaml_differential.py) through the reader alone ----
+    {
+        const std::string j = slurp(root + "/tests/golden/yaml_corpus.json");
+        const std::string cls_key = "{\"cls\":\"", text_key = "\"text\":\"";
+        int n_cases = 0, n_in_refused = 0, n_table_accepted = 0;
+        for (size_t at = j.find(cls_key); at != std::string::npos; at = j.find(cls_key, at)) {
+            at += cls_key.size();
+            const std::string cls = json_string(j, at);
+            at = j.find(text_key, at);
+            CHECK(at != std::string::npos);
+            if (at == std::string::npos) break;
+            at += text_key.size();
+            const std::string text = json_string(j, at);
+            ++n_cases;
+            bool refused = false;
+            try {
+                const yaml_lite::Node n = yaml_lite::parse(text);
+                (void)n;
+            } catch (const std::runtime_error&) {
+                refused = true;
+            }
+            if (cls == "in" && refused) ++n_in_refused;
+            if (cls == "bad-table" && !refused) ++n_table_accepted;
+        }
+        CHECK(n_cases >= 500);
+        CHECK(n_in_refused == 0);
+        CHECK(n_table_accepted == 0);
+    }
+    // ---- .obj statements that must be refused (tests/test_obj_differential.py's table) ----
+    {
+        const char* refused_objs[] = {"v 0 0 0\nv 1 0 0\nf 1 2 3\nv 0 1 0\n", "v 0 0 0\nv 1 0 0\nv 0 1 0\nf 1 0 2\n", "v 0 0 0\nv 1 0 0\nv 0 1 0\nf 1 2 -4\n",
+                                      "v 0 0 0\nv 1 0 0\nv 0 1 0\nf 1 2abc 3\n", "v 0 0 0\nv 1 0 0\nv 0 1 0\nvn 0 0 1\nf 1//1x 2 3\n",
+                                      "v 0 0 0\nv 1 0 0\nv 0 1 0\nf 1/1/1/1 2 3\n", "v 0 0 0\nv 1 0 0\nv 0 1 0\nf 1 2 x\n", "v 0 0 0\nv 1 0 0\nv 0 1 0\nf 1 2 3.0\n",
+                                      "v 1 2\n", "v 1 2 3abc\n", "v 1.0.0 2 3\n", "v 0x10 0 0\n", "v 1,5 0 0\n", "v + 0 0\n", "v +-1 0 0\n",
+                                      "v 0 0 0\nv 1 0 0\nv 0 1 0\nf /1 2 3\n", "v 0 0 0\r\nv 1 0 0\r\nv 0 1 0\r\nf 1 2 3junk\r\n", "v 1e", "f 1/"};
+        for (const char* t : refused_objs) {
+            const std::string p = tmp + "/selftest_refused.obj";
+            std::ofstream(p) << t;
+            CHECK(throws([&] { (void)rbrt::load_mesh_from_file(p, rbrt::Vec3(), rbrt::Vec3(0.1f, 0.2f, 0.3f), 1.0f, true); }));
+        }
+    }
     // ---- malformed .obj ----
     const char* bad_objs[] = {"v 0 0 0\nv 1 0 0\nv 0 1 0\nf 1 2 4\n", "v 0 0 0\nf 1 1\n", "v a b c\nv 0 0 0\nv 1 1 1\nf 1 2 3\n",
                               "f 1 2 3\n", "v 0 0 0\nv 1 0 0\nv 0 1 0\nf 0 1 2\n", "v 0 0 0\nv 1 0 0\nv 0 1 0\nf -4 -1 -2\n",

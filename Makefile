@@ -31,7 +31,8 @@ timers: $(LIBDIR)/librbrt_hip_timers.so
 $(LIBDIR)/librbrt_hip_timers.so: $(LIBDIR)/librbrt_hip.so
 	$(HIPCC) $(HIPFLAGS) -DRBRT_REGION_TIMERS=1 -shared -o $@ $(CSRC)/kernels.hip $(CSRC)/bvh_device.hip $(CSRC)/api.cpp $(CSRC)/bvh.cpp
 
-host:
+# (rbrt_amd/bin/rbrt links against librbrt_hip.so: a parallel make must not start the host before the library exists)
+host: $(LIBDIR)/librbrt_hip.so
 	@if [ -f rbrt_amd/host/Makefile ]; then $(MAKE) -C rbrt_amd/host; fi
 
 oracle:

@@ -133,6 +133,12 @@ int rbrt_hip_debug_primary_cull(rbrt_hip_scene_t* scene, const rbrt_camera_t* ca
 /* The same table for the camera rays of a RBRT_FLAG_THIN_LENS render with `lens` (kernels.hip primary_cull_kernel, "Lens
  * rays"). The lens is validated like the render entry points' (RBRT_ERR_INVALID_ARG). */
 int rbrt_hip_debug_primary_cull_lens(rbrt_hip_scene_t* scene, const rbrt_camera_lens_t* lens, uint32_t* out_words, size_t n_words);
+/* The same table as a render with `opts` computes it: the tree boxes the pass tests are grown by a pad that holds
+ * 1 / opts->min_dist, so the table belongs to a distance window. opts->flags are honoured (with RBRT_FLAG_THIN_LENS `cam` is
+ * the first member of a rbrt_camera_lens_t, as for a render) and validated like a render's (RBRT_ERR_INVALID_ARG). The two
+ * hooks above are this one with rbrt_render_opts_default's options. */
+int rbrt_hip_debug_primary_cull_opts(rbrt_hip_scene_t* scene, const rbrt_camera_t* cam, const rbrt_render_opts_t* opts,
+                                     uint32_t* out_words, size_t n_words);
 
 /* Test hook for smooth shading (rbrt_hip.h rbrt_scene_shading_t): for each of n rays (ox, oy, oz, dx, dy, dz; host array),
  * the normal the scatter of the megakernel would use at its closest hit (rbrt_hip_trace_rays' hit), computed by the same

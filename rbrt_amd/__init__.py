@@ -219,11 +219,20 @@ class HipScene:
                  mixed_pass_16=dict(passes=int(buf[58]) >> 32, lanes=int(buf[58]) & 0xFFFFFFFF))
         return d
 
-    def primary_cull(self, cam):
-        """The primary-ray culling table for `cam` (rbrt_hip_debug_primary_cull; test hook): uint32 (tiles_y, tiles_x)."""
+    def primary_cull(self, cam, opts=None, lens=None):
+        """The primary-ray culling table for `cam` (test hook): uint32 (tiles_y, tiles_x). Without `opts` the table of a render
+        with the default options (rbrt_hip_debug_primary_cull); with an abi.RenderOpts the table of a render with those --
+        its min_dist is part of the pad of the tree boxes the pass tests -- and, with `lens` (see _cam_arg), of its lens rays
+        (rbrt_hip_debug_primary_cull_opts)."""
         tx, ty = (cam.img_width_pix + 7) // 8, (cam.img_height_pix + 7) // 8
         out = np.zeros(tx * ty, np.uint32)
-        abi.check(self._lib.rbrt_hip_debug_primary_cull(self._h, C.byref(cam), out.ctypes.data_as(C.POINTER(C.c_uint32)), out.size))
+        words = out.ctypes.data_as(C.POINTER(C.c_uint32))
+        if opts is None and lens is None:
+            abi.check(self._lib.rbrt_hip_debug_primary_cull(self._h, C.byref(cam), words, out.size))
+        else:
+            opts = _opts_copy(opts if opts is not None else abi.default_opts())
+            cam_p, _keep = _cam_arg(cam, lens, opts)
+            abi.check(self._lib.rbrt_hip_debug_primary_cull_opts(self._h, cam_p, C.byref(opts), words, out.size))
         return out.reshape(ty, tx)
 
     def primary_cull_lens(self, cam, lens):

@@ -2360,23 +2360,27 @@ int rbrt_hip_debug_scatter(const rbrt_material_t* mats, const float* in_dir, con
     return RBRT_OK;
 }
 
-static int debug_primary_cull(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, uint32_t flags, uint32_t* out_words, size_t n_words);
 int rbrt_hip_debug_primary_cull(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, uint32_t* out_words, size_t n_words) {
-    return debug_primary_cull(s, cam, RBRT_FLAG_NONE, out_words, n_words);
+    rbrt_render_opts_t o;
+    rbrt_render_opts_default(&o);
+    return rbrt_hip_debug_primary_cull_opts(s, cam, &o, out_words, n_words);
 }
 int rbrt_hip_debug_primary_cull_lens(rbrt_hip_scene_t* s, const rbrt_camera_lens_t* lens, uint32_t* out_words, size_t n_words) {
-    return debug_primary_cull(s, lens ? &lens->cam : nullptr, RBRT_FLAG_THIN_LENS, out_words, n_words);
+    rbrt_render_opts_t o;
+    rbrt_render_opts_default(&o);
+    o.flags = RBRT_FLAG_THIN_LENS;
+    return rbrt_hip_debug_primary_cull_opts(s, lens ? &lens->cam : nullptr, &o, out_words, n_words);
 }
-static int debug_primary_cull(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, uint32_t flags, uint32_t* out_words, size_t n_words) {
-    if (!s || !cam || !out_words) return fail(RBRT_ERR_INVALID_ARG, "debug_primary_cull: null argument");
+int rbrt_hip_debug_primary_cull_opts(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, const rbrt_render_opts_t* opts, uint32_t* out_words,
+                                     size_t n_words) {
+    if (!s || !cam || !opts || !out_words) return fail(RBRT_ERR_INVALID_ARG, "debug_primary_cull: null argument");
     const uint32_t tiles_x = (cam->img_width_pix + RBRT_TILE - 1) / RBRT_TILE, tiles_y = (cam->img_height_pix + RBRT_TILE - 1) / RBRT_TILE;
     if (uint64_t(tiles_x) * tiles_y != n_words || n_words == 0 || n_words > 0xFFFFFFFFull)
         return fail(RBRT_ERR_INVALID_ARG, "debug_primary_cull: n_words must be the number of 8x8 tiles of the camera's image");
+    if (opts->tile_rank >= (opts->tile_world ? opts->tile_world : 1)) return fail(RBRT_ERR_INVALID_ARG, "tile_rank >= tile_world");
+    if (int rc = lens_invalid(cam, opts)) return rc;
     HIP_TRY(hipSetDevice(s->device));
-    rbrt_render_opts_t o;
-    rbrt_render_opts_default(&o);
-    o.flags = flags;
-    if (int rc = lens_invalid(cam, &o)) return rc;
+    const rbrt_render_opts_t& o = *opts;  // (the table is the whole image's, whatever the partition)
     TraceParams P;
     fill_trace_params(s, cam, &o, P);
     P.tiles_x = tiles_x, P.tiles_y = tiles_y, P.n_tiles = uint32_t(n_words);

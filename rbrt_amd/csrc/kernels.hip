@@ -293,6 +293,11 @@ __device__ __forceinline__ bool tri_test(V3 v0, V3 ea, V3 eb, V3 o, V3 d, float 
 // that point is strictly inside every ancestor's grown box (the |o|_inf term covers the o*inv
 // product of the FMA form), the slab interval contains t, and `tn <= best_t` (not <) keeps
 // equal-t candidates with a lower index reachable.
+// Where this has to hold is bounded by the reference itself: tri_test accepts only if |a| >= eps (a ~ twice the area
+// times |d| times a cosine) and eps < t < 1 / eps, below the scan's 1e6; for triangle size L, direction length D and hit
+// distance rho that is L^2 D >~ eps and eps D < rho < min(D / eps, 1e6 D). tests/cull_families.py sweep() walks that
+// window -- meshes 3e-7 to 3.5e6 across, eps from 1e-17 to 1e-2, |d| from 1e-4 to 1e4, a far small mesh, slivers eps
+// wide, the integer grid, a max_dist that cuts hits off -- through every tree, the megakernel and the tile pass.
 // ---------------------------------------------------------------------------------------------
 // n / d for a launch-constant divisor: m = floor(2^32 / d) (host, div_magic_of) under-estimates the quotient by
 // at most 2, fixed by two conditional steps; ~8 instructions instead of the ~40 of a 32-bit division.

@@ -21,7 +21,7 @@ def far_mesh(oracle, offset):
                             abi.material(abi.MAT_LAMBERTIAN, (0.6, 0.5, 0.4)))
 
 
-def slivers(oracle):
+def slivers(oracle, eps=EPS):
     """Long thin triangles a few eps wide, in every orientation: Moller-Trumbore's |a| is barely above eps for many rays."""
     rng = np.random.default_rng(21)
     n = 1200
@@ -32,7 +32,7 @@ def slivers(oracle):
     w -= (w * u).sum(1, keepdims=True) * u
     w /= np.linalg.norm(w, axis=1, keepdims=True)
     length = rng.uniform(0.5, 3.0, (n, 1))
-    width = EPS * rng.uniform(1.2, 4.0, (n, 1))
+    width = eps * rng.uniform(1.2, 4.0, (n, 1))
     tris = np.stack([p, p + u * length, p + u * length * 0.5 + w * width], 1)
     return oracle.mesh_prep(tris.astype(np.float32), mat=abi.material(abi.MAT_METAL, (0.8, 0.8, 0.9), 0.1))
 
@@ -70,6 +70,56 @@ def families(oracle):
     return out
 
 
+def rough_mesh(oracle, scale):
+    """The 1500-triangle rough stand-in, about 0.23 * scale across, centred near (0.3, -0.2, 0.1) * scale."""
+    return oracle.mesh_prep(standin.triangles(1500, "rough"), scale, (0.0, 0.0, 0.0), (0.3 * scale, -0.2 * scale, 0.1 * scale),
+                            abi.material(abi.MAT_LAMBERTIAN, (0.6, 0.5, 0.4)))
+
+
+def radius(md):
+    return float(np.linalg.norm((md.bbox_hi - md.bbox_lo).astype(np.float64)) / 2)
+
+
+def sweep(oracle):
+    """name -> (MeshData, lab environment for the host builder, min_dist, max_dist, direction lengths): the culling pad over
+    the window the reference itself admits. triangle.rs:146 accepts a hit only if |a| >= min_dist (a = e1 . (d x e2): about
+    twice the triangle's area times |d| times a cosine) and min_dist < t < 1 / min_dist, and triangle.rs:398 starts the scan
+    at t = 1e6; so for triangle size L, direction length D and hit distance rho a row has L^2 D >~ min_dist and
+    min_dist D < rho < min(D / min_dist, 1e6 D). Outside of that the scan finds nothing and there is nothing to compare.
+    Mesh sizes from 3e-7 to 3e6, min_dist from 1e-17 to 1e-2, direction lengths from 1e-4 to 1e4. max_dist is 1e5 bounding
+    radii (no ray of rays() starts further than 1e4 radii from its target: it plays no part) except in the row named for it,
+    where it is the bounding radius itself: the origins one radius from their targets have their hits right at the cut."""
+    unit = (0.2, 1.0, 3.0)
+    rows = {}
+
+    def add(name, md, min_dist, lengths=unit, env=None, max_dist=None):
+        rows[name] = (md, env or {}, min_dist, max_dist if max_dist is not None else 1e5 * radius(md), lengths)
+
+    add("s15_e1e-3", rough_mesh(oracle, 15.0), 1e-3)
+    add("s15_e1e-6", rough_mesh(oracle, 15.0), 1e-6)
+    add("s15_e1e-3_short_long", rough_mesh(oracle, 15.0), 1e-3, (1e-4, 1e4))
+    add("s15_e1e-3_long", rough_mesh(oracle, 15.0), 1e-3, (30.0, 1000.0))
+    add("s15_e1e-3_maxdist", rough_mesh(oracle, 15.0), 1e-3, max_dist=radius(rough_mesh(oracle, 15.0)))
+    add("s0.6_e1e-5", rough_mesh(oracle, 0.6), 1e-5)   # (0.6: no power of two times another row's scale)
+    add("s1.5e-3_e1e-11", rough_mesh(oracle, 1.5e-3), 1e-11)
+    add("s1.5e-3_e1e-7_short_long", rough_mesh(oracle, 1.5e-3), 1e-7, (1e-4, 1e4))
+    add("s1.5e-6_e1e-17", rough_mesh(oracle, 1.5e-6), 1e-17)
+    add("s1.5e4_e1e-6", rough_mesh(oracle, 1.5e4), 1e-6)
+    add("s1.5e7_e1e-9", rough_mesh(oracle, 1.5e7), 1e-9)
+    add("s1.5e7_e1e-9_short_long", rough_mesh(oracle, 1.5e7), 1e-9, (1e-3, 1e3))
+    add("far+1e+03_small", oracle.mesh_prep(standin.triangles(1500, "rough"), 0.043, (0.0, 0.0, 0.0), (1e3, -40.0, 2.0),
+                                            abi.material(abi.MAT_LAMBERTIAN, (0.6, 0.5, 0.4))), 1e-9)
+    add("slivers_e1e-6", slivers(oracle, 1e-6), 1e-6)
+    add("slivers_e1e-2", slivers(oracle, 1e-2), 1e-2)
+    add("grid_e2^-20", integer_grid(oracle), 2.0 ** -20)
+    return rows
+
+
+SWEEP = ["s15_e1e-3", "s15_e1e-6", "s15_e1e-3_short_long", "s15_e1e-3_long", "s15_e1e-3_maxdist", "s0.6_e1e-5", "s1.5e-3_e1e-11",
+         "s1.5e-3_e1e-7_short_long", "s1.5e-6_e1e-17", "s1.5e4_e1e-6", "s1.5e7_e1e-9", "s1.5e7_e1e-9_short_long", "far+1e+03_small",
+         "slivers_e1e-6", "slivers_e1e-2", "grid_e2^-20"]
+
+
 def targets(md, N, T, rng, n):
     """n points where culling is tight: node box corners / edge and face points of the tree, triangle vertices and edge points."""
     child = N[:, 24:28].view(np.int32)
@@ -90,9 +140,9 @@ def targets(md, N, T, rng, n):
     return np.where(rng.random((n, 1)) < 0.5, box_pts, tri_pts).astype(np.float64)
 
 
-def rays(md, N, T, n, seed=0):
+def rays(md, N, T, n, seed=0, eps=EPS, lengths=(0.2, 1.0, 3.0)):
     """n rays (float32 (n, 6)) aimed at targets(): origin distances 1.5 eps, R, 60 R, 1e4 R; a third of them grazing;
-    direction lengths 0.2, 1, 3."""
+    direction lengths drawn from `lengths`."""
     rng = np.random.default_rng(seed)
     p = targets(md, N, T, rng, n)
     R = float(np.linalg.norm((md.bbox_hi - md.bbox_lo).astype(np.float64)) / 2)
@@ -101,7 +151,7 @@ def rays(md, N, T, n, seed=0):
     axis = rng.integers(0, 3, n)
     d[graze, axis[graze]] *= 1e-6                      # nearly parallel to a box face
     d /= np.linalg.norm(d, axis=1, keepdims=True)
-    dist = rng.choice([1.5 * EPS, R, 60 * R, 1e4 * R], n)
+    dist = rng.choice([1.5 * eps, R, 60 * R, 1e4 * R], n)
     o = p - d * dist[:, None]
-    d = d * rng.choice([0.2, 1.0, 3.0], n)[:, None]
+    d = d * rng.choice(list(lengths), n)[:, None]
     return np.concatenate([o, d], 1).astype(np.float32)

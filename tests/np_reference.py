@@ -143,6 +143,17 @@ def bbox_hit(lo, hi, o, d) -> bool:
     return True
 
 
+def bbox_gate(lo, hi, rays):
+    """bbox_hit over an array of rays (n, 6) at once: (n,) bool."""
+    o, d = rays[:, :3], rays[:, 3:]
+    with np.errstate(all="ignore"):
+        tl = ((lo - o) / d).astype(f32)
+        tu = ((hi - o) / d).astype(f32)
+    t_min = np.fmax(np.fmax(np.fmin(tl, tu)[:, 0], np.fmin(tl, tu)[:, 1]), np.fmin(tl, tu)[:, 2])
+    t_max = np.fmin(np.fmin(np.fmax(tl, tu)[:, 0], np.fmax(tl, tu)[:, 1]), np.fmax(tl, tu)[:, 2])
+    return ~(t_max < 0) & ~(t_min > t_max)
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # triangle.rs:134-262 (all triangles, 8 per iteration -> here: all at once, elementwise = lane-wise) + 392-410
 # ---------------------------------------------------------------------------------------------------------------

@@ -185,23 +185,27 @@ def random_rays(md, n):
     return np.concatenate([o, d], 1).astype(np.float32)
 
 
-def check_walk_keeps_winner(oracle, md, N, T, n=1500, min_hits=300, rays=None):
-    """Walks the tree for every ray the scan says hits the mesh (rays: random_rays(md, n) unless given) and checks that the
-    winner's leaf is reached."""
+def check_walk_keeps_winner(oracle, md, N, T, n=1500, min_hits=300, rays=None, eps=0.001, max_dist=2000.0):
+    """Walks the tree for every ray the scan says hits the mesh (rays: random_rays(md, n) unless given) inside the distance
+    window (eps, max_dist) and checks that the winner's leaf is reached. The slab arithmetic is float64; the pad's terms are
+    rounded to float32 where the kernel rounds them (make_cull, node4_visit), so a pad that overflows to infinity here does
+    so there too: that only makes both permissive."""
     child = N[:, 24:28].view(np.int32)
     idx = T[:, 9].view(np.uint32)
     c = ((md.bbox_lo + md.bbox_hi) / 2).astype(np.float64)
     if rays is None:
         rays = random_rays(md, n)
     only_mesh = abi.SceneData(meshes=[md])
-    t, obj, tri, _ = oracle.trace_rays(only_mesh, rays)
-    assert (obj >= 0).sum() > min_hits
-    eps, radius = 0.001, np.linalg.norm((md.bbox_hi - md.bbox_lo).astype(np.float64) / 2) * 1.0001
+    t, obj, tri, _ = oracle.trace_rays(only_mesh, rays, eps, max_dist)
+    assert (obj >= 0).sum() > min_hits, int((obj >= 0).sum())
+    f32 = np.float32
+    eps = float(f32(eps))  # (what the library is handed)
+    radius = np.linalg.norm((md.bbox_hi - md.bbox_lo).astype(np.float64) / 2) * 1.0001
     for r in np.nonzero(obj >= 0)[0]:
         oo, dd = rays[r, :3].astype(np.float64), rays[r, 3:].astype(np.float64)
-        pad_base = 64 * 2.0 ** -24 * (np.linalg.norm(oo - c) + radius + np.abs(oo).max())
-        pad_k = pad_base * np.linalg.norm(dd) / eps
-        with np.errstate(divide="ignore", invalid="ignore"):
+        with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
+            pad_base = f32(64 * 2.0 ** -24 * (np.linalg.norm(oo - c) + radius + np.abs(oo).max()))
+            pad_k = f32(pad_base * f32(f32(np.linalg.norm(dd)) * f32(1.0 / eps)))
             inv = 1.0 / dd
         stack, reached = [0], set()
         while stack:
@@ -213,10 +217,11 @@ def check_walk_keeps_winner(oracle, md, N, T, n=1500, min_hits=300, rays=None):
             for k in range(4):
                 if child[node, k] == NO_CHILD:
                     continue
-                pad = pad_base + pad_k * N[node, 28 + k]
+                with np.errstate(over="ignore", invalid="ignore"):
+                    pad = float(f32(float(pad_k) * float(N[node, 28 + k]) + float(pad_base)))  # (one FMA: one rounding)
                 lo = N[node, [k, 4 + k, 8 + k]].astype(np.float64) - pad
                 hi = N[node, [12 + k, 16 + k, 20 + k]].astype(np.float64) + pad
-                with np.errstate(invalid="ignore"):
+                with np.errstate(over="ignore", invalid="ignore"):
                     t0, t1 = (lo - oo) * inv, (hi - oo) * inv
                 tn, tf = np.fmax.reduce(np.fmin(t0, t1)), np.fmin.reduce(np.fmax(t0, t1))
                 if tn <= tf and tf >= eps and tn <= t[r]:  # pruned with the FINAL best t: the hardest case
@@ -277,3 +282,24 @@ def test_culling_keeps_the_winner_on_adversarial_rays(oracle, monkeypatch, famil
     N, T, depth, me = build(md)
     check_invariants(md, N, T, depth, me)
     check_walk_keeps_winner(oracle, md, N, T, rays=cull_families.rays(md, N, T, 1500, seed=len(family)), min_hits=100)
+
+
+# rays per row of the walk below: enough for more than 100 scan hits in each (the rows far from the scan's t < 1e6 and the
+# slivers give the fewest per ray), few enough for the whole test to take a few minutes
+SWEEP_WALK_RAYS = {"s1.5e7_e1e-9": 2000, "slivers_e1e-6": 3000, "slivers_e1e-2": 3000}
+
+
+@pytest.mark.parametrize("row", __import__("cull_families").SWEEP)
+def test_culling_keeps_the_winner_over_the_hit_window(oracle, monkeypatch, row):
+    """The same walk over cull_families.sweep(): mesh sizes from 3e-7 to 3e6, min_dist from 1e-17 to 1e-2, direction lengths
+    from 1e-4 to 1e4, a far mesh 1e-2 across, slivers as wide as min_dist, the integer grid, and a max_dist that cuts hits
+    off -- the window in which the reference's own test can accept a hit at all."""
+    import cull_families
+    md, env, min_dist, max_dist, lengths = cull_families.sweep(oracle)[row]
+    monkeypatch.setenv("RBRT_HIP_LAB", "1")
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    N, T, depth, me = build(md)
+    check_invariants(md, N, T, depth, me)
+    rays = cull_families.rays(md, N, T, SWEEP_WALK_RAYS.get(row, 1000), seed=len(row), eps=min_dist, lengths=lengths)
+    check_walk_keeps_winner(oracle, md, N, T, rays=rays, min_hits=100, eps=min_dist, max_dist=max_dist)

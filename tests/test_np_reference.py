@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import gate_boxes
 import np_reference as R
 import scenes
 from rbrt_amd import abi
@@ -209,3 +210,24 @@ def test_quantise(oracle):
     vals = np.concatenate([np.random.default_rng(1).uniform(0, 1.2, 500), [0.0, 1.0, 0.99609375, 0.9921875, 4.0, -1.0, np.nan, np.inf]]).astype(f32)
     for c in vals:
         assert oracle.lib().rbrt_oracle_kat_quantise(float(c)) == R.quantise(c), c
+
+
+@pytest.mark.parametrize("box", list(gate_boxes.GATE_BOXES))
+def test_gate_inputs_split_each_box(oracle, box):
+    """A condition on the inputs of test_gpu_parity.test_division_free_mesh_gate_decides_like_the_ieee_form, with the numpy
+    form alone: the rays of every box are neither all accepted nor all rejected (the inverted box of a mesh without
+    triangles accepts every ray but those from an infinite origin), and the two boxes made for the gate's cut-offs have
+    their quotients on both sides of them."""
+    lo, hi, scales = gate_boxes.gate_box(oracle, box)
+    rays, _, _ = gate_boxes.gate_rays(box, lo, hi, scales)
+    rate = R.bbox_gate(lo, hi, rays).mean()
+    print(f"{box}: lo {lo} hi {hi}, {len(rays)} rays, accept rate {rate:.4f}")
+    assert 0.0 < rate < 1.0
+    if box == "config2":
+        assert 0.2 < rate < 0.9  # (what the one-box test asked of it)
+    with np.errstate(all="ignore"):
+        q = np.abs(np.concatenate([(lo - rays[:400_000, :3]) / rays[:400_000, 3:], (hi - rays[:400_000, :3]) / rays[:400_000, 3:]], 1)).max(1)
+    if box == "quotients_near_1e30":   # the largest quotient of a ray, within two decades of the cut-off on both sides
+        assert ((q > 1e28) & (q < 1e30)).mean() > 0.1 and ((q > 1e30) & (q < 1e32)).mean() > 0.1
+    if box == "quotients_near_1e-30":
+        assert ((q > 1e-32) & (q < 1e-30)).mean() > 0.1 and ((q > 1e-30) & (q < 1e-28)).mean() > 0.1

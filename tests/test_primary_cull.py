@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import scenes
+from np_reference import bbox_gate  # noqa: F401  (test_thin_lens reads it from here)
 from rbrt_amd import abi
 
 pytestmark = pytest.mark.gpu
@@ -45,17 +46,6 @@ def camera_rays(cam, u0, u1):
     return np.concatenate([o, d], -1).reshape(-1, 6).astype(f32)
 
 
-def bbox_gate(lo, hi, rays):
-    """aabbox.rs:28-58 over an array of rays (np_reference.bbox_hit, vectorised)."""
-    o, d = rays[:, :3], rays[:, 3:]
-    with np.errstate(all="ignore"):
-        tl = ((lo - o) / d).astype(f32)
-        tu = ((hi - o) / d).astype(f32)
-    t_min = np.fmax(np.fmax(np.fmin(tl, tu)[:, 0], np.fmin(tl, tu)[:, 1]), np.fmin(tl, tu)[:, 2])
-    t_max = np.fmin(np.fmin(np.fmax(tl, tu)[:, 0], np.fmax(tl, tu)[:, 1]), np.fmax(tl, tu)[:, 2])
-    return ~(t_max < 0) & ~(t_min > t_max)
-
-
 def tiles_of(mask, W, H):
     """(H*W,) bool per pixel -> (tiles_y, tiles_x) bool: any pixel of the tile."""
     ty, tx = (H + 7) // 8, (W + 7) // 8
@@ -76,21 +66,22 @@ def jitters(rng, W, H):
                (rng.integers(0, 1 << 24, (H, W)).astype(f32) * f32(2.0 ** -24)))
 
 
-def check_table(hip, oracle, cam, sc, rng, max_dist=2000.0, full_scene_jitters=8):
-    """Looks for a ray that passes a test its tile's word rules out. Returns the table."""
+def check_table(hip, oracle, cam, sc, rng, max_dist=2000.0, full_scene_jitters=8, min_dist=0.001):
+    """Looks for a ray that passes a test its tile's word rules out, in the table of a render with the distance window
+    (min_dist, max_dist): the pass grows the tree boxes it tests by a pad that holds 1 / min_dist. Returns the table."""
     W, H = cam.img_width_pix, cam.img_height_pix
     with hip.HipScene(sc) as hs:
-        table = hs.primary_cull(cam)
+        table = hs.primary_cull(cam, abi.default_opts(min_dist=min_dist, max_dist=max_dist))
     n_el = len(sc.spheres)
     reach = [np.zeros(table.shape, bool) for _ in range(n_el + len(sc.meshes))]
     anything = np.zeros(table.shape, bool)
     for n, (u0, u1) in enumerate(jitters(rng, W, H)):
         rays = camera_rays(cam, u0, u1)
         if n < full_scene_jitters:  # Scene::hit itself (all triangles, brute force): what a "background only" tile promises
-            _, obj, _, _ = oracle.trace_rays(sc, rays, 0.001, max_dist)
+            _, obj, _, _ = oracle.trace_rays(sc, rays, min_dist, max_dist)
             anything |= tiles_of(obj >= 0, W, H)
         for e, sp in enumerate(sc.spheres):
-            _, obj, _, _ = oracle.trace_rays(abi.SceneData(spheres=[sp]), rays, 0.001, max_dist)
+            _, obj, _, _ = oracle.trace_rays(abi.SceneData(spheres=[sp]), rays, min_dist, max_dist)
             reach[e] |= tiles_of(obj >= 0, W, H)
         for m, md in enumerate(sc.meshes):
             reach[n_el + m] |= tiles_of(bbox_gate(md.bbox_lo.astype(f32), md.bbox_hi.astype(f32), rays), W, H)

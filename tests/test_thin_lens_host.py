@@ -102,6 +102,16 @@ def test_the_debug_hook_rejects_a_null_lens():
     assert abi.load_hip().rbrt_hip_debug_primary_cull_lens(None, None, out.ctypes.data_as(C.POINTER(C.c_uint32)), 1) == abi.RBRT_ERR_INVALID_ARG
 
 
+def test_the_debug_hook_with_options_rejects_null_arguments():
+    """rbrt_hip_debug_primary_cull_opts: the table of a render with given options; no scene, camera or options is an error."""
+    out = np.zeros(1, np.uint32)
+    words = out.ctypes.data_as(C.POINTER(C.c_uint32))
+    opts = abi.default_opts(min_dist=1e-6)
+    assert abi.load_hip().rbrt_hip_debug_primary_cull_opts(None, None, C.byref(opts), words, 1) == abi.RBRT_ERR_INVALID_ARG
+    assert abi.load_hip().rbrt_hip_debug_primary_cull_opts(None, None, None, words, 1) == abi.RBRT_ERR_INVALID_ARG
+    assert b"null argument" in abi.load_hip().rbrt_hip_last_error()
+
+
 @pytest.mark.parametrize("aperture,focus", [(7.0, 15.0), (0.5, 2.25), (50.0, 3.0), (1e-3, 1000.0), (28.0 / 1.4, 6.5)])
 def test_the_host_derives_the_lens_bit_for_bit(tmp_path, aperture, focus):
     hs = abi.HostScene(_yaml(tmp_path, "lens", camera_aperture_mm=aperture, camera_focus_distance=focus), 24, 32)

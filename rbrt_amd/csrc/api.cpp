@@ -74,16 +74,39 @@ int fail(int code, const std::string& msg) {
     return code;
 }
 
-#define HIP_TRY(expr)                                                                                \
-    do {                                                                                             \
-        hipError_t _e = (expr);                                                                      \
-        if (_e != hipSuccess) {                                                                      \
-            int _code = (_e == hipErrorOutOfMemory) ? RBRT_ERR_OOM                                   \
-                        : (_e == hipErrorNoDevice || _e == hipErrorInvalidDevice) ? RBRT_ERR_NO_DEVICE \
-                                                                                  : RBRT_ERR_HIP;    \
-            return fail(_code, std::string(#expr) + ": " + hipGetErrorString(_e));                   \
-        }                                                                                            \
+// A failed HIP call as the ABI reports it: the one place that maps a hipError_t to an error code.
+int hip_fail(hipError_t e, const std::string& what) {
+    const int code = (e == hipErrorOutOfMemory) ? RBRT_ERR_OOM
+                     : (e == hipErrorNoDevice || e == hipErrorInvalidDevice) ? RBRT_ERR_NO_DEVICE
+                                                                             : RBRT_ERR_HIP;
+    return fail(code, what + ": " + hipGetErrorString(e));
+}
+
+#define HIP_TRY(expr)                                    \
+    do {                                                 \
+        hipError_t _e = (expr);                          \
+        if (_e != hipSuccess) return hip_fail(_e, #expr); \
     } while (0)
+
+// What a test hook returns after its chain of HIP calls. `who`: the hook, for the message.
+int hook_result(hipError_t e, const char* who) {
+    return e == hipSuccess ? RBRT_OK : fail(RBRT_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+}
+
+// A hipMalloc'ed array that lives as long as its scope: the temporaries of the builders and of the test hooks.
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    explicit DevBuf(T* owned = nullptr) : p(owned) {}
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { (void)hipFree(p); }
+    hipError_t alloc(size_t n) { return hipMalloc(reinterpret_cast<void**>(&p), n * sizeof(T)); }
+    T* get() const { return p; }
+    hipError_t from_host(const T* h, size_t n) { return hipMemcpy(p, h, n * sizeof(T), hipMemcpyHostToDevice); }
+    hipError_t upload(const T* h, size_t n) { const hipError_t e = alloc(n); return e != hipSuccess ? e : from_host(h, n); }
+    hipError_t to_host(T* h, size_t n) const { return hipMemcpy(h, p, n * sizeof(T), hipMemcpyDeviceToHost); }
+};
 
 uint32_t local_tiles_of(uint32_t n_tiles, uint32_t rank, uint32_t world) {
     return rank < n_tiles ? (n_tiles - rank + world - 1u) / world : 0u;
@@ -153,6 +176,42 @@ size_t workspace_cap_bytes() {
         if (v > 0) mb = size_t(v);
     }
     return mb << 20;
+}
+
+// The host builder links a leaf to its records by their position in the tree's own array; the scene keeps one array for
+// all meshes (leaf links are absolute positions in it), in which this tree's records start at tri_base.
+void rebase_leaf_links(std::vector<BvhNode4>& nodes, uint32_t tri_base) {
+    if (tri_base == 0) return;
+    for (BvhNode4& nd : nodes)
+        for (int c = 0; c < 4; ++c)
+            if (nd.child[c] < 0 && nd.child[c] != kNoChild) {
+                const uint32_t leaf = uint32_t(~nd.child[c]);
+                nd.child[c] = ~int32_t((((leaf >> kLeafBits) + tri_base) << kLeafBits) | (leaf & uint32_t(kLeafMax - 1)));
+            }
+}
+
+// A builder's arrays as malloc'ed copies for the caller (rbrt_hip_free_host); nothing is handed out when either cannot
+// be had. `who`: the hook, for the message.
+int copy_out(const BvhBuildResult& r, const char* who, void** nodes_out, size_t* n_nodes, void** tris_out, size_t* n_tris,
+             uint32_t* max_depth, float* max_e12) {
+    *n_nodes = r.nodes.size(), *n_tris = r.tris.size();
+    *nodes_out = std::malloc(std::max<size_t>(1, r.nodes.size() * sizeof(BvhNode4)));
+    *tris_out = std::malloc(std::max<size_t>(1, r.tris.size() * sizeof(BvhTri)));
+    if (!*nodes_out || !*tris_out) {
+        std::free(*nodes_out), std::free(*tris_out);
+        *nodes_out = *tris_out = nullptr;
+        return fail(RBRT_ERR_OOM, std::string(who) + ": malloc failed");
+    }
+    std::memcpy(*nodes_out, r.nodes.data(), r.nodes.size() * sizeof(BvhNode4));
+    std::memcpy(*tris_out, r.tris.data(), r.tris.size() * sizeof(BvhTri));
+    if (max_depth) *max_depth = r.max_depth;
+    if (max_e12) *max_e12 = r.max_e12;
+    return RBRT_OK;
+}
+
+// The tree of a mesh as the mesh table names it, whichever builder made it (scene_create's two, the background build).
+void set_tree(DevMesh& dm, const BvhNode4* d_nodes, float max_e12, size_t n_nodes, size_t n_tris) {
+    dm.nodes = d_nodes, dm.max_e12 = max_e12, dm.n_nodes = uint32_t(n_nodes), dm.n_tris = uint32_t(n_tris);
 }
 
 }  // namespace
@@ -385,23 +444,14 @@ struct Refine {
             BvhBuildResult& b = built[i];
             const size_t cap = size_t(i + 1 < meshes.size() ? tri_base[i + 1] : uint32_t(tri_total)) - tri_base[i];
             if (b.tris.size() > cap || b.nodes.empty()) return finish("the host builder's tree does not fit the mesh's records");
-            if (tri_base[i] != 0)
-                for (BvhNode4& nd : b.nodes)
-                    for (int c = 0; c < 4; ++c)
-                        if (nd.child[c] < 0 && nd.child[c] != kNoChild) {
-                            const uint32_t leaf = uint32_t(~nd.child[c]);
-                            nd.child[c] = ~int32_t((((leaf >> kLeafBits) + tri_base[i]) << kLeafBits) | (leaf & uint32_t(kLeafMax - 1)));
-                        }
+            rebase_leaf_links(b.nodes, tri_base[i]);
             void* p = nullptr;
             if (!hip(hipMalloc(&p, b.nodes.size() * sizeof(BvhNode4)), "hipMalloc(nodes)")) return;
             allocs.push_back(p);
             if (!hip(hipMemcpyAsync(p, b.nodes.data(), b.nodes.size() * sizeof(BvhNode4), hipMemcpyHostToDevice, st), "upload of the nodes")) return;
             std::copy(b.tris.begin(), b.tris.end(), h.begin() + tri_base[i]);
             nodes_delta_minus += meshes[i].n_nodes, nodes_delta_plus += b.nodes.size();
-            meshes[i].nodes = static_cast<const BvhNode4*>(p);
-            meshes[i].max_e12 = b.max_e12;
-            meshes[i].n_nodes = uint32_t(b.nodes.size());
-            meshes[i].n_tris = uint32_t(b.tris.size());
+            set_tree(meshes[i], static_cast<const BvhNode4*>(p), b.max_e12, b.nodes.size(), b.tris.size());
             stack_need = std::max(stack_need, b.stack_need);
             ++n_done;
         }
@@ -431,6 +481,20 @@ int ensure_device(int device) {
     if (device < 0 || device >= n) return fail(RBRT_ERR_INVALID_ARG, "device index out of range");
     HIP_TRY(hipSetDevice(device));
     return RBRT_OK;
+}
+
+// The self tests' three counters: zeroed on device 0, filled by `launch`, handed back in counts. `who`: the hook.
+template <class Launch>
+int device_counts3(const char* who, uint64_t counts[3], Launch launch) {
+    if (int rc = ensure_device(0)) return rc;
+    DevBuf<unsigned long long> d;
+    HIP_TRY(d.alloc(3));
+    hipError_t e = hipMemset(d.get(), 0, 3 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = launch(d.get());
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the counters are copied out as they are");
+    if (e == hipSuccess) e = d.to_host(reinterpret_cast<unsigned long long*>(counts), 3);
+    return hook_result(e, who);
 }
 
 // Device memory that lives as long as the scene (released by rbrt_hip_scene_destroy, never one by one). Called from the
@@ -473,14 +537,16 @@ hipError_t device_build_mesh(const rbrt_mesh_t& m, BvhTri* d_tris_out, uint32_t 
                              const BvhKnobs& knobs, double* upload_s = nullptr) {
     const double t_up0 = now_s();
     const float* src[12] = {m.v0x, m.v0y, m.v0z, m.e1x, m.e1y, m.e1z, m.e2x, m.e2y, m.e2z, m.nx, m.ny, m.nz};
-    float* d_soa = nullptr;
-    uint8_t* d_pad = nullptr;
+    DevBuf<float> soa_buf;
+    DevBuf<uint8_t> pad_buf;
     const size_t stride = (size_t(m.n_total) + 63u) & ~size_t(63);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_soa), stride * 12u * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_pad), m.n_total);
+    hipError_t e = soa_buf.alloc(stride * 12u);
+    if (e == hipSuccess) e = pad_buf.alloc(m.n_total);
+    float* const d_soa = soa_buf.get();
+    uint8_t* const d_pad = pad_buf.get();
     for (int k = 0; k < 12 && e == hipSuccess; ++k)
         e = hipMemcpy(d_soa + stride * k, src[k], size_t(m.n_total) * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_pad, m.is_padding, m.n_total, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = pad_buf.from_host(m.is_padding, m.n_total);
     if (upload_s) *upload_s = now_s() - t_up0;
     if (e == hipSuccess) {
         const DeviceMeshSoa soa = {d_soa, d_soa + stride, d_soa + 2 * stride, d_soa + 3 * stride, d_soa + 4 * stride,
@@ -490,7 +556,6 @@ hipError_t device_build_mesh(const rbrt_mesh_t& m, BvhTri* d_tris_out, uint32_t 
     if (e == hipSuccess && r->ok && d_normals)
         e = device_normals(d_soa + 9 * stride, d_soa + 10 * stride, d_soa + 11 * stride, m.n_total, d_normals, nullptr);
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    (void)hipFree(d_soa), (void)hipFree(d_pad);
     if (e != hipSuccess && r->d_nodes) {
         (void)hipFree(r->d_nodes);
         r->d_nodes = nullptr, r->ok = false;
@@ -1023,10 +1088,13 @@ std::vector<Normal4> smooth_normals_blob(const rbrt_mesh_t& m, const rbrt_mesh_n
     return blob;
 }
 
-int scene_create_impl(const rbrt_scene_t* scene, const rbrt_scene_shading_t* shading, int device, rbrt_hip_scene_t** out,
-                      const CreateHint& hint) {
-    if (!scene || !out) return fail(RBRT_ERR_INVALID_ARG, "scene_create: null argument");
-    *out = nullptr;
+// ---- Scene creation, step by step (scene_create_impl) ----------------------------------------------------------------
+
+// A scene that is destroyed when its scope ends, unless it has been release()d to the caller by then.
+using SceneGuard = std::unique_ptr<rbrt_hip_scene, int (*)(rbrt_hip_scene_t*)>;
+
+// Everything that is wrong with the caller's arrays, found without a device. elems: Scene::elements order.
+int check_scene(const rbrt_scene_t* scene, const rbrt_scene_shading_t* shading, std::vector<uint32_t>& elems) {
     if (scene->n_spheres && !scene->spheres) return fail(RBRT_ERR_INVALID_ARG, "spheres is null");
     if (scene->n_meshes && !scene->meshes) return fail(RBRT_ERR_INVALID_ARG, "meshes is null");
     if (scene->n_triangles && !scene->triangles) return fail(RBRT_ERR_INVALID_ARG, "triangles is null");
@@ -1038,7 +1106,7 @@ int scene_create_impl(const rbrt_scene_t* scene, const rbrt_scene_shading_t* sha
         if (int rc = check_material(scene->triangles[i].mat, "triangle", i)) return rc;
     // Scene::elements order: the given one (every sphere and triangle exactly once), else spheres then triangles
     const uint32_t n_elem = scene->n_spheres + scene->n_triangles;
-    std::vector<uint32_t> elems(n_elem);
+    elems.resize(n_elem);
     for (uint32_t e = 0; e < n_elem; ++e) elems[e] = e < scene->n_spheres ? e : (0x80000000u | (e - scene->n_spheres));
     if (scene->element_order && n_elem) {
         std::vector<uint8_t> seen_s(scene->n_spheres, 0), seen_t(scene->n_triangles, 0);
@@ -1061,298 +1129,329 @@ int scene_create_impl(const rbrt_scene_t* scene, const rbrt_scene_shading_t* sha
                           !m.e2z || !m.nx || !m.ny || !m.nz || !m.is_padding))
             return fail(RBRT_ERR_INVALID_ARG, "mesh array pointer is null");
     }
-    if (int rc = check_shading(*scene, shading)) return rc;
-    const double t_create0 = now_s();
-    if (int rc = ensure_device(device)) return rc;
+    return check_shading(*scene, shading);
+}
 
-    rbrt_hip_scene* s = new rbrt_hip_scene();
-    s->device = device;
-    s->create_times.hip_init_s = now_s() - t_create0;
-    double t_upload = 0.0, t_build = 0.0;
-    s->n_spheres = scene->n_spheres;
-    s->n_meshes = scene->n_meshes;
-    s->n_elem_tris = scene->n_triangles;
-    auto bail = [&](int rc) {
-        rbrt_hip_scene_destroy(s);
-        return rc;
-    };
-#define HIP_TRY_BAIL(expr)                                                                              \
-    do {                                                                                                \
-        hipError_t _e = (expr);                                                                         \
-        if (_e != hipSuccess)                                                                           \
-            return bail(fail(_e == hipErrorOutOfMemory ? RBRT_ERR_OOM : RBRT_ERR_HIP,                   \
-                             std::string(#expr) + ": " + hipGetErrorString(_e)));                       \
-    } while (0)
-
-    for (uint32_t i = 0; i < scene->n_spheres; ++i) {
-        rbrt_hip_scene::Bound b;
+// The objects' bounds, by object id (rbrt_hip_scene::h_bounds).
+std::vector<rbrt_hip_scene::Bound> object_bounds(const rbrt_scene_t& scene) {
+    std::vector<rbrt_hip_scene::Bound> bounds(size_t(scene.n_spheres) + scene.n_triangles + scene.n_meshes);
+    rbrt_hip_scene::Bound* b = bounds.data();
+    for (uint32_t i = 0; i < scene.n_spheres; ++i, ++b)
         for (int c = 0; c < 3; ++c)
-            b.lo[c] = scene->spheres[i].center[c] - scene->spheres[i].radius, b.hi[c] = scene->spheres[i].center[c] + scene->spheres[i].radius;
-        s->h_bounds.push_back(b);
-    }
-    for (uint32_t i = 0; i < scene->n_triangles; ++i) {
-        rbrt_hip_scene::Bound b;
+            b->lo[c] = scene.spheres[i].center[c] - scene.spheres[i].radius, b->hi[c] = scene.spheres[i].center[c] + scene.spheres[i].radius;
+    for (uint32_t i = 0; i < scene.n_triangles; ++i, ++b)
         for (int c = 0; c < 3; ++c) {
-            const float x0 = scene->triangles[i].corners[0][c], x1 = scene->triangles[i].corners[1][c], x2 = scene->triangles[i].corners[2][c];
-            b.lo[c] = std::min(x0, std::min(x1, x2)), b.hi[c] = std::max(x0, std::max(x1, x2));
+            const float x0 = scene.triangles[i].corners[0][c], x1 = scene.triangles[i].corners[1][c], x2 = scene.triangles[i].corners[2][c];
+            b->lo[c] = std::min(x0, std::min(x1, x2)), b->hi[c] = std::max(x0, std::max(x1, x2));
         }
-        s->h_bounds.push_back(b);
-    }
-    for (uint32_t i = 0; i < scene->n_meshes; ++i) {
-        rbrt_hip_scene::Bound b;
-        for (int c = 0; c < 3; ++c) b.lo[c] = scene->meshes[i].bbox_lo[c], b.hi[c] = scene->meshes[i].bbox_hi[c];
-        s->h_bounds.push_back(b);
-    }
-    std::vector<DevSphere> spheres(scene->n_spheres);
-    std::vector<DevTriangle> etris(scene->n_triangles);
-    std::vector<DevMaterial> mats(n_elem + scene->n_meshes);  // [object id]: elements in their order, then meshes
-    auto put_mat = [&](size_t k, const rbrt_material_t& m) {
-        for (int c = 0; c < 3; ++c) mats[k].albedo[c] = m.albedo[c];
-        mats[k].param = m.param;
-        mats[k].kind = dev_material_kind(m.kind);
-    };
+    for (uint32_t i = 0; i < scene.n_meshes; ++i, ++b)
+        for (int c = 0; c < 3; ++c) b->lo[c] = scene.meshes[i].bbox_lo[c], b->hi[c] = scene.meshes[i].bbox_hi[c];
+    return bounds;
+}
+
+DevMaterial dev_material_of(const rbrt_material_t& m) {
+    DevMaterial d{};
+    for (int c = 0; c < 3; ++c) d.albedo[c] = m.albedo[c];
+    d.param = m.param;
+    d.kind = dev_material_kind(m.kind);
+    return d;
+}
+
+// The tables of the elements as the kernels read them.
+struct ElementTables {
+    std::vector<DevSphere> spheres;
+    std::vector<DevTriangle> etris;
+    std::vector<DevMaterial> mats;  // [object id]: elements in their order, then meshes
+};
+ElementTables element_tables(const rbrt_scene_t& scene, const std::vector<uint32_t>& elems) {
+    ElementTables t;
+    t.spheres.resize(scene.n_spheres), t.etris.resize(scene.n_triangles), t.mats.resize(elems.size() + scene.n_meshes);
     // A scene WITHOUT triangle elements is tested by the kernels' sphere-only loop, where element e IS device sphere e (no
     // element table is uploaded): the device array is therefore laid out in Scene::elements order, so that a permuted
     // `element_order` gives every sphere its own material, object id and place in a tie (scene.rs:23-31). With triangle
     // elements the table `elems` names the spheres by their position in the caller's array, which is kept.
-    for (uint32_t i = 0; i < scene->n_spheres; ++i) {
-        const uint32_t src = scene->n_triangles == 0 ? elems[i] : i;
-        for (int c = 0; c < 3; ++c) spheres[i].center[c] = scene->spheres[src].center[c];
-        spheres[i].radius = scene->spheres[src].radius;
+    for (uint32_t i = 0; i < scene.n_spheres; ++i) {
+        const uint32_t src = scene.n_triangles == 0 ? elems[i] : i;
+        for (int c = 0; c < 3; ++c) t.spheres[i].center[c] = scene.spheres[src].center[c];
+        t.spheres[i].radius = scene.spheres[src].radius;
     }
-    for (uint32_t i = 0; i < scene->n_triangles; ++i) {  // BasicTriangle::new (triangle.rs:19-28): edges and normal, f32, unfused
-        const rbrt_triangle_t& t = scene->triangles[i];
-        DevTriangle& o = etris[i];
-        for (int c = 0; c < 3; ++c) o.v0[c] = t.corners[0][c], o.e0[c] = t.corners[1][c] - t.corners[0][c], o.e1[c] = t.corners[2][c] - t.corners[0][c];
+    for (uint32_t i = 0; i < scene.n_triangles; ++i) {  // BasicTriangle::new (triangle.rs:19-28): edges and normal, f32, unfused
+        const rbrt_triangle_t& tr = scene.triangles[i];
+        DevTriangle& o = t.etris[i];
+        for (int c = 0; c < 3; ++c) o.v0[c] = tr.corners[0][c], o.e0[c] = tr.corners[1][c] - tr.corners[0][c], o.e1[c] = tr.corners[2][c] - tr.corners[0][c];
         const float cx = o.e0[1] * o.e1[2] - o.e0[2] * o.e1[1], cy = o.e0[2] * o.e1[0] - o.e0[0] * o.e1[2], cz = o.e0[0] * o.e1[1] - o.e0[1] * o.e1[0];
         const float len = std::sqrt((cx * cx + cy * cy) + cz * cz);  // vec3.rs:111-126: length, then three divisions
         o.normal[0] = cx / len, o.normal[1] = cy / len, o.normal[2] = cz / len;
     }
-    for (uint32_t e = 0; e < n_elem; ++e)
-        put_mat(e, (elems[e] >> 31) ? scene->triangles[elems[e] & 0x7FFFFFFFu].mat : scene->spheres[elems[e]].mat);
-    std::vector<DevMesh> meshes(scene->n_meshes);
-    // One triangle array for the scene (leaf links are absolute positions in it): mesh i owns the records
-    // [tri_base[i], tri_base[i] + cap[i]), cap = what its builder can emit at most (bvh.h bvh_record_capacity: the scan-visible
-    // entries, the host builder's duplicated references, a dummy).
-    std::vector<uint32_t> tri_base(scene->n_meshes, 0);
-    uint64_t tri_total = 0;
-    for (uint32_t i = 0; i < scene->n_meshes; ++i) {
+    for (size_t e = 0; e < elems.size(); ++e)
+        t.mats[e] = dev_material_of((elems[e] >> 31) ? scene.triangles[elems[e] & 0x7FFFFFFFu].mat : scene.spheres[elems[e]].mat);
+    for (uint32_t i = 0; i < scene.n_meshes; ++i) t.mats[elems.size() + i] = dev_material_of(scene.meshes[i].mat);
+    return t;
+}
+
+// One triangle array for the scene (leaf links are absolute positions in it): mesh i owns the records
+// [tri_base[i], tri_base[i] + cap[i]), cap = what its builder can emit at most (bvh.h bvh_record_capacity: the scan-visible
+// entries, the host builder's duplicated references, a dummy).
+int alloc_records(rbrt_hip_scene* s, const rbrt_scene_t& scene, std::vector<uint32_t>& tri_base, uint64_t& tri_total) {
+    tri_base.assign(scene.n_meshes, 0);
+    tri_total = 0;
+    for (uint32_t i = 0; i < scene.n_meshes; ++i) {
         tri_base[i] = uint32_t(tri_total);
-        tri_total += bvh_record_capacity(scene->meshes[i].n_total);
-        if (tri_total >= (1ull << 25)) return bail(fail(RBRT_ERR_UNSUPPORTED, "more than 2^25 triangle records in one scene"));
+        tri_total += bvh_record_capacity(scene.meshes[i].n_total);
+        if (tri_total >= (1ull << 25)) return fail(RBRT_ERR_UNSUPPORTED, "more than 2^25 triangle records in one scene");
     }
-    {
-        void* p = nullptr;
-        const size_t bytes = std::max<size_t>(size_t(tri_total) * sizeof(BvhTri), 64);
-        HIP_TRY_BAIL(dev_alloc(s, bytes, &p));
-        s->d_tris = static_cast<BvhTri*>(p);  // (records no leaf points at are never read: left as they are)
-    }
-    // Builder of each mesh's first tree: whichever costs this call less (device_builder_is_cheaper), the host's tree
-    // following in the background for a handle (struct Refine); RBRT_BVH_BUILDER = host | device forces one and nothing
-    // follows. The device builder declines what it does not handle (tiny meshes, a tree deeper than the traversal stack
-    // allows) and the host builder takes over.
-    int builder_mode = 0;  // 0 by cost, 1 host, 2 device
-    if (const char* e = std::getenv("RBRT_BVH_BUILDER")) builder_mode = !std::strcmp(e, "host") ? 1 : !std::strcmp(e, "device") ? 2 : 0;
-    bool refine_allowed = builder_mode == 0 && !hint.one_shot;
-    s->one_shot = hint.one_shot;
-    if (const char* e = std::getenv("RBRT_BVH_REFINE")) refine_allowed = refine_allowed && e[0] != '0';
-    uint32_t device_min_tris = 0;  // (lab: a threshold on the entry count instead of the cost rule)
+    void* p = nullptr;
+    HIP_TRY(dev_alloc(s, std::max<size_t>(size_t(tri_total) * sizeof(BvhTri), 64), &p));
+    s->d_tris = static_cast<BvhTri*>(p);  // (records no leaf points at are never read: left as they are)
+    return RBRT_OK;
+}
+
+// Builder of each mesh's first tree: whichever costs this call less (device_builder_is_cheaper), the host's tree
+// following in the background for a handle (struct Refine); RBRT_BVH_BUILDER = host | device forces one and nothing
+// follows. The device builder declines what it does not handle (tiny meshes, a tree deeper than the traversal stack
+// allows) and the host builder takes over.
+struct BuilderChoice {
+    int mode = 0;  // 0 by cost, 1 host, 2 device
+    bool refine_allowed = false;
+    uint32_t device_min = 0;  // (lab: a threshold on the entry count instead of the cost rule)
     bool device_min_set = false;
-    BvhKnobs bvh_knobs;
-    {
-        std::string err;
-        if (!lab_u32("RBRT_BVH_DEVICE_MIN", 0, 1ll << 30, device_min_tris, err) || !lab_bvh_knobs(bvh_knobs, err))
-            return bail(fail(RBRT_ERR_INVALID_ARG, err));
-        device_min_set = lab_env("RBRT_BVH_DEVICE_MIN") != nullptr;
+    BvhKnobs knobs;
+    bool wants_device(uint32_t n_total, const CreateHint& hint) const {
+        if (mode != 0) return mode == 2;
+        return device_min_set ? n_total >= device_min : device_builder_is_cheaper(n_total, hint);
     }
+};
+int read_builder_choice(const CreateHint& hint, BuilderChoice& c) {
+    if (const char* e = std::getenv("RBRT_BVH_BUILDER")) c.mode = !std::strcmp(e, "host") ? 1 : !std::strcmp(e, "device") ? 2 : 0;
+    c.refine_allowed = c.mode == 0 && !hint.one_shot;
+    if (const char* e = std::getenv("RBRT_BVH_REFINE")) c.refine_allowed = c.refine_allowed && e[0] != '0';
+    std::string err;
+    if (!lab_u32("RBRT_BVH_DEVICE_MIN", 0, 1ll << 30, c.device_min, err) || !lab_bvh_knobs(c.knobs, err))
+        return fail(RBRT_ERR_INVALID_ARG, err);
+    c.device_min_set = lab_env("RBRT_BVH_DEVICE_MIN") != nullptr;
+    return RBRT_OK;
+}
+
+// What build_mesh made of one mesh, for scene_create to enter in the mesh table and to add to the scene's totals.
+struct MeshBuilt {
+    DevMesh dm{};
+    bool device_built = false;  // the GPU built the tree: dm.n_tris is then the builder's count of indexed triangles
+    uint32_t stack_need = 1;
+    double upload_s = 0.0, build_s = 0.0;
+};
+
+// One mesh: its normals (mn: the corner normals of a smooth mesh, or null), its tree by the builder `choice` names -- the
+// host's where the device builder declines --, its records at tri_base of the scene's array and its entry of the mesh table.
+int build_mesh(rbrt_hip_scene* s, const rbrt_mesh_t& m, const rbrt_mesh_normals_t* mn, uint32_t tri_base, const BuilderChoice& choice,
+               const CreateHint& hint, MeshBuilt& out) {
+    DevMesh& dm = out.dm;
+    const bool smooth = mn && m.n_total != 0;
+    void* p = nullptr;
+    HIP_TRY(dev_alloc(s, std::max<size_t>(size_t(m.n_total) * (sizeof(Normal4) + (smooth ? sizeof(SmoothRec) : 0)), 16), &p));
+    Normal4* const d_normals = static_cast<Normal4*>(p);
+    if (choice.wants_device(m.n_total, hint) && m.n_total >= 8) {
+        DeviceBvhResult r;
+        const double tb0 = now_s();
+        const hipError_t e = device_build_mesh(m, s->d_tris + tri_base, tri_base, d_normals, &r, choice.knobs, &out.upload_s);
+        out.build_s = now_s() - tb0 - out.upload_s;
+        if (e != hipSuccess) return hip_fail(e, "device BVH build");
+        if (r.ok) {
+            s->allocs.push_back(r.d_nodes);
+            set_tree(dm, r.d_nodes, r.max_e12, r.n_nodes, r.n_valid);
+            out.stack_need = 3u * (r.max_depth + 1u) + 1u;
+            out.device_built = true;
+        }
+    }
+    if (!out.device_built) {
+        const double tb0 = now_s();
+        BvhBuildResult bvh = build_bvh(m, choice.knobs.host);
+        rebase_leaf_links(bvh.nodes, tri_base);
+        std::vector<Normal4> normals;
+        if (smooth) {
+            normals = smooth_normals_blob(m, *mn);
+        } else {
+            normals.resize(m.n_total);
+            for (uint32_t k = 0; k < m.n_total; ++k) normals[k] = Normal4{m.nx[k], m.ny[k], m.nz[k], 0.0f};
+        }
+        const double tb1 = now_s();
+        BvhNode4* d_nodes = nullptr;
+        if (int rc = upload(s, bvh.nodes, &d_nodes)) return rc;
+        if (!bvh.tris.empty())
+            HIP_TRY(hipMemcpy(s->d_tris + tri_base, bvh.tris.data(), bvh.tris.size() * sizeof(BvhTri), hipMemcpyHostToDevice));
+        if (!normals.empty())
+            HIP_TRY(hipMemcpy(d_normals, normals.data(), normals.size() * sizeof(Normal4), hipMemcpyHostToDevice));
+        out.build_s += tb1 - tb0, out.upload_s += now_s() - tb1;
+        set_tree(dm, d_nodes, bvh.max_e12, bvh.nodes.size(), bvh.tris.size());
+        out.stack_need = bvh.stack_need;
+    } else if (smooth) {  // (the device builder wrote the flat Normal4s and has synchronised: the smooth ones replace them)
+        const double tu0 = now_s();
+        const std::vector<Normal4> blob = smooth_normals_blob(m, *mn);
+        HIP_TRY(hipMemcpy(d_normals, blob.data(), blob.size() * sizeof(Normal4), hipMemcpyHostToDevice));
+        out.upload_s += now_s() - tu0;
+    }
+    dm.tris = s->d_tris, dm.normals = d_normals;
+    float diag2 = 0.0f;
+    for (int c = 0; c < 3; ++c) {
+        dm.bbox_lo[c] = m.bbox_lo[c];
+        dm.bbox_hi[c] = m.bbox_hi[c];
+        dm.center[c] = 0.5f * m.bbox_lo[c] + 0.5f * m.bbox_hi[c];
+        float h = 0.5f * m.bbox_hi[c] - 0.5f * m.bbox_lo[c];
+        diag2 += h * h;
+    }
+    // Radius bounds |v - center| for every indexed vertex; padded a little for its own rounding.
+    dm.radius = std::sqrt(diag2) * 1.0001f;
+    if (!std::isfinite(dm.radius)) dm.radius = std::numeric_limits<float>::max();
+    return RBRT_OK;
+}
+
+// The scene's tables on the device, and its counters at zero.
+int upload_scene_tables(rbrt_hip_scene* s, const ElementTables& t, const std::vector<uint32_t>& elems, const std::vector<DevMesh>& meshes) {
+    if (int rc = upload(s, t.spheres, &s->d_spheres)) return rc;
+    if (s->n_elem_tris != 0) {
+        if (int rc = upload(s, t.etris, &s->d_elem_tris)) return rc;
+        if (int rc = upload(s, elems, &s->d_elems)) return rc;
+    }
+    if (int rc = upload(s, t.mats, &s->d_materials)) return rc;
+    if (int rc = upload(s, meshes, &s->d_meshes)) return rc;
+    return upload(s, std::vector<DevCounters>(1), &s->d_counters);  // (value-initialised: all zero)
+}
+
+// The lab knobs of a scene's launches (include/rbrt_hip_debug.h). waves_per_cu: RBRT_WAVES_PER_CU, 0 when not given.
+int read_scene_knobs(rbrt_hip_scene* s, uint32_t& waves_per_cu) {
+    std::string err;
+    uint32_t poison = 0, stripes = s->work_stripes, stripes_overlap = s->work_stripes_overlap;
+    uint32_t trace_launches = 0, trace_create = 0;
+    const bool knobs_ok =
+        lab_u32("RBRT_LDS_STACK", 1, kStackMax, s->stack_entries, err) &&
+        lab_u32("RBRT_LEAF_ROUND", 1, 64, s->leaf_round, err) && lab_u32("RBRT_Y_HIGH", 1, 64, s->y_high_water, err) &&
+        lab_u32("RBRT_Y_HIGH_PARKED", 1, 256, s->y_high_min_parked, err) && lab_u32("RBRT_Y_LOW", 1, 64, s->y_low_water, err) &&
+        lab_u32("RBRT_WAVES_PER_CU", 1, 32, waves_per_cu, err) && lab_u32("RBRT_LEAF_LEAVES", 1, 128, s->leaf_leaves, err) &&
+        lab_u32("RBRT_SHARE_IDLE", 0, 64, s->share_idle, err) && lab_u32("RBRT_WORK_STRIPES", 0, 65536, stripes, err) &&
+        lab_u32("RBRT_WORK_STRIPES_OVERLAP", 0, 65536, stripes_overlap, err) &&
+        lab_u32("RBRT_SHADE_ROUNDS", 1, kMaxShadeRounds, s->shade_rounds, err) &&
+        lab_u32("RBRT_SHADE_CONT_MIN", 1, 64, s->shade_cont_min, err) && lab_u32("RBRT_PIPELINE", 0, kMaxPipeline, s->pipeline, err) &&
+        lab_u32("RBRT_POISON_SAMPLES", 0, 1, poison, err) && lab_u32("RBRT_PRIMARY_CULL", 0, 1, s->primary_cull, err) &&
+        lab_u32("RBRT_OVERLAP_WAVES_PER_CU", 0, 16, s->overlap_waves_per_cu, err) && lab_u32("RBRT_TILE_TAIL_DIV", 1, 1024, s->tile_tail_div, err) &&
+        lab_u32("RBRT_HELPERS", 0, 2, s->helpers_mode, err) && lab_u32("RBRT_HELPER_MIN_ITEMS", 1, 1 << 24, s->helper_min_items, err) &&
+        lab_u32("RBRT_HELPER_MIN_LAUNCH_MI", 0, 4096, s->helper_min_launch_mi, err) && lab_u32("RBRT_HELPER_MIN_FREE", 1, 16, s->helper_min_free_per_cu, err) &&
+        lab_u32("RBRT_HELPER_ROUNDS", 1, 16, s->helper_rounds, err) && lab_u32("RBRT_TRACE_LAUNCHES", 0, 1, trace_launches, err) &&
+        lab_u32("RBRT_TRACE_CREATE", 0, 1, trace_create, err);
+    if (!knobs_ok) return fail(RBRT_ERR_INVALID_ARG, err);
+    s->trace_launches = trace_launches != 0u, s->trace_create = trace_create != 0u;
+    if ((stripes & (stripes - 1u)) != 0u || (stripes_overlap != kStripesAuto && (stripes_overlap & (stripes_overlap - 1u)) != 0u))  // the kernel shifts
+        return fail(RBRT_ERR_INVALID_ARG, "lab knob RBRT_WORK_STRIPES / RBRT_WORK_STRIPES_OVERLAP must be 0 or a power of two");
+    s->work_stripes = stripes, s->work_stripes_overlap = stripes_overlap;
+    s->poison_samples = poison != 0;
+    return RBRT_OK;
+}
+
+// The persistent grid of the scene's launches and the per-wave scratch that goes with it.
+int size_grid(rbrt_hip_scene* s, int device, uint32_t waves_per_cu) {
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return fail(RBRT_ERR_HIP, "hipGetDeviceProperties failed");
+    const int cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    if (s->stack_entries > s->stack_need) s->stack_entries = s->stack_need;
+    // resident waves per CU: LDS-limited (160 KiB per CU), at most 5 per SIMD (VGPR budget). (A thin-lens launch stages 32
+    // bytes more; where that costs it a wave per CU the waves of the grid beyond the resident ones start as others end.)
+    int per_cu = int((160u * 1024u) / megakernel_lds_bytes(s->stack_entries, s->n_spheres, s->n_meshes, s->n_elem_tris, 0u));
+    if (per_cu > 20) per_cu = 20;
+    if (per_cu < 1) per_cu = 1;
+    if (waves_per_cu != 0) per_cu = int(waves_per_cu), s->waves_fixed = true;
+    s->n_waves = uint32_t(cus * per_cu);
+    s->n_cus = uint32_t(cus);
+    s->hw_queues = g_hw_queues_at_load;
+    // per-wave scratch is indexed by workgroup (= wave): no grid is larger than n_waves; two more waves per CU for helper
+    // launches behind a full grid (a blocking caller's launch under RBRT_HELPERS=2)
+    s->scratch_waves = s->n_waves + 2u * s->n_cus;
+    return RBRT_OK;
+}
+
+// the host builder's tree of the device-built meshes, in the background (struct Refine)
+void start_refine(rbrt_hip_scene* s, int device, uint64_t tri_total, const std::vector<DevMesh>& meshes, const std::vector<uint32_t>& tri_base,
+                  const std::vector<uint32_t>& n_valid, const std::vector<uint8_t>& device_built, const BvhBuildOptions& shape) {
+    std::unique_ptr<Refine> r(new Refine());
+    r->device = device;
+    r->d_tris = s->d_tris, r->tri_total = size_t(tri_total);
+    r->meshes = meshes, r->tri_base = tri_base, r->n_valid = n_valid, r->wanted = device_built;
+    const unsigned hc = std::thread::hardware_concurrency();
+    r->max_threads = std::max(1u, hc / 2u);  // (the caller's thread goes on issuing launches)
+    r->shape = shape;
+    Refine* rp = r.get();
+    try {
+        r->th = std::thread([rp]() {
+            try {
+                rp->run();
+            } catch (...) {  // (no memory for the copy of the records or for the tree: the device's trees stay)
+                for (void* p : rp->allocs) (void)hipFree(p);
+                rp->allocs.clear();
+                rp->error = "out of host memory";
+                rp->state.store(2, std::memory_order_release);
+            }
+        });
+        s->refine = std::move(r);
+    } catch (...) {  // (no thread to be had: the device's tree stays)
+    }
+}
+
+int scene_create_impl(const rbrt_scene_t* scene, const rbrt_scene_shading_t* shading, int device, rbrt_hip_scene_t** out,
+                      const CreateHint& hint) {
+    if (!scene || !out) return fail(RBRT_ERR_INVALID_ARG, "scene_create: null argument");
+    *out = nullptr;
+    std::vector<uint32_t> elems;
+    if (int rc = check_scene(scene, shading, elems)) return rc;
+    const double t_create0 = now_s();
+    if (int rc = ensure_device(device)) return rc;
+
+    SceneGuard s(new rbrt_hip_scene(), rbrt_hip_scene_destroy);  // (destroyed by every return below but the last)
+    s->device = device;
+    s->one_shot = hint.one_shot;
+    s->create_times.hip_init_s = now_s() - t_create0;
+    s->n_spheres = scene->n_spheres, s->n_meshes = scene->n_meshes, s->n_elem_tris = scene->n_triangles;
+    s->h_bounds = object_bounds(*scene);
+    const ElementTables tables = element_tables(*scene, elems);
+    std::vector<uint32_t> tri_base;
+    uint64_t tri_total = 0;
+    if (int rc = alloc_records(s.get(), *scene, tri_base, tri_total)) return rc;
+    BuilderChoice choice;
+    if (int rc = read_builder_choice(hint, choice)) return rc;
+    std::vector<DevMesh> meshes(scene->n_meshes);
     std::vector<uint8_t> device_built(scene->n_meshes, 0);
     std::vector<uint32_t> n_valid_of(scene->n_meshes, 0);
+    double t_upload = 0.0, t_build = 0.0;
     const double t_meshes0 = now_s();
     for (uint32_t i = 0; i < scene->n_meshes; ++i) {
-        const rbrt_mesh_t& m = scene->meshes[i];
-        put_mat(n_elem + i, m.mat);
-        DevMesh& dm = meshes[i];
-        Normal4* d_normals = nullptr;
-        const bool smooth = mesh_is_smooth(shading, i) && m.n_total != 0;
-        {
-            void* p = nullptr;
-            const size_t per_entry = sizeof(Normal4) + (smooth ? sizeof(SmoothRec) : 0);
-            HIP_TRY_BAIL(dev_alloc(s, std::max<size_t>(size_t(m.n_total) * per_entry, 16), &p));
-            d_normals = static_cast<Normal4*>(p);
-        }
-        bool built = false;
-        const bool try_device = builder_mode == 2 || (builder_mode == 0 && (device_min_set ? m.n_total >= device_min_tris
-                                                                                           : device_builder_is_cheaper(m.n_total, hint)));
-        if (try_device && m.n_total >= 8) {
-            DeviceBvhResult r;
-            const double tb0 = now_s();
-            double up = 0.0;
-            const hipError_t e = device_build_mesh(m, s->d_tris + tri_base[i], tri_base[i], d_normals, &r, bvh_knobs, &up);
-            t_upload += up, t_build += now_s() - tb0 - up;
-            if (e != hipSuccess)
-                return bail(fail(e == hipErrorOutOfMemory ? RBRT_ERR_OOM : RBRT_ERR_HIP, std::string("device BVH build: ") + hipGetErrorString(e)));
-            if (r.ok) {
-                s->allocs.push_back(r.d_nodes);
-                dm.nodes = r.d_nodes;
-                dm.max_e12 = r.max_e12;
-                dm.n_nodes = r.n_nodes;
-                dm.n_tris = r.n_valid;
-                s->stack_need = std::max(s->stack_need, 3u * (r.max_depth + 1u) + 1u);
-                s->total_nodes += r.n_nodes;
-                s->total_tris += r.n_valid;
-                s->n_device_built += 1;
-                device_built[i] = 1, n_valid_of[i] = r.n_valid;
-                built = true;
-            }
-        }
-        if (!built) {
-            const double tb0 = now_s();
-            BvhBuildResult bvh = build_bvh(m, bvh_knobs.host);
-            if (tri_base[i] != 0)
-                for (BvhNode4& nd : bvh.nodes)
-                    for (int c = 0; c < 4; ++c)
-                        if (nd.child[c] < 0 && nd.child[c] != kNoChild) {
-                            const uint32_t leaf = uint32_t(~nd.child[c]);
-                            nd.child[c] = ~int32_t((((leaf >> kLeafBits) + tri_base[i]) << kLeafBits) | (leaf & uint32_t(kLeafMax - 1)));
-                        }
-            std::vector<Normal4> normals;
-            if (smooth) {
-                normals = smooth_normals_blob(m, shading->meshes[i]);
-            } else {
-                normals.resize(m.n_total);
-                for (uint32_t k = 0; k < m.n_total; ++k) normals[k] = Normal4{m.nx[k], m.ny[k], m.nz[k], 0.0f};
-            }
-            const double tb1 = now_s();
-            BvhNode4* d_nodes = nullptr;
-            if (int rc = upload(s, bvh.nodes, &d_nodes)) return bail(rc);
-            if (!bvh.tris.empty())
-                HIP_TRY_BAIL(hipMemcpy(s->d_tris + tri_base[i], bvh.tris.data(), bvh.tris.size() * sizeof(BvhTri), hipMemcpyHostToDevice));
-            if (!normals.empty())
-                HIP_TRY_BAIL(hipMemcpy(d_normals, normals.data(), normals.size() * sizeof(Normal4), hipMemcpyHostToDevice));
-            t_build += tb1 - tb0, t_upload += now_s() - tb1;
-            dm.nodes = d_nodes;
-            dm.max_e12 = bvh.max_e12;
-            dm.n_nodes = uint32_t(bvh.nodes.size());
-            dm.n_tris = uint32_t(bvh.tris.size());
-            s->stack_need = std::max(s->stack_need, bvh.stack_need);
-            s->total_nodes += bvh.nodes.size();
-            s->total_tris += bvh.tris.size();
-        }
-        if (built && smooth) {  // (the device builder wrote the flat Normal4s and has synchronised: the smooth ones replace them)
-            const double tu0 = now_s();
-            const std::vector<Normal4> blob = smooth_normals_blob(m, shading->meshes[i]);
-            HIP_TRY_BAIL(hipMemcpy(d_normals, blob.data(), blob.size() * sizeof(Normal4), hipMemcpyHostToDevice));
-            t_upload += now_s() - tu0;
-        }
-        dm.tris = s->d_tris, dm.normals = d_normals;
-        float diag2 = 0.0f;
-        for (int c = 0; c < 3; ++c) {
-            dm.bbox_lo[c] = m.bbox_lo[c];
-            dm.bbox_hi[c] = m.bbox_hi[c];
-            dm.center[c] = 0.5f * m.bbox_lo[c] + 0.5f * m.bbox_hi[c];
-            float h = 0.5f * m.bbox_hi[c] - 0.5f * m.bbox_lo[c];
-            diag2 += h * h;
-        }
-        // Radius bounds |v - center| for every indexed vertex; padded a little for its own rounding.
-        dm.radius = std::sqrt(diag2) * 1.0001f;
-        if (!std::isfinite(dm.radius)) dm.radius = std::numeric_limits<float>::max();
+        MeshBuilt b;
+        if (int rc = build_mesh(s.get(), scene->meshes[i], mesh_is_smooth(shading, i) ? &shading->meshes[i] : nullptr, tri_base[i], choice, hint, b))
+            return rc;
+        meshes[i] = b.dm;
+        t_upload += b.upload_s, t_build += b.build_s;
+        s->stack_need = std::max(s->stack_need, b.stack_need);
+        s->total_nodes += b.dm.n_nodes, s->total_tris += b.dm.n_tris;
+        if (b.device_built) s->n_device_built += 1, device_built[i] = 1, n_valid_of[i] = b.dm.n_tris;
     }
     const double t_meshes1 = now_s();
-    if (int rc = upload(s, spheres, &s->d_spheres)) return bail(rc);
-    if (scene->n_triangles != 0) {
-        if (int rc = upload(s, etris, &s->d_elem_tris)) return bail(rc);
-        if (int rc = upload(s, elems, &s->d_elems)) return bail(rc);
-    }
-    if (int rc = upload(s, mats, &s->d_materials)) return bail(rc);
-    if (int rc = upload(s, meshes, &s->d_meshes)) return bail(rc);
-    {
-        std::vector<DevCounters> z(1);
-        std::memset(z.data(), 0, sizeof(DevCounters));
-        if (int rc = upload(s, z, &s->d_counters)) return bail(rc);
-    }
-    {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, device) != hipSuccess) return bail(fail(RBRT_ERR_HIP, "hipGetDeviceProperties failed"));
-        int cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-        std::string err;
-        uint32_t waves_per_cu = 0, poison = 0, stripes = s->work_stripes, stripes_overlap = s->work_stripes_overlap;
-        uint32_t trace_launches = 0, trace_create = 0;
-        const bool knobs_ok =
-            lab_u32("RBRT_LDS_STACK", 1, kStackMax, s->stack_entries, err) &&
-            lab_u32("RBRT_LEAF_ROUND", 1, 64, s->leaf_round, err) && lab_u32("RBRT_Y_HIGH", 1, 64, s->y_high_water, err) &&
-            lab_u32("RBRT_Y_HIGH_PARKED", 1, 256, s->y_high_min_parked, err) && lab_u32("RBRT_Y_LOW", 1, 64, s->y_low_water, err) &&
-            lab_u32("RBRT_WAVES_PER_CU", 1, 32, waves_per_cu, err) && lab_u32("RBRT_LEAF_LEAVES", 1, 128, s->leaf_leaves, err) &&
-            lab_u32("RBRT_SHARE_IDLE", 0, 64, s->share_idle, err) && lab_u32("RBRT_WORK_STRIPES", 0, 65536, stripes, err) &&
-            lab_u32("RBRT_WORK_STRIPES_OVERLAP", 0, 65536, stripes_overlap, err) &&
-            lab_u32("RBRT_SHADE_ROUNDS", 1, kMaxShadeRounds, s->shade_rounds, err) &&
-            lab_u32("RBRT_SHADE_CONT_MIN", 1, 64, s->shade_cont_min, err) && lab_u32("RBRT_PIPELINE", 0, kMaxPipeline, s->pipeline, err) &&
-            lab_u32("RBRT_POISON_SAMPLES", 0, 1, poison, err) && lab_u32("RBRT_PRIMARY_CULL", 0, 1, s->primary_cull, err) &&
-            lab_u32("RBRT_OVERLAP_WAVES_PER_CU", 0, 16, s->overlap_waves_per_cu, err) && lab_u32("RBRT_TILE_TAIL_DIV", 1, 1024, s->tile_tail_div, err) &&
-            lab_u32("RBRT_HELPERS", 0, 2, s->helpers_mode, err) && lab_u32("RBRT_HELPER_MIN_ITEMS", 1, 1 << 24, s->helper_min_items, err) &&
-            lab_u32("RBRT_HELPER_MIN_LAUNCH_MI", 0, 4096, s->helper_min_launch_mi, err) && lab_u32("RBRT_HELPER_MIN_FREE", 1, 16, s->helper_min_free_per_cu, err) &&
-            lab_u32("RBRT_HELPER_ROUNDS", 1, 16, s->helper_rounds, err) && lab_u32("RBRT_TRACE_LAUNCHES", 0, 1, trace_launches, err) &&
-            lab_u32("RBRT_TRACE_CREATE", 0, 1, trace_create, err);
-        if (!knobs_ok) return bail(fail(RBRT_ERR_INVALID_ARG, err));
-        s->trace_launches = trace_launches != 0u, s->trace_create = trace_create != 0u;
-        if ((stripes & (stripes - 1u)) != 0u || (stripes_overlap != kStripesAuto && (stripes_overlap & (stripes_overlap - 1u)) != 0u))  // the kernel shifts
-            return bail(fail(RBRT_ERR_INVALID_ARG, "lab knob RBRT_WORK_STRIPES / RBRT_WORK_STRIPES_OVERLAP must be 0 or a power of two"));
-        s->work_stripes = stripes, s->work_stripes_overlap = stripes_overlap;
-        s->poison_samples = poison != 0;
-        if (s->stack_entries > s->stack_need) s->stack_entries = s->stack_need;
-        // resident waves per CU: LDS-limited (160 KiB per CU), at most 5 per SIMD (VGPR budget). (A thin-lens launch stages 32
-        // bytes more; where that costs it a wave per CU the waves of the grid beyond the resident ones start as others end.)
-        int per_cu = int((160u * 1024u) / megakernel_lds_bytes(s->stack_entries, s->n_spheres, s->n_meshes, s->n_elem_tris, 0u));
-        if (per_cu > 20) per_cu = 20;
-        if (per_cu < 1) per_cu = 1;
-        if (waves_per_cu != 0) per_cu = int(waves_per_cu), s->waves_fixed = true;
-        s->n_waves = uint32_t(cus * per_cu);
-        s->n_cus = uint32_t(cus);
-        s->hw_queues = g_hw_queues_at_load;
-        // per-wave scratch is indexed by workgroup (= wave): no grid is larger than n_waves; two more waves per CU for helper
-        // launches behind a full grid (a blocking caller's launch under RBRT_HELPERS=2)
-        s->scratch_waves = s->n_waves + 2u * s->n_cus;
-        // lanes up front: rbrt_hip_render_device then never allocates lanes (which synchronises the device); a one-shot
-        // call makes the lanes its batches will use (rbrt_hip_render)
-        const double t_lanes0 = now_s();
-        if (s->trace_create)
-            std::fprintf(stderr, "[rbrt_hip] scene_create: device %.3f ms, record array %.3f, meshes %.3f (upload %.3f, build %.3f), tables + properties %.3f\n",
-                         s->create_times.hip_init_s * 1e3, (t_meshes0 - t_create0 - s->create_times.hip_init_s) * 1e3, (t_meshes1 - t_meshes0) * 1e3,
-                         t_upload * 1e3, t_build * 1e3, (t_lanes0 - t_meshes1) * 1e3);
-        if (int rc = ensure_lanes(s, std::max(hint.one_shot ? 1u : kLanesAtCreate, s->pipeline))) return bail(rc);
-        // (the library's device code, loaded now instead of inside the first render)
-        if (launch_code_load(nullptr) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
-            return bail(fail(RBRT_ERR_HIP, "the library's device code does not load on this GPU (built for gfx950)"));
-        s->create_times.lanes_s = now_s() - t_lanes0;
-    }
-    // the host builder's tree of the device-built meshes, in the background (struct Refine)
-    if (refine_allowed && s->n_device_built != 0) {
-        std::unique_ptr<Refine> r(new Refine());
-        r->device = device;
-        r->d_tris = s->d_tris, r->tri_total = size_t(tri_total);
-        r->meshes = meshes, r->tri_base = tri_base, r->n_valid = n_valid_of, r->wanted = device_built;
-        const unsigned hc = std::thread::hardware_concurrency();
-        r->max_threads = std::max(1u, hc / 2u);  // (the caller's thread goes on issuing launches)
-        r->shape = bvh_knobs.host;
-        Refine* rp = r.get();
-        try {
-            r->th = std::thread([rp]() {
-                try {
-                    rp->run();
-                } catch (...) {  // (no memory for the copy of the records or for the tree: the device's trees stay)
-                    for (void* p : rp->allocs) (void)hipFree(p);
-                    rp->allocs.clear();
-                    rp->error = "out of host memory";
-                    rp->state.store(2, std::memory_order_release);
-                }
-            });
-            s->refine = std::move(r);
-        } catch (...) {  // (no thread to be had: the device's tree stays)
-        }
-    }
+    if (int rc = upload_scene_tables(s.get(), tables, elems, meshes)) return rc;
+    uint32_t waves_per_cu = 0;
+    if (int rc = read_scene_knobs(s.get(), waves_per_cu)) return rc;
+    if (int rc = size_grid(s.get(), device, waves_per_cu)) return rc;
+    // lanes up front: rbrt_hip_render_device then never allocates lanes (which synchronises the device); a one-shot
+    // call makes the lanes its batches will use (rbrt_hip_render)
+    const double t_lanes0 = now_s();
+    if (s->trace_create)
+        std::fprintf(stderr, "[rbrt_hip] scene_create: device %.3f ms, record array %.3f, meshes %.3f (upload %.3f, build %.3f), tables + properties %.3f\n",
+                     s->create_times.hip_init_s * 1e3, (t_meshes0 - t_create0 - s->create_times.hip_init_s) * 1e3, (t_meshes1 - t_meshes0) * 1e3,
+                     t_upload * 1e3, t_build * 1e3, (t_lanes0 - t_meshes1) * 1e3);
+    if (int rc = ensure_lanes(s.get(), std::max(hint.one_shot ? 1u : kLanesAtCreate, s->pipeline))) return rc;
+    // (the library's device code, loaded now instead of inside the first render)
+    if (launch_code_load(nullptr) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+        return fail(RBRT_ERR_HIP, "the library's device code does not load on this GPU (built for gfx950)");
+    s->create_times.lanes_s = now_s() - t_lanes0;
+    if (choice.refine_allowed && s->n_device_built != 0)
+        start_refine(s.get(), device, tri_total, meshes, tri_base, n_valid_of, device_built, choice.knobs.host);
     s->create_times.upload_s = t_upload, s->create_times.bvh_build_s = t_build;
     s->create_times.meshes_device_built = s->n_device_built, s->create_times.meshes_host_built = s->n_meshes - s->n_device_built;
     s->create_times.create_s = now_s() - t_create0;
-    *out = s;
+    *out = s.release();
     return RBRT_OK;
 }
 
@@ -2041,6 +2140,7 @@ int rbrt_hip_render_shaded(const rbrt_camera_t* cam, const rbrt_scene_t* scene, 
         hint.render_s_est = double(cam->img_width_pix) * cam->img_height_pix * opts->spp / w1 / 10.0e9;
     }
     if (int rc = scene_create_impl(scene, shading, 0, &s, hint)) return rc;
+    SceneGuard guard(s, rbrt_hip_scene_destroy);  // (the images are the scene's memory: dev_alloc)
     times = s->create_times;
     if (s->pipeline == 0) s->pipeline = 3;  // (the batches of this one render overlap on three lanes)
     const double t_render0 = now_s();
@@ -2051,42 +2151,24 @@ int rbrt_hip_render_shaded(const rbrt_camera_t* cam, const rbrt_scene_t* scene, 
                              : npix_img;
     float* d_rad = nullptr;
     uint8_t* d_rgb = nullptr;
-    int rc = RBRT_OK;
-    auto cleanup = [&]() { rbrt_hip_scene_destroy(s); };  // (the images are the scene's memory: dev_alloc)
-#define TRY_OR_CLEAN(expr)                                                                  \
-    do {                                                                                    \
-        hipError_t _e = (expr);                                                             \
-        if (_e != hipSuccess) {                                                             \
-            cleanup();                                                                      \
-            return fail(_e == hipErrorOutOfMemory ? RBRT_ERR_OOM : RBRT_ERR_HIP,            \
-                        std::string(#expr) + ": " + hipGetErrorString(_e));                 \
-        }                                                                                   \
-    } while (0)
-    if (n_out == 0) {
-        cleanup();
-        return RBRT_OK;
-    }
+    if (n_out == 0) return RBRT_OK;
     {
         void* p = nullptr;
         const size_t rad_bytes = (n_out * 3 * sizeof(float) + kSlabAlign - 1) & ~(kSlabAlign - 1);
-        TRY_OR_CLEAN(dev_alloc(s, rad_bytes + (out_rgb8 ? n_out * 3 : 0), &p));
+        HIP_TRY(dev_alloc(s, rad_bytes + (out_rgb8 ? n_out * 3 : 0), &p));
         d_rad = static_cast<float*>(p);
         if (out_rgb8) d_rgb = static_cast<uint8_t*>(p) + rad_bytes;
     }
-    rc = rbrt_hip_render_device(s, cam, opts, nullptr, d_rad, d_rgb);
-    if (rc) {
-        cleanup();
-        return rc;
-    }
-    TRY_OR_CLEAN(hipDeviceSynchronize());
+    if (int rc = rbrt_hip_render_device(s, cam, opts, nullptr, d_rad, d_rgb)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
     const double t_copy0 = now_s();
     times.render_s = t_copy0 - t_render0;
     if (world > 1) {
         // scatter this rank's packed tiles into the caller's full-size images
         std::vector<float> hr(n_out * 3);
         std::vector<uint8_t> hb(out_rgb8 ? n_out * 3 : 0);
-        TRY_OR_CLEAN(hipMemcpy(hr.data(), d_rad, hr.size() * sizeof(float), hipMemcpyDeviceToHost));
-        if (out_rgb8) TRY_OR_CLEAN(hipMemcpy(hb.data(), d_rgb, hb.size(), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(hr.data(), d_rad, hr.size() * sizeof(float), hipMemcpyDeviceToHost));
+        if (out_rgb8) HIP_TRY(hipMemcpy(hb.data(), d_rgb, hb.size(), hipMemcpyDeviceToHost));
         const uint32_t W = cam->img_width_pix, H = cam->img_height_pix;
         const uint32_t tiles_x = (W + RBRT_TILE - 1) / RBRT_TILE;
         const size_t n_local = n_out / 64;
@@ -2106,17 +2188,16 @@ int rbrt_hip_render_shaded(const rbrt_camera_t* cam, const rbrt_scene_t* scene, 
         }
     } else {
         if (out_radiance)
-            TRY_OR_CLEAN(hipMemcpy(out_radiance, d_rad, n_out * 3 * sizeof(float), hipMemcpyDeviceToHost));
-        if (out_rgb8) TRY_OR_CLEAN(hipMemcpy(out_rgb8, d_rgb, n_out * 3, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(out_radiance, d_rad, n_out * 3 * sizeof(float), hipMemcpyDeviceToHost));
+        if (out_rgb8) HIP_TRY(hipMemcpy(out_rgb8, d_rgb, n_out * 3, hipMemcpyDeviceToHost));
     }
     DevCounters c;
-    TRY_OR_CLEAN(hipMemcpy(&c, s->d_counters, sizeof(c), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&c, s->d_counters, sizeof(c), hipMemcpyDeviceToHost));
     const double t_destroy0 = now_s();
     times.copy_s = t_destroy0 - t_copy0;
-    cleanup();
+    guard.reset();
     times.destroy_s = now_s() - t_destroy0;
     times.total_s = now_s() - t_call0;
-#undef TRY_OR_CLEAN
     if (c.diag[57])
         return fail(RBRT_ERR_HIP, "the trace kernel detected corrupt internal state (a path slot without a valid sample index)");
     if (c.nan_discriminants)
@@ -2154,17 +2235,7 @@ int rbrt_hip_bvh_build_host(const rbrt_mesh_t* mesh, void** nodes_out, size_t* n
     BvhKnobs knobs;
     std::string err;
     if (!lab_bvh_knobs(knobs, err)) return fail(RBRT_ERR_INVALID_ARG, err);
-    BvhBuildResult r = build_bvh(*mesh, knobs.host);
-    *n_nodes = r.nodes.size();
-    *n_tris = r.tris.size();
-    *nodes_out = std::malloc(std::max<size_t>(1, r.nodes.size() * sizeof(BvhNode4)));
-    *tris_out = std::malloc(std::max<size_t>(1, r.tris.size() * sizeof(BvhTri)));
-    if (!*nodes_out || !*tris_out) return fail(RBRT_ERR_OOM, "bvh_build_host: malloc failed");
-    std::memcpy(*nodes_out, r.nodes.data(), r.nodes.size() * sizeof(BvhNode4));
-    std::memcpy(*tris_out, r.tris.data(), r.tris.size() * sizeof(BvhTri));
-    if (max_depth) *max_depth = r.max_depth;
-    if (max_e12) *max_e12 = r.max_e12;
-    return RBRT_OK;
+    return copy_out(build_bvh(*mesh, knobs.host), "bvh_build_host", nodes_out, n_nodes, tris_out, n_tris, max_depth, max_e12);
 }
 void rbrt_hip_free_host(void* p) { std::free(p); }
 
@@ -2177,17 +2248,8 @@ int rbrt_hip_bvh_build_host_records(const void* records, size_t n, void** nodes_
     BvhKnobs knobs;
     std::string err;
     if (!lab_bvh_knobs(knobs, err)) return fail(RBRT_ERR_INVALID_ARG, err);
-    BvhBuildResult r = build_bvh_from_records(static_cast<const BvhTri*>(records), n, knobs.host);
-    *n_nodes = r.nodes.size();
-    *n_tris = r.tris.size();
-    *nodes_out = std::malloc(std::max<size_t>(1, r.nodes.size() * sizeof(BvhNode4)));
-    *tris_out = std::malloc(std::max<size_t>(1, r.tris.size() * sizeof(BvhTri)));
-    if (!*nodes_out || !*tris_out) return fail(RBRT_ERR_OOM, "bvh_build_host_records: malloc failed");
-    std::memcpy(*nodes_out, r.nodes.data(), r.nodes.size() * sizeof(BvhNode4));
-    std::memcpy(*tris_out, r.tris.data(), r.tris.size() * sizeof(BvhTri));
-    if (max_depth) *max_depth = r.max_depth;
-    if (max_e12) *max_e12 = r.max_e12;
-    return RBRT_OK;
+    return copy_out(build_bvh_from_records(static_cast<const BvhTri*>(records), n, knobs.host), "bvh_build_host_records", nodes_out,
+                    n_nodes, tris_out, n_tris, max_depth, max_e12);
 }
 
 // Diagnostic: the GPU builder alone (bvh_device.hip), results copied back in the layout of rbrt_hip_bvh_build_host.
@@ -2202,24 +2264,22 @@ int rbrt_hip_bvh_build_device(const rbrt_mesh_t* mesh, void** nodes_out, size_t*
     if (!lab_bvh_knobs(knobs, err)) return fail(RBRT_ERR_INVALID_ARG, err);
     if (int rc = ensure_device(0)) return rc;
     if (mesh->n_total < 8) return RBRT_OK;
-    BvhTri* d_tris = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_tris), size_t(mesh->n_total) * sizeof(BvhTri)));
+    DevBuf<BvhTri> d_tris;
+    HIP_TRY(d_tris.alloc(mesh->n_total));
     DeviceBvhResult r;
-    hipError_t e = device_build_mesh(*mesh, d_tris, 0, nullptr, &r, knobs);
+    hipError_t e = device_build_mesh(*mesh, d_tris.get(), 0, nullptr, &r, knobs);
+    const DevBuf<BvhNode4> d_nodes(r.d_nodes);
+    BvhBuildResult h;
     if (e == hipSuccess && r.ok) {
-        *nodes_out = std::malloc(size_t(r.n_nodes) * sizeof(BvhNode4));
-        *tris_out = std::malloc(std::max<size_t>(1, size_t(r.n_valid) * sizeof(BvhTri)));
-        if (*nodes_out && *tris_out) {
-            e = hipMemcpy(*nodes_out, r.d_nodes, size_t(r.n_nodes) * sizeof(BvhNode4), hipMemcpyDeviceToHost);
-            if (e == hipSuccess) e = hipMemcpy(*tris_out, d_tris, size_t(r.n_valid) * sizeof(BvhTri), hipMemcpyDeviceToHost);
-            *n_nodes = r.n_nodes, *n_tris = r.n_valid, *built = 1;
-            if (max_depth) *max_depth = r.max_depth;
-            if (max_e12) *max_e12 = r.max_e12;
-        }
+        h.nodes.resize(r.n_nodes), h.tris.resize(r.n_valid);
+        h.max_depth = r.max_depth, h.max_e12 = r.max_e12;
+        e = d_nodes.to_host(h.nodes.data(), r.n_nodes);
+        if (e == hipSuccess) e = d_tris.to_host(h.tris.data(), r.n_valid);
     }
-    if (r.d_nodes) (void)hipFree(r.d_nodes);
-    (void)hipFree(d_tris);
     if (e != hipSuccess) return fail(RBRT_ERR_HIP, std::string("bvh_build_device: ") + hipGetErrorString(e));
+    if (!r.ok) return RBRT_OK;
+    if (int rc = copy_out(h, "bvh_build_device", nodes_out, n_nodes, tris_out, n_tris, max_depth, max_e12)) return rc;
+    *built = 1;
     return RBRT_OK;
 }
 
@@ -2230,41 +2290,25 @@ int rbrt_hip_selftest_gate(const float lo[3], const float hi[3], const float* ra
     if (!lo || !hi || (!rays && n) || !out_fast || !out_exact) return fail(RBRT_ERR_INVALID_ARG, "selftest_gate: null argument");
     if (n == 0) return RBRT_OK;
     if (int rc = ensure_device(0)) return rc;
-    float *d_box = nullptr, *d_rays = nullptr;
-    uint8_t *d_f = nullptr, *d_e = nullptr;
-    auto cleanup = [&]() { (void)hipFree(d_box), (void)hipFree(d_rays), (void)hipFree(d_f), (void)hipFree(d_e); };
+    DevBuf<float> d_box, d_rays;
+    DevBuf<uint8_t> d_f, d_e;
     const float box[6] = {lo[0], lo[1], lo[2], hi[0], hi[1], hi[2]};
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_box), sizeof(box));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_rays), n * 6 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_f), n);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_e), n);
-    if (e == hipSuccess) e = hipMemcpy(d_box, box, sizeof(box), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_rays, rays, n * 6 * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = launch_gate_selftest(d_box, d_rays, n, d_f, d_e);
+    hipError_t e = d_box.upload(box, 6);
+    if (e == hipSuccess) e = d_rays.upload(rays, n * 6);
+    if (e == hipSuccess) e = d_f.alloc(n);
+    if (e == hipSuccess) e = d_e.alloc(n);
+    if (e == hipSuccess) e = launch_gate_selftest(d_box.get(), d_rays.get(), n, d_f.get(), d_e.get());
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(out_fast, d_f, n, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(out_exact, d_e, n, hipMemcpyDeviceToHost);
-    cleanup();
-    if (e != hipSuccess) return fail(RBRT_ERR_HIP, std::string("selftest_gate: ") + hipGetErrorString(e));
-    return RBRT_OK;
+    if (e == hipSuccess) e = d_f.to_host(out_fast, n);
+    if (e == hipSuccess) e = d_e.to_host(out_exact, n);
+    return hook_result(e, "selftest_gate");
 }
 
 // Test hook: the kernels' short forms of IEEE sqrt / normalize against the compiler's, on n pseudo-random operands.
 int rbrt_hip_selftest_ieee(uint64_t seed, size_t n, uint64_t counts[3]) {
     if (!counts) return fail(RBRT_ERR_INVALID_ARG, "selftest_ieee: null argument");
     if (n >= (1ull << 32) * 256ull) return fail(RBRT_ERR_INVALID_ARG, "selftest_ieee: n too large");
-    if (int rc = ensure_device(0)) return rc;
-    unsigned long long* d = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), 3 * sizeof(unsigned long long)));
-    hipError_t e = hipMemset(d, 0, 3 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = launch_ieee_selftest(seed, n, d);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    unsigned long long h[3] = {0, 0, 0};
-    if (e == hipSuccess) e = hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(RBRT_ERR_HIP, std::string("selftest_ieee: ") + hipGetErrorString(e));
-    for (int k = 0; k < 3; ++k) counts[k] = h[k];
-    return RBRT_OK;
+    return device_counts3("selftest_ieee", counts, [&](unsigned long long* d) { return launch_ieee_selftest(seed, n, d); });
 }
 
 // Test hook: ieee_sqrt / normalize of the kernels on caller-supplied operands, with the path each element's wave took.
@@ -2275,26 +2319,24 @@ int rbrt_hip_debug_ieee(const float* x, size_t n, const float* v, size_t m, floa
     if (n >= (1ull << 32) * 256ull || m >= (1ull << 32) * 256ull) return fail(RBRT_ERR_INVALID_ARG, "debug_ieee: n or m too large");
     if (n == 0 && m == 0) return RBRT_OK;
     if (int rc = ensure_device(0)) return rc;
-    float *d_x = nullptr, *d_v = nullptr, *d_s = nullptr, *d_q = nullptr;
-    uint8_t *d_sf = nullptr, *d_qf = nullptr;
+    DevBuf<float> d_x, d_v, d_s, d_q;
+    DevBuf<uint8_t> d_sf, d_qf;
     const size_t nx = std::max<size_t>(n, 1), nv = std::max<size_t>(m, 1);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_x), nx * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_s), nx * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_sf), nx);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_v), nv * 3 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_q), nv * 3 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_qf), nv);
-    if (e == hipSuccess && n) e = hipMemcpy(d_x, x, n * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess && m) e = hipMemcpy(d_v, v, m * 3 * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = launch_ieee_debug(d_x, n, d_v, m, d_s, d_sf, d_q, d_qf);
+    hipError_t e = d_x.alloc(nx);
+    if (e == hipSuccess) e = d_s.alloc(nx);
+    if (e == hipSuccess) e = d_sf.alloc(nx);
+    if (e == hipSuccess) e = d_v.alloc(nv * 3);
+    if (e == hipSuccess) e = d_q.alloc(nv * 3);
+    if (e == hipSuccess) e = d_qf.alloc(nv);
+    if (e == hipSuccess && n) e = d_x.from_host(x, n);
+    if (e == hipSuccess && m) e = d_v.from_host(v, m * 3);
+    if (e == hipSuccess) e = launch_ieee_debug(d_x.get(), n, d_v.get(), m, d_s.get(), d_sf.get(), d_q.get(), d_qf.get());
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess && n) e = hipMemcpy(out_sqrt, d_s, n * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && n) e = hipMemcpy(out_sqrt_short, d_sf, n, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && m) e = hipMemcpy(out_norm, d_q, m * 3 * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && m) e = hipMemcpy(out_norm_short, d_qf, m, hipMemcpyDeviceToHost);
-    (void)hipFree(d_x), (void)hipFree(d_s), (void)hipFree(d_sf), (void)hipFree(d_v), (void)hipFree(d_q), (void)hipFree(d_qf);
-    if (e != hipSuccess) return fail(RBRT_ERR_HIP, std::string("debug_ieee: ") + hipGetErrorString(e));
-    return RBRT_OK;
+    if (e == hipSuccess && n) e = d_s.to_host(out_sqrt, n);
+    if (e == hipSuccess && n) e = d_sf.to_host(out_sqrt_short, n);
+    if (e == hipSuccess && m) e = d_q.to_host(out_norm, m * 3);
+    if (e == hipSuccess && m) e = d_qf.to_host(out_norm_short, m);
+    return hook_result(e, "debug_ieee");
 }
 
 // Test hook: ieee_sqrt of every float with bits in [first_bits, first_bits + n), checked on the device.
@@ -2302,18 +2344,7 @@ int rbrt_hip_selftest_sqrt_sweep(uint32_t first_bits, uint64_t n, uint64_t count
     if (!counts) return fail(RBRT_ERR_INVALID_ARG, "selftest_sqrt_sweep: null argument");
     if (first_bits < 0x00800000u || n > uint64_t(0x7F800000u - first_bits))
         return fail(RBRT_ERR_INVALID_ARG, "selftest_sqrt_sweep: the range must hold positive normal floats only");
-    if (int rc = ensure_device(0)) return rc;
-    unsigned long long* d = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), 3 * sizeof(unsigned long long)));
-    hipError_t e = hipMemset(d, 0, 3 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = launch_sqrt_sweep(first_bits, n, d);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    unsigned long long h[3] = {0, 0, 0};
-    if (e == hipSuccess) e = hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(RBRT_ERR_HIP, std::string("selftest_sqrt_sweep: ") + hipGetErrorString(e));
-    for (int k = 0; k < 3; ++k) counts[k] = h[k];
-    return RBRT_OK;
+    return device_counts3("selftest_sqrt_sweep", counts, [&](unsigned long long* d) { return launch_sqrt_sweep(first_bits, n, d); });
 }
 
 // Test hook: n scatter events (materials.rs:4-12) on the device functions the shading passes use. Host arrays.
@@ -2324,40 +2355,29 @@ int rbrt_hip_debug_scatter(const rbrt_material_t* mats, const float* in_dir, con
     std::vector<DevMaterial> hm(n);
     for (size_t i = 0; i < n; ++i) {
         if (int rc = check_material(mats[i], "event", i)) return rc;
-        for (int c = 0; c < 3; ++c) hm[i].albedo[c] = mats[i].albedo[c];
-        hm[i].param = mats[i].param, hm[i].kind = dev_material_kind(mats[i].kind);
+        hm[i] = dev_material_of(mats[i]);
     }
     if (int rc = ensure_device(0)) return rc;
-    DevMaterial* d_m = nullptr;
-    float *d_in = nullptr, *d_p = nullptr, *d_n = nullptr, *d_out = nullptr;
-    uint32_t *d_rng = nullptr, *d_rng_out = nullptr;
-    uint8_t* d_ok = nullptr;
-    auto cleanup = [&]() {
-        (void)hipFree(d_m), (void)hipFree(d_in), (void)hipFree(d_p), (void)hipFree(d_n), (void)hipFree(d_out), (void)hipFree(d_rng),
-            (void)hipFree(d_rng_out), (void)hipFree(d_ok);
-    };
-    const size_t v3 = n * 3 * sizeof(float), st = n * 2 * sizeof(uint32_t);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_m), n * sizeof(DevMaterial));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_in), v3);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_p), v3);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_n), v3);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_out), v3);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_rng), st);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_rng_out), st);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_ok), n);
-    if (e == hipSuccess) e = hipMemcpy(d_m, hm.data(), n * sizeof(DevMaterial), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_in, in_dir, v3, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_p, p, v3, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_n, normal, v3, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_rng, rng_state, st, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = launch_scatter_debug(d_m, d_in, d_p, d_n, d_rng, n, d_out, d_ok, d_rng_out);
+    DevBuf<DevMaterial> d_m;
+    DevBuf<float> d_in, d_p, d_n, d_out;
+    DevBuf<uint32_t> d_rng, d_rng_out;
+    DevBuf<uint8_t> d_ok;
+    const size_t v3 = n * 3, st = n * 2;  // floats of a vector array, words of a generator state array
+    hipError_t e = d_m.upload(hm.data(), n);
+    if (e == hipSuccess) e = d_in.upload(in_dir, v3);
+    if (e == hipSuccess) e = d_p.upload(p, v3);
+    if (e == hipSuccess) e = d_n.upload(normal, v3);
+    if (e == hipSuccess) e = d_rng.upload(rng_state, st);
+    if (e == hipSuccess) e = d_out.alloc(v3);
+    if (e == hipSuccess) e = d_rng_out.alloc(st);
+    if (e == hipSuccess) e = d_ok.alloc(n);
+    if (e == hipSuccess)
+        e = launch_scatter_debug(d_m.get(), d_in.get(), d_p.get(), d_n.get(), d_rng.get(), n, d_out.get(), d_ok.get(), d_rng_out.get());
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess && out_dir) e = hipMemcpy(out_dir, d_out, v3, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out_ok) e = hipMemcpy(out_ok, d_ok, n, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out_rng_state) e = hipMemcpy(out_rng_state, d_rng_out, st, hipMemcpyDeviceToHost);
-    cleanup();
-    if (e != hipSuccess) return fail(RBRT_ERR_HIP, std::string("debug_scatter: ") + hipGetErrorString(e));
-    return RBRT_OK;
+    if (e == hipSuccess && out_dir) e = d_out.to_host(out_dir, v3);
+    if (e == hipSuccess && out_ok) e = d_ok.to_host(out_ok, n);
+    if (e == hipSuccess && out_rng_state) e = d_rng_out.to_host(out_rng_state, st);
+    return hook_result(e, "debug_scatter");
 }
 
 int rbrt_hip_debug_primary_cull(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, uint32_t* out_words, size_t n_words) {
@@ -2384,14 +2404,13 @@ int rbrt_hip_debug_primary_cull_opts(rbrt_hip_scene_t* s, const rbrt_camera_t* c
     TraceParams P;
     fill_trace_params(s, cam, &o, P);
     P.tiles_x = tiles_x, P.tiles_y = tiles_y, P.n_tiles = uint32_t(n_words);
-    void* d = nullptr;
-    HIP_TRY(hipMalloc(&d, n_words * sizeof(uint32_t)));
-    P.tile_cull = static_cast<uint32_t*>(d);
+    DevBuf<uint32_t> d;
+    HIP_TRY(d.alloc(n_words));
+    P.tile_cull = d.get();
     hipError_t e = launch_primary_cull(P, nullptr);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     std::vector<uint32_t> by_number(n_words);
-    if (e == hipSuccess) e = hipMemcpy(by_number.data(), d, n_words * sizeof(uint32_t), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
+    if (e == hipSuccess) e = d.to_host(by_number.data(), n_words);
     if (e != hipSuccess) return fail(RBRT_ERR_HIP, std::string("debug_primary_cull: ") + hipGetErrorString(e));
     // (the table is indexed by tile NUMBER, rbrt_hip.h "How tiles are dealt to ranks"; the hook hands it over in image order)
     for (uint32_t ty = 0; ty < tiles_y; ++ty)
@@ -2409,17 +2428,13 @@ int rbrt_hip_debug_shading_normals(rbrt_hip_scene_t* s, const float* rays, size_
     o.max_dist = max_dist;
     TraceParams P;
     fill_trace_params(s, nullptr, &o, P);
-    float *d_rays = nullptr, *d_out = nullptr;
-    auto cleanup = [&]() { (void)hipFree(d_rays), (void)hipFree(d_out); };
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_rays), n * 6 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_out), n * 3 * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(d_rays, rays, n * 6 * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = launch_shading_normals(P, d_rays, n, d_out, nullptr);
+    DevBuf<float> d_rays, d_out;
+    hipError_t e = d_rays.upload(rays, n * 6);
+    if (e == hipSuccess) e = d_out.alloc(n * 3);
+    if (e == hipSuccess) e = launch_shading_normals(P, d_rays.get(), n, d_out.get(), nullptr);
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(out_normal, d_out, n * 3 * sizeof(float), hipMemcpyDeviceToHost);
-    cleanup();
-    if (e != hipSuccess) return fail(RBRT_ERR_HIP, std::string("debug_shading_normals: ") + hipGetErrorString(e));
-    return RBRT_OK;
+    if (e == hipSuccess) e = d_out.to_host(out_normal, n * 3);
+    return hook_result(e, "debug_shading_normals");
 }
 
 int rbrt_hip_trace_rays(rbrt_hip_scene_t* s, const float* rays, size_t n, float min_dist, float max_dist,
@@ -2433,35 +2448,20 @@ int rbrt_hip_trace_rays(rbrt_hip_scene_t* s, const float* rays, size_t n, float 
     o.max_dist = max_dist;
     TraceParams P;
     fill_trace_params(s, nullptr, &o, P);
-    float *d_rays = nullptr, *d_t = nullptr, *d_dist = nullptr;
-    int32_t *d_obj = nullptr, *d_tri = nullptr;
-    int rc = RBRT_OK;
-    auto cleanup = [&]() {
-        (void)hipFree(d_rays), (void)hipFree(d_t), (void)hipFree(d_dist), (void)hipFree(d_obj), (void)hipFree(d_tri);
-    };
-#define TRY_OR_CLEAN(expr)                                                                       \
-    do {                                                                                         \
-        hipError_t _e = (expr);                                                                  \
-        if (_e != hipSuccess) {                                                                  \
-            cleanup();                                                                           \
-            return fail(RBRT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));        \
-        }                                                                                        \
-    } while (0)
-    TRY_OR_CLEAN(hipMalloc(reinterpret_cast<void**>(&d_rays), n * 6 * sizeof(float)));
-    TRY_OR_CLEAN(hipMalloc(reinterpret_cast<void**>(&d_t), n * sizeof(float)));
-    TRY_OR_CLEAN(hipMalloc(reinterpret_cast<void**>(&d_dist), n * sizeof(float)));
-    TRY_OR_CLEAN(hipMalloc(reinterpret_cast<void**>(&d_obj), n * sizeof(int32_t)));
-    TRY_OR_CLEAN(hipMalloc(reinterpret_cast<void**>(&d_tri), n * sizeof(int32_t)));
-    TRY_OR_CLEAN(hipMemcpy(d_rays, rays, n * 6 * sizeof(float), hipMemcpyHostToDevice));
-    TRY_OR_CLEAN(launch_trace_rays(P, d_rays, n, d_t, d_obj, d_tri, d_dist, nullptr));
-    TRY_OR_CLEAN(hipDeviceSynchronize());
-    if (out_t) TRY_OR_CLEAN(hipMemcpy(out_t, d_t, n * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_dist) TRY_OR_CLEAN(hipMemcpy(out_dist, d_dist, n * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_obj) TRY_OR_CLEAN(hipMemcpy(out_obj, d_obj, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (out_tri) TRY_OR_CLEAN(hipMemcpy(out_tri, d_tri, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    cleanup();
-#undef TRY_OR_CLEAN
-    return rc;
+    DevBuf<float> d_rays, d_t, d_dist;
+    DevBuf<int32_t> d_obj, d_tri;
+    HIP_TRY(d_rays.upload(rays, n * 6));
+    HIP_TRY(d_t.alloc(n));
+    HIP_TRY(d_dist.alloc(n));
+    HIP_TRY(d_obj.alloc(n));
+    HIP_TRY(d_tri.alloc(n));
+    HIP_TRY(launch_trace_rays(P, d_rays.get(), n, d_t.get(), d_obj.get(), d_tri.get(), d_dist.get(), nullptr));
+    HIP_TRY(hipDeviceSynchronize());
+    if (out_t) HIP_TRY(d_t.to_host(out_t, n));
+    if (out_dist) HIP_TRY(d_dist.to_host(out_dist, n));
+    if (out_obj) HIP_TRY(d_obj.to_host(out_obj, n));
+    if (out_tri) HIP_TRY(d_tri.to_host(out_tri, n));
+    return RBRT_OK;
 }
 
 }  // extern "C"

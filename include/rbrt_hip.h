@@ -54,7 +54,8 @@ extern "C" {
                               them answers a kind-3 material with RBRT_ERR_INVALID_ARG), nor RBRT_FLAG_THIN_LENS with its
                               rbrt_camera_lens_t (rbrt_camera_t stays as it is: the lens wraps it) and
                               rbrt_hip_supported_flags, nor the smooth shading of meshes (rbrt_scene_shading_t and the
-                              two *_shaded entry points: rbrt_mesh_t and rbrt_scene_t stay as they are) */
+                              two *_shaded entry points: rbrt_mesh_t and rbrt_scene_t stay as they are), nor adaptive
+                              sampling (rbrt_hip_render_adaptive with its two structs: an added entry point) */
 
 typedef enum rbrt_status {
     RBRT_OK = 0,
@@ -316,14 +317,69 @@ int rbrt_hip_render_device(rbrt_hip_scene_t* scene, const rbrt_camera_t* cam,
 
 /* Progressive / checkpointed rendering (no counterpart in the reference, whose sample loop lib.rs:95-101 runs to the
  * end or not at all; a 4096 x 4096 x 4096 spp render is 68.7 G paths). Renders samples [sample_begin, sample_end) of
- * the opts->spp samples of every pixel and adds them, in sample order, to the running sums in d_accum (device,
- * fp32, indexed like d_radiance; read unless sample_begin == 0). The call with sample_end == opts->spp also
+ * the opts->spp samples of every pixel and adds them, in sample order, to the running sums in d_accum (device, fp32,
+ * ALWAYS in the rank's packed tile order, tile_world <= 1 included: rbrt_hip_packed_pixels(...) * 3 floats, which is more
+ * than H*W*3 when the image has ragged edge tiles; read unless sample_begin == 0). The call with sample_end == opts->spp also
  * writes the mean to d_radiance and its quantisation to d_rgb8 (either may be NULL). Calls must cover [0, spp) in
  * ascending, non-overlapping ranges; the final image is then bit-identical to one rbrt_hip_render_device call,
  * because the per-pixel additions happen in the same order. A checkpoint is d_accum plus sample_end. */
 int rbrt_hip_render_pass(rbrt_hip_scene_t* scene, const rbrt_camera_t* cam, const rbrt_render_opts_t* opts,
                          void* stream, uint32_t sample_begin, uint32_t sample_end, float* d_accum,
                          float* d_radiance, uint8_t* d_rgb8);
+
+/* ---- Adaptive sampling: tiles stop once their noise estimate converges -----------------------------------------------
+ * No counterpart in the reference, which gives every pixel num_samples samples (lib.rs:95-101). opts->spp becomes the upper
+ * limit N; each 8x8 tile is sampled in rounds until the estimate of its error falls below `threshold`. The random stream
+ * of a sample does not depend on spp and a pixel's samples are added in sample order, so a tile that stops after n samples
+ * is bit for bit the tile of rbrt_hip_render_device at spp = n.
+ *
+ * The rule. All arithmetic is float32, unfused, in the written order; division and sqrt are correctly rounded.
+ *   Rounds.  n_0 = min(min_samples, N), n_{k+1} = min(n_k + step, N). Every tile of the rank starts active with count 0.
+ *     Round k renders samples [n_{k-1}, n_k) (round 0: [0, n_0)) of every tile that is active at its start. Each pixel's
+ *     samples are added in sample order to two running sums: S gets every sample, S_even those with an even index.
+ *     After the round each tile that was active sets its count n_t = n_k and computes its error E. It stays active iff
+ *     n_k < N and not (E < threshold): a NaN keeps sampling, threshold = 0 stops nothing early. The call ends when no tile
+ *     is active.
+ *   Tile error after n samples, with h = (n + 1) / 2 (integer), inv_n = 1.0f / float(n), inv_h = 1.0f / float(h):
+ *     per pixel p of the tile (p = (y % 8) * 8 + (x % 8)), per channel c:
+ *         I_c = S_c * inv_n        A_c = S_even_c * inv_h
+ *     e_p = (|I_r - A_r| + |I_g - A_g|) + |I_b - A_b|
+ *     q_p = e_p / (sqrt((I_r + I_g) + I_b) + 0.0001f)
+ *     a pixel beyond a ragged image edge has q_p = 0
+ *     v = q;  for d in 1, 2, 4, 8, 16, 32:  v[p] = v[p] + v[p ^ d]     (all 64 at once; every p ends with the same bits)
+ *     E = v / float(number of the tile's pixels inside the image)
+ *     (the half-buffer estimate of Dammertz et al.: the image of all samples against the image of every other one)
+ *   Image.  A pixel of a tile with count n_t is S * (1.0f / float(n_t)), then the usual quantisation. A tile with
+ *     n_t == N is exactly what rbrt_hip_render_device writes; any tile is exactly the fixed render at spp = n_t. */
+typedef struct rbrt_adaptive_opts {
+    float threshold;      /* finite, >= 0 */
+    uint32_t min_samples; /* >= 2 */
+    uint32_t step;        /* >= 1 */
+    uint32_t reserved;    /* 0 */
+} rbrt_adaptive_opts_t;
+
+typedef struct rbrt_adaptive_result {
+    uint32_t rounds, reserved;
+    uint64_t samples;        /* sum over the rank's pixels inside the image of their tile's count */
+    uint64_t samples_fixed;  /* the same at spp everywhere */
+} rbrt_adaptive_result_t;
+
+/* Renders adaptively into DEVICE memory on `stream`. UNLIKE rbrt_hip_render_device THIS CALL BLOCKS: it reads the number of
+ * active tiles back once per round, and all its outputs are complete when it returns. The threading rule of
+ * rbrt_hip_render_device holds.
+ *   d_radiance, d_rgb8: indexed as in rbrt_hip_render_device (packed when tile_world > 1).
+ *   d_tile_samples, d_tile_error: [n_local_tiles] in the rank's ascending tile number (number -> image tile:
+ *     rbrt_hip_tile_xy): the tile's final count and the last error computed for it.
+ *   out: the call's totals. Every output pointer may be NULL.
+ * Honours the thin lens, the constant background, smooth handles and tile_rank / tile_world. rbrt_hip_scene_check works
+ * after it as after any render. The running sums and tile tables belong to the handle (grown on demand, released by
+ * rbrt_hip_scene_destroy). The call's trace launches get no helper launches (rbrt_hip_debug.h RBRT_HELPERS).
+ * RBRT_ERR_INVALID_ARG, before the device is touched: scene, cam, opts or adaptive NULL; adaptive->reserved != 0; a
+ * threshold that is not finite or negative; min_samples < 2; step == 0; RBRT_FLAG_COLLECT_STATS set (counting stays with
+ * the fixed paths); and whatever rbrt_hip_render_device rejects. */
+int rbrt_hip_render_adaptive(rbrt_hip_scene_t* scene, const rbrt_camera_t* cam, const rbrt_render_opts_t* opts,
+                             const rbrt_adaptive_opts_t* adaptive, void* stream, float* d_radiance, uint8_t* d_rgb8,
+                             uint32_t* d_tile_samples, float* d_tile_error, rbrt_adaptive_result_t* out);
 
 /* De-interleave gathered per-rank packed tile buffers (concatenated rank 0..world-1, each
  * rbrt_hip_packed_pixels(...)*3 floats, device memory) into a row-major float[H][W][3] device

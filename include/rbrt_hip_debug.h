@@ -48,6 +48,11 @@ extern "C" {
  * number of batches. Diagnostic. */
 int rbrt_hip_scene_last_batching(rbrt_hip_scene_t* scene, uint32_t* samples_per_batch, uint32_t* n_batches);
 
+/* The rounds of the last rbrt_hip_render_adaptive call on this scene: *n_rounds = how many there were, and
+ * active_tiles[k] (k < min(n, *n_rounds)) = the rank's tiles that were active at the start of round k. Diagnostic (the
+ * C++ host's --report prints it). */
+int rbrt_hip_scene_adaptive_rounds(rbrt_hip_scene_t* scene, uint32_t* active_tiles, size_t n, uint32_t* n_rounds);
+
 /* Test / diagnostic hook for Scene::hit (scene.rs:19-43): closest hit of n rays against the
  * resident scene. Host arrays. rays = n x {ox,oy,oz,dx,dy,dz}. Outputs (each may be NULL):
  *   out_t[n]      ray parameter of the winning object (NaN on miss)

@@ -123,6 +123,30 @@ class HipScene:
                                                  sample_end, C.c_void_p(d_accum), C.c_void_p(d_radiance or 0),
                                                  C.c_void_p(d_rgb8 or 0)))
 
+    def render_adaptive(self, cam: abi.Camera, opts: abi.RenderOpts, threshold: float, min_samples: int = 16, step: int = 64,
+                        d_radiance: int | None = None, d_rgb8: int | None = None, d_tile_samples: int | None = None,
+                        d_tile_error: int | None = None, stream: int | None = None, lens=None, reserved: int = 0) -> dict:
+        """Adaptive render into device pointers (rbrt_hip_render_adaptive): opts.spp is the upper limit, a tile stops once its
+        error estimate is below `threshold`. Blocking: the outputs are complete on return. d_tile_samples (uint32) and
+        d_tile_error (float32) take one entry per tile of the rank, in ascending tile number. Returns the call's totals:
+        rounds, samples, samples_fixed."""
+        opts = _opts_copy(opts)
+        cam_p, _keep = _cam_arg(cam, lens, opts)
+        a = abi.AdaptiveOpts(float(threshold), int(min_samples), int(step), int(reserved))
+        res = abi.AdaptiveResult()
+        abi.check(self._lib.rbrt_hip_render_adaptive(self._h, cam_p, C.byref(opts), C.byref(a), C.c_void_p(stream or 0),
+                                                     C.c_void_p(d_radiance or 0), C.c_void_p(d_rgb8 or 0),
+                                                     C.c_void_p(d_tile_samples or 0), C.c_void_p(d_tile_error or 0), C.byref(res)))
+        return dict(rounds=int(res.rounds), samples=int(res.samples), samples_fixed=int(res.samples_fixed))
+
+    def adaptive_rounds(self) -> list:
+        """Tiles active at the start of each round of the last render_adaptive call (rbrt_hip_scene_adaptive_rounds)."""
+        n = C.c_uint32()
+        abi.check(self._lib.rbrt_hip_scene_adaptive_rounds(self._h, None, 0, C.byref(n)))
+        buf = (C.c_uint32 * max(n.value, 1))()
+        abi.check(self._lib.rbrt_hip_scene_adaptive_rounds(self._h, buf, n.value, C.byref(n)))
+        return [int(buf[i]) for i in range(n.value)]
+
     def set_pipeline(self, depth: int):
         """Overlap consecutive trace launches over `depth` internal streams (rbrt_hip_scene_set_pipeline)."""
         abi.check(self._lib.rbrt_hip_scene_set_pipeline(self._h, int(depth)))

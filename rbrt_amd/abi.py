@@ -143,6 +143,14 @@ class RenderOpts(C.Structure):
     ]
 
 
+class AdaptiveOpts(C.Structure):  # rbrt_adaptive_opts_t
+    _fields_ = [("threshold", C.c_float), ("min_samples", C.c_uint32), ("step", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class AdaptiveResult(C.Structure):  # rbrt_adaptive_result_t
+    _fields_ = [("rounds", C.c_uint32), ("reserved", C.c_uint32), ("samples", C.c_uint64), ("samples_fixed", C.c_uint64)]
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("rays", C.c_uint64),
@@ -203,6 +211,8 @@ HIP_SYMBOLS = {
     "rbrt_hip_scene_create_shaded": (C.c_int, [C.POINTER(Scene), C.POINTER(SceneShading), C.c_int, C.POINTER(C.c_void_p)]),
     "rbrt_hip_render_shaded": (C.c_int, [C.POINTER(Camera), C.POINTER(Scene), C.POINTER(SceneShading), C.POINTER(RenderOpts),
                                          f32p, u8p]),
+    "rbrt_hip_render_adaptive": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderOpts), C.POINTER(AdaptiveOpts), C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AdaptiveResult)]),
 }
 # ... and include/rbrt_hip_debug.h (test hooks and diagnostics, same library)
 DEBUG_SYMBOLS = {
@@ -236,6 +246,7 @@ DEBUG_SYMBOLS = {
     "rbrt_hip_last_render_times": (C.c_int, [C.POINTER(CallTimes)]),
     "rbrt_hip_scene_refine_wait": (C.c_int, [C.c_void_p, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     "rbrt_hip_debug_shading_normals": (C.c_int, [C.c_void_p, f32p, C.c_size_t, C.c_float, C.c_float, f32p]),
+    "rbrt_hip_scene_adaptive_rounds": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32)]),
 }
 
 

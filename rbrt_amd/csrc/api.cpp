@@ -33,6 +33,10 @@ hipError_t launch_primary_cull(const TraceParams& P, hipStream_t stream);
 hipError_t launch_sky_resolve(const TraceParams& P, const ResolveParams& R, hipStream_t stream);
 hipError_t launch_code_load(hipStream_t stream);
 hipError_t launch_resolve(const ResolveParams& R, hipStream_t stream);
+hipError_t launch_resolve_even(const TraceParams& P, const ResolveParams& R, uint32_t n_active_tiles, hipStream_t stream);
+hipError_t launch_adaptive_lists(const AdaptiveParams& A, hipStream_t stream);
+hipError_t launch_tile_error(const AdaptiveParams& A, uint32_t n_active_tiles, hipStream_t stream);
+hipError_t launch_adaptive_finish(const AdaptiveParams& A, hipStream_t stream);
 hipError_t launch_unpack(const float* gathered, uint32_t width, uint32_t height, uint32_t world,
                          size_t rank_stride_pixels, float* out_radiance, uint8_t* out_rgb8, hipStream_t stream);
 hipError_t launch_trace_rays(const TraceParams& P, const float* rays, size_t n, float* out_t, int32_t* out_obj,
@@ -334,6 +338,18 @@ struct rbrt_hip_scene {
     uint32_t next_lane = 0;
     float* d_acc = nullptr;
     size_t acc_bytes = 0;
+    // Adaptive sampling (rbrt_hip_render_adaptive): the running sums S and S_even, the tiles' flags, counts and errors, the
+    // camera's culling words and the round's tile lists. Grown on demand from dev_alloc (an array that has grown leaves its
+    // old one with the scene until destroy, as a lane's tile tables do); the lanes' cached tile tables are not involved.
+    struct Adaptive {
+        float *d_sum = nullptr, *d_sum_even = nullptr;  // [n_local * 64 * 3] each
+        size_t sum_floats = 0;
+        uint32_t *d_cull = nullptr, *d_lists = nullptr, *d_active = nullptr, *d_tile_samples = nullptr, *d_n_active = nullptr;
+        float* d_tile_error = nullptr;
+        size_t cull_words = 0, local_tiles = 0;
+        hipEvent_t ev_lists = nullptr;
+        std::vector<uint32_t> round_active;  // tiles active at the start of each round of the last call (rbrt_hip_debug.h)
+    } adaptive;
     bool poison_samples = false;      // RBRT_POISON_SAMPLES
     // host copy of the objects' bounds, for the tile-direction choice below
     struct Bound {
@@ -1504,6 +1520,7 @@ int rbrt_hip_scene_destroy(rbrt_hip_scene_t* s) {
     if (s->aux_stream) (void)hipStreamDestroy(s->aux_stream);
     const double td3 = now_s();
     if (s->h_zeros) (void)hipHostFree(s->h_zeros);
+    if (s->adaptive.ev_lists) (void)hipEventDestroy(s->adaptive.ev_lists);
     const double td4 = now_s();
     for (void* p : s->allocs) (void)hipFree(p);
     if (s->d_acc) (void)hipFree(s->d_acc);
@@ -1575,6 +1592,17 @@ struct CallPlan {
     uint32_t s_begin = 0, s_end = 0, world = 1, tiles_x = 0, tiles_y = 0, n_tiles = 0, n_local = 0, depth = 1;  // depth: lanes in turn
     size_t npix = 0, per_sample = 0, batch = 0, need = 0, n_batches = 0;  // batch: samples per launch, need: their buffer
     bool stats = false, busy_at_call = false, streams_now = false, tile_pass = false, timing = false;
+    const struct AdaptiveRound* round = nullptr;  // the call is a round of rbrt_hip_render_adaptive (below), else null
+};
+
+// A round of an adaptive call, as render_samples sees it: the launches read the adaptive state's own tile tables instead of
+// a lane's cached set (the lane cache and its keys are not involved), the resolves keep S_even beside S and write no image.
+struct AdaptiveRound {
+    uint32_t* d_cull;    // the camera's culling words, or null (RBRT_PRIMARY_CULL=0)
+    uint32_t* d_lists;   // the round's lists (adaptive_lists_kernel)
+    float* d_sum_even;
+    uint32_t n_active;   // tiles on the two lists together, as the host read it back after the round before
+    hipEvent_t ev_lists;  // recorded on the caller's stream behind the kernel that wrote the lists: a lane's launch waits for it
 };
 
 // The call's tiles, its sample batches and the lanes they take turns on. False: the rank has no tiles, nothing to do.
@@ -1686,7 +1714,7 @@ int size_lane(rbrt_hip_scene* s, const CallPlan& c, uint32_t li) {
         HIP_TRY(hipMalloc(&p, need));
         B.d_sample_buf = static_cast<float*>(p), B.sample_buf_bytes = need;
     }
-    if (c.tile_pass && (n_tiles > L.tile_cull_words || lists_need > L.tile_lists_words)) {
+    if (c.tile_pass && !c.round && (n_tiles > L.tile_cull_words || lists_need > L.tile_lists_words)) {
         if (L.tiles[0].d_cull || L.tiles[0].d_lists) {
             if (int rc = sync_lanes(s, c.stream)) return rc;
             if (s->prep_stream) HIP_TRY(hipStreamSynchronize(s->prep_stream));
@@ -1788,7 +1816,7 @@ int issue_batches(rbrt_hip_scene* s, const CallPlan& c, const rbrt_render_opts_t
         // lanes taking turns a caller who renders one view again and again would otherwise pay the tile pass eight times)
         uint32_t lane_no = stats ? 0u : s->next_lane % c.depth;
         // (a call's later batches find its earlier ones in flight)
-        if (!stats && c.depth > 1 && c.tile_pass && !s->streaming_hint && b == 0 && !c.busy_at_call) {
+        if (!stats && c.depth > 1 && c.tile_pass && !c.round && !s->streaming_hint && b == 0 && !c.busy_at_call) {
             const auto want = tile_key(P, list_mode_for(false));
             for (uint32_t li = 0; li < c.depth; ++li)
                 if (find_tile_set(s->lanes[li], want)) lane_no = li;
@@ -1822,7 +1850,8 @@ int issue_batches(rbrt_hip_scene* s, const CallPlan& c, const rbrt_render_opts_t
             HIP_TRY(hipMemcpyAsync(B.d_work_counter, s->h_zeros, counter_bytes, hipMemcpyHostToDevice, ts));
             L.helper_pending = false;
         }
-        P.sample_base = base, P.batch = nb, P.batch_magic = div_magic_of(nb), P.n_items = uint64_t(c.npix) * nb;
+        P.sample_base = base, P.batch = nb, P.batch_magic = div_magic_of(nb);
+        P.n_items = (c.round ? uint64_t(c.round->n_active) * 64u : uint64_t(c.npix)) * nb;  // (a round: an upper bound, its active tiles)
         // (a caller that streams launches keeps doing so: the first launch after a pause -- the GPU is idle, but the
         // launch before it was issued into a busy one -- is still issued as one of a stream)
         const bool busy = piped && other_launch_in_flight(s, &L);
@@ -1843,7 +1872,10 @@ int issue_batches(rbrt_hip_scene* s, const CallPlan& c, const rbrt_render_opts_t
         // which of the lane's two sets of tile tables this launch reads: the one made for this camera and partition, else
         // the one used longer ago, filled now
         rbrt_hip_scene::Lane::TileSet* S = nullptr;
-        if (c.tile_pass) {
+        if (c.round) {  // (the round's own tables, in ascending order, written on the caller's stream)
+            P.tile_cull = c.round->d_cull, P.tile_lists = c.round->d_lists, P.tile_list_mode = 0u;
+            if (piped) HIP_TRY(hipStreamWaitEvent(ts, c.round->ev_lists, 0));
+        } else if (c.tile_pass) {
             const uint32_t list_mode = list_mode_for(overlapped && !stats);
             S = find_tile_set(L, tile_key(P, list_mode));
             if (!S) {
@@ -1871,13 +1903,15 @@ int issue_batches(rbrt_hip_scene* s, const CallPlan& c, const rbrt_render_opts_t
         if (S) HIP_TRY(hipStreamWaitEvent(ts, S->ev_lists, 0));  // (the set's tables: made on the prep stream, or at the first call on the caller's)
         // (a blocking call's batch shares the GPU with the batches behind it, `to_come`: the last one ends alone and takes the
         // full grid, the one before it shares with one, ...; a stream's launch takes the steady state's share: grid_for)
-        const uint32_t grid = stats ? s->n_waves : grid_for(s, overlapped, c.depth, call_streams, to_come, P.n_items);
+        uint32_t grid = stats ? s->n_waves : grid_for(s, overlapped, c.depth, call_streams, to_come, P.n_items);
+        // (a round: never more waves than its active tiles have chunks of work, each wave draws a whole chunk at a time)
+        if (c.round) grid = uint32_t(std::min<uint64_t>(grid, std::max<uint64_t>(P.n_items / 64u, 1u)));
         (grid < s->n_waves ? s->n_half_grid : s->n_full_grid) += 1;
         if (s->trace_launches)
             std::fprintf(stderr, "[rbrt_hip] trace launch: grid %u waves on %u CUs (%u waves per CU)\n", grid, s->n_cus, s->n_waves / s->n_cus);
         if (piped) HIP_TRY(hipEventRecord(L.ev_ready, ts));  // (behind everything the launch waits for: a helper launch waits for this)
         HIP_TRY(launch_trace_megakernel(P, grid, stats, ts));
-        if (piped && s->helpers_mode != 0u) {
+        if (piped && s->helpers_mode != 0u && !c.round) {  // (the launches of an adaptive round get no helpers: see rbrt_hip_render_adaptive)
             L.open.valid = true, L.open.P = P, L.open.grid = grid, L.open.helper_waves = 0u, L.open.rounds = 0u, L.open.seq = ++s->open_seq;
             if (s->helpers_mode == 2u) {  // (tests: a helper with every overlapped launch, on a stream of its own)
                 if (!s->aux_stream) HIP_TRY(hipStreamCreateWithFlags(&s->aux_stream, hipStreamNonBlocking));
@@ -1886,19 +1920,21 @@ int issue_batches(rbrt_hip_scene* s, const CallPlan& c, const rbrt_render_opts_t
         }
         if (c.timing) HIP_TRY(hipEventRecord(s->events[ev0 + 3 * b + 1], ts));
         R.sample_buf = B.d_sample_buf, R.work_counter = B.d_work_counter, R.tile_lists = P.tile_lists;
-        R.batch = nb, R.first_batch = base == 0, R.last_batch = base + nb == o->spp;
+        R.batch = nb, R.first_batch = base == 0, R.last_batch = !c.round && base + nb == o->spp;
+        R.sample_base = base;
         R.helper_words = P.helper_words, R.helper_seq = P.helper_seq;
         if (piped) {
             HIP_TRY(hipEventRecord(L.ev_traced, ts));
             L.in_use = true;
             HIP_TRY(hipStreamWaitEvent(stream, L.ev_traced, 0));
         }
-        HIP_TRY(launch_resolve(R, stream));
+        if (c.round) HIP_TRY(launch_resolve_even(P, R, c.round->n_active, stream));  // (both lists: the background-only tiles too)
+        else HIP_TRY(launch_resolve(R, stream));
         // The background-only tiles never reach the trace kernel: their pixels are finished here, on the caller's stream
         // like every write to its buffers. BEHIND the resolve although it needs only the lists: issued beside its own
         // trace launch it waited for wave slots that persistent trace waves hold until their launch ends (1.2 ms on
         // average for 0.05 ms of work, with the resolve queued behind it); now it runs in the slots that launch just freed.
-        if (c.tile_pass) HIP_TRY(launch_sky_resolve(P, R, stream));
+        if (c.tile_pass && !c.round) HIP_TRY(launch_sky_resolve(P, R, stream));
         if (S) {  // the set's last readers have been issued: a later pass into it waits for them
             HIP_TRY(hipEventRecord(S->ev_free, stream));
             S->free_recorded = true;
@@ -1917,11 +1953,9 @@ int issue_batches(rbrt_hip_scene* s, const CallPlan& c, const rbrt_render_opts_t
 
 }  // namespace
 
-// Samples [s_begin, s_end) of a render of o->spp samples per pixel. `acc` holds (and receives) the per-pixel running
-// sums in sample order -- lib.rs:95-100's `color +=` -- packed like the radiance output; it is read unless
-// s_begin == 0 and written unless s_end == o->spp, in which case the mean (lib.rs:101) and the quantisation go out.
-static int render_samples(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, const rbrt_render_opts_t* o, void* stream_v,
-                   uint32_t s_begin, uint32_t s_end, float* acc, float* d_radiance, uint8_t* d_rgb8) {
+// What every render call checks before the device is touched.
+static int check_render_args(const rbrt_hip_scene_t* s, const rbrt_camera_t* cam, const rbrt_render_opts_t* o, uint32_t s_begin,
+                             uint32_t s_end) {
     if (!s || !cam || !o) return fail(RBRT_ERR_INVALID_ARG, "render: null argument");
     if (o->spp == 0) return fail(RBRT_ERR_INVALID_ARG, "spp must be >= 1");
     if (s_begin >= s_end || s_end > o->spp) return fail(RBRT_ERR_INVALID_ARG, "sample range must satisfy begin < end <= spp");
@@ -1932,11 +1966,22 @@ static int render_samples(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, const r
     if (uint64_t(cam->img_width_pix) * cam->img_height_pix >= (1ull << 32))
         return fail(RBRT_ERR_UNSUPPORTED, "image has 2^32 or more pixels");
     if (o->tile_rank >= (o->tile_world ? o->tile_world : 1)) return fail(RBRT_ERR_INVALID_ARG, "tile_rank >= tile_world");
-    if (int rc = lens_invalid(cam, o)) return rc;
+    return lens_invalid(cam, o);
+}
+
+// Samples [s_begin, s_end) of a render of o->spp samples per pixel. `acc` holds (and receives) the per-pixel running
+// sums in sample order -- lib.rs:95-100's `color +=` -- packed like the radiance output; it is read unless
+// s_begin == 0 and written unless s_end == o->spp, in which case the mean (lib.rs:101) and the quantisation go out.
+// `round`: the call is a round of rbrt_hip_render_adaptive (AdaptiveRound), which writes `acc` always and no image.
+static int render_samples(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, const rbrt_render_opts_t* o, void* stream_v,
+                   uint32_t s_begin, uint32_t s_end, float* acc, float* d_radiance, uint8_t* d_rgb8,
+                   const AdaptiveRound* round = nullptr) {
+    if (int rc = check_render_args(s, cam, o, s_begin, s_end)) return rc;
     HIP_TRY(hipSetDevice(s->device));
     std::lock_guard<std::mutex> watcher_lock(s->mu);  // (the watcher of elastic launches looks at the lanes between calls, not during one)
     adopt_refined(s);  // (the background thread's trees, once they are on the device: this call's launches use them)
     CallPlan c{static_cast<hipStream_t>(stream_v), s_begin, s_end};
+    c.round = round;
     if (!plan_call(s, cam, o, c)) return RBRT_OK;
     if (int rc = ensure_lanes(s, c.depth)) return rc;
     if (int rc = prepare_call(s, c, acc)) return rc;
@@ -1947,6 +1992,7 @@ static int render_samples(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, const r
     R.tile_rank = o->tile_rank, R.tile_world = c.world, R.n_local_tiles = c.n_local;
     R.inv_spp = 1.0f / float(o->spp);  // lib.rs:101
     R.acc = acc ? acc : s->d_acc, R.out_radiance = d_radiance, R.out_rgb8 = d_rgb8;
+    R.acc_even = round ? round->d_sum_even : nullptr;
     R.counters = c.stats ? s->d_counters : nullptr, R.error_flag = &s->d_counters->diag[57];
     // For a stream every lane's buffers are sized here, at the first call that needs them, not when a lane first comes up in
     // the rotation (a hipMalloc in the middle of a stream of frames); otherwise a lane's are sized when a batch goes to it.
@@ -1957,13 +2003,13 @@ static int render_samples(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, const r
     // only if a second batch ever overlaps the first -- creating and destroying one costs the call 0.3 ms)
     if (c.tile_pass && !s->one_shot)
         if (int rc = ensure_prep_stream(s)) return rc;
-    if (c.tile_pass && c.streams_now)
+    if (c.tile_pass && c.streams_now && !round)
         if (int rc = warm_tile_tables(s, c, P)) return rc;
     if (int rc = issue_batches(s, c, o, P, R)) return rc;
 
     // the watcher of elastic launches: started by the first call of a stream, woken when there is a launch to look after
     s->last_call_s = now_s();
-    if (s->helpers_mode == 1u && c.depth > 1 && !c.stats) {
+    if (s->helpers_mode == 1u && c.depth > 1 && !c.stats && !round) {
         if (!s->watcher.joinable() && c.streams_now) {
             try {
                 s->watcher = std::thread([s]() {
@@ -1989,6 +2035,137 @@ int rbrt_hip_render_pass(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, const rb
                          uint32_t sample_begin, uint32_t sample_end, float* d_accum, float* d_radiance, uint8_t* d_rgb8) {
     if (!d_accum) return fail(RBRT_ERR_INVALID_ARG, "render_pass: d_accum is null");
     return render_samples(s, cam, o, stream, sample_begin, sample_end, d_accum, d_radiance, d_rgb8);
+}
+
+// ---- Adaptive sampling (the rule: include/rbrt_hip.h) -----------------------------------------------------------------
+// A call is a series of rounds on the caller's stream. A round: adaptive_lists_kernel makes the round's two tile lists from
+// the camera's culling words and the tiles' flags; render_samples renders the round's samples of the listed tiles into S
+// and S_even (AdaptiveRound: the launches read these lists, not a lane's cached set, so the lanes' tables and keys stay as
+// they are; the resolves always get lists, also with the tile pass off, so a stopped tile's sums are never written again);
+// tile_error_kernel sets each listed tile's count, error and flag and counts the tiles that go on; the host reads that
+// count back -- the one blocking read per round -- and sizes the next round's grids by it. A round whose work list is empty
+// launches a trace kernel that finds no work, one whose background list is empty a resolve whose threads all leave.
+// Helper launches are switched OFF for these launches: a round is short and ends in a drain the host waits for anyway,
+// and a helper wave that joins late would have to be waited for by every round's resolve; launches of other calls on the
+// handle keep their helpers (a helper still pending on a lane is waited for in front of the round's launch, as always).
+namespace {
+
+// The adaptive state of the handle, grown to the call's image. Under s->mu (dev_alloc).
+int size_adaptive(rbrt_hip_scene* s, const CallPlan& c) {
+    auto& A = s->adaptive;
+    void* p = nullptr;
+    const size_t sum_floats = c.npix * 3u;
+    if (sum_floats > A.sum_floats) {
+        HIP_TRY(dev_alloc(s, sum_floats * sizeof(float), &p));
+        A.d_sum = static_cast<float*>(p);
+        HIP_TRY(dev_alloc(s, sum_floats * sizeof(float), &p));
+        A.d_sum_even = static_cast<float*>(p);
+        A.sum_floats = sum_floats;
+    }
+    if (c.n_tiles > A.cull_words) {
+        HIP_TRY(dev_alloc(s, size_t(c.n_tiles) * sizeof(uint32_t), &p));
+        A.d_cull = static_cast<uint32_t*>(p), A.cull_words = c.n_tiles;
+    }
+    if (c.n_local > A.local_tiles) {
+        // one piece: the lists (header + two lists), flags, counts, errors and the count of active tiles
+        const size_t n = c.n_local, words = size_t(kTileListHeader) + 2u * n + 3u * n + 1u;
+        HIP_TRY(dev_alloc(s, words * sizeof(uint32_t), &p));
+        A.d_lists = static_cast<uint32_t*>(p);
+        A.d_active = A.d_lists + kTileListHeader + 2u * n;
+        A.d_tile_samples = A.d_active + n;
+        A.d_tile_error = reinterpret_cast<float*>(A.d_tile_samples + n);
+        A.d_n_active = A.d_tile_samples + 2u * n;
+        A.local_tiles = n;
+    }
+    if (!A.ev_lists) HIP_TRY(hipEventCreateWithFlags(&A.ev_lists, hipEventDisableTiming));
+    return RBRT_OK;
+}
+
+}  // namespace
+
+int rbrt_hip_render_adaptive(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, const rbrt_render_opts_t* o,
+                             const rbrt_adaptive_opts_t* a, void* stream_v, float* d_radiance, uint8_t* d_rgb8,
+                             uint32_t* d_tile_samples, float* d_tile_error, rbrt_adaptive_result_t* out) {
+    if (!s || !cam || !o || !a) return fail(RBRT_ERR_INVALID_ARG, "render_adaptive: null argument");
+    if (a->reserved != 0u) return fail(RBRT_ERR_INVALID_ARG, "render_adaptive: reserved must be 0");
+    if (!std::isfinite(a->threshold) || a->threshold < 0.0f)
+        return fail(RBRT_ERR_INVALID_ARG, "render_adaptive: threshold must be finite and >= 0");
+    if (a->min_samples < 2u) return fail(RBRT_ERR_INVALID_ARG, "render_adaptive: min_samples must be >= 2");
+    if (a->step == 0u) return fail(RBRT_ERR_INVALID_ARG, "render_adaptive: step must be >= 1");
+    if (o->flags & RBRT_FLAG_COLLECT_STATS)
+        return fail(RBRT_ERR_INVALID_ARG, "render_adaptive: RBRT_FLAG_COLLECT_STATS is not supported (counting stays with the fixed paths)");
+    const uint32_t N = o->spp;
+    if (int rc = check_render_args(s, cam, o, 0, N)) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    const hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    rbrt_adaptive_result_t res{};
+    auto& S = s->adaptive;
+    S.round_active.clear();
+    CallPlan c{stream, 0, std::min(a->min_samples, N)};
+    AdaptiveParams A;
+    std::memset(&A, 0, sizeof(A));
+    {
+        std::lock_guard<std::mutex> watcher_lock(s->mu);
+        adopt_refined(s);
+        if (!plan_call(s, cam, o, c)) {  // the rank has no tiles
+            if (out) *out = res;
+            return RBRT_OK;
+        }
+        if (int rc = size_adaptive(s, c)) return rc;
+        // the camera's culling words, once per call, into the adaptive state's own table
+        if (c.tile_pass) {
+            TraceParams P = call_params(s, cam, o, c);
+            P.tile_cull = S.d_cull, P.tile_lists = nullptr;
+            HIP_TRY(launch_primary_cull(P, stream));
+        }
+    }
+    A.width = cam->img_width_pix, A.height = cam->img_height_pix, A.tiles_x = c.tiles_x;
+    A.tile_rank = o->tile_rank, A.tile_world = c.world, A.n_local_tiles = c.n_local;
+    A.n_max = N, A.threshold = a->threshold;
+    A.tile_cull = c.tile_pass ? S.d_cull : nullptr, A.tile_lists = S.d_lists, A.active = S.d_active, A.n_active = S.d_n_active;
+    A.tile_samples = S.d_tile_samples, A.tile_error = S.d_tile_error, A.acc = S.d_sum, A.acc_even = S.d_sum_even;
+    A.out_radiance = d_radiance, A.out_rgb8 = d_rgb8;
+
+    uint32_t n_prev = 0, n_k = std::min(a->min_samples, N), n_active = c.n_local;
+    for (;;) {
+        A.n = n_k, A.first_round = res.rounds == 0u ? 1u : 0u;
+        HIP_TRY(launch_adaptive_lists(A, stream));
+        HIP_TRY(hipEventRecord(S.ev_lists, stream));
+        const AdaptiveRound round{A.tile_cull ? S.d_cull : nullptr, S.d_lists, S.d_sum_even, n_active, S.ev_lists};
+        if (int rc = render_samples(s, cam, o, stream_v, n_prev, n_k, S.d_sum, nullptr, nullptr, &round)) return rc;
+        HIP_TRY(launch_tile_error(A, n_active, stream));
+        S.round_active.push_back(n_active);
+        ++res.rounds;
+        uint32_t left = 0;
+        HIP_TRY(hipMemcpyAsync(&left, S.d_n_active, sizeof(left), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));  // (the lanes' launches included: the round's resolves waited for them)
+        n_active = left;
+        if (n_active == 0u || n_k >= N) break;  // (n_k == N leaves no tile active)
+        n_prev = n_k, n_k = uint32_t(std::min<uint64_t>(uint64_t(n_k) + a->step, N));
+    }
+    HIP_TRY(launch_adaptive_finish(A, stream));
+    const size_t n = c.n_local;
+    if (d_tile_samples) HIP_TRY(hipMemcpyAsync(d_tile_samples, S.d_tile_samples, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+    if (d_tile_error) HIP_TRY(hipMemcpyAsync(d_tile_error, S.d_tile_error, n * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    std::vector<uint32_t> counts(n);
+    HIP_TRY(hipMemcpyAsync(counts.data(), S.d_tile_samples, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    for (size_t tl = 0; tl < n; ++tl) {
+        uint32_t ty = 0, tx = 0;
+        rbrt_hip_tile_xy(uint32_t(tl) * c.world + o->tile_rank, c.tiles_x, &ty, &tx);
+        const uint64_t inside = uint64_t(std::min(RBRT_TILE, A.height - ty * RBRT_TILE)) * std::min(RBRT_TILE, A.width - tx * RBRT_TILE);
+        res.samples += inside * counts[tl], res.samples_fixed += inside * N;
+    }
+    if (out) *out = res;
+    return RBRT_OK;
+}
+
+int rbrt_hip_scene_adaptive_rounds(rbrt_hip_scene_t* s, uint32_t* active_tiles, size_t n, uint32_t* n_rounds) {
+    if (!s || !n_rounds || (n != 0 && !active_tiles)) return fail(RBRT_ERR_INVALID_ARG, "adaptive_rounds: null argument");
+    const auto& r = s->adaptive.round_active;
+    *n_rounds = uint32_t(r.size());
+    for (size_t i = 0; i < n && i < r.size(); ++i) active_tiles[i] = r[i];
+    return RBRT_OK;
 }
 
 int rbrt_hip_scene_set_pipeline(rbrt_hip_scene_t* s, uint32_t depth) {

@@ -213,6 +213,29 @@ struct ResolveParams {
     uint32_t* helper_words;            // TraceParams::helper_words of the launch this resolves (null: none)
     uint32_t helper_seq;               // ... and its sequence number, published in helper_words[1]
     unsigned long long* error_flag;    // DevCounters::diag[57]: raised if helper waves of the launch never finish (bounded wait)
+    // resolve_even_kernel / sky_resolve_even_kernel only (adaptive sampling; the plain resolves never read them)
+    float* acc_even;       // [n_local_tiles*64][3] running sum of the samples with an even index
+    uint32_t sample_base;  // index of the batch's first sample
+};
+
+// Adaptive sampling (include/rbrt_hip.h "Adaptive sampling"): what adaptive_lists_kernel, tile_error_kernel and
+// adaptive_finish_kernel need of one rbrt_hip_render_adaptive call. The arrays belong to the scene handle.
+struct AdaptiveParams {
+    uint32_t width, height, tiles_x;
+    uint32_t tile_rank, tile_world, n_local_tiles;
+    uint32_t n, n_max;            // n_k: samples of a tile that was active in this round; N = opts->spp
+    float threshold;
+    uint32_t first_round;         // 1: every tile is active, `active` is not read
+    const uint32_t* tile_cull;    // TraceParams::tile_cull of the call's camera, or null (no tile pass: no tile is background only)
+    uint32_t* tile_lists;         // the round's lists, laid out as TraceParams::tile_lists
+    uint32_t* active;             // [n_local_tiles] 1: the tile takes part in the next round
+    uint32_t* n_active;           // one word: tiles left active by the round (zeroed by adaptive_lists_kernel)
+    uint32_t* tile_samples;       // [n_local_tiles] n_t
+    float* tile_error;            // [n_local_tiles] the last E computed for the tile
+    const float* acc;             // S and S_even: ResolveParams::acc, ::acc_even
+    const float* acc_even;
+    float* out_radiance;          // as ResolveParams (adaptive_finish_kernel); may be null
+    uint8_t* out_rgb8;
 };
 
 }  // namespace rbrt

@@ -1291,6 +1291,207 @@ __host__ __device__ inline uint32_t local_tiles_of(uint32_t n_tiles, uint32_t ra
     return rank < n_tiles ? (n_tiles - rank + world - 1u) / world : 0u;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Adaptive sampling (rbrt_hip_render_adaptive; the rule is stated in include/rbrt_hip.h and DESIGN.md section 9).
+// A call is a series of rounds. Each round renders a few more samples of the tiles that are still active -- the trace
+// kernel and the two resolves below walk the round's own tile lists --, then tile_error_kernel decides which of them go
+// on. Every pixel keeps two running sums in sample order: S of all its samples, S_even of those with an even index.
+// ---------------------------------------------------------------------------------------------
+
+// resolve_kernel for a round: the batch is added to S and, sample by sample, to S_even; nothing goes out (the round never
+// is a call's last batch: adaptive_finish_kernel writes the image). A kernel of its own, so that resolve_kernel stays the
+// code it is. No wait for helper waves: the launches of an adaptive call get none (api.cpp issue_batches).
+__global__ __launch_bounds__(kSmallBlock) void resolve_even_kernel(const ResolveParams R) {
+    const size_t npix = size_t(R.tile_lists[0]) * 64u;
+    const size_t i = size_t(blockIdx.x) * kSmallBlock + threadIdx.x;
+    if (blockIdx.x == 0) {  // (as resolve_kernel: the launch's number, then its work counters for the lane's next launch)
+        if (R.helper_words && threadIdx.x == 0) {
+            __hip_atomic_store(R.helper_words + 1, R.helper_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        }
+        __syncthreads();
+        for (uint32_t w = threadIdx.x; w < kWorkShards * kWorkCounterStride; w += kSmallBlock) R.work_counter[w] = 0ull;
+    }
+    if (i >= npix) return;
+    const uint32_t p = uint32_t(i & 63u);
+    const uint32_t tile_local = R.tile_lists[kTileListHeader + (i >> 6)];
+    const size_t j = size_t(tile_local) * 64u + p;
+    const uint32_t tile = tile_local * R.tile_world + R.tile_rank;
+    uint32_t ty, tx;
+    tile_xy(tile, R.tiles_x, ty, tx);
+    const uint32_t row = ty * RBRT_TILE + (p >> 3), col = tx * RBRT_TILE + (p & 7u);
+    if (!(row < R.height && col < R.width)) return;  // (a slot beyond a ragged edge: its sums are never read)
+    float ax = 0.0f, ay = 0.0f, az = 0.0f, ex = 0.0f, ey = 0.0f, ez = 0.0f;
+    if (!R.first_batch) {
+        ax = R.acc[j * 3 + 0], ay = R.acc[j * 3 + 1], az = R.acc[j * 3 + 2];
+        ex = R.acc_even[j * 3 + 0], ey = R.acc_even[j * 3 + 1], ez = R.acc_even[j * 3 + 2];
+    }
+    for (uint32_t s = 0; s < R.batch; ++s) {
+        const float* sp = R.sample_buf + (size_t(s) * npix + i) * 3u;
+        const float cx = sp[0], cy = sp[1], cz = sp[2];
+        ax = ax + cx;
+        ay = ay + cy;
+        az = az + cz;
+        if (((R.sample_base + s) & 1u) == 0u) {
+            ex = ex + cx;
+            ey = ey + cy;
+            ez = ez + cz;
+        }
+    }
+    R.acc[j * 3 + 0] = ax, R.acc[j * 3 + 1] = ay, R.acc[j * 3 + 2] = az;
+    R.acc_even[j * 3 + 0] = ex, R.acc_even[j * 3 + 1] = ey, R.acc_even[j * 3 + 2] = ez;
+}
+
+// sky_resolve_kernel for a round: the same samples, the same order, into both sums.
+__global__ __launch_bounds__(kSmallBlock) void sky_resolve_even_kernel(const TraceParams P, const ResolveParams R) {
+    const size_t i = size_t(blockIdx.x) * kSmallBlock + threadIdx.x;
+    if (i >= size_t(R.tile_lists[1]) * 64u) return;
+    const uint32_t p = uint32_t(i & 63u);
+    const uint32_t tile_local = R.tile_lists[kTileListHeader + R.n_local_tiles + (i >> 6)];
+    const size_t j = size_t(tile_local) * 64u + p;
+    const uint32_t tile = tile_local * R.tile_world + R.tile_rank;
+    uint32_t ty, tx;
+    tile_xy(tile, R.tiles_x, ty, tx);
+    const uint32_t row = ty * RBRT_TILE + (p >> 3), col = tx * RBRT_TILE + (p & 7u);
+    if (!(row < R.height && col < R.width)) return;
+    float ax = 0.0f, ay = 0.0f, az = 0.0f, ex = 0.0f, ey = 0.0f, ez = 0.0f;
+    if (!R.first_batch) {
+        ax = R.acc[j * 3 + 0], ay = R.acc[j * 3 + 1], az = R.acc[j * 3 + 2];
+        ex = R.acc_even[j * 3 + 0], ey = R.acc_even[j * 3 + 1], ez = R.acc_even[j * 3 + 2];
+    }
+    const V3 pos = mk(P.cam.position), center = mk(P.cam.img_center_point), right = mk(P.cam.right), up = mk(P.cam.up);
+    for (uint32_t s = 0; s < R.batch; ++s) {
+        Rng rng;
+        rng.init(P.seed_key, row * R.width + col, P.sample_base + s);
+        V3 o = pos, f = camera_target(center, right, up, P.cam.mm_per_pix_hor, P.cam.mm_per_pix_vert, R.width, R.height, row, col, rng);
+        if (P.thin_lens) {
+            const float lens[7] = {P.lens_u[0], P.lens_u[1], P.lens_u[2], P.lens_v[0], P.lens_v[1], P.lens_v[2], P.focus_scale};
+            lens_point(o, f, lens, rng);
+        }
+        const V3 d = normalize(f - o);
+        const V3 c = background(d.y, P.bg, P.constant_bg);
+        ax = ax + c.x;
+        ay = ay + c.y;
+        az = az + c.z;
+        if (((P.sample_base + s) & 1u) == 0u) {
+            ex = ex + c.x;
+            ey = ey + c.y;
+            ez = ez + c.z;
+        }
+    }
+    R.acc[j * 3 + 0] = ax, R.acc[j * 3 + 1] = ay, R.acc[j * 3 + 2] = az;
+    R.acc_even[j * 3 + 0] = ex, R.acc_even[j * 3 + 1] = ey, R.acc_even[j * 3 + 2] = ez;
+}
+
+// The round's tile lists: the rank's ACTIVE tiles, those that see only the background (bit 31 of their culling word) on the
+// second list, the others on the work list, both ascending; inactive tiles on neither. One wave and no LDS, as
+// tile_lists_kernel<64>: every lane a contiguous run of local tiles, an exclusive scan of the runs' counts in between.
+// Also zeroes the count tile_error_kernel adds to.
+__global__ __launch_bounds__(64) void adaptive_lists_kernel(const AdaptiveParams A) {
+    const uint32_t n = A.n_local_tiles, t = threadIdx.x;
+    const uint32_t per = (n + 63u) / 64u;
+    const uint32_t lo = t * per < n ? t * per : n, hi = lo + per < n ? lo + per : n;
+    // class of a tile: 0 = work list, 1 = background only, 2 = inactive
+    const auto class_of = [&](uint32_t tl) -> uint32_t {
+        if (!A.first_round && A.active[tl] == 0u) return 2u;
+        return A.tile_cull ? A.tile_cull[tl * A.tile_world + A.tile_rank] >> 31 : 0u;
+    };
+    uint32_t mine[2] = {0u, 0u};
+    for (uint32_t tl = lo; tl < hi; ++tl) {
+        const uint32_t c = class_of(tl);
+        if (c < 2u) ++mine[c];
+    }
+    uint32_t incl[2] = {mine[0], mine[1]};
+    for (uint32_t d = 1; d < 64u; d <<= 1) {  // inclusive scans over the wave
+        const uint32_t v0 = uint32_t(__shfl_up(int(incl[0]), d, 64)), v1 = uint32_t(__shfl_up(int(incl[1]), d, 64));
+        if (t >= d) incl[0] += v0, incl[1] += v1;
+    }
+    const uint32_t n_work = uint32_t(__shfl(int(incl[0]), 63, 64)), n_sky = uint32_t(__shfl(int(incl[1]), 63, 64));
+    uint32_t r[2] = {incl[0] - mine[0], incl[1] - mine[1]};  // tiles of either list before this run
+    uint32_t* const work = A.tile_lists + kTileListHeader;
+    uint32_t* const sky = work + n;
+    for (uint32_t tl = lo; tl < hi; ++tl) {
+        const uint32_t c = class_of(tl);
+        if (c == 0u) work[r[0]++] = tl;
+        else if (c == 1u) sky[r[1]++] = tl;
+    }
+    if (t == 63u) {
+        A.tile_lists[0] = n_work;
+        A.tile_lists[1] = n_sky;
+        A.tile_lists[2] = 0u, A.tile_lists[3] = 0u;  // (no light tiles: the list is in mode 0's order)
+        *A.n_active = 0u;
+    }
+}
+
+// After a round: one wave per tile of the round's two lists, lane p = pixel p. The tile's error E by the half-buffer
+// estimate (float32, unfused, in the order of the rule), its count and whether it goes on; the tiles that go on are
+// counted, one atomic per wave.
+__global__ __launch_bounds__(64) void tile_error_kernel(const AdaptiveParams A) {
+    const uint32_t w = blockIdx.x, p = threadIdx.x;
+    const uint32_t n_work = A.tile_lists[0], n_sky = A.tile_lists[1];
+    if (w >= n_work + n_sky) return;  // (the grid is the host's count of active tiles: never smaller than the lists)
+    const uint32_t tile_local = w < n_work ? A.tile_lists[kTileListHeader + w] : A.tile_lists[kTileListHeader + A.n_local_tiles + (w - n_work)];
+    const size_t j = size_t(tile_local) * 64u + p;
+    const uint32_t tile = tile_local * A.tile_world + A.tile_rank;
+    uint32_t ty, tx;
+    tile_xy(tile, A.tiles_x, ty, tx);
+    const uint32_t row = ty * RBRT_TILE + (p >> 3), col = tx * RBRT_TILE + (p & 7u);
+    const uint32_t h = (A.n + 1u) / 2u;
+    const float inv_n = 1.0f / float(A.n), inv_h = 1.0f / float(h);
+    float q = 0.0f;
+    if (row < A.height && col < A.width) {
+        const float ir = A.acc[j * 3 + 0] * inv_n, ig = A.acc[j * 3 + 1] * inv_n, ib = A.acc[j * 3 + 2] * inv_n;
+        const float ar = A.acc_even[j * 3 + 0] * inv_h, ag = A.acc_even[j * 3 + 1] * inv_h, ab = A.acc_even[j * 3 + 2] * inv_h;
+        const float e = (__builtin_fabsf(ir - ar) + __builtin_fabsf(ig - ag)) + __builtin_fabsf(ib - ab);
+        q = e / (__builtin_sqrtf((ir + ig) + ib) + 0.0001f);
+    }
+    float v = q;
+    for (uint32_t d = 1; d < 64u; d <<= 1) v = v + __shfl_xor(v, int(d), 64);  // (a + b == b + a: every lane ends with the same bits)
+    const uint32_t rows_in = A.height - ty * RBRT_TILE < RBRT_TILE ? A.height - ty * RBRT_TILE : RBRT_TILE;
+    const uint32_t cols_in = A.width - tx * RBRT_TILE < RBRT_TILE ? A.width - tx * RBRT_TILE : RBRT_TILE;
+    const float err = v / float(rows_in * cols_in);
+    if (p == 0u) {
+        const bool go_on = A.n < A.n_max && !(err < A.threshold);  // (a NaN goes on)
+        A.tile_samples[tile_local] = A.n;
+        A.tile_error[tile_local] = err;
+        A.active[tile_local] = go_on ? 1u : 0u;
+        if (go_on) atomicAdd(A.n_active, 1u);
+    }
+}
+
+// The image of an adaptive call: every pixel its S times the reciprocal of its tile's count, then the quantisation;
+// indexing and ragged edges as resolve_store's last batch. One thread per pixel slot of the rank.
+__global__ __launch_bounds__(kSmallBlock) void adaptive_finish_kernel(const AdaptiveParams A) {
+    const size_t i = size_t(blockIdx.x) * kSmallBlock + threadIdx.x;
+    if (i >= size_t(A.n_local_tiles) * 64u) return;
+    const uint32_t p = uint32_t(i & 63u), tile_local = uint32_t(i >> 6);
+    const uint32_t tile = tile_local * A.tile_world + A.tile_rank;
+    uint32_t ty, tx;
+    tile_xy(tile, A.tiles_x, ty, tx);
+    const uint32_t row = ty * RBRT_TILE + (p >> 3), col = tx * RBRT_TILE + (p & 7u);
+    const bool valid = row < A.height && col < A.width, packed = A.tile_world > 1;
+    float ax = 0.0f, ay = 0.0f, az = 0.0f;
+    if (valid) {
+        const float inv = 1.0f / float(A.tile_samples[tile_local]);
+        ax = A.acc[i * 3 + 0] * inv;
+        ay = A.acc[i * 3 + 1] * inv;
+        az = A.acc[i * 3 + 2] * inv;
+    } else if (!packed) {
+        return;  // (a pixel slot beyond a ragged image edge: packed outputs carry it as zeros)
+    }
+    const size_t o = packed ? i * 3u : (size_t(row) * A.width + col) * 3u;
+    if (A.out_radiance) {
+        A.out_radiance[o + 0] = ax;
+        A.out_radiance[o + 1] = ay;
+        A.out_radiance[o + 2] = az;
+    }
+    if (A.out_rgb8) {
+        A.out_rgb8[o + 0] = quantise(ax);
+        A.out_rgb8[o + 1] = quantise(ay);
+        A.out_rgb8[o + 2] = quantise(az);
+    }
+}
+
 // Gathered per-rank packed tiles -> row-major image (rank r's block starts after the blocks of
 // ranks < r; inside a block tiles are in ascending global tile order).
 __global__ __launch_bounds__(kSmallBlock) void unpack_kernel(const float* __restrict__ gathered, uint32_t width,
@@ -1582,6 +1783,33 @@ hipError_t launch_resolve(const ResolveParams& R, hipStream_t stream) {
     const size_t npix = size_t(R.n_local_tiles) * 64u;
     if (npix == 0) return hipSuccess;
     hipLaunchKernelGGL(resolve_kernel, dim3(uint32_t((npix + kSmallBlock - 1) / kSmallBlock)), dim3(kSmallBlock), 0, stream, R);
+    return hipGetLastError();
+}
+
+// The kernels of an adaptive round. n_active_tiles: the host's count of the tiles on the round's two lists together
+// (either list is at most that long: the grids are sized by it, not by the image).
+hipError_t launch_resolve_even(const TraceParams& P, const ResolveParams& R, uint32_t n_active_tiles, hipStream_t stream) {
+    const size_t npix = size_t(n_active_tiles) * 64u;
+    if (npix == 0 || !R.tile_lists || !R.acc || !R.acc_even) return hipSuccess;
+    const dim3 grid(uint32_t((npix + kSmallBlock - 1) / kSmallBlock));
+    hipLaunchKernelGGL(resolve_even_kernel, grid, dim3(kSmallBlock), 0, stream, R);
+    hipLaunchKernelGGL(sky_resolve_even_kernel, grid, dim3(kSmallBlock), 0, stream, P, R);
+    return hipGetLastError();
+}
+hipError_t launch_adaptive_lists(const AdaptiveParams& A, hipStream_t stream) {
+    if (A.n_local_tiles == 0) return hipSuccess;
+    hipLaunchKernelGGL(adaptive_lists_kernel, dim3(1), dim3(64), 0, stream, A);
+    return hipGetLastError();
+}
+hipError_t launch_tile_error(const AdaptiveParams& A, uint32_t n_active_tiles, hipStream_t stream) {
+    if (n_active_tiles == 0) return hipSuccess;
+    hipLaunchKernelGGL(tile_error_kernel, dim3(n_active_tiles), dim3(64), 0, stream, A);
+    return hipGetLastError();
+}
+hipError_t launch_adaptive_finish(const AdaptiveParams& A, hipStream_t stream) {
+    const size_t npix = size_t(A.n_local_tiles) * 64u;
+    if (npix == 0 || (!A.out_radiance && !A.out_rgb8)) return hipSuccess;
+    hipLaunchKernelGGL(adaptive_finish_kernel, dim3(uint32_t((npix + kSmallBlock - 1) / kSmallBlock)), dim3(kSmallBlock), 0, stream, A);
     return hipGetLastError();
 }
 

@@ -5,7 +5,8 @@
 // --pass-samples N, --checkpoint FILE, --checkpoint-every N, --report FILE (machine-readable timing of the run),
 // --background R,G,B (a constant background instead of the reference's sky gradient), --aperture MM and
 // --focus-distance D (a thin lens: they override the YAML's camera_aperture_mm / camera_focus_distance), --shading flat|smooth
-// (overrides every mesh blueprint's `shading`).
+// (overrides every mesh blueprint's `shading`), --adaptive THRESHOLD with --min-samples N and --adaptive-step K (adaptive sampling:
+// --samples is the limit), --sample-map FILE (the per-pixel sample count of an adaptive render, scaled to 0-255).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -47,6 +48,13 @@ void usage() {
         "                                   direction, in scene units; overrides the YAML's camera_focus_distance\n"
         "      --shading <how>              flat (face normals) or smooth (corner normals: the .obj's vn, else area-weighted\n"
         "                                   vertex normals) for every mesh; overrides the YAML's `shading` [default: the YAML's]\n"
+        "      --adaptive <threshold>       adaptive sampling: every 8x8 tile is sampled in rounds until its error estimate\n"
+        "                                   falls below the threshold (0 stops nothing early); --samples is the limit.\n"
+        "                                   Cannot be combined with --gpus > 1, --checkpoint or --pass-samples\n"
+        "      --min-samples <n>            adaptive: samples of the first round, at least 2 [default: 16]\n"
+        "      --adaptive-step <k>          adaptive: samples of every later round, at least 1 [default: 64]\n"
+        "      --sample-map <file>          adaptive: write the per-pixel sample count there, scaled to 0-255 (same formats as\n"
+        "                                   the target file)\n"
         "  -h, --help                       Print help\n"
         "  -V, --version                    Print version\n");
 }
@@ -114,6 +122,12 @@ int main(int argc, char** argv) {
     float background[3] = {0.0f, 0.0f, 0.0f};
     std::optional<float> aperture, focus_distance;
     std::optional<bool> smooth;
+    std::optional<float> adaptive;
+    // (the step: every round ends in a drain and a read-back, 1.0 ms at 1024x768 whatever the round renders; with rounds of
+    // 16 a 256-spp render that traces a tenth of the samples took as long as the fixed one, with rounds of 64 half as long
+    // for 1 % more samples: profiles/adaptive_config2.txt)
+    uint32_t min_samples = 16, adaptive_step = 64;
+    std::string sample_map;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         std::string val;
@@ -188,6 +202,20 @@ int main(int argc, char** argv) {
                 return 2;
             }
             (a == "--aperture" ? aperture : focus_distance) = f;
+        } else if (a == "--adaptive") {
+            const char* v = value();
+            float f = 0.0f;
+            if (!parse_f32(v, f) || !std::isfinite(f) || f < 0.0f) {
+                std::fprintf(stderr, "error: invalid value '%s' for '--adaptive' (expected a finite threshold >= 0)\n", v);
+                return 2;
+            }
+            adaptive = f;
+        } else if (a == "--min-samples") {
+            u32(min_samples);
+        } else if (a == "--adaptive-step") {
+            u32(adaptive_step);
+        } else if (a == "--sample-map") {
+            sample_map = value();
         } else if (a == "--shading") {
             const std::string v = value();
             if (v != "flat" && v != "smooth") {
@@ -202,6 +230,20 @@ int main(int argc, char** argv) {
                          a.c_str());
             return 2;
         }
+    }
+    if (adaptive) {  // one GPU, one blocking call: refused by name before anything is loaded
+        const char* with = gpus > 1 ? "--gpus > 1" : !checkpoint.empty() ? "--checkpoint" : pass_samples != 0 ? "--pass-samples" : nullptr;
+        if (with) {
+            std::fprintf(stderr, "error: '--adaptive' cannot be combined with '%s'\n", with);
+            return 2;
+        }
+        if (min_samples < 2 || adaptive_step < 1) {
+            std::fprintf(stderr, "error: '--min-samples' must be at least 2 and '--adaptive-step' at least 1\n");
+            return 2;
+        }
+    } else if (!sample_map.empty()) {
+        std::fprintf(stderr, "error: '--sample-map' needs '--adaptive'\n");
+        return 2;
     }
     using clock = std::chrono::steady_clock;
     const auto secs = [](clock::time_point a, clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
@@ -228,16 +270,19 @@ int main(int argc, char** argv) {
         cfg.gather = gather;
         cfg.constant_background = constant_background;
         for (int c = 0; c < 3; ++c) cfg.background[c] = background[c];
+        if (adaptive) cfg.adaptive = true, cfg.adaptive_threshold = *adaptive, cfg.adaptive_min_samples = min_samples, cfg.adaptive_step = adaptive_step;
         rbrt::ImageBuffer img = rbrt::render_scene(cam, samples, scene, cfg);
         std::printf("Saving rendered image to %s\n", target.c_str());
         const auto t3 = clock::now();
         img.save(target);
+        if (!sample_map.empty()) img.save_sample_map(sample_map);
         const auto t4 = clock::now();
         if (!report_path.empty()) {
             uint64_t triangles = 0;
             for (const auto& m : scene.triangle_meshes) triangles += m.num_triangles;
             const uint32_t spp = samples_arg_for_report(samples);
-            const double rendered = double(width) * double(height) * double(spp - rep.resumed_from_sample);  // path samples of THIS run
+            const double rendered = adaptive ? double(rep.adaptive_samples)
+                                             : double(width) * double(height) * double(spp - rep.resumed_from_sample);  // path samples of THIS run
             std::string js = "{";
             const auto str = [&](const char* k, const std::string& v) { js += std::string("\"") + k + "\": \"" + json_escape(v) + "\", "; };
             const auto num = [&](const char* k, double v, const char* fmt = "%.6f") {
@@ -253,6 +298,14 @@ int main(int argc, char** argv) {
             str("bvh_builder", rep.builder), num("bvh_nodes", double(rep.bvh_nodes), "%.0f"), num("bvh_triangles", double(rep.bvh_triangles), "%.0f");
             num("passes", rep.passes, "%.0f"), num("pass_samples", rep.pass_spp, "%.0f");
             num("checkpoints_written", rep.checkpoints_written, "%.0f"), num("resumed_from_sample", rep.resumed_from_sample, "%.0f");
+            if (adaptive) {  // rounds, samples traced, samples a fixed render would trace, tiles active at the start of each round
+                num("adaptive_threshold", *adaptive, "%.9g"), num("min_samples", min_samples, "%.0f"), num("adaptive_step", adaptive_step, "%.0f");
+                num("adaptive_rounds", rep.adaptive_rounds, "%.0f"), num("samples_traced", double(rep.adaptive_samples), "%.0f");
+                num("samples_fixed", double(rep.adaptive_samples_fixed), "%.0f");
+                js += "\"active_tiles_per_round\": [";
+                for (size_t k = 0; k < rep.adaptive_active_tiles.size(); ++k) js += (k ? ", " : "") + std::to_string(rep.adaptive_active_tiles[k]);
+                js += "], ";
+            }
             // where the run's time went; the parts add up to total_s (other_s is what none of them covers: thread start,
             // checkpoint look-up, the report itself)
             const rbrt::LoadTimes lt = rbrt::load_times();

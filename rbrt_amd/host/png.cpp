@@ -200,6 +200,15 @@ std::vector<uint8_t> encode_qoi(const uint8_t* rgb, uint32_t w, uint32_t h) {
 // same here for the formats that hold an 8-bit RGB image LOSSLESSLY (so that the decoded pixels are the reference's):
 // png, ppm / pnm (binary P6), pam (P7), bmp, tga, tif / tiff, qoi. The crate's lossy or palette encoders (jpeg, gif,
 // webp, avif, ico) are not restated: the error names what is available.
+void ImageBuffer::save_sample_map(const std::string& path) const {
+    if (sample_map.size() != size_t(width) * height) throw Error("no sample map to save to " + path + ": the render was not adaptive");
+    ImageBuffer grey;
+    grey.width = width, grey.height = height;
+    grey.rgb.resize(sample_map.size() * 3);
+    for (size_t i = 0; i < sample_map.size(); ++i) grey.rgb[3 * i] = grey.rgb[3 * i + 1] = grey.rgb[3 * i + 2] = sample_map[i];
+    grey.save(path);
+}
+
 void ImageBuffer::save(const std::string& path) const {
     std::string ext;
     const size_t dot = path.find_last_of('.');

@@ -215,7 +215,9 @@ struct ImageBuffer {
     uint32_t width = 0, height = 0;
     std::vector<uint8_t> rgb;        // row-major, 3 bytes per pixel
     std::vector<float> radiance;     // row-major fp32 pre-gamma mean (extra to the reference)
+    std::vector<uint8_t> sample_map; // an adaptive render: one byte per pixel, its tile's sample count * 255 / samples (else empty)
     void save(const std::string& path) const;  // .png (8-bit RGB) or .ppm by extension
+    void save_sample_map(const std::string& path) const;  // the sample map as a grey image, through the same writers
 };
 void write_png(const std::string& path, const uint8_t* rgb, uint32_t width, uint32_t height);
 
@@ -236,6 +238,10 @@ struct RenderReport {
     std::string gather = "none";    // none (one GPU) | host | rccl
     std::string builder = "none";   // who built the BVHs: host | device | mixed | none (no mesh)
     uint64_t bvh_nodes = 0, bvh_triangles = 0;
+    // an adaptive render (RenderConfig::adaptive): rbrt_adaptive_result_t and the tiles active at the start of each round
+    uint32_t adaptive_rounds = 0;
+    uint64_t adaptive_samples = 0, adaptive_samples_fixed = 0;
+    std::vector<uint32_t> adaptive_active_tiles;
 };
 
 struct RenderConfig {  // additions that the reference hard-codes or lacks
@@ -252,6 +258,11 @@ struct RenderConfig {  // additions that the reference hard-codes or lacks
     RenderReport* report = nullptr;   // filled in when not null
     bool constant_background = false; // RBRT_FLAG_CONSTANT_BACKGROUND: escaped rays return `background` (the CLI's --background)
     float background[3] = {0.0f, 0.0f, 0.0f};
+    // Adaptive sampling (rbrt_hip_render_adaptive; the CLI's --adaptive): num_samples is the limit, a tile stops once its error
+    // estimate is below the threshold. One GPU, no checkpoint, no passes: render_scene refuses the combination by name.
+    bool adaptive = false;
+    float adaptive_threshold = 0.0f;
+    uint32_t adaptive_min_samples = 16, adaptive_step = 64;  // (the step: profiles/adaptive_config2.txt)
 };
 // rbrt_lib::render_scene (lib.rs:75-79): blocks until the image is complete. Runs on the GPU(s)
 // through the C ABI; there is no CPU path.

@@ -144,6 +144,10 @@ struct RcclApi {
     }
 };
 
+size_t npix_tiles(uint32_t width, uint32_t height) {
+    return size_t((width + RBRT_TILE - 1) / RBRT_TILE) * ((height + RBRT_TILE - 1) / RBRT_TILE);
+}
+
 double seconds_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
@@ -172,6 +176,11 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
     img.rgb.assign(n, 0);
     img.radiance.assign(n, 0.0f);
     if (num_samples == 0) throw Error("the number of samples must be at least 1");
+    if (cfg.adaptive) {  // (one blocking call of one GPU: rbrt_hip.h "Adaptive sampling")
+        if (cfg.n_gpus > 1) throw Error("--adaptive cannot be combined with --gpus > 1");
+        if (!cfg.checkpoint_path.empty()) throw Error("--adaptive cannot be combined with --checkpoint");
+        if (cfg.pass_spp != 0) throw Error("--adaptive cannot be combined with --pass-samples");
+    }
 
     const auto t_hip0 = std::chrono::steady_clock::now();
     const int n_dev = rbrt_hip_device_count();  // (the process's first HIP call: the runtime starts here)
@@ -355,7 +364,34 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
         // ---- passes ---- (every rank meets every barrier, failed or not: the loop bounds are the same for all)
         const auto t_passes = std::chrono::steady_clock::now();
         uint32_t pass_no = 0;
-        for (uint64_t b = start_sample; b < num_samples; b += pass_spp, ++pass_no) {
+        if (cfg.adaptive && !failed && npix) {
+            // one blocking call instead of the passes: the library's rounds are the passes (world == 1: checked above)
+            const rbrt_adaptive_opts_t ao = {cfg.adaptive_threshold, cfg.adaptive_min_samples, cfg.adaptive_step, 0u};
+            rbrt_adaptive_result_t ar{};
+            const size_t n_tiles = npix_tiles(img.width, img.height);
+            uint32_t* d_counts = nullptr;
+            std::vector<uint32_t> counts(n_tiles);
+            if (hip_ok(hipMalloc(reinterpret_cast<void**>(&d_counts), n_tiles * sizeof(uint32_t)), "hipMalloc(tile samples)")) {
+                if (rbrt_hip_render_adaptive(hs, &c, &o, &ao, stream, d_rad, d_rgb, d_counts, nullptr, &ar) != RBRT_OK) fail(rbrt_hip_last_error());
+                else hip_ok(hipMemcpy(counts.data(), d_counts, n_tiles * sizeof(uint32_t), hipMemcpyDeviceToHost), "download of the tile samples");
+                (void)hipFree(d_counts);
+            }
+            if (!failed) {
+                rep.adaptive_rounds = ar.rounds, rep.adaptive_samples = ar.samples, rep.adaptive_samples_fixed = ar.samples_fixed;
+                rep.adaptive_active_tiles.resize(ar.rounds);
+                uint32_t n_rounds = 0;
+                (void)rbrt_hip_scene_adaptive_rounds(hs, rep.adaptive_active_tiles.data(), rep.adaptive_active_tiles.size(), &n_rounds);
+                pass_no = ar.rounds;
+                img.sample_map.assign(size_t(img.width) * img.height, 0);
+                const uint32_t tiles_x = (img.width + RBRT_TILE - 1) / RBRT_TILE;
+                for (uint32_t row = 0; row < img.height; ++row)
+                    for (uint32_t col = 0; col < img.width; ++col) {
+                        const uint32_t t = rbrt_hip_tile_number(row / RBRT_TILE, col / RBRT_TILE, tiles_x);
+                        img.sample_map[size_t(row) * img.width + col] = uint8_t(uint64_t(counts[t]) * 255u / num_samples);
+                    }
+            }
+        }
+        for (uint64_t b = start_sample; b < num_samples && !cfg.adaptive; b += pass_spp, ++pass_no) {
             const uint32_t e = uint32_t(std::min<uint64_t>(num_samples, b + pass_spp));
             const bool last = e == num_samples;
             if (!failed && npix) {

@@ -55,7 +55,9 @@ extern "C" {
                               rbrt_camera_lens_t (rbrt_camera_t stays as it is: the lens wraps it) and
                               rbrt_hip_supported_flags, nor the smooth shading of meshes (rbrt_scene_shading_t and the
                               two *_shaded entry points: rbrt_mesh_t and rbrt_scene_t stay as they are), nor adaptive
-                              sampling (rbrt_hip_render_adaptive with its two structs: an added entry point) */
+                              sampling (rbrt_hip_render_adaptive with its two structs: an added entry point), nor the
+                              denoiser (rbrt_denoise_opts_t, rbrt_denoise_opts_default, rbrt_hip_denoise_halves and
+                              rbrt_hip_scene_denoise: added entry points) */
 
 typedef enum rbrt_status {
     RBRT_OK = 0,
@@ -380,6 +382,68 @@ typedef struct rbrt_adaptive_result {
 int rbrt_hip_render_adaptive(rbrt_hip_scene_t* scene, const rbrt_camera_t* cam, const rbrt_render_opts_t* opts,
                              const rbrt_adaptive_opts_t* adaptive, void* stream, float* d_radiance, uint8_t* d_rgb8,
                              uint32_t* d_tile_samples, float* d_tile_error, rbrt_adaptive_result_t* out);
+
+/* ---- Denoising: a dual-buffer non-local-means filter on the adaptive half sums -------------------------------------------
+ * No counterpart in the reference. The filter of Rousselle, Knaus and Zwicker (2012) for images without feature buffers: the
+ * image of the samples with an even index is filtered with weights taken from the image of the odd ones and the other way
+ * round (weights taken from the same noise would reinforce it), and the two results are mixed by their sample shares.
+ *
+ * The rule. All arithmetic is float32, unfused, in the written order; division and sqrt are correctly rounded. "Inside" means
+ * inside the W x H image; a sum "from 0" starts at 0.0f and adds its terms one at a time in the stated order.
+ *   Inputs.  Two half images A and B, float[H][W][3]; a per-pixel mix wa, float[H][W], the share of A; window_radius R,
+ *     patch_radius P, strength k. eps = 1e-7f, k2 = k * k.
+ *   Variance.  d_c[p] = (A_c[p] - B_c[p]) squared.  V_c[p] = (sum / float(count)) * 0.5f, where sum runs over the 3 x 3
+ *     neighbourhood of p (dy outer -1..1, dx inner -1..1, from 0) of d_c, only pixels inside are added and count is how many.
+ *   Pixel distance, for a guide image G, a pixel p and an offset o = (dy, dx), q = p + o: delta(p, o) = 0 if p or q is
+ *     outside, else per channel
+ *         t_c = (((G_c[q] - G_c[p]) squared) - (V_c[p] + min(V_c[p], V_c[q]))) / (eps + k2 * (V_c[p] + V_c[q]))
+ *     and delta = (t_r + t_g) + t_b.
+ *   Patch distance.  r_j = sum from 0 over i = -P..P, left to right, of delta(p + (j, i), o);  D = sum from 0 over
+ *     j = -P..P, top to bottom, of r_j;  D = D / float(3 * cy * cx), where cy * cx is the number of patch positions at which
+ *     both p + (j, i) and p + (j, i) + o are inside (both conditions are rectangles: the count is a product). Rows first,
+ *     columns second, both orders fixed: a kernel may share row sums between pixels; a sliding-window update is not the rule.
+ *   Weight.  t = max(0, 1 - 0.25f * max(D, 0)),  w = (t * t) * (t * t): the fourth power of a truncated line, which follows
+ *     e^-D and has support up to D = 4 (exp has no correctly rounded form on both sides of a test). At o = 0 every delta
+ *     is <= 0, so w = 1 exactly.
+ *   Filter.  filter(F, G)[p]_c = num_c / den, num_c = sum from 0 of w(p, o) * F_c[p + o], den = sum from 0 of w(p, o), both
+ *     over the window with dy outer -R..R and dx inner -R..R; offsets whose q is outside are skipped.
+ *   Output.  Ah = filter(A, guide B), Bh = filter(B, guide A), out_c = (Ah_c * wa) + (Bh_c * (1 - wa)), then the usual
+ *     quantisation for rgb8. With R = 0 the output is exactly (A * wa) + (B * (1 - wa)).
+ *   From a handle's sums, for a tile with count n, h = (n + 1) / 2 (integer), g = n - h:
+ *     A = S_even * (1.0f / float(h)),  B = (S - S_even) * (1.0f / float(g)),  wa = float(h) * (1.0f / float(n)).
+ * Finite inputs with |x| <= 1e6 give no NaN. A non-finite input pixel gives unspecified values in the pixels whose window
+ * holds it; it never faults. */
+typedef struct rbrt_denoise_opts {
+    uint32_t window_radius; /* R, 0..10 */
+    uint32_t patch_radius;  /* P, 0..4 */
+    float strength;         /* k, finite, > 0 */
+    uint32_t reserved;      /* 0 */
+} rbrt_denoise_opts_t;
+void rbrt_denoise_opts_default(rbrt_denoise_opts_t* opts); /* R = 5, P = 3, k = 0.7 */
+
+/* The filter on two half images in DEVICE memory (row-major float[H][W][3]; d_wa row-major float[H][W], NULL: 0.5
+ * everywhere). Needs no scene, like rbrt_hip_unpack_tiles. Writes the row-major result to d_radiance and / or its quantisation
+ * to d_rgb8 (either may be NULL). Asynchronous on `stream`. The call owns no device memory: the variance and everything else
+ * the kernel stages live in the kernel's LDS, so calls on different streams share nothing.
+ * RBRT_ERR_INVALID_ARG, before the device is touched: d_a, d_b or opts NULL; opts->reserved != 0; window_radius > 10;
+ * patch_radius > 4; a strength that is not finite or <= 0; width or height 0. */
+int rbrt_hip_denoise_halves(int device, void* stream, const float* d_a, const float* d_b, const float* d_wa,
+                            uint32_t width, uint32_t height, const rbrt_denoise_opts_t* opts,
+                            float* d_radiance, uint8_t* d_rgb8);
+
+/* Denoises the image of the handle's last rbrt_hip_render_adaptive call, from that call's S, S_even and tile counts (the
+ * handle remembers its width, height and tile_world). d_radiance, d_rgb8: row-major, as rbrt_hip_render_device's; d_half_a,
+ * d_half_b: the two half images A and B the filter worked on, float[H][W][3]. Every output may be NULL. Asynchronous on
+ * `stream`; the half images between the two kernels are the handle's memory (grown on demand, released by
+ * rbrt_hip_scene_destroy), so the threading rule of rbrt_hip_render_device holds. A fixed render or another denoise call in
+ * between changes nothing; the next adaptive call replaces the image.
+ * A rank lacks its neighbours' pixels: multi-rank denoising is out of scope (gather, rbrt_hip_unpack_tiles and
+ * rbrt_hip_denoise_halves on halves of one's own is the way).
+ * RBRT_ERR_INVALID_ARG, before the device is touched: scene or opts NULL; what rbrt_hip_denoise_halves refuses in opts; no
+ * adaptive render on the handle yet; the last one had opts->spp < 2 (a half would be empty).
+ * RBRT_ERR_UNSUPPORTED: the last adaptive render had tile_world > 1. */
+int rbrt_hip_scene_denoise(rbrt_hip_scene_t* scene, const rbrt_denoise_opts_t* opts, void* stream,
+                           float* d_radiance, uint8_t* d_rgb8, float* d_half_a, float* d_half_b);
 
 /* De-interleave gathered per-rank packed tile buffers (concatenated rank 0..world-1, each
  * rbrt_hip_packed_pixels(...)*3 floats, device memory) into a row-major float[H][W][3] device

@@ -53,6 +53,10 @@ int rbrt_hip_scene_last_batching(rbrt_hip_scene_t* scene, uint32_t* samples_per_
  * C++ host's --report prints it). */
 int rbrt_hip_scene_adaptive_rounds(rbrt_hip_scene_t* scene, uint32_t* active_tiles, size_t n, uint32_t* n_rounds);
 
+/* Edge in pixels of the square pixel tile one workgroup of the denoising kernel covers (rbrt_amd/csrc/denoise.hip): image
+ * sizes around it are where that kernel's edge handling changes (tests/test_denoise_gpu.py). */
+#define RBRT_DENOISE_TILE 16u
+
 /* Test / diagnostic hook for Scene::hit (scene.rs:19-43): closest hit of n rays against the
  * resident scene. Host arrays. rays = n x {ox,oy,oz,dx,dy,dz}. Outputs (each may be NULL):
  *   out_t[n]      ray parameter of the winning object (NaN on miss)

@@ -147,6 +147,16 @@ class HipScene:
         abi.check(self._lib.rbrt_hip_scene_adaptive_rounds(self._h, buf, n.value, C.byref(n)))
         return [int(buf[i]) for i in range(n.value)]
 
+    def denoise(self, d_radiance: int | None = None, d_rgb8: int | None = None, d_half_a: int | None = None,
+                d_half_b: int | None = None, window_radius: int | None = None, patch_radius: int | None = None,
+                strength: float | None = None, stream: int | None = None, reserved: int = 0):
+        """The denoised image of the last render_adaptive call into device pointers (rbrt_hip_scene_denoise): row-major
+        float32 / uint8 [H, W, 3]; d_half_a, d_half_b take the two half images the filter worked on. Asynchronous on `stream`.
+        A parameter left None takes the library's default (rbrt_denoise_opts_default: 5, 3, 0.7)."""
+        d = denoise_opts(window_radius, patch_radius, strength, reserved)
+        abi.check(self._lib.rbrt_hip_scene_denoise(self._h, C.byref(d), C.c_void_p(stream or 0), C.c_void_p(d_radiance or 0),
+                                                   C.c_void_p(d_rgb8 or 0), C.c_void_p(d_half_a or 0), C.c_void_p(d_half_b or 0)))
+
     def set_pipeline(self, depth: int):
         """Overlap consecutive trace launches over `depth` internal streams (rbrt_hip_scene_set_pipeline)."""
         abi.check(self._lib.rbrt_hip_scene_set_pipeline(self._h, int(depth)))
@@ -332,3 +342,29 @@ def unpack_tiles(device: int, d_gathered: int, width: int, height: int, world: i
     abi.check(load_hip().rbrt_hip_unpack_tiles_strided(device, C.c_void_p(stream or 0), C.c_void_p(d_gathered), width,
                                                        height, world, rank_stride_pixels, C.c_void_p(d_radiance or 0),
                                                        C.c_void_p(d_rgb8 or 0)))
+
+
+def denoise_opts(window_radius: int | None = None, patch_radius: int | None = None, strength: float | None = None,
+                 reserved: int = 0) -> abi.DenoiseOpts:
+    """rbrt_denoise_opts_default, with the parameters that are given put in."""
+    d = abi.DenoiseOpts()
+    load_hip().rbrt_denoise_opts_default(C.byref(d))
+    if window_radius is not None:
+        d.window_radius = int(window_radius)
+    if patch_radius is not None:
+        d.patch_radius = int(patch_radius)
+    if strength is not None:
+        d.strength = float(strength)
+    d.reserved = int(reserved)
+    return d
+
+
+def denoise_halves(device: int, d_a: int, d_b: int, d_wa: int | None, width: int, height: int, d_radiance: int | None,
+                   d_rgb8: int | None = None, window_radius: int | None = None, patch_radius: int | None = None,
+                   strength: float | None = None, stream: int | None = None, reserved: int = 0):
+    """The dual-buffer non-local-means filter on two half images in device memory (rbrt_hip_denoise_halves): d_a, d_b
+    row-major float32 [H, W, 3], d_wa float32 [H, W] or None (0.5 everywhere). Asynchronous on `stream`."""
+    d = denoise_opts(window_radius, patch_radius, strength, reserved)
+    abi.check(load_hip().rbrt_hip_denoise_halves(device, C.c_void_p(stream or 0), C.c_void_p(d_a), C.c_void_p(d_b),
+                                                 C.c_void_p(d_wa or 0), width, height, C.byref(d), C.c_void_p(d_radiance or 0),
+                                                 C.c_void_p(d_rgb8 or 0)))

@@ -151,6 +151,10 @@ class AdaptiveResult(C.Structure):  # rbrt_adaptive_result_t
     _fields_ = [("rounds", C.c_uint32), ("reserved", C.c_uint32), ("samples", C.c_uint64), ("samples_fixed", C.c_uint64)]
 
 
+class DenoiseOpts(C.Structure):  # rbrt_denoise_opts_t
+    _fields_ = [("window_radius", C.c_uint32), ("patch_radius", C.c_uint32), ("strength", C.c_float), ("reserved", C.c_uint32)]
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("rays", C.c_uint64),
@@ -213,6 +217,10 @@ HIP_SYMBOLS = {
                                          f32p, u8p]),
     "rbrt_hip_render_adaptive": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderOpts), C.POINTER(AdaptiveOpts), C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AdaptiveResult)]),
+    "rbrt_denoise_opts_default": (None, [C.POINTER(DenoiseOpts)]),
+    "rbrt_hip_denoise_halves": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                          C.POINTER(DenoiseOpts), C.c_void_p, C.c_void_p]),
+    "rbrt_hip_scene_denoise": (C.c_int, [C.c_void_p, C.POINTER(DenoiseOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 # ... and include/rbrt_hip_debug.h (test hooks and diagnostics, same library)
 DEBUG_SYMBOLS = {

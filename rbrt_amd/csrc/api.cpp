@@ -37,6 +37,8 @@ hipError_t launch_resolve_even(const TraceParams& P, const ResolveParams& R, uin
 hipError_t launch_adaptive_lists(const AdaptiveParams& A, hipStream_t stream);
 hipError_t launch_tile_error(const AdaptiveParams& A, uint32_t n_active_tiles, hipStream_t stream);
 hipError_t launch_adaptive_finish(const AdaptiveParams& A, hipStream_t stream);
+hipError_t launch_denoise(const DenoiseParams& D, hipStream_t stream);                 // denoise.hip
+hipError_t launch_denoise_halves(const DenoiseHalvesParams& Q, hipStream_t stream);
 hipError_t launch_unpack(const float* gathered, uint32_t width, uint32_t height, uint32_t world,
                          size_t rank_stride_pixels, float* out_radiance, uint8_t* out_rgb8, hipStream_t stream);
 hipError_t launch_trace_rays(const TraceParams& P, const float* rays, size_t n, float* out_t, int32_t* out_obj,
@@ -349,6 +351,14 @@ struct rbrt_hip_scene {
         size_t cull_words = 0, local_tiles = 0;
         hipEvent_t ev_lists = nullptr;
         std::vector<uint32_t> round_active;  // tiles active at the start of each round of the last call (rbrt_hip_debug.h)
+        // What rbrt_hip_scene_denoise needs of the last call: its image and partition, and whether it ran to its end. The
+        // denoiser's row-major half images A, B and their mix wa (dev_alloc, grown on demand like the sums).
+        struct Last {
+            bool any = false, complete = false;
+            uint32_t width = 0, height = 0, world = 1, spp = 0, tiles_x = 0;
+        } last;
+        float *d_half_a = nullptr, *d_half_b = nullptr, *d_wa = nullptr;
+        size_t half_pixels = 0;
     } adaptive;
     bool poison_samples = false;      // RBRT_POISON_SAMPLES
     // host copy of the objects' bounds, for the tile-direction choice below
@@ -2101,6 +2111,9 @@ int rbrt_hip_render_adaptive(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, cons
     rbrt_adaptive_result_t res{};
     auto& S = s->adaptive;
     S.round_active.clear();
+    S.last.any = true, S.last.complete = false;
+    S.last.width = cam->img_width_pix, S.last.height = cam->img_height_pix, S.last.world = o->tile_world ? o->tile_world : 1, S.last.spp = N;
+    S.last.tiles_x = (cam->img_width_pix + RBRT_TILE - 1) / RBRT_TILE;
     CallPlan c{stream, 0, std::min(a->min_samples, N)};
     AdaptiveParams A;
     std::memset(&A, 0, sizeof(A));
@@ -2157,6 +2170,76 @@ int rbrt_hip_render_adaptive(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, cons
         res.samples += inside * counts[tl], res.samples_fixed += inside * N;
     }
     if (out) *out = res;
+    S.last.complete = true;
+    return RBRT_OK;
+}
+
+// ---- Denoising (the rule: include/rbrt_hip.h; the kernels: denoise.hip) ----------------------------------------------------
+void rbrt_denoise_opts_default(rbrt_denoise_opts_t* o) {
+    if (!o) return;
+    o->window_radius = 5, o->patch_radius = 3, o->strength = 0.7f, o->reserved = 0;
+}
+
+static int check_denoise_opts(const rbrt_denoise_opts_t* d) {
+    if (d->reserved != 0u) return fail(RBRT_ERR_INVALID_ARG, "denoise: reserved must be 0");
+    if (d->window_radius > 10u) return fail(RBRT_ERR_INVALID_ARG, "denoise: window_radius must be 0..10");
+    if (d->patch_radius > 4u) return fail(RBRT_ERR_INVALID_ARG, "denoise: patch_radius must be 0..4");
+    if (!std::isfinite(d->strength) || !(d->strength > 0.0f)) return fail(RBRT_ERR_INVALID_ARG, "denoise: strength must be finite and > 0");
+    return RBRT_OK;
+}
+
+static DenoiseParams denoise_params(const float* a, const float* b, const float* wa, uint32_t width, uint32_t height,
+                                    const rbrt_denoise_opts_t* d, float* d_radiance, uint8_t* d_rgb8) {
+    DenoiseParams D;
+    std::memset(&D, 0, sizeof(D));
+    D.a = a, D.b = b, D.wa = wa, D.width = width, D.height = height;
+    D.window_radius = int32_t(d->window_radius), D.patch_radius = int32_t(d->patch_radius), D.k2 = d->strength * d->strength;
+    D.out_radiance = d_radiance, D.out_rgb8 = d_rgb8;
+    return D;
+}
+
+int rbrt_hip_denoise_halves(int device, void* stream, const float* d_a, const float* d_b, const float* d_wa, uint32_t width,
+                            uint32_t height, const rbrt_denoise_opts_t* d, float* d_radiance, uint8_t* d_rgb8) {
+    if (!d_a || !d_b || !d) return fail(RBRT_ERR_INVALID_ARG, "denoise_halves: null argument");
+    if (int rc = check_denoise_opts(d)) return rc;
+    if (width == 0 || height == 0) return fail(RBRT_ERR_INVALID_ARG, "denoise_halves: width and height must be >= 1");
+    if (uint64_t(width) * height >= (1ull << 32)) return fail(RBRT_ERR_UNSUPPORTED, "image has 2^32 or more pixels");
+    if (int rc = ensure_device(device)) return rc;
+    if (!d_radiance && !d_rgb8) return RBRT_OK;
+    HIP_TRY(launch_denoise(denoise_params(d_a, d_b, d_wa, width, height, d, d_radiance, d_rgb8), static_cast<hipStream_t>(stream)));
+    return RBRT_OK;
+}
+
+int rbrt_hip_scene_denoise(rbrt_hip_scene_t* s, const rbrt_denoise_opts_t* d, void* stream_v, float* d_radiance, uint8_t* d_rgb8,
+                           float* d_half_a, float* d_half_b) {
+    if (!s || !d) return fail(RBRT_ERR_INVALID_ARG, "scene_denoise: null argument");
+    if (int rc = check_denoise_opts(d)) return rc;
+    auto& S = s->adaptive;
+    if (!S.last.any) return fail(RBRT_ERR_INVALID_ARG, "scene_denoise: no adaptive render on this scene yet");
+    if (S.last.world > 1u)
+        return fail(RBRT_ERR_UNSUPPORTED, "scene_denoise: the last adaptive render had tile_world > 1 (a rank lacks its neighbours' pixels)");
+    if (S.last.spp < 2u) return fail(RBRT_ERR_INVALID_ARG, "scene_denoise: the last adaptive render had spp < 2 (a half would be empty)");
+    if (!S.last.complete) return fail(RBRT_ERR_INVALID_ARG, "scene_denoise: the last adaptive render did not complete");
+    HIP_TRY(hipSetDevice(s->device));
+    const hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    const size_t npix = size_t(S.last.width) * S.last.height;
+    {
+        std::lock_guard<std::mutex> watcher_lock(s->mu);  // (dev_alloc)
+        if (npix > S.half_pixels) {
+            void* p = nullptr;
+            HIP_TRY(dev_alloc(s, npix * 7u * sizeof(float), &p));  // one piece: A, B, wa
+            S.d_half_a = static_cast<float*>(p), S.d_half_b = S.d_half_a + npix * 3u, S.d_wa = S.d_half_b + npix * 3u;
+            S.half_pixels = npix;
+        }
+    }
+    DenoiseHalvesParams Q;
+    std::memset(&Q, 0, sizeof(Q));
+    Q.acc = S.d_sum, Q.acc_even = S.d_sum_even, Q.tile_samples = S.d_tile_samples;
+    Q.width = S.last.width, Q.height = S.last.height, Q.tiles_x = S.last.tiles_x;
+    Q.a = S.d_half_a, Q.b = S.d_half_b, Q.wa = S.d_wa, Q.out_a = d_half_a, Q.out_b = d_half_b;
+    HIP_TRY(launch_denoise_halves(Q, stream));
+    if (!d_radiance && !d_rgb8) return RBRT_OK;
+    HIP_TRY(launch_denoise(denoise_params(S.d_half_a, S.d_half_b, S.d_wa, S.last.width, S.last.height, d, d_radiance, d_rgb8), stream));
     return RBRT_OK;
 }
 

@@ -238,4 +238,29 @@ struct AdaptiveParams {
     uint8_t* out_rgb8;
 };
 
+// The denoiser (include/rbrt_hip.h "Denoising"; denoise.hip): one rbrt_hip_denoise_halves / rbrt_hip_scene_denoise call.
+struct DenoiseParams {
+    const float* a;        // [H][W][3] the two half images
+    const float* b;
+    const float* wa;       // [H][W] the share of `a`, or null: 0.5 everywhere
+    uint32_t width, height;
+    int32_t window_radius, patch_radius;
+    float k2;              // strength * strength
+    float* out_radiance;   // [H][W][3], may be null
+    uint8_t* out_rgb8;     // [H][W][3], may be null
+};
+
+// ... and the step in front of it on a handle: the packed sums of the last adaptive call -> row-major A, B and wa.
+struct DenoiseHalvesParams {
+    const float* acc;             // S and S_even (AdaptiveParams::acc, ::acc_even), tile_world = 1
+    const float* acc_even;
+    const uint32_t* tile_samples; // [n_tiles] n_t
+    uint32_t width, height, tiles_x;
+    float* a;                     // [H][W][3]
+    float* b;
+    float* wa;                    // [H][W]
+    float* out_a;                 // copies of a and b for the caller, may be null
+    float* out_b;
+};
+
 }  // namespace rbrt

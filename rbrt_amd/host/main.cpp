@@ -6,7 +6,9 @@
 // --background R,G,B (a constant background instead of the reference's sky gradient), --aperture MM and
 // --focus-distance D (a thin lens: they override the YAML's camera_aperture_mm / camera_focus_distance), --shading flat|smooth
 // (overrides every mesh blueprint's `shading`), --adaptive THRESHOLD with --min-samples N and --adaptive-step K (adaptive sampling:
-// --samples is the limit), --sample-map FILE (the per-pixel sample count of an adaptive render, scaled to 0-255).
+// --samples is the limit), --sample-map FILE (the per-pixel sample count of an adaptive render, scaled to 0-255), --denoise with
+// --denoise-radius R, --denoise-patch P and --denoise-strength K (the target file gets the dual-buffer non-local-means filter of
+// the render's two half images), --noisy FILE (also the unfiltered image).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -55,6 +57,14 @@ void usage() {
         "      --adaptive-step <k>          adaptive: samples of every later round, at least 1 [default: 64]\n"
         "      --sample-map <file>          adaptive: write the per-pixel sample count there, scaled to 0-255 (same formats as\n"
         "                                   the target file)\n"
+        "      --denoise                    filter the image: a dual-buffer non-local-means filter on the images of the even and\n"
+        "                                   the odd samples; the target file gets the filtered image. Renders through the adaptive\n"
+        "                                   path (without --adaptive: one round, the fixed render), so it cannot be combined with\n"
+        "                                   --gpus > 1, --checkpoint or --pass-samples; --samples must be at least 2\n"
+        "      --denoise-radius <r>         denoise: radius of the search window, 0 to 10 [default: 5]\n"
+        "      --denoise-patch <p>          denoise: radius of the compared patches, 0 to 4 [default: 3]\n"
+        "      --denoise-strength <k>       denoise: filter strength, above 0; larger smooths more [default: 0.7]\n"
+        "      --noisy <file>               denoise: also write the unfiltered image there (same formats as the target file)\n"
         "  -h, --help                       Print help\n"
         "  -V, --version                    Print version\n");
 }
@@ -128,6 +138,10 @@ int main(int argc, char** argv) {
     // for 1 % more samples: profiles/adaptive_config2.txt)
     uint32_t min_samples = 16, adaptive_step = 64;
     std::string sample_map;
+    bool denoise = false;
+    std::optional<uint32_t> denoise_radius, denoise_patch;
+    std::optional<float> denoise_strength;
+    std::string noisy;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         std::string val;
@@ -216,6 +230,31 @@ int main(int argc, char** argv) {
             u32(adaptive_step);
         } else if (a == "--sample-map") {
             sample_map = value();
+        } else if (a == "--denoise") {
+            if (has_val) {
+                std::fprintf(stderr, "error: '--denoise' takes no value\n");
+                return 2;
+            }
+            denoise = true;
+        } else if (a == "--denoise-radius" || a == "--denoise-patch") {
+            const bool radius = a == "--denoise-radius";
+            uint32_t v = 0;
+            u32(v);
+            if (v > (radius ? 10u : 4u)) {
+                std::fprintf(stderr, "error: invalid value '%u' for '%s' (expected 0 to %u)\n", v, a.c_str(), radius ? 10u : 4u);
+                return 2;
+            }
+            (radius ? denoise_radius : denoise_patch) = v;
+        } else if (a == "--denoise-strength") {
+            const char* v = value();
+            float f = 0.0f;
+            if (!parse_f32(v, f) || !std::isfinite(f) || !(f > 0.0f)) {
+                std::fprintf(stderr, "error: invalid value '%s' for '--denoise-strength' (expected a finite number > 0)\n", v);
+                return 2;
+            }
+            denoise_strength = f;
+        } else if (a == "--noisy") {
+            noisy = value();
         } else if (a == "--shading") {
             const std::string v = value();
             if (v != "flat" && v != "smooth") {
@@ -245,6 +284,24 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "error: '--sample-map' needs '--adaptive'\n");
         return 2;
     }
+    if (denoise) {  // the filter's input is the adaptive path's sums: it inherits that path's refusals, by name, before anything is loaded
+        const char* with = gpus > 1 ? "--gpus > 1" : !checkpoint.empty() ? "--checkpoint" : pass_samples != 0 ? "--pass-samples" : nullptr;
+        if (with) {
+            std::fprintf(stderr, "error: '--denoise' cannot be combined with '%s'\n", with);
+            return 2;
+        }
+        if (samples < 2) {
+            std::fprintf(stderr, "error: '--denoise' needs '--samples' of at least 2 (each half image needs a sample)\n");
+            return 2;
+        }
+    } else {
+        const char* alone = denoise_radius ? "--denoise-radius" : denoise_patch ? "--denoise-patch" : denoise_strength ? "--denoise-strength"
+                            : !noisy.empty() ? "--noisy" : nullptr;
+        if (alone) {
+            std::fprintf(stderr, "error: '%s' needs '--denoise'\n", alone);
+            return 2;
+        }
+    }
     using clock = std::chrono::steady_clock;
     const auto secs = [](clock::time_point a, clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
     try {
@@ -271,17 +328,24 @@ int main(int argc, char** argv) {
         cfg.constant_background = constant_background;
         for (int c = 0; c < 3; ++c) cfg.background[c] = background[c];
         if (adaptive) cfg.adaptive = true, cfg.adaptive_threshold = *adaptive, cfg.adaptive_min_samples = min_samples, cfg.adaptive_step = adaptive_step;
+        if (denoise) {
+            cfg.denoise = true, cfg.keep_noisy = !noisy.empty();
+            if (denoise_radius) cfg.denoise_window_radius = *denoise_radius;
+            if (denoise_patch) cfg.denoise_patch_radius = *denoise_patch;
+            if (denoise_strength) cfg.denoise_strength = *denoise_strength;
+        }
         rbrt::ImageBuffer img = rbrt::render_scene(cam, samples, scene, cfg);
         std::printf("Saving rendered image to %s\n", target.c_str());
         const auto t3 = clock::now();
         img.save(target);
         if (!sample_map.empty()) img.save_sample_map(sample_map);
+        if (!noisy.empty()) img.save_noisy(noisy);
         const auto t4 = clock::now();
         if (!report_path.empty()) {
             uint64_t triangles = 0;
             for (const auto& m : scene.triangle_meshes) triangles += m.num_triangles;
             const uint32_t spp = samples_arg_for_report(samples);
-            const double rendered = adaptive ? double(rep.adaptive_samples)
+            const double rendered = adaptive || denoise ? double(rep.adaptive_samples)
                                              : double(width) * double(height) * double(spp - rep.resumed_from_sample);  // path samples of THIS run
             std::string js = "{";
             const auto str = [&](const char* k, const std::string& v) { js += std::string("\"") + k + "\": \"" + json_escape(v) + "\", "; };
@@ -305,6 +369,10 @@ int main(int argc, char** argv) {
                 js += "\"active_tiles_per_round\": [";
                 for (size_t k = 0; k < rep.adaptive_active_tiles.size(); ++k) js += (k ? ", " : "") + std::to_string(rep.adaptive_active_tiles[k]);
                 js += "], ";
+            }
+            if (denoise) {  // the filter's parameters and its time on the GPU (a part of render_s)
+                num("denoise_window_radius", cfg.denoise_window_radius, "%.0f"), num("denoise_patch_radius", cfg.denoise_patch_radius, "%.0f");
+                num("denoise_strength", cfg.denoise_strength, "%.9g"), num("denoise_ms", rep.denoise_ms, "%.4f");
             }
             // where the run's time went; the parts add up to total_s (other_s is what none of them covers: thread start,
             // checkpoint look-up, the report itself)

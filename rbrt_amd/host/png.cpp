@@ -209,6 +209,13 @@ void ImageBuffer::save_sample_map(const std::string& path) const {
     grey.save(path);
 }
 
+void ImageBuffer::save_noisy(const std::string& path) const {
+    if (noisy_rgb.size() != size_t(width) * height * 3) throw Error("no unfiltered image to save to " + path + ": the render was not denoised");
+    ImageBuffer noisy;
+    noisy.width = width, noisy.height = height, noisy.rgb = noisy_rgb;
+    noisy.save(path);
+}
+
 void ImageBuffer::save(const std::string& path) const {
     std::string ext;
     const size_t dot = path.find_last_of('.');

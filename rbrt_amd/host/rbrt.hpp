@@ -216,8 +216,10 @@ struct ImageBuffer {
     std::vector<uint8_t> rgb;        // row-major, 3 bytes per pixel
     std::vector<float> radiance;     // row-major fp32 pre-gamma mean (extra to the reference)
     std::vector<uint8_t> sample_map; // an adaptive render: one byte per pixel, its tile's sample count * 255 / samples (else empty)
+    std::vector<uint8_t> noisy_rgb;  // a denoised render with RenderConfig::keep_noisy: the unfiltered image, like rgb (else empty)
     void save(const std::string& path) const;  // .png (8-bit RGB) or .ppm by extension
     void save_sample_map(const std::string& path) const;  // the sample map as a grey image, through the same writers
+    void save_noisy(const std::string& path) const;       // the unfiltered image of a denoised render, through the same writers
 };
 void write_png(const std::string& path, const uint8_t* rgb, uint32_t width, uint32_t height);
 
@@ -242,6 +244,7 @@ struct RenderReport {
     uint32_t adaptive_rounds = 0;
     uint64_t adaptive_samples = 0, adaptive_samples_fixed = 0;
     std::vector<uint32_t> adaptive_active_tiles;
+    double denoise_ms = 0.0;  // a denoised render (RenderConfig::denoise): rbrt_hip_scene_denoise on the GPU, between two events
 };
 
 struct RenderConfig {  // additions that the reference hard-codes or lacks
@@ -263,6 +266,14 @@ struct RenderConfig {  // additions that the reference hard-codes or lacks
     bool adaptive = false;
     float adaptive_threshold = 0.0f;
     uint32_t adaptive_min_samples = 16, adaptive_step = 64;  // (the step: profiles/adaptive_config2.txt)
+    // Denoising (rbrt_hip_scene_denoise; the CLI's --denoise): the image is the dual-buffer non-local-means filter of the
+    // render's two half sums. It works on the sums of the adaptive path: without `adaptive` the render goes through that path
+    // with threshold 0 and min_samples = step = num_samples, which is one round and bit for bit the fixed render. Inherits
+    // every refusal of `adaptive`; num_samples must be at least 2 (a half would be empty).
+    bool denoise = false;
+    uint32_t denoise_window_radius = 5, denoise_patch_radius = 3;  // (rbrt_denoise_opts_default)
+    float denoise_strength = 0.7f;
+    bool keep_noisy = false;  // also keep the unfiltered RGB8 image (ImageBuffer::noisy_rgb)
 };
 // rbrt_lib::render_scene (lib.rs:75-79): blocks until the image is complete. Runs on the GPU(s)
 // through the C ABI; there is no CPU path.

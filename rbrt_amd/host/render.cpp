@@ -154,7 +154,10 @@ double seconds_since(std::chrono::steady_clock::time_point t0) {
 
 }  // namespace
 
-ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& scene, const RenderConfig& cfg) {
+ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& scene, const RenderConfig& cfg_in) {
+    RenderConfig cfg = cfg_in;
+    if (cfg.denoise && !cfg.adaptive)  // (the filter's input is the adaptive path's sums: one round that stops nothing)
+        cfg.adaptive = true, cfg.adaptive_threshold = 0.0f, cfg.adaptive_min_samples = cfg.adaptive_step = std::max(num_samples, 2u);
     if (!cfg.quiet) std::printf("Starting rendering...\n");
     // (every rank's calls get &c, the camera inside its lens: with RBRT_FLAG_THIN_LENS the library reads the lens past it)
     const rbrt_camera_lens_t lens = cam.to_abi_lens();
@@ -177,10 +180,12 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
     img.radiance.assign(n, 0.0f);
     if (num_samples == 0) throw Error("the number of samples must be at least 1");
     if (cfg.adaptive) {  // (one blocking call of one GPU: rbrt_hip.h "Adaptive sampling")
-        if (cfg.n_gpus > 1) throw Error("--adaptive cannot be combined with --gpus > 1");
-        if (!cfg.checkpoint_path.empty()) throw Error("--adaptive cannot be combined with --checkpoint");
-        if (cfg.pass_spp != 0) throw Error("--adaptive cannot be combined with --pass-samples");
+        const std::string who = cfg_in.adaptive ? "--adaptive" : "--denoise";
+        if (cfg.n_gpus > 1) throw Error(who + " cannot be combined with --gpus > 1");
+        if (!cfg.checkpoint_path.empty()) throw Error(who + " cannot be combined with --checkpoint");
+        if (cfg.pass_spp != 0) throw Error(who + " cannot be combined with --pass-samples");
     }
+    if (cfg.denoise && num_samples < 2) throw Error("--denoise needs at least 2 samples (each half image needs one)");
 
     const auto t_hip0 = std::chrono::steady_clock::now();
     const int n_dev = rbrt_hip_device_count();  // (the process's first HIP call: the runtime starts here)
@@ -389,6 +394,25 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
                         const uint32_t t = rbrt_hip_tile_number(row / RBRT_TILE, col / RBRT_TILE, tiles_x);
                         img.sample_map[size_t(row) * img.width + col] = uint8_t(uint64_t(counts[t]) * 255u / num_samples);
                     }
+            }
+            if (!failed && cfg.denoise) {
+                // the filter works on the handle's sums and writes over the unfiltered image (kept first where it is wanted)
+                if (cfg.keep_noisy) {
+                    img.noisy_rgb.resize(n);
+                    hip_ok(hipMemcpy(img.noisy_rgb.data(), d_rgb, n, hipMemcpyDeviceToHost), "download of the unfiltered image");
+                }
+                const rbrt_denoise_opts_t dn = {cfg.denoise_window_radius, cfg.denoise_patch_radius, cfg.denoise_strength, 0u};
+                hipEvent_t e0 = nullptr, e1 = nullptr;
+                if (hip_ok(hipEventCreate(&e0), "hipEventCreate") && hip_ok(hipEventCreate(&e1), "hipEventCreate")) {
+                    hip_ok(hipEventRecord(e0, stream), "hipEventRecord");
+                    if (rbrt_hip_scene_denoise(hs, &dn, stream, d_rad, d_rgb, nullptr, nullptr) != RBRT_OK) fail(rbrt_hip_last_error());
+                    hip_ok(hipEventRecord(e1, stream), "hipEventRecord");
+                    float ms = 0.0f;
+                    if (hip_ok(hipStreamSynchronize(stream), "denoise") && !failed && hip_ok(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime"))
+                        rep.denoise_ms = ms;
+                }
+                if (e0) (void)hipEventDestroy(e0);
+                if (e1) (void)hipEventDestroy(e1);
             }
         }
         for (uint64_t b = start_sample; b < num_samples && !cfg.adaptive; b += pass_spp, ++pass_no) {

@@ -284,6 +284,9 @@ def test_threshold_zero_under_other_schedules(hip, data, tmp_path, rid, env, pip
 
 # ---- 5. the handle's other state ----------------------------------------------------------------------------------------------
 def test_plain_renders_before_and_after_and_two_sizes_on_one_handle(hip, data):
+    """Two image sizes and cameras on one handle, plain renders around every adaptive call. Both sizes, 37 x 21 and 40 x 24,
+    are 5 x 3 = 15 tiles: the adaptive state is sized by tiles, so it is allocated once here and never grows. Growth and the
+    shrink after it are covered by test_adaptive_many_tiles_gpu.py (test_the_adaptive_state_grows_and_shrinks_on_one_handle)."""
     import torch
     a, b = data["spheres_37x21"], data["spheres_40x24"]
 
@@ -294,7 +297,7 @@ def test_plain_renders_before_and_after_and_two_sizes_on_one_handle(hip, data):
         return t.cpu().numpy()
 
     with hip.HipScene(a.sc) as hs:
-        for c in (a, b, a):  # (the second size is the larger one: the state grows; then the smaller one again)
+        for c in (a, b, a):  # (the second size is the larger image, of as many tiles; then the smaller one again)
             before = plain(hs, c)
             assert np.array_equal(bits(before), bits(c.rest["zero"].image))
             for kind in ("median", "zero"):

@@ -3,7 +3,8 @@ bit for bit, and against a converged render.
 
 Synthetic halves go through denoise_halves: a smooth ramp plus noise (weights between 0 and 1), a block with A == B exactly
 (V = 0) and a block of values up to 1e6; sizes below the window, ragged, several workgroups, and one below / at / one above
-the kernel's tile edge (RBRT_DENOISE_TILE) in each direction. Through a handle the cases are test_adaptive_gpu.py's: the
+the kernel's tile edge (RBRT_DENOISE_TILE) in each direction; then sizes with workgroups whose halo lies wholly inside the
+image and grids of three to five workgroups in a direction (INTERIOR_SIZES). Through a handle the cases are test_adaptive_gpu.py's: the
 samples come from render_pass, the tile counts from np_adaptive, the thresholds from the restatement."""
 from __future__ import annotations
 
@@ -36,6 +37,15 @@ SIZES = [(1, 1), (5, 3), (8, 8), (37, 21), (40, 24),
          (EDGE - 1, 3), (EDGE, 3), (EDGE + 1, 3), (3, EDGE - 1), (3, EDGE), (3, EDGE + 1)]
 #          R  P  strength
 PARAMS = [(0, 0, 0.7), (1, 0, 0.45), (0, 3, 0.7), (2, 1, 1.3), (5, 3, 0.7), (10, 4, 0.7)]
+# Sizes with workgroups away from the image's edges (a workgroup is EDGE x EDGE = 16 x 16 pixels, its staged halo R + P):
+INTERIOR_SIZES = [(48, 48),   # 3 x 3 workgroups: the centre one's halo is wholly inside even at R 10, P 4 (16 - 14 >= 0, 32 + 14 <= 48)
+                  (50, 47),   # the same, with ragged last workgroups of 2 columns and 15 rows
+                  (80, 17),   # five workgroups across; the second row of workgroups is one pixel high: the offsets it skips
+                  (17, 80),   # (no q inside) differ from its neighbours'; and the same the other way round
+                  (64, 33)]   # four across, a third row of one pixel
+# ... at every row of PARAMS and at the two extremes of the staged edge against the edge of the delta area: the widest
+# window with no patch, and the widest patch (three delta positions a thread) with the smallest window
+INTERIOR_PARAMS = PARAMS + [(10, 0, 0.7), (1, 4, 0.7)]
 
 
 def bits(a):
@@ -98,9 +108,8 @@ def test_the_synthetic_inputs_exercise_the_weights():
     assert ((w > 0.01) & (w < 0.99)).sum() > 100 and (w == 0).any() and (w > 0.9).any(), np.histogram(w, 10, (0, 1))[0]
 
 
-@pytest.mark.parametrize("R,P,k", PARAMS, ids=[f"R{r}_P{p}" for r, p, _ in PARAMS])
-@pytest.mark.parametrize("w,h", SIZES, ids=[f"{w}x{h}" for w, h in SIZES])
-def test_halves_against_the_restatement(hip, w, h, R, P, k):
+def check_halves(hip, w, h, R, P, k):
+    """One synthetic case through denoise_halves, every way of asking for its outputs."""
     import torch
     a, b, wa, ah, bh = expected(w, h, R, P, k)
     exp = D.mix(ah, bh, wa)
@@ -119,6 +128,41 @@ def test_halves_against_the_restatement(hip, w, h, R, P, k):
     assert np.isnan(rad).all() and np.array_equal(rgb, D.quantise(exp))
     if R == 0:  # the identity: no filtering at all
         assert np.array_equal(bits(exp), bits(D.mix(a, b, wa)))
+
+
+@pytest.mark.parametrize("R,P,k", PARAMS, ids=[f"R{r}_P{p}" for r, p, _ in PARAMS])
+@pytest.mark.parametrize("w,h", SIZES, ids=[f"{w}x{h}" for w, h in SIZES])
+def test_halves_against_the_restatement(hip, w, h, R, P, k):
+    check_halves(hip, w, h, R, P, k)
+
+
+def test_the_centre_workgroup_of_48x48_has_weights_between_0_and_1():
+    """A condition on the inputs: synthetic()'s A == B quarter and its quarter of large values move with the size. At 48 x 48
+    and the default parameters the pixels of the centre workgroup (rows and columns 16..31) have weights strictly between
+    0.01 and 0.99 for more than 100 (pixel, offset) pairs: the one workgroup whose staged tile is clipped nowhere is neither
+    all 0 nor all 1."""
+    a, b, wa = synthetic(48, 48)
+    V = D.variance(a, b)
+    R, P, k = (D.DEFAULTS[n] for n in ("window_radius", "patch_radius", "strength"))
+    k2 = f32(k) * f32(k)
+    pairs = 0
+    for dy in range(-R, R + 1):
+        for dx in range(-R, R + 1):
+            w = D.weight(D.patch_distance(b, V, dy, dx, P, k2))[16:32, 16:32]
+            pairs += int(((w > 0.01) & (w < 0.99)).sum())
+    assert pairs > 100, pairs
+
+
+@pytest.mark.parametrize("R,P,k", INTERIOR_PARAMS, ids=[f"R{r}_P{p}" for r, p, _ in INTERIOR_PARAMS])
+@pytest.mark.parametrize("w,h", INTERIOR_SIZES, ids=[f"{w}x{h}" for w, h in INTERIOR_SIZES])
+def test_halves_with_interior_workgroups(hip, w, h, R, P, k):
+    """Workgroups whose whole halo is inside the image, and grids with a middle row and a middle column of workgroups: the
+    delta, row-sum and skip logic without the clipping that could mask an error in it."""
+    assert 0.45 <= k <= 1.3
+    a, b, wa, ah, bh = expected(w, h, R, P, k)
+    assert np.isfinite(ah).all() and np.isfinite(bh).all()  # (non-finite halves are outside the rule: fminf and np.minimum differ on NaN)
+    assert (w + EDGE - 1) // EDGE >= 3 or (h + EDGE - 1) // EDGE >= 3
+    check_halves(hip, w, h, R, P, k)
 
 
 def test_a_tiny_strength_filters_nothing(hip):

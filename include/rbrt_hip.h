@@ -57,7 +57,9 @@ extern "C" {
                               two *_shaded entry points: rbrt_mesh_t and rbrt_scene_t stay as they are), nor adaptive
                               sampling (rbrt_hip_render_adaptive with its two structs: an added entry point), nor the
                               denoiser (rbrt_denoise_opts_t, rbrt_denoise_opts_default, rbrt_hip_denoise_halves and
-                              rbrt_hip_scene_denoise: added entry points) */
+                              rbrt_hip_scene_denoise: added entry points), nor environment lighting (rbrt_environment_t and
+                              rbrt_hip_scene_set_environment: an added struct and entry point, no new flag bit, every
+                              existing struct untouched; a host detects it by the symbol) */
 
 typedef enum rbrt_status {
     RBRT_OK = 0,
@@ -219,7 +221,8 @@ typedef struct rbrt_render_opts {
 /* A ray that hits nothing returns `bg` exactly, instead of the reference's sky gradient t*(1,1,1) + (1-t)*bg
  * (lib.rs:68-71), which is white at the zenith whatever bg is. For dark scenes lit by RBRT_MAT_EMISSIVE objects.
  * Honoured by rbrt_hip_render, _render_device and _render_pass; every pass of one rbrt_hip_render_pass series must use
- * the same flag and bg, as it must use the same seed. */
+ * the same flag and bg, as it must use the same seed -- and the same environment (rbrt_hip_scene_set_environment), which
+ * takes the place of both while the handle has one. */
 #define RBRT_FLAG_CONSTANT_BACKGROUND 2u
 /* A thin lens (no counterpart in the reference, whose cam.rs:64-82 starts every ray at the position): camera rays start on
  * an elliptic disc around the position and all rays through one point of the image plane meet on the focus surface,
@@ -444,6 +447,52 @@ int rbrt_hip_denoise_halves(int device, void* stream, const float* d_a, const fl
  * RBRT_ERR_UNSUPPORTED: the last adaptive render had tile_world > 1. */
 int rbrt_hip_scene_denoise(rbrt_hip_scene_t* scene, const rbrt_denoise_opts_t* opts, void* stream,
                            float* d_radiance, uint8_t* d_rgb8, float* d_half_a, float* d_half_b);
+
+/* ---- Environment lighting: an octahedral radiance map for the rays that hit nothing ---------------------------------------
+ * No counterpart in the reference, whose rays that hit nothing see the sky gradient (lib.rs:68-71). An environment of size N
+ * (1 <= N <= 4096) is a square grid of (N + 1) x (N + 1) NODES E[j][i], j the row, each a linear RGB radiance. The nodes are
+ * the corners of N x N cells, so the bilinear interpolation never reads outside the grid; the octahedral fold identifies the
+ * boundary nodes that belong to the same direction (E[0][i] and E[0][N - i], E[N][i] and E[N][N - i], E[j][0] and E[N - j][0],
+ * E[j][N] and E[N - j][N]: a map that is to be continuous holds equal values there). +y is up, as in the sky gradient.
+ *
+ * The rule. All arithmetic is float32, unfused, in the written order; / is correctly rounded. For the direction d of the ray
+ * that hit nothing, as it was traced and not re-normalised:
+ *     s  = (|dx| + |dy|) + |dz|
+ *     px = dx / s;  py = dy / s;  pz = dz / s
+ *     if py >= 0:  u = px;  v = pz
+ *     else:        u = (1 - |pz|) * (px >= 0 ? 1 : -1);   v = (1 - |px|) * (pz >= 0 ? 1 : -1)
+ *     x  = ((u * 0.5f) + 0.5f) * float(N);    y = ((v * 0.5f) + 0.5f) * float(N)
+ *     i  = x >= 0 ? min(uint(floor(x)), N - 1) : 0      (a NaN compares false: i = 0);   j likewise from y
+ *     fx = x - float(i);   fy = y - float(j)
+ *     per channel c:
+ *       top = E[j][i]   + fx * (E[j][i+1]   - E[j][i])
+ *       bot = E[j+1][i] + fx * (E[j+1][i+1] - E[j+1][i])
+ *       L_c = top + fy * (bot - top)
+ * L takes the place of the background: colorize returns it for the ray that hit nothing (the path's fold a1 * (a2 * (... * L))
+ * starts from it), in the trace kernel and in the kernels that finish background-only tiles alike. The a + f * (b - a) form
+ * makes a constant map return its constant exactly. For every finite non-zero direction i and j stay in [0, N - 1] and fx, fy
+ * in [0, 1]. Whatever d is, i and j stay in [0, N - 1] (a NaN compares false), so no read is ever outside the map; a NaN or
+ * zero direction gives a NaN colour (an infinite component gives a NaN colour or, where the rule's quotients are 0, a node's).
+ *
+ * The environment is a STATE OF THE HANDLE. While one is set, every render on the handle uses it for the rays that hit nothing
+ * -- rbrt_hip_render_device, _render_pass, _render_adaptive and through that rbrt_hip_scene_denoise -- and opts->bg and
+ * RBRT_FLAG_CONSTANT_BACKGROUND are ignored. Every pass of one rbrt_hip_render_pass series must use the same environment, as
+ * it must use the same seed, flag and bg. There is no flag bit: a host detects the capability by the symbol. The one-shot
+ * rbrt_hip_render and rbrt_hip_trace_rays have no environment. Nothing else changes: what is hit, the random streams, the
+ * scatter records, the tile pass, the order of the sums, the counters. */
+typedef struct rbrt_environment {
+    uint32_t n;         /* N, 1..4096 */
+    uint32_t reserved;  /* 0 */
+    const float* nodes; /* HOST, float[n+1][n+1][3], row j first; finite, >= 0 */
+} rbrt_environment_t;
+
+/* Sets, replaces (env != NULL) or clears (env == NULL: back to opts->bg) the handle's environment. THIS CALL BLOCKS: it waits for
+ * the handle's outstanding work, copies the nodes to device memory the handle owns (16 bytes per node; released when the map
+ * is replaced or cleared and by rbrt_hip_scene_destroy) and returns with the map in place. The threading rule of
+ * rbrt_hip_render_device holds.
+ * RBRT_ERR_INVALID_ARG, before the device is touched, the handle keeping the map it had: scene NULL; n == 0 or n > 4096;
+ * reserved != 0; nodes NULL; a non-finite or negative component. */
+int rbrt_hip_scene_set_environment(rbrt_hip_scene_t* scene, const rbrt_environment_t* env);
 
 /* De-interleave gathered per-rank packed tile buffers (concatenated rank 0..world-1, each
  * rbrt_hip_packed_pixels(...)*3 floats, device memory) into a row-major float[H][W][3] device

@@ -156,6 +156,11 @@ int rbrt_hip_debug_primary_cull_opts(rbrt_hip_scene_t* scene, const rbrt_camera_
 int rbrt_hip_debug_shading_normals(rbrt_hip_scene_t* scene, const float* rays, size_t n, float min_dist, float max_dist,
                                    float* out_normal);
 
+/* Test hook for environment lighting (rbrt_hip.h rbrt_environment_t): the lookup alone, for n directions (dx, dy, dz; host
+ * array, used as they are), through the same device function the trace kernel and the background-only kernels call.
+ * out_rgb: host float[n][3]. RBRT_ERR_INVALID_ARG when the handle has no environment. */
+int rbrt_hip_debug_environment(rbrt_hip_scene_t* scene, const float* dirs, size_t n, float* out_rgb);
+
 /* Kernel timing with HIP events recorded on the launch stream around every trace-kernel launch
  * (and the resolve kernel after it). set_timing(scene, 1) starts / restarts the accumulation;
  * kernel_ms sums the durations of all launches since then (it synchronises on the last event) and

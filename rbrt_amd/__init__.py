@@ -157,6 +157,32 @@ class HipScene:
         abi.check(self._lib.rbrt_hip_scene_denoise(self._h, C.byref(d), C.c_void_p(stream or 0), C.c_void_p(d_radiance or 0),
                                                    C.c_void_p(d_rgb8 or 0), C.c_void_p(d_half_a or 0), C.c_void_p(d_half_b or 0)))
 
+    def set_environment(self, nodes, *, n: int | None = None, reserved: int = 0):
+        """Sets the handle's environment map (rbrt_hip_scene_set_environment): `nodes` float32 (N + 1, N + 1, 3), N taken
+        from its shape; None clears it (rays that hit nothing see opts.bg again). Blocking. `n` and `reserved` put other
+        values into the struct (tests of the refusals; with `n` given, nodes = None is a NULL pointer in a struct)."""
+        if nodes is None and n is None:
+            abi.check(self._lib.rbrt_hip_scene_set_environment(self._h, None))
+            return
+        env = abi.Environment()
+        if nodes is not None:
+            nodes = np.ascontiguousarray(nodes, np.float32)
+            if n is None:
+                if nodes.ndim != 3 or nodes.shape[0] != nodes.shape[1] or nodes.shape[2] != 3 or nodes.shape[0] < 2:
+                    raise ValueError("set_environment: nodes must have shape (N + 1, N + 1, 3)")
+                n = nodes.shape[0] - 1
+            env.nodes = abi.fptr(nodes)
+        env.n, env.reserved = int(n), int(reserved)
+        abi.check(self._lib.rbrt_hip_scene_set_environment(self._h, C.byref(env)))
+
+    def environment_lookup(self, dirs):
+        """The environment's radiance for each direction, used as it is (rbrt_hip_debug_environment; test hook): float32
+        (n, 3)."""
+        dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        out = np.zeros((dirs.shape[0], 3), np.float32)
+        abi.check(self._lib.rbrt_hip_debug_environment(self._h, abi.fptr(dirs), dirs.shape[0], abi.fptr(out)))
+        return out
+
     def set_pipeline(self, depth: int):
         """Overlap consecutive trace launches over `depth` internal streams (rbrt_hip_scene_set_pipeline)."""
         abi.check(self._lib.rbrt_hip_scene_set_pipeline(self._h, int(depth)))

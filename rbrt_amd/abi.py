@@ -155,6 +155,11 @@ class DenoiseOpts(C.Structure):  # rbrt_denoise_opts_t
     _fields_ = [("window_radius", C.c_uint32), ("patch_radius", C.c_uint32), ("strength", C.c_float), ("reserved", C.c_uint32)]
 
 
+class Environment(C.Structure):  # rbrt_environment_t
+    """An octahedral radiance map of (n + 1) x (n + 1) nodes: `nodes` points at host float32 [n + 1][n + 1][3]."""
+    _fields_ = [("n", C.c_uint32), ("reserved", C.c_uint32), ("nodes", f32p)]
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("rays", C.c_uint64),
@@ -221,6 +226,7 @@ HIP_SYMBOLS = {
     "rbrt_hip_denoise_halves": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
                                           C.POINTER(DenoiseOpts), C.c_void_p, C.c_void_p]),
     "rbrt_hip_scene_denoise": (C.c_int, [C.c_void_p, C.POINTER(DenoiseOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rbrt_hip_scene_set_environment": (C.c_int, [C.c_void_p, C.POINTER(Environment)]),
 }
 # ... and include/rbrt_hip_debug.h (test hooks and diagnostics, same library)
 DEBUG_SYMBOLS = {
@@ -255,6 +261,7 @@ DEBUG_SYMBOLS = {
     "rbrt_hip_scene_refine_wait": (C.c_int, [C.c_void_p, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     "rbrt_hip_debug_shading_normals": (C.c_int, [C.c_void_p, f32p, C.c_size_t, C.c_float, C.c_float, f32p]),
     "rbrt_hip_scene_adaptive_rounds": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32)]),
+    "rbrt_hip_debug_environment": (C.c_int, [C.c_void_p, f32p, C.c_size_t, f32p]),
 }
 
 
@@ -447,6 +454,14 @@ def load_host() -> C.CDLL:
     lib.rbrt_host_scene_scene.argtypes = [C.c_void_p]
     lib.rbrt_host_scene_shading.restype = C.POINTER(SceneShading)
     lib.rbrt_host_scene_shading.argtypes = [C.c_void_p]
+    lib.rbrt_host_scene_environment.restype = f32p
+    lib.rbrt_host_scene_environment.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+    lib.rbrt_host_read_pfm.restype = C.c_int
+    lib.rbrt_host_read_pfm.argtypes = [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), f32p]
+    lib.rbrt_host_environment_nodes.restype = C.c_int
+    lib.rbrt_host_environment_nodes.argtypes = [f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_double, f32p]
+    lib.rbrt_host_environment_fingerprint.restype = C.c_uint64
+    lib.rbrt_host_environment_fingerprint.argtypes = [f32p, C.c_uint32, C.c_uint64]
     lib.rbrt_host_scene_free.restype = None
     lib.rbrt_host_scene_free.argtypes = [C.c_void_p]
     lib.rbrt_host_save_image.restype = C.c_int
@@ -505,6 +520,15 @@ class HostScene:
     def shading_ptr(self):
         return None if self.shading is None else C.byref(self.shading)
 
+    def environment(self):
+        """The nodes the host made of the scene's environment_blueprint (rbrt_host_scene_environment): float32
+        (N + 1, N + 1, 3), what HipScene.set_environment takes; None when the scene has no environment."""
+        n = C.c_uint32()
+        p = self._lib.rbrt_host_scene_environment(self._h, C.byref(n))
+        if not p:
+            return None
+        return np.ctypeslib.as_array(p, (n.value + 1, n.value + 1, 3)).copy()
+
     def mesh_arrays(self, i: int) -> dict:
         m = self.struct.meshes[i]
         out = {k: np.ctypeslib.as_array(getattr(m, k), (m.n_total,)).copy() for k in MeshData.FIELDS}
@@ -527,6 +551,40 @@ class HostScene:
             self.close()
         except Exception:
             pass
+
+
+def read_pfm(path) -> np.ndarray:
+    """The host's PFM reader (rbrt_host_read_pfm): float32 (H, W, 3), top row first. RuntimeError with the reader's
+    message for anything it refuses."""
+    lib = load_host()
+    w, h = C.c_uint32(), C.c_uint32()
+    if lib.rbrt_host_read_pfm(str(path).encode(), C.byref(w), C.byref(h), None) != 0:
+        raise RuntimeError(lib.rbrt_host_last_error().decode(errors="replace"))
+    out = np.zeros((h.value, w.value, 3), np.float32)
+    if lib.rbrt_host_read_pfm(str(path).encode(), C.byref(w), C.byref(h), fptr(out)) != 0:
+        raise RuntimeError(lib.rbrt_host_last_error().decode(errors="replace"))
+    return out
+
+
+def environment_nodes(rgb: np.ndarray, n: int, rotation_deg: float = 0.0, intensity: float = 1.0) -> np.ndarray:
+    """The host's conversion of a latitude/longitude image (H, W, 3; top row first) into the (n + 1, n + 1, 3) nodes of
+    rbrt_environment_t (rbrt_host_environment_nodes)."""
+    lib = load_host()
+    rgb = np.ascontiguousarray(rgb, np.float32)
+    out = np.zeros((max(int(n), 0) + 1, max(int(n), 0) + 1, 3), np.float32)
+    if lib.rbrt_host_environment_nodes(fptr(rgb), rgb.shape[1], rgb.shape[0], int(n), float(rotation_deg), float(intensity), fptr(out)) != 0:
+        raise RuntimeError(lib.rbrt_host_last_error().decode(errors="replace"))
+    return out
+
+
+def environment_fingerprint(nodes, h: int) -> int:
+    """What an environment adds to the checkpoint fingerprint `h` (rbrt_host_environment_fingerprint); nodes None: no
+    environment."""
+    lib = load_host()
+    if nodes is None:
+        return int(lib.rbrt_host_environment_fingerprint(None, 0, h))
+    nodes = np.ascontiguousarray(nodes, np.float32)
+    return int(lib.rbrt_host_environment_fingerprint(fptr(nodes), nodes.shape[0] - 1, h))
 
 
 def save_image(path, rgb8: np.ndarray) -> None:

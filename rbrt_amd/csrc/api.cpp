@@ -27,7 +27,8 @@ hipError_t launch_trace_megakernel(const TraceParams& P, uint32_t n_waves, bool 
 hipError_t launch_trace_helper(const TraceParams& P, uint32_t n_waves, hipStream_t stream);
 size_t megakernel_gseq_bytes(uint32_t n_waves);
 size_t megakernel_gstack_bytes(uint32_t n_waves);
-size_t megakernel_lds_bytes(uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris, uint32_t thin_lens);
+size_t megakernel_lds_bytes(uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris, uint32_t thin_lens,
+                            uint32_t environment);
 int megakernel_occupancy_per_cu(size_t lds_bytes);
 hipError_t launch_primary_cull(const TraceParams& P, hipStream_t stream);
 hipError_t launch_sky_resolve(const TraceParams& P, const ResolveParams& R, hipStream_t stream);
@@ -44,6 +45,7 @@ hipError_t launch_unpack(const float* gathered, uint32_t width, uint32_t height,
 hipError_t launch_trace_rays(const TraceParams& P, const float* rays, size_t n, float* out_t, int32_t* out_obj,
                              int32_t* out_tri, float* out_dist, hipStream_t stream);
 hipError_t launch_shading_normals(const TraceParams& P, const float* rays, size_t n, float* out_normal, hipStream_t stream);
+hipError_t launch_environment_lookup(const EnvTexel* nodes, uint32_t n_env, const float* dirs, size_t n, float* out_rgb, hipStream_t stream);
 hipError_t launch_gate_selftest(const float* d_box, const float* d_rays, size_t n, uint8_t* d_fast, uint8_t* d_exact);
 hipError_t launch_ieee_selftest(uint64_t seed, size_t n, unsigned long long* d_counts);
 hipError_t launch_ieee_debug(const float* d_x, size_t n, const float* d_v, size_t m, float* d_sqrt, uint8_t* d_sqrt_short,
@@ -237,6 +239,10 @@ struct rbrt_hip_scene {
     DevMesh* d_meshes = nullptr;
     BvhTri* d_tris = nullptr;  // all meshes' triangle records
     DevCounters* d_counters = nullptr;
+    // The environment (rbrt_hip_scene_set_environment): (env_n + 1)^2 texels, a piece of its own in `allocs` that
+    // dev_release gives back when the map is replaced or cleared; null: rays that hit nothing see opts->bg / the gradient
+    EnvTexel* d_env = nullptr;
+    uint32_t env_n = 0;
     // workspace, grown on demand
     // Frame pipeline: consecutive trace launches (the batches of one render, or successive renders) alternate
     // over `pipeline` lanes. Every lane has its own sample buffer, work counters and per-wave scratch, and --
@@ -526,10 +532,11 @@ int device_counts3(const char* who, uint64_t counts[3], Launch launch) {
 // Device memory that lives as long as the scene (released by rbrt_hip_scene_destroy, never one by one). Called from the
 // thread that holds the scene (scene_create, or a render call under s->mu); the background builder has allocations of its own.
 constexpr size_t kSlabBytes = 32u << 20, kSlabMaxPiece = 8u << 20, kSlabAlign = 512;
-hipError_t dev_alloc(rbrt_hip_scene* s, size_t bytes, void** out) {
+// own_piece: a hipMalloc of its own whatever the size, for the one array that is released before the scene is (dev_release).
+hipError_t dev_alloc(rbrt_hip_scene* s, size_t bytes, void** out, bool own_piece = false) {
     bytes = (std::max<size_t>(bytes, 1) + kSlabAlign - 1) & ~(kSlabAlign - 1);
     *out = nullptr;
-    if (bytes > kSlabMaxPiece) {
+    if (bytes > kSlabMaxPiece || own_piece) {
         const hipError_t e = hipMalloc(out, bytes);
         if (e == hipSuccess) s->allocs.push_back(*out);
         return e;
@@ -544,6 +551,14 @@ hipError_t dev_alloc(rbrt_hip_scene* s, size_t bytes, void** out) {
     *out = s->slab_cur;
     s->slab_cur += bytes, s->slab_left -= bytes;
     return hipSuccess;
+}
+
+// Gives back a piece that dev_alloc made with own_piece (the caller has waited for the work that reads it).
+hipError_t dev_release(rbrt_hip_scene* s, void* p) {
+    const auto it = std::find(s->allocs.begin(), s->allocs.end(), p);
+    if (it == s->allocs.end()) return hipErrorInvalidValue;
+    s->allocs.erase(it);
+    return hipFree(p);
 }
 
 template <class T>
@@ -929,6 +944,7 @@ int fill_trace_params(const rbrt_hip_scene* s, const rbrt_camera_t* cam, const r
         P.focus_scale = lens->focus_scale;
     }
     P.seed_key = host_splitmix64(o->seed);
+    P.env_nodes = s->d_env, P.env_n = s->env_n;  // (the handle's state: bg and constant_bg are not read while it is set)
     P.n_spheres = s->n_spheres;
     P.n_meshes = s->n_meshes;
     P.n_elem_tris = s->n_elem_tris;
@@ -1379,7 +1395,7 @@ int size_grid(rbrt_hip_scene* s, int device, uint32_t waves_per_cu) {
     if (s->stack_entries > s->stack_need) s->stack_entries = s->stack_need;
     // resident waves per CU: LDS-limited (160 KiB per CU), at most 5 per SIMD (VGPR budget). (A thin-lens launch stages 32
     // bytes more; where that costs it a wave per CU the waves of the grid beyond the resident ones start as others end.)
-    int per_cu = int((160u * 1024u) / megakernel_lds_bytes(s->stack_entries, s->n_spheres, s->n_meshes, s->n_elem_tris, 0u));
+    int per_cu = int((160u * 1024u) / megakernel_lds_bytes(s->stack_entries, s->n_spheres, s->n_meshes, s->n_elem_tris, 0u, 0u));
     if (per_cu > 20) per_cu = 20;
     if (per_cu < 1) per_cu = 1;
     if (waves_per_cu != 0) per_cu = int(waves_per_cu), s->waves_fixed = true;
@@ -2262,6 +2278,43 @@ int rbrt_hip_scene_set_pipeline(rbrt_hip_scene_t* s, uint32_t depth) {
     return ensure_lanes(s, depth ? depth : 2u);
 }
 
+// The handle's environment map (rbrt_hip.h "Environment lighting"). Blocks: nothing that reads the old map is in flight when
+// it is released, and the new one is on the device when the call returns.
+int rbrt_hip_scene_set_environment(rbrt_hip_scene_t* s, const rbrt_environment_t* env) {
+    if (!s) return fail(RBRT_ERR_INVALID_ARG, "set_environment: null scene");
+    std::vector<EnvTexel> texels;
+    if (env) {
+        if (env->n == 0u || env->n > 4096u) return fail(RBRT_ERR_INVALID_ARG, "set_environment: n must be 1..4096");
+        if (env->reserved != 0u) return fail(RBRT_ERR_INVALID_ARG, "set_environment: reserved must be 0");
+        if (!env->nodes) return fail(RBRT_ERR_INVALID_ARG, "set_environment: null nodes");
+        const size_t count = size_t(env->n + 1u) * (env->n + 1u);
+        texels.resize(count);
+        for (size_t k = 0; k < count; ++k) {
+            const float* v = env->nodes + 3 * k;
+            for (int c = 0; c < 3; ++c)
+                if (!std::isfinite(v[c]) || v[c] < 0.0f)
+                    return fail(RBRT_ERR_INVALID_ARG, "set_environment: node " + std::to_string(k) + " has a non-finite or negative component");
+            texels[k] = EnvTexel{v[0], v[1], v[2], 0.0f};
+        }
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    std::lock_guard<std::mutex> watcher_lock(s->mu);
+    HIP_TRY(hipDeviceSynchronize());
+    void* p = nullptr;
+    if (env) {  // (the new map first: a failure leaves the handle as it was)
+        const hipError_t e = dev_alloc(s, texels.size() * sizeof(EnvTexel), &p, true);
+        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? RBRT_ERR_OOM : RBRT_ERR_HIP, std::string("set_environment: ") + hipGetErrorString(e));
+        const hipError_t c = hipMemcpy(p, texels.data(), texels.size() * sizeof(EnvTexel), hipMemcpyHostToDevice);
+        if (c != hipSuccess) {
+            (void)dev_release(s, p);
+            return fail(RBRT_ERR_HIP, std::string("set_environment: ") + hipGetErrorString(c));
+        }
+    }
+    if (s->d_env) HIP_TRY(dev_release(s, s->d_env));
+    s->d_env = static_cast<EnvTexel*>(p), s->env_n = env ? env->n : 0u;
+    return RBRT_OK;
+}
+
 int rbrt_hip_scene_stats(rbrt_hip_scene_t* s, rbrt_hip_stats_t* out) {
     if (!s || !out) return fail(RBRT_ERR_INVALID_ARG, "stats: null argument");
     HIP_TRY(hipSetDevice(s->device));
@@ -2346,7 +2399,7 @@ int rbrt_hip_scene_info(rbrt_hip_scene_t* s, rbrt_hip_scene_info_t* out) {
     out->bvh_stack_need = s->stack_need;
     out->n_nodes = s->total_nodes, out->n_triangles = s->total_tris;
     out->trace_waves = s->n_waves;
-    out->lds_bytes_per_wave = uint32_t(megakernel_lds_bytes(s->stack_entries, s->n_spheres, s->n_meshes, s->n_elem_tris, 0u));
+    out->lds_bytes_per_wave = uint32_t(megakernel_lds_bytes(s->stack_entries, s->n_spheres, s->n_meshes, s->n_elem_tris, 0u, 0u));
     (void)hipSetDevice(s->device);
     out->occupancy_api_waves_per_cu = uint32_t(megakernel_occupancy_per_cu(out->lds_bytes_per_wave));
     out->n_cus = s->n_cus;
@@ -2695,6 +2748,20 @@ int rbrt_hip_debug_shading_normals(rbrt_hip_scene_t* s, const float* rays, size_
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) e = d_out.to_host(out_normal, n * 3);
     return hook_result(e, "debug_shading_normals");
+}
+
+int rbrt_hip_debug_environment(rbrt_hip_scene_t* s, const float* dirs, size_t n, float* out_rgb) {
+    if (!s || (n && (!dirs || !out_rgb))) return fail(RBRT_ERR_INVALID_ARG, "debug_environment: null argument");
+    if (!s->d_env) return fail(RBRT_ERR_INVALID_ARG, "debug_environment: the handle has no environment");
+    if (n == 0) return RBRT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    DevBuf<float> d_dirs, d_out;
+    hipError_t e = d_dirs.upload(dirs, n * 3);
+    if (e == hipSuccess) e = d_out.alloc(n * 3);
+    if (e == hipSuccess) e = launch_environment_lookup(s->d_env, s->env_n, d_dirs.get(), n, d_out.get(), nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = d_out.to_host(out_rgb, n * 3);
+    return hook_result(e, "debug_environment");
 }
 
 int rbrt_hip_trace_rays(rbrt_hip_scene_t* s, const float* rays, size_t n, float min_dist, float max_dist,

@@ -133,6 +133,11 @@ struct DevCounters {  // mirrors rbrt_hip_stats_t's counters
     unsigned long long diag[64];
 };
 
+// One node of an environment map: 16 bytes, so that a node is one load.
+struct alignas(16) EnvTexel {
+    float r, g, b, pad;
+};
+
 // Kernel arguments of one trace launch (passed by value).
 struct TraceParams {
     rbrt_camera_t cam;
@@ -195,6 +200,9 @@ struct TraceParams {
     // RBRT_FLAG_THIN_LENS: thin_lens = 1 and the rbrt_camera_lens_t words past the camera; 0 (pinhole): the lens is never read
     uint32_t thin_lens;
     float lens_u[3], lens_v[3], focus_scale;
+    // The handle's environment (rbrt_hip_scene_set_environment): (env_n + 1)^2 texels of 16 bytes; null: bg / the sky gradient
+    const EnvTexel* env_nodes;
+    uint32_t env_n;
 };
 
 struct ResolveParams {

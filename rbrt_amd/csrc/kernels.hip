@@ -719,8 +719,37 @@ __device__ __forceinline__ V3 background(float dy, const float* bg, uint32_t con
     return t * mk(1.0f, 1.0f, 1.0f) + (1.0f - t) * mk(bg);
 }
 
+// The environment (rbrt_hip.h "Environment lighting"): what a ray that hits nothing sees while the handle has a
+// map. `nodes`: (n + 1) x (n + 1) texels of 16 bytes, row j first; `d`: the direction as traced, not re-normalised. The
+// octahedral fold and the bilinear weights use + - * /, abs, floor and comparisons only, unfused, in the written order: a
+// numpy restatement gives the same bits. The cell index is clamped to [0, n - 1] whatever d is (a NaN compares false:
+// index 0), so the four loads stay inside the map; a NaN or zero direction gives a NaN colour.
+__device__ __forceinline__ V3 environment_radiance(const EnvTexel* __restrict__ nodes, uint32_t n, V3 d) {
+    const float s = (__builtin_fabsf(d.x) + __builtin_fabsf(d.y)) + __builtin_fabsf(d.z);
+    const float px = d.x / s, py = d.y / s, pz = d.z / s;
+    float u = px, v = pz;
+    if (!(py >= 0.0f)) {  // the lower hemisphere: folded over the diagonals
+        u = (1.0f - __builtin_fabsf(pz)) * (px >= 0.0f ? 1.0f : -1.0f);
+        v = (1.0f - __builtin_fabsf(px)) * (pz >= 0.0f ? 1.0f : -1.0f);
+    }
+    const float fn = float(n);
+    const float x = ((u * 0.5f) + 0.5f) * fn, y = ((v * 0.5f) + 0.5f) * fn;
+    const uint32_t i = x >= 0.0f ? (x < fn ? uint32_t(__builtin_floorf(x)) : n - 1u) : 0u;
+    const uint32_t j = y >= 0.0f ? (y < fn ? uint32_t(__builtin_floorf(y)) : n - 1u) : 0u;
+    const float fx = x - float(i), fy = y - float(j);
+    const EnvTexel* row = nodes + size_t(j) * (n + 1u) + i;
+    const EnvTexel e00 = row[0], e01 = row[1], e10 = row[n + 1u], e11 = row[n + 2u];
+    const V3 a = mk(e00.r, e00.g, e00.b), b = mk(e01.r, e01.g, e01.b), c = mk(e10.r, e10.g, e10.b), e = mk(e11.r, e11.g, e11.b);
+    const V3 top = a + fx * (b - a);
+    const V3 bot = c + fx * (e - c);
+    return top + fy * (bot - top);
+}
+// ... out of line, for the counting build of the trace kernel (it spills already; inlined, the lookup adds to that)
+__device__ __noinline__ V3 environment_radiance_call(const EnvTexel* nodes, uint32_t n, V3 d) { return environment_radiance(nodes, n, d); }
+constexpr uint32_t kEnvDw = 4;  // words staged in the megakernel's LDS for a launch with a map: the address (2), n, pad
+
 __host__ __device__ inline uint32_t megakernel_lds_dwords(uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris,
-                                                          uint32_t thin_lens);
+                                                          uint32_t thin_lens, uint32_t environment);
 #include "megakernel.inl"
 
 // lib.rs:116-122: (sqrt(c) * 256) as u8 — Rust's float->int cast saturates and maps NaN to 0.
@@ -862,7 +891,7 @@ __global__ __launch_bounds__(kSmallBlock) void sky_resolve_kernel(const TracePar
                 lens_point(o, f, lens, rng);
             }
             const V3 d = normalize(f - o);
-            const V3 c = background(d.y, P.bg, P.constant_bg);
+            const V3 c = P.env_nodes ? environment_radiance(P.env_nodes, P.env_n, d) : background(d.y, P.bg, P.constant_bg);
             ax = ax + c.x;
             ay = ay + c.y;
             az = az + c.z;
@@ -1369,7 +1398,7 @@ __global__ __launch_bounds__(kSmallBlock) void sky_resolve_even_kernel(const Tra
             lens_point(o, f, lens, rng);
         }
         const V3 d = normalize(f - o);
-        const V3 c = background(d.y, P.bg, P.constant_bg);
+        const V3 c = P.env_nodes ? environment_radiance(P.env_nodes, P.env_n, d) : background(d.y, P.bg, P.constant_bg);
         ax = ax + c.x;
         ay = ay + c.y;
         az = az + c.z;
@@ -1570,6 +1599,17 @@ __global__ __launch_bounds__(kRaysBlock) void shading_normals_kernel(const Trace
     out[3 * i + 2] = nrm.z;
 }
 
+// The environment lookup alone, for arbitrary directions (test hook behind rbrt_hip_debug_environment).
+__global__ __launch_bounds__(kRaysBlock) void environment_lookup_kernel(const EnvTexel* __restrict__ nodes, uint32_t n_env,
+                                                                    const float* __restrict__ dirs, size_t n, float* __restrict__ out) {
+    const size_t i = size_t(blockIdx.x) * kRaysBlock + threadIdx.x;
+    if (i >= n) return;
+    const V3 c = environment_radiance(nodes, n_env, mk(dirs + 3 * i));
+    out[3 * i + 0] = c.x;
+    out[3 * i + 1] = c.y;
+    out[3 * i + 2] = c.z;
+}
+
 // Test hook (rbrt_hip_selftest_ieee): the short IEEE forms (sqrt_core inside ieee_sqrt, normalize) against the
 // compiler's on pseudo-random operands. Waves 0,1,2 (mod 4) draw every lane's operands from the whole domain the gates
 // admit, so the short forms are what runs: x in (2^-80, 2^100); the largest component of a in [2^-40, 2^(kNormTopExp+1))
@@ -1708,18 +1748,20 @@ size_t megakernel_gseq_bytes(uint32_t n_waves) { return size_t(n_waves) * kPool 
 size_t megakernel_gstack_bytes(uint32_t n_waves) { return size_t(n_waves) * kStackMax * 64u * sizeof(uint32_t); }
 
 __host__ __device__ inline uint32_t megakernel_lds_dwords(uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris,
-                                                          uint32_t thin_lens) {
+                                                          uint32_t thin_lens, uint32_t environment) {
     const uint32_t n_elem = n_spheres + n_elem_tris;
     const uint32_t scene = n_spheres * kSphDw + (n_elem + n_meshes) * kMatDw + n_meshes * kMeshDw + kGenDw +
                            (thin_lens ? kLensDw : 0u) +                                // a lens launch's lens (nothing for a pinhole)
+                           (environment ? kEnvDw : 0u) +                               // the map's address and size (nothing without one)
                            (n_elem_tris != 0u ? n_elem_tris * kTriDw + n_elem : 0u);  // triangle table + element order
     const uint32_t pool_pad = (uint32_t(kPool) + 63u) & ~63u;  // status + list: one byte per (padded) slot each
     uint32_t dw = uint32_t(kFields * kPool) + kCellDw + kTqDw + kHelpDw + pool_pad / 2u + stack_entries * 64u + scene;
     if (RBRT_REGION_TIMERS) dw += uint32_t(kNumRegions);  // analysis build: a u32 cycle accumulator per region
     return dw;
 }
-size_t megakernel_lds_bytes(uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris, uint32_t thin_lens) {
-    return size_t(megakernel_lds_dwords(stack_entries, n_spheres, n_meshes, n_elem_tris, thin_lens)) * sizeof(uint32_t);
+size_t megakernel_lds_bytes(uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris, uint32_t thin_lens,
+                            uint32_t environment) {
+    return size_t(megakernel_lds_dwords(stack_entries, n_spheres, n_meshes, n_elem_tris, thin_lens, environment)) * sizeof(uint32_t);
 }
 
 // What the HIP runtime says fits: resident single-wave workgroups of the trace kernel per CU at this much LDS (0 on error).
@@ -1735,14 +1777,14 @@ int megakernel_occupancy_per_cu(size_t lds_bytes) {
 // (work counters, sample buffer, tables), scratch slots from P.wave_base on.
 hipError_t launch_trace_helper(const TraceParams& P, uint32_t n_waves, hipStream_t stream) {
     if (P.n_items == 0 || n_waves == 0 || !P.helper_words) return hipSuccess;
-    const size_t lds = megakernel_lds_bytes(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris, P.thin_lens);
+    const size_t lds = megakernel_lds_bytes(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris, P.thin_lens, P.env_nodes ? 1u : 0u);
     hipLaunchKernelGGL((trace_megakernel<false, true>), dim3(n_waves), dim3(64), lds, stream, P);
     return hipGetLastError();
 }
 
 hipError_t launch_trace_megakernel(const TraceParams& P, uint32_t n_waves, bool stats, hipStream_t stream) {
     if (P.n_items == 0 || n_waves == 0) return hipSuccess;
-    const size_t lds = megakernel_lds_bytes(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris, P.thin_lens);
+    const size_t lds = megakernel_lds_bytes(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris, P.thin_lens, P.env_nodes ? 1u : 0u);
     if (stats)
         hipLaunchKernelGGL((trace_megakernel<true>), dim3(n_waves), dim3(64), lds, stream, P);
     else
@@ -1836,6 +1878,13 @@ hipError_t launch_shading_normals(const TraceParams& P, const float* rays, size_
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(shading_normals_kernel, dim3(uint32_t((n + kRaysBlock - 1) / kRaysBlock)), dim3(kRaysBlock),
                        size_t(kStackMax) * kRaysBlock * sizeof(uint32_t), stream, P, rays, n, out_normal);
+    return hipGetLastError();
+}
+
+hipError_t launch_environment_lookup(const EnvTexel* nodes, uint32_t n_env, const float* dirs, size_t n, float* out_rgb, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(environment_lookup_kernel, dim3(uint32_t((n + kRaysBlock - 1) / kRaysBlock)), dim3(kRaysBlock), 0, stream, nodes,
+                       n_env, dirs, n, out_rgb);
     return hipGetLastError();
 }
 

@@ -239,7 +239,7 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
     // (the accumulators sit at the very end of the workgroup's LDS: megakernel_lds_bytes adds room for them)
     // (u32: a wave spends at most a few million cycles in a region per launch; 76 bytes fit the slack of the product's
     // allocation granule, so this build keeps the product's 16 workgroups per CU)
-    uint32_t* const rt_acc = lds + (megakernel_lds_dwords(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris, P.thin_lens) - uint32_t(kNumRegions));
+    uint32_t* const rt_acc = lds + (megakernel_lds_dwords(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris, P.thin_lens, P.env_nodes ? 1u : 0u) - uint32_t(kNumRegions));
     if (lane < uint32_t(kNumRegions)) rt_acc[lane] = 0u;
     unsigned long long rt_prev = __builtin_amdgcn_s_memtime();
     const unsigned long long rt_wall0 = __builtin_amdgcn_s_memrealtime();  // 100 MHz, the same clock on every CU
@@ -321,7 +321,7 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
             dst[G_BATCH] = P.batch, dst[G_BATCH_MAGIC] = P.batch_magic;
             dst[G_TILES_X] = P.tiles_x, dst[G_TILES_X_MAGIC] = P.tiles_x_magic;
             dst[G_TILE_WORLD] = P.tile_world, dst[G_TILE_RANK] = P.tile_rank;
-            dst[G_N_LOCAL] = n_work, dst[G_FLAGS] = (P.tiles_reversed ? 1u : 0u) | (P.constant_bg ? 2u : 0u) | (P.thin_lens ? 4u : 0u);
+            dst[G_N_LOCAL] = n_work, dst[G_FLAGS] = (P.tiles_reversed ? 1u : 0u) | (P.constant_bg ? 2u : 0u) | (P.thin_lens ? 4u : 0u) | (P.env_nodes ? 8u : 0u);
             // (one word: a new one would take the header card's scene past 16 waves per CU, and reading the kernel argument cost
             // 3 SGPR spills. A lens launch's lens words sit behind everything else, at the dword offset from here that bits
             // 8 and up of the flags word carry: a pinhole launch's LDS -- and with it every current scene's occupancy -- and its
@@ -331,6 +331,13 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                 for (int c = 0; c < 3; ++c) gf[at + c] = P.lens_u[c], gf[at + 3 + c] = P.lens_v[c];
                 gf[at + 6] = P.focus_scale, dst[at + 7] = 0u;
                 dst[G_FLAGS] |= at << 8;
+            }
+            if (P.env_nodes) {  // the same way, behind the lens: the map's address and n (the kernel argument cost a VGPR spill)
+                const uint32_t at = kGenDw + (P.n_elem_tris != 0u ? P.n_elem_tris * kTriDw + n_elem : 0u);
+                const uint32_t ea = at + (P.thin_lens ? kLensDw : 0u);
+                const uint64_t addr = reinterpret_cast<uint64_t>(P.env_nodes);
+                dst[ea] = uint32_t(addr), dst[ea + 1] = uint32_t(addr >> 32), dst[ea + 2] = P.env_n, dst[ea + 3] = 0u;
+                dst[G_FLAGS] = (dst[G_FLAGS] & 0xFFu) | (at << 8);
             }
             dst[G_SAMPLE_BASE] = P.sample_base, dst[G_MAX_DEPTH] = P.max_depth;
             dst[G_SEED_LO] = uint32_t(P.seed_key), dst[G_SEED_HI] = uint32_t(P.seed_key >> 32);
@@ -820,7 +827,14 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                 const int32_t obj = int32_t((meta >> 14) & 255u) - 1;
                 V3 color = mk(0.0f, 0.0f, 0.0f);  // hit with depth 0 or a failed scatter: lib.rs:63-66
                 if (obj < 0) {
-                    color = background(__uint_as_float(POOL(F_DY, slot)), P.bg, gp[G_FLAGS] & 2u);  // lib.rs:68-71
+                    if (gp[G_FLAGS] & 8u) {  // the handle's environment takes the background's place
+                        const uint32_t* ew = gp + (gp[G_FLAGS] >> 8) + ((gp[G_FLAGS] & 4u) ? kLensDw : 0u);
+                        const EnvTexel* en = reinterpret_cast<const EnvTexel*>((uint64_t(ew[1]) << 32) | ew[0]);
+                        const V3 ed = mk(__uint_as_float(POOL(F_DX, slot)), __uint_as_float(POOL(F_DY, slot)), __uint_as_float(POOL(F_DZ, slot)));
+                        color = STATS ? environment_radiance_call(en, ew[2], ed) : environment_radiance(en, ew[2], ed);
+                    }
+                    else
+                        color = background(__uint_as_float(POOL(F_DY, slot)), P.bg, gp[G_FLAGS] & 2u);  // lib.rs:68-71
                 } else if (int32_t(sc.mat[uint32_t(obj) * kMatDw + 4]) == kDevMatEmissive) {
                     color = mk(reinterpret_cast<const float*>(sc.mat + uint32_t(obj) * kMatDw));  // an emitter: its radiance L
                 }

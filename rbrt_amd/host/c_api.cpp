@@ -79,6 +79,7 @@ int rbrt_host_scene_load(const char* yaml_path, uint32_t height, uint32_t width,
         auto* h = new rbrt_host_scene();
         h->cam = rbrt::camera_from_blueprint(bp.camera_blueprint, height, width);
         h->scene = rbrt::create_scene_from_scene_blueprint(bp);
+        if (bp.environment_blueprint) h->scene.environment = rbrt::load_environment(*bp.environment_blueprint);
         h->view = h->scene.to_abi();
         h->cam_abi = h->cam.to_abi();
         h->lens_abi = h->cam.to_abi_lens();
@@ -95,7 +96,48 @@ const rbrt_camera_lens_t* rbrt_host_scene_lens(const rbrt_host_scene* h) { retur
 const rbrt_scene_t* rbrt_host_scene_scene(const rbrt_host_scene* h) { return &h->view.scene; }
 // The corner normals of the smooth meshes (YAML `shading: smooth`), or NULL when every mesh is flat.
 const rbrt_scene_shading_t* rbrt_host_scene_shading(const rbrt_host_scene* h) { return h->view.shading_ptr(); }
+// The nodes made of the scene's environment_blueprint: float[*n + 1][*n + 1][3], what rbrt_environment_t::nodes takes; NULL
+// (and *n = 0) when the scene has none. Valid until rbrt_host_scene_free.
+const float* rbrt_host_scene_environment(const rbrt_host_scene* h, uint32_t* n) {
+    if (n) *n = h->scene.environment.n;
+    return h->scene.environment.n ? h->scene.environment.nodes.data() : nullptr;
+}
 void rbrt_host_scene_free(rbrt_host_scene* h) { delete h; }
+
+// TEST HOOKS (tests/test_environment_host.py). The PFM reader: the image's size and, when `rgb` is not NULL, its
+// width * height * 3 floats, top row first (call once for the size, once for the texels).
+int rbrt_host_read_pfm(const char* path, uint32_t* width, uint32_t* height, float* rgb) {
+    try {
+        const rbrt::PfmImage img = rbrt::read_pfm(path);
+        *width = img.width, *height = img.height;
+        if (rgb) std::memcpy(rgb, img.rgb.data(), img.rgb.size() * sizeof(float));
+        return 0;
+    } catch (const std::exception& e) {
+        g_err = e.what();
+        return -1;
+    }
+}
+// The conversion alone: a latitude/longitude image (top row first) -> nodes_out float[n + 1][n + 1][3].
+int rbrt_host_environment_nodes(const float* rgb, uint32_t width, uint32_t height, uint32_t n, double rotation_deg, double intensity,
+                                float* nodes_out) {
+    try {
+        rbrt::PfmImage img;
+        img.width = width, img.height = height;
+        img.rgb.assign(rgb, rgb + size_t(width) * height * 3);
+        const std::vector<float> nodes = rbrt::environment_nodes_from_latlong(img, n, rotation_deg, intensity);
+        std::memcpy(nodes_out, nodes.data(), nodes.size() * sizeof(float));
+        return 0;
+    } catch (const std::exception& e) {
+        g_err = e.what();
+        return -1;
+    }
+}
+// What the environment adds to a checkpoint's fingerprint `h` (n == 0 or nodes NULL: none).
+uint64_t rbrt_host_environment_fingerprint(const float* nodes, uint32_t n, uint64_t h) {
+    rbrt::Environment e;
+    if (nodes && n) e.n = n, e.nodes.assign(nodes, nodes + size_t(n + 1) * (n + 1) * 3);
+    return rbrt::environment_fingerprint(e, h);
+}
 
 int rbrt_host_write_png(const char* path, const uint8_t* rgb, uint32_t width, uint32_t height) {
     try {

@@ -8,7 +8,9 @@
 // (overrides every mesh blueprint's `shading`), --adaptive THRESHOLD with --min-samples N and --adaptive-step K (adaptive sampling:
 // --samples is the limit), --sample-map FILE (the per-pixel sample count of an adaptive render, scaled to 0-255), --denoise with
 // --denoise-radius R, --denoise-patch P and --denoise-strength K (the target file gets the dual-buffer non-local-means filter of
-// the render's two half images), --noisy FILE (also the unfiltered image).
+// the render's two half images), --noisy FILE (also the unfiltered image), --environment FILE.pfm | none with
+// --environment-rotation DEG, --environment-intensity X and --environment-resolution N (environment lighting: they override
+// the YAML's environment_blueprint).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -44,6 +46,12 @@ void usage() {
         "      --checkpoint-every <n>       checkpoint after every n-th pass [default: 1]\n"
         "      --background <r,g,b>         constant linear background radiance of rays that hit nothing, e.g. 0,0,0 for a scene\n"
         "                                   lit by emissive objects only [default: the sky gradient]\n"
+        "      --environment <file|none>    light the scene from a latitude/longitude radiance image (a colour PFM; its top row\n"
+        "                                   is +y, its middle column looks along -z) instead of the background; overrides the\n"
+        "                                   YAML's environment_blueprint, `none` switches that off. Not with --background\n"
+        "      --environment-rotation <deg> turns the environment about +y [default: the YAML's, else 0]\n"
+        "      --environment-intensity <x>  scales the environment's radiance, a finite number >= 0 [default: the YAML's, else 1]\n"
+        "      --environment-resolution <n> size of the octahedral map made of the image, 1 to 4096 [default: the YAML's, else 1024]\n"
         "      --aperture <mm>              lens diameter in mm, overrides the YAML's camera_aperture_mm; 0 = pinhole\n"
         "                                   [default: the YAML's, else 0]\n"
         "      --focus-distance <d>         distance from the camera position to the plane in focus, along the view\n"
@@ -142,6 +150,9 @@ int main(int argc, char** argv) {
     std::optional<uint32_t> denoise_radius, denoise_patch;
     std::optional<float> denoise_strength;
     std::string noisy;
+    std::optional<std::string> environment;  // a file, or "none"
+    std::optional<float> environment_rotation, environment_intensity;
+    std::optional<uint32_t> environment_resolution;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         std::string val;
@@ -255,6 +266,29 @@ int main(int argc, char** argv) {
             denoise_strength = f;
         } else if (a == "--noisy") {
             noisy = value();
+        } else if (a == "--environment") {
+            environment = std::string(value());
+            if (environment->empty()) {
+                std::fprintf(stderr, "error: invalid value '' for '--environment' (expected a PFM file or `none`)\n");
+                return 2;
+            }
+        } else if (a == "--environment-rotation" || a == "--environment-intensity") {
+            const bool rot = a == "--environment-rotation";
+            const char* v = value();
+            float f = 0.0f;
+            if (!parse_f32(v, f) || !std::isfinite(f) || (!rot && f < 0.0f)) {
+                std::fprintf(stderr, "error: invalid value '%s' for '%s' (expected a finite number%s)\n", v, a.c_str(), rot ? "" : " >= 0");
+                return 2;
+            }
+            (rot ? environment_rotation : environment_intensity) = f;
+        } else if (a == "--environment-resolution") {
+            uint32_t v = 0;
+            u32(v);
+            if (v < 1u || v > 4096u) {
+                std::fprintf(stderr, "error: invalid value '%u' for '--environment-resolution' (expected 1 to 4096)\n", v);
+                return 2;
+            }
+            environment_resolution = v;
         } else if (a == "--shading") {
             const std::string v = value();
             if (v != "flat" && v != "smooth") {
@@ -302,6 +336,10 @@ int main(int argc, char** argv) {
             return 2;
         }
     }
+    if (environment && *environment != "none" && constant_background) {
+        std::fprintf(stderr, "error: '--background' cannot be combined with '--environment' (the environment is the background)\n");
+        return 2;
+    }
     using clock = std::chrono::steady_clock;
     const auto secs = [](clock::time_point a, clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
     try {
@@ -311,9 +349,29 @@ int main(int argc, char** argv) {
         if (focus_distance) bp.camera_blueprint.camera_focus_distance = focus_distance;
         if (smooth)
             for (rbrt::TriangleMeshBlueprint& mb : bp.mesh_blueprints) mb.smooth = *smooth;
+        if (environment) {
+            if (*environment == "none") {
+                bp.environment_blueprint.reset();
+            } else {
+                if (!bp.environment_blueprint) bp.environment_blueprint = rbrt::EnvironmentBlueprint();
+                bp.environment_blueprint->file = *environment;
+            }
+        }
+        if (bp.environment_blueprint) {
+            if (environment_rotation) bp.environment_blueprint->rotation_deg = *environment_rotation;
+            if (environment_intensity) bp.environment_blueprint->intensity = *environment_intensity;
+            if (environment_resolution) bp.environment_blueprint->resolution = *environment_resolution;
+            if (constant_background)
+                throw rbrt::Error("'--background' cannot be combined with an environment (the scene file has an environment_blueprint; "
+                                  "'--environment none' switches it off)");
+        } else if (environment_rotation || environment_intensity || environment_resolution) {
+            throw rbrt::Error("'--environment-rotation', '--environment-intensity' and '--environment-resolution' need an environment "
+                              "('--environment FILE' or the scene file's environment_blueprint)");
+        }
         rbrt::Camera cam = rbrt::camera_from_blueprint(bp.camera_blueprint, height, width);  // (checks the lens again)
         const auto t1 = clock::now();
         rbrt::Scene scene = rbrt::create_scene_from_scene_blueprint(bp);  // .obj parse, transform, SoA conversion (mesh.rs:41-181)
+        if (bp.environment_blueprint) scene.environment = rbrt::load_environment(*bp.environment_blueprint);  // PFM read, conversion
         const auto t2 = clock::now();
         rbrt::RenderConfig cfg;
         rbrt::RenderReport rep;
@@ -370,6 +428,8 @@ int main(int argc, char** argv) {
                 for (size_t k = 0; k < rep.adaptive_active_tiles.size(); ++k) js += (k ? ", " : "") + std::to_string(rep.adaptive_active_tiles[k]);
                 js += "], ";
             }
+            if (scene.environment.n != 0u)  // the map that lit the scene
+                str("environment_file", scene.environment.file), num("environment_resolution", scene.environment.n, "%.0f");
             if (denoise) {  // the filter's parameters and its time on the GPU (a part of render_s)
                 num("denoise_window_radius", cfg.denoise_window_radius, "%.0f"), num("denoise_patch_radius", cfg.denoise_patch_radius, "%.0f");
                 num("denoise_strength", cfg.denoise_strength, "%.9g"), num("denoise_ms", rep.denoise_ms, "%.4f");

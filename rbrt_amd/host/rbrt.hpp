@@ -116,10 +116,19 @@ struct CameraBluePrint {
 };
 // Camera::create from a blueprint, with its lens (Camera::set_lens) when the blueprint has an aperture.
 Camera camera_from_blueprint(const CameraBluePrint& bp, uint32_t img_height_pix, uint32_t img_width_pix);
+// `environment_blueprint` (not in the reference): a latitude/longitude radiance image that lights the scene in place of the
+// sky gradient (include/rbrt_hip.h "Environment lighting").
+struct EnvironmentBlueprint {
+    std::string file;           // a colour PFM; row 0 is +y and its middle column looks along -z
+    float rotation_deg = 0.0f;  // turns the map about +y
+    float intensity = 1.0f;     // finite, >= 0
+    uint32_t resolution = 1024; // N of the node grid, 1..4096
+};
 struct SceneBlueprint {
     CameraBluePrint camera_blueprint;
     std::vector<TriangleMeshBlueprint> mesh_blueprints;
     std::vector<SphereBlueprint> sphere_blueprints;
+    std::optional<EnvironmentBlueprint> environment_blueprint;
 };
 SceneBlueprint load_blueprints_from_yaml_file(const std::string& filepath);
 SceneBlueprint load_blueprints_from_yaml_text(const std::string& text);
@@ -179,6 +188,28 @@ ObjMesh load_mesh_from_file(const std::string& filepath, Vec3 translation, Vec3 
 Vec3 get_triangle_normal(const std::array<Vec3, 3>& corners);                             // triangle.rs:30-34
 void compute_min_max_3d(const std::vector<std::array<Vec3, 3>>& tris, Vec3& lo, Vec3& hi);  // aabbox.rs:62-88
 
+// ---- environment lighting (environment.cpp) -------------------------------------------------------
+struct PfmImage {
+    uint32_t width = 0, height = 0;
+    std::vector<float> rgb;  // row-major, TOP row first (the file stores the bottom row first), 3 floats per texel
+};
+// A colour (`PF`) Portable Float Map, either byte order (the sign of the scale). Throws Error, with the reason, for anything
+// else: a grey `Pf`, a bad size or scale, a truncated file, bytes after the pixels, a texel that is not finite or is negative.
+PfmImage read_pfm(const std::string& path);
+// The (n + 1) x (n + 1) x 3 nodes of rbrt_environment_t from a latitude/longitude image (DESIGN.md "Environment lighting").
+std::vector<float> environment_nodes_from_latlong(const PfmImage& img, uint32_t n, double rotation_deg, double intensity);
+struct Environment {
+    uint32_t n = 0;            // 0: none
+    std::vector<float> nodes;  // float[n+1][n+1][3]
+    std::string file;          // where it came from (--report)
+    rbrt_environment_t to_abi() const { return rbrt_environment_t{n, 0u, nodes.data()}; }
+};
+// Reads the blueprint's image and converts it. create_scene_from_scene_blueprint mirrors the reference and knows nothing of
+// environments: a host assigns the result to Scene::environment itself (main.cpp, c_api.cpp).
+Environment load_environment(const EnvironmentBlueprint& bp);
+// What a checkpoint of a render with an environment must match besides the scene: `h` itself when there is none.
+uint64_t environment_fingerprint(const Environment& e, uint64_t h);
+
 struct Scene {
     // scene.rs:12-16: `elements: Vec<Box<dyn Intersectable + Sync>>` holds Spheres and BasicTriangles. Here the two
     // kinds sit in their own vectors; `element_order` gives the order Scene::hit tests them in (scene.rs:23-31: an
@@ -188,6 +219,7 @@ struct Scene {
     std::vector<BasicTriangle> basic_triangles;
     std::vector<uint32_t> element_order;
     std::vector<TriangleMesh> triangle_meshes;
+    Environment environment;  // n == 0: rays that hit nothing see the background (render_scene sets it on every rank's handle)
     // POD view for the C ABI; valid while this Scene is alive and unmodified.
     struct AbiView {
         std::vector<rbrt_sphere_t> spheres;

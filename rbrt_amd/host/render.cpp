@@ -228,6 +228,10 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
         want.fingerprint = fnv1a(&opts.flags, sizeof(opts.flags), want.fingerprint);
         want.fingerprint = fnv1a(opts.bg, sizeof(opts.bg), want.fingerprint);
     }
+    const bool has_env = scene.environment.n != 0u;
+    if (has_env && cfg.constant_background) throw Error("--background cannot be combined with an environment (the environment is the background)");
+    if (want.fingerprint != 0) want.fingerprint = environment_fingerprint(scene.environment, want.fingerprint);  // (unchanged without one)
+    const rbrt_environment_t env_abi = scene.environment.to_abi();
     if (cam.thin_lens) {  // (likewise: a pinhole run's checkpoints keep their fingerprint)
         if (!(rbrt_hip_supported_flags() & RBRT_FLAG_THIN_LENS)) throw Error("the HIP library does not support a thin lens");
         opts.flags |= RBRT_FLAG_THIN_LENS;
@@ -344,6 +348,7 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
         // (every pass is followed by a synchronisation here: only the sample batches INSIDE a pass overlap, on three lanes;
         // the library's default of eight is for streams of frames)
         if (hs) (void)rbrt_hip_scene_set_pipeline(hs, 3);
+        if (hs && has_env && rbrt_hip_scene_set_environment(hs, &env_abi) != RBRT_OK) fail(rbrt_hip_last_error());  // (every rank's handle)
         if (hs && rank == 0) {
             rbrt_hip_scene_info_t info;
             if (rbrt_hip_scene_info(hs, &info) == RBRT_OK) {

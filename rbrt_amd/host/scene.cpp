@@ -324,6 +324,20 @@ SceneBlueprint load_blueprints_from_yaml_text(const std::string& text) {
         b.material_param = opt_f32(s, "material_param", "material_param");
         bp.sphere_blueprints.push_back(b);
     }
+    if (const Node* en = root.find("environment_blueprint"); en && !en->is_null()) {  // (not in the reference; absent = none)
+        EnvironmentBlueprint e;
+        e.file = as_string(need(*en, "file", "environment_blueprint"), "environment_blueprint file");
+        if (const auto r = opt_f32(*en, "rotation_deg", "rotation_deg")) e.rotation_deg = *r;
+        if (const auto v = opt_f32(*en, "intensity", "intensity")) e.intensity = *v;
+        if (const auto v = opt_f32(*en, "resolution", "resolution")) {
+            if (!(*v >= 1.0f && *v <= 4096.0f) || *v != std::floor(*v)) throw Error("environment_blueprint: resolution must be an integer between 1 and 4096");
+            e.resolution = uint32_t(*v);
+        }
+        if (e.file.empty()) throw Error("environment_blueprint: file must name a PFM image");
+        if (!std::isfinite(e.rotation_deg)) throw Error("environment_blueprint: rotation_deg must be finite");
+        if (!std::isfinite(e.intensity) || e.intensity < 0.0f) throw Error("environment_blueprint: intensity must be a finite number >= 0");
+        bp.environment_blueprint = e;
+    }
     return bp;
 }
 

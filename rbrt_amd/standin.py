@@ -151,8 +151,50 @@ def triangles(n_triangles: int, kind: str = "smooth") -> np.ndarray:
     return v[f]
 
 
+def make_sky(width: int = 512, seed: int = 1) -> np.ndarray:
+    """A procedural STAND-IN sky as a latitude/longitude radiance image, float32 (width // 2, width, 3), top row = +y,
+    middle column = -z (what `environment_blueprint` expects): a blue gradient with a few seeded soft clouds, a bright
+    horizon band, a small sun of radiance ~60 and a dark ground. Deterministic for (width, seed)."""
+    h = max(width // 2, 1)
+    rng = np.random.default_rng(seed)
+    theta = (np.arange(h) + 0.5) / h * math.pi          # from +y
+    phi = ((np.arange(width) + 0.5) / width - 0.5) * 2.0 * math.pi  # 0 in the middle column = -z, + towards +x
+    st, ct = np.sin(theta)[:, None], np.cos(theta)[:, None]
+    d = np.stack([st * np.sin(phi)[None, :], np.broadcast_to(ct, (h, width)), -st * np.cos(phi)[None, :]], -1)
+    up = d[..., 1]
+    zenith, horizon, ground = np.array([0.10, 0.25, 0.80]), np.array([0.95, 0.90, 0.85]), np.array([0.05, 0.045, 0.04])
+    t = np.clip(up, 0.0, 1.0)[..., None] ** 0.5
+    sky = horizon * (1.0 - t) + zenith * t
+    for _ in range(6):  # soft clouds: seeded lobes in the upper hemisphere
+        c = rng.normal(size=3)
+        c[1] = abs(c[1]) * 0.6 + 0.15
+        c /= np.linalg.norm(c)
+        sky = sky + 0.35 * np.exp(rng.uniform(15.0, 40.0) * (d @ c - 1.0))[..., None]
+    band = np.exp(-(up / 0.04) ** 2)[..., None] * 0.6   # the horizon band
+    img = np.where(up[..., None] >= 0.0, sky, ground) + band * horizon
+    sun = np.array([0.45, 0.60, -0.66])
+    sun /= np.linalg.norm(sun)
+    img = img + np.array([60.0, 55.0, 45.0]) * np.exp(2500.0 * (d @ sun - 1.0))[..., None]  # ~2.3 degrees across
+    return np.ascontiguousarray(img, np.float32)
+
+
+def write_pfm(path, rgb: np.ndarray) -> None:
+    """A colour Portable Float Map (`PF`), little endian (scale -1.0); the file's rows run bottom to top."""
+    rgb = np.ascontiguousarray(rgb, np.float32)
+    h, w, _ = rgb.shape
+    with open(path, "wb") as f:
+        f.write(f"PF\n{w} {h}\n-1.0\n".encode())
+        f.write(rgb[::-1].astype("<f4").tobytes())
+
+
 if __name__ == "__main__":
     import sys
+    if len(sys.argv) > 1 and sys.argv[1] == "--environment":  # python -m rbrt_amd.standin --environment out.pfm [width] [seed]
+        out = sys.argv[2] if len(sys.argv) > 2 else "scenes/environment/standin_sky.pfm"
+        width = int(sys.argv[3]) if len(sys.argv) > 3 else 512
+        write_pfm(out, make_sky(width, int(sys.argv[4]) if len(sys.argv) > 4 else 1))
+        print(f"wrote {out} ({width} x {max(width // 2, 1)}, stand-in sky)")
+        sys.exit(0)
     out = sys.argv[1] if len(sys.argv) > 1 else "bunny.obj"
     n = int(sys.argv[2]) if len(sys.argv) > 2 else BUNNY_TRIANGLES
     ensure_obj(out, n)

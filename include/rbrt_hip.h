@@ -59,7 +59,9 @@ extern "C" {
                               denoiser (rbrt_denoise_opts_t, rbrt_denoise_opts_default, rbrt_hip_denoise_halves and
                               rbrt_hip_scene_denoise: added entry points), nor environment lighting (rbrt_environment_t and
                               rbrt_hip_scene_set_environment: an added struct and entry point, no new flag bit, every
-                              existing struct untouched; a host detects it by the symbol) */
+                              existing struct untouched; a host detects it by the symbol), nor the display transform
+                              (rbrt_tonemap_opts_t, rbrt_tonemap_result_t, rbrt_tonemap_opts_default and rbrt_hip_tonemap: added
+                              structs and entry points, detected by the symbol) */
 
 typedef enum rbrt_status {
     RBRT_OK = 0,
@@ -493,6 +495,81 @@ typedef struct rbrt_environment {
  * RBRT_ERR_INVALID_ARG, before the device is touched, the handle keeping the map it had: scene NULL; n == 0 or n > 4096;
  * reserved != 0; nodes NULL; a non-finite or negative component. */
 int rbrt_hip_scene_set_environment(rbrt_hip_scene_t* scene, const rbrt_environment_t* env);
+
+/* ---- Display transform: exposure, automatic exposure and tone mapping --------------------------------------------------------
+ * No counterpart in the reference, whose only way from radiance to a picture is the quantisation (sqrt(c) * 256) as u8
+ * (lib.rs:116-122): everything above 1.0 clips. The transform is a stage behind the image, like the denoiser: it reads n pixels
+ * X (RGB, linear radiance; the layout does not matter) and writes the transformed radiance and / or its quantisation.
+ *
+ * The rule. All arithmetic is float32, unfused, in the written order; / is correctly rounded; a constant is the float32 nearest
+ * to the decimal written.
+ *   Luminance of a colour c.  Y(c) = ((0.2126f * c_r) + (0.7152f * c_g)) + (0.0722f * c_b)
+ *   Histogram.  Made only when the exposure or the white point is automatic. A pixel is COUNTED iff the bits u of Y(X) satisfy
+ *     0x00800000 <= u <= 0x7F7FFFFF: a positive, normal, finite value. Zeros, denormals, negatives, infinities and NaN are
+ *     left out, and with them the zero padding of a packed tile buffer. A counted pixel's bin is u >> 19: 8 exponent bits and
+ *     4 mantissa bits, RBRT_TONEMAP_BINS = 4096 bins, each 2^(1/16) wide -- a logarithmic scale without a logarithm. M is the
+ *     number of counted pixels. The counts are integers: they do not depend on the order the pixels are visited in.
+ *   Rank pick, for a permille q in 0..1000.  k = ((M - 1) * q) / 1000 in 64-bit integers; b_q is the smallest bin with
+ *     hist[0] + ... + hist[b_q] > k; L_q is the float whose bits are (b_q << 19) | (1 << 18), the bin's midpoint in bits.
+ *   Exposure e.  opts.exposure > 0: e = opts.exposure. opts.exposure == 0 (automatic): e = opts.key / L_{key_permille} if
+ *     M > 0, else e = 1.0f.
+ *   White point w (used by the Reinhard curve only).  opts.white > 0: w = opts.white. opts.white == 0 (automatic):
+ *     w = e * L_{white_permille} if M > 0, else w = 1.0f. (white == 0 is automatic whatever the curve: a caller that wants
+ *     no histogram for a curve that ignores w passes any positive white.)
+ *   Per pixel, with c = (e * X_r, e * X_g, e * X_b):
+ *     RBRT_TONE_LINEAR    out = c
+ *     RBRT_TONE_REINHARD  extended Reinhard on the luminance: y = Y(c); s = (1.0f + (y / (w * w))) / (1.0f + y) if y > 0
+ *                         (false for NaN), else s = 1.0f; out_c = c_c * s. A grey of luminance w comes out with luminance 1.
+ *     RBRT_TONE_ACES      Narkowicz's rational fit, per channel: x = c_c * 0.6f;
+ *                         out_c = (x * ((2.51f * x) + 0.03f)) / ((x * ((2.43f * x) + 0.59f)) + 0.14f)
+ *   The float output is out; the 8-bit output is the usual quantisation of out.
+ * Two consequences. With e = 1 and RBRT_TONE_LINEAR the outputs are bit for bit the input and the render's own rgb8 (1.0f * x
+ * is x). Finite inputs with |e * X| <= 1e15 give no NaN (the squares in the ACES fit overflow to inf / inf near 3e38 / 0.6;
+ * Reinhard's y / (w * w) needs w * w neither 0 nor inf, which a w in 1e-15..1e15 gives). */
+#define RBRT_TONE_LINEAR 0u
+#define RBRT_TONE_REINHARD 1u
+#define RBRT_TONE_ACES 2u
+
+typedef struct rbrt_tonemap_opts {
+    uint32_t curve;          /* RBRT_TONE_LINEAR | _REINHARD | _ACES */
+    float exposure;          /* > 0: the multiplier; 0: automatic */
+    float key;               /* automatic exposure: what L_{key_permille} is mapped to; finite, > 0 */
+    uint32_t key_permille;   /* 0..1000 */
+    float white;             /* > 0: the white point; 0: automatic */
+    uint32_t white_permille; /* 0..1000 */
+    uint32_t reserved[2];    /* 0 */
+} rbrt_tonemap_opts_t;
+void rbrt_tonemap_opts_default(rbrt_tonemap_opts_t* opts); /* LINEAR, exposure 1, key 0.18, 500, white 0, 990 */
+
+typedef struct rbrt_tonemap_result { /* what the call chose; lives in the workspace, in device memory */
+    float exposure, white;           /* e and w as used */
+    float l_key, l_white;            /* the two L_q (0 when not computed) */
+    uint32_t counted, reserved;      /* M */
+    uint64_t pixels;                 /* n */
+} rbrt_tonemap_result_t;
+
+#define RBRT_TONEMAP_BINS 4096u
+#define RBRT_TONEMAP_RESULT_OFFSET (RBRT_TONEMAP_BINS * 4u)
+#define RBRT_TONEMAP_WORKSPACE_BYTES (RBRT_TONEMAP_RESULT_OFFSET + 32u)
+
+/* The transform on n_pixels pixels in DEVICE memory (float[n][3]; a row-major image is W * H pixels, a packed tile buffer
+ * rbrt_hip_packed_pixels(...) pixels). Asynchronous on `stream`; needs no scene, like rbrt_hip_unpack_tiles and
+ * rbrt_hip_denoise_halves, and owns no device memory. d_workspace: RBRT_TONEMAP_WORKSPACE_BYTES bytes of device memory of the
+ * caller's, 16-byte aligned; it may be NULL when neither exposure nor white is automatic. The call zeroes the histogram itself,
+ * in stream order. After the call the workspace holds the histogram as uint32[RBRT_TONEMAP_BINS] and, RBRT_TONEMAP_RESULT_OFFSET
+ * bytes in, the rbrt_tonemap_result_t (a host reads it with a 32-byte copy behind the stream). With a workspace the result is
+ * written even if nothing was automatic (counted, l_key and l_white are then 0 and so are the histogram's words). Two calls on
+ * different streams must not share a workspace.
+ * d_out_radiance (float[n][3]) may be exactly d_radiance (in place; any other overlap is undefined) or NULL; d_rgb8
+ * (uint8[n][3]) may be NULL. The kernels use 16-byte accesses when d_radiance and d_out_radiance are 16-byte aligned and d_rgb8
+ * 4-byte aligned; other pointers take a slower form that computes the same bits.
+ * RBRT_ERR_INVALID_ARG, before the device is touched: d_radiance or opts NULL; n_pixels == 0; an unknown curve; a non-zero
+ * reserved word; an exposure, key or white that is not finite; a negative exposure or white; key <= 0 while the exposure is
+ * automatic; a permille above 1000; automatic exposure or white with a NULL workspace; a workspace that is not 16-byte aligned.
+ * RBRT_ERR_UNSUPPORTED: n_pixels >= 2^32 (the bins are 32-bit). */
+int rbrt_hip_tonemap(int device, void* stream, const float* d_radiance, size_t n_pixels,
+                     const rbrt_tonemap_opts_t* opts, void* d_workspace,
+                     float* d_out_radiance, uint8_t* d_rgb8);
 
 /* De-interleave gathered per-rank packed tile buffers (concatenated rank 0..world-1, each
  * rbrt_hip_packed_pixels(...)*3 floats, device memory) into a row-major float[H][W][3] device

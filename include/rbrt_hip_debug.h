@@ -57,6 +57,12 @@ int rbrt_hip_scene_adaptive_rounds(rbrt_hip_scene_t* scene, uint32_t* active_til
  * sizes around it are where that kernel's edge handling changes (tests/test_denoise_gpu.py). */
 #define RBRT_DENOISE_TILE 16u
 
+/* The display transform's kernels (rbrt_amd/csrc/tonemap.hip): the pixels one workgroup takes per stride of its grid, and the
+ * cap of that grid. Pixel counts around BLOCK_PIXELS, and around MAX_BLOCKS * BLOCK_PIXELS where a workgroup starts to stride a
+ * second time, are where those kernels' paths change (tests/test_tonemap_gpu.py). */
+#define RBRT_TONEMAP_BLOCK_PIXELS 1024u
+#define RBRT_TONEMAP_MAX_BLOCKS 512u
+
 /* Test / diagnostic hook for Scene::hit (scene.rs:19-43): closest hit of n rays against the
  * resident scene. Host arrays. rays = n x {ox,oy,oz,dx,dy,dz}. Outputs (each may be NULL):
  *   out_t[n]      ray parameter of the winning object (NaN on miss)

@@ -4,7 +4,7 @@
 //
 // Goes to rbrt_lib/src/hip_ffi.rs (add `pub mod hip_ffi;` to rbrt_lib/src/lib.rs).
 
-use std::os::raw::{c_char, c_int};
+use std::os::raw::{c_char, c_int, c_void};
 
 #[repr(C)] #[derive(Copy, Clone)]
 pub struct RbrtMaterial { pub kind: i32, pub albedo: [f32; 3], pub param: f32 }   // 0 lambertian, 1 metal, 2 dielectric, 3 emissive
@@ -62,6 +62,20 @@ pub struct RbrtRenderOpts {
     pub seed: u64, pub tile_rank: u32, pub tile_world: u32, pub flags: u32, pub reserved: u32,
 }
 
+#[repr(C)]
+pub struct RbrtTonemapOpts {                           // rbrt_tonemap_opts_t: the display transform (exposure, tone curve)
+    pub curve: u32,                                    // 0 linear, 1 extended Reinhard, 2 ACES (Narkowicz)
+    pub exposure: f32,                                 // > 0: the multiplier; 0: automatic, from the luminance histogram
+    pub key: f32, pub key_permille: u32,               // automatic exposure: the luminance at this rank is mapped to key
+    pub white: f32, pub white_permille: u32,           // Reinhard's white point (> 0), or 0: the luminance at this rank
+    pub reserved: [u32; 2],                            // 0
+}
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct RbrtTonemapResult {                         // rbrt_tonemap_result_t: 32 bytes, 16 KiB into the device workspace
+    pub exposure: f32, pub white: f32, pub l_key: f32, pub l_white: f32, pub counted: u32, pub reserved: u32, pub pixels: u64,
+}
+pub const RBRT_TONEMAP_WORKSPACE_BYTES: usize = 4096 * 4 + 32;
+
 #[link(name = "rbrt_hip")]
 extern "C" {
     pub fn rbrt_render_opts_default(opts: *mut RbrtRenderOpts);
@@ -69,6 +83,10 @@ extern "C" {
                            out_radiance: *mut f32, out_rgb8: *mut u8) -> c_int;
     pub fn rbrt_hip_render_shaded(cam: *const RbrtCamera, scene: *const RbrtScene, shading: *const RbrtSceneShading,
                                   opts: *const RbrtRenderOpts, out_radiance: *mut f32, out_rgb8: *mut u8) -> c_int;
+    // device pointers; needs no scene handle. A host detects it by the symbol (the ABI version stays 2).
+    pub fn rbrt_tonemap_opts_default(opts: *mut RbrtTonemapOpts);
+    pub fn rbrt_hip_tonemap(device: c_int, stream: *mut c_void, d_radiance: *const f32, n_pixels: usize, opts: *const RbrtTonemapOpts,
+                            d_workspace: *mut c_void, d_out_radiance: *mut f32, d_rgb8: *mut u8) -> c_int;
     pub fn rbrt_hip_last_error() -> *const c_char;
     pub fn rbrt_hip_device_count() -> c_int;
     pub fn rbrt_hip_supported_flags() -> u32;           // test RBRT_FLAG_THIN_LENS here before relying on it

@@ -394,3 +394,34 @@ def denoise_halves(device: int, d_a: int, d_b: int, d_wa: int | None, width: int
     abi.check(load_hip().rbrt_hip_denoise_halves(device, C.c_void_p(stream or 0), C.c_void_p(d_a), C.c_void_p(d_b),
                                                  C.c_void_p(d_wa or 0), width, height, C.byref(d), C.c_void_p(d_radiance or 0),
                                                  C.c_void_p(d_rgb8 or 0)))
+
+
+def tonemap_opts(curve: int | None = None, exposure: float | None = None, key: float | None = None,
+                 key_permille: int | None = None, white: float | None = None, white_permille: int | None = None,
+                 reserved=(0, 0)) -> abi.TonemapOpts:
+    """rbrt_tonemap_opts_default (LINEAR, exposure 1, key 0.18 at permille 500, automatic white at permille 990), with the
+    parameters that are given put in. exposure or white 0: automatic."""
+    t = abi.TonemapOpts()
+    load_hip().rbrt_tonemap_opts_default(C.byref(t))
+    for name, value, kind in (("curve", curve, int), ("exposure", exposure, float), ("key", key, float),
+                              ("key_permille", key_permille, int), ("white", white, float), ("white_permille", white_permille, int)):
+        if value is not None:
+            setattr(t, name, kind(value))
+    t.reserved[0], t.reserved[1] = int(reserved[0]), int(reserved[1])
+    return t
+
+
+def tonemap(device: int, d_radiance: int, n_pixels: int, opts: abi.TonemapOpts, d_workspace: int | None,
+            d_out_radiance: int | None, d_rgb8: int | None = None, stream: int | None = None):
+    """The display transform on n_pixels pixels in device memory (rbrt_hip_tonemap): exposure, automatic exposure and white
+    point from the luminance histogram, and the tone curve. d_workspace: abi.TONEMAP_WORKSPACE_BYTES bytes of device memory
+    (the histogram, then an abi.TonemapResult), or None when nothing is automatic. d_out_radiance may be d_radiance (in
+    place). Asynchronous on `stream`."""
+    abi.check(load_hip().rbrt_hip_tonemap(device, C.c_void_p(stream or 0), C.c_void_p(d_radiance or 0), n_pixels,
+                                          C.byref(opts) if opts is not None else None, C.c_void_p(d_workspace or 0),
+                                          C.c_void_p(d_out_radiance or 0), C.c_void_p(d_rgb8 or 0)))
+
+
+def write_pfm(path, rgb) -> None:
+    """abi.write_pfm: a float32 (H, W, 3) image as a colour PFM."""
+    abi.write_pfm(path, rgb)

@@ -34,6 +34,12 @@ FLAG_COLLECT_STATS = 1
 FLAG_CONSTANT_BACKGROUND = 2  # rays that hit nothing return opts.bg instead of the sky gradient
 FLAG_THIN_LENS = 4  # the camera argument is the `cam` member of a CameraLens: defocus blur (rbrt_camera_lens_t)
 TILE = 8
+TONE_LINEAR, TONE_REINHARD, TONE_ACES = 0, 1, 2  # rbrt_tonemap_opts_t::curve
+TONEMAP_BINS = 4096
+TONEMAP_RESULT_OFFSET = TONEMAP_BINS * 4
+TONEMAP_WORKSPACE_BYTES = TONEMAP_RESULT_OFFSET + 32
+TONEMAP_BLOCK_PIXELS = 1024  # rbrt_hip_debug.h: pixels a workgroup of the transform's kernels takes per stride
+TONEMAP_MAX_BLOCKS = 512     # ... and the cap of their grid
 
 f32p = C.POINTER(C.c_float)
 u8p = C.POINTER(C.c_uint8)
@@ -155,6 +161,16 @@ class DenoiseOpts(C.Structure):  # rbrt_denoise_opts_t
     _fields_ = [("window_radius", C.c_uint32), ("patch_radius", C.c_uint32), ("strength", C.c_float), ("reserved", C.c_uint32)]
 
 
+class TonemapOpts(C.Structure):  # rbrt_tonemap_opts_t
+    _fields_ = [("curve", C.c_uint32), ("exposure", C.c_float), ("key", C.c_float), ("key_permille", C.c_uint32),
+                ("white", C.c_float), ("white_permille", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class TonemapResult(C.Structure):  # rbrt_tonemap_result_t: behind the histogram in the workspace, in device memory
+    _fields_ = [("exposure", C.c_float), ("white", C.c_float), ("l_key", C.c_float), ("l_white", C.c_float),
+                ("counted", C.c_uint32), ("reserved", C.c_uint32), ("pixels", C.c_uint64)]
+
+
 class Environment(C.Structure):  # rbrt_environment_t
     """An octahedral radiance map of (n + 1) x (n + 1) nodes: `nodes` points at host float32 [n + 1][n + 1][3]."""
     _fields_ = [("n", C.c_uint32), ("reserved", C.c_uint32), ("nodes", f32p)]
@@ -225,6 +241,9 @@ HIP_SYMBOLS = {
     "rbrt_denoise_opts_default": (None, [C.POINTER(DenoiseOpts)]),
     "rbrt_hip_denoise_halves": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
                                           C.POINTER(DenoiseOpts), C.c_void_p, C.c_void_p]),
+    "rbrt_tonemap_opts_default": (None, [C.POINTER(TonemapOpts)]),
+    "rbrt_hip_tonemap": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(TonemapOpts), C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
     "rbrt_hip_scene_denoise": (C.c_int, [C.c_void_p, C.POINTER(DenoiseOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rbrt_hip_scene_set_environment": (C.c_int, [C.c_void_p, C.POINTER(Environment)]),
 }
@@ -458,6 +477,10 @@ def load_host() -> C.CDLL:
     lib.rbrt_host_scene_environment.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     lib.rbrt_host_read_pfm.restype = C.c_int
     lib.rbrt_host_read_pfm.argtypes = [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), f32p]
+    lib.rbrt_host_read_pfm_any.restype = C.c_int
+    lib.rbrt_host_read_pfm_any.argtypes = [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), f32p]
+    lib.rbrt_host_write_pfm.restype = C.c_int
+    lib.rbrt_host_write_pfm.argtypes = [C.c_char_p, f32p, C.c_uint32, C.c_uint32]
     lib.rbrt_host_environment_nodes.restype = C.c_int
     lib.rbrt_host_environment_nodes.argtypes = [f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_double, f32p]
     lib.rbrt_host_environment_fingerprint.restype = C.c_uint64
@@ -553,17 +576,28 @@ class HostScene:
             pass
 
 
-def read_pfm(path) -> np.ndarray:
+def read_pfm(path, any_value: bool = False) -> np.ndarray:
     """The host's PFM reader (rbrt_host_read_pfm): float32 (H, W, 3), top row first. RuntimeError with the reader's
-    message for anything it refuses."""
+    message for anything it refuses. any_value: texels that are not finite or are negative are read too, bit for bit (what
+    write_pfm wrote); without it they are refused, as an environment map's are."""
     lib = load_host()
+    read = lib.rbrt_host_read_pfm_any if any_value else lib.rbrt_host_read_pfm
     w, h = C.c_uint32(), C.c_uint32()
-    if lib.rbrt_host_read_pfm(str(path).encode(), C.byref(w), C.byref(h), None) != 0:
+    if read(str(path).encode(), C.byref(w), C.byref(h), None) != 0:
         raise RuntimeError(lib.rbrt_host_last_error().decode(errors="replace"))
     out = np.zeros((h.value, w.value, 3), np.float32)
-    if lib.rbrt_host_read_pfm(str(path).encode(), C.byref(w), C.byref(h), fptr(out)) != 0:
+    if read(str(path).encode(), C.byref(w), C.byref(h), fptr(out)) != 0:
         raise RuntimeError(lib.rbrt_host_last_error().decode(errors="replace"))
     return out
+
+
+def write_pfm(path, rgb: np.ndarray) -> None:
+    """The host's PFM writer (rbrt_host_write_pfm; the CLI's --radiance): float32 (H, W, 3), top row first."""
+    rgb = np.ascontiguousarray(rgb, np.float32)
+    h, w, _ = rgb.shape
+    lib = load_host()
+    if lib.rbrt_host_write_pfm(str(path).encode(), fptr(rgb), w, h) != 0:
+        raise RuntimeError(lib.rbrt_host_last_error().decode(errors="replace"))
 
 
 def environment_nodes(rgb: np.ndarray, n: int, rotation_deg: float = 0.0, intensity: float = 1.0) -> np.ndarray:

@@ -40,6 +40,7 @@ hipError_t launch_tile_error(const AdaptiveParams& A, uint32_t n_active_tiles, h
 hipError_t launch_adaptive_finish(const AdaptiveParams& A, hipStream_t stream);
 hipError_t launch_denoise(const DenoiseParams& D, hipStream_t stream);                 // denoise.hip
 hipError_t launch_denoise_halves(const DenoiseHalvesParams& Q, hipStream_t stream);
+hipError_t launch_tonemap(const TonemapParams& T, hipStream_t stream);                 // tonemap.hip
 hipError_t launch_unpack(const float* gathered, uint32_t width, uint32_t height, uint32_t world,
                          size_t rank_stride_pixels, float* out_radiance, uint8_t* out_rgb8, hipStream_t stream);
 hipError_t launch_trace_rays(const TraceParams& P, const float* rays, size_t n, float* out_t, int32_t* out_obj,
@@ -2256,6 +2257,39 @@ int rbrt_hip_scene_denoise(rbrt_hip_scene_t* s, const rbrt_denoise_opts_t* d, vo
     HIP_TRY(launch_denoise_halves(Q, stream));
     if (!d_radiance && !d_rgb8) return RBRT_OK;
     HIP_TRY(launch_denoise(denoise_params(S.d_half_a, S.d_half_b, S.d_wa, S.last.width, S.last.height, d, d_radiance, d_rgb8), stream));
+    return RBRT_OK;
+}
+
+// ---- Display transform (the rule: include/rbrt_hip.h; the kernels: tonemap.hip) ----------------------------------------------
+void rbrt_tonemap_opts_default(rbrt_tonemap_opts_t* o) {
+    if (!o) return;
+    o->curve = RBRT_TONE_LINEAR, o->exposure = 1.0f, o->key = 0.18f, o->key_permille = 500u;
+    o->white = 0.0f, o->white_permille = 990u, o->reserved[0] = o->reserved[1] = 0u;
+}
+
+int rbrt_hip_tonemap(int device, void* stream, const float* d_radiance, size_t n_pixels, const rbrt_tonemap_opts_t* o,
+                     void* d_workspace, float* d_out_radiance, uint8_t* d_rgb8) {
+    if (!d_radiance || !o) return fail(RBRT_ERR_INVALID_ARG, "tonemap: null argument");
+    if (n_pixels == 0) return fail(RBRT_ERR_INVALID_ARG, "tonemap: n_pixels must be >= 1");
+    if (o->curve > RBRT_TONE_ACES) return fail(RBRT_ERR_INVALID_ARG, "tonemap: unknown curve");
+    if (o->reserved[0] != 0u || o->reserved[1] != 0u) return fail(RBRT_ERR_INVALID_ARG, "tonemap: reserved must be 0");
+    if (!std::isfinite(o->exposure) || !std::isfinite(o->key) || !std::isfinite(o->white))
+        return fail(RBRT_ERR_INVALID_ARG, "tonemap: exposure, key and white must be finite");
+    if (o->exposure < 0.0f || o->white < 0.0f) return fail(RBRT_ERR_INVALID_ARG, "tonemap: exposure and white must be >= 0");
+    const bool automatic = o->exposure == 0.0f || o->white == 0.0f;
+    if (o->exposure == 0.0f && !(o->key > 0.0f)) return fail(RBRT_ERR_INVALID_ARG, "tonemap: key must be > 0 for automatic exposure");
+    if (o->key_permille > 1000u || o->white_permille > 1000u) return fail(RBRT_ERR_INVALID_ARG, "tonemap: a permille must be 0..1000");
+    if (automatic && !d_workspace) return fail(RBRT_ERR_INVALID_ARG, "tonemap: automatic exposure or white needs a workspace");
+    if (reinterpret_cast<uintptr_t>(d_workspace) % 16u != 0u) return fail(RBRT_ERR_INVALID_ARG, "tonemap: the workspace must be 16-byte aligned");
+    if (uint64_t(n_pixels) >= (1ull << 32)) return fail(RBRT_ERR_UNSUPPORTED, "tonemap: 2^32 or more pixels (the bins are 32-bit)");
+    if (int rc = ensure_device(device)) return rc;
+    TonemapParams T;
+    std::memset(&T, 0, sizeof(T));
+    T.in = d_radiance, T.n = uint32_t(n_pixels), T.curve = o->curve;
+    T.exposure = o->exposure + 0.0f, T.white = o->white + 0.0f;  // (-0 is 0: automatic)
+    T.key = o->key, T.key_permille = o->key_permille, T.white_permille = o->white_permille;
+    T.hist = static_cast<uint32_t*>(d_workspace), T.out_radiance = d_out_radiance, T.out_rgb8 = d_rgb8;
+    HIP_TRY(launch_tonemap(T, static_cast<hipStream_t>(stream)));
     return RBRT_OK;
 }
 

@@ -271,4 +271,17 @@ struct DenoiseHalvesParams {
     float* out_b;
 };
 
+// The display transform (include/rbrt_hip.h "Display transform"; tonemap.hip): one rbrt_hip_tonemap call.
+struct TonemapParams {
+    const float* in;          // [n][3] linear radiance
+    uint32_t n;               // pixels, < 2^32
+    uint32_t curve;           // RBRT_TONE_*
+    float exposure, white;    // the manual values; 0: automatic
+    float key;
+    uint32_t key_permille, white_permille;
+    uint32_t* hist;           // the workspace: [RBRT_TONEMAP_BINS] words, the rbrt_tonemap_result_t behind them; may be null
+    float* out_radiance;      // [n][3], may be null or `in`
+    uint8_t* out_rgb8;        // [n][3], may be null
+};
+
 }  // namespace rbrt

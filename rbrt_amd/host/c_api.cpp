@@ -117,6 +117,28 @@ int rbrt_host_read_pfm(const char* path, uint32_t* width, uint32_t* height, floa
         return -1;
     }
 }
+// TEST HOOKS (tests/test_tonemap_host.py). The PFM writer of --radiance, and the reader with any_value: what the writer wrote
+// comes back bit for bit, NaN and negative texels included.
+int rbrt_host_write_pfm(const char* path, const float* rgb, uint32_t width, uint32_t height) {
+    try {
+        rbrt::write_pfm(path, rgb, width, height);
+        return 0;
+    } catch (const std::exception& e) {
+        g_err = e.what();
+        return -1;
+    }
+}
+int rbrt_host_read_pfm_any(const char* path, uint32_t* width, uint32_t* height, float* rgb) {
+    try {
+        const rbrt::PfmImage img = rbrt::read_pfm(path, true);
+        *width = img.width, *height = img.height;
+        if (rgb) std::memcpy(rgb, img.rgb.data(), img.rgb.size() * sizeof(float));
+        return 0;
+    } catch (const std::exception& e) {
+        g_err = e.what();
+        return -1;
+    }
+}
 // The conversion alone: a latitude/longitude image (top row first) -> nodes_out float[n + 1][n + 1][3].
 int rbrt_host_environment_nodes(const float* rgb, uint32_t width, uint32_t height, uint32_t n, double rotation_deg, double intensity,
                                 float* nodes_out) {

@@ -1,4 +1,5 @@
-// environment.cpp — environment lighting on the host side (no counterpart in the reference): the PFM reader and the
+// environment.cpp — environment lighting on the host side (no counterpart in the reference): the PFM reader (and the writer
+// of --radiance next to it) and the
 // conversion of a latitude/longitude image into the octahedral node grid of rbrt_environment_t (include/rbrt_hip.h
 // "Environment lighting"). The device looks the grid up with + - * / only; everything that needs atan2 / acos happens here,
 // once, in double.
@@ -35,7 +36,7 @@ bool parse_long(const std::string& t, long& out) {
 
 }  // namespace
 
-PfmImage read_pfm(const std::string& path) {
+PfmImage read_pfm(const std::string& path, bool any_value) {
     std::ifstream f(path, std::ios::binary);
     if (!f) throw Error("environment: cannot open \"" + path + "\"");
     std::stringstream ss;
@@ -73,13 +74,36 @@ PfmImage read_pfm(const std::string& path) {
                                          : uint32_t(b[3]) | uint32_t(b[2]) << 8 | uint32_t(b[1]) << 16 | uint32_t(b[0]) << 24;
             float v;
             std::memcpy(&v, &bits, 4);
-            if (!std::isfinite(v) || v < 0.0f)
+            if (!any_value && (!std::isfinite(v) || v < 0.0f))
                 throw bad("the texel in row " + std::to_string(row) + " (from the top), column " + std::to_string(k / 3u) +
                           " has a component that is not finite or is negative");
             dst[k] = v;
         }
     }
     return img;
+}
+
+// The writer read_pfm(path, true) undoes bit for bit: `PF`, the size, scale -1.0 (little-endian), rows bottom to top.
+void write_pfm(const std::string& path, const float* rgb, uint32_t width, uint32_t height) {
+    if (width == 0u || height == 0u || width > 65536u || height > 65536u) throw Error("write_pfm: the size must be between 1 and 65536");
+    std::string out = "PF\n" + std::to_string(width) + " " + std::to_string(height) + "\n-1.0\n";
+    const size_t header = out.size(), row_bytes = size_t(width) * 12u;
+    out.resize(header + row_bytes * height);
+    unsigned char* p = reinterpret_cast<unsigned char*>(&out[header]);
+    for (uint32_t row = 0; row < height; ++row) {
+        const float* src = rgb + size_t(height - 1u - row) * width * 3u;
+        for (size_t k = 0; k < size_t(width) * 3u; ++k) {
+            uint32_t bits;
+            std::memcpy(&bits, src + k, 4);
+            unsigned char* b = p + size_t(row) * row_bytes + 4u * k;
+            b[0] = uint8_t(bits), b[1] = uint8_t(bits >> 8), b[2] = uint8_t(bits >> 16), b[3] = uint8_t(bits >> 24);
+        }
+    }
+    std::ofstream f(path, std::ios::binary);
+    if (!f) throw Error("cannot write \"" + path + "\"");
+    f.write(out.data(), std::streamsize(out.size()));
+    f.close();
+    if (!f) throw Error("cannot write \"" + path + "\"");
 }
 
 // Node (j, i) of an N-grid looks along the octahedral direction of (u, v) = ((2i - N) / N, (2j - N) / N) -- 2i/N - 1 with

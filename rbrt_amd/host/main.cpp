@@ -10,7 +10,9 @@
 // --denoise-radius R, --denoise-patch P and --denoise-strength K (the target file gets the dual-buffer non-local-means filter of
 // the render's two half images), --noisy FILE (also the unfiltered image), --environment FILE.pfm | none with
 // --environment-rotation DEG, --environment-intensity X and --environment-resolution N (environment lighting: they override
-// the YAML's environment_blueprint).
+// the YAML's environment_blueprint), --exposure EV|auto with --exposure-key X, --tonemap none|reinhard|aces and --white X|auto
+// (the display transform between the radiance and the 8-bit target file: exposure in stops or chosen from the image's
+// luminance histogram, and a tone curve that rolls highlights off), --radiance FILE.pfm (the linear radiance, untransformed).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -73,6 +75,15 @@ void usage() {
         "      --denoise-patch <p>          denoise: radius of the compared patches, 0 to 4 [default: 3]\n"
         "      --denoise-strength <k>       denoise: filter strength, above 0; larger smooths more [default: 0.7]\n"
         "      --noisy <file>               denoise: also write the unfiltered image there (same formats as the target file)\n"
+        "      --exposure <EV|auto>         exposure of the target image in stops (the radiance is multiplied by 2^EV), or auto:\n"
+        "                                   the median luminance of the image is mapped to --exposure-key [default: 0]\n"
+        "      --exposure-key <x>           automatic exposure: what the median luminance is mapped to, above 0 [default: 0.18]\n"
+        "      --tonemap <curve>            tone curve of the target image: none (values above 1 clip), reinhard (extended\n"
+        "                                   Reinhard on the luminance) or aces (Narkowicz's fit) [default: none]\n"
+        "      --white <x|auto>             reinhard only: the exposed luminance that becomes white, above 0, or auto: the\n"
+        "                                   image's 99th percentile [default: auto]\n"
+        "      --radiance <file.pfm>        also write the linear radiance there as a colour PFM: before exposure and tone\n"
+        "                                   curve, filtered if --denoise is on\n"
         "  -h, --help                       Print help\n"
         "  -V, --version                    Print version\n");
 }
@@ -153,6 +164,10 @@ int main(int argc, char** argv) {
     std::optional<std::string> environment;  // a file, or "none"
     std::optional<float> environment_rotation, environment_intensity;
     std::optional<uint32_t> environment_resolution;
+    float exposure = 1.0f, exposure_key = 0.18f;  // the multiplier (0: automatic) and the key
+    uint32_t tone_curve = RBRT_TONE_LINEAR;
+    std::optional<float> white;  // given: the white point (0: automatic)
+    std::string radiance_file;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         std::string val;
@@ -289,6 +304,42 @@ int main(int argc, char** argv) {
                 return 2;
             }
             environment_resolution = v;
+        } else if (a == "--exposure") {
+            const std::string v = value();
+            float ev = 0.0f;
+            if (v == "auto") {
+                exposure = 0.0f;
+            } else if (parse_f32(v.c_str(), ev) && std::isfinite(ev) && std::isfinite(exposure = float(std::exp2(double(ev)))) && exposure > 0.0f) {
+            } else {
+                std::fprintf(stderr, "error: invalid value '%s' for '--exposure' (expected a number of stops whose 2^EV is a finite float above 0, or auto)\n", v.c_str());
+                return 2;
+            }
+        } else if (a == "--exposure-key") {
+            const char* v = value();
+            if (!parse_f32(v, exposure_key) || !std::isfinite(exposure_key) || !(exposure_key > 0.0f)) {
+                std::fprintf(stderr, "error: invalid value '%s' for '--exposure-key' (expected a finite number > 0)\n", v);
+                return 2;
+            }
+        } else if (a == "--tonemap") {
+            const std::string v = value();
+            if (v != "none" && v != "reinhard" && v != "aces") {
+                std::fprintf(stderr, "error: invalid value '%s' for '--tonemap' [possible values: none, reinhard, aces]\n", v.c_str());
+                return 2;
+            }
+            tone_curve = v == "none" ? RBRT_TONE_LINEAR : v == "reinhard" ? RBRT_TONE_REINHARD : RBRT_TONE_ACES;
+        } else if (a == "--white") {
+            const std::string v = value();
+            float f = 0.0f;
+            if (v == "auto") {
+                white = 0.0f;
+            } else if (parse_f32(v.c_str(), f) && std::isfinite(f) && f > 0.0f) {
+                white = f;
+            } else {
+                std::fprintf(stderr, "error: invalid value '%s' for '--white' (expected a finite number > 0, or auto)\n", v.c_str());
+                return 2;
+            }
+        } else if (a == "--radiance") {
+            radiance_file = value();
         } else if (a == "--shading") {
             const std::string v = value();
             if (v != "flat" && v != "smooth") {
@@ -336,6 +387,17 @@ int main(int argc, char** argv) {
             return 2;
         }
     }
+    if (white && tone_curve != RBRT_TONE_REINHARD) {
+        std::fprintf(stderr, "error: '--white' needs '--tonemap reinhard' (the other curves have no white point)\n");
+        return 2;
+    }
+    if (!radiance_file.empty() && (radiance_file.size() < 4 || radiance_file.compare(radiance_file.size() - 4, 4, ".pfm") != 0)) {
+        std::fprintf(stderr, "error: invalid value '%s' for '--radiance' (the linear radiance is written as a colour PFM: the name must end in .pfm)\n",
+                     radiance_file.c_str());
+        return 2;
+    }
+    // (0 EV and no curve is the identity: such a run makes no tonemap call at all and writes what it always wrote)
+    const bool transformed = exposure != 1.0f || tone_curve != RBRT_TONE_LINEAR;
     if (environment && *environment != "none" && constant_background) {
         std::fprintf(stderr, "error: '--background' cannot be combined with '--environment' (the environment is the background)\n");
         return 2;
@@ -392,12 +454,17 @@ int main(int argc, char** argv) {
             if (denoise_patch) cfg.denoise_patch_radius = *denoise_patch;
             if (denoise_strength) cfg.denoise_strength = *denoise_strength;
         }
+        if (transformed) {
+            cfg.tonemap = true, cfg.tonemap_curve = tone_curve, cfg.tonemap_exposure = exposure, cfg.tonemap_key = exposure_key;
+            cfg.tonemap_white = white ? *white : 0.0f;
+        }
         rbrt::ImageBuffer img = rbrt::render_scene(cam, samples, scene, cfg);
         std::printf("Saving rendered image to %s\n", target.c_str());
         const auto t3 = clock::now();
         img.save(target);
         if (!sample_map.empty()) img.save_sample_map(sample_map);
         if (!noisy.empty()) img.save_noisy(noisy);
+        if (!radiance_file.empty()) rbrt::write_pfm(radiance_file, img.radiance.data(), img.width, img.height);
         const auto t4 = clock::now();
         if (!report_path.empty()) {
             uint64_t triangles = 0;
@@ -433,6 +500,11 @@ int main(int argc, char** argv) {
             if (denoise) {  // the filter's parameters and its time on the GPU (a part of render_s)
                 num("denoise_window_radius", cfg.denoise_window_radius, "%.0f"), num("denoise_patch_radius", cfg.denoise_patch_radius, "%.0f");
                 num("denoise_strength", cfg.denoise_strength, "%.9g"), num("denoise_ms", rep.denoise_ms, "%.4f");
+            }
+            if (transformed) {  // the display transform: what it chose and its time on the GPU
+                str("tonemap", tone_curve == RBRT_TONE_LINEAR ? "none" : tone_curve == RBRT_TONE_REINHARD ? "reinhard" : "aces");
+                num("exposure", rep.tonemap_exposure, "%.9g"), num("white", rep.tonemap_white, "%.9g");
+                num("luminance_counted", rep.luminance_counted, "%.0f"), num("tonemap_ms", rep.tonemap_ms, "%.4f");
             }
             // where the run's time went; the parts add up to total_s (other_s is what none of them covers: thread start,
             // checkpoint look-up, the report itself)

@@ -195,7 +195,11 @@ struct PfmImage {
 };
 // A colour (`PF`) Portable Float Map, either byte order (the sign of the scale). Throws Error, with the reason, for anything
 // else: a grey `Pf`, a bad size or scale, a truncated file, bytes after the pixels, a texel that is not finite or is negative.
-PfmImage read_pfm(const std::string& path);
+// any_value: texels are taken as they are (what write_pfm wrote, NaN and negative values included), bit for bit.
+PfmImage read_pfm(const std::string& path, bool any_value = false);
+// A colour PFM of a row-major image, top row first: `PF`, little-endian (scale -1.0), rows bottom to top. Linear radiance leaves
+// the host this way (--radiance); ImageBuffer::save stays with the reference's 8-bit formats. Throws Error.
+void write_pfm(const std::string& path, const float* rgb, uint32_t width, uint32_t height);
 // The (n + 1) x (n + 1) x 3 nodes of rbrt_environment_t from a latitude/longitude image (DESIGN.md "Environment lighting").
 std::vector<float> environment_nodes_from_latlong(const PfmImage& img, uint32_t n, double rotation_deg, double intensity);
 struct Environment {
@@ -246,7 +250,7 @@ LoadTimes& load_times();
 struct ImageBuffer {
     uint32_t width = 0, height = 0;
     std::vector<uint8_t> rgb;        // row-major, 3 bytes per pixel
-    std::vector<float> radiance;     // row-major fp32 pre-gamma mean (extra to the reference)
+    std::vector<float> radiance;     // row-major fp32 pre-gamma mean (extra to the reference); linear whatever the display transform
     std::vector<uint8_t> sample_map; // an adaptive render: one byte per pixel, its tile's sample count * 255 / samples (else empty)
     std::vector<uint8_t> noisy_rgb;  // a denoised render with RenderConfig::keep_noisy: the unfiltered image, like rgb (else empty)
     void save(const std::string& path) const;  // .png (8-bit RGB) or .ppm by extension
@@ -277,6 +281,11 @@ struct RenderReport {
     uint64_t adaptive_samples = 0, adaptive_samples_fixed = 0;
     std::vector<uint32_t> adaptive_active_tiles;
     double denoise_ms = 0.0;  // a denoised render (RenderConfig::denoise): rbrt_hip_scene_denoise on the GPU, between two events
+    // a render with the display transform (RenderConfig::tonemap): e and w as used, the pixels the luminance histogram counted
+    // (0 when nothing was automatic) and rbrt_hip_tonemap on the GPU, between two events
+    float tonemap_exposure = 1.0f, tonemap_white = 1.0f;
+    uint32_t luminance_counted = 0;
+    double tonemap_ms = 0.0;
 };
 
 struct RenderConfig {  // additions that the reference hard-codes or lacks
@@ -306,6 +315,14 @@ struct RenderConfig {  // additions that the reference hard-codes or lacks
     uint32_t denoise_window_radius = 5, denoise_patch_radius = 3;  // (rbrt_denoise_opts_default)
     float denoise_strength = 0.7f;
     bool keep_noisy = false;  // also keep the unfiltered RGB8 image (ImageBuffer::noisy_rgb)
+    // The display transform (rbrt_hip_tonemap; the CLI's --exposure, --tonemap, --white): ImageBuffer::rgb (and noisy_rgb, with
+    // the same e and w) is the quantisation of the transformed image; ImageBuffer::radiance stays linear. It runs once, on the
+    // complete image, on rank 0's device: on the radiance that is there already, or on the gathered image.
+    bool tonemap = false;
+    uint32_t tonemap_curve = RBRT_TONE_LINEAR;
+    float tonemap_exposure = 1.0f;  // the multiplier; 0: automatic, the luminance at tonemap_key's rank is mapped to tonemap_key
+    float tonemap_key = 0.18f;
+    float tonemap_white = 0.0f;     // Reinhard's white point; 0: automatic
 };
 // rbrt_lib::render_scene (lib.rs:75-79): blocks until the image is complete. Runs on the GPU(s)
 // through the C ABI; there is no CPU path.

@@ -152,6 +152,44 @@ double seconds_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
 
+// The display transform's options of a render (rbrt_hip.h "Display transform"). Only the Reinhard curve reads the white point:
+// the other curves get a manual one, so that no histogram is made on its account.
+rbrt_tonemap_opts_t tonemap_opts_of(const RenderConfig& cfg) {
+    rbrt_tonemap_opts_t t;
+    rbrt_tonemap_opts_default(&t);
+    t.curve = cfg.tonemap_curve, t.exposure = cfg.tonemap_exposure, t.key = cfg.tonemap_key;
+    t.white = cfg.tonemap_curve == RBRT_TONE_REINHARD ? cfg.tonemap_white : 1.0f;
+    return t;
+}
+
+// One rbrt_hip_tonemap call on n_pixels of d_src (memory of `dev`), on `stream`: the quantised result goes through d_rgb to
+// host_rgb, what the call chose to *chosen, its time between two events to *ms. Returns the error, or an empty string.
+std::string run_tonemap(int dev, hipStream_t stream, const float* d_src, size_t n_pixels, const rbrt_tonemap_opts_t& t, uint8_t* d_rgb,
+                        uint8_t* host_rgb, rbrt_tonemap_result_t* chosen, float* ms) {
+    std::string err;
+    const auto ok = [&](hipError_t e, const char* what) {
+        if (e != hipSuccess && err.empty()) err = std::string(what) + ": " + hipGetErrorString(e);
+        return e == hipSuccess;
+    };
+    void* ws = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (ok(hipSetDevice(dev), "hipSetDevice") && ok(hipMalloc(&ws, RBRT_TONEMAP_WORKSPACE_BYTES), "hipMalloc(tonemap workspace)") &&
+        ok(hipEventCreate(&e0), "hipEventCreate") && ok(hipEventCreate(&e1), "hipEventCreate")) {
+        ok(hipEventRecord(e0, stream), "hipEventRecord");
+        if (rbrt_hip_tonemap(dev, stream, d_src, n_pixels, &t, ws, nullptr, d_rgb) != RBRT_OK && err.empty()) err = rbrt_hip_last_error();
+        ok(hipEventRecord(e1, stream), "hipEventRecord");
+        ok(hipMemcpyAsync(chosen, static_cast<const char*>(ws) + RBRT_TONEMAP_RESULT_OFFSET, sizeof(*chosen), hipMemcpyDeviceToHost, stream),
+           "download of the tonemap result");
+        ok(hipMemcpyAsync(host_rgb, d_rgb, n_pixels * 3, hipMemcpyDeviceToHost, stream), "download of the transformed image");
+        ok(hipStreamSynchronize(stream), "tonemap");
+        if (err.empty()) ok(hipEventElapsedTime(ms, e0, e1), "hipEventElapsedTime");
+    }
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (ws) (void)hipFree(ws);
+    return err;
+}
+
 }  // namespace
 
 ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& scene, const RenderConfig& cfg_in) {
@@ -309,6 +347,7 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
     float* d_slots = nullptr;  // rank 0, RCCL gather: world equal-size slots of packed tiles
     const size_t slot_pixels = world > 1 ? rbrt_hip_packed_pixels(img.width, img.height, 0, uint32_t(world)) : 0;
     RenderReport rep;
+    bool tonemapped = false;  // rank 0 has run the display transform on its device (else, where one is wanted, it runs after the host gather)
     rep.n_gpus = world;
     rep.pass_spp = pass_spp;
     rep.gather = world > 1 ? (use_rccl ? "rccl" : "host") : "none";
@@ -319,6 +358,7 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
     auto worker = [&](int rank) {
         rbrt_hip_scene_t* hs = nullptr;
         float *d_acc = nullptr, *d_rad = nullptr, *d_img = nullptr;
+        float* d_noisy = nullptr;  // a denoised, transformed render that keeps the unfiltered image: that image's radiance
         uint8_t* d_rgb = nullptr;
         hipStream_t stream = nullptr;
         bool failed = false;  // this rank's own view: it has recorded an error
@@ -334,6 +374,26 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
         auto hip_ok = [&](hipError_t e, const char* what) {
             if (e != hipSuccess) fail(std::string(what) + ": " + hipGetErrorString(e));
             return e == hipSuccess;
+        };
+        // The display transform of the complete image, which is d_src on this rank's device: img.rgb becomes its quantisation
+        // (img.radiance stays linear), and the unfiltered image, where one is kept, goes through the same e and w.
+        auto display_transform = [&](int on_dev, hipStream_t on_stream, const float* d_src, uint8_t* d_out8) {
+            rbrt_tonemap_result_t chosen{};
+            float ms = 0.0f;
+            const std::string e = run_tonemap(on_dev, on_stream, d_src, size_t(img.width) * img.height, tonemap_opts_of(cfg), d_out8,
+                                              img.rgb.data(), &chosen, &ms);
+            if (!e.empty()) return fail(e);
+            rep.tonemap_exposure = chosen.exposure, rep.tonemap_white = chosen.white, rep.luminance_counted = chosen.counted;
+            rep.tonemap_ms = ms;
+            if (d_noisy) {  // a second call, with what was chosen for the target image as manual values
+                rbrt_tonemap_opts_t t = tonemap_opts_of(cfg);
+                t.exposure = chosen.exposure, t.white = chosen.white;
+                rbrt_tonemap_result_t again{};
+                const std::string e2 = run_tonemap(on_dev, on_stream, d_noisy, size_t(img.width) * img.height, t, d_out8, img.noisy_rgb.data(),
+                                                   &again, &ms);
+                if (!e2.empty()) fail(e2);
+            }
+            tonemapped = true;
         };
         const auto t_start = std::chrono::steady_clock::now();
         rbrt_render_opts_t o = opts;
@@ -405,6 +465,8 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
                 if (cfg.keep_noisy) {
                     img.noisy_rgb.resize(n);
                     hip_ok(hipMemcpy(img.noisy_rgb.data(), d_rgb, n, hipMemcpyDeviceToHost), "download of the unfiltered image");
+                    if (cfg.tonemap && hip_ok(hipMalloc(reinterpret_cast<void**>(&d_noisy), n * sizeof(float)), "hipMalloc(unfiltered radiance)"))
+                        hip_ok(hipMemcpy(d_noisy, d_rad, n * sizeof(float), hipMemcpyDeviceToDevice), "copy of the unfiltered radiance");
                 }
                 const rbrt_denoise_opts_t dn = {cfg.denoise_window_radius, cfg.denoise_patch_radius, cfg.denoise_strength, 0u};
                 hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -495,6 +557,7 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
             if (!failed && npix) {
                 hip_ok(hipMemcpy(img.radiance.data(), d_rad, n * sizeof(float), hipMemcpyDeviceToHost), "download");
                 hip_ok(hipMemcpy(img.rgb.data(), d_rgb, n, hipMemcpyDeviceToHost), "download");
+                if (cfg.tonemap && !failed) display_transform(dev, stream, d_rad, d_rgb);  // on the radiance that is here already
             }
         } else if (use_rccl) {
             // The decision to enter the group is taken ONCE, between two barriers: before the first every rank has
@@ -555,6 +618,7 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
                 } else if (rank == 0 && !failed) {
                     hip_ok(hipMemcpy(img.radiance.data(), d_img, n * sizeof(float), hipMemcpyDeviceToHost), "download");
                     hip_ok(hipMemcpy(img.rgb.data(), d_rgb, n, hipMemcpyDeviceToHost), "download");
+                    if (cfg.tonemap && !failed) display_transform(dev, stream, d_img, d_rgb);  // on the gathered image
                 }
             }
         } else {
@@ -566,6 +630,7 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
         if (d_rad) (void)hipFree(d_rad);
         if (d_rgb) (void)hipFree(d_rgb);
         if (d_img) (void)hipFree(d_img);
+        if (d_noisy) (void)hipFree(d_noisy);
         if (rank == 0 && d_slots) (void)hipFree(d_slots);
         if (stream) (void)hipStreamDestroy(stream);
         rbrt_hip_scene_destroy(hs);
@@ -584,6 +649,29 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
     for (int r = 0; r < world; ++r)
         if (!errors[r].empty()) throw Error("GPU " + std::to_string(device_of(r)) + (cfg.oversubscribe ? " (rank " + std::to_string(r) + ")" : "") + ": " + errors[r]);
     if (!cfg.checkpoint_path.empty()) std::remove(cfg.checkpoint_path.c_str());  // (only reached when the render is complete)
+    if (cfg.tonemap && !tonemapped) {
+        // The ranks' tiles were merged on the host: the complete image goes up to rank 0's device once, so that the target file
+        // does not depend on how many GPUs rendered it or on how their tiles were gathered.
+        const int dev = device_of(0);
+        float* d_src = nullptr;
+        uint8_t* d_out8 = nullptr;
+        std::string err;
+        const auto ok = [&](hipError_t e, const char* what) {
+            if (e != hipSuccess && err.empty()) err = std::string(what) + ": " + hipGetErrorString(e);
+            return e == hipSuccess;
+        };
+        if (ok(hipSetDevice(dev), "hipSetDevice") && ok(hipMalloc(reinterpret_cast<void**>(&d_src), n * sizeof(float)), "hipMalloc(image)") &&
+            ok(hipMalloc(reinterpret_cast<void**>(&d_out8), n), "hipMalloc(rgb8)") &&
+            ok(hipMemcpy(d_src, img.radiance.data(), n * sizeof(float), hipMemcpyHostToDevice), "upload of the gathered image")) {
+            rbrt_tonemap_result_t chosen{};
+            float ms = 0.0f;
+            err = run_tonemap(dev, nullptr, d_src, n / 3, tonemap_opts_of(cfg), d_out8, img.rgb.data(), &chosen, &ms);
+            rep.tonemap_exposure = chosen.exposure, rep.tonemap_white = chosen.white, rep.luminance_counted = chosen.counted, rep.tonemap_ms = ms;
+        }
+        if (d_src) (void)hipFree(d_src);
+        if (d_out8) (void)hipFree(d_out8);
+        if (!err.empty()) throw Error("GPU " + std::to_string(dev) + ": " + err);
+    }
     if (!cfg.quiet) std::printf("\rRendering 100%% complete!\n");
     rep.resumed_from_sample = start_sample;
     {   // the slowest rank's set-up, split (the parts of one rank, so that they add up)

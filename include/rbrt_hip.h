@@ -61,7 +61,9 @@ extern "C" {
                               rbrt_hip_scene_set_environment: an added struct and entry point, no new flag bit, every
                               existing struct untouched; a host detects it by the symbol), nor the display transform
                               (rbrt_tonemap_opts_t, rbrt_tonemap_result_t, rbrt_tonemap_opts_default and rbrt_hip_tonemap: added
-                              structs and entry points, detected by the symbol) */
+                              structs and entry points, detected by the symbol), nor glare
+                              (rbrt_glare_opts_t, rbrt_glare_opts_default, rbrt_hip_glare_workspace_bytes and rbrt_hip_glare:
+                              an added struct and entry points, detected by the symbol) */
 
 typedef enum rbrt_status {
     RBRT_OK = 0,
@@ -570,6 +572,69 @@ typedef struct rbrt_tonemap_result { /* what the call chose; lives in the worksp
 int rbrt_hip_tonemap(int device, void* stream, const float* d_radiance, size_t n_pixels,
                      const rbrt_tonemap_opts_t* opts, void* d_workspace,
                      float* d_out_radiance, uint8_t* d_rgb8);
+
+/* ---- Glare: a pyramid bloom stage in front of the display transform ----------------------------------------------------------
+ * No counterpart in the reference. After any tone curve a sun of radiance 50 and one of radiance 5000 are the same white disc;
+ * a lens, or an eye, tells them apart by the share of a bright source's light that scatters into its surroundings (Spencer et
+ * al. 1995). The stage reads an image X, float[H][W][3], row-major, W, H >= 1, and writes the image with that share moved.
+ * It belongs between the radiance and the exposure: denoise -> glare -> display transform.
+ *
+ * The rule. All arithmetic is float32, unfused, in the written order; / is correctly rounded; a constant is the float32 nearest
+ * to the decimal written. Options: threshold T, intensity i, levels L, spread s.
+ *   Bright pass.  Y(c) is the display transform's luminance: ((0.2126f * c_r) + (0.7152f * c_g)) + (0.0722f * c_b). A pixel is
+ *     BRIGHT iff the bits u of Y(X) satisfy 0x00800000 <= u <= 0x7F7FFFFF (the display transform's "counted" test) and Y > T.
+ *     For a bright pixel k = (Y - T) / Y and B_c = X_c * k; every other pixel has B = 0. With T = 0, k is exactly 1. NaN,
+ *     infinities, zero, denormals and negative luminance never enter the pyramid: a non-finite pixel stays a defect of its own
+ *     pixel and poisons no neighbourhood.
+ *   Pyramid sizes.  W_0 = W, H_0 = H; W_l = (W_{l-1} + 1) / 2 and H_l = (H_{l-1} + 1) / 2 in integers (never 0).
+ *     cl(k, n) = min(max(k, 0), n - 1).
+ *   REDUCE (Burt-Adelson, weights 1 4 6 4 1 over 16, edges replicated) maps F of size h x w to h' x w'. Rows first:
+ *       r[y][x'] = ((((F[y][cl(2x'-2,w)] + (4.0f * F[y][cl(2x'-1,w)])) + (6.0f * F[y][cl(2x',w)])) + (4.0f * F[y][cl(2x'+1,w)]))
+ *                   + F[y][cl(2x'+2,w)]) * 0.0625f
+ *     then columns: D[y'][x'] is the same expression over r[cl(2y'-2,h)][x'] .. r[cl(2y'+2,h)][x'].
+ *     D_0 = B, and D_l = REDUCE(D_{l-1}) for l = 1..L.
+ *   EXPAND maps G of size h' x w' to h x w. Rows first, then columns with the same two forms. Along one axis, for the output
+ *     index x with k = x >> 1 (cl against the size of G along that axis):
+ *       even x:  ((G[cl(k-1)] + (6.0f * G[k])) + G[cl(k+1)]) * 0.125f
+ *       odd x:   (G[k] + G[cl(k+1)]) * 0.5f
+ *   Collapse.  G_L = D_L; for l = L-1 down to 1: G_l = D_l + (s * EXPAND(G_{l+1})); E = EXPAND(G_1) at H x W. D_0 is
+ *     deliberately not added: unblurred light is not glare. So no full-resolution intermediate is stored: the composite
+ *     recomputes B from X.
+ *   Normalisation.  n = 1, p = 1; for l = 2..L: p = p * s, then n = n + p. inv = 1.0f / n; a = i * inv.
+ *   Output.  out_c = (X_c - (i * B_c)) + (a * E_c). The 8-bit output is the usual quantisation of out.
+ * Consequences. An image with nothing bright comes back equal as floats (a -0.0f becomes +0.0f), and its rgb8 is identical.
+ * Light is moved, not added: for an impulse far from the edges each input's weights sum to 1/4 in REDUCE and to 4 in EXPAND,
+ * so sum(E) = n * sum(B) up to rounding and sum(out) = sum(X). A constant image with T = 0 and s = 1 gives B == X, E == L * X
+ * where the sums round exactly, and out == X. */
+#define RBRT_GLARE_MAX_LEVELS 8u
+
+typedef struct rbrt_glare_opts {
+    float threshold;      /* T: luminance above which a pixel is bright; finite, >= 0 */
+    float intensity;      /* i: the share of the bright light that is moved; in (0, 1] */
+    uint32_t levels;      /* L: 1..RBRT_GLARE_MAX_LEVELS; the widest lobe is about 2^(L+1) pixels */
+    float spread;         /* s: the weight of each coarser level against the one below it; finite, >= 0 */
+    uint32_t reserved[4]; /* 0 */
+} rbrt_glare_opts_t;
+void rbrt_glare_opts_default(rbrt_glare_opts_t* opts); /* T = 1, i = 0.1, L = 5, s = 1 */
+
+/* The bytes of device memory rbrt_hip_glare needs as its workspace: the pyramid's levels 1..levels, in the library's own layout
+ * (a pixel padded to 16 bytes). 0 for arguments the call would refuse: a zero size, levels 0 or above the maximum,
+ * width * height >= 2^31. */
+size_t rbrt_hip_glare_workspace_bytes(uint32_t width, uint32_t height, uint32_t levels);
+
+/* The stage on a row-major image in DEVICE memory. Asynchronous on `stream`; needs no scene and owns no device memory.
+ * d_workspace: rbrt_hip_glare_workspace_bytes(width, height, opts->levels) bytes of device memory of the caller's, 16-byte
+ * aligned; the call assumes nothing about its contents and leaves the pyramid in it. Two calls on different streams must not
+ * share a workspace. d_out_radiance (float[H][W][3]) may be exactly d_radiance (in place: a thread reads its own X before it
+ * writes; any other overlap is undefined) or NULL; d_rgb8 (uint8[H][W][3]) may be NULL; with both NULL nothing is launched.
+ * The composite uses 16-byte accesses when the width is a multiple of 4, d_radiance and d_out_radiance are 16-byte aligned and
+ * d_rgb8 is 4-byte aligned; anything else takes a slower form that computes the same bits.
+ * RBRT_ERR_INVALID_ARG, before the device is touched: d_radiance, opts or d_workspace NULL; width or height 0; levels 0 or above
+ * RBRT_GLARE_MAX_LEVELS; a non-zero reserved word; a threshold, intensity or spread that is not finite; threshold < 0;
+ * intensity outside (0, 1]; spread < 0; a workspace that is not 16-byte aligned.
+ * RBRT_ERR_UNSUPPORTED: width * height >= 2^31. */
+int rbrt_hip_glare(int device, void* stream, const float* d_radiance, uint32_t width, uint32_t height,
+                   const rbrt_glare_opts_t* opts, void* d_workspace, float* d_out_radiance, uint8_t* d_rgb8);
 
 /* De-interleave gathered per-rank packed tile buffers (concatenated rank 0..world-1, each
  * rbrt_hip_packed_pixels(...)*3 floats, device memory) into a row-major float[H][W][3] device

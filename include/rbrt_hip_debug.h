@@ -63,6 +63,12 @@ int rbrt_hip_scene_adaptive_rounds(rbrt_hip_scene_t* scene, uint32_t* active_til
 #define RBRT_TONEMAP_BLOCK_PIXELS 1024u
 #define RBRT_TONEMAP_MAX_BLOCKS 512u
 
+/* The glare stage's kernels (rbrt_amd/csrc/glare.hip): the tile of a pyramid level that one workgroup of the REDUCE kernel
+ * makes, from (2 * TILE_W + 3) x (2 * TILE_H + 3) pixels of the level above. Image sizes around twice the tile are where that
+ * kernel's edge handling changes; the composite's workgroup takes 4 * TILE_W x TILE_H pixels (tests/test_glare_gpu.py). */
+#define RBRT_GLARE_TILE_W 16u
+#define RBRT_GLARE_TILE_H 16u
+
 /* Test / diagnostic hook for Scene::hit (scene.rs:19-43): closest hit of n rays against the
  * resident scene. Host arrays. rays = n x {ox,oy,oz,dx,dy,dz}. Outputs (each may be NULL):
  *   out_t[n]      ray parameter of the winning object (NaN on miss)

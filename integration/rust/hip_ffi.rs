@@ -76,6 +76,16 @@ pub struct RbrtTonemapResult {                         // rbrt_tonemap_result_t:
 }
 pub const RBRT_TONEMAP_WORKSPACE_BYTES: usize = 4096 * 4 + 32;
 
+#[repr(C)]
+pub struct RbrtGlareOpts {                             // rbrt_glare_opts_t: glare, a pyramid bloom in front of the display transform
+    pub threshold: f32,                                // luminance above which a pixel is bright; >= 0
+    pub intensity: f32,                                // the share of the bright light that is moved; in (0, 1]
+    pub levels: u32,                                   // 1..=RBRT_GLARE_MAX_LEVELS
+    pub spread: f32,                                   // weight of each coarser level against the one below it; >= 0
+    pub reserved: [u32; 4],                            // 0
+}
+pub const RBRT_GLARE_MAX_LEVELS: u32 = 8;
+
 #[link(name = "rbrt_hip")]
 extern "C" {
     pub fn rbrt_render_opts_default(opts: *mut RbrtRenderOpts);
@@ -87,6 +97,11 @@ extern "C" {
     pub fn rbrt_tonemap_opts_default(opts: *mut RbrtTonemapOpts);
     pub fn rbrt_hip_tonemap(device: c_int, stream: *mut c_void, d_radiance: *const f32, n_pixels: usize, opts: *const RbrtTonemapOpts,
                             d_workspace: *mut c_void, d_out_radiance: *mut f32, d_rgb8: *mut u8) -> c_int;
+    // device pointers; needs no scene handle; the workspace is the caller's, rbrt_hip_glare_workspace_bytes(...) bytes, 16-byte aligned
+    pub fn rbrt_glare_opts_default(opts: *mut RbrtGlareOpts);
+    pub fn rbrt_hip_glare_workspace_bytes(width: u32, height: u32, levels: u32) -> usize;
+    pub fn rbrt_hip_glare(device: c_int, stream: *mut c_void, d_radiance: *const f32, width: u32, height: u32, opts: *const RbrtGlareOpts,
+                          d_workspace: *mut c_void, d_out_radiance: *mut f32, d_rgb8: *mut u8) -> c_int;
     pub fn rbrt_hip_last_error() -> *const c_char;
     pub fn rbrt_hip_device_count() -> c_int;
     pub fn rbrt_hip_supported_flags() -> u32;           // test RBRT_FLAG_THIN_LENS here before relying on it

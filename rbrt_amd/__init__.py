@@ -422,6 +422,35 @@ def tonemap(device: int, d_radiance: int, n_pixels: int, opts: abi.TonemapOpts, 
                                           C.c_void_p(d_out_radiance or 0), C.c_void_p(d_rgb8 or 0)))
 
 
+def glare_opts(threshold: float | None = None, intensity: float | None = None, levels: int | None = None,
+               spread: float | None = None, reserved=(0, 0, 0, 0)) -> abi.GlareOpts:
+    """rbrt_glare_opts_default (threshold 1, intensity 0.1, 5 levels, spread 1), with the parameters that are given put in."""
+    g = abi.GlareOpts()
+    load_hip().rbrt_glare_opts_default(C.byref(g))
+    for name, value, kind in (("threshold", threshold, float), ("intensity", intensity, float), ("levels", levels, int),
+                              ("spread", spread, float)):
+        if value is not None:
+            setattr(g, name, kind(value))
+    for k in range(4):
+        g.reserved[k] = int(reserved[k])
+    return g
+
+
+def glare_workspace_bytes(width: int, height: int, levels: int) -> int:
+    """rbrt_hip_glare_workspace_bytes: the device memory glare() needs for its pyramid; 0 for sizes or levels it refuses."""
+    return int(load_hip().rbrt_hip_glare_workspace_bytes(width, height, levels))
+
+
+def glare(device: int, d_radiance: int, width: int, height: int, opts: abi.GlareOpts, d_workspace: int | None,
+          d_out_radiance: int | None, d_rgb8: int | None = None, stream: int | None = None):
+    """The glare stage on a row-major image in device memory (rbrt_hip_glare): a share of every bright pixel's light is moved
+    into its surroundings through a pyramid of blurs. d_workspace: glare_workspace_bytes(width, height, opts.levels) bytes
+    of device memory, 16-byte aligned. d_out_radiance may be d_radiance (in place). Asynchronous on `stream`."""
+    abi.check(load_hip().rbrt_hip_glare(device, C.c_void_p(stream or 0), C.c_void_p(d_radiance or 0), width, height,
+                                        C.byref(opts) if opts is not None else None, C.c_void_p(d_workspace or 0),
+                                        C.c_void_p(d_out_radiance or 0), C.c_void_p(d_rgb8 or 0)))
+
+
 def write_pfm(path, rgb) -> None:
     """abi.write_pfm: a float32 (H, W, 3) image as a colour PFM."""
     abi.write_pfm(path, rgb)

@@ -40,6 +40,9 @@ TONEMAP_RESULT_OFFSET = TONEMAP_BINS * 4
 TONEMAP_WORKSPACE_BYTES = TONEMAP_RESULT_OFFSET + 32
 TONEMAP_BLOCK_PIXELS = 1024  # rbrt_hip_debug.h: pixels a workgroup of the transform's kernels takes per stride
 TONEMAP_MAX_BLOCKS = 512     # ... and the cap of their grid
+GLARE_MAX_LEVELS = 8         # rbrt_hip.h: the most levels of the glare stage's pyramid
+GLARE_TILE_W = 16            # rbrt_hip_debug.h: the tile of a pyramid level one workgroup of the REDUCE kernel makes
+GLARE_TILE_H = 16
 
 f32p = C.POINTER(C.c_float)
 u8p = C.POINTER(C.c_uint8)
@@ -171,6 +174,11 @@ class TonemapResult(C.Structure):  # rbrt_tonemap_result_t: behind the histogram
                 ("counted", C.c_uint32), ("reserved", C.c_uint32), ("pixels", C.c_uint64)]
 
 
+class GlareOpts(C.Structure):  # rbrt_glare_opts_t
+    _fields_ = [("threshold", C.c_float), ("intensity", C.c_float), ("levels", C.c_uint32), ("spread", C.c_float),
+                ("reserved", C.c_uint32 * 4)]
+
+
 class Environment(C.Structure):  # rbrt_environment_t
     """An octahedral radiance map of (n + 1) x (n + 1) nodes: `nodes` points at host float32 [n + 1][n + 1][3]."""
     _fields_ = [("n", C.c_uint32), ("reserved", C.c_uint32), ("nodes", f32p)]
@@ -244,6 +252,10 @@ HIP_SYMBOLS = {
     "rbrt_tonemap_opts_default": (None, [C.POINTER(TonemapOpts)]),
     "rbrt_hip_tonemap": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(TonemapOpts), C.c_void_p, C.c_void_p,
                                    C.c_void_p]),
+    "rbrt_glare_opts_default": (None, [C.POINTER(GlareOpts)]),
+    "rbrt_hip_glare_workspace_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint32]),
+    "rbrt_hip_glare": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(GlareOpts), C.c_void_p, C.c_void_p,
+                                 C.c_void_p]),
     "rbrt_hip_scene_denoise": (C.c_int, [C.c_void_p, C.POINTER(DenoiseOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rbrt_hip_scene_set_environment": (C.c_int, [C.c_void_p, C.POINTER(Environment)]),
 }

@@ -41,6 +41,7 @@ hipError_t launch_adaptive_finish(const AdaptiveParams& A, hipStream_t stream);
 hipError_t launch_denoise(const DenoiseParams& D, hipStream_t stream);                 // denoise.hip
 hipError_t launch_denoise_halves(const DenoiseHalvesParams& Q, hipStream_t stream);
 hipError_t launch_tonemap(const TonemapParams& T, hipStream_t stream);                 // tonemap.hip
+hipError_t launch_glare(const GlareParams& G, hipStream_t stream);                     // glare.hip
 hipError_t launch_unpack(const float* gathered, uint32_t width, uint32_t height, uint32_t world,
                          size_t rank_stride_pixels, float* out_radiance, uint8_t* out_rgb8, hipStream_t stream);
 hipError_t launch_trace_rays(const TraceParams& P, const float* rays, size_t n, float* out_t, int32_t* out_obj,
@@ -2290,6 +2291,57 @@ int rbrt_hip_tonemap(int device, void* stream, const float* d_radiance, size_t n
     T.key = o->key, T.key_permille = o->key_permille, T.white_permille = o->white_permille;
     T.hist = static_cast<uint32_t*>(d_workspace), T.out_radiance = d_out_radiance, T.out_rgb8 = d_rgb8;
     HIP_TRY(launch_tonemap(T, static_cast<hipStream_t>(stream)));
+    return RBRT_OK;
+}
+
+// ---- Glare (the rule: include/rbrt_hip.h; the kernels: glare.hip) -------------------------------------------------------------
+void rbrt_glare_opts_default(rbrt_glare_opts_t* o) {
+    if (!o) return;
+    o->threshold = 1.0f, o->intensity = 0.1f, o->levels = 5u, o->spread = 1.0f;
+    o->reserved[0] = o->reserved[1] = o->reserved[2] = o->reserved[3] = 0u;
+}
+
+size_t rbrt_hip_glare_workspace_bytes(uint32_t width, uint32_t height, uint32_t levels) {
+    if (width == 0u || height == 0u || levels == 0u || levels > RBRT_GLARE_MAX_LEVELS) return 0;
+    if (uint64_t(width) * height >= (1ull << 31)) return 0;
+    size_t pixels = 0;  // (levels 1..L, the layout of launch_glare: float4 a pixel, level after level)
+    uint32_t w = width, h = height;
+    for (uint32_t l = 1; l <= levels; ++l) {
+        w = (w + 1u) / 2u, h = (h + 1u) / 2u;
+        pixels += size_t(w) * h;
+    }
+    return pixels * 16u;
+}
+
+int rbrt_hip_glare(int device, void* stream, const float* d_radiance, uint32_t width, uint32_t height, const rbrt_glare_opts_t* o,
+                   void* d_workspace, float* d_out_radiance, uint8_t* d_rgb8) {
+    if (!d_radiance || !o || !d_workspace) return fail(RBRT_ERR_INVALID_ARG, "glare: null argument");
+    if (width == 0u || height == 0u) return fail(RBRT_ERR_INVALID_ARG, "glare: width and height must be >= 1");
+    if (o->levels == 0u || o->levels > RBRT_GLARE_MAX_LEVELS) return fail(RBRT_ERR_INVALID_ARG, "glare: levels must be 1..8");
+    if (o->reserved[0] != 0u || o->reserved[1] != 0u || o->reserved[2] != 0u || o->reserved[3] != 0u)
+        return fail(RBRT_ERR_INVALID_ARG, "glare: reserved must be 0");
+    if (!std::isfinite(o->threshold) || !std::isfinite(o->intensity) || !std::isfinite(o->spread))
+        return fail(RBRT_ERR_INVALID_ARG, "glare: threshold, intensity and spread must be finite");
+    if (o->threshold < 0.0f) return fail(RBRT_ERR_INVALID_ARG, "glare: threshold must be >= 0");
+    if (!(o->intensity > 0.0f) || o->intensity > 1.0f) return fail(RBRT_ERR_INVALID_ARG, "glare: intensity must be above 0 and at most 1");
+    if (o->spread < 0.0f) return fail(RBRT_ERR_INVALID_ARG, "glare: spread must be >= 0");
+    if (reinterpret_cast<uintptr_t>(d_workspace) % 16u != 0u) return fail(RBRT_ERR_INVALID_ARG, "glare: the workspace must be 16-byte aligned");
+    if (uint64_t(width) * height >= (1ull << 31)) return fail(RBRT_ERR_UNSUPPORTED, "glare: 2^31 or more pixels");
+    if (int rc = ensure_device(device)) return rc;
+    GlareParams G;
+    std::memset(&G, 0, sizeof(G));
+    G.in = d_radiance, G.width = width, G.height = height, G.levels = o->levels;
+    G.threshold = o->threshold + 0.0f, G.intensity = o->intensity, G.spread = o->spread + 0.0f;  // (-0 is 0)
+    // the rule's normalisation, in float, one operation a statement (this file is compiled with -ffp-contract=off)
+    float n = 1.0f, p = 1.0f;
+    for (uint32_t l = 2; l <= G.levels; ++l) {
+        p = p * G.spread;
+        n = n + p;
+    }
+    const float inv = 1.0f / n;
+    G.a = G.intensity * inv;
+    G.workspace = d_workspace, G.out_radiance = d_out_radiance, G.out_rgb8 = d_rgb8;
+    HIP_TRY(launch_glare(G, static_cast<hipStream_t>(stream)));
     return RBRT_OK;
 }
 

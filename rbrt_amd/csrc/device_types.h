@@ -284,4 +284,16 @@ struct TonemapParams {
     uint8_t* out_rgb8;        // [n][3], may be null
 };
 
+// The glare stage (include/rbrt_hip.h "Glare"; glare.hip): one rbrt_hip_glare call.
+struct GlareParams {
+    const float* in;          // [height][width][3] linear radiance
+    uint32_t width, height;   // width * height < 2^31
+    uint32_t levels;          // 1..RBRT_GLARE_MAX_LEVELS
+    float threshold, intensity, spread;
+    float a;                  // intensity * (1 / n), the rule's normalisation, computed on the host
+    void* workspace;          // the pyramid's levels 1..levels, float4 a pixel, level after level
+    float* out_radiance;      // [height][width][3], may be null or `in`
+    uint8_t* out_rgb8;        // [height][width][3], may be null
+};
+
 }  // namespace rbrt

@@ -13,6 +13,8 @@
 // the YAML's environment_blueprint), --exposure EV|auto with --exposure-key X, --tonemap none|reinhard|aces and --white X|auto
 // (the display transform between the radiance and the 8-bit target file: exposure in stops or chosen from the image's
 // luminance histogram, and a tone curve that rolls highlights off), --radiance FILE.pfm (the linear radiance, untransformed).
+// --glare INTENSITY with --glare-threshold T, --glare-levels L and --glare-spread S (glare: that share of the light above the
+// threshold is moved into a bright pixel's surroundings through a pyramid of blurs, in front of the display transform).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -82,8 +84,13 @@ void usage() {
         "                                   Reinhard on the luminance) or aces (Narkowicz's fit) [default: none]\n"
         "      --white <x|auto>             reinhard only: the exposed luminance that becomes white, above 0, or auto: the\n"
         "                                   image's 99th percentile [default: auto]\n"
-        "      --radiance <file.pfm>        also write the linear radiance there as a colour PFM: before exposure and tone\n"
-        "                                   curve, filtered if --denoise is on\n"
+        "      --glare <intensity>          glare: move this share, above 0 and at most 1, of the light of pixels brighter than\n"
+        "                                   --glare-threshold into their surroundings, before exposure and tone curve\n"
+        "      --glare-threshold <t>        glare: the luminance above which a pixel is bright, 0 or more [default: 1]\n"
+        "      --glare-levels <l>           glare: levels of the blur pyramid, 1 to 8; each doubles the widest halo [default: 5]\n"
+        "      --glare-spread <s>           glare: weight of each coarser level against the one below it, 0 or more [default: 1]\n"
+        "      --radiance <file.pfm>        also write the linear radiance there as a colour PFM: before glare, exposure and\n"
+        "                                   tone curve, filtered if --denoise is on\n"
         "  -h, --help                       Print help\n"
         "  -V, --version                    Print version\n");
 }
@@ -168,6 +175,8 @@ int main(int argc, char** argv) {
     uint32_t tone_curve = RBRT_TONE_LINEAR;
     std::optional<float> white;  // given: the white point (0: automatic)
     std::string radiance_file;
+    std::optional<float> glare, glare_threshold, glare_spread;  // --glare turns the stage on; the others need it
+    std::optional<uint32_t> glare_levels;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         std::string val;
@@ -338,6 +347,30 @@ int main(int argc, char** argv) {
                 std::fprintf(stderr, "error: invalid value '%s' for '--white' (expected a finite number > 0, or auto)\n", v.c_str());
                 return 2;
             }
+        } else if (a == "--glare") {
+            const char* v = value();
+            float f = 0.0f;
+            if (!parse_f32(v, f) || !std::isfinite(f) || !(f > 0.0f) || f > 1.0f) {
+                std::fprintf(stderr, "error: invalid value '%s' for '--glare' (expected a number above 0 and at most 1)\n", v);
+                return 2;
+            }
+            glare = f;
+        } else if (a == "--glare-threshold" || a == "--glare-spread") {
+            const char* v = value();
+            float f = 0.0f;
+            if (!parse_f32(v, f) || !std::isfinite(f) || f < 0.0f) {
+                std::fprintf(stderr, "error: invalid value '%s' for '%s' (expected a finite number >= 0)\n", v, a.c_str());
+                return 2;
+            }
+            (a == "--glare-threshold" ? glare_threshold : glare_spread) = f + 0.0f;
+        } else if (a == "--glare-levels") {
+            uint32_t v = 0;
+            u32(v);
+            if (v < 1u || v > RBRT_GLARE_MAX_LEVELS) {
+                std::fprintf(stderr, "error: invalid value '%u' for '--glare-levels' (expected 1 to %u)\n", v, RBRT_GLARE_MAX_LEVELS);
+                return 2;
+            }
+            glare_levels = v;
         } else if (a == "--radiance") {
             radiance_file = value();
         } else if (a == "--shading") {
@@ -384,6 +417,13 @@ int main(int argc, char** argv) {
                             : !noisy.empty() ? "--noisy" : nullptr;
         if (alone) {
             std::fprintf(stderr, "error: '%s' needs '--denoise'\n", alone);
+            return 2;
+        }
+    }
+    if (!glare) {
+        const char* alone = glare_threshold ? "--glare-threshold" : glare_levels ? "--glare-levels" : glare_spread ? "--glare-spread" : nullptr;
+        if (alone) {
+            std::fprintf(stderr, "error: '%s' needs '--glare'\n", alone);
             return 2;
         }
     }
@@ -454,6 +494,12 @@ int main(int argc, char** argv) {
             if (denoise_patch) cfg.denoise_patch_radius = *denoise_patch;
             if (denoise_strength) cfg.denoise_strength = *denoise_strength;
         }
+        if (glare) {
+            cfg.glare = true, cfg.glare_intensity = *glare;
+            if (glare_threshold) cfg.glare_threshold = *glare_threshold;
+            if (glare_levels) cfg.glare_levels = *glare_levels;
+            if (glare_spread) cfg.glare_spread = *glare_spread;
+        }
         if (transformed) {
             cfg.tonemap = true, cfg.tonemap_curve = tone_curve, cfg.tonemap_exposure = exposure, cfg.tonemap_key = exposure_key;
             cfg.tonemap_white = white ? *white : 0.0f;
@@ -500,6 +546,9 @@ int main(int argc, char** argv) {
             if (denoise) {  // the filter's parameters and its time on the GPU (a part of render_s)
                 num("denoise_window_radius", cfg.denoise_window_radius, "%.0f"), num("denoise_patch_radius", cfg.denoise_patch_radius, "%.0f");
                 num("denoise_strength", cfg.denoise_strength, "%.9g"), num("denoise_ms", rep.denoise_ms, "%.4f");
+            }
+            if (glare) {  // the glare stage: its options and its time on the GPU
+                num("glare", cfg.glare_intensity, "%.9g"), num("glare_levels", cfg.glare_levels, "%.0f"), num("glare_ms", rep.glare_ms, "%.4f");
             }
             if (transformed) {  // the display transform: what it chose and its time on the GPU
                 str("tonemap", tone_curve == RBRT_TONE_LINEAR ? "none" : tone_curve == RBRT_TONE_REINHARD ? "reinhard" : "aces");

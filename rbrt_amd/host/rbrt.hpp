@@ -286,6 +286,7 @@ struct RenderReport {
     float tonemap_exposure = 1.0f, tonemap_white = 1.0f;
     uint32_t luminance_counted = 0;
     double tonemap_ms = 0.0;
+    double glare_ms = 0.0;  // a render with glare (RenderConfig::glare): rbrt_hip_glare on the GPU, between two events
 };
 
 struct RenderConfig {  // additions that the reference hard-codes or lacks
@@ -323,6 +324,13 @@ struct RenderConfig {  // additions that the reference hard-codes or lacks
     float tonemap_exposure = 1.0f;  // the multiplier; 0: automatic, the luminance at tonemap_key's rank is mapped to tonemap_key
     float tonemap_key = 0.18f;
     float tonemap_white = 0.0f;     // Reinhard's white point; 0: automatic
+    // Glare (rbrt_hip_glare; the CLI's --glare, --glare-threshold, --glare-levels, --glare-spread): it runs once, on the complete
+    // image, directly in front of the display transform (denoise -> glare -> display transform), so automatic exposure sees
+    // the glared image. Without a display transform ImageBuffer::rgb is the glare call's own rgb8. ImageBuffer::radiance
+    // stays the scene's radiance without glare.
+    bool glare = false;
+    float glare_intensity = 0.1f, glare_threshold = 1.0f, glare_spread = 1.0f;  // (rbrt_glare_opts_default)
+    uint32_t glare_levels = 5;
 };
 // rbrt_lib::render_scene (lib.rs:75-79): blocks until the image is complete. Runs on the GPU(s)
 // through the C ABI; there is no CPU path.

@@ -190,6 +190,54 @@ std::string run_tonemap(int dev, hipStream_t stream, const float* d_src, size_t 
     return err;
 }
 
+// The glare stage's options of a render (rbrt_hip.h "Glare").
+rbrt_glare_opts_t glare_opts_of(const RenderConfig& cfg) {
+    rbrt_glare_opts_t g;
+    rbrt_glare_opts_default(&g);
+    g.threshold = cfg.glare_threshold, g.intensity = cfg.glare_intensity, g.levels = cfg.glare_levels, g.spread = cfg.glare_spread;
+    return g;
+}
+
+// What stands between the complete image's radiance d_src (w x h pixels in memory of `dev`) and the 8-bit image, on `stream`:
+// the glare stage, where the render has one, then the display transform, where it has one (`t`: its options). The last of the
+// two writes the quantised result, which goes through d_rgb to host_rgb; with both, the glared radiance passes through a
+// buffer of this call's own. *chosen and *tonemap_ms are run_tonemap's; *glare_ms is rbrt_hip_glare between two events.
+// Returns the error, or an empty string.
+std::string run_display(const RenderConfig& cfg, int dev, hipStream_t stream, const float* d_src, uint32_t w, uint32_t h,
+                        const rbrt_tonemap_opts_t& t, uint8_t* d_rgb, uint8_t* host_rgb, rbrt_tonemap_result_t* chosen, float* tonemap_ms,
+                        float* glare_ms) {
+    std::string err;
+    const auto ok = [&](hipError_t e, const char* what) {
+        if (e != hipSuccess && err.empty()) err = std::string(what) + ": " + hipGetErrorString(e);
+        return e == hipSuccess;
+    };
+    const size_t n_pixels = size_t(w) * h;
+    float* d_glared = nullptr;
+    if (cfg.glare) {
+        const rbrt_glare_opts_t g = glare_opts_of(cfg);
+        void* ws = nullptr;
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        if (ok(hipSetDevice(dev), "hipSetDevice") &&
+            ok(hipMalloc(&ws, rbrt_hip_glare_workspace_bytes(w, h, g.levels)), "hipMalloc(glare workspace)") &&
+            (!cfg.tonemap || ok(hipMalloc(reinterpret_cast<void**>(&d_glared), n_pixels * 3 * sizeof(float)), "hipMalloc(glared radiance)")) &&
+            ok(hipEventCreate(&e0), "hipEventCreate") && ok(hipEventCreate(&e1), "hipEventCreate")) {
+            ok(hipEventRecord(e0, stream), "hipEventRecord");
+            if (rbrt_hip_glare(dev, stream, d_src, w, h, &g, ws, d_glared, cfg.tonemap ? nullptr : d_rgb) != RBRT_OK && err.empty())
+                err = rbrt_hip_last_error();
+            ok(hipEventRecord(e1, stream), "hipEventRecord");
+            if (!cfg.tonemap) ok(hipMemcpyAsync(host_rgb, d_rgb, n_pixels * 3, hipMemcpyDeviceToHost, stream), "download of the glared image");
+            ok(hipStreamSynchronize(stream), "glare");
+            if (err.empty()) ok(hipEventElapsedTime(glare_ms, e0, e1), "hipEventElapsedTime");
+        }
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        if (ws) (void)hipFree(ws);
+    }
+    if (err.empty() && cfg.tonemap) err = run_tonemap(dev, stream, d_glared ? d_glared : d_src, n_pixels, t, d_rgb, host_rgb, chosen, tonemap_ms);
+    if (d_glared) (void)hipFree(d_glared);
+    return err;
+}
+
 }  // namespace
 
 ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& scene, const RenderConfig& cfg_in) {
@@ -347,7 +395,7 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
     float* d_slots = nullptr;  // rank 0, RCCL gather: world equal-size slots of packed tiles
     const size_t slot_pixels = world > 1 ? rbrt_hip_packed_pixels(img.width, img.height, 0, uint32_t(world)) : 0;
     RenderReport rep;
-    bool tonemapped = false;  // rank 0 has run the display transform on its device (else, where one is wanted, it runs after the host gather)
+    bool tonemapped = false;  // rank 0 has run glare and the display transform on its device (else, where either is wanted, they run after the host gather)
     rep.n_gpus = world;
     rep.pass_spp = pass_spp;
     rep.gather = world > 1 ? (use_rccl ? "rccl" : "host") : "none";
@@ -358,7 +406,7 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
     auto worker = [&](int rank) {
         rbrt_hip_scene_t* hs = nullptr;
         float *d_acc = nullptr, *d_rad = nullptr, *d_img = nullptr;
-        float* d_noisy = nullptr;  // a denoised, transformed render that keeps the unfiltered image: that image's radiance
+        float* d_noisy = nullptr;  // a denoised, glared or transformed render that keeps the unfiltered image: that image's radiance
         uint8_t* d_rgb = nullptr;
         hipStream_t stream = nullptr;
         bool failed = false;  // this rank's own view: it has recorded an error
@@ -375,22 +423,26 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
             if (e != hipSuccess) fail(std::string(what) + ": " + hipGetErrorString(e));
             return e == hipSuccess;
         };
-        // The display transform of the complete image, which is d_src on this rank's device: img.rgb becomes its quantisation
-        // (img.radiance stays linear), and the unfiltered image, where one is kept, goes through the same e and w.
+        // Glare and the display transform of the complete image, which is d_src on this rank's device: img.rgb becomes the
+        // quantisation of the result (img.radiance stays linear and without glare), and the unfiltered image, where one is kept,
+        // goes through the same glare options and the same e and w.
         auto display_transform = [&](int on_dev, hipStream_t on_stream, const float* d_src, uint8_t* d_out8) {
             rbrt_tonemap_result_t chosen{};
-            float ms = 0.0f;
-            const std::string e = run_tonemap(on_dev, on_stream, d_src, size_t(img.width) * img.height, tonemap_opts_of(cfg), d_out8,
-                                              img.rgb.data(), &chosen, &ms);
+            float ms = 0.0f, glare_ms = 0.0f;
+            const std::string e = run_display(cfg, on_dev, on_stream, d_src, img.width, img.height, tonemap_opts_of(cfg), d_out8,
+                                              img.rgb.data(), &chosen, &ms, &glare_ms);
             if (!e.empty()) return fail(e);
-            rep.tonemap_exposure = chosen.exposure, rep.tonemap_white = chosen.white, rep.luminance_counted = chosen.counted;
-            rep.tonemap_ms = ms;
-            if (d_noisy) {  // a second call, with what was chosen for the target image as manual values
+            if (cfg.tonemap) {
+                rep.tonemap_exposure = chosen.exposure, rep.tonemap_white = chosen.white, rep.luminance_counted = chosen.counted;
+                rep.tonemap_ms = ms;
+            }
+            rep.glare_ms = glare_ms;
+            if (d_noisy) {  // a second pass: the same glare, and what was chosen for the target image as manual values
                 rbrt_tonemap_opts_t t = tonemap_opts_of(cfg);
                 t.exposure = chosen.exposure, t.white = chosen.white;
                 rbrt_tonemap_result_t again{};
-                const std::string e2 = run_tonemap(on_dev, on_stream, d_noisy, size_t(img.width) * img.height, t, d_out8, img.noisy_rgb.data(),
-                                                   &again, &ms);
+                const std::string e2 = run_display(cfg, on_dev, on_stream, d_noisy, img.width, img.height, t, d_out8, img.noisy_rgb.data(),
+                                                   &again, &ms, &glare_ms);
                 if (!e2.empty()) fail(e2);
             }
             tonemapped = true;
@@ -465,7 +517,7 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
                 if (cfg.keep_noisy) {
                     img.noisy_rgb.resize(n);
                     hip_ok(hipMemcpy(img.noisy_rgb.data(), d_rgb, n, hipMemcpyDeviceToHost), "download of the unfiltered image");
-                    if (cfg.tonemap && hip_ok(hipMalloc(reinterpret_cast<void**>(&d_noisy), n * sizeof(float)), "hipMalloc(unfiltered radiance)"))
+                    if ((cfg.tonemap || cfg.glare) && hip_ok(hipMalloc(reinterpret_cast<void**>(&d_noisy), n * sizeof(float)), "hipMalloc(unfiltered radiance)"))
                         hip_ok(hipMemcpy(d_noisy, d_rad, n * sizeof(float), hipMemcpyDeviceToDevice), "copy of the unfiltered radiance");
                 }
                 const rbrt_denoise_opts_t dn = {cfg.denoise_window_radius, cfg.denoise_patch_radius, cfg.denoise_strength, 0u};
@@ -557,7 +609,7 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
             if (!failed && npix) {
                 hip_ok(hipMemcpy(img.radiance.data(), d_rad, n * sizeof(float), hipMemcpyDeviceToHost), "download");
                 hip_ok(hipMemcpy(img.rgb.data(), d_rgb, n, hipMemcpyDeviceToHost), "download");
-                if (cfg.tonemap && !failed) display_transform(dev, stream, d_rad, d_rgb);  // on the radiance that is here already
+                if ((cfg.tonemap || cfg.glare) && !failed) display_transform(dev, stream, d_rad, d_rgb);  // on the radiance that is here already
             }
         } else if (use_rccl) {
             // The decision to enter the group is taken ONCE, between two barriers: before the first every rank has
@@ -618,7 +670,7 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
                 } else if (rank == 0 && !failed) {
                     hip_ok(hipMemcpy(img.radiance.data(), d_img, n * sizeof(float), hipMemcpyDeviceToHost), "download");
                     hip_ok(hipMemcpy(img.rgb.data(), d_rgb, n, hipMemcpyDeviceToHost), "download");
-                    if (cfg.tonemap && !failed) display_transform(dev, stream, d_img, d_rgb);  // on the gathered image
+                    if ((cfg.tonemap || cfg.glare) && !failed) display_transform(dev, stream, d_img, d_rgb);  // on the gathered image
                 }
             }
         } else {
@@ -649,7 +701,7 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
     for (int r = 0; r < world; ++r)
         if (!errors[r].empty()) throw Error("GPU " + std::to_string(device_of(r)) + (cfg.oversubscribe ? " (rank " + std::to_string(r) + ")" : "") + ": " + errors[r]);
     if (!cfg.checkpoint_path.empty()) std::remove(cfg.checkpoint_path.c_str());  // (only reached when the render is complete)
-    if (cfg.tonemap && !tonemapped) {
+    if ((cfg.tonemap || cfg.glare) && !tonemapped) {
         // The ranks' tiles were merged on the host: the complete image goes up to rank 0's device once, so that the target file
         // does not depend on how many GPUs rendered it or on how their tiles were gathered.
         const int dev = device_of(0);
@@ -664,9 +716,10 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
             ok(hipMalloc(reinterpret_cast<void**>(&d_out8), n), "hipMalloc(rgb8)") &&
             ok(hipMemcpy(d_src, img.radiance.data(), n * sizeof(float), hipMemcpyHostToDevice), "upload of the gathered image")) {
             rbrt_tonemap_result_t chosen{};
-            float ms = 0.0f;
-            err = run_tonemap(dev, nullptr, d_src, n / 3, tonemap_opts_of(cfg), d_out8, img.rgb.data(), &chosen, &ms);
-            rep.tonemap_exposure = chosen.exposure, rep.tonemap_white = chosen.white, rep.luminance_counted = chosen.counted, rep.tonemap_ms = ms;
+            float ms = 0.0f, glare_ms = 0.0f;
+            err = run_display(cfg, dev, nullptr, d_src, img.width, img.height, tonemap_opts_of(cfg), d_out8, img.rgb.data(), &chosen, &ms, &glare_ms);
+            if (cfg.tonemap) rep.tonemap_exposure = chosen.exposure, rep.tonemap_white = chosen.white, rep.luminance_counted = chosen.counted, rep.tonemap_ms = ms;
+            rep.glare_ms = glare_ms;
         }
         if (d_src) (void)hipFree(d_src);
         if (d_out8) (void)hipFree(d_out8);

@@ -16,6 +16,15 @@
 // time that path is asked for: a single-GPU run, or the host gather, does not depend on it.
 // RenderConfig::oversubscribe (CLI --oversubscribe) maps rank r to device r % n_devices, so that every line of the
 // N-rank path except the RCCL calls themselves (which need distinct devices) runs on a box with fewer GPUs.
+//
+// How the file reads: render_scene, at the end, is the list of steps. make_plan refuses what cannot be rendered and starts the
+// HIP runtime; the checkpoint's fingerprint, reader and writer are checkpoint.cpp (no GPU code); bring_up_rccl makes the
+// communicators. A rank is a `Rank`: setup, render_adaptive (with denoise) or render_passes, one of gather_single /
+// gather_rccl / gather_host, release -- the four timed regions of Rank::run. What the ranks only read is the `Job`, what they
+// share and write is `Shared` (errors and failure counters, the barrier, checkpoint staging, the report, the timers, rank 0's
+// slots). `display` is glare and the display transform of the target and the unfiltered image; a rank calls it on its own
+// device, display_after_host_gather after uploading the merged image. Device memory, events, streams and first-error-wins
+// are the four small owners at the top; nothing else frees or destroys.
 #include <dlfcn.h>
 #include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>  // types and prototypes only: the library is not linked
@@ -27,10 +36,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <fstream>
 #include <mutex>
 #include <thread>
 
+#include "checkpoint.hpp"
 #include "rbrt.hpp"
 #include "../../include/rbrt_hip_debug.h"
 
@@ -57,49 +66,6 @@ class Barrier {  // all-ranks rendezvous between passes (checkpoint consistency,
     std::condition_variable cv_;
     int n_, count_ = 0;
     uint64_t gen_ = 0;
-};
-
-uint64_t fnv1a(const void* p, size_t n, uint64_t h) {
-    const unsigned char* b = static_cast<const unsigned char*>(p);
-    for (size_t i = 0; i < n; ++i) h = (h ^ b[i]) * 0x100000001B3ull;
-    return h;
-}
-
-// What a checkpoint must match to be resumed: everything the running sums depend on.
-uint64_t scene_fingerprint(const rbrt_camera_t& cam, const rbrt_scene_t& sc) {
-    uint64_t h = 0xCBF29CE484222325ull;
-    h = fnv1a(&cam, sizeof(cam), h);
-    for (uint32_t i = 0; i < sc.n_spheres; ++i) h = fnv1a(&sc.spheres[i], sizeof(rbrt_sphere_t), h);
-    for (uint32_t i = 0; i < sc.n_meshes; ++i) {
-        const rbrt_mesh_t& m = sc.meshes[i];
-        h = fnv1a(&m.n_total, sizeof(m.n_total), h);
-        h = fnv1a(&m.mat, sizeof(m.mat), h);
-        const float* arrs[12] = {m.v0x, m.v0y, m.v0z, m.e1x, m.e1y, m.e1z, m.e2x, m.e2y, m.e2z, m.nx, m.ny, m.nz};
-        for (const float* a : arrs) h = fnv1a(a, size_t(m.n_total) * sizeof(float), h);
-        h = fnv1a(m.is_padding, m.n_total, h);
-    }
-    return h;
-}
-
-// ... and the corner normals of smooth meshes, only when there are any (a flat scene's checkpoints keep their fingerprint).
-uint64_t shading_fingerprint(const rbrt_scene_t& sc, const rbrt_scene_shading_t* sh, uint64_t h) {
-    if (!sh || !sh->meshes) return h;
-    for (uint32_t i = 0; i < sh->n_meshes; ++i) {
-        const rbrt_mesh_normals_t& mn = sh->meshes[i];
-        const uint32_t smooth = mn.n0x != nullptr;
-        h = fnv1a(&smooth, sizeof(smooth), h);
-        if (!smooth) continue;
-        const float* arrs[9] = {mn.n0x, mn.n0y, mn.n0z, mn.n1x, mn.n1y, mn.n1z, mn.n2x, mn.n2y, mn.n2z};
-        for (const float* a : arrs) h = fnv1a(a, size_t(sc.meshes[i].n_total) * sizeof(float), h);
-    }
-    return h;
-}
-
-struct CheckpointHeader {
-    char magic[8];  // "RBRTCKP1"
-    uint32_t width, height, spp, world;
-    uint64_t seed, fingerprint;
-    uint32_t samples_done, reserved;
 };
 
 // librccl, loaded on first use (`--gather rccl` with more than one GPU).
@@ -162,34 +128,6 @@ rbrt_tonemap_opts_t tonemap_opts_of(const RenderConfig& cfg) {
     return t;
 }
 
-// One rbrt_hip_tonemap call on n_pixels of d_src (memory of `dev`), on `stream`: the quantised result goes through d_rgb to
-// host_rgb, what the call chose to *chosen, its time between two events to *ms. Returns the error, or an empty string.
-std::string run_tonemap(int dev, hipStream_t stream, const float* d_src, size_t n_pixels, const rbrt_tonemap_opts_t& t, uint8_t* d_rgb,
-                        uint8_t* host_rgb, rbrt_tonemap_result_t* chosen, float* ms) {
-    std::string err;
-    const auto ok = [&](hipError_t e, const char* what) {
-        if (e != hipSuccess && err.empty()) err = std::string(what) + ": " + hipGetErrorString(e);
-        return e == hipSuccess;
-    };
-    void* ws = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (ok(hipSetDevice(dev), "hipSetDevice") && ok(hipMalloc(&ws, RBRT_TONEMAP_WORKSPACE_BYTES), "hipMalloc(tonemap workspace)") &&
-        ok(hipEventCreate(&e0), "hipEventCreate") && ok(hipEventCreate(&e1), "hipEventCreate")) {
-        ok(hipEventRecord(e0, stream), "hipEventRecord");
-        if (rbrt_hip_tonemap(dev, stream, d_src, n_pixels, &t, ws, nullptr, d_rgb) != RBRT_OK && err.empty()) err = rbrt_hip_last_error();
-        ok(hipEventRecord(e1, stream), "hipEventRecord");
-        ok(hipMemcpyAsync(chosen, static_cast<const char*>(ws) + RBRT_TONEMAP_RESULT_OFFSET, sizeof(*chosen), hipMemcpyDeviceToHost, stream),
-           "download of the tonemap result");
-        ok(hipMemcpyAsync(host_rgb, d_rgb, n_pixels * 3, hipMemcpyDeviceToHost, stream), "download of the transformed image");
-        ok(hipStreamSynchronize(stream), "tonemap");
-        if (err.empty()) ok(hipEventElapsedTime(ms, e0, e1), "hipEventElapsedTime");
-    }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (ws) (void)hipFree(ws);
-    return err;
-}
-
 // The glare stage's options of a render (rbrt_hip.h "Glare").
 rbrt_glare_opts_t glare_opts_of(const RenderConfig& cfg) {
     rbrt_glare_opts_t g;
@@ -198,44 +136,648 @@ rbrt_glare_opts_t glare_opts_of(const RenderConfig& cfg) {
     return g;
 }
 
-// What stands between the complete image's radiance d_src (w x h pixels in memory of `dev`) and the 8-bit image, on `stream`:
-// the glare stage, where the render has one, then the display transform, where it has one (`t`: its options). The last of the
-// two writes the quantised result, which goes through d_rgb to host_rgb; with both, the glared radiance passes through a
-// buffer of this call's own. *chosen and *tonemap_ms are run_tonemap's; *glare_ms is rbrt_hip_glare between two events.
-// Returns the error, or an empty string.
-std::string run_display(const RenderConfig& cfg, int dev, hipStream_t stream, const float* d_src, uint32_t w, uint32_t h,
-                        const rbrt_tonemap_opts_t& t, uint8_t* d_rgb, uint8_t* host_rgb, rbrt_tonemap_result_t* chosen, float* tonemap_ms,
-                        float* glare_ms) {
-    std::string err;
-    const auto ok = [&](hipError_t e, const char* what) {
-        if (e != hipSuccess && err.empty()) err = std::string(what) + ": " + hipGetErrorString(e);
-        return e == hipSuccess;
-    };
-    const size_t n_pixels = size_t(w) * h;
-    float* d_glared = nullptr;
-    if (cfg.glare) {
-        const rbrt_glare_opts_t g = glare_opts_of(cfg);
-        void* ws = nullptr;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (ok(hipSetDevice(dev), "hipSetDevice") &&
-            ok(hipMalloc(&ws, rbrt_hip_glare_workspace_bytes(w, h, g.levels)), "hipMalloc(glare workspace)") &&
-            (!cfg.tonemap || ok(hipMalloc(reinterpret_cast<void**>(&d_glared), n_pixels * 3 * sizeof(float)), "hipMalloc(glared radiance)")) &&
-            ok(hipEventCreate(&e0), "hipEventCreate") && ok(hipEventCreate(&e1), "hipEventCreate")) {
-            ok(hipEventRecord(e0, stream), "hipEventRecord");
-            if (rbrt_hip_glare(dev, stream, d_src, w, h, &g, ws, d_glared, cfg.tonemap ? nullptr : d_rgb) != RBRT_OK && err.empty())
-                err = rbrt_hip_last_error();
-            ok(hipEventRecord(e1, stream), "hipEventRecord");
-            if (!cfg.tonemap) ok(hipMemcpyAsync(host_rgb, d_rgb, n_pixels * 3, hipMemcpyDeviceToHost, stream), "download of the glared image");
-            ok(hipStreamSynchronize(stream), "glare");
-            if (err.empty()) ok(hipEventElapsedTime(glare_ms, e0, e1), "hipEventElapsedTime");
-        }
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        if (ws) (void)hipFree(ws);
+// ---- the owners: what is created here ends with its owner, by reset() where the moment matters, else with the scope ---------
+// The first error of a sequence of calls; later ones are dropped. `count`, where given, is raised once, with that first error.
+class FirstError {
+  public:
+    explicit FirstError(std::atomic<int>* count = nullptr) : count_(count) {}
+    void set(const std::string& m) {
+        if (failed_) return;
+        failed_ = true;
+        msg_ = m.empty() ? "unknown error" : m;
+        if (count_) count_->fetch_add(1);
     }
-    if (err.empty() && cfg.tonemap) err = run_tonemap(dev, stream, d_glared ? d_glared : d_src, n_pixels, t, d_rgb, host_rgb, chosen, tonemap_ms);
-    if (d_glared) (void)hipFree(d_glared);
-    return err;
+    bool ok(hipError_t e, const char* what) {
+        if (e != hipSuccess) set(std::string(what) + ": " + hipGetErrorString(e));
+        return e == hipSuccess;
+    }
+    bool lib_ok(int rbrt_status) {  // of a call into the HIP library, which keeps its own message (rbrt_hip_last_error)
+        if (rbrt_status != RBRT_OK) set(rbrt_hip_last_error());
+        return rbrt_status == RBRT_OK;
+    }
+    bool failed() const { return failed_; }
+    const std::string& message() const { return msg_; }
+
+  private:
+    std::atomic<int>* count_;
+    bool failed_ = false;
+    std::string msg_;
+};
+
+class DeviceBuffer {  // move-only device memory: hipMalloc on request, hipFree at reset() or at the end of its life
+  public:
+    DeviceBuffer() = default;
+    DeviceBuffer(DeviceBuffer&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    DeviceBuffer& operator=(DeviceBuffer&& o) noexcept {
+        if (this != &o) reset(), p_ = o.p_, o.p_ = nullptr;
+        return *this;
+    }
+    ~DeviceBuffer() { reset(); }
+    bool alloc(size_t bytes, FirstError& err, const char* what) {
+        reset();
+        if (!err.ok(hipMalloc(&p_, bytes), what)) p_ = nullptr;
+        return p_ != nullptr;
+    }
+    void reset() {
+        if (p_) (void)hipFree(p_);
+        p_ = nullptr;
+    }
+    explicit operator bool() const { return p_ != nullptr; }
+    template <class T>
+    T* as() const { return static_cast<T*>(p_); }
+
+  private:
+    void* p_ = nullptr;
+};
+
+class EventTimer {  // two events around one call on a stream: create, start, the call, stop, the caller's synchronise, elapsed
+  public:
+    EventTimer() = default;
+    EventTimer(const EventTimer&) = delete;
+    EventTimer& operator=(const EventTimer&) = delete;
+    ~EventTimer() {
+        if (e0_) (void)hipEventDestroy(e0_);
+        if (e1_) (void)hipEventDestroy(e1_);
+    }
+    bool create(FirstError& err) { return err.ok(hipEventCreate(&e0_), "hipEventCreate") && err.ok(hipEventCreate(&e1_), "hipEventCreate"); }
+    void start(hipStream_t s, FirstError& err) { err.ok(hipEventRecord(e0_, s), "hipEventRecord"); }
+    void stop(hipStream_t s, FirstError& err) { err.ok(hipEventRecord(e1_, s), "hipEventRecord"); }
+    bool elapsed(float* ms, FirstError& err) {  // only of a sequence without an error
+        return !err.failed() && err.ok(hipEventElapsedTime(ms, e0_, e1_), "hipEventElapsedTime");
+    }
+
+  private:
+    hipEvent_t e0_ = nullptr, e1_ = nullptr;
+};
+
+class Stream {  // a rank's non-blocking stream: destroyed at reset() or at the end of its life
+  public:
+    Stream() = default;
+    Stream(const Stream&) = delete;
+    Stream& operator=(const Stream&) = delete;
+    ~Stream() { reset(); }
+    bool create(FirstError& err) { return err.ok(hipStreamCreateWithFlags(&s_, hipStreamNonBlocking), "hipStreamCreate"); }
+    void reset() {
+        if (s_) (void)hipStreamDestroy(s_);
+        s_ = nullptr;
+    }
+    hipStream_t get() const { return s_; }
+
+  private:
+    hipStream_t s_ = nullptr;
+};
+
+// ---- display: glare, then the display transform, of one complete image -------------------------------------------------------
+struct DisplaySite {  // where: the device and stream, the image's size, 8-bit staging memory of that device for one image
+    int dev;
+    hipStream_t stream;
+    uint32_t w, h;
+    uint8_t* d_rgb8;
+};
+struct DisplayStats {
+    rbrt_tonemap_result_t chosen{};  // what rbrt_hip_tonemap chose
+    float tonemap_ms = 0.0f, glare_ms = 0.0f;  // each call between two events
+};
+
+// rbrt_hip_glare on d_src. The stage that ends the chain writes the 8-bit image: without a display transform that is this one,
+// through site.d_rgb8 to host_rgb; with one, the glared radiance goes to *d_glared, memory of this call's making.
+void glare_stage(const RenderConfig& cfg, const DisplaySite& site, const float* d_src, DeviceBuffer* d_glared, uint8_t* host_rgb, float* ms,
+                 FirstError& err) {
+    const rbrt_glare_opts_t g = glare_opts_of(cfg);
+    const size_t n_pixels = size_t(site.w) * site.h;
+    DeviceBuffer ws;
+    EventTimer timer;
+    if (!(err.ok(hipSetDevice(site.dev), "hipSetDevice") &&
+          ws.alloc(rbrt_hip_glare_workspace_bytes(site.w, site.h, g.levels), err, "hipMalloc(glare workspace)") &&
+          (!cfg.tonemap || d_glared->alloc(n_pixels * 3 * sizeof(float), err, "hipMalloc(glared radiance)")) && timer.create(err)))
+        return;
+    timer.start(site.stream, err);
+    err.lib_ok(rbrt_hip_glare(site.dev, site.stream, d_src, site.w, site.h, &g, ws.as<void>(), d_glared->as<float>(), cfg.tonemap ? nullptr : site.d_rgb8));
+    timer.stop(site.stream, err);
+    if (!cfg.tonemap) err.ok(hipMemcpyAsync(host_rgb, site.d_rgb8, n_pixels * 3, hipMemcpyDeviceToHost, site.stream), "download of the glared image");
+    err.ok(hipStreamSynchronize(site.stream), "glare");
+    timer.elapsed(ms, err);
+}
+
+// rbrt_hip_tonemap on d_src with the options `t`: the quantised result through site.d_rgb8 to host_rgb, what the call chose
+// and its time to *st.
+void tonemap_stage(const DisplaySite& site, const float* d_src, const rbrt_tonemap_opts_t& t, uint8_t* host_rgb, DisplayStats* st, FirstError& err) {
+    const size_t n_pixels = size_t(site.w) * site.h;
+    DeviceBuffer ws;
+    EventTimer timer;
+    if (!(err.ok(hipSetDevice(site.dev), "hipSetDevice") && ws.alloc(RBRT_TONEMAP_WORKSPACE_BYTES, err, "hipMalloc(tonemap workspace)") &&
+          timer.create(err)))
+        return;
+    timer.start(site.stream, err);
+    err.lib_ok(rbrt_hip_tonemap(site.dev, site.stream, d_src, n_pixels, &t, ws.as<void>(), nullptr, site.d_rgb8));
+    timer.stop(site.stream, err);
+    err.ok(hipMemcpyAsync(&st->chosen, ws.as<char>() + RBRT_TONEMAP_RESULT_OFFSET, sizeof(st->chosen), hipMemcpyDeviceToHost, site.stream),
+           "download of the tonemap result");
+    err.ok(hipMemcpyAsync(host_rgb, site.d_rgb8, n_pixels * 3, hipMemcpyDeviceToHost, site.stream), "download of the transformed image");
+    err.ok(hipStreamSynchronize(site.stream), "tonemap");
+    timer.elapsed(&st->tonemap_ms, err);
+}
+
+// What stands between the complete image's radiance d_src and its 8-bit image in host_rgb: the glare stage, where the render
+// has one, then the display transform, where it has one. `err` must come in clean.
+void display_one(const RenderConfig& cfg, const DisplaySite& site, const float* d_src, const rbrt_tonemap_opts_t& t, uint8_t* host_rgb,
+                 DisplayStats* st, FirstError& err) {
+    DeviceBuffer d_glared;
+    if (cfg.glare) glare_stage(cfg, site, d_src, &d_glared, host_rgb, &st->glare_ms, err);
+    if (!err.failed() && cfg.tonemap) tonemap_stage(site, d_glared ? d_glared.as<float>() : d_src, t, host_rgb, st, err);
+}
+
+// The target image, then the unfiltered image where one is kept (d_noisy: its radiance, else null): img.rgb becomes the
+// quantisation of the result (img.radiance stays linear and without glare); the unfiltered image goes through the same glare
+// options and, as manual values, the exposure and white chosen for the target. The report's display figures are the target's.
+void display(const RenderConfig& cfg, const DisplaySite& site, const float* d_src, const float* d_noisy, ImageBuffer& img, RenderReport& rep,
+             FirstError& err) {
+    DisplayStats st;
+    display_one(cfg, site, d_src, tonemap_opts_of(cfg), img.rgb.data(), &st, err);
+    if (err.failed()) return;
+    if (cfg.tonemap) {
+        rep.tonemap_exposure = st.chosen.exposure, rep.tonemap_white = st.chosen.white, rep.luminance_counted = st.chosen.counted;
+        rep.tonemap_ms = st.tonemap_ms;
+    }
+    rep.glare_ms = st.glare_ms;
+    if (!d_noisy) return;
+    rbrt_tonemap_opts_t t = tonemap_opts_of(cfg);
+    t.exposure = st.chosen.exposure, t.white = st.chosen.white;
+    DisplayStats unreported;
+    display_one(cfg, site, d_noisy, t, img.noisy_rgb.data(), &unreported, err);
+}
+
+// ---- the plan: everything decided before a rank starts -----------------------------------------------------------------------
+struct Plan {
+    int n_dev = 0, world = 1;
+    bool oversubscribe = false;
+    double hip_start_s = 0.0;  // what the process's first HIP call took
+    uint32_t pass_spp = 0, ckpt_every = 1;
+    int stop_after = 0;  // test hook: give up after this many passes of THIS run (as an interrupted run would), checkpoint left on disk
+    // --gather rccl is a request, not a condition: whatever keeps RCCL from doing the gather -- the library is not there, two
+    // ranks share a device, the communicators do not come up, the exchange itself fails -- sends the ranks to the host gather
+    // in the same process (their tiles are still in their own memories), and the run says so on stderr and in --report.
+    // `rccl_note` is the reason, once there is one.
+    bool want_rccl = false;
+    std::string rccl_note;
+    int device_of(int rank) const { return oversubscribe ? rank % n_dev : rank; }
+};
+
+// Refuses what cannot be rendered, in this order, and starts the HIP runtime: nothing that calls HIP may exist before this.
+// adaptive_by: the option that sent the render down the adaptive path, for the messages.
+Plan make_plan(const RenderConfig& cfg, const std::string& adaptive_by, const Camera& cam, const Scene& scene, uint32_t num_samples) {
+    if (num_samples == 0) throw Error("the number of samples must be at least 1");
+    if (cfg.adaptive) {  // (one blocking call of one GPU: rbrt_hip.h "Adaptive sampling")
+        if (cfg.n_gpus > 1) throw Error(adaptive_by + " cannot be combined with --gpus > 1");
+        if (!cfg.checkpoint_path.empty()) throw Error(adaptive_by + " cannot be combined with --checkpoint");
+        if (cfg.pass_spp != 0) throw Error(adaptive_by + " cannot be combined with --pass-samples");
+    }
+    if (cfg.denoise && num_samples < 2) throw Error("--denoise needs at least 2 samples (each half image needs one)");
+    Plan p;
+    const auto t_hip0 = std::chrono::steady_clock::now();
+    p.n_dev = rbrt_hip_device_count();  // (the process's first HIP call: the runtime starts here)
+    p.hip_start_s = seconds_since(t_hip0);
+    if (p.n_dev < 1) throw Error(std::string("no HIP device: ") + rbrt_hip_last_error());
+    p.world = cfg.n_gpus < 1 ? 1 : cfg.n_gpus;
+    p.oversubscribe = cfg.oversubscribe;
+    if (p.world > p.n_dev && !cfg.oversubscribe)
+        throw Error("requested " + std::to_string(p.world) + " GPUs, " + std::to_string(p.n_dev) + " present");
+    p.want_rccl = p.world > 1 && cfg.gather == "rccl";
+    if (p.want_rccl && p.world > p.n_dev) {
+        p.rccl_note = "--gather rccl needs one GPU per rank (RCCL cannot put two ranks on one device)";
+        p.want_rccl = false;
+    }
+    // samples per pass: what was asked for, else passes of about 2^31 path samples each (a second or so of one GPU's
+    // share), so that long renders report progress and can checkpoint; a short render is one pass
+    p.pass_spp = cfg.pass_spp;
+    if (p.pass_spp == 0) {
+        const uint64_t per_spp = uint64_t(cam.img_width_pix) * cam.img_height_pix / uint64_t(p.world) + 1u;
+        p.pass_spp = uint32_t(std::min<uint64_t>(num_samples, std::max<uint64_t>(1, (1ull << 31) / per_spp)));
+    }
+    p.ckpt_every = cfg.checkpoint_every < 1 ? 1u : uint32_t(cfg.checkpoint_every);
+    if (const char* e = std::getenv("RBRT_TEST_STOP_AFTER_PASS")) p.stop_after = std::atoi(e);
+    if (scene.environment.n != 0u && cfg.constant_background)
+        throw Error("--background cannot be combined with an environment (the environment is the background)");
+    if (cam.thin_lens && !(rbrt_hip_supported_flags() & RBRT_FLAG_THIN_LENS)) throw Error("the HIP library does not support a thin lens");
+    return p;
+}
+
+rbrt_render_opts_t render_opts_of(const RenderConfig& cfg, const Camera& cam, uint32_t num_samples) {
+    rbrt_render_opts_t opts;
+    rbrt_render_opts_default(&opts);
+    opts.spp = num_samples;
+    opts.seed = cfg.seed;
+    if (cfg.constant_background) {
+        opts.flags |= RBRT_FLAG_CONSTANT_BACKGROUND;
+        for (int c = 0; c < 3; ++c) opts.bg[c] = cfg.background[c];
+    }
+    if (cam.thin_lens) opts.flags |= RBRT_FLAG_THIN_LENS;
+    return opts;
+}
+
+// ---- what the ranks share -----------------------------------------------------------------------------------------------------
+// What every rank reads and none changes, but for `img`, where the ranks write disjoint pixels.
+struct Job {
+    const RenderConfig& cfg;
+    const Plan& plan;
+    const rbrt_camera_lens_t& lens;  // (every call gets &lens.cam, the camera inside its lens: with RBRT_FLAG_THIN_LENS the library reads the lens past it)
+    const Scene::AbiView& view;
+    const rbrt_environment_t* env;  // null: none
+    rbrt_render_opts_t opts;
+    uint32_t num_samples;
+    CheckpointHeader want;
+    CheckpointRead resume;
+    ImageBuffer& img;
+    size_t n() const { return size_t(img.width) * img.height * 3; }  // values of the complete image
+    size_t rank_pixels(int rank) const {  // the pixels a rank renders: its packed tiles, or the image as it is
+        return plan.world > 1 ? rbrt_hip_packed_pixels(img.width, img.height, uint32_t(rank), uint32_t(plan.world)) : size_t(img.width) * img.height;
+    }
+    // A rank's running sums (rbrt_hip_render_pass's d_accum, a checkpoint's share): ALWAYS its packed tiles, one rank included,
+    // which is more than the image where its last tiles are ragged.
+    size_t sum_floats(int rank) const { return rbrt_hip_packed_pixels(img.width, img.height, uint32_t(rank), uint32_t(plan.world)) * 3; }
+};
+
+// Errors: a rank records its first failure in its own FirstError, which raises n_failed. Ranks never have to agree on
+// whether to go on rendering (a failed rank keeps meeting the barriers, idle); they DO have to agree on entering the RCCL
+// group, and that decision is read between two barriers, when nobody can be failing.
+struct Shared {
+    explicit Shared(const Plan& plan)
+        : errors(plan.world, FirstError(&n_failed)), barrier(plan.world), ckpt_acc(plan.world), comms(plan.world, nullptr), use_rccl(plan.want_rccl),
+          rccl_note(plan.rccl_note), t_setup(plan.world, 0.0), t_render(plan.world, 0.0), t_gather(plan.world, 0.0), t_release(plan.world, 0.0),
+          t_create(plan.world) {}
+    std::atomic<int> n_failed{0};
+    std::atomic<int> rccl_failed{0};  // ranks whose part of the RCCL exchange failed: not a failure of the run (host gather instead)
+    std::vector<FirstError> errors;   // [rank], each written by its rank alone and read after the ranks have joined
+    Barrier barrier;
+    std::vector<std::vector<float>> ckpt_acc;  // host copies of the running sums for the checkpoint writer
+    const RcclApi* rccl = nullptr;
+    std::vector<ncclComm_t> comms;
+    bool use_rccl;
+    std::mutex note_mutex;  // rccl_note, once the ranks run
+    std::string rccl_note;
+    DeviceBuffer d_slots;  // rank 0's, RCCL gather: world equal-size slots of packed tiles
+    RenderReport rep;
+    bool displayed = false;  // rank 0 has run glare and the display transform on its device (else, where either is wanted, they run after the host gather)
+    std::vector<double> t_setup, t_render, t_gather, t_release;
+    std::vector<rbrt_hip_call_times_t> t_create;
+};
+
+// The communicators of `--gather rccl` (one process, one communicator per GPU). Those that do not come up are aborted, the
+// note says why, and the run gathers through the host.
+void bring_up_rccl(const Plan& plan, Shared& sh) {
+    if (sh.use_rccl) {
+        try {
+            sh.rccl = &RcclApi::get();
+            std::vector<int> devs(plan.world);
+            for (int r = 0; r < plan.world; ++r) devs[r] = plan.device_of(r);
+            const ncclResult_t rc = sh.rccl->CommInitAll(sh.comms.data(), plan.world, devs.data());
+            if (rc != ncclSuccess) sh.rccl_note = std::string("ncclCommInitAll: ") + sh.rccl->GetErrorString(rc);
+        } catch (const Error& e) {
+            sh.rccl_note = e.what();
+        }
+        if (!sh.rccl_note.empty()) {
+            for (ncclComm_t& cm : sh.comms) {
+                if (cm && sh.rccl) (void)sh.rccl->CommAbort(cm);
+                cm = nullptr;
+            }
+            sh.use_rccl = false;
+        }
+    }
+    if (!sh.rccl_note.empty()) std::fprintf(stderr, "warning: %s; gathering through host memory instead\n", sh.rccl_note.c_str());
+}
+
+// A rank's packed tiles into the row-major image and its quantisation (lib.rs:116-122 on the host): tile tl of the rank is
+// tile number tl * world + rank. Ranks write disjoint pixels.
+void merge_rank_tiles(const float* packed, size_t n_tiles, uint32_t rank, uint32_t world, uint32_t width, uint32_t height, float* radiance,
+                      uint8_t* rgb) {
+    const uint32_t tiles_x = (width + RBRT_TILE - 1) / RBRT_TILE;
+    for (size_t tl = 0; tl < n_tiles; ++tl) {
+        uint32_t ty, tx;
+        rbrt_hip_tile_xy(uint32_t(tl) * world + rank, tiles_x, &ty, &tx);
+        for (uint32_t p = 0; p < 64; ++p) {
+            const uint32_t row = ty * RBRT_TILE + p / 8, col = tx * RBRT_TILE + p % 8;
+            if (row >= height || col >= width) continue;
+            const size_t src = (tl * 64 + p) * 3, dst = (size_t(row) * width + col) * 3;
+            for (int k = 0; k < 3; ++k) {
+                const float v = packed[src + k];
+                radiance[dst + k] = v;
+                const float q = std::sqrt(v) * 256.0f;
+                rgb[dst + k] = !(q == q) || q <= 0.0f ? 0 : q >= 255.0f ? 255 : uint8_t(q);
+            }
+        }
+    }
+}
+
+// ---- one rank: a thread, a device, its tiles ----------------------------------------------------------------------------------
+// Every rank meets every barrier, failed or not: a failed rank skips the work between them, never a wait().
+struct Rank {
+    Rank(const Job& job_, Shared& sh_, int rank_)
+        : job(job_), sh(sh_), cfg(job_.cfg), img(job_.img), rank(rank_), world(job_.plan.world), dev(job_.plan.device_of(rank_)), o(job_.opts),
+          npix(job_.rank_pixels(rank_)), err(sh_.errors[rank_]) {
+        o.tile_rank = uint32_t(rank);
+        o.tile_world = uint32_t(world);
+    }
+    void run();
+    void setup();
+    void render_adaptive();
+    void denoise();
+    void render_passes();
+    void gather_single();
+    void gather_rccl();
+    void gather_host();
+    void display_here(const float* d_src);
+    void release();
+
+    const Job& job;
+    Shared& sh;
+    const RenderConfig& cfg;
+    ImageBuffer& img;
+    const int rank, world, dev;
+    rbrt_render_opts_t o;
+    const size_t npix;
+    FirstError& err;  // this rank's
+    uint32_t pass_no = 0;
+    rbrt_hip_scene_t* hs = nullptr;
+    Stream stream;
+    DeviceBuffer d_acc, d_rad, d_rgb, d_img;
+    DeviceBuffer d_noisy;  // a denoised, glared or transformed render that keeps the unfiltered image: that image's radiance
+};
+
+// The four timed regions of a rank; the display stages of a one-GPU render are inside the gather region.
+void Rank::run() {
+    const auto t_start = std::chrono::steady_clock::now();
+    setup();
+    sh.t_setup[rank] = seconds_since(t_start);
+    const auto t_passes = std::chrono::steady_clock::now();
+    if (cfg.adaptive) render_adaptive();
+    else render_passes();
+    if (rank == 0) sh.rep.passes = pass_no;
+    // the reference would have panicked on a NaN discriminant (sphere.rs:33): surface it
+    if (hs && !err.failed()) err.lib_ok(rbrt_hip_scene_check(hs));
+    sh.t_render[rank] = seconds_since(t_passes);
+    const auto t_g = std::chrono::steady_clock::now();
+    if (world == 1) gather_single();
+    else if (sh.use_rccl) gather_rccl();
+    else gather_host();
+    sh.t_gather[rank] = seconds_since(t_g);
+    const auto t_rel = std::chrono::steady_clock::now();
+    release();
+    sh.t_release[rank] = seconds_since(t_rel);
+}
+
+void Rank::setup() {
+    err.lib_ok(rbrt_hip_scene_create_shaded(&job.view.scene, job.view.shading_ptr(), dev, &hs));
+    std::memset(&sh.t_create[rank], 0, sizeof(sh.t_create[rank]));
+    if (!hs) return;
+    (void)rbrt_hip_scene_create_times(hs, &sh.t_create[rank]);
+    // (every pass is followed by a synchronisation here: only the sample batches INSIDE a pass overlap, on three lanes;
+    // the library's default of eight is for streams of frames)
+    (void)rbrt_hip_scene_set_pipeline(hs, 3);
+    if (job.env) err.lib_ok(rbrt_hip_scene_set_environment(hs, job.env));  // (every rank's handle)
+    rbrt_hip_scene_info_t info;
+    if (rank == 0 && rbrt_hip_scene_info(hs, &info) == RBRT_OK) {
+        sh.rep.bvh_nodes = info.n_nodes, sh.rep.bvh_triangles = info.n_triangles;
+        sh.rep.builder = info.n_meshes == 0 ? "none" : info.n_meshes_device_built == info.n_meshes ? "device" : info.n_meshes_device_built == 0 ? "host" : "mixed";
+    }
+    if (!npix) return;
+    err.ok(hipSetDevice(dev), "hipSetDevice");
+    stream.create(err);
+    d_acc.alloc(job.sum_floats(rank) * sizeof(float), err, "hipMalloc(sums)");
+    d_rad.alloc(npix * 3 * sizeof(float), err, "hipMalloc(radiance)");
+    if (world == 1) d_rgb.alloc(npix * 3, err, "hipMalloc(rgb8)");
+    if (rank == 0 && sh.use_rccl) {
+        sh.d_slots.alloc(size_t(world) * job.rank_pixels(0) * 3 * sizeof(float), err, "hipMalloc(slots)");
+        d_img.alloc(job.n() * sizeof(float), err, "hipMalloc(image)");
+        d_rgb.alloc(job.n(), err, "hipMalloc(rgb8)");
+    }
+    if (!err.failed() && job.resume.samples_done != 0)
+        err.ok(hipMemcpy(d_acc.as<float>(), job.resume.sums[rank].data(), job.sum_floats(rank) * sizeof(float), hipMemcpyHostToDevice), "upload of the checkpoint");
+}
+
+// One blocking call instead of the passes: the library's rounds are the passes (one rank: the plan refused anything else).
+// Then the sample map, and the denoise stage where the render has one.
+void Rank::render_adaptive() {
+    if (err.failed() || !npix) return;
+    const rbrt_adaptive_opts_t ao = {cfg.adaptive_threshold, cfg.adaptive_min_samples, cfg.adaptive_step, 0u};
+    rbrt_adaptive_result_t ar{};
+    const size_t n_tiles = npix_tiles(img.width, img.height);
+    std::vector<uint32_t> counts(n_tiles);
+    {
+        DeviceBuffer d_counts;
+        if (d_counts.alloc(n_tiles * sizeof(uint32_t), err, "hipMalloc(tile samples)") &&
+            err.lib_ok(rbrt_hip_render_adaptive(hs, &job.lens.cam, &o, &ao, stream.get(), d_rad.as<float>(), d_rgb.as<uint8_t>(), d_counts.as<uint32_t>(), nullptr, &ar)))
+            err.ok(hipMemcpy(counts.data(), d_counts.as<uint32_t>(), n_tiles * sizeof(uint32_t), hipMemcpyDeviceToHost), "download of the tile samples");
+    }
+    if (err.failed()) return;
+    RenderReport& rep = sh.rep;
+    rep.adaptive_rounds = ar.rounds, rep.adaptive_samples = ar.samples, rep.adaptive_samples_fixed = ar.samples_fixed;
+    rep.adaptive_active_tiles.resize(ar.rounds);
+    uint32_t n_rounds = 0;
+    (void)rbrt_hip_scene_adaptive_rounds(hs, rep.adaptive_active_tiles.data(), rep.adaptive_active_tiles.size(), &n_rounds);
+    pass_no = ar.rounds;
+    img.sample_map.assign(size_t(img.width) * img.height, 0);
+    const uint32_t tiles_x = (img.width + RBRT_TILE - 1) / RBRT_TILE;
+    for (uint32_t row = 0; row < img.height; ++row)
+        for (uint32_t col = 0; col < img.width; ++col) {
+            const uint32_t t = rbrt_hip_tile_number(row / RBRT_TILE, col / RBRT_TILE, tiles_x);
+            img.sample_map[size_t(row) * img.width + col] = uint8_t(uint64_t(counts[t]) * 255u / job.num_samples);
+        }
+    if (cfg.denoise) denoise();
+}
+
+// The filter works on the handle's sums and writes over the unfiltered image (kept first where it is wanted).
+void Rank::denoise() {
+    const size_t n = job.n();
+    if (cfg.keep_noisy) {
+        img.noisy_rgb.resize(n);
+        err.ok(hipMemcpy(img.noisy_rgb.data(), d_rgb.as<uint8_t>(), n, hipMemcpyDeviceToHost), "download of the unfiltered image");
+        if ((cfg.tonemap || cfg.glare) && d_noisy.alloc(n * sizeof(float), err, "hipMalloc(unfiltered radiance)"))
+            err.ok(hipMemcpy(d_noisy.as<float>(), d_rad.as<float>(), n * sizeof(float), hipMemcpyDeviceToDevice), "copy of the unfiltered radiance");
+    }
+    const rbrt_denoise_opts_t dn = {cfg.denoise_window_radius, cfg.denoise_patch_radius, cfg.denoise_strength, 0u};
+    EventTimer timer;
+    if (!timer.create(err)) return;
+    timer.start(stream.get(), err);
+    err.lib_ok(rbrt_hip_scene_denoise(hs, &dn, stream.get(), d_rad.as<float>(), d_rgb.as<uint8_t>(), nullptr, nullptr));
+    timer.stop(stream.get(), err);
+    float ms = 0.0f;
+    err.ok(hipStreamSynchronize(stream.get()), "denoise");
+    if (timer.elapsed(&ms, err)) sh.rep.denoise_ms = ms;
+}
+
+// The passes, from the checkpoint's sample on. The loop bounds are the same for every rank, so every rank meets every barrier.
+void Rank::render_passes() {
+    const uint32_t num_samples = job.num_samples, pass_spp = job.plan.pass_spp;
+    for (uint64_t b = job.resume.samples_done; b < num_samples; b += pass_spp, ++pass_no) {
+        const uint32_t e = uint32_t(std::min<uint64_t>(num_samples, b + pass_spp));
+        const bool last = e == num_samples;
+        if (!err.failed() && npix &&
+            err.lib_ok(rbrt_hip_render_pass(hs, &job.lens.cam, &o, stream.get(), uint32_t(b), e, d_acc.as<float>(), last ? d_rad.as<float>() : nullptr,
+                                        last && world == 1 ? d_rgb.as<uint8_t>() : nullptr)))
+            err.ok(hipStreamSynchronize(stream.get()), "render pass");
+        const bool ckpt_now = !cfg.checkpoint_path.empty() && !last && (pass_no + 1) % job.plan.ckpt_every == 0;
+        if (ckpt_now && !err.failed() && npix) {
+            sh.ckpt_acc[rank].resize(job.sum_floats(rank));
+            err.ok(hipMemcpy(sh.ckpt_acc[rank].data(), d_acc.as<float>(), job.sum_floats(rank) * sizeof(float), hipMemcpyDeviceToHost), "download of the running sums");
+        }
+        if (world > 1 && (ckpt_now || !cfg.quiet)) sh.barrier.wait();  // every rank has finished the pass
+        if (rank == 0) {
+            if (!cfg.quiet) {  // lib.rs:105-110
+                std::printf("\rRendering %.1f%% complete!", double(e) / double(num_samples) * 100.0);
+                std::fflush(stdout);
+            }
+            // (between the two barriers of a checkpointing pass no other rank is running: the counter is stable)
+            if (ckpt_now && sh.n_failed.load() == 0) {
+                if (!write_checkpoint(cfg.checkpoint_path, job.want, e, sh.ckpt_acc)) err.set("cannot write checkpoint " + cfg.checkpoint_path);
+                if (!err.failed()) ++sh.rep.checkpoints_written;
+            }
+        }
+        if (world > 1 && ckpt_now) sh.barrier.wait();  // the sums may change again only after they are on disk
+        if (job.plan.stop_after > 0 && int(pass_no) + 1 == job.plan.stop_after && !last)
+            err.set("stopped after pass " + std::to_string(job.plan.stop_after) + " (RBRT_TEST_STOP_AFTER_PASS)");
+    }
+}
+
+// Glare and the display transform on this rank's device, of the complete image that is d_src there.
+void Rank::display_here(const float* d_src) {
+    if (!(cfg.tonemap || cfg.glare) || err.failed()) return;
+    display(cfg, DisplaySite{dev, stream.get(), img.width, img.height, d_rgb.as<uint8_t>()}, d_src, d_noisy.as<float>(), img, sh.rep, err);
+    sh.displayed = true;
+}
+
+void Rank::gather_single() {
+    if (err.failed() || !npix) return;
+    err.ok(hipMemcpy(img.radiance.data(), d_rad.as<float>(), job.n() * sizeof(float), hipMemcpyDeviceToHost), "download");
+    err.ok(hipMemcpy(img.rgb.data(), d_rgb.as<uint8_t>(), job.n(), hipMemcpyDeviceToHost), "download");
+    display_here(d_rad.as<float>());  // on the radiance that is here already
+}
+
+// --gather host: every rank's tiles over its own PCIe link, merged on the host (also where a failed RCCL gather ends).
+void Rank::gather_host() {
+    if (err.failed() || !npix) return;
+    std::vector<float> hr(npix * 3);
+    if (err.ok(hipMemcpy(hr.data(), d_rad.as<float>(), hr.size() * sizeof(float), hipMemcpyDeviceToHost), "download"))
+        merge_rank_tiles(hr.data(), npix / 64, uint32_t(rank), uint32_t(world), img.width, img.height, img.radiance.data(), img.rgb.data());
+}
+
+// --gather rccl: one grouped exchange, rank r > 0 sends its packed tiles, rank 0 receives each into that rank's slot,
+// de-interleaves and downloads the image.
+void Rank::gather_rccl() {
+    const RcclApi* rccl = sh.rccl;
+    float* d_slots = sh.d_slots.as<float>();
+    const size_t slot_pixels = job.rank_pixels(0);
+    // INVARIANT all enter the group or none: the decision is taken ONCE, between two barriers. Before the first every rank
+    // has recorded what it had to record, and until the second nobody runs code that can fail.
+    sh.barrier.wait();
+    const bool go = sh.n_failed.load() == 0;
+    sh.barrier.wait();
+    if (!go) return;
+    bool copied = true;
+    if (rank == 0) copied = err.ok(hipMemcpyAsync(d_slots, d_rad.as<float>(), npix * 3 * sizeof(float), hipMemcpyDeviceToDevice, stream.get()), "own tiles");
+    // INVARIANT every GroupStart has its GroupEnd, whatever the calls between them return: a rank that left the bracket
+    // open would block the others' GroupEnd.
+    ncclResult_t rc = rccl->GroupStart();
+    if (rank == 0) {
+        for (int r = 1; r < world && rc == ncclSuccess; ++r) {
+            const size_t cnt = job.rank_pixels(r) * 3;
+            if (cnt) rc = rccl->Recv(d_slots + size_t(r) * slot_pixels * 3, cnt, ncclFloat, r, sh.comms[0], stream.get());
+        }
+    } else if (npix && rc == ncclSuccess) {
+        rc = rccl->Send(d_rad.as<float>(), npix * 3, ncclFloat, 0, sh.comms[rank], stream.get());
+    }
+    const ncclResult_t rc2 = rccl->GroupEnd();
+    bool rccl_bad = false;  // this rank's part of the exchange failed: not an error of the run, the host gather takes over
+    auto rccl_fail = [&](const std::string& m) {
+        rccl_bad = true;
+        std::lock_guard<std::mutex> lk(sh.note_mutex);
+        if (sh.rccl_note.empty()) sh.rccl_note = m;
+        sh.rccl_failed.fetch_add(1);
+    };
+    if (rc != ncclSuccess || rc2 != ncclSuccess) rccl_fail(std::string("RCCL gather: ") + rccl->GetErrorString(rc != ncclSuccess ? rc : rc2));
+    if (rank == 0 && !err.failed() && !rccl_bad && copied)
+        err.lib_ok(rbrt_hip_unpack_tiles_strided(dev, stream.get(), d_slots, img.width, img.height, uint32_t(world), slot_pixels, d_img.as<float>(), d_rgb.as<uint8_t>()));
+    // INVARIANT no rank waits for ever: if a peer failed inside the group (its send or receive was never enqueued) this
+    // rank's side can not complete; it polls, and then aborts its communicator instead of hanging.
+    for (;;) {
+        const hipError_t q = hipStreamQuery(stream.get());
+        if (q == hipSuccess) break;
+        if (q != hipErrorNotReady) {
+            err.ok(q, "gather");
+            break;
+        }
+        if (sh.n_failed.load() != 0 || sh.rccl_failed.load() != 0) {
+            if (!rccl_bad) rccl_fail("RCCL gather abandoned: another rank's part of it failed");
+            (void)rccl->CommAbort(sh.comms[rank]);
+            sh.comms[rank] = nullptr;
+            break;
+        }
+        std::this_thread::sleep_for(std::chrono::microseconds(50));
+    }
+    // INVARIANT all fall back or none: did the exchange work for everyone is again one decision between two barriers. If
+    // not, the tiles are still where they were rendered: every rank takes the host path, in this same process.
+    sh.barrier.wait();
+    const bool fell_back = sh.rccl_failed.load() != 0;
+    sh.barrier.wait();
+    if (fell_back) return gather_host();
+    if (rank != 0 || err.failed()) return;
+    err.ok(hipMemcpy(img.radiance.data(), d_img.as<float>(), job.n() * sizeof(float), hipMemcpyDeviceToHost), "download");
+    err.ok(hipMemcpy(img.rgb.data(), d_rgb.as<uint8_t>(), job.n(), hipMemcpyDeviceToHost), "download");
+    display_here(d_img.as<float>());  // on the gathered image
+}
+
+// The lifetimes end here, in this order, inside the release region: nothing is left to fall off the end of the thread.
+void Rank::release() {
+    d_acc.reset();
+    d_rad.reset();
+    d_rgb.reset();
+    d_img.reset();
+    d_noisy.reset();
+    if (rank == 0) sh.d_slots.reset();
+    stream.reset();
+    rbrt_hip_scene_destroy(hs);
+    hs = nullptr;
+}
+
+// ---- the steps of render_scene that are not a rank's --------------------------------------------------------------------------
+CheckpointRead resume_from_checkpoint(const Job& job) {
+    const std::string& path = job.cfg.checkpoint_path;
+    if (path.empty()) return CheckpointRead();
+    std::vector<size_t> counts(job.plan.world);
+    for (int r = 0; r < job.plan.world; ++r) counts[r] = job.sum_floats(r);
+    CheckpointRead res = read_checkpoint(path, job.want, counts);
+    if (res.found && !job.cfg.quiet) {
+        if (res.samples_done != 0)
+            std::printf("Resuming from checkpoint %s at sample %u of %u\n", path.c_str(), res.samples_done, job.num_samples);
+        else
+            std::printf("Checkpoint %s does not match this render (scene, size, samples, seed or GPU count): starting over\n", path.c_str());
+    }
+    return res;
+}
+
+// The ranks' tiles were merged on the host: the complete image goes up to rank 0's device once, so that the target file
+// does not depend on how many GPUs rendered it or on how their tiles were gathered. On the null stream.
+void display_after_host_gather(const Job& job, RenderReport& rep) {
+    const int dev = job.plan.device_of(0);
+    FirstError err;
+    DeviceBuffer d_src, d_out8;
+    if (err.ok(hipSetDevice(dev), "hipSetDevice") && d_src.alloc(job.n() * sizeof(float), err, "hipMalloc(image)") &&
+        d_out8.alloc(job.n(), err, "hipMalloc(rgb8)") &&
+        err.ok(hipMemcpy(d_src.as<float>(), job.img.radiance.data(), job.n() * sizeof(float), hipMemcpyHostToDevice), "upload of the gathered image"))
+        display(job.cfg, DisplaySite{dev, nullptr, job.img.width, job.img.height, d_out8.as<uint8_t>()}, d_src.as<float>(), nullptr, job.img, rep, err);
+    if (err.failed()) throw Error("GPU " + std::to_string(dev) + ": " + err.message());
+}
+
+// The report's times: each region is its slowest rank's; the set-up is split into the parts of ONE rank, so that they add up.
+void report_times(const Plan& plan, const Shared& sh, RenderReport& rep) {
+    const size_t slow = size_t(std::max_element(sh.t_setup.begin(), sh.t_setup.end()) - sh.t_setup.begin());
+    const rbrt_hip_call_times_t& ct = sh.t_create[slow];
+    rep.upload_build_s = sh.t_setup[slow];
+    rep.hip_init_s = plan.hip_start_s + ct.hip_init_s, rep.upload_s = ct.upload_s, rep.bvh_build_s = ct.bvh_build_s;
+    rep.lanes_s = ct.lanes_s + std::max(0.0, ct.create_s - ct.hip_init_s - ct.upload_s - ct.bvh_build_s - ct.lanes_s);
+    rep.buffers_s = std::max(0.0, sh.t_setup[slow] - ct.create_s);
+    rep.release_s = *std::max_element(sh.t_release.begin(), sh.t_release.end());
+    rep.render_s = *std::max_element(sh.t_render.begin(), sh.t_render.end());
+    rep.gather_s = *std::max_element(sh.t_gather.begin(), sh.t_gather.end());
 }
 
 }  // namespace
@@ -245,499 +787,51 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
     if (cfg.denoise && !cfg.adaptive)  // (the filter's input is the adaptive path's sums: one round that stops nothing)
         cfg.adaptive = true, cfg.adaptive_threshold = 0.0f, cfg.adaptive_min_samples = cfg.adaptive_step = std::max(num_samples, 2u);
     if (!cfg.quiet) std::printf("Starting rendering...\n");
-    // (every rank's calls get &c, the camera inside its lens: with RBRT_FLAG_THIN_LENS the library reads the lens past it)
-    const rbrt_camera_lens_t lens = cam.to_abi_lens();
-    const rbrt_camera_t& c = lens.cam;
-    const Scene::AbiView view = scene.to_abi();
-    rbrt_render_opts_t opts;
-    rbrt_render_opts_default(&opts);
-    opts.spp = num_samples;
-    opts.seed = cfg.seed;
-    if (cfg.constant_background) {
-        opts.flags |= RBRT_FLAG_CONSTANT_BACKGROUND;
-        for (int c = 0; c < 3; ++c) opts.bg[c] = cfg.background[c];
-    }
-
     ImageBuffer img;
     img.width = cam.img_width_pix;
     img.height = cam.img_height_pix;
-    const size_t n = size_t(img.width) * img.height * 3;
-    img.rgb.assign(n, 0);
-    img.radiance.assign(n, 0.0f);
-    if (num_samples == 0) throw Error("the number of samples must be at least 1");
-    if (cfg.adaptive) {  // (one blocking call of one GPU: rbrt_hip.h "Adaptive sampling")
-        const std::string who = cfg_in.adaptive ? "--adaptive" : "--denoise";
-        if (cfg.n_gpus > 1) throw Error(who + " cannot be combined with --gpus > 1");
-        if (!cfg.checkpoint_path.empty()) throw Error(who + " cannot be combined with --checkpoint");
-        if (cfg.pass_spp != 0) throw Error(who + " cannot be combined with --pass-samples");
-    }
-    if (cfg.denoise && num_samples < 2) throw Error("--denoise needs at least 2 samples (each half image needs one)");
+    img.rgb.assign(size_t(img.width) * img.height * 3, 0);
+    img.radiance.assign(img.rgb.size(), 0.0f);
 
-    const auto t_hip0 = std::chrono::steady_clock::now();
-    const int n_dev = rbrt_hip_device_count();  // (the process's first HIP call: the runtime starts here)
-    const double hip_start_s = seconds_since(t_hip0);
-    if (n_dev < 1) throw Error(std::string("no HIP device: ") + rbrt_hip_last_error());
-    const int world = cfg.n_gpus < 1 ? 1 : cfg.n_gpus;
-    if (world > n_dev && !cfg.oversubscribe)
-        throw Error("requested " + std::to_string(world) + " GPUs, " + std::to_string(n_dev) + " present");
-    const auto device_of = [&](int rank) { return cfg.oversubscribe ? rank % n_dev : rank; };
-    // --gather rccl is a request, not a condition: whatever keeps RCCL from doing the gather -- the library is not
-    // there, two ranks share a device, the communicators do not come up, the exchange itself fails -- sends the ranks
-    // to the host gather in the same process (their tiles are still in their own memories), and the run says so on
-    // stderr and in --report. `rccl_note` is the reason, once there is one.
-    bool use_rccl = world > 1 && cfg.gather == "rccl";
-    std::string rccl_note;
-    if (use_rccl && world > n_dev) {
-        rccl_note = "--gather rccl needs one GPU per rank (RCCL cannot put two ranks on one device)";
-        use_rccl = false;
-    }
-
-    // samples per pass: what was asked for, else passes of about 2^31 path samples each (a second or so of one GPU's
-    // share), so that long renders report progress and can checkpoint; a short render is one pass
-    uint32_t pass_spp = cfg.pass_spp;
-    if (pass_spp == 0) {
-        const uint64_t per_spp = uint64_t(img.width) * img.height / uint64_t(world) + 1u;
-        pass_spp = uint32_t(std::min<uint64_t>(num_samples, std::max<uint64_t>(1, (1ull << 31) / per_spp)));
-    }
-    const uint32_t ckpt_every = cfg.checkpoint_every < 1 ? 1u : uint32_t(cfg.checkpoint_every);
-    // test hook: give up after this many passes of THIS run (as an interrupted run would), checkpoint left on disk
-    int stop_after = 0;
-    if (const char* e = std::getenv("RBRT_TEST_STOP_AFTER_PASS")) stop_after = std::atoi(e);
-
-    // ---- resume ------------------------------------------------------------------------------------------------
-    CheckpointHeader want{};
-    std::memcpy(want.magic, "RBRTCKP1", 8);
-    want.width = img.width, want.height = img.height, want.spp = num_samples, want.world = uint32_t(world);
-    want.seed = cfg.seed;
-    want.fingerprint = cfg.checkpoint_path.empty() ? 0 : shading_fingerprint(view.scene, view.shading_ptr(), scene_fingerprint(c, view.scene));
-    if (want.fingerprint != 0 && cfg.constant_background) {  // (only then: a default run keeps its checkpoints' fingerprint)
-        want.fingerprint = fnv1a(&opts.flags, sizeof(opts.flags), want.fingerprint);
-        want.fingerprint = fnv1a(opts.bg, sizeof(opts.bg), want.fingerprint);
-    }
-    const bool has_env = scene.environment.n != 0u;
-    if (has_env && cfg.constant_background) throw Error("--background cannot be combined with an environment (the environment is the background)");
-    if (want.fingerprint != 0) want.fingerprint = environment_fingerprint(scene.environment, want.fingerprint);  // (unchanged without one)
+    // ---- plan, job, resume, communicators --------------------------------------------------------------------------------
+    const rbrt_camera_lens_t lens = cam.to_abi_lens();
+    const Scene::AbiView view = scene.to_abi();
     const rbrt_environment_t env_abi = scene.environment.to_abi();
-    if (cam.thin_lens) {  // (likewise: a pinhole run's checkpoints keep their fingerprint)
-        if (!(rbrt_hip_supported_flags() & RBRT_FLAG_THIN_LENS)) throw Error("the HIP library does not support a thin lens");
-        opts.flags |= RBRT_FLAG_THIN_LENS;
-        if (want.fingerprint != 0) {
-            const uint32_t bit = RBRT_FLAG_THIN_LENS;
-            want.fingerprint = fnv1a(&bit, sizeof(bit), want.fingerprint);
-            want.fingerprint = fnv1a(lens.lens_u, sizeof(lens.lens_u), want.fingerprint);
-            want.fingerprint = fnv1a(lens.lens_v, sizeof(lens.lens_v), want.fingerprint);
-            want.fingerprint = fnv1a(&lens.focus_scale, sizeof(lens.focus_scale), want.fingerprint);
-        }
-    }
-    uint32_t start_sample = 0;
-    std::vector<std::vector<float>> resume_acc(world);
-    if (!cfg.checkpoint_path.empty()) {
-        std::ifstream in(cfg.checkpoint_path, std::ios::binary);
-        CheckpointHeader h{};
-        if (in && in.read(reinterpret_cast<char*>(&h), sizeof(h))) {
-            const bool same = !std::memcmp(h.magic, want.magic, 8) && h.width == want.width && h.height == want.height &&
-                              h.spp == want.spp && h.world == want.world && h.seed == want.seed &&
-                              h.fingerprint == want.fingerprint && h.samples_done > 0 && h.samples_done < num_samples;
-            bool ok = same;
-            for (int r = 0; ok && r < world; ++r) {
-                uint64_t cnt = 0;
-                ok = bool(in.read(reinterpret_cast<char*>(&cnt), sizeof(cnt)));
-                const size_t expect = world > 1 ? rbrt_hip_packed_pixels(img.width, img.height, uint32_t(r), uint32_t(world)) * 3 : n;
-                ok = ok && cnt == expect;
-                if (ok) {
-                    resume_acc[r].resize(cnt);
-                    ok = bool(in.read(reinterpret_cast<char*>(resume_acc[r].data()), std::streamsize(cnt * sizeof(float))));
-                }
-            }
-            if (ok) {
-                start_sample = h.samples_done;
-                if (!cfg.quiet) std::printf("Resuming from checkpoint %s at sample %u of %u\n", cfg.checkpoint_path.c_str(), start_sample, num_samples);
-            } else {
-                for (auto& v : resume_acc) v.clear();
-                if (!cfg.quiet) std::printf("Checkpoint %s does not match this render (scene, size, samples, seed or GPU count): starting over\n",
-                                            cfg.checkpoint_path.c_str());
-            }
-        }
-    }
+    const Plan plan = make_plan(cfg, cfg_in.adaptive ? "--adaptive" : "--denoise", cam, scene, num_samples);
+    Job job{cfg, plan, lens, view, scene.environment.n != 0u ? &env_abi : nullptr, render_opts_of(cfg, cam, num_samples), num_samples, {}, {}, img};
+    job.want = checkpoint_header(img.width, img.height, num_samples, uint32_t(plan.world), cfg.seed,
+                                 checkpoint_fingerprint(cfg.checkpoint_path, lens, job.opts, view.scene, view.shading_ptr(), scene.environment));
+    job.resume = resume_from_checkpoint(job);
+    Shared sh(plan);
+    bring_up_rccl(plan, sh);
+    RenderReport& rep = sh.rep;
+    rep.n_gpus = plan.world;
+    rep.pass_spp = plan.pass_spp;
+    rep.gather = plan.world > 1 ? (sh.use_rccl ? "rccl" : "host") : "none";
+    if (!sh.rccl_note.empty()) rep.gather = "host (rccl was asked for: " + sh.rccl_note + ")";
 
-    // ---- RCCL communicators (one process, one communicator per GPU) -----------------------------------------------
-    const RcclApi* rccl = nullptr;
-    std::vector<ncclComm_t> comms(world, nullptr);
-    if (use_rccl) {
-        try {
-            rccl = &RcclApi::get();
-            std::vector<int> devs(world);
-            for (int r = 0; r < world; ++r) devs[r] = device_of(r);
-            const ncclResult_t rc = rccl->CommInitAll(comms.data(), world, devs.data());
-            if (rc != ncclSuccess) rccl_note = std::string("ncclCommInitAll: ") + rccl->GetErrorString(rc);
-        } catch (const Error& e) {
-            rccl_note = e.what();
-        }
-        if (!rccl_note.empty()) {
-            for (ncclComm_t& cm : comms) {
-                if (cm && rccl) (void)rccl->CommAbort(cm);
-                cm = nullptr;
-            }
-            use_rccl = false;
-        }
-    }
-    if (!rccl_note.empty()) std::fprintf(stderr, "warning: %s; gathering through host memory instead\n", rccl_note.c_str());
-
-    // Errors: a rank records its first failure under the mutex and raises the counter. Ranks never have to agree on
-    // whether to go on rendering (a failed rank keeps meeting the barriers, idle); they DO have to agree on entering
-    // the RCCL group, and that decision is read between two barriers, when nobody can be failing.
-    std::mutex err_mutex;
-    std::vector<std::string> errors(world);
-    std::atomic<int> n_failed{0};
-    std::atomic<int> rccl_failed{0};  // ranks whose part of the RCCL exchange failed: not a failure of the run (host gather instead)
-    std::vector<std::vector<float>> ckpt_acc(world);  // host copies of the running sums for the checkpoint writer
-    Barrier barrier(world);
-    float* d_slots = nullptr;  // rank 0, RCCL gather: world equal-size slots of packed tiles
-    const size_t slot_pixels = world > 1 ? rbrt_hip_packed_pixels(img.width, img.height, 0, uint32_t(world)) : 0;
-    RenderReport rep;
-    bool tonemapped = false;  // rank 0 has run glare and the display transform on its device (else, where either is wanted, they run after the host gather)
-    rep.n_gpus = world;
-    rep.pass_spp = pass_spp;
-    rep.gather = world > 1 ? (use_rccl ? "rccl" : "host") : "none";
-    if (!rccl_note.empty()) rep.gather = "host (rccl was asked for: " + rccl_note + ")";
-    std::vector<double> t_setup(world, 0.0), t_render(world, 0.0), t_gather(world, 0.0), t_release(world, 0.0);
-    std::vector<rbrt_hip_call_times_t> t_create(world);
-
-    auto worker = [&](int rank) {
-        rbrt_hip_scene_t* hs = nullptr;
-        float *d_acc = nullptr, *d_rad = nullptr, *d_img = nullptr;
-        float* d_noisy = nullptr;  // a denoised, glared or transformed render that keeps the unfiltered image: that image's radiance
-        uint8_t* d_rgb = nullptr;
-        hipStream_t stream = nullptr;
-        bool failed = false;  // this rank's own view: it has recorded an error
-        auto fail = [&](const std::string& m) {
-            if (failed) return;
-            failed = true;
-            {
-                std::lock_guard<std::mutex> lk(err_mutex);
-                errors[rank] = m.empty() ? "unknown error" : m;
-            }
-            n_failed.fetch_add(1);
-        };
-        auto hip_ok = [&](hipError_t e, const char* what) {
-            if (e != hipSuccess) fail(std::string(what) + ": " + hipGetErrorString(e));
-            return e == hipSuccess;
-        };
-        // Glare and the display transform of the complete image, which is d_src on this rank's device: img.rgb becomes the
-        // quantisation of the result (img.radiance stays linear and without glare), and the unfiltered image, where one is kept,
-        // goes through the same glare options and the same e and w.
-        auto display_transform = [&](int on_dev, hipStream_t on_stream, const float* d_src, uint8_t* d_out8) {
-            rbrt_tonemap_result_t chosen{};
-            float ms = 0.0f, glare_ms = 0.0f;
-            const std::string e = run_display(cfg, on_dev, on_stream, d_src, img.width, img.height, tonemap_opts_of(cfg), d_out8,
-                                              img.rgb.data(), &chosen, &ms, &glare_ms);
-            if (!e.empty()) return fail(e);
-            if (cfg.tonemap) {
-                rep.tonemap_exposure = chosen.exposure, rep.tonemap_white = chosen.white, rep.luminance_counted = chosen.counted;
-                rep.tonemap_ms = ms;
-            }
-            rep.glare_ms = glare_ms;
-            if (d_noisy) {  // a second pass: the same glare, and what was chosen for the target image as manual values
-                rbrt_tonemap_opts_t t = tonemap_opts_of(cfg);
-                t.exposure = chosen.exposure, t.white = chosen.white;
-                rbrt_tonemap_result_t again{};
-                const std::string e2 = run_display(cfg, on_dev, on_stream, d_noisy, img.width, img.height, t, d_out8, img.noisy_rgb.data(),
-                                                   &again, &ms, &glare_ms);
-                if (!e2.empty()) fail(e2);
-            }
-            tonemapped = true;
-        };
-        const auto t_start = std::chrono::steady_clock::now();
-        rbrt_render_opts_t o = opts;
-        o.tile_rank = uint32_t(rank);
-        o.tile_world = uint32_t(world);
-        const int dev = device_of(rank);
-        const size_t npix = world > 1 ? rbrt_hip_packed_pixels(img.width, img.height, o.tile_rank, o.tile_world)
-                                      : size_t(img.width) * img.height;
-        if (rbrt_hip_scene_create_shaded(&view.scene, view.shading_ptr(), dev, &hs) != RBRT_OK) fail(rbrt_hip_last_error());
-        std::memset(&t_create[rank], 0, sizeof(t_create[rank]));
-        if (hs) (void)rbrt_hip_scene_create_times(hs, &t_create[rank]);
-        // (every pass is followed by a synchronisation here: only the sample batches INSIDE a pass overlap, on three lanes;
-        // the library's default of eight is for streams of frames)
-        if (hs) (void)rbrt_hip_scene_set_pipeline(hs, 3);
-        if (hs && has_env && rbrt_hip_scene_set_environment(hs, &env_abi) != RBRT_OK) fail(rbrt_hip_last_error());  // (every rank's handle)
-        if (hs && rank == 0) {
-            rbrt_hip_scene_info_t info;
-            if (rbrt_hip_scene_info(hs, &info) == RBRT_OK) {
-                rep.bvh_nodes = info.n_nodes, rep.bvh_triangles = info.n_triangles;
-                rep.builder = info.n_meshes == 0 ? "none" : info.n_meshes_device_built == info.n_meshes ? "device" : info.n_meshes_device_built == 0 ? "host" : "mixed";
-            }
-        }
-        if (hs && npix) {
-            hip_ok(hipSetDevice(dev), "hipSetDevice");
-            hip_ok(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking), "hipStreamCreate");
-            hip_ok(hipMalloc(reinterpret_cast<void**>(&d_acc), npix * 3 * sizeof(float)), "hipMalloc(sums)");
-            hip_ok(hipMalloc(reinterpret_cast<void**>(&d_rad), npix * 3 * sizeof(float)), "hipMalloc(radiance)");
-            if (world == 1) hip_ok(hipMalloc(reinterpret_cast<void**>(&d_rgb), npix * 3), "hipMalloc(rgb8)");
-            if (rank == 0 && use_rccl) {
-                hip_ok(hipMalloc(reinterpret_cast<void**>(&d_slots), size_t(world) * slot_pixels * 3 * sizeof(float)), "hipMalloc(slots)");
-                hip_ok(hipMalloc(reinterpret_cast<void**>(&d_img), n * sizeof(float)), "hipMalloc(image)");
-                hip_ok(hipMalloc(reinterpret_cast<void**>(&d_rgb), n), "hipMalloc(rgb8)");
-            }
-            if (!failed && start_sample != 0)
-                hip_ok(hipMemcpy(d_acc, resume_acc[rank].data(), npix * 3 * sizeof(float), hipMemcpyHostToDevice), "upload of the checkpoint");
-        }
-        t_setup[rank] = seconds_since(t_start);
-        // ---- passes ---- (every rank meets every barrier, failed or not: the loop bounds are the same for all)
-        const auto t_passes = std::chrono::steady_clock::now();
-        uint32_t pass_no = 0;
-        if (cfg.adaptive && !failed && npix) {
-            // one blocking call instead of the passes: the library's rounds are the passes (world == 1: checked above)
-            const rbrt_adaptive_opts_t ao = {cfg.adaptive_threshold, cfg.adaptive_min_samples, cfg.adaptive_step, 0u};
-            rbrt_adaptive_result_t ar{};
-            const size_t n_tiles = npix_tiles(img.width, img.height);
-            uint32_t* d_counts = nullptr;
-            std::vector<uint32_t> counts(n_tiles);
-            if (hip_ok(hipMalloc(reinterpret_cast<void**>(&d_counts), n_tiles * sizeof(uint32_t)), "hipMalloc(tile samples)")) {
-                if (rbrt_hip_render_adaptive(hs, &c, &o, &ao, stream, d_rad, d_rgb, d_counts, nullptr, &ar) != RBRT_OK) fail(rbrt_hip_last_error());
-                else hip_ok(hipMemcpy(counts.data(), d_counts, n_tiles * sizeof(uint32_t), hipMemcpyDeviceToHost), "download of the tile samples");
-                (void)hipFree(d_counts);
-            }
-            if (!failed) {
-                rep.adaptive_rounds = ar.rounds, rep.adaptive_samples = ar.samples, rep.adaptive_samples_fixed = ar.samples_fixed;
-                rep.adaptive_active_tiles.resize(ar.rounds);
-                uint32_t n_rounds = 0;
-                (void)rbrt_hip_scene_adaptive_rounds(hs, rep.adaptive_active_tiles.data(), rep.adaptive_active_tiles.size(), &n_rounds);
-                pass_no = ar.rounds;
-                img.sample_map.assign(size_t(img.width) * img.height, 0);
-                const uint32_t tiles_x = (img.width + RBRT_TILE - 1) / RBRT_TILE;
-                for (uint32_t row = 0; row < img.height; ++row)
-                    for (uint32_t col = 0; col < img.width; ++col) {
-                        const uint32_t t = rbrt_hip_tile_number(row / RBRT_TILE, col / RBRT_TILE, tiles_x);
-                        img.sample_map[size_t(row) * img.width + col] = uint8_t(uint64_t(counts[t]) * 255u / num_samples);
-                    }
-            }
-            if (!failed && cfg.denoise) {
-                // the filter works on the handle's sums and writes over the unfiltered image (kept first where it is wanted)
-                if (cfg.keep_noisy) {
-                    img.noisy_rgb.resize(n);
-                    hip_ok(hipMemcpy(img.noisy_rgb.data(), d_rgb, n, hipMemcpyDeviceToHost), "download of the unfiltered image");
-                    if ((cfg.tonemap || cfg.glare) && hip_ok(hipMalloc(reinterpret_cast<void**>(&d_noisy), n * sizeof(float)), "hipMalloc(unfiltered radiance)"))
-                        hip_ok(hipMemcpy(d_noisy, d_rad, n * sizeof(float), hipMemcpyDeviceToDevice), "copy of the unfiltered radiance");
-                }
-                const rbrt_denoise_opts_t dn = {cfg.denoise_window_radius, cfg.denoise_patch_radius, cfg.denoise_strength, 0u};
-                hipEvent_t e0 = nullptr, e1 = nullptr;
-                if (hip_ok(hipEventCreate(&e0), "hipEventCreate") && hip_ok(hipEventCreate(&e1), "hipEventCreate")) {
-                    hip_ok(hipEventRecord(e0, stream), "hipEventRecord");
-                    if (rbrt_hip_scene_denoise(hs, &dn, stream, d_rad, d_rgb, nullptr, nullptr) != RBRT_OK) fail(rbrt_hip_last_error());
-                    hip_ok(hipEventRecord(e1, stream), "hipEventRecord");
-                    float ms = 0.0f;
-                    if (hip_ok(hipStreamSynchronize(stream), "denoise") && !failed && hip_ok(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime"))
-                        rep.denoise_ms = ms;
-                }
-                if (e0) (void)hipEventDestroy(e0);
-                if (e1) (void)hipEventDestroy(e1);
-            }
-        }
-        for (uint64_t b = start_sample; b < num_samples && !cfg.adaptive; b += pass_spp, ++pass_no) {
-            const uint32_t e = uint32_t(std::min<uint64_t>(num_samples, b + pass_spp));
-            const bool last = e == num_samples;
-            if (!failed && npix) {
-                if (rbrt_hip_render_pass(hs, &c, &o, stream, uint32_t(b), e, d_acc, last ? d_rad : nullptr, last ? (world == 1 ? d_rgb : nullptr) : nullptr) != RBRT_OK)
-                    fail(rbrt_hip_last_error());
-                else
-                    hip_ok(hipStreamSynchronize(stream), "render pass");
-            }
-            const bool ckpt_now = !cfg.checkpoint_path.empty() && !last && (pass_no + 1) % ckpt_every == 0;
-            if (ckpt_now && !failed && npix) {
-                ckpt_acc[rank].resize(npix * 3);
-                hip_ok(hipMemcpy(ckpt_acc[rank].data(), d_acc, npix * 3 * sizeof(float), hipMemcpyDeviceToHost), "download of the running sums");
-            }
-            if (world > 1 && (ckpt_now || !cfg.quiet)) barrier.wait();  // every rank has finished the pass
-            if (rank == 0) {
-                if (!cfg.quiet) {  // lib.rs:105-110
-                    std::printf("\rRendering %.1f%% complete!", double(e) / double(num_samples) * 100.0);
-                    std::fflush(stdout);
-                }
-                // (between the two barriers of a checkpointing pass no other rank is running: the counter is stable)
-                if (ckpt_now && n_failed.load() == 0) {
-                    const std::string tmp = cfg.checkpoint_path + ".tmp";
-                    std::ofstream out(tmp, std::ios::binary | std::ios::trunc);
-                    CheckpointHeader h = want;
-                    h.samples_done = e;
-                    out.write(reinterpret_cast<const char*>(&h), sizeof(h));
-                    for (int r = 0; r < world; ++r) {
-                        const uint64_t cnt = ckpt_acc[r].size();
-                        out.write(reinterpret_cast<const char*>(&cnt), sizeof(cnt));
-                        out.write(reinterpret_cast<const char*>(ckpt_acc[r].data()), std::streamsize(cnt * sizeof(float)));
-                    }
-                    out.close();
-                    if (!out || std::rename(tmp.c_str(), cfg.checkpoint_path.c_str()) != 0) fail("cannot write checkpoint " + cfg.checkpoint_path);
-                    if (!failed) ++rep.checkpoints_written;
-                }
-            }
-            if (world > 1 && ckpt_now) barrier.wait();  // the sums may change again only after they are on disk
-            if (stop_after > 0 && int(pass_no) + 1 == stop_after && !last) fail("stopped after pass " + std::to_string(stop_after) + " (RBRT_TEST_STOP_AFTER_PASS)");
-        }
-        if (rank == 0) rep.passes = pass_no;
-        // ---- the reference would have panicked on a NaN discriminant (sphere.rs:33): surface it ----
-        if (hs && !failed && rbrt_hip_scene_check(hs) != RBRT_OK) fail(rbrt_hip_last_error());
-        t_render[rank] = seconds_since(t_passes);
-        // ---- gather ----
-        const auto t_g = std::chrono::steady_clock::now();
-        // --gather host: every rank's tiles over its own PCIe link, merged on the host (also where a failed RCCL gather ends)
-        auto host_gather = [&]() {
-            if (failed || !npix) return;
-            std::vector<float> hr(npix * 3);
-            if (hip_ok(hipMemcpy(hr.data(), d_rad, hr.size() * sizeof(float), hipMemcpyDeviceToHost), "download")) {
-                const uint32_t tiles_x = (img.width + RBRT_TILE - 1) / RBRT_TILE;
-                for (size_t tl = 0; tl < npix / 64; ++tl) {  // (ranks write disjoint pixels of the shared image)
-                    const uint32_t tile = uint32_t(tl) * uint32_t(world) + uint32_t(rank);
-                    uint32_t ty, tx;
-                    rbrt_hip_tile_xy(tile, tiles_x, &ty, &tx);
-                    for (uint32_t p = 0; p < 64; ++p) {
-                        const uint32_t row = ty * RBRT_TILE + p / 8, col = tx * RBRT_TILE + p % 8;
-                        if (row >= img.height || col >= img.width) continue;
-                        const size_t src = (tl * 64 + p) * 3, dst = (size_t(row) * img.width + col) * 3;
-                        for (int k = 0; k < 3; ++k) {  // lib.rs:116-122 on the host for this path
-                            const float v = hr[src + k];
-                            img.radiance[dst + k] = v;
-                            const float q = std::sqrt(v) * 256.0f;
-                            img.rgb[dst + k] = !(q == q) || q <= 0.0f ? 0 : q >= 255.0f ? 255 : uint8_t(q);
-                        }
-                    }
-                }
-            }
-        };
-
-        if (world == 1) {
-            if (!failed && npix) {
-                hip_ok(hipMemcpy(img.radiance.data(), d_rad, n * sizeof(float), hipMemcpyDeviceToHost), "download");
-                hip_ok(hipMemcpy(img.rgb.data(), d_rgb, n, hipMemcpyDeviceToHost), "download");
-                if ((cfg.tonemap || cfg.glare) && !failed) display_transform(dev, stream, d_rad, d_rgb);  // on the radiance that is here already
-            }
-        } else if (use_rccl) {
-            // The decision to enter the group is taken ONCE, between two barriers: before the first every rank has
-            // recorded what it had to record, and until the second nobody runs code that can fail. All enter or none.
-            barrier.wait();
-            const bool go = n_failed.load() == 0;
-            barrier.wait();
-            if (go) {
-                // one grouped exchange: rank r > 0 sends its packed tiles, rank 0 receives each into that rank's slot
-                bool copied = true;
-                if (rank == 0) copied = hip_ok(hipMemcpyAsync(d_slots, d_rad, npix * 3 * sizeof(float), hipMemcpyDeviceToDevice, stream), "own tiles");
-                ncclResult_t rc = rccl->GroupStart();
-                if (rank == 0) {
-                    for (int r = 1; r < world && rc == ncclSuccess; ++r) {
-                        const size_t cnt = rbrt_hip_packed_pixels(img.width, img.height, uint32_t(r), uint32_t(world)) * 3;
-                        if (cnt) rc = rccl->Recv(d_slots + size_t(r) * slot_pixels * 3, cnt, ncclFloat, r, comms[0], stream);
-                    }
-                } else if (npix && rc == ncclSuccess) {
-                    rc = rccl->Send(d_rad, npix * 3, ncclFloat, 0, comms[rank], stream);
-                }
-                const ncclResult_t rc2 = rccl->GroupEnd();
-                bool rccl_bad = false;  // this rank's part of the exchange failed
-                auto rccl_fail = [&](const std::string& m) {
-                    rccl_bad = true;
-                    std::lock_guard<std::mutex> lk(err_mutex);
-                    if (rccl_note.empty()) rccl_note = m;
-                    rccl_failed.fetch_add(1);
-                };
-                if (rc != ncclSuccess || rc2 != ncclSuccess) rccl_fail(std::string("RCCL gather: ") + rccl->GetErrorString(rc != ncclSuccess ? rc : rc2));
-                if (rank == 0 && !failed && !rccl_bad && copied) {
-                    if (rbrt_hip_unpack_tiles_strided(dev, stream, d_slots, img.width, img.height, uint32_t(world), slot_pixels, d_img, d_rgb) != RBRT_OK)
-                        fail(rbrt_hip_last_error());
-                }
-                // Wait for the exchange, but not for ever: if a peer failed inside the group (its send or receive was
-                // never enqueued) this rank's side can not complete; it then aborts its communicator instead of hanging.
-                for (;;) {
-                    const hipError_t q = hipStreamQuery(stream);
-                    if (q == hipSuccess) break;
-                    if (q != hipErrorNotReady) {
-                        hip_ok(q, "gather");
-                        break;
-                    }
-                    if (n_failed.load() != 0 || rccl_failed.load() != 0) {
-                        if (!rccl_bad) rccl_fail("RCCL gather abandoned: another rank's part of it failed");
-                        (void)rccl->CommAbort(comms[rank]);
-                        comms[rank] = nullptr;
-                        break;
-                    }
-                    std::this_thread::sleep_for(std::chrono::microseconds(50));
-                }
-                // Did the exchange work for everyone? Again one decision between two barriers. If not, the tiles are still
-                // where they were rendered: every rank takes the host path, in this same process.
-                barrier.wait();
-                const bool fell_back = rccl_failed.load() != 0;
-                barrier.wait();
-                if (fell_back) {
-                    host_gather();
-                } else if (rank == 0 && !failed) {
-                    hip_ok(hipMemcpy(img.radiance.data(), d_img, n * sizeof(float), hipMemcpyDeviceToHost), "download");
-                    hip_ok(hipMemcpy(img.rgb.data(), d_rgb, n, hipMemcpyDeviceToHost), "download");
-                    if ((cfg.tonemap || cfg.glare) && !failed) display_transform(dev, stream, d_img, d_rgb);  // on the gathered image
-                }
-            }
-        } else {
-            host_gather();
-        }
-        t_gather[rank] = seconds_since(t_g);
-        const auto t_rel = std::chrono::steady_clock::now();
-        if (d_acc) (void)hipFree(d_acc);
-        if (d_rad) (void)hipFree(d_rad);
-        if (d_rgb) (void)hipFree(d_rgb);
-        if (d_img) (void)hipFree(d_img);
-        if (d_noisy) (void)hipFree(d_noisy);
-        if (rank == 0 && d_slots) (void)hipFree(d_slots);
-        if (stream) (void)hipStreamDestroy(stream);
-        rbrt_hip_scene_destroy(hs);
-        t_release[rank] = seconds_since(t_rel);
-    };
+    // ---- the ranks: one thread per GPU, rank 0 on this one ------------------------------------------------------------------
+    const auto worker = [&](int rank) { Rank(job, sh, rank).run(); };
     std::vector<std::thread> threads;
-    for (int r = 1; r < world; ++r) threads.emplace_back(worker, r);
+    for (int r = 1; r < plan.world; ++r) threads.emplace_back(worker, r);
     worker(0);
     for (auto& t : threads) t.join();
-    for (ncclComm_t cm : comms)
-        if (cm) (void)rccl->CommDestroy(cm);
-    if (rccl_failed.load() != 0) {
-        std::fprintf(stderr, "warning: %s; gathered through host memory instead\n", rccl_note.c_str());
-        rep.gather = "host (rccl was asked for: " + rccl_note + ")";
+
+    // ---- what the ranks left --------------------------------------------------------------------------------------------------
+    for (ncclComm_t cm : sh.comms)
+        if (cm) (void)sh.rccl->CommDestroy(cm);
+    if (sh.rccl_failed.load() != 0) {
+        std::fprintf(stderr, "warning: %s; gathered through host memory instead\n", sh.rccl_note.c_str());
+        rep.gather = "host (rccl was asked for: " + sh.rccl_note + ")";
     }
-    for (int r = 0; r < world; ++r)
-        if (!errors[r].empty()) throw Error("GPU " + std::to_string(device_of(r)) + (cfg.oversubscribe ? " (rank " + std::to_string(r) + ")" : "") + ": " + errors[r]);
+    for (int r = 0; r < plan.world; ++r)
+        if (sh.errors[r].failed())
+            throw Error("GPU " + std::to_string(plan.device_of(r)) + (cfg.oversubscribe ? " (rank " + std::to_string(r) + ")" : "") + ": " + sh.errors[r].message());
     if (!cfg.checkpoint_path.empty()) std::remove(cfg.checkpoint_path.c_str());  // (only reached when the render is complete)
-    if ((cfg.tonemap || cfg.glare) && !tonemapped) {
-        // The ranks' tiles were merged on the host: the complete image goes up to rank 0's device once, so that the target file
-        // does not depend on how many GPUs rendered it or on how their tiles were gathered.
-        const int dev = device_of(0);
-        float* d_src = nullptr;
-        uint8_t* d_out8 = nullptr;
-        std::string err;
-        const auto ok = [&](hipError_t e, const char* what) {
-            if (e != hipSuccess && err.empty()) err = std::string(what) + ": " + hipGetErrorString(e);
-            return e == hipSuccess;
-        };
-        if (ok(hipSetDevice(dev), "hipSetDevice") && ok(hipMalloc(reinterpret_cast<void**>(&d_src), n * sizeof(float)), "hipMalloc(image)") &&
-            ok(hipMalloc(reinterpret_cast<void**>(&d_out8), n), "hipMalloc(rgb8)") &&
-            ok(hipMemcpy(d_src, img.radiance.data(), n * sizeof(float), hipMemcpyHostToDevice), "upload of the gathered image")) {
-            rbrt_tonemap_result_t chosen{};
-            float ms = 0.0f, glare_ms = 0.0f;
-            err = run_display(cfg, dev, nullptr, d_src, img.width, img.height, tonemap_opts_of(cfg), d_out8, img.rgb.data(), &chosen, &ms, &glare_ms);
-            if (cfg.tonemap) rep.tonemap_exposure = chosen.exposure, rep.tonemap_white = chosen.white, rep.luminance_counted = chosen.counted, rep.tonemap_ms = ms;
-            rep.glare_ms = glare_ms;
-        }
-        if (d_src) (void)hipFree(d_src);
-        if (d_out8) (void)hipFree(d_out8);
-        if (!err.empty()) throw Error("GPU " + std::to_string(dev) + ": " + err);
-    }
+    if ((cfg.tonemap || cfg.glare) && !sh.displayed) display_after_host_gather(job, rep);
     if (!cfg.quiet) std::printf("\rRendering 100%% complete!\n");
-    rep.resumed_from_sample = start_sample;
-    {   // the slowest rank's set-up, split (the parts of one rank, so that they add up)
-        const size_t slow = size_t(std::max_element(t_setup.begin(), t_setup.end()) - t_setup.begin());
-        const rbrt_hip_call_times_t& ct = t_create[slow];
-        rep.upload_build_s = t_setup[slow];
-        rep.hip_init_s = hip_start_s + ct.hip_init_s, rep.upload_s = ct.upload_s, rep.bvh_build_s = ct.bvh_build_s;
-        rep.lanes_s = ct.lanes_s + std::max(0.0, ct.create_s - ct.hip_init_s - ct.upload_s - ct.bvh_build_s - ct.lanes_s);
-        rep.buffers_s = std::max(0.0, t_setup[slow] - ct.create_s);
-        rep.release_s = *std::max_element(t_release.begin(), t_release.end());
-    }
-    rep.render_s = *std::max_element(t_render.begin(), t_render.end());
-    rep.gather_s = *std::max_element(t_gather.begin(), t_gather.end());
+    rep.resumed_from_sample = job.resume.samples_done;
+    report_times(plan, sh, rep);
     if (cfg.report) *cfg.report = rep;
     return img;
 }

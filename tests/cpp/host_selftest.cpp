@@ -17,6 +17,7 @@
 #include <thread>
 #include <cstring>
 #include "../../rbrt_amd/csrc/bvh.h"
+#include "../../rbrt_amd/host/checkpoint.hpp"
 #include "../../rbrt_amd/host/rbrt.hpp"
 #include "../../rbrt_amd/host/yaml_lite.hpp"
 
@@ -122,6 +123,131 @@ static void check_bvh(const rbrt_mesh_t& m) {
     CHECK(r.tris.size() <= rbrt::bvh_record_capacity(m.n_total));
     CHECK(r.max_depth <= uint32_t(rbrt::kMaxBvhDepth));
     CHECK(leaves == r.n_leaves || r.n_indexed <= uint32_t(rbrt::kLeafMax));
+}
+
+// The fixed scene of the checkpoint-fingerprint cases: one sphere, one from_triangles mesh, a camera from literal arguments; each
+// feature on request.
+struct FingerprintCase {
+    rbrt::Camera cam;
+    rbrt::Scene scene;
+    rbrt_render_opts_t opts;
+};
+static FingerprintCase fingerprint_case(bool smooth, bool background, bool lens, bool env) {
+    using rbrt::Vec3;
+    FingerprintCase c{rbrt::Camera::create(Vec3(0.5f, 1.0f, 2.0f), Vec3(0.0f, -0.25f, -1.0f), Vec3(0.0f, 1.0f, 0.0f), 48, 64, 35.0f), rbrt::Scene(),
+                      rbrt_render_opts_t()};
+    std::memset(&c.opts, 0, sizeof(c.opts));
+    if (lens) c.cam.set_lens(12.5f, 4.0f), c.opts.flags |= RBRT_FLAG_THIN_LENS;
+    if (background) c.opts.flags |= RBRT_FLAG_CONSTANT_BACKGROUND, c.opts.bg[0] = 0.25f, c.opts.bg[1] = 0.5f, c.opts.bg[2] = 0.125f;
+    c.scene.elements.push_back(rbrt::Sphere{Vec3(0.5f, -1.0f, -4.0f), 1.25f, rbrt::Material::metal(Vec3(0.75f, 0.5f, 0.25f), 0.125f)});
+    const std::vector<std::array<Vec3, 3>> tris = {{Vec3(0, 0, -3), Vec3(1, 0, -3), Vec3(0, 1, -3)},
+                                                   {Vec3(1, 0, -3), Vec3(1, 1, -3.5f), Vec3(0, 1, -3)},
+                                                   {Vec3(-1, 0, -2), Vec3(0, 0, -3), Vec3(0, 1, -3)}};
+    const std::vector<std::array<Vec3, 3>> normals = {{Vec3(0, 0, 1), Vec3(0.6f, 0, 0.8f), Vec3(0, 0.6f, 0.8f)},
+                                                      {Vec3(0.6f, 0, 0.8f), Vec3(0, 1, 0), Vec3(0, 0.6f, 0.8f)},
+                                                      {Vec3(-0.8f, 0, 0.6f), Vec3(0, 0, 1), Vec3(0, 0.6f, 0.8f)}};
+    c.scene.triangle_meshes.push_back(
+        rbrt::TriangleMesh::from_triangles(tris, rbrt::Material::lambertian(Vec3(0.5f, 0.25f, 0.75f)), smooth ? &normals : nullptr));
+    if (env) {
+        c.scene.environment.n = 2;
+        for (int i = 0; i < 27; ++i) c.scene.environment.nodes.push_back(0.125f * float(i) + 0.5f);
+    }
+    return c;
+}
+
+static uint64_t fingerprint_of(bool smooth, bool background, bool lens, bool env, const std::string& path = "x.ckpt") {
+    const FingerprintCase c = fingerprint_case(smooth, background, lens, env);
+    const rbrt::Scene::AbiView v = c.scene.to_abi();
+    return rbrt::checkpoint_fingerprint(path, c.cam.to_abi_lens(), c.opts, v.scene, v.shading_ptr(), c.scene.environment);
+}
+
+// The checkpoint file (rbrt_amd/host/checkpoint.cpp): a round trip, everything that must be refused, and the fingerprints.
+static void check_checkpoint(const std::string& tmp) {
+    const std::string path = tmp + "/selftest.ckpt";
+    const rbrt::CheckpointHeader want = rbrt::checkpoint_header(136, 100, 10, 3, 6, 0x1234567890ABCDEFull);
+    const std::vector<size_t> counts = {15, 0, 7};  // ragged, one rank without a pixel
+    std::vector<std::vector<float>> sums(3);
+    for (size_t r = 0; r < 3; ++r)
+        for (size_t i = 0; i < counts[r]; ++i) sums[r].push_back(float(r) * 100.0f + float(i) + 0.25f);
+    CHECK(rbrt::write_checkpoint(path, want, 4, sums));
+    CHECK(slurp(path + ".tmp").empty());  // renamed, not copied
+    const std::string good = slurp(path);
+    CHECK(good.size() == sizeof(rbrt::CheckpointHeader) + 3 * 8 + (15 + 0 + 7) * sizeof(float));
+    {
+        const rbrt::CheckpointRead r = rbrt::read_checkpoint(path, want, counts);
+        CHECK(r.found && r.samples_done == 4 && r.sums == sums);
+    }
+    const auto starts_over = [&](const std::string& bytes, const rbrt::CheckpointHeader& w, const std::vector<size_t>& cnts, bool found = true) {
+        const std::string p = tmp + "/selftest_bad.ckpt";
+        std::ofstream(p, std::ios::binary).write(bytes.data(), std::streamsize(bytes.size()));
+        const rbrt::CheckpointRead r = rbrt::read_checkpoint(p, w, cnts);
+        bool empty = r.samples_done == 0 && r.found == found;
+        for (const auto& v : r.sums) empty = empty && v.empty();
+        return empty;
+    };
+    CHECK(!starts_over(good, want, counts));  // (the helper itself: the good bytes resume)
+    {   // no file at all: nothing found, start at 0
+        const rbrt::CheckpointRead r = rbrt::read_checkpoint(tmp + "/does_not_exist.ckpt", want, counts);
+        CHECK(!r.found && r.samples_done == 0);
+    }
+    {   // a wrong magic, a change in each single header field, samples_done of 0 and of spp
+        std::string b = good;
+        b[7] = '2';
+        CHECK(starts_over(b, want, counts));
+        using H = rbrt::CheckpointHeader;
+        void (*const change[6])(H&) = {[](H& w) { w.width = 137; }, [](H& w) { w.height = 101; },        [](H& w) { w.spp = 11; },
+                                       [](H& w) { w.world = 2; },   [](H& w) { w.seed = 7; }, [](H& w) { w.fingerprint ^= 1ull << 63; }};
+        for (const auto& f : change) {
+            H w = want;
+            f(w);
+            CHECK(std::memcmp(&w, &want, sizeof(w)) != 0);
+            CHECK(starts_over(good, w, counts));
+        }
+        H two = want;
+        two.world = 2;
+        const std::vector<size_t> counts_of_two = {15, 0};
+        CHECK(starts_over(good, two, counts_of_two));
+        for (uint32_t done : {0u, 10u, 11u}) {
+            rbrt::CheckpointHeader h = want;
+            h.samples_done = done;
+            b = good;
+            std::memcpy(&b[0], &h, sizeof(h));
+            CHECK(starts_over(b, want, counts));
+        }
+    }
+    // a per-rank count that differs from the expected one, in the file and in the expectation, including 2^60
+    const size_t count_at[3] = {sizeof(rbrt::CheckpointHeader), sizeof(rbrt::CheckpointHeader) + 8 + 15 * 4, sizeof(rbrt::CheckpointHeader) + 16 + 15 * 4};
+    for (size_t r = 0; r < 3; ++r)
+        for (uint64_t cnt : {uint64_t(counts[r] + 1), uint64_t(counts[r] - 1), uint64_t(1) << 60, ~uint64_t(0)}) {
+            std::string b = good;
+            std::memcpy(&b[count_at[r]], &cnt, sizeof(cnt));
+            CHECK(starts_over(b, want, counts));
+        }
+    for (const std::vector<size_t>& other : {std::vector<size_t>{15, 0, 8}, std::vector<size_t>{14, 0, 7}, std::vector<size_t>{15, 1, 7}})
+        CHECK(starts_over(good, want, other));
+    // truncated: at the header (nothing found), in a count, in the middle of a rank's floats, one byte short of the end
+    CHECK(starts_over(good.substr(0, 0), want, counts, false));
+    CHECK(starts_over(good.substr(0, sizeof(rbrt::CheckpointHeader) - 1), want, counts, false));
+    CHECK(starts_over(good.substr(0, sizeof(rbrt::CheckpointHeader)), want, counts));
+    CHECK(starts_over(good.substr(0, count_at[0] + 3), want, counts));
+    CHECK(starts_over(good.substr(0, count_at[0] + 8 + 30), want, counts));
+    CHECK(starts_over(good.substr(0, count_at[2] + 5), want, counts));
+    CHECK(starts_over(good.substr(0, good.size() - 1), want, counts));
+    CHECK(!rbrt::write_checkpoint("/nonexistent_dir/x.ckpt", want, 4, sums));
+    // Fingerprints: the literals are what the code BEFORE checkpoint.cpp existed gave for these scenes (render.cpp's inlined
+    // fingerprint, run on this scene), so a checkpoint written by an older build still resumes. Never refresh them from
+    // checkpoint_fingerprint itself.
+    const uint64_t fps[7] = {fingerprint_of(false, false, false, false), fingerprint_of(true, false, false, false), fingerprint_of(false, true, false, false),
+                             fingerprint_of(false, false, true, false),  fingerprint_of(false, false, false, true), fingerprint_of(false, false, true, true),
+                             fingerprint_of(true, true, true, true)};
+    const uint64_t expect[7] = {0x82785BBCB5E4D395ull, 0xE3C6F6411327AB30ull, 0x4AA9C19C5A330C66ull, 0xF96F44E083404CEFull,
+                                0x9B00D435A4E59A30ull, 0x49339898107624AEull, 0x5DE63705418334B8ull};
+    for (int i = 0; i < 7; ++i) {
+        CHECK(fps[i] == expect[i]);
+        for (int k = 0; k < i; ++k) CHECK(fps[i] != fps[k]);
+    }
+    CHECK(fingerprint_of(true, true, true, true, "") == 0);  // no path, no checkpoint to match
+    CHECK(fingerprint_of(false, false, false, false, "other.ckpt") == expect[0]);
 }
 
 int main(int argc, char** argv) {
@@ -252,6 +378,8 @@ int main(int argc, char** argv) {
         one.save(tmp + "/selftest_one.qoi");
         one.save(tmp + "/selftest_one.bmp");
     }
+    // ---- the checkpoint file and its fingerprint ----
+    check_checkpoint(tmp);
     // ---- BasicTriangle elements and the element order in the ABI view (triangle.rs:9-34, scene.rs:23-31) ----
     {
         rbrt::Scene sc;

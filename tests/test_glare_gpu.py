@@ -357,6 +357,18 @@ def test_cli_glare_alone_and_in_front_of_the_display_transform(hip, tmp_path):
     assert js3["gpus"] == 2 and np.array_equal(png(out3), png(out1))
 
 
+def test_cli_two_ranks_glare_and_automatic_exposure_after_the_host_gather(hip, tmp_path):
+    """Both display stages on the image two ranks rendered and the host merged (it goes up to rank 0's device once): the same
+    bytes and the same chosen exposure as the one-rank run, where the stages work on the radiance that never left the device."""
+    stages = ("--glare", "0.3", "--exposure", "auto", "--tonemap", "aces")
+    one, js1 = cli(tmp_path, "one", *stages)
+    two, js2 = cli(tmp_path, "two", *stages, "--gpus", "2", "--oversubscribe", "--gather", "host")
+    assert js1["gpus"] == 1 and js2["gpus"] == 2 and js2["gather"] == "host"
+    assert two.read_bytes() == one.read_bytes()
+    assert js2["exposure"] == js1["exposure"] and js1["exposure"] > 0 and js2["tonemap"] == "aces" and f32(js2["glare"]) == f32(0.3)
+    assert not np.array_equal(png(two), png(cli(tmp_path, "plain")[0]))  # (the stages did something)
+
+
 def test_cli_the_noisy_file_gets_the_same_glare(hip, tmp_path):
     import torch
     pfm, noisy = tmp_path / "r.pfm", tmp_path / "noisy.png"

@@ -80,6 +80,46 @@ def test_cli_n_ranks_on_one_gpu_checkpoint_resume_and_host_merge(hip, oracle, tm
     assert 0.9 * j["total_s"] <= sum(j[k] for k in parts) <= 1.5 * j["total_s"] and j["obj_load_s"] > 0 and j["hip_init_s"] > 0
 
 
+def test_cli_checkpoint_every_second_pass_two_ranks_resumes_from_the_last_one_written(hip, oracle, tmp_path):
+    """`--checkpoint-every 2` with passes of 2 samples: passes end at samples 2, 4, 6, ..., and every second one of a run writes
+    the file. Interrupted after its third pass, the run leaves the checkpoint of sample 4 (the sums of sample 6 were never
+    written). The second run counts its passes from there -- 4..6, 6..8 (its second pass: the one checkpoint it writes), 8..10 --
+    gives the oracle's image and removes the file."""
+    cfg = _scene_file(tmp_path)
+    out, ck, rep = tmp_path / "out.png", tmp_path / "render.ckpt", tmp_path / "report.json"
+    cmd = [str(RBRT), "-c", str(cfg), "-t", str(out), "--height", str(H), "-w", str(W), "-s", "10", "--seed", "6", "--gpus", "2",
+           "--oversubscribe", "--pass-samples", "2", "--checkpoint-every", "2", "--checkpoint", str(ck), "--report", str(rep)]
+    r1 = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=dict(os.environ, RBRT_TEST_STOP_AFTER_PASS="3"))
+    assert r1.returncode == 101 and "stopped after pass 3" in r1.stderr, (r1.returncode, r1.stderr[-2000:])
+    assert ck.exists() and not out.exists() and not rep.exists()
+    assert ck.stat().st_size == 48 + sum(8 + hip.packed_pixels(W, H, r, 2) * 3 * 4 for r in range(2))
+    r2 = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert r2.returncode == 0, r2.stderr[-2000:]
+    assert "Resuming from checkpoint" in r2.stdout and "at sample 4 of 10" in r2.stdout
+    j = json.loads(rep.read_text())
+    assert j["resumed_from_sample"] == 4 and j["passes"] == 3 and j["checkpoints_written"] == 1 and j["gpus"] == 2
+    assert not ck.exists()
+    _, exp8, _ = oracle.render(scenes.camera(oracle, W, H), scenes.example_scene(oracle, 1203), abi.default_opts(spp=10, seed=6))
+    assert np.array_equal(_png(out), exp8)
+
+
+def test_cli_one_rank_resumes_every_pixel_of_a_ragged_image(hip, oracle, tmp_path):
+    """One rank's running sums are in packed tile order too (rbrt_hip.h: rbrt_hip_render_pass), which at a height that is no
+    multiple of the tile is more than the image: the checkpoint has to hold all of them, or the last tile row comes back from
+    a resume without its earlier samples."""
+    cfg = _scene_file(tmp_path)
+    out, ck = tmp_path / "out.png", tmp_path / "render.ckpt"
+    cmd = [str(RBRT), "-c", str(cfg), "-t", str(out), "--height", str(H), "-w", str(W), "-s", "10", "--seed", "6", "--pass-samples", "3",
+           "--checkpoint", str(ck)]
+    r1 = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=dict(os.environ, RBRT_TEST_STOP_AFTER_PASS="2"))
+    assert r1.returncode == 101 and "stopped after pass 2" in r1.stderr, (r1.returncode, r1.stderr[-2000:])
+    assert ck.stat().st_size == 48 + 8 + hip.packed_pixels(W, H, 0, 1) * 3 * 4 and hip.packed_pixels(W, H, 0, 1) > W * H
+    r2 = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert r2.returncode == 0 and "at sample 6 of 10" in r2.stdout, r2.stderr[-2000:]
+    _, exp8, _ = oracle.render(scenes.camera(oracle, W, H), scenes.example_scene(oracle, 1203), abi.default_opts(spp=10, seed=6))
+    assert np.array_equal(_png(out), exp8)
+
+
 def test_cli_one_pass_n_ranks_equals_one_rank(hip, tmp_path):
     """No passes, no checkpoint (one barrier-free pass per rank): the 5-rank image is the 1-rank image, byte for byte."""
     cfg = _scene_file(tmp_path, 2004)

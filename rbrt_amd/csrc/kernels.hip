@@ -163,14 +163,18 @@ __device__ __forceinline__ bool sphere_hit(V3 c, float radius, V3 o, V3 d, float
     float b = dot(d * 2.0f, l);
     float cc = dot(l, l) - radius * radius;
     float sol = b * b - 4.0f * a * cc;
-    if (sol != sol) {  // the reference panics here (sphere.rs:33); count it and miss
-        atomicAdd(&counters->nan_discriminants, 1ull);
+    if (!(sol >= 0.0f)) {  // negative: a miss. NaN: the reference panics here (sphere.rs:33); count it and miss
+        if (sol != sol) atomicAdd(&counters->nan_discriminants, 1ull);
         return false;
     }
-    if (sol < 0.0f) return false;
-    float t = (-b - ieee_sqrt(sol)) / (2.0f * a);
+    // One square root and one 2a serve both roots (the reference writes them out twice; the second root's block runs
+    // behind a wave vote, where the compiler does not merge them). The second division stays: choosing the numerator
+    // by the sign of -b - s before a single division needs a gate on its operands, and every form of that gate cost
+    // ten more scalar-register spills in the trace kernel (DESIGN.md §6 "Measured and dropped").
+    const float s = ieee_sqrt(sol), den = 2.0f * a;
+    float t = (-b - s) / den;
     if (sol > 0.0f && t < 0.0f) {
-        t = (-b + ieee_sqrt(sol)) / (2.0f * a);
+        t = (-b + s) / den;
         if (t < 0.0f) return false;
     }
     V3 p = o + t * d;
@@ -628,9 +632,8 @@ __device__ __forceinline__ float schlick(float cosine, float ref_index) {  // di
     return r0 + (1.0f - r0) * (x * x4);  // powi(5) = x * (x^2)^2
 }
 
-__device__ __forceinline__ bool refract(V3 dir, V3 n, float ni_over_nt, V3& out) {  // dielectric.rs:68-85
-    V3 v = normalize(dir);
-    V3 nu = normalize(n);
+// dielectric.rs:72-85: refract on unit vectors, v = normalize(dir), nu = normalize(n)
+__device__ __forceinline__ bool refract_unit(V3 v, V3 nu, float ni_over_nt, V3& out) {
     float c = dot(v, nu);
     float discr = 1.0f - (ni_over_nt * ni_over_nt) * (1.0f - c * c);
     if (discr > 0.0f) {
@@ -638,6 +641,48 @@ __device__ __forceinline__ bool refract(V3 dir, V3 n, float ni_over_nt, V3& out)
         return true;
     }
     return false;
+}
+__device__ __forceinline__ bool refract(V3 dir, V3 n, float ni_over_nt, V3& out) {  // dielectric.rs:68-85
+    return refract_unit(normalize(dir), normalize(n), ni_over_nt, out);
+}
+
+// dielectric.rs:11-59. The reference normalises the incoming direction three times (in reflect, for the cosine, in refract)
+// and the normal or its negation three times. Here du and nu are computed once when every active lane's operands pass
+// normalize's gate, so that both came from its short path: there normalize(-1.0f * n) is -normalize(n) bit for bit, because
+// every step (the squares, the square root and the reciprocal of an unchanged length, the products and fused residuals
+// with a negated numerator) is odd-symmetric under round-to-nearest, and no component is 0 or NaN. A wave with a lane
+// outside the gate (a zero, subnormal, huge or NaN operand) runs the reference's sequence as written.
+__device__ __forceinline__ void scatter_dielectric(float ref_index, V3 in_d, V3 n, Rng& rng, V3& out_d) {
+    bool short_d, short_n;
+    const V3 du = normalize(in_d, short_d);
+    const V3 nu = normalize(n, short_n);
+    V3 reflected, refracted = mk(0.0f, 0.0f, 0.0f);
+    float reflect_prob;
+    if (short_d && short_n) {
+        const float a = dot(du, nu);
+        const bool leaving = a > 0.0f;
+        const V3 outward = leaving ? mk(-nu.x, -nu.y, -nu.z) : nu;
+        const float ni_over_nt = leaving ? ref_index : 1.0f / ref_index;
+        const float cosine = leaving ? ref_index * a : -a;
+        reflect_prob = refract_unit(du, outward, ni_over_nt, refracted) ? schlick(cosine, ref_index) : 1.0f;
+        reflected = normalize(du - 2.0f * nu * a);  // reflect(in_d, n), last: du and nu end here
+    } else {
+        reflected = reflect(in_d, n);
+        V3 outward;
+        float ni_over_nt, cosine;
+        float a = dot(normalize(in_d), normalize(n));
+        if (a > 0.0f) {
+            outward = -1.0f * n;
+            ni_over_nt = ref_index;
+            cosine = ref_index * a;
+        } else {
+            outward = n;
+            ni_over_nt = 1.0f / ref_index;
+            cosine = -a;
+        }
+        reflect_prob = refract(in_d, outward, ni_over_nt, refracted) ? schlick(cosine, ref_index) : 1.0f;
+    }
+    out_d = (rng.next_f32() < reflect_prob) ? reflected : refracted;
 }
 
 // RayScattering::scatter for the three materials that scatter (not for an emitter: callers never pass one). Returns the
@@ -652,22 +697,7 @@ __device__ __forceinline__ bool scatter(const DevMaterial& m, V3 in_d, V3 p, V3 
         out_d = normalize(target + m.param * random_point_in_unit_sphere(rng));
         return dot(out_d, n) > 0.0f;
     } else {  // dielectric.rs:11-59
-        V3 reflected = reflect(in_d, n);
-        V3 outward;
-        float ni_over_nt, cosine;
-        float a = dot(normalize(in_d), normalize(n));
-        if (a > 0.0f) {
-            outward = -1.0f * n;
-            ni_over_nt = m.param;
-            cosine = m.param * a;
-        } else {
-            outward = n;
-            ni_over_nt = 1.0f / m.param;
-            cosine = -a;
-        }
-        V3 refracted = mk(0.0f, 0.0f, 0.0f);
-        float reflect_prob = refract(in_d, outward, ni_over_nt, refracted) ? schlick(cosine, m.param) : 1.0f;
-        out_d = (rng.next_f32() < reflect_prob) ? reflected : refracted;
+        scatter_dielectric(m.param, in_d, n, rng, out_d);
         return true;
     }
 }

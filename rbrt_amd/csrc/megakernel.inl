@@ -997,7 +997,8 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                     nd = normalize(target + m.param * random_point_in_unit_sphere(rng));
                     ok = dot(nd, n) > 0.0f;
                 } else {  // dielectric.rs:11-59
-                    ok = scatter(m, d, p, n, rng, nd);
+                    scatter_dielectric(m.param, d, n, rng, nd);
+                    ok = true;
                 }
                 if (ok) {
                     if (lk != ST_DIEL) {  // attenuation (1,1,1) is an exact identity, not recorded

@@ -63,7 +63,9 @@ extern "C" {
                               (rbrt_tonemap_opts_t, rbrt_tonemap_result_t, rbrt_tonemap_opts_default and rbrt_hip_tonemap: added
                               structs and entry points, detected by the symbol), nor glare
                               (rbrt_glare_opts_t, rbrt_glare_opts_default, rbrt_hip_glare_workspace_bytes and rbrt_hip_glare:
-                              an added struct and entry points, detected by the symbol) */
+                              an added struct and entry points, detected by the symbol), nor the feature buffers
+                              (rbrt_feature_opts_t, rbrt_feature_opts_default and rbrt_hip_render_features: an added struct
+                              and entry points, detected by the symbol) */
 
 typedef enum rbrt_status {
     RBRT_OK = 0,
@@ -635,6 +637,56 @@ size_t rbrt_hip_glare_workspace_bytes(uint32_t width, uint32_t height, uint32_t 
  * RBRT_ERR_UNSUPPORTED: width * height >= 2^31. */
 int rbrt_hip_glare(int device, void* stream, const float* d_radiance, uint32_t width, uint32_t height,
                    const rbrt_glare_opts_t* opts, void* d_workspace, float* d_out_radiance, uint8_t* d_rgb8);
+
+/* ---- Feature buffers: albedo, normal, depth and coverage of the primary rays ---------------------------------------------------
+ * No counterpart in the reference, whose render_scene returns colour only. Every stage above sees colour only, too; these
+ * buffers say which surface a pixel shows: what a feature-guided filter, a compositing mask or an external denoiser reads, or
+ * a depth or normal pass of its own. They are made from the render's own primary rays, by a kernel of their own.
+ *
+ * The rule. All arithmetic is float32, unfused, in the written order; / and sqrt are correctly rounded.
+ *   Rays.  For pixel (row, col) and sample s in 0..n-1 the primary ray (o, d) is the render's own: the stream keyed
+ *     (opts->seed, row * W + col, s) draws the column jitter, then the row jitter, which place the target T (cam.rs:64-82); with
+ *     RBRT_FLAG_THIN_LENS the lens draws follow exactly as rbrt_camera_lens_t documents, else o = position and F = T;
+ *     d = normalize(F - o). A sample's stream does not depend on spp, so n is independent of opts->spp.
+ *   Hit.  The closest hit is Scene::hit with opts->min_dist and opts->max_dist: what rbrt_hip_trace_rays returns.
+ *   Per sample:             a ray that hits nothing    a hit of object k with material m
+ *     albedo a              (0, 0, 0)                  lambertian, metal: m.albedo; dielectric: (1, 1, 1), its attenuation;
+ *                                                      emissive: m.albedo, the emitted radiance, which may exceed 1
+ *     normal N              (0, 0, 0)                  normalize(g): three divisions by the length. g is the normal the scatter pass
+ *                                                      would use for this ray, what rbrt_hip_debug_shading_normals returns: a
+ *                                                      sphere's (o + t d) - centre, a BasicTriangle's stored normal, a mesh's stored
+ *                                                      face normal or the smooth one. Not flipped towards the ray; no guard.
+ *     depth z               0                          dist_from_ray_orig of the winner (rbrt_hip_trace_rays' out_dist)
+ *     coverage c            0                          1
+ *   Sums.  Every channel of a pixel is a sum from 0 that adds sample 0, 1, ... in that order, then multiplied by
+ *     inv_n = 1.0f / float(n). The normal's mean is not renormalised. The depth's mean includes the zeros of the rays that hit
+ *     nothing; the coverage tells them apart.
+ *   object is an int32: the object id of sample 0 in rbrt_hip_trace_rays' numbering (rbrt_scene_t), or -1 when it hits nothing.
+ * Not read: opts->spp, max_depth, bg, RBRT_FLAG_CONSTANT_BACKGROUND and the handle's environment. A NaN sphere discriminant is
+ * counted as in a render, so rbrt_hip_scene_check reports it.
+ * Consequence. A scene made only of emitters, rendered with RBRT_FLAG_CONSTANT_BACKGROUND and bg = 0 at spp = n, has a radiance
+ * image equal bit for bit to its albedo buffer: both are the same sums of L and +0 in sample order, times 1.0f / float(n). */
+typedef struct rbrt_feature_opts {
+    uint32_t samples;     /* n, 1..65536 */
+    uint32_t reserved[3]; /* 0 */
+} rbrt_feature_opts_t;
+void rbrt_feature_opts_default(rbrt_feature_opts_t* opts); /* samples = 4 */
+
+/* The feature buffers of `cam` into DEVICE memory, row-major: d_albedo and d_normal float[H][W][3], d_depth and d_coverage
+ * float[H][W], d_object int32[H][W]. Every output may be NULL; with all of them NULL nothing is launched and the call returns
+ * RBRT_OK. Asynchronous on `stream`; the threading rule of rbrt_hip_render_device holds. The call owns no device memory and does
+ * not touch the handle's accumulators, adaptive sums, tile tables or pipeline lanes: renders, rbrt_hip_render_adaptive and
+ * rbrt_hip_scene_denoise before and after it give what they give without it. It takes the handle's current tree, as
+ * rbrt_hip_trace_rays does; the result does not depend on which tree. Works on smooth handles; honours element_order and
+ * BasicTriangles. With RBRT_FLAG_THIN_LENS `cam` is the `cam` member of an rbrt_camera_lens_t, as for a render.
+ * RBRT_ERR_INVALID_ARG, before the device is touched: scene, cam, opts or features NULL; samples 0 or above 65536; a non-zero
+ * reserved word; RBRT_FLAG_COLLECT_STATS set; and what rbrt_hip_render_device rejects in the camera (an image without pixels), the
+ * lens or the partition (tile_rank >= tile_world).
+ * RBRT_ERR_UNSUPPORTED: tile_world > 1 (a host gathers the image, and the features of the whole frame cost one rank little);
+ * an image of 2^32 pixels or more. */
+int rbrt_hip_render_features(rbrt_hip_scene_t* scene, const rbrt_camera_t* cam, const rbrt_render_opts_t* opts,
+                             const rbrt_feature_opts_t* features, void* stream, float* d_albedo, float* d_normal,
+                             float* d_depth, float* d_coverage, int32_t* d_object);
 
 /* De-interleave gathered per-rank packed tile buffers (concatenated rank 0..world-1, each
  * rbrt_hip_packed_pixels(...)*3 floats, device memory) into a row-major float[H][W][3] device

@@ -157,6 +157,20 @@ class HipScene:
         abi.check(self._lib.rbrt_hip_scene_denoise(self._h, C.byref(d), C.c_void_p(stream or 0), C.c_void_p(d_radiance or 0),
                                                    C.c_void_p(d_rgb8 or 0), C.c_void_p(d_half_a or 0), C.c_void_p(d_half_b or 0)))
 
+    def render_features(self, cam: abi.Camera, opts: abi.RenderOpts, samples: int | None = None, d_albedo: int | None = None,
+                        d_normal: int | None = None, d_depth: int | None = None, d_coverage: int | None = None,
+                        d_object: int | None = None, lens=None, stream: int | None = None, reserved=(0, 0, 0)):
+        """The feature buffers of the primary rays into device pointers (rbrt_hip_render_features): the means over `samples`
+        samples a pixel (None: the library's default, 4) of the albedo and the normal, float32 [H, W, 3], of the depth and
+        the coverage, float32 [H, W], and the object id of sample 0, int32 [H, W]; each may be None. Asynchronous on `stream`.
+        `lens`: see _cam_arg (opts is not changed)."""
+        opts = _opts_copy(opts)
+        cam_p, _keep = _cam_arg(cam, lens, opts)
+        f = feature_opts(samples, reserved)
+        abi.check(self._lib.rbrt_hip_render_features(self._h, cam_p, C.byref(opts), C.byref(f), C.c_void_p(stream or 0),
+                                                     C.c_void_p(d_albedo or 0), C.c_void_p(d_normal or 0), C.c_void_p(d_depth or 0),
+                                                     C.c_void_p(d_coverage or 0), C.c_void_p(d_object or 0)))
+
     def set_environment(self, nodes, *, n: int | None = None, reserved: int = 0):
         """Sets the handle's environment map (rbrt_hip_scene_set_environment): `nodes` float32 (N + 1, N + 1, 3), N taken
         from its shape; None clears it (rays that hit nothing see opts.bg again). Blocking. `n` and `reserved` put other
@@ -449,6 +463,11 @@ def glare(device: int, d_radiance: int, width: int, height: int, opts: abi.Glare
     abi.check(load_hip().rbrt_hip_glare(device, C.c_void_p(stream or 0), C.c_void_p(d_radiance or 0), width, height,
                                         C.byref(opts) if opts is not None else None, C.c_void_p(d_workspace or 0),
                                         C.c_void_p(d_out_radiance or 0), C.c_void_p(d_rgb8 or 0)))
+
+
+def feature_opts(samples: int | None = None, reserved=(0, 0, 0)) -> abi.FeatureOpts:
+    """rbrt_feature_opts_default (4 samples), with `samples` put in when it is given."""
+    return abi.feature_opts(samples, reserved)
 
 
 def write_pfm(path, rgb) -> None:

@@ -179,6 +179,10 @@ class GlareOpts(C.Structure):  # rbrt_glare_opts_t
                 ("reserved", C.c_uint32 * 4)]
 
 
+class FeatureOpts(C.Structure):  # rbrt_feature_opts_t
+    _fields_ = [("samples", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
 class Environment(C.Structure):  # rbrt_environment_t
     """An octahedral radiance map of (n + 1) x (n + 1) nodes: `nodes` points at host float32 [n + 1][n + 1][3]."""
     _fields_ = [("n", C.c_uint32), ("reserved", C.c_uint32), ("nodes", f32p)]
@@ -258,6 +262,9 @@ HIP_SYMBOLS = {
                                  C.c_void_p]),
     "rbrt_hip_scene_denoise": (C.c_int, [C.c_void_p, C.POINTER(DenoiseOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rbrt_hip_scene_set_environment": (C.c_int, [C.c_void_p, C.POINTER(Environment)]),
+    "rbrt_feature_opts_default": (None, [C.POINTER(FeatureOpts)]),
+    "rbrt_hip_render_features": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderOpts), C.POINTER(FeatureOpts), C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 # ... and include/rbrt_hip_debug.h (test hooks and diagnostics, same library)
 DEBUG_SYMBOLS = {
@@ -459,6 +466,17 @@ def default_opts(spp: int = 5, seed: int = 1, **kw) -> RenderOpts:
         else:
             setattr(o, k, v)
     return o
+
+
+def feature_opts(samples: int | None = None, reserved=(0, 0, 0)) -> FeatureOpts:
+    """rbrt_feature_opts_default (4 samples a pixel), with `samples` put in when it is given."""
+    f = FeatureOpts()
+    load_hip().rbrt_feature_opts_default(C.byref(f))
+    if samples is not None:
+        f.samples = int(samples)
+    for k in range(3):
+        f.reserved[k] = int(reserved[k])
+    return f
 
 
 # ------------------------------------------------------------------------------------------

@@ -48,6 +48,7 @@ hipError_t launch_trace_rays(const TraceParams& P, const float* rays, size_t n, 
                              int32_t* out_tri, float* out_dist, hipStream_t stream);
 hipError_t launch_shading_normals(const TraceParams& P, const float* rays, size_t n, float* out_normal, hipStream_t stream);
 hipError_t launch_environment_lookup(const EnvTexel* nodes, uint32_t n_env, const float* dirs, size_t n, float* out_rgb, hipStream_t stream);
+hipError_t launch_features(const TraceParams& P, const FeatureParams& F, hipStream_t stream);  // features.inl
 hipError_t launch_gate_selftest(const float* d_box, const float* d_rays, size_t n, uint8_t* d_fast, uint8_t* d_exact);
 hipError_t launch_ieee_selftest(uint64_t seed, size_t n, unsigned long long* d_counts);
 hipError_t launch_ieee_debug(const float* d_x, size_t n, const float* d_v, size_t m, float* d_sqrt, uint8_t* d_sqrt_short,
@@ -2342,6 +2343,44 @@ int rbrt_hip_glare(int device, void* stream, const float* d_radiance, uint32_t w
     G.a = G.intensity * inv;
     G.workspace = d_workspace, G.out_radiance = d_out_radiance, G.out_rgb8 = d_rgb8;
     HIP_TRY(launch_glare(G, static_cast<hipStream_t>(stream)));
+    return RBRT_OK;
+}
+
+// ---- Feature buffers (the rule: include/rbrt_hip.h; the kernel: features.inl) ---------------------------------------------------
+void rbrt_feature_opts_default(rbrt_feature_opts_t* f) {
+    if (!f) return;
+    f->samples = 4u;
+    f->reserved[0] = f->reserved[1] = f->reserved[2] = 0u;
+}
+
+// One launch on the caller's stream that reads the scene's arrays and writes the caller's buffers: no lane, no accumulator, no
+// tile table. The tree is the one the handle has now (fill_trace_params; a tree the background builder has finished is adopted
+// by the next render call, as for rbrt_hip_trace_rays).
+int rbrt_hip_render_features(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, const rbrt_render_opts_t* o, const rbrt_feature_opts_t* f,
+                             void* stream, float* d_albedo, float* d_normal, float* d_depth, float* d_coverage, int32_t* d_object) {
+    if (!s || !cam || !o || !f) return fail(RBRT_ERR_INVALID_ARG, "render_features: null argument");
+    if (f->samples == 0u || f->samples > 65536u) return fail(RBRT_ERR_INVALID_ARG, "render_features: samples must be 1..65536");
+    if (f->reserved[0] != 0u || f->reserved[1] != 0u || f->reserved[2] != 0u)
+        return fail(RBRT_ERR_INVALID_ARG, "render_features: reserved must be 0");
+    if (o->flags & RBRT_FLAG_COLLECT_STATS)
+        return fail(RBRT_ERR_INVALID_ARG, "render_features: RBRT_FLAG_COLLECT_STATS belongs to the render calls");
+    if (cam->img_width_pix == 0 || cam->img_height_pix == 0) return fail(RBRT_ERR_INVALID_ARG, "render_features: image has zero pixels");
+    if (o->tile_rank >= (o->tile_world ? o->tile_world : 1)) return fail(RBRT_ERR_INVALID_ARG, "render_features: tile_rank >= tile_world");
+    if (int rc = lens_invalid(cam, o)) return rc;
+    if (o->tile_world > 1u) return fail(RBRT_ERR_UNSUPPORTED, "render_features: tile_world > 1 (features are made of the whole frame)");
+    if (uint64_t(cam->img_width_pix) * cam->img_height_pix >= (1ull << 32))
+        return fail(RBRT_ERR_UNSUPPORTED, "render_features: image has 2^32 or more pixels");
+    if (!d_albedo && !d_normal && !d_depth && !d_coverage && !d_object) return RBRT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    TraceParams P;
+    fill_trace_params(s, cam, o, P);
+    P.tiles_x = (cam->img_width_pix + RBRT_TILE - 1) / RBRT_TILE, P.tiles_y = (cam->img_height_pix + RBRT_TILE - 1) / RBRT_TILE;
+    P.n_tiles = P.tiles_x * P.tiles_y;
+    FeatureParams F;
+    std::memset(&F, 0, sizeof(F));
+    F.samples = f->samples, F.inv_n = 1.0f / float(f->samples), F.stack_entries = s->stack_need;
+    F.albedo = d_albedo, F.normal = d_normal, F.depth = d_depth, F.coverage = d_coverage, F.object = d_object;
+    HIP_TRY(launch_features(P, F, static_cast<hipStream_t>(stream)));
     return RBRT_OK;
 }
 

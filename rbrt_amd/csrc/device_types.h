@@ -226,6 +226,19 @@ struct ResolveParams {
     uint32_t sample_base;  // index of the batch's first sample
 };
 
+// The feature buffers (include/rbrt_hip.h "Feature buffers"; features.inl): what one rbrt_hip_render_features call adds to the
+// TraceParams of its camera and options (of which it reads the camera, the lens, the distances, the seed and the scene).
+struct FeatureParams {
+    uint32_t samples;        // n
+    float inv_n;             // 1.0f / float(n)
+    uint32_t stack_entries;  // per-lane traversal stack entries in LDS: the handle's bvh_stack_need
+    float* albedo;           // [H][W][3] row-major; every output may be null
+    float* normal;           // [H][W][3]
+    float* depth;            // [H][W]
+    float* coverage;         // [H][W]
+    int32_t* object;         // [H][W]
+};
+
 // Adaptive sampling (include/rbrt_hip.h "Adaptive sampling"): what adaptive_lists_kernel, tile_error_kernel and
 // adaptive_finish_kernel need of one rbrt_hip_render_adaptive call. The arrays belong to the scene handle.
 struct AdaptiveParams {

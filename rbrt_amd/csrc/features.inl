@@ -1,0 +1,84 @@
+// features.inl — the feature buffers of the primary rays (include/rbrt_hip.h "Feature buffers"). Included by kernels.hip,
+// whose device functions it shares: the render's own streams and cameras (Rng, camera_target, lens_point), Scene::hit
+// (scene_hit) and the normal the scatter pass would use (mesh_shading_normal).
+//
+// One wave per 8x8 tile, lane p = (y % 8) * 8 + (x % 8): the primary rays of a tile are coherent, so the lanes of a wave walk
+// the same part of a tree. Each lane loops over its own n samples, which keeps the sums in sample order without atomics. The
+// traversal stack is per lane in dynamic LDS with stride 64, FeatureParams::stack_entries deep -- what the handle's deepest
+// tree can need, not kStackMax, so a CU holds as many waves as it has slots for. A lane beyond a ragged edge leaves at once:
+// nothing below exchanges data between lanes (the wave votes inside ieee_sqrt, normalize and lens_point only choose between
+// forms that give the same bits, and see the active lanes only).
+
+constexpr int kFeatureBlock = 64;
+
+__global__ __launch_bounds__(kFeatureBlock) void features_kernel(const TraceParams P, const FeatureParams F) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    uint32_t* stack = lds + threadIdx.x;
+    const uint32_t width = P.cam.img_width_pix, height = P.cam.img_height_pix;
+    const uint32_t ty = blockIdx.x / P.tiles_x, tx = blockIdx.x - ty * P.tiles_x;
+    const uint32_t p = threadIdx.x;
+    const uint32_t row = ty * RBRT_TILE + (p >> 3), col = tx * RBRT_TILE + (p & 7u);
+    if (row >= height || col >= width) return;
+    const V3 pos = mk(P.cam.position), center = mk(P.cam.img_center_point), right = mk(P.cam.right), up = mk(P.cam.up);
+    const uint32_t n_elem = P.n_spheres + P.n_elem_tris;
+    V3 a = mk(0.0f, 0.0f, 0.0f), nsum = mk(0.0f, 0.0f, 0.0f);
+    float z = 0.0f, c = 0.0f;
+    int32_t first_obj = -1;
+    for (uint32_t s = 0; s < F.samples; ++s) {
+        Rng rng;
+        rng.init(P.seed_key, row * width + col, s);
+        V3 o = pos, f = camera_target(center, right, up, P.cam.mm_per_pix_hor, P.cam.mm_per_pix_vert, width, height, row, col, rng);
+        if (P.thin_lens) {
+            const float lens[7] = {P.lens_u[0], P.lens_u[1], P.lens_u[2], P.lens_v[0], P.lens_v[1], P.lens_v[2], P.focus_scale};
+            lens_point(o, f, lens, rng);
+        }
+        const V3 d = normalize(f - o);
+        HitRec h;
+        LocalCounters lc = {0, 0, 0, 0, 0};
+        scene_hit<false>(P, o, d, stack, uint32_t(kFeatureBlock), h, lc);
+        if (s == 0) first_obj = h.obj;
+        V3 sa = mk(0.0f, 0.0f, 0.0f), sn = mk(0.0f, 0.0f, 0.0f);  // a miss: every channel adds +0
+        float sz = 0.0f, sc = 0.0f;
+        if (h.obj >= 0) {
+            const DevMaterial m = P.materials[h.obj];
+            sa = m.kind == RBRT_MAT_DIELECTRIC ? mk(1.0f, 1.0f, 1.0f) : mk(m.albedo);  // dielectric.rs:18: its attenuation
+            V3 g;
+            if (uint32_t(h.obj) < n_elem) {
+                const uint32_t desc = P.elems != nullptr ? P.elems[h.obj] : uint32_t(h.obj);
+                if (desc >> 31) g = mk(P.elem_tris[desc & 0x7FFFFFFFu].normal);  // triangle.rs:432
+                else g = (o + h.t * d) - mk(P.spheres[desc].center);             // sphere.rs:56
+            } else {
+                g = mesh_shading_normal(P.meshes[uint32_t(h.obj) - n_elem].normals, h.tri, o, d);
+            }
+            sn = normalize(g);  // not flipped towards the ray, no guard
+            sz = h.dist;
+            sc = 1.0f;
+        }
+        a = a + sa;
+        nsum = nsum + sn;
+        z = z + sz;
+        c = c + sc;
+    }
+    const size_t i = size_t(row) * width + col;
+    if (F.albedo) {
+        F.albedo[i * 3 + 0] = a.x * F.inv_n;
+        F.albedo[i * 3 + 1] = a.y * F.inv_n;
+        F.albedo[i * 3 + 2] = a.z * F.inv_n;
+    }
+    if (F.normal) {
+        F.normal[i * 3 + 0] = nsum.x * F.inv_n;
+        F.normal[i * 3 + 1] = nsum.y * F.inv_n;
+        F.normal[i * 3 + 2] = nsum.z * F.inv_n;
+    }
+    if (F.depth) F.depth[i] = z * F.inv_n;
+    if (F.coverage) F.coverage[i] = c * F.inv_n;
+    if (F.object) F.object[i] = first_obj;
+}
+
+// One single-wave workgroup per tile of the image, row-major; F.stack_entries * 64 words of LDS each.
+hipError_t launch_features(const TraceParams& P, const FeatureParams& F, hipStream_t stream) {
+    if (P.n_tiles == 0) return hipSuccess;
+    const size_t lds = size_t(F.stack_entries) * kFeatureBlock * sizeof(uint32_t);  // (a multiple of 256 bytes: the base stays 16-byte aligned)
+    hipLaunchKernelGGL(features_kernel, dim3(P.n_tiles), dim3(kFeatureBlock), lds, stream, P, F);
+    return hipGetLastError();
+}

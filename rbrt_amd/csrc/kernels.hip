@@ -1911,6 +1911,8 @@ hipError_t launch_shading_normals(const TraceParams& P, const float* rays, size_
     return hipGetLastError();
 }
 
+#include "features.inl"
+
 hipError_t launch_environment_lookup(const EnvTexel* nodes, uint32_t n_env, const float* dirs, size_t n, float* out_rgb, hipStream_t stream) {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(environment_lookup_kernel, dim3(uint32_t((n + kRaysBlock - 1) / kRaysBlock)), dim3(kRaysBlock), 0, stream, nodes,

@@ -15,6 +15,8 @@
 // luminance histogram, and a tone curve that rolls highlights off), --radiance FILE.pfm (the linear radiance, untransformed).
 // --glare INTENSITY with --glare-threshold T, --glare-levels L and --glare-spread S (glare: that share of the light above the
 // threshold is moved into a bright pixel's surroundings through a pyramid of blurs, in front of the display transform).
+// --features PREFIX with --feature-samples N (the feature buffers of the primary rays -- albedo, normal, depth, coverage -- as
+// four colour PFMs, made after the render on the same handle).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -91,6 +93,10 @@ void usage() {
         "      --glare-spread <s>           glare: weight of each coarser level against the one below it, 0 or more [default: 1]\n"
         "      --radiance <file.pfm>        also write the linear radiance there as a colour PFM: before glare, exposure and\n"
         "                                   tone curve, filtered if --denoise is on\n"
+        "      --features <prefix>          also write the feature buffers of the primary rays: <prefix>.albedo.pfm, .normal.pfm,\n"
+        "                                   .depth.pfm and .coverage.pfm (colour PFMs; depth and coverage as three equal\n"
+        "                                   channels). Cannot be combined with --gpus > 1\n"
+        "      --feature-samples <n>        features: primary rays per pixel, 1 to 65536 [default: --samples, at most 8]\n"
         "  -h, --help                       Print help\n"
         "  -V, --version                    Print version\n");
 }
@@ -177,6 +183,8 @@ int main(int argc, char** argv) {
     std::string radiance_file;
     std::optional<float> glare, glare_threshold, glare_spread;  // --glare turns the stage on; the others need it
     std::optional<uint32_t> glare_levels;
+    std::optional<std::string> features;  // the prefix of the four files
+    std::optional<uint32_t> feature_samples;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         std::string val;
@@ -373,6 +381,20 @@ int main(int argc, char** argv) {
             glare_levels = v;
         } else if (a == "--radiance") {
             radiance_file = value();
+        } else if (a == "--features") {
+            features = std::string(value());
+            if (features->empty()) {
+                std::fprintf(stderr, "error: invalid value '' for '--features' (expected the prefix of the four files it writes)\n");
+                return 2;
+            }
+        } else if (a == "--feature-samples") {
+            uint32_t v = 0;
+            u32(v);
+            if (v < 1u || v > 65536u) {
+                std::fprintf(stderr, "error: invalid value '%u' for '--feature-samples' (expected 1 to 65536)\n", v);
+                return 2;
+            }
+            feature_samples = v;
         } else if (a == "--shading") {
             const std::string v = value();
             if (v != "flat" && v != "smooth") {
@@ -426,6 +448,15 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "error: '%s' needs '--glare'\n", alone);
             return 2;
         }
+    }
+    if (features) {  // of the whole frame, on the render's handle: refused by name before anything is loaded
+        if (gpus > 1) {
+            std::fprintf(stderr, "error: '--features' cannot be combined with '--gpus > 1'\n");
+            return 2;
+        }
+    } else if (feature_samples) {
+        std::fprintf(stderr, "error: '--feature-samples' needs '--features'\n");
+        return 2;
     }
     if (white && tone_curve != RBRT_TONE_REINHARD) {
         std::fprintf(stderr, "error: '--white' needs '--tonemap reinhard' (the other curves have no white point)\n");
@@ -504,6 +535,7 @@ int main(int argc, char** argv) {
             cfg.tonemap = true, cfg.tonemap_curve = tone_curve, cfg.tonemap_exposure = exposure, cfg.tonemap_key = exposure_key;
             cfg.tonemap_white = white ? *white : 0.0f;
         }
+        if (features) cfg.features = true, cfg.feature_samples = feature_samples ? *feature_samples : std::max(1u, std::min(samples, 8u));
         rbrt::ImageBuffer img = rbrt::render_scene(cam, samples, scene, cfg);
         std::printf("Saving rendered image to %s\n", target.c_str());
         const auto t3 = clock::now();
@@ -511,6 +543,7 @@ int main(int argc, char** argv) {
         if (!sample_map.empty()) img.save_sample_map(sample_map);
         if (!noisy.empty()) img.save_noisy(noisy);
         if (!radiance_file.empty()) rbrt::write_pfm(radiance_file, img.radiance.data(), img.width, img.height);
+        if (features) img.save_features(*features);
         const auto t4 = clock::now();
         if (!report_path.empty()) {
             uint64_t triangles = 0;
@@ -554,6 +587,11 @@ int main(int argc, char** argv) {
                 str("tonemap", tone_curve == RBRT_TONE_LINEAR ? "none" : tone_curve == RBRT_TONE_REINHARD ? "reinhard" : "aces");
                 num("exposure", rep.tonemap_exposure, "%.9g"), num("white", rep.tonemap_white, "%.9g");
                 num("luminance_counted", rep.luminance_counted, "%.0f"), num("tonemap_ms", rep.tonemap_ms, "%.4f");
+            }
+            if (features) {  // the feature buffers: their samples a pixel and their time on the GPU (a part of gather_s)
+                char b[96];
+                std::snprintf(b, sizeof(b), "\"features\": {\"samples\": %u, \"ms\": %.4f}, ", cfg.feature_samples, rep.features_ms);
+                js += b;
             }
             // where the run's time went; the parts add up to total_s (other_s is what none of them covers: thread start,
             // checkpoint look-up, the report itself)

@@ -216,6 +216,23 @@ void ImageBuffer::save_noisy(const std::string& path) const {
     noisy.save(path);
 }
 
+// The feature buffers of a render with RenderConfig::features, through the colour PFM writer: depth and coverage are grey,
+// written as three equal channels (a reader of colour PFMs reads all four).
+void ImageBuffer::save_features(const std::string& prefix) const {
+    const size_t n = size_t(width) * height;
+    if (feature_albedo.size() != n * 3 || feature_normal.size() != n * 3 || feature_depth.size() != n || feature_coverage.size() != n)
+        throw Error("no feature buffers to save to " + prefix + ".*.pfm: the render made none");
+    write_pfm(prefix + ".albedo.pfm", feature_albedo.data(), width, height);
+    write_pfm(prefix + ".normal.pfm", feature_normal.data(), width, height);
+    std::vector<float> grey(n * 3);
+    const auto write_grey = [&](const char* name, const std::vector<float>& src) {
+        for (size_t i = 0; i < n; ++i) grey[3 * i] = grey[3 * i + 1] = grey[3 * i + 2] = src[i];
+        write_pfm(prefix + name, grey.data(), width, height);
+    };
+    write_grey(".depth.pfm", feature_depth);
+    write_grey(".coverage.pfm", feature_coverage);
+}
+
 void ImageBuffer::save(const std::string& path) const {
     std::string ext;
     const size_t dot = path.find_last_of('.');

@@ -253,6 +253,10 @@ struct ImageBuffer {
     std::vector<float> radiance;     // row-major fp32 pre-gamma mean (extra to the reference); linear whatever the display transform
     std::vector<uint8_t> sample_map; // an adaptive render: one byte per pixel, its tile's sample count * 255 / samples (else empty)
     std::vector<uint8_t> noisy_rgb;  // a denoised render with RenderConfig::keep_noisy: the unfiltered image, like rgb (else empty)
+    // a render with RenderConfig::features: the feature buffers of the primary rays, row-major (else empty)
+    std::vector<float> feature_albedo, feature_normal;  // 3 floats per pixel
+    std::vector<float> feature_depth, feature_coverage; // 1 float per pixel
+    void save_features(const std::string& prefix) const;  // PREFIX.albedo.pfm, .normal.pfm, .depth.pfm, .coverage.pfm (colour PFMs; grey as three equal channels)
     void save(const std::string& path) const;  // .png (8-bit RGB) or .ppm by extension
     void save_sample_map(const std::string& path) const;  // the sample map as a grey image, through the same writers
     void save_noisy(const std::string& path) const;       // the unfiltered image of a denoised render, through the same writers
@@ -287,6 +291,7 @@ struct RenderReport {
     uint32_t luminance_counted = 0;
     double tonemap_ms = 0.0;
     double glare_ms = 0.0;  // a render with glare (RenderConfig::glare): rbrt_hip_glare on the GPU, between two events
+    double features_ms = 0.0;  // a render with feature buffers (RenderConfig::features): rbrt_hip_render_features, between two events
 };
 
 struct RenderConfig {  // additions that the reference hard-codes or lacks
@@ -331,6 +336,11 @@ struct RenderConfig {  // additions that the reference hard-codes or lacks
     bool glare = false;
     float glare_intensity = 0.1f, glare_threshold = 1.0f, glare_spread = 1.0f;  // (rbrt_glare_opts_default)
     uint32_t glare_levels = 5;
+    // Feature buffers (rbrt_hip_render_features; the CLI's --features, --feature-samples): after the render, on the same
+    // handle, the albedo, normal, depth and coverage of the primary rays, feature_samples samples a pixel, into
+    // ImageBuffer::feature_*. One GPU: render_scene refuses the combination with more by name.
+    bool features = false;
+    uint32_t feature_samples = 4;  // 1..65536
 };
 // rbrt_lib::render_scene (lib.rs:75-79): blocks until the image is complete. Runs on the GPU(s)
 // through the C ABI; there is no CPU path.

@@ -333,6 +333,10 @@ Plan make_plan(const RenderConfig& cfg, const std::string& adaptive_by, const Ca
         if (cfg.pass_spp != 0) throw Error(adaptive_by + " cannot be combined with --pass-samples");
     }
     if (cfg.denoise && num_samples < 2) throw Error("--denoise needs at least 2 samples (each half image needs one)");
+    if (cfg.features) {  // (of the whole frame, on one handle: rbrt_hip.h "Feature buffers")
+        if (cfg.n_gpus > 1) throw Error("--features cannot be combined with --gpus > 1");
+        if (cfg.feature_samples == 0 || cfg.feature_samples > 65536u) throw Error("--feature-samples must be 1 to 65536");
+    }
     Plan p;
     const auto t_hip0 = std::chrono::steady_clock::now();
     p.n_dev = rbrt_hip_device_count();  // (the process's first HIP call: the runtime starts here)
@@ -482,6 +486,7 @@ struct Rank {
     void render_adaptive();
     void denoise();
     void render_passes();
+    void features();
     void gather_single();
     void gather_rccl();
     void gather_host();
@@ -516,6 +521,7 @@ void Rank::run() {
     if (hs && !err.failed()) err.lib_ok(rbrt_hip_scene_check(hs));
     sh.t_render[rank] = seconds_since(t_passes);
     const auto t_g = std::chrono::steady_clock::now();
+    if (world == 1 && cfg.features) features();
     if (world == 1) gather_single();
     else if (sh.use_rccl) gather_rccl();
     else gather_host();
@@ -636,6 +642,34 @@ void Rank::render_passes() {
         if (job.plan.stop_after > 0 && int(pass_no) + 1 == job.plan.stop_after && !last)
             err.set("stopped after pass " + std::to_string(job.plan.stop_after) + " (RBRT_TEST_STOP_AFTER_PASS)");
     }
+}
+
+// The feature buffers of the frame, after the render, on the same handle and stream: one call between two events, into memory of
+// this step's making, then to the image.
+void Rank::features() {
+    if (err.failed() || !npix) return;
+    const size_t n_pixels = size_t(img.width) * img.height;
+    rbrt_feature_opts_t fo;
+    rbrt_feature_opts_default(&fo);
+    fo.samples = cfg.feature_samples;
+    DeviceBuffer d_out;  // albedo, normal, depth, coverage: 3 + 3 + 1 + 1 floats a pixel
+    EventTimer timer;
+    if (!(d_out.alloc(n_pixels * 8 * sizeof(float), err, "hipMalloc(feature buffers)") && timer.create(err))) return;
+    float* const d_albedo = d_out.as<float>();
+    float *const d_normal = d_albedo + n_pixels * 3, *const d_depth = d_normal + n_pixels * 3, *const d_coverage = d_depth + n_pixels;
+    timer.start(stream.get(), err);
+    err.lib_ok(rbrt_hip_render_features(hs, &job.lens.cam, &o, &fo, stream.get(), d_albedo, d_normal, d_depth, d_coverage, nullptr));
+    timer.stop(stream.get(), err);
+    err.ok(hipStreamSynchronize(stream.get()), "feature buffers");
+    float ms = 0.0f;
+    if (timer.elapsed(&ms, err)) sh.rep.features_ms = ms;
+    if (err.failed()) return;
+    img.feature_albedo.resize(n_pixels * 3), img.feature_normal.resize(n_pixels * 3), img.feature_depth.resize(n_pixels), img.feature_coverage.resize(n_pixels);
+    err.ok(hipMemcpy(img.feature_albedo.data(), d_albedo, n_pixels * 3 * sizeof(float), hipMemcpyDeviceToHost), "download of the albedo");
+    err.ok(hipMemcpy(img.feature_normal.data(), d_normal, n_pixels * 3 * sizeof(float), hipMemcpyDeviceToHost), "download of the normals");
+    err.ok(hipMemcpy(img.feature_depth.data(), d_depth, n_pixels * sizeof(float), hipMemcpyDeviceToHost), "download of the depth");
+    err.ok(hipMemcpy(img.feature_coverage.data(), d_coverage, n_pixels * sizeof(float), hipMemcpyDeviceToHost), "download of the coverage");
+    if (hs && !err.failed()) err.lib_ok(rbrt_hip_scene_check(hs));  // (a NaN discriminant is counted here as in a render)
 }
 
 // Glare and the display transform on this rank's device, of the complete image that is d_src there.

@@ -20,7 +20,7 @@ BINDIR := rbrt_amd/bin
 
 all: $(LIBDIR)/librbrt_hip.so host oracle
 
-$(LIBDIR)/librbrt_hip.so: $(CSRC)/kernels.hip $(CSRC)/megakernel.inl $(CSRC)/features.inl $(CSRC)/api.cpp $(CSRC)/bvh.cpp $(CSRC)/bvh.h \
+$(LIBDIR)/librbrt_hip.so: $(CSRC)/kernels.hip $(CSRC)/megakernel.inl $(CSRC)/features.inl $(CSRC)/short_paths.inl $(CSRC)/api.cpp $(CSRC)/bvh.cpp $(CSRC)/bvh.h \
                           $(CSRC)/bvh_device.hip $(CSRC)/bvh_device.h $(CSRC)/denoise.hip $(CSRC)/tonemap.hip $(CSRC)/glare.hip \
                           $(CSRC)/device_types.h include/rbrt_hip.h include/rbrt_hip_debug.h
 	@mkdir -p $(LIBDIR)

@@ -189,6 +189,23 @@ int rbrt_hip_scene_launch_mix(rbrt_hip_scene_t* scene, uint32_t* n_full_grid, ui
  * caller has stopped issuing (api.cpp "Elastic launches"; lab knob RBRT_HELPERS=0|1|2: never, automatic, with every launch). */
 int rbrt_hip_scene_helper_launches(rbrt_hip_scene_t* scene, uint32_t* n);
 
+/* The short-path stage (DESIGN.md "The tile pass"; short_paths.inl): a streaming kernel in front of every trace launch that
+ * has tile tables finishes the two-ray paths of the tiles no camera ray of which can pass a mesh box, and the trace kernel
+ * skips those samples. The image is the same bits either way. For the handle's later launches, mode 0: never (the A/B and
+ * the tests need both); 1 (the default): in front of the launches that run beside others -- those of a stream of calls, and a
+ * call's sample batches but the last -- where the stage's own latency is hidden, not in front of a blocking frame, which
+ * would pay it in full; 2: in front of every launch; anything else is RBRT_ERR_INVALID_ARG. Counting launches
+ * (RBRT_FLAG_COLLECT_STATS), the rounds of rbrt_hip_render_adaptive, renders without the tile pass and scenes of more than
+ * seven meshes never have the stage. */
+int rbrt_hip_scene_set_short_paths(rbrt_hip_scene_t* scene, int mode);
+/* Test hook: the finished masks the stage wrote for the handle's LAST trace launch that had one, after waiting for the
+ * device. One word per chunk of 64 work items in hand-out order -- chunk = (position in the launch's tile work list) *
+ * (samples of the launch) + (sample within the launch), bit p = pixel p of the 8x8 tile -- a set bit: the stage finished
+ * that sample (or its pixel lies beyond a ragged edge), a clear one: the trace kernel traced it; the chunks of tiles the
+ * stage does not work on are zero. *n_chunks: the launch's chunks (0: no launch of the handle has had the stage); at most
+ * n words are written to out_masks (host array; may be NULL with n = 0). */
+int rbrt_hip_debug_short_masks(rbrt_hip_scene_t* scene, uint64_t* out_masks, size_t n, size_t* n_chunks);
+
 /* Where the wall-clock time of rbrt_hip_scene_create (and, for the one-shot rbrt_hip_render, of the whole call) went, in
  * seconds. The parts of create_s: hip_init_s + upload_s + bvh_build_s + lanes_s (+ a remainder of validation and small
  * allocations); of total_s: create_s + render_s + copy_s + destroy_s. bench.py's one_shot leg and the CLI's --report read it. */

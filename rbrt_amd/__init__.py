@@ -201,6 +201,21 @@ class HipScene:
         """Overlap consecutive trace launches over `depth` internal streams (rbrt_hip_scene_set_pipeline)."""
         abi.check(self._lib.rbrt_hip_scene_set_pipeline(self._h, int(depth)))
 
+    def set_short_paths(self, mode: int = 1):
+        """The short-path stage in front of the trace launches (rbrt_hip_scene_set_short_paths): 0 never, 1 automatic (the
+        launches that run beside others), 2 every launch; same image."""
+        abi.check(self._lib.rbrt_hip_scene_set_short_paths(self._h, int(mode)))
+
+    def short_masks(self):
+        """The finished masks of the last trace launch that had the short-path stage (rbrt_hip_debug_short_masks; test
+        hook): uint64 (n_chunks,), chunk = work-list position * samples of the launch + sample; empty if there was none."""
+        n = C.c_size_t()
+        abi.check(self._lib.rbrt_hip_debug_short_masks(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, np.uint64)
+        if n.value:
+            abi.check(self._lib.rbrt_hip_debug_short_masks(self._h, out.ctypes.data_as(C.POINTER(C.c_uint64)), n.value, C.byref(n)))
+        return out
+
     def set_timing(self, on: bool = True):
         abi.check(self._lib.rbrt_hip_scene_set_timing(self._h, int(on)))
 

@@ -300,6 +300,8 @@ DEBUG_SYMBOLS = {
     "rbrt_hip_debug_shading_normals": (C.c_int, [C.c_void_p, f32p, C.c_size_t, C.c_float, C.c_float, f32p]),
     "rbrt_hip_scene_adaptive_rounds": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32)]),
     "rbrt_hip_debug_environment": (C.c_int, [C.c_void_p, f32p, C.c_size_t, f32p]),
+    "rbrt_hip_scene_set_short_paths": (C.c_int, [C.c_void_p, C.c_int]),
+    "rbrt_hip_debug_short_masks": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(C.c_size_t)]),
 }
 
 

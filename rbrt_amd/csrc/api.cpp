@@ -32,6 +32,7 @@ size_t megakernel_lds_bytes(uint32_t stack_entries, uint32_t n_spheres, uint32_t
 int megakernel_occupancy_per_cu(size_t lds_bytes);
 hipError_t launch_primary_cull(const TraceParams& P, hipStream_t stream);
 hipError_t launch_sky_resolve(const TraceParams& P, const ResolveParams& R, hipStream_t stream);
+hipError_t launch_short_paths(const TraceParams& P, uint32_t n_waves, hipStream_t stream);  // short_paths.inl
 hipError_t launch_code_load(hipStream_t stream);
 hipError_t launch_resolve(const ResolveParams& R, hipStream_t stream);
 hipError_t launch_resolve_even(const TraceParams& P, const ResolveParams& R, uint32_t n_active_tiles, hipStream_t stream);
@@ -267,6 +268,7 @@ struct rbrt_hip_scene {
             float* d_sample_buf = nullptr;
             size_t sample_buf_bytes = 0;
             unsigned long long* d_work_counter = nullptr;
+            unsigned long long* d_short_masks = nullptr;  // TraceParams::short_masks: one word per 64 samples, behind the samples
             hipEvent_t ev_resolved = nullptr;
             bool in_use = false;  // ev_resolved has been recorded at least once
         } bufs[1];
@@ -393,6 +395,18 @@ struct rbrt_hip_scene {
     bool trace_create = false;      // RBRT_TRACE_CREATE=1 (lab): where scene_create's and scene_destroy's time went
     uint32_t tile_tail_div = 8;       // RBRT_TILE_TAIL_DIV (mode 4)
     uint32_t primary_cull = 1;    // RBRT_PRIMARY_CULL (0: no tile pass, the trace kernel renders every tile)
+    // The short-path stage (short_paths.inl) in front of trace launches that have tile tables (rbrt_hip_scene_set_short_paths):
+    // 0 never, 1 in front of the launches that run beside others (a stream's, a call's batches but the last), 2 always; and
+    // what rbrt_hip_debug_short_masks needs of the last launch that had one.
+    // (1 is the default: the stage finishes its samples more cheaply than the trace kernel but as a kernel of its own it has
+    // a tail of its own -- alone on the GPU it takes 0.49 ms of a 1024x768x50 frame and shortens the trace launch by 0.2; in
+    // a stream both tails are covered by the neighbours' work: profiles/short_paths_config2.txt)
+    uint32_t short_paths = 1;
+    struct LastShort {
+        const unsigned long long* d_masks = nullptr;
+        const uint32_t* d_lists = nullptr;
+        uint32_t batch = 0;
+    } last_short;
     uint32_t shade_rounds = 1;    // RBRT_SHADE_ROUNDS (rounds while work items are left; unbounded afterwards)
     uint32_t shade_cont_min = 8;  // RBRT_SHADE_CONT_MIN
     // stats / timing
@@ -610,6 +624,7 @@ hipError_t device_build_mesh(const rbrt_mesh_t& m, BvhTri* d_tris_out, uint32_t 
 uint32_t div_magic_of(uint32_t d) { return d <= 1 ? 0xFFFFFFFFu : uint32_t(0x100000000ull / d); }  // kernels.hip div_magic
 
 constexpr uint32_t kMaxPipeline = 8;
+constexpr uint32_t kShortMaxWaves = 1u << 20;  // grid of the short-path stage: a wave per tile of the rank, striding beyond this
 constexpr uint32_t kLanesAtCreate = 4;  // lanes made by scene_create (deeper pipelines: rbrt_hip_scene_set_pipeline makes the rest)
 constexpr size_t kMaxTimedLaunches = 4096;  // timing events are recycled per set_timing, never more than this many launches
 
@@ -1737,11 +1752,15 @@ int size_lane(rbrt_hip_scene* s, const CallPlan& c, uint32_t li) {
         if (B.d_sample_buf) {
             if (int rc = sync_lanes(s, c.stream)) return rc;
             HIP_TRY(hipFree(B.d_sample_buf));
-            B.d_sample_buf = nullptr, B.sample_buf_bytes = 0;
+            if (s->last_short.d_masks == B.d_short_masks) s->last_short = {};
+            B.d_sample_buf = nullptr, B.sample_buf_bytes = 0, B.d_short_masks = nullptr;
         }
+        // (behind the samples, in the same allocation: the short-path stage's word per chunk of 64 samples, 0.5 % on top)
         void* p = nullptr;
-        HIP_TRY(hipMalloc(&p, need));
+        const size_t chunk_bytes = 64u * 3u * sizeof(float);
+        HIP_TRY(hipMalloc(&p, need + need / chunk_bytes * sizeof(unsigned long long)));
         B.d_sample_buf = static_cast<float*>(p), B.sample_buf_bytes = need;
+        B.d_short_masks = reinterpret_cast<unsigned long long*>(static_cast<char*>(p) + need);
     }
     if (c.tile_pass && !c.round && (n_tiles > L.tile_cull_words || lists_need > L.tile_lists_words)) {
         if (L.tiles[0].d_cull || L.tiles[0].d_lists) {
@@ -1938,6 +1957,14 @@ int issue_batches(rbrt_hip_scene* s, const CallPlan& c, const rbrt_render_opts_t
         (grid < s->n_waves ? s->n_half_grid : s->n_full_grid) += 1;
         if (s->trace_launches)
             std::fprintf(stderr, "[rbrt_hip] trace launch: grid %u waves on %u CUs (%u waves per CU)\n", grid, s->n_cus, s->n_waves / s->n_cus);
+        // The short-path stage: on the launch's stream in front of it, behind the lane's previous resolve (it writes the
+        // sample buffer) and the tile tables. Not for counting launches (the stage keeps no counters), rounds of an adaptive
+        // call, a scene whose meshes the culling word has no bits for, or -- unless asked for -- a launch that runs alone.
+        if (S && !stats && s->n_meshes <= 7u && (s->short_paths == 2u || (s->short_paths == 1u && overlapped))) {
+            P.short_masks = B.d_short_masks;
+            HIP_TRY(launch_short_paths(P, std::min<uint32_t>(c.n_local, kShortMaxWaves), ts));  // (a wave per tile)
+            s->last_short.d_masks = B.d_short_masks, s->last_short.d_lists = P.tile_lists, s->last_short.batch = nb;
+        }
         if (piped) HIP_TRY(hipEventRecord(L.ev_ready, ts));  // (behind everything the launch waits for: a helper launch waits for this)
         HIP_TRY(launch_trace_megakernel(P, grid, stats, ts));
         if (piped && s->helpers_mode != 0u && !c.round) {  // (the launches of an adaptive round get no helpers: see rbrt_hip_render_adaptive)
@@ -2389,6 +2416,30 @@ int rbrt_hip_scene_adaptive_rounds(rbrt_hip_scene_t* s, uint32_t* active_tiles, 
     const auto& r = s->adaptive.round_active;
     *n_rounds = uint32_t(r.size());
     for (size_t i = 0; i < n && i < r.size(); ++i) active_tiles[i] = r[i];
+    return RBRT_OK;
+}
+
+int rbrt_hip_scene_set_short_paths(rbrt_hip_scene_t* s, int mode) {
+    if (!s) return fail(RBRT_ERR_INVALID_ARG, "set_short_paths: null scene");
+    if (mode < 0 || mode > 2) return fail(RBRT_ERR_INVALID_ARG, "set_short_paths: mode must be 0 (off), 1 (automatic) or 2 (every launch)");
+    std::lock_guard<std::mutex> watcher_lock(s->mu);  // (a helper launch copies the parameters of the launch it joins)
+    s->short_paths = uint32_t(mode);
+    return RBRT_OK;
+}
+
+int rbrt_hip_debug_short_masks(rbrt_hip_scene_t* s, uint64_t* out_masks, size_t n, size_t* n_chunks) {
+    if (!s || !n_chunks || (n != 0 && !out_masks)) return fail(RBRT_ERR_INVALID_ARG, "debug_short_masks: null argument");
+    HIP_TRY(hipSetDevice(s->device));
+    std::lock_guard<std::mutex> watcher_lock(s->mu);
+    *n_chunks = 0;
+    const auto& ls = s->last_short;
+    if (!ls.d_masks) return RBRT_OK;  // (no launch of this handle has had the stage)
+    HIP_TRY(hipDeviceSynchronize());
+    uint32_t n_work = 0;
+    HIP_TRY(hipMemcpy(&n_work, ls.d_lists, sizeof(n_work), hipMemcpyDeviceToHost));
+    *n_chunks = size_t(n_work) * ls.batch;
+    const size_t m = std::min(n, *n_chunks);
+    if (m != 0) HIP_TRY(hipMemcpy(out_masks, ls.d_masks, m * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return RBRT_OK;
 }
 

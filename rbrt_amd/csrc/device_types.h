@@ -203,6 +203,11 @@ struct TraceParams {
     // The handle's environment (rbrt_hip_scene_set_environment): (env_n + 1)^2 texels of 16 bytes; null: bg / the sky gradient
     const EnvTexel* env_nodes;
     uint32_t env_n;
+    // The short-path stage (short_paths.inl, run in front of the trace launch on its stream; null: off). One 64-bit word per
+    // chunk of 64 work items, indexed by chunk number (work item >> 6): bit p set = item p of the chunk is finished -- its
+    // sample is in sample_buf already, or its pixel lies beyond a ragged edge -- and the trace kernel hands it to nobody.
+    // The stage writes every word of the launch: zero for the chunks of tiles it does not work on.
+    unsigned long long* short_masks;
 };
 
 struct ResolveParams {

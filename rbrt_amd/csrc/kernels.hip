@@ -1912,6 +1912,7 @@ hipError_t launch_shading_normals(const TraceParams& P, const float* rays, size_
 }
 
 #include "features.inl"
+#include "short_paths.inl"
 
 hipError_t launch_environment_lookup(const EnvTexel* nodes, uint32_t n_env, const float* dirs, size_t n, float* out_rgb, hipStream_t stream) {
     if (n == 0) return hipSuccess;

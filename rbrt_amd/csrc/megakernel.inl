@@ -132,15 +132,35 @@ __device__ __forceinline__ uint32_t classify(const SceneLds& sc, int32_t obj, ui
 // the cheap shards ran dry first and the launch ended wherever the longest paths are.
 constexpr uint32_t kWorkChunk = 64;
 struct WorkSource {
-    uint32_t res_next = 0, res_end = 0;  // wave-uniform: the chunk being handed out (global item numbers)
+    // wave-uniform: the chunk being handed out. res_base is its first global item number, bit p of res_mask says that item
+    // res_base + p is still to be handed out: a fresh chunk starts with all 64 bits, less the items the short-path stage has
+    // finished already (TraceParams::short_masks)
+    uint32_t res_base = 0;
+    unsigned long long res_mask = 0;
     uint32_t shard = 0;                  // wave-uniform: shard to draw from next
-    uint32_t pend_shard = 0;             // wave-uniform: shard of the request in flight
     uint32_t n_dry = 0;                  // wave-uniform: consecutive shards found exhausted
     unsigned long long pend_base = 0;    // lane 0: result of the request in flight
     bool pending = false;                // wave-uniform
 
     uint32_t n_chunks = 0;               // wave-uniform: chunks of the launch (its work items / 64)
 
+    // Between two generation steps the wave-uniform state above lives in four LDS words, not in SGPRs the rest of the kernel
+    // would have to spill around (the product kernel's SGPR spills: 42 with the state in registers, 34 so): the first words
+    // of `helpers`, which shared traversals use only once the work has run out -- and by then no chunk is in hand (res_mask
+    // is 0 whenever next_chunk is asked and fails), `more` is false and all four words are zero again. The request in flight
+    // stays where the atomic returns it, in lane 0's registers.
+    __device__ __forceinline__ void load(const uint32_t* w) {
+        res_base = uni(w[0]);
+        res_mask = (unsigned long long)uni(w[1]) | ((unsigned long long)uni(w[2]) << 32);
+        const uint32_t st = uni(w[3]);
+        shard = st & 255u, n_dry = (st >> 8) & 255u, pending = (st >> 16) != 0u;
+    }
+    __device__ __forceinline__ void store(uint32_t* w, uint32_t lane, bool more) const {
+        if (lane == 0) {
+            w[0] = res_mask != 0ull ? res_base : 0u, w[1] = uint32_t(res_mask), w[2] = uint32_t(res_mask >> 32);
+            w[3] = more ? shard | (n_dry << 8) | (pending ? 1u << 16 : 0u) : 0u;
+        }
+    }
     __device__ __forceinline__ void init(uint32_t n_items) {
         n_chunks = n_items >> 6;  // (a multiple of the chunk size: 64 pixel slots per tile)
         uint32_t xcc;
@@ -168,8 +188,14 @@ struct WorkSource {
             else
                 pend_base = atomicAdd(P.work_counter + shard * kWorkCounterStride, (unsigned long long)kWorkChunk);
         }
-        pend_shard = shard;
-        pending = true;
+        pending = true;  // (`shard` stays what it is until the request has been used: only next_chunk moves it on)
+    }
+    // The items of the chunk that starts at item `lo` which are still to be traced: all of them, or those the short-path
+    // stage left (one load of the chunk's word, the same for every lane, brought to SGPRs like the counter's value below).
+    __device__ __forceinline__ unsigned long long open_mask(const TraceParams& P, uint32_t lo) const {
+        if (!P.short_masks) return ~0ull;
+        const unsigned long long done = P.short_masks[lo >> 6];
+        return ~((unsigned long long)uni(uint32_t(done)) | ((unsigned long long)uni(uint32_t(done >> 32)) << 32));
     }
     // Blocks until a chunk is in hand: [lo, hi) global items. Returns false when every shard is exhausted.
     template <bool HELPER>
@@ -178,7 +204,7 @@ struct WorkSource {
             prefetch<HELPER>(P, lane);
             // (lane 0's result, through SGPRs. next_chunk runs in wave-uniform control flow, so the first active lane IS lane 0.)
             const uint32_t l_lo = uni(uint32_t(pend_base)), l_hi = uni(uint32_t(pend_base >> 32));
-            const uint32_t ps = uni(pend_shard);
+            const uint32_t ps = uni(shard);  // the shard of the request
             pending = false;
             if (l_hi == 0u) {  // (a counter beyond 2^32 is far beyond every shard's end)
                 if (P.work_stripes) {  // (a power of two: api.cpp)
@@ -352,6 +378,7 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
     // work items are reserved from the global counter in chunks, the next chunk asynchronously
     WorkSource work;
     work.init(n_items);
+    work.store(helpers, lane, true);  // (behind the zeroing of `helpers` above)
     LocalCounters lc = {0, 0, 0, 0, 0};
     uint32_t n_samples_done = 0;
     uint32_t dg_pass[kNumStatus] = {0, 0, 0, 0, 0, 0}, dg_lanes[kNumStatus] = {0, 0, 0, 0, 0, 0};
@@ -882,20 +909,46 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
             // ---- new paths (cam.rs:64-82); work items come from the sharded global counters ----
             const uint64_t want = wballot(need_new && more_work);
             if (want) {
-                const uint32_t n_want = uint32_t(__popcll(want));
-                const uint32_t avail = work.res_end - work.res_next;
-                uint32_t new_lo = 0, new_hi = 0;
-                if (avail < n_want) {
-                    more_work = work.template next_chunk<HELPER>(P, lane, new_lo, new_hi);
-                    if (STATS && !more_work) dg_rt_workout = __builtin_amdgcn_s_memrealtime();
+                // The wanting lanes are served from the chunk in hand and, when that runs out, from further chunks: lane p
+                // of the wave speaks for item p of the chunk, and the k-th item still to be handed out goes -- through the
+                // triangle queue's LDS words, which only leaf rounds use -- to the k-th wanting lane not served yet. A chunk
+                // the short-path stage finished whole opens with an empty mask and costs its load and nothing else.
+                // (`left` wanting lanes are not served yet: they are the `left` first ones, and a step's items fill the queue
+                // downwards from word left - 1)
+                const uint32_t rk = lane_rank(want);
+                uint32_t left = uint32_t(__popcll(want));
+                work.load(helpers);
+                for (;;) {
+                    if (work.res_mask == 0ull) {
+                        uint32_t new_lo = 0, new_hi = 0;
+                        more_work = work.template next_chunk<HELPER>(P, lane, new_lo, new_hi);
+                        if (!more_work) {
+                            if (STATS) dg_rt_workout = __builtin_amdgcn_s_memrealtime();
 #if RBRT_REGION_TIMERS
-                    if (!more_work) rt_wall_workout = __builtin_amdgcn_s_memrealtime();
+                            rt_wall_workout = __builtin_amdgcn_s_memrealtime();
 #endif
+                            break;
+                        }
+                        // reserve the chunk after this one now; its result is not needed before this one is used up
+                        work.template prefetch<HELPER>(P, lane);
+                        work.res_base = new_lo;
+                        work.res_mask = work.open_mask(P, new_lo);  // (a chunk is 64 items: new_hi - new_lo, next_chunk)
+                        continue;
+                    }
+                    // (the mask is in SGPRs: a lane's own bit is a select on it, not a 64-bit shift in VGPRs)
+                    const uint32_t r = lane_rank(work.res_mask);
+                    const bool give = __builtin_amdgcn_inverse_ballot_w64(work.res_mask) && r < left;
+                    const uint64_t given = wballot(give);
+                    if (give) tq[left - 1u - r] = work.res_base + lane;
+                    work.res_mask &= ~given;
+                    left -= uint32_t(__popcll(given));
+                    if (left == 0u) break;
                 }
+                work.store(helpers, lane, more_work);
+                __syncthreads();
                 if (need_new) {
-                    const uint32_t rk = lane_rank(want);
-                    const uint32_t it = rk < avail ? work.res_next + rk : new_lo + (rk - avail);
-                    if (rk < avail || it < new_hi) {
+                    if (rk >= left) {
+                        const uint32_t it = tq[rk];
                         const uint32_t pp = it & 63u;
                         const uint32_t ts = it >> 6;
                         const uint32_t batch = gp[G_BATCH];
@@ -928,14 +981,6 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                         }
                     }
                 }
-                if (avail < n_want) {
-                    work.res_next = WorkSource::uni(new_lo + (n_want - avail) < new_hi ? new_lo + (n_want - avail) : new_hi);
-                    work.res_end = WorkSource::uni(new_hi);
-                } else {
-                    work.res_next = WorkSource::uni(work.res_next + n_want);
-                }
-                // reserve the next chunk now; its result is not needed before a later TERM pass
-                if (more_work && work.res_end - work.res_next < 64u) work.template prefetch<HELPER>(P, lane);
             }
         }
         RBRT_MARK(scatter_load);

@@ -65,7 +65,10 @@ extern "C" {
                               (rbrt_glare_opts_t, rbrt_glare_opts_default, rbrt_hip_glare_workspace_bytes and rbrt_hip_glare:
                               an added struct and entry points, detected by the symbol), nor the feature buffers
                               (rbrt_feature_opts_t, rbrt_feature_opts_default and rbrt_hip_render_features: an added struct
-                              and entry points, detected by the symbol) */
+                              and entry points, detected by the symbol), nor the guided denoiser
+                              (rbrt_guided_opts_t, rbrt_guided_opts_default, rbrt_hip_guided_workspace_bytes,
+                              rbrt_hip_denoise_guided and rbrt_hip_scene_denoise_guided: an added struct and entry points,
+                              detected by the symbol) */
 
 typedef enum rbrt_status {
     RBRT_OK = 0,
@@ -687,6 +690,86 @@ void rbrt_feature_opts_default(rbrt_feature_opts_t* opts); /* samples = 4 */
 int rbrt_hip_render_features(rbrt_hip_scene_t* scene, const rbrt_camera_t* cam, const rbrt_render_opts_t* opts,
                              const rbrt_feature_opts_t* features, void* stream, float* d_albedo, float* d_normal,
                              float* d_depth, float* d_coverage, int32_t* d_object);
+
+/* ---- Guided denoising: an edge-avoiding a-trous filter on the half images, guided by the feature buffers ---------------------
+ * No counterpart in the reference. The a-trous wavelet filter of Dammertz, Sewtz, Hanika and Lensch (2010): a 5 x 5 B-spline
+ * kernel whose taps move apart by a factor of two from level to level, every tap weighed by how well the two pixels agree in
+ * normal, depth, albedo and colour. Two additions: the albedo is divided out before the filter and multiplied back behind it
+ * (texture is not noise), and a per-pixel variance, estimated from the difference of the two half images and carried from level
+ * to level, scales the colour term, as the spatial part of SVGF does. The non-local-means filter above compares noisy patches
+ * with noisy patches; this one asks the feature buffers where the edges are.
+ *
+ * The rule. All arithmetic is float32, unfused, in the written order; / is correctly rounded; a constant is the float32
+ * nearest to the decimal written. "Inside" means inside the W x H image; a sum "from 0" starts at 0.0f and adds its terms one
+ * at a time in the stated order.
+ *   Inputs.  Half images A, B, float[H][W][3]; their mix wa, float[H][W] (NULL: 0.5 everywhere); albedo rho and normal N,
+ *     float[H][W][3]; depth z and coverage c, float[H][W]; levels L; the sigmas colour kc, normal kn, depth kz, albedo ka; flags.
+ *     eps = 1e-7f, floor = 0.01f. On the host, in float32: kc2 = kc * kc, kz2 = kz * kz, in = 1.0f / (kn * kn),
+ *     ia = 1.0f / (ka * ka).
+ *   Prepare, per pixel p and channel c.
+ *     m_c = max(rho_c + (1.0f - c), floor): a ray that hit nothing counts as albedo 1, so a background pixel is not divided by 0
+ *       and a partly covered pixel gets the mean of its samples' effective albedos.
+ *     u_c = m_c, or 1.0f with RBRT_GUIDED_NO_DEMODULATION (m guides the weights either way).
+ *     a_c = A_c / u_c;  b_c = B_c / u_c;  I_c = (a_c * wa) + (b_c * (1.0f - wa));  e_c = (a_c - b_c) squared.
+ *     V_c[p] = (sum / float(count)) * 0.25f, where sum runs over the 3 x 3 neighbourhood of p (dy outer -1..1, dx inner -1..1,
+ *       from 0) of e_c, only pixels inside are added and count is how many: the variance of the mean of two halves.
+ *   Level l = 0..L-1, step s = 1 << l. Every level reads the previous level's I and V and writes new ones, never in place.
+ *     h = (0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f). Taps: j outer -2..2, i inner -2..2, q = p + (j * s, i * s) (row, column);
+ *     a tap whose q is outside is skipped. hh = h[j + 2] * h[i + 2] (exact).
+ *       n = N[q] - N[p];       Dn = (((n_x * n_x) + (n_y * n_y)) + (n_z * n_z)) * in
+ *       a = m[q] - m[p];       Da = (((a_r * a_r) + (a_g * a_g)) + (a_b * a_b)) * ia
+ *       dz = z[q] - z[p];      Dz = (dz * dz) / (eps + (kz2 * (z[p] * z[q])))    (a relative depth: two zeros agree, a zero
+ *                                                                                 against a hit does not)
+ *       g_c = I_c[q] - I_c[p]; t_c = (g_c * g_c) / (eps + (kc2 * (V_c[p] + V_c[q])));  Dc = ((t_r + t_g) + t_b) * 0.33333334f
+ *       D = ((Dn + Dz) + Da) + Dc;   f = max(0, 1 - 0.25f * max(D, 0));   w = hh * ((f * f) * (f * f))
+ *     (the weight of "Denoising" above). Sums from 0 in tap order: num_c += w * I_c[q]; nv_c += (w * w) * V_c[q]; den += w.
+ *     The centre tap has D = 0 and w = 0.140625, so den > 0 always. I'_c = num_c / den; V'_c = nv_c / (den * den). The last
+ *     level's V' is not needed.
+ *   Output.  out_c = I_c * u_c, then the usual quantisation for rgb8.
+ * Finite inputs give no NaN when |A|, |B| <= 1e6, the features are finite and z >= 0. A non-finite input gives unspecified values
+ * in the pixels whose taps reach it; it never faults. */
+#define RBRT_GUIDED_NO_DEMODULATION 1u /* flags: filter the radiance itself (u = 1); the albedo still guides the weights */
+#define RBRT_GUIDED_MAX_LEVELS 6u
+typedef struct rbrt_guided_opts {
+    uint32_t levels;                      /* L, 1..RBRT_GUIDED_MAX_LEVELS */
+    float colour, normal, depth, albedo;  /* kc, kn, kz, ka: finite, > 0; larger lets more through */
+    uint32_t flags;                       /* RBRT_GUIDED_* */
+    uint32_t reserved[2];                 /* 0 */
+} rbrt_guided_opts_t;
+void rbrt_guided_opts_default(rbrt_guided_opts_t* opts); /* L = 5, kc = 2, kn = 0.35, kz = 0.05, ka = 0.1, flags 0 */
+
+/* Bytes of workspace rbrt_hip_denoise_guided needs for a width x height image: the packed guides ({N, z} and {m, 0}, 16 bytes a
+ * pixel each) and two sets of {I, 0} and {V, 0} planes, which the levels read and write in turns: 96 bytes a pixel. 0 for sizes
+ * the call refuses. */
+size_t rbrt_hip_guided_workspace_bytes(uint32_t width, uint32_t height);
+
+/* The filter on two half images and four feature buffers in DEVICE memory, all row-major (d_a, d_b, d_albedo, d_normal
+ * float[H][W][3]; d_wa, d_depth, d_coverage float[H][W]; d_wa NULL: 0.5 everywhere). Needs no scene. Writes the row-major result
+ * to d_radiance and / or its quantisation to d_rgb8 (either may be NULL; with both NULL nothing is launched). Asynchronous on
+ * `stream`. The call owns no device memory: d_workspace is the caller's, rbrt_hip_guided_workspace_bytes(width, height) bytes,
+ * 16-byte aligned; nothing is assumed about its contents, and calls on different streams need different workspaces. An
+ * output may be exactly d_a or d_b (the first kernel has consumed every input before an output is written); any other overlap
+ * is undefined.
+ * RBRT_ERR_INVALID_ARG, before the device is touched: d_a, d_b, d_albedo, d_normal, d_depth, d_coverage, opts or d_workspace
+ * NULL; width or height 0; levels 0 or above 6; a sigma that is not finite or <= 0; an unknown flag bit; a non-zero reserved
+ * word; a workspace that is not 16-byte aligned.
+ * RBRT_ERR_UNSUPPORTED: width * height >= 2^31. */
+int rbrt_hip_denoise_guided(int device, void* stream, const float* d_a, const float* d_b, const float* d_wa,
+                            const float* d_albedo, const float* d_normal, const float* d_depth, const float* d_coverage,
+                            uint32_t width, uint32_t height, const rbrt_guided_opts_t* opts, void* d_workspace,
+                            float* d_radiance, uint8_t* d_rgb8);
+
+/* The same filter on the image of the handle's last rbrt_hip_render_adaptive call: A, B and wa are made from that call's sums
+ * into the handle's half-image memory exactly as rbrt_hip_scene_denoise makes them; the feature buffers (of the same camera:
+ * rbrt_hip_render_features) and the workspace are the caller's. The two calls do not disturb each other. Either output may be
+ * NULL; with both NULL the call checks its arguments and the handle's last render and then does nothing: no device is set, no
+ * memory of the handle grows, nothing is launched. The threading rule of rbrt_hip_render_device holds.
+ * RBRT_ERR_INVALID_ARG, before the device is touched: scene NULL; what rbrt_hip_denoise_guided refuses in opts, the feature
+ * pointers and the workspace; no adaptive render on the handle yet; the last one had opts->spp < 2.
+ * RBRT_ERR_UNSUPPORTED: the last adaptive render had tile_world > 1. */
+int rbrt_hip_scene_denoise_guided(rbrt_hip_scene_t* scene, const rbrt_guided_opts_t* opts, void* stream,
+                                  const float* d_albedo, const float* d_normal, const float* d_depth, const float* d_coverage,
+                                  void* d_workspace, float* d_radiance, uint8_t* d_rgb8);
 
 /* De-interleave gathered per-rank packed tile buffers (concatenated rank 0..world-1, each
  * rbrt_hip_packed_pixels(...)*3 floats, device memory) into a row-major float[H][W][3] device

@@ -57,6 +57,17 @@ int rbrt_hip_scene_adaptive_rounds(rbrt_hip_scene_t* scene, uint32_t* active_til
  * sizes around it are where that kernel's edge handling changes (tests/test_denoise_gpu.py). */
 #define RBRT_DENOISE_TILE 16u
 
+/* Edge in pixels of the square pixel tile one workgroup of the guided denoiser's level kernel covers
+ * (rbrt_amd/csrc/guided.hip): image sizes around it are where a workgroup is added (tests/test_guided_gpu.py). */
+#define RBRT_GUIDED_TILE 16u
+/* The levels of that kernel whose step is at most this stage their tile and its halo in LDS; the levels above read global
+ * memory. Both forms compute the same bits. rbrt_hip_debug_guided_staging(0..4) changes it for the process and returns the
+ * value in force, (-1) only asks (tools/guided_cost.py measures each; tests/test_guided_gpu.py compares their bits). The
+ * switch is the process's, not a handle's or a stream's: every call of the filter reads it once when it starts, so changing it
+ * while other threads call the filter changes only which form their next calls launch, never a result. */
+#define RBRT_GUIDED_STAGED_MAX_STEP 4u
+int rbrt_hip_debug_guided_staging(int max_step);
+
 /* The display transform's kernels (rbrt_amd/csrc/tonemap.hip): the pixels one workgroup takes per stride of its grid, and the
  * cap of that grid. Pixel counts around BLOCK_PIXELS, and around MAX_BLOCKS * BLOCK_PIXELS where a workgroup starts to stride a
  * second time, are where those kernels' paths change (tests/test_tonemap_gpu.py). */

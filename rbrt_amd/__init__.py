@@ -157,6 +157,17 @@ class HipScene:
         abi.check(self._lib.rbrt_hip_scene_denoise(self._h, C.byref(d), C.c_void_p(stream or 0), C.c_void_p(d_radiance or 0),
                                                    C.c_void_p(d_rgb8 or 0), C.c_void_p(d_half_a or 0), C.c_void_p(d_half_b or 0)))
 
+    def denoise_guided(self, d_albedo: int, d_normal: int, d_depth: int, d_coverage: int, d_workspace: int,
+                       d_radiance: int | None = None, d_rgb8: int | None = None, opts: abi.GuidedOpts | None = None,
+                       stream: int | None = None):
+        """The guided filter on the last render_adaptive call's image (rbrt_hip_scene_denoise_guided): the feature buffers are
+        render_features' of the same camera, d_workspace guided_workspace_bytes(W, H) bytes of device memory. `opts`:
+        guided_opts(...), None for the library's defaults. Asynchronous on `stream`."""
+        g = opts if opts is not None else guided_opts()
+        abi.check(self._lib.rbrt_hip_scene_denoise_guided(self._h, C.byref(g), C.c_void_p(stream or 0), C.c_void_p(d_albedo or 0),
+                                                          C.c_void_p(d_normal or 0), C.c_void_p(d_depth or 0), C.c_void_p(d_coverage or 0),
+                                                          C.c_void_p(d_workspace or 0), C.c_void_p(d_radiance or 0), C.c_void_p(d_rgb8 or 0)))
+
     def render_features(self, cam: abi.Camera, opts: abi.RenderOpts, samples: int | None = None, d_albedo: int | None = None,
                         d_normal: int | None = None, d_depth: int | None = None, d_coverage: int | None = None,
                         d_object: int | None = None, lens=None, stream: int | None = None, reserved=(0, 0, 0)):
@@ -423,6 +434,48 @@ def denoise_halves(device: int, d_a: int, d_b: int, d_wa: int | None, width: int
     abi.check(load_hip().rbrt_hip_denoise_halves(device, C.c_void_p(stream or 0), C.c_void_p(d_a), C.c_void_p(d_b),
                                                  C.c_void_p(d_wa or 0), width, height, C.byref(d), C.c_void_p(d_radiance or 0),
                                                  C.c_void_p(d_rgb8 or 0)))
+
+
+def guided_opts(levels: int | None = None, colour: float | None = None, normal: float | None = None, depth: float | None = None,
+                albedo: float | None = None, flags: int | None = None, reserved=(0, 0)) -> abi.GuidedOpts:
+    """rbrt_guided_opts_default (5 levels, colour 2, normal 0.35, depth 0.05, albedo 0.1, flags 0), with the parameters that are
+    given put in."""
+    g = abi.GuidedOpts()
+    load_hip().rbrt_guided_opts_default(C.byref(g))
+    for name, value, kind in (("levels", levels, int), ("colour", colour, float), ("normal", normal, float), ("depth", depth, float),
+                              ("albedo", albedo, float), ("flags", flags, int)):
+        if value is not None:
+            setattr(g, name, kind(value))
+    g.reserved[0], g.reserved[1] = int(reserved[0]), int(reserved[1])
+    return g
+
+
+def guided_workspace_bytes(width: int, height: int) -> int:
+    """rbrt_hip_guided_workspace_bytes: the device memory denoise_guided() needs; 0 for sizes it refuses."""
+    return int(load_hip().rbrt_hip_guided_workspace_bytes(width, height))
+
+
+def denoise_guided(device: int, d_a: int, d_b: int, d_wa: int | None, d_albedo: int, d_normal: int, d_depth: int, d_coverage: int,
+                   width: int, height: int, d_workspace: int, d_radiance: int | None, d_rgb8: int | None = None,
+                   opts: abi.GuidedOpts | None = None, stream: int | None = None):
+    """The feature-guided a-trous filter on two half images in device memory (rbrt_hip_denoise_guided): d_a, d_b, d_albedo,
+    d_normal row-major float32 [H, W, 3]; d_wa (None: 0.5 everywhere), d_depth, d_coverage float32 [H, W]; d_workspace
+    guided_workspace_bytes(width, height) bytes, 16-byte aligned. `opts`: guided_opts(...), None for the library's defaults.
+    An output may be d_a or d_b. Asynchronous on `stream`."""
+    g = opts if opts is not None else guided_opts()
+    abi.check(load_hip().rbrt_hip_denoise_guided(device, C.c_void_p(stream or 0), C.c_void_p(d_a or 0), C.c_void_p(d_b or 0),
+                                                 C.c_void_p(d_wa or 0), C.c_void_p(d_albedo or 0), C.c_void_p(d_normal or 0),
+                                                 C.c_void_p(d_depth or 0), C.c_void_p(d_coverage or 0), width, height, C.byref(g),
+                                                 C.c_void_p(d_workspace or 0), C.c_void_p(d_radiance or 0), C.c_void_p(d_rgb8 or 0)))
+
+
+def guided_staging(max_step: int = -1) -> int:
+    """rbrt_hip_debug_guided_staging (test and measurement hook): the levels with a step of at most `max_step` (0..4) stage
+    their tile in LDS; -1 asks. Returns the value in force."""
+    rc = int(load_hip().rbrt_hip_debug_guided_staging(int(max_step)))
+    if rc < 0:
+        abi.check(rc)
+    return rc
 
 
 def tonemap_opts(curve: int | None = None, exposure: float | None = None, key: float | None = None,

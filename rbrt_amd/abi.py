@@ -40,6 +40,8 @@ TONEMAP_RESULT_OFFSET = TONEMAP_BINS * 4
 TONEMAP_WORKSPACE_BYTES = TONEMAP_RESULT_OFFSET + 32
 TONEMAP_BLOCK_PIXELS = 1024  # rbrt_hip_debug.h: pixels a workgroup of the transform's kernels takes per stride
 TONEMAP_MAX_BLOCKS = 512     # ... and the cap of their grid
+GUIDED_NO_DEMODULATION = 1   # rbrt_hip.h: RBRT_GUIDED_NO_DEMODULATION
+GUIDED_MAX_LEVELS = 6        # rbrt_hip.h: the most levels of the guided denoiser
 GLARE_MAX_LEVELS = 8         # rbrt_hip.h: the most levels of the glare stage's pyramid
 GLARE_TILE_W = 16            # rbrt_hip_debug.h: the tile of a pyramid level one workgroup of the REDUCE kernel makes
 GLARE_TILE_H = 16
@@ -183,6 +185,11 @@ class FeatureOpts(C.Structure):  # rbrt_feature_opts_t
     _fields_ = [("samples", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
+class GuidedOpts(C.Structure):  # rbrt_guided_opts_t
+    _fields_ = [("levels", C.c_uint32), ("colour", C.c_float), ("normal", C.c_float), ("depth", C.c_float), ("albedo", C.c_float),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 class Environment(C.Structure):  # rbrt_environment_t
     """An octahedral radiance map of (n + 1) x (n + 1) nodes: `nodes` points at host float32 [n + 1][n + 1][3]."""
     _fields_ = [("n", C.c_uint32), ("reserved", C.c_uint32), ("nodes", f32p)]
@@ -265,9 +272,16 @@ HIP_SYMBOLS = {
     "rbrt_feature_opts_default": (None, [C.POINTER(FeatureOpts)]),
     "rbrt_hip_render_features": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderOpts), C.POINTER(FeatureOpts), C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rbrt_guided_opts_default": (None, [C.POINTER(GuidedOpts)]),
+    "rbrt_hip_guided_workspace_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "rbrt_hip_denoise_guided": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(GuidedOpts), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rbrt_hip_scene_denoise_guided": (C.c_int, [C.c_void_p, C.POINTER(GuidedOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 # ... and include/rbrt_hip_debug.h (test hooks and diagnostics, same library)
 DEBUG_SYMBOLS = {
+    "rbrt_hip_debug_guided_staging": (C.c_int, [C.c_int]),
     "rbrt_hip_scene_last_batching": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "rbrt_hip_trace_rays": (C.c_int, [C.c_void_p, f32p, C.c_size_t, C.c_float, C.c_float, f32p, i32p, i32p, f32p]),
     "rbrt_hip_selftest_ieee": (C.c_int, [C.c_uint64, C.c_size_t, C.POINTER(C.c_uint64)]),

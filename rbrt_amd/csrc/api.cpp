@@ -43,6 +43,7 @@ hipError_t launch_denoise(const DenoiseParams& D, hipStream_t stream);          
 hipError_t launch_denoise_halves(const DenoiseHalvesParams& Q, hipStream_t stream);
 hipError_t launch_tonemap(const TonemapParams& T, hipStream_t stream);                 // tonemap.hip
 hipError_t launch_glare(const GlareParams& G, hipStream_t stream);                     // glare.hip
+hipError_t launch_guided(const GuidedParams& G, uint32_t staged_max_step, hipStream_t stream);  // guided.hip
 hipError_t launch_unpack(const float* gathered, uint32_t width, uint32_t height, uint32_t world,
                          size_t rank_stride_pixels, float* out_radiance, uint8_t* out_rgb8, hipStream_t stream);
 hipError_t launch_trace_rays(const TraceParams& P, const float* rays, size_t n, float* out_t, int32_t* out_obj,
@@ -2256,18 +2257,22 @@ int rbrt_hip_denoise_halves(int device, void* stream, const float* d_a, const fl
     return RBRT_OK;
 }
 
-int rbrt_hip_scene_denoise(rbrt_hip_scene_t* s, const rbrt_denoise_opts_t* d, void* stream_v, float* d_radiance, uint8_t* d_rgb8,
-                           float* d_half_a, float* d_half_b) {
-    if (!s || !d) return fail(RBRT_ERR_INVALID_ARG, "scene_denoise: null argument");
-    if (int rc = check_denoise_opts(d)) return rc;
-    auto& S = s->adaptive;
-    if (!S.last.any) return fail(RBRT_ERR_INVALID_ARG, "scene_denoise: no adaptive render on this scene yet");
+// What both handle calls refuse in the last adaptive render, under the name of the call.
+static int check_last_adaptive(rbrt_hip_scene_t* s, const char* call) {
+    const auto& S = s->adaptive;
+    const std::string c(call);
+    if (!S.last.any) return fail(RBRT_ERR_INVALID_ARG, c + ": no adaptive render on this scene yet");
     if (S.last.world > 1u)
-        return fail(RBRT_ERR_UNSUPPORTED, "scene_denoise: the last adaptive render had tile_world > 1 (a rank lacks its neighbours' pixels)");
-    if (S.last.spp < 2u) return fail(RBRT_ERR_INVALID_ARG, "scene_denoise: the last adaptive render had spp < 2 (a half would be empty)");
-    if (!S.last.complete) return fail(RBRT_ERR_INVALID_ARG, "scene_denoise: the last adaptive render did not complete");
+        return fail(RBRT_ERR_UNSUPPORTED, c + ": the last adaptive render had tile_world > 1 (a rank lacks its neighbours' pixels)");
+    if (S.last.spp < 2u) return fail(RBRT_ERR_INVALID_ARG, c + ": the last adaptive render had spp < 2 (a half would be empty)");
+    if (!S.last.complete) return fail(RBRT_ERR_INVALID_ARG, c + ": the last adaptive render did not complete");
+    return RBRT_OK;
+}
+
+// The handle's half images A, B and their mix wa from the sums of its last adaptive call (grown on demand), on `stream`.
+static int scene_halves(rbrt_hip_scene_t* s, hipStream_t stream, float* d_half_a, float* d_half_b) {
+    auto& S = s->adaptive;
     HIP_TRY(hipSetDevice(s->device));
-    const hipStream_t stream = static_cast<hipStream_t>(stream_v);
     const size_t npix = size_t(S.last.width) * S.last.height;
     {
         std::lock_guard<std::mutex> watcher_lock(s->mu);  // (dev_alloc)
@@ -2284,8 +2289,99 @@ int rbrt_hip_scene_denoise(rbrt_hip_scene_t* s, const rbrt_denoise_opts_t* d, vo
     Q.width = S.last.width, Q.height = S.last.height, Q.tiles_x = S.last.tiles_x;
     Q.a = S.d_half_a, Q.b = S.d_half_b, Q.wa = S.d_wa, Q.out_a = d_half_a, Q.out_b = d_half_b;
     HIP_TRY(launch_denoise_halves(Q, stream));
+    return RBRT_OK;
+}
+
+int rbrt_hip_scene_denoise(rbrt_hip_scene_t* s, const rbrt_denoise_opts_t* d, void* stream_v, float* d_radiance, uint8_t* d_rgb8,
+                           float* d_half_a, float* d_half_b) {
+    if (!s || !d) return fail(RBRT_ERR_INVALID_ARG, "scene_denoise: null argument");
+    if (int rc = check_denoise_opts(d)) return rc;
+    if (int rc = check_last_adaptive(s, "scene_denoise")) return rc;
+    auto& S = s->adaptive;
+    const hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    if (int rc = scene_halves(s, stream, d_half_a, d_half_b)) return rc;
     if (!d_radiance && !d_rgb8) return RBRT_OK;
     HIP_TRY(launch_denoise(denoise_params(S.d_half_a, S.d_half_b, S.d_wa, S.last.width, S.last.height, d, d_radiance, d_rgb8), stream));
+    return RBRT_OK;
+}
+
+// ---- Guided denoising (the rule: include/rbrt_hip.h; the kernels: guided.hip) ------------------------------------------------
+void rbrt_guided_opts_default(rbrt_guided_opts_t* o) {
+    if (!o) return;
+    o->levels = 5u, o->colour = 2.0f, o->normal = 0.35f, o->depth = 0.05f, o->albedo = 0.1f, o->flags = 0u;
+    o->reserved[0] = o->reserved[1] = 0u;
+}
+
+// The levels whose step is at most this stage their tile in LDS; the others read global memory (profiles/guided_config2.txt
+// has the comparison). rbrt_hip_debug_guided_staging changes it for the process.
+static std::atomic<uint32_t> g_guided_staged_max_step{RBRT_GUIDED_STAGED_MAX_STEP};
+
+int rbrt_hip_debug_guided_staging(int max_step) {
+    if (max_step < -1 || max_step > 4) return fail(RBRT_ERR_INVALID_ARG, "debug_guided_staging: max_step must be -1 (ask) or 0..4");
+    if (max_step >= 0) g_guided_staged_max_step.store(uint32_t(max_step));
+    return int(g_guided_staged_max_step.load());
+}
+
+size_t rbrt_hip_guided_workspace_bytes(uint32_t width, uint32_t height) {
+    if (width == 0u || height == 0u || uint64_t(width) * height >= (1ull << 31)) return 0;
+    return size_t(width) * height * 96u;  // (the layout of launch_guided: six planes of one float4 a pixel)
+}
+
+static int check_guided_args(const rbrt_guided_opts_t* g, const float* d_albedo, const float* d_normal, const float* d_depth,
+                             const float* d_coverage, const void* d_workspace) {
+    if (!g || !d_albedo || !d_normal || !d_depth || !d_coverage || !d_workspace) return fail(RBRT_ERR_INVALID_ARG, "denoise_guided: null argument");
+    if (g->levels == 0u || g->levels > RBRT_GUIDED_MAX_LEVELS) return fail(RBRT_ERR_INVALID_ARG, "denoise_guided: levels must be 1..6");
+    for (const float k : {g->colour, g->normal, g->depth, g->albedo})
+        if (!std::isfinite(k) || !(k > 0.0f)) return fail(RBRT_ERR_INVALID_ARG, "denoise_guided: colour, normal, depth and albedo must be finite and > 0");
+    if (g->flags & ~RBRT_GUIDED_NO_DEMODULATION) return fail(RBRT_ERR_INVALID_ARG, "denoise_guided: unknown flag bit");
+    if (g->reserved[0] != 0u || g->reserved[1] != 0u) return fail(RBRT_ERR_INVALID_ARG, "denoise_guided: reserved must be 0");
+    if (reinterpret_cast<uintptr_t>(d_workspace) % 16u != 0u) return fail(RBRT_ERR_INVALID_ARG, "denoise_guided: the workspace must be 16-byte aligned");
+    return RBRT_OK;
+}
+
+static GuidedParams guided_params(const float* a, const float* b, const float* wa, const float* d_albedo, const float* d_normal,
+                                  const float* d_depth, const float* d_coverage, uint32_t width, uint32_t height,
+                                  const rbrt_guided_opts_t* g, void* d_workspace, float* d_radiance, uint8_t* d_rgb8) {
+    GuidedParams G;
+    std::memset(&G, 0, sizeof(G));
+    G.a = a, G.b = b, G.wa = wa, G.albedo = d_albedo, G.normal = d_normal, G.depth = d_depth, G.coverage = d_coverage;
+    G.width = width, G.height = height, G.levels = g->levels, G.flags = g->flags;
+    // the rule's host-side values, in float, one operation a statement (this file is compiled with -ffp-contract=off)
+    const float kn2 = g->normal * g->normal, ka2 = g->albedo * g->albedo;
+    G.kc2 = g->colour * g->colour, G.kz2 = g->depth * g->depth;
+    G.in = 1.0f / kn2, G.ia = 1.0f / ka2;
+    G.workspace = d_workspace, G.out_radiance = d_radiance, G.out_rgb8 = d_rgb8;
+    return G;
+}
+
+int rbrt_hip_denoise_guided(int device, void* stream, const float* d_a, const float* d_b, const float* d_wa, const float* d_albedo,
+                            const float* d_normal, const float* d_depth, const float* d_coverage, uint32_t width, uint32_t height,
+                            const rbrt_guided_opts_t* g, void* d_workspace, float* d_radiance, uint8_t* d_rgb8) {
+    if (!d_a || !d_b) return fail(RBRT_ERR_INVALID_ARG, "denoise_guided: null argument");
+    if (int rc = check_guided_args(g, d_albedo, d_normal, d_depth, d_coverage, d_workspace)) return rc;
+    if (width == 0u || height == 0u) return fail(RBRT_ERR_INVALID_ARG, "denoise_guided: width and height must be >= 1");
+    if (uint64_t(width) * height >= (1ull << 31)) return fail(RBRT_ERR_UNSUPPORTED, "denoise_guided: 2^31 or more pixels");
+    if (int rc = ensure_device(device)) return rc;
+    if (!d_radiance && !d_rgb8) return RBRT_OK;
+    HIP_TRY(launch_guided(guided_params(d_a, d_b, d_wa, d_albedo, d_normal, d_depth, d_coverage, width, height, g, d_workspace, d_radiance, d_rgb8),
+                          g_guided_staged_max_step.load(), static_cast<hipStream_t>(stream)));
+    return RBRT_OK;
+}
+
+int rbrt_hip_scene_denoise_guided(rbrt_hip_scene_t* s, const rbrt_guided_opts_t* g, void* stream_v, const float* d_albedo,
+                                  const float* d_normal, const float* d_depth, const float* d_coverage, void* d_workspace,
+                                  float* d_radiance, uint8_t* d_rgb8) {
+    if (!s) return fail(RBRT_ERR_INVALID_ARG, "scene_denoise_guided: null argument");
+    if (int rc = check_guided_args(g, d_albedo, d_normal, d_depth, d_coverage, d_workspace)) return rc;
+    if (int rc = check_last_adaptive(s, "scene_denoise_guided")) return rc;
+    auto& S = s->adaptive;
+    if (uint64_t(S.last.width) * S.last.height >= (1ull << 31)) return fail(RBRT_ERR_UNSUPPORTED, "scene_denoise_guided: 2^31 or more pixels");
+    if (!d_radiance && !d_rgb8) return RBRT_OK;  // (no half image to hand out either: nothing to do)
+    const hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    if (int rc = scene_halves(s, stream, nullptr, nullptr)) return rc;
+    HIP_TRY(launch_guided(guided_params(S.d_half_a, S.d_half_b, S.d_wa, d_albedo, d_normal, d_depth, d_coverage, S.last.width, S.last.height, g,
+                                        d_workspace, d_radiance, d_rgb8),
+                          g_guided_staged_max_step.load(), stream));
     return RBRT_OK;
 }
 

@@ -314,4 +314,22 @@ struct GlareParams {
     uint8_t* out_rgb8;        // [height][width][3], may be null
 };
 
+// The guided denoiser (include/rbrt_hip.h "Guided denoising"; guided.hip): one rbrt_hip_denoise_guided call.
+struct GuidedParams {
+    const float* a;          // [H][W][3] the two half images
+    const float* b;
+    const float* wa;         // [H][W] the share of `a`, or null: 0.5 everywhere
+    const float* albedo;     // [H][W][3]
+    const float* normal;     // [H][W][3]
+    const float* depth;      // [H][W]
+    const float* coverage;   // [H][W]
+    uint32_t width, height;  // width * height < 2^31
+    uint32_t levels;         // 1..RBRT_GUIDED_MAX_LEVELS
+    uint32_t flags;          // RBRT_GUIDED_*
+    float kc2, kz2, in, ia;  // the rule's host-side values
+    void* workspace;         // six planes of width * height float4: {N, z}, {m, 0}, then {I, 0} and {V, 0} twice
+    float* out_radiance;     // [H][W][3], may be null, `a` or `b`
+    uint8_t* out_rgb8;       // [H][W][3], may be null
+};
+
 }  // namespace rbrt

@@ -16,7 +16,9 @@
 // --glare INTENSITY with --glare-threshold T, --glare-levels L and --glare-spread S (glare: that share of the light above the
 // threshold is moved into a bright pixel's surroundings through a pyramid of blurs, in front of the display transform).
 // --features PREFIX with --feature-samples N (the feature buffers of the primary rays -- albedo, normal, depth, coverage -- as
-// four colour PFMs, made after the render on the same handle).
+// four colour PFMs, made after the render on the same handle). --denoise-guided with --guided-levels L, --guided-colour K,
+// --guided-normal K, --guided-depth K, --guided-albedo K and --guided-no-demodulation (the target file gets the edge-avoiding
+// a-trous filter of the render's two half images, guided by those feature buffers).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -79,6 +81,17 @@ void usage() {
         "      --denoise-patch <p>          denoise: radius of the compared patches, 0 to 4 [default: 3]\n"
         "      --denoise-strength <k>       denoise: filter strength, above 0; larger smooths more [default: 0.7]\n"
         "      --noisy <file>               denoise: also write the unfiltered image there (same formats as the target file)\n"
+        "      --denoise-guided             filter the image with the feature buffers as guides: an edge-avoiding a-trous filter\n"
+        "                                   on the images of the even and the odd samples, which smooths only where albedo,\n"
+        "                                   normal and depth of the primary rays agree. Renders like --denoise and cannot be\n"
+        "                                   combined with it or with --gpus > 1; --samples must be at least 2; --noisy and\n"
+        "                                   --feature-samples apply\n"
+        "      --guided-levels <l>          denoise-guided: levels of the filter, 1 to 6; each doubles its reach [default: 5]\n"
+        "      --guided-colour <k>          denoise-guided: colour tolerance in standard deviations, above 0 [default: 2]\n"
+        "      --guided-normal <k>          denoise-guided: tolerance of the normal's difference, above 0 [default: 0.35]\n"
+        "      --guided-depth <k>           denoise-guided: tolerance of the relative depth difference, above 0 [default: 0.05]\n"
+        "      --guided-albedo <k>          denoise-guided: tolerance of the albedo's difference, above 0 [default: 0.1]\n"
+        "      --guided-no-demodulation     denoise-guided: filter the radiance itself instead of radiance / albedo\n"
         "      --exposure <EV|auto>         exposure of the target image in stops (the radiance is multiplied by 2^EV), or auto:\n"
         "                                   the median luminance of the image is mapped to --exposure-key [default: 0]\n"
         "      --exposure-key <x>           automatic exposure: what the median luminance is mapped to, above 0 [default: 0.18]\n"
@@ -174,6 +187,9 @@ int main(int argc, char** argv) {
     std::optional<uint32_t> denoise_radius, denoise_patch;
     std::optional<float> denoise_strength;
     std::string noisy;
+    bool denoise_guided = false, guided_no_demodulation = false;
+    std::optional<uint32_t> guided_levels;
+    std::optional<float> guided_colour, guided_normal, guided_depth, guided_albedo;
     std::optional<std::string> environment;  // a file, or "none"
     std::optional<float> environment_rotation, environment_intensity;
     std::optional<uint32_t> environment_resolution;
@@ -298,6 +314,28 @@ int main(int argc, char** argv) {
             denoise_strength = f;
         } else if (a == "--noisy") {
             noisy = value();
+        } else if (a == "--denoise-guided" || a == "--guided-no-demodulation") {
+            if (has_val) {
+                std::fprintf(stderr, "error: '%s' takes no value\n", a.c_str());
+                return 2;
+            }
+            (a == "--denoise-guided" ? denoise_guided : guided_no_demodulation) = true;
+        } else if (a == "--guided-levels") {
+            uint32_t v = 0;
+            u32(v);
+            if (v < 1u || v > RBRT_GUIDED_MAX_LEVELS) {
+                std::fprintf(stderr, "error: invalid value '%u' for '--guided-levels' (expected 1 to %u)\n", v, RBRT_GUIDED_MAX_LEVELS);
+                return 2;
+            }
+            guided_levels = v;
+        } else if (a == "--guided-colour" || a == "--guided-normal" || a == "--guided-depth" || a == "--guided-albedo") {
+            const char* v = value();
+            float f = 0.0f;
+            if (!parse_f32(v, f) || !std::isfinite(f) || !(f > 0.0f)) {
+                std::fprintf(stderr, "error: invalid value '%s' for '%s' (expected a finite number > 0)\n", v, a.c_str());
+                return 2;
+            }
+            (a == "--guided-colour" ? guided_colour : a == "--guided-normal" ? guided_normal : a == "--guided-depth" ? guided_depth : guided_albedo) = f;
         } else if (a == "--environment") {
             environment = std::string(value());
             if (environment->empty()) {
@@ -436,9 +474,27 @@ int main(int argc, char** argv) {
         }
     } else {
         const char* alone = denoise_radius ? "--denoise-radius" : denoise_patch ? "--denoise-patch" : denoise_strength ? "--denoise-strength"
-                            : !noisy.empty() ? "--noisy" : nullptr;
+                            : !noisy.empty() && !denoise_guided ? "--noisy" : nullptr;
         if (alone) {
             std::fprintf(stderr, "error: '%s' needs '--denoise'\n", alone);
+            return 2;
+        }
+    }
+    if (denoise_guided) {  // the same sums as --denoise, and the feature buffers of one handle: refused by name before anything is loaded
+        const char* with = denoise ? "--denoise" : gpus > 1 ? "--gpus > 1" : !checkpoint.empty() ? "--checkpoint" : pass_samples != 0 ? "--pass-samples" : nullptr;
+        if (with) {
+            std::fprintf(stderr, "error: '--denoise-guided' cannot be combined with '%s'\n", with);
+            return 2;
+        }
+        if (samples < 2) {
+            std::fprintf(stderr, "error: '--denoise-guided' needs '--samples' of at least 2 (each half image needs a sample)\n");
+            return 2;
+        }
+    } else {
+        const char* alone = guided_levels ? "--guided-levels" : guided_colour ? "--guided-colour" : guided_normal ? "--guided-normal"
+                            : guided_depth ? "--guided-depth" : guided_albedo ? "--guided-albedo" : guided_no_demodulation ? "--guided-no-demodulation" : nullptr;
+        if (alone) {
+            std::fprintf(stderr, "error: '%s' needs '--denoise-guided'\n", alone);
             return 2;
         }
     }
@@ -454,7 +510,7 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "error: '--features' cannot be combined with '--gpus > 1'\n");
             return 2;
         }
-    } else if (feature_samples) {
+    } else if (feature_samples && !denoise_guided) {
         std::fprintf(stderr, "error: '--feature-samples' needs '--features'\n");
         return 2;
     }
@@ -525,6 +581,14 @@ int main(int argc, char** argv) {
             if (denoise_patch) cfg.denoise_patch_radius = *denoise_patch;
             if (denoise_strength) cfg.denoise_strength = *denoise_strength;
         }
+        if (denoise_guided) {
+            cfg.denoise_guided = true, cfg.keep_noisy = !noisy.empty(), cfg.guided_demodulate = !guided_no_demodulation;
+            if (guided_levels) cfg.guided_levels = *guided_levels;
+            if (guided_colour) cfg.guided_colour = *guided_colour;
+            if (guided_normal) cfg.guided_normal = *guided_normal;
+            if (guided_depth) cfg.guided_depth = *guided_depth;
+            if (guided_albedo) cfg.guided_albedo = *guided_albedo;
+        }
         if (glare) {
             cfg.glare = true, cfg.glare_intensity = *glare;
             if (glare_threshold) cfg.glare_threshold = *glare_threshold;
@@ -535,7 +599,8 @@ int main(int argc, char** argv) {
             cfg.tonemap = true, cfg.tonemap_curve = tone_curve, cfg.tonemap_exposure = exposure, cfg.tonemap_key = exposure_key;
             cfg.tonemap_white = white ? *white : 0.0f;
         }
-        if (features) cfg.features = true, cfg.feature_samples = feature_samples ? *feature_samples : std::max(1u, std::min(samples, 8u));
+        if (features) cfg.features = true;
+        if (features || denoise_guided) cfg.feature_samples = feature_samples ? *feature_samples : std::max(1u, std::min(samples, 8u));
         rbrt::ImageBuffer img = rbrt::render_scene(cam, samples, scene, cfg);
         std::printf("Saving rendered image to %s\n", target.c_str());
         const auto t3 = clock::now();
@@ -549,7 +614,7 @@ int main(int argc, char** argv) {
             uint64_t triangles = 0;
             for (const auto& m : scene.triangle_meshes) triangles += m.num_triangles;
             const uint32_t spp = samples_arg_for_report(samples);
-            const double rendered = adaptive || denoise ? double(rep.adaptive_samples)
+            const double rendered = adaptive || denoise || denoise_guided ? double(rep.adaptive_samples)
                                              : double(width) * double(height) * double(spp - rep.resumed_from_sample);  // path samples of THIS run
             std::string js = "{";
             const auto str = [&](const char* k, const std::string& v) { js += std::string("\"") + k + "\": \"" + json_escape(v) + "\", "; };
@@ -579,6 +644,10 @@ int main(int argc, char** argv) {
             if (denoise) {  // the filter's parameters and its time on the GPU (a part of render_s)
                 num("denoise_window_radius", cfg.denoise_window_radius, "%.0f"), num("denoise_patch_radius", cfg.denoise_patch_radius, "%.0f");
                 num("denoise_strength", cfg.denoise_strength, "%.9g"), num("denoise_ms", rep.denoise_ms, "%.4f");
+            }
+            if (denoise_guided) {  // the guided filter's parameters and its time on the GPU (a part of gather_s, behind the feature buffers)
+                num("guided_levels", cfg.guided_levels, "%.0f"), num("guided_colour", cfg.guided_colour, "%.9g"), num("guided_normal", cfg.guided_normal, "%.9g");
+                num("guided_depth", cfg.guided_depth, "%.9g"), num("guided_albedo", cfg.guided_albedo, "%.9g"), num("guided_ms", rep.guided_ms, "%.4f");
             }
             if (glare) {  // the glare stage: its options and its time on the GPU
                 num("glare", cfg.glare_intensity, "%.9g"), num("glare_levels", cfg.glare_levels, "%.0f"), num("glare_ms", rep.glare_ms, "%.4f");

@@ -291,6 +291,7 @@ struct RenderReport {
     uint32_t luminance_counted = 0;
     double tonemap_ms = 0.0;
     double glare_ms = 0.0;  // a render with glare (RenderConfig::glare): rbrt_hip_glare on the GPU, between two events
+    double guided_ms = 0.0;  // a render with the guided filter (RenderConfig::denoise_guided): rbrt_hip_scene_denoise_guided, between two events
     double features_ms = 0.0;  // a render with feature buffers (RenderConfig::features): rbrt_hip_render_features, between two events
 };
 
@@ -341,6 +342,14 @@ struct RenderConfig {  // additions that the reference hard-codes or lacks
     // ImageBuffer::feature_*. One GPU: render_scene refuses the combination with more by name.
     bool features = false;
     uint32_t feature_samples = 4;  // 1..65536
+    // Guided denoising (rbrt_hip_scene_denoise_guided; the CLI's --denoise-guided, --guided-*): the image is the edge-avoiding
+    // a-trous filter of the render's two half sums, guided by the feature buffers, which are made on the same handle with
+    // feature_samples samples a pixel whether `features` is set or not. Goes through the adaptive path like `denoise`, inherits
+    // its refusals, and cannot be combined with it; keep_noisy works as with `denoise`.
+    bool denoise_guided = false;
+    uint32_t guided_levels = 5;  // (rbrt_guided_opts_default)
+    float guided_colour = 2.0f, guided_normal = 0.35f, guided_depth = 0.05f, guided_albedo = 0.1f;
+    bool guided_demodulate = true;  // false: RBRT_GUIDED_NO_DEMODULATION
 };
 // rbrt_lib::render_scene (lib.rs:75-79): blocks until the image is complete. Runs on the GPU(s)
 // through the C ABI; there is no CPU path.

@@ -333,6 +333,14 @@ Plan make_plan(const RenderConfig& cfg, const std::string& adaptive_by, const Ca
         if (cfg.pass_spp != 0) throw Error(adaptive_by + " cannot be combined with --pass-samples");
     }
     if (cfg.denoise && num_samples < 2) throw Error("--denoise needs at least 2 samples (each half image needs one)");
+    if (cfg.denoise_guided) {  // (rbrt_hip.h "Guided denoising": the same sums, and the feature buffers of the same handle)
+        if (cfg.denoise) throw Error("--denoise-guided cannot be combined with --denoise");
+        if (num_samples < 2) throw Error("--denoise-guided needs at least 2 samples (each half image needs one)");
+        if (cfg.guided_levels == 0 || cfg.guided_levels > RBRT_GUIDED_MAX_LEVELS) throw Error("--guided-levels must be 1 to 6");
+        for (const float k : {cfg.guided_colour, cfg.guided_normal, cfg.guided_depth, cfg.guided_albedo})
+            if (!std::isfinite(k) || !(k > 0.0f)) throw Error("--guided-colour, --guided-normal, --guided-depth and --guided-albedo must be finite and above 0");
+        if (cfg.feature_samples == 0 || cfg.feature_samples > 65536u) throw Error("--feature-samples must be 1 to 65536");
+    }
     if (cfg.features) {  // (of the whole frame, on one handle: rbrt_hip.h "Feature buffers")
         if (cfg.n_gpus > 1) throw Error("--features cannot be combined with --gpus > 1");
         if (cfg.feature_samples == 0 || cfg.feature_samples > 65536u) throw Error("--feature-samples must be 1 to 65536");
@@ -484,7 +492,9 @@ struct Rank {
     void run();
     void setup();
     void render_adaptive();
+    void keep_noisy();
     void denoise();
+    void denoise_guided();
     void render_passes();
     void features();
     void gather_single();
@@ -505,6 +515,7 @@ struct Rank {
     rbrt_hip_scene_t* hs = nullptr;
     Stream stream;
     DeviceBuffer d_acc, d_rad, d_rgb, d_img;
+    DeviceBuffer d_features;  // a render with feature buffers: albedo, normal, depth, coverage (3 + 3 + 1 + 1 floats a pixel)
     DeviceBuffer d_noisy;  // a denoised, glared or transformed render that keeps the unfiltered image: that image's radiance
 };
 
@@ -521,7 +532,8 @@ void Rank::run() {
     if (hs && !err.failed()) err.lib_ok(rbrt_hip_scene_check(hs));
     sh.t_render[rank] = seconds_since(t_passes);
     const auto t_g = std::chrono::steady_clock::now();
-    if (world == 1 && cfg.features) features();
+    if (world == 1 && (cfg.features || cfg.denoise_guided)) features();
+    if (world == 1 && cfg.denoise_guided) denoise_guided();  // (in front of glare and the display transform, like denoise)
     if (world == 1) gather_single();
     else if (sh.use_rccl) gather_rccl();
     else gather_host();
@@ -591,8 +603,8 @@ void Rank::render_adaptive() {
     if (cfg.denoise) denoise();
 }
 
-// The filter works on the handle's sums and writes over the unfiltered image (kept first where it is wanted).
-void Rank::denoise() {
+// The unfiltered image, where it is wanted, before a filter writes over it.
+void Rank::keep_noisy() {
     const size_t n = job.n();
     if (cfg.keep_noisy) {
         img.noisy_rgb.resize(n);
@@ -600,6 +612,11 @@ void Rank::denoise() {
         if ((cfg.tonemap || cfg.glare) && d_noisy.alloc(n * sizeof(float), err, "hipMalloc(unfiltered radiance)"))
             err.ok(hipMemcpy(d_noisy.as<float>(), d_rad.as<float>(), n * sizeof(float), hipMemcpyDeviceToDevice), "copy of the unfiltered radiance");
     }
+}
+
+// The filter works on the handle's sums and writes over the unfiltered image (kept first where it is wanted).
+void Rank::denoise() {
+    keep_noisy();
     const rbrt_denoise_opts_t dn = {cfg.denoise_window_radius, cfg.denoise_patch_radius, cfg.denoise_strength, 0u};
     EventTimer timer;
     if (!timer.create(err)) return;
@@ -609,6 +626,27 @@ void Rank::denoise() {
     float ms = 0.0f;
     err.ok(hipStreamSynchronize(stream.get()), "denoise");
     if (timer.elapsed(&ms, err)) sh.rep.denoise_ms = ms;
+}
+
+// The guided filter: the handle's sums again, and the feature buffers features() has left on the device.
+void Rank::denoise_guided() {
+    if (err.failed() || !npix) return;
+    keep_noisy();
+    const size_t n_pixels = size_t(img.width) * img.height;
+    const rbrt_guided_opts_t g = {cfg.guided_levels, cfg.guided_colour, cfg.guided_normal, cfg.guided_depth, cfg.guided_albedo,
+                                  cfg.guided_demodulate ? 0u : RBRT_GUIDED_NO_DEMODULATION, {0u, 0u}};
+    const float* const d_albedo = d_features.as<float>();
+    const float *const d_normal = d_albedo + n_pixels * 3, *const d_depth = d_normal + n_pixels * 3, *const d_coverage = d_depth + n_pixels;
+    DeviceBuffer d_workspace;
+    EventTimer timer;
+    if (!(d_workspace.alloc(rbrt_hip_guided_workspace_bytes(img.width, img.height), err, "hipMalloc(guided workspace)") && timer.create(err))) return;
+    timer.start(stream.get(), err);
+    err.lib_ok(rbrt_hip_scene_denoise_guided(hs, &g, stream.get(), d_albedo, d_normal, d_depth, d_coverage, d_workspace.as<void>(),
+                                             d_rad.as<float>(), d_rgb.as<uint8_t>()));
+    timer.stop(stream.get(), err);
+    float ms = 0.0f;
+    err.ok(hipStreamSynchronize(stream.get()), "guided denoise");
+    if (timer.elapsed(&ms, err)) sh.rep.guided_ms = ms;
 }
 
 // The passes, from the checkpoint's sample on. The loop bounds are the same for every rank, so every rank meets every barrier.
@@ -645,17 +683,16 @@ void Rank::render_passes() {
 }
 
 // The feature buffers of the frame, after the render, on the same handle and stream: one call between two events, into memory of
-// this step's making, then to the image.
+// the rank's, then, where --features asked for them, to the image.
 void Rank::features() {
     if (err.failed() || !npix) return;
     const size_t n_pixels = size_t(img.width) * img.height;
     rbrt_feature_opts_t fo;
     rbrt_feature_opts_default(&fo);
     fo.samples = cfg.feature_samples;
-    DeviceBuffer d_out;  // albedo, normal, depth, coverage: 3 + 3 + 1 + 1 floats a pixel
-    EventTimer timer;
-    if (!(d_out.alloc(n_pixels * 8 * sizeof(float), err, "hipMalloc(feature buffers)") && timer.create(err))) return;
-    float* const d_albedo = d_out.as<float>();
+    EventTimer timer;  // (d_features lives until release: the guided filter reads it)
+    if (!(d_features.alloc(n_pixels * 8 * sizeof(float), err, "hipMalloc(feature buffers)") && timer.create(err))) return;
+    float* const d_albedo = d_features.as<float>();
     float *const d_normal = d_albedo + n_pixels * 3, *const d_depth = d_normal + n_pixels * 3, *const d_coverage = d_depth + n_pixels;
     timer.start(stream.get(), err);
     err.lib_ok(rbrt_hip_render_features(hs, &job.lens.cam, &o, &fo, stream.get(), d_albedo, d_normal, d_depth, d_coverage, nullptr));
@@ -664,11 +701,13 @@ void Rank::features() {
     float ms = 0.0f;
     if (timer.elapsed(&ms, err)) sh.rep.features_ms = ms;
     if (err.failed()) return;
-    img.feature_albedo.resize(n_pixels * 3), img.feature_normal.resize(n_pixels * 3), img.feature_depth.resize(n_pixels), img.feature_coverage.resize(n_pixels);
-    err.ok(hipMemcpy(img.feature_albedo.data(), d_albedo, n_pixels * 3 * sizeof(float), hipMemcpyDeviceToHost), "download of the albedo");
-    err.ok(hipMemcpy(img.feature_normal.data(), d_normal, n_pixels * 3 * sizeof(float), hipMemcpyDeviceToHost), "download of the normals");
-    err.ok(hipMemcpy(img.feature_depth.data(), d_depth, n_pixels * sizeof(float), hipMemcpyDeviceToHost), "download of the depth");
-    err.ok(hipMemcpy(img.feature_coverage.data(), d_coverage, n_pixels * sizeof(float), hipMemcpyDeviceToHost), "download of the coverage");
+    if (cfg.features) {  // (the guided filter alone reads them on the device: nothing comes to the host)
+        img.feature_albedo.resize(n_pixels * 3), img.feature_normal.resize(n_pixels * 3), img.feature_depth.resize(n_pixels), img.feature_coverage.resize(n_pixels);
+        err.ok(hipMemcpy(img.feature_albedo.data(), d_albedo, n_pixels * 3 * sizeof(float), hipMemcpyDeviceToHost), "download of the albedo");
+        err.ok(hipMemcpy(img.feature_normal.data(), d_normal, n_pixels * 3 * sizeof(float), hipMemcpyDeviceToHost), "download of the normals");
+        err.ok(hipMemcpy(img.feature_depth.data(), d_depth, n_pixels * sizeof(float), hipMemcpyDeviceToHost), "download of the depth");
+        err.ok(hipMemcpy(img.feature_coverage.data(), d_coverage, n_pixels * sizeof(float), hipMemcpyDeviceToHost), "download of the coverage");
+    }
     if (hs && !err.failed()) err.lib_ok(rbrt_hip_scene_check(hs));  // (a NaN discriminant is counted here as in a render)
 }
 
@@ -766,6 +805,7 @@ void Rank::release() {
     d_rgb.reset();
     d_img.reset();
     d_noisy.reset();
+    d_features.reset();
     if (rank == 0) sh.d_slots.reset();
     stream.reset();
     rbrt_hip_scene_destroy(hs);
@@ -818,7 +858,7 @@ void report_times(const Plan& plan, const Shared& sh, RenderReport& rep) {
 
 ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& scene, const RenderConfig& cfg_in) {
     RenderConfig cfg = cfg_in;
-    if (cfg.denoise && !cfg.adaptive)  // (the filter's input is the adaptive path's sums: one round that stops nothing)
+    if ((cfg.denoise || cfg.denoise_guided) && !cfg.adaptive)  // (the filter's input is the adaptive path's sums: one round that stops nothing)
         cfg.adaptive = true, cfg.adaptive_threshold = 0.0f, cfg.adaptive_min_samples = cfg.adaptive_step = std::max(num_samples, 2u);
     if (!cfg.quiet) std::printf("Starting rendering...\n");
     ImageBuffer img;
@@ -831,7 +871,7 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
     const rbrt_camera_lens_t lens = cam.to_abi_lens();
     const Scene::AbiView view = scene.to_abi();
     const rbrt_environment_t env_abi = scene.environment.to_abi();
-    const Plan plan = make_plan(cfg, cfg_in.adaptive ? "--adaptive" : "--denoise", cam, scene, num_samples);
+    const Plan plan = make_plan(cfg, cfg_in.adaptive ? "--adaptive" : cfg_in.denoise_guided ? "--denoise-guided" : "--denoise", cam, scene, num_samples);
     Job job{cfg, plan, lens, view, scene.environment.n != 0u ? &env_abi : nullptr, render_opts_of(cfg, cam, num_samples), num_samples, {}, {}, img};
     job.want = checkpoint_header(img.width, img.height, num_samples, uint32_t(plan.world), cfg.seed,
                                  checkpoint_fingerprint(cfg.checkpoint_path, lens, job.opts, view.scene, view.shading_ptr(), scene.environment));

@@ -68,7 +68,9 @@ extern "C" {
                               and entry points, detected by the symbol), nor the guided denoiser
                               (rbrt_guided_opts_t, rbrt_guided_opts_default, rbrt_hip_guided_workspace_bytes,
                               rbrt_hip_denoise_guided and rbrt_hip_scene_denoise_guided: an added struct and entry points,
-                              detected by the symbol) */
+                              detected by the symbol), nor temporal accumulation (rbrt_temporal_opts_t,
+                              rbrt_temporal_opts_default, rbrt_hip_temporal_history_bytes and rbrt_hip_temporal_accumulate:
+                              an added struct and entry points, detected by the symbol) */
 
 typedef enum rbrt_status {
     RBRT_OK = 0,
@@ -770,6 +772,86 @@ int rbrt_hip_denoise_guided(int device, void* stream, const float* d_a, const fl
 int rbrt_hip_scene_denoise_guided(rbrt_hip_scene_t* scene, const rbrt_guided_opts_t* opts, void* stream,
                                   const float* d_albedo, const float* d_normal, const float* d_depth, const float* d_coverage,
                                   void* d_workspace, float* d_radiance, uint8_t* d_rgb8);
+
+/* ---- Temporal accumulation: reproject the last frame's half images into this frame ------------------------------------------
+ * No counterpart in the reference. In a stream of frames from a moving camera every pixel's point is projected into the last
+ * frame's camera, the last frame's accumulated halves are read there (bilinear, four taps, each tap tested against this
+ * pixel's depth and normal) and mixed with this frame's halves by the length of the history: the temporal part of SVGF. A is
+ * only ever mixed with A's history and B with B's, so the halves stay independent estimates and what both denoisers derive
+ * from A - B stays valid and shrinks as the history grows. The outputs go into rbrt_hip_denoise_halves or
+ * rbrt_hip_denoise_guided unchanged.
+ *
+ * The rule. All arithmetic is float32, unfused, in the written order; / and sqrt are correctly rounded;
+ * dot(a, b) = ((a_x * b_x) + (a_y * b_y)) + (a_z * b_z); a sum "from 0" starts at 0.0f and adds its terms one at a time in the
+ * stated order; a constant is the float32 nearest to the decimal written; s * v and v +- w on vectors work per component.
+ *   Inputs.  Half images A, B, float[H][W][3]; normal N, float[H][W][3]; depth z and coverage c, float[H][W], as
+ *     rbrt_hip_render_features writes them; the camera K of this frame and K' of the last (only the pinhole part: with a thin
+ *     lens the reprojection goes through the lens centre); max_history M, depth tolerance kz, normal tolerance kn; the history
+ *     of the last frame, per pixel q: A'prev[q], B'prev[q], len'[q], N'[q], z'[q], c'[q].
+ *   Camera constants of K' (host, one operation a statement).
+ *     n = right x up: n_x = (r_y * u_z) - (r_z * u_y), and so on cyclically. w = img_center_point - position. wn = dot(w, n).
+ *     rr = dot(right, right); uu = dot(up, up); ru = dot(right, up); det = (rr * uu) - (ru * ru).
+ *     sx = 0.001f * mm_per_pix_hor; sy = 0.001f * mm_per_pix_vert. hx = float(W / 2), hy = float(H / 2), integer halving.
+ *   Centre ray of pixel p = (row, col) in K: the render's own ray with both jitter draws at 0.5.
+ *     cm = (float(col) - hx) * mm_per_pix_hor; rm = (float(row) - hy) * mm_per_pix_vert.
+ *     T = (img_center_point + ((0.001f * cm) * right)) - ((0.001f * rm) * up).
+ *     e = T - position; d = e / sqrt(dot(e, e)), three divisions by the length.
+ *   Point.  If c[p] > 0 the pixel is a surface pixel: zbar = z[p] / c[p], P = position + (zbar * d), v = P - position'.
+ *     Else it is a background pixel and v = d: a point at infinity, because sky and environment depend on direction only.
+ *   Projection into K'.
+ *     t = wn / dot(v, n). No history unless t > 0 and t < inf (a NaN compares false).
+ *     Q = (t * v) - w. qr = dot(Q, right'). qu = dot(Q, up').
+ *     a = ((qr * uu) - (qu * ru)) / det. b = ((qr * ru) - (qu * rr)) / det. (`up` is the raw YAML vector, neither normalised
+ *     nor perpendicular to the view, so the image-plane coordinates come from a Gram solve.)
+ *     xs = (a / sx) + hx. ys = (b / sy) + hy.
+ *     No history unless xs > -1, xs < W, ys > -1 and ys < H; the tests are made on the floats, before any conversion.
+ *     i = floor(xs), j = floor(ys). fx = xs - float(i), fy = ys - float(j). gx = 1 - fx, gy = 1 - fy.
+ *   Taps, in this order: (j, i) with bw = gx * gy; (j, i + 1) with fx * gy; (j + 1, i) with gx * fy; (j + 1, i + 1) with
+ *     fx * fy (row, column). A tap q is accepted iff it is inside the image and
+ *       surface pixel: c'[q] > 0, and |zq - ze| <= kz * ze with zq = z'[q] / c'[q] and ze = sqrt(dot(v, v)), and
+ *         dot(D, D) <= kn * kn with D = N[p] - N'[q];
+ *       background pixel: c'[q] == 0.
+ *   Sums from 0 over the accepted taps, in tap order: ws += bw; sa_c += bw * A'prev_c[q]; sb_c likewise; sl += bw * len'[q].
+ *     The history is valid iff ws >= 0.01f.
+ *   Result.  Without a valid history, or without any history at all (the first frame): A' = A and B' = B exactly, len = 1.
+ *     Else HA_c = sa_c / ws, HB_c = sb_c / ws, hl = sl / ws; len = min(hl + 1, M); alpha = 1 / len;
+ *     A'_c = HA_c + (alpha * (A_c - HA_c)); B' likewise.
+ *   The next history holds A', B', len and this frame's N, z, c.
+ * Consequences. A pixel with no valid history passes through bit for bit. A history value at a tap that is not accepted never
+ * influences any output. A static camera and scene give the running mean of the frames, up to the bilinear footprint of
+ * |xs - col|. Whatever the inputs are, NaN and infinities included, no read leaves the buffers. A non-finite input gives
+ * unspecified values in the pixels whose taps reach it, and never a fault. */
+typedef struct rbrt_temporal_opts {
+    float max_history;     /* M: finite, >= 1 */
+    float depth;           /* kz: finite, >= 0 */
+    float normal;          /* kn: finite, >= 0 */
+    uint32_t flags;        /* 0 */
+    uint32_t reserved[4];  /* 0 */
+} rbrt_temporal_opts_t;
+void rbrt_temporal_opts_default(rbrt_temporal_opts_t* opts); /* M = 32, kz = 0.05, kn = 0.35, flags 0 */
+
+/* Bytes of one history of a width x height image. The history is in the library's own layout: 48 bytes a pixel as three
+ * 16-byte records {A', len}, {B', c}, {N, z}, three planes of width * height records, so that a tap is three aligned 16-byte
+ * loads. 0 for sizes the call refuses. */
+size_t rbrt_hip_temporal_history_bytes(uint32_t width, uint32_t height);
+
+/* One frame of the rule on buffers in DEVICE memory, all row-major (d_a, d_b, d_normal float[H][W][3]; d_depth, d_coverage
+ * float[H][W]); width and height are cam's. Asynchronous on `stream`; needs no scene and owns no device memory.
+ * d_history_in is the history the last frame's call wrote (NULL: the first frame; cam_prev may then be NULL too and is not
+ * read); d_history_out receives the next one. They must differ: the caller keeps two and alternates. Nothing is assumed about
+ * the contents of d_history_out. Every output (d_history_out, d_out_a, d_out_b, d_out_length: float[H][W]) may be NULL; with
+ * all four NULL nothing is launched. d_out_a may be exactly d_a and d_out_b exactly d_b (a thread reads its own pixel before
+ * it writes); any other overlap is undefined.
+ * RBRT_ERR_INVALID_ARG, before the device is touched: d_a, d_b, d_normal, d_depth, d_coverage, cam or opts NULL; cam_prev NULL
+ * with a history; d_history_in == d_history_out (non-NULL); a history that is not 16-byte aligned; an image without pixels;
+ * cam_prev's size differing from cam's; max_history not finite or < 1; depth or normal not finite or < 0; a non-zero flag or
+ * reserved word; a cam_prev whose det or wn is 0 or not finite, or whose mm_per_pix is not finite and > 0; the same for
+ * cam's mm_per_pix.
+ * RBRT_ERR_UNSUPPORTED: 2^31 pixels or more. */
+int rbrt_hip_temporal_accumulate(int device, void* stream, const float* d_a, const float* d_b, const float* d_normal,
+                                 const float* d_depth, const float* d_coverage, const rbrt_camera_t* cam,
+                                 const rbrt_camera_t* cam_prev, const rbrt_temporal_opts_t* opts, const void* d_history_in,
+                                 void* d_history_out, float* d_out_a, float* d_out_b, float* d_out_length);
 
 /* De-interleave gathered per-rank packed tile buffers (concatenated rank 0..world-1, each
  * rbrt_hip_packed_pixels(...)*3 floats, device memory) into a row-major float[H][W][3] device

@@ -68,6 +68,11 @@ int rbrt_hip_scene_adaptive_rounds(rbrt_hip_scene_t* scene, uint32_t* active_til
 #define RBRT_GUIDED_STAGED_MAX_STEP 4u
 int rbrt_hip_debug_guided_staging(int max_step);
 
+/* The temporal accumulation's kernel (rbrt_amd/csrc/temporal.hip) has no tile: a workgroup takes this many consecutive pixels
+ * of the row-major image, so there is no RBRT_TEMPORAL_TILE. Pixel counts around it, as one row and as one column, are where a
+ * workgroup is added (tests/test_temporal_gpu.py). */
+#define RBRT_TEMPORAL_BLOCK 256u
+
 /* The display transform's kernels (rbrt_amd/csrc/tonemap.hip): the pixels one workgroup takes per stride of its grid, and the
  * cap of that grid. Pixel counts around BLOCK_PIXELS, and around MAX_BLOCKS * BLOCK_PIXELS where a workgroup starts to stride a
  * second time, are where those kernels' paths change (tests/test_tonemap_gpu.py). */

@@ -478,6 +478,42 @@ def guided_staging(max_step: int = -1) -> int:
     return rc
 
 
+def temporal_opts(max_history: float | None = None, depth: float | None = None, normal: float | None = None,
+                  flags: int | None = None, reserved=(0, 0, 0, 0)) -> abi.TemporalOpts:
+    """rbrt_temporal_opts_default (max_history 32, depth 0.05, normal 0.35, flags 0), with the parameters that are given put in."""
+    t = abi.TemporalOpts()
+    load_hip().rbrt_temporal_opts_default(C.byref(t))
+    for name, value, kind in (("max_history", max_history, float), ("depth", depth, float), ("normal", normal, float), ("flags", flags, int)):
+        if value is not None:
+            setattr(t, name, kind(value))
+    for k in range(4):
+        t.reserved[k] = int(reserved[k])
+    return t
+
+
+def temporal_history_bytes(width: int, height: int) -> int:
+    """rbrt_hip_temporal_history_bytes: the device memory of one history of temporal_accumulate(); 0 for sizes it refuses."""
+    return int(load_hip().rbrt_hip_temporal_history_bytes(width, height))
+
+
+def temporal_accumulate(device: int, d_a: int, d_b: int, d_normal: int, d_depth: int, d_coverage: int, cam: abi.Camera,
+                        cam_prev: abi.Camera | None, d_history_in: int | None, d_history_out: int | None,
+                        d_out_a: int | None = None, d_out_b: int | None = None, d_out_length: int | None = None,
+                        opts: abi.TemporalOpts | None = None, stream: int | None = None):
+    """One frame of temporal accumulation in device memory (rbrt_hip_temporal_accumulate): d_a, d_b, d_normal row-major float32
+    [H, W, 3]; d_depth, d_coverage and d_out_length float32 [H, W], W and H being `cam`'s; the histories
+    temporal_history_bytes(W, H) bytes each, 16-byte aligned, two that alternate. d_history_in None: the first frame (cam_prev
+    may then be None). d_out_a may be d_a and d_out_b may be d_b. `opts`: temporal_opts(...), None for the library's defaults.
+    Asynchronous on `stream`."""
+    t = opts if opts is not None else temporal_opts()
+    abi.check(load_hip().rbrt_hip_temporal_accumulate(device, C.c_void_p(stream or 0), C.c_void_p(d_a or 0), C.c_void_p(d_b or 0),
+                                                      C.c_void_p(d_normal or 0), C.c_void_p(d_depth or 0), C.c_void_p(d_coverage or 0),
+                                                      C.byref(cam) if cam is not None else None,
+                                                      C.byref(cam_prev) if cam_prev is not None else None, C.byref(t),
+                                                      C.c_void_p(d_history_in or 0), C.c_void_p(d_history_out or 0),
+                                                      C.c_void_p(d_out_a or 0), C.c_void_p(d_out_b or 0), C.c_void_p(d_out_length or 0)))
+
+
 def tonemap_opts(curve: int | None = None, exposure: float | None = None, key: float | None = None,
                  key_permille: int | None = None, white: float | None = None, white_permille: int | None = None,
                  reserved=(0, 0)) -> abi.TonemapOpts:

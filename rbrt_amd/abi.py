@@ -42,6 +42,8 @@ TONEMAP_BLOCK_PIXELS = 1024  # rbrt_hip_debug.h: pixels a workgroup of the trans
 TONEMAP_MAX_BLOCKS = 512     # ... and the cap of their grid
 GUIDED_NO_DEMODULATION = 1   # rbrt_hip.h: RBRT_GUIDED_NO_DEMODULATION
 GUIDED_MAX_LEVELS = 6        # rbrt_hip.h: the most levels of the guided denoiser
+TEMPORAL_HISTORY_BYTES_PER_PIXEL = 48  # rbrt_hip.h: three 16-byte records {A', len}, {B', c}, {N, z}
+TEMPORAL_BLOCK = 256         # rbrt_hip_debug.h: consecutive pixels a workgroup of the temporal kernel takes
 GLARE_MAX_LEVELS = 8         # rbrt_hip.h: the most levels of the glare stage's pyramid
 GLARE_TILE_W = 16            # rbrt_hip_debug.h: the tile of a pyramid level one workgroup of the REDUCE kernel makes
 GLARE_TILE_H = 16
@@ -190,6 +192,11 @@ class GuidedOpts(C.Structure):  # rbrt_guided_opts_t
                 ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+class TemporalOpts(C.Structure):  # rbrt_temporal_opts_t
+    _fields_ = [("max_history", C.c_float), ("depth", C.c_float), ("normal", C.c_float), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
+
+
 class Environment(C.Structure):  # rbrt_environment_t
     """An octahedral radiance map of (n + 1) x (n + 1) nodes: `nodes` points at host float32 [n + 1][n + 1][3]."""
     _fields_ = [("n", C.c_uint32), ("reserved", C.c_uint32), ("nodes", f32p)]
@@ -278,6 +285,11 @@ HIP_SYMBOLS = {
                                           C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(GuidedOpts), C.c_void_p, C.c_void_p, C.c_void_p]),
     "rbrt_hip_scene_denoise_guided": (C.c_int, [C.c_void_p, C.POINTER(GuidedOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rbrt_temporal_opts_default": (None, [C.POINTER(TemporalOpts)]),
+    "rbrt_hip_temporal_history_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "rbrt_hip_temporal_accumulate": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.POINTER(Camera), C.POINTER(Camera), C.POINTER(TemporalOpts), C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 # ... and include/rbrt_hip_debug.h (test hooks and diagnostics, same library)
 DEBUG_SYMBOLS = {

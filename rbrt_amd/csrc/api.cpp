@@ -44,6 +44,7 @@ hipError_t launch_denoise_halves(const DenoiseHalvesParams& Q, hipStream_t strea
 hipError_t launch_tonemap(const TonemapParams& T, hipStream_t stream);                 // tonemap.hip
 hipError_t launch_glare(const GlareParams& G, hipStream_t stream);                     // glare.hip
 hipError_t launch_guided(const GuidedParams& G, uint32_t staged_max_step, hipStream_t stream);  // guided.hip
+hipError_t launch_temporal(const TemporalParams& T, hipStream_t stream);                // temporal.hip
 hipError_t launch_unpack(const float* gathered, uint32_t width, uint32_t height, uint32_t world,
                          size_t rank_stride_pixels, float* out_radiance, uint8_t* out_rgb8, hipStream_t stream);
 hipError_t launch_trace_rays(const TraceParams& P, const float* rays, size_t n, float* out_t, int32_t* out_obj,
@@ -2382,6 +2383,86 @@ int rbrt_hip_scene_denoise_guided(rbrt_hip_scene_t* s, const rbrt_guided_opts_t*
     HIP_TRY(launch_guided(guided_params(S.d_half_a, S.d_half_b, S.d_wa, d_albedo, d_normal, d_depth, d_coverage, S.last.width, S.last.height, g,
                                         d_workspace, d_radiance, d_rgb8),
                           g_guided_staged_max_step.load(), stream));
+    return RBRT_OK;
+}
+
+// ---- Temporal accumulation (the rule: include/rbrt_hip.h; the kernel: temporal.hip) -----------------------------------------
+void rbrt_temporal_opts_default(rbrt_temporal_opts_t* o) {
+    if (!o) return;
+    o->max_history = 32.0f, o->depth = 0.05f, o->normal = 0.35f, o->flags = 0u;
+    for (uint32_t& r : o->reserved) r = 0u;
+}
+
+size_t rbrt_hip_temporal_history_bytes(uint32_t width, uint32_t height) {
+    if (width == 0u || height == 0u || uint64_t(width) * height >= (1ull << 31)) return 0;
+    return size_t(width) * height * 48u;  // (the layout of temporal.hip: three planes of one float4 a pixel)
+}
+
+static bool positive_finite(float x) { return std::isfinite(x) && x > 0.0f; }
+static float dot3(const float* a, const float* b) {  // the rule's dot, one operation a statement
+    const float x = a[0] * b[0], y = a[1] * b[1], z = a[2] * b[2];
+    const float xy = x + y;
+    return xy + z;
+}
+
+int rbrt_hip_temporal_accumulate(int device, void* stream, const float* d_a, const float* d_b, const float* d_normal,
+                                 const float* d_depth, const float* d_coverage, const rbrt_camera_t* cam, const rbrt_camera_t* prev,
+                                 const rbrt_temporal_opts_t* o, const void* d_history_in, void* d_history_out, float* d_out_a,
+                                 float* d_out_b, float* d_out_length) {
+    if (!d_a || !d_b || !d_normal || !d_depth || !d_coverage || !cam || !o) return fail(RBRT_ERR_INVALID_ARG, "temporal_accumulate: null argument");
+    if (d_history_in && !prev) return fail(RBRT_ERR_INVALID_ARG, "temporal_accumulate: a history needs cam_prev");
+    if (d_history_in && d_history_in == d_history_out)
+        return fail(RBRT_ERR_INVALID_ARG, "temporal_accumulate: d_history_in and d_history_out must differ (keep two and alternate)");
+    if (reinterpret_cast<uintptr_t>(d_history_in) % 16u != 0u || reinterpret_cast<uintptr_t>(d_history_out) % 16u != 0u)
+        return fail(RBRT_ERR_INVALID_ARG, "temporal_accumulate: a history must be 16-byte aligned");
+    const uint32_t width = cam->img_width_pix, height = cam->img_height_pix;
+    if (width == 0u || height == 0u) return fail(RBRT_ERR_INVALID_ARG, "temporal_accumulate: width and height must be >= 1");
+    if (d_history_in && (prev->img_width_pix != width || prev->img_height_pix != height))
+        return fail(RBRT_ERR_INVALID_ARG, "temporal_accumulate: cam_prev's image size differs from cam's");
+    if (!std::isfinite(o->max_history) || !(o->max_history >= 1.0f)) return fail(RBRT_ERR_INVALID_ARG, "temporal_accumulate: max_history must be finite and >= 1");
+    for (const float k : {o->depth, o->normal})
+        if (!std::isfinite(k) || !(k >= 0.0f)) return fail(RBRT_ERR_INVALID_ARG, "temporal_accumulate: depth and normal must be finite and >= 0");
+    if (o->flags != 0u) return fail(RBRT_ERR_INVALID_ARG, "temporal_accumulate: unknown flag bit");
+    for (const uint32_t r : o->reserved)
+        if (r != 0u) return fail(RBRT_ERR_INVALID_ARG, "temporal_accumulate: reserved must be 0");
+    if (!positive_finite(cam->mm_per_pix_hor) || !positive_finite(cam->mm_per_pix_vert))
+        return fail(RBRT_ERR_INVALID_ARG, "temporal_accumulate: cam's mm_per_pix must be finite and > 0");
+
+    TemporalParams T;
+    std::memset(&T, 0, sizeof(T));
+    T.a = d_a, T.b = d_b, T.normal = d_normal, T.depth = d_depth, T.coverage = d_coverage;
+    T.history_in = d_history_in, T.history_out = d_history_out, T.out_a = d_out_a, T.out_b = d_out_b, T.out_length = d_out_length;
+    T.width = width, T.height = height;
+    T.max_history = o->max_history, T.kz = o->depth, T.kn2 = o->normal * o->normal;
+    for (int k = 0; k < 3; ++k)
+        T.pos[k] = cam->position[k], T.right[k] = cam->right[k], T.up[k] = cam->up[k], T.center[k] = cam->img_center_point[k];
+    T.mm_hor = cam->mm_per_pix_hor, T.mm_vert = cam->mm_per_pix_vert;
+    T.hx = float(width / 2u), T.hy = float(height / 2u);
+    if (d_history_in) {
+        if (!positive_finite(prev->mm_per_pix_hor) || !positive_finite(prev->mm_per_pix_vert))
+            return fail(RBRT_ERR_INVALID_ARG, "temporal_accumulate: cam_prev's mm_per_pix must be finite and > 0");
+        // the rule's constants of K', in float, one operation a statement (this file is compiled with -ffp-contract=off)
+        const float* r = prev->right;
+        const float* u = prev->up;
+        for (int k = 0; k < 3; ++k) {
+            const int k1 = (k + 1) % 3, k2 = (k + 2) % 3;
+            const float m0 = r[k1] * u[k2], m1 = r[k2] * u[k1];
+            T.n[k] = m0 - m1;
+            T.w[k] = prev->img_center_point[k] - prev->position[k];
+            T.pos_prev[k] = prev->position[k], T.right_prev[k] = r[k], T.up_prev[k] = u[k];
+        }
+        T.wn = dot3(T.w, T.n);
+        T.rr = dot3(r, r), T.uu = dot3(u, u), T.ru = dot3(r, u);
+        const float d0 = T.rr * T.uu, d1 = T.ru * T.ru;
+        T.det = d0 - d1;
+        T.sx = 0.001f * prev->mm_per_pix_hor, T.sy = 0.001f * prev->mm_per_pix_vert;
+        if (!std::isfinite(T.det) || T.det == 0.0f || !std::isfinite(T.wn) || T.wn == 0.0f)
+            return fail(RBRT_ERR_INVALID_ARG, "temporal_accumulate: cam_prev is degenerate (right x up, or its distance to the image plane, is 0 or not finite)");
+    }
+    if (uint64_t(width) * height >= (1ull << 31)) return fail(RBRT_ERR_UNSUPPORTED, "temporal_accumulate: 2^31 or more pixels");
+    if (int rc = ensure_device(device)) return rc;
+    if (!d_history_out && !d_out_a && !d_out_b && !d_out_length) return RBRT_OK;
+    HIP_TRY(launch_temporal(T, static_cast<hipStream_t>(stream)));
     return RBRT_OK;
 }
 

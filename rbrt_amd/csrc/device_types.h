@@ -332,4 +332,27 @@ struct GuidedParams {
     uint8_t* out_rgb8;       // [H][W][3], may be null
 };
 
+// Temporal accumulation (include/rbrt_hip.h "Temporal accumulation"; temporal.hip): one rbrt_hip_temporal_accumulate call.
+struct TemporalParams {
+    const float* a;             // [H][W][3] this frame's half images
+    const float* b;
+    const float* normal;        // [H][W][3]
+    const float* depth;         // [H][W]
+    const float* coverage;      // [H][W]
+    const void* history_in;     // three planes of width * height float4: {A', len}, {B', c}, {N, z}; null: the first frame
+    void* history_out;          // the same layout, may be null
+    float* out_a;               // [H][W][3], may be null or `a`
+    float* out_b;               // [H][W][3], may be null or `b`
+    float* out_length;          // [H][W], may be null
+    uint32_t width, height;     // width * height < 2^31
+    float max_history, kz, kn2; // M, kz and kn * kn
+    // this frame's camera K
+    float pos[3], right[3], up[3], center[3];
+    float mm_hor, mm_vert;
+    // the last frame's camera K' and the rule's constants of it (unused without a history)
+    float pos_prev[3], right_prev[3], up_prev[3];
+    float n[3], w[3];
+    float wn, rr, uu, ru, det, sx, sy, hx, hy;
+};
+
 }  // namespace rbrt

@@ -18,7 +18,9 @@
 // --features PREFIX with --feature-samples N (the feature buffers of the primary rays -- albedo, normal, depth, coverage -- as
 // four colour PFMs, made after the render on the same handle). --denoise-guided with --guided-levels L, --guided-colour K,
 // --guided-normal K, --guided-depth K, --guided-albedo K and --guided-no-demodulation (the target file gets the edge-avoiding
-// a-trous filter of the render's two half images, guided by those feature buffers).
+// a-trous filter of the render's two half images, guided by those feature buffers). --frames N with --camera-step DX,DY,DZ,
+// --temporal-max-history M, --temporal-depth K, --temporal-normal K and --history-map FILE (a stream of N frames from a moving
+// camera: every frame's half images are accumulated onto the reprojected ones of the frames before it, the last frame is written).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -92,6 +94,19 @@ void usage() {
         "      --guided-depth <k>           denoise-guided: tolerance of the relative depth difference, above 0 [default: 0.05]\n"
         "      --guided-albedo <k>          denoise-guided: tolerance of the albedo's difference, above 0 [default: 0.1]\n"
         "      --guided-no-demodulation     denoise-guided: filter the radiance itself instead of radiance / albedo\n"
+        "      --frames <n>                 render a stream of n frames, at least 1, and write the last one: every frame's two half\n"
+        "                                   images are mixed with those of the frames before it, reprojected through the depth\n"
+        "                                   and normal of the primary rays (temporal accumulation). Frame k renders with seed + k.\n"
+        "                                   Renders like --denoise and cannot be combined with --adaptive, --gpus > 1,\n"
+        "                                   --checkpoint or --pass-samples; --samples must be at least 2; --denoise or\n"
+        "                                   --denoise-guided filter the accumulated image; --feature-samples applies\n"
+        "      --camera-step <dx,dy,dz>     frames: frame k's camera position and image centre are moved by k times this\n"
+        "                                   [default: 0,0,0]\n"
+        "      --temporal-max-history <m>   frames: the longest history a pixel keeps, at least 1 [default: 32]\n"
+        "      --temporal-depth <k>         frames: tolerance of the relative depth difference, 0 or more [default: 0.05]\n"
+        "      --temporal-normal <k>        frames: tolerance of the normal's difference, 0 or more [default: 0.35]\n"
+        "      --history-map <file>         frames: write the last frame's history length over --temporal-max-history there as a\n"
+        "                                   grey image (same formats as the target file)\n"
         "      --exposure <EV|auto>         exposure of the target image in stops (the radiance is multiplied by 2^EV), or auto:\n"
         "                                   the median luminance of the image is mapped to --exposure-key [default: 0]\n"
         "      --exposure-key <x>           automatic exposure: what the median luminance is mapped to, above 0 [default: 0.18]\n"
@@ -149,6 +164,24 @@ bool parse_f32(const char* s, float& out) {
     return true;
 }
 
+// "DX,DY,DZ": three finite floats
+bool parse_vec3(const char* s, float out[3]) {
+    const char* p = s;
+    for (int c = 0; c < 3; ++c) {
+        char* end = nullptr;
+        const float v = std::strtof(p, &end);
+        if (end == p || !std::isfinite(v)) return false;
+        out[c] = v;
+        if (c < 2) {
+            if (*end != ',') return false;
+            p = end + 1;
+        } else if (*end != '\0') {
+            return false;
+        }
+    }
+    return true;
+}
+
 bool parse_rgb(const char* s, float out[3]) {
     const char* p = s;
     for (int c = 0; c < 3; ++c) {
@@ -201,6 +234,11 @@ int main(int argc, char** argv) {
     std::optional<uint32_t> glare_levels;
     std::optional<std::string> features;  // the prefix of the four files
     std::optional<uint32_t> feature_samples;
+    std::optional<uint32_t> frames;  // --frames turns temporal accumulation on; the options below need it
+    std::optional<float> temporal_max_history, temporal_depth, temporal_normal;
+    float camera_step[3] = {0.0f, 0.0f, 0.0f};
+    bool camera_step_given = false;
+    std::string history_map;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         std::string val;
@@ -433,6 +471,32 @@ int main(int argc, char** argv) {
                 return 2;
             }
             feature_samples = v;
+        } else if (a == "--frames") {
+            uint32_t v = 0;
+            u32(v);
+            if (v < 1u) {
+                std::fprintf(stderr, "error: invalid value '%u' for '--frames' (expected at least 1)\n", v);
+                return 2;
+            }
+            frames = v;
+        } else if (a == "--camera-step") {
+            const char* v = value();
+            if (!parse_vec3(v, camera_step)) {
+                std::fprintf(stderr, "error: invalid value '%s' for '--camera-step' (expected DX,DY,DZ: three finite numbers)\n", v);
+                return 2;
+            }
+            camera_step_given = true;
+        } else if (a == "--temporal-max-history" || a == "--temporal-depth" || a == "--temporal-normal") {
+            const bool history = a == "--temporal-max-history";
+            const char* v = value();
+            float f = 0.0f;
+            if (!parse_f32(v, f) || !std::isfinite(f) || !(f >= (history ? 1.0f : 0.0f))) {
+                std::fprintf(stderr, "error: invalid value '%s' for '%s' (expected a finite number >= %d)\n", v, a.c_str(), history ? 1 : 0);
+                return 2;
+            }
+            (history ? temporal_max_history : a == "--temporal-depth" ? temporal_depth : temporal_normal) = f + 0.0f;
+        } else if (a == "--history-map") {
+            history_map = value();
         } else if (a == "--shading") {
             const std::string v = value();
             if (v != "flat" && v != "smooth") {
@@ -498,6 +562,24 @@ int main(int argc, char** argv) {
             return 2;
         }
     }
+    if (frames) {  // every frame is one round of the adaptive path on one handle: refused by name before anything is loaded
+        const char* with = adaptive ? "--adaptive" : gpus > 1 ? "--gpus > 1" : !checkpoint.empty() ? "--checkpoint" : pass_samples != 0 ? "--pass-samples" : nullptr;
+        if (with) {
+            std::fprintf(stderr, "error: '--frames' cannot be combined with '%s'\n", with);
+            return 2;
+        }
+        if (samples < 2) {
+            std::fprintf(stderr, "error: '--frames' needs '--samples' of at least 2 (each half image needs a sample)\n");
+            return 2;
+        }
+    } else {
+        const char* alone = camera_step_given ? "--camera-step" : temporal_max_history ? "--temporal-max-history" : temporal_depth ? "--temporal-depth"
+                            : temporal_normal ? "--temporal-normal" : !history_map.empty() ? "--history-map" : nullptr;
+        if (alone) {
+            std::fprintf(stderr, "error: '%s' needs '--frames'\n", alone);
+            return 2;
+        }
+    }
     if (!glare) {
         const char* alone = glare_threshold ? "--glare-threshold" : glare_levels ? "--glare-levels" : glare_spread ? "--glare-spread" : nullptr;
         if (alone) {
@@ -510,7 +592,7 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "error: '--features' cannot be combined with '--gpus > 1'\n");
             return 2;
         }
-    } else if (feature_samples && !denoise_guided) {
+    } else if (feature_samples && !denoise_guided && !frames) {
         std::fprintf(stderr, "error: '--feature-samples' needs '--features'\n");
         return 2;
     }
@@ -599,8 +681,15 @@ int main(int argc, char** argv) {
             cfg.tonemap = true, cfg.tonemap_curve = tone_curve, cfg.tonemap_exposure = exposure, cfg.tonemap_key = exposure_key;
             cfg.tonemap_white = white ? *white : 0.0f;
         }
+        if (frames) {
+            cfg.frames = *frames;
+            for (int c = 0; c < 3; ++c) cfg.camera_step[c] = camera_step[c];
+            if (temporal_max_history) cfg.temporal_max_history = *temporal_max_history;
+            if (temporal_depth) cfg.temporal_depth = *temporal_depth;
+            if (temporal_normal) cfg.temporal_normal = *temporal_normal;
+        }
         if (features) cfg.features = true;
-        if (features || denoise_guided) cfg.feature_samples = feature_samples ? *feature_samples : std::max(1u, std::min(samples, 8u));
+        if (features || denoise_guided || frames) cfg.feature_samples = feature_samples ? *feature_samples : std::max(1u, std::min(samples, 8u));
         rbrt::ImageBuffer img = rbrt::render_scene(cam, samples, scene, cfg);
         std::printf("Saving rendered image to %s\n", target.c_str());
         const auto t3 = clock::now();
@@ -609,12 +698,20 @@ int main(int argc, char** argv) {
         if (!noisy.empty()) img.save_noisy(noisy);
         if (!radiance_file.empty()) rbrt::write_pfm(radiance_file, img.radiance.data(), img.width, img.height);
         if (features) img.save_features(*features);
+        if (!history_map.empty()) {  // a grey image through the same writers, like the sample map
+            if (img.history_map.size() != size_t(img.width) * img.height) throw rbrt::Error("no history map to save to " + history_map);
+            rbrt::ImageBuffer grey;
+            grey.width = img.width, grey.height = img.height;
+            grey.rgb.resize(img.history_map.size() * 3);
+            for (size_t k = 0; k < img.history_map.size(); ++k) grey.rgb[3 * k] = grey.rgb[3 * k + 1] = grey.rgb[3 * k + 2] = img.history_map[k];
+            grey.save(history_map);
+        }
         const auto t4 = clock::now();
         if (!report_path.empty()) {
             uint64_t triangles = 0;
             for (const auto& m : scene.triangle_meshes) triangles += m.num_triangles;
             const uint32_t spp = samples_arg_for_report(samples);
-            const double rendered = adaptive || denoise || denoise_guided ? double(rep.adaptive_samples)
+            const double rendered = adaptive || denoise || denoise_guided || frames ? double(rep.adaptive_samples)
                                              : double(width) * double(height) * double(spp - rep.resumed_from_sample);  // path samples of THIS run
             std::string js = "{";
             const auto str = [&](const char* k, const std::string& v) { js += std::string("\"") + k + "\": \"" + json_escape(v) + "\", "; };
@@ -648,6 +745,17 @@ int main(int argc, char** argv) {
             if (denoise_guided) {  // the guided filter's parameters and its time on the GPU (a part of gather_s, behind the feature buffers)
                 num("guided_levels", cfg.guided_levels, "%.0f"), num("guided_colour", cfg.guided_colour, "%.9g"), num("guided_normal", cfg.guided_normal, "%.9g");
                 num("guided_depth", cfg.guided_depth, "%.9g"), num("guided_albedo", cfg.guided_albedo, "%.9g"), num("guided_ms", rep.guided_ms, "%.4f");
+            }
+            if (frames) {  // the stream of frames: its options and the accumulation's time on the GPU, the mean per frame (a part of render_s)
+                num("frames", cfg.frames, "%.0f"), num("temporal_max_history", cfg.temporal_max_history, "%.9g"), num("temporal_depth", cfg.temporal_depth, "%.9g");
+                num("temporal_normal", cfg.temporal_normal, "%.9g"), num("temporal_ms", rep.temporal_ms, "%.4f");
+                js += "\"camera_step\": [";
+                for (int c = 0; c < 3; ++c) {
+                    char b[32];
+                    std::snprintf(b, sizeof(b), "%s%.9g", c ? ", " : "", double(cfg.camera_step[c]));
+                    js += b;
+                }
+                js += "], ";
             }
             if (glare) {  // the glare stage: its options and its time on the GPU
                 num("glare", cfg.glare_intensity, "%.9g"), num("glare_levels", cfg.glare_levels, "%.0f"), num("glare_ms", rep.glare_ms, "%.4f");

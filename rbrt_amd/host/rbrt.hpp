@@ -256,6 +256,7 @@ struct ImageBuffer {
     // a render with RenderConfig::features: the feature buffers of the primary rays, row-major (else empty)
     std::vector<float> feature_albedo, feature_normal;  // 3 floats per pixel
     std::vector<float> feature_depth, feature_coverage; // 1 float per pixel
+    std::vector<uint8_t> history_map;  // a render with RenderConfig::frames: one byte per pixel, the last frame's len * 255 / max_history (else empty)
     void save_features(const std::string& prefix) const;  // PREFIX.albedo.pfm, .normal.pfm, .depth.pfm, .coverage.pfm (colour PFMs; grey as three equal channels)
     void save(const std::string& path) const;  // .png (8-bit RGB) or .ppm by extension
     void save_sample_map(const std::string& path) const;  // the sample map as a grey image, through the same writers
@@ -293,6 +294,7 @@ struct RenderReport {
     double glare_ms = 0.0;  // a render with glare (RenderConfig::glare): rbrt_hip_glare on the GPU, between two events
     double guided_ms = 0.0;  // a render with the guided filter (RenderConfig::denoise_guided): rbrt_hip_scene_denoise_guided, between two events
     double features_ms = 0.0;  // a render with feature buffers (RenderConfig::features): rbrt_hip_render_features, between two events
+    double temporal_ms = 0.0;  // a render of several frames (RenderConfig::frames): rbrt_hip_temporal_accumulate between two events, the mean per frame
 };
 
 struct RenderConfig {  // additions that the reference hard-codes or lacks
@@ -350,6 +352,16 @@ struct RenderConfig {  // additions that the reference hard-codes or lacks
     uint32_t guided_levels = 5;  // (rbrt_guided_opts_default)
     float guided_colour = 2.0f, guided_normal = 0.35f, guided_depth = 0.05f, guided_albedo = 0.1f;
     bool guided_demodulate = true;  // false: RBRT_GUIDED_NO_DEMODULATION
+    // Temporal accumulation (rbrt_hip_temporal_accumulate; the CLI's --frames, --camera-step, --temporal-*): `frames` frames are
+    // rendered and the last one is the image. Frame k has the camera's position and image centre moved by float(k) * camera_step
+    // (float32, per component) and renders with seed + k; each frame goes through the adaptive path's one round that stops
+    // nothing, gives its half images and its feature buffers (feature_samples a pixel), and is accumulated onto the history of
+    // the frames before it. The accumulated halves of the last frame then go through the guided filter (denoise_guided), the
+    // non-local-means filter (denoise) or, with neither, their plain mix. Inherits the adaptive path's refusals; not with
+    // `adaptive` itself; num_samples must be at least 2. 0: one frame without any of this.
+    uint32_t frames = 0;
+    float camera_step[3] = {0.0f, 0.0f, 0.0f};
+    float temporal_max_history = 32.0f, temporal_depth = 0.05f, temporal_normal = 0.35f;  // (rbrt_temporal_opts_default)
 };
 // rbrt_lib::render_scene (lib.rs:75-79): blocks until the image is complete. Runs on the GPU(s)
 // through the C ABI; there is no CPU path.

@@ -325,7 +325,7 @@ struct Plan {
 
 // Refuses what cannot be rendered, in this order, and starts the HIP runtime: nothing that calls HIP may exist before this.
 // adaptive_by: the option that sent the render down the adaptive path, for the messages.
-Plan make_plan(const RenderConfig& cfg, const std::string& adaptive_by, const Camera& cam, const Scene& scene, uint32_t num_samples) {
+Plan make_plan(const RenderConfig& cfg, const std::string& adaptive_by, bool cfg_adaptive_given, const Camera& cam, const Scene& scene, uint32_t num_samples) {
     if (num_samples == 0) throw Error("the number of samples must be at least 1");
     if (cfg.adaptive) {  // (one blocking call of one GPU: rbrt_hip.h "Adaptive sampling")
         if (cfg.n_gpus > 1) throw Error(adaptive_by + " cannot be combined with --gpus > 1");
@@ -339,6 +339,16 @@ Plan make_plan(const RenderConfig& cfg, const std::string& adaptive_by, const Ca
         if (cfg.guided_levels == 0 || cfg.guided_levels > RBRT_GUIDED_MAX_LEVELS) throw Error("--guided-levels must be 1 to 6");
         for (const float k : {cfg.guided_colour, cfg.guided_normal, cfg.guided_depth, cfg.guided_albedo})
             if (!std::isfinite(k) || !(k > 0.0f)) throw Error("--guided-colour, --guided-normal, --guided-depth and --guided-albedo must be finite and above 0");
+        if (cfg.feature_samples == 0 || cfg.feature_samples > 65536u) throw Error("--feature-samples must be 1 to 65536");
+    }
+    if (cfg.frames) {  // (rbrt_hip.h "Temporal accumulation": every frame is one round of the adaptive path on one handle)
+        if (cfg_adaptive_given) throw Error("--frames cannot be combined with --adaptive");
+        if (num_samples < 2) throw Error("--frames needs at least 2 samples (each half image needs one)");
+        for (const float s : cfg.camera_step)
+            if (!std::isfinite(s)) throw Error("--camera-step must be three finite numbers");
+        if (!std::isfinite(cfg.temporal_max_history) || !(cfg.temporal_max_history >= 1.0f)) throw Error("--temporal-max-history must be finite and at least 1");
+        for (const float k : {cfg.temporal_depth, cfg.temporal_normal})
+            if (!std::isfinite(k) || !(k >= 0.0f)) throw Error("--temporal-depth and --temporal-normal must be finite and at least 0");
         if (cfg.feature_samples == 0 || cfg.feature_samples > 65536u) throw Error("--feature-samples must be 1 to 65536");
     }
     if (cfg.features) {  // (of the whole frame, on one handle: rbrt_hip.h "Feature buffers")
@@ -497,6 +507,8 @@ struct Rank {
     void denoise_guided();
     void render_passes();
     void features();
+    void download_features();
+    void temporal();
     void gather_single();
     void gather_rccl();
     void gather_host();
@@ -525,15 +537,17 @@ void Rank::run() {
     setup();
     sh.t_setup[rank] = seconds_since(t_start);
     const auto t_passes = std::chrono::steady_clock::now();
-    if (cfg.adaptive) render_adaptive();
+    if (cfg.frames) temporal();
+    else if (cfg.adaptive) render_adaptive();
     else render_passes();
     if (rank == 0) sh.rep.passes = pass_no;
     // the reference would have panicked on a NaN discriminant (sphere.rs:33): surface it
     if (hs && !err.failed()) err.lib_ok(rbrt_hip_scene_check(hs));
     sh.t_render[rank] = seconds_since(t_passes);
     const auto t_g = std::chrono::steady_clock::now();
-    if (world == 1 && (cfg.features || cfg.denoise_guided)) features();
-    if (world == 1 && cfg.denoise_guided) denoise_guided();  // (in front of glare and the display transform, like denoise)
+    // (a render of several frames has made its feature buffers and filtered its image frame by frame: temporal())
+    if (world == 1 && !cfg.frames && (cfg.features || cfg.denoise_guided)) features();
+    if (world == 1 && !cfg.frames && cfg.denoise_guided) denoise_guided();  // (in front of glare and the display transform, like denoise)
     if (world == 1) gather_single();
     else if (sh.use_rccl) gather_rccl();
     else gather_host();
@@ -701,14 +715,128 @@ void Rank::features() {
     float ms = 0.0f;
     if (timer.elapsed(&ms, err)) sh.rep.features_ms = ms;
     if (err.failed()) return;
-    if (cfg.features) {  // (the guided filter alone reads them on the device: nothing comes to the host)
+    download_features();
+    if (hs && !err.failed()) err.lib_ok(rbrt_hip_scene_check(hs));  // (a NaN discriminant is counted here as in a render)
+}
+
+// d_features to the image, where --features asked for them (the filters alone read them on the device: nothing comes to the host).
+void Rank::download_features() {
+    const size_t n_pixels = size_t(img.width) * img.height;
+    const float* const d_albedo = d_features.as<float>();
+    const float *const d_normal = d_albedo + n_pixels * 3, *const d_depth = d_normal + n_pixels * 3, *const d_coverage = d_depth + n_pixels;
+    if (cfg.features && !err.failed()) {
         img.feature_albedo.resize(n_pixels * 3), img.feature_normal.resize(n_pixels * 3), img.feature_depth.resize(n_pixels), img.feature_coverage.resize(n_pixels);
         err.ok(hipMemcpy(img.feature_albedo.data(), d_albedo, n_pixels * 3 * sizeof(float), hipMemcpyDeviceToHost), "download of the albedo");
         err.ok(hipMemcpy(img.feature_normal.data(), d_normal, n_pixels * 3 * sizeof(float), hipMemcpyDeviceToHost), "download of the normals");
         err.ok(hipMemcpy(img.feature_depth.data(), d_depth, n_pixels * sizeof(float), hipMemcpyDeviceToHost), "download of the depth");
         err.ok(hipMemcpy(img.feature_coverage.data(), d_coverage, n_pixels * sizeof(float), hipMemcpyDeviceToHost), "download of the coverage");
     }
-    if (hs && !err.failed()) err.lib_ok(rbrt_hip_scene_check(hs));  // (a NaN discriminant is counted here as in a render)
+}
+
+// A stream of cfg.frames frames from a camera that moves by cfg.camera_step a frame; the last one is the image. Per frame: the
+// adaptive path's one round that stops nothing (seed + k), its two half images, its feature buffers, and the accumulation onto
+// the history the frame before left; two histories alternate. The accumulated halves of the last frame then go through the
+// guided filter, the non-local-means filter or, with neither, their plain mix (window radius 0), all with the one mix wa every
+// pixel of a one-round render has. The unfiltered image and the feature buffers are the last frame's.
+void Rank::temporal() {
+    if (err.failed() || !npix) return;
+    const size_t n_pixels = size_t(img.width) * img.height, n = job.n();
+    const uint32_t num_samples = job.num_samples;
+    const rbrt_adaptive_opts_t ao = {cfg.adaptive_threshold, cfg.adaptive_min_samples, cfg.adaptive_step, 0u};
+    rbrt_denoise_opts_t dn = {cfg.denoise_window_radius, cfg.denoise_patch_radius, cfg.denoise_strength, 0u};
+    rbrt_feature_opts_t fo;
+    rbrt_feature_opts_default(&fo);
+    fo.samples = cfg.feature_samples;
+    rbrt_temporal_opts_t to;
+    rbrt_temporal_opts_default(&to);
+    to.max_history = cfg.temporal_max_history, to.depth = cfg.temporal_depth, to.normal = cfg.temporal_normal;
+    const size_t history_bytes = rbrt_hip_temporal_history_bytes(img.width, img.height);
+    if (history_bytes == 0) {
+        err.set("--frames: the image is too large for temporal accumulation (2^31 pixels or more)");
+        return;
+    }
+    DeviceBuffer d_half_a, d_half_b, d_history[2], d_length, d_wa;
+    EventTimer timer;
+    if (!(d_features.alloc(n_pixels * 8 * sizeof(float), err, "hipMalloc(feature buffers)") && d_half_a.alloc(n * sizeof(float), err, "hipMalloc(half image)") &&
+          d_half_b.alloc(n * sizeof(float), err, "hipMalloc(half image)") && d_history[0].alloc(history_bytes, err, "hipMalloc(history)") &&
+          d_history[1].alloc(history_bytes, err, "hipMalloc(history)") && d_length.alloc(n_pixels * sizeof(float), err, "hipMalloc(history length)") &&
+          d_wa.alloc(n_pixels * sizeof(float), err, "hipMalloc(mix)") && timer.create(err)))
+        return;
+    float* const d_albedo = d_features.as<float>();
+    float *const d_normal = d_albedo + n_pixels * 3, *const d_depth = d_normal + n_pixels * 3, *const d_coverage = d_depth + n_pixels;
+    RenderReport& rep = sh.rep;
+    rbrt_camera_lens_t lens_prev = job.lens;
+    double ms_sum = 0.0;
+    for (uint32_t k = 0; k < cfg.frames && !err.failed(); ++k) {
+        rbrt_camera_lens_t lens = job.lens;  // (with a thin lens the lens moves with its camera)
+        for (int c = 0; c < 3; ++c) {
+            const float shift = float(k) * cfg.camera_step[c];
+            lens.cam.position[c] = job.lens.cam.position[c] + shift;
+            lens.cam.img_center_point[c] = job.lens.cam.img_center_point[c] + shift;
+        }
+        rbrt_render_opts_t ok = o;
+        ok.seed = o.seed + k;  // (the same seed would accumulate the same noise)
+        rbrt_adaptive_result_t ar{};
+        if (!err.lib_ok(rbrt_hip_render_adaptive(hs, &lens.cam, &ok, &ao, stream.get(), d_rad.as<float>(), d_rgb.as<uint8_t>(), nullptr, nullptr, &ar))) break;
+        rep.adaptive_rounds = ar.rounds, rep.adaptive_samples += ar.samples, rep.adaptive_samples_fixed += ar.samples_fixed;
+        if (!err.lib_ok(rbrt_hip_scene_denoise(hs, &dn, stream.get(), nullptr, nullptr, d_half_a.as<float>(), d_half_b.as<float>()))) break;
+        if (!err.lib_ok(rbrt_hip_render_features(hs, &lens.cam, &ok, &fo, stream.get(), d_albedo, d_normal, d_depth, d_coverage, nullptr))) break;
+        timer.start(stream.get(), err);
+        err.lib_ok(rbrt_hip_temporal_accumulate(dev, stream.get(), d_half_a.as<float>(), d_half_b.as<float>(), d_normal, d_depth, d_coverage, &lens.cam,
+                                                k ? &lens_prev.cam : nullptr, &to, k ? d_history[(k - 1u) & 1u].as<void>() : nullptr,
+                                                d_history[k & 1u].as<void>(), d_half_a.as<float>(), d_half_b.as<float>(),
+                                                k + 1u == cfg.frames ? d_length.as<float>() : nullptr));
+        timer.stop(stream.get(), err);
+        err.ok(hipStreamSynchronize(stream.get()), "frame");
+        float ms = 0.0f;
+        if (timer.elapsed(&ms, err)) ms_sum += ms;
+        if (hs && !err.failed()) err.lib_ok(rbrt_hip_scene_check(hs));
+        lens_prev = lens;
+        ++pass_no;
+        if (!cfg.quiet) {
+            std::printf("\rRendering %.1f%% complete!", double(k + 1u) / double(cfg.frames) * 100.0);
+            std::fflush(stdout);
+        }
+    }
+    if (err.failed()) return;
+    rep.temporal_ms = ms_sum / double(cfg.frames);
+    keep_noisy();
+    download_features();
+    // the history length of the last frame, as a share of the longest there can be
+    std::vector<float> length(n_pixels);
+    if (err.ok(hipMemcpy(length.data(), d_length.as<float>(), n_pixels * sizeof(float), hipMemcpyDeviceToHost), "download of the history length")) {
+        img.history_map.resize(n_pixels);
+        for (size_t i = 0; i < n_pixels; ++i) {
+            const float v = (length[i] / cfg.temporal_max_history) * 255.0f;
+            img.history_map[i] = !(v == v) || v <= 0.0f ? 0 : v >= 255.0f ? 255 : uint8_t(v);
+        }
+    }
+    // every pixel of a one-round render has the same count n: h = (n + 1) / 2 samples in A, so wa = float(h) * (1.0f / float(n))
+    const float inv_n = 1.0f / float(num_samples);
+    const std::vector<float> wa(n_pixels, float((num_samples + 1u) / 2u) * inv_n);
+    if (!err.ok(hipMemcpy(d_wa.as<float>(), wa.data(), n_pixels * sizeof(float), hipMemcpyHostToDevice), "upload of the mix")) return;
+    if (cfg.denoise_guided) {
+        const rbrt_guided_opts_t g = {cfg.guided_levels, cfg.guided_colour, cfg.guided_normal, cfg.guided_depth, cfg.guided_albedo,
+                                      cfg.guided_demodulate ? 0u : RBRT_GUIDED_NO_DEMODULATION, {0u, 0u}};
+        DeviceBuffer d_workspace;
+        if (!d_workspace.alloc(rbrt_hip_guided_workspace_bytes(img.width, img.height), err, "hipMalloc(guided workspace)")) return;
+        timer.start(stream.get(), err);
+        err.lib_ok(rbrt_hip_denoise_guided(dev, stream.get(), d_half_a.as<float>(), d_half_b.as<float>(), d_wa.as<float>(), d_albedo, d_normal, d_depth,
+                                           d_coverage, img.width, img.height, &g, d_workspace.as<void>(), d_rad.as<float>(), d_rgb.as<uint8_t>()));
+        timer.stop(stream.get(), err);
+        err.ok(hipStreamSynchronize(stream.get()), "guided denoise");
+        float ms = 0.0f;
+        if (timer.elapsed(&ms, err)) rep.guided_ms = ms;
+    } else {
+        if (!cfg.denoise) dn.window_radius = 0u;  // exactly A * wa + B * (1 - wa)
+        timer.start(stream.get(), err);
+        err.lib_ok(rbrt_hip_denoise_halves(dev, stream.get(), d_half_a.as<float>(), d_half_b.as<float>(), d_wa.as<float>(), img.width, img.height, &dn,
+                                           d_rad.as<float>(), d_rgb.as<uint8_t>()));
+        timer.stop(stream.get(), err);
+        err.ok(hipStreamSynchronize(stream.get()), "denoise");
+        float ms = 0.0f;
+        if (timer.elapsed(&ms, err) && cfg.denoise) rep.denoise_ms = ms;
+    }
 }
 
 // Glare and the display transform on this rank's device, of the complete image that is d_src there.
@@ -858,7 +986,7 @@ void report_times(const Plan& plan, const Shared& sh, RenderReport& rep) {
 
 ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& scene, const RenderConfig& cfg_in) {
     RenderConfig cfg = cfg_in;
-    if ((cfg.denoise || cfg.denoise_guided) && !cfg.adaptive)  // (the filter's input is the adaptive path's sums: one round that stops nothing)
+    if ((cfg.denoise || cfg.denoise_guided || cfg.frames) && !cfg.adaptive)  // (the filter's input is the adaptive path's sums: one round that stops nothing)
         cfg.adaptive = true, cfg.adaptive_threshold = 0.0f, cfg.adaptive_min_samples = cfg.adaptive_step = std::max(num_samples, 2u);
     if (!cfg.quiet) std::printf("Starting rendering...\n");
     ImageBuffer img;
@@ -871,7 +999,8 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
     const rbrt_camera_lens_t lens = cam.to_abi_lens();
     const Scene::AbiView view = scene.to_abi();
     const rbrt_environment_t env_abi = scene.environment.to_abi();
-    const Plan plan = make_plan(cfg, cfg_in.adaptive ? "--adaptive" : cfg_in.denoise_guided ? "--denoise-guided" : "--denoise", cam, scene, num_samples);
+    const Plan plan = make_plan(cfg, cfg_in.adaptive ? "--adaptive" : cfg_in.frames ? "--frames" : cfg_in.denoise_guided ? "--denoise-guided" : "--denoise", cfg_in.adaptive,
+                                cam, scene, num_samples);
     Job job{cfg, plan, lens, view, scene.environment.n != 0u ? &env_abi : nullptr, render_opts_of(cfg, cam, num_samples), num_samples, {}, {}, img};
     job.want = checkpoint_header(img.width, img.height, num_samples, uint32_t(plan.world), cfg.seed,
                                  checkpoint_fingerprint(cfg.checkpoint_path, lens, job.opts, view.scene, view.shading_ptr(), scene.environment));

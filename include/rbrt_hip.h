@@ -70,7 +70,10 @@ extern "C" {
                               rbrt_hip_denoise_guided and rbrt_hip_scene_denoise_guided: an added struct and entry points,
                               detected by the symbol), nor temporal accumulation (rbrt_temporal_opts_t,
                               rbrt_temporal_opts_default, rbrt_hip_temporal_history_bytes and rbrt_hip_temporal_accumulate:
-                              an added struct and entry points, detected by the symbol) */
+                              an added struct and entry points, detected by the symbol), nor guided upsampling
+                              (rbrt_upsample_opts_t, rbrt_upsample_opts_default, rbrt_hip_upsample_camera,
+                              rbrt_hip_upsample_workspace_bytes and rbrt_hip_upsample_halves: an added struct and entry
+                              points, detected by the symbol) */
 
 typedef enum rbrt_status {
     RBRT_OK = 0,
@@ -852,6 +855,97 @@ int rbrt_hip_temporal_accumulate(int device, void* stream, const float* d_a, con
                                  const float* d_depth, const float* d_coverage, const rbrt_camera_t* cam,
                                  const rbrt_camera_t* cam_prev, const rbrt_temporal_opts_t* opts, const void* d_history_in,
                                  void* d_history_out, float* d_out_a, float* d_out_b, float* d_out_length);
+
+/* ---- Guided upsampling: trace a smaller image, reconstruct the full one from the full-size feature buffers -------------------
+ * No counterpart in the reference. The trace kernel's cost is proportional to the pixel count; the feature buffers are cheap.
+ * So the image is traced with a camera of 1 / f the size in each direction (rbrt_hip_upsample_camera; an ordinary render), the
+ * features are made at full size, and every full pixel takes its two half images from the four low pixels around it, each
+ * weighed by its bilinear weight times how well the low pixel's features agree with the full pixel's: a joint bilateral
+ * upsampling (Kopf, Cohen, Lischinski and Uyttendaele 2007) with the guided filter's distances and weight. The albedo is
+ * divided out at low size and multiplied back at full size, so an albedo edge is as sharp as the feature buffers. A and B get
+ * the same weights and the weights come from the features only, never from the noise: the halves stay independent estimates
+ * and what both denoisers derive from A - B stays valid. The outputs go into rbrt_hip_temporal_accumulate,
+ * rbrt_hip_denoise_halves or rbrt_hip_denoise_guided unchanged.
+ *
+ * The low camera. f in 1..RBRT_UPSAMPLE_MAX_FACTOR; w = (W + f - 1) / f, h = (H + f - 1) / f (integer division). `low` is `full`
+ * except for the size (w, h), mm_per_pix_* = float(f) * mm_per_pix_*, and img_center_point, which is shifted so that low pixel
+ * (j, i)'s footprint on the image plane is exactly the union of the footprints of the full pixels of its block (below; where W
+ * or H is no multiple of f the last low pixels reach beyond the full image). The render centres pixel col on col - W / 2
+ * (integer halving) and jitters by u - 0.5, so in float32, unfused, in this order:
+ *     kx = (float(f * (w / 2)) - float(W / 2)) + (0.5f * float(f - 1));  ky likewise from h and H;
+ *     c' = (c + ((0.001f * (kx * mm_per_pix_hor)) * right)) - ((0.001f * (ky * mm_per_pix_vert)) * up), per component.
+ * Low pixel i's centre then lies on full coordinate i * f + (f - 1) / 2. A thin lens keeps lens_u, lens_v and focus_scale: the
+ * caller wraps the low camera in its own rbrt_camera_lens_t.
+ *
+ * The rule. All arithmetic is float32, unfused, in the written order; / is correctly rounded; a constant is the float32
+ * nearest to the decimal written; a sum "from 0" starts at 0.0f and adds its terms one at a time in the stated order;
+ * max(x, y) is C's fmaxf: the other operand when one is a NaN.
+ *   Inputs.  Low half images a, b, float[h][w][3]; their mix wa, float[h][w] (NULL: 0.5 everywhere); the full-size albedo rho
+ *     and normal N, float[H][W][3], depth z and coverage c, float[H][W], as rbrt_hip_render_features writes them for the full
+ *     camera; the factor f; the sigmas normal kn, depth kz, albedo ka; flags. On the host: in = 1.0f / (kn * kn),
+ *     ia = 1.0f / (ka * ka), kz2 = kz * kz, invf = 1.0f / float(f). eps = 1e-7f, floor = 0.01f.
+ *   Reduce, per low pixel q = (j, i) (row, column). Its block is the full pixels of the rows j * f .. min(j * f + f, H) - 1 and
+ *     the columns i * f .. min(i * f + f, W) - 1; cnt is their number; inv = 1.0f / float(cnt).
+ *     Each of the eight feature channels: x_l[q] = (the sum of x over the block, rows outer, columns inner, from 0) * inv. That
+ *       gives rho_l, N_l, z_l, c_l: the features the low pixel's own samples would have seen, because the footprints coincide.
+ *     m_l = max(rho_l + (1.0f - c_l), floor) per channel (the guided filter's effective albedo).
+ *     u_l = m_l, or 1.0f with RBRT_UPSAMPLE_NO_DEMODULATION (m guides the weights either way).
+ *     a~ = a / u_l;  b~ = b / u_l.
+ *   Gather, per full pixel p = (R, C) (row, column).
+ *     m = max(rho + (1.0f - c), floor) per channel; u = m, or 1.0f with the flag.
+ *     xl = ((float(C) + 0.5f) * invf) - 0.5f;  i = floor(xl);  fx = xl - float(i);  gx = 1.0f - fx.
+ *     Rows likewise from R: j, fy, gy.
+ *     Four taps in this order, each with a bilinear weight bw: (j, i) with gx * gy; (j, i + 1) with fx * gy; (j + 1, i) with
+ *     gx * fy; (j + 1, i + 1) with fx * fy. Each tap index is clamped into the low image as an integer (the edges are
+ *     replicated): that is q.
+ *       n = N_l[q] - N[p];     Dn = (((n_x * n_x) + (n_y * n_y)) + (n_z * n_z)) * in
+ *       d = m_l[q] - m[p];     Da = (((d_r * d_r) + (d_g * d_g)) + (d_b * d_b)) * ia
+ *       dz = z_l[q] - z[p];    Dz = (dz * dz) / (eps + (kz2 * (z[p] * z_l[q])))
+ *       D = (Dn + Dz) + Da;    g = max(0, 1 - 0.25f * max(D, 0));    wt = bw * ((g * g) * (g * g))
+ *     (the distances and the weight of "Guided denoising" above). A tap is added only if wt > 0 (a NaN compares false). Sums
+ *     from 0 over the added taps, in tap order: den += wt; na_c += wt * a~_c[q]; nb_c += wt * b~_c[q]; nw += wt * wa[q].
+ *   Result.  If den >= 0.01f: A_c = (na_c / den) * u_c; B_c = (nb_c / den) * u_c; wa' = nw / den.
+ *     Else the fallback, with q0 = (R / f, C / f) by integer division, the low pixel whose block holds p:
+ *     A_c = a~_c[q0] * u_c; B_c = b~_c[q0] * u_c; wa' = wa[q0].
+ * Consequences. A tap with zero weight never influences any output, whatever it holds, NaN and infinities included; the
+ * fallback pixel q0 of a pixel without enough weight does. Every index comes from integers and from floors of finite values
+ * made from integers, clamped as integers, so no read leaves the buffers whatever the floats are. With f = 1, the flag set and
+ * finite features the output is the input bit for bit (but for a -0 in a or b, which comes out as +0). Light does not cross
+ * an edge of the features: changing the low pixels on one side changes nothing on the other but fallback pixels. */
+#define RBRT_UPSAMPLE_MAX_FACTOR 4u
+#define RBRT_UPSAMPLE_NO_DEMODULATION 1u /* flags: interpolate the radiance itself (u = 1); the albedo still guides the weights */
+typedef struct rbrt_upsample_opts {
+    uint32_t factor;              /* f, 1..RBRT_UPSAMPLE_MAX_FACTOR */
+    float normal, depth, albedo;  /* kn, kz, ka: finite, > 0; larger lets more through */
+    uint32_t flags;               /* RBRT_UPSAMPLE_* */
+    uint32_t reserved[3];         /* 0 */
+} rbrt_upsample_opts_t;
+void rbrt_upsample_opts_default(rbrt_upsample_opts_t* opts); /* f = 2, kn = 0.5, kz = 0.1, ka = 0.2, flags 0 */
+
+/* The low camera of the rule above, on the host alone: no device is touched.
+ * RBRT_ERR_INVALID_ARG: full or low NULL; factor 0 or above RBRT_UPSAMPLE_MAX_FACTOR; an image without pixels; an mm_per_pix
+ * that is not finite. `low` may be `full` itself. */
+int rbrt_hip_upsample_camera(const rbrt_camera_t* full, uint32_t factor, rbrt_camera_t* low);
+
+/* Bytes of workspace rbrt_hip_upsample_halves needs for a width x height (full-size) image at `factor`: the packed low
+ * records in the library's own layout, four planes of one 16-byte record a low pixel, {a~, wa}, {b~, z_l}, {N_l, c_l},
+ * {m_l, 0}: 64 bytes a low pixel, so that a tap is four aligned 16-byte loads. 0 for what the call refuses. */
+size_t rbrt_hip_upsample_workspace_bytes(uint32_t width, uint32_t height, uint32_t factor);
+
+/* The rule on buffers in DEVICE memory, all row-major. width and height are the FULL size W, H; d_a, d_b are float[h][w][3] and
+ * d_wa float[h][w] at the low size of opts->factor (d_wa NULL: 0.5 everywhere); the feature buffers are full size; the outputs
+ * are full size, d_out_a and d_out_b float[H][W][3], d_out_wa float[H][W]. Any output may be NULL; with all three NULL nothing
+ * is launched. Needs no scene, owns no device memory, asynchronous on `stream`: d_workspace is the caller's,
+ * rbrt_hip_upsample_workspace_bytes(width, height, factor) bytes, 16-byte aligned; nothing is assumed about its contents, and
+ * calls on different streams need different workspaces. No input may overlap an output or the workspace.
+ * RBRT_ERR_INVALID_ARG, before the device is touched: d_a, d_b, d_albedo, d_normal, d_depth, d_coverage, opts or d_workspace
+ * NULL; width or height 0; factor 0 or above RBRT_UPSAMPLE_MAX_FACTOR; a sigma that is not finite or <= 0; an unknown flag bit;
+ * a non-zero reserved word; a workspace that is not 16-byte aligned.
+ * RBRT_ERR_UNSUPPORTED: width * height >= 2^31. */
+int rbrt_hip_upsample_halves(int device, void* stream, const float* d_a, const float* d_b, const float* d_wa,
+                             const float* d_albedo, const float* d_normal, const float* d_depth, const float* d_coverage,
+                             uint32_t width, uint32_t height, const rbrt_upsample_opts_t* opts, void* d_workspace,
+                             float* d_out_a, float* d_out_b, float* d_out_wa);
 
 /* De-interleave gathered per-rank packed tile buffers (concatenated rank 0..world-1, each
  * rbrt_hip_packed_pixels(...)*3 floats, device memory) into a row-major float[H][W][3] device

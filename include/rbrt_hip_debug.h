@@ -73,6 +73,12 @@ int rbrt_hip_debug_guided_staging(int max_step);
  * workgroup is added (tests/test_temporal_gpu.py). */
 #define RBRT_TEMPORAL_BLOCK 256u
 
+/* The guided upsampling's gather kernel (rbrt_amd/csrc/upsample.hip): the tile of FULL pixels one workgroup makes, whose low
+ * pixels it stages in LDS. Sizes around it, and twice it so that an interior workgroup exists, are where that kernel's paths
+ * change (tests/test_upsample_gpu.py). The reduce kernel has no tile: a workgroup takes 256 consecutive low pixels. */
+#define RBRT_UPSAMPLE_TILE_W 32u
+#define RBRT_UPSAMPLE_TILE_H 8u
+
 /* The display transform's kernels (rbrt_amd/csrc/tonemap.hip): the pixels one workgroup takes per stride of its grid, and the
  * cap of that grid. Pixel counts around BLOCK_PIXELS, and around MAX_BLOCKS * BLOCK_PIXELS where a workgroup starts to stride a
  * second time, are where those kernels' paths change (tests/test_tonemap_gpu.py). */

@@ -514,6 +514,47 @@ def temporal_accumulate(device: int, d_a: int, d_b: int, d_normal: int, d_depth:
                                                       C.c_void_p(d_out_a or 0), C.c_void_p(d_out_b or 0), C.c_void_p(d_out_length or 0)))
 
 
+def upsample_opts(factor: int | None = None, normal: float | None = None, depth: float | None = None, albedo: float | None = None,
+                  flags: int | None = None, reserved=(0, 0, 0)) -> abi.UpsampleOpts:
+    """rbrt_upsample_opts_default (factor 2, normal 0.5, depth 0.1, albedo 0.2, flags 0), with the parameters that are given put in."""
+    t = abi.UpsampleOpts()
+    load_hip().rbrt_upsample_opts_default(C.byref(t))
+    for name, value, kind in (("factor", factor, int), ("normal", normal, float), ("depth", depth, float), ("albedo", albedo, float),
+                              ("flags", flags, int)):
+        if value is not None:
+            setattr(t, name, kind(value))
+    for k in range(3):
+        t.reserved[k] = int(reserved[k])
+    return t
+
+
+def upsample_workspace_bytes(width: int, height: int, factor: int) -> int:
+    """rbrt_hip_upsample_workspace_bytes: the workspace of upsample_halves() for a width x height full-size image; 0 for what it refuses."""
+    return int(load_hip().rbrt_hip_upsample_workspace_bytes(width, height, factor))
+
+
+def upsample_camera(cam: abi.Camera, factor: int) -> abi.Camera:
+    """rbrt_hip_upsample_camera: the camera of the low image whose pixels' footprints are the unions of `cam`'s f x f blocks."""
+    low = abi.Camera()
+    abi.check(load_hip().rbrt_hip_upsample_camera(C.byref(cam) if cam is not None else None, factor, C.byref(low)))
+    return low
+
+
+def upsample_halves(device: int, d_a: int, d_b: int, d_wa: int | None, d_albedo: int, d_normal: int, d_depth: int, d_coverage: int,
+                    width: int, height: int, d_workspace: int, d_out_a: int | None = None, d_out_b: int | None = None,
+                    d_out_wa: int | None = None, opts: abi.UpsampleOpts | None = None, stream: int | None = None):
+    """Guided upsampling in device memory (rbrt_hip_upsample_halves): d_a, d_b float32 [h, w, 3] and d_wa float32 [h, w] (None: 0.5
+    everywhere) at the low size of opts.factor; the features and the outputs at the full size width x height; d_workspace
+    upsample_workspace_bytes(width, height, factor) bytes, 16-byte aligned. `opts`: upsample_opts(...), None for the library's
+    defaults. Asynchronous on `stream`."""
+    t = opts if opts is not None else upsample_opts()
+    abi.check(load_hip().rbrt_hip_upsample_halves(device, C.c_void_p(stream or 0), C.c_void_p(d_a or 0), C.c_void_p(d_b or 0),
+                                                  C.c_void_p(d_wa or 0), C.c_void_p(d_albedo or 0), C.c_void_p(d_normal or 0),
+                                                  C.c_void_p(d_depth or 0), C.c_void_p(d_coverage or 0), width, height, C.byref(t),
+                                                  C.c_void_p(d_workspace or 0), C.c_void_p(d_out_a or 0), C.c_void_p(d_out_b or 0),
+                                                  C.c_void_p(d_out_wa or 0)))
+
+
 def tonemap_opts(curve: int | None = None, exposure: float | None = None, key: float | None = None,
                  key_permille: int | None = None, white: float | None = None, white_permille: int | None = None,
                  reserved=(0, 0)) -> abi.TonemapOpts:

@@ -44,6 +44,11 @@ GUIDED_NO_DEMODULATION = 1   # rbrt_hip.h: RBRT_GUIDED_NO_DEMODULATION
 GUIDED_MAX_LEVELS = 6        # rbrt_hip.h: the most levels of the guided denoiser
 TEMPORAL_HISTORY_BYTES_PER_PIXEL = 48  # rbrt_hip.h: three 16-byte records {A', len}, {B', c}, {N, z}
 TEMPORAL_BLOCK = 256         # rbrt_hip_debug.h: consecutive pixels a workgroup of the temporal kernel takes
+UPSAMPLE_MAX_FACTOR = 4      # rbrt_hip.h: RBRT_UPSAMPLE_MAX_FACTOR
+UPSAMPLE_NO_DEMODULATION = 1  # rbrt_hip.h: RBRT_UPSAMPLE_NO_DEMODULATION
+UPSAMPLE_WORKSPACE_BYTES_PER_LOW_PIXEL = 64  # rbrt_hip.h: four 16-byte records {a~, wa}, {b~, z_l}, {N_l, c_l}, {m_l, 0}
+UPSAMPLE_TILE_W = 32         # rbrt_hip_debug.h: the tile of full pixels one workgroup of the upsampling's gather kernel makes
+UPSAMPLE_TILE_H = 8
 GLARE_MAX_LEVELS = 8         # rbrt_hip.h: the most levels of the glare stage's pyramid
 GLARE_TILE_W = 16            # rbrt_hip_debug.h: the tile of a pyramid level one workgroup of the REDUCE kernel makes
 GLARE_TILE_H = 16
@@ -197,6 +202,11 @@ class TemporalOpts(C.Structure):  # rbrt_temporal_opts_t
                 ("reserved", C.c_uint32 * 4)]
 
 
+class UpsampleOpts(C.Structure):  # rbrt_upsample_opts_t
+    _fields_ = [("factor", C.c_uint32), ("normal", C.c_float), ("depth", C.c_float), ("albedo", C.c_float), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 3)]
+
+
 class Environment(C.Structure):  # rbrt_environment_t
     """An octahedral radiance map of (n + 1) x (n + 1) nodes: `nodes` points at host float32 [n + 1][n + 1][3]."""
     _fields_ = [("n", C.c_uint32), ("reserved", C.c_uint32), ("nodes", f32p)]
@@ -290,6 +300,12 @@ HIP_SYMBOLS = {
     "rbrt_hip_temporal_accumulate": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.POINTER(Camera), C.POINTER(Camera), C.POINTER(TemporalOpts), C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rbrt_upsample_opts_default": (None, [C.POINTER(UpsampleOpts)]),
+    "rbrt_hip_upsample_camera": (C.c_int, [C.POINTER(Camera), C.c_uint32, C.POINTER(Camera)]),
+    "rbrt_hip_upsample_workspace_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint32]),
+    "rbrt_hip_upsample_halves": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(UpsampleOpts), C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
 }
 # ... and include/rbrt_hip_debug.h (test hooks and diagnostics, same library)
 DEBUG_SYMBOLS = {

@@ -45,6 +45,7 @@ hipError_t launch_tonemap(const TonemapParams& T, hipStream_t stream);          
 hipError_t launch_glare(const GlareParams& G, hipStream_t stream);                     // glare.hip
 hipError_t launch_guided(const GuidedParams& G, uint32_t staged_max_step, hipStream_t stream);  // guided.hip
 hipError_t launch_temporal(const TemporalParams& T, hipStream_t stream);                // temporal.hip
+hipError_t launch_upsample(const UpsampleParams& U, hipStream_t stream);                // upsample.hip
 hipError_t launch_unpack(const float* gathered, uint32_t width, uint32_t height, uint32_t world,
                          size_t rank_stride_pixels, float* out_radiance, uint8_t* out_rgb8, hipStream_t stream);
 hipError_t launch_trace_rays(const TraceParams& P, const float* rays, size_t n, float* out_t, int32_t* out_obj,
@@ -2463,6 +2464,76 @@ int rbrt_hip_temporal_accumulate(int device, void* stream, const float* d_a, con
     if (int rc = ensure_device(device)) return rc;
     if (!d_history_out && !d_out_a && !d_out_b && !d_out_length) return RBRT_OK;
     HIP_TRY(launch_temporal(T, static_cast<hipStream_t>(stream)));
+    return RBRT_OK;
+}
+
+// ---- Guided upsampling (the rule: include/rbrt_hip.h; the kernels: upsample.hip) ----------------------------------------------
+void rbrt_upsample_opts_default(rbrt_upsample_opts_t* o) {
+    if (!o) return;
+    o->factor = 2u, o->normal = 0.5f, o->depth = 0.1f, o->albedo = 0.2f, o->flags = 0u;
+    for (uint32_t& r : o->reserved) r = 0u;
+}
+
+int rbrt_hip_upsample_camera(const rbrt_camera_t* full, uint32_t factor, rbrt_camera_t* low) {
+    if (!full || !low) return fail(RBRT_ERR_INVALID_ARG, "upsample_camera: null argument");
+    if (factor == 0u || factor > RBRT_UPSAMPLE_MAX_FACTOR) return fail(RBRT_ERR_INVALID_ARG, "upsample_camera: factor must be 1..4");
+    const uint32_t W = full->img_width_pix, H = full->img_height_pix;
+    if (W == 0u || H == 0u) return fail(RBRT_ERR_INVALID_ARG, "upsample_camera: width and height must be >= 1");
+    if (!std::isfinite(full->mm_per_pix_hor) || !std::isfinite(full->mm_per_pix_vert))
+        return fail(RBRT_ERR_INVALID_ARG, "upsample_camera: mm_per_pix must be finite");
+    const uint32_t f = factor;
+    const uint32_t w = uint32_t((uint64_t(W) + f - 1u) / f), h = uint32_t((uint64_t(H) + f - 1u) / f);
+    // the rule's shift, in float, one operation a statement (this file is compiled with -ffp-contract=off)
+    const float half = 0.5f * float(f - 1u);
+    const float dx = float(f * (w / 2u)) - float(W / 2u), dy = float(f * (h / 2u)) - float(H / 2u);
+    const float kx = dx + half, ky = dy + half;
+    const float mx = kx * full->mm_per_pix_hor, my = ky * full->mm_per_pix_vert;
+    const float sx = 0.001f * mx, sy = 0.001f * my;
+    rbrt_camera_t out = *full;
+    for (int k = 0; k < 3; ++k) {
+        const float r = sx * full->right[k], u = sy * full->up[k];
+        const float cr = full->img_center_point[k] + r;
+        out.img_center_point[k] = cr - u;
+    }
+    out.mm_per_pix_hor = float(f) * full->mm_per_pix_hor, out.mm_per_pix_vert = float(f) * full->mm_per_pix_vert;
+    out.img_width_pix = w, out.img_height_pix = h;
+    *low = out;
+    return RBRT_OK;
+}
+
+size_t rbrt_hip_upsample_workspace_bytes(uint32_t width, uint32_t height, uint32_t factor) {
+    if (width == 0u || height == 0u || factor == 0u || factor > RBRT_UPSAMPLE_MAX_FACTOR || uint64_t(width) * height >= (1ull << 31)) return 0;
+    const size_t w = (size_t(width) + factor - 1u) / factor, h = (size_t(height) + factor - 1u) / factor;
+    return w * h * 64u;  // (the layout of upsample.hip: four planes of one float4 a low pixel)
+}
+
+int rbrt_hip_upsample_halves(int device, void* stream, const float* d_a, const float* d_b, const float* d_wa, const float* d_albedo,
+                             const float* d_normal, const float* d_depth, const float* d_coverage, uint32_t width, uint32_t height,
+                             const rbrt_upsample_opts_t* o, void* d_workspace, float* d_out_a, float* d_out_b, float* d_out_wa) {
+    if (!d_a || !d_b || !d_albedo || !d_normal || !d_depth || !d_coverage || !o || !d_workspace)
+        return fail(RBRT_ERR_INVALID_ARG, "upsample_halves: null argument");
+    if (width == 0u || height == 0u) return fail(RBRT_ERR_INVALID_ARG, "upsample_halves: width and height must be >= 1");
+    if (o->factor == 0u || o->factor > RBRT_UPSAMPLE_MAX_FACTOR) return fail(RBRT_ERR_INVALID_ARG, "upsample_halves: factor must be 1..4");
+    for (const float k : {o->normal, o->depth, o->albedo})
+        if (!positive_finite(k)) return fail(RBRT_ERR_INVALID_ARG, "upsample_halves: normal, depth and albedo must be finite and > 0");
+    if ((o->flags & ~RBRT_UPSAMPLE_NO_DEMODULATION) != 0u) return fail(RBRT_ERR_INVALID_ARG, "upsample_halves: unknown flag bit");
+    for (const uint32_t r : o->reserved)
+        if (r != 0u) return fail(RBRT_ERR_INVALID_ARG, "upsample_halves: reserved must be 0");
+    if (reinterpret_cast<uintptr_t>(d_workspace) % 16u != 0u) return fail(RBRT_ERR_INVALID_ARG, "upsample_halves: the workspace must be 16-byte aligned");
+    if (uint64_t(width) * height >= (1ull << 31)) return fail(RBRT_ERR_UNSUPPORTED, "upsample_halves: 2^31 or more pixels");
+
+    UpsampleParams U;
+    std::memset(&U, 0, sizeof(U));
+    U.a = d_a, U.b = d_b, U.wa = d_wa, U.albedo = d_albedo, U.normal = d_normal, U.depth = d_depth, U.coverage = d_coverage;
+    U.workspace = d_workspace, U.out_a = d_out_a, U.out_b = d_out_b, U.out_wa = d_out_wa;
+    U.width = width, U.height = height, U.factor = o->factor, U.flags = o->flags;
+    U.low_width = (width + o->factor - 1u) / o->factor, U.low_height = (height + o->factor - 1u) / o->factor;
+    // the rule's constants, in float, one operation a statement
+    const float kn2 = o->normal * o->normal, ka2 = o->albedo * o->albedo;
+    U.in = 1.0f / kn2, U.ia = 1.0f / ka2, U.kz2 = o->depth * o->depth, U.invf = 1.0f / float(o->factor);
+    if (int rc = ensure_device(device)) return rc;
+    if (!d_out_a && !d_out_b && !d_out_wa) return RBRT_OK;
+    HIP_TRY(launch_upsample(U, static_cast<hipStream_t>(stream)));
     return RBRT_OK;
 }
 

@@ -355,4 +355,23 @@ struct TemporalParams {
     float wn, rr, uu, ru, det, sx, sy, hx, hy;
 };
 
+// Guided upsampling (include/rbrt_hip.h "Guided upsampling"; upsample.hip): one rbrt_hip_upsample_halves call.
+struct UpsampleParams {
+    const float* a;             // [h][w][3] the low half images
+    const float* b;
+    const float* wa;            // [h][w], may be null: 0.5 everywhere
+    const float* albedo;        // [H][W][3] the full-size features
+    const float* normal;        // [H][W][3]
+    const float* depth;         // [H][W]
+    const float* coverage;      // [H][W]
+    void* workspace;            // four planes of w * h float4: {a~, wa}, {b~, z_l}, {N_l, c_l}, {m_l, 0}
+    float* out_a;               // [H][W][3], may be null
+    float* out_b;               // [H][W][3], may be null
+    float* out_wa;              // [H][W], may be null
+    uint32_t width, height;     // W, H: W * H < 2^31
+    uint32_t low_width, low_height;  // w = (W + f - 1) / f, h likewise
+    uint32_t factor, flags;     // f in 1..RBRT_UPSAMPLE_MAX_FACTOR
+    float in, ia, kz2, invf;    // 1 / (kn * kn), 1 / (ka * ka), kz * kz, 1 / float(f)
+};
+
 }  // namespace rbrt

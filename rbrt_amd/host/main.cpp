@@ -21,6 +21,8 @@
 // a-trous filter of the render's two half images, guided by those feature buffers). --frames N with --camera-step DX,DY,DZ,
 // --temporal-max-history M, --temporal-depth K, --temporal-normal K and --history-map FILE (a stream of N frames from a moving
 // camera: every frame's half images are accumulated onto the reprojected ones of the frames before it, the last frame is written).
+// --upscale F with --upscale-normal K, --upscale-depth K and --upscale-albedo K (the image is traced at 1 / F of its size in each
+// direction and its two half images are brought to full size under the guidance of the full-size feature buffers).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -107,6 +109,16 @@ void usage() {
         "      --temporal-normal <k>        frames: tolerance of the normal's difference, 0 or more [default: 0.35]\n"
         "      --history-map <file>         frames: write the last frame's history length over --temporal-max-history there as a\n"
         "                                   grey image (same formats as the target file)\n"
+        "      --upscale <f>                trace the image at 1 / f of its width and height, f 2 to 4, and reconstruct the full size:\n"
+        "                                   the two half images of the small render are interpolated to --width x --height with\n"
+        "                                   weights from the feature buffers of the full-size primary rays (guided upsampling).\n"
+        "                                   Renders like --denoise and cannot be combined with --adaptive, --gpus > 1,\n"
+        "                                   --checkpoint, --pass-samples or --sample-map; --samples must be at least 2;\n"
+        "                                   --frames, --denoise or --denoise-guided work on the full-size half images;\n"
+        "                                   --noisy writes their plain mix; --feature-samples applies\n"
+        "      --upscale-normal <k>         upscale: tolerance of the normal's difference, above 0 [default: 0.5]\n"
+        "      --upscale-depth <k>          upscale: tolerance of the relative depth difference, above 0 [default: 0.1]\n"
+        "      --upscale-albedo <k>         upscale: tolerance of the albedo's difference, above 0 [default: 0.2]\n"
         "      --exposure <EV|auto>         exposure of the target image in stops (the radiance is multiplied by 2^EV), or auto:\n"
         "                                   the median luminance of the image is mapped to --exposure-key [default: 0]\n"
         "      --exposure-key <x>           automatic exposure: what the median luminance is mapped to, above 0 [default: 0.18]\n"
@@ -239,6 +251,8 @@ int main(int argc, char** argv) {
     float camera_step[3] = {0.0f, 0.0f, 0.0f};
     bool camera_step_given = false;
     std::string history_map;
+    std::optional<uint32_t> upscale;  // --upscale turns guided upsampling on; the options below need it
+    std::optional<float> upscale_normal, upscale_depth, upscale_albedo;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         std::string val;
@@ -497,6 +511,22 @@ int main(int argc, char** argv) {
             (history ? temporal_max_history : a == "--temporal-depth" ? temporal_depth : temporal_normal) = f + 0.0f;
         } else if (a == "--history-map") {
             history_map = value();
+        } else if (a == "--upscale") {
+            uint32_t v = 0;
+            u32(v);
+            if (v < 2u || v > RBRT_UPSAMPLE_MAX_FACTOR) {
+                std::fprintf(stderr, "error: invalid value '%u' for '--upscale' (expected 2 to %u)\n", v, RBRT_UPSAMPLE_MAX_FACTOR);
+                return 2;
+            }
+            upscale = v;
+        } else if (a == "--upscale-normal" || a == "--upscale-depth" || a == "--upscale-albedo") {
+            const char* v = value();
+            float f = 0.0f;
+            if (!parse_f32(v, f) || !std::isfinite(f) || !(f > 0.0f)) {
+                std::fprintf(stderr, "error: invalid value '%s' for '%s' (expected a finite number > 0)\n", v, a.c_str());
+                return 2;
+            }
+            (a == "--upscale-normal" ? upscale_normal : a == "--upscale-depth" ? upscale_depth : upscale_albedo) = f;
         } else if (a == "--shading") {
             const std::string v = value();
             if (v != "flat" && v != "smooth") {
@@ -522,7 +552,7 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "error: '--min-samples' must be at least 2 and '--adaptive-step' at least 1\n");
             return 2;
         }
-    } else if (!sample_map.empty()) {
+    } else if (!sample_map.empty() && !upscale) {  // (with --upscale the refusal below names both)
         std::fprintf(stderr, "error: '--sample-map' needs '--adaptive'\n");
         return 2;
     }
@@ -538,7 +568,7 @@ int main(int argc, char** argv) {
         }
     } else {
         const char* alone = denoise_radius ? "--denoise-radius" : denoise_patch ? "--denoise-patch" : denoise_strength ? "--denoise-strength"
-                            : !noisy.empty() && !denoise_guided ? "--noisy" : nullptr;
+                            : !noisy.empty() && !denoise_guided && !upscale ? "--noisy" : nullptr;
         if (alone) {
             std::fprintf(stderr, "error: '%s' needs '--denoise'\n", alone);
             return 2;
@@ -580,6 +610,24 @@ int main(int argc, char** argv) {
             return 2;
         }
     }
+    if (upscale) {  // a small render through one round of the adaptive path on one handle: refused by name before anything is loaded
+        const char* with = adaptive ? "--adaptive" : gpus > 1 ? "--gpus > 1" : !checkpoint.empty() ? "--checkpoint" : pass_samples != 0 ? "--pass-samples"
+                           : !sample_map.empty() ? "--sample-map" : nullptr;
+        if (with) {
+            std::fprintf(stderr, "error: '--upscale' cannot be combined with '%s'\n", with);
+            return 2;
+        }
+        if (samples < 2) {
+            std::fprintf(stderr, "error: '--upscale' needs '--samples' of at least 2 (each half image needs a sample)\n");
+            return 2;
+        }
+    } else {
+        const char* alone = upscale_normal ? "--upscale-normal" : upscale_depth ? "--upscale-depth" : upscale_albedo ? "--upscale-albedo" : nullptr;
+        if (alone) {
+            std::fprintf(stderr, "error: '%s' needs '--upscale'\n", alone);
+            return 2;
+        }
+    }
     if (!glare) {
         const char* alone = glare_threshold ? "--glare-threshold" : glare_levels ? "--glare-levels" : glare_spread ? "--glare-spread" : nullptr;
         if (alone) {
@@ -592,7 +640,7 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "error: '--features' cannot be combined with '--gpus > 1'\n");
             return 2;
         }
-    } else if (feature_samples && !denoise_guided && !frames) {
+    } else if (feature_samples && !denoise_guided && !frames && !upscale) {
         std::fprintf(stderr, "error: '--feature-samples' needs '--features'\n");
         return 2;
     }
@@ -688,8 +736,14 @@ int main(int argc, char** argv) {
             if (temporal_depth) cfg.temporal_depth = *temporal_depth;
             if (temporal_normal) cfg.temporal_normal = *temporal_normal;
         }
+        if (upscale) {
+            cfg.upscale = *upscale, cfg.keep_noisy = !noisy.empty();
+            if (upscale_normal) cfg.upscale_normal = *upscale_normal;
+            if (upscale_depth) cfg.upscale_depth = *upscale_depth;
+            if (upscale_albedo) cfg.upscale_albedo = *upscale_albedo;
+        }
         if (features) cfg.features = true;
-        if (features || denoise_guided || frames) cfg.feature_samples = feature_samples ? *feature_samples : std::max(1u, std::min(samples, 8u));
+        if (features || denoise_guided || frames || upscale) cfg.feature_samples = feature_samples ? *feature_samples : std::max(1u, std::min(samples, 8u));
         rbrt::ImageBuffer img = rbrt::render_scene(cam, samples, scene, cfg);
         std::printf("Saving rendered image to %s\n", target.c_str());
         const auto t3 = clock::now();
@@ -711,7 +765,7 @@ int main(int argc, char** argv) {
             uint64_t triangles = 0;
             for (const auto& m : scene.triangle_meshes) triangles += m.num_triangles;
             const uint32_t spp = samples_arg_for_report(samples);
-            const double rendered = adaptive || denoise || denoise_guided || frames ? double(rep.adaptive_samples)
+            const double rendered = adaptive || denoise || denoise_guided || frames || upscale ? double(rep.adaptive_samples)
                                              : double(width) * double(height) * double(spp - rep.resumed_from_sample);  // path samples of THIS run
             std::string js = "{";
             const auto str = [&](const char* k, const std::string& v) { js += std::string("\"") + k + "\": \"" + json_escape(v) + "\", "; };
@@ -756,6 +810,11 @@ int main(int argc, char** argv) {
                     js += b;
                 }
                 js += "], ";
+            }
+            if (upscale) {  // guided upsampling: its options, the size that was traced and the stage's time on the GPU, the mean per frame (a part of render_s)
+                num("upscale", cfg.upscale, "%.0f"), num("render_width", rep.render_width, "%.0f"), num("render_height", rep.render_height, "%.0f");
+                num("upscale_normal", cfg.upscale_normal, "%.9g"), num("upscale_depth", cfg.upscale_depth, "%.9g"), num("upscale_albedo", cfg.upscale_albedo, "%.9g");
+                num("upsample_ms", rep.upsample_ms, "%.4f");
             }
             if (glare) {  // the glare stage: its options and its time on the GPU
                 num("glare", cfg.glare_intensity, "%.9g"), num("glare_levels", cfg.glare_levels, "%.0f"), num("glare_ms", rep.glare_ms, "%.4f");

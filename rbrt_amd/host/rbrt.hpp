@@ -294,6 +294,8 @@ struct RenderReport {
     double glare_ms = 0.0;  // a render with glare (RenderConfig::glare): rbrt_hip_glare on the GPU, between two events
     double guided_ms = 0.0;  // a render with the guided filter (RenderConfig::denoise_guided): rbrt_hip_scene_denoise_guided, between two events
     double features_ms = 0.0;  // a render with feature buffers (RenderConfig::features): rbrt_hip_render_features, between two events
+    double upsample_ms = 0.0;  // a render with guided upsampling (RenderConfig::upscale): rbrt_hip_upsample_halves between two events, the mean per frame
+    uint32_t render_width = 0, render_height = 0;  // ... and the size that was traced
     double temporal_ms = 0.0;  // a render of several frames (RenderConfig::frames): rbrt_hip_temporal_accumulate between two events, the mean per frame
 };
 
@@ -362,6 +364,15 @@ struct RenderConfig {  // additions that the reference hard-codes or lacks
     uint32_t frames = 0;
     float camera_step[3] = {0.0f, 0.0f, 0.0f};
     float temporal_max_history = 32.0f, temporal_depth = 0.05f, temporal_normal = 0.35f;  // (rbrt_temporal_opts_default)
+    // Guided upsampling (rbrt_hip_upsample_halves; the CLI's --upscale, --upscale-*): the image is traced with the low camera of
+    // rbrt_hip_upsample_camera (1 / upscale of the size in each direction) through the adaptive path's one round that stops
+    // nothing, its two half images are brought to full size under the guidance of the full camera's feature buffers
+    // (feature_samples a pixel), and everything behind that -- `frames`, the filters, glare, the display transform -- runs at
+    // full size as it does without. With keep_noisy the unfiltered image is the plain mix of the upsampled halves (of the last
+    // frame, before its accumulation). Inherits the adaptive path's refusals; not with `adaptive` itself; num_samples must be at
+    // least 2. 0: the image is traced at its own size.
+    uint32_t upscale = 0;  // 0, or 2..RBRT_UPSAMPLE_MAX_FACTOR
+    float upscale_normal = 0.5f, upscale_depth = 0.1f, upscale_albedo = 0.2f;  // (rbrt_upsample_opts_default)
 };
 // rbrt_lib::render_scene (lib.rs:75-79): blocks until the image is complete. Runs on the GPU(s)
 // through the C ABI; there is no CPU path.

@@ -351,6 +351,14 @@ Plan make_plan(const RenderConfig& cfg, const std::string& adaptive_by, bool cfg
             if (!std::isfinite(k) || !(k >= 0.0f)) throw Error("--temporal-depth and --temporal-normal must be finite and at least 0");
         if (cfg.feature_samples == 0 || cfg.feature_samples > 65536u) throw Error("--feature-samples must be 1 to 65536");
     }
+    if (cfg.upscale) {  // (rbrt_hip.h "Guided upsampling": a small render through one round of the adaptive path on one handle)
+        if (cfg_adaptive_given) throw Error("--upscale cannot be combined with --adaptive");
+        if (cfg.upscale < 2u || cfg.upscale > RBRT_UPSAMPLE_MAX_FACTOR) throw Error("--upscale must be 2 to 4");
+        if (num_samples < 2) throw Error("--upscale needs at least 2 samples (each half image needs one)");
+        for (const float k : {cfg.upscale_normal, cfg.upscale_depth, cfg.upscale_albedo})
+            if (!std::isfinite(k) || !(k > 0.0f)) throw Error("--upscale-normal, --upscale-depth and --upscale-albedo must be finite and above 0");
+        if (cfg.feature_samples == 0 || cfg.feature_samples > 65536u) throw Error("--feature-samples must be 1 to 65536");
+    }
     if (cfg.features) {  // (of the whole frame, on one handle: rbrt_hip.h "Feature buffers")
         if (cfg.n_gpus > 1) throw Error("--features cannot be combined with --gpus > 1");
         if (cfg.feature_samples == 0 || cfg.feature_samples > 65536u) throw Error("--feature-samples must be 1 to 65536");
@@ -537,7 +545,7 @@ void Rank::run() {
     setup();
     sh.t_setup[rank] = seconds_since(t_start);
     const auto t_passes = std::chrono::steady_clock::now();
-    if (cfg.frames) temporal();
+    if (cfg.frames || cfg.upscale) temporal();
     else if (cfg.adaptive) render_adaptive();
     else render_passes();
     if (rank == 0) sh.rep.passes = pass_no;
@@ -545,9 +553,10 @@ void Rank::run() {
     if (hs && !err.failed()) err.lib_ok(rbrt_hip_scene_check(hs));
     sh.t_render[rank] = seconds_since(t_passes);
     const auto t_g = std::chrono::steady_clock::now();
-    // (a render of several frames has made its feature buffers and filtered its image frame by frame: temporal())
-    if (world == 1 && !cfg.frames && (cfg.features || cfg.denoise_guided)) features();
-    if (world == 1 && !cfg.frames && cfg.denoise_guided) denoise_guided();  // (in front of glare and the display transform, like denoise)
+    // (a render of several frames, or an upsampled one, has made its feature buffers and filtered its image frame by frame: temporal())
+    const bool by_frames = cfg.frames || cfg.upscale;
+    if (world == 1 && !by_frames && (cfg.features || cfg.denoise_guided)) features();
+    if (world == 1 && !by_frames && cfg.denoise_guided) denoise_guided();  // (in front of glare and the display transform, like denoise)
     if (world == 1) gather_single();
     else if (sh.use_rccl) gather_rccl();
     else gather_host();
@@ -738,83 +747,122 @@ void Rank::download_features() {
 // the history the frame before left; two histories alternate. The accumulated halves of the last frame then go through the
 // guided filter, the non-local-means filter or, with neither, their plain mix (window radius 0), all with the one mix wa every
 // pixel of a one-round render has. The unfiltered image and the feature buffers are the last frame's.
+// With cfg.upscale every frame is traced with the low camera of rbrt_hip_upsample_camera, its half images are low size, the
+// feature buffers are the full camera's, and rbrt_hip_upsample_halves makes the full-size halves everything behind it reads;
+// the unfiltered image is then the plain mix of the last frame's upsampled halves. Without cfg.frames there is one frame and no
+// accumulation.
 void Rank::temporal() {
     if (err.failed() || !npix) return;
     const size_t n_pixels = size_t(img.width) * img.height, n = job.n();
-    const uint32_t num_samples = job.num_samples;
+    const uint32_t num_samples = job.num_samples, n_frames = cfg.frames ? cfg.frames : 1u, factor = cfg.upscale;
     const rbrt_adaptive_opts_t ao = {cfg.adaptive_threshold, cfg.adaptive_min_samples, cfg.adaptive_step, 0u};
     rbrt_denoise_opts_t dn = {cfg.denoise_window_radius, cfg.denoise_patch_radius, cfg.denoise_strength, 0u};
+    const rbrt_denoise_opts_t plain_mix = {0u, cfg.denoise_patch_radius, cfg.denoise_strength, 0u};  // exactly A * wa + B * (1 - wa)
     rbrt_feature_opts_t fo;
     rbrt_feature_opts_default(&fo);
     fo.samples = cfg.feature_samples;
     rbrt_temporal_opts_t to;
     rbrt_temporal_opts_default(&to);
     to.max_history = cfg.temporal_max_history, to.depth = cfg.temporal_depth, to.normal = cfg.temporal_normal;
-    const size_t history_bytes = rbrt_hip_temporal_history_bytes(img.width, img.height);
-    if (history_bytes == 0) {
+    rbrt_upsample_opts_t uo;
+    rbrt_upsample_opts_default(&uo);
+    uo.factor = factor ? factor : 1u, uo.normal = cfg.upscale_normal, uo.depth = cfg.upscale_depth, uo.albedo = cfg.upscale_albedo;
+    const size_t history_bytes = cfg.frames ? rbrt_hip_temporal_history_bytes(img.width, img.height) : 0;
+    if (cfg.frames && history_bytes == 0) {
         err.set("--frames: the image is too large for temporal accumulation (2^31 pixels or more)");
         return;
     }
-    DeviceBuffer d_half_a, d_half_b, d_history[2], d_length, d_wa;
-    EventTimer timer;
+    const size_t upsample_bytes = factor ? rbrt_hip_upsample_workspace_bytes(img.width, img.height, factor) : 0;
+    if (factor && upsample_bytes == 0) {
+        err.set("--upscale: the image is too large for guided upsampling (2^31 pixels or more)");
+        return;
+    }
+    const size_t n_low = factor ? size_t((img.width + factor - 1u) / factor) * ((img.height + factor - 1u) / factor) * 3u : 0;  // values of a low half image
+    DeviceBuffer d_half_a, d_half_b, d_history[2], d_length, d_wa, d_low_a, d_low_b, d_upsample;
+    EventTimer timer, up_timer;
     if (!(d_features.alloc(n_pixels * 8 * sizeof(float), err, "hipMalloc(feature buffers)") && d_half_a.alloc(n * sizeof(float), err, "hipMalloc(half image)") &&
-          d_half_b.alloc(n * sizeof(float), err, "hipMalloc(half image)") && d_history[0].alloc(history_bytes, err, "hipMalloc(history)") &&
-          d_history[1].alloc(history_bytes, err, "hipMalloc(history)") && d_length.alloc(n_pixels * sizeof(float), err, "hipMalloc(history length)") &&
-          d_wa.alloc(n_pixels * sizeof(float), err, "hipMalloc(mix)") && timer.create(err)))
+          d_half_b.alloc(n * sizeof(float), err, "hipMalloc(half image)") && d_wa.alloc(n_pixels * sizeof(float), err, "hipMalloc(mix)") && timer.create(err) &&
+          up_timer.create(err)))
+        return;
+    if (cfg.frames && !(d_history[0].alloc(history_bytes, err, "hipMalloc(history)") && d_history[1].alloc(history_bytes, err, "hipMalloc(history)") &&
+                        d_length.alloc(n_pixels * sizeof(float), err, "hipMalloc(history length)")))
+        return;
+    if (factor && !(d_low_a.alloc(n_low * sizeof(float), err, "hipMalloc(low half image)") && d_low_b.alloc(n_low * sizeof(float), err, "hipMalloc(low half image)") &&
+                    d_upsample.alloc(upsample_bytes, err, "hipMalloc(upsampling workspace)")))
         return;
     float* const d_albedo = d_features.as<float>();
     float *const d_normal = d_albedo + n_pixels * 3, *const d_depth = d_normal + n_pixels * 3, *const d_coverage = d_depth + n_pixels;
+    // every pixel of a one-round render has the same count n: h = (n + 1) / 2 samples in A, so wa = float(h) * (1.0f / float(n))
+    const float inv_n = 1.0f / float(num_samples);
+    const std::vector<float> wa(n_pixels, float((num_samples + 1u) / 2u) * inv_n);
+    if (!err.ok(hipMemcpy(d_wa.as<float>(), wa.data(), n_pixels * sizeof(float), hipMemcpyHostToDevice), "upload of the mix")) return;
     RenderReport& rep = sh.rep;
     rbrt_camera_lens_t lens_prev = job.lens;
-    double ms_sum = 0.0;
-    for (uint32_t k = 0; k < cfg.frames && !err.failed(); ++k) {
+    double ms_sum = 0.0, up_ms_sum = 0.0;
+    for (uint32_t k = 0; k < n_frames && !err.failed(); ++k) {
         rbrt_camera_lens_t lens = job.lens;  // (with a thin lens the lens moves with its camera)
         for (int c = 0; c < 3; ++c) {
             const float shift = float(k) * cfg.camera_step[c];
             lens.cam.position[c] = job.lens.cam.position[c] + shift;
             lens.cam.img_center_point[c] = job.lens.cam.img_center_point[c] + shift;
         }
+        rbrt_camera_lens_t traced = lens;  // (the low camera keeps the lens: lens_u, lens_v and focus_scale)
+        if (factor && !err.lib_ok(rbrt_hip_upsample_camera(&lens.cam, factor, &traced.cam))) break;
+        rep.render_width = traced.cam.img_width_pix, rep.render_height = traced.cam.img_height_pix;
         rbrt_render_opts_t ok = o;
         ok.seed = o.seed + k;  // (the same seed would accumulate the same noise)
         rbrt_adaptive_result_t ar{};
-        if (!err.lib_ok(rbrt_hip_render_adaptive(hs, &lens.cam, &ok, &ao, stream.get(), d_rad.as<float>(), d_rgb.as<uint8_t>(), nullptr, nullptr, &ar))) break;
+        // (d_rad and d_rgb are full size: a low image fits)
+        if (!err.lib_ok(rbrt_hip_render_adaptive(hs, &traced.cam, &ok, &ao, stream.get(), d_rad.as<float>(), d_rgb.as<uint8_t>(), nullptr, nullptr, &ar))) break;
         rep.adaptive_rounds = ar.rounds, rep.adaptive_samples += ar.samples, rep.adaptive_samples_fixed += ar.samples_fixed;
-        if (!err.lib_ok(rbrt_hip_scene_denoise(hs, &dn, stream.get(), nullptr, nullptr, d_half_a.as<float>(), d_half_b.as<float>()))) break;
+        if (!err.lib_ok(rbrt_hip_scene_denoise(hs, &dn, stream.get(), nullptr, nullptr, (factor ? d_low_a : d_half_a).as<float>(),
+                                               (factor ? d_low_b : d_half_b).as<float>())))
+            break;
         if (!err.lib_ok(rbrt_hip_render_features(hs, &lens.cam, &ok, &fo, stream.get(), d_albedo, d_normal, d_depth, d_coverage, nullptr))) break;
-        timer.start(stream.get(), err);
-        err.lib_ok(rbrt_hip_temporal_accumulate(dev, stream.get(), d_half_a.as<float>(), d_half_b.as<float>(), d_normal, d_depth, d_coverage, &lens.cam,
-                                                k ? &lens_prev.cam : nullptr, &to, k ? d_history[(k - 1u) & 1u].as<void>() : nullptr,
-                                                d_history[k & 1u].as<void>(), d_half_a.as<float>(), d_half_b.as<float>(),
-                                                k + 1u == cfg.frames ? d_length.as<float>() : nullptr));
-        timer.stop(stream.get(), err);
+        if (factor) {
+            up_timer.start(stream.get(), err);
+            err.lib_ok(rbrt_hip_upsample_halves(dev, stream.get(), d_low_a.as<float>(), d_low_b.as<float>(), nullptr, d_albedo, d_normal, d_depth, d_coverage,
+                                                img.width, img.height, &uo, d_upsample.as<void>(), d_half_a.as<float>(), d_half_b.as<float>(), nullptr));
+            up_timer.stop(stream.get(), err);
+            if (cfg.keep_noisy && k + 1u == n_frames)  // the unfiltered image: the upsampled halves' plain mix, before the accumulation
+                err.lib_ok(rbrt_hip_denoise_halves(dev, stream.get(), d_half_a.as<float>(), d_half_b.as<float>(), d_wa.as<float>(), img.width, img.height,
+                                                   &plain_mix, d_rad.as<float>(), d_rgb.as<uint8_t>()));
+        }
+        if (cfg.frames) {
+            timer.start(stream.get(), err);
+            err.lib_ok(rbrt_hip_temporal_accumulate(dev, stream.get(), d_half_a.as<float>(), d_half_b.as<float>(), d_normal, d_depth, d_coverage, &lens.cam,
+                                                    k ? &lens_prev.cam : nullptr, &to, k ? d_history[(k - 1u) & 1u].as<void>() : nullptr,
+                                                    d_history[k & 1u].as<void>(), d_half_a.as<float>(), d_half_b.as<float>(),
+                                                    k + 1u == cfg.frames ? d_length.as<float>() : nullptr));
+            timer.stop(stream.get(), err);
+        }
         err.ok(hipStreamSynchronize(stream.get()), "frame");
         float ms = 0.0f;
-        if (timer.elapsed(&ms, err)) ms_sum += ms;
+        if (cfg.frames && timer.elapsed(&ms, err)) ms_sum += ms;
+        if (factor && up_timer.elapsed(&ms, err)) up_ms_sum += ms;
         if (hs && !err.failed()) err.lib_ok(rbrt_hip_scene_check(hs));
         lens_prev = lens;
         ++pass_no;
         if (!cfg.quiet) {
-            std::printf("\rRendering %.1f%% complete!", double(k + 1u) / double(cfg.frames) * 100.0);
+            std::printf("\rRendering %.1f%% complete!", double(k + 1u) / double(n_frames) * 100.0);
             std::fflush(stdout);
         }
     }
     if (err.failed()) return;
-    rep.temporal_ms = ms_sum / double(cfg.frames);
+    if (cfg.frames) rep.temporal_ms = ms_sum / double(n_frames);
+    if (factor) rep.upsample_ms = up_ms_sum / double(n_frames);
     keep_noisy();
     download_features();
-    // the history length of the last frame, as a share of the longest there can be
-    std::vector<float> length(n_pixels);
-    if (err.ok(hipMemcpy(length.data(), d_length.as<float>(), n_pixels * sizeof(float), hipMemcpyDeviceToHost), "download of the history length")) {
-        img.history_map.resize(n_pixels);
-        for (size_t i = 0; i < n_pixels; ++i) {
-            const float v = (length[i] / cfg.temporal_max_history) * 255.0f;
-            img.history_map[i] = !(v == v) || v <= 0.0f ? 0 : v >= 255.0f ? 255 : uint8_t(v);
+    if (cfg.frames) {  // the history length of the last frame, as a share of the longest there can be
+        std::vector<float> length(n_pixels);
+        if (err.ok(hipMemcpy(length.data(), d_length.as<float>(), n_pixels * sizeof(float), hipMemcpyDeviceToHost), "download of the history length")) {
+            img.history_map.resize(n_pixels);
+            for (size_t i = 0; i < n_pixels; ++i) {
+                const float v = (length[i] / cfg.temporal_max_history) * 255.0f;
+                img.history_map[i] = !(v == v) || v <= 0.0f ? 0 : v >= 255.0f ? 255 : uint8_t(v);
+            }
         }
     }
-    // every pixel of a one-round render has the same count n: h = (n + 1) / 2 samples in A, so wa = float(h) * (1.0f / float(n))
-    const float inv_n = 1.0f / float(num_samples);
-    const std::vector<float> wa(n_pixels, float((num_samples + 1u) / 2u) * inv_n);
-    if (!err.ok(hipMemcpy(d_wa.as<float>(), wa.data(), n_pixels * sizeof(float), hipMemcpyHostToDevice), "upload of the mix")) return;
     if (cfg.denoise_guided) {
         const rbrt_guided_opts_t g = {cfg.guided_levels, cfg.guided_colour, cfg.guided_normal, cfg.guided_depth, cfg.guided_albedo,
                                       cfg.guided_demodulate ? 0u : RBRT_GUIDED_NO_DEMODULATION, {0u, 0u}};
@@ -986,7 +1034,7 @@ void report_times(const Plan& plan, const Shared& sh, RenderReport& rep) {
 
 ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& scene, const RenderConfig& cfg_in) {
     RenderConfig cfg = cfg_in;
-    if ((cfg.denoise || cfg.denoise_guided || cfg.frames) && !cfg.adaptive)  // (the filter's input is the adaptive path's sums: one round that stops nothing)
+    if ((cfg.denoise || cfg.denoise_guided || cfg.frames || cfg.upscale) && !cfg.adaptive)  // (the filter's input is the adaptive path's sums: one round that stops nothing)
         cfg.adaptive = true, cfg.adaptive_threshold = 0.0f, cfg.adaptive_min_samples = cfg.adaptive_step = std::max(num_samples, 2u);
     if (!cfg.quiet) std::printf("Starting rendering...\n");
     ImageBuffer img;
@@ -999,7 +1047,7 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
     const rbrt_camera_lens_t lens = cam.to_abi_lens();
     const Scene::AbiView view = scene.to_abi();
     const rbrt_environment_t env_abi = scene.environment.to_abi();
-    const Plan plan = make_plan(cfg, cfg_in.adaptive ? "--adaptive" : cfg_in.frames ? "--frames" : cfg_in.denoise_guided ? "--denoise-guided" : "--denoise", cfg_in.adaptive,
+    const Plan plan = make_plan(cfg, cfg_in.adaptive ? "--adaptive" : cfg_in.upscale ? "--upscale" : cfg_in.frames ? "--frames" : cfg_in.denoise_guided ? "--denoise-guided" : "--denoise", cfg_in.adaptive,
                                 cam, scene, num_samples);
     Job job{cfg, plan, lens, view, scene.environment.n != 0u ? &env_abi : nullptr, render_opts_of(cfg, cam, num_samples), num_samples, {}, {}, img};
     job.want = checkpoint_header(img.width, img.height, num_samples, uint32_t(plan.world), cfg.seed,

@@ -73,7 +73,9 @@ extern "C" {
                               an added struct and entry points, detected by the symbol), nor guided upsampling
                               (rbrt_upsample_opts_t, rbrt_upsample_opts_default, rbrt_hip_upsample_camera,
                               rbrt_hip_upsample_workspace_bytes and rbrt_hip_upsample_halves: an added struct and entry
-                              points, detected by the symbol) */
+                              points, detected by the symbol), nor spike removal (rbrt_despike_opts_t,
+                              rbrt_despike_result_t, rbrt_despike_opts_default and rbrt_hip_despike_halves: added structs
+                              and entry points, detected by the symbol) */
 
 typedef enum rbrt_status {
     RBRT_OK = 0,
@@ -946,6 +948,70 @@ int rbrt_hip_upsample_halves(int device, void* stream, const float* d_a, const f
                              const float* d_albedo, const float* d_normal, const float* d_depth, const float* d_coverage,
                              uint32_t width, uint32_t height, const rbrt_upsample_opts_t* opts, void* d_workspace,
                              float* d_out_a, float* d_out_b, float* d_out_wa);
+
+/* ---- Spike removal: a rank-order firefly clamp on the two half images ----------------------------------------------------------
+ * No counterpart in the reference. A diffuse path that finds a small, very bright light by chance leaves one sample thousands
+ * of times brighter than its neighbours (the lambertian has no pdf, so the light cannot be sampled). Every stage behind the
+ * trace kernel takes a pixel's noise to be of moderate size: the denoisers spread such a pixel, the accumulation carries it,
+ * upsampling enlarges it, glare blooms it. This stage runs in front of them all. A pixel of one half image is limited to a
+ * multiple of the larger of two witnesses: the k-th largest luminance among its neighbours in its own half, and its own
+ * luminance in the OTHER half, which holds an independent estimate of the same pixel. A highlight that both halves see, or
+ * that k + 1 neighbouring pixels of one half share, therefore passes; a lone sample does not. No median, no sorting: only
+ * comparisons and, in a limited pixel, one division.
+ *
+ * The rule. All arithmetic is float32, unfused, in the written order; / is correctly rounded; a constant is the float32
+ * nearest to the decimal written; max and min are C's fmaxf and fminf. MAXF = 3.4028235e38f. fin(x) is
+ * x <= MAXF && x >= -MAXF, so a NaN is not finite. Y(c) = ((0.2126f * c_r) + (0.7152f * c_g)) + (0.0722f * c_b), the display
+ * transform's luminance. pos(x) = x if fin(x) && x > 0.0f, else +0.0f.
+ *   Inputs.  Half images A and B, float[H][W][3]; the radius R in 1..RBRT_DESPIKE_MAX_RADIUS; the rank k in
+ *     1..RBRT_DESPIKE_MAX_RANK; the threshold t, finite, >= 1; the floor f, finite, >= 0.
+ *   For the half X with the other half O, at the pixel p:
+ *     y = Y(X[p]);  yo = Y(O[p]).
+ *     r = the k-th largest element of the multiset that holds pos(Y(X[q])) for every q = p + (dy, dx) with |dy|, |dx| <= R,
+ *       q != p, q inside the image, and k zeros (+0.0f). Only values matter, so neither the scan's order nor ties do. A
+ *       neighbour that is not finite, or not above 0, stands for one more zero, which changes nothing: k zeros are there
+ *       already. So r >= +0.0f, and a pixel with fewer than k usable neighbours gets r = 0.
+ *     base = max(r, pos(yo));  lim = min((t * base) + f, MAXF).
+ *     If !fin(y): the pixel is flagged and X'[p] = (lim, lim, lim).
+ *     Else if y > lim: the pixel is flagged, s = lim / y and X'_c[p] = X_c[p] * s per channel.
+ *     Else X'[p] = X[p], bit for bit.
+ *   mask[p] has bit 0 set when A was flagged at p and bit 1 set when B was; result.spikes_a and result.spikes_b count the
+ *   flagged pixels of A and of B. The mix wa of the halves is not the stage's business: it stays what it was.
+ * Consequences. An unflagged pixel passes bit for bit. A pixel's result depends only on its own half's window and on the other
+ * half's same pixel. A flagged pixel comes out finite: lim is finite and at least 0, and a finite y above lim >= 0 has finite
+ * channels and 0 <= s < 1. A value that both halves hold equally at p is never flagged: since t >= 1 and f >= 0,
+ * y > (t * max(r, y)) + f is false. A cluster of k + 1 mutually adjacent equal spikes in one half survives (each has k equal
+ * neighbours, so r = y); a cluster of k does not (each has k - 1). Swapping A and B swaps A' and B' and the mask's two bits.
+ * With no flagged pixel the call is the identity and both counts are 0. */
+#define RBRT_DESPIKE_MAX_RADIUS 2u
+#define RBRT_DESPIKE_MAX_RANK 4u
+typedef struct rbrt_despike_opts {
+    uint32_t radius;       /* R, 1..RBRT_DESPIKE_MAX_RADIUS: the window is (2 R + 1) x (2 R + 1) */
+    uint32_t rank;         /* k, 1..RBRT_DESPIKE_MAX_RANK */
+    float threshold;       /* t: finite, >= 1 */
+    float floor;           /* f: finite, >= 0 */
+    uint32_t flags;        /* 0 */
+    uint32_t reserved[3];  /* 0 */
+} rbrt_despike_opts_t;
+void rbrt_despike_opts_default(rbrt_despike_opts_t* opts); /* R = 2, k = 2, t = 4, f = 0.01, flags 0 */
+
+typedef struct rbrt_despike_result { /* what the call found; lives in device memory */
+    uint32_t spikes_a, spikes_b;     /* the flagged pixels of A and of B */
+    uint32_t reserved[2];            /* 0 */
+} rbrt_despike_result_t;
+
+/* The rule on buffers in DEVICE memory, all row-major: d_a, d_b, d_out_a and d_out_b float[height][width][3] (4-byte alignment
+ * is enough), d_mask uint8[height][width], d_result one rbrt_despike_result_t (a host reads it with a 16-byte copy behind the
+ * stream). Any output may be NULL; with all four NULL nothing is launched. The call zeroes d_result on the stream before its
+ * kernel adds to it: nothing is assumed about what it held. Needs no scene, owns no device memory, asynchronous on `stream`.
+ * No input may overlap an output: other workgroups read a pixel's neighbours.
+ * RBRT_ERR_INVALID_ARG, before the device is touched: d_a, d_b or opts NULL; width or height 0; radius outside
+ * 1..RBRT_DESPIKE_MAX_RADIUS; rank outside 1..RBRT_DESPIKE_MAX_RANK; a threshold that is not finite or below 1; a floor that is
+ * not finite or below 0; a non-zero flag or reserved word; an output that equals an input.
+ * RBRT_ERR_UNSUPPORTED: width * height >= 2^31. */
+int rbrt_hip_despike_halves(int device, void* stream, const float* d_a, const float* d_b, uint32_t width, uint32_t height,
+                            const rbrt_despike_opts_t* opts, float* d_out_a, float* d_out_b, uint8_t* d_mask,
+                            rbrt_despike_result_t* d_result);
 
 /* De-interleave gathered per-rank packed tile buffers (concatenated rank 0..world-1, each
  * rbrt_hip_packed_pixels(...)*3 floats, device memory) into a row-major float[H][W][3] device

@@ -79,6 +79,13 @@ int rbrt_hip_debug_guided_staging(int max_step);
 #define RBRT_UPSAMPLE_TILE_W 32u
 #define RBRT_UPSAMPLE_TILE_H 8u
 
+/* The spike removal's kernel (rbrt_amd/csrc/despike.hip): the tile of pixels one workgroup makes, whose luminances it stages in
+ * LDS with a halo of the radius. Sizes around it, twice it, and three times it and a little where an interior workgroup has
+ * halos on all four sides, and spikes either side of a tile's edge and the radius away from it, are where that kernel's
+ * paths change (tests/test_despike_gpu.py, tests/despike_cases.py). */
+#define RBRT_DESPIKE_TILE_W 32u
+#define RBRT_DESPIKE_TILE_H 8u
+
 /* The display transform's kernels (rbrt_amd/csrc/tonemap.hip): the pixels one workgroup takes per stride of its grid, and the
  * cap of that grid. Pixel counts around BLOCK_PIXELS, and around MAX_BLOCKS * BLOCK_PIXELS where a workgroup starts to stride a
  * second time, are where those kernels' paths change (tests/test_tonemap_gpu.py). */

@@ -555,6 +555,31 @@ def upsample_halves(device: int, d_a: int, d_b: int, d_wa: int | None, d_albedo:
                                                   C.c_void_p(d_out_wa or 0)))
 
 
+def despike_opts(radius: int | None = None, rank: int | None = None, threshold: float | None = None, floor: float | None = None,
+                 flags: int | None = None, reserved=(0, 0, 0)) -> abi.DespikeOpts:
+    """rbrt_despike_opts_default (radius 2, rank 2, threshold 4, floor 0.01, flags 0), with the parameters that are given put in."""
+    t = abi.DespikeOpts()
+    load_hip().rbrt_despike_opts_default(C.byref(t))
+    for name, value, kind in (("radius", radius, int), ("rank", rank, int), ("threshold", threshold, float), ("floor", floor, float),
+                              ("flags", flags, int)):
+        if value is not None:
+            setattr(t, name, kind(value))
+    for k in range(3):
+        t.reserved[k] = int(reserved[k])
+    return t
+
+
+def despike_halves(device: int, d_a: int, d_b: int, width: int, height: int, d_out_a: int | None = None, d_out_b: int | None = None,
+                   d_mask: int | None = None, d_result: int | None = None, opts: abi.DespikeOpts | None = None, stream: int | None = None):
+    """Spike removal in device memory (rbrt_hip_despike_halves): d_a, d_b and the outputs d_out_a, d_out_b float32 [height, width, 3],
+    d_mask uint8 [height, width] (bit 0: A was limited, bit 1: B), d_result 16 bytes (an abi.DespikeResult, zeroed by the call).
+    `opts`: despike_opts(...), None for the library's defaults. Asynchronous on `stream`."""
+    t = opts if opts is not None else despike_opts()
+    abi.check(load_hip().rbrt_hip_despike_halves(device, C.c_void_p(stream or 0), C.c_void_p(d_a or 0), C.c_void_p(d_b or 0), width, height,
+                                                 C.byref(t), C.c_void_p(d_out_a or 0), C.c_void_p(d_out_b or 0), C.c_void_p(d_mask or 0),
+                                                 C.c_void_p(d_result or 0)))
+
+
 def tonemap_opts(curve: int | None = None, exposure: float | None = None, key: float | None = None,
                  key_permille: int | None = None, white: float | None = None, white_permille: int | None = None,
                  reserved=(0, 0)) -> abi.TonemapOpts:

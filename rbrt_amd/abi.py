@@ -49,6 +49,10 @@ UPSAMPLE_NO_DEMODULATION = 1  # rbrt_hip.h: RBRT_UPSAMPLE_NO_DEMODULATION
 UPSAMPLE_WORKSPACE_BYTES_PER_LOW_PIXEL = 64  # rbrt_hip.h: four 16-byte records {a~, wa}, {b~, z_l}, {N_l, c_l}, {m_l, 0}
 UPSAMPLE_TILE_W = 32         # rbrt_hip_debug.h: the tile of full pixels one workgroup of the upsampling's gather kernel makes
 UPSAMPLE_TILE_H = 8
+DESPIKE_MAX_RADIUS = 2       # rbrt_hip.h: RBRT_DESPIKE_MAX_RADIUS
+DESPIKE_MAX_RANK = 4         # rbrt_hip.h: RBRT_DESPIKE_MAX_RANK
+DESPIKE_TILE_W = 32          # rbrt_hip_debug.h: the tile of pixels one workgroup of the spike removal's kernel makes
+DESPIKE_TILE_H = 8
 GLARE_MAX_LEVELS = 8         # rbrt_hip.h: the most levels of the glare stage's pyramid
 GLARE_TILE_W = 16            # rbrt_hip_debug.h: the tile of a pyramid level one workgroup of the REDUCE kernel makes
 GLARE_TILE_H = 16
@@ -207,6 +211,15 @@ class UpsampleOpts(C.Structure):  # rbrt_upsample_opts_t
                 ("reserved", C.c_uint32 * 3)]
 
 
+class DespikeOpts(C.Structure):  # rbrt_despike_opts_t
+    _fields_ = [("radius", C.c_uint32), ("rank", C.c_uint32), ("threshold", C.c_float), ("floor", C.c_float), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 3)]
+
+
+class DespikeResult(C.Structure):  # rbrt_despike_result_t: in device memory
+    _fields_ = [("spikes_a", C.c_uint32), ("spikes_b", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 class Environment(C.Structure):  # rbrt_environment_t
     """An octahedral radiance map of (n + 1) x (n + 1) nodes: `nodes` points at host float32 [n + 1][n + 1][3]."""
     _fields_ = [("n", C.c_uint32), ("reserved", C.c_uint32), ("nodes", f32p)]
@@ -306,6 +319,9 @@ HIP_SYMBOLS = {
     "rbrt_hip_upsample_halves": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(UpsampleOpts), C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p]),
+    "rbrt_despike_opts_default": (None, [C.POINTER(DespikeOpts)]),
+    "rbrt_hip_despike_halves": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(DespikeOpts), C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 # ... and include/rbrt_hip_debug.h (test hooks and diagnostics, same library)
 DEBUG_SYMBOLS = {

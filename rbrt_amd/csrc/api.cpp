@@ -46,6 +46,7 @@ hipError_t launch_glare(const GlareParams& G, hipStream_t stream);              
 hipError_t launch_guided(const GuidedParams& G, uint32_t staged_max_step, hipStream_t stream);  // guided.hip
 hipError_t launch_temporal(const TemporalParams& T, hipStream_t stream);                // temporal.hip
 hipError_t launch_upsample(const UpsampleParams& U, hipStream_t stream);                // upsample.hip
+hipError_t launch_despike(const DespikeParams& D, hipStream_t stream);                  // despike.hip
 hipError_t launch_unpack(const float* gathered, uint32_t width, uint32_t height, uint32_t world,
                          size_t rank_stride_pixels, float* out_radiance, uint8_t* out_rgb8, hipStream_t stream);
 hipError_t launch_trace_rays(const TraceParams& P, const float* rays, size_t n, float* out_t, int32_t* out_obj,
@@ -2534,6 +2535,39 @@ int rbrt_hip_upsample_halves(int device, void* stream, const float* d_a, const f
     if (int rc = ensure_device(device)) return rc;
     if (!d_out_a && !d_out_b && !d_out_wa) return RBRT_OK;
     HIP_TRY(launch_upsample(U, static_cast<hipStream_t>(stream)));
+    return RBRT_OK;
+}
+
+// ---- Spike removal (the rule: include/rbrt_hip.h; the kernel: despike.hip) -----------------------------------------------------
+void rbrt_despike_opts_default(rbrt_despike_opts_t* o) {
+    if (!o) return;
+    o->radius = 2u, o->rank = 2u, o->threshold = 4.0f, o->floor = 0.01f, o->flags = 0u;
+    for (uint32_t& r : o->reserved) r = 0u;
+}
+
+int rbrt_hip_despike_halves(int device, void* stream, const float* d_a, const float* d_b, uint32_t width, uint32_t height,
+                            const rbrt_despike_opts_t* o, float* d_out_a, float* d_out_b, uint8_t* d_mask, rbrt_despike_result_t* d_result) {
+    if (!d_a || !d_b || !o) return fail(RBRT_ERR_INVALID_ARG, "despike_halves: null argument");
+    if (width == 0u || height == 0u) return fail(RBRT_ERR_INVALID_ARG, "despike_halves: width and height must be >= 1");
+    if (o->radius == 0u || o->radius > RBRT_DESPIKE_MAX_RADIUS) return fail(RBRT_ERR_INVALID_ARG, "despike_halves: radius must be 1..2");
+    if (o->rank == 0u || o->rank > RBRT_DESPIKE_MAX_RANK) return fail(RBRT_ERR_INVALID_ARG, "despike_halves: rank must be 1..4");
+    if (!std::isfinite(o->threshold) || !(o->threshold >= 1.0f)) return fail(RBRT_ERR_INVALID_ARG, "despike_halves: threshold must be finite and >= 1");
+    if (!std::isfinite(o->floor) || !(o->floor >= 0.0f)) return fail(RBRT_ERR_INVALID_ARG, "despike_halves: floor must be finite and >= 0");
+    if (o->flags != 0u) return fail(RBRT_ERR_INVALID_ARG, "despike_halves: unknown flag bit");
+    for (const uint32_t r : o->reserved)
+        if (r != 0u) return fail(RBRT_ERR_INVALID_ARG, "despike_halves: reserved must be 0");
+    for (const void* out : {static_cast<const void*>(d_out_a), static_cast<const void*>(d_out_b), static_cast<const void*>(d_mask),
+                            static_cast<const void*>(d_result)})
+        if (out && (out == d_a || out == d_b)) return fail(RBRT_ERR_INVALID_ARG, "despike_halves: an output must not be an input");
+    if (uint64_t(width) * height >= (1ull << 31)) return fail(RBRT_ERR_UNSUPPORTED, "despike_halves: 2^31 or more pixels");
+
+    DespikeParams D;
+    std::memset(&D, 0, sizeof(D));
+    D.a = d_a, D.b = d_b, D.out_a = d_out_a, D.out_b = d_out_b, D.mask = d_mask, D.counts = reinterpret_cast<uint32_t*>(d_result);
+    D.width = width, D.height = height, D.radius = o->radius, D.rank = o->rank, D.threshold = o->threshold, D.floor = o->floor;
+    if (int rc = ensure_device(device)) return rc;
+    if (!d_out_a && !d_out_b && !d_mask && !d_result) return RBRT_OK;
+    HIP_TRY(launch_despike(D, static_cast<hipStream_t>(stream)));
     return RBRT_OK;
 }
 

@@ -374,4 +374,17 @@ struct UpsampleParams {
     float in, ia, kz2, invf;    // 1 / (kn * kn), 1 / (ka * ka), kz * kz, 1 / float(f)
 };
 
+// Spike removal (include/rbrt_hip.h "Spike removal"; despike.hip): one rbrt_hip_despike_halves call.
+struct DespikeParams {
+    const float* a;             // [H][W][3] the half images
+    const float* b;
+    float* out_a;               // [H][W][3], may be null
+    float* out_b;               // [H][W][3], may be null
+    uint8_t* mask;              // [H][W], may be null
+    uint32_t* counts;           // the rbrt_despike_result_t: {spikes_a, spikes_b, 0, 0}, zeroed on the stream; may be null
+    uint32_t width, height;     // W, H: W * H < 2^31
+    uint32_t radius, rank;      // R in 1..RBRT_DESPIKE_MAX_RADIUS, k in 1..RBRT_DESPIKE_MAX_RANK
+    float threshold, floor;     // t, f
+};
+
 }  // namespace rbrt

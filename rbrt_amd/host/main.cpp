@@ -23,6 +23,9 @@
 // camera: every frame's half images are accumulated onto the reprojected ones of the frames before it, the last frame is written).
 // --upscale F with --upscale-normal K, --upscale-depth K and --upscale-albedo K (the image is traced at 1 / F of its size in each
 // direction and its two half images are brought to full size under the guidance of the full-size feature buffers).
+// --despike with --despike-threshold T, --despike-rank K, --despike-radius R and --spike-map FILE (a pixel of either half image
+// that is far brighter than its neighbours in that half and than the same pixel of the other half is limited, in front of
+// every stage that reads the half images).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -84,7 +87,9 @@ void usage() {
         "      --denoise-radius <r>         denoise: radius of the search window, 0 to 10 [default: 5]\n"
         "      --denoise-patch <p>          denoise: radius of the compared patches, 0 to 4 [default: 3]\n"
         "      --denoise-strength <k>       denoise: filter strength, above 0; larger smooths more [default: 0.7]\n"
-        "      --noisy <file>               denoise: also write the unfiltered image there (same formats as the target file)\n"
+        "      --noisy <file>               denoise: also write the unfiltered image there (same formats as the target file); with\n"
+        "                                   --despike that is the image in front of spike removal (with --upscale as well: the\n"
+        "                                   plain mix of the upsampled half images, behind it)\n"
         "      --denoise-guided             filter the image with the feature buffers as guides: an edge-avoiding a-trous filter\n"
         "                                   on the images of the even and the odd samples, which smooths only where albedo,\n"
         "                                   normal and depth of the primary rays agree. Renders like --denoise and cannot be\n"
@@ -119,6 +124,18 @@ void usage() {
         "      --upscale-normal <k>         upscale: tolerance of the normal's difference, above 0 [default: 0.5]\n"
         "      --upscale-depth <k>          upscale: tolerance of the relative depth difference, above 0 [default: 0.1]\n"
         "      --upscale-albedo <k>         upscale: tolerance of the albedo's difference, above 0 [default: 0.2]\n"
+        "      --despike                    remove spikes (fireflies): a pixel of either half image whose luminance is above\n"
+        "                                   --despike-threshold times the larger of the --despike-rank-th largest luminance among\n"
+        "                                   its neighbours in that half and its own luminance in the other half is scaled down to\n"
+        "                                   that limit, in front of --upscale, --frames, --denoise and --denoise-guided. Renders\n"
+        "                                   like --denoise and cannot be combined with --adaptive, --gpus > 1, --checkpoint,\n"
+        "                                   --pass-samples or --sample-map; --samples must be at least 2; --noisy applies\n"
+        "      --despike-threshold <t>      despike: the factor above the witnesses, at least 1 [default: 4]\n"
+        "      --despike-rank <k>           despike: which of the neighbours' luminances counts, 1 to 4: k + 1 equally bright\n"
+        "                                   pixels next to each other are kept [default: 2]\n"
+        "      --despike-radius <r>         despike: radius of the neighbourhood, 1 or 2 [default: 2]\n"
+        "      --spike-map <file>           despike: write where pixels were limited there as a grey image at the size that was\n"
+        "                                   traced: 0 none, 85 the first half image, 170 the second, 255 both\n"
         "      --exposure <EV|auto>         exposure of the target image in stops (the radiance is multiplied by 2^EV), or auto:\n"
         "                                   the median luminance of the image is mapped to --exposure-key [default: 0]\n"
         "      --exposure-key <x>           automatic exposure: what the median luminance is mapped to, above 0 [default: 0.18]\n"
@@ -253,6 +270,10 @@ int main(int argc, char** argv) {
     std::string history_map;
     std::optional<uint32_t> upscale;  // --upscale turns guided upsampling on; the options below need it
     std::optional<float> upscale_normal, upscale_depth, upscale_albedo;
+    bool despike = false;  // --despike turns spike removal on; the options below need it
+    std::optional<float> despike_threshold;
+    std::optional<uint32_t> despike_rank, despike_radius;
+    std::string spike_map;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         std::string val;
@@ -527,6 +548,28 @@ int main(int argc, char** argv) {
                 return 2;
             }
             (a == "--upscale-normal" ? upscale_normal : a == "--upscale-depth" ? upscale_depth : upscale_albedo) = f;
+        } else if (a == "--despike") {
+            despike = true;
+        } else if (a == "--despike-threshold") {
+            const char* v = value();
+            float f = 0.0f;
+            if (!parse_f32(v, f) || !std::isfinite(f) || !(f >= 1.0f)) {
+                std::fprintf(stderr, "error: invalid value '%s' for '--despike-threshold' (expected a finite number >= 1)\n", v);
+                return 2;
+            }
+            despike_threshold = f;
+        } else if (a == "--despike-rank" || a == "--despike-radius") {
+            const bool rank = a == "--despike-rank";
+            const uint32_t most = rank ? RBRT_DESPIKE_MAX_RANK : RBRT_DESPIKE_MAX_RADIUS;
+            uint32_t v = 0;
+            u32(v);
+            if (v < 1u || v > most) {
+                std::fprintf(stderr, "error: invalid value '%u' for '%s' (expected 1 to %u)\n", v, a.c_str(), most);
+                return 2;
+            }
+            (rank ? despike_rank : despike_radius) = v;
+        } else if (a == "--spike-map") {
+            spike_map = value();
         } else if (a == "--shading") {
             const std::string v = value();
             if (v != "flat" && v != "smooth") {
@@ -552,7 +595,7 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "error: '--min-samples' must be at least 2 and '--adaptive-step' at least 1\n");
             return 2;
         }
-    } else if (!sample_map.empty() && !upscale) {  // (with --upscale the refusal below names both)
+    } else if (!sample_map.empty() && !upscale && !despike) {  // (with --upscale or --despike the refusal below names both)
         std::fprintf(stderr, "error: '--sample-map' needs '--adaptive'\n");
         return 2;
     }
@@ -568,7 +611,7 @@ int main(int argc, char** argv) {
         }
     } else {
         const char* alone = denoise_radius ? "--denoise-radius" : denoise_patch ? "--denoise-patch" : denoise_strength ? "--denoise-strength"
-                            : !noisy.empty() && !denoise_guided && !upscale ? "--noisy" : nullptr;
+                            : !noisy.empty() && !denoise_guided && !upscale && !despike ? "--noisy" : nullptr;
         if (alone) {
             std::fprintf(stderr, "error: '%s' needs '--denoise'\n", alone);
             return 2;
@@ -625,6 +668,25 @@ int main(int argc, char** argv) {
         const char* alone = upscale_normal ? "--upscale-normal" : upscale_depth ? "--upscale-depth" : upscale_albedo ? "--upscale-albedo" : nullptr;
         if (alone) {
             std::fprintf(stderr, "error: '%s' needs '--upscale'\n", alone);
+            return 2;
+        }
+    }
+    if (despike) {  // the half images of one round of the adaptive path on one handle: refused by name before anything is loaded
+        const char* with = adaptive ? "--adaptive" : gpus > 1 ? "--gpus > 1" : !checkpoint.empty() ? "--checkpoint" : pass_samples != 0 ? "--pass-samples"
+                           : !sample_map.empty() ? "--sample-map" : nullptr;
+        if (with) {
+            std::fprintf(stderr, "error: '--despike' cannot be combined with '%s'\n", with);
+            return 2;
+        }
+        if (samples < 2) {
+            std::fprintf(stderr, "error: '--despike' needs '--samples' of at least 2 (each half image needs a sample)\n");
+            return 2;
+        }
+    } else {
+        const char* alone = despike_threshold ? "--despike-threshold" : despike_rank ? "--despike-rank" : despike_radius ? "--despike-radius"
+                            : !spike_map.empty() ? "--spike-map" : nullptr;
+        if (alone) {
+            std::fprintf(stderr, "error: '%s' needs '--despike'\n", alone);
             return 2;
         }
     }
@@ -742,6 +804,12 @@ int main(int argc, char** argv) {
             if (upscale_depth) cfg.upscale_depth = *upscale_depth;
             if (upscale_albedo) cfg.upscale_albedo = *upscale_albedo;
         }
+        if (despike) {
+            cfg.despike = true, cfg.keep_noisy = !noisy.empty();
+            if (despike_threshold) cfg.despike_threshold = *despike_threshold;
+            if (despike_rank) cfg.despike_rank = *despike_rank;
+            if (despike_radius) cfg.despike_radius = *despike_radius;
+        }
         if (features) cfg.features = true;
         if (features || denoise_guided || frames || upscale) cfg.feature_samples = feature_samples ? *feature_samples : std::max(1u, std::min(samples, 8u));
         rbrt::ImageBuffer img = rbrt::render_scene(cam, samples, scene, cfg);
@@ -752,6 +820,14 @@ int main(int argc, char** argv) {
         if (!noisy.empty()) img.save_noisy(noisy);
         if (!radiance_file.empty()) rbrt::write_pfm(radiance_file, img.radiance.data(), img.width, img.height);
         if (features) img.save_features(*features);
+        if (!spike_map.empty()) {  // a grey image through the same writers, at the size that was traced
+            if (img.spike_map.empty() || img.spike_map.size() != size_t(img.spike_map_width) * img.spike_map_height) throw rbrt::Error("no spike map to save to " + spike_map);
+            rbrt::ImageBuffer grey;
+            grey.width = img.spike_map_width, grey.height = img.spike_map_height;
+            grey.rgb.resize(img.spike_map.size() * 3);
+            for (size_t k = 0; k < img.spike_map.size(); ++k) grey.rgb[3 * k] = grey.rgb[3 * k + 1] = grey.rgb[3 * k + 2] = img.spike_map[k];
+            grey.save(spike_map);
+        }
         if (!history_map.empty()) {  // a grey image through the same writers, like the sample map
             if (img.history_map.size() != size_t(img.width) * img.height) throw rbrt::Error("no history map to save to " + history_map);
             rbrt::ImageBuffer grey;
@@ -765,7 +841,7 @@ int main(int argc, char** argv) {
             uint64_t triangles = 0;
             for (const auto& m : scene.triangle_meshes) triangles += m.num_triangles;
             const uint32_t spp = samples_arg_for_report(samples);
-            const double rendered = adaptive || denoise || denoise_guided || frames || upscale ? double(rep.adaptive_samples)
+            const double rendered = adaptive || denoise || denoise_guided || frames || upscale || despike ? double(rep.adaptive_samples)
                                              : double(width) * double(height) * double(spp - rep.resumed_from_sample);  // path samples of THIS run
             std::string js = "{";
             const auto str = [&](const char* k, const std::string& v) { js += std::string("\"") + k + "\": \"" + json_escape(v) + "\", "; };
@@ -815,6 +891,10 @@ int main(int argc, char** argv) {
                 num("upscale", cfg.upscale, "%.0f"), num("render_width", rep.render_width, "%.0f"), num("render_height", rep.render_height, "%.0f");
                 num("upscale_normal", cfg.upscale_normal, "%.9g"), num("upscale_depth", cfg.upscale_depth, "%.9g"), num("upscale_albedo", cfg.upscale_albedo, "%.9g");
                 num("upsample_ms", rep.upsample_ms, "%.4f");
+            }
+            if (despike) {  // spike removal: its options, the stage's time on the GPU and what it limited in either half image, the means per frame
+                num("despike_threshold", cfg.despike_threshold, "%.9g"), num("despike_rank", cfg.despike_rank, "%.0f"), num("despike_radius", cfg.despike_radius, "%.0f");
+                num("despike_ms", rep.despike_ms, "%.4f"), num("spikes_a", rep.spikes_a, "%.9g"), num("spikes_b", rep.spikes_b, "%.9g");
             }
             if (glare) {  // the glare stage: its options and its time on the GPU
                 num("glare", cfg.glare_intensity, "%.9g"), num("glare_levels", cfg.glare_levels, "%.0f"), num("glare_ms", rep.glare_ms, "%.4f");

@@ -257,6 +257,8 @@ struct ImageBuffer {
     std::vector<float> feature_albedo, feature_normal;  // 3 floats per pixel
     std::vector<float> feature_depth, feature_coverage; // 1 float per pixel
     std::vector<uint8_t> history_map;  // a render with RenderConfig::frames: one byte per pixel, the last frame's len * 255 / max_history (else empty)
+    std::vector<uint8_t> spike_map;  // a render with RenderConfig::despike: one byte per traced pixel of the last frame, 0 none, 85 A, 170 B, 255 both (else empty)
+    uint32_t spike_map_width = 0, spike_map_height = 0;  // ... and its size: the traced one, which RenderConfig::upscale makes smaller than the image's
     void save_features(const std::string& prefix) const;  // PREFIX.albedo.pfm, .normal.pfm, .depth.pfm, .coverage.pfm (colour PFMs; grey as three equal channels)
     void save(const std::string& path) const;  // .png (8-bit RGB) or .ppm by extension
     void save_sample_map(const std::string& path) const;  // the sample map as a grey image, through the same writers
@@ -296,6 +298,8 @@ struct RenderReport {
     double features_ms = 0.0;  // a render with feature buffers (RenderConfig::features): rbrt_hip_render_features, between two events
     double upsample_ms = 0.0;  // a render with guided upsampling (RenderConfig::upscale): rbrt_hip_upsample_halves between two events, the mean per frame
     uint32_t render_width = 0, render_height = 0;  // ... and the size that was traced
+    double despike_ms = 0.0;  // a render with spike removal (RenderConfig::despike): rbrt_hip_despike_halves between two events, the mean per frame
+    double spikes_a = 0.0, spikes_b = 0.0;  // ... and the pixels it limited in either half image, the mean per frame
     double temporal_ms = 0.0;  // a render of several frames (RenderConfig::frames): rbrt_hip_temporal_accumulate between two events, the mean per frame
 };
 
@@ -373,6 +377,14 @@ struct RenderConfig {  // additions that the reference hard-codes or lacks
     // least 2. 0: the image is traced at its own size.
     uint32_t upscale = 0;  // 0, or 2..RBRT_UPSAMPLE_MAX_FACTOR
     float upscale_normal = 0.5f, upscale_depth = 0.1f, upscale_albedo = 0.2f;  // (rbrt_upsample_opts_default)
+    // Spike removal (rbrt_hip_despike_halves; the CLI's --despike, --despike-*): the render goes through the adaptive path's one
+    // round that stops nothing, like `frames` and `upscale`, and its two half images are limited right behind the handle, at the
+    // size that was traced, in front of upsampling, accumulation and either filter. keep_noisy keeps its meaning: the render's own
+    // image, in front of the stage (with `upscale`: the upsampled halves' mix). Inherits the adaptive path's refusals; not with
+    // `adaptive` itself; num_samples must be at least 2. ImageBuffer::spike_map is the last frame's mask.
+    bool despike = false;
+    uint32_t despike_radius = 2, despike_rank = 2;  // (rbrt_despike_opts_default; the floor stays the library's)
+    float despike_threshold = 4.0f;
 };
 // rbrt_lib::render_scene (lib.rs:75-79): blocks until the image is complete. Runs on the GPU(s)
 // through the C ABI; there is no CPU path.

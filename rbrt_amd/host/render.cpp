@@ -359,6 +359,13 @@ Plan make_plan(const RenderConfig& cfg, const std::string& adaptive_by, bool cfg
             if (!std::isfinite(k) || !(k > 0.0f)) throw Error("--upscale-normal, --upscale-depth and --upscale-albedo must be finite and above 0");
         if (cfg.feature_samples == 0 || cfg.feature_samples > 65536u) throw Error("--feature-samples must be 1 to 65536");
     }
+    if (cfg.despike) {  // (rbrt_hip.h "Spike removal": on the half images of one round of the adaptive path on one handle)
+        if (cfg_adaptive_given) throw Error("--despike cannot be combined with --adaptive");
+        if (num_samples < 2) throw Error("--despike needs at least 2 samples (each half image needs one)");
+        if (cfg.despike_radius == 0u || cfg.despike_radius > RBRT_DESPIKE_MAX_RADIUS) throw Error("--despike-radius must be 1 or 2");
+        if (cfg.despike_rank == 0u || cfg.despike_rank > RBRT_DESPIKE_MAX_RANK) throw Error("--despike-rank must be 1 to 4");
+        if (!std::isfinite(cfg.despike_threshold) || !(cfg.despike_threshold >= 1.0f)) throw Error("--despike-threshold must be finite and at least 1");
+    }
     if (cfg.features) {  // (of the whole frame, on one handle: rbrt_hip.h "Feature buffers")
         if (cfg.n_gpus > 1) throw Error("--features cannot be combined with --gpus > 1");
         if (cfg.feature_samples == 0 || cfg.feature_samples > 65536u) throw Error("--feature-samples must be 1 to 65536");
@@ -545,7 +552,7 @@ void Rank::run() {
     setup();
     sh.t_setup[rank] = seconds_since(t_start);
     const auto t_passes = std::chrono::steady_clock::now();
-    if (cfg.frames || cfg.upscale) temporal();
+    if (cfg.frames || cfg.upscale || cfg.despike) temporal();
     else if (cfg.adaptive) render_adaptive();
     else render_passes();
     if (rank == 0) sh.rep.passes = pass_no;
@@ -553,8 +560,8 @@ void Rank::run() {
     if (hs && !err.failed()) err.lib_ok(rbrt_hip_scene_check(hs));
     sh.t_render[rank] = seconds_since(t_passes);
     const auto t_g = std::chrono::steady_clock::now();
-    // (a render of several frames, or an upsampled one, has made its feature buffers and filtered its image frame by frame: temporal())
-    const bool by_frames = cfg.frames || cfg.upscale;
+    // (a render of several frames, an upsampled or a despiked one has made its feature buffers and filtered its image frame by frame: temporal())
+    const bool by_frames = cfg.frames || cfg.upscale || cfg.despike;
     if (world == 1 && !by_frames && (cfg.features || cfg.denoise_guided)) features();
     if (world == 1 && !by_frames && cfg.denoise_guided) denoise_guided();  // (in front of glare and the display transform, like denoise)
     if (world == 1) gather_single();
@@ -751,6 +758,10 @@ void Rank::download_features() {
 // feature buffers are the full camera's, and rbrt_hip_upsample_halves makes the full-size halves everything behind it reads;
 // the unfiltered image is then the plain mix of the last frame's upsampled halves. Without cfg.frames there is one frame and no
 // accumulation.
+// With cfg.despike rbrt_hip_despike_halves runs right behind the handle's half images, at the size that was traced, in front of
+// upsampling, accumulation and either filter: the handle's halves go to two buffers of their own and the stage writes where they
+// went without it. The unfiltered image stays the render's own, in front of the stage (with cfg.upscale: the upsampled halves'
+// mix, behind it). With cfg.despike alone the feature buffers are made only where something asks for them.
 void Rank::temporal() {
     if (err.failed() || !npix) return;
     const size_t n_pixels = size_t(img.width) * img.height, n = job.n();
@@ -778,8 +789,12 @@ void Rank::temporal() {
         return;
     }
     const size_t n_low = factor ? size_t((img.width + factor - 1u) / factor) * ((img.height + factor - 1u) / factor) * 3u : 0;  // values of a low half image
-    DeviceBuffer d_half_a, d_half_b, d_history[2], d_length, d_wa, d_low_a, d_low_b, d_upsample;
-    EventTimer timer, up_timer;
+    rbrt_despike_opts_t so;
+    rbrt_despike_opts_default(&so);
+    so.radius = cfg.despike_radius, so.rank = cfg.despike_rank, so.threshold = cfg.despike_threshold;
+    const bool need_features = cfg.frames || factor || cfg.denoise_guided || cfg.features;
+    DeviceBuffer d_half_a, d_half_b, d_history[2], d_length, d_wa, d_low_a, d_low_b, d_upsample, d_raw_a, d_raw_b, d_spike_mask, d_spike_result;
+    EventTimer timer, up_timer, spike_timer;
     if (!(d_features.alloc(n_pixels * 8 * sizeof(float), err, "hipMalloc(feature buffers)") && d_half_a.alloc(n * sizeof(float), err, "hipMalloc(half image)") &&
           d_half_b.alloc(n * sizeof(float), err, "hipMalloc(half image)") && d_wa.alloc(n_pixels * sizeof(float), err, "hipMalloc(mix)") && timer.create(err) &&
           up_timer.create(err)))
@@ -792,13 +807,18 @@ void Rank::temporal() {
         return;
     float* const d_albedo = d_features.as<float>();
     float *const d_normal = d_albedo + n_pixels * 3, *const d_depth = d_normal + n_pixels * 3, *const d_coverage = d_depth + n_pixels;
+    const size_t n_traced = factor ? n_low : n;  // values of a half image at the size that is traced
+    if (cfg.despike && !(d_raw_a.alloc(n_traced * sizeof(float), err, "hipMalloc(half image)") && d_raw_b.alloc(n_traced * sizeof(float), err, "hipMalloc(half image)") &&
+                         d_spike_mask.alloc(n_traced / 3u, err, "hipMalloc(spike mask)") && d_spike_result.alloc(sizeof(rbrt_despike_result_t), err, "hipMalloc(spike counts)") &&
+                         spike_timer.create(err)))
+        return;
     // every pixel of a one-round render has the same count n: h = (n + 1) / 2 samples in A, so wa = float(h) * (1.0f / float(n))
     const float inv_n = 1.0f / float(num_samples);
     const std::vector<float> wa(n_pixels, float((num_samples + 1u) / 2u) * inv_n);
     if (!err.ok(hipMemcpy(d_wa.as<float>(), wa.data(), n_pixels * sizeof(float), hipMemcpyHostToDevice), "upload of the mix")) return;
     RenderReport& rep = sh.rep;
     rbrt_camera_lens_t lens_prev = job.lens;
-    double ms_sum = 0.0, up_ms_sum = 0.0;
+    double ms_sum = 0.0, up_ms_sum = 0.0, spike_ms_sum = 0.0, spikes_a_sum = 0.0, spikes_b_sum = 0.0;
     for (uint32_t k = 0; k < n_frames && !err.failed(); ++k) {
         rbrt_camera_lens_t lens = job.lens;  // (with a thin lens the lens moves with its camera)
         for (int c = 0; c < 3; ++c) {
@@ -815,10 +835,17 @@ void Rank::temporal() {
         // (d_rad and d_rgb are full size: a low image fits)
         if (!err.lib_ok(rbrt_hip_render_adaptive(hs, &traced.cam, &ok, &ao, stream.get(), d_rad.as<float>(), d_rgb.as<uint8_t>(), nullptr, nullptr, &ar))) break;
         rep.adaptive_rounds = ar.rounds, rep.adaptive_samples += ar.samples, rep.adaptive_samples_fixed += ar.samples_fixed;
-        if (!err.lib_ok(rbrt_hip_scene_denoise(hs, &dn, stream.get(), nullptr, nullptr, (factor ? d_low_a : d_half_a).as<float>(),
-                                               (factor ? d_low_b : d_half_b).as<float>())))
+        float *const d_traced_a = (factor ? d_low_a : d_half_a).as<float>(), *const d_traced_b = (factor ? d_low_b : d_half_b).as<float>();
+        if (!err.lib_ok(rbrt_hip_scene_denoise(hs, &dn, stream.get(), nullptr, nullptr, cfg.despike ? d_raw_a.as<float>() : d_traced_a,
+                                               cfg.despike ? d_raw_b.as<float>() : d_traced_b)))
             break;
-        if (!err.lib_ok(rbrt_hip_render_features(hs, &lens.cam, &ok, &fo, stream.get(), d_albedo, d_normal, d_depth, d_coverage, nullptr))) break;
+        if (cfg.despike) {
+            spike_timer.start(stream.get(), err);
+            err.lib_ok(rbrt_hip_despike_halves(dev, stream.get(), d_raw_a.as<float>(), d_raw_b.as<float>(), traced.cam.img_width_pix, traced.cam.img_height_pix, &so,
+                                               d_traced_a, d_traced_b, d_spike_mask.as<uint8_t>(), d_spike_result.as<rbrt_despike_result_t>()));
+            spike_timer.stop(stream.get(), err);
+        }
+        if (need_features && !err.lib_ok(rbrt_hip_render_features(hs, &lens.cam, &ok, &fo, stream.get(), d_albedo, d_normal, d_depth, d_coverage, nullptr))) break;
         if (factor) {
             up_timer.start(stream.get(), err);
             err.lib_ok(rbrt_hip_upsample_halves(dev, stream.get(), d_low_a.as<float>(), d_low_b.as<float>(), nullptr, d_albedo, d_normal, d_depth, d_coverage,
@@ -840,6 +867,12 @@ void Rank::temporal() {
         float ms = 0.0f;
         if (cfg.frames && timer.elapsed(&ms, err)) ms_sum += ms;
         if (factor && up_timer.elapsed(&ms, err)) up_ms_sum += ms;
+        if (cfg.despike && !err.failed()) {
+            if (spike_timer.elapsed(&ms, err)) spike_ms_sum += ms;
+            rbrt_despike_result_t found{};
+            if (err.ok(hipMemcpy(&found, d_spike_result.as<void>(), sizeof(found), hipMemcpyDeviceToHost), "download of the spike counts"))
+                spikes_a_sum += double(found.spikes_a), spikes_b_sum += double(found.spikes_b);
+        }
         if (hs && !err.failed()) err.lib_ok(rbrt_hip_scene_check(hs));
         lens_prev = lens;
         ++pass_no;
@@ -851,8 +884,18 @@ void Rank::temporal() {
     if (err.failed()) return;
     if (cfg.frames) rep.temporal_ms = ms_sum / double(n_frames);
     if (factor) rep.upsample_ms = up_ms_sum / double(n_frames);
+    if (cfg.despike) {  // the means per frame; the mask of the last frame, at the size that was traced
+        rep.despike_ms = spike_ms_sum / double(n_frames), rep.spikes_a = spikes_a_sum / double(n_frames), rep.spikes_b = spikes_b_sum / double(n_frames);
+        std::vector<uint8_t> mask(n_traced / 3u);
+        if (err.ok(hipMemcpy(mask.data(), d_spike_mask.as<void>(), mask.size(), hipMemcpyDeviceToHost), "download of the spike mask")) {
+            img.spike_map.resize(mask.size());
+            for (size_t i = 0; i < mask.size(); ++i) img.spike_map[i] = uint8_t((mask[i] & 3u) * 85u);  // 0 none, 85 A, 170 B, 255 both
+            img.spike_map_width = factor ? (img.width + factor - 1u) / factor : img.width;
+            img.spike_map_height = factor ? (img.height + factor - 1u) / factor : img.height;
+        }
+    }
     keep_noisy();
-    download_features();
+    if (need_features) download_features();
     if (cfg.frames) {  // the history length of the last frame, as a share of the longest there can be
         std::vector<float> length(n_pixels);
         if (err.ok(hipMemcpy(length.data(), d_length.as<float>(), n_pixels * sizeof(float), hipMemcpyDeviceToHost), "download of the history length")) {
@@ -1034,7 +1077,7 @@ void report_times(const Plan& plan, const Shared& sh, RenderReport& rep) {
 
 ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& scene, const RenderConfig& cfg_in) {
     RenderConfig cfg = cfg_in;
-    if ((cfg.denoise || cfg.denoise_guided || cfg.frames || cfg.upscale) && !cfg.adaptive)  // (the filter's input is the adaptive path's sums: one round that stops nothing)
+    if ((cfg.denoise || cfg.denoise_guided || cfg.frames || cfg.upscale || cfg.despike) && !cfg.adaptive)  // (the filter's input is the adaptive path's sums: one round that stops nothing)
         cfg.adaptive = true, cfg.adaptive_threshold = 0.0f, cfg.adaptive_min_samples = cfg.adaptive_step = std::max(num_samples, 2u);
     if (!cfg.quiet) std::printf("Starting rendering...\n");
     ImageBuffer img;
@@ -1047,7 +1090,7 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
     const rbrt_camera_lens_t lens = cam.to_abi_lens();
     const Scene::AbiView view = scene.to_abi();
     const rbrt_environment_t env_abi = scene.environment.to_abi();
-    const Plan plan = make_plan(cfg, cfg_in.adaptive ? "--adaptive" : cfg_in.upscale ? "--upscale" : cfg_in.frames ? "--frames" : cfg_in.denoise_guided ? "--denoise-guided" : "--denoise", cfg_in.adaptive,
+    const Plan plan = make_plan(cfg, cfg_in.adaptive ? "--adaptive" : cfg_in.upscale ? "--upscale" : cfg_in.despike ? "--despike" : cfg_in.frames ? "--frames" : cfg_in.denoise_guided ? "--denoise-guided" : "--denoise", cfg_in.adaptive,
                                 cam, scene, num_samples);
     Job job{cfg, plan, lens, view, scene.environment.n != 0u ? &env_abi : nullptr, render_opts_of(cfg, cam, num_samples), num_samples, {}, {}, img};
     job.want = checkpoint_header(img.width, img.height, num_samples, uint32_t(plan.world), cfg.seed,

@@ -75,7 +75,10 @@ extern "C" {
                               rbrt_hip_upsample_workspace_bytes and rbrt_hip_upsample_halves: an added struct and entry
                               points, detected by the symbol), nor spike removal (rbrt_despike_opts_t,
                               rbrt_despike_result_t, rbrt_despike_opts_default and rbrt_hip_despike_halves: added structs
-                              and entry points, detected by the symbol) */
+                              and entry points, detected by the symbol), nor image comparison (rbrt_compare_opts_t,
+                              rbrt_compare_result_t, rbrt_compare_summary_t, rbrt_compare_opts_default,
+                              rbrt_hip_compare_workspace_bytes, rbrt_hip_compare_images and rbrt_compare_summary: added
+                              structs and entry points, detected by the symbol) */
 
 typedef enum rbrt_status {
     RBRT_OK = 0,
@@ -1012,6 +1015,88 @@ typedef struct rbrt_despike_result { /* what the call found; lives in device mem
 int rbrt_hip_despike_halves(int device, void* stream, const float* d_a, const float* d_b, uint32_t width, uint32_t height,
                             const rbrt_despike_opts_t* opts, float* d_out_a, float* d_out_b, uint8_t* d_mask,
                             rbrt_despike_result_t* d_result);
+
+/* ---- Image comparison: MSE, MAE, relative MSE and SSIM of an image against a reference ---------------------------------------
+ * No counterpart in the reference. Every reconstruction stage trades samples for image quality; this stage says how far an
+ * image X is from a reference R: the sums behind the mean squared, mean absolute and relative squared error, the largest
+ * absolute difference, a mean structural similarity (SSIM) on tone-compressed luminance and, per pixel, the relative error
+ * and the SSIM. The sums across workgroups take a fixed order (no float atomics: a slab of per-tile partials and a second
+ * kernel that sums it), so two calls on the same inputs give the same 64 bytes, and so does a restatement on a CPU.
+ *
+ * The rule. All per-pixel arithmetic is float32, unfused, in the written order; / is correctly rounded; a constant is the
+ * float32 nearest to the decimal written. fin, MAXF, Y(c) and pos(x) are those of "Spike removal" above. eps is the options'
+ * epsilon.
+ *   Usable pixels. A pixel p is usable when all six channels of X[p] and R[p] are fin.
+ *   Errors of a usable pixel, with e_c = X_c - R_c:
+ *     se  = ((e_r * e_r) + (e_g * e_g)) + (e_b * e_b)
+ *     ae  = (|e_r| + |e_g|) + |e_b|
+ *     rel = (((e_r * e_r) / ((R_r * R_r) + eps)) + ((e_g * e_g) / ((R_g * R_g) + eps))) + ((e_b * e_b) / ((R_b * R_b) + eps))
+ *     mx  = max(max(|e_r|, |e_g|), |e_b|)
+ *   A pixel that is not usable contributes nothing to these: it is counted in `skipped`, and its value in the rel map is +0.0f.
+ *   SSIM, at every pixel, usable or not. u = T(Y(X[p])) and v = T(Y(R[p])) with T(y) = pos(y) / (1.0f + pos(y)): a luminance
+ *   that is not finite or not above 0 stands as 0, and the range is [0, 1). The window is 11 taps, separable, with the weights
+ *     g[0..5] = 0.00102838012f, 0.00759875821f, 0.0360007733f, 0.109360687f, 0.213005543f, 0.266011715f,  g[10 - i] = g[i]
+ *   (a Gaussian of sigma 1.5, normalised; the literals are the rule, no exp is evaluated). The five planes are
+ *   m in {u, v, u * u, v * v, u * v}; coordinates are clamped to the image: cx(x) = min(max(x, 0), W - 1), cy likewise.
+ *     rows:     h_m(y, x) = sum over i = 0..10 of g[i] * m(y, cx(x + i - 5)), added left to right from the first product;
+ *     columns:  V_m(y, x) = sum over j = 0..10 of g[j] * h_m(cy(y + j - 5), x), added the same way.
+ *     mu = V_u;  mv = V_v;  su = V_uu - (mu * mu);  sv = V_vv - (mv * mv);  suv = V_uv - (mu * mv);  C1 = 0.0001f;  C2 = 0.0009f
+ *     ssim = (((2.0f * (mu * mv)) + C1) * ((2.0f * suv) + C2)) / ((((mu * mu) + (mv * mv)) + C1) * ((su + sv) + C2))
+ *   Sums. se, ae, rel and ssim are converted to double, one value per pixel, and each is summed in double in this order. The
+ *   image is cut into tiles of RBRT_COMPARE_TILE_W x RBRT_COMPARE_TILE_H pixels. A tile's 256 values are indexed
+ *   t = ty * RBRT_COMPARE_TILE_W + tx; a pixel outside the image counts as +0.0, and so does an unusable one in se, ae and rel.
+ *   They are summed by the pairwise tree: for s = 1, 2, 4, ..., 128: v[i] = v[i] + v[i + s] at every i that is a multiple of
+ *   2 s; v[0] is the tile's sum. The tiles' sums, in row-major tile order j, are summed by 256 lanes: lane t adds the tiles
+ *   j = t, t + 256, ... in ascending order onto +0.0, and the same tree over t follows. max_abs is the fmaxf of all mx (0 with
+ *   no usable pixel); usable and skipped are integer counts.
+ * Consequences. X equal to R bit for bit gives all sums 0, max_abs 0 and ssim exactly 1.0f at every pixel: the planes of u
+ * and v are then equal, and 2 * (a * a) and (a * a) + (a * a) are the same float. Swapping X and R leaves se, ae, mx and ssim
+ * unchanged (every product and sum of the SSIM is symmetric in u and v), but not rel. A pixel's ssim depends only on the
+ * 11 x 11 clamped window around it. Squares that overflow give an infinite sum, which is not hidden. */
+#define RBRT_COMPARE_TILE_W 16u
+#define RBRT_COMPARE_TILE_H 16u
+typedef struct rbrt_compare_opts {
+    float epsilon;         /* eps of rel: finite, > 0 */
+    uint32_t flags;        /* 0 */
+    uint32_t reserved[2];  /* 0 */
+} rbrt_compare_opts_t;
+void rbrt_compare_opts_default(rbrt_compare_opts_t* opts); /* epsilon = 0.01, flags 0 */
+
+typedef struct rbrt_compare_result {  /* what the call found; lives in device memory; 64 bytes */
+    double sum_se, sum_ae, sum_rel;   /* over the usable pixels */
+    double sum_ssim;                  /* over all pixels */
+    float max_abs;
+    uint32_t usable, skipped;         /* usable + skipped = width * height */
+    uint32_t reserved[5];             /* 0 */
+} rbrt_compare_result_t;
+
+typedef struct rbrt_compare_summary { /* the means a host makes of a result: rbrt_compare_summary */
+    double mse, mae, relmse, psnr_db, ssim;
+} rbrt_compare_summary_t;
+
+/* The bytes of the workspace one rbrt_hip_compare_images call at this size needs: a record of partial sums per tile. 0 where
+ * width or height is 0 or width * height >= 2^31. */
+size_t rbrt_hip_compare_workspace_bytes(uint32_t width, uint32_t height);
+
+/* The rule on buffers in DEVICE memory, all row-major: d_x and d_ref float[height][width][3] (4-byte alignment is enough; they
+ * may be the same buffer), d_rel_map and d_ssim_map float[height][width], d_result one rbrt_compare_result_t (8-byte aligned; a
+ * host reads it with a 64-byte copy behind the stream), d_workspace rbrt_hip_compare_workspace_bytes(width, height) bytes of
+ * the caller's, 8-byte aligned, needed only with d_result. Any output may be NULL; with all three NULL nothing is launched.
+ * Nothing is assumed about what the workspace or the result held before: every byte that is read has been written by this
+ * call. Needs no scene, owns no device memory, asynchronous on `stream`.
+ * RBRT_ERR_INVALID_ARG, before the device is touched: d_x, d_ref or opts NULL; d_workspace NULL with a d_result; a d_workspace
+ * or d_result that is not 8-byte aligned; width or height 0; an epsilon that is not finite or not above 0; a non-zero flag or
+ * reserved word; an output that equals an input, another output or the workspace.
+ * RBRT_ERR_UNSUPPORTED: width * height >= 2^31. */
+int rbrt_hip_compare_images(int device, void* stream, const float* d_x, const float* d_ref, uint32_t width, uint32_t height,
+                            const rbrt_compare_opts_t* opts, void* d_workspace, float* d_rel_map, float* d_ssim_map,
+                            rbrt_compare_result_t* d_result);
+
+/* Host only, needs no GPU: the means of a result that was copied to the host. With n = 3 * usable:
+ * mse = sum_se / n, mae = sum_ae / n, relmse = sum_rel / n, ssim = sum_ssim / (width * height),
+ * psnr_db = 10 * log10((peak * peak) / mse), which is +inf at an mse of 0. All five are NaN when usable is 0. */
+void rbrt_compare_summary(const rbrt_compare_result_t* result, uint32_t width, uint32_t height, double peak,
+                          rbrt_compare_summary_t* out);
 
 /* De-interleave gathered per-rank packed tile buffers (concatenated rank 0..world-1, each
  * rbrt_hip_packed_pixels(...)*3 floats, device memory) into a row-major float[H][W][3] device

@@ -580,6 +580,42 @@ def despike_halves(device: int, d_a: int, d_b: int, width: int, height: int, d_o
                                                  C.c_void_p(d_result or 0)))
 
 
+def compare_opts(epsilon: float | None = None, flags: int | None = None, reserved=(0, 0)) -> abi.CompareOpts:
+    """rbrt_compare_opts_default (epsilon 0.01, flags 0), with the parameters that are given put in."""
+    t = abi.CompareOpts()
+    load_hip().rbrt_compare_opts_default(C.byref(t))
+    if epsilon is not None:
+        t.epsilon = float(epsilon)
+    if flags is not None:
+        t.flags = int(flags)
+    for k in range(2):
+        t.reserved[k] = int(reserved[k])
+    return t
+
+
+def compare_workspace_bytes(width: int, height: int) -> int:
+    """The bytes of the workspace a compare_images call with a result needs at this size (rbrt_hip_compare_workspace_bytes)."""
+    return int(load_hip().rbrt_hip_compare_workspace_bytes(width, height))
+
+
+def compare_images(device: int, d_x: int, d_ref: int, width: int, height: int, d_workspace: int | None = None, d_rel_map: int | None = None,
+                   d_ssim_map: int | None = None, d_result: int | None = None, opts: abi.CompareOpts | None = None, stream: int | None = None):
+    """An image against a reference in device memory (rbrt_hip_compare_images): d_x and d_ref float32 [height, width, 3], the maps
+    d_rel_map and d_ssim_map float32 [height, width], d_result 64 bytes (an abi.CompareResult), d_workspace compare_workspace_bytes
+    of the caller's, needed with d_result. `opts`: compare_opts(...), None for the library's defaults. Asynchronous on `stream`."""
+    t = opts if opts is not None else compare_opts()
+    abi.check(load_hip().rbrt_hip_compare_images(device, C.c_void_p(stream or 0), C.c_void_p(d_x or 0), C.c_void_p(d_ref or 0), width, height,
+                                                 C.byref(t), C.c_void_p(d_workspace or 0), C.c_void_p(d_rel_map or 0), C.c_void_p(d_ssim_map or 0),
+                                                 C.c_void_p(d_result or 0)))
+
+
+def compare_summary(result: abi.CompareResult, width: int, height: int, peak: float = 1.0) -> abi.CompareSummary:
+    """The means of a result that was copied to the host (rbrt_compare_summary; needs no GPU): mse, mae, relmse, psnr_db, ssim."""
+    out = abi.CompareSummary()
+    load_hip().rbrt_compare_summary(C.byref(result), width, height, float(peak), C.byref(out))
+    return out
+
+
 def tonemap_opts(curve: int | None = None, exposure: float | None = None, key: float | None = None,
                  key_permille: int | None = None, white: float | None = None, white_permille: int | None = None,
                  reserved=(0, 0)) -> abi.TonemapOpts:

@@ -53,6 +53,8 @@ DESPIKE_MAX_RADIUS = 2       # rbrt_hip.h: RBRT_DESPIKE_MAX_RADIUS
 DESPIKE_MAX_RANK = 4         # rbrt_hip.h: RBRT_DESPIKE_MAX_RANK
 DESPIKE_TILE_W = 32          # rbrt_hip_debug.h: the tile of pixels one workgroup of the spike removal's kernel makes
 DESPIKE_TILE_H = 8
+COMPARE_TILE_W = 16          # rbrt_hip.h: RBRT_COMPARE_TILE_W, the tile of the image comparison's sums (part of its rule)
+COMPARE_TILE_H = 16
 GLARE_MAX_LEVELS = 8         # rbrt_hip.h: the most levels of the glare stage's pyramid
 GLARE_TILE_W = 16            # rbrt_hip_debug.h: the tile of a pyramid level one workgroup of the REDUCE kernel makes
 GLARE_TILE_H = 16
@@ -220,6 +222,19 @@ class DespikeResult(C.Structure):  # rbrt_despike_result_t: in device memory
     _fields_ = [("spikes_a", C.c_uint32), ("spikes_b", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+class CompareOpts(C.Structure):  # rbrt_compare_opts_t
+    _fields_ = [("epsilon", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class CompareResult(C.Structure):  # rbrt_compare_result_t: in device memory, 64 bytes
+    _fields_ = [("sum_se", C.c_double), ("sum_ae", C.c_double), ("sum_rel", C.c_double), ("sum_ssim", C.c_double), ("max_abs", C.c_float),
+                ("usable", C.c_uint32), ("skipped", C.c_uint32), ("reserved", C.c_uint32 * 5)]
+
+
+class CompareSummary(C.Structure):  # rbrt_compare_summary_t
+    _fields_ = [("mse", C.c_double), ("mae", C.c_double), ("relmse", C.c_double), ("psnr_db", C.c_double), ("ssim", C.c_double)]
+
+
 class Environment(C.Structure):  # rbrt_environment_t
     """An octahedral radiance map of (n + 1) x (n + 1) nodes: `nodes` points at host float32 [n + 1][n + 1][3]."""
     _fields_ = [("n", C.c_uint32), ("reserved", C.c_uint32), ("nodes", f32p)]
@@ -322,6 +337,11 @@ HIP_SYMBOLS = {
     "rbrt_despike_opts_default": (None, [C.POINTER(DespikeOpts)]),
     "rbrt_hip_despike_halves": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(DespikeOpts), C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rbrt_compare_opts_default": (None, [C.POINTER(CompareOpts)]),
+    "rbrt_hip_compare_workspace_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "rbrt_hip_compare_images": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(CompareOpts), C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rbrt_compare_summary": (None, [C.POINTER(CompareResult), C.c_uint32, C.c_uint32, C.c_double, C.POINTER(CompareSummary)]),
 }
 # ... and include/rbrt_hip_debug.h (test hooks and diagnostics, same library)
 DEBUG_SYMBOLS = {

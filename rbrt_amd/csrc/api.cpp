@@ -47,6 +47,7 @@ hipError_t launch_guided(const GuidedParams& G, uint32_t staged_max_step, hipStr
 hipError_t launch_temporal(const TemporalParams& T, hipStream_t stream);                // temporal.hip
 hipError_t launch_upsample(const UpsampleParams& U, hipStream_t stream);                // upsample.hip
 hipError_t launch_despike(const DespikeParams& D, hipStream_t stream);                  // despike.hip
+hipError_t launch_compare(const CompareParams& C, hipStream_t stream);                  // compare.hip
 hipError_t launch_unpack(const float* gathered, uint32_t width, uint32_t height, uint32_t world,
                          size_t rank_stride_pixels, float* out_radiance, uint8_t* out_rgb8, hipStream_t stream);
 hipError_t launch_trace_rays(const TraceParams& P, const float* rays, size_t n, float* out_t, int32_t* out_obj,
@@ -2569,6 +2570,65 @@ int rbrt_hip_despike_halves(int device, void* stream, const float* d_a, const fl
     if (!d_out_a && !d_out_b && !d_mask && !d_result) return RBRT_OK;
     HIP_TRY(launch_despike(D, static_cast<hipStream_t>(stream)));
     return RBRT_OK;
+}
+
+// ---- Image comparison (the rule: include/rbrt_hip.h; the kernels: compare.hip) -------------------------------------------------
+void rbrt_compare_opts_default(rbrt_compare_opts_t* o) {
+    if (!o) return;
+    o->epsilon = 0.01f, o->flags = 0u;
+    for (uint32_t& r : o->reserved) r = 0u;
+}
+
+static uint64_t compare_tiles(uint32_t width, uint32_t height) {
+    return uint64_t((width + RBRT_COMPARE_TILE_W - 1u) / RBRT_COMPARE_TILE_W) * ((height + RBRT_COMPARE_TILE_H - 1u) / RBRT_COMPARE_TILE_H);
+}
+
+size_t rbrt_hip_compare_workspace_bytes(uint32_t width, uint32_t height) {
+    if (width == 0u || height == 0u || uint64_t(width) * height >= (1ull << 31)) return 0;
+    return size_t(compare_tiles(width, height)) * sizeof(CompareTilePartial);
+}
+
+int rbrt_hip_compare_images(int device, void* stream, const float* d_x, const float* d_ref, uint32_t width, uint32_t height,
+                            const rbrt_compare_opts_t* o, void* d_workspace, float* d_rel_map, float* d_ssim_map, rbrt_compare_result_t* d_result) {
+    if (!d_x || !d_ref || !o) return fail(RBRT_ERR_INVALID_ARG, "compare_images: null argument");
+    if (d_result && !d_workspace) return fail(RBRT_ERR_INVALID_ARG, "compare_images: a result needs a workspace (null argument)");
+    if ((reinterpret_cast<uintptr_t>(d_workspace) & 7u) != 0u || (reinterpret_cast<uintptr_t>(d_result) & 7u) != 0u)
+        return fail(RBRT_ERR_INVALID_ARG, "compare_images: the workspace and the result must be 8-byte aligned");
+    if (width == 0u || height == 0u) return fail(RBRT_ERR_INVALID_ARG, "compare_images: width and height must be >= 1");
+    if (!std::isfinite(o->epsilon) || !(o->epsilon > 0.0f)) return fail(RBRT_ERR_INVALID_ARG, "compare_images: epsilon must be finite and above 0");
+    if (o->flags != 0u) return fail(RBRT_ERR_INVALID_ARG, "compare_images: unknown flag bit");
+    for (const uint32_t r : o->reserved)
+        if (r != 0u) return fail(RBRT_ERR_INVALID_ARG, "compare_images: reserved must be 0");
+    const void* const outs[4] = {d_rel_map, d_ssim_map, d_result, d_result ? d_workspace : nullptr};
+    for (int i = 0; i < 4; ++i) {
+        if (!outs[i]) continue;
+        if (outs[i] == d_x || outs[i] == d_ref) return fail(RBRT_ERR_INVALID_ARG, "compare_images: an output must not be an input");
+        for (int j = 0; j < i; ++j)
+            if (outs[i] == outs[j]) return fail(RBRT_ERR_INVALID_ARG, "compare_images: an output must not be another output");
+    }
+    if (uint64_t(width) * height >= (1ull << 31)) return fail(RBRT_ERR_UNSUPPORTED, "compare_images: 2^31 or more pixels");
+
+    CompareParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.x = d_x, P.ref = d_ref, P.rel_map = d_rel_map, P.ssim_map = d_ssim_map;
+    P.partials = d_result ? static_cast<CompareTilePartial*>(d_workspace) : nullptr, P.result = d_result;
+    P.width = width, P.height = height, P.epsilon = o->epsilon;
+    P.tiles_x = (width + RBRT_COMPARE_TILE_W - 1u) / RBRT_COMPARE_TILE_W, P.tiles = uint32_t(compare_tiles(width, height));
+    if (int rc = ensure_device(device)) return rc;
+    if (!d_rel_map && !d_ssim_map && !d_result) return RBRT_OK;
+    HIP_TRY(launch_compare(P, static_cast<hipStream_t>(stream)));
+    return RBRT_OK;
+}
+
+void rbrt_compare_summary(const rbrt_compare_result_t* r, uint32_t width, uint32_t height, double peak, rbrt_compare_summary_t* out) {
+    if (!out) return;
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    out->mse = out->mae = out->relmse = out->psnr_db = out->ssim = nan;
+    if (!r || r->usable == 0u) return;
+    const double n = 3.0 * double(r->usable);
+    out->mse = r->sum_se / n, out->mae = r->sum_ae / n, out->relmse = r->sum_rel / n;
+    out->ssim = r->sum_ssim / (double(width) * double(height));
+    out->psnr_db = 10.0 * std::log10((peak * peak) / out->mse);
 }
 
 // ---- Display transform (the rule: include/rbrt_hip.h; the kernels: tonemap.hip) ----------------------------------------------

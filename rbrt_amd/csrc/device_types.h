@@ -387,4 +387,26 @@ struct DespikeParams {
     float threshold, floor;     // t, f
 };
 
+// Image comparison (include/rbrt_hip.h "Image comparison"; compare.hip): what one tile leaves in the workspace for the reduce
+// kernel, and one rbrt_hip_compare_images call.
+struct CompareTilePartial {
+    double se, ae, rel, ssim;   // the tile's pairwise-tree sums
+    float mx;                   // the fmaxf of the tile's mx
+    uint32_t usable, skipped;   // the tile's pixels inside the image
+    uint32_t pad;               // 0
+};
+static_assert(sizeof(CompareTilePartial) == 48, "the workspace holds 48 bytes a tile");
+
+struct CompareParams {
+    const float* x;             // [H][W][3] the image
+    const float* ref;           // [H][W][3] the reference; may be x
+    float* rel_map;             // [H][W], may be null
+    float* ssim_map;            // [H][W], may be null
+    CompareTilePartial* partials;  // [tiles] the caller's workspace; null without a result
+    void* result;               // the rbrt_compare_result_t, may be null
+    uint32_t width, height;     // W, H: W * H < 2^31
+    uint32_t tiles_x, tiles;    // ceil(W / 16), and that times ceil(H / 16)
+    float epsilon;              // eps
+};
+
 }  // namespace rbrt

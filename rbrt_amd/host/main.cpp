@@ -26,6 +26,8 @@
 // --despike with --despike-threshold T, --despike-rank K, --despike-radius R and --spike-map FILE (a pixel of either half image
 // that is far brighter than its neighbours in that half and than the same pixel of the other half is limited, in front of
 // every stage that reads the half images).
+// --compare REF.pfm with --compare-epsilon E, --error-map FILE and --ssim-map FILE (the frame's final linear radiance against a
+// reference image of the same size: MSE, MAE, relative MSE, PSNR and SSIM, on the GPU, in a fixed order of summation).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -136,6 +138,18 @@ void usage() {
         "      --despike-radius <r>         despike: radius of the neighbourhood, 1 or 2 [default: 2]\n"
         "      --spike-map <file>           despike: write where pixels were limited there as a grey image at the size that was\n"
         "                                   traced: 0 none, 85 the first half image, 170 the second, 255 both\n"
+        "      --compare <ref.pfm>          compare the final linear radiance (what --radiance writes; with --frames the last\n"
+        "                                   frame) with this colour PFM of the same size, on the GPU, after the frame: prints the\n"
+        "                                   MSE, MAE, relative MSE, PSNR (peak 1) and mean SSIM; --report gains compare_*. The\n"
+        "                                   sums take a fixed order: the same images give the same bits. Works with every other\n"
+        "                                   flag; pixels with a channel that is not finite are skipped and counted\n"
+        "      --compare-epsilon <e>        compare: the epsilon of the relative error (x - r)^2 / (r^2 + e), above 0\n"
+        "                                   [default: 0.01]\n"
+        "      --error-map <file>           compare: write the relative error of every pixel there: .pfm as floats (a colour PFM\n"
+        "                                   of three equal channels), any other target format as 8-bit grey, 0 black to 1 and\n"
+        "                                   above white\n"
+        "      --ssim-map <file>            compare: write the SSIM of every pixel there, likewise: 8-bit grey from 0 and below\n"
+        "                                   black to 1 (identical) white\n"
         "      --exposure <EV|auto>         exposure of the target image in stops (the radiance is multiplied by 2^EV), or auto:\n"
         "                                   the median luminance of the image is mapped to --exposure-key [default: 0]\n"
         "      --exposure-key <x>           automatic exposure: what the median luminance is mapped to, above 0 [default: 0.18]\n"
@@ -274,6 +288,8 @@ int main(int argc, char** argv) {
     std::optional<float> despike_threshold;
     std::optional<uint32_t> despike_rank, despike_radius;
     std::string spike_map;
+    std::string compare_file, error_map, ssim_map;  // --compare turns the comparison on; the maps and the epsilon need it
+    std::optional<float> compare_epsilon;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         std::string val;
@@ -570,6 +586,27 @@ int main(int argc, char** argv) {
             (rank ? despike_rank : despike_radius) = v;
         } else if (a == "--spike-map") {
             spike_map = value();
+        } else if (a == "--compare") {
+            compare_file = value();
+            if (compare_file.empty()) {
+                std::fprintf(stderr, "error: invalid value '' for '--compare' (expected a PFM file)\n");
+                return 2;
+            }
+        } else if (a == "--compare-epsilon") {
+            const char* v = value();
+            float f = 0.0f;
+            if (!parse_f32(v, f) || !std::isfinite(f) || !(f > 0.0f)) {
+                std::fprintf(stderr, "error: invalid value '%s' for '--compare-epsilon' (expected a finite number above 0)\n", v);
+                return 2;
+            }
+            compare_epsilon = f;
+        } else if (a == "--error-map" || a == "--ssim-map") {
+            const std::string v = value();
+            if (v.empty()) {
+                std::fprintf(stderr, "error: invalid value '' for '%s' (expected a file)\n", a.c_str());
+                return 2;
+            }
+            (a == "--error-map" ? error_map : ssim_map) = v;
         } else if (a == "--shading") {
             const std::string v = value();
             if (v != "flat" && v != "smooth") {
@@ -687,6 +724,26 @@ int main(int argc, char** argv) {
                             : !spike_map.empty() ? "--spike-map" : nullptr;
         if (alone) {
             std::fprintf(stderr, "error: '%s' needs '--despike'\n", alone);
+            return 2;
+        }
+    }
+    rbrt::PfmImage compare_ref;  // read, and its size checked, before anything is loaded or rendered
+    if (compare_file.empty()) {
+        const char* alone = compare_epsilon ? "--compare-epsilon" : !error_map.empty() ? "--error-map" : !ssim_map.empty() ? "--ssim-map" : nullptr;
+        if (alone) {
+            std::fprintf(stderr, "error: '%s' needs '--compare'\n", alone);
+            return 2;
+        }
+    } else {
+        try {
+            compare_ref = rbrt::read_pfm(compare_file, true);
+        } catch (const std::exception& e) {
+            std::fprintf(stderr, "error: '--compare': cannot read the reference: %s\n", e.what());
+            return 2;
+        }
+        if (compare_ref.width != width || compare_ref.height != height) {
+            std::fprintf(stderr, "error: '--compare': the reference '%s' is %u x %u, the image %u x %u\n", compare_file.c_str(), compare_ref.width, compare_ref.height,
+                         width, height);
             return 2;
         }
     }
@@ -813,6 +870,14 @@ int main(int argc, char** argv) {
         if (features) cfg.features = true;
         if (features || denoise_guided || frames || upscale) cfg.feature_samples = feature_samples ? *feature_samples : std::max(1u, std::min(samples, 8u));
         rbrt::ImageBuffer img = rbrt::render_scene(cam, samples, scene, cfg);
+        // the comparison: after the frame, on device 0, whatever made the frame (its time on the host is a part of the report's other_s)
+        rbrt::ImageComparison cmp;
+        if (!compare_file.empty()) {
+            cmp = rbrt::compare_images(img, compare_ref, compare_epsilon ? *compare_epsilon : 0.01f, !error_map.empty(), !ssim_map.empty());
+            std::printf("Compared with %s: mse %.9g, mae %.9g, relmse %.9g, psnr %.4f dB, ssim %.6f, max abs %.9g, %u pixels usable, %u skipped\n", compare_file.c_str(),
+                        cmp.summary.mse, cmp.summary.mae, cmp.summary.relmse, cmp.summary.psnr_db, cmp.summary.ssim, double(cmp.result.max_abs), cmp.result.usable,
+                        cmp.result.skipped);
+        }
         std::printf("Saving rendered image to %s\n", target.c_str());
         const auto t3 = clock::now();
         img.save(target);
@@ -828,6 +893,27 @@ int main(int argc, char** argv) {
             for (size_t k = 0; k < img.spike_map.size(); ++k) grey.rgb[3 * k] = grey.rgb[3 * k + 1] = grey.rgb[3 * k + 2] = img.spike_map[k];
             grey.save(spike_map);
         }
+        // a map of the comparison: .pfm gets the floats (three equal channels, like the feature buffers' grey files), every other
+        // name an 8-bit grey through the target's writers: v clipped to [0, 1], times 255, rounded to nearest; NaN is black
+        const auto save_map = [&](const std::string& path, const std::vector<float>& m) {
+            if (m.size() != size_t(img.width) * img.height) throw rbrt::Error("no map to save to " + path);
+            if (path.size() >= 4 && path.compare(path.size() - 4, 4, ".pfm") == 0) {
+                std::vector<float> three(m.size() * 3);
+                for (size_t k = 0; k < m.size(); ++k) three[3 * k] = three[3 * k + 1] = three[3 * k + 2] = m[k];
+                rbrt::write_pfm(path, three.data(), img.width, img.height);
+                return;
+            }
+            rbrt::ImageBuffer grey;
+            grey.width = img.width, grey.height = img.height;
+            grey.rgb.resize(m.size() * 3);
+            for (size_t k = 0; k < m.size(); ++k) {
+                const float t = m[k] > 0.0f ? std::min(m[k], 1.0f) : 0.0f;
+                grey.rgb[3 * k] = grey.rgb[3 * k + 1] = grey.rgb[3 * k + 2] = uint8_t(std::floor((t * 255.0f) + 0.5f));
+            }
+            grey.save(path);
+        };
+        if (!error_map.empty()) save_map(error_map, cmp.rel_map);
+        if (!ssim_map.empty()) save_map(ssim_map, cmp.ssim_map);
         if (!history_map.empty()) {  // a grey image through the same writers, like the sample map
             if (img.history_map.size() != size_t(img.width) * img.height) throw rbrt::Error("no history map to save to " + history_map);
             rbrt::ImageBuffer grey;
@@ -903,6 +989,17 @@ int main(int argc, char** argv) {
                 str("tonemap", tone_curve == RBRT_TONE_LINEAR ? "none" : tone_curve == RBRT_TONE_REINHARD ? "reinhard" : "aces");
                 num("exposure", rep.tonemap_exposure, "%.9g"), num("white", rep.tonemap_white, "%.9g");
                 num("luminance_counted", rep.luminance_counted, "%.0f"), num("tonemap_ms", rep.tonemap_ms, "%.4f");
+            }
+            if (!compare_file.empty()) {  // the comparison with the reference: doubles with 17 digits, so that they read back bit for bit;
+                                          // one that is not finite (the PSNR of identical images) as a string, "inf", "-inf" or "nan"
+                const auto dbl = [&](const char* k, double v) {
+                    if (std::isfinite(v)) num(k, v, "%.17g");
+                    else str(k, std::isnan(v) ? "nan" : v > 0 ? "inf" : "-inf");
+                };
+                str("compare_file", compare_file), num("compare_epsilon", compare_epsilon ? *compare_epsilon : 0.01f, "%.9g");
+                dbl("compare_mse", cmp.summary.mse), dbl("compare_mae", cmp.summary.mae), dbl("compare_relmse", cmp.summary.relmse);
+                dbl("compare_psnr_db", cmp.summary.psnr_db), dbl("compare_ssim", cmp.summary.ssim), dbl("compare_max_abs", double(cmp.result.max_abs));
+                num("compare_usable", cmp.result.usable, "%.0f"), num("compare_skipped", cmp.result.skipped, "%.0f"), num("compare_ms", cmp.ms, "%.4f");
             }
             if (features) {  // the feature buffers: their samples a pixel and their time on the GPU (a part of gather_s)
                 char b[96];

@@ -386,6 +386,19 @@ struct RenderConfig {  // additions that the reference hard-codes or lacks
     uint32_t despike_radius = 2, despike_rank = 2;  // (rbrt_despike_opts_default; the floor stays the library's)
     float despike_threshold = 4.0f;
 };
+// What compare_images found (rbrt_hip.h "Image comparison"): the stage's result as it left the device, the means of it with a peak
+// of 1, the stage's time between two events, and the maps that were asked for, one float per pixel (else empty).
+struct ImageComparison {
+    uint32_t width = 0, height = 0;
+    rbrt_compare_result_t result{};
+    rbrt_compare_summary_t summary{};
+    double ms = 0.0;
+    std::vector<float> rel_map, ssim_map;
+};
+// The image's linear radiance against a reference of the same size (the CLI's --compare, --compare-epsilon, --error-map,
+// --ssim-map): uploads both to device 0, runs rbrt_hip_compare_images between two events and brings back what it made.
+// Throws Error: another size, a bad epsilon, anything the device refuses.
+ImageComparison compare_images(const ImageBuffer& img, const PfmImage& ref, float epsilon = 0.01f, bool want_rel_map = false, bool want_ssim_map = false);
 // rbrt_lib::render_scene (lib.rs:75-79): blocks until the image is complete. Runs on the GPU(s)
 // through the C ABI; there is no CPU path.
 ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& scene, const RenderConfig& cfg = {});

@@ -1130,4 +1130,52 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
     return img;
 }
 
+// rbrt_hip_compare_images on the image's linear radiance and a reference of its size, on device 0: both are uploaded, the stage
+// runs between two events on a stream of this call's making, and the result, the means and the maps that were asked for come
+// back. Every device object is this call's own and ends with it.
+ImageComparison compare_images(const ImageBuffer& img, const PfmImage& ref, float epsilon, bool want_rel_map, bool want_ssim_map) {
+    if (img.width == 0u || img.height == 0u || img.radiance.size() != size_t(img.width) * img.height * 3u) throw Error("compare: the image holds no radiance");
+    if (ref.width != img.width || ref.height != img.height || ref.rgb.size() != img.radiance.size())
+        throw Error("compare: the reference is " + std::to_string(ref.width) + " x " + std::to_string(ref.height) + ", the image " + std::to_string(img.width) + " x " +
+                    std::to_string(img.height));
+    if (!std::isfinite(epsilon) || !(epsilon > 0.0f)) throw Error("--compare-epsilon must be finite and above 0");
+    rbrt_compare_opts_t o;
+    rbrt_compare_opts_default(&o);
+    o.epsilon = epsilon;
+    const size_t n_pixels = size_t(img.width) * img.height, image_bytes = n_pixels * 3u * sizeof(float), map_bytes = n_pixels * sizeof(float);
+    ImageComparison out;
+    out.width = img.width, out.height = img.height;
+    FirstError err;
+    Stream stream;
+    EventTimer timer;
+    DeviceBuffer d_x, d_ref, d_ws, d_rel, d_ssim, d_result;
+    float ms = 0.0f;
+    if (err.ok(hipSetDevice(0), "hipSetDevice") && stream.create(err) && timer.create(err) && d_x.alloc(image_bytes, err, "hipMalloc(compared image)") &&
+        d_ref.alloc(image_bytes, err, "hipMalloc(reference image)") &&
+        d_ws.alloc(rbrt_hip_compare_workspace_bytes(img.width, img.height), err, "hipMalloc(compare workspace)") &&
+        d_result.alloc(sizeof(rbrt_compare_result_t), err, "hipMalloc(compare result)") && (!want_rel_map || d_rel.alloc(map_bytes, err, "hipMalloc(error map)")) &&
+        (!want_ssim_map || d_ssim.alloc(map_bytes, err, "hipMalloc(ssim map)")) &&
+        err.ok(hipMemcpyAsync(d_x.as<void>(), img.radiance.data(), image_bytes, hipMemcpyHostToDevice, stream.get()), "upload of the image") &&
+        err.ok(hipMemcpyAsync(d_ref.as<void>(), ref.rgb.data(), image_bytes, hipMemcpyHostToDevice, stream.get()), "upload of the reference")) {
+        timer.start(stream.get(), err);
+        err.lib_ok(rbrt_hip_compare_images(0, stream.get(), d_x.as<float>(), d_ref.as<float>(), img.width, img.height, &o, d_ws.as<void>(), d_rel.as<float>(),
+                                           d_ssim.as<float>(), d_result.as<rbrt_compare_result_t>()));
+        timer.stop(stream.get(), err);
+        if (!err.failed()) err.ok(hipStreamSynchronize(stream.get()), "hipStreamSynchronize(compare)");
+        if (timer.elapsed(&ms, err)) out.ms = double(ms);
+        if (!err.failed()) err.ok(hipMemcpy(&out.result, d_result.as<void>(), sizeof(out.result), hipMemcpyDeviceToHost), "download of the comparison");
+        if (want_rel_map && !err.failed()) {
+            out.rel_map.resize(n_pixels);
+            err.ok(hipMemcpy(out.rel_map.data(), d_rel.as<void>(), map_bytes, hipMemcpyDeviceToHost), "download of the error map");
+        }
+        if (want_ssim_map && !err.failed()) {
+            out.ssim_map.resize(n_pixels);
+            err.ok(hipMemcpy(out.ssim_map.data(), d_ssim.as<void>(), map_bytes, hipMemcpyDeviceToHost), "download of the ssim map");
+        }
+    }
+    if (err.failed()) throw Error("compare: " + err.message());
+    rbrt_compare_summary(&out.result, img.width, img.height, 1.0, &out.summary);
+    return out;
+}
+
 }  // namespace rbrt

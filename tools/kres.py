@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Print VGPR / spill / scratch / occupancy of every kernel in kernels.hip, denoise.hip, tonemap.hip, glare.hip, guided.hip, temporal.hip, upsample.hip and despike.hip (hipcc -Rpass-analysis)."""
+"""Print VGPR / spill / scratch / occupancy of every kernel in kernels.hip, denoise.hip, tonemap.hip, glare.hip, guided.hip, temporal.hip, upsample.hip, despike.hip and compare.hip (hipcc -Rpass-analysis)."""
 import re
 import subprocess
 import sys
@@ -8,7 +8,7 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
 flags = subprocess.run(["make", "-s", "-C", str(ROOT), "print-hipflags"], capture_output=True, text=True, check=True).stdout.split()
 out = ""
-for src in ("kernels.hip", "denoise.hip", "tonemap.hip", "glare.hip", "guided.hip", "temporal.hip", "upsample.hip", "despike.hip"):
+for src in ("kernels.hip", "denoise.hip", "tonemap.hip", "glare.hip", "guided.hip", "temporal.hip", "upsample.hip", "despike.hip", "compare.hip"):
     cmd = ["/opt/rocm/bin/hipcc", *flags, f"-I{ROOT}/include", "--cuda-device-only",
            "-c", str(ROOT / "rbrt_amd/csrc" / src), "-o", "/tmp/kres.o", "-Rpass-analysis=kernel-resource-usage"]
     out += subprocess.run(cmd, capture_output=True, text=True).stderr

@@ -54,7 +54,8 @@ extern "C" {
                               them answers a kind-3 material with RBRT_ERR_INVALID_ARG), nor RBRT_FLAG_THIN_LENS with its
                               rbrt_camera_lens_t (rbrt_camera_t stays as it is: the lens wraps it) and
                               rbrt_hip_supported_flags, nor the smooth shading of meshes (rbrt_scene_shading_t and the
-                              two *_shaded entry points: rbrt_mesh_t and rbrt_scene_t stay as they are), nor adaptive
+                              two *_shaded entry points: rbrt_mesh_t and rbrt_scene_t stay as they are), nor solid patterns
+                              (rbrt_scene_patterns_t and the two *_patterned entry points, detected by the symbol), nor adaptive
                               sampling (rbrt_hip_render_adaptive with its two structs: an added entry point), nor the
                               denoiser (rbrt_denoise_opts_t, rbrt_denoise_opts_default, rbrt_hip_denoise_halves and
                               rbrt_hip_scene_denoise: added entry points), nor environment lighting (rbrt_environment_t and
@@ -201,6 +202,33 @@ typedef struct rbrt_scene_shading {
     const rbrt_mesh_normals_t* meshes;  /* [n_meshes], the scene's mesh order; NULL = every mesh flat */
 } rbrt_scene_shading_t;
 
+/* Solid patterns (no counterpart in the reference, where an object has one albedo). An object whose material is
+ * RBRT_MAT_LAMBERTIAN may carry a 3-D checker in world space: two albedos, chosen by the cell the hit point lies in. When
+ * scatter runs at the hit point p = o + t d of such an object (the point it scatters from anyway), in float32, unfused, in
+ * this order, with inv = 1.0f / size computed once on the host, per component c:
+ *     t_c = (p_c - origin_c) * inv
+ *     u_c = min(max(t_c, -1e9f), 1e9f)        (fmaxf, fminf: the other operand when one is NaN, so a NaN counts as -1e9)
+ *     k_c = int32(floor(u_c))
+ *     odd = (k_x ^ k_y ^ k_z) & 1             (an xor of parities cannot overflow where a sum could)
+ * A hit in an odd cell attenuates the path with albedo2, a hit in an even cell with the material's albedo. Nothing else
+ * changes: the scatter direction and its draws, what is hit (the BVH, the tile pass), the order of the fold, the counters,
+ * emitters, the lens, smooth shading, the environment. A scene without patterns renders bit for bit as it does through
+ * the other entry points; a pattern whose albedo2 equals the material's albedo renders bit for bit as the scene without it.
+ * The feature buffers' albedo (rbrt_hip_render_features) is the cell's colour, sample by sample. */
+#define RBRT_PATTERN_NONE 0u
+#define RBRT_PATTERN_CHECKER 1u
+typedef struct rbrt_pattern {      /* 32 bytes */
+    uint32_t kind;                 /* RBRT_PATTERN_* */
+    float albedo2[3];              /* the odd cells' albedo; the even cells have the material's own */
+    float origin[3];
+    float size;                    /* a cell's edge, world units */
+} rbrt_pattern_t;
+typedef struct rbrt_scene_patterns {
+    uint32_t n_objects;            /* == n_spheres + n_triangles + n_meshes */
+    uint32_t reserved;             /* 0 */
+    const rbrt_pattern_t* objects; /* [n_objects], by object id (rbrt_scene_t's numbering); NULL = none */
+} rbrt_scene_patterns_t;
+
 /* The 8 of Camera's 14 fields (cam.rs:4-19) that get_ray_through_pixel (cam.rs:64-82) reads. */
 typedef struct rbrt_camera {
     float position[3];
@@ -305,6 +333,10 @@ int rbrt_hip_render(const rbrt_camera_t* cam, const rbrt_scene_t* scene,
 /* The same with smooth meshes (rbrt_hip_scene_create_shaded's checks); shading = NULL is rbrt_hip_render. */
 int rbrt_hip_render_shaded(const rbrt_camera_t* cam, const rbrt_scene_t* scene, const rbrt_scene_shading_t* shading,
                            const rbrt_render_opts_t* opts, float* out_radiance, uint8_t* out_rgb8);
+/* ... and with solid patterns (rbrt_hip_scene_create_patterned's checks); patterns = NULL is rbrt_hip_render_shaded. */
+int rbrt_hip_render_patterned(const rbrt_camera_t* cam, const rbrt_scene_t* scene, const rbrt_scene_shading_t* shading,
+                              const rbrt_scene_patterns_t* patterns, const rbrt_render_opts_t* opts, float* out_radiance,
+                              uint8_t* out_rgb8);
 
 /* ---- resident scene: upload + BVH build once, render many times --------------------------- */
 
@@ -316,6 +348,17 @@ int rbrt_hip_scene_destroy(rbrt_hip_scene_t* scene);
  * entries included). rbrt_hip_render_device and rbrt_hip_render_pass need nothing more on a handle made this way. */
 int rbrt_hip_scene_create_shaded(const rbrt_scene_t* scene, const rbrt_scene_shading_t* shading, int device,
                                  rbrt_hip_scene_t** out);
+/* rbrt_hip_scene_create_shaded with solid patterns (rbrt_scene_patterns_t above). patterns = NULL, or objects = NULL, or
+ * every kind RBRT_PATTERN_NONE behaves exactly like rbrt_hip_scene_create_shaded: the same image, the same LDS per wave.
+ * There is no flag bit: a host detects the capability by this symbol. The handle keeps its patterns for its lifetime and
+ * every render call on it honours them. Before the device is touched, RBRT_ERR_INVALID_ARG: patterns->n_objects differs
+ * from the scene's object count, reserved != 0, an unknown kind, a checker on an object that is not RBRT_MAT_LAMBERTIAN, a
+ * size that is not finite or <= 0 or whose 1.0f / size is not finite, a non-finite origin, a non-finite or negative
+ * albedo2 component. RBRT_ERR_UNSUPPORTED: more than 256 objects and patterned objects together (a path records one byte
+ * per bounce, and a patterned object takes a second value of that byte for its odd cells; the scene's own limit of 255
+ * objects stands). */
+int rbrt_hip_scene_create_patterned(const rbrt_scene_t* scene, const rbrt_scene_shading_t* shading,
+                                    const rbrt_scene_patterns_t* patterns, int device, rbrt_hip_scene_t** out);
 
 /* Number of pixels this rank owns for a W x H image under (tile_rank, tile_world), counting
  * the padded pixels of partial edge tiles (each tile contributes RBRT_TILE*RBRT_TILE slots). */
@@ -663,7 +706,8 @@ int rbrt_hip_glare(int device, void* stream, const float* d_radiance, uint32_t w
  *     d = normalize(F - o). A sample's stream does not depend on spp, so n is independent of opts->spp.
  *   Hit.  The closest hit is Scene::hit with opts->min_dist and opts->max_dist: what rbrt_hip_trace_rays returns.
  *   Per sample:             a ray that hits nothing    a hit of object k with material m
- *     albedo a              (0, 0, 0)                  lambertian, metal: m.albedo; dielectric: (1, 1, 1), its attenuation;
+ *     albedo a              (0, 0, 0)                  lambertian, metal: m.albedo (a patterned lambertian: the colour of the hit's
+ *                                                      cell, rbrt_pattern_t); dielectric: (1, 1, 1), its attenuation;
  *                                                      emissive: m.albedo, the emitted radiance, which may exceed 1
  *     normal N              (0, 0, 0)                  normalize(g): three divisions by the length. g is the normal the scatter pass
  *                                                      would use for this ray, what rbrt_hip_debug_shading_normals returns: a

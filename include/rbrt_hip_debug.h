@@ -197,6 +197,14 @@ int rbrt_hip_debug_primary_cull_opts(rbrt_hip_scene_t* scene, const rbrt_camera_
 int rbrt_hip_debug_shading_normals(rbrt_hip_scene_t* scene, const float* rays, size_t n, float min_dist, float max_dist,
                                    float* out_normal);
 
+/* Test hook for solid patterns (rbrt_hip.h rbrt_scene_patterns_t): for each of n rays (ox, oy, oz, dx, dy, dz; host array),
+ * the attenuation scatter would record at its closest hit (rbrt_hip_trace_rays' hit), the material entry chosen by the same
+ * device function the scatter pass, the short-path stage and the feature buffers use: a patterned object gives its cell's
+ * colour, other lambertians and metals their albedo, a dielectric (1, 1, 1), an emitter its radiance.
+ * out_albedo: host float[n][3], NaN for a miss. */
+int rbrt_hip_debug_surface_albedo(rbrt_hip_scene_t* scene, const float* rays, size_t n, float min_dist, float max_dist,
+                                  float* out_albedo);
+
 /* Test hook for environment lighting (rbrt_hip.h rbrt_environment_t): the lookup alone, for n directions (dx, dy, dz; host
  * array, used as they are), through the same device function the trace kernel and the background-only kernels call.
  * out_rgb: host float[n][3]. RBRT_ERR_INVALID_ARG when the handle has no environment. */

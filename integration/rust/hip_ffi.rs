@@ -56,6 +56,19 @@ pub struct RbrtSceneShading {                          // rbrt_scene_shading_t: 
     pub reserved: u32,                                 // 0
     pub meshes: *const RbrtMeshNormals,                // one per mesh, or null = every mesh flat
 }
+#[repr(C)] #[derive(Copy, Clone)]
+pub struct RbrtPattern {                               // rbrt_pattern_t: a solid pattern of one lambertian object, 32 bytes
+    pub kind: u32,                                     // 0 none, 1 checker
+    pub albedo2: [f32; 3],                             // the odd cells' albedo; the even cells have the material's own
+    pub origin: [f32; 3],
+    pub size: f32,                                     // a cell's edge, world units
+}
+#[repr(C)]
+pub struct RbrtScenePatterns {                         // rbrt_scene_patterns_t
+    pub n_objects: u32,                                // == n_spheres + n_triangles + n_meshes
+    pub reserved: u32,                                 // 0
+    pub objects: *const RbrtPattern,                   // by object id, or null = none
+}
 #[repr(C)]
 pub struct RbrtRenderOpts {
     pub spp: u32, pub max_depth: u32, pub min_dist: f32, pub max_dist: f32, pub bg: [f32; 3],
@@ -93,6 +106,12 @@ extern "C" {
                            out_radiance: *mut f32, out_rgb8: *mut u8) -> c_int;
     pub fn rbrt_hip_render_shaded(cam: *const RbrtCamera, scene: *const RbrtScene, shading: *const RbrtSceneShading,
                                   opts: *const RbrtRenderOpts, out_radiance: *mut f32, out_rgb8: *mut u8) -> c_int;
+    // solid patterns: a host detects the capability by the symbol (no flag bit); patterns = null is rbrt_hip_render_shaded
+    pub fn rbrt_hip_render_patterned(cam: *const RbrtCamera, scene: *const RbrtScene, shading: *const RbrtSceneShading,
+                                     patterns: *const RbrtScenePatterns, opts: *const RbrtRenderOpts, out_radiance: *mut f32,
+                                     out_rgb8: *mut u8) -> c_int;
+    pub fn rbrt_hip_scene_create_patterned(scene: *const RbrtScene, shading: *const RbrtSceneShading, patterns: *const RbrtScenePatterns,
+                                           device: c_int, out: *mut *mut c_void) -> c_int;
     // device pointers; needs no scene handle. A host detects it by the symbol (the ABI version stays 2).
     pub fn rbrt_tonemap_opts_default(opts: *mut RbrtTonemapOpts);
     pub fn rbrt_hip_tonemap(device: c_int, stream: *mut c_void, d_radiance: *const f32, n_pixels: usize, opts: *const RbrtTonemapOpts,

@@ -52,8 +52,10 @@ def render_scene(cam: abi.Camera, num_samples: int, scene: abi.SceneData, seed: 
     rad = np.zeros((H, W, 3), np.float32) if want_radiance else None
     rgb = np.empty((H, W, 3), np.uint8) if not want_radiance else np.zeros((H, W, 3), np.uint8)
     out = (rad.ctypes.data_as(abi.f32p) if want_radiance else None, rgb.ctypes.data_as(abi.u8p))
-    shading = _shading_ptr(scene)
-    if shading is None:
+    shading, patterns = _shading_ptr(scene), _patterns_ptr(scene)
+    if patterns is not None:
+        rc = lib.rbrt_hip_render_patterned(cam_p, scene.ptr(), shading, patterns, C.byref(opts), *out)
+    elif shading is None:
         rc = lib.rbrt_hip_render(cam_p, scene.ptr(), C.byref(opts), *out)
     else:
         rc = lib.rbrt_hip_render_shaded(cam_p, scene.ptr(), shading, C.byref(opts), *out)
@@ -64,6 +66,12 @@ def render_scene(cam: abi.Camera, num_samples: int, scene: abi.SceneData, seed: 
 def _shading_ptr(scene):
     """The scene's rbrt_scene_shading_t*, None when no mesh carries corner normals."""
     f = getattr(scene, "shading_ptr", None)
+    return f() if f is not None else None
+
+
+def _patterns_ptr(scene):
+    """The scene's rbrt_scene_patterns_t*, None when no object carries a solid pattern."""
+    f = getattr(scene, "patterns_ptr", None)
     return f() if f is not None else None
 
 
@@ -82,8 +90,10 @@ class HipScene:
         self._h = C.c_void_p()
         self.device = device
         self.scene = scene  # keep host arrays alive
-        shading = _shading_ptr(scene)
-        if shading is None:
+        shading, patterns = _shading_ptr(scene), _patterns_ptr(scene)
+        if patterns is not None:
+            abi.check(self._lib.rbrt_hip_scene_create_patterned(scene.ptr(), shading, patterns, device, C.byref(self._h)))
+        elif shading is None:
             abi.check(self._lib.rbrt_hip_scene_create(scene.ptr(), device, C.byref(self._h)))
         else:
             abi.check(self._lib.rbrt_hip_scene_create_shaded(scene.ptr(), shading, device, C.byref(self._h)))
@@ -346,6 +356,15 @@ class HipScene:
         abi.check(self._lib.rbrt_hip_debug_primary_cull_lens(self._h, C.byref(lens), out.ctypes.data_as(C.POINTER(C.c_uint32)),
                                                              out.size))
         return out.reshape(ty, tx)
+
+    def surface_albedo(self, rays, min_dist=0.001, max_dist=2000.0):
+        """The attenuation scatter would record at each ray's closest hit, NaN for a miss (rbrt_hip_debug_surface_albedo;
+        test hook): float32 (n, 3)."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        out = np.zeros((rays.shape[0], 3), np.float32)
+        abi.check(self._lib.rbrt_hip_debug_surface_albedo(self._h, rays.ctypes.data_as(abi.f32p), rays.shape[0], min_dist,
+                                                          max_dist, out.ctypes.data_as(abi.f32p)))
+        return out
 
     def shading_normals(self, rays, min_dist=0.001, max_dist=2000.0):
         """The normal the scatter pass would use at each ray's closest hit, NaN for a miss (rbrt_hip_debug_shading_normals;

@@ -116,6 +116,24 @@ class SceneShading(C.Structure):
     _fields_ = [("n_meshes", C.c_uint32), ("reserved", C.c_uint32), ("meshes", C.POINTER(MeshNormals))]
 
 
+PATTERN_NONE, PATTERN_CHECKER = 0, 1
+
+
+class Pattern(C.Structure):
+    """rbrt_pattern_t: a solid pattern of one object (32 bytes)."""
+    _fields_ = [("kind", C.c_uint32), ("albedo2", C.c_float * 3), ("origin", C.c_float * 3), ("size", C.c_float)]
+
+
+class ScenePatterns(C.Structure):
+    """rbrt_scene_patterns_t: one Pattern per object of the scene, by object id."""
+    _fields_ = [("n_objects", C.c_uint32), ("reserved", C.c_uint32), ("objects", C.POINTER(Pattern))]
+
+
+def checker(albedo2, size, origin=(0.0, 0.0, 0.0)) -> Pattern:
+    """A RBRT_PATTERN_CHECKER: albedo2 in the odd cells, cells of edge `size` counted from `origin`."""
+    return Pattern(PATTERN_CHECKER, _f3(albedo2), _f3(origin), float(size))
+
+
 class Camera(C.Structure):
     _fields_ = [
         ("position", C.c_float * 3),
@@ -298,6 +316,10 @@ HIP_SYMBOLS = {
     "rbrt_hip_scene_info": (C.c_int, [C.c_void_p, C.POINTER(SceneInfo)]),
     "rbrt_hip_supported_flags": (C.c_uint32, []),
     "rbrt_hip_scene_create_shaded": (C.c_int, [C.POINTER(Scene), C.POINTER(SceneShading), C.c_int, C.POINTER(C.c_void_p)]),
+    "rbrt_hip_scene_create_patterned": (C.c_int, [C.POINTER(Scene), C.POINTER(SceneShading), C.POINTER(ScenePatterns), C.c_int,
+                                                  C.POINTER(C.c_void_p)]),
+    "rbrt_hip_render_patterned": (C.c_int, [C.POINTER(Camera), C.POINTER(Scene), C.POINTER(SceneShading), C.POINTER(ScenePatterns),
+                                            C.POINTER(RenderOpts), f32p, u8p]),
     "rbrt_hip_render_shaded": (C.c_int, [C.POINTER(Camera), C.POINTER(Scene), C.POINTER(SceneShading), C.POINTER(RenderOpts),
                                          f32p, u8p]),
     "rbrt_hip_render_adaptive": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderOpts), C.POINTER(AdaptiveOpts), C.c_void_p,
@@ -376,6 +398,7 @@ DEBUG_SYMBOLS = {
     "rbrt_hip_last_render_times": (C.c_int, [C.POINTER(CallTimes)]),
     "rbrt_hip_scene_refine_wait": (C.c_int, [C.c_void_p, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     "rbrt_hip_debug_shading_normals": (C.c_int, [C.c_void_p, f32p, C.c_size_t, C.c_float, C.c_float, f32p]),
+    "rbrt_hip_debug_surface_albedo": (C.c_int, [C.c_void_p, f32p, C.c_size_t, C.c_float, C.c_float, f32p]),
     "rbrt_hip_scene_adaptive_rounds": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32)]),
     "rbrt_hip_debug_environment": (C.c_int, [C.c_void_p, f32p, C.c_size_t, f32p]),
     "rbrt_hip_scene_set_short_paths": (C.c_int, [C.c_void_p, C.c_int]),
@@ -461,9 +484,10 @@ def fptr(a: np.ndarray):
 class SceneData:
     """Owns the numpy arrays and ctypes arrays a `Scene` struct points into."""
 
-    def __init__(self, spheres=(), meshes=(), triangles=(), element_order=None):
+    def __init__(self, spheres=(), meshes=(), triangles=(), element_order=None, patterns=None):
         # spheres: iterable of (center, radius, Material); meshes: iterable of MeshData; triangles: iterable of
-        # (corners (3,3), Material); element_order: None or entries as in rbrt_scene_t.element_order
+        # (corners (3,3), Material); element_order: None or entries as in rbrt_scene_t.element_order;
+        # patterns: None or {object id: Pattern} (rbrt_scene_t's numbering: elements in their order, then meshes)
         self.spheres = list(spheres)
         self.meshes = list(meshes)
         self.triangles = list(triangles)
@@ -490,6 +514,13 @@ class SceneData:
                 self._nrm[i] = md.normals_struct
         self.shading = (SceneShading(len(self.meshes), 0, self._nrm)
                         if any(md.normals is not None for md in self.meshes) else None)
+        # solid patterns: an rbrt_scene_patterns_t only when some object carries one
+        self.pattern_of = dict(patterns or {})
+        n_obj = len(self.spheres) + len(self.triangles) + len(self.meshes)
+        self._pat = (Pattern * max(1, n_obj))()
+        for k, p in self.pattern_of.items():
+            self._pat[int(k)] = p
+        self.patterns = ScenePatterns(n_obj, 0, self._pat) if self.pattern_of else None
 
     def ptr(self):
         return C.byref(self.struct)
@@ -497,6 +528,10 @@ class SceneData:
     def shading_ptr(self):
         """The rbrt_scene_shading_t* of the *_shaded entry points, or None when every mesh is flat."""
         return None if self.shading is None else C.byref(self.shading)
+
+    def patterns_ptr(self):
+        """The rbrt_scene_patterns_t* of the *_patterned entry points, or None when no object carries a pattern."""
+        return None if self.patterns is None else C.byref(self.patterns)
 
 
 class MeshData:
@@ -583,6 +618,8 @@ def load_host() -> C.CDLL:
     lib.rbrt_host_scene_scene.argtypes = [C.c_void_p]
     lib.rbrt_host_scene_shading.restype = C.POINTER(SceneShading)
     lib.rbrt_host_scene_shading.argtypes = [C.c_void_p]
+    lib.rbrt_host_scene_patterns.restype = C.POINTER(ScenePatterns)
+    lib.rbrt_host_scene_patterns.argtypes = [C.c_void_p]
     lib.rbrt_host_scene_environment.restype = f32p
     lib.rbrt_host_scene_environment.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     lib.rbrt_host_read_pfm.restype = C.c_int
@@ -646,12 +683,17 @@ class HostScene:
         self.struct = self._lib.rbrt_host_scene_scene(self._h).contents
         sp = self._lib.rbrt_host_scene_shading(self._h)  # NULL unless some mesh is smooth
         self.shading = sp.contents if sp else None
+        pp = self._lib.rbrt_host_scene_patterns(self._h)  # NULL unless some object carries a checker
+        self.patterns = pp.contents if pp else None
 
     def ptr(self):
         return C.byref(self.struct)
 
     def shading_ptr(self):
         return None if self.shading is None else C.byref(self.shading)
+
+    def patterns_ptr(self):
+        return None if self.patterns is None else C.byref(self.patterns)
 
     def environment(self):
         """The nodes the host made of the scene's environment_blueprint (rbrt_host_scene_environment): float32

@@ -28,7 +28,7 @@ hipError_t launch_trace_helper(const TraceParams& P, uint32_t n_waves, hipStream
 size_t megakernel_gseq_bytes(uint32_t n_waves);
 size_t megakernel_gstack_bytes(uint32_t n_waves);
 size_t megakernel_lds_bytes(uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris, uint32_t thin_lens,
-                            uint32_t environment);
+                            uint32_t environment, uint32_t pattern_dw);
 int megakernel_occupancy_per_cu(size_t lds_bytes);
 hipError_t launch_primary_cull(const TraceParams& P, hipStream_t stream);
 hipError_t launch_sky_resolve(const TraceParams& P, const ResolveParams& R, hipStream_t stream);
@@ -53,6 +53,7 @@ hipError_t launch_unpack(const float* gathered, uint32_t width, uint32_t height,
 hipError_t launch_trace_rays(const TraceParams& P, const float* rays, size_t n, float* out_t, int32_t* out_obj,
                              int32_t* out_tri, float* out_dist, hipStream_t stream);
 hipError_t launch_shading_normals(const TraceParams& P, const float* rays, size_t n, float* out_normal, hipStream_t stream);
+hipError_t launch_surface_albedo(const TraceParams& P, const float* rays, size_t n, float* out_albedo, hipStream_t stream);
 hipError_t launch_environment_lookup(const EnvTexel* nodes, uint32_t n_env, const float* dirs, size_t n, float* out_rgb, hipStream_t stream);
 hipError_t launch_features(const TraceParams& P, const FeatureParams& F, hipStream_t stream);  // features.inl
 hipError_t launch_gate_selftest(const float* d_box, const float* d_rays, size_t n, uint8_t* d_fast, uint8_t* d_exact);
@@ -238,6 +239,7 @@ constexpr uint32_t kStripesAuto = 0xFFFFFFFFu;  // rbrt_hip_scene::work_stripes_
 struct rbrt_hip_scene {
     int device = 0;
     uint32_t n_spheres = 0, n_meshes = 0, n_elem_tris = 0;
+    uint32_t n_patterns = 0;  // patterned objects: second entries behind the materials (device_types.h DevPattern)
     std::vector<void*> allocs;  // everything hipMalloc'ed for the scene itself
     char* slab_cur = nullptr;   // dev_alloc: the scene's arrays below kSlabMaxPiece are cut from slabs (a hipMalloc / hipFree
     size_t slab_left = 0;       // pair costs 0.1-0.15 ms whatever its size: eleven of them were a tenth of a one-shot call)
@@ -971,6 +973,7 @@ int fill_trace_params(const rbrt_hip_scene* s, const rbrt_camera_t* cam, const r
     P.n_spheres = s->n_spheres;
     P.n_meshes = s->n_meshes;
     P.n_elem_tris = s->n_elem_tris;
+    P.pattern_dw = pattern_table_dwords(s->n_patterns);
     P.spheres = s->d_spheres;
     P.elem_tris = s->d_elem_tris;
     P.elems = s->d_elems;
@@ -1043,8 +1046,8 @@ bool device_builder_is_cheaper(uint32_t n_total, const CreateHint& hint) {
     return n_total >= 8u && device_s < host_s;
 }
 
-int scene_create_impl(const rbrt_scene_t* scene, const rbrt_scene_shading_t* shading, int device, rbrt_hip_scene_t** out,
-                      const CreateHint& hint);
+int scene_create_impl(const rbrt_scene_t* scene, const rbrt_scene_shading_t* shading, const rbrt_scene_patterns_t* patterns, int device,
+                      rbrt_hip_scene_t** out, const CreateHint& hint);
 
 }  // namespace
 
@@ -1096,11 +1099,16 @@ uint32_t rbrt_hip_tile_number(uint32_t tile_row, uint32_t tile_col, uint32_t til
 }
 
 int rbrt_hip_scene_create(const rbrt_scene_t* scene, int device, rbrt_hip_scene_t** out) {
-    return scene_create_impl(scene, nullptr, device, out, CreateHint());
+    return rbrt_hip_scene_create_shaded(scene, nullptr, device, out);
 }
 
 int rbrt_hip_scene_create_shaded(const rbrt_scene_t* scene, const rbrt_scene_shading_t* shading, int device, rbrt_hip_scene_t** out) {
-    return scene_create_impl(scene, shading, device, out, CreateHint());
+    return rbrt_hip_scene_create_patterned(scene, shading, nullptr, device, out);
+}
+
+int rbrt_hip_scene_create_patterned(const rbrt_scene_t* scene, const rbrt_scene_shading_t* shading, const rbrt_scene_patterns_t* patterns,
+                                    int device, rbrt_hip_scene_t** out) {
+    return scene_create_impl(scene, shading, patterns, device, out, CreateHint());
 }
 
 }  // extern "C"
@@ -1125,6 +1133,42 @@ int check_shading(const rbrt_scene_t& scene, const rbrt_scene_shading_t* sh) {
                 if (!std::isfinite(p[k]))
                     return fail(RBRT_ERR_INVALID_ARG, "shading: mesh " + std::to_string(i) + " has a non-finite corner normal at entry " + std::to_string(k));
     }
+    return RBRT_OK;
+}
+
+// The material of object `id` (rbrt_scene_t's numbering: the elements in their order, then the meshes).
+const rbrt_material_t& object_material(const rbrt_scene_t& scene, const std::vector<uint32_t>& elems, uint32_t id) {
+    if (id >= elems.size()) return scene.meshes[id - elems.size()].mat;
+    return (elems[id] >> 31) ? scene.triangles[elems[id] & 0x7FFFFFFFu].mat : scene.spheres[elems[id]].mat;
+}
+bool object_is_patterned(const rbrt_scene_patterns_t* pt, uint32_t id) { return pt && pt->objects && pt->objects[id].kind != RBRT_PATTERN_NONE; }
+
+// The solid patterns (rbrt_hip.h rbrt_scene_patterns_t): found wrong without a device, like everything in check_scene.
+int check_patterns(const rbrt_scene_t& scene, const std::vector<uint32_t>& elems, const rbrt_scene_patterns_t* pt) {
+    if (!pt) return RBRT_OK;
+    const uint64_t n_obj = uint64_t(elems.size()) + scene.n_meshes;
+    if (pt->n_objects != n_obj) return fail(RBRT_ERR_INVALID_ARG, "patterns: n_objects differs from the scene's spheres + triangles + meshes");
+    if (pt->reserved != 0) return fail(RBRT_ERR_INVALID_ARG, "patterns: reserved must be 0");
+    if (!pt->objects) return RBRT_OK;
+    uint64_t n_pat = 0;
+    for (uint32_t id = 0; id < pt->n_objects; ++id) {
+        const rbrt_pattern_t& p = pt->objects[id];
+        const std::string who = "patterns: object " + std::to_string(id);
+        if (p.kind == RBRT_PATTERN_NONE) continue;
+        if (p.kind != RBRT_PATTERN_CHECKER) return fail(RBRT_ERR_INVALID_ARG, who + " has an unknown pattern kind " + std::to_string(p.kind));
+        if (object_material(scene, elems, id).kind != RBRT_MAT_LAMBERTIAN)
+            return fail(RBRT_ERR_INVALID_ARG, who + " carries a checker but its material is not lambertian");
+        if (!std::isfinite(p.size) || !(p.size > 0.0f) || !std::isfinite(1.0f / p.size))
+            return fail(RBRT_ERR_INVALID_ARG, who + ": size must be finite and > 0, and so must 1 / size");
+        for (int c = 0; c < 3; ++c) {
+            if (!std::isfinite(p.origin[c])) return fail(RBRT_ERR_INVALID_ARG, who + ": origin is not finite");
+            if (!std::isfinite(p.albedo2[c]) || p.albedo2[c] < 0.0f) return fail(RBRT_ERR_INVALID_ARG, who + ": albedo2 must be finite and >= 0");
+        }
+        ++n_pat;
+    }
+    // A bounce records one byte: object ids 0..n_obj-1, then one further value per patterned object (the fold's entry number).
+    if (n_obj + n_pat > uint64_t(kMaxMaterialEntries))
+        return fail(RBRT_ERR_UNSUPPORTED, "more than 256 objects and patterned objects together (spheres + triangles + meshes + patterns) in one scene");
     return RBRT_OK;
 }
 
@@ -1159,7 +1203,7 @@ std::vector<Normal4> smooth_normals_blob(const rbrt_mesh_t& m, const rbrt_mesh_n
 using SceneGuard = std::unique_ptr<rbrt_hip_scene, int (*)(rbrt_hip_scene_t*)>;
 
 // Everything that is wrong with the caller's arrays, found without a device. elems: Scene::elements order.
-int check_scene(const rbrt_scene_t* scene, const rbrt_scene_shading_t* shading, std::vector<uint32_t>& elems) {
+int check_scene(const rbrt_scene_t* scene, const rbrt_scene_shading_t* shading, const rbrt_scene_patterns_t* patterns, std::vector<uint32_t>& elems) {
     if (scene->n_spheres && !scene->spheres) return fail(RBRT_ERR_INVALID_ARG, "spheres is null");
     if (scene->n_meshes && !scene->meshes) return fail(RBRT_ERR_INVALID_ARG, "meshes is null");
     if (scene->n_triangles && !scene->triangles) return fail(RBRT_ERR_INVALID_ARG, "triangles is null");
@@ -1194,7 +1238,8 @@ int check_scene(const rbrt_scene_t* scene, const rbrt_scene_shading_t* shading, 
                           !m.e2z || !m.nx || !m.ny || !m.nz || !m.is_padding))
             return fail(RBRT_ERR_INVALID_ARG, "mesh array pointer is null");
     }
-    return check_shading(*scene, shading);
+    if (int rc = check_shading(*scene, shading)) return rc;
+    return check_patterns(*scene, elems, patterns);
 }
 
 // The objects' bounds, by object id (rbrt_hip_scene::h_bounds).
@@ -1226,9 +1271,10 @@ DevMaterial dev_material_of(const rbrt_material_t& m) {
 struct ElementTables {
     std::vector<DevSphere> spheres;
     std::vector<DevTriangle> etris;
-    std::vector<DevMaterial> mats;  // [object id]: elements in their order, then meshes
+    std::vector<DevMaterial> mats;  // [object id]: elements in their order, then meshes; then the patterned objects' second entries
+    std::vector<DevPattern> patterns;  // one per second entry, in their order: uploaded right behind mats
 };
-ElementTables element_tables(const rbrt_scene_t& scene, const std::vector<uint32_t>& elems) {
+ElementTables element_tables(const rbrt_scene_t& scene, const std::vector<uint32_t>& elems, const rbrt_scene_patterns_t* pt) {
     ElementTables t;
     t.spheres.resize(scene.n_spheres), t.etris.resize(scene.n_triangles), t.mats.resize(elems.size() + scene.n_meshes);
     // A scene WITHOUT triangle elements is tested by the kernels' sphere-only loop, where element e IS device sphere e (no
@@ -1251,6 +1297,27 @@ ElementTables element_tables(const rbrt_scene_t& scene, const std::vector<uint32
     for (size_t e = 0; e < elems.size(); ++e)
         t.mats[e] = dev_material_of((elems[e] >> 31) ? scene.triangles[elems[e] & 0x7FFFFFFFu].mat : scene.spheres[elems[e]].mat);
     for (uint32_t i = 0; i < scene.n_meshes; ++i) t.mats[elems.size() + i] = dev_material_of(scene.meshes[i].mat);
+    // Solid patterns (device_types.h DevPattern): a lambertian's param word becomes its link, 0 without a pattern.
+    const uint32_t n_obj = uint32_t(t.mats.size());
+    uint32_t n_pat = 0;
+    for (uint32_t id = 0; id < n_obj; ++id) n_pat += object_is_patterned(pt, id) ? 1u : 0u;
+    for (uint32_t id = 0, k = 0; id < n_obj; ++id) {
+        if (t.mats[id].kind != RBRT_MAT_LAMBERTIAN) continue;
+        uint32_t link = 0;
+        if (object_is_patterned(pt, id)) {
+            const rbrt_pattern_t& p = pt->objects[id];
+            DevMaterial second = t.mats[id];
+            DevPattern rec;
+            for (int c = 0; c < 3; ++c) second.albedo[c] = p.albedo2[c], rec.origin[c] = p.origin[c];
+            second.param = 0.0f;
+            rec.inv = 1.0f / p.size;
+            const uint32_t rec_dw = uint32_t(((n_obj + n_pat) * sizeof(DevMaterial) + k * sizeof(DevPattern)) / 4);
+            link = (rec_dw << kPatternLinkShift) | (n_obj + k);
+            t.mats.push_back(second), t.patterns.push_back(rec);
+            ++k;
+        }
+        std::memcpy(&t.mats[id].param, &link, sizeof(link));
+    }
     return t;
 }
 
@@ -1376,7 +1443,16 @@ int upload_scene_tables(rbrt_hip_scene* s, const ElementTables& t, const std::ve
         if (int rc = upload(s, t.etris, &s->d_elem_tris)) return rc;
         if (int rc = upload(s, elems, &s->d_elems)) return rc;
     }
-    if (int rc = upload(s, t.mats, &s->d_materials)) return rc;
+    {   // the materials and, in the same allocation, the DevPatterns behind them
+        static_assert(sizeof(DevMaterial) % 4 == 0 && sizeof(DevPattern) % 4 == 0, "the table is staged as dwords");
+        std::vector<uint32_t> words((t.mats.size() * sizeof(DevMaterial) + t.patterns.size() * sizeof(DevPattern)) / 4);
+        if (!t.mats.empty()) std::memcpy(words.data(), t.mats.data(), t.mats.size() * sizeof(DevMaterial));
+        if (!t.patterns.empty())
+            std::memcpy(words.data() + t.mats.size() * sizeof(DevMaterial) / 4, t.patterns.data(), t.patterns.size() * sizeof(DevPattern));
+        uint32_t* d_words = nullptr;
+        if (int rc = upload(s, words, &d_words)) return rc;
+        s->d_materials = reinterpret_cast<DevMaterial*>(d_words);
+    }
     if (int rc = upload(s, meshes, &s->d_meshes)) return rc;
     return upload(s, std::vector<DevCounters>(1), &s->d_counters);  // (value-initialised: all zero)
 }
@@ -1418,7 +1494,7 @@ int size_grid(rbrt_hip_scene* s, int device, uint32_t waves_per_cu) {
     if (s->stack_entries > s->stack_need) s->stack_entries = s->stack_need;
     // resident waves per CU: LDS-limited (160 KiB per CU), at most 5 per SIMD (VGPR budget). (A thin-lens launch stages 32
     // bytes more; where that costs it a wave per CU the waves of the grid beyond the resident ones start as others end.)
-    int per_cu = int((160u * 1024u) / megakernel_lds_bytes(s->stack_entries, s->n_spheres, s->n_meshes, s->n_elem_tris, 0u, 0u));
+    int per_cu = int((160u * 1024u) / megakernel_lds_bytes(s->stack_entries, s->n_spheres, s->n_meshes, s->n_elem_tris, 0u, 0u, pattern_table_dwords(s->n_patterns)));
     if (per_cu > 20) per_cu = 20;
     if (per_cu < 1) per_cu = 1;
     if (waves_per_cu != 0) per_cu = int(waves_per_cu), s->waves_fixed = true;
@@ -1458,12 +1534,12 @@ void start_refine(rbrt_hip_scene* s, int device, uint64_t tri_total, const std::
     }
 }
 
-int scene_create_impl(const rbrt_scene_t* scene, const rbrt_scene_shading_t* shading, int device, rbrt_hip_scene_t** out,
-                      const CreateHint& hint) {
+int scene_create_impl(const rbrt_scene_t* scene, const rbrt_scene_shading_t* shading, const rbrt_scene_patterns_t* patterns, int device,
+                      rbrt_hip_scene_t** out, const CreateHint& hint) {
     if (!scene || !out) return fail(RBRT_ERR_INVALID_ARG, "scene_create: null argument");
     *out = nullptr;
     std::vector<uint32_t> elems;
-    if (int rc = check_scene(scene, shading, elems)) return rc;
+    if (int rc = check_scene(scene, shading, patterns, elems)) return rc;
     const double t_create0 = now_s();
     if (int rc = ensure_device(device)) return rc;
 
@@ -1473,7 +1549,8 @@ int scene_create_impl(const rbrt_scene_t* scene, const rbrt_scene_shading_t* sha
     s->create_times.hip_init_s = now_s() - t_create0;
     s->n_spheres = scene->n_spheres, s->n_meshes = scene->n_meshes, s->n_elem_tris = scene->n_triangles;
     s->h_bounds = object_bounds(*scene);
-    const ElementTables tables = element_tables(*scene, elems);
+    const ElementTables tables = element_tables(*scene, elems, patterns);
+    s->n_patterns = uint32_t(tables.patterns.size());
     std::vector<uint32_t> tri_base;
     uint64_t tri_total = 0;
     if (int rc = alloc_records(s.get(), *scene, tri_base, tri_total)) return rc;
@@ -2917,7 +2994,7 @@ int rbrt_hip_scene_info(rbrt_hip_scene_t* s, rbrt_hip_scene_info_t* out) {
     out->bvh_stack_need = s->stack_need;
     out->n_nodes = s->total_nodes, out->n_triangles = s->total_tris;
     out->trace_waves = s->n_waves;
-    out->lds_bytes_per_wave = uint32_t(megakernel_lds_bytes(s->stack_entries, s->n_spheres, s->n_meshes, s->n_elem_tris, 0u, 0u));
+    out->lds_bytes_per_wave = uint32_t(megakernel_lds_bytes(s->stack_entries, s->n_spheres, s->n_meshes, s->n_elem_tris, 0u, 0u, pattern_table_dwords(s->n_patterns)));
     (void)hipSetDevice(s->device);
     out->occupancy_api_waves_per_cu = uint32_t(megakernel_occupancy_per_cu(out->lds_bytes_per_wave));
     out->n_cus = s->n_cus;
@@ -2955,6 +3032,11 @@ int rbrt_hip_render(const rbrt_camera_t* cam, const rbrt_scene_t* scene, const r
 
 int rbrt_hip_render_shaded(const rbrt_camera_t* cam, const rbrt_scene_t* scene, const rbrt_scene_shading_t* shading,
                            const rbrt_render_opts_t* opts, float* out_radiance, uint8_t* out_rgb8) {
+    return rbrt_hip_render_patterned(cam, scene, shading, nullptr, opts, out_radiance, out_rgb8);
+}
+
+int rbrt_hip_render_patterned(const rbrt_camera_t* cam, const rbrt_scene_t* scene, const rbrt_scene_shading_t* shading,
+                              const rbrt_scene_patterns_t* patterns, const rbrt_render_opts_t* opts, float* out_radiance, uint8_t* out_rgb8) {
     if (!cam || !scene || !opts) return fail(RBRT_ERR_INVALID_ARG, "render: null argument");
     if (int rc = lens_invalid(cam, opts)) return rc;
     const double t_call0 = now_s();
@@ -2970,7 +3052,7 @@ int rbrt_hip_render_shaded(const rbrt_camera_t* cam, const rbrt_scene_t* scene, 
         const uint32_t w1 = opts->tile_world ? opts->tile_world : 1;
         hint.render_s_est = double(cam->img_width_pix) * cam->img_height_pix * opts->spp / w1 / 10.0e9;
     }
-    if (int rc = scene_create_impl(scene, shading, 0, &s, hint)) return rc;
+    if (int rc = scene_create_impl(scene, shading, patterns, 0, &s, hint)) return rc;
     SceneGuard guard(s, rbrt_hip_scene_destroy);  // (the images are the scene's memory: dev_alloc)
     times = s->create_times;
     if (s->pipeline == 0) s->pipeline = 3;  // (the batches of this one render overlap on three lanes)
@@ -3266,6 +3348,25 @@ int rbrt_hip_debug_shading_normals(rbrt_hip_scene_t* s, const float* rays, size_
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) e = d_out.to_host(out_normal, n * 3);
     return hook_result(e, "debug_shading_normals");
+}
+
+int rbrt_hip_debug_surface_albedo(rbrt_hip_scene_t* s, const float* rays, size_t n, float min_dist, float max_dist, float* out_albedo) {
+    if (!s || (n && (!rays || !out_albedo))) return fail(RBRT_ERR_INVALID_ARG, "debug_surface_albedo: null argument");
+    if (n == 0) return RBRT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    rbrt_render_opts_t o;
+    rbrt_render_opts_default(&o);
+    o.min_dist = min_dist;
+    o.max_dist = max_dist;
+    TraceParams P;
+    fill_trace_params(s, nullptr, &o, P);
+    DevBuf<float> d_rays, d_out;
+    hipError_t e = d_rays.upload(rays, n * 6);
+    if (e == hipSuccess) e = d_out.alloc(n * 3);
+    if (e == hipSuccess) e = launch_surface_albedo(P, d_rays.get(), n, d_out.get(), nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = d_out.to_host(out_albedo, n * 3);
+    return hook_result(e, "debug_surface_albedo");
 }
 
 int rbrt_hip_debug_environment(rbrt_hip_scene_t* s, const float* dirs, size_t n, float* out_rgb) {

@@ -99,13 +99,31 @@ struct DevTriangle {
 
 struct DevMaterial {
     float albedo[3];
-    float param;
+    float param;   // a lambertian's: the bits of its pattern link (DevPattern below), 0 without a pattern
     int32_t kind;  // rbrt_material_kind_t, except that an emitter is stored as kDevMatEmissive
 };
 // Device code of RBRT_MAT_EMISSIVE. The megakernel's classify() turns a hit into status ST_LAMB + kind, and ST_LAMB - 1 is
 // ST_TERM: an emitter's hit ends its path without a compare in the kernel (the TERM pass then starts the fold from L).
 constexpr int32_t kDevMatEmissive = -1;
 RBRT_HOST_DEVICE inline int32_t dev_material_kind(int32_t kind) { return kind == RBRT_MAT_EMISSIVE ? kDevMatEmissive : kind; }
+
+// Solid patterns (rbrt_hip.h rbrt_scene_patterns_t). A scene with n_pat patterned objects has a material table of
+// n_obj + n_pat entries, the k-th patterned object's albedo2 in entry n_obj + k, and n_pat DevPatterns right behind the table,
+// in the same allocation: everything a kernel stages or reads as "the materials". A lambertian never reads its param, so
+// the DEVICE copy of that word is the object's link: 0 for every unpatterned lambertian, whatever the caller passed, else
+// (dword offset of its DevPattern from the table's start << kPatternLinkShift) | its second entry's number. A scatter
+// records the entry's number where it recorded the object id (one byte per bounce), and the fold looks it up as it did.
+struct DevPattern {
+    float origin[3];
+    float inv;  // 1.0f / size
+};
+constexpr uint32_t kPatternLinkShift = 8;
+// dwords a scene's patterns add behind the n_obj materials: the second entries, then the DevPatterns
+RBRT_HOST_DEVICE inline uint32_t pattern_table_dwords(uint32_t n_pat) {
+    return n_pat * uint32_t((sizeof(DevMaterial) + sizeof(DevPattern)) / 4);
+}
+// Entry numbers are record bytes (<= 255); object ids also pass through pack_meta's 8-bit field as id + 1 (<= 254).
+constexpr int kMaxMaterialEntries = 256;  // objects + patterned objects
 
 struct DevMesh {
     const BvhNode4* nodes;
@@ -208,6 +226,8 @@ struct TraceParams {
     // sample is in sample_buf already, or its pixel lies beyond a ragged edge -- and the trace kernel hands it to nobody.
     // The stage writes every word of the launch: zero for the chunks of tiles it does not work on.
     unsigned long long* short_masks;
+    // Solid patterns: the dwords behind the n_obj materials that belong to the table (pattern_table_dwords; 0: no patterns)
+    uint32_t pattern_dw;
 };
 
 struct ResolveParams {

@@ -42,6 +42,10 @@ __global__ __launch_bounds__(kFeatureBlock) void features_kernel(const TracePara
         if (h.obj >= 0) {
             const DevMaterial m = P.materials[h.obj];
             sa = m.kind == RBRT_MAT_DIELECTRIC ? mk(1.0f, 1.0f, 1.0f) : mk(m.albedo);  // dielectric.rs:18: its attenuation
+            if (m.kind == RBRT_MAT_LAMBERTIAN && __float_as_uint(m.param) != 0u) {  // a patterned object: the cell's colour
+                const uint32_t* mat = reinterpret_cast<const uint32_t*>(P.materials);
+                sa = mk(P.materials[surface_entry(mat, uint32_t(h.obj), __float_as_uint(m.param), o + h.t * d)].albedo);
+            }
             V3 g;
             if (uint32_t(h.obj) < n_elem) {
                 const uint32_t desc = P.elems != nullptr ? P.elems[h.obj] : uint32_t(h.obj);

@@ -596,6 +596,28 @@ __device__ __forceinline__ V3 mesh_shading_normal(const Normal4* normals, uint32
 }
 
 // ---------------------------------------------------------------------------------------------
+// Solid patterns (rbrt_hip.h rbrt_scene_patterns_t; device_types.h DevPattern)
+// ---------------------------------------------------------------------------------------------
+// Which entry of the material table a hit of object `obj` at p records: the object's own, or -- a patterned lambertian
+// whose hit lies in an odd cell -- its second entry. `mat`: the table as dwords (in LDS or where the host put it); `link`:
+// the object's pattern link (DevMaterial::param of a lambertian: 0 = no pattern, the one compare an unpatterned hit pays).
+__device__ __forceinline__ int32_t checker_cell(float t) {
+    const float u = __builtin_fminf(__builtin_fmaxf(t, -1e9f), 1e9f);  // (a NaN counts as -1e9)
+    return int32_t(__builtin_floorf(u));
+}
+__device__ __forceinline__ uint32_t surface_entry(const uint32_t* mat, uint32_t obj, uint32_t link, V3 p) {
+    if (link == 0u) return obj;
+    const float* r = reinterpret_cast<const float*>(mat + (link >> kPatternLinkShift));  // DevPattern: origin, inv
+    const float inv = r[3];
+    const int32_t kx = checker_cell((p.x - r[0]) * inv), ky = checker_cell((p.y - r[1]) * inv), kz = checker_cell((p.z - r[2]) * inv);
+    return ((kx ^ ky ^ kz) & 1) ? (link & 255u) : obj;
+}
+// The link of any object: only a lambertian's param word is one (a metal's is its roughness, a dielectric's its index).
+__device__ __forceinline__ uint32_t surface_link(const uint32_t* mat, uint32_t obj) {
+    return int32_t(mat[obj * 5u + 4u]) == RBRT_MAT_LAMBERTIAN ? mat[obj * 5u + 3u] : 0u;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Materials
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ V3 random_point_in_unit_sphere(Rng& rng) {  // materials.rs:14-30
@@ -779,7 +801,7 @@ __device__ __noinline__ V3 environment_radiance_call(const EnvTexel* nodes, uint
 constexpr uint32_t kEnvDw = 4;  // words staged in the megakernel's LDS for a launch with a map: the address (2), n, pad
 
 __host__ __device__ inline uint32_t megakernel_lds_dwords(uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris,
-                                                          uint32_t thin_lens, uint32_t environment);
+                                                          uint32_t thin_lens, uint32_t environment, uint32_t pattern_dw);
 #include "megakernel.inl"
 
 // lib.rs:116-122: (sqrt(c) * 256) as u8 — Rust's float->int cast saturates and maps NaN to 0.
@@ -1629,6 +1651,33 @@ __global__ __launch_bounds__(kRaysBlock) void shading_normals_kernel(const Trace
     out[3 * i + 2] = nrm.z;
 }
 
+// The attenuation the scatter pass would record at the closest hit of arbitrary rays (test hook behind rbrt_hip_debug_surface_albedo).
+__global__ __launch_bounds__(kRaysBlock) void surface_albedo_kernel(const TraceParams P, const float* __restrict__ rays, size_t n,
+                                                                float* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    uint32_t* stack = lds + threadIdx.x;
+    const size_t i = size_t(blockIdx.x) * kRaysBlock + threadIdx.x;
+    if (i >= n) return;
+    const V3 o = mk(rays + 6 * i), d = mk(rays + 6 * i + 3);
+    HitRec h;
+    LocalCounters lc = {0, 0, 0, 0, 0};
+    scene_hit<false>(P, o, d, stack, uint32_t(kRaysBlock), h, lc);
+    const float nanv = __int_as_float(0x7fc00000);
+    V3 a = mk(nanv, nanv, nanv);
+    if (h.obj >= 0) {
+        const uint32_t* mat = reinterpret_cast<const uint32_t*>(P.materials);
+        if (int32_t(mat[uint32_t(h.obj) * 5u + 4u]) == RBRT_MAT_DIELECTRIC) {
+            a = mk(1.0f, 1.0f, 1.0f);  // dielectric.rs:18
+        } else {
+            const uint32_t ent = surface_entry(mat, uint32_t(h.obj), surface_link(mat, uint32_t(h.obj)), o + h.t * d);
+            a = mk(reinterpret_cast<const float*>(mat + ent * 5u));
+        }
+    }
+    out[3 * i + 0] = a.x;
+    out[3 * i + 1] = a.y;
+    out[3 * i + 2] = a.z;
+}
+
 // The environment lookup alone, for arbitrary directions (test hook behind rbrt_hip_debug_environment).
 __global__ __launch_bounds__(kRaysBlock) void environment_lookup_kernel(const EnvTexel* __restrict__ nodes, uint32_t n_env,
                                                                     const float* __restrict__ dirs, size_t n, float* __restrict__ out) {
@@ -1778,9 +1827,10 @@ size_t megakernel_gseq_bytes(uint32_t n_waves) { return size_t(n_waves) * kPool 
 size_t megakernel_gstack_bytes(uint32_t n_waves) { return size_t(n_waves) * kStackMax * 64u * sizeof(uint32_t); }
 
 __host__ __device__ inline uint32_t megakernel_lds_dwords(uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris,
-                                                          uint32_t thin_lens, uint32_t environment) {
+                                                          uint32_t thin_lens, uint32_t environment, uint32_t pattern_dw) {
     const uint32_t n_elem = n_spheres + n_elem_tris;
     const uint32_t scene = n_spheres * kSphDw + (n_elem + n_meshes) * kMatDw + n_meshes * kMeshDw + kGenDw +
+                           pattern_dw +                                                // second entries and DevPatterns (nothing without patterns)
                            (thin_lens ? kLensDw : 0u) +                                // a lens launch's lens (nothing for a pinhole)
                            (environment ? kEnvDw : 0u) +                               // the map's address and size (nothing without one)
                            (n_elem_tris != 0u ? n_elem_tris * kTriDw + n_elem : 0u);  // triangle table + element order
@@ -1790,8 +1840,8 @@ __host__ __device__ inline uint32_t megakernel_lds_dwords(uint32_t stack_entries
     return dw;
 }
 size_t megakernel_lds_bytes(uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris, uint32_t thin_lens,
-                            uint32_t environment) {
-    return size_t(megakernel_lds_dwords(stack_entries, n_spheres, n_meshes, n_elem_tris, thin_lens, environment)) * sizeof(uint32_t);
+                            uint32_t environment, uint32_t pattern_dw) {
+    return size_t(megakernel_lds_dwords(stack_entries, n_spheres, n_meshes, n_elem_tris, thin_lens, environment, pattern_dw)) * sizeof(uint32_t);
 }
 
 // What the HIP runtime says fits: resident single-wave workgroups of the trace kernel per CU at this much LDS (0 on error).
@@ -1807,14 +1857,14 @@ int megakernel_occupancy_per_cu(size_t lds_bytes) {
 // (work counters, sample buffer, tables), scratch slots from P.wave_base on.
 hipError_t launch_trace_helper(const TraceParams& P, uint32_t n_waves, hipStream_t stream) {
     if (P.n_items == 0 || n_waves == 0 || !P.helper_words) return hipSuccess;
-    const size_t lds = megakernel_lds_bytes(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris, P.thin_lens, P.env_nodes ? 1u : 0u);
+    const size_t lds = megakernel_lds_bytes(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris, P.thin_lens, P.env_nodes ? 1u : 0u, P.pattern_dw);
     hipLaunchKernelGGL((trace_megakernel<false, true>), dim3(n_waves), dim3(64), lds, stream, P);
     return hipGetLastError();
 }
 
 hipError_t launch_trace_megakernel(const TraceParams& P, uint32_t n_waves, bool stats, hipStream_t stream) {
     if (P.n_items == 0 || n_waves == 0) return hipSuccess;
-    const size_t lds = megakernel_lds_bytes(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris, P.thin_lens, P.env_nodes ? 1u : 0u);
+    const size_t lds = megakernel_lds_bytes(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris, P.thin_lens, P.env_nodes ? 1u : 0u, P.pattern_dw);
     if (stats)
         hipLaunchKernelGGL((trace_megakernel<true>), dim3(n_waves), dim3(64), lds, stream, P);
     else
@@ -1908,6 +1958,13 @@ hipError_t launch_shading_normals(const TraceParams& P, const float* rays, size_
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(shading_normals_kernel, dim3(uint32_t((n + kRaysBlock - 1) / kRaysBlock)), dim3(kRaysBlock),
                        size_t(kStackMax) * kRaysBlock * sizeof(uint32_t), stream, P, rays, n, out_normal);
+    return hipGetLastError();
+}
+
+hipError_t launch_surface_albedo(const TraceParams& P, const float* rays, size_t n, float* out_albedo, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(surface_albedo_kernel, dim3(uint32_t((n + kRaysBlock - 1) / kRaysBlock)), dim3(kRaysBlock),
+                       size_t(kStackMax) * kRaysBlock * sizeof(uint32_t), stream, P, rays, n, out_albedo);
     return hipGetLastError();
 }
 

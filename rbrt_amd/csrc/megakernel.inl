@@ -265,7 +265,7 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
     // (the accumulators sit at the very end of the workgroup's LDS: megakernel_lds_bytes adds room for them)
     // (u32: a wave spends at most a few million cycles in a region per launch; 76 bytes fit the slack of the product's
     // allocation granule, so this build keeps the product's 16 workgroups per CU)
-    uint32_t* const rt_acc = lds + (megakernel_lds_dwords(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris, P.thin_lens, P.env_nodes ? 1u : 0u) - uint32_t(kNumRegions));
+    uint32_t* const rt_acc = lds + (megakernel_lds_dwords(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris, P.thin_lens, P.env_nodes ? 1u : 0u, P.pattern_dw) - uint32_t(kNumRegions));
     if (lane < uint32_t(kNumRegions)) rt_acc[lane] = 0u;
     unsigned long long rt_prev = __builtin_amdgcn_s_memtime();
     const unsigned long long rt_wall0 = __builtin_amdgcn_s_memrealtime();  // 100 MHz, the same clock on every CU
@@ -322,8 +322,9 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
         uint32_t* dst = sc_base;
         for (uint32_t i = lane; i < P.n_spheres * kSphDw; i += 64) dst[i] = gs[i];
         dst += P.n_spheres * kSphDw;
-        for (uint32_t i = lane; i < n_obj * kMatDw; i += 64) dst[i] = gm[i];
-        dst += n_obj * kMatDw;
+        // (with patterns: the second entries and the DevPatterns behind the objects' materials are part of the table)
+        for (uint32_t i = lane; i < n_obj * kMatDw + P.pattern_dw; i += 64) dst[i] = gm[i];
+        dst += n_obj * kMatDw + P.pattern_dw;
         for (uint32_t i = lane; i < P.n_meshes * kMeshDw; i += 64) dst[i] = gh[i];
         // what path generation reads (camera, work decomposition): kept in LDS rather than in ~30 SGPRs that the
         // rest of the kernel would have to spill around (the spill code is VALU: v_readlane / v_writelane)
@@ -369,11 +370,11 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
             dst[G_SEED_LO] = uint32_t(P.seed_key), dst[G_SEED_HI] = uint32_t(P.seed_key >> 32);
         }
     }
-    const uint32_t* const gp = sc_base + P.n_spheres * kSphDw + n_obj * kMatDw + P.n_meshes * kMeshDw;
+    const uint32_t* const gp = sc_base + P.n_spheres * kSphDw + n_obj * kMatDw + P.pattern_dw + P.n_meshes * kMeshDw;
     const float* const gpf = reinterpret_cast<const float*>(gp);
     const uint32_t* const gtri = gp + kGenDw;
     const SceneLds sc = {reinterpret_cast<const float*>(sc_base), sc_base + P.n_spheres * kSphDw,
-                         sc_base + P.n_spheres * kSphDw + n_obj * kMatDw, reinterpret_cast<const float*>(gtri),
+                         sc_base + P.n_spheres * kSphDw + n_obj * kMatDw + P.pattern_dw, reinterpret_cast<const float*>(gtri),
                          gtri + P.n_elem_tris * kTriDw};
     // work items are reserved from the global counter in chunks, the next chunk asynchronously
     WorkSource work;
@@ -1047,7 +1048,9 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                 }
                 if (ok) {
                     if (lk != ST_DIEL) {  // attenuation (1,1,1) is an exact identity, not recorded
-                        word |= uint32_t(s_obj) << (8u * (nrec & 3u));
+                        // the material entry the fold will look up: the object's, or a patterned lambertian's second one
+                        const uint32_t ent = lk == ST_LAMB ? surface_entry(sc.mat, uint32_t(s_obj), __float_as_uint(m.param), p) : uint32_t(s_obj);
+                        word |= ent << (8u * (nrec & 3u));
                         if ((nrec & 3u) == 3u) {
                             gseq[size_t(slot) * kSeqWords + (nrec >> 2)] = word;
                             word = 0;

@@ -115,7 +115,8 @@ __device__ __forceinline__ bool short_path_sample(const TraceParams& P, const Sc
             ok = true;
         }
         if (ok) {
-            if (next != ST_DIEL) rec = obj;
+            if (next != ST_DIEL)  // (the entry the trace kernel's scatter would record: a patterned lambertian's cell)
+                rec = next == ST_LAMB ? int32_t(surface_entry(sc.mat, uint32_t(obj), __float_as_uint(param), p)) : obj;
             o = p;
             d = nd;
             depth -= 1u;

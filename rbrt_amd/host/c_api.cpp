@@ -96,6 +96,8 @@ const rbrt_camera_lens_t* rbrt_host_scene_lens(const rbrt_host_scene* h) { retur
 const rbrt_scene_t* rbrt_host_scene_scene(const rbrt_host_scene* h) { return &h->view.scene; }
 // The corner normals of the smooth meshes (YAML `shading: smooth`), or NULL when every mesh is flat.
 const rbrt_scene_shading_t* rbrt_host_scene_shading(const rbrt_host_scene* h) { return h->view.shading_ptr(); }
+// The solid patterns of the scene's objects (YAML `checker_albedo` / `checker_size`), or NULL when no object carries one.
+const rbrt_scene_patterns_t* rbrt_host_scene_patterns(const rbrt_host_scene* h) { return h->view.patterns_ptr(); }
 // The nodes made of the scene's environment_blueprint: float[*n + 1][*n + 1][3], what rbrt_environment_t::nodes takes; NULL
 // (and *n = 0) when the scene has none. Valid until rbrt_host_scene_free.
 const float* rbrt_host_scene_environment(const rbrt_host_scene* h, uint32_t* n) {

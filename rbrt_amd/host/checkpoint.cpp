@@ -44,12 +44,29 @@ uint64_t shading_fingerprint(const rbrt_scene_t& sc, const rbrt_scene_shading_t*
     return h;
 }
 
+// ... and the solid patterns, only when there are any (an unpatterned scene's checkpoints keep their fingerprint).
+uint64_t patterns_fingerprint(const rbrt_scene_patterns_t* pt, uint64_t h) {
+    if (!pt || !pt->objects) return h;
+    bool any = false;
+    for (uint32_t i = 0; i < pt->n_objects; ++i) any = any || pt->objects[i].kind != RBRT_PATTERN_NONE;
+    if (!any) return h;
+    for (uint32_t i = 0; i < pt->n_objects; ++i) {
+        const rbrt_pattern_t& p = pt->objects[i];
+        h = fnv1a(&p.kind, sizeof(p.kind), h);
+        if (p.kind == RBRT_PATTERN_NONE) continue;
+        h = fnv1a(p.albedo2, sizeof(p.albedo2), h);
+        h = fnv1a(p.origin, sizeof(p.origin), h);
+        h = fnv1a(&p.size, sizeof(p.size), h);
+    }
+    return h;
+}
+
 }  // namespace
 
 uint64_t checkpoint_fingerprint(const std::string& path, const rbrt_camera_lens_t& lens, const rbrt_render_opts_t& opts, const rbrt_scene_t& sc,
-                                const rbrt_scene_shading_t* sh, const Environment& env) {
+                                const rbrt_scene_shading_t* sh, const Environment& env, const rbrt_scene_patterns_t* pt) {
     if (path.empty()) return 0;
-    uint64_t h = shading_fingerprint(sc, sh, scene_fingerprint(lens.cam, sc));
+    uint64_t h = patterns_fingerprint(pt, shading_fingerprint(sc, sh, scene_fingerprint(lens.cam, sc)));
     if (opts.flags & RBRT_FLAG_CONSTANT_BACKGROUND) {
         const uint32_t flags = opts.flags & ~RBRT_FLAG_THIN_LENS;  // (the word as it was hashed before there was a lens bit)
         h = fnv1a(&flags, sizeof(flags), h);

@@ -91,6 +91,15 @@ struct Material {
 std::optional<Material> create_material_from_description(const std::string& mat_type, std::optional<Vec3> albedo,
                                                          std::optional<float> material_param);
 
+// A solid checker (not in the reference; include/rbrt_hip.h rbrt_pattern_t): YAML `checker_albedo`, `checker_size` and
+// `checker_origin` on a sphere or mesh blueprint whose material is lambertian.
+struct Checker {
+    Vec3 albedo2;
+    float size = 0;
+    Vec3 origin;
+    rbrt_pattern_t to_abi() const;
+};
+
 // ---- blueprints.rs:15-48 -------------------------------------------------------------------------
 struct TriangleMeshBlueprint {
     std::string obj_filepath;
@@ -100,6 +109,7 @@ struct TriangleMeshBlueprint {
     std::optional<Vec3> albedo;
     std::optional<float> material_param;
     bool smooth = false;  // `shading: smooth` (not in the reference): shade with corner normals, rbrt_scene_shading_t
+    std::optional<Checker> checker;
 };
 struct SphereBlueprint {
     float radius = 0;
@@ -107,6 +117,7 @@ struct SphereBlueprint {
     std::string material_type;
     std::optional<Vec3> albedo;
     std::optional<float> material_param;
+    std::optional<Checker> checker;
 };
 struct CameraBluePrint {
     Vec3 camera_up, camera_look_at, camera_position;
@@ -138,6 +149,7 @@ struct Sphere {
     Vec3 center;
     float radius = 0;
     Material material;
+    std::optional<Checker> checker;  // lambertian only
 };
 
 // triangle.rs:9-34: a single triangle as a scene element (the reference's second Intersectable). The YAML factory
@@ -145,6 +157,7 @@ struct Sphere {
 struct BasicTriangle {
     std::array<Vec3, 3> corners;  // counter-clockwise
     Material material;
+    std::optional<Checker> checker;  // lambertian only
 };
 
 struct TriangleMesh {
@@ -157,6 +170,7 @@ struct TriangleMesh {
     Vec3 bbox_lower, bbox_upper;
     Material material;
     uint32_t num_triangles = 0;  // before padding
+    std::optional<Checker> checker;  // lambertian only
     // Smooth shading (not in the reference): corner_normals[k][c] = component c of corner k's normal of every SoA entry
     // (padding entries copy entry 0's, as the other arrays do); all empty = a flat mesh.
     std::vector<float> corner_normals[3][3];
@@ -235,6 +249,11 @@ struct Scene {
         bool any_smooth = false;
         // what rbrt_hip_scene_create_shaded gets: NULL when no mesh is smooth
         const rbrt_scene_shading_t* shading_ptr() const { return any_smooth ? &shading : nullptr; }
+        std::vector<rbrt_pattern_t> pattern_of;  // [object id]: the elements in their order, then the meshes
+        rbrt_scene_patterns_t patterns{};
+        bool any_pattern = false;
+        // what rbrt_hip_scene_create_patterned gets: NULL when no object carries a checker
+        const rbrt_scene_patterns_t* patterns_ptr() const { return any_pattern ? &patterns : nullptr; }
     };
     AbiView to_abi() const;
 };

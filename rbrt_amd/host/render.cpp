@@ -574,7 +574,7 @@ void Rank::run() {
 }
 
 void Rank::setup() {
-    err.lib_ok(rbrt_hip_scene_create_shaded(&job.view.scene, job.view.shading_ptr(), dev, &hs));
+    err.lib_ok(rbrt_hip_scene_create_patterned(&job.view.scene, job.view.shading_ptr(), job.view.patterns_ptr(), dev, &hs));
     std::memset(&sh.t_create[rank], 0, sizeof(sh.t_create[rank]));
     if (!hs) return;
     (void)rbrt_hip_scene_create_times(hs, &sh.t_create[rank]);
@@ -1094,7 +1094,7 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
                                 cam, scene, num_samples);
     Job job{cfg, plan, lens, view, scene.environment.n != 0u ? &env_abi : nullptr, render_opts_of(cfg, cam, num_samples), num_samples, {}, {}, img};
     job.want = checkpoint_header(img.width, img.height, num_samples, uint32_t(plan.world), cfg.seed,
-                                 checkpoint_fingerprint(cfg.checkpoint_path, lens, job.opts, view.scene, view.shading_ptr(), scene.environment));
+                                 checkpoint_fingerprint(cfg.checkpoint_path, lens, job.opts, view.scene, view.shading_ptr(), scene.environment, view.patterns_ptr()));
     job.resume = resume_from_checkpoint(job);
     Shared sh(plan);
     bring_up_rccl(plan, sh);

@@ -271,7 +271,47 @@ const std::vector<Node>& as_list(const Node& n, const char* what) {
     throw Error(std::string(what) + ": expected a sequence");
 }
 
+// The optional checker keys of a sphere or mesh blueprint `m` (not in the reference). The pair checker_albedo / checker_size
+// makes one; checker_origin defaults to 0. Whether the material can carry it is decided with the material
+// (create_scene_from_scene_blueprint).
+std::optional<Checker> opt_checker(const Node& m) {
+    const std::optional<Vec3> albedo = opt_vec3(m, "checker_albedo", "checker_albedo");
+    const std::optional<float> size = opt_f32(m, "checker_size", "checker_size");
+    const std::optional<Vec3> origin = opt_vec3(m, "checker_origin", "checker_origin");
+    if (albedo && !size) throw Error("checker_albedo needs checker_size (the edge of a cell, in world units)");
+    if (size && !albedo) throw Error("checker_size needs checker_albedo (the albedo of the odd cells)");
+    if (origin && !albedo) throw Error("checker_origin needs checker_albedo and checker_size");
+    if (!albedo) return std::nullopt;
+    if (!std::isfinite(*size) || !(*size > 0.0f) || !std::isfinite(1.0f / *size))
+        throw Error("checker_size must be a finite number > 0 whose reciprocal is finite");
+    for (const float c : {albedo->x, albedo->y, albedo->z})
+        if (!std::isfinite(c) || c < 0.0f) throw Error("checker_albedo must be finite and >= 0");
+    Checker ck;
+    ck.albedo2 = *albedo, ck.size = *size;
+    if (origin) {
+        for (const float c : {origin->x, origin->y, origin->z})
+            if (!std::isfinite(c)) throw Error("checker_origin must be finite");
+        ck.origin = *origin;
+    }
+    return ck;
+}
+
+// A checker goes on a lambertian object only: anything else keeps its one albedo (and a metal's param is its roughness).
+void need_lambertian_for_checker(const std::optional<Checker>& ck, const Material& mat, const std::string& material_type) {
+    if (ck && mat.abi.kind != RBRT_MAT_LAMBERTIAN)
+        throw Error("checker_albedo: a checker needs a lambertian material, not `" + material_type + "`");
+}
+
 }  // namespace
+
+rbrt_pattern_t Checker::to_abi() const {
+    rbrt_pattern_t p{};
+    p.kind = RBRT_PATTERN_CHECKER;
+    put3(p.albedo2, albedo2);
+    put3(p.origin, origin);
+    p.size = size;
+    return p;
+}
 
 SceneBlueprint load_blueprints_from_yaml_text(const std::string& text) {
     Node root;
@@ -313,6 +353,7 @@ SceneBlueprint load_blueprints_from_yaml_text(const std::string& text) {
             if (v != "flat" && v != "smooth") throw Error("shading: expected `flat` or `smooth`, got `" + v + "`");
             b.smooth = v == "smooth";
         }
+        b.checker = opt_checker(m);
         bp.mesh_blueprints.push_back(b);
     }
     for (const Node& s : as_list(need(root, "sphere_blueprints", "scene"), "sphere_blueprints")) {
@@ -322,6 +363,7 @@ SceneBlueprint load_blueprints_from_yaml_text(const std::string& text) {
         b.material_type = as_string(need(s, "material_type", "sphere blueprint"), "material_type");
         b.albedo = opt_vec3(s, "albedo", "albedo");
         b.material_param = opt_f32(s, "material_param", "material_param");
+        b.checker = opt_checker(s);
         bp.sphere_blueprints.push_back(b);
     }
     if (const Node* en = root.find("environment_blueprint"); en && !en->is_null()) {  // (not in the reference; absent = none)
@@ -665,6 +707,21 @@ Scene::AbiView Scene::to_abi() const {
         v.normals.push_back(m.to_abi_normals());
         v.any_smooth = v.any_smooth || m.smooth();
     }
+    {   // solid patterns, by object id: the elements in their order (element_order, else spheres then triangles), then the meshes
+        const size_t n_elem = elements.size() + basic_triangles.size();
+        for (size_t e = 0; e < n_elem; ++e) {
+            const uint32_t d = element_order.size() == n_elem ? element_order[e] : uint32_t(e < elements.size() ? e : (0x80000000u | (e - elements.size())));
+            const size_t idx = d & 0x7FFFFFFFu;
+            const std::optional<Checker>* ck = nullptr;
+            if ((d >> 31) && idx < basic_triangles.size()) ck = &basic_triangles[idx].checker;
+            if (!(d >> 31) && idx < elements.size()) ck = &elements[idx].checker;
+            v.pattern_of.push_back(ck && *ck ? (*ck)->to_abi() : rbrt_pattern_t{});
+        }
+        for (const TriangleMesh& m : triangle_meshes) v.pattern_of.push_back(m.checker ? m.checker->to_abi() : rbrt_pattern_t{});
+        for (const rbrt_pattern_t& p : v.pattern_of) v.any_pattern = v.any_pattern || p.kind != RBRT_PATTERN_NONE;
+        v.patterns.n_objects = uint32_t(v.pattern_of.size());
+        v.patterns.objects = v.pattern_of.data();
+    }
     v.shading.n_meshes = uint32_t(v.meshes.size());
     v.shading.meshes = v.normals.data();
     v.scene.n_spheres = uint32_t(v.spheres.size());
@@ -691,13 +748,16 @@ Scene create_scene_from_scene_blueprint(const SceneBlueprint& bp) {
             std::printf("Failed to parse material info provided with mesh!\n");
             continue;
         }
+        need_lambertian_for_checker(mb.checker, *mat, mb.material_type);
         scene.triangle_meshes.push_back(
             TriangleMesh::create(mb.obj_filepath, mb.translation, mb.rotation_rad, mb.scale, *mat, mb.smooth));
+        scene.triangle_meshes.back().checker = mb.checker;
     }
     for (const SphereBlueprint& sb : bp.sphere_blueprints) {
         auto mat = create_material_from_description(sb.material_type, sb.albedo, sb.material_param);
         if (!mat) continue;
-        scene.elements.push_back(Sphere{sb.center, sb.radius, *mat});
+        need_lambertian_for_checker(sb.checker, *mat, sb.material_type);
+        scene.elements.push_back(Sphere{sb.center, sb.radius, *mat, sb.checker});
     }
     return scene;
 }

@@ -20,16 +20,16 @@ BINDIR := rbrt_amd/bin
 
 all: $(LIBDIR)/librbrt_hip.so host oracle
 
-$(LIBDIR)/librbrt_hip.so: $(CSRC)/kernels.hip $(CSRC)/megakernel.inl $(CSRC)/features.inl $(CSRC)/short_paths.inl $(CSRC)/api.cpp $(CSRC)/bvh.cpp $(CSRC)/bvh.h \
+$(LIBDIR)/librbrt_hip.so: $(CSRC)/kernels.hip $(CSRC)/megakernel.inl $(CSRC)/features.inl $(CSRC)/short_paths.inl $(CSRC)/api.cpp $(CSRC)/api_common.h $(CSRC)/frame_stages.cpp $(CSRC)/selftests.cpp $(CSRC)/bvh.cpp $(CSRC)/bvh.h \
                           $(CSRC)/bvh_device.hip $(CSRC)/bvh_device.h $(CSRC)/denoise.hip $(CSRC)/tonemap.hip $(CSRC)/glare.hip $(CSRC)/guided.hip $(CSRC)/temporal.hip $(CSRC)/upsample.hip $(CSRC)/despike.hip $(CSRC)/compare.hip \
                           $(CSRC)/device_types.h include/rbrt_hip.h include/rbrt_hip_debug.h
 	@mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(CSRC)/kernels.hip $(CSRC)/bvh_device.hip $(CSRC)/denoise.hip $(CSRC)/tonemap.hip $(CSRC)/glare.hip $(CSRC)/guided.hip $(CSRC)/temporal.hip $(CSRC)/upsample.hip $(CSRC)/despike.hip $(CSRC)/compare.hip $(CSRC)/api.cpp $(CSRC)/bvh.cpp
+	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(CSRC)/kernels.hip $(CSRC)/bvh_device.hip $(CSRC)/denoise.hip $(CSRC)/tonemap.hip $(CSRC)/glare.hip $(CSRC)/guided.hip $(CSRC)/temporal.hip $(CSRC)/upsample.hip $(CSRC)/despike.hip $(CSRC)/compare.hip $(CSRC)/api.cpp $(CSRC)/frame_stages.cpp $(CSRC)/selftests.cpp $(CSRC)/bvh.cpp
 
 # Analysis build (not the product): every region marker of the megakernel stamps s_memtime; tools/region_profile.py reads it.
 timers: $(LIBDIR)/librbrt_hip_timers.so
-$(LIBDIR)/librbrt_hip_timers.so: $(LIBDIR)/librbrt_hip.so $(CSRC)/denoise.hip $(CSRC)/tonemap.hip $(CSRC)/glare.hip $(CSRC)/guided.hip $(CSRC)/temporal.hip $(CSRC)/upsample.hip $(CSRC)/despike.hip $(CSRC)/compare.hip
-	$(HIPCC) $(HIPFLAGS) -DRBRT_REGION_TIMERS=1 -shared -o $@ $(CSRC)/kernels.hip $(CSRC)/bvh_device.hip $(CSRC)/denoise.hip $(CSRC)/tonemap.hip $(CSRC)/glare.hip $(CSRC)/guided.hip $(CSRC)/temporal.hip $(CSRC)/upsample.hip $(CSRC)/despike.hip $(CSRC)/compare.hip $(CSRC)/api.cpp $(CSRC)/bvh.cpp
+$(LIBDIR)/librbrt_hip_timers.so: $(LIBDIR)/librbrt_hip.so $(CSRC)/denoise.hip $(CSRC)/tonemap.hip $(CSRC)/glare.hip $(CSRC)/guided.hip $(CSRC)/temporal.hip $(CSRC)/upsample.hip $(CSRC)/despike.hip $(CSRC)/compare.hip $(CSRC)/frame_stages.cpp $(CSRC)/selftests.cpp
+	$(HIPCC) $(HIPFLAGS) -DRBRT_REGION_TIMERS=1 -shared -o $@ $(CSRC)/kernels.hip $(CSRC)/bvh_device.hip $(CSRC)/denoise.hip $(CSRC)/tonemap.hip $(CSRC)/glare.hip $(CSRC)/guided.hip $(CSRC)/temporal.hip $(CSRC)/upsample.hip $(CSRC)/despike.hip $(CSRC)/compare.hip $(CSRC)/api.cpp $(CSRC)/frame_stages.cpp $(CSRC)/selftests.cpp $(CSRC)/bvh.cpp
 
 # (rbrt_amd/bin/rbrt links against librbrt_hip.so: a parallel make must not start the host before the library exists)
 host: $(LIBDIR)/librbrt_hip.so

@@ -1,4 +1,7 @@
-// api.cpp — implementation of the C ABI in include/rbrt_hip.h on top of the gfx950 kernels.
+// api.cpp — implementation of the C ABI in include/rbrt_hip.h on top of the gfx950 kernels: everything that needs a scene handle
+// (scene creation, the render calls, the hooks that take a scene or share code with scene creation), and the error message
+// behind every call. The image stages of the frame pipeline are in frame_stages.cpp, the self tests that need no scene in
+// selftests.cpp; api_common.h has what the three files share.
 // Host C++ only (compiled by hipcc for the HIP runtime headers); no torch, no Python.
 #include <hip/hip_runtime_api.h>
 
@@ -17,12 +20,13 @@
 #include <thread>
 #include <vector>
 
+#include "api_common.h"
 #include "bvh.h"
 #include "bvh_device.h"
 #include "device_types.h"
 #include "../../include/rbrt_hip_debug.h"
 
-namespace rbrt {
+namespace rbrt {  // (the launch wrappers only this file calls; api_common.h has the others)
 hipError_t launch_trace_megakernel(const TraceParams& P, uint32_t n_waves, bool stats, hipStream_t stream);
 hipError_t launch_trace_helper(const TraceParams& P, uint32_t n_waves, hipStream_t stream);
 size_t megakernel_gseq_bytes(uint32_t n_waves);
@@ -39,15 +43,7 @@ hipError_t launch_resolve_even(const TraceParams& P, const ResolveParams& R, uin
 hipError_t launch_adaptive_lists(const AdaptiveParams& A, hipStream_t stream);
 hipError_t launch_tile_error(const AdaptiveParams& A, uint32_t n_active_tiles, hipStream_t stream);
 hipError_t launch_adaptive_finish(const AdaptiveParams& A, hipStream_t stream);
-hipError_t launch_denoise(const DenoiseParams& D, hipStream_t stream);                 // denoise.hip
 hipError_t launch_denoise_halves(const DenoiseHalvesParams& Q, hipStream_t stream);
-hipError_t launch_tonemap(const TonemapParams& T, hipStream_t stream);                 // tonemap.hip
-hipError_t launch_glare(const GlareParams& G, hipStream_t stream);                     // glare.hip
-hipError_t launch_guided(const GuidedParams& G, uint32_t staged_max_step, hipStream_t stream);  // guided.hip
-hipError_t launch_temporal(const TemporalParams& T, hipStream_t stream);                // temporal.hip
-hipError_t launch_upsample(const UpsampleParams& U, hipStream_t stream);                // upsample.hip
-hipError_t launch_despike(const DespikeParams& D, hipStream_t stream);                  // despike.hip
-hipError_t launch_compare(const CompareParams& C, hipStream_t stream);                  // compare.hip
 hipError_t launch_unpack(const float* gathered, uint32_t width, uint32_t height, uint32_t world,
                          size_t rank_stride_pixels, float* out_radiance, uint8_t* out_rgb8, hipStream_t stream);
 hipError_t launch_trace_rays(const TraceParams& P, const float* rays, size_t n, float* out_t, int32_t* out_obj,
@@ -56,11 +52,6 @@ hipError_t launch_shading_normals(const TraceParams& P, const float* rays, size_
 hipError_t launch_surface_albedo(const TraceParams& P, const float* rays, size_t n, float* out_albedo, hipStream_t stream);
 hipError_t launch_environment_lookup(const EnvTexel* nodes, uint32_t n_env, const float* dirs, size_t n, float* out_rgb, hipStream_t stream);
 hipError_t launch_features(const TraceParams& P, const FeatureParams& F, hipStream_t stream);  // features.inl
-hipError_t launch_gate_selftest(const float* d_box, const float* d_rays, size_t n, uint8_t* d_fast, uint8_t* d_exact);
-hipError_t launch_ieee_selftest(uint64_t seed, size_t n, unsigned long long* d_counts);
-hipError_t launch_ieee_debug(const float* d_x, size_t n, const float* d_v, size_t m, float* d_sqrt, uint8_t* d_sqrt_short,
-                             float* d_norm, uint8_t* d_norm_short);
-hipError_t launch_sqrt_sweep(uint32_t first, uint64_t n, unsigned long long* d_counts);
 hipError_t launch_scatter_debug(const DevMaterial* d_mats, const float* d_in_dir, const float* d_p, const float* d_normal,
                                  const uint32_t* d_rng, size_t n, float* d_out_dir, uint8_t* d_out_ok, uint32_t* d_out_rng);
 uint64_t host_splitmix64(uint64_t x);
@@ -69,8 +60,43 @@ uint64_t host_splitmix64(uint64_t x);
 using namespace rbrt;
 
 namespace {
+thread_local std::string g_last_error;  // what rbrt_hip_last_error() returns: ONE object for the three files, behind fail()
+}  // namespace
 
-thread_local std::string g_last_error;
+// What api_common.h declares for frame_stages.cpp and selftests.cpp too, defined here, behind the one message.
+namespace rbrt {
+
+int fail(int code, const std::string& msg) {
+    g_last_error = msg;
+    return code;
+}
+
+int hip_fail(hipError_t e, const std::string& what) {
+    const int code = (e == hipErrorOutOfMemory) ? RBRT_ERR_OOM
+                     : (e == hipErrorNoDevice || e == hipErrorInvalidDevice) ? RBRT_ERR_NO_DEVICE
+                                                                             : RBRT_ERR_HIP;
+    return fail(code, what + ": " + hipGetErrorString(e));
+}
+
+int hook_result(hipError_t e, const char* who) {
+    return e == hipSuccess ? RBRT_OK : fail(RBRT_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+}
+
+int ensure_device(int device) {
+    int n = 0;
+    hipError_t e = hipGetDeviceCount(&n);
+    if (e != hipSuccess || n <= 0)
+        return fail(RBRT_ERR_NO_DEVICE, std::string("no HIP device available: ") +
+                                            (e != hipSuccess ? hipGetErrorString(e) : "device count is 0"));
+    if (device < 0 || device >= n) return fail(RBRT_ERR_INVALID_ARG, "device index out of range");
+    HIP_TRY(hipSetDevice(device));
+    return RBRT_OK;
+}
+
+}  // namespace rbrt
+
+namespace {
+
 thread_local rbrt_hip_call_times_t g_last_render_times{};  // of this thread's last rbrt_hip_render (rbrt_hip_debug.h)
 
 // GPU_MAX_HW_QUEUES as the process had it when this library was LOADED: the HIP runtime reads the variable when it starts,
@@ -86,45 +112,6 @@ const uint32_t g_hw_queues_at_load = [] {
 }();
 
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-int fail(int code, const std::string& msg) {
-    g_last_error = msg;
-    return code;
-}
-
-// A failed HIP call as the ABI reports it: the one place that maps a hipError_t to an error code.
-int hip_fail(hipError_t e, const std::string& what) {
-    const int code = (e == hipErrorOutOfMemory) ? RBRT_ERR_OOM
-                     : (e == hipErrorNoDevice || e == hipErrorInvalidDevice) ? RBRT_ERR_NO_DEVICE
-                                                                             : RBRT_ERR_HIP;
-    return fail(code, what + ": " + hipGetErrorString(e));
-}
-
-#define HIP_TRY(expr)                                    \
-    do {                                                 \
-        hipError_t _e = (expr);                          \
-        if (_e != hipSuccess) return hip_fail(_e, #expr); \
-    } while (0)
-
-// What a test hook returns after its chain of HIP calls. `who`: the hook, for the message.
-int hook_result(hipError_t e, const char* who) {
-    return e == hipSuccess ? RBRT_OK : fail(RBRT_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-}
-
-// A hipMalloc'ed array that lives as long as its scope: the temporaries of the builders and of the test hooks.
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    explicit DevBuf(T* owned = nullptr) : p(owned) {}
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc(reinterpret_cast<void**>(&p), n * sizeof(T)); }
-    T* get() const { return p; }
-    hipError_t from_host(const T* h, size_t n) { return hipMemcpy(p, h, n * sizeof(T), hipMemcpyHostToDevice); }
-    hipError_t upload(const T* h, size_t n) { const hipError_t e = alloc(n); return e != hipSuccess ? e : from_host(h, n); }
-    hipError_t to_host(T* h, size_t n) const { return hipMemcpy(h, p, n * sizeof(T), hipMemcpyDeviceToHost); }
-};
 
 uint32_t local_tiles_of(uint32_t n_tiles, uint32_t rank, uint32_t world) {
     return rank < n_tiles ? (n_tiles - rank + world - 1u) / world : 0u;
@@ -527,31 +514,6 @@ struct Refine {
 };
 
 namespace {
-
-int ensure_device(int device) {
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n <= 0)
-        return fail(RBRT_ERR_NO_DEVICE, std::string("no HIP device available: ") +
-                                            (e != hipSuccess ? hipGetErrorString(e) : "device count is 0"));
-    if (device < 0 || device >= n) return fail(RBRT_ERR_INVALID_ARG, "device index out of range");
-    HIP_TRY(hipSetDevice(device));
-    return RBRT_OK;
-}
-
-// The self tests' three counters: zeroed on device 0, filled by `launch`, handed back in counts. `who`: the hook.
-template <class Launch>
-int device_counts3(const char* who, uint64_t counts[3], Launch launch) {
-    if (int rc = ensure_device(0)) return rc;
-    DevBuf<unsigned long long> d;
-    HIP_TRY(d.alloc(3));
-    hipError_t e = hipMemset(d.get(), 0, 3 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = launch(d.get());
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the counters are copied out as they are");
-    if (e == hipSuccess) e = d.to_host(reinterpret_cast<unsigned long long*>(counts), 3);
-    return hook_result(e, who);
-}
 
 // Device memory that lives as long as the scene (released by rbrt_hip_scene_destroy, never one by one). Called from the
 // thread that holds the scene (scene_create, or a render call under s->mu); the background builder has allocations of its own.
@@ -2302,42 +2264,7 @@ int rbrt_hip_render_adaptive(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, cons
     return RBRT_OK;
 }
 
-// ---- Denoising (the rule: include/rbrt_hip.h; the kernels: denoise.hip) ----------------------------------------------------
-void rbrt_denoise_opts_default(rbrt_denoise_opts_t* o) {
-    if (!o) return;
-    o->window_radius = 5, o->patch_radius = 3, o->strength = 0.7f, o->reserved = 0;
-}
-
-static int check_denoise_opts(const rbrt_denoise_opts_t* d) {
-    if (d->reserved != 0u) return fail(RBRT_ERR_INVALID_ARG, "denoise: reserved must be 0");
-    if (d->window_radius > 10u) return fail(RBRT_ERR_INVALID_ARG, "denoise: window_radius must be 0..10");
-    if (d->patch_radius > 4u) return fail(RBRT_ERR_INVALID_ARG, "denoise: patch_radius must be 0..4");
-    if (!std::isfinite(d->strength) || !(d->strength > 0.0f)) return fail(RBRT_ERR_INVALID_ARG, "denoise: strength must be finite and > 0");
-    return RBRT_OK;
-}
-
-static DenoiseParams denoise_params(const float* a, const float* b, const float* wa, uint32_t width, uint32_t height,
-                                    const rbrt_denoise_opts_t* d, float* d_radiance, uint8_t* d_rgb8) {
-    DenoiseParams D;
-    std::memset(&D, 0, sizeof(D));
-    D.a = a, D.b = b, D.wa = wa, D.width = width, D.height = height;
-    D.window_radius = int32_t(d->window_radius), D.patch_radius = int32_t(d->patch_radius), D.k2 = d->strength * d->strength;
-    D.out_radiance = d_radiance, D.out_rgb8 = d_rgb8;
-    return D;
-}
-
-int rbrt_hip_denoise_halves(int device, void* stream, const float* d_a, const float* d_b, const float* d_wa, uint32_t width,
-                            uint32_t height, const rbrt_denoise_opts_t* d, float* d_radiance, uint8_t* d_rgb8) {
-    if (!d_a || !d_b || !d) return fail(RBRT_ERR_INVALID_ARG, "denoise_halves: null argument");
-    if (int rc = check_denoise_opts(d)) return rc;
-    if (width == 0 || height == 0) return fail(RBRT_ERR_INVALID_ARG, "denoise_halves: width and height must be >= 1");
-    if (uint64_t(width) * height >= (1ull << 32)) return fail(RBRT_ERR_UNSUPPORTED, "image has 2^32 or more pixels");
-    if (int rc = ensure_device(device)) return rc;
-    if (!d_radiance && !d_rgb8) return RBRT_OK;
-    HIP_TRY(launch_denoise(denoise_params(d_a, d_b, d_wa, width, height, d, d_radiance, d_rgb8), static_cast<hipStream_t>(stream)));
-    return RBRT_OK;
-}
-
+// ---- Denoising a handle's last adaptive render (the stages themselves, their checks and parameter blocks: frame_stages.cpp) ----
 // What both handle calls refuse in the last adaptive render, under the name of the call.
 static int check_last_adaptive(rbrt_hip_scene_t* s, const char* call) {
     const auto& S = s->adaptive;
@@ -2386,69 +2313,6 @@ int rbrt_hip_scene_denoise(rbrt_hip_scene_t* s, const rbrt_denoise_opts_t* d, vo
     return RBRT_OK;
 }
 
-// ---- Guided denoising (the rule: include/rbrt_hip.h; the kernels: guided.hip) ------------------------------------------------
-void rbrt_guided_opts_default(rbrt_guided_opts_t* o) {
-    if (!o) return;
-    o->levels = 5u, o->colour = 2.0f, o->normal = 0.35f, o->depth = 0.05f, o->albedo = 0.1f, o->flags = 0u;
-    o->reserved[0] = o->reserved[1] = 0u;
-}
-
-// The levels whose step is at most this stage their tile in LDS; the others read global memory (profiles/guided_config2.txt
-// has the comparison). rbrt_hip_debug_guided_staging changes it for the process.
-static std::atomic<uint32_t> g_guided_staged_max_step{RBRT_GUIDED_STAGED_MAX_STEP};
-
-int rbrt_hip_debug_guided_staging(int max_step) {
-    if (max_step < -1 || max_step > 4) return fail(RBRT_ERR_INVALID_ARG, "debug_guided_staging: max_step must be -1 (ask) or 0..4");
-    if (max_step >= 0) g_guided_staged_max_step.store(uint32_t(max_step));
-    return int(g_guided_staged_max_step.load());
-}
-
-size_t rbrt_hip_guided_workspace_bytes(uint32_t width, uint32_t height) {
-    if (width == 0u || height == 0u || uint64_t(width) * height >= (1ull << 31)) return 0;
-    return size_t(width) * height * 96u;  // (the layout of launch_guided: six planes of one float4 a pixel)
-}
-
-static int check_guided_args(const rbrt_guided_opts_t* g, const float* d_albedo, const float* d_normal, const float* d_depth,
-                             const float* d_coverage, const void* d_workspace) {
-    if (!g || !d_albedo || !d_normal || !d_depth || !d_coverage || !d_workspace) return fail(RBRT_ERR_INVALID_ARG, "denoise_guided: null argument");
-    if (g->levels == 0u || g->levels > RBRT_GUIDED_MAX_LEVELS) return fail(RBRT_ERR_INVALID_ARG, "denoise_guided: levels must be 1..6");
-    for (const float k : {g->colour, g->normal, g->depth, g->albedo})
-        if (!std::isfinite(k) || !(k > 0.0f)) return fail(RBRT_ERR_INVALID_ARG, "denoise_guided: colour, normal, depth and albedo must be finite and > 0");
-    if (g->flags & ~RBRT_GUIDED_NO_DEMODULATION) return fail(RBRT_ERR_INVALID_ARG, "denoise_guided: unknown flag bit");
-    if (g->reserved[0] != 0u || g->reserved[1] != 0u) return fail(RBRT_ERR_INVALID_ARG, "denoise_guided: reserved must be 0");
-    if (reinterpret_cast<uintptr_t>(d_workspace) % 16u != 0u) return fail(RBRT_ERR_INVALID_ARG, "denoise_guided: the workspace must be 16-byte aligned");
-    return RBRT_OK;
-}
-
-static GuidedParams guided_params(const float* a, const float* b, const float* wa, const float* d_albedo, const float* d_normal,
-                                  const float* d_depth, const float* d_coverage, uint32_t width, uint32_t height,
-                                  const rbrt_guided_opts_t* g, void* d_workspace, float* d_radiance, uint8_t* d_rgb8) {
-    GuidedParams G;
-    std::memset(&G, 0, sizeof(G));
-    G.a = a, G.b = b, G.wa = wa, G.albedo = d_albedo, G.normal = d_normal, G.depth = d_depth, G.coverage = d_coverage;
-    G.width = width, G.height = height, G.levels = g->levels, G.flags = g->flags;
-    // the rule's host-side values, in float, one operation a statement (this file is compiled with -ffp-contract=off)
-    const float kn2 = g->normal * g->normal, ka2 = g->albedo * g->albedo;
-    G.kc2 = g->colour * g->colour, G.kz2 = g->depth * g->depth;
-    G.in = 1.0f / kn2, G.ia = 1.0f / ka2;
-    G.workspace = d_workspace, G.out_radiance = d_radiance, G.out_rgb8 = d_rgb8;
-    return G;
-}
-
-int rbrt_hip_denoise_guided(int device, void* stream, const float* d_a, const float* d_b, const float* d_wa, const float* d_albedo,
-                            const float* d_normal, const float* d_depth, const float* d_coverage, uint32_t width, uint32_t height,
-                            const rbrt_guided_opts_t* g, void* d_workspace, float* d_radiance, uint8_t* d_rgb8) {
-    if (!d_a || !d_b) return fail(RBRT_ERR_INVALID_ARG, "denoise_guided: null argument");
-    if (int rc = check_guided_args(g, d_albedo, d_normal, d_depth, d_coverage, d_workspace)) return rc;
-    if (width == 0u || height == 0u) return fail(RBRT_ERR_INVALID_ARG, "denoise_guided: width and height must be >= 1");
-    if (uint64_t(width) * height >= (1ull << 31)) return fail(RBRT_ERR_UNSUPPORTED, "denoise_guided: 2^31 or more pixels");
-    if (int rc = ensure_device(device)) return rc;
-    if (!d_radiance && !d_rgb8) return RBRT_OK;
-    HIP_TRY(launch_guided(guided_params(d_a, d_b, d_wa, d_albedo, d_normal, d_depth, d_coverage, width, height, g, d_workspace, d_radiance, d_rgb8),
-                          g_guided_staged_max_step.load(), static_cast<hipStream_t>(stream)));
-    return RBRT_OK;
-}
-
 int rbrt_hip_scene_denoise_guided(rbrt_hip_scene_t* s, const rbrt_guided_opts_t* g, void* stream_v, const float* d_albedo,
                                   const float* d_normal, const float* d_depth, const float* d_coverage, void* d_workspace,
                                   float* d_radiance, uint8_t* d_rgb8) {
@@ -2462,333 +2326,7 @@ int rbrt_hip_scene_denoise_guided(rbrt_hip_scene_t* s, const rbrt_guided_opts_t*
     if (int rc = scene_halves(s, stream, nullptr, nullptr)) return rc;
     HIP_TRY(launch_guided(guided_params(S.d_half_a, S.d_half_b, S.d_wa, d_albedo, d_normal, d_depth, d_coverage, S.last.width, S.last.height, g,
                                         d_workspace, d_radiance, d_rgb8),
-                          g_guided_staged_max_step.load(), stream));
-    return RBRT_OK;
-}
-
-// ---- Temporal accumulation (the rule: include/rbrt_hip.h; the kernel: temporal.hip) -----------------------------------------
-void rbrt_temporal_opts_default(rbrt_temporal_opts_t* o) {
-    if (!o) return;
-    o->max_history = 32.0f, o->depth = 0.05f, o->normal = 0.35f, o->flags = 0u;
-    for (uint32_t& r : o->reserved) r = 0u;
-}
-
-size_t rbrt_hip_temporal_history_bytes(uint32_t width, uint32_t height) {
-    if (width == 0u || height == 0u || uint64_t(width) * height >= (1ull << 31)) return 0;
-    return size_t(width) * height * 48u;  // (the layout of temporal.hip: three planes of one float4 a pixel)
-}
-
-static bool positive_finite(float x) { return std::isfinite(x) && x > 0.0f; }
-static float dot3(const float* a, const float* b) {  // the rule's dot, one operation a statement
-    const float x = a[0] * b[0], y = a[1] * b[1], z = a[2] * b[2];
-    const float xy = x + y;
-    return xy + z;
-}
-
-int rbrt_hip_temporal_accumulate(int device, void* stream, const float* d_a, const float* d_b, const float* d_normal,
-                                 const float* d_depth, const float* d_coverage, const rbrt_camera_t* cam, const rbrt_camera_t* prev,
-                                 const rbrt_temporal_opts_t* o, const void* d_history_in, void* d_history_out, float* d_out_a,
-                                 float* d_out_b, float* d_out_length) {
-    if (!d_a || !d_b || !d_normal || !d_depth || !d_coverage || !cam || !o) return fail(RBRT_ERR_INVALID_ARG, "temporal_accumulate: null argument");
-    if (d_history_in && !prev) return fail(RBRT_ERR_INVALID_ARG, "temporal_accumulate: a history needs cam_prev");
-    if (d_history_in && d_history_in == d_history_out)
-        return fail(RBRT_ERR_INVALID_ARG, "temporal_accumulate: d_history_in and d_history_out must differ (keep two and alternate)");
-    if (reinterpret_cast<uintptr_t>(d_history_in) % 16u != 0u || reinterpret_cast<uintptr_t>(d_history_out) % 16u != 0u)
-        return fail(RBRT_ERR_INVALID_ARG, "temporal_accumulate: a history must be 16-byte aligned");
-    const uint32_t width = cam->img_width_pix, height = cam->img_height_pix;
-    if (width == 0u || height == 0u) return fail(RBRT_ERR_INVALID_ARG, "temporal_accumulate: width and height must be >= 1");
-    if (d_history_in && (prev->img_width_pix != width || prev->img_height_pix != height))
-        return fail(RBRT_ERR_INVALID_ARG, "temporal_accumulate: cam_prev's image size differs from cam's");
-    if (!std::isfinite(o->max_history) || !(o->max_history >= 1.0f)) return fail(RBRT_ERR_INVALID_ARG, "temporal_accumulate: max_history must be finite and >= 1");
-    for (const float k : {o->depth, o->normal})
-        if (!std::isfinite(k) || !(k >= 0.0f)) return fail(RBRT_ERR_INVALID_ARG, "temporal_accumulate: depth and normal must be finite and >= 0");
-    if (o->flags != 0u) return fail(RBRT_ERR_INVALID_ARG, "temporal_accumulate: unknown flag bit");
-    for (const uint32_t r : o->reserved)
-        if (r != 0u) return fail(RBRT_ERR_INVALID_ARG, "temporal_accumulate: reserved must be 0");
-    if (!positive_finite(cam->mm_per_pix_hor) || !positive_finite(cam->mm_per_pix_vert))
-        return fail(RBRT_ERR_INVALID_ARG, "temporal_accumulate: cam's mm_per_pix must be finite and > 0");
-
-    TemporalParams T;
-    std::memset(&T, 0, sizeof(T));
-    T.a = d_a, T.b = d_b, T.normal = d_normal, T.depth = d_depth, T.coverage = d_coverage;
-    T.history_in = d_history_in, T.history_out = d_history_out, T.out_a = d_out_a, T.out_b = d_out_b, T.out_length = d_out_length;
-    T.width = width, T.height = height;
-    T.max_history = o->max_history, T.kz = o->depth, T.kn2 = o->normal * o->normal;
-    for (int k = 0; k < 3; ++k)
-        T.pos[k] = cam->position[k], T.right[k] = cam->right[k], T.up[k] = cam->up[k], T.center[k] = cam->img_center_point[k];
-    T.mm_hor = cam->mm_per_pix_hor, T.mm_vert = cam->mm_per_pix_vert;
-    T.hx = float(width / 2u), T.hy = float(height / 2u);
-    if (d_history_in) {
-        if (!positive_finite(prev->mm_per_pix_hor) || !positive_finite(prev->mm_per_pix_vert))
-            return fail(RBRT_ERR_INVALID_ARG, "temporal_accumulate: cam_prev's mm_per_pix must be finite and > 0");
-        // the rule's constants of K', in float, one operation a statement (this file is compiled with -ffp-contract=off)
-        const float* r = prev->right;
-        const float* u = prev->up;
-        for (int k = 0; k < 3; ++k) {
-            const int k1 = (k + 1) % 3, k2 = (k + 2) % 3;
-            const float m0 = r[k1] * u[k2], m1 = r[k2] * u[k1];
-            T.n[k] = m0 - m1;
-            T.w[k] = prev->img_center_point[k] - prev->position[k];
-            T.pos_prev[k] = prev->position[k], T.right_prev[k] = r[k], T.up_prev[k] = u[k];
-        }
-        T.wn = dot3(T.w, T.n);
-        T.rr = dot3(r, r), T.uu = dot3(u, u), T.ru = dot3(r, u);
-        const float d0 = T.rr * T.uu, d1 = T.ru * T.ru;
-        T.det = d0 - d1;
-        T.sx = 0.001f * prev->mm_per_pix_hor, T.sy = 0.001f * prev->mm_per_pix_vert;
-        if (!std::isfinite(T.det) || T.det == 0.0f || !std::isfinite(T.wn) || T.wn == 0.0f)
-            return fail(RBRT_ERR_INVALID_ARG, "temporal_accumulate: cam_prev is degenerate (right x up, or its distance to the image plane, is 0 or not finite)");
-    }
-    if (uint64_t(width) * height >= (1ull << 31)) return fail(RBRT_ERR_UNSUPPORTED, "temporal_accumulate: 2^31 or more pixels");
-    if (int rc = ensure_device(device)) return rc;
-    if (!d_history_out && !d_out_a && !d_out_b && !d_out_length) return RBRT_OK;
-    HIP_TRY(launch_temporal(T, static_cast<hipStream_t>(stream)));
-    return RBRT_OK;
-}
-
-// ---- Guided upsampling (the rule: include/rbrt_hip.h; the kernels: upsample.hip) ----------------------------------------------
-void rbrt_upsample_opts_default(rbrt_upsample_opts_t* o) {
-    if (!o) return;
-    o->factor = 2u, o->normal = 0.5f, o->depth = 0.1f, o->albedo = 0.2f, o->flags = 0u;
-    for (uint32_t& r : o->reserved) r = 0u;
-}
-
-int rbrt_hip_upsample_camera(const rbrt_camera_t* full, uint32_t factor, rbrt_camera_t* low) {
-    if (!full || !low) return fail(RBRT_ERR_INVALID_ARG, "upsample_camera: null argument");
-    if (factor == 0u || factor > RBRT_UPSAMPLE_MAX_FACTOR) return fail(RBRT_ERR_INVALID_ARG, "upsample_camera: factor must be 1..4");
-    const uint32_t W = full->img_width_pix, H = full->img_height_pix;
-    if (W == 0u || H == 0u) return fail(RBRT_ERR_INVALID_ARG, "upsample_camera: width and height must be >= 1");
-    if (!std::isfinite(full->mm_per_pix_hor) || !std::isfinite(full->mm_per_pix_vert))
-        return fail(RBRT_ERR_INVALID_ARG, "upsample_camera: mm_per_pix must be finite");
-    const uint32_t f = factor;
-    const uint32_t w = uint32_t((uint64_t(W) + f - 1u) / f), h = uint32_t((uint64_t(H) + f - 1u) / f);
-    // the rule's shift, in float, one operation a statement (this file is compiled with -ffp-contract=off)
-    const float half = 0.5f * float(f - 1u);
-    const float dx = float(f * (w / 2u)) - float(W / 2u), dy = float(f * (h / 2u)) - float(H / 2u);
-    const float kx = dx + half, ky = dy + half;
-    const float mx = kx * full->mm_per_pix_hor, my = ky * full->mm_per_pix_vert;
-    const float sx = 0.001f * mx, sy = 0.001f * my;
-    rbrt_camera_t out = *full;
-    for (int k = 0; k < 3; ++k) {
-        const float r = sx * full->right[k], u = sy * full->up[k];
-        const float cr = full->img_center_point[k] + r;
-        out.img_center_point[k] = cr - u;
-    }
-    out.mm_per_pix_hor = float(f) * full->mm_per_pix_hor, out.mm_per_pix_vert = float(f) * full->mm_per_pix_vert;
-    out.img_width_pix = w, out.img_height_pix = h;
-    *low = out;
-    return RBRT_OK;
-}
-
-size_t rbrt_hip_upsample_workspace_bytes(uint32_t width, uint32_t height, uint32_t factor) {
-    if (width == 0u || height == 0u || factor == 0u || factor > RBRT_UPSAMPLE_MAX_FACTOR || uint64_t(width) * height >= (1ull << 31)) return 0;
-    const size_t w = (size_t(width) + factor - 1u) / factor, h = (size_t(height) + factor - 1u) / factor;
-    return w * h * 64u;  // (the layout of upsample.hip: four planes of one float4 a low pixel)
-}
-
-int rbrt_hip_upsample_halves(int device, void* stream, const float* d_a, const float* d_b, const float* d_wa, const float* d_albedo,
-                             const float* d_normal, const float* d_depth, const float* d_coverage, uint32_t width, uint32_t height,
-                             const rbrt_upsample_opts_t* o, void* d_workspace, float* d_out_a, float* d_out_b, float* d_out_wa) {
-    if (!d_a || !d_b || !d_albedo || !d_normal || !d_depth || !d_coverage || !o || !d_workspace)
-        return fail(RBRT_ERR_INVALID_ARG, "upsample_halves: null argument");
-    if (width == 0u || height == 0u) return fail(RBRT_ERR_INVALID_ARG, "upsample_halves: width and height must be >= 1");
-    if (o->factor == 0u || o->factor > RBRT_UPSAMPLE_MAX_FACTOR) return fail(RBRT_ERR_INVALID_ARG, "upsample_halves: factor must be 1..4");
-    for (const float k : {o->normal, o->depth, o->albedo})
-        if (!positive_finite(k)) return fail(RBRT_ERR_INVALID_ARG, "upsample_halves: normal, depth and albedo must be finite and > 0");
-    if ((o->flags & ~RBRT_UPSAMPLE_NO_DEMODULATION) != 0u) return fail(RBRT_ERR_INVALID_ARG, "upsample_halves: unknown flag bit");
-    for (const uint32_t r : o->reserved)
-        if (r != 0u) return fail(RBRT_ERR_INVALID_ARG, "upsample_halves: reserved must be 0");
-    if (reinterpret_cast<uintptr_t>(d_workspace) % 16u != 0u) return fail(RBRT_ERR_INVALID_ARG, "upsample_halves: the workspace must be 16-byte aligned");
-    if (uint64_t(width) * height >= (1ull << 31)) return fail(RBRT_ERR_UNSUPPORTED, "upsample_halves: 2^31 or more pixels");
-
-    UpsampleParams U;
-    std::memset(&U, 0, sizeof(U));
-    U.a = d_a, U.b = d_b, U.wa = d_wa, U.albedo = d_albedo, U.normal = d_normal, U.depth = d_depth, U.coverage = d_coverage;
-    U.workspace = d_workspace, U.out_a = d_out_a, U.out_b = d_out_b, U.out_wa = d_out_wa;
-    U.width = width, U.height = height, U.factor = o->factor, U.flags = o->flags;
-    U.low_width = (width + o->factor - 1u) / o->factor, U.low_height = (height + o->factor - 1u) / o->factor;
-    // the rule's constants, in float, one operation a statement
-    const float kn2 = o->normal * o->normal, ka2 = o->albedo * o->albedo;
-    U.in = 1.0f / kn2, U.ia = 1.0f / ka2, U.kz2 = o->depth * o->depth, U.invf = 1.0f / float(o->factor);
-    if (int rc = ensure_device(device)) return rc;
-    if (!d_out_a && !d_out_b && !d_out_wa) return RBRT_OK;
-    HIP_TRY(launch_upsample(U, static_cast<hipStream_t>(stream)));
-    return RBRT_OK;
-}
-
-// ---- Spike removal (the rule: include/rbrt_hip.h; the kernel: despike.hip) -----------------------------------------------------
-void rbrt_despike_opts_default(rbrt_despike_opts_t* o) {
-    if (!o) return;
-    o->radius = 2u, o->rank = 2u, o->threshold = 4.0f, o->floor = 0.01f, o->flags = 0u;
-    for (uint32_t& r : o->reserved) r = 0u;
-}
-
-int rbrt_hip_despike_halves(int device, void* stream, const float* d_a, const float* d_b, uint32_t width, uint32_t height,
-                            const rbrt_despike_opts_t* o, float* d_out_a, float* d_out_b, uint8_t* d_mask, rbrt_despike_result_t* d_result) {
-    if (!d_a || !d_b || !o) return fail(RBRT_ERR_INVALID_ARG, "despike_halves: null argument");
-    if (width == 0u || height == 0u) return fail(RBRT_ERR_INVALID_ARG, "despike_halves: width and height must be >= 1");
-    if (o->radius == 0u || o->radius > RBRT_DESPIKE_MAX_RADIUS) return fail(RBRT_ERR_INVALID_ARG, "despike_halves: radius must be 1..2");
-    if (o->rank == 0u || o->rank > RBRT_DESPIKE_MAX_RANK) return fail(RBRT_ERR_INVALID_ARG, "despike_halves: rank must be 1..4");
-    if (!std::isfinite(o->threshold) || !(o->threshold >= 1.0f)) return fail(RBRT_ERR_INVALID_ARG, "despike_halves: threshold must be finite and >= 1");
-    if (!std::isfinite(o->floor) || !(o->floor >= 0.0f)) return fail(RBRT_ERR_INVALID_ARG, "despike_halves: floor must be finite and >= 0");
-    if (o->flags != 0u) return fail(RBRT_ERR_INVALID_ARG, "despike_halves: unknown flag bit");
-    for (const uint32_t r : o->reserved)
-        if (r != 0u) return fail(RBRT_ERR_INVALID_ARG, "despike_halves: reserved must be 0");
-    for (const void* out : {static_cast<const void*>(d_out_a), static_cast<const void*>(d_out_b), static_cast<const void*>(d_mask),
-                            static_cast<const void*>(d_result)})
-        if (out && (out == d_a || out == d_b)) return fail(RBRT_ERR_INVALID_ARG, "despike_halves: an output must not be an input");
-    if (uint64_t(width) * height >= (1ull << 31)) return fail(RBRT_ERR_UNSUPPORTED, "despike_halves: 2^31 or more pixels");
-
-    DespikeParams D;
-    std::memset(&D, 0, sizeof(D));
-    D.a = d_a, D.b = d_b, D.out_a = d_out_a, D.out_b = d_out_b, D.mask = d_mask, D.counts = reinterpret_cast<uint32_t*>(d_result);
-    D.width = width, D.height = height, D.radius = o->radius, D.rank = o->rank, D.threshold = o->threshold, D.floor = o->floor;
-    if (int rc = ensure_device(device)) return rc;
-    if (!d_out_a && !d_out_b && !d_mask && !d_result) return RBRT_OK;
-    HIP_TRY(launch_despike(D, static_cast<hipStream_t>(stream)));
-    return RBRT_OK;
-}
-
-// ---- Image comparison (the rule: include/rbrt_hip.h; the kernels: compare.hip) -------------------------------------------------
-void rbrt_compare_opts_default(rbrt_compare_opts_t* o) {
-    if (!o) return;
-    o->epsilon = 0.01f, o->flags = 0u;
-    for (uint32_t& r : o->reserved) r = 0u;
-}
-
-static uint64_t compare_tiles(uint32_t width, uint32_t height) {
-    return uint64_t((width + RBRT_COMPARE_TILE_W - 1u) / RBRT_COMPARE_TILE_W) * ((height + RBRT_COMPARE_TILE_H - 1u) / RBRT_COMPARE_TILE_H);
-}
-
-size_t rbrt_hip_compare_workspace_bytes(uint32_t width, uint32_t height) {
-    if (width == 0u || height == 0u || uint64_t(width) * height >= (1ull << 31)) return 0;
-    return size_t(compare_tiles(width, height)) * sizeof(CompareTilePartial);
-}
-
-int rbrt_hip_compare_images(int device, void* stream, const float* d_x, const float* d_ref, uint32_t width, uint32_t height,
-                            const rbrt_compare_opts_t* o, void* d_workspace, float* d_rel_map, float* d_ssim_map, rbrt_compare_result_t* d_result) {
-    if (!d_x || !d_ref || !o) return fail(RBRT_ERR_INVALID_ARG, "compare_images: null argument");
-    if (d_result && !d_workspace) return fail(RBRT_ERR_INVALID_ARG, "compare_images: a result needs a workspace (null argument)");
-    if ((reinterpret_cast<uintptr_t>(d_workspace) & 7u) != 0u || (reinterpret_cast<uintptr_t>(d_result) & 7u) != 0u)
-        return fail(RBRT_ERR_INVALID_ARG, "compare_images: the workspace and the result must be 8-byte aligned");
-    if (width == 0u || height == 0u) return fail(RBRT_ERR_INVALID_ARG, "compare_images: width and height must be >= 1");
-    if (!std::isfinite(o->epsilon) || !(o->epsilon > 0.0f)) return fail(RBRT_ERR_INVALID_ARG, "compare_images: epsilon must be finite and above 0");
-    if (o->flags != 0u) return fail(RBRT_ERR_INVALID_ARG, "compare_images: unknown flag bit");
-    for (const uint32_t r : o->reserved)
-        if (r != 0u) return fail(RBRT_ERR_INVALID_ARG, "compare_images: reserved must be 0");
-    const void* const outs[4] = {d_rel_map, d_ssim_map, d_result, d_result ? d_workspace : nullptr};
-    for (int i = 0; i < 4; ++i) {
-        if (!outs[i]) continue;
-        if (outs[i] == d_x || outs[i] == d_ref) return fail(RBRT_ERR_INVALID_ARG, "compare_images: an output must not be an input");
-        for (int j = 0; j < i; ++j)
-            if (outs[i] == outs[j]) return fail(RBRT_ERR_INVALID_ARG, "compare_images: an output must not be another output");
-    }
-    if (uint64_t(width) * height >= (1ull << 31)) return fail(RBRT_ERR_UNSUPPORTED, "compare_images: 2^31 or more pixels");
-
-    CompareParams P;
-    std::memset(&P, 0, sizeof(P));
-    P.x = d_x, P.ref = d_ref, P.rel_map = d_rel_map, P.ssim_map = d_ssim_map;
-    P.partials = d_result ? static_cast<CompareTilePartial*>(d_workspace) : nullptr, P.result = d_result;
-    P.width = width, P.height = height, P.epsilon = o->epsilon;
-    P.tiles_x = (width + RBRT_COMPARE_TILE_W - 1u) / RBRT_COMPARE_TILE_W, P.tiles = uint32_t(compare_tiles(width, height));
-    if (int rc = ensure_device(device)) return rc;
-    if (!d_rel_map && !d_ssim_map && !d_result) return RBRT_OK;
-    HIP_TRY(launch_compare(P, static_cast<hipStream_t>(stream)));
-    return RBRT_OK;
-}
-
-void rbrt_compare_summary(const rbrt_compare_result_t* r, uint32_t width, uint32_t height, double peak, rbrt_compare_summary_t* out) {
-    if (!out) return;
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    out->mse = out->mae = out->relmse = out->psnr_db = out->ssim = nan;
-    if (!r || r->usable == 0u) return;
-    const double n = 3.0 * double(r->usable);
-    out->mse = r->sum_se / n, out->mae = r->sum_ae / n, out->relmse = r->sum_rel / n;
-    out->ssim = r->sum_ssim / (double(width) * double(height));
-    out->psnr_db = 10.0 * std::log10((peak * peak) / out->mse);
-}
-
-// ---- Display transform (the rule: include/rbrt_hip.h; the kernels: tonemap.hip) ----------------------------------------------
-void rbrt_tonemap_opts_default(rbrt_tonemap_opts_t* o) {
-    if (!o) return;
-    o->curve = RBRT_TONE_LINEAR, o->exposure = 1.0f, o->key = 0.18f, o->key_permille = 500u;
-    o->white = 0.0f, o->white_permille = 990u, o->reserved[0] = o->reserved[1] = 0u;
-}
-
-int rbrt_hip_tonemap(int device, void* stream, const float* d_radiance, size_t n_pixels, const rbrt_tonemap_opts_t* o,
-                     void* d_workspace, float* d_out_radiance, uint8_t* d_rgb8) {
-    if (!d_radiance || !o) return fail(RBRT_ERR_INVALID_ARG, "tonemap: null argument");
-    if (n_pixels == 0) return fail(RBRT_ERR_INVALID_ARG, "tonemap: n_pixels must be >= 1");
-    if (o->curve > RBRT_TONE_ACES) return fail(RBRT_ERR_INVALID_ARG, "tonemap: unknown curve");
-    if (o->reserved[0] != 0u || o->reserved[1] != 0u) return fail(RBRT_ERR_INVALID_ARG, "tonemap: reserved must be 0");
-    if (!std::isfinite(o->exposure) || !std::isfinite(o->key) || !std::isfinite(o->white))
-        return fail(RBRT_ERR_INVALID_ARG, "tonemap: exposure, key and white must be finite");
-    if (o->exposure < 0.0f || o->white < 0.0f) return fail(RBRT_ERR_INVALID_ARG, "tonemap: exposure and white must be >= 0");
-    const bool automatic = o->exposure == 0.0f || o->white == 0.0f;
-    if (o->exposure == 0.0f && !(o->key > 0.0f)) return fail(RBRT_ERR_INVALID_ARG, "tonemap: key must be > 0 for automatic exposure");
-    if (o->key_permille > 1000u || o->white_permille > 1000u) return fail(RBRT_ERR_INVALID_ARG, "tonemap: a permille must be 0..1000");
-    if (automatic && !d_workspace) return fail(RBRT_ERR_INVALID_ARG, "tonemap: automatic exposure or white needs a workspace");
-    if (reinterpret_cast<uintptr_t>(d_workspace) % 16u != 0u) return fail(RBRT_ERR_INVALID_ARG, "tonemap: the workspace must be 16-byte aligned");
-    if (uint64_t(n_pixels) >= (1ull << 32)) return fail(RBRT_ERR_UNSUPPORTED, "tonemap: 2^32 or more pixels (the bins are 32-bit)");
-    if (int rc = ensure_device(device)) return rc;
-    TonemapParams T;
-    std::memset(&T, 0, sizeof(T));
-    T.in = d_radiance, T.n = uint32_t(n_pixels), T.curve = o->curve;
-    T.exposure = o->exposure + 0.0f, T.white = o->white + 0.0f;  // (-0 is 0: automatic)
-    T.key = o->key, T.key_permille = o->key_permille, T.white_permille = o->white_permille;
-    T.hist = static_cast<uint32_t*>(d_workspace), T.out_radiance = d_out_radiance, T.out_rgb8 = d_rgb8;
-    HIP_TRY(launch_tonemap(T, static_cast<hipStream_t>(stream)));
-    return RBRT_OK;
-}
-
-// ---- Glare (the rule: include/rbrt_hip.h; the kernels: glare.hip) -------------------------------------------------------------
-void rbrt_glare_opts_default(rbrt_glare_opts_t* o) {
-    if (!o) return;
-    o->threshold = 1.0f, o->intensity = 0.1f, o->levels = 5u, o->spread = 1.0f;
-    o->reserved[0] = o->reserved[1] = o->reserved[2] = o->reserved[3] = 0u;
-}
-
-size_t rbrt_hip_glare_workspace_bytes(uint32_t width, uint32_t height, uint32_t levels) {
-    if (width == 0u || height == 0u || levels == 0u || levels > RBRT_GLARE_MAX_LEVELS) return 0;
-    if (uint64_t(width) * height >= (1ull << 31)) return 0;
-    size_t pixels = 0;  // (levels 1..L, the layout of launch_glare: float4 a pixel, level after level)
-    uint32_t w = width, h = height;
-    for (uint32_t l = 1; l <= levels; ++l) {
-        w = (w + 1u) / 2u, h = (h + 1u) / 2u;
-        pixels += size_t(w) * h;
-    }
-    return pixels * 16u;
-}
-
-int rbrt_hip_glare(int device, void* stream, const float* d_radiance, uint32_t width, uint32_t height, const rbrt_glare_opts_t* o,
-                   void* d_workspace, float* d_out_radiance, uint8_t* d_rgb8) {
-    if (!d_radiance || !o || !d_workspace) return fail(RBRT_ERR_INVALID_ARG, "glare: null argument");
-    if (width == 0u || height == 0u) return fail(RBRT_ERR_INVALID_ARG, "glare: width and height must be >= 1");
-    if (o->levels == 0u || o->levels > RBRT_GLARE_MAX_LEVELS) return fail(RBRT_ERR_INVALID_ARG, "glare: levels must be 1..8");
-    if (o->reserved[0] != 0u || o->reserved[1] != 0u || o->reserved[2] != 0u || o->reserved[3] != 0u)
-        return fail(RBRT_ERR_INVALID_ARG, "glare: reserved must be 0");
-    if (!std::isfinite(o->threshold) || !std::isfinite(o->intensity) || !std::isfinite(o->spread))
-        return fail(RBRT_ERR_INVALID_ARG, "glare: threshold, intensity and spread must be finite");
-    if (o->threshold < 0.0f) return fail(RBRT_ERR_INVALID_ARG, "glare: threshold must be >= 0");
-    if (!(o->intensity > 0.0f) || o->intensity > 1.0f) return fail(RBRT_ERR_INVALID_ARG, "glare: intensity must be above 0 and at most 1");
-    if (o->spread < 0.0f) return fail(RBRT_ERR_INVALID_ARG, "glare: spread must be >= 0");
-    if (reinterpret_cast<uintptr_t>(d_workspace) % 16u != 0u) return fail(RBRT_ERR_INVALID_ARG, "glare: the workspace must be 16-byte aligned");
-    if (uint64_t(width) * height >= (1ull << 31)) return fail(RBRT_ERR_UNSUPPORTED, "glare: 2^31 or more pixels");
-    if (int rc = ensure_device(device)) return rc;
-    GlareParams G;
-    std::memset(&G, 0, sizeof(G));
-    G.in = d_radiance, G.width = width, G.height = height, G.levels = o->levels;
-    G.threshold = o->threshold + 0.0f, G.intensity = o->intensity, G.spread = o->spread + 0.0f;  // (-0 is 0)
-    // the rule's normalisation, in float, one operation a statement (this file is compiled with -ffp-contract=off)
-    float n = 1.0f, p = 1.0f;
-    for (uint32_t l = 2; l <= G.levels; ++l) {
-        p = p * G.spread;
-        n = n + p;
-    }
-    const float inv = 1.0f / n;
-    G.a = G.intensity * inv;
-    G.workspace = d_workspace, G.out_radiance = d_out_radiance, G.out_rgb8 = d_rgb8;
-    HIP_TRY(launch_glare(G, static_cast<hipStream_t>(stream)));
+                          guided_staged_max_step(), stream));
     return RBRT_OK;
 }
 
@@ -3194,70 +2732,6 @@ int rbrt_hip_bvh_build_device(const rbrt_mesh_t* mesh, void** nodes_out, size_t*
     if (int rc = copy_out(h, "bvh_build_device", nodes_out, n_nodes, tris_out, n_tris, max_depth, max_e12)) return rc;
     *built = 1;
     return RBRT_OK;
-}
-
-// Test hook: BoundingBox::hit (aabbox.rs:28-58) on n rays against one box, by the division-free form the megakernel
-// uses (out_fast) and by the verbatim IEEE form (out_exact). Host arrays.
-int rbrt_hip_selftest_gate(const float lo[3], const float hi[3], const float* rays, size_t n, uint8_t* out_fast,
-                           uint8_t* out_exact) {
-    if (!lo || !hi || (!rays && n) || !out_fast || !out_exact) return fail(RBRT_ERR_INVALID_ARG, "selftest_gate: null argument");
-    if (n == 0) return RBRT_OK;
-    if (int rc = ensure_device(0)) return rc;
-    DevBuf<float> d_box, d_rays;
-    DevBuf<uint8_t> d_f, d_e;
-    const float box[6] = {lo[0], lo[1], lo[2], hi[0], hi[1], hi[2]};
-    hipError_t e = d_box.upload(box, 6);
-    if (e == hipSuccess) e = d_rays.upload(rays, n * 6);
-    if (e == hipSuccess) e = d_f.alloc(n);
-    if (e == hipSuccess) e = d_e.alloc(n);
-    if (e == hipSuccess) e = launch_gate_selftest(d_box.get(), d_rays.get(), n, d_f.get(), d_e.get());
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = d_f.to_host(out_fast, n);
-    if (e == hipSuccess) e = d_e.to_host(out_exact, n);
-    return hook_result(e, "selftest_gate");
-}
-
-// Test hook: the kernels' short forms of IEEE sqrt / normalize against the compiler's, on n pseudo-random operands.
-int rbrt_hip_selftest_ieee(uint64_t seed, size_t n, uint64_t counts[3]) {
-    if (!counts) return fail(RBRT_ERR_INVALID_ARG, "selftest_ieee: null argument");
-    if (n >= (1ull << 32) * 256ull) return fail(RBRT_ERR_INVALID_ARG, "selftest_ieee: n too large");
-    return device_counts3("selftest_ieee", counts, [&](unsigned long long* d) { return launch_ieee_selftest(seed, n, d); });
-}
-
-// Test hook: ieee_sqrt / normalize of the kernels on caller-supplied operands, with the path each element's wave took.
-int rbrt_hip_debug_ieee(const float* x, size_t n, const float* v, size_t m, float* out_sqrt, uint8_t* out_sqrt_short,
-                        float* out_norm, uint8_t* out_norm_short) {
-    if ((n && (!x || !out_sqrt || !out_sqrt_short)) || (m && (!v || !out_norm || !out_norm_short)))
-        return fail(RBRT_ERR_INVALID_ARG, "debug_ieee: null argument");
-    if (n >= (1ull << 32) * 256ull || m >= (1ull << 32) * 256ull) return fail(RBRT_ERR_INVALID_ARG, "debug_ieee: n or m too large");
-    if (n == 0 && m == 0) return RBRT_OK;
-    if (int rc = ensure_device(0)) return rc;
-    DevBuf<float> d_x, d_v, d_s, d_q;
-    DevBuf<uint8_t> d_sf, d_qf;
-    const size_t nx = std::max<size_t>(n, 1), nv = std::max<size_t>(m, 1);
-    hipError_t e = d_x.alloc(nx);
-    if (e == hipSuccess) e = d_s.alloc(nx);
-    if (e == hipSuccess) e = d_sf.alloc(nx);
-    if (e == hipSuccess) e = d_v.alloc(nv * 3);
-    if (e == hipSuccess) e = d_q.alloc(nv * 3);
-    if (e == hipSuccess) e = d_qf.alloc(nv);
-    if (e == hipSuccess && n) e = d_x.from_host(x, n);
-    if (e == hipSuccess && m) e = d_v.from_host(v, m * 3);
-    if (e == hipSuccess) e = launch_ieee_debug(d_x.get(), n, d_v.get(), m, d_s.get(), d_sf.get(), d_q.get(), d_qf.get());
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess && n) e = d_s.to_host(out_sqrt, n);
-    if (e == hipSuccess && n) e = d_sf.to_host(out_sqrt_short, n);
-    if (e == hipSuccess && m) e = d_q.to_host(out_norm, m * 3);
-    if (e == hipSuccess && m) e = d_qf.to_host(out_norm_short, m);
-    return hook_result(e, "debug_ieee");
-}
-
-// Test hook: ieee_sqrt of every float with bits in [first_bits, first_bits + n), checked on the device.
-int rbrt_hip_selftest_sqrt_sweep(uint32_t first_bits, uint64_t n, uint64_t counts[3]) {
-    if (!counts) return fail(RBRT_ERR_INVALID_ARG, "selftest_sqrt_sweep: null argument");
-    if (first_bits < 0x00800000u || n > uint64_t(0x7F800000u - first_bits))
-        return fail(RBRT_ERR_INVALID_ARG, "selftest_sqrt_sweep: the range must hold positive normal floats only");
-    return device_counts3("selftest_sqrt_sweep", counts, [&](unsigned long long* d) { return launch_sqrt_sweep(first_bits, n, d); });
 }
 
 // Test hook: n scatter events (materials.rs:4-12) on the device functions the shading passes use. Host arrays.

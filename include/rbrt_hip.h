@@ -55,7 +55,8 @@ extern "C" {
                               rbrt_camera_lens_t (rbrt_camera_t stays as it is: the lens wraps it) and
                               rbrt_hip_supported_flags, nor the smooth shading of meshes (rbrt_scene_shading_t and the
                               two *_shaded entry points: rbrt_mesh_t and rbrt_scene_t stay as they are), nor solid patterns
-                              (rbrt_scene_patterns_t and the two *_patterned entry points, detected by the symbol), nor adaptive
+                              (rbrt_scene_patterns_t and the two *_patterned entry points, detected by the symbol), nor the camera shutter (rbrt_shutter_t and
+                              rbrt_hip_scene_set_shutter: handle state like the environment, detected by the symbol), nor adaptive
                               sampling (rbrt_hip_render_adaptive with its two structs: an added entry point), nor the
                               denoiser (rbrt_denoise_opts_t, rbrt_denoise_opts_default, rbrt_hip_denoise_halves and
                               rbrt_hip_scene_denoise: added entry points), nor environment lighting (rbrt_environment_t and
@@ -327,7 +328,8 @@ typedef struct rbrt_hip_scene rbrt_hip_scene_t; /* opaque: device-resident scene
 
 /* Renders the whole image (tile_world ignored unless > 1, then only this rank's tiles are
  * written and all other pixels are left untouched). out_radiance and out_rgb8 are HOST buffers of
- * H*W*3 elements; either may be NULL. */
+ * H*W*3 elements; either may be NULL. The one-shot calls (this one, _render_shaded and _render_patterned) have no
+ * shutter ("Camera shutter", below): the scene they make lives for the call only and nothing can set one on it. */
 int rbrt_hip_render(const rbrt_camera_t* cam, const rbrt_scene_t* scene,
                     const rbrt_render_opts_t* opts, float* out_radiance, uint8_t* out_rgb8);
 /* The same with smooth meshes (rbrt_hip_scene_create_shaded's checks); shading = NULL is rbrt_hip_render. */
@@ -389,7 +391,8 @@ int rbrt_hip_render_device(rbrt_hip_scene_t* scene, const rbrt_camera_t* cam,
  * than H*W*3 when the image has ragged edge tiles; read unless sample_begin == 0). The call with sample_end == opts->spp also
  * writes the mean to d_radiance and its quantisation to d_rgb8 (either may be NULL). Calls must cover [0, spp) in
  * ascending, non-overlapping ranges; the final image is then bit-identical to one rbrt_hip_render_device call,
- * because the per-pixel additions happen in the same order. A checkpoint is d_accum plus sample_end. */
+ * because the per-pixel additions happen in the same order. A checkpoint is d_accum plus sample_end. Every pass of one
+ * series must use the same seed, lens and shutter (rbrt_hip_scene_set_shutter: do not call it between two passes). */
 int rbrt_hip_render_pass(rbrt_hip_scene_t* scene, const rbrt_camera_t* cam, const rbrt_render_opts_t* opts,
                          void* stream, uint32_t sample_begin, uint32_t sample_end, float* d_accum,
                          float* d_radiance, uint8_t* d_rgb8);
@@ -555,6 +558,42 @@ typedef struct rbrt_environment {
  * RBRT_ERR_INVALID_ARG, before the device is touched, the handle keeping the map it had: scene NULL; n == 0 or n > 4096;
  * reserved != 0; nodes NULL; a non-finite or negative component. */
 int rbrt_hip_scene_set_environment(rbrt_hip_scene_t* scene, const rbrt_environment_t* env);
+
+/* ---- Camera shutter: motion blur of a translating camera ------------------------------------------------------------------------
+ * No counterpart in the reference, whose camera is exposed for an instant. A handle may carry a shutter: the vector `travel`
+ * (scene units), the translation of the whole camera -- position and image plane alike -- between the opening and the closing
+ * of the shutter. The `cam` of a render is the camera at the opening.
+ *
+ * The rule. For every sample of a render on such a handle the origin o and the direction d are made exactly as without a
+ * shutter: after the jitter draws, after the lens draws when RBRT_FLAG_THIN_LENS is set, with d = normalize(F - o) computed.
+ * Then, in float32, unfused:
+ *     t   = the next draw of the sample's stream            (u in [0, 1))
+ *     o_c = o_c + (t * travel_c)                            for c = x, y, z
+ * and the bounce draws follow. d is NOT recomputed: a translation does not turn a ray, so d keeps the bits it has without a
+ * shutter. A zero travel still draws (as an all-zero lens does): its image is not the shutterless one. A handle without a
+ * shutter draws nothing and renders bit for bit what it renders without this section. A ray that hits nothing returns a
+ * colour that depends on d only (the background, the gradient, the environment): the pixels of background-only tiles are what
+ * they are without a shutter, and the kernels that finish them make no draw for it. Everything that reads the origin reads
+ * the shifted one: the hit tests, the hit point p = o + t d of a pattern, the shading normal of a smooth mesh, the sphere normal.
+ *
+ * The shutter is a STATE OF THE HANDLE, like the environment. While one is set, rbrt_hip_render_device, _render_pass,
+ * _render_adaptive (and through it rbrt_hip_scene_denoise) and rbrt_hip_render_features honour it, with and without a lens,
+ * for every tile_rank / tile_world; the feature buffers trace the render's own camera rays, the shutter draw included. Every
+ * pass of one rbrt_hip_render_pass series must use the same shutter, as it must use the same seed and lens. There is no flag
+ * bit: a host detects the capability by the symbol. The one-shot rbrt_hip_render, rbrt_hip_render_shaded and
+ * rbrt_hip_render_patterned and rbrt_hip_trace_rays have no shutter. The tile pass widens its margins by |travel| (tables made
+ * for one travel never serve another); a travel longer than the distance to everything in the scene culls nothing. */
+typedef struct rbrt_shutter {
+    float travel[3];   /* scene units; finite */
+    uint32_t reserved; /* 0 */
+} rbrt_shutter_t;
+
+/* Sets, replaces (shutter != NULL) or clears (shutter == NULL: no shutter) the handle's shutter. Nothing is copied to the
+ * device: the travel goes with the launches issued after the call, launches in flight keep theirs. The threading rule of
+ * rbrt_hip_render_device holds.
+ * RBRT_ERR_INVALID_ARG, before the device is touched, the handle keeping the shutter it had: scene NULL; a travel that is not
+ * finite; reserved != 0. */
+int rbrt_hip_scene_set_shutter(rbrt_hip_scene_t* scene, const rbrt_shutter_t* shutter);
 
 /* ---- Display transform: exposure, automatic exposure and tone mapping --------------------------------------------------------
  * No counterpart in the reference, whose only way from radiance to a picture is the quantisation (sqrt(c) * 256) as u8

@@ -103,7 +103,8 @@ int rbrt_hip_debug_guided_staging(int max_step);
  *   out_t[n]      ray parameter of the winning object (NaN on miss)
  *   out_obj[n]    -1 on miss, sphere index in [0,n_spheres), or n_spheres + mesh index
  *   out_tri[n]    winning triangle index (reference numbering) for mesh hits, else -1
- *   out_dist[n]   dist_from_ray_orig of the winner (lib.rs:35)                            */
+ *   out_dist[n]   dist_from_ray_orig of the winner (lib.rs:35)
+ * The rays are traced as given: the handle's shutter (rbrt_hip_scene_set_shutter) does not move them. */
 int rbrt_hip_trace_rays(rbrt_hip_scene_t* scene, const float* rays, size_t n, float min_dist,
                         float max_dist, float* out_t, int32_t* out_obj, int32_t* out_tri,
                         float* out_dist);
@@ -183,6 +184,12 @@ int rbrt_hip_debug_primary_cull(rbrt_hip_scene_t* scene, const rbrt_camera_t* ca
 /* The same table for the camera rays of a RBRT_FLAG_THIN_LENS render with `lens` (kernels.hip primary_cull_kernel, "Lens
  * rays"). The lens is validated like the render entry points' (RBRT_ERR_INVALID_ARG). */
 int rbrt_hip_debug_primary_cull_lens(rbrt_hip_scene_t* scene, const rbrt_camera_lens_t* lens, uint32_t* out_words, size_t n_words);
+/* The same table for the camera rays of a render with the shutter `travel` (rbrt_hip.h "Camera shutter"; kernels.hip
+ * primary_cull_kernel, "Shutter rays"), whatever shutter the handle has, which the hook leaves as it is. cam: the camera;
+ * lens: NULL for a pinhole, else the lens whose `cam` member is used and `cam` is ignored (it may be NULL). The lens is
+ * validated like a render's, the travel like rbrt_hip_scene_set_shutter's (RBRT_ERR_INVALID_ARG). */
+int rbrt_hip_debug_primary_cull_shutter(rbrt_hip_scene_t* scene, const rbrt_camera_t* cam, const rbrt_camera_lens_t* lens,
+                                        const float travel[3], uint32_t* out_words, size_t n_words);
 /* The same table as a render with `opts` computes it: the tree boxes the pass tests are grown by a pad that holds
  * 1 / opts->min_dist, so the table belongs to a distance window. opts->flags are honoured (with RBRT_FLAG_THIN_LENS `cam` is
  * the first member of a rbrt_camera_lens_t, as for a render) and validated like a render's (RBRT_ERR_INVALID_ARG). The two

@@ -99,6 +99,12 @@ pub struct RbrtGlareOpts {                             // rbrt_glare_opts_t: gla
 }
 pub const RBRT_GLARE_MAX_LEVELS: u32 = 8;
 
+#[repr(C)]
+pub struct RbrtShutter {                               // rbrt_shutter_t: the camera's translation while the shutter is open, 16 bytes
+    pub travel: [f32; 3],                              // scene units; finite
+    pub reserved: u32,                                 // 0
+}
+
 #[link(name = "rbrt_hip")]
 extern "C" {
     pub fn rbrt_render_opts_default(opts: *mut RbrtRenderOpts);
@@ -112,6 +118,8 @@ extern "C" {
                                      out_rgb8: *mut u8) -> c_int;
     pub fn rbrt_hip_scene_create_patterned(scene: *const RbrtScene, shading: *const RbrtSceneShading, patterns: *const RbrtScenePatterns,
                                            device: c_int, out: *mut *mut c_void) -> c_int;
+    // the camera shutter: a state of the handle, like the environment; shutter = null clears it. Detected by the symbol (no flag bit)
+    pub fn rbrt_hip_scene_set_shutter(scene: *mut c_void, shutter: *const RbrtShutter) -> c_int;
     // device pointers; needs no scene handle. A host detects it by the symbol (the ABI version stays 2).
     pub fn rbrt_tonemap_opts_default(opts: *mut RbrtTonemapOpts);
     pub fn rbrt_hip_tonemap(device: c_int, stream: *mut c_void, d_radiance: *const f32, n_pixels: usize, opts: *const RbrtTonemapOpts,

@@ -210,6 +210,18 @@ class HipScene:
         env.n, env.reserved = int(n), int(reserved)
         abi.check(self._lib.rbrt_hip_scene_set_environment(self._h, C.byref(env)))
 
+    def set_shutter(self, travel, *, reserved: int = 0):
+        """Sets the handle's shutter (rbrt_hip_scene_set_shutter): `travel` = (dx, dy, dz), the camera's translation during
+        the exposure in scene units; None clears it (no shutter: no draw is made for it). `reserved` puts another value into
+        the struct (tests of the refusals)."""
+        if travel is None:
+            abi.check(self._lib.rbrt_hip_scene_set_shutter(self._h, None))
+            return
+        sh = abi.Shutter()
+        sh.travel[:] = [float(np.float32(v)) for v in travel]
+        sh.reserved = int(reserved)
+        abi.check(self._lib.rbrt_hip_scene_set_shutter(self._h, C.byref(sh)))
+
     def environment_lookup(self, dirs):
         """The environment's radiance for each direction, used as it is (rbrt_hip_debug_environment; test hook): float32
         (n, 3)."""
@@ -355,6 +367,21 @@ class HipScene:
         out = np.zeros(tx * ty, np.uint32)
         abi.check(self._lib.rbrt_hip_debug_primary_cull_lens(self._h, C.byref(lens), out.ctypes.data_as(C.POINTER(C.c_uint32)),
                                                              out.size))
+        return out.reshape(ty, tx)
+
+    def primary_cull_shutter(self, cam, lens, travel):
+        """The same table for the camera rays of `cam` -- with `lens` (None: a pinhole) -- on a handle whose shutter is
+        `travel` (rbrt_hip_debug_primary_cull_shutter; test hook). The handle's own shutter is neither read nor changed."""
+        if lens is not None:
+            if not isinstance(lens, abi.CameraLens):
+                lens = abi.camera_lens(cam, *lens)
+            else:
+                lens = abi.camera_lens(cam, tuple(lens.lens_u), tuple(lens.lens_v), lens.focus_scale)
+        tv = (C.c_float * 3)(*[float(np.float32(v)) for v in travel])
+        tx, ty = (cam.img_width_pix + 7) // 8, (cam.img_height_pix + 7) // 8
+        out = np.zeros(tx * ty, np.uint32)
+        abi.check(self._lib.rbrt_hip_debug_primary_cull_shutter(self._h, C.byref(cam), C.byref(lens) if lens is not None else None, tv,
+                                                                out.ctypes.data_as(C.POINTER(C.c_uint32)), out.size))
         return out.reshape(ty, tx)
 
     def surface_albedo(self, rays, min_dist=0.001, max_dist=2000.0):

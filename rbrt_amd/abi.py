@@ -258,6 +258,11 @@ class Environment(C.Structure):  # rbrt_environment_t
     _fields_ = [("n", C.c_uint32), ("reserved", C.c_uint32), ("nodes", f32p)]
 
 
+class Shutter(C.Structure):  # rbrt_shutter_t
+    """The camera's translation between the opening and the closing of the shutter, in scene units."""
+    _fields_ = [("travel", C.c_float * 3), ("reserved", C.c_uint32)]
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("rays", C.c_uint64),
@@ -336,6 +341,7 @@ HIP_SYMBOLS = {
                                  C.c_void_p]),
     "rbrt_hip_scene_denoise": (C.c_int, [C.c_void_p, C.POINTER(DenoiseOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rbrt_hip_scene_set_environment": (C.c_int, [C.c_void_p, C.POINTER(Environment)]),
+    "rbrt_hip_scene_set_shutter": (C.c_int, [C.c_void_p, C.POINTER(Shutter)]),
     "rbrt_feature_opts_default": (None, [C.POINTER(FeatureOpts)]),
     "rbrt_hip_render_features": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderOpts), C.POINTER(FeatureOpts), C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -392,6 +398,8 @@ DEBUG_SYMBOLS = {
                                         C.POINTER(C.c_uint32)]),
     "rbrt_hip_debug_primary_cull": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(C.c_uint32), C.c_size_t]),
     "rbrt_hip_debug_primary_cull_lens": (C.c_int, [C.c_void_p, C.POINTER(CameraLens), C.POINTER(C.c_uint32), C.c_size_t]),
+    "rbrt_hip_debug_primary_cull_shutter": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(CameraLens), C.POINTER(C.c_float),
+                                                      C.POINTER(C.c_uint32), C.c_size_t]),
     "rbrt_hip_debug_primary_cull_opts": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderOpts), C.POINTER(C.c_uint32), C.c_size_t]),
     "rbrt_hip_scene_helper_launches": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "rbrt_hip_scene_create_times": (C.c_int, [C.c_void_p, C.POINTER(CallTimes)]),
@@ -614,6 +622,10 @@ def load_host() -> C.CDLL:
     lib.rbrt_host_scene_camera.argtypes = [C.c_void_p]
     lib.rbrt_host_scene_lens.restype = C.POINTER(CameraLens)
     lib.rbrt_host_scene_lens.argtypes = [C.c_void_p]
+    lib.rbrt_host_scene_shutter_travel.restype = f32p
+    lib.rbrt_host_scene_shutter_travel.argtypes = [C.c_void_p]
+    lib.rbrt_host_shutter_fingerprint.restype = C.c_uint64
+    lib.rbrt_host_shutter_fingerprint.argtypes = [f32p, C.c_uint64]
     lib.rbrt_host_scene_scene.restype = C.POINTER(Scene)
     lib.rbrt_host_scene_scene.argtypes = [C.c_void_p]
     lib.rbrt_host_scene_shading.restype = C.POINTER(SceneShading)
@@ -680,6 +692,9 @@ class HostScene:
         if lp:
             self.lens = CameraLens()
             C.memmove(C.byref(self.lens), lp, C.sizeof(CameraLens))
+        # the YAML's camera_shutter_travel as a tuple of three floats (what HipScene.set_shutter takes), else None
+        tp = self._lib.rbrt_host_scene_shutter_travel(self._h)
+        self.shutter_travel = (float(tp[0]), float(tp[1]), float(tp[2])) if tp else None
         self.struct = self._lib.rbrt_host_scene_scene(self._h).contents
         sp = self._lib.rbrt_host_scene_shading(self._h)  # NULL unless some mesh is smooth
         self.shading = sp.contents if sp else None
@@ -771,6 +786,15 @@ def environment_fingerprint(nodes, h: int) -> int:
         return int(lib.rbrt_host_environment_fingerprint(None, 0, h))
     nodes = np.ascontiguousarray(nodes, np.float32)
     return int(lib.rbrt_host_environment_fingerprint(fptr(nodes), nodes.shape[0] - 1, h))
+
+
+def shutter_fingerprint(travel, h: int) -> int:
+    """What a shutter adds to the checkpoint fingerprint `h` (rbrt_host_shutter_fingerprint); travel None: no shutter."""
+    lib = load_host()
+    if travel is None:
+        return int(lib.rbrt_host_shutter_fingerprint(None, h))
+    tv = (C.c_float * 3)(*[float(np.float32(v)) for v in travel])
+    return int(lib.rbrt_host_shutter_fingerprint(tv, h))
 
 
 def save_image(path, rgb8: np.ndarray) -> None:

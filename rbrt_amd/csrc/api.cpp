@@ -32,7 +32,7 @@ hipError_t launch_trace_helper(const TraceParams& P, uint32_t n_waves, hipStream
 size_t megakernel_gseq_bytes(uint32_t n_waves);
 size_t megakernel_gstack_bytes(uint32_t n_waves);
 size_t megakernel_lds_bytes(uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris, uint32_t thin_lens,
-                            uint32_t environment, uint32_t pattern_dw);
+                            uint32_t environment, uint32_t pattern_dw, uint32_t shutter);
 int megakernel_occupancy_per_cu(size_t lds_bytes);
 hipError_t launch_primary_cull(const TraceParams& P, hipStream_t stream);
 hipError_t launch_sky_resolve(const TraceParams& P, const ResolveParams& R, hipStream_t stream);
@@ -241,6 +241,10 @@ struct rbrt_hip_scene {
     // dev_release gives back when the map is replaced or cleared; null: rays that hit nothing see opts->bg / the gradient
     EnvTexel* d_env = nullptr;
     uint32_t env_n = 0;
+    // The shutter (rbrt_hip_scene_set_shutter): host state only, it goes with every launch's TraceParams; has_shutter false:
+    // no draw is made for it
+    bool has_shutter = false;
+    float travel[3] = {0.0f, 0.0f, 0.0f};
     // workspace, grown on demand
     // Frame pipeline: consecutive trace launches (the batches of one render, or successive renders) alternate
     // over `pipeline` lanes. Every lane has its own sample buffer, work counters and per-wave scratch, and --
@@ -281,6 +285,8 @@ struct rbrt_hip_scene {
             float min_dist;      // the tree boxes of the pass are grown by a pad that holds 1 / min_dist (TraceParams::eps_frac)
             uint32_t thin_lens;  // RBRT_FLAG_THIN_LENS and its lens (all zero for a pinhole camera)
             float lens_u[3], lens_v[3], focus_scale;
+            uint32_t shutter;    // the handle's shutter when the tables were made (all zero without one): it widens the margins
+            float travel[3];
         };
         struct TileSet {
             uint32_t* d_cull = nullptr;    // [n_tiles]
@@ -932,6 +938,10 @@ int fill_trace_params(const rbrt_hip_scene* s, const rbrt_camera_t* cam, const r
     }
     P.seed_key = host_splitmix64(o->seed);
     P.env_nodes = s->d_env, P.env_n = s->env_n;  // (the handle's state: bg and constant_bg are not read while it is set)
+    if (cam && s->has_shutter) {  // (the handle's state as well; without a camera -- rbrt_hip_trace_rays and the ray hooks -- no shutter)
+        P.shutter = 1u;
+        for (int c = 0; c < 3; ++c) P.travel[c] = s->travel[c];
+    }
     P.n_spheres = s->n_spheres;
     P.n_meshes = s->n_meshes;
     P.n_elem_tris = s->n_elem_tris;
@@ -1456,7 +1466,7 @@ int size_grid(rbrt_hip_scene* s, int device, uint32_t waves_per_cu) {
     if (s->stack_entries > s->stack_need) s->stack_entries = s->stack_need;
     // resident waves per CU: LDS-limited (160 KiB per CU), at most 5 per SIMD (VGPR budget). (A thin-lens launch stages 32
     // bytes more; where that costs it a wave per CU the waves of the grid beyond the resident ones start as others end.)
-    int per_cu = int((160u * 1024u) / megakernel_lds_bytes(s->stack_entries, s->n_spheres, s->n_meshes, s->n_elem_tris, 0u, 0u, pattern_table_dwords(s->n_patterns)));
+    int per_cu = int((160u * 1024u) / megakernel_lds_bytes(s->stack_entries, s->n_spheres, s->n_meshes, s->n_elem_tris, 0u, 0u, pattern_table_dwords(s->n_patterns), 0u));
     if (per_cu > 20) per_cu = 20;
     if (per_cu < 1) per_cu = 1;
     if (waves_per_cu != 0) per_cu = int(waves_per_cu), s->waves_fixed = true;
@@ -1837,13 +1847,16 @@ int ensure_prep_stream(rbrt_hip_scene* s) {
 }
 
 // What a set of tile tables is made for: P's camera, lens (the tables of a lens camera are not those of the pinhole camera
-// it wraps), partition and min_dist, and the order of its work list. Keys are compared with memcmp: hence the memset.
+// it wraps), shutter (a table made for one travel never serves another: its margins hold |travel|), partition and
+// min_dist, and the order of its work list. Keys are compared with memcmp: hence the memset.
 rbrt_hip_scene::Lane::TileKey tile_key(const TraceParams& P, uint32_t list_mode) {
     rbrt_hip_scene::Lane::TileKey k;
     std::memset(&k, 0, sizeof(k));
     k.cam = P.cam, k.rank = P.tile_rank, k.world = P.tile_world, k.list_mode = list_mode, k.min_dist = P.min_dist;
     k.thin_lens = P.thin_lens, k.focus_scale = P.focus_scale;
     for (int c = 0; c < 3; ++c) k.lens_u[c] = P.lens_u[c], k.lens_v[c] = P.lens_v[c];
+    k.shutter = P.shutter;
+    for (int c = 0; c < 3; ++c) k.travel[c] = P.travel[c];
     return k;
 }
 
@@ -2448,6 +2461,25 @@ int rbrt_hip_scene_set_environment(rbrt_hip_scene_t* s, const rbrt_environment_t
     return RBRT_OK;
 }
 
+// The handle's shutter (rbrt_hip.h "Camera shutter"): host state that goes with the TraceParams of every later launch. Under
+// the watcher's lock, as every change of what a launch is made of; launches in flight carry their own copy.
+static int travel_invalid(const float* travel, const char* who) {
+    for (int c = 0; c < 3; ++c)
+        if (!std::isfinite(travel[c])) return fail(RBRT_ERR_INVALID_ARG, std::string(who) + ": travel must be finite");
+    return RBRT_OK;
+}
+int rbrt_hip_scene_set_shutter(rbrt_hip_scene_t* s, const rbrt_shutter_t* shutter) {
+    if (!s) return fail(RBRT_ERR_INVALID_ARG, "set_shutter: null scene");
+    if (shutter) {
+        if (int rc = travel_invalid(shutter->travel, "set_shutter")) return rc;
+        if (shutter->reserved != 0u) return fail(RBRT_ERR_INVALID_ARG, "set_shutter: reserved must be 0");
+    }
+    std::lock_guard<std::mutex> watcher_lock(s->mu);
+    s->has_shutter = shutter != nullptr;
+    for (int c = 0; c < 3; ++c) s->travel[c] = shutter ? shutter->travel[c] : 0.0f;
+    return RBRT_OK;
+}
+
 int rbrt_hip_scene_stats(rbrt_hip_scene_t* s, rbrt_hip_stats_t* out) {
     if (!s || !out) return fail(RBRT_ERR_INVALID_ARG, "stats: null argument");
     HIP_TRY(hipSetDevice(s->device));
@@ -2532,7 +2564,7 @@ int rbrt_hip_scene_info(rbrt_hip_scene_t* s, rbrt_hip_scene_info_t* out) {
     out->bvh_stack_need = s->stack_need;
     out->n_nodes = s->total_nodes, out->n_triangles = s->total_tris;
     out->trace_waves = s->n_waves;
-    out->lds_bytes_per_wave = uint32_t(megakernel_lds_bytes(s->stack_entries, s->n_spheres, s->n_meshes, s->n_elem_tris, 0u, 0u, pattern_table_dwords(s->n_patterns)));
+    out->lds_bytes_per_wave = uint32_t(megakernel_lds_bytes(s->stack_entries, s->n_spheres, s->n_meshes, s->n_elem_tris, 0u, 0u, pattern_table_dwords(s->n_patterns), 0u));
     (void)hipSetDevice(s->device);
     out->occupancy_api_waves_per_cu = uint32_t(megakernel_occupancy_per_cu(out->lds_bytes_per_wave));
     out->n_cus = s->n_cus;
@@ -2767,6 +2799,8 @@ int rbrt_hip_debug_scatter(const rbrt_material_t* mats, const float* in_dir, con
     return hook_result(e, "debug_scatter");
 }
 
+static int primary_cull_table(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, const rbrt_render_opts_t* opts, const float* travel,
+                              uint32_t* out_words, size_t n_words);
 int rbrt_hip_debug_primary_cull(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, uint32_t* out_words, size_t n_words) {
     rbrt_render_opts_t o;
     rbrt_render_opts_default(&o);
@@ -2778,8 +2812,22 @@ int rbrt_hip_debug_primary_cull_lens(rbrt_hip_scene_t* s, const rbrt_camera_lens
     o.flags = RBRT_FLAG_THIN_LENS;
     return rbrt_hip_debug_primary_cull_opts(s, lens ? &lens->cam : nullptr, &o, out_words, n_words);
 }
+int rbrt_hip_debug_primary_cull_shutter(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, const rbrt_camera_lens_t* lens, const float travel[3],
+                                        uint32_t* out_words, size_t n_words) {
+    if (!travel) return fail(RBRT_ERR_INVALID_ARG, "debug_primary_cull_shutter: null travel");
+    if (int rc = travel_invalid(travel, "debug_primary_cull_shutter")) return rc;
+    rbrt_render_opts_t o;
+    rbrt_render_opts_default(&o);
+    if (lens) o.flags = RBRT_FLAG_THIN_LENS;
+    return primary_cull_table(s, lens ? &lens->cam : cam, &o, travel, out_words, n_words);
+}
 int rbrt_hip_debug_primary_cull_opts(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, const rbrt_render_opts_t* opts, uint32_t* out_words,
                                      size_t n_words) {
+    return primary_cull_table(s, cam, opts, nullptr, out_words, n_words);
+}
+// The tile pass's table for `cam` and `opts`, in image order. travel: null = the handle's shutter, if it has one.
+static int primary_cull_table(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, const rbrt_render_opts_t* opts, const float* travel,
+                              uint32_t* out_words, size_t n_words) {
     if (!s || !cam || !opts || !out_words) return fail(RBRT_ERR_INVALID_ARG, "debug_primary_cull: null argument");
     const uint32_t tiles_x = (cam->img_width_pix + RBRT_TILE - 1) / RBRT_TILE, tiles_y = (cam->img_height_pix + RBRT_TILE - 1) / RBRT_TILE;
     if (uint64_t(tiles_x) * tiles_y != n_words || n_words == 0 || n_words > 0xFFFFFFFFull)
@@ -2790,6 +2838,10 @@ int rbrt_hip_debug_primary_cull_opts(rbrt_hip_scene_t* s, const rbrt_camera_t* c
     const rbrt_render_opts_t& o = *opts;  // (the table is the whole image's, whatever the partition)
     TraceParams P;
     fill_trace_params(s, cam, &o, P);
+    if (travel) {
+        P.shutter = 1u;
+        for (int c = 0; c < 3; ++c) P.travel[c] = travel[c];
+    }
     P.tiles_x = tiles_x, P.tiles_y = tiles_y, P.n_tiles = uint32_t(n_words);
     DevBuf<uint32_t> d;
     HIP_TRY(d.alloc(n_words));

@@ -218,6 +218,10 @@ struct TraceParams {
     // RBRT_FLAG_THIN_LENS: thin_lens = 1 and the rbrt_camera_lens_t words past the camera; 0 (pinhole): the lens is never read
     uint32_t thin_lens;
     float lens_u[3], lens_v[3], focus_scale;
+    // The handle's shutter (rbrt_hip_scene_set_shutter): shutter = 1 and the camera's translation during the exposure;
+    // 0 (no shutter): the travel is never read and no draw is made for it
+    uint32_t shutter;
+    float travel[3];
     // The handle's environment (rbrt_hip_scene_set_environment): (env_n + 1)^2 texels of 16 bytes; null: bg / the sky gradient
     const EnvTexel* env_nodes;
     uint32_t env_n;

@@ -33,6 +33,7 @@ __global__ __launch_bounds__(kFeatureBlock) void features_kernel(const TracePara
             lens_point(o, f, lens, rng);
         }
         const V3 d = normalize(f - o);
+        if (P.shutter) shutter_origin(o, P.travel, rng);  // (the render's own camera rays: the handle's shutter moves them too)
         HitRec h;
         LocalCounters lc = {0, 0, 0, 0, 0};
         scene_hit<false>(P, o, d, stack, uint32_t(kFeatureBlock), h, lc);

@@ -762,6 +762,15 @@ __device__ __forceinline__ void lens_point(V3& o, V3& f, const float* lens, Rng&
     f = pos + lens[6] * (f - pos);
 }
 constexpr uint32_t kLensDw = 8;  // lens words staged in the megakernel's LDS for a lens launch: lens_u, lens_v, focus_scale, pad
+// The shutter (rbrt_hip.h "Camera shutter"): after the ray (o, d) of a sample has been made -- jitter,
+// lens and normalize(f - o) included -- the next draw of its stream places the whole camera on its way from the opening to
+// the closing position: o += t * travel, unfused, a product and a sum per component. d is NOT recomputed: a translation
+// does not turn a ray. The bounce draws follow. A ray that hits nothing depends on d only, so the sky resolves never call this.
+__device__ __forceinline__ void shutter_origin(V3& o, const float* travel, Rng& rng) {
+    const float t = rng.next_f32();
+    o = o + t * mk(travel);
+}
+constexpr uint32_t kShutterDw = 4;  // words staged in the megakernel's LDS for a shutter launch: travel, pad
 
 // lib.rs:68-71: what a ray that hits nothing sees; the direction as it is (not re-normalised).
 // `constant` (RBRT_FLAG_CONSTANT_BACKGROUND): bg itself.
@@ -801,7 +810,7 @@ __device__ __noinline__ V3 environment_radiance_call(const EnvTexel* nodes, uint
 constexpr uint32_t kEnvDw = 4;  // words staged in the megakernel's LDS for a launch with a map: the address (2), n, pad
 
 __host__ __device__ inline uint32_t megakernel_lds_dwords(uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris,
-                                                          uint32_t thin_lens, uint32_t environment, uint32_t pattern_dw);
+                                                          uint32_t thin_lens, uint32_t environment, uint32_t pattern_dw, uint32_t shutter);
 #include "megakernel.inl"
 
 // lib.rs:116-122: (sqrt(c) * 256) as u8 — Rust's float->int cast saturates and maps NaN to 0.
@@ -1020,6 +1029,27 @@ __global__ __launch_bounds__(kSmallBlock) void sky_resolve_kernel(const TracePar
 // |F - o| >= focus_scale plane_dist - a replaces the pinhole's `angle`. With a >= focus_scale plane_dist (the lens may
 // reach the focus surface), or a NaN anywhere, the angle is NaN and nothing is culled. For a pinhole a = beta = 0 and
 // every rule is the one above, bit for bit.
+//
+// Shutter rays (rbrt_hip.h "Camera shutter"; TraceParams::shutter). A shutter ray is a pinhole or lens ray (o, d) whose origin
+// moves to o' = o + t travel, 0 <= t < 1, and whose direction stays d, bit for bit. Two kinds of quantity used `a` above, and
+// the shutter touches one of them only:
+//   the ORIGIN's distance from the position: |o' - position| <= a + |travel|. In float, t travel_c is one rounding (at most
+//     u |travel|) and the sum another (at most u (|o| + |travel|)); 16 u (|position| + a + |travel|), the lens's own u16 term,
+//     covers both many times over. That is `org_a` = a + |travel| + 16 u (|position| + a + |travel|). It takes a's place
+//     wherever a stood for where a ray STARTS: the radii R_out + org_a and R_in - org_a, the slabs' reach and
+//     box_unreachable's (org_a + w (l + r + org_a), org_a + w (far + org_a): a point of the line o' + s d is within
+//     org_a + |s| sin w of the line through the position with a direction of the tile's cone, as before), the box's bounding
+//     sphere, and the float-error slacks that hold the origin's distance from the object (the sphere test's, the box test's,
+//     the tree pad, whose |o|_inf grows by org_a).
+//   the DIRECTION's angle to the tile's pinhole directions: beta = asin(a / (focus_scale plane_dist)) and the float error
+//     `angle` of normalize(F - o), with |F - o| >= focus_scale plane_dist - a. d is the unshuttered ray's, so these keep `a`
+//     (`lens_a`): the shutter widens neither the cone nor the deep-cut caps nor w. For a pinhole with a shutter beta = 0 and
+//     `angle` is the pinhole's.
+// The argument for backward lines is the lens's: a line from o' cuts (misses) the ball as a line from the position cuts (misses)
+// the ball moved by position - o', which contains the ball of radius R - org_a (lies inside the one of radius R + org_a) around
+// the same centre; the forward rule R_out < l keeps every origin outside the sphere. Without a shutter org_a = a exactly (the
+// branch is not taken) and every rule is the one above, bit for bit. A travel so long that R_out >= l for every object, or
+// a NaN, makes every comparison false: nothing is culled.
 // ---------------------------------------------------------------------------------------------
 struct D3 {
     double x, y, z;
@@ -1128,6 +1158,14 @@ __global__ __launch_bounds__(kCullBlock, 4) void primary_cull_kernel(const Trace
         lens_beta = sb / sqrt(1.0 - sb * sb);  // tan beta >= beta (no asin: its code cost the pass VGPR spills)
         if (!(sb < 1.0) || !(lens_beta == lens_beta)) angle = __builtin_nan("");  // (nothing is culled)
     }
+    // Shutter rays (header, "Shutter rays"): org_a bounds the distance of a ray's origin from the position, lens_a goes on
+    // bounding what enters its direction. Without a shutter they are the same number.
+    double org_a = lens_a;
+    if (P.shutter) {
+        const double tl = dlen(d3(P.travel));
+        org_a = lens_a + tl + 16.0 * (1.0 / 16777216.0) * (dlen(pos) + lens_a + tl);
+        if (!(org_a == org_a)) angle = __builtin_nan("");  // (nothing is culled)
+    }
     CullSlab cols, rows;
     cols.n_lo = unit_or_nan(dcross(a + (0.001 * cm0) * right, up));
     cols.n_hi = unit_or_nan(dcross(a + (0.001 * cm1) * right, up));
@@ -1160,10 +1198,10 @@ __global__ __launch_bounds__(kCullBlock, 4) void primary_cull_kernel(const Trace
             const double r = double(sp.radius), l = dlen(q);
             if (r > 0.0 && r < 1e30 && l < 1e30) {  // (false for NaN)
                 // (the second term is the analysed one, 15x the bound in the header; the others are loose change on top)
-                const double lo = l + lens_a;  // (the distance of a ray's origin from the centre)
+                const double lo = l + org_a;  // (the distance of a ray's origin from the centre)
                 const double slack = 1e-5 * r + 1e-5 * (lo * lo + r * r) / r + 1e-6 * lo;
-                const double reach = r + slack + lens_a + w_dir * (l + r + lens_a);
-                const double r_out = r + slack + lens_a, r_in = r - slack - lens_a;
+                const double reach = r + slack + org_a + w_dir * (l + r + org_a);
+                const double r_out = r + slack + org_a, r_in = r - slack - org_a;
                 const D3 qhat = (1.0 / l) * q;
                 out = cols.outside(q, reach) || rows.outside(q, reach) ||
                       (cone.misses(qhat, l, r_out, 1.0) && (cone.misses(qhat, l, r_out, -1.0) || cone.backward_deep(qhat, l, r_in)));
@@ -1176,8 +1214,8 @@ __global__ __launch_bounds__(kCullBlock, 4) void primary_cull_kernel(const Trace
     const auto box_unreachable = [&](D3 lo, D3 hi, double slack, double far) -> bool {
         const D3 q = 0.5 * (lo + hi) - pos;
         const double l = dlen(q);
-        if (cone.misses((1.0 / l) * q, l, 0.5 * dlen(hi - lo) * 1.001 + slack + lens_a, 1.0)) return true;
-        const double reach = slack + lens_a + w_dir * (far + lens_a);
+        if (cone.misses((1.0 / l) * q, l, 0.5 * dlen(hi - lo) * 1.001 + slack + org_a, 1.0)) return true;
+        const double reach = slack + org_a + w_dir * (far + org_a);
         for (uint32_t slab = 0; slab < 2u; ++slab) {
             const CullSlab& sl = slab ? rows : cols;
             bool pos_side = true, neg_side = true;
@@ -1211,7 +1249,7 @@ __global__ __launch_bounds__(kCullBlock, 4) void primary_cull_kernel(const Trace
         // skip a NaN, and an axis whose line runs outside its slab gives t_min = +inf or t_max = -inf: a miss, as in
         // geometry.) The slack is 16 u far, three times that bound; the angle between the float ray and the exact
         // line of its pixel is added on top by box_unreachable (angle * far). Round 3 had a chosen 1e-4 far here.
-        const double slack = 16.0 * (1.0 / 16777216.0) * (far + lens_a);
+        const double slack = 16.0 * (1.0 / 16777216.0) * (far + org_a);
         const bool out = finite && box_unreachable(d3(md.bbox_lo), d3(md.bbox_hi), slack, far);
         if (out) word |= 1u << (24u + m);
         // A ray may pass the mesh's box and still have no triangle to hit: the tile is free of the mesh as well when
@@ -1225,7 +1263,7 @@ __global__ __launch_bounds__(kCullBlock, 4) void primary_cull_kernel(const Trace
         // of whose rays enters a grown box of some level takes no triangle below it.
         const D3 mc = d3(md.center) - pos;
         const double o_inf = fmax(fmax(fabs(pos.x), fabs(pos.y)), fabs(pos.z));
-        const double pad_base = 64.0 * (1.0 / 16777216.0) * (dlen(mc) + double(md.radius) + o_inf + lens_a);
+        const double pad_base = 64.0 * (1.0 / 16777216.0) * (dlen(mc) + double(md.radius) + o_inf + org_a);
         bool mesh_free = out;
         if (!out && all && finite && md.n_nodes != 0u) {  // (only where the answer matters: nothing else is in reach so far)
             constexpr uint32_t kCullLevels = 6;
@@ -1827,12 +1865,13 @@ size_t megakernel_gseq_bytes(uint32_t n_waves) { return size_t(n_waves) * kPool 
 size_t megakernel_gstack_bytes(uint32_t n_waves) { return size_t(n_waves) * kStackMax * 64u * sizeof(uint32_t); }
 
 __host__ __device__ inline uint32_t megakernel_lds_dwords(uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris,
-                                                          uint32_t thin_lens, uint32_t environment, uint32_t pattern_dw) {
+                                                          uint32_t thin_lens, uint32_t environment, uint32_t pattern_dw, uint32_t shutter) {
     const uint32_t n_elem = n_spheres + n_elem_tris;
     const uint32_t scene = n_spheres * kSphDw + (n_elem + n_meshes) * kMatDw + n_meshes * kMeshDw + kGenDw +
                            pattern_dw +                                                // second entries and DevPatterns (nothing without patterns)
                            (thin_lens ? kLensDw : 0u) +                                // a lens launch's lens (nothing for a pinhole)
                            (environment ? kEnvDw : 0u) +                               // the map's address and size (nothing without one)
+                           (shutter ? kShutterDw : 0u) +                               // a shutter launch's travel (nothing without a shutter)
                            (n_elem_tris != 0u ? n_elem_tris * kTriDw + n_elem : 0u);  // triangle table + element order
     const uint32_t pool_pad = (uint32_t(kPool) + 63u) & ~63u;  // status + list: one byte per (padded) slot each
     uint32_t dw = uint32_t(kFields * kPool) + kCellDw + kTqDw + kHelpDw + pool_pad / 2u + stack_entries * 64u + scene;
@@ -1840,8 +1879,8 @@ __host__ __device__ inline uint32_t megakernel_lds_dwords(uint32_t stack_entries
     return dw;
 }
 size_t megakernel_lds_bytes(uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris, uint32_t thin_lens,
-                            uint32_t environment, uint32_t pattern_dw) {
-    return size_t(megakernel_lds_dwords(stack_entries, n_spheres, n_meshes, n_elem_tris, thin_lens, environment, pattern_dw)) * sizeof(uint32_t);
+                            uint32_t environment, uint32_t pattern_dw, uint32_t shutter) {
+    return size_t(megakernel_lds_dwords(stack_entries, n_spheres, n_meshes, n_elem_tris, thin_lens, environment, pattern_dw, shutter)) * sizeof(uint32_t);
 }
 
 // What the HIP runtime says fits: resident single-wave workgroups of the trace kernel per CU at this much LDS (0 on error).
@@ -1857,14 +1896,14 @@ int megakernel_occupancy_per_cu(size_t lds_bytes) {
 // (work counters, sample buffer, tables), scratch slots from P.wave_base on.
 hipError_t launch_trace_helper(const TraceParams& P, uint32_t n_waves, hipStream_t stream) {
     if (P.n_items == 0 || n_waves == 0 || !P.helper_words) return hipSuccess;
-    const size_t lds = megakernel_lds_bytes(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris, P.thin_lens, P.env_nodes ? 1u : 0u, P.pattern_dw);
+    const size_t lds = megakernel_lds_bytes(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris, P.thin_lens, P.env_nodes ? 1u : 0u, P.pattern_dw, P.shutter);
     hipLaunchKernelGGL((trace_megakernel<false, true>), dim3(n_waves), dim3(64), lds, stream, P);
     return hipGetLastError();
 }
 
 hipError_t launch_trace_megakernel(const TraceParams& P, uint32_t n_waves, bool stats, hipStream_t stream) {
     if (P.n_items == 0 || n_waves == 0) return hipSuccess;
-    const size_t lds = megakernel_lds_bytes(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris, P.thin_lens, P.env_nodes ? 1u : 0u, P.pattern_dw);
+    const size_t lds = megakernel_lds_bytes(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris, P.thin_lens, P.env_nodes ? 1u : 0u, P.pattern_dw, P.shutter);
     if (stats)
         hipLaunchKernelGGL((trace_megakernel<true>), dim3(n_waves), dim3(64), lds, stream, P);
     else

@@ -265,7 +265,7 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
     // (the accumulators sit at the very end of the workgroup's LDS: megakernel_lds_bytes adds room for them)
     // (u32: a wave spends at most a few million cycles in a region per launch; 76 bytes fit the slack of the product's
     // allocation granule, so this build keeps the product's 16 workgroups per CU)
-    uint32_t* const rt_acc = lds + (megakernel_lds_dwords(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris, P.thin_lens, P.env_nodes ? 1u : 0u, P.pattern_dw) - uint32_t(kNumRegions));
+    uint32_t* const rt_acc = lds + (megakernel_lds_dwords(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris, P.thin_lens, P.env_nodes ? 1u : 0u, P.pattern_dw, P.shutter) - uint32_t(kNumRegions));
     if (lane < uint32_t(kNumRegions)) rt_acc[lane] = 0u;
     unsigned long long rt_prev = __builtin_amdgcn_s_memtime();
     const unsigned long long rt_wall0 = __builtin_amdgcn_s_memrealtime();  // 100 MHz, the same clock on every CU
@@ -365,6 +365,13 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                 const uint64_t addr = reinterpret_cast<uint64_t>(P.env_nodes);
                 dst[ea] = uint32_t(addr), dst[ea + 1] = uint32_t(addr >> 32), dst[ea + 2] = P.env_n, dst[ea + 3] = 0u;
                 dst[G_FLAGS] = (dst[G_FLAGS] & 0xFFu) | (at << 8);
+            }
+            if (P.shutter) {  // the same way, behind the lens and the map: the travel, announced by bit 4 (nothing without a shutter)
+                const uint32_t at = kGenDw + (P.n_elem_tris != 0u ? P.n_elem_tris * kTriDw + n_elem : 0u);
+                const uint32_t sa = at + (P.thin_lens ? kLensDw : 0u) + (P.env_nodes ? kEnvDw : 0u);
+                for (int c = 0; c < 3; ++c) gf[sa + c] = P.travel[c];
+                dst[sa + 3] = 0u;
+                dst[G_FLAGS] = (dst[G_FLAGS] & 0xFFu) | 16u | (at << 8);
             }
             dst[G_SAMPLE_BASE] = P.sample_base, dst[G_MAX_DEPTH] = P.max_depth;
             dst[G_SEED_LO] = uint32_t(P.seed_key), dst[G_SEED_HI] = uint32_t(P.seed_key >> 32);
@@ -975,6 +982,8 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                             if (gen_flags & 4u)  // RBRT_FLAG_THIN_LENS (the same for every lane): the lens words at dword gen_flags >> 8
                                 lens_point(o, f, gpf + (gen_flags >> 8), rng);
                             d = normalize(f - o);
+                            if (gen_flags & 16u)  // the handle's shutter (the same for every lane): the travel behind the lens and the map
+                                shutter_origin(o, gpf + (gen_flags >> 8) + ((gen_flags & 4u) ? kLensDw : 0u) + ((gen_flags & 8u) ? kEnvDw : 0u), rng);
                             depth = gp[G_MAX_DEPTH];
                             nrec = 0;
                             word = 0;

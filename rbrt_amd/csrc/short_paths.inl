@@ -86,6 +86,7 @@ __device__ __forceinline__ bool short_path_sample(const TraceParams& P, const Sc
                          img_h, row, col, rng);
     if (P.thin_lens) lens_point(o, f, lens, rng);
     V3 d = normalize(f - o);
+    if (P.shutter) shutter_origin(o, P.travel, rng);
     uint32_t depth = P.max_depth;
     float closest, ht;
     int32_t obj;

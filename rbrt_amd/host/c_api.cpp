@@ -4,6 +4,7 @@
 #include <cstring>
 #include <string>
 
+#include "checkpoint.hpp"
 #include "rbrt.hpp"
 #include "yaml_lite.hpp"
 
@@ -66,6 +67,8 @@ struct rbrt_host_scene {
     rbrt::Scene::AbiView view;
     rbrt_camera_t cam_abi;
     rbrt_camera_lens_t lens_abi;
+    bool shutter = false;
+    float travel[3] = {0.0f, 0.0f, 0.0f};
 };
 
 extern "C" {
@@ -83,6 +86,7 @@ int rbrt_host_scene_load(const char* yaml_path, uint32_t height, uint32_t width,
         h->view = h->scene.to_abi();
         h->cam_abi = h->cam.to_abi();
         h->lens_abi = h->cam.to_abi_lens();
+        if (const auto& tr = bp.camera_blueprint.camera_shutter_travel) h->shutter = true, h->travel[0] = tr->x, h->travel[1] = tr->y, h->travel[2] = tr->z;
         *out = h;
         return 0;
     } catch (const std::exception& e) {
@@ -93,6 +97,8 @@ int rbrt_host_scene_load(const char* yaml_path, uint32_t height, uint32_t width,
 const rbrt_camera_t* rbrt_host_scene_camera(const rbrt_host_scene* h) { return &h->cam_abi; }
 // The camera with its thin lens (camera_aperture_mm > 0), or NULL for a pinhole camera.
 const rbrt_camera_lens_t* rbrt_host_scene_lens(const rbrt_host_scene* h) { return h->cam.thin_lens ? &h->lens_abi : nullptr; }
+// The scene's camera_shutter_travel (three floats, what rbrt_shutter_t::travel takes), or NULL when it has none.
+const float* rbrt_host_scene_shutter_travel(const rbrt_host_scene* h) { return h->shutter ? h->travel : nullptr; }
 const rbrt_scene_t* rbrt_host_scene_scene(const rbrt_host_scene* h) { return &h->view.scene; }
 // The corner normals of the smooth meshes (YAML `shading: smooth`), or NULL when every mesh is flat.
 const rbrt_scene_shading_t* rbrt_host_scene_shading(const rbrt_host_scene* h) { return h->view.shading_ptr(); }
@@ -162,6 +168,9 @@ uint64_t rbrt_host_environment_fingerprint(const float* nodes, uint32_t n, uint6
     if (nodes && n) e.n = n, e.nodes.assign(nodes, nodes + size_t(n + 1) * (n + 1) * 3);
     return rbrt::environment_fingerprint(e, h);
 }
+
+// What a shutter adds to a checkpoint's fingerprint `h` (travel NULL: none, h itself).
+uint64_t rbrt_host_shutter_fingerprint(const float* travel, uint64_t h) { return rbrt::shutter_fingerprint(travel, h); }
 
 int rbrt_host_write_png(const char* path, const uint8_t* rgb, uint32_t width, uint32_t height) {
     try {

@@ -64,7 +64,7 @@ uint64_t patterns_fingerprint(const rbrt_scene_patterns_t* pt, uint64_t h) {
 }  // namespace
 
 uint64_t checkpoint_fingerprint(const std::string& path, const rbrt_camera_lens_t& lens, const rbrt_render_opts_t& opts, const rbrt_scene_t& sc,
-                                const rbrt_scene_shading_t* sh, const Environment& env, const rbrt_scene_patterns_t* pt) {
+                                const rbrt_scene_shading_t* sh, const Environment& env, const rbrt_scene_patterns_t* pt, const float* travel) {
     if (path.empty()) return 0;
     uint64_t h = patterns_fingerprint(pt, shading_fingerprint(sc, sh, scene_fingerprint(lens.cam, sc)));
     if (opts.flags & RBRT_FLAG_CONSTANT_BACKGROUND) {
@@ -80,7 +80,14 @@ uint64_t checkpoint_fingerprint(const std::string& path, const rbrt_camera_lens_
         h = fnv1a(lens.lens_v, sizeof(lens.lens_v), h);
         h = fnv1a(&lens.focus_scale, sizeof(lens.focus_scale), h);
     }
-    return h;
+    return shutter_fingerprint(travel, h);
+}
+
+uint64_t shutter_fingerprint(const float* travel, uint64_t h) {
+    if (!travel) return h;
+    const char tag[8] = {'s', 'h', 'u', 't', 't', 'e', 'r', 0};
+    h = fnv1a(tag, sizeof(tag), h);
+    return fnv1a(travel, 3 * sizeof(float), h);
 }
 
 CheckpointHeader checkpoint_header(uint32_t width, uint32_t height, uint32_t spp, uint32_t world, uint64_t seed, uint64_t fingerprint) {

@@ -111,6 +111,13 @@ void usage() {
         "                                   --denoise-guided filter the accumulated image; --feature-samples applies\n"
         "      --camera-step <dx,dy,dz>     frames: frame k's camera position and image centre are moved by k times this\n"
         "                                   [default: 0,0,0]\n"
+        "      --shutter-travel <dx,dy,dz>  a camera shutter: the whole camera moves by this, in scene units, while a frame is exposed\n"
+        "                                   (motion blur of a translating camera); every sample starts somewhere on the way. Overrides\n"
+        "                                   the YAML's camera_shutter_travel; works with --gpus, --adaptive, --features, --upscale,\n"
+        "                                   --pass-samples and --checkpoint (a checkpoint resumes only with the same travel)\n"
+        "      --shutter <s>                frames: the travel is s times --camera-step, s 0 or more (0.5: open for half the step);\n"
+        "                                   frame k still opens at k times the step, and the accumulation reprojects through the\n"
+        "                                   opening cameras. Needs --camera-step; not together with --shutter-travel\n"
         "      --temporal-max-history <m>   frames: the longest history a pixel keeps, at least 1 [default: 32]\n"
         "      --temporal-depth <k>         frames: tolerance of the relative depth difference, 0 or more [default: 0.05]\n"
         "      --temporal-normal <k>        frames: tolerance of the normal's difference, 0 or more [default: 0.35]\n"
@@ -281,6 +288,9 @@ int main(int argc, char** argv) {
     std::optional<float> temporal_max_history, temporal_depth, temporal_normal;
     float camera_step[3] = {0.0f, 0.0f, 0.0f};
     bool camera_step_given = false;
+    std::optional<float> shutter;  // --shutter S: the travel is S * camera_step
+    float shutter_travel[3] = {0.0f, 0.0f, 0.0f};
+    bool shutter_travel_given = false;
     std::string history_map;
     std::optional<uint32_t> upscale;  // --upscale turns guided upsampling on; the options below need it
     std::optional<float> upscale_normal, upscale_depth, upscale_albedo;
@@ -537,6 +547,21 @@ int main(int argc, char** argv) {
                 return 2;
             }
             camera_step_given = true;
+        } else if (a == "--shutter-travel") {
+            const char* v = value();
+            if (!parse_vec3(v, shutter_travel)) {
+                std::fprintf(stderr, "error: invalid value '%s' for '--shutter-travel' (expected DX,DY,DZ: three finite numbers)\n", v);
+                return 2;
+            }
+            shutter_travel_given = true;
+        } else if (a == "--shutter") {
+            const char* v = value();
+            float f = 0.0f;
+            if (!parse_f32(v, f) || !std::isfinite(f) || !(f >= 0.0f)) {
+                std::fprintf(stderr, "error: invalid value '%s' for '--shutter' (expected a finite number >= 0: the part of a frame's camera step the shutter is open for)\n", v);
+                return 2;
+            }
+            shutter = f + 0.0f;
         } else if (a == "--temporal-max-history" || a == "--temporal-depth" || a == "--temporal-normal") {
             const bool history = a == "--temporal-max-history";
             const char* v = value();
@@ -689,6 +714,22 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "error: '%s' needs '--frames'\n", alone);
             return 2;
         }
+    }
+    if (shutter && shutter_travel_given) {
+        std::fprintf(stderr, "error: '--shutter' cannot be combined with '--shutter-travel' (either is the whole travel)\n");
+        return 2;
+    }
+    if (shutter && !camera_step_given) {
+        std::fprintf(stderr, "error: '--shutter' needs '--camera-step' (the travel is that part of the step; '--shutter-travel' takes a travel itself)\n");
+        return 2;
+    }
+    if (shutter) {  // travel = S * camera_step, float32
+        for (int c = 0; c < 3; ++c) shutter_travel[c] = *shutter * camera_step[c];
+        for (int c = 0; c < 3; ++c)
+            if (!std::isfinite(shutter_travel[c])) {
+                std::fprintf(stderr, "error: '--shutter' times '--camera-step' is not finite\n");
+                return 2;
+            }
     }
     if (upscale) {  // a small render through one round of the adaptive path on one handle: refused by name before anything is loaded
         const char* with = adaptive ? "--adaptive" : gpus > 1 ? "--gpus > 1" : !checkpoint.empty() ? "--checkpoint" : pass_samples != 0 ? "--pass-samples"
@@ -848,6 +889,12 @@ int main(int argc, char** argv) {
             cfg.tonemap = true, cfg.tonemap_curve = tone_curve, cfg.tonemap_exposure = exposure, cfg.tonemap_key = exposure_key;
             cfg.tonemap_white = white ? *white : 0.0f;
         }
+        if (shutter || shutter_travel_given) {  // (the flags override the YAML's camera_shutter_travel)
+            cfg.shutter = true;
+            for (int c = 0; c < 3; ++c) cfg.shutter_travel[c] = shutter_travel[c];
+        } else if (const auto& tr = bp.camera_blueprint.camera_shutter_travel) {
+            cfg.shutter = true, cfg.shutter_travel[0] = tr->x, cfg.shutter_travel[1] = tr->y, cfg.shutter_travel[2] = tr->z;
+        }
         if (frames) {
             cfg.frames = *frames;
             for (int c = 0; c < 3; ++c) cfg.camera_step[c] = camera_step[c];
@@ -969,6 +1016,15 @@ int main(int argc, char** argv) {
                 for (int c = 0; c < 3; ++c) {
                     char b[32];
                     std::snprintf(b, sizeof(b), "%s%.9g", c ? ", " : "", double(cfg.camera_step[c]));
+                    js += b;
+                }
+                js += "], ";
+            }
+            if (cfg.shutter) {  // the camera's translation while the shutter was open
+                js += "\"shutter_travel\": [";
+                for (int c = 0; c < 3; ++c) {
+                    char b[32];
+                    std::snprintf(b, sizeof(b), "%s%.9g", c ? ", " : "", double(cfg.shutter_travel[c]));
                     js += b;
                 }
                 js += "], ";

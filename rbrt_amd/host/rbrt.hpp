@@ -124,6 +124,9 @@ struct CameraBluePrint {
     float camera_focal_length_mm = 0;
     std::optional<float> camera_aperture_mm;     // lens diameter in mm; absent or 0: pinhole
     std::optional<float> camera_focus_distance;  // scene units from the position to the focus plane, along look_at
+    // `camera_shutter_travel: [dx, dy, dz]` (not in the reference): the camera's translation while the shutter is open, in
+    // scene units (include/rbrt_hip.h "Camera shutter"); absent: no shutter
+    std::optional<Vec3> camera_shutter_travel;
 };
 // Camera::create from a blueprint, with its lens (Camera::set_lens) when the blueprint has an aperture.
 Camera camera_from_blueprint(const CameraBluePrint& bp, uint32_t img_height_pix, uint32_t img_width_pix);
@@ -386,6 +389,12 @@ struct RenderConfig {  // additions that the reference hard-codes or lacks
     // `adaptive` itself; num_samples must be at least 2. 0: one frame without any of this.
     uint32_t frames = 0;
     float camera_step[3] = {0.0f, 0.0f, 0.0f};
+    // The camera shutter (rbrt_hip_scene_set_shutter; the YAML's camera_shutter_travel, the CLI's --shutter-travel and
+    // --shutter): every rank's handle gets it, so every frame, pass and round and the feature buffers are exposed while the
+    // camera moves by shutter_travel. With --frames, frame k opens at k * camera_step as without a shutter, and the
+    // accumulation reprojects through the frames' opening cameras.
+    bool shutter = false;
+    float shutter_travel[3] = {0.0f, 0.0f, 0.0f};
     float temporal_max_history = 32.0f, temporal_depth = 0.05f, temporal_normal = 0.35f;  // (rbrt_temporal_opts_default)
     // Guided upsampling (rbrt_hip_upsample_halves; the CLI's --upscale, --upscale-*): the image is traced with the low camera of
     // rbrt_hip_upsample_camera (1 / upscale of the size in each direction) through the adaptive path's one round that stops

@@ -341,6 +341,9 @@ Plan make_plan(const RenderConfig& cfg, const std::string& adaptive_by, bool cfg
             if (!std::isfinite(k) || !(k > 0.0f)) throw Error("--guided-colour, --guided-normal, --guided-depth and --guided-albedo must be finite and above 0");
         if (cfg.feature_samples == 0 || cfg.feature_samples > 65536u) throw Error("--feature-samples must be 1 to 65536");
     }
+    if (cfg.shutter)
+        for (const float s : cfg.shutter_travel)
+            if (!std::isfinite(s)) throw Error("the shutter's travel must be three finite numbers");
     if (cfg.frames) {  // (rbrt_hip.h "Temporal accumulation": every frame is one round of the adaptive path on one handle)
         if (cfg_adaptive_given) throw Error("--frames cannot be combined with --adaptive");
         if (num_samples < 2) throw Error("--frames needs at least 2 samples (each half image needs one)");
@@ -582,6 +585,11 @@ void Rank::setup() {
     // the library's default of eight is for streams of frames)
     (void)rbrt_hip_scene_set_pipeline(hs, 3);
     if (job.env) err.lib_ok(rbrt_hip_scene_set_environment(hs, job.env));  // (every rank's handle)
+    if (cfg.shutter) {  // (every rank's handle as well: every pass, round and frame and the feature buffers read it from there)
+        rbrt_shutter_t sht{};
+        for (int c = 0; c < 3; ++c) sht.travel[c] = cfg.shutter_travel[c];
+        err.lib_ok(rbrt_hip_scene_set_shutter(hs, &sht));
+    }
     rbrt_hip_scene_info_t info;
     if (rank == 0 && rbrt_hip_scene_info(hs, &info) == RBRT_OK) {
         sh.rep.bvh_nodes = info.n_nodes, sh.rep.bvh_triangles = info.n_triangles;
@@ -826,7 +834,9 @@ void Rank::temporal() {
             lens.cam.position[c] = job.lens.cam.position[c] + shift;
             lens.cam.img_center_point[c] = job.lens.cam.img_center_point[c] + shift;
         }
-        rbrt_camera_lens_t traced = lens;  // (the low camera keeps the lens: lens_u, lens_v and focus_scale)
+        // (with a shutter -- the handle's state, Rank::setup -- frame k is exposed from this camera on, over cfg.shutter_travel; the
+        // accumulation below reprojects through these opening cameras, as it does without one)
+        rbrt_camera_lens_t traced = lens;  // (the low camera keeps the lens: lens_u, lens_v and focus_scale; the travel is in scene units and stays, too)
         if (factor && !err.lib_ok(rbrt_hip_upsample_camera(&lens.cam, factor, &traced.cam))) break;
         rep.render_width = traced.cam.img_width_pix, rep.render_height = traced.cam.img_height_pix;
         rbrt_render_opts_t ok = o;
@@ -1094,7 +1104,8 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
                                 cam, scene, num_samples);
     Job job{cfg, plan, lens, view, scene.environment.n != 0u ? &env_abi : nullptr, render_opts_of(cfg, cam, num_samples), num_samples, {}, {}, img};
     job.want = checkpoint_header(img.width, img.height, num_samples, uint32_t(plan.world), cfg.seed,
-                                 checkpoint_fingerprint(cfg.checkpoint_path, lens, job.opts, view.scene, view.shading_ptr(), scene.environment, view.patterns_ptr()));
+                                 checkpoint_fingerprint(cfg.checkpoint_path, lens, job.opts, view.scene, view.shading_ptr(), scene.environment, view.patterns_ptr(),
+                                                        cfg.shutter ? cfg.shutter_travel : nullptr));
     job.resume = resume_from_checkpoint(job);
     Shared sh(plan);
     bring_up_rccl(plan, sh);

@@ -329,6 +329,19 @@ SceneBlueprint load_blueprints_from_yaml_text(const std::string& text) {
         as_f32(need(cam, "camera_focal_length_mm", "camera_blueprint"), "camera_focal_length_mm");
     bp.camera_blueprint.camera_aperture_mm = opt_f32(cam, "camera_aperture_mm", "camera_aperture_mm");
     bp.camera_blueprint.camera_focus_distance = opt_f32(cam, "camera_focus_distance", "camera_focus_distance");
+    if (const Node* tr = cam.find("camera_shutter_travel"); tr && !tr->is_null()) {  // [dx, dy, dz], or x / y / z like the other vectors
+        Vec3 v;
+        if (tr->kind == Node::List) {
+            if (tr->list.size() != 3) throw Error("camera_shutter_travel: expected [dx, dy, dz], three numbers");
+            v = Vec3(as_f32(tr->list[0], "camera_shutter_travel"), as_f32(tr->list[1], "camera_shutter_travel"),
+                     as_f32(tr->list[2], "camera_shutter_travel"));
+        } else {
+            v = as_vec3(*tr, "camera_shutter_travel");
+        }
+        if (!std::isfinite(v.x) || !std::isfinite(v.y) || !std::isfinite(v.z))
+            throw Error("camera_shutter_travel must be three finite numbers (the camera's translation during the exposure)");
+        bp.camera_blueprint.camera_shutter_travel = v;
+    }
     {  // (checked here, so that a bad lens is a load error; the CLI's --aperture / --focus-distance are checked again)
         const CameraBluePrint& cb = bp.camera_blueprint;
         const float ap = cb.camera_aperture_mm ? *cb.camera_aperture_mm : 0.0f;

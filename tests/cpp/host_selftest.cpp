@@ -4,6 +4,7 @@
 // Inputs: the two shipped scenes with a generated .obj, a set of malformed YAML / .obj texts that must be rejected
 // with rbrt::Error (the reference panics there: blueprints.rs:80,87, mesh.rs:89) and never crash, and meshes large
 // enough to take the builder's multi-threaded path (bvh.cpp splice).
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -18,6 +19,7 @@
 #include <cstring>
 #include "../../rbrt_amd/csrc/bvh.h"
 #include "../../rbrt_amd/host/checkpoint.hpp"
+#include "../../rbrt_amd/host/cli.hpp"
 #include "../../rbrt_amd/host/rbrt.hpp"
 #include "../../rbrt_amd/host/yaml_lite.hpp"
 
@@ -250,7 +252,47 @@ static void check_checkpoint(const std::string& tmp) {
     CHECK(fingerprint_of(false, false, false, false, "other.ckpt") == expect[0]);
 }
 
+// ---- the command line's parser and checks, in-process: the code a few argvs return and what they left in the options ----
+// (every refusal also writes its line to stderr; tests/test_cli_refusals_host.py pins those texts on the binary)
+struct Cli {
+    CliOptions o;
+    int parsed, checked = CLI_RUN;
+    Cli(std::vector<std::string> args) {
+        std::vector<char*> argv{const_cast<char*>("rbrt")};
+        for (std::string& a : args) argv.push_back(a.data());
+        rbrt::PfmImage ref;
+        parsed = parse_cli(int(argv.size()), argv.data(), o);
+        if (parsed == CLI_RUN) checked = check_cli(o, ref);
+    }
+};
+
+static void check_cli_parser() {
+    CHECK(Cli({}).parsed == CLI_RUN && Cli({}).checked == CLI_RUN && Cli({}).o.samples == 5);
+    CHECK(Cli({"-h", "--bogus"}).parsed == CLI_HELP && Cli({"--bogus", "-h"}).parsed == 2 && Cli({"bogus"}).parsed == 2);
+    {  // one of each reader, in both spellings
+        const Cli c({"-w", "7", "--height=9", "--denoise", "--denoise-radius", "10", "--denoise-strength=1e-3", "--background", "1,0,0.5", "--gather", "rccl",
+                     "--tonemap=aces", "--compare-epsilon", "0.5", "--error-map", "e.png", "--compare", "missing.pfm", "--seed", "banana", "-t", "--noisy"});
+        CHECK(c.parsed == CLI_RUN && c.o.width == 7 && c.o.height == 9 && c.o.denoise && c.o.denoise_radius == 10u && c.o.denoise_strength == 1e-3f);
+        CHECK(c.o.constant_background && c.o.background[2] == 0.5f && c.o.gather == "rccl" && c.o.tone_curve == RBRT_TONE_ACES && c.o.seed == 0);
+        CHECK(c.o.target == "--noisy" && c.o.noisy.empty() && c.o.error_map == "e.png");
+        CHECK(c.checked == 2);  // the reference cannot be read
+    }
+    for (const char* last : {"--samples", "-c", "--glare", "--camera-step", "--shading", "--features"}) CHECK(Cli({"--denoise", last}).parsed == 2);
+    for (const char* bad : {"--width=-1", "--width=4294967296", "--width=", "--denoise-radius=11", "--frames=0", "--glare=1.5", "--glare=nan", "--adaptive=inf",
+                            "--camera-step=1,2", "--camera-step=1,2,inf", "--background=-1,0,0", "--shading=round", "--features=", "--denoise=1", "--exposure=128"})
+        CHECK(Cli({bad}).parsed == 2);
+    CHECK(Cli({"--despike=1", "--oversubscribe=1"}).o.despike && Cli({"--despike=1", "--oversubscribe=1"}).o.oversubscribe);
+    CHECK(Cli({"--exposure", "auto"}).o.exposure == 0.0f && Cli({"--exposure=-1"}).o.exposure == 0.5f && Cli({"--white", "auto", "--tonemap", "reinhard"}).o.white == 0.0f);
+    CHECK(std::signbit(*Cli({"--adaptive=-0"}).o.adaptive) && !std::signbit(*Cli({"--frames=2", "--temporal-depth=-0"}).o.temporal_depth));
+    // the groups: the first conflict of the chain, --samples, the first dependant; what stands between and behind them
+    CHECK(Cli({"--upscale", "2"}).checked == CLI_RUN && Cli({"--upscale", "2", "--sample-map", "m.png"}).checked == 2 && Cli({"--upscale", "2", "-s", "1"}).checked == 2);
+    CHECK(Cli({"--upscale-depth", "0.1"}).checked == 2 && Cli({"--guided-no-demodulation"}).checked == 2 && Cli({"--noisy", "n.png", "--despike"}).checked == CLI_RUN);
+    CHECK(Cli({"--frames", "2", "--camera-step", "3e38,0,0", "--shutter", "2"}).checked == 2 && Cli({"--frames", "2", "--camera-step", "1,0,0", "--shutter", "2"}).checked == CLI_RUN);
+    CHECK(Cli({"--white", "2"}).checked == 2 && Cli({"--radiance", "r.png"}).checked == 2 && Cli({"--environment", "x.pfm", "--background", "0,0,0"}).checked == 2);
+}
+
 int main(int argc, char** argv) {
+    check_cli_parser();
     const std::string root = argc > 1 ? argv[1] : ".";
     const std::string tmp = argc > 2 ? argv[2] : "/tmp";
     const std::string obj = tmp + "/selftest_bunny.obj";

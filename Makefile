@@ -22,7 +22,7 @@ all: $(LIBDIR)/librbrt_hip.so host oracle
 
 $(LIBDIR)/librbrt_hip.so: $(CSRC)/kernels.hip $(CSRC)/megakernel.inl $(CSRC)/features.inl $(CSRC)/short_paths.inl $(CSRC)/api.cpp $(CSRC)/api_common.h $(CSRC)/frame_stages.cpp $(CSRC)/selftests.cpp $(CSRC)/bvh.cpp $(CSRC)/bvh.h \
                           $(CSRC)/bvh_device.hip $(CSRC)/bvh_device.h $(CSRC)/denoise.hip $(CSRC)/tonemap.hip $(CSRC)/glare.hip $(CSRC)/guided.hip $(CSRC)/temporal.hip $(CSRC)/upsample.hip $(CSRC)/despike.hip $(CSRC)/compare.hip \
-                          $(CSRC)/device_types.h include/rbrt_hip.h include/rbrt_hip_debug.h
+                          $(CSRC)/device_types.h $(CSRC)/trace_knobs.h include/rbrt_hip.h include/rbrt_hip_debug.h
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(CSRC)/kernels.hip $(CSRC)/bvh_device.hip $(CSRC)/denoise.hip $(CSRC)/tonemap.hip $(CSRC)/glare.hip $(CSRC)/guided.hip $(CSRC)/temporal.hip $(CSRC)/upsample.hip $(CSRC)/despike.hip $(CSRC)/compare.hip $(CSRC)/api.cpp $(CSRC)/frame_stages.cpp $(CSRC)/selftests.cpp $(CSRC)/bvh.cpp
 

@@ -233,6 +233,21 @@ int rbrt_hip_scene_launch_mix(rbrt_hip_scene_t* scene, uint32_t* n_full_grid, ui
  * caller has stopped issuing (api.cpp "Elastic launches"; lab knob RBRT_HELPERS=0|1|2: never, automatic, with every launch). */
 int rbrt_hip_scene_helper_launches(rbrt_hip_scene_t* scene, uint32_t* n);
 
+/* Which build of the trace kernel the handle's last trace launch ran (its helper launches run the same one). The kernel
+ * has a general build and a PLAIN one, which has the default values of the lab knobs RBRT_Y_LOW, RBRT_Y_HIGH,
+ * RBRT_Y_HIGH_PARKED, RBRT_LEAF_ROUND, RBRT_LEAF_LEAVES, RBRT_SHARE_IDLE, RBRT_SHADE_ROUNDS and RBRT_SHADE_CONT_MIN
+ * (rbrt_amd/csrc/trace_knobs.h) and the plain scene -- spheres and exactly one mesh, no BasicTriangle element, no lens, no
+ * shutter, no environment map, no pattern -- built in as constants. A launch runs the PLAIN build when all of that holds for
+ * it and it is not a counting launch (RBRT_FLAG_COLLECT_STATS). Both compute the same bits (tests/test_plain_build_gpu.py).
+ * *build: RBRT_TRACE_BUILD_NONE before the first launch.
+ * The choice has a lab control of its own, read and validated by rbrt_hip_scene_create under the rules of the lab knobs at
+ * the top of this file: RBRT_TRACE_BUILD=auto (the default: as described) | general (the general build for every launch of
+ * the handle, for A/B runs and the bit comparison); any other string is RBRT_ERR_INVALID_ARG. */
+#define RBRT_TRACE_BUILD_NONE 0
+#define RBRT_TRACE_BUILD_GENERAL 1
+#define RBRT_TRACE_BUILD_PLAIN 2
+int rbrt_hip_scene_last_trace_build(rbrt_hip_scene_t* scene, int* build);
+
 /* The short-path stage (DESIGN.md "The tile pass"; short_paths.inl): a streaming kernel in front of every trace launch that
  * has tile tables finishes the two-ray paths of the tiles no camera ray of which can pass a mesh box, and the trace kernel
  * skips those samples. The image is the same bits either way. For the handle's later launches, mode 0: never (the A/B and

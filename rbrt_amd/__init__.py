@@ -270,6 +270,13 @@ class HipScene:
         abi.check(self._lib.rbrt_hip_scene_helper_launches(self._h, C.byref(n)))
         return n.value
 
+    def last_trace_build(self) -> str:
+        """The build of the trace kernel the last trace launch ran: "none", "general" or "plain"
+        (rbrt_hip_scene_last_trace_build)."""
+        b = C.c_int()
+        abi.check(self._lib.rbrt_hip_scene_last_trace_build(self._h, C.byref(b)))
+        return ("none", "general", "plain")[b.value]
+
     def create_times(self) -> dict:
         """Where the time of rbrt_hip_scene_create went (rbrt_hip_scene_create_times)."""
         t = abi.CallTimes()

@@ -402,6 +402,7 @@ DEBUG_SYMBOLS = {
                                                       C.POINTER(C.c_uint32), C.c_size_t]),
     "rbrt_hip_debug_primary_cull_opts": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderOpts), C.POINTER(C.c_uint32), C.c_size_t]),
     "rbrt_hip_scene_helper_launches": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "rbrt_hip_scene_last_trace_build": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "rbrt_hip_scene_create_times": (C.c_int, [C.c_void_p, C.POINTER(CallTimes)]),
     "rbrt_hip_last_render_times": (C.c_int, [C.POINTER(CallTimes)]),
     "rbrt_hip_scene_refine_wait": (C.c_int, [C.c_void_p, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_double)]),

@@ -27,8 +27,9 @@
 #include "../../include/rbrt_hip_debug.h"
 
 namespace rbrt {  // (the launch wrappers only this file calls; api_common.h has the others)
-hipError_t launch_trace_megakernel(const TraceParams& P, uint32_t n_waves, bool stats, hipStream_t stream);
-hipError_t launch_trace_helper(const TraceParams& P, uint32_t n_waves, hipStream_t stream);
+bool trace_params_are_plain(const TraceParams& P);
+hipError_t launch_trace_megakernel(const TraceParams& P, uint32_t n_waves, bool stats, bool plain, hipStream_t stream);
+hipError_t launch_trace_helper(const TraceParams& P, uint32_t n_waves, bool plain, hipStream_t stream);
 size_t megakernel_gseq_bytes(uint32_t n_waves);
 size_t megakernel_gstack_bytes(uint32_t n_waves);
 size_t megakernel_lds_bytes(uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris, uint32_t thin_lens,
@@ -315,6 +316,7 @@ struct rbrt_hip_scene {
             bool valid = false;
             TraceParams P;
             uint32_t grid = 0, helper_waves = 0, rounds = 0;
+            bool plain = false;         // the build of the trace kernel it runs: its helper launches run the same
             uint64_t seq = 0;           // issue number: a later launch has more of its work left
         } open;
     };
@@ -380,12 +382,13 @@ struct rbrt_hip_scene {
     uint32_t stack_need = 1;  // deepest BVH: 3 per level + 1
     uint32_t n_waves = 0;  // persistent megakernel grid: as many single-wave workgroups as fit the LDS
     uint32_t stack_entries = kLdsStack;  // per-lane stack entries kept in LDS (RBRT_LDS_STACK)
-    uint32_t y_low_water = 28;    // RBRT_Y_LOW
-    uint32_t y_high_water = 28, y_high_min_parked = 16;  // RBRT_Y_HIGH, RBRT_Y_HIGH_PARKED
-    uint32_t leaf_round = 6;      // RBRT_LEAF_ROUND
-    uint32_t leaf_leaves = 16;    // RBRT_LEAF_LEAVES
-    uint32_t share_idle = 4;      // RBRT_SHARE_IDLE (0: no shared traversals)
-    uint32_t work_stripes = 16;   // RBRT_WORK_STRIPES: chunks (of 64 work items) per stripe for a launch that has the GPU to itself; 0 = contiguous shards
+    // (the trace kernel's knobs start at trace_knobs.h's defaults: the kernel's PLAIN build has exactly those built in)
+    uint32_t y_low_water = kDefaultKnobs.y_low_water;    // RBRT_Y_LOW
+    uint32_t y_high_water = kDefaultKnobs.y_high_water, y_high_min_parked = kDefaultKnobs.y_high_min_parked;  // RBRT_Y_HIGH, RBRT_Y_HIGH_PARKED
+    uint32_t leaf_round = kDefaultKnobs.leaf_round;      // RBRT_LEAF_ROUND
+    uint32_t leaf_leaves = kDefaultKnobs.leaf_leaves;    // RBRT_LEAF_LEAVES
+    uint32_t share_idle = kDefaultKnobs.share_idle;      // RBRT_SHARE_IDLE (0: no shared traversals)
+    uint32_t work_stripes = kDefaultWorkStripes;   // RBRT_WORK_STRIPES: chunks (of 64 work items) per stripe for a launch that has the GPU to itself; 0 = contiguous shards
     // RBRT_WORK_STRIPES_OVERLAP: the same for a launch issued while another is running. Automatic (kStripesAuto): contiguous
     // shards for a big launch, stripes of 4 chunks for one below 20 M work items -- measured per step on one box, 4 against
     // 0: the frame of config 2 (39 M) +1.0 %, the 871k mesh +2.0 %, the rough mesh -0.8 %; a half (20 M) -0.8 %, a quarter
@@ -407,8 +410,13 @@ struct rbrt_hip_scene {
         const uint32_t* d_lists = nullptr;
         uint32_t batch = 0;
     } last_short;
-    uint32_t shade_rounds = 1;    // RBRT_SHADE_ROUNDS (rounds while work items are left; unbounded afterwards)
-    uint32_t shade_cont_min = 8;  // RBRT_SHADE_CONT_MIN
+    uint32_t shade_rounds = kDefaultKnobs.shade_rounds;      // RBRT_SHADE_ROUNDS (rounds while work items are left; unbounded afterwards)
+    uint32_t shade_cont_min = kDefaultKnobs.shade_cont_min;  // RBRT_SHADE_CONT_MIN
+    // RBRT_TRACE_BUILD=auto|general (lab): false = the PLAIN build of the trace kernel wherever a launch qualifies for it
+    // (kernels.hip trace_params_are_plain), true = the general build always. last_trace_build: what the last trace launch ran
+    // (rbrt_hip_debug.h rbrt_hip_scene_last_trace_build).
+    bool trace_build_general = false;
+    int last_trace_build = RBRT_TRACE_BUILD_NONE;
     // stats / timing
     rbrt_hip_stats_t stats{};
     bool stats_pending = false;
@@ -806,7 +814,7 @@ int issue_helper(rbrt_hip_scene* s, rbrt_hip_scene::Lane& L, uint32_t waves, hip
     TraceParams P = L.open.P;
     P.wave_base = L.open.grid + L.open.helper_waves;
     P.helper_min_items = s->helpers_mode == 2u ? 0u : s->helper_min_items;  // (tests: every helper wave joins)
-    HIP_TRY(launch_trace_helper(P, waves, carrier));
+    HIP_TRY(launch_trace_helper(P, waves, L.open.plain, carrier));
     HIP_TRY(hipEventRecord(L.ev_helper, carrier));
     L.helper_pending = true;
     L.open.helper_waves += waves, L.open.rounds += 1u;
@@ -1450,6 +1458,11 @@ int read_scene_knobs(rbrt_hip_scene* s, uint32_t& waves_per_cu) {
         lab_u32("RBRT_HELPER_ROUNDS", 1, 16, s->helper_rounds, err) && lab_u32("RBRT_TRACE_LAUNCHES", 0, 1, trace_launches, err) &&
         lab_u32("RBRT_TRACE_CREATE", 0, 1, trace_create, err);
     if (!knobs_ok) return fail(RBRT_ERR_INVALID_ARG, err);
+    if (const char* b = lab_env("RBRT_TRACE_BUILD")) {
+        if (std::strcmp(b, "auto") != 0 && std::strcmp(b, "general") != 0)
+            return fail(RBRT_ERR_INVALID_ARG, std::string("lab knob RBRT_TRACE_BUILD=") + b + " is not valid (see include/rbrt_hip_debug.h)");
+        s->trace_build_general = b[0] == 'g';
+    }
     s->trace_launches = trace_launches != 0u, s->trace_create = trace_create != 0u;
     if ((stripes & (stripes - 1u)) != 0u || (stripes_overlap != kStripesAuto && (stripes_overlap & (stripes_overlap - 1u)) != 0u))  // the kernel shifts
         return fail(RBRT_ERR_INVALID_ARG, "lab knob RBRT_WORK_STRIPES / RBRT_WORK_STRIPES_OVERLAP must be 0 or a power of two");
@@ -1657,6 +1670,14 @@ int rbrt_hip_scene_helper_launches(rbrt_hip_scene_t* s, uint32_t* n) {
     if (!s || !n) return fail(RBRT_ERR_INVALID_ARG, "helper_launches: null argument");
     std::lock_guard<std::mutex> watcher_lock(s->mu);
     *n = s->n_helper_launches;
+    return RBRT_OK;
+}
+
+// Which build of the trace kernel the handle's last trace launch ran.
+int rbrt_hip_scene_last_trace_build(rbrt_hip_scene_t* s, int* build) {
+    if (!s || !build) return fail(RBRT_ERR_INVALID_ARG, "last_trace_build: null argument");
+    std::lock_guard<std::mutex> watcher_lock(s->mu);
+    *build = s->last_trace_build;
     return RBRT_OK;
 }
 
@@ -2023,9 +2044,13 @@ int issue_batches(rbrt_hip_scene* s, const CallPlan& c, const rbrt_render_opts_t
             s->last_short.d_masks = B.d_short_masks, s->last_short.d_lists = P.tile_lists, s->last_short.batch = nb;
         }
         if (piped) HIP_TRY(hipEventRecord(L.ev_ready, ts));  // (behind everything the launch waits for: a helper launch waits for this)
-        HIP_TRY(launch_trace_megakernel(P, grid, stats, ts));
+        // (the PLAIN build: the same kernel with the default knobs and the one-mesh scene built in, megakernel.inl; a counting
+        // launch, a lab knob, a second mesh, an element triangle, a lens, a shutter, a map or a pattern run the general one)
+        const bool plain = !stats && !s->trace_build_general && trace_params_are_plain(P);
+        s->last_trace_build = plain ? RBRT_TRACE_BUILD_PLAIN : RBRT_TRACE_BUILD_GENERAL;
+        HIP_TRY(launch_trace_megakernel(P, grid, stats, plain, ts));
         if (piped && s->helpers_mode != 0u && !c.round) {  // (the launches of an adaptive round get no helpers: see rbrt_hip_render_adaptive)
-            L.open.valid = true, L.open.P = P, L.open.grid = grid, L.open.helper_waves = 0u, L.open.rounds = 0u, L.open.seq = ++s->open_seq;
+            L.open.valid = true, L.open.P = P, L.open.grid = grid, L.open.helper_waves = 0u, L.open.rounds = 0u, L.open.plain = plain, L.open.seq = ++s->open_seq;
             if (s->helpers_mode == 2u) {  // (tests: a helper with every overlapped launch, on a stream of its own)
                 if (!s->aux_stream) HIP_TRY(hipStreamCreateWithFlags(&s->aux_stream, hipStreamNonBlocking));
                 if (int rc = issue_helper(s, L, s->n_cus, s->aux_stream)) return rc;

@@ -3,6 +3,7 @@
 #include <stdint.h>
 
 #include "../../include/rbrt_hip.h"
+#include "trace_knobs.h"
 
 namespace rbrt {
 

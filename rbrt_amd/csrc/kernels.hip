@@ -626,13 +626,17 @@ __device__ __forceinline__ V3 random_point_in_unit_sphere(Rng& rng) {  // materi
     // still rounds to 1.0, sqrt(1 + 2^-22) rounds to 1 + 2^-23. So the loop can compare the squared
     // length and skip an IEEE square root per iteration with bit-identical accept/reject decisions
     // (checked exhaustively around 1.0 in tests/test_oracle_kats.py).
+    // A component is 2.0f * next_f32() - 1.0f with next_f32() = float(k) * 2^-24, k < 2^24: float(k), both products and the
+    // difference (k - 2^23) * 2^-23 are all exact, so one fused multiply-add of float(k), exact as well, is the same float
+    // for every k (tests/test_unit_sphere_point.py runs all 2^24) and two VALU instructions fewer per component.
+    const auto component = [&]() { return __builtin_fmaf(float(rng.next_u32() >> 8), 0x1p-23f, -1.0f); };
     V3 p;
     float s;
     do {
-        float x = rng.next_f32();
-        float y = rng.next_f32();
-        float z = rng.next_f32();
-        p = 2.0f * mk(x, y, z) - mk(1.0f, 1.0f, 1.0f);
+        const float x = component();
+        const float y = component();
+        const float z = component();
+        p = mk(x, y, z);
         s = (p.x * p.x + p.y * p.y) + p.z * p.z;
     } while (s > 1.00000011920928955078125f);
     return p;
@@ -1890,24 +1894,41 @@ int megakernel_occupancy_per_cu(size_t lds_bytes) {
     return e == hipSuccess ? n : 0;
 }
 
+// Does the launch qualify for the PLAIN build of the trace kernel (megakernel.inl TraceView)? Every constant that build has
+// in place of a parameter is compared with the parameter here, and nowhere else.
+bool trace_params_are_plain(const TraceParams& P) {
+    return P.n_meshes == 1u && P.n_elem_tris == 0u && P.thin_lens == 0u && P.shutter == 0u && P.env_nodes == nullptr && P.pattern_dw == 0u &&
+           P.y_low_water == kDefaultKnobs.y_low_water && P.y_high_water == kDefaultKnobs.y_high_water &&
+           P.y_high_min_parked == kDefaultKnobs.y_high_min_parked && P.leaf_round == kDefaultKnobs.leaf_round &&
+           P.leaf_leaves == kDefaultKnobs.leaf_leaves && P.share_idle == kDefaultKnobs.share_idle &&
+           P.shade_rounds == kDefaultKnobs.shade_rounds && P.shade_cont_min == kDefaultKnobs.shade_cont_min;
+}
+
 // n_waves single-wave workgroups; each loops until the global work counter (zeroed by the caller on
 // this stream) runs out, so any grid size is correct and no wave ever waits on another.
 // A helper launch (api.cpp "Elastic launches"): more waves for a launch that is already running -- the same parameters
 // (work counters, sample buffer, tables), scratch slots from P.wave_base on.
-hipError_t launch_trace_helper(const TraceParams& P, uint32_t n_waves, hipStream_t stream) {
+hipError_t launch_trace_helper(const TraceParams& P, uint32_t n_waves, bool plain, hipStream_t stream) {
     if (P.n_items == 0 || n_waves == 0 || !P.helper_words) return hipSuccess;
     const size_t lds = megakernel_lds_bytes(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris, P.thin_lens, P.env_nodes ? 1u : 0u, P.pattern_dw, P.shutter);
-    hipLaunchKernelGGL((trace_megakernel<false, true>), dim3(n_waves), dim3(64), lds, stream, P);
+    if (plain && trace_params_are_plain(P))
+        hipLaunchKernelGGL((trace_megakernel<false, true, true>), dim3(n_waves), dim3(64), lds, stream, P);
+    else
+        hipLaunchKernelGGL((trace_megakernel<false, true, false>), dim3(n_waves), dim3(64), lds, stream, P);
     return hipGetLastError();
 }
 
-hipError_t launch_trace_megakernel(const TraceParams& P, uint32_t n_waves, bool stats, hipStream_t stream) {
+// `plain`: the caller allows the PLAIN build (megakernel.inl TraceView); it runs only if the parameters are what it has built
+// in, whatever the caller says, and never for a counting launch.
+hipError_t launch_trace_megakernel(const TraceParams& P, uint32_t n_waves, bool stats, bool plain, hipStream_t stream) {
     if (P.n_items == 0 || n_waves == 0) return hipSuccess;
     const size_t lds = megakernel_lds_bytes(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris, P.thin_lens, P.env_nodes ? 1u : 0u, P.pattern_dw, P.shutter);
     if (stats)
-        hipLaunchKernelGGL((trace_megakernel<true>), dim3(n_waves), dim3(64), lds, stream, P);
+        hipLaunchKernelGGL((trace_megakernel<true, false, false>), dim3(n_waves), dim3(64), lds, stream, P);
+    else if (plain && trace_params_are_plain(P))
+        hipLaunchKernelGGL((trace_megakernel<false, false, true>), dim3(n_waves), dim3(64), lds, stream, P);
     else
-        hipLaunchKernelGGL((trace_megakernel<false>), dim3(n_waves), dim3(64), lds, stream, P);
+        hipLaunchKernelGGL((trace_megakernel<false, false, false>), dim3(n_waves), dim3(64), lds, stream, P);
     return hipGetLastError();
 }
 

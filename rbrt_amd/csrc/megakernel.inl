@@ -237,10 +237,45 @@ struct WorkSource {
     }
 };
 
-// Three builds: the product, the counting build (STATS: diagnostics into DevCounters) and the helper build (HELPER: extra
-// waves for a launch that is already running, api.cpp "Elastic launches").
-template <bool STATS, bool HELPER = false>
+// What a build of the kernel reads of its launch's parameters where the PLAIN build has a constant instead: the lab knobs
+// at their defaults (trace_knobs.h) and the plain scene -- spheres and exactly ONE mesh, no BasicTriangle element, no lens,
+// no shutter, no environment map, no pattern: every scene the reference's YAML describes. The kernel reads every such
+// value through these accessors and nowhere else, so the two builds are the same logic; launch_trace_megakernel runs the
+// PLAIN build only for launches whose parameters ARE these constants (trace_params_are_plain). (work_stripes is chosen
+// per launch, api.cpp: it stays a run-time value.)
+template <bool PLAIN>
+struct TraceView {
+    const TraceParams& P;
+#define RBRT_KNOB(name) \
+    __device__ __forceinline__ uint32_t name() const { return PLAIN ? kDefaultKnobs.name : P.name; }
+    RBRT_KNOB(y_low_water) RBRT_KNOB(y_high_water) RBRT_KNOB(y_high_min_parked) RBRT_KNOB(leaf_round) RBRT_KNOB(leaf_leaves)
+    RBRT_KNOB(share_idle) RBRT_KNOB(shade_rounds) RBRT_KNOB(shade_cont_min)
+#undef RBRT_KNOB
+    __device__ __forceinline__ uint32_t n_meshes() const { return PLAIN ? 1u : P.n_meshes; }
+    __device__ __forceinline__ uint32_t n_elem_tris() const { return PLAIN ? 0u : P.n_elem_tris; }
+    __device__ __forceinline__ uint32_t pattern_dw() const { return PLAIN ? 0u : P.pattern_dw; }
+    // (without patterns every lambertian's link is 0, api.cpp element_tables: surface_entry would return the object itself)
+    __device__ __forceinline__ bool may_have_patterns() const { return !PLAIN; }
+    __device__ __forceinline__ bool thin_lens() const { return PLAIN ? false : P.thin_lens != 0u; }
+    __device__ __forceinline__ bool shutter() const { return PLAIN ? false : P.shutter != 0u; }
+    __device__ __forceinline__ bool environment() const { return PLAIN ? false : P.env_nodes != nullptr; }
+    // the G_FLAGS word as staged in LDS: bits 0 and 1 (tile order, constant background) are any launch's; the lens, map and
+    // shutter bits and the offset of their words are zero in a plain launch
+    __device__ __forceinline__ uint32_t gen_flags(uint32_t word) const { return PLAIN ? word & 3u : word; }
+    // a mesh index read back from a path's state: with one mesh there is only mesh 0
+    __device__ __forceinline__ uint32_t mesh_index(uint32_t m) const { return PLAIN ? 0u : m; }
+    // Is the closest hit so far (object obj >= 0) of a ray that is about to search, or has just searched, mesh `mesh_index`
+    // an element? Else it is an EARLIER mesh of the same ray, and mesh 0 has none.
+    __device__ __forceinline__ bool hit_is_element(int32_t obj, uint32_t n_elem) const { return PLAIN ? true : uint32_t(obj) < n_elem; }
+};
+
+// Four builds: the product's two (general, and PLAIN: TraceView), the counting build (STATS: diagnostics into DevCounters,
+// always general) and the helper builds (HELPER: extra waves for a launch that is already running, api.cpp "Elastic
+// launches"; the build of the launch they join).
+template <bool STATS, bool HELPER = false, bool PLAIN = false>
 __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(const TraceParams P) {
+    static_assert(!(STATS && PLAIN), "the counting build is general");
+    const TraceView<PLAIN> K = {P};
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     constexpr uint32_t kPoolPad = (uint32_t(kPool) + 63u) & ~63u;  // census loops run in groups of 64 slots
     uint32_t* const pool = lds;
@@ -312,8 +347,8 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
     cell[lane] = kNoHitKey;
     if (lane < kHelpDw) helpers[lane] = 0u;
     // scene tables behind the stacks
-    const uint32_t n_elem = P.n_spheres + P.n_elem_tris;  // Scene::elements: spheres and BasicTriangles, in the scene's order
-    const uint32_t n_obj = n_elem + P.n_meshes;
+    const uint32_t n_elem = P.n_spheres + K.n_elem_tris();  // Scene::elements: spheres and BasicTriangles, in the scene's order
+    const uint32_t n_obj = n_elem + K.n_meshes();
     uint32_t* const sc_base = stack_base + P.stack_entries * 64u;
     {
         const uint32_t* gs = reinterpret_cast<const uint32_t*>(P.spheres);
@@ -323,18 +358,18 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
         for (uint32_t i = lane; i < P.n_spheres * kSphDw; i += 64) dst[i] = gs[i];
         dst += P.n_spheres * kSphDw;
         // (with patterns: the second entries and the DevPatterns behind the objects' materials are part of the table)
-        for (uint32_t i = lane; i < n_obj * kMatDw + P.pattern_dw; i += 64) dst[i] = gm[i];
-        dst += n_obj * kMatDw + P.pattern_dw;
-        for (uint32_t i = lane; i < P.n_meshes * kMeshDw; i += 64) dst[i] = gh[i];
+        for (uint32_t i = lane; i < n_obj * kMatDw + K.pattern_dw(); i += 64) dst[i] = gm[i];
+        dst += n_obj * kMatDw + K.pattern_dw();
+        for (uint32_t i = lane; i < K.n_meshes() * kMeshDw; i += 64) dst[i] = gh[i];
         // what path generation reads (camera, work decomposition): kept in LDS rather than in ~30 SGPRs that the
         // rest of the kernel would have to spill around (the spill code is VALU: v_readlane / v_writelane)
-        dst += P.n_meshes * kMeshDw;
+        dst += K.n_meshes() * kMeshDw;
         uint32_t* const gen_dst = dst;
-        if (P.n_elem_tris != 0u) {  // behind the generation parameters: the triangle elements and the element order
+        if (K.n_elem_tris() != 0u) {  // behind the generation parameters: the triangle elements and the element order
             const uint32_t* gt = reinterpret_cast<const uint32_t*>(P.elem_tris);
             uint32_t* td = gen_dst + kGenDw;
-            for (uint32_t i = lane; i < P.n_elem_tris * kTriDw; i += 64) td[i] = gt[i];
-            td += P.n_elem_tris * kTriDw;
+            for (uint32_t i = lane; i < K.n_elem_tris() * kTriDw; i += 64) td[i] = gt[i];
+            td += K.n_elem_tris() * kTriDw;
             for (uint32_t i = lane; i < n_elem; i += 64) td[i] = P.elems[i];
         }
         if (lane == 0) {
@@ -348,27 +383,27 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
             dst[G_BATCH] = P.batch, dst[G_BATCH_MAGIC] = P.batch_magic;
             dst[G_TILES_X] = P.tiles_x, dst[G_TILES_X_MAGIC] = P.tiles_x_magic;
             dst[G_TILE_WORLD] = P.tile_world, dst[G_TILE_RANK] = P.tile_rank;
-            dst[G_N_LOCAL] = n_work, dst[G_FLAGS] = (P.tiles_reversed ? 1u : 0u) | (P.constant_bg ? 2u : 0u) | (P.thin_lens ? 4u : 0u) | (P.env_nodes ? 8u : 0u);
+            dst[G_N_LOCAL] = n_work, dst[G_FLAGS] = (P.tiles_reversed ? 1u : 0u) | (P.constant_bg ? 2u : 0u) | (K.thin_lens() ? 4u : 0u) | (K.environment() ? 8u : 0u);
             // (one word: a new one would take the header card's scene past 16 waves per CU, and reading the kernel argument cost
             // 3 SGPR spills. A lens launch's lens words sit behind everything else, at the dword offset from here that bits
             // 8 and up of the flags word carry: a pinhole launch's LDS -- and with it every current scene's occupancy -- and its
             // layout are what they were.)
-            if (P.thin_lens) {
-                const uint32_t at = kGenDw + (P.n_elem_tris != 0u ? P.n_elem_tris * kTriDw + n_elem : 0u);  // behind everything else
+            if (K.thin_lens()) {
+                const uint32_t at = kGenDw + (K.n_elem_tris() != 0u ? K.n_elem_tris() * kTriDw + n_elem : 0u);  // behind everything else
                 for (int c = 0; c < 3; ++c) gf[at + c] = P.lens_u[c], gf[at + 3 + c] = P.lens_v[c];
                 gf[at + 6] = P.focus_scale, dst[at + 7] = 0u;
                 dst[G_FLAGS] |= at << 8;
             }
-            if (P.env_nodes) {  // the same way, behind the lens: the map's address and n (the kernel argument cost a VGPR spill)
-                const uint32_t at = kGenDw + (P.n_elem_tris != 0u ? P.n_elem_tris * kTriDw + n_elem : 0u);
-                const uint32_t ea = at + (P.thin_lens ? kLensDw : 0u);
+            if (K.environment()) {  // the same way, behind the lens: the map's address and n (the kernel argument cost a VGPR spill)
+                const uint32_t at = kGenDw + (K.n_elem_tris() != 0u ? K.n_elem_tris() * kTriDw + n_elem : 0u);
+                const uint32_t ea = at + (K.thin_lens() ? kLensDw : 0u);
                 const uint64_t addr = reinterpret_cast<uint64_t>(P.env_nodes);
                 dst[ea] = uint32_t(addr), dst[ea + 1] = uint32_t(addr >> 32), dst[ea + 2] = P.env_n, dst[ea + 3] = 0u;
                 dst[G_FLAGS] = (dst[G_FLAGS] & 0xFFu) | (at << 8);
             }
-            if (P.shutter) {  // the same way, behind the lens and the map: the travel, announced by bit 4 (nothing without a shutter)
-                const uint32_t at = kGenDw + (P.n_elem_tris != 0u ? P.n_elem_tris * kTriDw + n_elem : 0u);
-                const uint32_t sa = at + (P.thin_lens ? kLensDw : 0u) + (P.env_nodes ? kEnvDw : 0u);
+            if (K.shutter()) {  // the same way, behind the lens and the map: the travel, announced by bit 4 (nothing without a shutter)
+                const uint32_t at = kGenDw + (K.n_elem_tris() != 0u ? K.n_elem_tris() * kTriDw + n_elem : 0u);
+                const uint32_t sa = at + (K.thin_lens() ? kLensDw : 0u) + (K.environment() ? kEnvDw : 0u);
                 for (int c = 0; c < 3; ++c) gf[sa + c] = P.travel[c];
                 dst[sa + 3] = 0u;
                 dst[G_FLAGS] = (dst[G_FLAGS] & 0xFFu) | 16u | (at << 8);
@@ -377,12 +412,12 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
             dst[G_SEED_LO] = uint32_t(P.seed_key), dst[G_SEED_HI] = uint32_t(P.seed_key >> 32);
         }
     }
-    const uint32_t* const gp = sc_base + P.n_spheres * kSphDw + n_obj * kMatDw + P.pattern_dw + P.n_meshes * kMeshDw;
+    const uint32_t* const gp = sc_base + P.n_spheres * kSphDw + n_obj * kMatDw + K.pattern_dw() + K.n_meshes() * kMeshDw;
     const float* const gpf = reinterpret_cast<const float*>(gp);
     const uint32_t* const gtri = gp + kGenDw;
     const SceneLds sc = {reinterpret_cast<const float*>(sc_base), sc_base + P.n_spheres * kSphDw,
-                         sc_base + P.n_spheres * kSphDw + n_obj * kMatDw + P.pattern_dw, reinterpret_cast<const float*>(gtri),
-                         gtri + P.n_elem_tris * kTriDw};
+                         sc_base + P.n_spheres * kSphDw + n_obj * kMatDw + K.pattern_dw(), reinterpret_cast<const float*>(gtri),
+                         gtri + K.n_elem_tris() * kTriDw};
     // work items are reserved from the global counter in chunks, the next chunk asynchronously
     WorkSource work;
     work.init(n_items);
@@ -447,7 +482,7 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
     };
     auto pop = [&]() -> int32_t { return stack_at(--t_sp); };
     auto id_slot = [&]() { return t_ids & 255u; };
-    auto id_mesh = [&]() { return (t_ids >> 8) & 255u; };
+    auto id_mesh = [&]() { return K.mesh_index((t_ids >> 8) & 255u); };
     auto id_owner = [&]() { return (t_ids >> 16) & 63u; };
     auto id_given = [&]() { return t_ids >> 22; };
 
@@ -461,7 +496,7 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                 int32_t obj = int32_t((meta >> 14) & 255u) - 1;
                 float closest = 3.40282347e+38f;  // f32::MAX (scene.rs:21)
                 if (obj >= 0) {                   // dist_from_ray_orig of the closest hit so far
-                    if (uint32_t(obj) < n_elem) {
+                    if (K.hit_is_element(obj, n_elem)) {
                         closest = __uint_as_float(POOL(F_TRI, slot));  // an element (sphere / triangle): stored by the pass that found it
                     } else {                      // an earlier mesh of this ray: recomputed as it was computed
                         const V3 pc = t_o + __uint_as_float(POOL(F_T, slot)) * t_d;
@@ -481,10 +516,10 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                         }
                     }
                 }
-                const uint32_t m2 = next_gated_mesh<STATS>(sc, P.n_meshes, t_mesh + 1u, t_o, t_d, closest, lc);
+                const uint32_t m2 = next_gated_mesh<STATS>(sc, K.n_meshes(), t_mesh + 1u, t_o, t_d, closest, lc);
                 const uint32_t depth = meta & 127u;
-                POOL(F_META, slot) = pack_meta(depth, (meta >> 7) & 127u, obj, m2 < P.n_meshes ? m2 : 0u);
-                status[slot] = m2 < P.n_meshes ? ST_TRAV : classify(sc, obj, depth);
+                POOL(F_META, slot) = pack_meta(depth, (meta >> 7) & 127u, obj, m2 < K.n_meshes() ? m2 : 0u);
+                status[slot] = m2 < K.n_meshes() ? ST_TRAV : classify(sc, obj, depth);
                 t_has_result = 0;
             }
         }
@@ -510,7 +545,7 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
         RBRT_MARK(refill);
         // ---- idle lanes take parked rays (in batches: only when enough lanes are idle) ----
         // with plenty of parked rays the lanes are topped up sooner (y_high_water) than when few wait
-        const uint32_t y_refill = cnt[ST_TRAV] >= P.y_high_min_parked ? P.y_high_water : P.y_low_water;
+        const uint32_t y_refill = cnt[ST_TRAV] >= K.y_high_min_parked() ? K.y_high_water() : K.y_low_water();
         if (cnt[ST_TRAV] != 0 && (n_active < y_refill || n_active + cnt[ST_TRAV] <= 64u)) {
             uint32_t ny = 0;
 #pragma unroll
@@ -533,7 +568,7 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                     t_d = mk(__uint_as_float(POOL(F_DX, slot)), __uint_as_float(POOL(F_DY, slot)),
                              __uint_as_float(POOL(F_DZ, slot)));
                     const uint32_t r_meta = POOL(F_META, slot);
-                    const uint32_t t_mesh = (r_meta >> 22) & 255u;
+                    const uint32_t t_mesh = K.mesh_index((r_meta >> 22) & 255u);
                     t_ids = slot | (t_mesh << 8) | (lane << 16);
                     const uint32_t* md = sc.mesh + t_mesh * kMeshDw;
                     t_nodes = lds_ptr<BvhNode4>(md + MD_NODES);
@@ -553,7 +588,7 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                                            // its distance to the same few ulps)
                             const float omax = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(t_o.x), __builtin_fabsf(t_o.y)),
                                                                __builtin_fabsf(t_o.z));
-                            const float ref = __uint_as_float(uint32_t(r_obj) < n_elem ? POOL(F_TRI, slot) : POOL(F_T, slot));
+                            const float ref = __uint_as_float(K.hit_is_element(r_obj, n_elem) ? POOL(F_TRI, slot) : POOL(F_T, slot));
                             const float bound = ref * 1.001f + 0.001f * (1.0f + omax);
                             if (bound < 100000.0f) t_best = bound, t_best_idx = 0xFFFFFFFFu;
                         }
@@ -589,7 +624,7 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
         // Traverse while the lanes are well filled; shade when they are not (that is what parks new
         // rays) or when shading work has piled up to a full wave.
         const bool drain = !more_work;
-        const bool traverse = n_active != 0 && (best == 0 || (n_active >= P.y_low_water && best < 64u));
+        const bool traverse = n_active != 0 && (best == 0 || (n_active >= K.y_low_water() && best < 64u));
         if (traverse) {
             if (STATS) {
                 ++dg_pass[ST_TRAV];
@@ -601,7 +636,7 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
             }
             // leave as soon as enough lanes are idle to make a refill / shading pass worthwhile; when no
             // other work exists, as soon as one lane has a result (it creates shading work)
-            const uint32_t y_keep = cnt[ST_TRAV] >= P.y_high_min_parked ? P.y_high_water : P.y_low_water;
+            const uint32_t y_keep = cnt[ST_TRAV] >= K.y_high_min_parked() ? K.y_high_water() : K.y_low_water();
             // (once the work items have run out -- the drain -- there is nothing to keep lanes filled FOR: what counts is
             // how few, and how full, the remaining rounds are, so a burst in the drain runs until every lane has finished)
             const uint32_t keep = drain ? 1u
@@ -609,7 +644,7 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                                                                      : n_active;
             // (traversals are shared in the drain only: before it, a parked ray uses an idle lane better, and the
             // per-step bookkeeping of sharing costs more than the lanes it fills)
-            const bool share = P.share_idle != 0u && drain;
+            const bool share = K.share_idle() != 0u && drain;
             // (two copies of the loop: the bulk of a frame runs the one without any of the sharing code. One loop that
             // tested `share` per step cost the bulk 3-5 %: register allocation at the 128-VGPR limit)
             auto burst = [&](auto share_tag) {
@@ -635,7 +670,7 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                     const uint64_t busy = wballot((t_active | t_has_result) != 0u);
                     const uint64_t givers = wballot(t_active != 0u && t_sp > id_given());
                     const uint32_t n_idle = 64u - uint32_t(__popcll(busy));
-                    if (n_idle >= P.share_idle && givers != 0ull) {
+                    if (n_idle >= K.share_idle() && givers != 0ull) {
                         const uint32_t n_givers = uint32_t(__popcll(givers)), n_pairs = n_idle < n_givers ? n_idle : n_givers;
                         int32_t give = kNoChild;
                         if (t_active != 0u && t_sp > id_given() && lane_rank(givers) < n_pairs) {
@@ -696,7 +731,7 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                     ++dg_walk_rounds;
                     dg_walk_lanes += uint32_t(__popcll(walk_mask));
                 }
-                if (n_pend_leaves >= P.leaf_leaves || (n_pend_leaves != 0 && (n_stalled >= P.leaf_round || walk_mask == 0ull))) {
+                if (n_pend_leaves >= K.leaf_leaves() || (n_pend_leaves != 0 && (n_stalled >= K.leaf_round() || walk_mask == 0ull))) {
         RBRT_MARK(leaf_round);
                     // ---- leaf round: the pending triangles are dealt out to ALL lanes, one triangle each ----
                     // (a leaf holds 1..4 triangles and only some lanes hold a leaf: testing them where they are
@@ -862,8 +897,8 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                 const int32_t obj = int32_t((meta >> 14) & 255u) - 1;
                 V3 color = mk(0.0f, 0.0f, 0.0f);  // hit with depth 0 or a failed scatter: lib.rs:63-66
                 if (obj < 0) {
-                    if (gp[G_FLAGS] & 8u) {  // the handle's environment takes the background's place
-                        const uint32_t* ew = gp + (gp[G_FLAGS] >> 8) + ((gp[G_FLAGS] & 4u) ? kLensDw : 0u);
+                    if (K.gen_flags(gp[G_FLAGS]) & 8u) {  // the handle's environment takes the background's place
+                        const uint32_t* ew = gp + (K.gen_flags(gp[G_FLAGS]) >> 8) + ((K.gen_flags(gp[G_FLAGS]) & 4u) ? kLensDw : 0u);
                         const EnvTexel* en = reinterpret_cast<const EnvTexel*>((uint64_t(ew[1]) << 32) | ew[0]);
                         const V3 ed = mk(__uint_as_float(POOL(F_DX, slot)), __uint_as_float(POOL(F_DY, slot)), __uint_as_float(POOL(F_DZ, slot)));
                         color = STATS ? environment_radiance_call(en, ew[2], ed) : environment_radiance(en, ew[2], ed);
@@ -978,7 +1013,7 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                             o = mk(gpf + G_POS);
                             V3 f = camera_target(mk(gpf + G_CENTER), mk(gpf + G_RIGHT), mk(gpf + G_UP), gpf[G_MMH], gpf[G_MMV], img_w,
                                                  img_h, row, col, rng);
-                            const uint32_t gen_flags = uint32_t(__builtin_amdgcn_readfirstlane(int(gp[G_FLAGS])));
+                            const uint32_t gen_flags = K.gen_flags(uint32_t(__builtin_amdgcn_readfirstlane(int(gp[G_FLAGS]))));
                             if (gen_flags & 4u)  // RBRT_FLAG_THIN_LENS (the same for every lane): the lens words at dword gen_flags >> 8
                                 lens_point(o, f, gpf + (gen_flags >> 8), rng);
                             d = normalize(f - o);
@@ -1027,11 +1062,11 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                 const V3 p = o + s_ht * d;  // same expression as inside the intersection routines
                 V3 n;
                 if (uint32_t(s_obj) < n_elem) {
-                    const uint32_t desc = P.n_elem_tris != 0u ? sc.elem[uint32_t(s_obj)] : uint32_t(s_obj);
+                    const uint32_t desc = K.n_elem_tris() != 0u ? sc.elem[uint32_t(s_obj)] : uint32_t(s_obj);
                     if (desc >> 31) n = mk(sc.tri + (desc & 0x7FFFFFFFu) * kTriDw + 9);  // triangle.rs:432: the stored normal
                     else n = p - mk(sc.sph + desc * kSphDw);                            // sphere.rs:56, unnormalised
                 } else {  // the stored face normal (mesh.rs:253-257), or a smooth mesh's shading normal
-                    n = mesh_shading_normal(lds_ptr<Normal4>(sc.mesh + (uint32_t(s_obj) - n_elem) * kMeshDw + MD_NORMALS), s_tri, o, d);
+                    n = mesh_shading_normal(lds_ptr<Normal4>(sc.mesh + K.mesh_index(uint32_t(s_obj) - n_elem) * kMeshDw + MD_NORMALS), s_tri, o, d);
                 }
                 DevMaterial m;
                 {
@@ -1058,7 +1093,7 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                 if (ok) {
                     if (lk != ST_DIEL) {  // attenuation (1,1,1) is an exact identity, not recorded
                         // the material entry the fold will look up: the object's, or a patterned lambertian's second one
-                        const uint32_t ent = lk == ST_LAMB ? surface_entry(sc.mat, uint32_t(s_obj), __float_as_uint(m.param), p) : uint32_t(s_obj);
+                        const uint32_t ent = lk == ST_LAMB && K.may_have_patterns() ? surface_entry(sc.mat, uint32_t(s_obj), __float_as_uint(m.param), p) : uint32_t(s_obj);
                         word |= ent << (8u * (nrec & 3u));
                         if ((nrec & 3u) == 3u) {
                             gseq[size_t(slot) * kSeqWords + (nrec >> 2)] = word;
@@ -1109,7 +1144,7 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                         }
                     }
                 };
-                if (P.n_elem_tris == 0u) {
+                if (K.n_elem_tris() == 0u) {
                     for (uint32_t i = 0; i < P.n_spheres; ++i) test_sphere(i, sc.sph + i * kSphDw);
                 } else {
                     for (uint32_t e = 0; e < n_elem; ++e) {
@@ -1129,8 +1164,8 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                     }
                 }
                 RBRT_MARK(gate);
-                gated = next_gated_mesh<STATS>(sc, P.n_meshes, 0, o, d, closest, lc);
-                next = gated < P.n_meshes ? uint32_t(ST_TRAV) : classify(sc, s_obj, depth);
+                gated = next_gated_mesh<STATS>(sc, K.n_meshes(), 0, o, d, closest, lc);
+                next = gated < K.n_meshes() ? uint32_t(ST_TRAV) : classify(sc, s_obj, depth);
             }
             // stay in registers? only sphere hits that need shading, while enough lanes do (or the wave
             // has no other work left), and for a bounded number of rounds
@@ -1138,7 +1173,7 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
             const bool cand = have_ray && next >= ST_LAMB;
             const uint32_t n_cand = uint32_t(__popcll(wballot(cand)));
             const bool go = n_cand != 0 && round < kMaxShadeRounds &&
-                            (more_work ? (round < P.shade_rounds && n_cand >= P.shade_cont_min) : true);
+                            (more_work ? (round < K.shade_rounds() && n_cand >= K.shade_cont_min()) : true);
             if (have_ray && !(cand && go)) {
                 POOL(F_OX, slot) = __float_as_uint(o.x);
                 POOL(F_OY, slot) = __float_as_uint(o.y);
@@ -1152,7 +1187,7 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                 POOL(F_WORD, slot) = word;
                 POOL(F_T, slot) = __float_as_uint(s_ht);
                 POOL(F_TRI, slot) = __float_as_uint(closest);  // (meaningful while the closest hit is a sphere)
-                POOL(F_META, slot) = pack_meta(depth, nrec, s_obj, gated < P.n_meshes ? gated : 0u);
+                POOL(F_META, slot) = pack_meta(depth, nrec, s_obj, gated < K.n_meshes() ? gated : 0u);
                 status[slot] = uint8_t(next);
             } else if (round == 1 && kind == ST_TERM && !have_ray && (is_main || is_gen)) {
                 status[slot] = ST_EMPTY;  // no work item left (or a pixel outside a ragged image edge)

@@ -11,7 +11,7 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 KERNEL_SOURCES = ("rbrt_amd/csrc/kernels.hip", "rbrt_amd/csrc/megakernel.inl", "rbrt_amd/csrc/features.inl", "rbrt_amd/csrc/short_paths.inl",
-                  "rbrt_amd/csrc/device_types.h",
+                  "rbrt_amd/csrc/device_types.h", "rbrt_amd/csrc/trace_knobs.h",
                   "rbrt_amd/csrc/bvh.cpp", "rbrt_amd/csrc/bvh.h", "rbrt_amd/csrc/bvh_device.hip", "rbrt_amd/csrc/bvh_device.h",
                   "rbrt_amd/csrc/denoise.hip", "rbrt_amd/csrc/tonemap.hip", "rbrt_amd/csrc/glare.hip", "rbrt_amd/csrc/guided.hip", "rbrt_amd/csrc/temporal.hip", "rbrt_amd/csrc/upsample.hip", "rbrt_amd/csrc/despike.hip", "rbrt_amd/csrc/compare.hip",
                   "rbrt_amd/csrc/api.cpp", "rbrt_amd/csrc/api_common.h", "rbrt_amd/csrc/frame_stages.cpp", "rbrt_amd/csrc/selftests.cpp",

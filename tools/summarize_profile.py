@@ -48,7 +48,7 @@ for f in glob.glob(str(SRC / "*" / "*" / "*counter_collection.csv")):
 for pass_name, f in newest.items():
     for r in csv.DictReader(open(f)):
         k = r["Kernel_Name"]
-        if "trace_megakernel<false, false>" not in k:  # (the product build: no counters, not the helper build)
+        if "trace_megakernel<false, false, " not in k:  # (the product builds, general and PLAIN: no counters, not the helper builds)
             continue
         per[k][r["Counter_Name"]] += float(r["Counter_Value"])
         ndisp[(k, r["Counter_Name"])].add((pass_name, r["Dispatch_Id"]))  # (a counter collected in two passes: averaged over both)

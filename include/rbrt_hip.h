@@ -56,7 +56,8 @@ extern "C" {
                               rbrt_hip_supported_flags, nor the smooth shading of meshes (rbrt_scene_shading_t and the
                               two *_shaded entry points: rbrt_mesh_t and rbrt_scene_t stay as they are), nor solid patterns
                               (rbrt_scene_patterns_t and the two *_patterned entry points, detected by the symbol), nor the camera shutter (rbrt_shutter_t and
-                              rbrt_hip_scene_set_shutter: handle state like the environment, detected by the symbol), nor adaptive
+                              rbrt_hip_scene_set_shutter: handle state like the environment, detected by the symbol), nor moving spheres (rbrt_motion_t and
+                              rbrt_hip_scene_set_motion: handle state like the shutter, detected by the symbol), nor adaptive
                               sampling (rbrt_hip_render_adaptive with its two structs: an added entry point), nor the
                               denoiser (rbrt_denoise_opts_t, rbrt_denoise_opts_default, rbrt_hip_denoise_halves and
                               rbrt_hip_scene_denoise: added entry points), nor environment lighting (rbrt_environment_t and
@@ -392,7 +393,8 @@ int rbrt_hip_render_device(rbrt_hip_scene_t* scene, const rbrt_camera_t* cam,
  * writes the mean to d_radiance and its quantisation to d_rgb8 (either may be NULL). Calls must cover [0, spp) in
  * ascending, non-overlapping ranges; the final image is then bit-identical to one rbrt_hip_render_device call,
  * because the per-pixel additions happen in the same order. A checkpoint is d_accum plus sample_end. Every pass of one
- * series must use the same seed, lens and shutter (rbrt_hip_scene_set_shutter: do not call it between two passes). */
+ * series must use the same seed, lens, shutter and motion (rbrt_hip_scene_set_shutter, rbrt_hip_scene_set_motion: do not call
+ * them between two passes). */
 int rbrt_hip_render_pass(rbrt_hip_scene_t* scene, const rbrt_camera_t* cam, const rbrt_render_opts_t* opts,
                          void* stream, uint32_t sample_begin, uint32_t sample_end, float* d_accum,
                          float* d_radiance, uint8_t* d_rgb8);
@@ -594,6 +596,47 @@ typedef struct rbrt_shutter {
  * RBRT_ERR_INVALID_ARG, before the device is touched, the handle keeping the shutter it had: scene NULL; a travel that is not
  * finite; reserved != 0. */
 int rbrt_hip_scene_set_shutter(rbrt_hip_scene_t* scene, const rbrt_shutter_t* shutter);
+
+/* ---- Moving spheres: object motion blur on the shutter's time draw -------------------------------------------------------------
+ * No counterpart in the reference. A handle may carry a motion: one vector travel_i (scene units) per sphere of the scene, the
+ * sphere's translation between the opening and the closing of the shutter. The sphere's `center` in the scene is its position
+ * at the opening.
+ *
+ * The draw. A sample's ray (o, d) is made exactly as without a motion: jitter, lens draws, d = normalize(F - o). If the handle
+ * has a shutter OR a motion, the next draw of the stream is t (u in [0, 1)): ONE draw for both, because camera and objects
+ * share one exposure. With a shutter, o += t * travel as in "Camera shutter". With a motion, t belongs to the sample for its
+ * whole path. A handle with a shutter and no motion renders bit for bit what it renders without this section; so does a
+ * handle with neither. A motion whose vectors are all zero still draws: its image is that of a zero-travel shutter.
+ *
+ * The sphere. Wherever a path of that sample reads sphere i's centre, it reads, in float32, unfused, a product and a sum per
+ * component,
+ *     c_i(t)_c = center_i_c + (t * travel_i_c)                 for c = x, y, z
+ * in the hit test of every ray of the path, camera ray and bounces alike, and in the normal p - c_i(t). The radius, the
+ * materials, meshes, BasicTriangle elements, the background and the environment do not move. A solid checker
+ * (rbrt_scene_patterns_t) is a pattern of world space and stays where it is: the surface of a moving sphere moves through it.
+ *
+ * The motion is a STATE OF THE HANDLE, like the shutter. While one is set, rbrt_hip_render_device, _render_pass,
+ * _render_adaptive (and the denoisers that read its halves) and rbrt_hip_render_features (the depth and the normal of the
+ * moved sphere) honour it, for every tile_rank / tile_world, in helper launches and in the short-path stage. Every pass of one
+ * rbrt_hip_render_pass series must use the same motion. rbrt_hip_trace_rays and the ray hooks have no sample stream and see
+ * the spheres at their opening positions, as they see no shutter. The one-shot rbrt_hip_render* calls cannot carry a motion,
+ * for the reason they cannot carry a shutter. There is no flag bit and the ABI version stays 2: a host detects the capability
+ * by the symbol. The tile pass widens sphere i's margins by |travel_i| (kernels.hip primary_cull_kernel, "Moving spheres");
+ * a scene with a motion never runs the trace kernel's plain build. Not built: moving meshes and BasicTriangles, rotation or
+ * other paths than a straight line, objects that advance between the frames of a stream (every frame exposes the same sweep),
+ * motion vectors as a feature buffer, a pattern that travels with its sphere, a time argument for rbrt_hip_trace_rays. */
+typedef struct rbrt_motion {
+    uint32_t n_spheres;  /* the scene's sphere count */
+    uint32_t reserved;   /* 0 */
+    const float* travel; /* [n_spheres][3], in the order of rbrt_scene_t::spheres; scene units; finite */
+} rbrt_motion_t;
+
+/* Sets, replaces (motion != NULL) or clears (motion == NULL: no motion) the handle's motion. The vectors are copied: the call
+ * waits for the handle's launches in flight and puts them on the device. The threading rule of rbrt_hip_render_device holds.
+ * RBRT_ERR_INVALID_ARG, before the device is touched, the handle keeping the motion it had: scene NULL; n_spheres other than
+ * the scene's sphere count; reserved != 0; travel NULL with n_spheres > 0; a component that is not finite; a
+ * center + travel that is not finite in float32. */
+int rbrt_hip_scene_set_motion(rbrt_hip_scene_t* scene, const rbrt_motion_t* motion);
 
 /* ---- Display transform: exposure, automatic exposure and tone mapping --------------------------------------------------------
  * No counterpart in the reference, whose only way from radiance to a picture is the quantisation (sqrt(c) * 256) as u8

@@ -104,7 +104,8 @@ int rbrt_hip_debug_guided_staging(int max_step);
  *   out_obj[n]    -1 on miss, sphere index in [0,n_spheres), or n_spheres + mesh index
  *   out_tri[n]    winning triangle index (reference numbering) for mesh hits, else -1
  *   out_dist[n]   dist_from_ray_orig of the winner (lib.rs:35)
- * The rays are traced as given: the handle's shutter (rbrt_hip_scene_set_shutter) does not move them. */
+ * The rays are traced as given: the handle's shutter (rbrt_hip_scene_set_shutter) does not move them, and they see the spheres
+ * at their opening positions whatever motion the handle has (rbrt_hip_scene_set_motion): there is no sample stream to draw t from. */
 int rbrt_hip_trace_rays(rbrt_hip_scene_t* scene, const float* rays, size_t n, float min_dist,
                         float max_dist, float* out_t, int32_t* out_obj, int32_t* out_tri,
                         float* out_dist);

@@ -105,6 +105,13 @@ pub struct RbrtShutter {                               // rbrt_shutter_t: the ca
     pub reserved: u32,                                 // 0
 }
 
+#[repr(C)]
+pub struct RbrtMotion {                                // rbrt_motion_t: a travel per sphere while the shutter is open, 16 bytes
+    pub n_spheres: u32,                                // the scene's sphere count
+    pub reserved: u32,                                 // 0
+    pub travel: *const f32,                            // [n_spheres][3], scene units; finite; copied by the call
+}
+
 #[link(name = "rbrt_hip")]
 extern "C" {
     pub fn rbrt_render_opts_default(opts: *mut RbrtRenderOpts);
@@ -120,6 +127,8 @@ extern "C" {
                                            device: c_int, out: *mut *mut c_void) -> c_int;
     // the camera shutter: a state of the handle, like the environment; shutter = null clears it. Detected by the symbol (no flag bit)
     pub fn rbrt_hip_scene_set_shutter(scene: *mut c_void, shutter: *const RbrtShutter) -> c_int;
+    // moving spheres: a state of the handle that shares the shutter's draw; motion = null clears it. Detected by the symbol
+    pub fn rbrt_hip_scene_set_motion(scene: *mut c_void, motion: *const RbrtMotion) -> c_int;
     // device pointers; needs no scene handle. A host detects it by the symbol (the ABI version stays 2).
     pub fn rbrt_tonemap_opts_default(opts: *mut RbrtTonemapOpts);
     pub fn rbrt_hip_tonemap(device: c_int, stream: *mut c_void, d_radiance: *const f32, n_pixels: usize, opts: *const RbrtTonemapOpts,

@@ -222,6 +222,20 @@ class HipScene:
         sh.reserved = int(reserved)
         abi.check(self._lib.rbrt_hip_scene_set_shutter(self._h, C.byref(sh)))
 
+    def set_motion(self, travels, *, n_spheres: int | None = None, reserved: int = 0, null_travel: bool = False):
+        """Sets the handle's motion (rbrt_hip_scene_set_motion): `travels` = (n_spheres, 3), every sphere's translation during
+        the exposure in scene units, in the order of the scene's spheres; None clears it. `n_spheres`, `reserved` and
+        `null_travel` put other values into the struct (tests of the refusals)."""
+        if travels is None:
+            abi.check(self._lib.rbrt_hip_scene_set_motion(self._h, None))
+            return
+        tv = np.ascontiguousarray(np.asarray(travels, np.float32).reshape(-1, 3))
+        mo = abi.Motion()
+        mo.n_spheres = int(len(tv) if n_spheres is None else n_spheres)
+        mo.reserved = int(reserved)
+        mo.travel = None if null_travel else tv.ctypes.data_as(abi.f32p)
+        abi.check(self._lib.rbrt_hip_scene_set_motion(self._h, C.byref(mo)))
+
     def environment_lookup(self, dirs):
         """The environment's radiance for each direction, used as it is (rbrt_hip_debug_environment; test hook): float32
         (n, 3)."""

@@ -263,6 +263,11 @@ class Shutter(C.Structure):  # rbrt_shutter_t
     _fields_ = [("travel", C.c_float * 3), ("reserved", C.c_uint32)]
 
 
+class Motion(C.Structure):  # rbrt_motion_t
+    """A travel per sphere between the opening and the closing of the shutter, in scene units: travel = float[n_spheres][3]."""
+    _fields_ = [("n_spheres", C.c_uint32), ("reserved", C.c_uint32), ("travel", f32p)]
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("rays", C.c_uint64),
@@ -342,6 +347,7 @@ HIP_SYMBOLS = {
     "rbrt_hip_scene_denoise": (C.c_int, [C.c_void_p, C.POINTER(DenoiseOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rbrt_hip_scene_set_environment": (C.c_int, [C.c_void_p, C.POINTER(Environment)]),
     "rbrt_hip_scene_set_shutter": (C.c_int, [C.c_void_p, C.POINTER(Shutter)]),
+    "rbrt_hip_scene_set_motion": (C.c_int, [C.c_void_p, C.POINTER(Motion)]),
     "rbrt_feature_opts_default": (None, [C.POINTER(FeatureOpts)]),
     "rbrt_hip_render_features": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderOpts), C.POINTER(FeatureOpts), C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -627,6 +633,10 @@ def load_host() -> C.CDLL:
     lib.rbrt_host_scene_shutter_travel.argtypes = [C.c_void_p]
     lib.rbrt_host_shutter_fingerprint.restype = C.c_uint64
     lib.rbrt_host_shutter_fingerprint.argtypes = [f32p, C.c_uint64]
+    lib.rbrt_host_scene_motion.restype = f32p
+    lib.rbrt_host_scene_motion.argtypes = [C.c_void_p]
+    lib.rbrt_host_motion_fingerprint.restype = C.c_uint64
+    lib.rbrt_host_motion_fingerprint.argtypes = [f32p, C.c_uint32, C.c_uint64]
     lib.rbrt_host_scene_scene.restype = C.POINTER(Scene)
     lib.rbrt_host_scene_scene.argtypes = [C.c_void_p]
     lib.rbrt_host_scene_shading.restype = C.POINTER(SceneShading)
@@ -697,6 +707,9 @@ class HostScene:
         tp = self._lib.rbrt_host_scene_shutter_travel(self._h)
         self.shutter_travel = (float(tp[0]), float(tp[1]), float(tp[2])) if tp else None
         self.struct = self._lib.rbrt_host_scene_scene(self._h).contents
+        # the spheres' shutter_travel keys as float32 (n_spheres, 3) (what HipScene.set_motion takes), else None
+        mp = self._lib.rbrt_host_scene_motion(self._h)
+        self.motion = np.ctypeslib.as_array(mp, shape=(self.struct.n_spheres, 3)).astype(np.float32).copy() if mp else None
         sp = self._lib.rbrt_host_scene_shading(self._h)  # NULL unless some mesh is smooth
         self.shading = sp.contents if sp else None
         pp = self._lib.rbrt_host_scene_patterns(self._h)  # NULL unless some object carries a checker
@@ -796,6 +809,15 @@ def shutter_fingerprint(travel, h: int) -> int:
         return int(lib.rbrt_host_shutter_fingerprint(None, h))
     tv = (C.c_float * 3)(*[float(np.float32(v)) for v in travel])
     return int(lib.rbrt_host_shutter_fingerprint(tv, h))
+
+
+def motion_fingerprint(travels, h: int) -> int:
+    """What a motion adds to the checkpoint fingerprint `h` (rbrt_host_motion_fingerprint); travels None: no motion."""
+    lib = load_host()
+    if travels is None:
+        return int(lib.rbrt_host_motion_fingerprint(None, 0, h))
+    tv = np.ascontiguousarray(np.asarray(travels, np.float32).reshape(-1, 3))
+    return int(lib.rbrt_host_motion_fingerprint(tv.ctypes.data_as(f32p), len(tv), h))
 
 
 def save_image(path, rgb8: np.ndarray) -> None:

@@ -32,8 +32,9 @@ hipError_t launch_trace_megakernel(const TraceParams& P, uint32_t n_waves, bool 
 hipError_t launch_trace_helper(const TraceParams& P, uint32_t n_waves, bool plain, hipStream_t stream);
 size_t megakernel_gseq_bytes(uint32_t n_waves);
 size_t megakernel_gstack_bytes(uint32_t n_waves);
+size_t megakernel_gtime_bytes(uint32_t n_waves);
 size_t megakernel_lds_bytes(uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris, uint32_t thin_lens,
-                            uint32_t environment, uint32_t pattern_dw, uint32_t shutter);
+                            uint32_t environment, uint32_t pattern_dw, uint32_t shutter, uint32_t motion);
 int megakernel_occupancy_per_cu(size_t lds_bytes);
 hipError_t launch_primary_cull(const TraceParams& P, hipStream_t stream);
 hipError_t launch_sky_resolve(const TraceParams& P, const ResolveParams& R, hipStream_t stream);
@@ -246,6 +247,15 @@ struct rbrt_hip_scene {
     // no draw is made for it
     bool has_shutter = false;
     float travel[3] = {0.0f, 0.0f, 0.0f};
+    // The motion (rbrt_hip_scene_set_motion): a travel per sphere, [n_spheres][3] in the DEVICE array's order (sphere_src: the
+    // caller's index of device sphere i, element_tables), allocated at the first call and kept; has_motion false: never read.
+    // motion_gen numbers the calls: a tile table made for one motion never serves another (TileKey). h_spheres: the device
+    // array's host copy, for the call's check of centre + travel.
+    bool has_motion = false;
+    float* d_motion = nullptr;
+    uint32_t motion_gen = 0;
+    std::vector<DevSphere> h_spheres;
+    std::vector<uint32_t> sphere_src;
     // workspace, grown on demand
     // Frame pipeline: consecutive trace launches (the batches of one render, or successive renders) alternate
     // over `pipeline` lanes. Every lane has its own sample buffer, work counters and per-wave scratch, and --
@@ -273,6 +283,7 @@ struct rbrt_hip_scene {
         } bufs[1];
         uint32_t* d_gseq = nullptr;
         uint32_t* d_gstack = nullptr;
+        float* d_gtime = nullptr;  // TraceParams::gtime: allocated by the lane's first motion launch
         // The tile pass (kernels.hip primary_cull_kernel + tile_lists_kernel): which of the rank's tiles see only the
         // background, for one camera and tile partition (`key`). A lane has TWO sets of tables: the pass for a camera the
         // lane has not seen is issued when the CALL is made, on the scene's high-priority `prep_stream`, into the set the
@@ -288,6 +299,7 @@ struct rbrt_hip_scene {
             float lens_u[3], lens_v[3], focus_scale;
             uint32_t shutter;    // the handle's shutter when the tables were made (all zero without one): it widens the margins
             float travel[3];
+            uint32_t motion_gen;  // the handle's motion when the tables were made, by the number of the call that set it (0 without one)
         };
         struct TileSet {
             uint32_t* d_cull = nullptr;    // [n_tiles]
@@ -950,6 +962,7 @@ int fill_trace_params(const rbrt_hip_scene* s, const rbrt_camera_t* cam, const r
         P.shutter = 1u;
         for (int c = 0; c < 3; ++c) P.travel[c] = s->travel[c];
     }
+    if (cam && s->has_motion) P.motion = s->d_motion, P.motion_gen = s->motion_gen;  // (the same: the ray hooks see the spheres at the opening)
     P.n_spheres = s->n_spheres;
     P.n_meshes = s->n_meshes;
     P.n_elem_tris = s->n_elem_tris;
@@ -1419,6 +1432,8 @@ int build_mesh(rbrt_hip_scene* s, const rbrt_mesh_t& m, const rbrt_mesh_normals_
 // The scene's tables on the device, and its counters at zero.
 int upload_scene_tables(rbrt_hip_scene* s, const ElementTables& t, const std::vector<uint32_t>& elems, const std::vector<DevMesh>& meshes) {
     if (int rc = upload(s, t.spheres, &s->d_spheres)) return rc;
+    s->h_spheres = t.spheres, s->sphere_src.resize(t.spheres.size());
+    for (uint32_t i = 0; i < uint32_t(t.spheres.size()); ++i) s->sphere_src[i] = s->n_elem_tris == 0 ? elems[i] : i;  // (element_tables' order)
     if (s->n_elem_tris != 0) {
         if (int rc = upload(s, t.etris, &s->d_elem_tris)) return rc;
         if (int rc = upload(s, elems, &s->d_elems)) return rc;
@@ -1479,7 +1494,7 @@ int size_grid(rbrt_hip_scene* s, int device, uint32_t waves_per_cu) {
     if (s->stack_entries > s->stack_need) s->stack_entries = s->stack_need;
     // resident waves per CU: LDS-limited (160 KiB per CU), at most 5 per SIMD (VGPR budget). (A thin-lens launch stages 32
     // bytes more; where that costs it a wave per CU the waves of the grid beyond the resident ones start as others end.)
-    int per_cu = int((160u * 1024u) / megakernel_lds_bytes(s->stack_entries, s->n_spheres, s->n_meshes, s->n_elem_tris, 0u, 0u, pattern_table_dwords(s->n_patterns), 0u));
+    int per_cu = int((160u * 1024u) / megakernel_lds_bytes(s->stack_entries, s->n_spheres, s->n_meshes, s->n_elem_tris, 0u, 0u, pattern_table_dwords(s->n_patterns), 0u, 0u));
     if (per_cu > 20) per_cu = 20;
     if (per_cu < 1) per_cu = 1;
     if (waves_per_cu != 0) per_cu = int(waves_per_cu), s->waves_fixed = true;
@@ -1878,6 +1893,7 @@ rbrt_hip_scene::Lane::TileKey tile_key(const TraceParams& P, uint32_t list_mode)
     for (int c = 0; c < 3; ++c) k.lens_u[c] = P.lens_u[c], k.lens_v[c] = P.lens_v[c];
     k.shutter = P.shutter;
     for (int c = 0; c < 3; ++c) k.travel[c] = P.travel[c];
+    k.motion_gen = P.motion ? P.motion_gen : 0u;
     return k;
 }
 
@@ -1995,6 +2011,14 @@ int issue_batches(rbrt_hip_scene* s, const CallPlan& c, const rbrt_render_opts_t
                          : 0u;  // (contiguous shards; with half grids three deep small launches preferred stripes of 4, round 3)
         P.sample_buf = B.d_sample_buf, P.work_counter = B.d_work_counter, P.gseq = L.d_gseq, P.gstack = L.d_gstack;
         P.helper_words = L.d_helper_words, P.helper_seq = ++L.seq, P.wave_base = 0u;
+        if (P.motion) {  // a motion launch: the draw of the path in every pool slot, beside gseq (helper launches read L.open.P)
+            if (!L.d_gtime) {
+                void* p = nullptr;
+                HIP_TRY(dev_alloc(s, megakernel_gtime_bytes(s->scratch_waves), &p));
+                L.d_gtime = static_cast<float*>(p);
+            }
+            P.gtime = L.d_gtime;
+        }
         // which of the lane's two sets of tile tables this launch reads: the one made for this camera and partition, else
         // the one used longer ago, filled now
         rbrt_hip_scene::Lane::TileSet* S = nullptr;
@@ -2045,7 +2069,7 @@ int issue_batches(rbrt_hip_scene* s, const CallPlan& c, const rbrt_render_opts_t
         }
         if (piped) HIP_TRY(hipEventRecord(L.ev_ready, ts));  // (behind everything the launch waits for: a helper launch waits for this)
         // (the PLAIN build: the same kernel with the default knobs and the one-mesh scene built in, megakernel.inl; a counting
-        // launch, a lab knob, a second mesh, an element triangle, a lens, a shutter, a map or a pattern run the general one)
+        // launch, a lab knob, a second mesh, an element triangle, a lens, a shutter, a motion, a map or a pattern run the general one)
         const bool plain = !stats && !s->trace_build_general && trace_params_are_plain(P);
         s->last_trace_build = plain ? RBRT_TRACE_BUILD_PLAIN : RBRT_TRACE_BUILD_GENERAL;
         HIP_TRY(launch_trace_megakernel(P, grid, stats, plain, ts));
@@ -2505,6 +2529,43 @@ int rbrt_hip_scene_set_shutter(rbrt_hip_scene_t* s, const rbrt_shutter_t* shutte
     return RBRT_OK;
 }
 
+// The handle's motion (rbrt_hip.h "Moving spheres"). Everything is checked before the device is touched; then, like the
+// environment, the call waits for the launches that read the old travels and puts the new ones on the device.
+int rbrt_hip_scene_set_motion(rbrt_hip_scene_t* s, const rbrt_motion_t* motion) {
+    if (!s) return fail(RBRT_ERR_INVALID_ARG, "set_motion: null scene");
+    std::vector<float> dev;  // in the device array's order
+    if (motion) {
+        if (motion->n_spheres != s->n_spheres) return fail(RBRT_ERR_INVALID_ARG, "set_motion: n_spheres differs from the scene's sphere count");
+        if (motion->reserved != 0u) return fail(RBRT_ERR_INVALID_ARG, "set_motion: reserved must be 0");
+        if (motion->n_spheres != 0u && !motion->travel) return fail(RBRT_ERR_INVALID_ARG, "set_motion: null travel");
+        dev.resize(size_t(s->n_spheres) * 3u);
+        for (uint32_t i = 0; i < s->n_spheres; ++i) {
+            const float* tv = motion->travel + 3u * size_t(s->sphere_src[i]);
+            for (int c = 0; c < 3; ++c) {
+                if (!std::isfinite(tv[c])) return fail(RBRT_ERR_INVALID_ARG, "set_motion: sphere " + std::to_string(s->sphere_src[i]) + " has a travel that is not finite");
+                const volatile float end = s->h_spheres[i].center[c] + tv[c];  // (float32, as the kernels add it)
+                if (!std::isfinite(end)) return fail(RBRT_ERR_INVALID_ARG, "set_motion: sphere " + std::to_string(s->sphere_src[i]) + ": center + travel is not finite");
+                dev[3u * i + c] = tv[c];
+            }
+        }
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    std::lock_guard<std::mutex> watcher_lock(s->mu);
+    if (motion) {
+        HIP_TRY(hipDeviceSynchronize());
+        if (!s->d_motion) {
+            void* p = nullptr;
+            HIP_TRY(dev_alloc(s, std::max<size_t>(dev.size() * sizeof(float), 16), &p));
+            s->d_motion = static_cast<float*>(p);
+        }
+        if (!dev.empty()) HIP_TRY(hipMemcpy(s->d_motion, dev.data(), dev.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    s->has_motion = motion != nullptr;
+    s->motion_gen += 1u;
+    if (s->motion_gen == 0u) s->motion_gen = 1u;
+    return RBRT_OK;
+}
+
 int rbrt_hip_scene_stats(rbrt_hip_scene_t* s, rbrt_hip_stats_t* out) {
     if (!s || !out) return fail(RBRT_ERR_INVALID_ARG, "stats: null argument");
     HIP_TRY(hipSetDevice(s->device));
@@ -2589,7 +2650,7 @@ int rbrt_hip_scene_info(rbrt_hip_scene_t* s, rbrt_hip_scene_info_t* out) {
     out->bvh_stack_need = s->stack_need;
     out->n_nodes = s->total_nodes, out->n_triangles = s->total_tris;
     out->trace_waves = s->n_waves;
-    out->lds_bytes_per_wave = uint32_t(megakernel_lds_bytes(s->stack_entries, s->n_spheres, s->n_meshes, s->n_elem_tris, 0u, 0u, pattern_table_dwords(s->n_patterns), 0u));
+    out->lds_bytes_per_wave = uint32_t(megakernel_lds_bytes(s->stack_entries, s->n_spheres, s->n_meshes, s->n_elem_tris, 0u, 0u, pattern_table_dwords(s->n_patterns), 0u, 0u));
     (void)hipSetDevice(s->device);
     out->occupancy_api_waves_per_cu = uint32_t(megakernel_occupancy_per_cu(out->lds_bytes_per_wave));
     out->n_cus = s->n_cus;

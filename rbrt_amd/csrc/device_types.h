@@ -223,6 +223,12 @@ struct TraceParams {
     // 0 (no shutter): the travel is never read and no draw is made for it
     uint32_t shutter;
     float travel[3];
+    // The handle's motion (rbrt_hip_scene_set_motion): motion = [n_spheres][3], sphere i's translation during the exposure, on the
+    // device; null (no motion): never read, and without a shutter no draw is made. gtime: [n_waves][kPool], the draw t of the path
+    // in each pool slot of the trace kernel, beside gseq; allocated, written and read in a motion launch only
+    const float* motion;
+    float* gtime;
+    uint32_t motion_gen;  // host only: the number of the rbrt_hip_scene_set_motion call the travels are from (the tile-table key)
     // The handle's environment (rbrt_hip_scene_set_environment): (env_n + 1)^2 texels of 16 bytes; null: bg / the sky gradient
     const EnvTexel* env_nodes;
     uint32_t env_n;

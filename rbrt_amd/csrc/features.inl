@@ -33,10 +33,13 @@ __global__ __launch_bounds__(kFeatureBlock) void features_kernel(const TracePara
             lens_point(o, f, lens, rng);
         }
         const V3 d = normalize(f - o);
-        if (P.shutter) shutter_origin(o, P.travel, rng);  // (the render's own camera rays: the handle's shutter moves them too)
+        // (the render's own camera rays: the handle's shutter moves them too, and its motion the spheres they see -- one draw)
+        float mt = 0.0f;
+        if (P.shutter || P.motion) mt = rng.next_f32();
+        if (P.shutter) shutter_origin(o, P.travel, mt);
         HitRec h;
         LocalCounters lc = {0, 0, 0, 0, 0};
-        scene_hit<false>(P, o, d, stack, uint32_t(kFeatureBlock), h, lc);
+        scene_hit<false>(P, o, d, stack, uint32_t(kFeatureBlock), h, lc, P.motion, mt);
         if (s == 0) first_obj = h.obj;
         V3 sa = mk(0.0f, 0.0f, 0.0f), sn = mk(0.0f, 0.0f, 0.0f);  // a miss: every channel adds +0
         float sz = 0.0f, sc = 0.0f;
@@ -51,7 +54,8 @@ __global__ __launch_bounds__(kFeatureBlock) void features_kernel(const TracePara
             if (uint32_t(h.obj) < n_elem) {
                 const uint32_t desc = P.elems != nullptr ? P.elems[h.obj] : uint32_t(h.obj);
                 if (desc >> 31) g = mk(P.elem_tris[desc & 0x7FFFFFFFu].normal);  // triangle.rs:432
-                else g = (o + h.t * d) - mk(P.spheres[desc].center);             // sphere.rs:56
+                else g = (o + h.t * d) - (P.motion ? sphere_centre_at(P.spheres[desc].center, P.motion + desc * kMotionDw, mt)
+                                                   : mk(P.spheres[desc].center));  // sphere.rs:56
             } else {
                 g = mesh_shading_normal(P.meshes[uint32_t(h.obj) - n_elem].normals, h.tri, o, d);
             }

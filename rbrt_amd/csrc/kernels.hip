@@ -519,9 +519,11 @@ struct HitRec {
 };
 
 // scene.rs:19-43: spheres in order, then meshes in order, strictly smaller distance wins.
+// motion: null, or the spheres' travels [n_spheres][3] with the path's draw mt (sphere_centre_at, below).
+__device__ __forceinline__ V3 sphere_centre_at(const float* centre, const float* travel, float t);
 template <bool STATS>
 __device__ __forceinline__ void scene_hit(const TraceParams& P, V3 o, V3 d, uint32_t* stack, uint32_t stride,
-                                          HitRec& h, LocalCounters& lc) {
+                                          HitRec& h, LocalCounters& lc, const float* motion = nullptr, float mt = 0.0f) {
     float closest = 3.40282347e+38f;  // f32::MAX
     h.obj = -1;
     h.t = 0.0f;
@@ -536,7 +538,8 @@ __device__ __forceinline__ void scene_hit(const TraceParams& P, V3 o, V3 d, uint
             hit = basic_triangle_hit(P.elem_tris[desc & 0x7FFFFFFFu].v0, o, d, P.min_dist, P.max_dist, t, dist);
         } else {
             const DevSphere sp = P.spheres[desc];
-            hit = sphere_hit(mk(sp.center), sp.radius, o, d, P.min_dist, P.max_dist, t, dist, P.counters);
+            const V3 c = motion ? sphere_centre_at(sp.center, motion + desc * 3u, mt) : mk(sp.center);
+            hit = sphere_hit(c, sp.radius, o, d, P.min_dist, P.max_dist, t, dist, P.counters);
         }
         if (hit && dist < closest) {
             closest = dist;
@@ -770,11 +773,15 @@ constexpr uint32_t kLensDw = 8;  // lens words staged in the megakernel's LDS fo
 // lens and normalize(f - o) included -- the next draw of its stream places the whole camera on its way from the opening to
 // the closing position: o += t * travel, unfused, a product and a sum per component. d is NOT recomputed: a translation
 // does not turn a ray. The bounce draws follow. A ray that hits nothing depends on d only, so the sky resolves never call this.
-__device__ __forceinline__ void shutter_origin(V3& o, const float* travel, Rng& rng) {
-    const float t = rng.next_f32();
-    o = o + t * mk(travel);
-}
+__device__ __forceinline__ void shutter_origin(V3& o, const float* travel, float t) { o = o + t * mk(travel); }
+__device__ __forceinline__ void shutter_origin(V3& o, const float* travel, Rng& rng) { shutter_origin(o, travel, rng.next_f32()); }
 constexpr uint32_t kShutterDw = 4;  // words staged in the megakernel's LDS for a shutter launch: travel, pad
+// Moving spheres (rbrt_hip.h "Moving spheres"): the same draw t -- ONE draw for the shutter and the motion,
+// camera and objects share an exposure -- belongs to the sample for its whole path, and wherever a path reads a sphere's
+// centre it reads c(t) = c + (t * travel_i), unfused, a product and a sum per component: the hit test of every ray of the
+// path and the normal p - c(t). The radius, the materials and everything that is not a sphere stay where they are.
+__device__ __forceinline__ V3 sphere_centre_at(const float* centre, const float* travel, float t) { return mk(centre) + t * mk(travel); }
+constexpr uint32_t kMotionDw = 3;  // words per sphere staged in the megakernel's LDS for a motion launch: its travel
 
 // lib.rs:68-71: what a ray that hits nothing sees; the direction as it is (not re-normalised).
 // `constant` (RBRT_FLAG_CONSTANT_BACKGROUND): bg itself.
@@ -814,7 +821,8 @@ __device__ __noinline__ V3 environment_radiance_call(const EnvTexel* nodes, uint
 constexpr uint32_t kEnvDw = 4;  // words staged in the megakernel's LDS for a launch with a map: the address (2), n, pad
 
 __host__ __device__ inline uint32_t megakernel_lds_dwords(uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris,
-                                                          uint32_t thin_lens, uint32_t environment, uint32_t pattern_dw, uint32_t shutter);
+                                                          uint32_t thin_lens, uint32_t environment, uint32_t pattern_dw, uint32_t shutter,
+                                                          uint32_t motion);
 #include "megakernel.inl"
 
 // lib.rs:116-122: (sqrt(c) * 256) as u8 — Rust's float->int cast saturates and maps NaN to 0.
@@ -1054,6 +1062,19 @@ __global__ __launch_bounds__(kSmallBlock) void sky_resolve_kernel(const TracePar
 // the same centre; the forward rule R_out < l keeps every origin outside the sphere. Without a shutter org_a = a exactly (the
 // branch is not taken) and every rule is the one above, bit for bit. A travel so long that R_out >= l for every object, or
 // a NaN, makes every comparison false: nothing is culled.
+//
+// Moving spheres (rbrt_hip.h "Moving spheres"; TraceParams::motion). The camera ray of a sample with the draw t tests sphere i
+// at c_i(t) = fl(c_i + fl(t travel_i)), 0 <= t < 1. A line from o' meets the ball around c_i(t) as the line from
+// o' - (c_i(t) - c_i), with the same direction, meets the ball around c_i: the argument above for a moved origin, per
+// sphere. That origin is within org_a + |c_i(t) - c_i| of the position, and |c_i(t) - c_i| <= |travel_i| + the float error of
+// the two operations: the product is one rounding per component (at most u |travel_i| in length), the sum another (at most
+// u (|c_i| + |travel_i|)); 16 u (|c_i| + |travel_i|) covers both many times over. Hence, for sphere i alone,
+//     org_a_i = org_a + |travel_i| + 16 u (|c_i| + |travel_i|)
+// wherever org_a stands in its rule: lo, slack, reach, r_out, r_in. The direction is the unmoved ray's, so the cone, the
+// caps and w keep their numbers, and mesh boxes -- which do not move -- keep org_a. The shutter's t and the motion's t are
+// the same draw, which the bound never uses: it holds for every pair of them. Without a motion org_a_i = org_a exactly (the
+// branch is not taken) and every word is what it was, bit for bit. The bit proves the CAMERA ray's test fails; a bounce ray
+// of the path tests every sphere.
 // ---------------------------------------------------------------------------------------------
 struct D3 {
     double x, y, z;
@@ -1190,6 +1211,7 @@ __global__ __launch_bounds__(kCullBlock, 4) void primary_cull_kernel(const Trace
     cone.cos_rho = cos(rho), cone.sin_rho = sin(rho);
     cone.cos_w = cos(w_dir), cone.sin_w = sin(w_dir);
 
+    const double org_all = org_a;  // (the spheres shadow the name with their own: "Moving spheres")
     const uint32_t n_elem = P.n_spheres + P.n_elem_tris;
     uint32_t word = 0;
     bool all = n_elem <= 24u && P.n_meshes <= 7u && P.n_elem_tris == 0u;
@@ -1200,6 +1222,13 @@ __global__ __launch_bounds__(kCullBlock, 4) void primary_cull_kernel(const Trace
             const DevSphere sp = P.spheres[desc];
             const D3 q = d3(sp.center) - pos;
             const double r = double(sp.radius), l = dlen(q);
+            // Moving spheres (header, "Moving spheres"): this sphere's own bound on where a ray starts RELATIVE TO IT. Without
+            // a motion it is org_a itself (the branch is not taken).
+            double org_a = org_all;
+            if (P.motion) {
+                const double tl = dlen(d3(P.motion + desc * kMotionDw));
+                org_a = org_all + tl + 16.0 * (1.0 / 16777216.0) * (dlen(d3(sp.center)) + tl);
+            }
             if (r > 0.0 && r < 1e30 && l < 1e30) {  // (false for NaN)
                 // (the second term is the analysed one, 15x the bound in the header; the others are loose change on top)
                 const double lo = l + org_a;  // (the distance of a ray's origin from the centre)
@@ -1867,15 +1896,18 @@ __global__ __launch_bounds__(kBlock) void scatter_debug_kernel(const DevMaterial
 // ---------------------------------------------------------------------------------------------
 size_t megakernel_gseq_bytes(uint32_t n_waves) { return size_t(n_waves) * kPool * kSeqWords * sizeof(uint32_t); }
 size_t megakernel_gstack_bytes(uint32_t n_waves) { return size_t(n_waves) * kStackMax * 64u * sizeof(uint32_t); }
+size_t megakernel_gtime_bytes(uint32_t n_waves) { return size_t(n_waves) * kPool * sizeof(float); }  // TraceParams::gtime
 
 __host__ __device__ inline uint32_t megakernel_lds_dwords(uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris,
-                                                          uint32_t thin_lens, uint32_t environment, uint32_t pattern_dw, uint32_t shutter) {
+                                                          uint32_t thin_lens, uint32_t environment, uint32_t pattern_dw, uint32_t shutter,
+                                                          uint32_t motion) {
     const uint32_t n_elem = n_spheres + n_elem_tris;
     const uint32_t scene = n_spheres * kSphDw + (n_elem + n_meshes) * kMatDw + n_meshes * kMeshDw + kGenDw +
                            pattern_dw +                                                // second entries and DevPatterns (nothing without patterns)
                            (thin_lens ? kLensDw : 0u) +                                // a lens launch's lens (nothing for a pinhole)
                            (environment ? kEnvDw : 0u) +                               // the map's address and size (nothing without one)
                            (shutter ? kShutterDw : 0u) +                               // a shutter launch's travel (nothing without a shutter)
+                           (motion ? n_spheres * kMotionDw : 0u) +                     // a motion launch's travels (nothing without a motion)
                            (n_elem_tris != 0u ? n_elem_tris * kTriDw + n_elem : 0u);  // triangle table + element order
     const uint32_t pool_pad = (uint32_t(kPool) + 63u) & ~63u;  // status + list: one byte per (padded) slot each
     uint32_t dw = uint32_t(kFields * kPool) + kCellDw + kTqDw + kHelpDw + pool_pad / 2u + stack_entries * 64u + scene;
@@ -1883,8 +1915,8 @@ __host__ __device__ inline uint32_t megakernel_lds_dwords(uint32_t stack_entries
     return dw;
 }
 size_t megakernel_lds_bytes(uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris, uint32_t thin_lens,
-                            uint32_t environment, uint32_t pattern_dw, uint32_t shutter) {
-    return size_t(megakernel_lds_dwords(stack_entries, n_spheres, n_meshes, n_elem_tris, thin_lens, environment, pattern_dw, shutter)) * sizeof(uint32_t);
+                            uint32_t environment, uint32_t pattern_dw, uint32_t shutter, uint32_t motion) {
+    return size_t(megakernel_lds_dwords(stack_entries, n_spheres, n_meshes, n_elem_tris, thin_lens, environment, pattern_dw, shutter, motion)) * sizeof(uint32_t);
 }
 
 // What the HIP runtime says fits: resident single-wave workgroups of the trace kernel per CU at this much LDS (0 on error).
@@ -1897,7 +1929,7 @@ int megakernel_occupancy_per_cu(size_t lds_bytes) {
 // Does the launch qualify for the PLAIN build of the trace kernel (megakernel.inl TraceView)? Every constant that build has
 // in place of a parameter is compared with the parameter here, and nowhere else.
 bool trace_params_are_plain(const TraceParams& P) {
-    return P.n_meshes == 1u && P.n_elem_tris == 0u && P.thin_lens == 0u && P.shutter == 0u && P.env_nodes == nullptr && P.pattern_dw == 0u &&
+    return P.n_meshes == 1u && P.n_elem_tris == 0u && P.thin_lens == 0u && P.shutter == 0u && P.motion == nullptr && P.env_nodes == nullptr && P.pattern_dw == 0u &&
            P.y_low_water == kDefaultKnobs.y_low_water && P.y_high_water == kDefaultKnobs.y_high_water &&
            P.y_high_min_parked == kDefaultKnobs.y_high_min_parked && P.leaf_round == kDefaultKnobs.leaf_round &&
            P.leaf_leaves == kDefaultKnobs.leaf_leaves && P.share_idle == kDefaultKnobs.share_idle &&
@@ -1910,7 +1942,7 @@ bool trace_params_are_plain(const TraceParams& P) {
 // (work counters, sample buffer, tables), scratch slots from P.wave_base on.
 hipError_t launch_trace_helper(const TraceParams& P, uint32_t n_waves, bool plain, hipStream_t stream) {
     if (P.n_items == 0 || n_waves == 0 || !P.helper_words) return hipSuccess;
-    const size_t lds = megakernel_lds_bytes(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris, P.thin_lens, P.env_nodes ? 1u : 0u, P.pattern_dw, P.shutter);
+    const size_t lds = megakernel_lds_bytes(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris, P.thin_lens, P.env_nodes ? 1u : 0u, P.pattern_dw, P.shutter, P.motion ? 1u : 0u);
     if (plain && trace_params_are_plain(P))
         hipLaunchKernelGGL((trace_megakernel<false, true, true>), dim3(n_waves), dim3(64), lds, stream, P);
     else
@@ -1922,7 +1954,7 @@ hipError_t launch_trace_helper(const TraceParams& P, uint32_t n_waves, bool plai
 // in, whatever the caller says, and never for a counting launch.
 hipError_t launch_trace_megakernel(const TraceParams& P, uint32_t n_waves, bool stats, bool plain, hipStream_t stream) {
     if (P.n_items == 0 || n_waves == 0) return hipSuccess;
-    const size_t lds = megakernel_lds_bytes(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris, P.thin_lens, P.env_nodes ? 1u : 0u, P.pattern_dw, P.shutter);
+    const size_t lds = megakernel_lds_bytes(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris, P.thin_lens, P.env_nodes ? 1u : 0u, P.pattern_dw, P.shutter, P.motion ? 1u : 0u);
     if (stats)
         hipLaunchKernelGGL((trace_megakernel<true, false, false>), dim3(n_waves), dim3(64), lds, stream, P);
     else if (plain && trace_params_are_plain(P))

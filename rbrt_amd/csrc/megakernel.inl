@@ -258,9 +258,10 @@ struct TraceView {
     __device__ __forceinline__ bool may_have_patterns() const { return !PLAIN; }
     __device__ __forceinline__ bool thin_lens() const { return PLAIN ? false : P.thin_lens != 0u; }
     __device__ __forceinline__ bool shutter() const { return PLAIN ? false : P.shutter != 0u; }
+    __device__ __forceinline__ bool motion() const { return PLAIN ? false : P.motion != nullptr; }
     __device__ __forceinline__ bool environment() const { return PLAIN ? false : P.env_nodes != nullptr; }
-    // the G_FLAGS word as staged in LDS: bits 0 and 1 (tile order, constant background) are any launch's; the lens, map and
-    // shutter bits and the offset of their words are zero in a plain launch
+    // the G_FLAGS word as staged in LDS: bits 0 and 1 (tile order, constant background) are any launch's; the lens, map,
+    // shutter and motion bits and the offset of their words are zero in a plain launch
     __device__ __forceinline__ uint32_t gen_flags(uint32_t word) const { return PLAIN ? word & 3u : word; }
     // a mesh index read back from a path's state: with one mesh there is only mesh 0
     __device__ __forceinline__ uint32_t mesh_index(uint32_t m) const { return PLAIN ? 0u : m; }
@@ -300,7 +301,7 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
     // (the accumulators sit at the very end of the workgroup's LDS: megakernel_lds_bytes adds room for them)
     // (u32: a wave spends at most a few million cycles in a region per launch; 76 bytes fit the slack of the product's
     // allocation granule, so this build keeps the product's 16 workgroups per CU)
-    uint32_t* const rt_acc = lds + (megakernel_lds_dwords(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris, P.thin_lens, P.env_nodes ? 1u : 0u, P.pattern_dw, P.shutter) - uint32_t(kNumRegions));
+    uint32_t* const rt_acc = lds + (megakernel_lds_dwords(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris, P.thin_lens, P.env_nodes ? 1u : 0u, P.pattern_dw, P.shutter, P.motion ? 1u : 0u) - uint32_t(kNumRegions));
     if (lane < uint32_t(kNumRegions)) rt_acc[lane] = 0u;
     unsigned long long rt_prev = __builtin_amdgcn_s_memtime();
     const unsigned long long rt_wall0 = __builtin_amdgcn_s_memrealtime();  // 100 MHz, the same clock on every CU
@@ -317,6 +318,9 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
     // (a helper launch's waves take the scratch slots behind those of the launch they help)
     const uint32_t wave_slot = HELPER ? blockIdx.x + P.wave_base : blockIdx.x;
     uint32_t* const gseq = P.gseq + size_t(wave_slot) * uint32_t(kPool) * kSeqWords;
+    // (a motion launch: the draw t of the path in each pool slot, written where the path is generated and read where a parked
+    // path is loaded for a scatter; the pool's fields in LDS are full. Never touched without a motion: the pointer is null.)
+    float* const gtime = P.gtime + size_t(wave_slot) * uint32_t(kPool);
     if (HELPER) {
         // registered BEFORE the first draw from the counters: a helper wave that holds work is counted in helper_words[0] by
         // the time the launch's last work item is handed out, and the resolve waits for that count to return to zero
@@ -372,6 +376,12 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
             td += K.n_elem_tris() * kTriDw;
             for (uint32_t i = lane; i < n_elem; i += 64) td[i] = P.elems[i];
         }
+        if (K.motion()) {  // behind the lens, the map and the shutter: the spheres' travels, announced by bit 5 (nothing without a motion)
+            uint32_t* md = gen_dst + kGenDw + (K.n_elem_tris() != 0u ? K.n_elem_tris() * kTriDw + n_elem : 0u) + (K.thin_lens() ? kLensDw : 0u) +
+                           (K.environment() ? kEnvDw : 0u) + (K.shutter() ? kShutterDw : 0u);
+            const uint32_t* gmv = reinterpret_cast<const uint32_t*>(P.motion);
+            for (uint32_t i = lane; i < P.n_spheres * kMotionDw; i += 64) md[i] = gmv[i];
+        }
         if (lane == 0) {
             float* gf = reinterpret_cast<float*>(dst);
             for (int c = 0; c < 3; ++c) {
@@ -408,6 +418,7 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                 dst[sa + 3] = 0u;
                 dst[G_FLAGS] = (dst[G_FLAGS] & 0xFFu) | 16u | (at << 8);
             }
+            if (K.motion()) dst[G_FLAGS] = (dst[G_FLAGS] & 0xFFu) | 32u | ((kGenDw + (K.n_elem_tris() != 0u ? K.n_elem_tris() * kTriDw + n_elem : 0u)) << 8);
             dst[G_SAMPLE_BASE] = P.sample_base, dst[G_MAX_DEPTH] = P.max_depth;
             dst[G_SEED_LO] = uint32_t(P.seed_key), dst[G_SEED_HI] = uint32_t(P.seed_key >> 32);
         }
@@ -887,6 +898,12 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
         Rng rng = {0u, 0u};
         uint32_t item = 0, depth = 0, nrec = 0, word = 0;
         bool have_ray = false;
+        // A motion launch (wave-uniform, decided per launch: bit 5 of the flags word; constant 0 in the PLAIN build): mtr = the
+        // spheres' travels in LDS, mt = the draw t of the path this lane holds (sphere_centre_at)
+        const uint32_t mflags = K.gen_flags(uint32_t(__builtin_amdgcn_readfirstlane(int(gp[G_FLAGS]))));
+        const bool motion = (mflags & 32u) != 0u;
+        const float* const mtr = gpf + (mflags >> 8) + ((mflags & 4u) ? kLensDw : 0u) + ((mflags & 8u) ? kEnvDw : 0u) + ((mflags & 16u) ? kShutterDw : 0u);
+        float mt = 0.0f;
 
         RBRT_MARK(term);
         if (kind == ST_TERM) {
@@ -1017,8 +1034,12 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                             if (gen_flags & 4u)  // RBRT_FLAG_THIN_LENS (the same for every lane): the lens words at dword gen_flags >> 8
                                 lens_point(o, f, gpf + (gen_flags >> 8), rng);
                             d = normalize(f - o);
-                            if (gen_flags & 16u)  // the handle's shutter (the same for every lane): the travel behind the lens and the map
-                                shutter_origin(o, gpf + (gen_flags >> 8) + ((gen_flags & 4u) ? kLensDw : 0u) + ((gen_flags & 8u) ? kEnvDw : 0u), rng);
+                            if (gen_flags & 48u) {  // a shutter, a motion or both (the same for every lane): ONE draw
+                                mt = rng.next_f32();
+                                if (gen_flags & 16u)  // the handle's shutter: the travel behind the lens and the map
+                                    shutter_origin(o, gpf + (gen_flags >> 8) + ((gen_flags & 4u) ? kLensDw : 0u) + ((gen_flags & 8u) ? kEnvDw : 0u), mt);
+                                if (gen_flags & 32u) gtime[slot] = mt;  // the path keeps it through every park and resume
+                            }
                             depth = gp[G_MAX_DEPTH];
                             nrec = 0;
                             word = 0;
@@ -1055,6 +1076,7 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
             s_obj = int32_t((meta >> 14) & 255u) - 1;
             s_ht = __uint_as_float(POOL(F_T, slot));
             s_tri = POOL(F_TRI, slot);
+            if (motion) mt = gtime[slot];
         }
         RBRT_MARK(round_top);
         for (uint32_t round = 1;; ++round) {
@@ -1064,7 +1086,7 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                 if (uint32_t(s_obj) < n_elem) {
                     const uint32_t desc = K.n_elem_tris() != 0u ? sc.elem[uint32_t(s_obj)] : uint32_t(s_obj);
                     if (desc >> 31) n = mk(sc.tri + (desc & 0x7FFFFFFFu) * kTriDw + 9);  // triangle.rs:432: the stored normal
-                    else n = p - mk(sc.sph + desc * kSphDw);                            // sphere.rs:56, unnormalised
+                    else n = p - (motion ? sphere_centre_at(sc.sph + desc * kSphDw, mtr + desc * kMotionDw, mt) : mk(sc.sph + desc * kSphDw));  // sphere.rs:56, unnormalised
                 } else {  // the stored face normal (mesh.rs:253-257), or a smooth mesh's shading normal
                     n = mesh_shading_normal(lds_ptr<Normal4>(sc.mesh + K.mesh_index(uint32_t(s_obj) - n_elem) * kMeshDw + MD_NORMALS), s_tri, o, d);
                 }
@@ -1127,16 +1149,16 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                 // Scene::elements in their order (scene.rs:23-31). Two copies of the loop: a scene without BasicTriangles
                 // (every scene the reference's YAML can describe) runs the one that knows only spheres -- with the
                 // element-kind test inside a single loop the sphere-only frame was 2 % slower.
-                auto test_sphere = [&](uint32_t e, const float* sp) {
+                auto test_sphere = [&](uint32_t e, const float* sp, V3 c) {
                     float t, dist;
                     if (STATS) {  // how often a wave runs the expensive part of sphere_hit, and for how many lanes
-                        const V3 l = o - mk(sp);
+                        const V3 l = o - c;
                         const float bq = dot(d * 2.0f, l);
                         const float sol = bq * bq - 4.0f * dot(d, d) * (dot(l, l) - sp[3] * sp[3]);
                         const uint64_t m = wballot(sol >= 0.0f);
                         if (m != 0ull) ++dg_sph_tails, dg_sph_pairs += uint32_t(__popcll(m));
                     }
-                    if (sphere_hit(mk(sp), sp[3], o, d, P.min_dist, P.max_dist, t, dist, P.counters)) {
+                    if (sphere_hit(c, sp[3], o, d, P.min_dist, P.max_dist, t, dist, P.counters)) {
                         if (dist < closest) {
                             closest = dist;
                             s_ht = t;
@@ -1144,8 +1166,13 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                         }
                     }
                 };
-                if (K.n_elem_tris() == 0u) {
-                    for (uint32_t i = 0; i < P.n_spheres; ++i) test_sphere(i, sc.sph + i * kSphDw);
+                // (and a third for a motion launch's spheres, so that the other two pay nothing for it; with BasicTriangles the
+                // element loop asks per sphere, a wave-uniform question)
+                if (K.n_elem_tris() == 0u && !motion) {
+                    for (uint32_t i = 0; i < P.n_spheres; ++i) test_sphere(i, sc.sph + i * kSphDw, mk(sc.sph + i * kSphDw));
+                } else if (K.n_elem_tris() == 0u) {
+                    for (uint32_t i = 0; i < P.n_spheres; ++i)
+                        test_sphere(i, sc.sph + i * kSphDw, sphere_centre_at(sc.sph + i * kSphDw, mtr + i * kMotionDw, mt));
                 } else {
                     for (uint32_t e = 0; e < n_elem; ++e) {
                         const uint32_t desc = sc.elem[e];  // (wave-uniform: which kind of element this is)
@@ -1159,7 +1186,8 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                                 }
                             }
                         } else {
-                            test_sphere(e, sc.sph + desc * kSphDw);
+                            test_sphere(e, sc.sph + desc * kSphDw,
+                                        motion ? sphere_centre_at(sc.sph + desc * kSphDw, mtr + desc * kMotionDw, mt) : mk(sc.sph + desc * kSphDw));
                         }
                     }
                 }

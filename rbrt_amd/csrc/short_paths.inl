@@ -42,8 +42,10 @@ constexpr uint32_t kShortKeepNum = 3, kShortKeepDen = 4;  // ... and the share o
 
 // The closest element hit of a ray (scene.rs:23-31): elements in their order, strict `<`. `skip`: culling bits of the
 // elements (bit e < 24) whose test is known to fail -- 0 for any ray but a camera ray of the word's tile.
+// mt: the sample's draw t; with a motion (P.motion) a sphere is tested where it is then (sphere_centre_at), and the skip bits are
+// the tile pass's widened ones, which hold for every t.
 __device__ __forceinline__ void short_closest_element(const TraceParams& P, const SceneLds& sc, uint32_t n_elem, uint32_t skip, V3 o, V3 d,
-                                                      float& closest, float& ht, int32_t& obj) {
+                                                      float mt, float& closest, float& ht, int32_t& obj) {
     closest = 3.40282347e+38f;  // f32::MAX (scene.rs:21)
     ht = 0.0f;
     obj = -1;
@@ -56,7 +58,8 @@ __device__ __forceinline__ void short_closest_element(const TraceParams& P, cons
         } else {
             if (e < 24u && ((skip >> e) & 1u)) continue;
             const float* sp = sc.sph + desc * kSphDw;
-            hit = sphere_hit(mk(sp), sp[3], o, d, P.min_dist, P.max_dist, t, dist, P.counters);
+            const V3 c = P.motion ? sphere_centre_at(sp, P.motion + desc * kMotionDw, mt) : mk(sp);
+            hit = sphere_hit(c, sp[3], o, d, P.min_dist, P.max_dist, t, dist, P.counters);
         }
         if (hit && dist < closest) {
             closest = dist;
@@ -86,11 +89,13 @@ __device__ __forceinline__ bool short_path_sample(const TraceParams& P, const Sc
                          img_h, row, col, rng);
     if (P.thin_lens) lens_point(o, f, lens, rng);
     V3 d = normalize(f - o);
-    if (P.shutter) shutter_origin(o, P.travel, rng);
+    float mt = 0.0f;  // one draw for the shutter and the motion; with a motion it stays the sample's for both rays
+    if (P.shutter || P.motion) mt = rng.next_f32();
+    if (P.shutter) shutter_origin(o, P.travel, mt);
     uint32_t depth = P.max_depth;
     float closest, ht;
     int32_t obj;
-    short_closest_element(P, sc, n_elem, word, o, d, closest, ht, obj);
+    short_closest_element(P, sc, n_elem, word, o, d, mt, closest, ht, obj);
     uint32_t next = classify(sc, obj, depth);
     V3 color = mk(0.0f, 0.0f, 0.0f);
     int32_t rec = -1;  // the bounce whose albedo attenuates the path (a dielectric's (1,1,1) is not recorded)
@@ -99,7 +104,7 @@ __device__ __forceinline__ bool short_path_sample(const TraceParams& P, const Sc
         const uint32_t desc = P.n_elem_tris != 0u ? sc.elem[uint32_t(obj)] : uint32_t(obj);
         V3 n;
         if (desc >> 31) n = mk(sc.tri + (desc & 0x7FFFFFFFu) * kTriDw + 9);  // triangle.rs:432: the stored normal
-        else n = p - mk(sc.sph + desc * kSphDw);                            // sphere.rs:56, unnormalised
+        else n = p - (P.motion ? sphere_centre_at(sc.sph + desc * kSphDw, P.motion + desc * kMotionDw, mt) : mk(sc.sph + desc * kSphDw));  // sphere.rs:56, unnormalised
         const float param = __uint_as_float(sc.mat[uint32_t(obj) * kMatDw + 3]);
         V3 nd;
         bool ok;
@@ -121,7 +126,7 @@ __device__ __forceinline__ bool short_path_sample(const TraceParams& P, const Sc
             o = p;
             d = nd;
             depth -= 1u;
-            short_closest_element(P, sc, n_elem, 0u, o, d, closest, ht, obj);
+            short_closest_element(P, sc, n_elem, 0u, o, d, mt, closest, ht, obj);
             LocalCounters lc = {0, 0, 0, 0, 0};
             const uint32_t gated = next_gated_mesh<false>(sc, P.n_meshes, 0u, o, d, closest, lc);
             next = gated < P.n_meshes ? uint32_t(ST_TRAV) : classify(sc, obj, depth);

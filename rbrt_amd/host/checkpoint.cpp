@@ -64,7 +64,8 @@ uint64_t patterns_fingerprint(const rbrt_scene_patterns_t* pt, uint64_t h) {
 }  // namespace
 
 uint64_t checkpoint_fingerprint(const std::string& path, const rbrt_camera_lens_t& lens, const rbrt_render_opts_t& opts, const rbrt_scene_t& sc,
-                                const rbrt_scene_shading_t* sh, const Environment& env, const rbrt_scene_patterns_t* pt, const float* travel) {
+                                const rbrt_scene_shading_t* sh, const Environment& env, const rbrt_scene_patterns_t* pt, const float* travel,
+                                const std::vector<float>* motion) {
     if (path.empty()) return 0;
     uint64_t h = patterns_fingerprint(pt, shading_fingerprint(sc, sh, scene_fingerprint(lens.cam, sc)));
     if (opts.flags & RBRT_FLAG_CONSTANT_BACKGROUND) {
@@ -80,7 +81,16 @@ uint64_t checkpoint_fingerprint(const std::string& path, const rbrt_camera_lens_
         h = fnv1a(lens.lens_v, sizeof(lens.lens_v), h);
         h = fnv1a(&lens.focus_scale, sizeof(lens.focus_scale), h);
     }
-    return shutter_fingerprint(travel, h);
+    h = shutter_fingerprint(travel, h);
+    return motion && !motion->empty() ? motion_fingerprint(motion->data(), uint32_t(motion->size() / 3u), h) : h;
+}
+
+uint64_t motion_fingerprint(const float* travels, uint32_t n_spheres, uint64_t h) {
+    if (!travels) return h;
+    const char tag[8] = {'m', 'o', 't', 'i', 'o', 'n', 0, 0};
+    h = fnv1a(tag, sizeof(tag), h);
+    h = fnv1a(&n_spheres, sizeof(n_spheres), h);
+    return fnv1a(travels, size_t(n_spheres) * 3u * sizeof(float), h);
 }
 
 uint64_t shutter_fingerprint(const float* travel, uint64_t h) {

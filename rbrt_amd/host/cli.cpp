@@ -212,6 +212,7 @@ int parse_cli(int argc, char** argv, CliOptions& o) {
         else if (a.is("--frames")) ok = a.u32(o.frames, 1);
         else if (a.is("--camera-step")) ok = a.triple(o.camera_step, o.camera_step_given, false, step);
         else if (a.is("--shutter-travel")) ok = a.triple(o.shutter_travel, o.shutter_travel_given, false, step);
+        else if (a.is("--no-motion")) ok = a.flag(o.no_motion);
         else if (a.is("--shutter"))
             ok = a.f32_unsigned_zero(o.shutter, at_least_0, "a finite number >= 0: the part of a frame's camera step the shutter is open for");
         else if (a.is("--temporal-max-history")) ok = a.f32_unsigned_zero(o.temporal_max_history, at_least_1, "a finite number >= 1");
@@ -414,6 +415,7 @@ rbrt::RenderConfig config_of(const CliOptions& o, const rbrt::SceneBlueprint& bp
         cfg.tonemap = true, cfg.tonemap_curve = o.tone_curve, cfg.tonemap_exposure = o.exposure, cfg.tonemap_key = o.exposure_key;
         cfg.tonemap_white = o.white ? *o.white : 0.0f;
     }
+    cfg.no_motion = o.no_motion;
     if (o.shutter || o.shutter_travel_given) {  // (the flags override the YAML's camera_shutter_travel)
         cfg.shutter = true;
         for (int c = 0; c < 3; ++c) cfg.shutter_travel[c] = o.shutter ? *o.shutter * o.camera_step[c] : o.shutter_travel[c];

@@ -48,6 +48,7 @@ struct CliOptions {
     std::optional<float> shutter;  // --shutter S: the travel is S * camera_step
     float shutter_travel[3] = {0.0f, 0.0f, 0.0f};
     bool shutter_travel_given = false;
+    bool no_motion = false;  // --no-motion: the spheres' shutter_travel keys are ignored
     std::string history_map;
     std::optional<uint32_t> upscale;  // --upscale turns guided upsampling on; the options below need it
     std::optional<float> upscale_normal, upscale_depth, upscale_albedo;

@@ -118,6 +118,10 @@ struct SphereBlueprint {
     std::optional<Vec3> albedo;
     std::optional<float> material_param;
     std::optional<Checker> checker;
+    // `shutter_travel: [dx, dy, dz]` (not in the reference): the sphere's translation while the shutter is open, in scene
+    // units (include/rbrt_hip.h "Moving spheres"); absent: the sphere stays -- and a scene none of whose spheres has the key has
+    // no motion at all
+    std::optional<Vec3> shutter_travel;
 };
 struct CameraBluePrint {
     Vec3 camera_up, camera_look_at, camera_position;
@@ -153,6 +157,7 @@ struct Sphere {
     float radius = 0;
     Material material;
     std::optional<Checker> checker;  // lambertian only
+    std::optional<Vec3> shutter_travel;  // the YAML's shutter_travel: absent, the sphere stays
 };
 
 // triangle.rs:9-34: a single triangle as a scene element (the reference's second Intersectable). The YAML factory
@@ -259,6 +264,9 @@ struct Scene {
         const rbrt_scene_patterns_t* patterns_ptr() const { return any_pattern ? &patterns : nullptr; }
     };
     AbiView to_abi() const;
+    // The scene's motion (rbrt_motion_t::travel): [elements.size()][3], zeros for the spheres without a shutter_travel; EMPTY
+    // when no sphere has one (no motion: no draw is made for it). A key with a zero vector counts: its scene has a motion.
+    std::vector<float> motion_travels() const;
 };
 Scene create_scene_from_scene_blueprint(const SceneBlueprint& bp);
 // Where create_scene_from_scene_blueprint spent its time, summed over the meshes of the calling thread's scenes (--report).
@@ -395,6 +403,10 @@ struct RenderConfig {  // additions that the reference hard-codes or lacks
     // accumulation reprojects through the frames' opening cameras.
     bool shutter = false;
     float shutter_travel[3] = {0.0f, 0.0f, 0.0f};
+    // Moving spheres (rbrt_hip_scene_set_motion): the spheres' shutter_travel keys go to every rank's handle like the shutter,
+    // with which they share the draw; with --frames every frame exposes the same sweep (objects do not advance from frame to
+    // frame). no_motion (the CLI's --no-motion): the keys are ignored, the scene renders as if it had none.
+    bool no_motion = false;
     float temporal_max_history = 32.0f, temporal_depth = 0.05f, temporal_normal = 0.35f;  // (rbrt_temporal_opts_default)
     // Guided upsampling (rbrt_hip_upsample_halves; the CLI's --upscale, --upscale-*): the image is traced with the low camera of
     // rbrt_hip_upsample_camera (1 / upscale of the size in each direction) through the adaptive path's one round that stops

@@ -428,6 +428,7 @@ struct Job {
     CheckpointHeader want;
     CheckpointRead resume;
     ImageBuffer& img;
+    std::vector<float> motion;  // Scene::motion_travels, empty without one or with RenderConfig::no_motion: every rank's handle gets it
     size_t n() const { return size_t(img.width) * img.height * 3; }  // values of the complete image
     size_t rank_pixels(int rank) const {  // the pixels a rank renders: its packed tiles, or the image as it is
         return plan.world > 1 ? rbrt_hip_packed_pixels(img.width, img.height, uint32_t(rank), uint32_t(plan.world)) : size_t(img.width) * img.height;
@@ -589,6 +590,11 @@ void Rank::setup() {
         rbrt_shutter_t sht{};
         for (int c = 0; c < 3; ++c) sht.travel[c] = cfg.shutter_travel[c];
         err.lib_ok(rbrt_hip_scene_set_shutter(hs, &sht));
+    }
+    if (!job.motion.empty()) {  // (and the spheres' travels, which share the shutter's draw)
+        rbrt_motion_t mo{};
+        mo.n_spheres = uint32_t(job.motion.size() / 3u), mo.travel = job.motion.data();
+        err.lib_ok(rbrt_hip_scene_set_motion(hs, &mo));
     }
     rbrt_hip_scene_info_t info;
     if (rank == 0 && rbrt_hip_scene_info(hs, &info) == RBRT_OK) {
@@ -1102,10 +1108,11 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
     const rbrt_environment_t env_abi = scene.environment.to_abi();
     const Plan plan = make_plan(cfg, cfg_in.adaptive ? "--adaptive" : cfg_in.upscale ? "--upscale" : cfg_in.despike ? "--despike" : cfg_in.frames ? "--frames" : cfg_in.denoise_guided ? "--denoise-guided" : "--denoise", cfg_in.adaptive,
                                 cam, scene, num_samples);
-    Job job{cfg, plan, lens, view, scene.environment.n != 0u ? &env_abi : nullptr, render_opts_of(cfg, cam, num_samples), num_samples, {}, {}, img};
+    Job job{cfg, plan, lens, view, scene.environment.n != 0u ? &env_abi : nullptr, render_opts_of(cfg, cam, num_samples), num_samples, {}, {}, img, {}};
+    if (!cfg.no_motion) job.motion = scene.motion_travels();
     job.want = checkpoint_header(img.width, img.height, num_samples, uint32_t(plan.world), cfg.seed,
                                  checkpoint_fingerprint(cfg.checkpoint_path, lens, job.opts, view.scene, view.shading_ptr(), scene.environment, view.patterns_ptr(),
-                                                        cfg.shutter ? cfg.shutter_travel : nullptr));
+                                                        cfg.shutter ? cfg.shutter_travel : nullptr, &job.motion));
     job.resume = resume_from_checkpoint(job);
     Shared sh(plan);
     bring_up_rccl(plan, sh);

@@ -91,6 +91,14 @@ void write_report(const CliOptions& o, const rbrt::RenderConfig& cfg, const rbrt
         j.vec3("camera_step", cfg.camera_step);
     }
     if (cfg.shutter) j.vec3("shutter_travel", cfg.shutter_travel);  // the camera's translation while the shutter was open
+    if (const std::vector<float> mv = scene.motion_travels(); !mv.empty() && !cfg.no_motion) {  // the spheres that moved meanwhile: index and travel
+        std::string list;
+        for (size_t i = 0; i < scene.elements.size(); ++i)
+            if (scene.elements[i].shutter_travel)
+                list += std::string(list.empty() ? "" : ", ") + "{\"sphere\": " + std::to_string(i) + ", \"travel\": [" + JsonLine::text(mv[3 * i], "%.9g") + ", " +
+                        JsonLine::text(mv[3 * i + 1], "%.9g") + ", " + JsonLine::text(mv[3 * i + 2], "%.9g") + "]}";
+        j.raw("moving_spheres", "[" + list + "]");
+    }
     if (o.upscale) {  // guided upsampling: its options, the size that was traced and the stage's time on the GPU, the mean per frame (a part of render_s)
         j.num("upscale", cfg.upscale, "%.0f"), j.num("render_width", rep.render_width, "%.0f"), j.num("render_height", rep.render_height, "%.0f");
         j.num("upscale_normal", cfg.upscale_normal, "%.9g"), j.num("upscale_depth", cfg.upscale_depth, "%.9g"), j.num("upscale_albedo", cfg.upscale_albedo, "%.9g");

@@ -271,6 +271,23 @@ const std::vector<Node>& as_list(const Node& n, const char* what) {
     throw Error(std::string(what) + ": expected a sequence");
 }
 
+// A travel `key` of `m` (the camera's camera_shutter_travel, a sphere's shutter_travel; not in the reference): [dx, dy, dz], or
+// x / y / z like the other vectors; absent or null: none. `what` ends the message of a vector that is not finite.
+std::optional<Vec3> opt_travel(const Node& m, const char* key, const char* what) {
+    const Node* tr = m.find(key);
+    if (!tr || tr->is_null()) return std::nullopt;
+    Vec3 v;
+    if (tr->kind == Node::List) {
+        if (tr->list.size() != 3) throw Error(std::string(key) + ": expected [dx, dy, dz], three numbers");
+        v = Vec3(as_f32(tr->list[0], key), as_f32(tr->list[1], key), as_f32(tr->list[2], key));
+    } else {
+        v = as_vec3(*tr, key);
+    }
+    if (!std::isfinite(v.x) || !std::isfinite(v.y) || !std::isfinite(v.z))
+        throw Error(std::string(key) + " must be three finite numbers (" + what + ")");
+    return v;
+}
+
 // The optional checker keys of a sphere or mesh blueprint `m` (not in the reference). The pair checker_albedo / checker_size
 // makes one; checker_origin defaults to 0. Whether the material can carry it is decided with the material
 // (create_scene_from_scene_blueprint).
@@ -329,19 +346,7 @@ SceneBlueprint load_blueprints_from_yaml_text(const std::string& text) {
         as_f32(need(cam, "camera_focal_length_mm", "camera_blueprint"), "camera_focal_length_mm");
     bp.camera_blueprint.camera_aperture_mm = opt_f32(cam, "camera_aperture_mm", "camera_aperture_mm");
     bp.camera_blueprint.camera_focus_distance = opt_f32(cam, "camera_focus_distance", "camera_focus_distance");
-    if (const Node* tr = cam.find("camera_shutter_travel"); tr && !tr->is_null()) {  // [dx, dy, dz], or x / y / z like the other vectors
-        Vec3 v;
-        if (tr->kind == Node::List) {
-            if (tr->list.size() != 3) throw Error("camera_shutter_travel: expected [dx, dy, dz], three numbers");
-            v = Vec3(as_f32(tr->list[0], "camera_shutter_travel"), as_f32(tr->list[1], "camera_shutter_travel"),
-                     as_f32(tr->list[2], "camera_shutter_travel"));
-        } else {
-            v = as_vec3(*tr, "camera_shutter_travel");
-        }
-        if (!std::isfinite(v.x) || !std::isfinite(v.y) || !std::isfinite(v.z))
-            throw Error("camera_shutter_travel must be three finite numbers (the camera's translation during the exposure)");
-        bp.camera_blueprint.camera_shutter_travel = v;
-    }
+    bp.camera_blueprint.camera_shutter_travel = opt_travel(cam, "camera_shutter_travel", "the camera's translation during the exposure");
     {  // (checked here, so that a bad lens is a load error; the CLI's --aperture / --focus-distance are checked again)
         const CameraBluePrint& cb = bp.camera_blueprint;
         const float ap = cb.camera_aperture_mm ? *cb.camera_aperture_mm : 0.0f;
@@ -377,6 +382,12 @@ SceneBlueprint load_blueprints_from_yaml_text(const std::string& text) {
         b.albedo = opt_vec3(s, "albedo", "albedo");
         b.material_param = opt_f32(s, "material_param", "material_param");
         b.checker = opt_checker(s);
+        b.shutter_travel = opt_travel(s, "shutter_travel", "the sphere's translation during the exposure");
+        if (b.shutter_travel) {  // (what rbrt_hip_scene_set_motion would refuse, as a load error that names the sphere)
+            const Vec3 end(b.center.x + b.shutter_travel->x, b.center.y + b.shutter_travel->y, b.center.z + b.shutter_travel->z);
+            if (!std::isfinite(end.x) || !std::isfinite(end.y) || !std::isfinite(end.z))
+                throw Error("shutter_travel: center + shutter_travel of sphere " + std::to_string(bp.sphere_blueprints.size()) + " is not finite");
+        }
         bp.sphere_blueprints.push_back(b);
     }
     if (const Node* en = root.find("environment_blueprint"); en && !en->is_null()) {  // (not in the reference; absent = none)
@@ -751,6 +762,17 @@ Scene::AbiView Scene::to_abi() const {
     return v;
 }
 
+std::vector<float> Scene::motion_travels() const {
+    bool any = false;
+    for (const Sphere& s : elements) any = any || s.shutter_travel.has_value();
+    std::vector<float> out;
+    if (!any) return out;
+    out.assign(elements.size() * 3u, 0.0f);
+    for (size_t i = 0; i < elements.size(); ++i)
+        if (const auto& tr = elements[i].shutter_travel) out[3 * i] = tr->x, out[3 * i + 1] = tr->y, out[3 * i + 2] = tr->z;
+    return out;
+}
+
 // blueprints.rs:132-158: meshes first (loading the files), then spheres; objects whose material
 // cannot be built are dropped.
 Scene create_scene_from_scene_blueprint(const SceneBlueprint& bp) {
@@ -770,7 +792,7 @@ Scene create_scene_from_scene_blueprint(const SceneBlueprint& bp) {
         auto mat = create_material_from_description(sb.material_type, sb.albedo, sb.material_param);
         if (!mat) continue;
         need_lambertian_for_checker(sb.checker, *mat, sb.material_type);
-        scene.elements.push_back(Sphere{sb.center, sb.radius, *mat, sb.checker});
+        scene.elements.push_back(Sphere{sb.center, sb.radius, *mat, sb.checker, sb.shutter_travel});
     }
     return scene;
 }

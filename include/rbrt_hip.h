@@ -57,7 +57,9 @@ extern "C" {
                               two *_shaded entry points: rbrt_mesh_t and rbrt_scene_t stay as they are), nor solid patterns
                               (rbrt_scene_patterns_t and the two *_patterned entry points, detected by the symbol), nor the camera shutter (rbrt_shutter_t and
                               rbrt_hip_scene_set_shutter: handle state like the environment, detected by the symbol), nor moving spheres (rbrt_motion_t and
-                              rbrt_hip_scene_set_motion: handle state like the shutter, detected by the symbol), nor adaptive
+                              rbrt_hip_scene_set_motion: handle state like the shutter, detected by the symbol), nor animation
+                              (rbrt_hip_scene_set_motion_phase, rbrt_hip_render_features_motion and
+                              rbrt_hip_temporal_accumulate_moving: added entry points, each detected by its symbol), nor adaptive
                               sampling (rbrt_hip_render_adaptive with its two structs: an added entry point), nor the
                               denoiser (rbrt_denoise_opts_t, rbrt_denoise_opts_default, rbrt_hip_denoise_halves and
                               rbrt_hip_scene_denoise: added entry points), nor environment lighting (rbrt_environment_t and
@@ -623,8 +625,8 @@ int rbrt_hip_scene_set_shutter(rbrt_hip_scene_t* scene, const rbrt_shutter_t* sh
  * for the reason they cannot carry a shutter. There is no flag bit and the ABI version stays 2: a host detects the capability
  * by the symbol. The tile pass widens sphere i's margins by |travel_i| (kernels.hip primary_cull_kernel, "Moving spheres");
  * a scene with a motion never runs the trace kernel's plain build. Not built: moving meshes and BasicTriangles, rotation or
- * other paths than a straight line, objects that advance between the frames of a stream (every frame exposes the same sweep),
- * motion vectors as a feature buffer, a pattern that travels with its sphere, a time argument for rbrt_hip_trace_rays. */
+ * other paths than a straight line, a pattern that travels with its sphere, a time argument for rbrt_hip_trace_rays. (Spheres
+ * that advance between the frames of a stream, and their travel as a feature buffer: "Animation", below.) */
 typedef struct rbrt_motion {
     uint32_t n_spheres;  /* the scene's sphere count */
     uint32_t reserved;   /* 0 */
@@ -986,6 +988,67 @@ int rbrt_hip_temporal_accumulate(int device, void* stream, const float* d_a, con
                                  const float* d_depth, const float* d_coverage, const rbrt_camera_t* cam,
                                  const rbrt_camera_t* cam_prev, const rbrt_temporal_opts_t* opts, const void* d_history_in,
                                  void* d_history_out, float* d_out_a, float* d_out_b, float* d_out_length);
+
+/* ---- Animation: spheres advance from frame to frame, and the accumulation follows them ------------------------------------------
+ * No counterpart in the reference. Three additions on top of "Moving spheres", "Feature buffers" and "Temporal accumulation",
+ * each detected by its symbol; the ABI version stays 2, no struct changes, and a host that calls none of them gets, bit for
+ * bit, what it got before. All arithmetic is float32, unfused, in the written order.
+ *
+ * 1. The phase. A handle has a phase, a float, 0 until rbrt_hip_scene_set_motion_phase sets another. It has an effect only
+ * while a motion is set, and it survives rbrt_hip_scene_set_motion (set, replace and clear). A sample's draw t is made exactly
+ * as in "Moving spheres": one draw, shared with the shutter, which keeps the raw t (o += t * travel). Wherever a path of that
+ * sample reads sphere i's centre it reads
+ *     s        = phase + t                          (one addition)
+ *     c_i(s)_c = center_i_c + (s * travel_i_c)      for c = x, y, z
+ * in the trace kernel's motion launch (every park, resume, helper launch and scatter), in the short-path stage, in
+ * rbrt_hip_render_features and in the tile pass, whose margins are made around the advanced centre center_i + phase * travel_i
+ * (kernels.hip, "A phase"): a sphere that has left the view is culled again. With phase == 0, s has the bits of t (0.0f + t
+ * with t >= +0): a handle that never calls the function, or sets 0, renders bit for bit what it renders without this section.
+ * The phase counts exposures: frame k of a stream whose spheres advance P exposures a frame runs at phase float(k) * P.
+ * Like the shutter's travel the phase goes with the launches issued after the call; launches in flight keep theirs. Nothing is
+ * copied to the device and nothing waits: the call is meant to be made once a frame. One phase must serve every pass of one
+ * rbrt_hip_render_pass series, every round of one rbrt_hip_render_adaptive call (the call reads it once a launch: do not
+ * change it from another thread meanwhile), and the low render and the full-size features of one upscaled frame. The plain
+ * build of the trace kernel is not involved: a scene with a motion never runs it.
+ * RBRT_ERR_INVALID_ARG, before the device is touched, the handle keeping its phase: scene NULL; a phase that is not finite;
+ * with a motion set, a center_i + ((phase + 1) * travel_i) that is not finite in float32. rbrt_hip_scene_set_motion makes the
+ * same check of its travels against the handle's phase. */
+int rbrt_hip_scene_set_motion_phase(rbrt_hip_scene_t* scene, float phase);
+
+/* 2. The motion buffer. rbrt_hip_render_features with one more output, d_motion, float[H][W][3], which may be NULL like the
+ * others; rbrt_hip_render_features is this call with d_motion NULL, and runs the kernel it has always run. Per sample: a hit
+ * of sphere i on a handle with a motion contributes travel_i; a miss, a hit of a mesh or of a BasicTriangle, and any hit on a
+ * handle without a motion contribute (+0, +0, +0). Per pixel each of the three sums starts from 0, adds sample 0, 1, ... in
+ * that order and is then multiplied by inv_n, like the other channels. The buffer is in scene units per exposure and does not
+ * depend on the phase. The ray, the hit and the other five outputs are what rbrt_hip_render_features gives; on a handle with a
+ * phase they see the spheres at c_i(s). The refusals are those of rbrt_hip_render_features; with all six outputs NULL nothing
+ * is launched. */
+int rbrt_hip_render_features_motion(rbrt_hip_scene_t* scene, const rbrt_camera_t* cam, const rbrt_render_opts_t* opts,
+                                    const rbrt_feature_opts_t* fopts, void* stream, float* d_albedo, float* d_normal, float* d_depth,
+                                    float* d_coverage, int32_t* d_object, float* d_motion);
+
+/* 3. Motion-aware accumulation. rbrt_hip_temporal_accumulate with two more arguments behind d_coverage: d_motion, the motion
+ * buffer Mv of THIS frame, and phase_step, this frame's phase minus the last frame's (pass the step itself, not the difference
+ * of two rounded products). The rule is that of "Temporal accumulation" with one insertion. For a surface pixel, after
+ * P = position + (zbar * d):
+ *     m_c    = Mv_c[p] / c[p]            per component: the mean travel of the samples that hit, as zbar is their mean depth
+ *     P_last = P - (phase_step * m)      where the point was when the last frame's shutter opened
+ *     v      = P_last - position'
+ * and everything after v is the rule's: the projection, the four taps, the depth test against ze = sqrt(dot(v, v)), the
+ * normal test, the sums and the mix. Background pixels are untouched. The motion is not stored: the history keeps its 48-byte
+ * layout, and the histories of the two calls are interchangeable. A translation does not turn a normal, so the normal test
+ * compares what it compared; that is why only translations are supported. Limits: only the primary hit is followed. The
+ * shadow and the reflection of a moving sphere, and what is seen through glass, lag behind as they do under
+ * rbrt_hip_temporal_accumulate; meshes and BasicTriangles do not move. NaN and infinities in d_motion only move xs and ys,
+ * which are tested as before: no read leaves the buffers.
+ * d_motion NULL gives exactly rbrt_hip_temporal_accumulate -- the same kernel, the same outputs bit for bit -- and phase_step is
+ * not read. Everything that call refuses is refused, and with d_motion a phase_step that is not finite (RBRT_ERR_INVALID_ARG).
+ * The call reads 12 more bytes a pixel than the plain one. */
+int rbrt_hip_temporal_accumulate_moving(int device, void* stream, const float* d_a, const float* d_b, const float* d_normal,
+                                        const float* d_depth, const float* d_coverage, const float* d_motion, float phase_step,
+                                        const rbrt_camera_t* cam, const rbrt_camera_t* cam_prev, const rbrt_temporal_opts_t* opts,
+                                        const void* d_history_in, void* d_history_out, float* d_out_a, float* d_out_b,
+                                        float* d_out_length);
 
 /* ---- Guided upsampling: trace a smaller image, reconstruct the full one from the full-size feature buffers -------------------
  * No counterpart in the reference. The trace kernel's cost is proportional to the pixel count; the feature buffers are cheap.

@@ -129,6 +129,17 @@ extern "C" {
     pub fn rbrt_hip_scene_set_shutter(scene: *mut c_void, shutter: *const RbrtShutter) -> c_int;
     // moving spheres: a state of the handle that shares the shutter's draw; motion = null clears it. Detected by the symbol
     pub fn rbrt_hip_scene_set_motion(scene: *mut c_void, motion: *const RbrtMotion) -> c_int;
+    // animation: the phase of the handle's motion (a sample with the draw t sees sphere i at center_i + (phase + t) * travel_i),
+    // the motion buffer beside the feature buffers, and the accumulation that follows the spheres. Each detected by its symbol
+    pub fn rbrt_hip_scene_set_motion_phase(scene: *mut c_void, phase: f32) -> c_int;
+    pub fn rbrt_hip_render_features_motion(scene: *mut c_void, cam: *const RbrtCamera, opts: *const RbrtRenderOpts, fopts: *const c_void,
+                                           stream: *mut c_void, d_albedo: *mut f32, d_normal: *mut f32, d_depth: *mut f32,
+                                           d_coverage: *mut f32, d_object: *mut i32, d_motion: *mut f32) -> c_int;
+    pub fn rbrt_hip_temporal_accumulate_moving(device: c_int, stream: *mut c_void, d_a: *const f32, d_b: *const f32, d_normal: *const f32,
+                                               d_depth: *const f32, d_coverage: *const f32, d_motion: *const f32, phase_step: f32,
+                                               cam: *const RbrtCamera, cam_prev: *const RbrtCamera, opts: *const c_void,
+                                               d_history_in: *const c_void, d_history_out: *mut c_void, d_out_a: *mut f32,
+                                               d_out_b: *mut f32, d_out_length: *mut f32) -> c_int;
     // device pointers; needs no scene handle. A host detects it by the symbol (the ABI version stays 2).
     pub fn rbrt_tonemap_opts_default(opts: *mut RbrtTonemapOpts);
     pub fn rbrt_hip_tonemap(device: c_int, stream: *mut c_void, d_radiance: *const f32, n_pixels: usize, opts: *const RbrtTonemapOpts,

@@ -180,14 +180,21 @@ class HipScene:
 
     def render_features(self, cam: abi.Camera, opts: abi.RenderOpts, samples: int | None = None, d_albedo: int | None = None,
                         d_normal: int | None = None, d_depth: int | None = None, d_coverage: int | None = None,
-                        d_object: int | None = None, lens=None, stream: int | None = None, reserved=(0, 0, 0)):
+                        d_object: int | None = None, lens=None, stream: int | None = None, reserved=(0, 0, 0),
+                        d_motion: int | None = None):
         """The feature buffers of the primary rays into device pointers (rbrt_hip_render_features): the means over `samples`
         samples a pixel (None: the library's default, 4) of the albedo and the normal, float32 [H, W, 3], of the depth and
         the coverage, float32 [H, W], and the object id of sample 0, int32 [H, W]; each may be None. Asynchronous on `stream`.
-        `lens`: see _cam_arg (opts is not changed)."""
+        `lens`: see _cam_arg (opts is not changed). `d_motion` (not None: rbrt_hip_render_features_motion; 0 is its NULL): the
+        mean travel of what the samples hit, float32 [H, W, 3]."""
         opts = _opts_copy(opts)
         cam_p, _keep = _cam_arg(cam, lens, opts)
         f = feature_opts(samples, reserved)
+        if d_motion is not None:
+            abi.check(self._lib.rbrt_hip_render_features_motion(self._h, cam_p, C.byref(opts), C.byref(f), C.c_void_p(stream or 0),
+                                                                C.c_void_p(d_albedo or 0), C.c_void_p(d_normal or 0), C.c_void_p(d_depth or 0),
+                                                                C.c_void_p(d_coverage or 0), C.c_void_p(d_object or 0), C.c_void_p(d_motion or 0)))
+            return
         abi.check(self._lib.rbrt_hip_render_features(self._h, cam_p, C.byref(opts), C.byref(f), C.c_void_p(stream or 0),
                                                      C.c_void_p(d_albedo or 0), C.c_void_p(d_normal or 0), C.c_void_p(d_depth or 0),
                                                      C.c_void_p(d_coverage or 0), C.c_void_p(d_object or 0)))
@@ -235,6 +242,11 @@ class HipScene:
         mo.reserved = int(reserved)
         mo.travel = None if null_travel else tv.ctypes.data_as(abi.f32p)
         abi.check(self._lib.rbrt_hip_scene_set_motion(self._h, C.byref(mo)))
+
+    def set_motion_phase(self, phase: float):
+        """Sets the phase of the handle's motion (rbrt_hip_scene_set_motion_phase): a sample with the draw t sees sphere i at
+        center_i + (phase + t) * travel_i. 0 by default; it goes with the launches issued after the call."""
+        abi.check(self._lib.rbrt_hip_scene_set_motion_phase(self._h, C.c_float(phase)))
 
     def environment_lookup(self, dirs):
         """The environment's radiance for each direction, used as it is (rbrt_hip_debug_environment; test hook): float32
@@ -566,13 +578,23 @@ def temporal_history_bytes(width: int, height: int) -> int:
 def temporal_accumulate(device: int, d_a: int, d_b: int, d_normal: int, d_depth: int, d_coverage: int, cam: abi.Camera,
                         cam_prev: abi.Camera | None, d_history_in: int | None, d_history_out: int | None,
                         d_out_a: int | None = None, d_out_b: int | None = None, d_out_length: int | None = None,
-                        opts: abi.TemporalOpts | None = None, stream: int | None = None):
+                        opts: abi.TemporalOpts | None = None, stream: int | None = None, d_motion: int | None = None,
+                        phase_step: float | None = None):
     """One frame of temporal accumulation in device memory (rbrt_hip_temporal_accumulate): d_a, d_b, d_normal row-major float32
     [H, W, 3]; d_depth, d_coverage and d_out_length float32 [H, W], W and H being `cam`'s; the histories
     temporal_history_bytes(W, H) bytes each, 16-byte aligned, two that alternate. d_history_in None: the first frame (cam_prev
     may then be None). d_out_a may be d_a and d_out_b may be d_b. `opts`: temporal_opts(...), None for the library's defaults.
-    Asynchronous on `stream`."""
+    Asynchronous on `stream`. With `d_motion` or `phase_step` not None the call is rbrt_hip_temporal_accumulate_moving: d_motion
+    this frame's motion buffer, float32 [H, W, 3] (None or 0: its NULL), phase_step this frame's phase minus the last one's."""
     t = opts if opts is not None else temporal_opts()
+    if d_motion is not None or phase_step is not None:
+        abi.check(load_hip().rbrt_hip_temporal_accumulate_moving(
+            device, C.c_void_p(stream or 0), C.c_void_p(d_a or 0), C.c_void_p(d_b or 0), C.c_void_p(d_normal or 0), C.c_void_p(d_depth or 0),
+            C.c_void_p(d_coverage or 0), C.c_void_p(d_motion or 0), C.c_float(0.0 if phase_step is None else phase_step),
+            C.byref(cam) if cam is not None else None, C.byref(cam_prev) if cam_prev is not None else None, C.byref(t),
+            C.c_void_p(d_history_in or 0), C.c_void_p(d_history_out or 0), C.c_void_p(d_out_a or 0), C.c_void_p(d_out_b or 0),
+            C.c_void_p(d_out_length or 0)))
+        return
     abi.check(load_hip().rbrt_hip_temporal_accumulate(device, C.c_void_p(stream or 0), C.c_void_p(d_a or 0), C.c_void_p(d_b or 0),
                                                       C.c_void_p(d_normal or 0), C.c_void_p(d_depth or 0), C.c_void_p(d_coverage or 0),
                                                       C.byref(cam) if cam is not None else None,

@@ -348,6 +348,12 @@ HIP_SYMBOLS = {
     "rbrt_hip_scene_set_environment": (C.c_int, [C.c_void_p, C.POINTER(Environment)]),
     "rbrt_hip_scene_set_shutter": (C.c_int, [C.c_void_p, C.POINTER(Shutter)]),
     "rbrt_hip_scene_set_motion": (C.c_int, [C.c_void_p, C.POINTER(Motion)]),
+    "rbrt_hip_scene_set_motion_phase": (C.c_int, [C.c_void_p, C.c_float]),
+    "rbrt_hip_render_features_motion": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderOpts), C.POINTER(FeatureOpts), C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rbrt_hip_temporal_accumulate_moving": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p, C.c_float, C.POINTER(Camera), C.POINTER(Camera), C.POINTER(TemporalOpts),
+                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rbrt_feature_opts_default": (None, [C.POINTER(FeatureOpts)]),
     "rbrt_hip_render_features": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderOpts), C.POINTER(FeatureOpts), C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -256,6 +256,10 @@ struct rbrt_hip_scene {
     uint32_t motion_gen = 0;
     std::vector<DevSphere> h_spheres;
     std::vector<uint32_t> sphere_src;
+    // The motion's phase (rbrt_hip_scene_set_motion_phase; rbrt_hip.h "Animation"): a word of the launch's parameters, read only
+    // while a motion is set; h_motion: the travels' host copy in the device array's order, for the check of the sweep's end.
+    float motion_phase = 0.0f;
+    std::vector<float> h_motion;
     // workspace, grown on demand
     // Frame pipeline: consecutive trace launches (the batches of one render, or successive renders) alternate
     // over `pipeline` lanes. Every lane has its own sample buffer, work counters and per-wave scratch, and --
@@ -300,6 +304,7 @@ struct rbrt_hip_scene {
             uint32_t shutter;    // the handle's shutter when the tables were made (all zero without one): it widens the margins
             float travel[3];
             uint32_t motion_gen;  // the handle's motion when the tables were made, by the number of the call that set it (0 without one)
+            float motion_phase;   // ... and its phase (0 without a motion): the margins are made around the advanced centres
         };
         struct TileSet {
             uint32_t* d_cull = nullptr;    // [n_tiles]
@@ -962,7 +967,7 @@ int fill_trace_params(const rbrt_hip_scene* s, const rbrt_camera_t* cam, const r
         P.shutter = 1u;
         for (int c = 0; c < 3; ++c) P.travel[c] = s->travel[c];
     }
-    if (cam && s->has_motion) P.motion = s->d_motion, P.motion_gen = s->motion_gen;  // (the same: the ray hooks see the spheres at the opening)
+    if (cam && s->has_motion) P.motion = s->d_motion, P.motion_gen = s->motion_gen, P.motion_phase = s->motion_phase;  // (the same: the ray hooks see the spheres at the opening)
     P.n_spheres = s->n_spheres;
     P.n_meshes = s->n_meshes;
     P.n_elem_tris = s->n_elem_tris;
@@ -1894,6 +1899,7 @@ rbrt_hip_scene::Lane::TileKey tile_key(const TraceParams& P, uint32_t list_mode)
     k.shutter = P.shutter;
     for (int c = 0; c < 3; ++c) k.travel[c] = P.travel[c];
     k.motion_gen = P.motion ? P.motion_gen : 0u;
+    k.motion_phase = P.motion ? P.motion_phase : 0.0f;
     return k;
 }
 
@@ -2404,6 +2410,13 @@ void rbrt_feature_opts_default(rbrt_feature_opts_t* f) {
 // by the next render call, as for rbrt_hip_trace_rays).
 int rbrt_hip_render_features(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, const rbrt_render_opts_t* o, const rbrt_feature_opts_t* f,
                              void* stream, float* d_albedo, float* d_normal, float* d_depth, float* d_coverage, int32_t* d_object) {
+    return rbrt_hip_render_features_motion(s, cam, o, f, stream, d_albedo, d_normal, d_depth, d_coverage, d_object, nullptr);
+}
+
+// (d_motion NULL: the kernel's build without the channel, what rbrt_hip_render_features has always launched)
+int rbrt_hip_render_features_motion(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, const rbrt_render_opts_t* o, const rbrt_feature_opts_t* f,
+                                    void* stream, float* d_albedo, float* d_normal, float* d_depth, float* d_coverage, int32_t* d_object,
+                                    float* d_motion) {
     if (!s || !cam || !o || !f) return fail(RBRT_ERR_INVALID_ARG, "render_features: null argument");
     if (f->samples == 0u || f->samples > 65536u) return fail(RBRT_ERR_INVALID_ARG, "render_features: samples must be 1..65536");
     if (f->reserved[0] != 0u || f->reserved[1] != 0u || f->reserved[2] != 0u)
@@ -2416,7 +2429,7 @@ int rbrt_hip_render_features(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, cons
     if (o->tile_world > 1u) return fail(RBRT_ERR_UNSUPPORTED, "render_features: tile_world > 1 (features are made of the whole frame)");
     if (uint64_t(cam->img_width_pix) * cam->img_height_pix >= (1ull << 32))
         return fail(RBRT_ERR_UNSUPPORTED, "render_features: image has 2^32 or more pixels");
-    if (!d_albedo && !d_normal && !d_depth && !d_coverage && !d_object) return RBRT_OK;
+    if (!d_albedo && !d_normal && !d_depth && !d_coverage && !d_object && !d_motion) return RBRT_OK;
     HIP_TRY(hipSetDevice(s->device));
     TraceParams P;
     fill_trace_params(s, cam, o, P);
@@ -2425,7 +2438,7 @@ int rbrt_hip_render_features(rbrt_hip_scene_t* s, const rbrt_camera_t* cam, cons
     FeatureParams F;
     std::memset(&F, 0, sizeof(F));
     F.samples = f->samples, F.inv_n = 1.0f / float(f->samples), F.stack_entries = s->stack_need;
-    F.albedo = d_albedo, F.normal = d_normal, F.depth = d_depth, F.coverage = d_coverage, F.object = d_object;
+    F.albedo = d_albedo, F.normal = d_normal, F.depth = d_depth, F.coverage = d_coverage, F.object = d_object, F.motion = d_motion;
     HIP_TRY(launch_features(P, F, static_cast<hipStream_t>(stream)));
     return RBRT_OK;
 }
@@ -2529,6 +2542,14 @@ int rbrt_hip_scene_set_shutter(rbrt_hip_scene_t* s, const rbrt_shutter_t* shutte
     return RBRT_OK;
 }
 
+// A component of the end of sphere i's sweep at `phase`, center + ((phase + 1) * travel) in float32 as the kernels make it: finite?
+static bool sweep_end_finite(float center, float travel, float phase) {
+    const volatile float s1 = phase + 1.0f;
+    const volatile float prod = s1 * travel;
+    const volatile float end = center + prod;
+    return std::isfinite(end);
+}
+
 // The handle's motion (rbrt_hip.h "Moving spheres"). Everything is checked before the device is touched; then, like the
 // environment, the call waits for the launches that read the old travels and puts the new ones on the device.
 int rbrt_hip_scene_set_motion(rbrt_hip_scene_t* s, const rbrt_motion_t* motion) {
@@ -2545,6 +2566,8 @@ int rbrt_hip_scene_set_motion(rbrt_hip_scene_t* s, const rbrt_motion_t* motion) 
                 if (!std::isfinite(tv[c])) return fail(RBRT_ERR_INVALID_ARG, "set_motion: sphere " + std::to_string(s->sphere_src[i]) + " has a travel that is not finite");
                 const volatile float end = s->h_spheres[i].center[c] + tv[c];  // (float32, as the kernels add it)
                 if (!std::isfinite(end)) return fail(RBRT_ERR_INVALID_ARG, "set_motion: sphere " + std::to_string(s->sphere_src[i]) + ": center + travel is not finite");
+                if (!sweep_end_finite(s->h_spheres[i].center[c], tv[c], s->motion_phase))
+                    return fail(RBRT_ERR_INVALID_ARG, "set_motion: sphere " + std::to_string(s->sphere_src[i]) + ": center + (phase + 1) * travel is not finite");
                 dev[3u * i + c] = tv[c];
             }
         }
@@ -2561,8 +2584,25 @@ int rbrt_hip_scene_set_motion(rbrt_hip_scene_t* s, const rbrt_motion_t* motion) 
         if (!dev.empty()) HIP_TRY(hipMemcpy(s->d_motion, dev.data(), dev.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     s->has_motion = motion != nullptr;
+    s->h_motion = std::move(dev);
     s->motion_gen += 1u;
     if (s->motion_gen == 0u) s->motion_gen = 1u;
+    return RBRT_OK;
+}
+
+// The motion's phase (rbrt_hip.h "Animation"): a word of the handle that fill_trace_params copies into the parameters of every
+// launch issued from now on. A launch in flight has its own copy (kernel arguments; a helper launch copies those of the launch
+// it joins), so nothing waits and the device is not touched.
+int rbrt_hip_scene_set_motion_phase(rbrt_hip_scene_t* s, float phase) {
+    if (!s) return fail(RBRT_ERR_INVALID_ARG, "set_motion_phase: null scene");
+    if (!std::isfinite(phase)) return fail(RBRT_ERR_INVALID_ARG, "set_motion_phase: the phase is not finite");
+    if (s->has_motion)
+        for (uint32_t i = 0; i < s->n_spheres; ++i)
+            for (int c = 0; c < 3; ++c)
+                if (!sweep_end_finite(s->h_spheres[i].center[c], s->h_motion[3u * i + c], phase))
+                    return fail(RBRT_ERR_INVALID_ARG, "set_motion_phase: sphere " + std::to_string(s->sphere_src[i]) + ": center + (phase + 1) * travel is not finite");
+    std::lock_guard<std::mutex> watcher_lock(s->mu);  // (a helper launch copies the parameters of the launch it joins)
+    s->motion_phase = phase;
     return RBRT_OK;
 }
 

@@ -224,11 +224,14 @@ struct TraceParams {
     uint32_t shutter;
     float travel[3];
     // The handle's motion (rbrt_hip_scene_set_motion): motion = [n_spheres][3], sphere i's translation during the exposure, on the
-    // device; null (no motion): never read, and without a shutter no draw is made. gtime: [n_waves][kPool], the draw t of the path
-    // in each pool slot of the trace kernel, beside gseq; allocated, written and read in a motion launch only
+    // device; null (no motion): never read, and without a shutter no draw is made. gtime: [n_waves][kPool], the time s = phase + t
+    // of the path in each pool slot of the trace kernel, beside gseq; allocated, written and read in a motion launch only
     const float* motion;
     float* gtime;
     uint32_t motion_gen;  // host only: the number of the rbrt_hip_scene_set_motion call the travels are from (the tile-table key)
+    // The motion's phase (rbrt_hip_scene_set_motion_phase): a sample with the draw t sees sphere i at c_i + (s * travel_i),
+    // s = motion_phase + t, one float32 addition. Read only where `motion` is not null; 0 gives s the bits of t
+    float motion_phase;
     // The handle's environment (rbrt_hip_scene_set_environment): (env_n + 1)^2 texels of 16 bytes; null: bg / the sky gradient
     const EnvTexel* env_nodes;
     uint32_t env_n;
@@ -273,6 +276,8 @@ struct FeatureParams {
     float* depth;            // [H][W]
     float* coverage;         // [H][W]
     int32_t* object;         // [H][W]
+    float* motion;           // [H][W][3]: the mean travel of what the samples hit (rbrt_hip_render_features_motion); null in
+                             // every launch of the kernel's build without the channel
 };
 
 // Adaptive sampling (include/rbrt_hip.h "Adaptive sampling"): what adaptive_lists_kernel, tile_error_kernel and
@@ -384,6 +389,10 @@ struct TemporalParams {
     float pos_prev[3], right_prev[3], up_prev[3];
     float n[3], w[3];
     float wn, rr, uu, ru, det, sx, sy, hx, hy;
+    // rbrt_hip_temporal_accumulate_moving: [H][W][3] the motion buffer of this frame and this frame's phase minus the last
+    // frame's; null in every launch of the kernel's build that follows no motion, which reads neither
+    const float* motion;
+    float phase_step;
 };
 
 // Guided upsampling (include/rbrt_hip.h "Guided upsampling"; upsample.hip): one rbrt_hip_upsample_halves call.

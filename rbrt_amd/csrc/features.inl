@@ -8,9 +8,13 @@
 // tree can need, not kStackMax, so a CU holds as many waves as it has slots for. A lane beyond a ragged edge leaves at once:
 // nothing below exchanges data between lanes (the wave votes inside ieee_sqrt, normalize and lens_point only choose between
 // forms that give the same bits, and see the active lanes only).
+//
+// Two builds: features_kernel<false> is what rbrt_hip_render_features has always launched; features_kernel<true> also sums
+// the travel of the sphere each sample hits (rbrt_hip_render_features_motion with d_motion; include/rbrt_hip.h "Animation").
 
 constexpr int kFeatureBlock = 64;
 
+template <bool MOTION>
 __global__ __launch_bounds__(kFeatureBlock) void features_kernel(const TraceParams P, const FeatureParams F) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     uint32_t* stack = lds + threadIdx.x;
@@ -23,6 +27,7 @@ __global__ __launch_bounds__(kFeatureBlock) void features_kernel(const TracePara
     const uint32_t n_elem = P.n_spheres + P.n_elem_tris;
     V3 a = mk(0.0f, 0.0f, 0.0f), nsum = mk(0.0f, 0.0f, 0.0f);
     float z = 0.0f, c = 0.0f;
+    V3 mv = mk(0.0f, 0.0f, 0.0f);  // (MOTION only)
     int32_t first_obj = -1;
     for (uint32_t s = 0; s < F.samples; ++s) {
         Rng rng;
@@ -37,12 +42,14 @@ __global__ __launch_bounds__(kFeatureBlock) void features_kernel(const TracePara
         float mt = 0.0f;
         if (P.shutter || P.motion) mt = rng.next_f32();
         if (P.shutter) shutter_origin(o, P.travel, mt);
+        if (P.motion) mt = P.motion_phase + mt;  // "Animation": s = phase + t, the spheres' time; the shutter kept the raw t
         HitRec h;
         LocalCounters lc = {0, 0, 0, 0, 0};
         scene_hit<false>(P, o, d, stack, uint32_t(kFeatureBlock), h, lc, P.motion, mt);
         if (s == 0) first_obj = h.obj;
         V3 sa = mk(0.0f, 0.0f, 0.0f), sn = mk(0.0f, 0.0f, 0.0f);  // a miss: every channel adds +0
         float sz = 0.0f, sc = 0.0f;
+        V3 sm = mk(0.0f, 0.0f, 0.0f);  // ... and a mesh, a BasicTriangle and anything on a handle without a motion
         if (h.obj >= 0) {
             const DevMaterial m = P.materials[h.obj];
             sa = m.kind == RBRT_MAT_DIELECTRIC ? mk(1.0f, 1.0f, 1.0f) : mk(m.albedo);  // dielectric.rs:18: its attenuation
@@ -54,8 +61,11 @@ __global__ __launch_bounds__(kFeatureBlock) void features_kernel(const TracePara
             if (uint32_t(h.obj) < n_elem) {
                 const uint32_t desc = P.elems != nullptr ? P.elems[h.obj] : uint32_t(h.obj);
                 if (desc >> 31) g = mk(P.elem_tris[desc & 0x7FFFFFFFu].normal);  // triangle.rs:432
-                else g = (o + h.t * d) - (P.motion ? sphere_centre_at(P.spheres[desc].center, P.motion + desc * kMotionDw, mt)
-                                                   : mk(P.spheres[desc].center));  // sphere.rs:56
+                else {
+                    g = (o + h.t * d) - (P.motion ? sphere_centre_at(P.spheres[desc].center, P.motion + desc * kMotionDw, mt)
+                                                  : mk(P.spheres[desc].center));  // sphere.rs:56
+                    if (MOTION && P.motion) sm = mk(P.motion + desc * kMotionDw);
+                }
             } else {
                 g = mesh_shading_normal(P.meshes[uint32_t(h.obj) - n_elem].normals, h.tri, o, d);
             }
@@ -67,6 +77,7 @@ __global__ __launch_bounds__(kFeatureBlock) void features_kernel(const TracePara
         nsum = nsum + sn;
         z = z + sz;
         c = c + sc;
+        if (MOTION) mv = mv + sm;
     }
     const size_t i = size_t(row) * width + col;
     if (F.albedo) {
@@ -82,12 +93,18 @@ __global__ __launch_bounds__(kFeatureBlock) void features_kernel(const TracePara
     if (F.depth) F.depth[i] = z * F.inv_n;
     if (F.coverage) F.coverage[i] = c * F.inv_n;
     if (F.object) F.object[i] = first_obj;
+    if (MOTION) {
+        F.motion[i * 3 + 0] = mv.x * F.inv_n;
+        F.motion[i * 3 + 1] = mv.y * F.inv_n;
+        F.motion[i * 3 + 2] = mv.z * F.inv_n;
+    }
 }
 
 // One single-wave workgroup per tile of the image, row-major; F.stack_entries * 64 words of LDS each.
 hipError_t launch_features(const TraceParams& P, const FeatureParams& F, hipStream_t stream) {
     if (P.n_tiles == 0) return hipSuccess;
     const size_t lds = size_t(F.stack_entries) * kFeatureBlock * sizeof(uint32_t);  // (a multiple of 256 bytes: the base stays 16-byte aligned)
-    hipLaunchKernelGGL(features_kernel, dim3(P.n_tiles), dim3(kFeatureBlock), lds, stream, P, F);
+    if (F.motion) hipLaunchKernelGGL(features_kernel<true>, dim3(P.n_tiles), dim3(kFeatureBlock), lds, stream, P, F);
+    else hipLaunchKernelGGL(features_kernel<false>, dim3(P.n_tiles), dim3(kFeatureBlock), lds, stream, P, F);
     return hipGetLastError();
 }

@@ -166,6 +166,15 @@ int rbrt_hip_temporal_accumulate(int device, void* stream, const float* d_a, con
                                  const float* d_depth, const float* d_coverage, const rbrt_camera_t* cam, const rbrt_camera_t* prev,
                                  const rbrt_temporal_opts_t* o, const void* d_history_in, void* d_history_out, float* d_out_a,
                                  float* d_out_b, float* d_out_length) {
+    return rbrt_hip_temporal_accumulate_moving(device, stream, d_a, d_b, d_normal, d_depth, d_coverage, nullptr, 0.0f, cam, prev, o, d_history_in,
+                                               d_history_out, d_out_a, d_out_b, d_out_length);
+}
+
+// (d_motion NULL: the plain rule and the kernel's build that has always run it; phase_step is then not read)
+int rbrt_hip_temporal_accumulate_moving(int device, void* stream, const float* d_a, const float* d_b, const float* d_normal,
+                                        const float* d_depth, const float* d_coverage, const float* d_motion, float phase_step,
+                                        const rbrt_camera_t* cam, const rbrt_camera_t* prev, const rbrt_temporal_opts_t* o,
+                                        const void* d_history_in, void* d_history_out, float* d_out_a, float* d_out_b, float* d_out_length) {
     if (!d_a || !d_b || !d_normal || !d_depth || !d_coverage || !cam || !o) return fail(RBRT_ERR_INVALID_ARG, "temporal_accumulate: null argument");
     if (d_history_in && !prev) return fail(RBRT_ERR_INVALID_ARG, "temporal_accumulate: a history needs cam_prev");
     if (d_history_in && d_history_in == d_history_out)
@@ -182,10 +191,12 @@ int rbrt_hip_temporal_accumulate(int device, void* stream, const float* d_a, con
     if (!all_zero(o->reserved)) return fail(RBRT_ERR_INVALID_ARG, "temporal_accumulate: reserved must be 0");
     if (!positive_finite(cam->mm_per_pix_hor) || !positive_finite(cam->mm_per_pix_vert))
         return fail(RBRT_ERR_INVALID_ARG, "temporal_accumulate: cam's mm_per_pix must be finite and > 0");
+    if (d_motion && !std::isfinite(phase_step)) return fail(RBRT_ERR_INVALID_ARG, "temporal_accumulate_moving: phase_step is not finite");
 
     TemporalParams T = zeroed<TemporalParams>();
     T.a = d_a, T.b = d_b, T.normal = d_normal, T.depth = d_depth, T.coverage = d_coverage;
     T.history_in = d_history_in, T.history_out = d_history_out, T.out_a = d_out_a, T.out_b = d_out_b, T.out_length = d_out_length;
+    if (d_motion) T.motion = d_motion, T.phase_step = phase_step;
     T.width = width, T.height = height;
     T.max_history = o->max_history, T.kz = o->depth, T.kn2 = o->normal * o->normal;
     for (int k = 0; k < 3; ++k)

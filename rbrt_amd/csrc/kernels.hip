@@ -1075,6 +1075,22 @@ __global__ __launch_bounds__(kSmallBlock) void sky_resolve_kernel(const TracePar
 // the same draw, which the bound never uses: it holds for every pair of them. Without a motion org_a_i = org_a exactly (the
 // branch is not taken) and every word is what it was, bit for bit. The bit proves the CAMERA ray's test fails; a bounce ray
 // of the path tests every sphere.
+//
+// A phase (rbrt_hip.h "Animation"; TraceParams::motion_phase = ph). The camera ray of a sample with the draw t tests sphere i at
+// c_i(s) = fl(c_i + fl(s travel_i)), s = fl(ph + t). The bound follows the sphere: it is made around the ADVANCED centre
+// C_i = c_i + ph travel_i, which the kernel has in double (the product of two floats is exact there, the sum rounds at 2^-53),
+// not around c_i with (|ph| + 1) |travel_i| of margin, under which nothing would be culled at frame 40. What is left between
+// C_i and c_i(s), with |s| <= (|ph| + 1)(1 + u):
+//     s = ph + t + e_s, |e_s| <= u (|ph| + 1)                      the ONE rounding the phase adds
+//     s travel_i - ph travel_i = (t + e_s) travel_i                 at most |travel_i| + u (|ph| + 1) |travel_i| long
+//     fl(s travel_i): one rounding per component                    at most u |s| |travel_i| <= u (1 + u) (|ph| + 1) |travel_i|
+//     fl(c_i + ...): one rounding per component                     at most u (|c_i| + (1 + 2u) (|ph| + 1) |travel_i|)
+// together |c_i(s) - C_i| <= |travel_i| + 3 u (|c_i| + (|ph| + 1) |travel_i|) + O(u^2): the candidate
+//     org_a_i = org_a + |travel_i| + 16 u (|c_i| + (|ph| + 1) |travel_i|)
+// covers the float error five times over, C_i's own rounding in double included. q = (c_i - position) + ph travel_i, and l and
+// qhat are taken from it (in that order, so that the centre's registers are free before the product is made). With
+// ph = 0, C_i = c_i exactly and the margin is the one above: every word is what it was without a phase, bit for bit. The
+// margin grows with |ph| only through the rounding term, 1e-6 (|ph| + 1) |travel_i|.
 // ---------------------------------------------------------------------------------------------
 struct D3 {
     double x, y, z;
@@ -1220,15 +1236,18 @@ __global__ __launch_bounds__(kCullBlock, 4) void primary_cull_kernel(const Trace
         bool out = false;
         if (!(desc >> 31)) {
             const DevSphere sp = P.spheres[desc];
-            const D3 q = d3(sp.center) - pos;
-            const double r = double(sp.radius), l = dlen(q);
-            // Moving spheres (header, "Moving spheres"): this sphere's own bound on where a ray starts RELATIVE TO IT. Without
-            // a motion it is org_a itself (the branch is not taken).
+            // Moving spheres (header, "Moving spheres", "A phase"): this sphere's own bound on where a ray starts RELATIVE TO IT,
+            // around the centre the phase has advanced it to. Without a motion they are org_a and the centre themselves (the
+            // branch is not taken).
+            D3 q = d3(sp.center) - pos;
             double org_a = org_all;
             if (P.motion) {
-                const double tl = dlen(d3(P.motion + desc * kMotionDw));
-                org_a = org_all + tl + 16.0 * (1.0 / 16777216.0) * (dlen(d3(sp.center)) + tl);
+                const D3 tv = d3(P.motion + desc * kMotionDw);
+                const double ph = double(P.motion_phase), tl = dlen(tv);
+                org_a = org_all + tl + 16.0 * (1.0 / 16777216.0) * (dlen(d3(sp.center)) + (fabs(ph) + 1.0) * tl);
+                q = q + ph * tv;  // (C_i - position)
             }
+            const double r = double(sp.radius), l = dlen(q);
             if (r > 0.0 && r < 1e30 && l < 1e30) {  // (false for NaN)
                 // (the second term is the analysed one, 15x the bound in the header; the others are loose change on top)
                 const double lo = l + org_a;  // (the distance of a ray's origin from the centre)
@@ -1907,7 +1926,7 @@ __host__ __device__ inline uint32_t megakernel_lds_dwords(uint32_t stack_entries
                            (thin_lens ? kLensDw : 0u) +                                // a lens launch's lens (nothing for a pinhole)
                            (environment ? kEnvDw : 0u) +                               // the map's address and size (nothing without one)
                            (shutter ? kShutterDw : 0u) +                               // a shutter launch's travel (nothing without a shutter)
-                           (motion ? n_spheres * kMotionDw : 0u) +                     // a motion launch's travels (nothing without a motion)
+                           (motion ? n_spheres * kMotionDw + 1u : 0u) +                // a motion launch's travels and phase (nothing without a motion)
                            (n_elem_tris != 0u ? n_elem_tris * kTriDw + n_elem : 0u);  // triangle table + element order
     const uint32_t pool_pad = (uint32_t(kPool) + 63u) & ~63u;  // status + list: one byte per (padded) slot each
     uint32_t dw = uint32_t(kFields * kPool) + kCellDw + kTqDw + kHelpDw + pool_pad / 2u + stack_entries * 64u + scene;

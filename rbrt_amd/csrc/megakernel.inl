@@ -381,6 +381,7 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                            (K.environment() ? kEnvDw : 0u) + (K.shutter() ? kShutterDw : 0u);
             const uint32_t* gmv = reinterpret_cast<const uint32_t*>(P.motion);
             for (uint32_t i = lane; i < P.n_spheres * kMotionDw; i += 64) md[i] = gmv[i];
+            if (lane == 0) md[P.n_spheres * kMotionDw] = __float_as_uint(P.motion_phase);  // ... and the phase behind them ("Animation")
         }
         if (lane == 0) {
             float* gf = reinterpret_cast<float*>(dst);
@@ -899,7 +900,8 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
         uint32_t item = 0, depth = 0, nrec = 0, word = 0;
         bool have_ray = false;
         // A motion launch (wave-uniform, decided per launch: bit 5 of the flags word; constant 0 in the PLAIN build): mtr = the
-        // spheres' travels in LDS, mt = the draw t of the path this lane holds (sphere_centre_at)
+        // spheres' travels in LDS with the motion's phase behind them, mt = the time s = phase + t of the path this lane holds
+        // (sphere_centre_at; the phase is read from LDS where a path is generated: as a kernel argument it cost an SGPR spill)
         const uint32_t mflags = K.gen_flags(uint32_t(__builtin_amdgcn_readfirstlane(int(gp[G_FLAGS]))));
         const bool motion = (mflags & 32u) != 0u;
         const float* const mtr = gpf + (mflags >> 8) + ((mflags & 4u) ? kLensDw : 0u) + ((mflags & 8u) ? kEnvDw : 0u) + ((mflags & 16u) ? kShutterDw : 0u);
@@ -1038,7 +1040,9 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                                 mt = rng.next_f32();
                                 if (gen_flags & 16u)  // the handle's shutter: the travel behind the lens and the map
                                     shutter_origin(o, gpf + (gen_flags >> 8) + ((gen_flags & 4u) ? kLensDw : 0u) + ((gen_flags & 8u) ? kEnvDw : 0u), mt);
-                                if (gen_flags & 32u) gtime[slot] = mt;  // the path keeps it through every park and resume
+                                // the path keeps the spheres' time through every park and resume: s = phase + t ("Animation"; the
+                                // shutter above kept the raw t, and a phase of 0 leaves t's bits)
+                                if (gen_flags & 32u) mt = mtr[P.n_spheres * kMotionDw] + mt, gtime[slot] = mt;
                             }
                             depth = gp[G_MAX_DEPTH];
                             nrec = 0;

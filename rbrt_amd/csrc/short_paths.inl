@@ -92,6 +92,7 @@ __device__ __forceinline__ bool short_path_sample(const TraceParams& P, const Sc
     float mt = 0.0f;  // one draw for the shutter and the motion; with a motion it stays the sample's for both rays
     if (P.shutter || P.motion) mt = rng.next_f32();
     if (P.shutter) shutter_origin(o, P.travel, mt);
+    if (P.motion) mt = P.motion_phase + mt;  // "Animation": s = phase + t, the spheres' time; the shutter kept the raw t
     uint32_t depth = P.max_depth;
     float closest, ht;
     int32_t obj;

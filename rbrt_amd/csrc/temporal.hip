@@ -14,6 +14,10 @@
 //   are accumulated sequentially in the rule's order: no atomics, no cross-lane sums, no LDS. A thread reads its own pixel of
 //   A and B before it writes, so an output may lie on its input. Every tap index is tested against the image as an integer
 //   before it is used: no read leaves the buffers whatever the floats are.
+//   Two builds: temporal_kernel<false> is the rule of "Temporal accumulation" and what rbrt_hip_temporal_accumulate has always
+//   launched; temporal_kernel<true> (rbrt_hip_temporal_accumulate_moving with a motion buffer) reads 12 more bytes a pixel, the
+//   pixel's own mean travel, and looks the history up where the surface WAS: one division per component, a product and a
+//   difference in front of v. Whatever the motion's floats are they only move xs and ys, which are tested as before.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -42,6 +46,7 @@ struct Sums {
     float ws, sa[3], sb[3], sl;
 };
 
+template <bool MOVING>
 __global__ __launch_bounds__(kThreads) void temporal_kernel(const TemporalParams T) {
     const size_t npix = size_t(T.width) * T.height;
     const size_t p = size_t(blockIdx.x) * kThreads + threadIdx.x;
@@ -70,7 +75,12 @@ __global__ __launch_bounds__(kThreads) void temporal_kernel(const TemporalParams
         F3 v = d;
         if (surface) {
             const float zbar = z / c;
-            const F3 P = pos + (zbar * d);
+            F3 P = pos + (zbar * d);
+            if (MOVING) {  // "Animation": the point where it was when the last frame's shutter opened
+                const F3 mv = f3(T.motion + p * 3);
+                const F3 m = F3{mv.x / c, mv.y / c, mv.z / c};
+                P = P - (T.phase_step * m);
+            }
             v = P - f3(T.pos_prev);
         }
         // its projection into K'
@@ -150,11 +160,13 @@ __global__ __launch_bounds__(kThreads) void temporal_kernel(const TemporalParams
 
 }  // namespace
 
-// (the arguments have been checked: rbrt_hip_temporal_accumulate)
+// (the arguments have been checked: rbrt_hip_temporal_accumulate, rbrt_hip_temporal_accumulate_moving; T.motion chooses the build)
 hipError_t launch_temporal(const TemporalParams& T, hipStream_t stream) {
     const size_t npix = size_t(T.width) * T.height;
     if (npix == 0 || npix >= (size_t(1) << 31)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(temporal_kernel, dim3(uint32_t((npix + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream, T);
+    const dim3 grid(uint32_t((npix + kThreads - 1) / kThreads));
+    if (T.motion) hipLaunchKernelGGL(temporal_kernel<true>, grid, dim3(kThreads), 0, stream, T);
+    else hipLaunchKernelGGL(temporal_kernel<false>, grid, dim3(kThreads), 0, stream, T);
     return hipGetLastError();
 }
 

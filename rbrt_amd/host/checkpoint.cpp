@@ -65,7 +65,7 @@ uint64_t patterns_fingerprint(const rbrt_scene_patterns_t* pt, uint64_t h) {
 
 uint64_t checkpoint_fingerprint(const std::string& path, const rbrt_camera_lens_t& lens, const rbrt_render_opts_t& opts, const rbrt_scene_t& sc,
                                 const rbrt_scene_shading_t* sh, const Environment& env, const rbrt_scene_patterns_t* pt, const float* travel,
-                                const std::vector<float>* motion) {
+                                const std::vector<float>* motion, float motion_step) {
     if (path.empty()) return 0;
     uint64_t h = patterns_fingerprint(pt, shading_fingerprint(sc, sh, scene_fingerprint(lens.cam, sc)));
     if (opts.flags & RBRT_FLAG_CONSTANT_BACKGROUND) {
@@ -82,7 +82,13 @@ uint64_t checkpoint_fingerprint(const std::string& path, const rbrt_camera_lens_
         h = fnv1a(&lens.focus_scale, sizeof(lens.focus_scale), h);
     }
     h = shutter_fingerprint(travel, h);
-    return motion && !motion->empty() ? motion_fingerprint(motion->data(), uint32_t(motion->size() / 3u), h) : h;
+    if (!motion || motion->empty()) return h;
+    h = motion_fingerprint(motion->data(), uint32_t(motion->size() / 3u), h);
+    if (motion_step != 0.0f) {  // (the spheres advance between frames: other sums)
+        const char tag[8] = {'m', 's', 't', 'e', 'p', 0, 0, 0};
+        h = fnv1a(&motion_step, sizeof(motion_step), fnv1a(tag, sizeof(tag), h));
+    }
+    return h;
 }
 
 uint64_t motion_fingerprint(const float* travels, uint32_t n_spheres, uint64_t h) {

@@ -24,10 +24,11 @@ CheckpointHeader checkpoint_header(uint32_t width, uint32_t height, uint32_t spp
 // only where the render has it (so that a render without it keeps the fingerprint its checkpoints were written with), the
 // corner normals of smooth meshes, the solid patterns (pt), the constant background (opts.flags, opts.bg), the environment, the thin lens
 // (opts.flags says whether `lens` has one), the shutter (`travel`: null without one), the motion (`motion`: null or empty
-// without one). 0 for an empty path: there is no checkpoint to match.
+// without one) and, with a motion, a motion_step other than 0 (RenderConfig::motion_step). 0 for an empty path: there is no
+// checkpoint to match.
 uint64_t checkpoint_fingerprint(const std::string& path, const rbrt_camera_lens_t& lens, const rbrt_render_opts_t& opts, const rbrt_scene_t& sc,
                                 const rbrt_scene_shading_t* sh, const Environment& env, const rbrt_scene_patterns_t* pt = nullptr,
-                                const float* travel = nullptr, const std::vector<float>* motion = nullptr);
+                                const float* travel = nullptr, const std::vector<float>* motion = nullptr, float motion_step = 0.0f);
 // The shutter's part of it: h itself without a shutter (travel null), else h continued over a tag and the three floats -- a
 // zero travel included, whose draw makes its sums another render's.
 uint64_t shutter_fingerprint(const float* travel, uint64_t h);

@@ -213,6 +213,7 @@ int parse_cli(int argc, char** argv, CliOptions& o) {
         else if (a.is("--camera-step")) ok = a.triple(o.camera_step, o.camera_step_given, false, step);
         else if (a.is("--shutter-travel")) ok = a.triple(o.shutter_travel, o.shutter_travel_given, false, step);
         else if (a.is("--no-motion")) ok = a.flag(o.no_motion);
+        else if (a.is("--motion-step")) ok = a.f32(o.motion_step, finite, "a finite number: the exposures the moving spheres advance from one frame to the next");
         else if (a.is("--shutter"))
             ok = a.f32_unsigned_zero(o.shutter, at_least_0, "a finite number >= 0: the part of a frame's camera step the shutter is open for");
         else if (a.is("--temporal-max-history")) ok = a.f32_unsigned_zero(o.temporal_max_history, at_least_1, "a finite number >= 1");
@@ -304,6 +305,10 @@ int check_cli(const CliOptions& o, rbrt::PfmImage& compare_ref) {
                       {"--temporal-depth", o.temporal_depth.has_value()}, {"--temporal-normal", o.temporal_normal.has_value()},
                       {"--history-map", !o.history_map.empty()}});
     if (rc != CLI_RUN) return rc;
+    if (o.motion_step && !o.frames)
+        return refuse("error: '--motion-step' needs '--frames' (the spheres advance that many exposures from one frame to the next)\n");
+    if (o.motion_step && !std::isfinite(float(*o.frames - 1u) * *o.motion_step))  // (the last frame's phase, float32: the render loop makes the same product)
+        return refuse("error: '--motion-step' times the last frame's number is not finite\n");
     if (o.shutter && o.shutter_travel_given) return refuse("error: '--shutter' cannot be combined with '--shutter-travel' (either is the whole travel)\n");
     if (o.shutter && !o.camera_step_given)
         return refuse("error: '--shutter' needs '--camera-step' (the travel is that part of the step; '--shutter-travel' takes a travel itself)\n");
@@ -416,6 +421,7 @@ rbrt::RenderConfig config_of(const CliOptions& o, const rbrt::SceneBlueprint& bp
         cfg.tonemap_white = o.white ? *o.white : 0.0f;
     }
     cfg.no_motion = o.no_motion;
+    if (o.motion_step) cfg.motion_step = *o.motion_step;
     if (o.shutter || o.shutter_travel_given) {  // (the flags override the YAML's camera_shutter_travel)
         cfg.shutter = true;
         for (int c = 0; c < 3; ++c) cfg.shutter_travel[c] = o.shutter ? *o.shutter * o.camera_step[c] : o.shutter_travel[c];

@@ -49,6 +49,7 @@ struct CliOptions {
     float shutter_travel[3] = {0.0f, 0.0f, 0.0f};
     bool shutter_travel_given = false;
     bool no_motion = false;  // --no-motion: the spheres' shutter_travel keys are ignored
+    std::optional<float> motion_step;  // --motion-step P: the moving spheres advance P exposures a frame (needs --frames)
     std::string history_map;
     std::optional<uint32_t> upscale;  // --upscale turns guided upsampling on; the options below need it
     std::optional<float> upscale_normal, upscale_depth, upscale_albedo;

@@ -231,6 +231,7 @@ void ImageBuffer::save_features(const std::string& prefix) const {
     };
     write_grey(".depth.pfm", feature_depth);
     write_grey(".coverage.pfm", feature_coverage);
+    if (feature_motion.size() == n * 3) write_pfm(prefix + ".motion.pfm", feature_motion.data(), width, height);  // (a scene with a motion)
 }
 
 void ImageBuffer::save(const std::string& path) const {

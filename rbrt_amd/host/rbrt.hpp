@@ -285,6 +285,7 @@ struct ImageBuffer {
     std::vector<uint8_t> noisy_rgb;  // a denoised render with RenderConfig::keep_noisy: the unfiltered image, like rgb (else empty)
     // a render with RenderConfig::features: the feature buffers of the primary rays, row-major (else empty)
     std::vector<float> feature_albedo, feature_normal;  // 3 floats per pixel
+    std::vector<float> feature_motion;                  // 3 floats per pixel; empty unless the scene has a motion (PREFIX.motion.pfm)
     std::vector<float> feature_depth, feature_coverage; // 1 float per pixel
     std::vector<uint8_t> history_map;  // a render with RenderConfig::frames: one byte per pixel, the last frame's len * 255 / max_history (else empty)
     std::vector<uint8_t> spike_map;  // a render with RenderConfig::despike: one byte per traced pixel of the last frame, 0 none, 85 A, 170 B, 255 both (else empty)
@@ -407,6 +408,10 @@ struct RenderConfig {  // additions that the reference hard-codes or lacks
     // with which they share the draw; with --frames every frame exposes the same sweep (objects do not advance from frame to
     // frame). no_motion (the CLI's --no-motion): the keys are ignored, the scene renders as if it had none.
     bool no_motion = false;
+    // Animation (rbrt_hip_scene_set_motion_phase; the CLI's --motion-step, which needs --frames): frame k runs at the phase
+    // float(k) * motion_step, and with a motion and a step other than 0 the frame loop asks the features call for the motion
+    // buffer and accumulates with rbrt_hip_temporal_accumulate_moving. 0: every frame exposes the same sweep, as without the flag.
+    float motion_step = 0.0f;
     float temporal_max_history = 32.0f, temporal_depth = 0.05f, temporal_normal = 0.35f;  // (rbrt_temporal_opts_default)
     // Guided upsampling (rbrt_hip_upsample_halves; the CLI's --upscale, --upscale-*): the image is traced with the low camera of
     // rbrt_hip_upsample_camera (1 / upscale of the size in each direction) through the adaptive path's one round that stops

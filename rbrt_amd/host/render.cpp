@@ -546,6 +546,11 @@ struct Rank {
     rbrt_hip_scene_t* hs = nullptr;
     Stream stream;
     DeviceBuffer d_acc, d_rad, d_rgb, d_img;
+    // the motion buffer (rbrt_hip_render_features_motion), 3 floats a pixel: on a scene with a motion, where --features writes it
+    // or the frames' accumulation follows the spheres
+    DeviceBuffer d_motion;
+    bool animated() const { return !job.motion.empty() && cfg.frames && cfg.motion_step != 0.0f; }
+    bool want_motion() const { return !job.motion.empty() && (cfg.features || animated()); }
     DeviceBuffer d_features;  // a render with feature buffers: albedo, normal, depth, coverage (3 + 3 + 1 + 1 floats a pixel)
     DeviceBuffer d_noisy;  // a denoised, glared or transformed render that keeps the unfiltered image: that image's radiance
 };
@@ -736,10 +741,14 @@ void Rank::features() {
     fo.samples = cfg.feature_samples;
     EventTimer timer;  // (d_features lives until release: the guided filter reads it)
     if (!(d_features.alloc(n_pixels * 8 * sizeof(float), err, "hipMalloc(feature buffers)") && timer.create(err))) return;
+    if (want_motion() && !d_motion.alloc(n_pixels * 3 * sizeof(float), err, "hipMalloc(motion buffer)")) return;
     float* const d_albedo = d_features.as<float>();
     float *const d_normal = d_albedo + n_pixels * 3, *const d_depth = d_normal + n_pixels * 3, *const d_coverage = d_depth + n_pixels;
     timer.start(stream.get(), err);
-    err.lib_ok(rbrt_hip_render_features(hs, &job.lens.cam, &o, &fo, stream.get(), d_albedo, d_normal, d_depth, d_coverage, nullptr));
+    if (want_motion())
+        err.lib_ok(rbrt_hip_render_features_motion(hs, &job.lens.cam, &o, &fo, stream.get(), d_albedo, d_normal, d_depth, d_coverage, nullptr, d_motion.as<float>()));
+    else
+        err.lib_ok(rbrt_hip_render_features(hs, &job.lens.cam, &o, &fo, stream.get(), d_albedo, d_normal, d_depth, d_coverage, nullptr));
     timer.stop(stream.get(), err);
     err.ok(hipStreamSynchronize(stream.get()), "feature buffers");
     float ms = 0.0f;
@@ -760,6 +769,10 @@ void Rank::download_features() {
         err.ok(hipMemcpy(img.feature_normal.data(), d_normal, n_pixels * 3 * sizeof(float), hipMemcpyDeviceToHost), "download of the normals");
         err.ok(hipMemcpy(img.feature_depth.data(), d_depth, n_pixels * sizeof(float), hipMemcpyDeviceToHost), "download of the depth");
         err.ok(hipMemcpy(img.feature_coverage.data(), d_coverage, n_pixels * sizeof(float), hipMemcpyDeviceToHost), "download of the coverage");
+        if (want_motion()) {
+            img.feature_motion.resize(n_pixels * 3);
+            err.ok(hipMemcpy(img.feature_motion.data(), d_motion.as<float>(), n_pixels * 3 * sizeof(float), hipMemcpyDeviceToHost), "download of the motion buffer");
+        }
     }
 }
 
@@ -819,6 +832,7 @@ void Rank::temporal() {
     if (factor && !(d_low_a.alloc(n_low * sizeof(float), err, "hipMalloc(low half image)") && d_low_b.alloc(n_low * sizeof(float), err, "hipMalloc(low half image)") &&
                     d_upsample.alloc(upsample_bytes, err, "hipMalloc(upsampling workspace)")))
         return;
+    if (need_features && want_motion() && !d_motion.alloc(n_pixels * 3 * sizeof(float), err, "hipMalloc(motion buffer)")) return;
     float* const d_albedo = d_features.as<float>();
     float *const d_normal = d_albedo + n_pixels * 3, *const d_depth = d_normal + n_pixels * 3, *const d_coverage = d_depth + n_pixels;
     const size_t n_traced = factor ? n_low : n;  // values of a half image at the size that is traced
@@ -842,6 +856,9 @@ void Rank::temporal() {
         }
         // (with a shutter -- the handle's state, Rank::setup -- frame k is exposed from this camera on, over cfg.shutter_travel; the
         // accumulation below reprojects through these opening cameras, as it does without one)
+        // Animation: frame k exposes the spheres from the phase float(k) * step on, one phase for the low render and the full-size
+        // features of the frame (without the flag, or with a step of 0, the handle keeps the phase 0 it was made with)
+        if (animated() && !err.lib_ok(rbrt_hip_scene_set_motion_phase(hs, float(k) * cfg.motion_step))) break;
         rbrt_camera_lens_t traced = lens;  // (the low camera keeps the lens: lens_u, lens_v and focus_scale; the travel is in scene units and stays, too)
         if (factor && !err.lib_ok(rbrt_hip_upsample_camera(&lens.cam, factor, &traced.cam))) break;
         rep.render_width = traced.cam.img_width_pix, rep.render_height = traced.cam.img_height_pix;
@@ -861,7 +878,11 @@ void Rank::temporal() {
                                                d_traced_a, d_traced_b, d_spike_mask.as<uint8_t>(), d_spike_result.as<rbrt_despike_result_t>()));
             spike_timer.stop(stream.get(), err);
         }
-        if (need_features && !err.lib_ok(rbrt_hip_render_features(hs, &lens.cam, &ok, &fo, stream.get(), d_albedo, d_normal, d_depth, d_coverage, nullptr))) break;
+        if (need_features && want_motion()) {
+            if (!err.lib_ok(rbrt_hip_render_features_motion(hs, &lens.cam, &ok, &fo, stream.get(), d_albedo, d_normal, d_depth, d_coverage, nullptr, d_motion.as<float>()))) break;
+        } else if (need_features && !err.lib_ok(rbrt_hip_render_features(hs, &lens.cam, &ok, &fo, stream.get(), d_albedo, d_normal, d_depth, d_coverage, nullptr))) {
+            break;
+        }
         if (factor) {
             up_timer.start(stream.get(), err);
             err.lib_ok(rbrt_hip_upsample_halves(dev, stream.get(), d_low_a.as<float>(), d_low_b.as<float>(), nullptr, d_albedo, d_normal, d_depth, d_coverage,
@@ -871,7 +892,14 @@ void Rank::temporal() {
                 err.lib_ok(rbrt_hip_denoise_halves(dev, stream.get(), d_half_a.as<float>(), d_half_b.as<float>(), d_wa.as<float>(), img.width, img.height,
                                                    &plain_mix, d_rad.as<float>(), d_rgb.as<uint8_t>()));
         }
-        if (cfg.frames) {
+        if (animated()) {  // the history is looked up where the spheres were a step ago
+            timer.start(stream.get(), err);
+            err.lib_ok(rbrt_hip_temporal_accumulate_moving(dev, stream.get(), d_half_a.as<float>(), d_half_b.as<float>(), d_normal, d_depth, d_coverage,
+                                                           d_motion.as<float>(), cfg.motion_step, &lens.cam, k ? &lens_prev.cam : nullptr, &to,
+                                                           k ? d_history[(k - 1u) & 1u].as<void>() : nullptr, d_history[k & 1u].as<void>(), d_half_a.as<float>(),
+                                                           d_half_b.as<float>(), k + 1u == cfg.frames ? d_length.as<float>() : nullptr));
+            timer.stop(stream.get(), err);
+        } else if (cfg.frames) {
             timer.start(stream.get(), err);
             err.lib_ok(rbrt_hip_temporal_accumulate(dev, stream.get(), d_half_a.as<float>(), d_half_b.as<float>(), d_normal, d_depth, d_coverage, &lens.cam,
                                                     k ? &lens_prev.cam : nullptr, &to, k ? d_history[(k - 1u) & 1u].as<void>() : nullptr,
@@ -1041,6 +1069,7 @@ void Rank::release() {
     d_img.reset();
     d_noisy.reset();
     d_features.reset();
+    d_motion.reset();
     if (rank == 0) sh.d_slots.reset();
     stream.reset();
     rbrt_hip_scene_destroy(hs);
@@ -1112,7 +1141,7 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
     if (!cfg.no_motion) job.motion = scene.motion_travels();
     job.want = checkpoint_header(img.width, img.height, num_samples, uint32_t(plan.world), cfg.seed,
                                  checkpoint_fingerprint(cfg.checkpoint_path, lens, job.opts, view.scene, view.shading_ptr(), scene.environment, view.patterns_ptr(),
-                                                        cfg.shutter ? cfg.shutter_travel : nullptr, &job.motion));
+                                                        cfg.shutter ? cfg.shutter_travel : nullptr, &job.motion, cfg.motion_step));
     job.resume = resume_from_checkpoint(job);
     Shared sh(plan);
     bring_up_rccl(plan, sh);

@@ -98,6 +98,7 @@ void write_report(const CliOptions& o, const rbrt::RenderConfig& cfg, const rbrt
                 list += std::string(list.empty() ? "" : ", ") + "{\"sphere\": " + std::to_string(i) + ", \"travel\": [" + JsonLine::text(mv[3 * i], "%.9g") + ", " +
                         JsonLine::text(mv[3 * i + 1], "%.9g") + ", " + JsonLine::text(mv[3 * i + 2], "%.9g") + "]}";
         j.raw("moving_spheres", "[" + list + "]");
+        if (o.motion_step) j.num("motion_step", cfg.motion_step, "%.9g");  // the exposures they advance from one frame to the next
     }
     if (o.upscale) {  // guided upsampling: its options, the size that was traced and the stage's time on the GPU, the mean per frame (a part of render_s)
         j.num("upscale", cfg.upscale, "%.0f"), j.num("render_width", rep.render_width, "%.0f"), j.num("render_height", rep.render_height, "%.0f");

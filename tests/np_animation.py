@@ -20,6 +20,7 @@ import np_features
 import np_motion as NM
 import np_pattern
 import np_reference as R
+import np_smooth
 import np_temporal as NT
 import test_np_reference as T
 from rbrt_amd import abi
@@ -43,6 +44,7 @@ def restated_image(cam, sc, opts, travels, phase, lens=None, shutter=None, nodes
     nc, ns = T.np_cam(cam), np_pattern.np_scene(sc)
     tv = NM.travels_of(travels)
     assert len(tv) == len(ns["spheres"])
+    assert not ns["patterns"] or nodes is None  # (np_env.colorize knows no pattern: np_whole.restated_image does both)
     bg = np.array(list(opts.bg), f32)
     const = bool(opts.flags & abi.FLAG_CONSTANT_BACKGROUND)
     H, W = cam.img_height_pix, cam.img_width_pix
@@ -68,17 +70,34 @@ def primary_rays(cam, seed, n, phase, lens=None, shutter=None, pixels=None):
     return rays, spheres_time(phase, ts)
 
 
-def np_hits(sc, rays, ss, travels, lo, hi):
-    """(obj, dist, g) of primary_rays' rays, each against the scene at its own s: np_reference.scene_hit."""
+def np_hits(sc, rays, ss, travels, lo, hi, points=False):
+    """(obj, dist, g) of primary_rays' rays, each against the scene at its own s: np_smooth.scene_hit (np_reference's, with the
+    shading normal of a smooth mesh, the normal scatter would use). points: also the hit points p = o + t d, (P, n, 3)."""
     ns = np_pattern.np_scene(sc)
     P, n = ss.shape
-    obj, dist, g = np.full((P, n), -1, np.int64), np.zeros((P, n), f32), np.zeros((P, n, 3), f32)
+    obj, dist, g, pts = np.full((P, n), -1, np.int64), np.zeros((P, n), f32), np.zeros((P, n, 3), f32), np.zeros((P, n, 3), f32)
     for p in range(P):
         for s in range(n):
-            hit = R.scene_hit(NM.scene_at(ns, travels, ss[p, s]), rays[p, s, :3], rays[p, s, 3:], f32(lo), f32(hi))
+            hit = np_smooth.scene_hit(NM.scene_at(ns, travels, ss[p, s]), rays[p, s, :3], rays[p, s, 3:], f32(lo), f32(hi))
             if hit is not None:
-                obj[p, s], dist[p, s], g[p, s] = hit["obj"], hit["dist"], hit["normal"]
-    return obj, dist, g
+                obj[p, s], dist[p, s], g[p, s], pts[p, s] = hit["obj"], hit["dist"], hit["normal"], hit["point"]
+    return (obj, dist, g, pts) if points else (obj, dist, g)
+
+
+def cell_albedo(sc, obj, pts, n):
+    """The albedo channel over the first n samples with the cell's colour of a patterned object (np_pattern.hit_albedo at the
+    hit point; include/rbrt_hip.h "Solid patterns": sample by sample): obj (P, >= n), pts (P, >= n, 3) -> float32 (P, 3), sums
+    from 0 in sample order times inv_n, as np_features.from_hits makes them from the table alone."""
+    table = np.vstack([np_features.object_albedos(sc), np.zeros((1, 3), f32)])
+    patterns = getattr(sc, "pattern_of", None)
+    sm = np.zeros((obj.shape[0], 3), f32)
+    for s in range(n):
+        a = np.zeros((obj.shape[0], 3), f32)
+        for p in range(obj.shape[0]):
+            if obj[p, s] >= 0:
+                a[p] = np_pattern.hit_albedo(patterns, obj[p, s], table[obj[p, s]], pts[p, s])
+        sm = sm + a
+    return (sm * (f32(1.0) / f32(n))).astype(f32)
 
 
 def object_travels(sc, travels):
@@ -107,18 +126,24 @@ def motion_from_hits(sc, travels, obj, n):
 
 def features(cam, sc, opts, n, travels, phase=0.0, lens=None, shutter=None, pixels=None):
     """(np_features.Features, motion (H, W, 3)) of a handle with the motion `travels` at `phase`; travels None: a handle without
-    a motion (np_features' own rays, no draw), whose motion buffer is all +0."""
+    a motion (np_features' own rays and no draw -- or, with a shutter, the shutter's rays and its draw; the spheres stay where
+    they are whatever the phase), whose motion buffer is all +0. The albedo of a patterned object is its cell's colour."""
     H, W = cam.img_height_pix, cam.img_width_pix
     pix = np_features.all_pixels(cam) if pixels is None else list(pixels)
     if travels is None:
-        assert shutter is None
-        rays = np_features.primary_rays(cam, opts.seed, n, lens, pix)
+        if shutter is None:
+            rays = np_features.primary_rays(cam, opts.seed, n, lens, pix)
+        else:
+            rays, _ = NM.primary_rays(cam, opts.seed, n, lens=lens, shutter=shutter, pixels=pix)
         ss, tv = np.zeros(rays.shape[:2], f32), np.zeros((len(sc.spheres), 3), f32)
     else:
         rays, ss = primary_rays(cam, opts.seed, n, phase, lens=lens, shutter=shutter, pixels=pix)
         tv = travels
-    obj, dist, g = np_hits(sc, rays, ss, tv, opts.min_dist, opts.max_dist)
-    feat = np_features.scatter_pixels(np_features.from_hits(sc, obj, dist, g, n), pix, H, W)
+    obj, dist, g, pts = np_hits(sc, rays, ss, tv, opts.min_dist, opts.max_dist, points=True)
+    part = np_features.from_hits(sc, obj, dist, g, n)
+    if getattr(sc, "pattern_of", None):
+        part = part._replace(albedo=cell_albedo(sc, obj, pts, n))
+    feat = np_features.scatter_pixels(part, pix, H, W)
     mv = np.zeros((H, W, 3), f32)
     mv[[p[0] for p in pix], [p[1] for p in pix]] = motion_from_hits(sc, travels, obj, n)
     return feat, mv

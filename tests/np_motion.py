@@ -54,6 +54,7 @@ def restated_image(cam, sc, opts, travels, lens=None, shutter=None, nodes=None, 
     nc, ns = T.np_cam(cam), np_pattern.np_scene(sc)
     tv = travels_of(travels)
     assert len(tv) == len(ns["spheres"])
+    assert not ns["patterns"] or nodes is None  # (np_env.colorize knows no pattern: np_whole.restated_image does both)
     bg = np.array(list(opts.bg), f32)
     const = bool(opts.flags & abi.FLAG_CONSTANT_BACKGROUND)
     H, W = cam.img_height_pix, cam.img_width_pix

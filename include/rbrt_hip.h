@@ -59,7 +59,8 @@ extern "C" {
                               rbrt_hip_scene_set_shutter: handle state like the environment, detected by the symbol), nor moving spheres (rbrt_motion_t and
                               rbrt_hip_scene_set_motion: handle state like the shutter, detected by the symbol), nor animation
                               (rbrt_hip_scene_set_motion_phase, rbrt_hip_render_features_motion and
-                              rbrt_hip_temporal_accumulate_moving: added entry points, each detected by its symbol), nor adaptive
+                              rbrt_hip_temporal_accumulate_moving: added entry points, each detected by its symbol), nor moving
+                              meshes (rbrt_mesh_motion_t and rbrt_hip_scene_set_mesh_motion: handle state, detected by the symbol), nor adaptive
                               sampling (rbrt_hip_render_adaptive with its two structs: an added entry point), nor the
                               denoiser (rbrt_denoise_opts_t, rbrt_denoise_opts_default, rbrt_hip_denoise_halves and
                               rbrt_hip_scene_denoise: added entry points), nor environment lighting (rbrt_environment_t and
@@ -624,7 +625,7 @@ int rbrt_hip_scene_set_shutter(rbrt_hip_scene_t* scene, const rbrt_shutter_t* sh
  * the spheres at their opening positions, as they see no shutter. The one-shot rbrt_hip_render* calls cannot carry a motion,
  * for the reason they cannot carry a shutter. There is no flag bit and the ABI version stays 2: a host detects the capability
  * by the symbol. The tile pass widens sphere i's margins by |travel_i| (kernels.hip primary_cull_kernel, "Moving spheres");
- * a scene with a motion never runs the trace kernel's plain build. Not built: moving meshes and BasicTriangles, rotation or
+ * a scene with a motion never runs the trace kernel's plain build. Not built: moving BasicTriangles, rotation or
  * other paths than a straight line, a pattern that travels with its sphere, a time argument for rbrt_hip_trace_rays. (Spheres
  * that advance between the frames of a stream, and their travel as a feature buffer: "Animation", below.) */
 typedef struct rbrt_motion {
@@ -1017,8 +1018,8 @@ int rbrt_hip_scene_set_motion_phase(rbrt_hip_scene_t* scene, float phase);
 
 /* 2. The motion buffer. rbrt_hip_render_features with one more output, d_motion, float[H][W][3], which may be NULL like the
  * others; rbrt_hip_render_features is this call with d_motion NULL, and runs the kernel it has always run. Per sample: a hit
- * of sphere i on a handle with a motion contributes travel_i; a miss, a hit of a mesh or of a BasicTriangle, and any hit on a
- * handle without a motion contribute (+0, +0, +0). Per pixel each of the three sums starts from 0, adds sample 0, 1, ... in
+ * of sphere i on a handle with a motion contributes travel_i; a hit of mesh m on a handle with a mesh motion contributes w_m
+ * ("Moving meshes"); a miss, a hit of a BasicTriangle, and any other hit contribute (+0, +0, +0). Per pixel each of the three sums starts from 0, adds sample 0, 1, ... in
  * that order and is then multiplied by inv_n, like the other channels. The buffer is in scene units per exposure and does not
  * depend on the phase. The ray, the hit and the other five outputs are what rbrt_hip_render_features gives; on a handle with a
  * phase they see the spheres at c_i(s). The refusals are those of rbrt_hip_render_features; with all six outputs NULL nothing
@@ -1039,7 +1040,7 @@ int rbrt_hip_render_features_motion(rbrt_hip_scene_t* scene, const rbrt_camera_t
  * layout, and the histories of the two calls are interchangeable. A translation does not turn a normal, so the normal test
  * compares what it compared; that is why only translations are supported. Limits: only the primary hit is followed. The
  * shadow and the reflection of a moving sphere, and what is seen through glass, lag behind as they do under
- * rbrt_hip_temporal_accumulate; meshes and BasicTriangles do not move. NaN and infinities in d_motion only move xs and ys,
+ * rbrt_hip_temporal_accumulate; BasicTriangles do not move (a mesh's travel enters d_motion: "Moving meshes"). NaN and infinities in d_motion only move xs and ys,
  * which are tested as before: no read leaves the buffers.
  * d_motion NULL gives exactly rbrt_hip_temporal_accumulate -- the same kernel, the same outputs bit for bit -- and phase_step is
  * not read. Everything that call refuses is refused, and with d_motion a phase_step that is not finite (RBRT_ERR_INVALID_ARG).
@@ -1049,6 +1050,53 @@ int rbrt_hip_temporal_accumulate_moving(int device, void* stream, const float* d
                                         const rbrt_camera_t* cam, const rbrt_camera_t* cam_prev, const rbrt_temporal_opts_t* opts,
                                         const void* d_history_in, void* d_history_out, float* d_out_a, float* d_out_b,
                                         float* d_out_length);
+
+/* ---- Moving meshes: a travel per mesh on the shutter's time draw ------------------------------------------------------------------
+ * No counterpart in the reference. A rigid translation needs no moved geometry: a ray (o, d) meets a mesh displaced by v exactly
+ * where the ray (o - v, d) meets the mesh at rest. The trees, the triangle records, the normals and both builders stay
+ * untouched; what changes is which origin the mesh test reads. All arithmetic is float32, unfused, in the written order.
+ *
+ * State. A handle may carry a mesh motion: one vector w_m per mesh of rbrt_scene_t::meshes, in scene units, the mesh's
+ * translation between the opening and the closing of the shutter. The mesh as uploaded is its position at the opening. It is
+ * handle state like rbrt_hip_scene_set_motion: no struct changes, no flag bit, the ABI version stays 2 and a host detects the
+ * capability by the symbol. The sphere motion and the mesh motion are set and cleared independently; each survives the
+ * other's calls, and the phase ("Animation") survives both.
+ *
+ * The draw. A handle with a shutter OR a sphere motion OR a mesh motion makes the one draw t, in the place where it is made
+ * today. The time is s = phase + t, as in "Animation". A handle with a mesh motion and no sphere motion behaves as one whose
+ * sphere motion is all zeros: the existing rule with zero travels describes its spheres.
+ *
+ * The mesh. Wherever a path of that sample tests mesh m, on the camera ray and every bounce, it reads the origin
+ *     o_m,c = o_c - (s * w_m,c)        for c = x, y, z   (a product, then a difference)
+ * and everything mesh.rs does with the ray is done with (o_m, d): the box gate; the culling record of the traversal; the
+ * triangle scan with its tie rule and its t > eps && t < 1e5; p_m = o_m + t * d, dist = length(o_m - p_m) and the distance
+ * window; for a smooth mesh, the barycentrics of the shading normal. In world space, and what they were: the comparison of
+ * dist against the closest hit so far (strict <, spheres first, meshes in order), and the hit point the path continues from,
+ * p = o + t * d with the path's own o -- the expression the scatter pass uses for every object, and the point a solid checker
+ * is evaluated at: the pattern stays in world space and the mesh moves through it. A translation does not turn a normal, so
+ * the stored normals are read as they are.
+ *
+ * While a mesh motion is set, rbrt_hip_render_device, _render_pass, _render_adaptive and rbrt_hip_render_features honour it,
+ * for every tile_rank / tile_world, in helper launches, in the short-path stage and in the tile pass (kernels.hip
+ * primary_cull_kernel, "Moving meshes"). A scene with a mesh motion never runs the trace kernel's plain build; after a clear
+ * a scene that ran it runs it again. rbrt_hip_trace_rays and the ray hooks have no sample stream and see the meshes at rest.
+ * The one-shot rbrt_hip_render* calls cannot carry a mesh motion. In rbrt_hip_render_features_motion a sample that hits mesh m
+ * on a handle with a mesh motion contributes w_m; nothing else changes in that call, so rbrt_hip_temporal_accumulate_moving
+ * follows a moving mesh as it follows a moving sphere.
+ * Not built: moving BasicTriangles, rotation, a pattern that travels with its mesh, a time argument for rbrt_hip_trace_rays. */
+typedef struct rbrt_mesh_motion {
+    uint32_t n_meshes;   /* the scene's mesh count */
+    uint32_t reserved;   /* 0 */
+    const float* travel; /* [n_meshes][3], in the order of rbrt_scene_t::meshes; finite */
+} rbrt_mesh_motion_t;
+
+/* Sets, replaces (motion != NULL) or clears (NULL) the handle's mesh motion. The vectors are copied: the call waits for the
+ * handle's launches in flight and puts them on the device. The threading rule of rbrt_hip_scene_set_motion holds.
+ * RBRT_ERR_INVALID_ARG, before the device is touched, the handle keeping what it had: scene NULL; n_meshes other than the
+ * scene's mesh count; reserved != 0; travel NULL with n_meshes > 0; a component that is not finite; a mesh whose box corner
+ * plus (phase + 1) * travel is not finite in float32. rbrt_hip_scene_set_motion_phase makes the same check of the mesh travels
+ * against the new phase. */
+int rbrt_hip_scene_set_mesh_motion(rbrt_hip_scene_t* scene, const rbrt_mesh_motion_t* motion);
 
 /* ---- Guided upsampling: trace a smaller image, reconstruct the full one from the full-size feature buffers -------------------
  * No counterpart in the reference. The trace kernel's cost is proportional to the pixel count; the feature buffers are cheap.

@@ -112,6 +112,13 @@ pub struct RbrtMotion {                                // rbrt_motion_t: a trave
     pub travel: *const f32,                            // [n_spheres][3], scene units; finite; copied by the call
 }
 
+#[repr(C)]
+pub struct RbrtMeshMotion {                            // rbrt_mesh_motion_t: a travel per mesh while the shutter is open, 16 bytes
+    pub n_meshes: u32,                                 // the scene's mesh count
+    pub reserved: u32,                                 // 0
+    pub travel: *const f32,                            // [n_meshes][3], scene units; finite; copied by the call
+}
+
 #[link(name = "rbrt_hip")]
 extern "C" {
     pub fn rbrt_render_opts_default(opts: *mut RbrtRenderOpts);
@@ -132,6 +139,9 @@ extern "C" {
     // animation: the phase of the handle's motion (a sample with the draw t sees sphere i at center_i + (phase + t) * travel_i),
     // the motion buffer beside the feature buffers, and the accumulation that follows the spheres. Each detected by its symbol
     pub fn rbrt_hip_scene_set_motion_phase(scene: *mut c_void, phase: f32) -> c_int;
+    // moving meshes: a state of the handle beside the spheres' motion, on the same draw and phase (wherever a path tests mesh m it
+    // reads the origin o - (phase + t) * travel_m); motion = null clears it. Detected by the symbol
+    pub fn rbrt_hip_scene_set_mesh_motion(scene: *mut c_void, motion: *const RbrtMeshMotion) -> c_int;
     pub fn rbrt_hip_render_features_motion(scene: *mut c_void, cam: *const RbrtCamera, opts: *const RbrtRenderOpts, fopts: *const c_void,
                                            stream: *mut c_void, d_albedo: *mut f32, d_normal: *mut f32, d_depth: *mut f32,
                                            d_coverage: *mut f32, d_object: *mut i32, d_motion: *mut f32) -> c_int;

@@ -243,6 +243,20 @@ class HipScene:
         mo.travel = None if null_travel else tv.ctypes.data_as(abi.f32p)
         abi.check(self._lib.rbrt_hip_scene_set_motion(self._h, C.byref(mo)))
 
+    def set_mesh_motion(self, travels, *, n_meshes: int | None = None, reserved: int = 0, null_travel: bool = False):
+        """Sets the handle's mesh motion (rbrt_hip_scene_set_mesh_motion): `travels` = (n_meshes, 3), every mesh's translation
+        during the exposure in scene units, in the order of the scene's meshes; None clears it. `n_meshes`, `reserved` and
+        `null_travel` put other values into the struct (tests of the refusals)."""
+        if travels is None:
+            abi.check(self._lib.rbrt_hip_scene_set_mesh_motion(self._h, None))
+            return
+        tv = np.ascontiguousarray(np.asarray(travels, np.float32).reshape(-1, 3))
+        mo = abi.MeshMotion()
+        mo.n_meshes = int(len(tv) if n_meshes is None else n_meshes)
+        mo.reserved = int(reserved)
+        mo.travel = None if null_travel else tv.ctypes.data_as(abi.f32p)
+        abi.check(self._lib.rbrt_hip_scene_set_mesh_motion(self._h, C.byref(mo)))
+
     def set_motion_phase(self, phase: float):
         """Sets the phase of the handle's motion (rbrt_hip_scene_set_motion_phase): a sample with the draw t sees sphere i at
         center_i + (phase + t) * travel_i. 0 by default; it goes with the launches issued after the call."""

@@ -268,6 +268,11 @@ class Motion(C.Structure):  # rbrt_motion_t
     _fields_ = [("n_spheres", C.c_uint32), ("reserved", C.c_uint32), ("travel", f32p)]
 
 
+class MeshMotion(C.Structure):  # rbrt_mesh_motion_t
+    """A travel per mesh between the opening and the closing of the shutter, in scene units: travel = float[n_meshes][3]."""
+    _fields_ = [("n_meshes", C.c_uint32), ("reserved", C.c_uint32), ("travel", f32p)]
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("rays", C.c_uint64),
@@ -349,6 +354,7 @@ HIP_SYMBOLS = {
     "rbrt_hip_scene_set_shutter": (C.c_int, [C.c_void_p, C.POINTER(Shutter)]),
     "rbrt_hip_scene_set_motion": (C.c_int, [C.c_void_p, C.POINTER(Motion)]),
     "rbrt_hip_scene_set_motion_phase": (C.c_int, [C.c_void_p, C.c_float]),
+    "rbrt_hip_scene_set_mesh_motion": (C.c_int, [C.c_void_p, C.POINTER(MeshMotion)]),
     "rbrt_hip_render_features_motion": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderOpts), C.POINTER(FeatureOpts), C.c_void_p,
                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rbrt_hip_temporal_accumulate_moving": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -641,6 +647,10 @@ def load_host() -> C.CDLL:
     lib.rbrt_host_shutter_fingerprint.argtypes = [f32p, C.c_uint64]
     lib.rbrt_host_scene_motion.restype = f32p
     lib.rbrt_host_scene_motion.argtypes = [C.c_void_p]
+    lib.rbrt_host_scene_mesh_motion.restype = f32p
+    lib.rbrt_host_scene_mesh_motion.argtypes = [C.c_void_p]
+    lib.rbrt_host_mesh_motion_fingerprint.restype = C.c_uint64
+    lib.rbrt_host_mesh_motion_fingerprint.argtypes = [f32p, C.c_uint32, C.c_uint64]
     lib.rbrt_host_motion_fingerprint.restype = C.c_uint64
     lib.rbrt_host_motion_fingerprint.argtypes = [f32p, C.c_uint32, C.c_uint64]
     lib.rbrt_host_scene_scene.restype = C.POINTER(Scene)
@@ -716,6 +726,9 @@ class HostScene:
         # the spheres' shutter_travel keys as float32 (n_spheres, 3) (what HipScene.set_motion takes), else None
         mp = self._lib.rbrt_host_scene_motion(self._h)
         self.motion = np.ctypeslib.as_array(mp, shape=(self.struct.n_spheres, 3)).astype(np.float32).copy() if mp else None
+        # the meshes' shutter_travel keys as float32 (n_meshes, 3) (what HipScene.set_mesh_motion takes), else None
+        mm = self._lib.rbrt_host_scene_mesh_motion(self._h)
+        self.mesh_motion = np.ctypeslib.as_array(mm, shape=(self.struct.n_meshes, 3)).astype(np.float32).copy() if mm else None
         sp = self._lib.rbrt_host_scene_shading(self._h)  # NULL unless some mesh is smooth
         self.shading = sp.contents if sp else None
         pp = self._lib.rbrt_host_scene_patterns(self._h)  # NULL unless some object carries a checker
@@ -824,6 +837,15 @@ def motion_fingerprint(travels, h: int) -> int:
         return int(lib.rbrt_host_motion_fingerprint(None, 0, h))
     tv = np.ascontiguousarray(np.asarray(travels, np.float32).reshape(-1, 3))
     return int(lib.rbrt_host_motion_fingerprint(tv.ctypes.data_as(f32p), len(tv), h))
+
+
+def mesh_motion_fingerprint(travels, h: int) -> int:
+    """What a mesh motion adds to the checkpoint fingerprint `h` (rbrt_host_mesh_motion_fingerprint); travels None: none."""
+    lib = load_host()
+    if travels is None:
+        return int(lib.rbrt_host_mesh_motion_fingerprint(None, 0, h))
+    tv = np.ascontiguousarray(np.asarray(travels, np.float32).reshape(-1, 3))
+    return int(lib.rbrt_host_mesh_motion_fingerprint(tv.ctypes.data_as(f32p), len(tv), h))
 
 
 def save_image(path, rgb8: np.ndarray) -> None:

@@ -34,7 +34,7 @@ size_t megakernel_gseq_bytes(uint32_t n_waves);
 size_t megakernel_gstack_bytes(uint32_t n_waves);
 size_t megakernel_gtime_bytes(uint32_t n_waves);
 size_t megakernel_lds_bytes(uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris, uint32_t thin_lens,
-                            uint32_t environment, uint32_t pattern_dw, uint32_t shutter, uint32_t motion);
+                            uint32_t environment, uint32_t pattern_dw, uint32_t shutter, uint32_t motion, uint32_t mesh_motion);
 int megakernel_occupancy_per_cu(size_t lds_bytes);
 hipError_t launch_primary_cull(const TraceParams& P, hipStream_t stream);
 hipError_t launch_sky_resolve(const TraceParams& P, const ResolveParams& R, hipStream_t stream);
@@ -260,6 +260,17 @@ struct rbrt_hip_scene {
     // while a motion is set; h_motion: the travels' host copy in the device array's order, for the check of the sweep's end.
     float motion_phase = 0.0f;
     std::vector<float> h_motion;
+    // The mesh motion (rbrt_hip_scene_set_mesh_motion; rbrt_hip.h "Moving meshes"): a travel per mesh, [n_meshes][3] in the order
+    // of rbrt_scene_t::meshes, allocated at the first call and kept; has_mesh_motion false: never read. mesh_motion_gen numbers
+    // the calls (TileKey), h_mesh_motion is the host copy and h_mesh_boxes the meshes' boxes (lo, hi) for the check of the
+    // sweep's end. d_zero_motion: [n_spheres][3] zeros, the sphere travels of a launch with a mesh motion on a handle without a
+    // sphere motion ("behaves as one whose sphere motion is all zeros").
+    bool has_mesh_motion = false;
+    float* d_mesh_motion = nullptr;
+    float* d_zero_motion = nullptr;
+    uint32_t mesh_motion_gen = 0;
+    std::vector<float> h_mesh_motion;
+    std::vector<float> h_mesh_boxes;
     // workspace, grown on demand
     // Frame pipeline: consecutive trace launches (the batches of one render, or successive renders) alternate
     // over `pipeline` lanes. Every lane has its own sample buffer, work counters and per-wave scratch, and --
@@ -305,6 +316,7 @@ struct rbrt_hip_scene {
             float travel[3];
             uint32_t motion_gen;  // the handle's motion when the tables were made, by the number of the call that set it (0 without one)
             float motion_phase;   // ... and its phase (0 without a motion): the margins are made around the advanced centres
+            uint32_t mesh_motion_gen;  // the handle's mesh motion, by the number of the call that set it (0 without one)
         };
         struct TileSet {
             uint32_t* d_cull = nullptr;    // [n_tiles]
@@ -968,6 +980,10 @@ int fill_trace_params(const rbrt_hip_scene* s, const rbrt_camera_t* cam, const r
         for (int c = 0; c < 3; ++c) P.travel[c] = s->travel[c];
     }
     if (cam && s->has_motion) P.motion = s->d_motion, P.motion_gen = s->motion_gen, P.motion_phase = s->motion_phase;  // (the same: the ray hooks see the spheres at the opening)
+    if (cam && s->has_mesh_motion) {  // (the same again: the ray hooks see the meshes at rest)
+        P.mesh_motion = s->d_mesh_motion, P.mesh_motion_gen = s->mesh_motion_gen, P.motion_phase = s->motion_phase;
+        if (!s->has_motion) P.motion = s->d_zero_motion, P.motion_gen = 0u;  // a sphere motion of all zeros
+    }
     P.n_spheres = s->n_spheres;
     P.n_meshes = s->n_meshes;
     P.n_elem_tris = s->n_elem_tris;
@@ -1454,6 +1470,9 @@ int upload_scene_tables(rbrt_hip_scene* s, const ElementTables& t, const std::ve
         s->d_materials = reinterpret_cast<DevMaterial*>(d_words);
     }
     if (int rc = upload(s, meshes, &s->d_meshes)) return rc;
+    s->h_mesh_boxes.resize(meshes.size() * 6u);
+    for (size_t m = 0; m < meshes.size(); ++m)
+        for (int c = 0; c < 3; ++c) s->h_mesh_boxes[6u * m + c] = meshes[m].bbox_lo[c], s->h_mesh_boxes[6u * m + 3u + c] = meshes[m].bbox_hi[c];
     return upload(s, std::vector<DevCounters>(1), &s->d_counters);  // (value-initialised: all zero)
 }
 
@@ -1499,7 +1518,7 @@ int size_grid(rbrt_hip_scene* s, int device, uint32_t waves_per_cu) {
     if (s->stack_entries > s->stack_need) s->stack_entries = s->stack_need;
     // resident waves per CU: LDS-limited (160 KiB per CU), at most 5 per SIMD (VGPR budget). (A thin-lens launch stages 32
     // bytes more; where that costs it a wave per CU the waves of the grid beyond the resident ones start as others end.)
-    int per_cu = int((160u * 1024u) / megakernel_lds_bytes(s->stack_entries, s->n_spheres, s->n_meshes, s->n_elem_tris, 0u, 0u, pattern_table_dwords(s->n_patterns), 0u, 0u));
+    int per_cu = int((160u * 1024u) / megakernel_lds_bytes(s->stack_entries, s->n_spheres, s->n_meshes, s->n_elem_tris, 0u, 0u, pattern_table_dwords(s->n_patterns), 0u, 0u, 0u));
     if (per_cu > 20) per_cu = 20;
     if (per_cu < 1) per_cu = 1;
     if (waves_per_cu != 0) per_cu = int(waves_per_cu), s->waves_fixed = true;
@@ -1900,6 +1919,7 @@ rbrt_hip_scene::Lane::TileKey tile_key(const TraceParams& P, uint32_t list_mode)
     for (int c = 0; c < 3; ++c) k.travel[c] = P.travel[c];
     k.motion_gen = P.motion ? P.motion_gen : 0u;
     k.motion_phase = P.motion ? P.motion_phase : 0.0f;
+    k.mesh_motion_gen = P.mesh_motion ? P.mesh_motion_gen : 0u;
     return k;
 }
 
@@ -2590,6 +2610,58 @@ int rbrt_hip_scene_set_motion(rbrt_hip_scene_t* s, const rbrt_motion_t* motion) 
     return RBRT_OK;
 }
 
+// Mesh m's box corners at the end of its sweep at `phase`, corner + ((phase + 1) * travel) in float32: all finite? (A mesh
+// without triangles has an infinite box: it has nothing to sweep.) `tv`: the mesh's travel.
+static bool mesh_sweep_end_finite(const rbrt_hip_scene* s, uint32_t m, const float* tv, float phase) {
+    for (int k = 0; k < 6; ++k) {
+        const float corner = s->h_mesh_boxes[6u * m + uint32_t(k)];
+        if (!std::isfinite(corner)) continue;
+        if (!sweep_end_finite(corner, tv[k % 3], phase)) return false;
+    }
+    return true;
+}
+
+// The handle's mesh motion (rbrt_hip.h "Moving meshes"): rbrt_hip_scene_set_motion's twin, with a state of its own.
+int rbrt_hip_scene_set_mesh_motion(rbrt_hip_scene_t* s, const rbrt_mesh_motion_t* motion) {
+    if (!s) return fail(RBRT_ERR_INVALID_ARG, "set_mesh_motion: null scene");
+    std::vector<float> dev;
+    if (motion) {
+        if (motion->n_meshes != s->n_meshes) return fail(RBRT_ERR_INVALID_ARG, "set_mesh_motion: n_meshes differs from the scene's mesh count");
+        if (motion->reserved != 0u) return fail(RBRT_ERR_INVALID_ARG, "set_mesh_motion: reserved must be 0");
+        if (motion->n_meshes != 0u && !motion->travel) return fail(RBRT_ERR_INVALID_ARG, "set_mesh_motion: null travel");
+        dev.assign(motion->travel, motion->travel + size_t(s->n_meshes) * 3u);
+        for (uint32_t m = 0; m < s->n_meshes; ++m) {
+            for (int c = 0; c < 3; ++c)
+                if (!std::isfinite(dev[3u * m + c])) return fail(RBRT_ERR_INVALID_ARG, "set_mesh_motion: mesh " + std::to_string(m) + " has a travel that is not finite");
+            if (!mesh_sweep_end_finite(s, m, dev.data() + 3u * m, s->motion_phase))
+                return fail(RBRT_ERR_INVALID_ARG, "set_mesh_motion: mesh " + std::to_string(m) + ": box + (phase + 1) * travel is not finite");
+        }
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    std::lock_guard<std::mutex> watcher_lock(s->mu);
+    if (motion) {
+        HIP_TRY(hipDeviceSynchronize());
+        if (!s->d_mesh_motion) {
+            void* p = nullptr;
+            HIP_TRY(dev_alloc(s, std::max<size_t>(dev.size() * sizeof(float), 16), &p));
+            s->d_mesh_motion = static_cast<float*>(p);
+        }
+        if (!s->d_zero_motion) {
+            void* p = nullptr;
+            const size_t bytes = std::max<size_t>(size_t(s->n_spheres) * 3u * sizeof(float), 16);
+            HIP_TRY(dev_alloc(s, bytes, &p));
+            HIP_TRY(hipMemset(p, 0, bytes));
+            s->d_zero_motion = static_cast<float*>(p);
+        }
+        if (!dev.empty()) HIP_TRY(hipMemcpy(s->d_mesh_motion, dev.data(), dev.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    s->has_mesh_motion = motion != nullptr;
+    s->h_mesh_motion = std::move(dev);
+    s->mesh_motion_gen += 1u;
+    if (s->mesh_motion_gen == 0u) s->mesh_motion_gen = 1u;
+    return RBRT_OK;
+}
+
 // The motion's phase (rbrt_hip.h "Animation"): a word of the handle that fill_trace_params copies into the parameters of every
 // launch issued from now on. A launch in flight has its own copy (kernel arguments; a helper launch copies those of the launch
 // it joins), so nothing waits and the device is not touched.
@@ -2601,6 +2673,10 @@ int rbrt_hip_scene_set_motion_phase(rbrt_hip_scene_t* s, float phase) {
             for (int c = 0; c < 3; ++c)
                 if (!sweep_end_finite(s->h_spheres[i].center[c], s->h_motion[3u * i + c], phase))
                     return fail(RBRT_ERR_INVALID_ARG, "set_motion_phase: sphere " + std::to_string(s->sphere_src[i]) + ": center + (phase + 1) * travel is not finite");
+    if (s->has_mesh_motion)
+        for (uint32_t m = 0; m < s->n_meshes; ++m)
+            if (!mesh_sweep_end_finite(s, m, s->h_mesh_motion.data() + 3u * m, phase))
+                return fail(RBRT_ERR_INVALID_ARG, "set_motion_phase: mesh " + std::to_string(m) + ": box + (phase + 1) * travel is not finite");
     std::lock_guard<std::mutex> watcher_lock(s->mu);  // (a helper launch copies the parameters of the launch it joins)
     s->motion_phase = phase;
     return RBRT_OK;
@@ -2690,7 +2766,7 @@ int rbrt_hip_scene_info(rbrt_hip_scene_t* s, rbrt_hip_scene_info_t* out) {
     out->bvh_stack_need = s->stack_need;
     out->n_nodes = s->total_nodes, out->n_triangles = s->total_tris;
     out->trace_waves = s->n_waves;
-    out->lds_bytes_per_wave = uint32_t(megakernel_lds_bytes(s->stack_entries, s->n_spheres, s->n_meshes, s->n_elem_tris, 0u, 0u, pattern_table_dwords(s->n_patterns), 0u, 0u));
+    out->lds_bytes_per_wave = uint32_t(megakernel_lds_bytes(s->stack_entries, s->n_spheres, s->n_meshes, s->n_elem_tris, 0u, 0u, pattern_table_dwords(s->n_patterns), 0u, 0u, 0u));
     (void)hipSetDevice(s->device);
     out->occupancy_api_waves_per_cu = uint32_t(megakernel_occupancy_per_cu(out->lds_bytes_per_wave));
     out->n_cus = s->n_cus;

@@ -242,6 +242,11 @@ struct TraceParams {
     unsigned long long* short_masks;
     // Solid patterns: the dwords behind the n_obj materials that belong to the table (pattern_table_dwords; 0: no patterns)
     uint32_t pattern_dw;
+    // The handle's mesh motion (rbrt_hip_scene_set_mesh_motion): mesh_motion = [n_meshes][3], mesh m's translation during the
+    // exposure, on the device; null (no mesh motion): never read. A launch with one always has `motion` too (the handle's, or
+    // all zeros) and with it gtime and the phase: wherever a path tests mesh m it reads the origin o - (s * w_m), s = phase + t
+    const float* mesh_motion;
+    uint32_t mesh_motion_gen;  // host only: the number of the rbrt_hip_scene_set_mesh_motion call (the tile-table key)
 };
 
 struct ResolveParams {

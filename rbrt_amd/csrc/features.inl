@@ -11,10 +11,12 @@
 //
 // Two builds: features_kernel<false> is what rbrt_hip_render_features has always launched; features_kernel<true> also sums
 // the travel of the sphere each sample hits (rbrt_hip_render_features_motion with d_motion; include/rbrt_hip.h "Animation").
+// Each exists a second time for a handle with a mesh motion (MM; "Moving meshes"): the mesh loop of scene_hit and the shading
+// normal read the per-mesh origin, and a mesh hit adds the mesh's travel. A handle without one launches the builds it always has.
 
 constexpr int kFeatureBlock = 64;
 
-template <bool MOTION>
+template <bool MOTION, bool MM = false>
 __global__ __launch_bounds__(kFeatureBlock) void features_kernel(const TraceParams P, const FeatureParams F) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     uint32_t* stack = lds + threadIdx.x;
@@ -45,7 +47,7 @@ __global__ __launch_bounds__(kFeatureBlock) void features_kernel(const TracePara
         if (P.motion) mt = P.motion_phase + mt;  // "Animation": s = phase + t, the spheres' time; the shutter kept the raw t
         HitRec h;
         LocalCounters lc = {0, 0, 0, 0, 0};
-        scene_hit<false>(P, o, d, stack, uint32_t(kFeatureBlock), h, lc, P.motion, mt);
+        scene_hit<false, MM>(P, o, d, stack, uint32_t(kFeatureBlock), h, lc, P.motion, mt, P.mesh_motion);
         if (s == 0) first_obj = h.obj;
         V3 sa = mk(0.0f, 0.0f, 0.0f), sn = mk(0.0f, 0.0f, 0.0f);  // a miss: every channel adds +0
         float sz = 0.0f, sc = 0.0f;
@@ -67,7 +69,9 @@ __global__ __launch_bounds__(kFeatureBlock) void features_kernel(const TracePara
                     if (MOTION && P.motion) sm = mk(P.motion + desc * kMotionDw);
                 }
             } else {
-                g = mesh_shading_normal(P.meshes[uint32_t(h.obj) - n_elem].normals, h.tri, o, d);
+                const uint32_t hm = uint32_t(h.obj) - n_elem;
+                g = mesh_shading_normal(P.meshes[hm].normals, h.tri, MM ? mesh_origin_at(o, P.mesh_motion + hm * kMeshMotionDw, mt) : o, d);
+                if (MOTION && MM) sm = mk(P.mesh_motion + hm * kMeshMotionDw);
             }
             sn = normalize(g);  // not flipped towards the ray, no guard
             sz = h.dist;
@@ -104,7 +108,9 @@ __global__ __launch_bounds__(kFeatureBlock) void features_kernel(const TracePara
 hipError_t launch_features(const TraceParams& P, const FeatureParams& F, hipStream_t stream) {
     if (P.n_tiles == 0) return hipSuccess;
     const size_t lds = size_t(F.stack_entries) * kFeatureBlock * sizeof(uint32_t);  // (a multiple of 256 bytes: the base stays 16-byte aligned)
-    if (F.motion) hipLaunchKernelGGL(features_kernel<true>, dim3(P.n_tiles), dim3(kFeatureBlock), lds, stream, P, F);
+    if (P.mesh_motion && F.motion) hipLaunchKernelGGL((features_kernel<true, true>), dim3(P.n_tiles), dim3(kFeatureBlock), lds, stream, P, F);
+    else if (P.mesh_motion) hipLaunchKernelGGL((features_kernel<false, true>), dim3(P.n_tiles), dim3(kFeatureBlock), lds, stream, P, F);
+    else if (F.motion) hipLaunchKernelGGL(features_kernel<true>, dim3(P.n_tiles), dim3(kFeatureBlock), lds, stream, P, F);
     else hipLaunchKernelGGL(features_kernel<false>, dim3(P.n_tiles), dim3(kFeatureBlock), lds, stream, P, F);
     return hipGetLastError();
 }

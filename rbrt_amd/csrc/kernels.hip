@@ -520,10 +520,15 @@ struct HitRec {
 
 // scene.rs:19-43: spheres in order, then meshes in order, strictly smaller distance wins.
 // motion: null, or the spheres' travels [n_spheres][3] with the path's draw mt (sphere_centre_at, below).
+// mesh_motion (MM builds only): the meshes' travels [n_meshes][3]; mesh m is tested with the origin mesh_origin_at(o, w_m, mt)
+// in everything mesh.rs does with the ray, and its dist competes with the world-space distances of the others.
 __device__ __forceinline__ V3 sphere_centre_at(const float* centre, const float* travel, float t);
-template <bool STATS>
-__device__ __forceinline__ void scene_hit(const TraceParams& P, V3 o, V3 d, uint32_t* stack, uint32_t stride,
-                                          HitRec& h, LocalCounters& lc, const float* motion = nullptr, float mt = 0.0f) {
+__device__ __forceinline__ V3 mesh_origin_at(V3 o, const float* travel, float s);
+template <bool STATS, bool MM = false>
+__device__ __forceinline__ void scene_hit(const TraceParams& P, V3 o_world, V3 d, uint32_t* stack, uint32_t stride,
+                                          HitRec& h, LocalCounters& lc, const float* motion = nullptr, float mt = 0.0f,
+                                          const float* mesh_motion = nullptr) {
+    const V3 o = o_world;
     float closest = 3.40282347e+38f;  // f32::MAX
     h.obj = -1;
     h.t = 0.0f;
@@ -549,6 +554,7 @@ __device__ __forceinline__ void scene_hit(const TraceParams& P, V3 o, V3 d, uint
     }
     for (uint32_t m = 0; m < P.n_meshes; ++m) {
         const DevMesh& M = P.meshes[m];
+        const V3 o = MM ? mesh_origin_at(o_world, mesh_motion + m * 3u, mt) : o_world;  // (shadows the world origin: "Moving meshes")
         if (!bbox_gate(M.bbox_lo, M.bbox_hi, o, d)) continue;  // mesh.rs:233-235
         if (STATS) ++lc.gate;
         float t;
@@ -782,6 +788,11 @@ constexpr uint32_t kShutterDw = 4;  // words staged in the megakernel's LDS for 
 // path and the normal p - c(t). The radius, the materials and everything that is not a sphere stay where they are.
 __device__ __forceinline__ V3 sphere_centre_at(const float* centre, const float* travel, float t) { return mk(centre) + t * mk(travel); }
 constexpr uint32_t kMotionDw = 3;  // words per sphere staged in the megakernel's LDS for a motion launch: its travel
+// Moving meshes (rbrt_hip.h "Moving meshes"): a ray (o, d) meets a mesh displaced by v where the ray
+// (o - v, d) meets the mesh at rest, so wherever a path tests mesh m it reads the origin o_m = o - (s * w_m), s = phase + t the
+// sample's time: unfused, a product and a difference per component. The trees, the triangles and the normals stay untouched.
+__device__ __forceinline__ V3 mesh_origin_at(V3 o, const float* travel, float s) { return o - s * mk(travel); }
+constexpr uint32_t kMeshMotionDw = 3;  // words per mesh staged behind the spheres' travels and the phase in a launch with a mesh motion
 
 // lib.rs:68-71: what a ray that hits nothing sees; the direction as it is (not re-normalised).
 // `constant` (RBRT_FLAG_CONSTANT_BACKGROUND): bg itself.
@@ -822,7 +833,7 @@ constexpr uint32_t kEnvDw = 4;  // words staged in the megakernel's LDS for a la
 
 __host__ __device__ inline uint32_t megakernel_lds_dwords(uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris,
                                                           uint32_t thin_lens, uint32_t environment, uint32_t pattern_dw, uint32_t shutter,
-                                                          uint32_t motion);
+                                                          uint32_t motion, uint32_t mesh_motion);
 #include "megakernel.inl"
 
 // lib.rs:116-122: (sqrt(c) * 256) as u8 — Rust's float->int cast saturates and maps NaN to 0.
@@ -1091,6 +1102,27 @@ __global__ __launch_bounds__(kSmallBlock) void sky_resolve_kernel(const TracePar
 // qhat are taken from it (in that order, so that the centre's registers are free before the product is made). With
 // ph = 0, C_i = c_i exactly and the margin is the one above: every word is what it was without a phase, bit for bit. The
 // margin grows with |ph| only through the rounding term, 1e-6 (|ph| + 1) |travel_i|.
+//
+// Moving meshes (rbrt_hip.h "Moving meshes"; TraceParams::mesh_motion, w = w_m, ph the phase). The camera ray (o', d) of a sample
+// with the draw t tests mesh m -- its box gate, and through make_cull the grown boxes of its tree -- as the ray (o_m, d),
+// o_m = fl(o' - fl(s w)), s = fl(ph + t), 0 <= t < 1: the mesh, its box and its tree at rest, the direction bit for bit. So
+// bit 24 + m and the descent ask the questions above of a ray that starts somewhere else, and, as for a sphere, the bound
+// follows the object: mesh m gets its own position, advanced in double,
+//     pos_m = position - ph w          (the product of two floats is exact in double; the difference rounds at 2^-53)
+// and its own bound on where a ray starts relative to it. What is left between pos_m and o_m:
+//     o' - position                                                 at most org_a long (lens and shutter, above)
+//     s = ph + t + e_s, |e_s| <= u (|ph| + 1)                      so s w - ph w = (t + e_s) w: at most |w| + u (|ph| + 1) |w|
+//     fl(s w): one rounding per component                           at most u |s| |w| <= u (1 + u) (|ph| + 1) |w|
+//     fl(o' - ...): one rounding per component                      at most u (|position| + org_a + (1 + 2u) (|ph| + 1) |w|)
+// together |o_m - pos_m| <= org_a + |w| + 3 u (|position| + org_a + (|ph| + 1) |w|) + O(u^2): the candidate
+//     org_a_m = org_a + |w| + 16 u (|position| + org_a + (|ph| + 1) |w|)
+// covers the float error five times over, pos_m's own rounding included. pos_m and org_a_m take the place of pos and org_a
+// wherever they stand for mesh m: the corners' distances (`far`, the finiteness test), the box slack 16 u (far + org_a_m),
+// box_unreachable's centre, bounding sphere, `reach` and corner vectors, and the tree pad's dlen(mc), |o|_inf (of pos_m, plus
+// org_a_m) and org_a. The slabs' planes pass through pos_m with the normals they had and the cone keeps its axis and angles:
+// those are made of DIRECTIONS, and d is the unmoved ray's. The time the bound never uses is the one draw the shutter and
+// the spheres share: it holds for every t. Without a mesh motion pos_m = pos and org_a_m = org_a exactly (the branch is not
+// taken) and every word of the table is what it was. The bit proves the CAMERA ray's test fails; a bounce ray tests every mesh.
 // ---------------------------------------------------------------------------------------------
 struct D3 {
     double x, y, z;
@@ -1153,6 +1185,8 @@ constexpr int kCullBlock = 64;       // one wave per workgroup: the launch sprea
 constexpr uint32_t kCullLanes = 4;   // lanes per tile
 // (at most 128 VGPRs, like a trace wave: a wave of this kernel then fits the slot ONE exiting trace wave leaves on its SIMD;
 // at 140 it needed two of them to have left)
+// (MM: the build for a launch with a mesh motion, "Moving meshes"; every other launch runs the code it always has)
+template <bool MM>
 __global__ __launch_bounds__(kCullBlock, 4) void primary_cull_kernel(const TraceParams P) {
     // (a rank of a multi-GPU render makes the words of ITS tiles only -- tile = local * world + rank, the only words its
     // lists and its launch read: an eighth of the pass for an eighth of the frame)
@@ -1263,7 +1297,8 @@ __global__ __launch_bounds__(kCullBlock, 4) void primary_cull_kernel(const Trace
         else all = false;
     }
     // can a forward camera ray of the tile enter this box? (bounding sphere against the cone; corners against the slabs)
-    const auto box_unreachable = [&](D3 lo, D3 hi, double slack, double far) -> bool {
+    // (pos, org_a: the camera's, or mesh m's own in a launch with a mesh motion -- header, "Moving meshes")
+    const auto box_unreachable = [&](D3 lo, D3 hi, double slack, double far, D3 pos, double org_a) -> bool {
         const D3 q = 0.5 * (lo + hi) - pos;
         const double l = dlen(q);
         if (cone.misses((1.0 / l) * q, l, 0.5 * dlen(hi - lo) * 1.001 + slack + org_a, 1.0)) return true;
@@ -1283,6 +1318,15 @@ __global__ __launch_bounds__(kCullBlock, 4) void primary_cull_kernel(const Trace
     };
     for (uint32_t m = 0; m < P.n_meshes && m < 7u; ++m) {
         const DevMesh& md = P.meshes[m];
+        // Moving meshes (header): this mesh's own position and origin bound. Without a mesh motion they are the camera's.
+        D3 pos = d3(c.position);
+        double org_a = org_all;
+        if (MM) {
+            const D3 tv = d3(P.mesh_motion + m * kMeshMotionDw);
+            const double ph = double(P.motion_phase), tl = dlen(tv);
+            org_a = org_all + tl + 16.0 * (1.0 / 16777216.0) * (dlen(pos) + org_all + (fabs(ph) + 1.0) * tl);
+            pos = pos - ph * tv;
+        }
         double far = 0.0;
         bool finite = true;
         for (uint32_t k = 0; k < 8u; ++k) {
@@ -1302,7 +1346,7 @@ __global__ __launch_bounds__(kCullBlock, 4) void primary_cull_kernel(const Trace
         // geometry.) The slack is 16 u far, three times that bound; the angle between the float ray and the exact
         // line of its pixel is added on top by box_unreachable (angle * far). Round 3 had a chosen 1e-4 far here.
         const double slack = 16.0 * (1.0 / 16777216.0) * (far + org_a);
-        const bool out = finite && box_unreachable(d3(md.bbox_lo), d3(md.bbox_hi), slack, far);
+        const bool out = finite && box_unreachable(d3(md.bbox_lo), d3(md.bbox_hi), slack, far, pos, org_a);
         if (out) word |= 1u << (24u + m);
         // A ray may pass the mesh's box and still have no triangle to hit: the tile is free of the mesh as well when
         // every box in the top kCullLevels levels of its tree is out of the tile's reach. Depth first, descending only where
@@ -1335,7 +1379,7 @@ __global__ __launch_bounds__(kCullBlock, 4) void primary_cull_kernel(const Trace
                     const D3 lo = D3{double(nd.lo_x[c]), double(nd.lo_y[c]), double(nd.lo_z[c])};
                     const D3 hi = D3{double(nd.hi_x[c]), double(nd.hi_y[c]), double(nd.hi_z[c])};
                     if (!(dlen(lo - pos) < 1e30 && dlen(hi - pos) < 1e30)) state = 2u;
-                    else if (!box_unreachable(lo, hi, pad_base * (double(nd.max_e12[c]) * 1.001 * double(P.eps_frac) + 1.0), far))
+                    else if (!box_unreachable(lo, hi, pad_base * (double(nd.max_e12[c]) * 1.001 * double(P.eps_frac) + 1.0), far, pos, org_a))
                         state = (link >= 0 && (e & 7u) + 1u < kCullLevels) ? 1u : 2u;
                 }
                 const uint32_t open = uint32_t(__builtin_amdgcn_ballot_w64(state == 1u) >> quad_shift) & 15u;
@@ -1919,7 +1963,7 @@ size_t megakernel_gtime_bytes(uint32_t n_waves) { return size_t(n_waves) * kPool
 
 __host__ __device__ inline uint32_t megakernel_lds_dwords(uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris,
                                                           uint32_t thin_lens, uint32_t environment, uint32_t pattern_dw, uint32_t shutter,
-                                                          uint32_t motion) {
+                                                          uint32_t motion, uint32_t mesh_motion) {
     const uint32_t n_elem = n_spheres + n_elem_tris;
     const uint32_t scene = n_spheres * kSphDw + (n_elem + n_meshes) * kMatDw + n_meshes * kMeshDw + kGenDw +
                            pattern_dw +                                                // second entries and DevPatterns (nothing without patterns)
@@ -1927,6 +1971,7 @@ __host__ __device__ inline uint32_t megakernel_lds_dwords(uint32_t stack_entries
                            (environment ? kEnvDw : 0u) +                               // the map's address and size (nothing without one)
                            (shutter ? kShutterDw : 0u) +                               // a shutter launch's travel (nothing without a shutter)
                            (motion ? n_spheres * kMotionDw + 1u : 0u) +                // a motion launch's travels and phase (nothing without a motion)
+                           (mesh_motion ? n_meshes * kMeshMotionDw : 0u) +             // the meshes' travels (nothing without a mesh motion)
                            (n_elem_tris != 0u ? n_elem_tris * kTriDw + n_elem : 0u);  // triangle table + element order
     const uint32_t pool_pad = (uint32_t(kPool) + 63u) & ~63u;  // status + list: one byte per (padded) slot each
     uint32_t dw = uint32_t(kFields * kPool) + kCellDw + kTqDw + kHelpDw + pool_pad / 2u + stack_entries * 64u + scene;
@@ -1934,8 +1979,8 @@ __host__ __device__ inline uint32_t megakernel_lds_dwords(uint32_t stack_entries
     return dw;
 }
 size_t megakernel_lds_bytes(uint32_t stack_entries, uint32_t n_spheres, uint32_t n_meshes, uint32_t n_elem_tris, uint32_t thin_lens,
-                            uint32_t environment, uint32_t pattern_dw, uint32_t shutter, uint32_t motion) {
-    return size_t(megakernel_lds_dwords(stack_entries, n_spheres, n_meshes, n_elem_tris, thin_lens, environment, pattern_dw, shutter, motion)) * sizeof(uint32_t);
+                            uint32_t environment, uint32_t pattern_dw, uint32_t shutter, uint32_t motion, uint32_t mesh_motion) {
+    return size_t(megakernel_lds_dwords(stack_entries, n_spheres, n_meshes, n_elem_tris, thin_lens, environment, pattern_dw, shutter, motion, mesh_motion)) * sizeof(uint32_t);
 }
 
 // What the HIP runtime says fits: resident single-wave workgroups of the trace kernel per CU at this much LDS (0 on error).
@@ -1948,7 +1993,7 @@ int megakernel_occupancy_per_cu(size_t lds_bytes) {
 // Does the launch qualify for the PLAIN build of the trace kernel (megakernel.inl TraceView)? Every constant that build has
 // in place of a parameter is compared with the parameter here, and nowhere else.
 bool trace_params_are_plain(const TraceParams& P) {
-    return P.n_meshes == 1u && P.n_elem_tris == 0u && P.thin_lens == 0u && P.shutter == 0u && P.motion == nullptr && P.env_nodes == nullptr && P.pattern_dw == 0u &&
+    return P.n_meshes == 1u && P.n_elem_tris == 0u && P.thin_lens == 0u && P.shutter == 0u && P.motion == nullptr && P.mesh_motion == nullptr && P.env_nodes == nullptr && P.pattern_dw == 0u &&
            P.y_low_water == kDefaultKnobs.y_low_water && P.y_high_water == kDefaultKnobs.y_high_water &&
            P.y_high_min_parked == kDefaultKnobs.y_high_min_parked && P.leaf_round == kDefaultKnobs.leaf_round &&
            P.leaf_leaves == kDefaultKnobs.leaf_leaves && P.share_idle == kDefaultKnobs.share_idle &&
@@ -1961,8 +2006,10 @@ bool trace_params_are_plain(const TraceParams& P) {
 // (work counters, sample buffer, tables), scratch slots from P.wave_base on.
 hipError_t launch_trace_helper(const TraceParams& P, uint32_t n_waves, bool plain, hipStream_t stream) {
     if (P.n_items == 0 || n_waves == 0 || !P.helper_words) return hipSuccess;
-    const size_t lds = megakernel_lds_bytes(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris, P.thin_lens, P.env_nodes ? 1u : 0u, P.pattern_dw, P.shutter, P.motion ? 1u : 0u);
-    if (plain && trace_params_are_plain(P))
+    const size_t lds = megakernel_lds_bytes(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris, P.thin_lens, P.env_nodes ? 1u : 0u, P.pattern_dw, P.shutter, P.motion ? 1u : 0u, P.mesh_motion ? 1u : 0u);
+    if (P.mesh_motion)  // (a launch with a mesh motion is never plain: trace_params_are_plain)
+        hipLaunchKernelGGL((trace_megakernel<false, true, false, true>), dim3(n_waves), dim3(64), lds, stream, P);
+    else if (plain && trace_params_are_plain(P))
         hipLaunchKernelGGL((trace_megakernel<false, true, true>), dim3(n_waves), dim3(64), lds, stream, P);
     else
         hipLaunchKernelGGL((trace_megakernel<false, true, false>), dim3(n_waves), dim3(64), lds, stream, P);
@@ -1973,8 +2020,13 @@ hipError_t launch_trace_helper(const TraceParams& P, uint32_t n_waves, bool plai
 // in, whatever the caller says, and never for a counting launch.
 hipError_t launch_trace_megakernel(const TraceParams& P, uint32_t n_waves, bool stats, bool plain, hipStream_t stream) {
     if (P.n_items == 0 || n_waves == 0) return hipSuccess;
-    const size_t lds = megakernel_lds_bytes(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris, P.thin_lens, P.env_nodes ? 1u : 0u, P.pattern_dw, P.shutter, P.motion ? 1u : 0u);
-    if (stats)
+    const size_t lds = megakernel_lds_bytes(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris, P.thin_lens, P.env_nodes ? 1u : 0u, P.pattern_dw, P.shutter, P.motion ? 1u : 0u, P.mesh_motion ? 1u : 0u);
+    if (P.mesh_motion && !P.motion) return hipErrorInvalidValue;  // (fill_trace_params gives such a launch the zero travels)
+    if (stats && P.mesh_motion)
+        hipLaunchKernelGGL((trace_megakernel<true, false, false, true>), dim3(n_waves), dim3(64), lds, stream, P);
+    else if (P.mesh_motion)
+        hipLaunchKernelGGL((trace_megakernel<false, false, false, true>), dim3(n_waves), dim3(64), lds, stream, P);
+    else if (stats)
         hipLaunchKernelGGL((trace_megakernel<true, false, false>), dim3(n_waves), dim3(64), lds, stream, P);
     else if (plain && trace_params_are_plain(P))
         hipLaunchKernelGGL((trace_megakernel<false, false, true>), dim3(n_waves), dim3(64), lds, stream, P);
@@ -1989,7 +2041,8 @@ hipError_t launch_primary_cull(const TraceParams& P, hipStream_t stream) {
     const uint32_t cull_tiles = P.tile_world > 1u ? local_tiles_of(P.n_tiles, P.tile_rank, P.tile_world) : P.n_tiles;
     if (cull_tiles == 0u) return hipSuccess;
     const size_t cull_threads = size_t(cull_tiles) * kCullLanes;
-    hipLaunchKernelGGL(primary_cull_kernel, dim3(uint32_t((cull_threads + kCullBlock - 1) / kCullBlock)), dim3(kCullBlock), 0, stream, P);
+    if (P.mesh_motion) hipLaunchKernelGGL(primary_cull_kernel<true>, dim3(uint32_t((cull_threads + kCullBlock - 1) / kCullBlock)), dim3(kCullBlock), 0, stream, P);
+    else hipLaunchKernelGGL(primary_cull_kernel<false>, dim3(uint32_t((cull_threads + kCullBlock - 1) / kCullBlock)), dim3(kCullBlock), 0, stream, P);
     if (P.tile_lists) {
         if (P.tile_lists_wide) hipLaunchKernelGGL(tile_lists_kernel<256>, dim3(1), dim3(256), 0, stream, P);
         else hipLaunchKernelGGL(tile_lists_kernel<64>, dim3(1), dim3(64), 0, stream, P);

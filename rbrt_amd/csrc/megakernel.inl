@@ -112,6 +112,29 @@ __device__ __forceinline__ uint32_t next_gated_mesh(const SceneLds& sc, uint32_t
     }
     return m;
 }
+// ... in a launch with a mesh motion ("Moving meshes"): the gate of mesh m reads o_m = mesh_origin_at(o, w_m, s), o the WORLD
+// origin of the ray and s the path's time. `beyond` is made per mesh from o_m: `closest` is a distance along the ray, which is
+// the same number for (o, d) and (o_m, d) -- a translation changes no parameter t --, and a mesh hit's dist = length(o_m - (o_m
+// + t d)) is t up to the rounding of o_m + t d and of the length, a few ulp of |o_m|_inf + t. A box the ray from o_m enters
+// only beyond closest * 1.001 + 0.001 (1 + |o_m|_inf) therefore holds no triangle whose dist could be < closest: the bound
+// made for the world ray holds with o_m in place of o, term for term (its absolute part scales with the origin the mesh test
+// itself reads, which is what the roundings scale with).
+template <bool STATS>
+__device__ __forceinline__ uint32_t next_gated_mesh_moving(const SceneLds& sc, uint32_t n_meshes, uint32_t m0, V3 o, V3 d,
+                                                           float closest, LocalCounters& lc, const float* mesh_travels, float s) {
+    uint32_t m = m0;
+    for (; m < n_meshes; ++m) {
+        const float* md = reinterpret_cast<const float*>(sc.mesh + m * kMeshDw);
+        const V3 om = mesh_origin_at(o, mesh_travels + m * kMeshMotionDw, s);
+        const float beyond =
+            closest * 1.001f + 0.001f * (1.0f + __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(om.x), __builtin_fabsf(om.y)), __builtin_fabsf(om.z)));
+        if (bbox_gate_fast(md + MD_BBOX_LO, md + MD_BBOX_HI, om, d, beyond)) {
+            if (STATS) ++lc.gate;
+            break;
+        }
+    }
+    return m;
+}
 
 // What has to happen next to a path whose closest hit is known. An emitter's device kind is kDevMatEmissive, which this
 // maps to ST_TERM: its path ends here, at any depth, without a scatter.
@@ -272,10 +295,13 @@ struct TraceView {
 
 // Four builds: the product's two (general, and PLAIN: TraceView), the counting build (STATS: diagnostics into DevCounters,
 // always general) and the helper builds (HELPER: extra waves for a launch that is already running, api.cpp "Elastic
-// launches"; the build of the launch they join).
-template <bool STATS, bool HELPER = false, bool PLAIN = false>
+// launches"; the build of the launch they join). Each general build exists a second time for launches with a mesh motion
+// (MM, "Moving meshes": chosen where PLAIN is chosen, by TraceParams::mesh_motion): the mesh test reads a per-mesh origin
+// there, and every launch without a mesh motion runs code in which none of that exists.
+template <bool STATS, bool HELPER = false, bool PLAIN = false, bool MM = false>
 __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(const TraceParams P) {
     static_assert(!(STATS && PLAIN), "the counting build is general");
+    static_assert(!(MM && PLAIN), "a launch with a mesh motion is general");
     const TraceView<PLAIN> K = {P};
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     constexpr uint32_t kPoolPad = (uint32_t(kPool) + 63u) & ~63u;  // census loops run in groups of 64 slots
@@ -301,7 +327,7 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
     // (the accumulators sit at the very end of the workgroup's LDS: megakernel_lds_bytes adds room for them)
     // (u32: a wave spends at most a few million cycles in a region per launch; 76 bytes fit the slack of the product's
     // allocation granule, so this build keeps the product's 16 workgroups per CU)
-    uint32_t* const rt_acc = lds + (megakernel_lds_dwords(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris, P.thin_lens, P.env_nodes ? 1u : 0u, P.pattern_dw, P.shutter, P.motion ? 1u : 0u) - uint32_t(kNumRegions));
+    uint32_t* const rt_acc = lds + (megakernel_lds_dwords(P.stack_entries, P.n_spheres, P.n_meshes, P.n_elem_tris, P.thin_lens, P.env_nodes ? 1u : 0u, P.pattern_dw, P.shutter, P.motion ? 1u : 0u, P.mesh_motion ? 1u : 0u) - uint32_t(kNumRegions));
     if (lane < uint32_t(kNumRegions)) rt_acc[lane] = 0u;
     unsigned long long rt_prev = __builtin_amdgcn_s_memtime();
     const unsigned long long rt_wall0 = __builtin_amdgcn_s_memrealtime();  // 100 MHz, the same clock on every CU
@@ -382,6 +408,10 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
             const uint32_t* gmv = reinterpret_cast<const uint32_t*>(P.motion);
             for (uint32_t i = lane; i < P.n_spheres * kMotionDw; i += 64) md[i] = gmv[i];
             if (lane == 0) md[P.n_spheres * kMotionDw] = __float_as_uint(P.motion_phase);  // ... and the phase behind them ("Animation")
+            if (MM) {  // ... and the meshes' travels behind the phase, in a launch with a mesh motion only ("Moving meshes")
+                const uint32_t* gmm = reinterpret_cast<const uint32_t*>(P.mesh_motion);
+                for (uint32_t i = lane; i < P.n_meshes * kMeshMotionDw; i += 64) md[P.n_spheres * kMotionDw + 1u + i] = gmm[i];
+            }
         }
         if (lane == 0) {
             float* gf = reinterpret_cast<float*>(dst);
@@ -497,6 +527,24 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
     auto id_mesh = [&]() { return K.mesh_index((t_ids >> 8) & 255u); };
     auto id_owner = [&]() { return (t_ids >> 16) & 63u; };
     auto id_given = [&]() { return t_ids >> 22; };
+    // Moving meshes (MM builds only; rbrt_hip.h "Moving meshes"). The meshes' travels sit in LDS behind the spheres' travels and
+    // the phase (staged above); a parked path's world origin is in the pool and its time s in gtime. A traversal lane keeps
+    // o_m = mesh_origin_at(o, w_m, s) of the mesh it walks in t_o: no register is added, and everything mesh.rs does with the
+    // ray -- make_cull, the triangle tests, p and dist of the finalise step -- reads it from there.
+    auto mesh_travels = [&]() -> const float* {
+        const uint32_t fl = uint32_t(__builtin_amdgcn_readfirstlane(int(gp[G_FLAGS])));
+        return gpf + (fl >> 8) + ((fl & 4u) ? kLensDw : 0u) + ((fl & 8u) ? kEnvDw : 0u) + ((fl & 16u) ? kShutterDw : 0u) + P.n_spheres * kMotionDw + 1u;
+    };
+    auto pool_origin = [&](uint32_t slot) {
+        return mk(__uint_as_float(POOL(F_OX, slot)), __uint_as_float(POOL(F_OY, slot)), __uint_as_float(POOL(F_OZ, slot)));
+    };
+    // dist of the hit a path in `slot` holds on mesh `em`, an EARLIER mesh of the ray being searched: the rule's own
+    // expression, from that mesh's origin and the stored t -- the bits the finalise step compared when it took the hit
+    auto earlier_mesh_dist = [&](uint32_t slot, uint32_t em) {
+        const V3 oe = mesh_origin_at(pool_origin(slot), mesh_travels() + em * kMeshMotionDw, gtime[slot]);
+        const V3 pc = oe + __uint_as_float(POOL(F_T, slot)) * t_d;
+        return length(oe - pc);
+    };
 
     for (;;) {
         RBRT_MARK(finalise);
@@ -510,9 +558,11 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                 if (obj >= 0) {                   // dist_from_ray_orig of the closest hit so far
                     if (K.hit_is_element(obj, n_elem)) {
                         closest = __uint_as_float(POOL(F_TRI, slot));  // an element (sphere / triangle): stored by the pass that found it
-                    } else {                      // an earlier mesh of this ray: recomputed as it was computed
+                    } else if (!MM) {             // an earlier mesh of this ray: recomputed as it was computed
                         const V3 pc = t_o + __uint_as_float(POOL(F_T, slot)) * t_d;
                         closest = length(t_o - pc);
+                    } else {                      // ... which, with a mesh motion, was from THAT mesh's origin
+                        closest = earlier_mesh_dist(slot, uint32_t(obj) - n_elem);
                     }
                 }
                 if (t_best > eps && t_best < 100000.0f && t_best_idx != 0xFFFFFFFFu) {  // triangle.rs:405
@@ -528,7 +578,9 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                         }
                     }
                 }
-                const uint32_t m2 = next_gated_mesh<STATS>(sc, K.n_meshes(), t_mesh + 1u, t_o, t_d, closest, lc);
+                // (with a mesh motion t_o is mesh t_mesh's origin: the next mesh's gate starts from the path's own, in the pool)
+                const uint32_t m2 = MM ? next_gated_mesh_moving<STATS>(sc, K.n_meshes(), t_mesh + 1u, pool_origin(slot), t_d, closest, lc, mesh_travels(), gtime[slot])
+                                       : next_gated_mesh<STATS>(sc, K.n_meshes(), t_mesh + 1u, t_o, t_d, closest, lc);
                 const uint32_t depth = meta & 127u;
                 POOL(F_META, slot) = pack_meta(depth, (meta >> 7) & 127u, obj, m2 < K.n_meshes() ? m2 : 0u);
                 status[slot] = m2 < K.n_meshes() ? ST_TRAV : classify(sc, obj, depth);
@@ -581,6 +633,7 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                              __uint_as_float(POOL(F_DZ, slot)));
                     const uint32_t r_meta = POOL(F_META, slot);
                     const uint32_t t_mesh = K.mesh_index((r_meta >> 22) & 255u);
+                    if (MM) t_o = mesh_origin_at(t_o, mesh_travels() + t_mesh * kMeshMotionDw, gtime[slot]);  // o_m: "Moving meshes"
                     t_ids = slot | (t_mesh << 8) | (lane << 16);
                     const uint32_t* md = sc.mesh + t_mesh * kMeshDw;
                     t_nodes = lds_ptr<BvhNode4>(md + MD_NODES);
@@ -594,13 +647,21 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                     // relaxed by 1e-3 relative and 1e-3 (1 + max |o|) absolute, so a triangle beyond it is certain
                     // to fail the exact `dist < closest` that the finalise step still applies to whatever is found.
                     // Index 0xFFFFFFFF (no triangle has it) marks "nothing found below the bound".
+                    // With a mesh motion t_o is o_m, and so is omax: the finalise step's dist is length(o_m - (o_m + t d)), whose
+                    // roundings are a few ulp of |o_m|_inf + t -- the origin the bound is relaxed by is the one the distance is
+                    // made from, so the relaxation covers the exact `dist < closest` as before. `ref` must be a DISTANCE for that:
+                    // a sphere's is (world space, the number dist is compared with); an earlier mesh's t equals its dist only to
+                    // a few ulp of ITS origin, which may lie far from o_m, so an MM build takes that mesh's dist itself, recomputed
+                    // as the finalise step will (earlier_mesh_dist).
                     {
                         const int32_t r_obj = int32_t((r_meta >> 14) & 255u) - 1;
                         if (r_obj >= 0) {  // (a sphere: F_TRI is its distance; an earlier mesh: F_T is its t, equal to
                                            // its distance to the same few ulps)
                             const float omax = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(t_o.x), __builtin_fabsf(t_o.y)),
                                                                __builtin_fabsf(t_o.z));
-                            const float ref = __uint_as_float(K.hit_is_element(r_obj, n_elem) ? POOL(F_TRI, slot) : POOL(F_T, slot));
+                            const float ref = MM && !K.hit_is_element(r_obj, n_elem)
+                                                  ? earlier_mesh_dist(slot, uint32_t(r_obj) - n_elem)
+                                                  : __uint_as_float(K.hit_is_element(r_obj, n_elem) ? POOL(F_TRI, slot) : POOL(F_T, slot));
                             const float bound = ref * 1.001f + 0.001f * (1.0f + omax);
                             if (bound < 100000.0f) t_best = bound, t_best_idx = 0xFFFFFFFFu;
                         }
@@ -1092,7 +1153,10 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                     if (desc >> 31) n = mk(sc.tri + (desc & 0x7FFFFFFFu) * kTriDw + 9);  // triangle.rs:432: the stored normal
                     else n = p - (motion ? sphere_centre_at(sc.sph + desc * kSphDw, mtr + desc * kMotionDw, mt) : mk(sc.sph + desc * kSphDw));  // sphere.rs:56, unnormalised
                 } else {  // the stored face normal (mesh.rs:253-257), or a smooth mesh's shading normal
-                    n = mesh_shading_normal(lds_ptr<Normal4>(sc.mesh + K.mesh_index(uint32_t(s_obj) - n_elem) * kMeshDw + MD_NORMALS), s_tri, o, d);
+                    // (a smooth mesh's barycentrics are those of the test that made the hit: from o_m with a mesh motion)
+                    const uint32_t hm = K.mesh_index(uint32_t(s_obj) - n_elem);
+                    n = mesh_shading_normal(lds_ptr<Normal4>(sc.mesh + hm * kMeshDw + MD_NORMALS), s_tri,
+                                            MM ? mesh_origin_at(o, mesh_travels() + hm * kMeshMotionDw, mt) : o, d);
                 }
                 DevMaterial m;
                 {
@@ -1196,7 +1260,8 @@ __global__ __launch_bounds__(64, RBRT_MK_WAVES_PER_SIMD) void trace_megakernel(c
                     }
                 }
                 RBRT_MARK(gate);
-                gated = next_gated_mesh<STATS>(sc, K.n_meshes(), 0, o, d, closest, lc);
+                gated = MM ? next_gated_mesh_moving<STATS>(sc, K.n_meshes(), 0, o, d, closest, lc, mesh_travels(), mt)
+                           : next_gated_mesh<STATS>(sc, K.n_meshes(), 0, o, d, closest, lc);
                 next = gated < K.n_meshes() ? uint32_t(ST_TRAV) : classify(sc, s_obj, depth);
             }
             // stay in registers? only sphere hits that need shading, while enough lanes do (or the wave

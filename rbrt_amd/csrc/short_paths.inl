@@ -78,6 +78,7 @@ __device__ __forceinline__ V3 short_end_colour(const TraceParams& P, const Scene
 
 // One sample of a tile of the stage, pixel (row, col) inside the image: true if it is finished here (its colour stored at
 // sample_buf[item]), false if it is the trace kernel's. `word`: the tile's culling word; s: the sample within the launch.
+template <bool MM>
 __device__ __forceinline__ bool short_path_sample(const TraceParams& P, const SceneLds& sc, const float* lens, uint32_t n_elem, uint32_t word,
                                                   uint32_t row, uint32_t col, uint32_t s, uint32_t item) {
     const uint32_t img_w = P.cam.img_width_pix, img_h = P.cam.img_height_pix;
@@ -129,7 +130,10 @@ __device__ __forceinline__ bool short_path_sample(const TraceParams& P, const Sc
             depth -= 1u;
             short_closest_element(P, sc, n_elem, 0u, o, d, mt, closest, ht, obj);
             LocalCounters lc = {0, 0, 0, 0, 0};
-            const uint32_t gated = next_gated_mesh<false>(sc, P.n_meshes, 0u, o, d, closest, lc);
+            // (with a mesh motion the gate of mesh m reads o_m at the sample's time: "Moving meshes"; the camera ray went on
+            // trusting the tile pass's mesh bits, which hold for every time of the exposure)
+            const uint32_t gated = MM ? next_gated_mesh_moving<false>(sc, P.n_meshes, 0u, o, d, closest, lc, P.mesh_motion, mt)
+                                                 : next_gated_mesh<false>(sc, P.n_meshes, 0u, o, d, closest, lc);
             next = gated < P.n_meshes ? uint32_t(ST_TRAV) : classify(sc, obj, depth);
             if (next == ST_TERM) color = short_end_colour(P, sc, obj, d);
             else finished = false;
@@ -147,6 +151,8 @@ __device__ __forceinline__ bool short_path_sample(const TraceParams& P, const Sc
     return finished;
 }
 
+// (MM: the build for a launch with a mesh motion; every other launch runs the code it always has)
+template <bool MM>
 __global__ __launch_bounds__(kShortBlock) void short_paths_kernel(const TraceParams P) {
     const uint32_t lane = threadIdx.x;
     const uint32_t n_work = uint32_t(__builtin_amdgcn_readfirstlane(int(P.tile_lists[0])));
@@ -181,7 +187,7 @@ __global__ __launch_bounds__(kShortBlock) void short_paths_kernel(const TracePar
                 break;
             }
             // (a slot beyond a ragged edge: nothing to write, nothing to hand out)
-            const bool finished = !(row < img_h && col < img_w) || short_path_sample(P, sc, lens, n_elem, word, row, col, s, s * npix + widx * 64u + lane);
+            const bool finished = !(row < img_h && col < img_w) || short_path_sample<MM>(P, sc, lens, n_elem, word, row, col, s, s * npix + widx * 64u + lane);
             const uint64_t mask = __builtin_amdgcn_ballot_w64(finished);
             if (s < kShortProbe) probe_finished += uint32_t(__popcll(mask));
             if (lane == 0) masks[s] = mask;
@@ -194,6 +200,7 @@ __global__ __launch_bounds__(kShortBlock) void short_paths_kernel(const TracePar
 // P.short_masks are those of the trace launch that follows on the same stream.
 hipError_t launch_short_paths(const TraceParams& P, uint32_t n_waves, hipStream_t stream) {
     if (P.n_items == 0 || n_waves == 0 || !P.short_masks || !P.tile_cull || !P.tile_lists) return hipSuccess;
-    hipLaunchKernelGGL(short_paths_kernel, dim3(n_waves), dim3(kShortBlock), 0, stream, P);
+    if (P.mesh_motion) hipLaunchKernelGGL(short_paths_kernel<true>, dim3(n_waves), dim3(kShortBlock), 0, stream, P);
+    else hipLaunchKernelGGL(short_paths_kernel<false>, dim3(n_waves), dim3(kShortBlock), 0, stream, P);
     return hipGetLastError();
 }

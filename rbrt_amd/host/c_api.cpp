@@ -70,6 +70,7 @@ struct rbrt_host_scene {
     bool shutter = false;
     float travel[3] = {0.0f, 0.0f, 0.0f};
     std::vector<float> motion;  // Scene::motion_travels
+    std::vector<float> mesh_motion;  // Scene::mesh_motion_travels
 };
 
 extern "C" {
@@ -89,6 +90,7 @@ int rbrt_host_scene_load(const char* yaml_path, uint32_t height, uint32_t width,
         h->lens_abi = h->cam.to_abi_lens();
         if (const auto& tr = bp.camera_blueprint.camera_shutter_travel) h->shutter = true, h->travel[0] = tr->x, h->travel[1] = tr->y, h->travel[2] = tr->z;
         h->motion = h->scene.motion_travels();
+        h->mesh_motion = h->scene.mesh_motion_travels();
         *out = h;
         return 0;
     } catch (const std::exception& e) {
@@ -104,6 +106,9 @@ const float* rbrt_host_scene_shutter_travel(const rbrt_host_scene* h) { return h
 // The spheres' shutter_travel keys as rbrt_motion_t::travel takes them, [n_spheres][3] with zeros for the spheres without one, or
 // NULL when no sphere has the key (no motion).
 const float* rbrt_host_scene_motion(const rbrt_host_scene* h) { return h->motion.empty() ? nullptr : h->motion.data(); }
+// The meshes' shutter_travel keys as rbrt_mesh_motion_t::travel takes them, [n_meshes][3] with zeros for the meshes without one,
+// or NULL when no mesh has the key (no mesh motion).
+const float* rbrt_host_scene_mesh_motion(const rbrt_host_scene* h) { return h->mesh_motion.empty() ? nullptr : h->mesh_motion.data(); }
 const rbrt_scene_t* rbrt_host_scene_scene(const rbrt_host_scene* h) { return &h->view.scene; }
 // The corner normals of the smooth meshes (YAML `shading: smooth`), or NULL when every mesh is flat.
 const rbrt_scene_shading_t* rbrt_host_scene_shading(const rbrt_host_scene* h) { return h->view.shading_ptr(); }
@@ -178,6 +183,9 @@ uint64_t rbrt_host_environment_fingerprint(const float* nodes, uint32_t n, uint6
 uint64_t rbrt_host_shutter_fingerprint(const float* travel, uint64_t h) { return rbrt::shutter_fingerprint(travel, h); }
 // What a motion adds to it (travels NULL: none, h itself).
 uint64_t rbrt_host_motion_fingerprint(const float* travels, uint32_t n_spheres, uint64_t h) { return rbrt::motion_fingerprint(travels, n_spheres, h); }
+
+// What a mesh motion adds to it (travels NULL: none, h itself).
+uint64_t rbrt_host_mesh_motion_fingerprint(const float* travels, uint32_t n_meshes, uint64_t h) { return rbrt::mesh_motion_fingerprint(travels, n_meshes, h); }
 
 int rbrt_host_write_png(const char* path, const uint8_t* rgb, uint32_t width, uint32_t height) {
     try {

@@ -65,7 +65,7 @@ uint64_t patterns_fingerprint(const rbrt_scene_patterns_t* pt, uint64_t h) {
 
 uint64_t checkpoint_fingerprint(const std::string& path, const rbrt_camera_lens_t& lens, const rbrt_render_opts_t& opts, const rbrt_scene_t& sc,
                                 const rbrt_scene_shading_t* sh, const Environment& env, const rbrt_scene_patterns_t* pt, const float* travel,
-                                const std::vector<float>* motion, float motion_step) {
+                                const std::vector<float>* motion, float motion_step, const std::vector<float>* mesh_motion) {
     if (path.empty()) return 0;
     uint64_t h = patterns_fingerprint(pt, shading_fingerprint(sc, sh, scene_fingerprint(lens.cam, sc)));
     if (opts.flags & RBRT_FLAG_CONSTANT_BACKGROUND) {
@@ -82,9 +82,11 @@ uint64_t checkpoint_fingerprint(const std::string& path, const rbrt_camera_lens_
         h = fnv1a(&lens.focus_scale, sizeof(lens.focus_scale), h);
     }
     h = shutter_fingerprint(travel, h);
-    if (!motion || motion->empty()) return h;
-    h = motion_fingerprint(motion->data(), uint32_t(motion->size() / 3u), h);
-    if (motion_step != 0.0f) {  // (the spheres advance between frames: other sums)
+    const bool spheres_move = motion && !motion->empty(), meshes_move = mesh_motion && !mesh_motion->empty();
+    if (!spheres_move && !meshes_move) return h;
+    if (spheres_move) h = motion_fingerprint(motion->data(), uint32_t(motion->size() / 3u), h);
+    if (meshes_move) h = mesh_motion_fingerprint(mesh_motion->data(), uint32_t(mesh_motion->size() / 3u), h);
+    if (motion_step != 0.0f) {  // (the spheres and meshes advance between frames: other sums)
         const char tag[8] = {'m', 's', 't', 'e', 'p', 0, 0, 0};
         h = fnv1a(&motion_step, sizeof(motion_step), fnv1a(tag, sizeof(tag), h));
     }
@@ -97,6 +99,14 @@ uint64_t motion_fingerprint(const float* travels, uint32_t n_spheres, uint64_t h
     h = fnv1a(tag, sizeof(tag), h);
     h = fnv1a(&n_spheres, sizeof(n_spheres), h);
     return fnv1a(travels, size_t(n_spheres) * 3u * sizeof(float), h);
+}
+
+uint64_t mesh_motion_fingerprint(const float* travels, uint32_t n_meshes, uint64_t h) {
+    if (!travels) return h;
+    const char tag[8] = {'m', 'e', 's', 'h', 'm', 'o', 't', 0};
+    h = fnv1a(tag, sizeof(tag), h);
+    h = fnv1a(&n_meshes, sizeof(n_meshes), h);
+    return fnv1a(travels, size_t(n_meshes) * 3u * sizeof(float), h);
 }
 
 uint64_t shutter_fingerprint(const float* travel, uint64_t h) {

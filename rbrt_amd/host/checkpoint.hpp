@@ -28,13 +28,17 @@ CheckpointHeader checkpoint_header(uint32_t width, uint32_t height, uint32_t spp
 // checkpoint to match.
 uint64_t checkpoint_fingerprint(const std::string& path, const rbrt_camera_lens_t& lens, const rbrt_render_opts_t& opts, const rbrt_scene_t& sc,
                                 const rbrt_scene_shading_t* sh, const Environment& env, const rbrt_scene_patterns_t* pt = nullptr,
-                                const float* travel = nullptr, const std::vector<float>* motion = nullptr, float motion_step = 0.0f);
+                                const float* travel = nullptr, const std::vector<float>* motion = nullptr, float motion_step = 0.0f,
+                                const std::vector<float>* mesh_motion = nullptr);
 // The shutter's part of it: h itself without a shutter (travel null), else h continued over a tag and the three floats -- a
 // zero travel included, whose draw makes its sums another render's.
 uint64_t shutter_fingerprint(const float* travel, uint64_t h);
 // The motion's part of it (Scene::motion_travels; `motion` null or empty: none, h itself): h continued over a tag, the number of
 // spheres and their travels -- an all-zero motion included, whose draw makes its sums another render's.
 uint64_t motion_fingerprint(const float* travels, uint32_t n_spheres, uint64_t h);
+// The mesh motion's part of it (Scene::mesh_motion_travels; null: none, h itself): h continued over a tag, the number of meshes
+// and their travels. Only a scene one of whose meshes has the key comes here, so every other fingerprint keeps its bytes.
+uint64_t mesh_motion_fingerprint(const float* travels, uint32_t n_meshes, uint64_t h);
 
 struct CheckpointRead {
     bool found = false;         // the file is there and as long as a header

@@ -110,6 +110,10 @@ struct TriangleMeshBlueprint {
     std::optional<float> material_param;
     bool smooth = false;  // `shading: smooth` (not in the reference): shade with corner normals, rbrt_scene_shading_t
     std::optional<Checker> checker;
+    // `shutter_travel: [dx, dy, dz]` (not in the reference): the mesh's translation while the shutter is open, in scene units
+    // (include/rbrt_hip.h "Moving meshes"); absent: the mesh stays -- and a scene none of whose meshes has the key has no mesh
+    // motion at all
+    std::optional<Vec3> shutter_travel;
 };
 struct SphereBlueprint {
     float radius = 0;
@@ -179,6 +183,7 @@ struct TriangleMesh {
     Material material;
     uint32_t num_triangles = 0;  // before padding
     std::optional<Checker> checker;  // lambertian only
+    std::optional<Vec3> shutter_travel;  // the YAML's shutter_travel: absent, the mesh stays
     // Smooth shading (not in the reference): corner_normals[k][c] = component c of corner k's normal of every SoA entry
     // (padding entries copy entry 0's, as the other arrays do); all empty = a flat mesh.
     std::vector<float> corner_normals[3][3];
@@ -267,6 +272,9 @@ struct Scene {
     // The scene's motion (rbrt_motion_t::travel): [elements.size()][3], zeros for the spheres without a shutter_travel; EMPTY
     // when no sphere has one (no motion: no draw is made for it). A key with a zero vector counts: its scene has a motion.
     std::vector<float> motion_travels() const;
+    // The scene's mesh motion (rbrt_mesh_motion_t::travel): [triangle_meshes.size()][3], zeros for the meshes without a
+    // shutter_travel; EMPTY when no mesh has one (no mesh motion). A key with a zero vector counts.
+    std::vector<float> mesh_motion_travels() const;
 };
 Scene create_scene_from_scene_blueprint(const SceneBlueprint& bp);
 // Where create_scene_from_scene_blueprint spent its time, summed over the meshes of the calling thread's scenes (--report).
@@ -285,7 +293,7 @@ struct ImageBuffer {
     std::vector<uint8_t> noisy_rgb;  // a denoised render with RenderConfig::keep_noisy: the unfiltered image, like rgb (else empty)
     // a render with RenderConfig::features: the feature buffers of the primary rays, row-major (else empty)
     std::vector<float> feature_albedo, feature_normal;  // 3 floats per pixel
-    std::vector<float> feature_motion;                  // 3 floats per pixel; empty unless the scene has a motion (PREFIX.motion.pfm)
+    std::vector<float> feature_motion;                  // 3 floats per pixel; empty unless the scene has a motion, of spheres or meshes (PREFIX.motion.pfm)
     std::vector<float> feature_depth, feature_coverage; // 1 float per pixel
     std::vector<uint8_t> history_map;  // a render with RenderConfig::frames: one byte per pixel, the last frame's len * 255 / max_history (else empty)
     std::vector<uint8_t> spike_map;  // a render with RenderConfig::despike: one byte per traced pixel of the last frame, 0 none, 85 A, 170 B, 255 both (else empty)

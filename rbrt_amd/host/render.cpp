@@ -429,6 +429,8 @@ struct Job {
     CheckpointRead resume;
     ImageBuffer& img;
     std::vector<float> motion;  // Scene::motion_travels, empty without one or with RenderConfig::no_motion: every rank's handle gets it
+    std::vector<float> mesh_motion;  // Scene::mesh_motion_travels, likewise
+    bool moves() const { return !motion.empty() || !mesh_motion.empty(); }
     size_t n() const { return size_t(img.width) * img.height * 3; }  // values of the complete image
     size_t rank_pixels(int rank) const {  // the pixels a rank renders: its packed tiles, or the image as it is
         return plan.world > 1 ? rbrt_hip_packed_pixels(img.width, img.height, uint32_t(rank), uint32_t(plan.world)) : size_t(img.width) * img.height;
@@ -549,8 +551,8 @@ struct Rank {
     // the motion buffer (rbrt_hip_render_features_motion), 3 floats a pixel: on a scene with a motion, where --features writes it
     // or the frames' accumulation follows the spheres
     DeviceBuffer d_motion;
-    bool animated() const { return !job.motion.empty() && cfg.frames && cfg.motion_step != 0.0f; }
-    bool want_motion() const { return !job.motion.empty() && (cfg.features || animated()); }
+    bool animated() const { return job.moves() && cfg.frames && cfg.motion_step != 0.0f; }
+    bool want_motion() const { return job.moves() && (cfg.features || animated()); }
     DeviceBuffer d_features;  // a render with feature buffers: albedo, normal, depth, coverage (3 + 3 + 1 + 1 floats a pixel)
     DeviceBuffer d_noisy;  // a denoised, glared or transformed render that keeps the unfiltered image: that image's radiance
 };
@@ -600,6 +602,11 @@ void Rank::setup() {
         rbrt_motion_t mo{};
         mo.n_spheres = uint32_t(job.motion.size() / 3u), mo.travel = job.motion.data();
         err.lib_ok(rbrt_hip_scene_set_motion(hs, &mo));
+    }
+    if (!job.mesh_motion.empty()) {  // (and the meshes', on the same draw)
+        rbrt_mesh_motion_t mm{};
+        mm.n_meshes = uint32_t(job.mesh_motion.size() / 3u), mm.travel = job.mesh_motion.data();
+        err.lib_ok(rbrt_hip_scene_set_mesh_motion(hs, &mm));
     }
     rbrt_hip_scene_info_t info;
     if (rank == 0 && rbrt_hip_scene_info(hs, &info) == RBRT_OK) {
@@ -1137,11 +1144,11 @@ ImageBuffer render_scene(const Camera& cam, uint32_t num_samples, const Scene& s
     const rbrt_environment_t env_abi = scene.environment.to_abi();
     const Plan plan = make_plan(cfg, cfg_in.adaptive ? "--adaptive" : cfg_in.upscale ? "--upscale" : cfg_in.despike ? "--despike" : cfg_in.frames ? "--frames" : cfg_in.denoise_guided ? "--denoise-guided" : "--denoise", cfg_in.adaptive,
                                 cam, scene, num_samples);
-    Job job{cfg, plan, lens, view, scene.environment.n != 0u ? &env_abi : nullptr, render_opts_of(cfg, cam, num_samples), num_samples, {}, {}, img, {}};
-    if (!cfg.no_motion) job.motion = scene.motion_travels();
+    Job job{cfg, plan, lens, view, scene.environment.n != 0u ? &env_abi : nullptr, render_opts_of(cfg, cam, num_samples), num_samples, {}, {}, img, {}, {}};
+    if (!cfg.no_motion) job.motion = scene.motion_travels(), job.mesh_motion = scene.mesh_motion_travels();
     job.want = checkpoint_header(img.width, img.height, num_samples, uint32_t(plan.world), cfg.seed,
                                  checkpoint_fingerprint(cfg.checkpoint_path, lens, job.opts, view.scene, view.shading_ptr(), scene.environment, view.patterns_ptr(),
-                                                        cfg.shutter ? cfg.shutter_travel : nullptr, &job.motion, cfg.motion_step));
+                                                        cfg.shutter ? cfg.shutter_travel : nullptr, &job.motion, cfg.motion_step, &job.mesh_motion));
     job.resume = resume_from_checkpoint(job);
     Shared sh(plan);
     bring_up_rccl(plan, sh);

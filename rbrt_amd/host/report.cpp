@@ -100,6 +100,15 @@ void write_report(const CliOptions& o, const rbrt::RenderConfig& cfg, const rbrt
         j.raw("moving_spheres", "[" + list + "]");
         if (o.motion_step) j.num("motion_step", cfg.motion_step, "%.9g");  // the exposures they advance from one frame to the next
     }
+    if (const std::vector<float> mw = scene.mesh_motion_travels(); !mw.empty() && !cfg.no_motion) {  // ... and the meshes: index and travel
+        std::string list;
+        for (size_t i = 0; i < scene.triangle_meshes.size(); ++i)
+            if (scene.triangle_meshes[i].shutter_travel)
+                list += std::string(list.empty() ? "" : ", ") + "{\"mesh\": " + std::to_string(i) + ", \"travel\": [" + JsonLine::text(mw[3 * i], "%.9g") + ", " +
+                        JsonLine::text(mw[3 * i + 1], "%.9g") + ", " + JsonLine::text(mw[3 * i + 2], "%.9g") + "]}";
+        j.raw("moving_meshes", "[" + list + "]");
+        if (o.motion_step && scene.motion_travels().empty()) j.num("motion_step", cfg.motion_step, "%.9g");
+    }
     if (o.upscale) {  // guided upsampling: its options, the size that was traced and the stage's time on the GPU, the mean per frame (a part of render_s)
         j.num("upscale", cfg.upscale, "%.0f"), j.num("render_width", rep.render_width, "%.0f"), j.num("render_height", rep.render_height, "%.0f");
         j.num("upscale_normal", cfg.upscale_normal, "%.9g"), j.num("upscale_depth", cfg.upscale_depth, "%.9g"), j.num("upscale_albedo", cfg.upscale_albedo, "%.9g");

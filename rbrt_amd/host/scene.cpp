@@ -372,6 +372,11 @@ SceneBlueprint load_blueprints_from_yaml_text(const std::string& text) {
             b.smooth = v == "smooth";
         }
         b.checker = opt_checker(m);
+        try {
+            b.shutter_travel = opt_travel(m, "shutter_travel", "the mesh's translation during the exposure");
+        } catch (const Error& e) {  // (a message that names the mesh, as the sphere's names the sphere)
+            throw Error("mesh " + std::to_string(bp.mesh_blueprints.size()) + ": " + e.what());
+        }
         bp.mesh_blueprints.push_back(b);
     }
     for (const Node& s : as_list(need(root, "sphere_blueprints", "scene"), "sphere_blueprints")) {
@@ -762,6 +767,17 @@ Scene::AbiView Scene::to_abi() const {
     return v;
 }
 
+std::vector<float> Scene::mesh_motion_travels() const {
+    bool any = false;
+    for (const TriangleMesh& m : triangle_meshes) any = any || m.shutter_travel.has_value();
+    std::vector<float> out;
+    if (!any) return out;
+    out.assign(triangle_meshes.size() * 3u, 0.0f);
+    for (size_t i = 0; i < triangle_meshes.size(); ++i)
+        if (const auto& tr = triangle_meshes[i].shutter_travel) out[3 * i] = tr->x, out[3 * i + 1] = tr->y, out[3 * i + 2] = tr->z;
+    return out;
+}
+
 std::vector<float> Scene::motion_travels() const {
     bool any = false;
     for (const Sphere& s : elements) any = any || s.shutter_travel.has_value();
@@ -787,6 +803,17 @@ Scene create_scene_from_scene_blueprint(const SceneBlueprint& bp) {
         scene.triangle_meshes.push_back(
             TriangleMesh::create(mb.obj_filepath, mb.translation, mb.rotation_rad, mb.scale, *mat, mb.smooth));
         scene.triangle_meshes.back().checker = mb.checker;
+        if (mb.shutter_travel) {  // (what rbrt_hip_scene_set_mesh_motion would refuse, as a load error that names the mesh)
+            const TriangleMesh& tm = scene.triangle_meshes.back();
+            const float corners[6] = {tm.bbox_lower.x, tm.bbox_lower.y, tm.bbox_lower.z, tm.bbox_upper.x, tm.bbox_upper.y, tm.bbox_upper.z};
+            const float tv[3] = {mb.shutter_travel->x, mb.shutter_travel->y, mb.shutter_travel->z};
+            for (int k = 0; k < 6; ++k) {
+                const volatile float end = corners[k] + tv[k % 3];  // (float32, as the library adds it)
+                if (std::isfinite(corners[k]) && !std::isfinite(end))
+                    throw Error("shutter_travel: box + shutter_travel of mesh " + std::to_string(scene.triangle_meshes.size() - 1) + " is not finite");
+            }
+            scene.triangle_meshes.back().shutter_travel = mb.shutter_travel;
+        }
     }
     for (const SphereBlueprint& sb : bp.sphere_blueprints) {
         auto mat = create_material_from_description(sb.material_type, sb.albedo, sb.material_param);
